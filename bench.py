@@ -9,9 +9,11 @@ bare as `python bench.py --gpus N`, by this script itself (launch_ranks: N fresh
 same per-GPU batch shape on every rank (weak scaling; default B=32/GPU so the curve continues the N=1 point, `--batch 256` is
 BASELINE configs[2]), gradient exchange over RCCL per step.  Rank 0 prints ONE JSON line.
 
-Extra legs on the same line (rank 0, N=1 only for cpu_baseline):
+A plain run sets up, warms up, times the steps and prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step).
+--full adds the extra legs on the same line (rank 0, N=1 only for cpu_baseline):
   roofline     - the dominant kernel (the biLSTM recurrence), timed with HIP events on its own stream inside the timed region
-  cpu_baseline - the oracle's stock-PyTorch CPU training loop on the same shapes, bounded sample
+  cpu_baseline - the oracle's stock-PyTorch CPU training loop on the same shapes, bounded sample (--no-cpu-baseline drops it)
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -59,6 +61,92 @@ def launch_ranks(n: int) -> int:
     return rc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_EMBED_ROWS = 4096
+
+
+def dump_outputs(model, t, lengths, out_dir):
+    """What a caller of the timed path holds after its last step, as float32 DIR/<name>.npy: the six losses (loss.<name>), every
+    parameter after the optimizer step (param.<name>) and its gradient (grad.<name>).  Of embed.weight only rows the batch's tokens
+    index are written (the only rows with a gradient): all of them, or a fixed seeded sample of DUMP_EMBED_ROWS when there are more;
+    embed.weight.row_ids holds their ids (float64).  At the default shapes that is about 40 MB, never more than DUMP_LIMIT_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"loss.{k}": np.array([v], dtype=np.float32) for k, v in model.read_losses().items()}
+    model._assign_grad_views()
+    tc, lc = t.cpu(), lengths.cpu()
+    mask = torch.arange(tc.shape[0]).unsqueeze(1) < lc.unsqueeze(0)        # positions inside each sample's length
+    ids = torch.unique(tc[mask]).numpy()
+    if ids.size > DUMP_EMBED_ROWS:
+        ids = np.sort(np.random.default_rng(0).choice(ids, DUMP_EMBED_ROWS, replace=False))
+    rows = torch.from_numpy(ids).to(t.device)
+    for name, p in model.named_parameters():
+        w, g = p.detach(), p.grad
+        if name == "embed.weight":
+            arrays["embed.weight.row_ids"] = ids.astype(np.float64)
+            w, g = w[rows], g[rows]
+        arrays[f"param.{name}"] = w.float().cpu().numpy()
+        arrays[f"grad.{name}"] = g.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def roofline_legs(model, args, lengths, elapsed):
+    """(roofline, roofline_serial_chain) of the recurrent launches sampled with HIP events during the timed steps (--full)."""
+    from mmda_amd import _lib
+    lib = model._lib
+    # ---- roofline of the dominant kernel (biLSTM recurrence; 4 launches per step with equal algorithmic FLOPs)
+    ms4 = (C.c_float * 4)()
+    nst = C.c_int()
+    _lib.check(lib.mmda_misa_timing_collect(model._h, C.byref(ms4), C.byref(nst)), "timing_collect")
+    lib.mmda_misa_timing_end(model._h)
+    ms = [float(x) for x in ms4]
+    sumH2 = 300 ** 2 + 35 ** 2 + 74 ** 2
+    real_steps = float(lengths.sum().item())            # sum_b len_b (= T*B when not ragged)
+    flops_per_launch = 16.0 * real_steps * sumH2        # 2 dirs * 2 FLOP/MAC * 4H*H per (sample, step), summed over modalities
+    if args.rnncell == "gru":
+        flops_per_launch *= 0.75                        # three gate blocks (the padded fourth slot is not algorithmic work)
+    names = ["lstm_fwd_kernel(layer1)", "lstm_fwd_kernel(layer2)", "lstm_bwd_kernel(layer2)", "lstm_bwd_kernel(layer1)"]
+    k = max(range(4), key=lambda i: ms[i])
+    peak = 2500.0 if args.precision == "bf16" else 157.3
+    achieved = flops_per_launch / (ms[k] * 1e-3) / 1e12 if ms[k] > 0 else 0.0
+    # HBM bytes per launch of that kernel from the PMC counters (FETCH_SIZE + WRITE_SIZE, separate rocprofv3 passes, see
+    # profiles/): only valid for the configuration the profile was taken on, otherwise null
+    # (PMC counters cannot be read from inside the process: they come from the committed rocprofv3 passes of THIS command,
+    # tools/prof_pmc.sh -> profiles/pmc_traffic.json; FETCH_SIZE doubled: on gfx950 it counts half the bytes of wide reads)
+    traffic = mfma_busy = None
+    tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tfile):
+        try:
+            tj = json.load(open(tfile))
+            if (tj.get("batch"), tj.get("seq_len"), tj.get("precision")) == (args.batch, args.seq_len, args.precision) and not args.ragged:
+                kn = names[k].split("(")[0]
+                traffic = tj["bytes_per_launch"].get(kn)
+                mfma_busy = {"chip_percent": tj.get("mfma_util_chip_percent", {}).get(kn),
+                             "share_of_wave_cycles_percent": tj.get("mfma_busy_share_of_wave_cycles_percent", {}).get(kn),
+                             "source": tj.get("source")}
+        except Exception:
+            traffic = mfma_busy = None
+    roofline = {"bound": "mfma", "kernel": names[k], "achieved": round(achieved, 3), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 6), "traffic": traffic, "launch_ms": round(ms[k], 4),
+                "all_launch_ms": {n: round(m, 4) for n, m in zip(names, ms)},
+                "recurrent_share_of_step": round(sum(ms) / (elapsed / args.steps * 1e3), 3), "timed_steps": nst.value,
+                "mfma_busy": mfma_busy}
+    # What actually bounds that kernel: neither MFMA nor HBM but the chain of T dependent cross-CU hand-offs (h_t needs every hidden
+    # tile of h_{t-1}).  Its floor is the MI355X's one-to-one hand-off price (0.8 - 1.0 us per hop on an idle chip); frac = T x floor
+    # / launch time.
+    hop_floor_us = 0.9
+    chain_steps = int(lengths.max().item())
+    roofline_chain = {"bound": "serial_chain", "kernel": names[k], "steps": chain_steps, "floor_us_per_step": hop_floor_us,
+                      "achieved_us_per_step": round(ms[k] * 1e3 / max(chain_steps, 1), 3),
+                      "frac": round(chain_steps * hop_floor_us / (ms[k] * 1e3), 4) if ms[k] > 0 else 0.0,
+                      "all_us_per_step": {n: round(m * 1e3 / max(chain_steps, 1), 3) for n, m in zip(names, ms)}}
+    return roofline, roofline_chain
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -73,7 +161,10 @@ def main():
     ap.add_argument("--rnncell", default="lstm", choices=["lstm", "gru"], help="config.rnncell (the headline config is lstm)")
     ap.add_argument("--fp8-fusion", type=int, default=0, help="BASELINE configs[4]: the fusion layer's feed-forward products on block-scaled fp8 (forward)")
     ap.add_argument("--global-stats", type=int, default=0, help="N > 1: DiffLoss / CMD / conf on the batch of all ranks (config.dp_global_stats; the headline runs keep DDP semantics)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline: per-kernel HIP-event timing of the "
+                                                         "recurrences (roofline) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--streaming-recurrence", action="store_true", help="bf16: stream W_hh from L2 per step instead of LDS-resident")
     ap.add_argument("--cpu-steps", type=int, default=0, help="0 = pick a count that takes ~10-30 s")
     ap.add_argument("--launch-check", action="store_true", help="every rank prints its rendezvous environment and exits (no GPU call): tests the launcher")
@@ -140,7 +231,7 @@ def main():
     for _ in range(args.warmup):
         step()
     lib = model._lib
-    if rank == 0 and not os.environ.get("MMDA_BENCH_NO_KERNEL_TIMING"):
+    if rank == 0 and args.full and not os.environ.get("MMDA_BENCH_NO_KERNEL_TIMING"):
         # HIP events around the four recurrent launches of every 8th timed step (25 samples at the default 200 steps): the eight
         # event records cost ~35 us per step, which the metric should not carry on every step.  A short run (the driver's 20 steps)
         # samples four of its steps, never every one.
@@ -170,56 +261,11 @@ def main():
             torch.distributed.destroy_process_group()
         return
 
-    if os.environ.get("MMDA_BENCH_NO_KERNEL_TIMING"):        # diagnostic: the step rate without the per-kernel HIP events
+    if args.dump_outputs:
+        dump_outputs(model, t, lengths, args.dump_outputs)
+    if args.full and os.environ.get("MMDA_BENCH_NO_KERNEL_TIMING"):        # diagnostic: the step rate without the per-kernel HIP events
         print(json.dumps({"ms_per_step_without_kernel_events": round(1e3 * elapsed / args.steps, 4)}))
         return
-    # ---- roofline of the dominant kernel (biLSTM recurrence; 4 launches per step with equal algorithmic FLOPs)
-    ms4 = (C.c_float * 4)()
-    nst = C.c_int()
-    _lib.check(lib.mmda_misa_timing_collect(model._h, C.byref(ms4), C.byref(nst)), "timing_collect")
-    lib.mmda_misa_timing_end(model._h)
-    ms = [float(x) for x in ms4]
-    sumH2 = 300 ** 2 + 35 ** 2 + 74 ** 2
-    real_steps = float(lengths.sum().item())            # sum_b len_b (= T*B when not ragged)
-    flops_per_launch = 16.0 * real_steps * sumH2        # 2 dirs * 2 FLOP/MAC * 4H*H per (sample, step), summed over modalities
-    if args.rnncell == "gru":
-        flops_per_launch *= 0.75                        # three gate blocks (the padded fourth slot is not algorithmic work)
-    names = ["lstm_fwd_kernel(layer1)", "lstm_fwd_kernel(layer2)", "lstm_bwd_kernel(layer2)", "lstm_bwd_kernel(layer1)"]
-    k = max(range(4), key=lambda i: ms[i])
-    peak = 2500.0 if args.precision == "bf16" else 157.3
-    achieved = flops_per_launch / (ms[k] * 1e-3) / 1e12 if ms[k] > 0 else 0.0
-    # HBM bytes per launch of that kernel from the PMC counters (FETCH_SIZE + WRITE_SIZE, separate rocprofv3 passes, see
-    # profiles/): only valid for the configuration the profile was taken on, otherwise null
-    # (PMC counters cannot be read from inside the process: they come from the committed rocprofv3 passes of THIS command,
-    # tools/prof_pmc.sh -> profiles/pmc_traffic.json; FETCH_SIZE doubled as the MI355X guide prescribes for gfx950)
-    traffic = mfma_busy = None
-    tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tfile):
-        try:
-            tj = json.load(open(tfile))
-            if (tj.get("batch"), tj.get("seq_len"), tj.get("precision")) == (args.batch, args.seq_len, args.precision) and not args.ragged:
-                kn = names[k].split("(")[0]
-                traffic = tj["bytes_per_launch"].get(kn)
-                mfma_busy = {"chip_percent": tj.get("mfma_util_chip_percent", {}).get(kn),
-                             "share_of_wave_cycles_percent": tj.get("mfma_busy_share_of_wave_cycles_percent", {}).get(kn),
-                             "source": tj.get("source")}
-        except Exception:
-            traffic = mfma_busy = None
-    roofline = {"bound": "mfma", "kernel": names[k], "achieved": round(achieved, 3), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 6), "traffic": traffic, "launch_ms": round(ms[k], 4),
-                "all_launch_ms": {n: round(m, 4) for n, m in zip(names, ms)},
-                "recurrent_share_of_step": round(sum(ms) / (elapsed / args.steps * 1e3), 3), "timed_steps": nst.value,
-                "mfma_busy": mfma_busy}
-    # What actually bounds that kernel: neither MFMA nor HBM but the chain of T dependent cross-CU hand-offs (h_t needs every hidden
-    # tile of h_{t-1}).  Its floor is the guide's handoff-1to1 price (0.8 - 1.0 us per hop on an idle chip, MI355X_MICROARCH.md
-    # price list); frac = T x floor / launch time.
-    hop_floor_us = 0.9
-    chain_steps = int(lengths.max().item())
-    roofline_chain = {"bound": "serial_chain", "kernel": names[k], "steps": chain_steps, "floor_us_per_step": hop_floor_us,
-                      "achieved_us_per_step": round(ms[k] * 1e3 / max(chain_steps, 1), 3),
-                      "frac": round(chain_steps * hop_floor_us / (ms[k] * 1e3), 4) if ms[k] > 0 else 0.0,
-                      "all_us_per_step": {n: round(m * 1e3 / max(chain_steps, 1), 3) for n, m in zip(names, ms)}}
-
     total_samples = args.batch * world * args.steps
     value = total_samples / elapsed
     out = {
@@ -234,13 +280,13 @@ def main():
                    "parallelism": f"dp{world}" if world > 1 else "single", "use_confidNet": bool(args.confidnet),
                    "rnncell": args.rnncell, "dp_global_stats": bool(args.global_stats) and world > 1},
         "gflop_per_sample": 1.184 if args.seq_len == 50 else round(3 * (7736080 * args.seq_len + 7832576) / 1e9, 3),
-        "roofline": roofline,
-        "roofline_serial_chain": roofline_chain,
-        "losses": {k_: round(v_, 5) for k_, v_ in losses.items()},
     }
+    if args.full:
+        out["roofline"], out["roofline_serial_chain"] = roofline_legs(model, args, lengths, elapsed)
+    out["losses"] = {k_: round(v_, 5) for k_, v_ in losses.items()}
 
     # ---- CPU baseline: the oracle's stock-PyTorch port of the reference loop on this box's host cores (N=1 only)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import misa_oracle as orc
         # host cores this process may actually use (cgroup/affinity share, 16 on a 1-GPU box), not the machine's count:
         # oversubscribing torch's intra-op pool makes the CPU loop orders of magnitude slower

@@ -10,6 +10,15 @@ from golden_util import SIDE, batch_of, case_names, load_case, sample_idx
 RTOL, ATOL = 2e-5, 2e-6     # fp32 torch-vs-torch; same kernels for LSTM, closed forms elsewhere
 
 
+def assert_outputs_close(got, ref, err_msg=""):
+    """Forward outputs of the oracle against the reference's.  The reference's own fp32 outputs lie up to ~1.1 x (ATOL + RTOL |x|)
+    from exact arithmetic (the oracle evaluated in float64, real_b256_t6_full's utt_t_orig), so a host whose BLAS sums in another
+    order (another CPU vendor's code path) can land twice that far from the fixture on a few elements.  Hence, as for the Adam
+    steps below: 99.9 % of the elements within (ATOL, RTOL), every element within (4 ATOL, RTOL)."""
+    np.testing.assert_allclose(got, ref, rtol=RTOL, atol=4 * ATOL, err_msg=err_msg)
+    assert (np.abs(got - ref) <= ATOL + RTOL * np.abs(ref)).mean() >= 0.999, err_msg
+
+
 @pytest.mark.parametrize("name", case_names(large=True))
 def test_oracle_forward_losses_grads(name):
     z, meta, cfg = load_case(name)
@@ -22,11 +31,11 @@ def test_oracle_forward_losses_grads(name):
     for k in batch:
         assert torch.equal(batch[k], b2[k]), f"synthetic batch generator drifted for {k}"
     o, L, G = orc.loss_and_grads(P, cfg, batch)
-    np.testing.assert_allclose(o.scores.detach().numpy(), z["out::scores"], rtol=RTOL, atol=ATOL)
+    assert_outputs_close(o.scores.detach().numpy(), z["out::scores"])
     np.testing.assert_array_equal(o.labels.detach().numpy(), z["out::labels"])
-    np.testing.assert_allclose(o.tcp.detach().numpy(), z["out::tcp"], rtol=RTOL, atol=ATOL)
+    assert_outputs_close(o.tcp.detach().numpy(), z["out::tcp"])
     for s in SIDE:
-        np.testing.assert_allclose(getattr(o, s).detach().numpy(), z["out::" + s], rtol=RTOL, atol=ATOL, err_msg=s)
+        assert_outputs_close(getattr(o, s).detach().numpy(), z["out::" + s], err_msg=s)
     if not cfg.use_cmd_sim:
         for m in "tva":
             np.testing.assert_allclose(getattr(o, f"domain_label_{m}").detach().numpy(),

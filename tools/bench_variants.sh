@@ -5,7 +5,7 @@ B=${1:-32}
 cp mmda_amd/libmmda_hip.so /tmp/base.so
 for v in /tmp/base.so build_variants/*.so; do
   cp $v mmda_amd/libmmda_hip.so
-  python bench.py --batch $B --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --batch $B --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

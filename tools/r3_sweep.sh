@@ -1,9 +1,9 @@
 # round-3 configuration sweep (same flags as DESIGN section 4's list): ms/step of every shape / mode the bench can run
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-run() { name=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > gpurun_out/sw_$name.json 2> gpurun_out/sw_$name.err; python - <<PY
+cd "$(dirname "$0")/.."; OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/sw_$name.json" 2> "$OUT/sw_$name.err"; python - <<PY
 import json
 try:
-    j=json.load(open("gpurun_out/sw_$name.json")); print("$name", j["ms_per_step"], "ms", round(j["value"]), "samples/s", j["roofline"]["all_launch_ms"])
+    j=json.load(open("$OUT/sw_$name.json")); print("$name", j["ms_per_step"], "ms", round(j["value"]), "samples/s", j["roofline"]["all_launch_ms"])
 except Exception as e:
     print("$name FAILED", e)
 PY
