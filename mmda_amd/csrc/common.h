@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/mmda_hip.h"
 
 #define WAVE 64
@@ -11,6 +12,13 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 bf16 = one 16x1
 typedef __attribute__((ext_vector_type(4))) float f32x4;     // 16x16 accumulator fragment
 
 void mmda_set_error(const char* what, hipError_t e);
+
+// Host: the environment switches of DESIGN §7a.  Callers keep the value in a function-local static, so each is read once per process.
+static inline int mmda_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline bool mmda_env_set(const char* name) { return getenv(name) != nullptr; }
 #define MMDA_CHECK_LAUNCH(name)                                   \
   do {                                                            \
     hipError_t _e = hipGetLastError();                            \

@@ -2,7 +2,6 @@
 // conversion launch in lstm.hip) and the host-side launch table.
 #pragma once
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -187,9 +186,9 @@ inline int conv_build(const mmda_convert_job* jobs, int cnt, ConvLaunch& L, int&
     const int ext_r = j.transposed ? (j.ldt > j.rows ? j.ldt : j.rows) : j.rows;
     L.tx[k] = ceil_div(ext_c, 64);
     {
-      static const int no_vec = getenv("MMDA_CONVERT_SCALAR") ? 1 : 0;      // ablation: the 2-byte-per-lane form
+      // 16-byte loads where the job allows them; the 2-byte-per-lane form takes the rest (measured slower where both apply)
       const int g = j.src_bf16 ? 8 : 4;                // elements per 16-byte load
-      bool v = !no_vec && (j.ld % g) == 0 && (j.cols % g) == 0 && j.cols >= g && ((uintptr_t)j.src & 15) == 0;
+      bool v = (j.ld % g) == 0 && (j.cols % g) == 0 && j.cols >= g && ((uintptr_t)j.src & 15) == 0;
       if (j.plain) v = v && ((uintptr_t)j.plain & 15) == 0;
       if (j.transposed) v = v && ((uintptr_t)j.transposed & 15) == 0;
       L.vec[k] = v ? 1 : 0;

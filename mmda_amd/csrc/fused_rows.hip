@@ -8,7 +8,6 @@
 #include "common.h"
 #include "rowlocal.h"
 #include "fused_rows.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -667,7 +666,7 @@ int mmda_fused_fwd_a(const FusedFwdA* a, void* stream) {
   if (!a || a->B <= 0 || a->nb <= 0 || a->nb > 2 || a->hs != 128 || a->nhead != 2 || a->ln1.n != 128) return MMDA_EINVAL;
   if (a->d_recon && (!a->orig || !a->d_orig)) return MMDA_EINVAL;
   // (the reconstruction in workgroups of its own while both roles together leave the chip half empty; MMDA_FUSED_SPLIT=0: never)
-  static const int split_on = getenv("MMDA_FUSED_SPLIT") ? atoi(getenv("MMDA_FUSED_SPLIT")) : 1;
+  static const int split_on = mmda_env_int("MMDA_FUSED_SPLIT", 1);
   FusedFwdA f = *a;
   const int nblk = ceil_div(a->B, a->nb);
   f.split_recon = (split_on && nblk <= 64) ? 1 : 0;

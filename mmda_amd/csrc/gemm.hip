@@ -5,7 +5,6 @@
 // Tile 64x64x32, 256 threads = 4 waves (2x2), each wave a 32x32 sub-tile = 2x2 MFMA 16x16 accumulators.
 #include "common.h"
 #include "splitk.h"
-#include <stdlib.h>
 #include <vector>
 
 namespace {
@@ -429,8 +428,7 @@ extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
   // large aligned bf16 GEMMs -> 128x128 tile kernel with 16-byte staging loads
   const bool aligned = ((a->lda | a->ldb | a->K) & 3) == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0 &&
                        ((a->strideA | a->strideB) & 3) == 0 && (!a->transA || (a->M & 3) == 0) && (a->transB || (a->N & 3) == 0);
-  static const bool use128 = []() { const char* e = getenv("MMDA_GEMM128"); return !(e && e[0] == '0'); }();   // A/B switch (tools/)
-  if (use128 && a->mode == MMDA_BF16 && plain_epilogue && aligned && !a->A2 && !a->gather && !a->bias_grad && a->M >= 128 && a->N >= 128) {
+  if (a->mode == MMDA_BF16 && plain_epilogue && aligned && !a->A2 && !a->gather && !a->bias_grad && a->M >= 128 && a->N >= 128) {
     const int tiles128 = ceil_div(a->N, TN) * ceil_div(a->M, TM) * a->batch;
     int sk = 1;
     if (nk >= 8 && tiles128 <= 256) {

@@ -12,7 +12,6 @@
 #include "convert_tile.h"
 #include "splitk.h"
 #include <algorithm>
-#include <stdlib.h>
 #include <vector>
 
 namespace {
@@ -761,32 +760,28 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
   // Three kernel classes.  0: 64 x 64 register-staged (small / unaligned problems), 1: 128 x 128 register-staged, 2: 128 x 128
   // LDS-DMA pipelined (gemm_bf16_dma_kernel).  Class 2 takes every problem whose operands can be moved by 16-byte LDS-DMA (nt: always
   // -- rows are 16-byte aligned by contract; tn: leading dimensions multiples of 8 and 16-byte aligned bases) and whose output is at
-  // least MMDA_GEMM_DMA_MIN (default 96) rows and columns; MMDA_GEMM_DMA=0 switches it off, MMDA_GEMM_DMA_STAGES=2|3 sets the depth of
-  // its LDS ring (2: 64 KB, two workgroups per CU; 3: 96 KB, one).
-  static const int t128_min = getenv("MMDA_GEMM_T128_MIN") ? atoi(getenv("MMDA_GEMM_T128_MIN")) : 512;     // experiment switch
-  static const int dma_on = getenv("MMDA_GEMM_DMA") ? atoi(getenv("MMDA_GEMM_DMA")) : 1;
-  static const int dma_min = getenv("MMDA_GEMM_DMA_MIN") ? atoi(getenv("MMDA_GEMM_DMA_MIN")) : 96;
-  static const int dma_stages = getenv("MMDA_GEMM_DMA_STAGES") ? atoi(getenv("MMDA_GEMM_DMA_STAGES")) : 2;
+  // least DMA_MIN rows and columns; MMDA_GEMM_DMA=0 switches it off, MMDA_GEMM_DMA_STAGES=2|3 sets the depth of its LDS ring (2: 64 KB,
+  // two workgroups per CU; 3: 96 KB, one).  Class 1 takes a problem of at least T128_MIN_TILES 128 x 128 tiles (smaller thresholds
+  // measured slower at these sizes).
+  constexpr int T128_MIN_TILES = 512, DMA_MIN = 96;
+  static const int dma_on = mmda_env_int("MMDA_GEMM_DMA", 1);
+  static const int dma_stages = mmda_env_int("MMDA_GEMM_DMA_STAGES", 2);
   // ... and only in a call of large-batch problems -- some problem with >= 8192 rows (nt) or k-rows (tn): T * B of the step.  Measured
   // (step, ms; DMA class on / off): B=32 0.694 / 0.657, B=64 0.834 / 0.822, B=128 1.167 / 1.174, B=256 1.85 / 2.02 -- below that the
   // problems are a few k-tiles on a few hundred workgroups, where the register-staged 64 x 64 kernel at four workgroups per CU is
   // ahead.  MMDA_GEMM_DMA_MIN_ROWS moves the limit.
-  static const int dma_min_rows = getenv("MMDA_GEMM_DMA_MIN_ROWS") ? atoi(getenv("MMDA_GEMM_DMA_MIN_ROWS")) : 8192;
+  static const int dma_min_rows = mmda_env_int("MMDA_GEMM_DMA_MIN_ROWS", 8192);
   int call_rows = 0;
   for (int i = 0; i < n; ++i) call_rows = max(call_rows, args[i].tn ? args[i].K : args[i].M);
-  // (experiment switch MMDA_GEMM_DMA_FWD=1: calls of forward products only -- nothing accumulates -- take the DMA class at any size)
-  static const int dma_fwd = getenv("MMDA_GEMM_DMA_FWD") ? atoi(getenv("MMDA_GEMM_DMA_FWD")) : 0;
-  bool fwd_only = n > 0;
-  for (int i = 0; i < n; ++i) fwd_only = fwd_only && !args[i].accumulate && !args[i].tn && !args[i].bias_grad;
-  const bool dma_call = dma_on && (call_rows >= dma_min_rows || (dma_fwd && fwd_only));
+  const bool dma_call = dma_on && call_rows >= dma_min_rows;
   // (OFF by default since the end of round 3: with the rest of the step as it is now the B=256 step measures 1.690 ms without the
   //  class against 1.705 with it -- its 147 KB workgroups do not fit a CU beside a recurrent kernel's, and on the main stream they
-  //  are no faster than two 128-row workgroups per CU; MMDA_GEMM_DMA_TALL=1 switches it on)
-  static const int dma_tall = getenv("MMDA_GEMM_DMA_TALL") ? atoi(getenv("MMDA_GEMM_DMA_TALL")) : 0;
-  static const int tall_stages = getenv("MMDA_GEMM_DMA_TALL_STAGES") ? atoi(getenv("MMDA_GEMM_DMA_TALL_STAGES")) : 3;
+  //  are no faster than two 128-row workgroups per CU; MMDA_GEMM_DMA_TALL=1 switches it on.  Its LDS ring has three stages: two
+  //  measured slower)
+  static const int dma_tall = mmda_env_int("MMDA_GEMM_DMA_TALL", 0);
   auto class_of = [&](const mmda_gemm_bf16_args& a) {
     const int Ne = a.N + (a.bias_grad ? 1 : 0);
-    if (dma_call && a.M >= dma_min && Ne >= dma_min) {
+    if (dma_call && a.M >= DMA_MIN && Ne >= DMA_MIN) {
       bool ok = true;
       if (a.tn) ok = !(a.lda & 7) && !(a.ldb & 7) && !(((uintptr_t)a.A | (uintptr_t)a.B) & 15) && ((double)a.K + 64.0) * (double)max(a.lda, a.ldb) < 2.0e9;
       // 256-row tiles (class 3) for the long k-walks of a tall output: K >= 1024, M >= 512 (input gradients: K = 8H; weight gradients:
@@ -795,7 +790,7 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
       if (ok && dma_tall && a.K >= 1024 && a.M >= 512) return 3;
       if (ok) return 2;
     }
-    return ceil_div(Ne, 128) * ceil_div(a.M, 128) >= t128_min ? 1 : 0;
+    return ceil_div(Ne, 128) * ceil_div(a.M, 128) >= T128_MIN_TILES ? 1 : 0;
   };
   // ---- plan: per class, the problems in launch order and their split-K
   struct Plan { std::vector<int> order; std::vector<int> sks; };
@@ -827,7 +822,6 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
     int64_t work2 = 0;                                    // class 2: k-tiles of the whole launch
     for (int i : order) work2 += (int64_t)tiles_of(args[i], T) * ceil_div(args[i].K, TK);
     // pass 1: the split of every problem on its own
-    static const int split_min_nk = getenv("MMDA_GEMM_SPLIT_MIN_NK") ? atoi(getenv("MMDA_GEMM_SPLIT_MIN_NK")) : 128;
     for (int i : order) {
       const mmda_gemm_bf16_args& a = args[i];
       const int tiles = tiles_of(a, T);
@@ -852,32 +846,21 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
         // is cut until the slots are full.  Below that nothing is split any more: with the slices combined through slabs and a reduce
         // launch (round 3) instead of float atomics, a split costs the MOSEI-sized problems more than its parallelism returns --
         // measured, alternating runs (step, ms; split / no split): B=16 0.621 / 0.612, B=32 0.665 / 0.652, B=64 0.846 / 0.842,
-        // B=128 1.206 / 1.196.  MMDA_GEMM_SPLIT_MIN_NK moves the limit (8: round 2's policy).
-        static const int long_k = getenv("MMDA_GEMM_LONGK_SPLIT") ? atoi(getenv("MMDA_GEMM_LONGK_SPLIT")) : 1;
-        sk = long_k ? ceil_div(1024, tiles) : 1;
+        // B=128 1.206 / 1.196 (round 2 split from 8 k-tiles).
+        sk = ceil_div(1024, tiles);
         while (sk > 1 && (nk / sk < 16 || sk * out_mb > 24.0)) --sk;
-      } else if (split_min_nk < 128 && tiles < 256 && nk >= split_min_nk) {
-        sk = ceil_div(512, tiles);
-        if (sk > nk / 4) sk = nk / 4;
-        while (sk > 1 && sk * out_mb > 6.0) --sk;
-        if (sk > 16) sk = 16;
-        if (sk < 1) sk = 1;
       }
-      static const int max_split = getenv("MMDA_GEMM_MAX_SPLIT") ? atoi(getenv("MMDA_GEMM_MAX_SPLIT")) : 0;      // experiment switch
-      if (max_split > 0 && sk > max_split) sk = max_split;
       // a fresh (non-accumulated) output gains from a split only with a long K loop in a launch that would otherwise leave the chip
       // underfilled
       if (sk > 1 && !a.accumulate && (crowded || nk < 16)) sk = 1;
       sks[i] = sk;
     }
-    // pass 2: the launch as a whole.  The chip holds SLOTS workgroups of this kernel at once; a launch of 1.x times that runs a second,
-    // mostly empty round.  While the launch sits between one and two rounds, the most finely split problems give slices back.
+    // pass 2: the launch as a whole.  The chip holds `resident` workgroups of this kernel at once; a launch of 1.x times that runs a
+    // second, mostly empty round.  While the launch sits between one and two rounds, the most finely split problems give slices back.
     {
-      static const int slots = getenv("MMDA_GEMM_SLOTS") ? atoi(getenv("MMDA_GEMM_SLOTS")) : -1;
-      const int sl = slots >= 0 ? slots : resident;
       auto total = [&]() { int64_t t = 0; for (int i : order) t += (int64_t)tiles_of(args[i], T) * sks[i]; return t; };
       int64_t tot = total();
-      while (ci < 2 && sl > 0 && tot > sl && tot < 2 * (int64_t)sl) {
+      while (ci < 2 && tot > resident && tot < 2 * (int64_t)resident) {
         int best = -1;
         for (int i : order) if (sks[i] > 1 && (best < 0 || sks[i] > sks[best] || (sks[i] == sks[best] && tiles_of(args[i], T) > tiles_of(args[best], T)))) best = i;
         if (best < 0) break;
@@ -927,8 +910,7 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
       for (int k = G.n; k <= GROUP_MAX; ++k) G.start[k] = blocks;
       for (int k = G.n; k < GROUP_MAX; ++k) { G.p[k] = G.p[0]; G.tx[k] = G.ty[k] = G.splitk[k] = 1; G.tile[k] = T; G.slab[k] = nullptr; G.ldn[k] = 0; }
       if (ci == 3) {
-        if (tall_stages == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<2, 256>), dim3(blocks), dim3(512), 0, s, G);
-        else hipLaunchKernelGGL((gemm_bf16_dma_kernel<3, 256>), dim3(blocks), dim3(512), 0, s, G);
+        hipLaunchKernelGGL((gemm_bf16_dma_kernel<3, 256>), dim3(blocks), dim3(512), 0, s, G);
       } else if (ci == 2) {
         if (dma_stages == 3) hipLaunchKernelGGL((gemm_bf16_dma_kernel<3, 128>), dim3(blocks), dim3(256), 0, s, G);
         else hipLaunchKernelGGL((gemm_bf16_dma_kernel<2, 128>), dim3(blocks), dim3(256), 0, s, G);

@@ -14,7 +14,6 @@
 // Up to 8 independent problems per launch.  Deterministic: no atomics, fixed reduction order.
 #include "common.h"
 #include "transpose_tile.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -25,7 +24,6 @@ struct SkinnyLaunch {
   mmda_skinny_args p[SK_MAXP];
   int start[SK_MAXP + 1];
   int tx[SK_MAXP];
-  int nsplit[SK_MAXP];           // 1: waves split N (short K), 0: waves split K
   int n;
 };
 
@@ -34,7 +32,7 @@ __device__ __forceinline__ bool vec_ok(const float* p, int ld) { return (((uintp
 
 // One product: acc[t] += A[row0 + 16t .. , :] * op(B)[:, col0 ..] over this wave's chunks.
 // VEC: float4 loads along k for A (and for B when TB); needs 16-B aligned bases, ld % 4 == 0 and K % 4 == 0.
-template <bool TB, bool VEC, int WK>
+template <bool TB, bool VEC>
 __device__ __forceinline__ void skinny_product(f32x4 (&acc)[2], const float* __restrict__ A, const float* __restrict__ A2, int lda,
                                                const float* __restrict__ Bm, int ldb, int M, int N, int K, int row0, int col0,
                                                int wave, int lane) {
@@ -101,12 +99,12 @@ __device__ __forceinline__ void skinny_product(f32x4 (&acc)[2], const float* __r
 
   if (wave >= nchunks) return;                       // wave-uniform
 #pragma unroll
-  for (int p = 0; p < SK_PF; ++p) load(p, wave + WK * p);            // chunks past the end load clamped addresses and read as zero
-  for (int base = wave; base < nchunks; base += WK * SK_PF) {
+  for (int p = 0; p < SK_PF; ++p) load(p, wave + SK_WAVES * p);            // chunks past the end load clamped addresses and read as zero
+  for (int base = wave; base < nchunks; base += SK_WAVES * SK_PF) {
 #pragma unroll
     for (int p = 0; p < SK_PF; ++p) {
-      if (base + WK * p < nchunks) mma(p);           // wave-uniform
-      const int next = base + WK * (p + SK_PF);
+      if (base + SK_WAVES * p < nchunks) mma(p);           // wave-uniform
+      const int next = base + SK_WAVES * (p + SK_PF);
       if (next < nchunks) load(p, next);             // wave-uniform
     }
   }
@@ -134,73 +132,6 @@ __device__ __forceinline__ void skinny_epilogue(const mmda_skinny_args& g, int m
   }
 }
 
-// Short K, wide N (the FFN up-projection and its input gradient: M = 6B, N = 2048, K = 128): no K split.  The block's eight
-// waves tile a 64 x 128 output (2 x 4 waves of 32 x 32 = 2 x 2 MFMA tiles each), every wave walks the whole K with four
-// float4 loads (two A row tiles, two B column tiles) per 16-deep chunk feeding 16 MFMAs, and writes its tile straight from
-// the accumulators.  The K-split form spends 768 workgroups on one chunk each for this shape.  NT, 16-byte aligned operands only.
-__device__ __forceinline__ void skinny_wide(const mmda_skinny_args& g, int row0, int col0, int lane) {
-  const int r = lane & 15, q = lane >> 4;
-  const int M = g.M, N = g.N, K = g.K;
-  const int nchunks = (K + 15) >> 4;
-  const int ar0 = min(row0 + r, M - 1), ar1 = min(row0 + 16 + r, M - 1);
-  const int bc0 = min(col0 + r, N - 1), bc1 = min(col0 + 16 + r, N - 1);
-  const bool a0_ok = row0 + r < M, a1_ok = row0 + 16 + r < M, b0_ok = col0 + r < N, b1_ok = col0 + 16 + r < N;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int PF = 4;
-  f4 ra0[PF], ra1[PF], rb0[PF], rb1[PF];
-  const f4 z = {0.f, 0.f, 0.f, 0.f};
-  auto load = [&](int slot, int c) {
-    const int k = c * 16 + 4 * q;
-    const int kc = min(k, K - 4);
-    const bool k_ok = k < K;
-    f4 a0 = *reinterpret_cast<const f4*>(g.A + (int64_t)ar0 * g.lda + kc);
-    f4 a1 = *reinterpret_cast<const f4*>(g.A + (int64_t)ar1 * g.lda + kc);
-    if (g.A2) {
-      a0 += *reinterpret_cast<const f4*>(g.A2 + (int64_t)ar0 * g.lda + kc);
-      a1 += *reinterpret_cast<const f4*>(g.A2 + (int64_t)ar1 * g.lda + kc);
-    }
-    const f4 b0 = *reinterpret_cast<const f4*>(g.B + (int64_t)bc0 * g.ldb + kc);
-    const f4 b1 = *reinterpret_cast<const f4*>(g.B + (int64_t)bc1 * g.ldb + kc);
-    ra0[slot] = (a0_ok && k_ok) ? a0 : z; ra1[slot] = (a1_ok && k_ok) ? a1 : z;
-    rb0[slot] = (b0_ok && k_ok) ? b0 : z; rb1[slot] = (b1_ok && k_ok) ? b1 : z;
-  };
-  auto mma = [&](int slot) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra0[slot][s], rb0[slot][s], acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra0[slot][s], rb1[slot][s], acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra1[slot][s], rb0[slot][s], acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra1[slot][s], rb1[slot][s], acc[1][1], 0, 0, 0);
-    }
-  };
-#pragma unroll
-  for (int p = 0; p < PF; ++p) load(p, p);
-  for (int base = 0; base < nchunks; base += PF) {
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      if (base + p < nchunks) mma(p);
-      if (base + p + PF < nchunks) load(p, base + p + PF);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = col0 + j * 16 + (lane & 15);
-      if (n >= N) continue;
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = row0 + i * 16 + (lane >> 4) * 4 + rg;
-        if (m < M) skinny_epilogue(g, m, n, acc[i][j][rg]);
-      }
-    }
-}
-
-template <int WK>
 __device__ __forceinline__ void skinny_products(f32x4 (&acc)[2], const mmda_skinny_args& g, int row0, int col0, int wave, int lane) {
   for (int prod = 0; prod < 2; ++prod) {
     const float* A = prod ? g.A_2nd : g.A;
@@ -210,11 +141,11 @@ __device__ __forceinline__ void skinny_products(f32x4 (&acc)[2], const mmda_skin
     if (!A || K <= 0) continue;
     const bool va = vec_ok(A, lda) && (K & 3) == 0 && (!A2 || vec_ok(A2, lda));
     if (g.transB) {
-      if (va && vec_ok(Bm, ldb)) skinny_product<true, true, WK>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
-      else skinny_product<true, false, WK>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
+      if (va && vec_ok(Bm, ldb)) skinny_product<true, true>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
+      else skinny_product<true, false>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
     } else {
-      if (va) skinny_product<false, true, WK>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
-      else skinny_product<false, false, WK>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
+      if (va) skinny_product<false, true>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
+      else skinny_product<false, false>(acc, A, A2, lda, Bm, ldb, g.M, g.N, K, row0, col0, wave, lane);
     }
   }
 }
@@ -230,31 +161,8 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkinnyLaunch L) {
   const int bx = local % L.tx[pi], by = local / L.tx[pi];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  if (L.nsplit[pi] == 2) {
-    // 64 x 128 block tile, wave (wr, wc) = (wave >> 2, wave & 3) owns 32 x 32
-    const int row0 = by * 64 + (wave >> 2) * 32, col0 = bx * 128 + (wave & 3) * 32;
-    if (row0 >= g.M || col0 >= g.N) return;              // wave-uniform; no barrier on this path
-    skinny_wide(g, row0, col0, lane);
-    return;
-  }
-  if (L.nsplit[pi]) {
-    // short K, wide N: the eight waves take eight adjacent 16-column tiles and each walks the whole K; no cross-wave sum
-    const int row0 = by * SK_TM, col0 = (bx * SK_WAVES + wave) * SK_TN;
-    if (col0 >= g.N) return;                             // wave-uniform; no barrier on this path
-    skinny_products<1>(acc, g, row0, col0, 0, lane);
-    const int n = col0 + (lane & 15);
-    if (n >= g.N) return;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = row0 + t * 16 + (lane >> 4) * 4 + rg;
-        if (m < g.M) skinny_epilogue(g, m, n, acc[t][rg]);
-      }
-    return;
-  }
   const int row0 = by * SK_TM, col0 = bx * SK_TN;
-  skinny_products<SK_WAVES>(acc, g, row0, col0, wave, lane);
+  skinny_products(acc, g, row0, col0, wave, lane);
   // D fragment: col = lane & 15, row = (lane >> 4) * 4 + reg
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -299,23 +207,15 @@ extern "C" int mmda_gemm_skinny(const mmda_skinny_args* args, int n, void* strea
       if (a.M == 0 || a.N == 0) continue;
       const int k = L.n++;
       L.p[k] = a;
-      // Column-split form (one wave per 16-column tile walks the whole K; K <= 256): OFF unless MMDA_SKINNY_NSPLIT_MIN_N is set.
-      // Measured on the training step it loses to the K-split form at every shape of the fusion block (1.35 -> 1.43 ms per
-      // step with it on for N >= 128, 1.37 for N >= 1024): eight waves sharing one k-walk's latency beat eight walking alone.
-      static const int nsplit_min_n = getenv("MMDA_SKINNY_NSPLIT_MIN_N") ? atoi(getenv("MMDA_SKINNY_NSPLIT_MIN_N")) : (1 << 30);
-      L.nsplit[k] = (a.K <= 256 && a.K2 <= 256 && a.N >= nsplit_min_n) ? 1 : 0;
-      // wide form: NT, single product, K <= 256 and a multiple of 4, N >= 1024, 16-byte aligned operands
-      static const int wide_min_n = getenv("MMDA_SKINNY_WIDE_MIN_N") ? atoi(getenv("MMDA_SKINNY_WIDE_MIN_N")) : (1 << 30);    // OFF by default: measured +15 us per step against the K-split form at N = 2048
-      const bool al = ((((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.A2) & 15) == 0) && !(a.lda & 3) && !(a.ldb & 3) && !(a.K & 3);
-      if (a.transB && a.K2 <= 0 && a.K <= 256 && a.N >= wide_min_n && al && !a.C2) L.nsplit[k] = 2;
-      int rows_per_block = SK_TM;
-      if (L.nsplit[k] == 2) { L.tx[k] = ceil_div(a.N, 128); rows_per_block = 64; }
-      else L.tx[k] = L.nsplit[k] ? ceil_div(a.N, SK_WAVES * SK_TN) : ceil_div(a.N, SK_TN);
+      // One form: the eight waves of a 32 x 16 tile split K.  A column-split form (one wave per 16-column tile walks the whole
+      // K) lost at every shape of the fusion block (1.35 -> 1.43 ms per step for N >= 128), and a 64 x 128 "wide" tile for
+      // short K lost 15 us per step at N = 2048: eight waves sharing one k-walk's latency beat eight walking alone.
+      L.tx[k] = ceil_div(a.N, SK_TN);
       L.start[k] = blocks;
-      blocks += L.tx[k] * ceil_div(a.M, rows_per_block);
+      blocks += L.tx[k] * ceil_div(a.M, SK_TM);
     }
     for (int k = L.n; k <= SK_MAXP; ++k) L.start[k] = blocks;
-    for (int k = L.n; k < SK_MAXP; ++k) { L.p[k] = L.p[0]; L.tx[k] = 1; L.nsplit[k] = 0; }
+    for (int k = L.n; k < SK_MAXP; ++k) { L.p[k] = L.p[0]; L.tx[k] = 1; }
     if (blocks == 0) continue;
     hipLaunchKernelGGL(gemm_skinny_kernel, dim3(blocks), dim3(512), 0, s, L);
     MMDA_CHECK_LAUNCH("mmda_gemm_skinny");

@@ -21,7 +21,6 @@
 //   single-workgroup-per-CU blocks (LDS > 80 KB each) and chunks larger batches over several launches.
 #include "common.h"
 #include <algorithm>
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -150,20 +149,18 @@ constexpr unsigned OOB = 0xFFFFFF00u;
 __device__ __forceinline__ float ldf(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
 }
-// (cache policy of the bulk stores -- stash, hseq, gate gradients -- as a build-time knob.  Measured at B=32, step in ms: default
-//  write-back 0.722, nt 0.740, sc1 write-through 0.751, sc0 sc1 0.753: the end-of-kernel write-back of what is still dirty costs less
-//  than write-through traffic beside the hand-offs)
-#ifndef MMDA_STASH_AUX
-#define MMDA_STASH_AUX 0
-#endif
+// cache policy of the bulk stores -- stash, hseq, gate gradients: write-back.  (Measured at B=32, step in ms: write-back 0.722, nt
+// 0.740, sc1 write-through 0.751, sc0 sc1 0.753: the end-of-kernel write-back of what is still dirty costs less than write-through
+// traffic beside the hand-offs.)
+constexpr int STASH_AUX = 0;
 __device__ __forceinline__ void stf(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, MMDA_STASH_AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, STASH_AUX);
 }
 __device__ __forceinline__ f32x4 ldf4(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 __device__ __forceinline__ void stf4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, MMDA_STASH_AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, STASH_AUX);
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -419,45 +416,10 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_cluster_kernel(CLaunch L) {
 // flight ~130 cycles apart to cut the quantisation of the wait, but every read in flight queues in the polling CU's memory pipeline in
 // front of the loads that fetch the data (measured below).  Returns false on timeout / abort (bounded spin).
 // (flag reads in flight per polling wave: B=256, all eight groups in one launch, step 2.375 ms with four, 2.354 with two, 2.338 with one)
-#ifndef MMDA_FLAGPOLL
-#define MMDA_FLAGPOLL 1
-#endif
 __device__ __forceinline__ bool poll_tiles(const unsigned char* poll_flag, const unsigned char* abort_w, bool watching, unsigned need) {
-  if (MMDA_FLAGPOLL == 1) {
-    for (unsigned spins = 0;; ++spins) {
-      const unsigned f = ld_flag(poll_flag);
-      if (__all(!watching || (int)(f - need) >= 0)) return true;
-      if (spins > SPIN_LIMIT || ((spins & 255u) == 0 && spins && ld_flag(abort_w) != 0)) return false;
-    }
-  }
-  if (MMDA_FLAGPOLL == 2) {
-    unsigned f0 = ld_flag(poll_flag);
-    __builtin_amdgcn_s_sleep(2);
-    unsigned f1 = ld_flag(poll_flag);
-    for (unsigned spins = 0;; spins += 2) {
-      if (__all(!watching || (int)(f0 - need) >= 0)) return true;
-      f0 = ld_flag(poll_flag);
-      if (__all(!watching || (int)(f1 - need) >= 0)) return true;
-      f1 = ld_flag(poll_flag);
-      if (spins > SPIN_LIMIT || ((spins & 255u) == 0 && spins && ld_flag(abort_w) != 0)) return false;
-    }
-  }
-  unsigned f0 = ld_flag(poll_flag);
-  __builtin_amdgcn_s_sleep(2);
-  unsigned f1 = ld_flag(poll_flag);
-  __builtin_amdgcn_s_sleep(2);
-  unsigned f2 = ld_flag(poll_flag);
-  __builtin_amdgcn_s_sleep(2);
-  unsigned f3 = ld_flag(poll_flag);
-  for (unsigned spins = 0;; spins += 4) {
-    if (__all(!watching || (int)(f0 - need) >= 0)) return true;
-    f0 = ld_flag(poll_flag);
-    if (__all(!watching || (int)(f1 - need) >= 0)) return true;
-    f1 = ld_flag(poll_flag);
-    if (__all(!watching || (int)(f2 - need) >= 0)) return true;
-    f2 = ld_flag(poll_flag);
-    if (__all(!watching || (int)(f3 - need) >= 0)) return true;
-    f3 = ld_flag(poll_flag);
+  for (unsigned spins = 0;; ++spins) {
+    const unsigned f = ld_flag(poll_flag);
+    if (__all(!watching || (int)(f - need) >= 0)) return true;
     if (spins > SPIN_LIMIT || ((spins & 255u) == 0 && spins && ld_flag(abort_w) != 0)) return false;
   }
 }
@@ -642,7 +604,6 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_wave_kernel(CLaunch L) {
   auto do_step = [&](int step, float (&P)[4][4], float (&Pp)[4][4], auto first_tag, auto fm_tag) {
     constexpr bool FIRST = decltype(first_tag)::value;
     constexpr int FM = decltype(fm_tag)::value;
-    constexpr bool ALLK = false;          // true: all KSM k-steps unconditionally (measured slower: see the note at the loop)
     const int t = dir ? T - 1 - step : step;
     const unsigned epoch = L.epoch_base + (unsigned)step + 1u;
     f32x4 acc[4];
@@ -666,7 +627,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_wave_kernel(CLaunch L) {
       // instead was measured slower)
 #pragma unroll
       for (int k2 = 0; k2 < KSM; ++k2) {
-        if (ALLK || k2 < KS) {                           // workgroup-uniform
+        if (k2 < KS) {                                   // workgroup-uniform
 #pragma unroll
           for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[k2], wreg[g][k2], acc[g], 0, 0, 0);
         }
@@ -1241,7 +1202,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_wave_kernel(CLaunch L) {
         if (f32_dg) stf4(rg, o, f32x4{dgv[r][0], dgv[r][1], dgv[r][2], dgv[r][3]});
         if (has_dg16) {                                // the same four values rounded to bf16: 8 bytes at half the byte offset
           const u32x2 pk = {pack_bf16x2(dgv[r][0], dgv[r][1]), pack_bf16x2(dgv[r][2], dgv[r][3])};
-          __builtin_amdgcn_raw_buffer_store_b64(pk, rg16, inb[r] ? (og[r] + (unsigned)t * sg) >> 1 : OOB, 0, MMDA_STASH_AUX);
+          __builtin_amdgcn_raw_buffer_store_b64(pk, rg16, inb[r] ? (og[r] + (unsigned)t * sg) >> 1 : OOB, 0, STASH_AUX);
         }
       } else {
 #pragma unroll
@@ -1447,19 +1408,13 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_wave_kernel(CLaunch L) {
 // waves together have seen every tile's four flags for step s+1, hence after every reader of the step-s image has finished with it.
 // A wave whose poll times out raises the abort word and from then on stops waiting (its results are garbage, the host discards the
 // launch) but keeps arriving at the barriers, so the grid always drains.
-// Steady-state data polling: PSETS copies of a wave's three loads in flight, PGAP x 64 cycles between their first issues (one copy:
-// before the first).  Measured at B=32 (step, ms): one copy 0.740 (0 / 256 / 512 cycles of first delay: equal, 1024: 0.763), two copies
-// issued back to back 0.738, two spaced by 512 / 1024 cycles 0.92 / 0.90, three 1.03, four 1.15 -- every read in flight sits in the
-// consumer CU's memory queue in front of the one that will return the data, so polling harder makes the hand-off slower.
-#ifndef MMDA_PSETS
-#define MMDA_PSETS 1
-#define MMDA_PGAP 0
-#endif
-// ... and 64 cycles of s_sleep between a stale answer and the next question (B=32 step 0.676 -> 0.668 ms; 128 / 256 cycles: 0.676 / 0.692)
-#ifndef MMDA_POLL_SLEEP
-#define MMDA_POLL_SLEEP 1
-#endif
-constexpr int PSETS = MMDA_PSETS, PGAP = MMDA_PGAP;
+// Steady-state data polling: one copy of a wave's three loads in flight, issued at once.  Measured at B=32 (step, ms): one copy 0.740
+// (0 / 256 / 512 cycles of first delay: equal, 1024: 0.763), two copies issued back to back 0.738, two spaced by 512 / 1024 cycles
+// 0.92 / 0.90, three 1.03, four 1.15 -- every read in flight sits in the consumer CU's memory queue in front of the one that will
+// return the data, so polling harder makes the hand-off slower.
+// ... and POLL_SLEEP x 64 cycles of s_sleep between a stale answer and the next question (B=32 step 0.676 -> 0.668 ms; 128 / 256
+// cycles: 0.676 / 0.692)
+constexpr int POLL_SLEEP = 1;
 constexpr int QUAD_LDS = 2 * 4 * 16 * 16 * 4 * 4;      // bytes: parity x source wave x 16 rows x 16 units x 4 gates, fp32
 
 __device__ __forceinline__ bool flags4_reached(u32x4 f, unsigned need) {
@@ -1613,8 +1568,8 @@ __global__ __launch_bounds__(256, 4) void lstm_fwd_quad_kernel(CLaunch L) {   //
 #pragma unroll
         for (int j = 0; j < 3; ++j) fa[j] = ld16_sc1(xr, par + foff[j]);
       } else {                                           // steady state: the fragments themselves say when they are there
-        // (PSETS copies of the three loads in flight: see the note at PSETS -- one is best)
-        u32x4 fs[PSETS][3];
+        // (one copy of the three loads in flight: see the note at POLL_SLEEP)
+        u32x4 fs[3];
         // the fragments with the expected tag XORed off (what the MFMAs take); an element that still carries the other tag keeps a tag
         // bit -- `stale` -- and a nonexistent tile reads as zero and stays zero (cl = 0)
         auto untag = [&](u32x4 (&x)[3], const u32x4 (&f)[3]) {
@@ -1627,26 +1582,16 @@ __global__ __launch_bounds__(256, 4) void lstm_fwd_quad_kernel(CLaunch L) {   //
           }
           return (t & TAGS) != 0;
         };
-        if (PSETS == 1 && PGAP > 0) __builtin_amdgcn_s_sleep(PGAP);
 #pragma unroll
-        for (int q = 0; q < PSETS; ++q) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j) fs[q][j] = ld16_sc1(xr, par + foff[j]);
-          if (q + 1 < PSETS) __builtin_amdgcn_s_sleep(PGAP);
-        }
+        for (int j = 0; j < 3; ++j) fs[j] = ld16_sc1(xr, par + foff[j]);
         bool got = false;
-        for (unsigned spins = 0; !got; spins += PSETS) {
+        for (unsigned spins = 0; !got; ++spins) {
+          if (!__any(untag(fa, fs)) || dead) {
+            got = true;
+          } else {
+            __builtin_amdgcn_s_sleep(POLL_SLEEP);           // a short pause before asking again (see POLL_SLEEP)
 #pragma unroll
-          for (int q = 0; q < PSETS; ++q) {
-            if (!got) {
-              if (!__any(untag(fa, fs[q])) || dead) {
-                got = true;
-              } else {
-                __builtin_amdgcn_s_sleep(MMDA_POLL_SLEEP);          // a short pause before asking again (see PSETS)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) fs[q][j] = ld16_sc1(xr, par + foff[j]);
-              }
-            }
+            for (int j = 0; j < 3; ++j) fs[j] = ld16_sc1(xr, par + foff[j]);
           }
           if (!got && (spins > SPIN_LIMIT || ((spins & 255u) == 0 && spins && ld_flag(abort_w) != 0))) {
             dead = true; got = true;
@@ -1918,7 +1863,7 @@ __global__ __launch_bounds__(256, 4) void lstm_bwd_quad_kernel(CLaunch L) {   //
     if (f32_dg) stf4(rg, o, f32x4{dgv[0], dgv[1], dgv[2], dgv[3]});
     if (has_dg16) {
       const u32x2 pk = {pack_bf16x2(dgv[0], dgv[1]), pack_bf16x2(dgv[2], dgv[3])};
-      __builtin_amdgcn_raw_buffer_store_b64(pk, rg16, inb ? (og + (unsigned)t * sg) >> 1 : OOB, 0, MMDA_STASH_AUX);
+      __builtin_amdgcn_raw_buffer_store_b64(pk, rg16, inb ? (og + (unsigned)t * sg) >> 1 : OOB, 0, STASH_AUX);
     }
   };
   bool fast = false;
@@ -1950,7 +1895,7 @@ __global__ __launch_bounds__(256, 4) void lstm_bwd_quad_kernel(CLaunch L) {   //
 #pragma unroll
         for (int l = 0; l < 3; ++l) fa[l] = ld16_sc1(xr, par + goff[l]);
       } else {
-        u32x4 fs[PSETS][3];                              // (see the forward kernel)
+        u32x4 fs[3];                                     // (see the forward kernel)
         auto untag = [&](u32x4 (&x)[3], const u32x4 (&f)[3]) {
           unsigned t = 0;
 #pragma unroll
@@ -1961,26 +1906,16 @@ __global__ __launch_bounds__(256, 4) void lstm_bwd_quad_kernel(CLaunch L) {   //
           }
           return (t & TAGS) != 0;
         };
-        if (PSETS == 1 && PGAP > 0) __builtin_amdgcn_s_sleep(PGAP);
 #pragma unroll
-        for (int q = 0; q < PSETS; ++q) {
-#pragma unroll
-          for (int l = 0; l < 3; ++l) fs[q][l] = ld16_sc1(xr, par + goff[l]);
-          if (q + 1 < PSETS) __builtin_amdgcn_s_sleep(PGAP);
-        }
+        for (int l = 0; l < 3; ++l) fs[l] = ld16_sc1(xr, par + goff[l]);
         bool got = false;
-        for (unsigned spins = 0; !got; spins += PSETS) {
+        for (unsigned spins = 0; !got; ++spins) {
+          if (!__any(untag(fa, fs)) || dead) {
+            got = true;
+          } else {
+            __builtin_amdgcn_s_sleep(POLL_SLEEP);           // a short pause before asking again (see POLL_SLEEP)
 #pragma unroll
-          for (int q = 0; q < PSETS; ++q) {
-            if (!got) {
-              if (!__any(untag(fa, fs[q])) || dead) {
-                got = true;
-              } else {
-                __builtin_amdgcn_s_sleep(MMDA_POLL_SLEEP);          // a short pause before asking again (see PSETS)
-#pragma unroll
-                for (int l = 0; l < 3; ++l) fs[q][l] = ld16_sc1(xr, par + goff[l]);
-              }
-            }
+            for (int l = 0; l < 3; ++l) fs[l] = ld16_sc1(xr, par + goff[l]);
           }
           if (!got && (spins > SPIN_LIMIT || ((spins & 255u) == 0 && spins && ld_flag(abort_w) != 0))) {
             dead = true; got = true;
@@ -2138,12 +2073,10 @@ extern "C" int mmda_debug_set_lstm_stamps(void* device_buffer) { g_dbg = (unsign
 namespace {
 // The wave-autonomous kernels run when every descriptor's W_hh k-steps fit their register-resident form.  Their blocks hold
 // 1, 2 or 4 waves (one (hidden tile, m-tile) each): the fewest waves per block that still fit one launch, because the waves
-// of a block share the CU's address unit and the per-step memory instructions are what they queue on.
-bool wave_form_ok(int n, const mmda_lstm_desc* descs, bool bwd, int* wpb_out, int ngt = 1) {
-  static const int no_wave = getenv("MMDA_LSTM_BARRIER_FWD") ? 1 : 0;        // ablation: the barrier-synchronised forward kernel
-  static const int force_wpb = getenv("MMDA_LSTM_WPB") ? atoi(getenv("MMDA_LSTM_WPB")) : 0;
-  static const int no_wave_b = getenv("MMDA_LSTM_BARRIER_BWD") ? 1 : 0;      // ablation: the barrier-synchronised backward kernel
-  bool ok = bwd ? !no_wave_b : !no_wave;
+// of a block share the CU's address unit and the per-step memory instructions are what they queue on.  (Beyond 320 hidden units
+// the barrier-synchronised kernels run instead; where both fit, they measured slower.)
+bool wave_form_ok(int n, const mmda_lstm_desc* descs, int* wpb_out, int ngt = 1) {
+  bool ok = true;
   for (int i = 0; i < n; ++i) ok = ok && round_up(descs[i].H, 32) / 32 <= 10;
   auto count_wgs = [&](int w) { int t = 0; for (int i = 0; i < n; ++i) t += 2 * ceil_div(2 * (round_up(descs[i].H, 16) / 16), w); return t; };
   int wpb = 4;
@@ -2151,11 +2084,10 @@ bool wave_form_ok(int n, const mmda_lstm_desc* descs, bool bwd, int* wpb_out, in
     // ... of ALL ngt batch groups where possible (B = 256: eight groups, 864 waves = 240 four-wave blocks, one wave per SIMD): the
     // groups are independent chains, and a second launch for the groups that did not fit costs a whole extra walk of the sequence,
     // where more waves per CU cost a fraction of a step (they queue on the CU's address unit, not on each other's hand-offs).
-    static const int per_group = getenv("MMDA_LSTM_WPB_PER_GROUP") ? 1 : 0;      // ablation: round 1's choice (fit ONE group)
-    const int groups = per_group ? 1 : (ngt < 1 ? 1 : ngt);
+    // (Round 1 fitted one group only: measured slower.)
+    const int groups = ngt < 1 ? 1 : ngt;
     wpb = 1;
     while (wpb < 4 && count_wgs(wpb) * groups > MAX_WG_PER_LAUNCH) wpb *= 2;
-    if (force_wpb == 1 || force_wpb == 2 || force_wpb == 4) wpb = force_wpb;
     if (count_wgs(wpb) > MAX_WG_PER_LAUNCH) ok = false;
   }
   if (wpb_out) *wpb_out = ok ? wpb : 4;
@@ -2171,7 +2103,7 @@ bool cluster_applicable(int n, const mmda_lstm_desc* descs, int B, int T, bool b
     if (!descs[i].xchg) return false;
     if (descs[i].cell != descs[0].cell) return false;
     // the GRU cell exists in the wave-autonomous kernels only (and in the streaming kernels of lstm.hip)
-    if (descs[i].cell != MMDA_CELL_LSTM && !wave_form_ok(n, descs, bwd, nullptr)) return false;
+    if (descs[i].cell != MMDA_CELL_LSTM && !wave_form_ok(n, descs, nullptr)) return false;
     if (bwd && (!descs[i].wpack_c[0] || !descs[i].wpack_c[1])) return false;
     if (descs[i].gate_minor != descs[0].gate_minor) return false;
     plans[i] = plan_for(descs[i].H);
@@ -2205,7 +2137,7 @@ extern "C" int mmda_lstm_bwd_emits_dg_bf16(int mode, int n, const mmda_lstm_desc
   Plan plans[MAXD];
   size_t lds = 0;
   if (!cluster_applicable(n, descs, B, T, true, plans, &lds)) return 0;
-  if (!wave_form_ok(n, descs, true, nullptr)) return 0;
+  if (!wave_form_ok(n, descs, nullptr)) return 0;
   for (int i = 0; i < n; ++i)
     if (!descs[i].gate_minor) return 0;
   return 1;
@@ -2220,13 +2152,13 @@ int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, c
   if (!cluster_applicable(n, descs, B, T, bwd, plans, &lds)) return MMDA_OK;
   const int ngt = ceil_div(B, GROUP);
   int wpb = 4;
-  const bool fwd_wave = wave_form_ok(n, descs, bwd, &wpb, ngt);   // (named for the forward kernel; selects the wave-autonomous form of either pass)
+  const bool fwd_wave = wave_form_ok(n, descs, &wpb, ngt);   // (named for the forward kernel; selects the wave-autonomous form of either pass)
   const bool gru = descs[0].cell == MMDA_CELL_GRU;            // cluster_applicable() admitted GRU only together with the wave form
   // Four waves per tile (lstm_fwd_quad_kernel): gate-minor layout, every group's tiles in one launch at one workgroup per tile.
   // MMDA_LSTM_NO_QUAD: ablation (the one-wave-per-tile kernels).
   bool quad = false;
   {
-    static const int no_quad = getenv("MMDA_LSTM_NO_QUAD") ? 1 : 0;
+    static const bool no_quad = mmda_env_set("MMDA_LSTM_NO_QUAD");
     int tiles = 0;
     bool okq = fwd_wave && !no_quad && g_dbg == nullptr;
     for (int i = 0; i < n; ++i) {
@@ -2243,8 +2175,7 @@ int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, c
                                       per_cu(reinterpret_cast<const void*>(lstm_fwd_quad_kernel<MMDA_CELL_GRU, 0>)));
     static const int occ_b = std::min(per_cu(reinterpret_cast<const void*>(lstm_bwd_quad_kernel<MMDA_CELL_LSTM, 2, 2>)),
                                       per_cu(reinterpret_cast<const void*>(lstm_bwd_quad_kernel<MMDA_CELL_GRU, 2, 2>)));
-    static const int quad_cap = getenv("MMDA_LSTM_QUAD_CAP") ? atoi(getenv("MMDA_LSTM_QUAD_CAP")) : MAX_WG_QUAD;
-    const int cap = std::min(quad_cap, 240 * (bwd ? occ_b : occ_f));
+    const int cap = std::min(MAX_WG_QUAD, 240 * (bwd ? occ_b : occ_f));
     quad = okq && tiles * ngt <= cap;
     if (quad) wpb = 1;
   }
@@ -2281,15 +2212,14 @@ int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, c
     }
     // Placement (speed only): blocks b and b + 8 are dealt to the same XCD, so the members of one cluster get block ids that
     // are equal mod 8; clusters go to the XCD with the fewest members so far.
-    static const int use_place = getenv("MMDA_NO_PLACEMENT") ? 0 : 1;
-    static const int xcd_env = getenv("MMDA_XCD_LOCAL") ? atoi(getenv("MMDA_XCD_LOCAL")) : 1;      // 0: ablation (always write through)
+    static const int xcd_env = mmda_env_int("MMDA_XCD_LOCAL", 1);      // 0: ablation (always write through); 3: test hook
     L.xcd_local = xcd_env;
     for (int b = 0; b < MAXB; ++b) L.blk2role[b] = -1;
     int grid_blocks = wg;
     {
       int used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       const int per_xcd = quad ? 32 * 4 : 32;             // block slots per XCD
-      bool fits = use_place && wg <= 8 * per_xcd;
+      bool fits = wg <= 8 * per_xcd;
       // (first role, members).  Wave form with one wave per block: a wave exchanges data only with the waves of its own m-tile
       // (roles first + mt, first + mt + 2, ...), so each m-tile is a cluster of its own (19 blocks for text: fits an XCD's 32 CUs).
       const bool by_mt = fwd_wave && wpb == 1;
@@ -2316,24 +2246,22 @@ int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, c
       if (fits) { for (int b = 0; b < MAXB; ++b) L.blk2role[b] = map[b]; grid_blocks = 8 * max_slots; }
       else { for (int b = 0; b < wg && b < MAXB; ++b) L.blk2role[b] = (short)b; L.xcd_local = 0; }
       // only the wave kernels verify the placement (per m-tile: every wave reads the XCC ids of all hidden tiles of its m-tile)
-      // before they rely on it; the barrier-form kernels' unchecked variant stays an experiment (MMDA_XCD_LOCAL=2)
-      if (!fwd_wave && xcd_env != 2) L.xcd_local = 0;
+      // before they rely on it; the barrier-form kernels always write through
+      if (!fwd_wave) L.xcd_local = 0;
     }
     bool bwd_regs = true;                    // every descriptor's n-tiles fit the register-resident form (<= 10 per wave)
     for (int i = 0; i < n; ++i) bwd_regs = bwd_regs && L.d[i].nHT <= 20;
     // Wave form: the kernel needs 2 KB per wave.  With one wave per block it asks for the CU's whole LDS instead: that keeps every
     // LDS-using workgroup of a concurrent kernel (weight-gradient GEMMs and conversions on the side stream) off the ~110 CUs
-    // that host a recurrent wave, and leaves them the other ~145.  (MMDA_LSTM_LDS_KB: ablation.)
-    static const int lds_kb = getenv("MMDA_LSTM_LDS_KB") ? atoi(getenv("MMDA_LSTM_LDS_KB")) : 160;
+    // that host a recurrent wave, and leaves them the other ~145.
     // Only while the launch leaves a good part of the chip free (<= 160 blocks): every block then needs a CU of its own, and the
     // members of a cluster must all be resident at once -- a launch that wants most of the 256 CUs keeps the small allocation, so
     // that its blocks can share CUs if something else (another process on the GPU) holds some.
     const bool reserve = wpb == 1 && grid_blocks <= 160;
     // backward, four waves per block (large batches): the two waves of an m-tile pre-reduce their partial dh tiles in LDS and publish
-    // one partial per producer PAIR (lstm_bwd_wave_kernel<..., PAIR = 1>): 4 x 2 KB + 4 x 10 KB + the epoch words.  MMDA_LSTM_PAIR=0: off.
-    static const int pair_on = getenv("MMDA_LSTM_PAIR") ? atoi(getenv("MMDA_LSTM_PAIR")) : 1;
-    const bool pair_bwd = pair_on && bwd && fwd_wave && !quad && wpb == 4 && L.gate_minor && !gru && g_dbg == nullptr;
-    const size_t lds_launch = fwd_wave ? (reserve ? (size_t)(lds_kb < 32 ? 32 : lds_kb > 160 ? 160 : lds_kb) * 1024
+    // one partial per producer PAIR (lstm_bwd_wave_kernel<..., PAIR = 1>): 4 x 2 KB + 4 x 10 KB + the epoch words.
+    const bool pair_bwd = bwd && fwd_wave && !quad && wpb == 4 && L.gate_minor && !gru && g_dbg == nullptr;
+    const size_t lds_launch = fwd_wave ? (reserve ? (size_t)160 * 1024
                                                   : (quad ? (size_t)QUAD_LDS : (pair_bwd ? (size_t)(4 * 2048 + 4 * 10240 + 64) : (size_t)4 * 2048))) : lds;
     dim3 grid(grid_blocks), block(quad ? 256 : (fwd_wave ? 64 * wpb : 256));
     // the cycle stamps of tools/diag_lstm_phases.py live in a kernel instance of their own (gate-minor LSTM only): even a never-taken
@@ -2349,8 +2277,7 @@ int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, c
         any_dh = any_dh || L.d[i].d_hseq != nullptr;
         all_dh = all_dh && L.d[i].d_hseq != nullptr;
       }
-      static const int no_spec = getenv("MMDA_LSTM_NO_SPEC") ? 1 : 0;
-      if (all16 && !no_spec) spec = !any_dh ? 1 : (all_dh ? 2 : 0);
+      if (all16) spec = !any_dh ? 1 : (all_dh ? 2 : 0);
     }
 #define LAUNCH_C()                                                                                               \
   do {                                                                                                           \

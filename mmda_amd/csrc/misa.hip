@@ -18,7 +18,6 @@ int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D
 #include <map>
 #include <string>
 #include <vector>
-#include <stdlib.h>
 
 namespace {
 
@@ -76,7 +75,7 @@ struct mmda_misa {
   int64_t zero_cls = 0, zero_recon = 0;      // ... its tail: d_scores from zero_cls, d_orig + d_recon from zero_recon (see loss seeds)
   int64_t gpad_begin = 0, gpad_end = 0;      // GRU: four-slot weight gradients (zeroed at set_workspace, re-zeroed by the unpad kernel)
   int64_t z, pmean, prstd, orig, x6, rsum, recon, dom_z, dom_h, dom, qkv, probs, ctx, attn_out, ln1_mean, ln1_rstd, x1, f1, f2,
-      ln2_mean, ln2_rstd, hfused, logits, tcp, scores, labels, losses, diff_work, touched, ffn_parts, pg_parts, ln_parts;
+      ln2_mean, ln2_rstd, hfused, logits, tcp, scores, labels, losses, diff_work, ffn_parts, pg_parts, ln_parts;
   // K-major (transposed) fp32 copies of the fusion block's weights for its input-gradient GEMMs (made once per step)
   int64_t head_wT, l2_wT, l1_wT, out_wT, in_wT, rec_wT, priv_wT, sh_wT, d1_wT = -1, d2_wT = -1, pwT[3];
   int wT_valid = 0;
@@ -86,8 +85,7 @@ struct mmda_misa {
   // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
   // recurrence runs there, on the side stream (set by mmda_misa_train_step around its backward pass)
   int adam_early_on = 0; float ae_lr = 0.f, ae_clip = 0.f; int ae_step = 0; int64_t adam_early_done = 0;
-  int tn_wgrad = 0;                // bit l: layer l + 1's weight-gradient GEMMs read dG / inputs / hseq as they lie (tn form): no transposed copies
-  int embed_early_done = 0;        // this step's early optimizer pass also covered the embedding rows the batch does not touch
+  bool tn_wgrad = false;           // the weight-gradient GEMMs read dG / inputs / hseq as they lie (tn form): no transposed copies
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
   int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
@@ -328,7 +326,6 @@ int64_t layout(mmda_misa* m, int B, int T, bool commit) {
   o->rec_part = k.take(3 * BH);                             // d_recon W_rec, made beside the backward pass's first stretch for its third (fused_rows.h)
   o->esort = k.take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (dist.hip)
   o->pg_parts = k.take((int64_t)B * FUSED_PG_SLOTS * 2 * 128);      // per-sample LayerNorm gamma / beta gradient partials of the fused backward stretches
-  o->touched = k.take((c.vocab + 3) / 4);              // one byte per embedding row: occurs in this batch (see mmda_clamp_adam_rows)
   o->head_wT = k.take((int64_t)6 * hs * NC); o->l2_wT = k.take((int64_t)FFN * hs); o->l1_wT = k.take((int64_t)hs * FFN);
   o->out_wT = k.take((int64_t)hs * hs); o->in_wT = k.take((int64_t)hs * 3 * hs); o->rec_wT = k.take((int64_t)3 * hs * hs);
   o->priv_wT = k.take((int64_t)3 * hs * hs); o->sh_wT = k.take((int64_t)hs * hs);
@@ -423,7 +420,7 @@ void lin_dw(Ctx& c, int mode, int M, int N, int K, const float* dy, const float*
 }
 
 // ---- row-skinny forms (fusion block at B <= SKINNY_MAX_B): see gemm_skinny.hip
-static const int SKINNY_MAX_B = getenv("MMDA_SKINNY_MAX_B") ? atoi(getenv("MMDA_SKINNY_MAX_B")) : 256;   // (env: tile-shape experiments)
+constexpr int SKINNY_MAX_B = 256;
 // y(M,N) = act(x(M,K) W(N,K)^T + b)
 mmda_skinny_args sk_nt(int M, int N, int K, const float* x, int ldx, const float* W, const float* b, float* y, int ldy, int act = 0) {
   mmda_skinny_args g = {};
@@ -459,15 +456,14 @@ void ev_rec(mmda_misa* m, int step, int slot, int which, void* stream) {
 // there; side_join() makes `main_stream` wait for it.  Without overlap the main stream itself is returned.
 int side_fork(mmda_misa* m, void* main_stream, void** out) {
   *out = main_stream;
-  static const int no_side = getenv("MMDA_NO_SIDE") ? atoi(getenv("MMDA_NO_SIDE")) : 0;      // diagnostics: everything on one stream
-  if (!m->use_side || no_side) return MMDA_OK;
+  if (!m->use_side) return MMDA_OK;
   if (!m->side) {
     if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess) return MMDA_ELAUNCH;
     // The fork / join events order streams of ONE device: no system-scope fence with them (hipEventDisableSystemFence -- "device
     // memory may not be visible to the host and other devices", neither of which waits on these events; every kernel still ends with
     // its own device-scope release).  With the fence a recorded event costs the recording stream 6 us between two launches, without
     // it 3 (tools/micro/fork_cost.hip).  MMDA_EVENT_SYSFENCE=1: with the fence.
-    static const int sysfence = getenv("MMDA_EVENT_SYSFENCE") ? atoi(getenv("MMDA_EVENT_SYSFENCE")) : 0;
+    static const int sysfence = mmda_env_int("MMDA_EVENT_SYSFENCE", 0);
     const unsigned evf = hipEventDisableTiming | (sysfence ? 0u : hipEventDisableSystemFence);
     if (hipEventCreateWithFlags(&m->ev_fork, evf) != hipSuccess) return MMDA_ELAUNCH;
     if (hipEventCreateWithFlags(&m->ev_join, evf) != hipSuccess) return MMDA_ELAUNCH;
@@ -750,14 +746,14 @@ int backward_only_jobs(mmda_misa* m, mmda_convert_job* cj) {
     Mod& md = m->mod[i];
     for (int l = 0; l < 2; ++l) {
       Rnn& r = md.rnn[l];
-      if ((m->tn_wgrad >> l) & 1) {
+      if (m->tn_wgrad) {
         for (int d = 0; d < 2; ++d)
           cj[n++] = mmda_convert_job{WS(md.hseq[l]) + d * md.H, 2 * md.H, R, md.H, nullptr, WS(r.hbp[d]), r.ldH, nullptr, 0};
       } else {
         cj[n++] = mmda_convert_job{WS(md.hseq[l]), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(r.hbT), m->ldR};
       }
     }
-    if (!(m->tn_wgrad & 2)) cj[n++] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), m->ldR};
+    if (!m->tn_wgrad) cj[n++] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), m->ldR};
   }
   return n;
 }
@@ -782,7 +778,7 @@ int eager_side_losses(mmda_misa* m, void* stream, bool hseq2_t) {
   // ... unless the main stream will not wait for this chain before the LayerNorm-1 stretch of the backward pass (flag join on the
   // device, small batches: see mmda_misa::jflags) -- the chain then has two launches of slack and the clear comes back here, in ONE
   // launch with the activation-gradient region, at the head of the chain.
-  static const int zg_side = getenv("MMDA_ZERO_GRAD_SIDE") ? atoi(getenv("MMDA_ZERO_GRAD_SIDE")) : -1;
+  static const int zg_side = mmda_env_int("MMDA_ZERO_GRAD_SIDE", -1);
   const bool fj_plan = m->flag_join_ok && m->seed_recon && m->seed_cls && ss != stream && m->jflags;      // (what forward()'s end will decide)
   const bool zg_here = zg_side >= 0 ? zg_side != 0 : (fj_plan && B <= 64);
   if (!rc && zg_here && m->zero_grad_pending) {
@@ -890,62 +886,45 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
   // GEMM epilogues) AND the resident-weights kernels will run, forward and backward.
   int gm = 0;
-  static const int no_gm = getenv("MMDA_NO_GATE_MINOR") ? 1 : 0;     // ablation switch
-  if (bfg && (B % 8) == 0 && T > 0 && !no_gm) gm = probe_resident(1, 0) && probe_resident(1, 1);
+  if (bfg && (B % 8) == 0 && T > 0) gm = probe_resident(1, 0) && probe_resident(1, 1);
   m->gate_minor = gm;
   const bool inf = m->inference != 0;                   // no backward follows: transposed copies and stashes are not needed
   m->last_fwd_inference = inf;
-  // The transposed copies are read by the backward pass only: with a side stream they are made there, beside the recurrent
-  // kernels (`late_t`), and the main stream converts just what the forward GEMMs read.
-  // (measured: the fork's marker packet on the main stream and the L2 traffic beside the forward recurrences cost ~15 us more
-  // than the smaller main-stream conversions save, so this stays an ablation switch, off by default)
-  static const int late_t_on = getenv("MMDA_LATE_T") ? atoi(getenv("MMDA_LATE_T")) : 0;
-  const bool late_t = bfg && m->use_side && !inf && late_t_on;
+  // The transposed copies, which only the backward pass reads, are made on the main stream with the forward ones.  (Making them on
+  // the side stream beside the forward recurrences measured ~15 us slower: the fork's marker packet on the main stream and the L2
+  // traffic beside the recurrences cost more than the smaller main-stream conversions save.)
   // Weight gradients in the tn form of the bf16 GEMM (dW = dG^T X on row-major dG, X, hseq): the transposed copies of the inputs, of
   // hseq and of the gate gradients are not made at all (B=256: 0.33 ms of conversions per step).  Needs the gate gradients as bf16
   // from the recurrent kernel (gate-minor resident path).  Up to T*B = 4096 rows: measured (step, ms) B=32 0.759 -> 0.745, B=64 0.928 ->
   // 0.917, but B=128 1.362 -> 1.391, B=256 2.39 -> 2.55, T=500 4.06 -> 4.08 -- in isolation the tn kernel matches the nt one at K = 1600
   // and runs 15 - 20 % slower at K = 12800 (twice the LDS read instructions per k-tile), which at large batches outweighs the
-  // conversions it saves.  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere; MMDA_GEMM_TN_MAX_ROWS moves the limit.
-  static const int tn_on = getenv("MMDA_GEMM_TN") ? atoi(getenv("MMDA_GEMM_TN")) : 1;
-  // Round 3: the LDS-DMA pipelined GEMM (gemm_bf16_dma_kernel) runs the tn form at K = 12800 as fast as the nt form, so the limit is
-  // gone by default (B=256: the 0.47 ms of transposing conversions per step with it).
-  static const int tn_max_rows = getenv("MMDA_GEMM_TN_MAX_ROWS") ? atoi(getenv("MMDA_GEMM_TN_MAX_ROWS")) : (1 << 30);
-  // (Layer 1 alone in the tn form beyond that limit -- its transposed gate-gradient copy, 0.2 ms at B=256, is the one that cannot hide
-  // beside a recurrence -- measured slower too: B=128 1.285 -> 1.315 ms, B=256 2.20 -> 2.29, T=500 3.92 -> 3.96.  MMDA_GEMM_TN_L1=1.)
-  static const int tn_l1 = getenv("MMDA_GEMM_TN_L1") ? atoi(getenv("MMDA_GEMM_TN_L1")) : 0;
-  const bool tn_any = bfg && gm && tn_on && !late_t && (B % 8) == 0 && probe_resident(1, 2);
-  const bool tnw = tn_any && R <= tn_max_rows;
-  const bool tn_ok = tnw || (tn_any && tn_l1);           // layer 1 in the tn form
-  m->tn_wgrad = (tn_ok && !inf) ? (tnw ? 3 : 1) : 0;
-  auto first_jobs = [&](bool plain, bool transposed, mmda_convert_job* cj) -> int {
+  // conversions it saves.  Round 3: the LDS-DMA pipelined GEMM (gemm_bf16_dma_kernel) runs the tn form at K = 12800 as fast as the nt
+  // form, so both layers take it at every size (B=256: the 0.47 ms of transposing conversions per step with it; a row limit, with or
+  // without layer 1 alone in the tn form beyond it, measured slower).  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere.
+  static const int tn_on = mmda_env_int("MMDA_GEMM_TN", 1);
+  const bool tn_ok = bfg && gm && tn_on && (B % 8) == 0 && probe_resident(1, 2);
+  m->tn_wgrad = tn_ok && !inf;
+  // the first conversions: W_ih of both layers and the layer-1 inputs, plain and (`transposed`) K-major
+  auto first_jobs = [&](bool transposed, mmda_convert_job* cj) -> int {
     int n = 0;
     for (int i = 0; i < 3; ++i) {
       for (int l = 0; l < 2; ++l) {
         Rnn& r = m->mod[i].rnn[l];
-        cj[n++] = mmda_convert_job{rW_ih(m, r), r.D, 8 * r.H, r.D, nullptr, plain ? WS(r.wb) : nullptr, plain ? r.ldD : 0,
+        cj[n++] = mmda_convert_job{rW_ih(m, r), r.D, 8 * r.H, r.D, nullptr, WS(r.wb), r.ldD,
                                    transposed ? WS(r.wbT) : nullptr, transposed ? r.ldG : 0, gm ? r.H : 0};
       }
       Rnn& r0 = m->mod[i].rnn[0];
       const float* src = i == 0 ? PP(m->embed) : xin[i];
       const bool xt = transposed && !tn_ok;              // layer-1 inputs transposed: only the nt form of layer 1's dW_ih reads them
-      if (plain || xt)
-        cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, plain ? WS(r0.xb) : nullptr, plain ? r0.ldD : 0,
-                                   xt ? WS(r0.xbT) : nullptr, xt ? ldR : 0};
+      cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, WS(r0.xb), r0.ldD, xt ? WS(r0.xbT) : nullptr, xt ? ldR : 0};
     }
     return n;
   };
-  auto first_converts = [&](bool plain, bool transposed, void* st) -> int {
-    mmda_convert_job cj[9];
-    const int n = first_jobs(plain, transposed, cj);
-    return mmda_convert_bf16(cj, n, st);
-  };
-  // Merged form (bf16 operand copies in use): the twelve packings and the first conversions go out as ONE launch on the main stream
+  // bf16 operand copies in use: the twelve packings and the first conversions go out as ONE launch on the main stream
   // (mmda_lstm_pack_whh_and_convert) -- no fork, no cross-stream wait in front of the first recurrent kernel (each costs the main stream
   // 4 - 14 us).  The K-major copies of the fusion block's weights, which only the backward pass reads, then ride on the first fork that
-  // happens anyway (wT_pending).  MMDA_PACK_MERGE=0: round 1's form (packing on the side stream, joined by an event).
-  static const int pack_merge = getenv("MMDA_PACK_MERGE") ? atoi(getenv("MMDA_PACK_MERGE")) : 1;
-  const bool merged = bfg && pack_merge && !late_t;
+  // happens anyway (wT_pending).  (Merged measured equal to round 1's form -- packing on the side stream, joined by an event -- which
+  // the fp32 mode keeps.)
   m->wT_pending = 0;
   {
     // The forward packing always; the resident-weights backward packing when those kernels will run the backward pass and the
@@ -965,13 +944,13 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     m->packed_c_valid = want_c ? 1 : 0;
     m->wT_valid = 0;
     const bool want_wT = B <= SKINNY_MAX_B && !m->inference;
-    if (merged) {
+    if (bfg) {
       mmda_convert_job cj[9];
-      const int nj = first_jobs(true, !inf, cj);
+      const int nj = first_jobs(!inf, cj);
       // ... and the K-major copies of the fusion block's weights (backward pass) in the same launch: 6 MB of traffic that cost a
       // launch of its own 7 - 9 us at the head of the loss chain (side stream, the longer of the two chains beside the fusion block)
       // or, at B >= 128, 15 us with its gap on the main stream.  MMDA_WT_MERGE=0: on the first fork as before.
-      static const int wt_merge = getenv("MMDA_WT_MERGE") ? atoi(getenv("MMDA_WT_MERGE")) : 1;
+      static const int wt_merge = mmda_env_int("MMDA_WT_MERGE", 1);
       std::vector<mmda_transpose_job> tj;
       if (want_wT && wt_merge) weight_transpose_jobs(m, tj);
       if (tj.size() > 20) tj.clear();
@@ -988,11 +967,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     }
   }
   if (x.rc) return x.rc;
-  if (merged) {
-    // (done by the merged launch above)
-  } else if (bfg) {
-    x.rc = first_converts(true, !inf && !late_t, stream);
-  } else {
+  if (!bfg) {
     // embedding rows (models.py:201)
     x.rc = mmda_embed_gather(PP(m->embed), t_ids, R, c.d_t, WS(m->mod[0].x), stream);
   }
@@ -1026,26 +1001,6 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
       if (hipStreamWaitEvent((hipStream_t)stream, m->ev_pack, 0) != hipSuccess) x.rc = MMDA_ELAUNCH;
     }
     if (x.rc) return x.rc;
-    if (late_t) {
-      // Side stream, beside this layer's recurrent kernel (which leaves ~145 CUs idle), joined at the end of forward():
-      //   layer 1: W_ih^T of both layers (dX) and the layer-1 inputs transposed (dW_ih)
-      //   layer 2: its inputs transposed (dW_ih) and hseq^T of layer 1 (dW_hh)
-      // A join costs the main stream ~10 us however early the side stream finished, so only work that an existing join covers
-      // is moved there.
-      void* ss = nullptr;
-      x.rc = side_fork(m, stream, &ss);
-      if (!x.rc && l == 0) x.rc = first_converts(false, true, ss);
-      if (!x.rc && l == 1) {
-        mmda_convert_job cj[6];
-        for (int i = 0; i < 3; ++i) {
-          Mod& md = m->mod[i];
-          cj[i] = mmda_convert_job{WS(md.hseq[0]), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[0].hbT), ldR};
-          cj[3 + i] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), ldR};
-        }
-        x.rc = mmda_convert_bf16(cj, 6, ss);
-      }
-      if (x.rc) return x.rc;
-    }
     ev_rec(m, m->ev_fwd, l, 0, stream);
     x.rc = mmda_lstm_fwd(mode, 3, desc, B, T, lengths, stream);
     ev_rec(m, m->ev_fwd, l, 1, stream);
@@ -1064,7 +1019,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
         for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(m->mod[i].rnn[1].xb); ln[i].ld_bf16 = m->mod[i].rnn[1].ldD; }
       // ... and ONLY as that copy where nothing reads the fp32 output: an evaluation pass, or a training step whose layer-2 weight
       // gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
-      if (bfg && (inf || (m->tn_wgrad & 2)))
+      if (bfg && (inf || m->tn_wgrad))
         for (int i = 0; i < 3; ++i) ln[i].y = nullptr;
       x.rc = mmda_layernorm_fwd_multi(ln, 3, stream);
     } else if (!x.rc && !m->eager_losses && ((bfg && !inf) || m->zero_grad_pending || m->wT_pending)) {
@@ -1102,15 +1057,13 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     sk_launch(x, g, 4);
     // The row-local stretches as one launch each (fused_rows.hip): recon + qkv -> attention -> out-proj -> LayerNorm 1, and
     // LayerNorm 2 -> heads.  MMDA_ROW_FUSE=0: the launches they replace (4 and 3).
-    static const int row_fuse_on = getenv("MMDA_ROW_FUSE") ? atoi(getenv("MMDA_ROW_FUSE")) : 1;
+    static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
     const bool row_fuse = row_fuse_on && c.use_cmd_sim && hs == 128 && NHEAD == 2;
     // loss seeds by the stretches (see mmda_misa::emo_eager); MMDA_LOSS_SEEDS=0: by the loss launch behind the forward pass, as before
-    static const int loss_seeds_on = getenv("MMDA_LOSS_SEEDS") ? atoi(getenv("MMDA_LOSS_SEEDS")) : 1;
+    static const int loss_seeds_on = mmda_env_int("MMDA_LOSS_SEEDS", 1);
     m->seed_recon = (loss_seeds_on && row_fuse && m->eager_losses && m->emo_eager) ? 1 : 0;
     m->seed_cls = (m->seed_recon && !c.use_confidNet) ? 1 : 0;
     if (!x.rc) x.rc = eager_side_losses(m, stream, bfg && !inf);
-    static const int fuse_nb_env = getenv("MMDA_ROW_FUSE_NB") ? atoi(getenv("MMDA_ROW_FUSE_NB")) : 1;      // samples per workgroup (B=32: 0.722 ms with 2, 0.712 with 1; B=256 equal)
-    const int fuse_nb = ((B % 2) == 0 && fuse_nb_env == 2) ? 2 : 1;
     mmda_ln_args l1 = {};
     l1.rows = 6 * B; l1.n = hs; l1.x = WS(m->x6); l1.res = WS(m->attn_out); l1.gamma = PP(m->n1_w); l1.beta = PP(m->n1_b);
     l1.y = WS(m->x1); l1.mean = WS(m->ln1_mean); l1.rstd = WS(m->ln1_rstd); l1.drop_p = p_tf; l1.drop_seed = seed;
@@ -1118,7 +1071,8 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     if (row_fuse) {
       if (!x.rc) {
         FusedFwdA f = {};
-        f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = fuse_nb; f.x6 = WS(m->x6);
+        // one sample per workgroup in every stretch (two measured B=32 0.722 ms against 0.712; B=256 equal)
+        f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1; f.x6 = WS(m->x6);
         f.rec_w = PP(m->rec_w); f.rec_b = PP(m->rec_b); f.recon = WS(m->recon);
         f.in_w = PP(m->in_w); f.in_b = PP(m->in_b); f.qkv = WS(m->qkv);
         f.ctx = WS(m->ctx); f.probs = WS(m->probs); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
@@ -1153,7 +1107,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
       if (!x.rc) x.rc = mmda_layernorm_fwd(&l1, stream);
     }
     // feed-forward pair: one launch split over the hidden units (fused_rows.hip), its partial products summed by the stretch behind it
-    static const int ffn_fuse_on = getenv("MMDA_FFN_FUSE") ? atoi(getenv("MMDA_FFN_FUSE")) : 1;
+    static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
     const bool ffn_fuse = row_fuse && ffn_fuse_on && !m->fusion_fp8 && (FFN % 32) == 0;
     if (m->fusion_fp8) {
       if (!x.rc) x.rc = ffn_fp8(m, p_tf, seed, stream);
@@ -1178,7 +1132,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     if (row_fuse) {
       if (!x.rc) {
         FusedFwdC f = {};
-        f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = fuse_nb; f.ln2 = l2;
+        f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1; f.ln2 = l2;
         if (ffn_fuse) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(m->l2_b); f.f2 = WS(m->f2); }
         f.hfused = WS(m->hfused); f.head_w = PP(m->head_w); f.head_b = PP(m->head_b); f.logits = WS(m->logits);
         f.threshold = c.threshold; f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.labels = WS(m->labels);
@@ -1357,11 +1311,9 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     const bool wt = m->wT_valid != 0;                   // K-major weight copies from this step's forward (side stream, joined there)
     // The row-local stretches as one launch each (fused_rows.hip): heads' sigmoid' -> d_hfused -> LayerNorm 2, and LayerNorm 1 ->
     // ... -> the projection LayerNorms.  MMDA_ROW_FUSE=0: the launches they replace (3 and 6).
-    static const int row_fuse_on = getenv("MMDA_ROW_FUSE") ? atoi(getenv("MMDA_ROW_FUSE")) : 1;
+    static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
     const bool row_fuse = row_fuse_on && wt && c.use_cmd_sim && hs == 128 && NHEAD == 2;
     if (m->fj1 && !row_fuse) { x.rc = flag_join_fallback(m, stream); m->fj1 = 0; if (x.rc) return x.rc; }     // (no kernel here waits on the device)
-    static const int fuse_nb_env = getenv("MMDA_ROW_FUSE_NB") ? atoi(getenv("MMDA_ROW_FUSE_NB")) : 1;      // samples per workgroup (B=32: 0.722 ms with 2, 0.712 with 1; B=256 equal)
-    const int fuse_nb = ((B % 2) == 0 && fuse_nb_env == 2) ? 2 : 1;
     mmda_ln_bwd_args l2a = {};
     l2a.rows = 6 * B; l2a.n = hs; l2a.dy = WS(m->d_hfused); l2a.x = WS(m->x1); l2a.res = WS(m->f2); l2a.gamma = PP(m->n2_w);
     l2a.mean = WS(m->ln2_mean); l2a.rstd = WS(m->ln2_rstd); l2a.d_x = WS(m->d_x1); l2a.d_res = WS(m->d_f2);
@@ -1369,15 +1321,15 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     l2a.permute_S = S6; l2a.permute_B = B;
     if (row_fuse) {
       FusedBwdC f = {};
-      f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = fuse_nb;
+      f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1;
       f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.d_tcp = WS(m->d_tcp); f.d_scores = WS(m->d_scores); f.d_logits = WS(m->d_logits);
       // flag join pending: d_tcp is all zeros (no ConfidNet gradients in that mode), but cleared by the side stream's chain, which
       // this launch does not wait for -- NULL reads as zero
       if (m->fj1) f.d_tcp = nullptr;
       // the reconstruction term of stretch A's d_x6 chain, in workgroups of this launch (small batches: both sets fit the chip twice
       // over; MMDA_FUSED_SPLIT=0: inside stretch A as before)
-      static const int fsplit = getenv("MMDA_FUSED_SPLIT") ? atoi(getenv("MMDA_FUSED_SPLIT")) : 1;
-      rec_hoisted = fsplit && m->rec_part >= 0 && ceil_div(B, fuse_nb) <= 64;
+      static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
+      rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
       if (rec_hoisted) { f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.rec_part = WS(m->rec_part); }
       f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(m->head_w); f.d_hfused = WS(m->d_hfused); f.ln2 = l2a;
       f.pg_parts = WS(m->pg_parts);
@@ -1393,7 +1345,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     lin_dw(x, fmode, B, NC, 6 * hs, WS(m->d_logits), WS(m->hfused), GG(m->head_w), GG(m->head_b));
     // FFN
     // d f1 = (d f2 W2) * [f1 > 0] / (1-p): f1 is stored post-relu, post-dropout, so f1 > 0 <=> kept and pre-activation > 0
-    static const int ffn_fuse_on = getenv("MMDA_FFN_FUSE") ? atoi(getenv("MMDA_FFN_FUSE")) : 1;
+    static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
     const bool ffn_fuse = row_fuse && ffn_fuse_on && (FFN % 32) == 0;
     if (ffn_fuse) {
       if (!x.rc) {
@@ -1417,7 +1369,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     // norm1 + self-attention ... projection LayerNorms
     if (row_fuse && !x.rc) {
       FusedBwdA f = {};
-      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = fuse_nb;
+      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1;
       if (ffn_fuse) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.d_x1 = WS(m->d_x1); }
       mmda_ln_bwd_args& l = f.ln1;
       l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
@@ -1441,7 +1393,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
         // Waiting workgroups hold their CU's LDS (104 KB each): with one on every CU the side stream's kernels could not start, and
         // the wait would never end -- on the device only while the stretch leaves most of the chip free; otherwise the event, here
         // (two launches later than the end of the forward pass, where it used to be: the loss chain is the longer one at large B)
-        if (ceil_div(B, fuse_nb) <= 64) { f.wait_flag = m->jflags; f.wait_value = m->jval[0]; f.wait_err = m->jflags + 2; }
+        if (B <= 64) { f.wait_flag = m->jflags; f.wait_value = m->jval[0]; f.wait_err = m->jflags + 2; }
         else x.rc = flag_join_fallback(m, stream);
         m->fj1 = 0;
       }
@@ -1647,7 +1599,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     }
     if (!x.rc && B <= SKINNY_MAX_B) x.rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, ss);
     // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
-    static const int sort_early = getenv("MMDA_SORT_EARLY") ? atoi(getenv("MMDA_SORT_EARLY")) : 1;
+    static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
     m->esort_valid = 0;
     if (!x.rc && sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(R)) {
       x.rc = mmda_embed_sort_ids(t_ids, R, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
@@ -1672,30 +1624,16 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
       const int nj = backward_only_jobs(m, cj);
       x.rc = mmda_convert_bf16(cj, nj, ss);
     }
-    // Experiment, OFF by default (MMDA_ADAM_EMBED_SPLIT=1): clip + Adam of the embedding rows this batch does NOT touch, here, beside
-    // the layer-2 recurrence (the side stream is idle for ~100 us behind the GEMMs above).  Their gradient is zero whatever the rest of
-    // the backward pass does (the bucket was cleared during the forward pass, the scatter at the end adds into the touched rows only),
-    // and torch's dense Adam moves them by their momentum all the same: 6 of the 10.8 M parameters would leave the tail of the step
-    // (-32 us).  Measured at B=32: the 170 MB it streams beside the recurrence slow that kernel's hand-offs by 24 us (0.071 -> 0.095 ms)
-    // and the step ends up 14 us LONGER (0.769 -> 0.783 ms); behind the early optimizer pass beside the layer-1 recurrence instead, the
-    // side stream becomes the longer of the two and the join waits (0.766 -> 0.834 ms).
-    static const int embed_split = getenv("MMDA_ADAM_EMBED_SPLIT") ? atoi(getenv("MMDA_ADAM_EMBED_SPLIT")) : 0;
-    if (!x.rc && m->adam_early_on && embed_split == 1 && m->use_side && m->M1 && m->V1 && m->embed + (int64_t)c.vocab * c.d_t == m->flat) {
-      unsigned char* mask = reinterpret_cast<unsigned char*>(WS(m->touched));
-      x.rc = mmda_mark_rows(mask, c.vocab, t_ids, R, ss);
-      if (!x.rc) x.rc = mmda_clamp_adam_rows(PP(m->embed), GG(m->embed), m->M1 + m->embed, m->V1 + m->embed, c.vocab, c.d_t, mask, 0,
-                                             m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
-      if (!x.rc) m->embed_early_done = 1;
-    }
+    // (Clip + Adam of the embedding rows this batch does not touch, here beside the layer-2 recurrence, measured slower: at B=32 its
+    // 170 MB stream slows the recurrence's hand-offs and the step by 14 us; behind the early optimizer pass, by 68 us.)
   }
   if (x.rc) return x.rc;
   // encoders, top layer first
   const float* xin[3] = {WS(m->mod[0].x), v, a};
-  // Layer 2's weight-gradient GEMMs run beside the layer-1 recurrent kernel on the side stream (MMDA_DW_OVERLAP=0: held back and
-  // issued with layer 1's in one grouped launch after it).  The wave-autonomous recurrence runs one wave on each of ~110 CUs,
+  // Layer 2's weight-gradient GEMMs run beside the layer-1 recurrent kernel on the side stream (faster than holding them back for
+  // one grouped launch with layer 1's after it).  The wave-autonomous recurrence runs one wave on each of ~110 CUs,
   // raises its priority and reserves those CUs' whole LDS, so the GEMM's workgroups land on the other ~145 CUs; what the two still
   // share is L2 and fabric bandwidth (the recurrence slows by ~30 us, the GEMMs' ~65 us leave the critical path).
-  static const int dw_overlap = getenv("MMDA_DW_OVERLAP") ? atoi(getenv("MMDA_DW_OVERLAP")) : 1;
   std::vector<mmda_gemm_bf16_args> bside;
   for (int l = 1; l >= 0; --l) {
     mmda_lstm_desc desc[3];
@@ -1738,9 +1676,9 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
                                 m->ldR};
       if (kdg) { dgj[i].src = WS(r.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
     }
-    const bool tn = bfg && ((m->tn_wgrad >> l) & 1);   // weight gradients straight from dG / inputs / hseq as they lie (no dG^T)
+    const bool tn = bfg && m->tn_wgrad;   // weight gradients straight from dG / inputs / hseq as they lie (no dG^T)
     if (tn && !kdg) return MMDA_EINVAL;                // (forward() set tn_wgrad only where the recurrent kernel writes bf16 dG)
-    const bool dg_on_side = bfg && kdg && l == 1 && dw_overlap && m->use_side && !tn;
+    const bool dg_on_side = bfg && kdg && l == 1 && m->use_side && !tn;
     if (bfg && !dg_on_side && !tn) {
       x.rc = mmda_convert_bf16(dgj, 3, stream);
       if (x.rc) return x.rc;
@@ -1811,7 +1749,6 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     }
     group_end(x);
     x.deferring = false;
-    if (l == 0 && !dw_overlap) { bmain.insert(bmain.end(), bside.begin(), bside.end()); bside.clear(); }
     if (!x.rc && !bmain.empty()) x.rc = mmda_gemm_bf16_grouped(bmain.data(), (int)bmain.size(), stream);
     if (l == 1 && !x.rc) {
       // the inter-layer LayerNorm backward gives d(hseq of layer 1): input gradients on the main stream (they feed the next
@@ -1841,7 +1778,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
       if (!x.rc && dg_on_side) x.rc = mmda_convert_bf16(dgj, 3, ss);
       if (!x.rc) x.rc = ln_split ? mmda_ln_parts_finish(lb, 3, WS(m->ln_parts), ss) : mmda_layernorm_param_grads(lb, 3, ss);
       if (!x.rc && !x.deferred.empty()) x.rc = mmda_gemm_grouped(x.deferred.data(), (int)x.deferred.size(), ss);
-      const bool l2_early = !bside.empty() && dw_overlap;
+      const bool l2_early = !bside.empty();
       if (!x.rc && l2_early) { x.rc = mmda_gemm_bf16_grouped(bside.data(), (int)bside.size(), ss); bside.clear(); }
       x.deferred.clear();
       // Everything issued so far on either stream is final for the fusion block, the LayerNorms and -- when its weight-gradient
@@ -1859,15 +1796,6 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
         if (!x.rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
           x.rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
           if (!x.rc) m->adam_early_done = m->early_floats;
-          // (MMDA_ADAM_EMBED_SPLIT=2: the untouched embedding rows behind it, i.e. beside the tail GEMMs rather than a recurrence)
-          static const int embed_split2 = getenv("MMDA_ADAM_EMBED_SPLIT") ? atoi(getenv("MMDA_ADAM_EMBED_SPLIT")) : 0;
-          if (!x.rc && embed_split2 == 2 && m->use_side && m->embed + (int64_t)c.vocab * c.d_t == m->flat) {
-            unsigned char* mask = reinterpret_cast<unsigned char*>(WS(m->touched));
-            x.rc = mmda_mark_rows(mask, c.vocab, t_ids, R, ss);
-            if (!x.rc) x.rc = mmda_clamp_adam_rows(PP(m->embed), GG(m->embed), m->M1 + m->embed, m->V1 + m->embed, c.vocab, c.d_t, mask, 0,
-                                                   m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
-            if (!x.rc) m->embed_early_done = 1;
-          }
         }
       }
     } else if (!x.rc) {
@@ -1971,7 +1899,7 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   m->zero_grad_pending = m->T > 0 ? 1 : 0;
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
-  static const int flag_join_on = getenv("MMDA_FLAG_JOIN") ? atoi(getenv("MMDA_FLAG_JOIN")) : 1;
+  static const int flag_join_on = mmda_env_int("MMDA_FLAG_JOIN", 1);
   m->flag_join_ok = (flag_join_on && m->use_side) ? 1 : 0; m->fj1 = m->fj2 = 0;
   int rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
   if (rc) return rc;
@@ -1981,9 +1909,8 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   if (m->zero_grad_pending) return MMDA_ELAUNCH;        // forward() always reaches its fusion block
   rc = mmda_misa_losses(m, emo, 1, stream);
   if (rc) return rc;
-  static const int adam_split = getenv("MMDA_ADAM_SPLIT") ? atoi(getenv("MMDA_ADAM_SPLIT")) : 1;     // 0: ablation (one launch at the end)
-  m->adam_early_on = (do_adam && adam_split) ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
-  m->embed_early_done = 0;
+  // (the early optimizer pass beside the layer-1 recurrence: faster than one launch for the whole bucket at the end)
+  m->adam_early_on = do_adam ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
   rc = mmda_misa_backward(m, t_ids, v, a, lengths, stream);
   m->adam_early_on = 0; m->flag_join_ok = 0;
   if (rc) return rc;
@@ -1992,15 +1919,11 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   if (do_adam) {
     // the rest of the bucket (layer-1 recurrent layers, embedding -- or everything, if the backward pass stepped nothing early)
     const int64_t o = m->adam_early_done;
-    const int64_t end = m->embed_early_done ? m->embed : m->flat;
     // (flag join: this launch does not complete before the side stream's weight-gradient GEMMs and early optimizer pass have)
     const bool fj = m->fj2 != 0;
     m->fj2 = 0;
-    rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, end - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
+    rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, m->flat - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
                               fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr, stream);
-    if (!rc && m->embed_early_done)          // the rows of this batch (their gradient has just been scattered)
-      rc = mmda_clamp_adam_rows(m->P + m->embed, m->G + m->embed, m->M1 + m->embed, m->V1 + m->embed, m->cfg.vocab, m->cfg.d_t,
-                                reinterpret_cast<const unsigned char*>(m->ws + m->touched), 1, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step, stream);
   }
   return rc;
 }

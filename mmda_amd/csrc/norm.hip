@@ -1,7 +1,6 @@
 // Row-wise kernels: LayerNorm forward/backward (wave-per-row shuffle reductions), embedding gather / scatter-add,
 // small elementwise helpers.  All HBM-bound; loads are lane-consecutive (coalesced 256 B per wave instruction).
 #include "common.h"
-#include <stdlib.h>
 #include "rowlocal.h"
 #include "splitk.h"
 
@@ -510,8 +509,7 @@ extern "C" int mmda_layernorm_fwd_multi(const mmda_ln_args* a, int n, void* stre
             ((((uintptr_t)q.x | (uintptr_t)q.y | (uintptr_t)q.gamma | (uintptr_t)q.beta) & (4 * vw - 1)) == 0) &&      // (a NULL y is aligned)
             (!q.y_bf16 || ((q.ld_bf16 & 7) == 0 && ((uintptr_t)q.y_bf16 & 7) == 0 && ceil_div(q.ld_bf16, vw * 64) <= LNV_MAX));
     }
-    static const int ln_vec_on = getenv("MMDA_LN_VEC") ? atoi(getenv("MMDA_LN_VEC")) : 1;
-    if (vec && ln_vec_on) {
+    if (vec) {
       int nv = 1;                                        // groups per lane: the widest problem in ITS group size (bf16 copy included)
       for (int k = 0; k < L.n; ++k) {
         const int vw = (L.a[k].n & 3) ? 2 : 4;
@@ -580,8 +578,7 @@ bool ln_bwd_vec_applies(const mmda_ln_bwd_args& q) {
 int ln_parts_blocks(const mmda_ln_bwd_args& q) { int nb = ceil_div(q.rows, 16); return nb > 512 ? 512 : (nb < 1 ? 1 : nb); }
 }  // namespace
 bool mmda_ln_bwd_parts_applies(const mmda_ln_bwd_args* a, int n) {
-  static const int ln_vec_on = getenv("MMDA_LN_VEC") ? atoi(getenv("MMDA_LN_VEC")) : 1;
-  if (!ln_vec_on || !a || n <= 0 || n > LN_MAXP) return false;
+  if (!a || n <= 0 || n > LN_MAXP) return false;
   for (int i = 0; i < n; ++i)
     if (ln_bwd_check(a + i) || !ln_bwd_vec_applies(a[i])) return false;
   return true;
@@ -661,16 +658,14 @@ extern "C" int mmda_embed_scatter_add(float* dW, const int64_t* ids, int rows, i
   if (!dW || !ids || !dX || rows < 0 || dim <= 0 || dim > 1024) return MMDA_EINVAL;
   if (rows == 0) return MMDA_OK;
   // long lists: sort-based list-order sums (dist.hip) -- the scan below costs rows^2 / 256 id compares (B=256, T=50: 158 us against
-  // 9 us at B=32).  MMDA_SCATTER_SORT_MIN moves the limit.
+  // 9 us at B=32).
   return mmda_embed_scatter_add_masked(dW, ids, rows, dim, dX, nullptr, 0, stream);
 }
 
 // (internal) lists of this length take the sort-based form
-bool mmda_embed_scatter_sorts(int rows) {
-  static const int sort_min_env = getenv("MMDA_SCATTER_SORT_MIN") ? atoi(getenv("MMDA_SCATTER_SORT_MIN")) : 3072;
-  const int sort_min = sort_min_env > ES_MAX ? ES_MAX + 1 : sort_min_env;
-  return rows >= sort_min;
-}
+constexpr int ES_SORT_MIN = 3072;
+static_assert(ES_SORT_MIN <= ES_MAX, "the scan form holds at most ES_MAX positions");
+bool mmda_embed_scatter_sorts(int rows) { return rows >= ES_SORT_MIN; }
 // (internal, misa.hip) the same with the batch's lengths: positions p = t * B + b with t >= lengths[b] are padding and are skipped
 int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream) {
   if (!dW || !ids || !dX || rows < 0 || dim <= 0 || dim > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
