@@ -47,6 +47,26 @@ struct Mod {           // one modality: two stacked biLSTMs with a LayerNorm bet
   int64_t x, gates[2], c[2], hseq[2], normed, ln_mean, ln_rstd, utt, d_utt, d_hseq1, d_normed, d_x, xchg, xchg_floats;
 };
 
+// Every choice of a form of the training step, made once per step by plan_step() at the start of mmda_misa_forward() and read by every
+// part of the step.  What a launch's outcome sets or what is consumed later (wT_valid, side_pending, fj1, ...) stays in mmda_misa.
+struct StepPlan {
+  bool inf = false;                 // evaluation pass: no backward follows -- no stash, no copies that only the backward pass reads
+  bool bfg = false;                 // bf16 mode with bf16 operand copies: the LSTM-sized GEMMs read them (gemm_bf16.hip)
+  int gm = 0;                       // gate-minor layout of `gates` (see mmda_lstm_desc.gate_minor)
+  bool kdg = false;                 // the backward recurrence writes the gate gradients as bf16, and only so
+  bool tn_wgrad = false;            // the weight-gradient GEMMs read dG / inputs / hseq as they lie (tn form): no transposed copies
+  bool want_b = false, want_c = false;     // W_hh packings made: for the streaming / the resident-weights backward kernels
+  bool want_wT = false, wT_merge = false;  // K-major fusion-weight copies (row-skinny backward); made in the step's first launch
+  bool skinny = false;              // fusion block on row-skinny GEMMs (B <= SKINNY_MAX_B), else on the tiled generic kernel
+  bool row_fuse = false;            // ... as fused row-local stretches (the backward pass also needs wT_valid)
+  bool ffn_fuse_fwd = false, ffn_fuse_bwd = false;   // the feed-forward pair fused (forward / backward differ: see plan_step)
+  bool seed_recon = false, seed_cls = false;         // the forward stretches store these loss seeds (see mmda_misa::emo_eager)
+  bool fj_on = false, fj_fwd = false, fj_device = false;   // flag joins; the forward one; ... waited for on the device
+  bool zg_here = false;             // the gradient bucket is cleared at the head of the loss chain (eager_side_losses)
+  bool rec_hoisted = false;         // stretch C's launch makes d_recon W_rec for stretch A
+  bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
+};
+
 enum { SITE_ATTN = 1, SITE_DROP1 = 2, SITE_FFN = 3, SITE_DROP2 = 4, SITE_CLS = 5, SITE_DISC = 6,
        SITE_RRELU = 7 /* .. 9: the three projections' random slopes */, SITE_RRELU_DISC = 10 };
 constexpr int FFN = 2048, NHEAD = 2, S6 = 6;
@@ -62,6 +82,7 @@ struct mmda_misa {
   hipEvent_t ev_early = nullptr;             // recorded by backward() when the gradients of the bucket prefix are final
   int64_t early_floats = 0; int early_valid = 0;
   Mod mod[3];
+  StepPlan plan;                             // the decisions of the step in flight (plan_step); its state is below
   // fusion parameter offsets
   int64_t priv_w, priv_b, sh_w, sh_b, rec_w, rec_b, d1_w = -1, d1_b = -1, d2_w = -1, d2_b = -1, sp_w, sp_b;
   int64_t head_w, head_b, embed;
@@ -85,7 +106,6 @@ struct mmda_misa {
   // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
   // recurrence runs there, on the side stream (set by mmda_misa_train_step around its backward pass)
   int adam_early_on = 0; float ae_lr = 0.f, ae_clip = 0.f; int ae_step = 0; int64_t adam_early_done = 0;
-  bool tn_wgrad = false;           // the weight-gradient GEMMs read dG / inputs / hseq as they lie (tn form): no transposed copies
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
   int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
@@ -95,16 +115,14 @@ struct mmda_misa {
   unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_cluster.hip)
   hipStream_t side = nullptr;      // second stream for weight-gradient GEMMs (created lazily; no device memory)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pack = nullptr;
-  int pack_b_valid = 0;            // the streaming backward packing of W_hh was made by the last forward
   int side_pending = 0, use_side = 1;
-  int use_cluster = 1, packed_c_valid = 0;
+  int use_cluster = 1;
   int use_bf16_gemm = 1;           // bf16 mode: LSTM-sized GEMMs read bf16 operand copies (gemm_bf16.hip)
-  int gate_minor = 0;              // layout of `gates` chosen by the last forward (see mmda_lstm_desc.gate_minor)
-  int inference = 0, last_fwd_inference = 0;   // evaluation passes: no stash, no copies that only the backward pass reads
+  int inference = 0;               // evaluation passes: no stash, no copies that only the backward pass reads
   int zero_grad_pending = 0;       // train_step: the gradient bucket is cleared inside forward(), beside the fusion block
   // train_step: the losses that read only the private/shared representations (diff, CMD) are issued by forward() on the side
   // stream as soon as those exist, beside the transformer layer and the heads; mmda_misa_losses() then adds the rest
-  int eager_losses = 0, eager_done = 0;
+  int eager_losses = 0, eager_done = 0;      // eager_done: that chain, and any loss seeds, not yet taken up by mmda_misa_losses
   // Data-parallel "global statistics" mode (mmda_misa_set_external_batch_losses): the batch-statistic losses -- DiffLoss, CMD and the
   // confidence loss -- were computed by the caller on the batch of ALL ranks (all-gathered inputs, the same loss entry points), their
   // sums written into losses[1], [2], [4] and their gradient rows of THIS rank added into d_x6 / d_scores / d_tcp behind
@@ -116,7 +134,6 @@ struct mmda_misa {
   // leaves the critical path between the forward and the backward pass (14 us at B=32): it runs on the side stream beside the
   // layer-2 backward recurrence.  Values are bit-identical to the loss launch's (same expressions on the same operands).
   const float* emo_eager = nullptr;          // labels of the step in flight (train_step)
-  int seed_recon = 0, seed_cls = 0;          // this step's forward wrote those seeds
   const float* misc_deferred = nullptr;      // labels: the loss-value launch is still to be issued (backward's first side fork)
   // Flag joins (training step; common.h: flag_wait): where the main stream needs a side-stream chain's results, the consuming KERNEL
   // waits on the device for a word that a one-thread launch behind the chain sets, instead of the stream waiting for an event -- an
@@ -132,7 +149,7 @@ struct mmda_misa {
   // GEMM and the optimizer); word [3] tells the main stream it is there (a one-wave wait launch in front of the sums).
   int64_t esort = -1; int esort_valid = 0; unsigned esort_val = 0u;
   int64_t rec_part = -1;
-  int flag_join_ok = 0, fj1 = 0, fj2 = 0, fj1_armed = 0;
+  int fj1 = 0, fj2 = 0, fj1_armed = 0;
   int ldR = 0;
   // cluster-exchange regions: at the front of the workspace, sized by B alone, so a change of T (every batch under the reference's
   // collate) neither moves nor clears them -- flags are monotonic epochs.  Cleared (on the caller's stream) only when the buffer
@@ -439,6 +456,11 @@ mmda_skinny_args sk_dx(int M, int N, int K, const float* dy, int lddy, const flo
   g.M = M; g.N = K; g.K = N; g.transB = 1; g.A = dy; g.lda = lddy; g.B = WT; g.ldb = N; g.C = dx; g.ldc = lddx; g.accumulate = acc;
   return g;
 }
+// ... through WT where this step made the K-major copy (wt), else through W as it lies
+mmda_skinny_args sk_dxw(bool wt, int M, int N, int K, const float* dy, int lddy, const float* WT, const float* W, float* dx, int lddx,
+                        int acc) {
+  return wt ? sk_dx(M, N, K, dy, lddy, WT, dx, lddx, acc) : sk_nn(M, N, K, dy, lddy, W, dx, lddx, acc);
+}
 void sk_launch(Ctx& c, const mmda_skinny_args* p, int n) {
   if (!c.rc) c.rc = mmda_gemm_skinny(p, n, c.s);
 }
@@ -562,6 +584,92 @@ mmda_act_params act_params(mmda_misa* m, int training, uint64_t seed, int site, 
 int check_ready(const mmda_misa* m) {
   if (!m || !m->P || !m->ws) return MMDA_EINVAL;
   return MMDA_OK;
+}
+
+// recurrent descriptor of modality i, layer l: forward (W_hh packed for the forward kernels, utt) or backward (streaming backward
+// packing, the resident-weights one where `with_c`, d_utt, d(hseq of layer 1))
+mmda_lstm_desc lstm_desc(mmda_misa* m, int i, int l, bool bwd, int gate_minor, bool with_c) {
+  Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+  const int64_t* wp = bwd ? r.pack_b : r.pack_f;
+  mmda_lstm_desc d = {};
+  d.H = r.H; d.gates = WS(md.gates[l]); d.cstash = WS(md.c[l]); d.hseq = WS(md.hseq[l]);
+  d.wpack[0] = WS(wp[0]); d.wpack[1] = WS(wp[1]);
+  if (with_c) { d.wpack_c[0] = WS(r.pack_c[0]); d.wpack_c[1] = WS(r.pack_c[1]); }
+  d.utt = WS(bwd ? md.d_utt : md.utt); d.layer = l; d.d_hseq = bwd && l == 0 ? WS(md.d_hseq1) : nullptr;
+  d.xchg = (m->use_cluster && md.xchg >= 0) ? (void*)WS(md.xchg) : nullptr; d.epoch_base = m->epoch;
+  d.gate_minor = gate_minor; d.cell = m->cfg.rnncell;
+  return d;
+}
+
+constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
+
+// the decisions of one step (see StepPlan); the switches that select a form of the step are read here only
+StepPlan plan_step(mmda_misa* m) {
+  static const int tn_on = mmda_env_int("MMDA_GEMM_TN", 1);
+  static const int wt_merge = mmda_env_int("MMDA_WT_MERGE", 1);
+  static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
+  static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
+  static const int loss_seeds_on = mmda_env_int("MMDA_LOSS_SEEDS", 1);
+  static const int flag_join_on = mmda_env_int("MMDA_FLAG_JOIN", 1);
+  static const int zg_side = mmda_env_int("MMDA_ZERO_GRAD_SIDE", -1);
+  static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
+  static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
+  const mmda_misa_config& c = m->cfg;
+  const int B = m->B, T = m->T, mode = c.mode;
+  StepPlan P;
+  // which recurrent kernels will run: decides the packings of W_hh that are made and the layout of `gates`
+  auto probe_resident = [&](int gate_minor, int backward) -> bool {
+    if (T <= 0 || mode != MMDA_BF16) return false;
+    mmda_lstm_desc probe[3];
+    for (int i = 0; i < 3; ++i) probe[i] = lstm_desc(m, i, 0, false, gate_minor, true);
+    if (backward == 2) return mmda_lstm_bwd_emits_dg_bf16(mode, 3, probe, B, T) != 0;      // ... and writes the gate gradients as bf16
+    return mmda_lstm_resident_applicable(mode, 3, probe, B, T, backward) != 0;
+  };
+  P.inf = m->inference != 0;
+  P.bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
+  // Gate-minor layout of the pre-activations / stash / gate gradients ([dir][unit][gate], 16-byte accesses in the recurrent
+  // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
+  // GEMM epilogues) AND the resident-weights kernels will run, forward and backward.
+  if (P.bfg && (B % 8) == 0 && T > 0) P.gm = probe_resident(1, 0) && probe_resident(1, 1);
+  // The backward probe with the backward pass's own descriptors gives the same answer: they differ from these only in pointers
+  // (pack_b, d_utt, d_hseq) and in wpack_c, which the backward pass sets because want_c holds -- bf16, resident, training -- and
+  // without which probe_resident(1, 2) fails anyway (no exchange buffers without use_cluster).
+  P.kdg = !P.inf && P.bfg && P.gm && probe_resident(1, 2);
+  // Weight gradients in the tn form of the bf16 GEMM (dW = dG^T X on row-major dG, X, hseq): the transposed copies of the inputs, of
+  // hseq and of the gate gradients are not made at all (B=256: 0.33 ms of conversions per step).  Needs the gate gradients as bf16
+  // from the recurrent kernel (gate-minor resident path).  Up to T*B = 4096 rows: measured (step, ms) B=32 0.759 -> 0.745, B=64 0.928 ->
+  // 0.917, but B=128 1.362 -> 1.391, B=256 2.39 -> 2.55, T=500 4.06 -> 4.08 -- in isolation the tn kernel matches the nt one at K = 1600
+  // and runs 15 - 20 % slower at K = 12800 (twice the LDS read instructions per k-tile), which at large batches outweighs the
+  // conversions it saves.  Round 3: the LDS-DMA pipelined GEMM (gemm_bf16_dma_kernel) runs the tn form at K = 12800 as fast as the nt
+  // form, so both layers take it at every size (B=256: the 0.47 ms of transposing conversions per step with it; a row limit, with or
+  // without layer 1 alone in the tn form beyond it, measured slower).  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere.
+  P.tn_wgrad = P.kdg && tn_on;
+  // The forward packing always; the resident-weights backward packing when those kernels will run the backward pass and the
+  // streaming backward packing only when they will not; neither for an evaluation pass.
+  P.want_c = !P.inf && m->use_cluster && mode == MMDA_BF16;
+  P.want_b = !P.inf && !(P.want_c && probe_resident(0, 1));
+  P.skinny = B <= SKINNY_MAX_B;
+  P.want_wT = P.skinny && !P.inf;
+  P.wT_merge = P.bfg && P.want_wT && wt_merge;
+  // The row-local stretches as one launch each (fused_rows.hip): recon + qkv -> attention -> out-proj -> LayerNorm 1, and LayerNorm 2
+  // -> heads; backward: heads' sigmoid' -> d_hfused -> LayerNorm 2, and LayerNorm 1 -> ... -> the projection LayerNorms.
+  // MMDA_ROW_FUSE=0: the launches they replace (4 and 3 forward, 3 and 6 backward).
+  P.row_fuse = P.skinny && row_fuse_on && c.use_cmd_sim && c.hidden == 128 && NHEAD == 2;
+  // The feed-forward pair as one launch split over the hidden units.  The fp8 forward (fusion_fp8) has products of its own, but the
+  // backward pass reads the f32 f1 / f2 it writes like the exact path's, so the fused dX kernel serves it as well.
+  P.ffn_fuse_fwd = P.row_fuse && ffn_fuse_on && !m->fusion_fp8 && (FFN % 32) == 0;
+  P.ffn_fuse_bwd = P.row_fuse && ffn_fuse_on && (FFN % 32) == 0;
+  // loss seeds by the stretches (see mmda_misa::emo_eager); MMDA_LOSS_SEEDS=0: by the loss launch behind the forward pass, as before
+  P.seed_recon = loss_seeds_on && P.row_fuse && m->eager_losses && m->emo_eager;
+  P.seed_cls = P.seed_recon && !c.use_confidNet;
+  // flag joins (see mmda_misa::jflags) in a fused training step (train_step sets eager_losses around its forward pass)
+  P.fj_on = flag_join_on && m->use_side && m->eager_losses;
+  P.fj_fwd = P.fj_on && P.seed_recon && P.seed_cls;
+  P.fj_device = P.fj_fwd && B <= FJ_DEVICE_MAX_B;
+  P.zg_here = zg_side >= 0 ? zg_side != 0 : P.fj_device;
+  P.rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
+  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B);
+  return P;
 }
 
 }  // namespace
@@ -746,21 +854,21 @@ int backward_only_jobs(mmda_misa* m, mmda_convert_job* cj) {
     Mod& md = m->mod[i];
     for (int l = 0; l < 2; ++l) {
       Rnn& r = md.rnn[l];
-      if (m->tn_wgrad) {
+      if (m->plan.tn_wgrad) {
         for (int d = 0; d < 2; ++d)
           cj[n++] = mmda_convert_job{WS(md.hseq[l]) + d * md.H, 2 * md.H, R, md.H, nullptr, WS(r.hbp[d]), r.ldH, nullptr, 0};
       } else {
         cj[n++] = mmda_convert_job{WS(md.hseq[l]), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(r.hbT), m->ldR};
       }
     }
-    if (!m->tn_wgrad) cj[n++] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), m->ldR};
+    if (!m->plan.tn_wgrad) cj[n++] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), m->ldR};
   }
   return n;
 }
 
 // side stream, right after x6 = [private x3, shared x3] exists: clear the loss sums and the loss-seeded activation gradients,
 // then DiffLoss and CMD with their gradients (they read x6 only), then the gradient bucket if train_step left that to forward()
-int eager_side_losses(mmda_misa* m, void* stream, bool hseq2_t) {
+int eager_side_losses(mmda_misa* m, void* stream) {
   if (!m->eager_losses) return MMDA_OK;
   const mmda_misa_config& c = m->cfg;
   const int B = m->B, hs = c.hidden;
@@ -769,19 +877,16 @@ int eager_side_losses(mmda_misa* m, void* stream, bool hseq2_t) {
   int rc = side_fork(m, stream, &ss);
   // (large batches: the loss chain on the side stream is the longer one by far -- the weight transposes go to the main stream)
   if (!rc && m->wT_pending) rc = weight_transposes(m, B >= 128 ? stream : ss);
-  (void)hseq2_t;                   // (the backward pass's operand copies are made by backward() itself: backward_only_jobs)
   // (the forward stretches on the main stream STORE the seeds they own: clearing those here would race with them)
-  const int64_t zend = m->seed_cls ? m->zero_cls : m->seed_recon ? m->zero_recon : m->zero_end;
+  const StepPlan& P = m->plan;
+  const int64_t zend = P.seed_cls ? m->zero_cls : P.seed_recon ? m->zero_recon : m->zero_end;
   // The gradient bucket (43 MB, 11 us) is cleared on the MAIN stream behind the fork: since the row-local stretches were fused the
   // side stream's loss chain (72 us at B=32), not the main stream's fusion block (55 us), is what the join at the end of forward() waits
   // for.  (Nothing on either stream touches the bucket before the backward pass; MMDA_ZERO_GRAD_SIDE=1: the old place.)
   // ... unless the main stream will not wait for this chain before the LayerNorm-1 stretch of the backward pass (flag join on the
   // device, small batches: see mmda_misa::jflags) -- the chain then has two launches of slack and the clear comes back here, in ONE
   // launch with the activation-gradient region, at the head of the chain.
-  static const int zg_side = mmda_env_int("MMDA_ZERO_GRAD_SIDE", -1);
-  const bool fj_plan = m->flag_join_ok && m->seed_recon && m->seed_cls && ss != stream && m->jflags;      // (what forward()'s end will decide)
-  const bool zg_here = zg_side >= 0 ? zg_side != 0 : (fj_plan && B <= 64);
-  if (!rc && zg_here && m->zero_grad_pending) {
+  if (!rc && P.zg_here && m->zero_grad_pending) {
     rc = mmda_zero2(WS(m->zero_begin), zend - m->zero_begin, m->G, m->flat, ss);
     m->zero_grad_pending = 0;
   } else if (!rc) {
@@ -791,7 +896,7 @@ int eager_side_losses(mmda_misa* m, void* stream, bool hseq2_t) {
   if (!rc) rc = mmda_loss_diff(WS(m->x6), BH, B, hs, c.diff_weight, L + 1, WS(m->d_x6), WS(m->diff_work), ss);
   // the chain's last launch sets the flag-join word itself where it can (single-workgroup CMD: no one-thread launch behind it)
   m->fj1_armed = 0;
-  if (!rc && c.use_cmd_sim && fj_plan && mmda_loss_cmd_sets_flag(B, hs)) {
+  if (!rc && c.use_cmd_sim && P.fj_fwd && m->jflags && mmda_loss_cmd_sets_flag(B, hs)) {
     mmda_loss_cmd_arm_flag(m->jflags + 0, m->jval[0] + 1);
     m->fj1_armed = 1;
   }
@@ -839,71 +944,84 @@ extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
   return MMDA_OK;
 }
 
-extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
-                                 int training, uint64_t seed, void* stream) {
-  if (check_ready(m) || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
-  const mmda_misa_config& c = m->cfg;
-  const int B = m->B, T = m->T, hs = c.hidden, mode = c.mode, NC = 6 + c.ncls;
-  // The fusion block (projections, private/shared/recon, transformer layer, heads) is 2 % of the FLOPs and feeds the
-  // batch-statistic losses: it always runs on the exact f32 MFMA path.  `mode` (bf16) covers the LSTM GEMMs + recurrences.
-  const int fmode = MMDA_F32;
-  const int R = T * B;
-  Ctx x{m, stream};
-  m->training = training; m->seed = seed;
-  const float p_tf = training ? c.fusion_dropout : 0.f, p_cls = training ? c.dropout : 0.f;
+namespace {
+// One pass of the step in flight, as a sequence of stages: the GEMM context and what every stage reads -- the plan, the
+// configuration, the batch shape and the dropout of the step.  Each stage sets rc and issues nothing once it is set.
+struct Pass : Ctx {
+  const StepPlan& P;
+  const mmda_misa_config& c;
+  const int B, T, R, hs, NC, mode;
+  static constexpr int fmode = MMDA_F32;     // the fusion block's GEMMs: exact path (see mmda_misa_forward)
+  const int64_t BH; const float p_tf, p_cls; const uint64_t seed;
+  Pass(mmda_misa* m_, void* s_)
+      : Ctx{m_, s_}, P(m_->plan), c(m_->cfg), B(m_->B), T(m_->T), R(m_->T * m_->B), hs(c.hidden), NC(6 + c.ncls), mode(c.mode),
+        BH((int64_t)B * hs), p_tf(m_->training ? c.fusion_dropout : 0.f), p_cls(m_->training ? c.dropout : 0.f), seed(m_->seed) {}
+  mmda_ln_args proj_ln_fwd(int i), norm1_fwd(), norm2_fwd();             // LayerNorm arguments (builders below)
+  mmda_ln_bwd_args proj_ln_bwd(int i), norm1_bwd(), norm2_bwd();
+  // forward, in this order: operands, layers 1 and 2, the fusion block in one of two forms
+  void fwd_operands(const int64_t* t_ids, const float* const* xin);
+  void fwd_encoder_layer(int l, const float* const* xin, const int32_t* lengths);
+  void fwd_fusion_skinny(), fwd_fusion_tiled();
+  // backward, in this order: the fusion block's dX chain in one of three forms, its weight gradients, the side chain, layers 2 and 1
+  void bwd_fusion_fused(), bwd_fusion_skinny(), bwd_fusion_tiled(), skinny_ffn_dx(bool wt), skinny_proj_dx(bool wt);
+  void fusion_wgrads(), bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* lengths);
+  void bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_ids, const int32_t* lengths);
+};
 
-  // W_hh -> MFMA fragment order (weights changed since the last step): all twelve matrices in one launch, on the side stream
-  // underneath the embedding gather and the first input GEMM; joined before the first recurrent kernel.
-  if (is_gru(m)) {          // GRU parameters -> four-slot layout (everything below reads the padded copies)
-    mmda_gru_pad_job gj[MMDA_GRU_PAD_MAX];
-    int n = gru_jobs(m, m->P, false, gj);
-    x.rc = mmda_gru_pad_params(gj, n, stream);
-    if (x.rc) return x.rc;
-  }
-  // which recurrent kernels will run: decides the packings of W_hh that are made and the layout of `gates`
-  auto probe_resident = [&](int gate_minor, int backward) -> bool {
-    if (T <= 0 || mode != MMDA_BF16) return false;
-    mmda_lstm_desc probe[3];
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i]; Rnn& r = md.rnn[0];
-      probe[i] = mmda_lstm_desc{};
-      probe[i].H = r.H; probe[i].gates = WS(md.gates[0]); probe[i].cstash = WS(md.c[0]); probe[i].hseq = WS(md.hseq[0]);
-      probe[i].wpack[0] = WS(r.pack_f[0]); probe[i].wpack[1] = WS(r.pack_f[1]);
-      probe[i].wpack_c[0] = WS(r.pack_c[0]); probe[i].wpack_c[1] = WS(r.pack_c[1]); probe[i].utt = WS(md.utt);
-      probe[i].xchg = (m->use_cluster && md.xchg >= 0) ? (void*)WS(md.xchg) : nullptr; probe[i].gate_minor = gate_minor;
-      probe[i].cell = c.rnncell;
-    }
-    if (backward == 2) return mmda_lstm_bwd_emits_dg_bf16(mode, 3, probe, B, T) != 0;      // ... and writes the gate gradients as bf16
-    return mmda_lstm_resident_applicable(mode, 3, probe, B, T, backward) != 0;
-  };
+// LayerNorm arguments of the fusion block: the projections' (+ activation), norm1 and norm2 (residual and dropout ride along)
+mmda_ln_args Pass::proj_ln_fwd(int i) {
+  mmda_ln_args ln = {};
+  ln.rows = B; ln.n = hs; ln.x = WS(m->z + i * BH); ln.gamma = PP(m->mod[i].plw); ln.beta = PP(m->mod[i].plb);
+  ln.y = WS(m->orig + i * BH); ln.mean = WS(m->pmean + i * B); ln.rstd = WS(m->prstd + i * B); ln.act = c.act;
+  ln.eps = 1e-5f; ln.actp = act_params(m, m->training, seed, SITE_RRELU + i, false);
+  return ln;
+}
+mmda_ln_args Pass::norm1_fwd() {
+  mmda_ln_args ln = {};
+  ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x6); ln.res = WS(m->attn_out); ln.gamma = PP(m->n1_w); ln.beta = PP(m->n1_b);
+  ln.y = WS(m->x1); ln.mean = WS(m->ln1_mean); ln.rstd = WS(m->ln1_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
+  ln.drop_site = SITE_DROP1; ln.eps = 1e-5f;
+  return ln;
+}
+mmda_ln_args Pass::norm2_fwd() {
+  mmda_ln_args ln = {};
+  ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x1); ln.res = WS(m->f2); ln.gamma = PP(m->n2_w); ln.beta = PP(m->n2_b);
+  ln.y = WS(m->hfused); ln.mean = WS(m->ln2_mean); ln.rstd = WS(m->ln2_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
+  ln.drop_site = SITE_DROP2; ln.permute_S = S6; ln.permute_B = B; ln.eps = 1e-5f;   // emits h = cat(h[0..5], dim=1)
+  return ln;
+}
+mmda_ln_bwd_args Pass::proj_ln_bwd(int i) {
+  mmda_ln_bwd_args l = {};
+  l.rows = B; l.n = hs; l.dy = WS(m->d_orig + i * BH); l.x = WS(m->z + i * BH); l.gamma = PP(m->mod[i].plw);
+  l.mean = WS(m->pmean + i * B); l.rstd = WS(m->prstd + i * B); l.d_x = WS(m->d_z + i * BH);
+  l.dgamma = GG(m->mod[i].plw); l.dbeta = GG(m->mod[i].plb); l.act = c.act;
+  l.actp = act_params(m, m->training, seed, SITE_RRELU + i, true);
+  return l;
+}
+mmda_ln_bwd_args Pass::norm1_bwd() {
+  mmda_ln_bwd_args l = {};
+  l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
+  l.mean = WS(m->ln1_mean); l.rstd = WS(m->ln1_rstd); l.d_x = WS(m->d_x6); l.accumulate_dx = 1; l.d_res = WS(m->d_attn_out);
+  l.dgamma = GG(m->n1_w); l.dbeta = GG(m->n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
+  return l;
+}
+mmda_ln_bwd_args Pass::norm2_bwd() {
+  mmda_ln_bwd_args l = {};
+  l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_hfused); l.x = WS(m->x1); l.res = WS(m->f2); l.gamma = PP(m->n2_w);
+  l.mean = WS(m->ln2_mean); l.rstd = WS(m->ln2_rstd); l.d_x = WS(m->d_x1); l.d_res = WS(m->d_f2);
+  l.dgamma = GG(m->n2_w); l.dbeta = GG(m->n2_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP2;
+  l.permute_S = S6; l.permute_B = B;
+  return l;
+}
+
+// W_hh -> MFMA fragment order (weights changed since the last step), the bf16 operand copies or (fp32) the embedding rows
+void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
   // bf16 mode: the input GEMMs read bf16 operand copies (K-major, 16-B rows): W_ih of both layers (plain for the forward,
   // transposed for dX) and the layer-1 inputs -- the text rows are gathered from the embedding matrix by the conversion itself
   // (models.py:201), so no fp32 copy of them is made.
-  const bool bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
-  const int ldR = m->ldR;
-  const float* xin[3] = {WS(m->mod[0].x), v, a};
-  // Gate-minor layout of the pre-activations / stash / gate gradients ([dir][unit][gate], 16-byte accesses in the recurrent
-  // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
-  // GEMM epilogues) AND the resident-weights kernels will run, forward and backward.
-  int gm = 0;
-  if (bfg && (B % 8) == 0 && T > 0) gm = probe_resident(1, 0) && probe_resident(1, 1);
-  m->gate_minor = gm;
-  const bool inf = m->inference != 0;                   // no backward follows: transposed copies and stashes are not needed
-  m->last_fwd_inference = inf;
   // The transposed copies, which only the backward pass reads, are made on the main stream with the forward ones.  (Making them on
   // the side stream beside the forward recurrences measured ~15 us slower: the fork's marker packet on the main stream and the L2
   // traffic beside the recurrences cost more than the smaller main-stream conversions save.)
-  // Weight gradients in the tn form of the bf16 GEMM (dW = dG^T X on row-major dG, X, hseq): the transposed copies of the inputs, of
-  // hseq and of the gate gradients are not made at all (B=256: 0.33 ms of conversions per step).  Needs the gate gradients as bf16
-  // from the recurrent kernel (gate-minor resident path).  Up to T*B = 4096 rows: measured (step, ms) B=32 0.759 -> 0.745, B=64 0.928 ->
-  // 0.917, but B=128 1.362 -> 1.391, B=256 2.39 -> 2.55, T=500 4.06 -> 4.08 -- in isolation the tn kernel matches the nt one at K = 1600
-  // and runs 15 - 20 % slower at K = 12800 (twice the LDS read instructions per k-tile), which at large batches outweighs the
-  // conversions it saves.  Round 3: the LDS-DMA pipelined GEMM (gemm_bf16_dma_kernel) runs the tn form at K = 12800 as fast as the nt
-  // form, so both layers take it at every size (B=256: the 0.47 ms of transposing conversions per step with it; a row limit, with or
-  // without layer 1 alone in the tn form beyond it, measured slower).  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere.
-  static const int tn_on = mmda_env_int("MMDA_GEMM_TN", 1);
-  const bool tn_ok = bfg && gm && tn_on && (B % 8) == 0 && probe_resident(1, 2);
-  m->tn_wgrad = tn_ok && !inf;
   // the first conversions: W_ih of both layers and the layer-1 inputs, plain and (`transposed`) K-major
   auto first_jobs = [&](bool transposed, mmda_convert_job* cj) -> int {
     int n = 0;
@@ -911,12 +1029,12 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
       for (int l = 0; l < 2; ++l) {
         Rnn& r = m->mod[i].rnn[l];
         cj[n++] = mmda_convert_job{rW_ih(m, r), r.D, 8 * r.H, r.D, nullptr, WS(r.wb), r.ldD,
-                                   transposed ? WS(r.wbT) : nullptr, transposed ? r.ldG : 0, gm ? r.H : 0};
+                                   transposed ? WS(r.wbT) : nullptr, transposed ? r.ldG : 0, P.gm ? r.H : 0};
       }
       Rnn& r0 = m->mod[i].rnn[0];
       const float* src = i == 0 ? PP(m->embed) : xin[i];
-      const bool xt = transposed && !tn_ok;              // layer-1 inputs transposed: only the nt form of layer 1's dW_ih reads them
-      cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, WS(r0.xb), r0.ldD, xt ? WS(r0.xbT) : nullptr, xt ? ldR : 0};
+      const bool xt = transposed && !P.tn_wgrad;         // layer-1 inputs transposed: only the nt form of layer 1's dW_ih reads them
+      cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, WS(r0.xb), r0.ldD, xt ? WS(r0.xbT) : nullptr, xt ? m->ldR : 0};
     }
     return n;
   };
@@ -926,300 +1044,273 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   // happens anyway (wT_pending).  (Merged measured equal to round 1's form -- packing on the side stream, joined by an event -- which
   // the fp32 mode keeps.)
   m->wT_pending = 0;
-  {
-    // The forward packing always; the resident-weights backward packing when those kernels will run the backward pass and the
-    // streaming backward packing only when they will not; neither for an evaluation pass.
-    const bool infer = m->inference != 0;
-    const bool want_c = !infer && m->use_cluster && mode == MMDA_BF16;
-    const bool want_b = !infer && !(want_c && probe_resident(0, 1));
-    int Hs[12]; const float* Wp[12]; void* Fp[12]; void* Bp[12]; void* Cp[12];
-    int k = 0;
-    for (int i = 0; i < 3; ++i)
-      for (int l = 0; l < 2; ++l)
-        for (int d = 0; d < 2; ++d, ++k) {
-          Rnn& r = m->mod[i].rnn[l];
-          Hs[k] = r.H; Wp[k] = rW_hh(m, r, d); Fp[k] = WS(r.pack_f[d]); Bp[k] = want_b ? WS(r.pack_b[d]) : nullptr; Cp[k] = WS(r.pack_c[d]);
-        }
-    m->pack_b_valid = want_b ? 1 : 0;
-    m->packed_c_valid = want_c ? 1 : 0;
-    m->wT_valid = 0;
-    const bool want_wT = B <= SKINNY_MAX_B && !m->inference;
-    if (bfg) {
-      mmda_convert_job cj[9];
-      const int nj = first_jobs(!inf, cj);
-      // ... and the K-major copies of the fusion block's weights (backward pass) in the same launch: 6 MB of traffic that cost a
-      // launch of its own 7 - 9 us at the head of the loss chain (side stream, the longer of the two chains beside the fusion block)
-      // or, at B >= 128, 15 us with its gap on the main stream.  MMDA_WT_MERGE=0: on the first fork as before.
-      static const int wt_merge = mmda_env_int("MMDA_WT_MERGE", 1);
-      std::vector<mmda_transpose_job> tj;
-      if (want_wT && wt_merge) weight_transpose_jobs(m, tj);
-      if (tj.size() > 20) tj.clear();
-      x.rc = mmda_lstm_pack_convert_transpose(12, Hs, Wp, Fp, Bp, want_c ? Cp : nullptr, cj, nj, tj.data(), (int)tj.size(), stream);
-      m->wT_pending = (want_wT && tj.empty()) ? 1 : 0;
-      if (!tj.empty()) m->wT_valid = x.rc ? 0 : 1;
-    } else {
-      void* ss = nullptr;
-      x.rc = side_fork(m, stream, &ss);
-      if (!x.rc) x.rc = mmda_lstm_pack_whh_multi(mode, 12, Hs, Wp, Fp, Bp, want_c ? Cp : nullptr, ss);
-      // the first recurrent kernel waits for the packing only, not for the transposes issued behind it
-      if (!x.rc && ss != stream && hipEventRecord(m->ev_pack, (hipStream_t)ss) != hipSuccess) x.rc = MMDA_ELAUNCH;
-      if (!x.rc && want_wT) x.rc = weight_transposes(m, ss);
-    }
-  }
-  if (x.rc) return x.rc;
-  if (!bfg) {
+  int Hs[12]; const float* Wp[12]; void* Fp[12]; void* Bp[12]; void* Cp[12];
+  int k = 0;
+  for (int i = 0; i < 3; ++i)
+    for (int l = 0; l < 2; ++l)
+      for (int d = 0; d < 2; ++d, ++k) {
+        Rnn& r = m->mod[i].rnn[l];
+        Hs[k] = r.H; Wp[k] = rW_hh(m, r, d); Fp[k] = WS(r.pack_f[d]); Bp[k] = P.want_b ? WS(r.pack_b[d]) : nullptr; Cp[k] = WS(r.pack_c[d]);
+      }
+  m->wT_valid = 0;
+  if (P.bfg) {
+    mmda_convert_job cj[9];
+    const int nj = first_jobs(!P.inf, cj);
+    // ... and the K-major copies of the fusion block's weights (backward pass) in the same launch: 6 MB of traffic that cost a
+    // launch of its own 7 - 9 us at the head of the loss chain (side stream, the longer of the two chains beside the fusion block)
+    // or, at B >= 128, 15 us with its gap on the main stream.  MMDA_WT_MERGE=0: on the first fork as before.
+    std::vector<mmda_transpose_job> tj;
+    if (P.wT_merge) weight_transpose_jobs(m, tj);
+    if (tj.size() > 20) tj.clear();
+    rc = mmda_lstm_pack_convert_transpose(12, Hs, Wp, Fp, Bp, P.want_c ? Cp : nullptr, cj, nj, tj.data(), (int)tj.size(), s);
+    m->wT_pending = (P.want_wT && tj.empty()) ? 1 : 0;
+    if (!tj.empty()) m->wT_valid = rc ? 0 : 1;
+  } else {
+    void* ss = nullptr;
+    rc = side_fork(m, s, &ss);
+    if (!rc) rc = mmda_lstm_pack_whh_multi(mode, 12, Hs, Wp, Fp, Bp, P.want_c ? Cp : nullptr, ss);
+    // the first recurrent kernel waits for the packing only, not for the transposes issued behind it
+    if (!rc && ss != s && hipEventRecord(m->ev_pack, (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
+    if (!rc && P.want_wT) rc = weight_transposes(m, ss);
     // embedding rows (models.py:201)
-    x.rc = mmda_embed_gather(PP(m->embed), t_ids, R, c.d_t, WS(m->mod[0].x), stream);
+    if (!rc) rc = mmda_embed_gather(PP(m->embed), t_ids, R, m->cfg.d_t, WS(m->mod[0].x), s);
   }
-  for (int l = 0; l < 2; ++l) {
-    mmda_lstm_desc desc[3];
-    mmda_gemm_bf16_args bg[3];
-    group_begin(x);
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-      const float* in = l == 0 ? xin[i] : WS(md.normed);
-      // time-batched input-to-hidden GEMM for both directions: (R, D) x (8H, D)^T + b_ih + b_hh
-      if (bfg) {
-        bg[i] = mmda_gemm_bf16_args{};
-        bg[i].M = R; bg[i].N = 8 * r.H; bg[i].K = r.D; bg[i].A = WS(r.xb); bg[i].lda = r.ldD; bg[i].B = WS(r.wb); bg[i].ldb = r.ldD;
-        bg[i].C = WS(md.gates[l]); bg[i].ldc = 8 * r.H; bg[i].bias = rB_ih(m, r); bg[i].bias2 = rB_hh(m, r);
-        bg[i].perm_n_H = gm ? r.H : 0;
-      } else {
-        gemm(x, mode, 0, 1, R, 8 * r.H, r.D, in, r.D, rW_ih(m, r), r.D, WS(md.gates[l]), 8 * r.H, rB_ih(m, r), rB_hh(m, r));
-      }
-      desc[i] = mmda_lstm_desc{};
-      desc[i].H = r.H; desc[i].gates = WS(md.gates[l]); desc[i].cstash = WS(md.c[l]); desc[i].hseq = WS(md.hseq[l]);
-      desc[i].wpack[0] = WS(r.pack_f[0]); desc[i].wpack[1] = WS(r.pack_f[1]);
-      desc[i].utt = WS(md.utt); desc[i].layer = l; desc[i].d_hseq = nullptr;
-      desc[i].xchg = (m->use_cluster && md.xchg >= 0) ? (void*)WS(md.xchg) : nullptr; desc[i].epoch_base = m->epoch;
-      desc[i].gate_minor = gm; desc[i].forward_only = inf; desc[i].cell = c.rnncell;
-    }
-    if (bfg && !x.rc) x.rc = mmda_gemm_bf16_grouped(bg, 3, stream);
-    m->epoch += (unsigned)T + 2u;
-    group_end(x);
-    if (!x.rc && l == 0 && m->side_pending && m->use_side) {   // packed W_hh ready (the side stream carries on with its transposes)
-      if (hipStreamWaitEvent((hipStream_t)stream, m->ev_pack, 0) != hipSuccess) x.rc = MMDA_ELAUNCH;
-    }
-    if (x.rc) return x.rc;
-    ev_rec(m, m->ev_fwd, l, 0, stream);
-    x.rc = mmda_lstm_fwd(mode, 3, desc, B, T, lengths, stream);
-    ev_rec(m, m->ev_fwd, l, 1, stream);
-    if (x.rc) return x.rc;
-    if (l == 0) {
-      mmda_ln_args ln[3];
-      for (int i = 0; i < 3; ++i) {
-        Mod& md = m->mod[i];
-        ln[i] = mmda_ln_args{};
-        ln[i].rows = R; ln[i].n = 2 * md.H; ln[i].x = WS(md.hseq[0]); ln[i].gamma = PP(md.ln_w); ln[i].beta = PP(md.ln_b);
-        ln[i].y = WS(md.normed); ln[i].mean = WS(md.ln_mean); ln[i].rstd = WS(md.ln_rstd); ln[i].eps = 1e-5f;
-      }
-      // (bf16 GEMMs: the LayerNorm also writes its output as the bf16 operand copy layer 2's input GEMM reads; the copies that only
-      //  the backward pass needs -- hseq, transposed inputs -- are made later on the side stream: backward_only_jobs)
-      if (bfg)
-        for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(m->mod[i].rnn[1].xb); ln[i].ld_bf16 = m->mod[i].rnn[1].ldD; }
-      // ... and ONLY as that copy where nothing reads the fp32 output: an evaluation pass, or a training step whose layer-2 weight
-      // gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
-      if (bfg && (inf || m->tn_wgrad))
-        for (int i = 0; i < 3; ++i) ln[i].y = nullptr;
-      x.rc = mmda_layernorm_fwd_multi(ln, 3, stream);
-    } else if (!x.rc && !m->eager_losses && ((bfg && !inf) || m->zero_grad_pending || m->wT_pending)) {
-      // side stream, beside the fusion block: the gradient bucket is cleared (train_step) and hseq^T of layer 2 is made for its
-      // dW_hh.  Joined at the end of forward(), so everything the backward pass issues on either stream is ordered behind both.
-      void* ss = nullptr;
-      x.rc = side_fork(m, stream, &ss);
-      if (!x.rc && m->wT_pending) x.rc = weight_transposes(m, ss);
-      if (!x.rc && m->zero_grad_pending && !m->eager_losses) { x.rc = mmda_misa_zero_grad(m, ss); m->zero_grad_pending = 0; }
+}
 
+// encoder layer l: input GEMM and recurrence of the three modalities; then layer 1's LayerNorm, or layer 2's fork beside the fusion block
+void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* lengths) {
+  mmda_lstm_desc desc[3];
+  mmda_gemm_bf16_args bg[3];
+  group_begin(*this);
+  for (int i = 0; i < 3; ++i) {
+    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+    const float* in = l == 0 ? xin[i] : WS(md.normed);
+    // time-batched input-to-hidden GEMM for both directions: (R, D) x (8H, D)^T + b_ih + b_hh
+    if (P.bfg) {
+      bg[i] = mmda_gemm_bf16_args{};
+      bg[i].M = R; bg[i].N = 8 * r.H; bg[i].K = r.D; bg[i].A = WS(r.xb); bg[i].lda = r.ldD; bg[i].B = WS(r.wb); bg[i].ldb = r.ldD;
+      bg[i].C = WS(md.gates[l]); bg[i].ldc = 8 * r.H; bg[i].bias = rB_ih(m, r); bg[i].bias2 = rB_hh(m, r);
+      bg[i].perm_n_H = P.gm ? r.H : 0;
+    } else {
+      gemm(*this, mode, 0, 1, R, 8 * r.H, r.D, in, r.D, rW_ih(m, r), r.D, WS(md.gates[l]), 8 * r.H, rB_ih(m, r), rB_hh(m, r));
     }
+    desc[i] = lstm_desc(m, i, l, false, P.gm, false);
+    desc[i].forward_only = P.inf;
   }
-  if (x.rc) return x.rc;
-  // shared_private (models.py:265-279)
-  const int64_t BH = (int64_t)B * hs;
-  if (B <= SKINNY_MAX_B) {
-    // ---- few rows: row-skinny GEMMs, independent ones grouped per launch (12 launches for the whole block)
-    mmda_skinny_args g[8];
+  if (P.bfg && !rc) rc = mmda_gemm_bf16_grouped(bg, 3, s);
+  m->epoch += (unsigned)T + 2u;
+  group_end(*this);
+  if (!rc && l == 0 && m->side_pending && m->use_side) {   // packed W_hh ready (the side stream carries on with its transposes)
+    if (hipStreamWaitEvent((hipStream_t)s, m->ev_pack, 0) != hipSuccess) rc = MMDA_ELAUNCH;
+  }
+  if (rc) return;
+  ev_rec(m, m->ev_fwd, l, 0, s);
+  rc = mmda_lstm_fwd(mode, 3, desc, B, T, lengths, s);
+  ev_rec(m, m->ev_fwd, l, 1, s);
+  if (rc) return;
+  if (l == 0) {
     mmda_ln_args ln[3];
     for (int i = 0; i < 3; ++i) {
       Mod& md = m->mod[i];
-      g[i] = sk_nt(B, hs, 4 * md.H, WS(md.utt), 4 * md.H, PP(md.pw), PP(md.pb), WS(m->z + i * BH), hs);
       ln[i] = mmda_ln_args{};
-      ln[i].rows = B; ln[i].n = hs; ln[i].x = WS(m->z + i * BH); ln[i].gamma = PP(md.plw); ln[i].beta = PP(md.plb);
-      ln[i].y = WS(m->orig + i * BH); ln[i].mean = WS(m->pmean + i * B); ln[i].rstd = WS(m->prstd + i * B); ln[i].act = c.act;
-      ln[i].eps = 1e-5f; ln[i].actp = act_params(m, training, seed, SITE_RRELU + i, false);
+      ln[i].rows = R; ln[i].n = 2 * md.H; ln[i].x = WS(md.hseq[0]); ln[i].gamma = PP(md.ln_w); ln[i].beta = PP(md.ln_b);
+      ln[i].y = WS(md.normed); ln[i].mean = WS(md.ln_mean); ln[i].rstd = WS(md.ln_rstd); ln[i].eps = 1e-5f;
     }
-    sk_launch(x, g, 3);
-    if (!x.rc) x.rc = mmda_layernorm_fwd_multi(ln, 3, stream);
-    // private x3 and shared (one weight over the stacked 3B rows), sigmoid epilogue
-    for (int i = 0; i < 3; ++i)
-      g[i] = sk_nt(B, hs, hs, WS(m->orig + i * BH), hs, PP(m->priv_w + (int64_t)i * hs * hs), PP(m->priv_b + i * hs), WS(m->x6 + i * BH), hs,
-                   MMDA_ACT_SIGMOID);
-    g[3] = sk_nt(3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), PP(m->sh_b), WS(m->x6 + 3 * BH), hs, MMDA_ACT_SIGMOID);
-    sk_launch(x, g, 4);
-    // The row-local stretches as one launch each (fused_rows.hip): recon + qkv -> attention -> out-proj -> LayerNorm 1, and
-    // LayerNorm 2 -> heads.  MMDA_ROW_FUSE=0: the launches they replace (4 and 3).
-    static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
-    const bool row_fuse = row_fuse_on && c.use_cmd_sim && hs == 128 && NHEAD == 2;
-    // loss seeds by the stretches (see mmda_misa::emo_eager); MMDA_LOSS_SEEDS=0: by the loss launch behind the forward pass, as before
-    static const int loss_seeds_on = mmda_env_int("MMDA_LOSS_SEEDS", 1);
-    m->seed_recon = (loss_seeds_on && row_fuse && m->eager_losses && m->emo_eager) ? 1 : 0;
-    m->seed_cls = (m->seed_recon && !c.use_confidNet) ? 1 : 0;
-    if (!x.rc) x.rc = eager_side_losses(m, stream, bfg && !inf);
-    mmda_ln_args l1 = {};
-    l1.rows = 6 * B; l1.n = hs; l1.x = WS(m->x6); l1.res = WS(m->attn_out); l1.gamma = PP(m->n1_w); l1.beta = PP(m->n1_b);
-    l1.y = WS(m->x1); l1.mean = WS(m->ln1_mean); l1.rstd = WS(m->ln1_rstd); l1.drop_p = p_tf; l1.drop_seed = seed;
-    l1.drop_site = SITE_DROP1; l1.eps = 1e-5f;
-    if (row_fuse) {
-      if (!x.rc) {
-        FusedFwdA f = {};
-        // one sample per workgroup in every stretch (two measured B=32 0.722 ms against 0.712; B=256 equal)
-        f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1; f.x6 = WS(m->x6);
-        f.rec_w = PP(m->rec_w); f.rec_b = PP(m->rec_b); f.recon = WS(m->recon);
-        f.in_w = PP(m->in_w); f.in_b = PP(m->in_b); f.qkv = WS(m->qkv);
-        f.ctx = WS(m->ctx); f.probs = WS(m->probs); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
-        f.out_w = PP(m->out_w); f.out_b = PP(m->out_b); f.attn_out = WS(m->attn_out); f.ln1 = l1;
-        if (m->seed_recon) {
-          f.orig = WS(m->orig); f.d_recon = WS(m->d_recon); f.d_orig = WS(m->d_orig);
-          f.recon_inv_n = 1.0f / (float)(3 * BH); f.recon_scale = c.recon_weight;
-        }
-        x.rc = mmda_fused_fwd_a(&f, stream);
+    // (bf16 GEMMs: the LayerNorm also writes its output as the bf16 operand copy layer 2's input GEMM reads; the copies that only
+    //  the backward pass needs -- hseq, transposed inputs -- are made later on the side stream: backward_only_jobs)
+    if (P.bfg)
+      for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(m->mod[i].rnn[1].xb); ln[i].ld_bf16 = m->mod[i].rnn[1].ldD; }
+    // ... and ONLY as that copy where nothing reads the fp32 output: an evaluation pass, or a training step whose layer-2 weight
+    // gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
+    if (P.bfg && (P.inf || P.tn_wgrad))
+      for (int i = 0; i < 3; ++i) ln[i].y = nullptr;
+    rc = mmda_layernorm_fwd_multi(ln, 3, s);
+  } else if (!m->eager_losses && ((P.bfg && !P.inf) || m->zero_grad_pending || m->wT_pending)) {
+    // side stream, beside the fusion block: the gradient bucket is cleared (train_step) and hseq^T of layer 2 is made for its
+    // dW_hh.  Joined at the end of forward(), so everything the backward pass issues on either stream is ordered behind both.
+    void* ss = nullptr;
+    rc = side_fork(m, s, &ss);
+    if (!rc && m->wT_pending) rc = weight_transposes(m, ss);
+    if (!rc && m->zero_grad_pending && !m->eager_losses) { rc = mmda_misa_zero_grad(m, ss); m->zero_grad_pending = 0; }
+  }
+}
+
+// shared_private (models.py:265-279) onwards, few rows: row-skinny GEMMs, independent ones grouped per launch (12 launches for the
+// whole block) -- or the fused row-local stretches (P.row_fuse)
+void Pass::fwd_fusion_skinny() {
+  mmda_skinny_args g[8];
+  mmda_ln_args ln[3];
+  for (int i = 0; i < 3; ++i) {
+    Mod& md = m->mod[i];
+    g[i] = sk_nt(B, hs, 4 * md.H, WS(md.utt), 4 * md.H, PP(md.pw), PP(md.pb), WS(m->z + i * BH), hs);
+    ln[i] = proj_ln_fwd(i);
+  }
+  sk_launch(*this, g, 3);
+  if (!rc) rc = mmda_layernorm_fwd_multi(ln, 3, s);
+  // private x3 and shared (one weight over the stacked 3B rows), sigmoid epilogue
+  for (int i = 0; i < 3; ++i)
+    g[i] = sk_nt(B, hs, hs, WS(m->orig + i * BH), hs, PP(m->priv_w + (int64_t)i * hs * hs), PP(m->priv_b + i * hs), WS(m->x6 + i * BH), hs,
+                 MMDA_ACT_SIGMOID);
+  g[3] = sk_nt(3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), PP(m->sh_b), WS(m->x6 + 3 * BH), hs, MMDA_ACT_SIGMOID);
+  sk_launch(*this, g, 4);
+  if (!rc) rc = eager_side_losses(m, s);
+  const mmda_ln_args l1 = norm1_fwd();
+  if (P.row_fuse) {
+    if (!rc) {
+      FusedFwdA f = {};
+      // one sample per workgroup in every stretch (two measured B=32 0.722 ms against 0.712; B=256 equal)
+      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1; f.x6 = WS(m->x6);
+      f.rec_w = PP(m->rec_w); f.rec_b = PP(m->rec_b); f.recon = WS(m->recon);
+      f.in_w = PP(m->in_w); f.in_b = PP(m->in_b); f.qkv = WS(m->qkv);
+      f.ctx = WS(m->ctx); f.probs = WS(m->probs); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
+      f.out_w = PP(m->out_w); f.out_b = PP(m->out_b); f.attn_out = WS(m->attn_out); f.ln1 = l1;
+      if (P.seed_recon) {
+        f.orig = WS(m->orig); f.d_recon = WS(m->d_recon); f.d_orig = WS(m->d_orig);
+        f.recon_inv_n = 1.0f / (float)(3 * BH); f.recon_scale = c.recon_weight;
       }
-    } else {
-      // reconstruct from private + shared (models.py:254-262), the q/k/v projection of the six tokens (models.py:243) and the
-      // discriminator's first layer all read x6 only
-      int n = 0;
-      for (int i = 0; i < 3; ++i) {
-        g[n] = sk_nt(B, hs, hs, WS(m->x6 + i * BH), hs, PP(m->rec_w + (int64_t)i * hs * hs), PP(m->rec_b + i * hs), WS(m->recon + i * BH), hs);
-        g[n++].A2 = WS(m->x6 + (3 + i) * BH);
-      }
-      g[n++] = sk_nt(6 * B, 3 * hs, hs, WS(m->x6), hs, PP(m->in_w), PP(m->in_b), WS(m->qkv), 3 * hs);
-      if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, hs, hs, WS(m->x6 + 3 * BH), hs, PP(m->d1_w), PP(m->d1_b), WS(m->dom_z), hs);
-      sk_launch(x, g, n);
-      if (!c.use_cmd_sim && !x.rc)
-        {
-        const mmda_act_params ap = act_params(m, training, seed, SITE_RRELU_DISC, false);
-        x.rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, stream);
-      }
-      if (!x.rc) x.rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, stream);
-      n = 0;
-      g[n++] = sk_nt(6 * B, hs, hs, WS(m->ctx), hs, PP(m->out_w), PP(m->out_b), WS(m->attn_out), hs);
-      if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, 3, hs, WS(m->dom_h), hs, PP(m->d2_w), PP(m->d2_b), WS(m->dom), 3);
-      sk_launch(x, g, n);
-      if (!x.rc) x.rc = mmda_layernorm_fwd(&l1, stream);
-    }
-    // feed-forward pair: one launch split over the hidden units (fused_rows.hip), its partial products summed by the stretch behind it
-    static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
-    const bool ffn_fuse = row_fuse && ffn_fuse_on && !m->fusion_fp8 && (FFN % 32) == 0;
-    if (m->fusion_fp8) {
-      if (!x.rc) x.rc = ffn_fp8(m, p_tf, seed, stream);
-    } else if (ffn_fuse) {
-      if (!x.rc) {
-        FusedFfnFwd f = {};
-        f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.x1 = WS(m->x1); f.w1 = PP(m->l1_w); f.b1 = PP(m->l1_b); f.f1 = WS(m->f1);
-        f.p = p_tf; f.seed = seed; f.site = SITE_FFN; f.w2 = PP(m->l2_w); f.parts = WS(m->ffn_parts);
-        x.rc = mmda_fused_ffn_fwd(&f, stream);
-      }
-    } else {
-      g[0] = sk_nt(6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), PP(m->l1_b), WS(m->f1), FFN, MMDA_ACT_RELU);
-      g[0].drop_p = p_tf; g[0].drop_seed = seed; g[0].drop_site = SITE_FFN;
-      sk_launch(x, g, 1);
-      g[0] = sk_nt(6 * B, hs, FFN, WS(m->f1), FFN, PP(m->l2_w), PP(m->l2_b), WS(m->f2), hs);
-      sk_launch(x, g, 1);
-    }
-    mmda_ln_args l2 = {};
-    l2.rows = 6 * B; l2.n = hs; l2.x = WS(m->x1); l2.res = WS(m->f2); l2.gamma = PP(m->n2_w); l2.beta = PP(m->n2_b);
-    l2.y = WS(m->hfused); l2.mean = WS(m->ln2_mean); l2.rstd = WS(m->ln2_rstd); l2.drop_p = p_tf; l2.drop_seed = seed;
-    l2.drop_site = SITE_DROP2; l2.permute_S = S6; l2.permute_B = B; l2.eps = 1e-5f;   // emits h = cat(h[0..5], dim=1)
-    if (row_fuse) {
-      if (!x.rc) {
-        FusedFwdC f = {};
-        f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1; f.ln2 = l2;
-        if (ffn_fuse) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(m->l2_b); f.f2 = WS(m->f2); }
-        f.hfused = WS(m->hfused); f.head_w = PP(m->head_w); f.head_b = PP(m->head_b); f.logits = WS(m->logits);
-        f.threshold = c.threshold; f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.labels = WS(m->labels);
-        f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS;
-        if (m->seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(m->d_scores); }
-        x.rc = mmda_fused_fwd_c(&f, stream);
-      }
-    } else {
-      if (!x.rc) x.rc = mmda_layernorm_fwd(&l2, stream);
-      g[0] = sk_nt(B, NC, 6 * hs, WS(m->hfused), 6 * hs, PP(m->head_w), PP(m->head_b), WS(m->logits), NC);
-      sk_launch(x, g, 1);
-      if (!x.rc)
-        x.rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
-                              stream);
+      rc = mmda_fused_fwd_a(&f, s);
     }
   } else {
-    // ---- many rows: the tiled generic kernel
-    for (int i = 0; i < 3 && !x.rc; ++i) {
-      Mod& md = m->mod[i];
-      lin_fwd(x, fmode, B, hs, 4 * md.H, WS(md.utt), PP(md.pw), PP(md.pb), WS(m->z + i * BH));
-      if (x.rc) break;
-      mmda_ln_args ln = {};
-      ln.rows = B; ln.n = hs; ln.x = WS(m->z + i * BH); ln.gamma = PP(md.plw); ln.beta = PP(md.plb); ln.y = WS(m->orig + i * BH);
-      ln.mean = WS(m->pmean + i * B); ln.rstd = WS(m->prstd + i * B); ln.act = c.act; ln.eps = 1e-5f;
-      ln.actp = act_params(m, training, seed, SITE_RRELU + i, false);
-      x.rc = mmda_layernorm_fwd(&ln, stream);
+    // reconstruct from private + shared (models.py:254-262), the q/k/v projection of the six tokens (models.py:243) and the
+    // discriminator's first layer all read x6 only
+    int n = 0;
+    for (int i = 0; i < 3; ++i) {
+      g[n] = sk_nt(B, hs, hs, WS(m->x6 + i * BH), hs, PP(m->rec_w + (int64_t)i * hs * hs), PP(m->rec_b + i * hs), WS(m->recon + i * BH), hs);
+      g[n++].A2 = WS(m->x6 + (3 + i) * BH);
     }
-    // private (three weights, batched) and shared (one weight over the stacked 3B rows), sigmoid epilogue
-    gemm(x, fmode, 0, 1, B, hs, hs, WS(m->orig), hs, PP(m->priv_w), hs, WS(m->x6), hs, PP(m->priv_b), nullptr, 0, MMDA_ACT_SIGMOID, 3,
-         BH, (int64_t)hs * hs, BH, hs);
-    gemm(x, fmode, 0, 1, 3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), hs, WS(m->x6 + 3 * BH), hs, PP(m->sh_b), nullptr, 0,
-         MMDA_ACT_SIGMOID);
-    m->seed_recon = m->seed_cls = 0;
-    if (!x.rc) x.rc = eager_side_losses(m, stream, bfg && !inf);
-    // reconstruct (models.py:254-262)
-    if (!x.rc) x.rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, stream);
-    gemm(x, fmode, 0, 1, B, hs, hs, WS(m->rsum), hs, PP(m->rec_w), hs, WS(m->recon), hs, PP(m->rec_b), nullptr, 0, 0, 3, BH,
-         (int64_t)hs * hs, BH, hs);
-    // adversarial discriminator behind the gradient-reversal layer (models.py:219-227); identity in forward
-    if (!c.use_cmd_sim) {
-      lin_fwd(x, fmode, 3 * B, hs, hs, WS(m->x6 + 3 * BH), PP(m->d1_w), PP(m->d1_b), WS(m->dom_z));
-      if (!x.rc) {
-      const mmda_act_params ap = act_params(m, training, seed, SITE_RRELU_DISC, false);
-      x.rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, stream);
+    g[n++] = sk_nt(6 * B, 3 * hs, hs, WS(m->x6), hs, PP(m->in_w), PP(m->in_b), WS(m->qkv), 3 * hs);
+    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, hs, hs, WS(m->x6 + 3 * BH), hs, PP(m->d1_w), PP(m->d1_b), WS(m->dom_z), hs);
+    sk_launch(*this, g, n);
+    if (!c.use_cmd_sim && !rc) {
+      const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, false);
+      rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-      lin_fwd(x, fmode, 3 * B, 3, hs, WS(m->dom_h), PP(m->d2_w), PP(m->d2_b), WS(m->dom));
-    }
-    // 1-layer transformer fusion over the six tokens (models.py:243-245; torch post-norm encoder layer)
-    lin_fwd(x, fmode, 6 * B, 3 * hs, hs, WS(m->x6), PP(m->in_w), PP(m->in_b), WS(m->qkv));
-    if (!x.rc) x.rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, stream);
-    lin_fwd(x, fmode, 6 * B, hs, hs, WS(m->ctx), PP(m->out_w), PP(m->out_b), WS(m->attn_out));
-    if (!x.rc) {
-      mmda_ln_args ln = {};
-      ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x6); ln.res = WS(m->attn_out); ln.gamma = PP(m->n1_w); ln.beta = PP(m->n1_b);
-      ln.y = WS(m->x1); ln.mean = WS(m->ln1_mean); ln.rstd = WS(m->ln1_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
-      ln.drop_site = SITE_DROP1; ln.eps = 1e-5f;
-      x.rc = mmda_layernorm_fwd(&ln, stream);
-    }
-    if (m->fusion_fp8) {
-      if (!x.rc) x.rc = ffn_fp8(m, p_tf, seed, stream);
-    } else {
-      mmda_gemm_args e = {};
-      e.drop_p = p_tf; e.drop_seed = seed; e.drop_site = SITE_FFN;
-      gemm(x, fmode, 0, 1, 6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), hs, WS(m->f1), FFN, PP(m->l1_b), nullptr, 0, MMDA_ACT_RELU, 1, 0,
-           0, 0, 0, &e);
-      lin_fwd(x, fmode, 6 * B, hs, FFN, WS(m->f1), PP(m->l2_w), PP(m->l2_b), WS(m->f2));
-    }
-    if (!x.rc) {
-      mmda_ln_args ln = {};
-      ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x1); ln.res = WS(m->f2); ln.gamma = PP(m->n2_w); ln.beta = PP(m->n2_b);
-      ln.y = WS(m->hfused); ln.mean = WS(m->ln2_mean); ln.rstd = WS(m->ln2_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
-      ln.drop_site = SITE_DROP2; ln.permute_S = S6; ln.permute_B = B; ln.eps = 1e-5f;   // emits h = cat(h[0..5], dim=1)
-      x.rc = mmda_layernorm_fwd(&ln, stream);
-    }
-    // heads (models.py:247-249)
-    lin_fwd(x, fmode, B, NC, 6 * hs, WS(m->hfused), PP(m->head_w), PP(m->head_b), WS(m->logits));
-    if (!x.rc)
-      x.rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
-                            stream);
+    if (!rc) rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, s);
+    n = 0;
+    g[n++] = sk_nt(6 * B, hs, hs, WS(m->ctx), hs, PP(m->out_w), PP(m->out_b), WS(m->attn_out), hs);
+    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, 3, hs, WS(m->dom_h), hs, PP(m->d2_w), PP(m->d2_b), WS(m->dom), 3);
+    sk_launch(*this, g, n);
+    if (!rc) rc = mmda_layernorm_fwd(&l1, s);
   }
+  // feed-forward pair: one launch split over the hidden units (fused_rows.hip), its partial products summed by the stretch behind it
+  if (m->fusion_fp8) {
+    if (!rc) rc = ffn_fp8(m, p_tf, seed, s);
+  } else if (P.ffn_fuse_fwd) {
+    if (!rc) {
+      FusedFfnFwd f = {};
+      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.x1 = WS(m->x1); f.w1 = PP(m->l1_w); f.b1 = PP(m->l1_b); f.f1 = WS(m->f1);
+      f.p = p_tf; f.seed = seed; f.site = SITE_FFN; f.w2 = PP(m->l2_w); f.parts = WS(m->ffn_parts);
+      rc = mmda_fused_ffn_fwd(&f, s);
+    }
+  } else {
+    g[0] = sk_nt(6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), PP(m->l1_b), WS(m->f1), FFN, MMDA_ACT_RELU);
+    g[0].drop_p = p_tf; g[0].drop_seed = seed; g[0].drop_site = SITE_FFN;
+    sk_launch(*this, g, 1);
+    g[0] = sk_nt(6 * B, hs, FFN, WS(m->f1), FFN, PP(m->l2_w), PP(m->l2_b), WS(m->f2), hs);
+    sk_launch(*this, g, 1);
+  }
+  const mmda_ln_args l2 = norm2_fwd();
+  if (P.row_fuse) {
+    if (!rc) {
+      FusedFwdC f = {};
+      f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1; f.ln2 = l2;
+      if (P.ffn_fuse_fwd) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(m->l2_b); f.f2 = WS(m->f2); }
+      f.hfused = WS(m->hfused); f.head_w = PP(m->head_w); f.head_b = PP(m->head_b); f.logits = WS(m->logits);
+      f.threshold = c.threshold; f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.labels = WS(m->labels);
+      f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS;
+      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(m->d_scores); }
+      rc = mmda_fused_fwd_c(&f, s);
+    }
+  } else {
+    if (!rc) rc = mmda_layernorm_fwd(&l2, s);
+    g[0] = sk_nt(B, NC, 6 * hs, WS(m->hfused), 6 * hs, PP(m->head_w), PP(m->head_b), WS(m->logits), NC);
+    sk_launch(*this, g, 1);
+    if (!rc)
+      rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
+                            s);
+  }
+}
+
+// the same, many rows: the tiled generic kernel
+void Pass::fwd_fusion_tiled() {
+  for (int i = 0; i < 3 && !rc; ++i) {
+    Mod& md = m->mod[i];
+    lin_fwd(*this, fmode, B, hs, 4 * md.H, WS(md.utt), PP(md.pw), PP(md.pb), WS(m->z + i * BH));
+    if (rc) break;
+    const mmda_ln_args ln = proj_ln_fwd(i);
+    rc = mmda_layernorm_fwd(&ln, s);
+  }
+  // private (three weights, batched) and shared (one weight over the stacked 3B rows), sigmoid epilogue
+  gemm(*this, fmode, 0, 1, B, hs, hs, WS(m->orig), hs, PP(m->priv_w), hs, WS(m->x6), hs, PP(m->priv_b), nullptr, 0, MMDA_ACT_SIGMOID, 3,
+       BH, (int64_t)hs * hs, BH, hs);
+  gemm(*this, fmode, 0, 1, 3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), hs, WS(m->x6 + 3 * BH), hs, PP(m->sh_b), nullptr, 0,
+       MMDA_ACT_SIGMOID);
+  if (!rc) rc = eager_side_losses(m, s);
+  // reconstruct (models.py:254-262)
+  if (!rc) rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, s);
+  gemm(*this, fmode, 0, 1, B, hs, hs, WS(m->rsum), hs, PP(m->rec_w), hs, WS(m->recon), hs, PP(m->rec_b), nullptr, 0, 0, 3, BH,
+       (int64_t)hs * hs, BH, hs);
+  // adversarial discriminator behind the gradient-reversal layer (models.py:219-227); identity in forward
+  if (!c.use_cmd_sim) {
+    lin_fwd(*this, fmode, 3 * B, hs, hs, WS(m->x6 + 3 * BH), PP(m->d1_w), PP(m->d1_b), WS(m->dom_z));
+    if (!rc) {
+      const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, false);
+      rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
+    }
+    lin_fwd(*this, fmode, 3 * B, 3, hs, WS(m->dom_h), PP(m->d2_w), PP(m->d2_b), WS(m->dom));
+  }
+  // 1-layer transformer fusion over the six tokens (models.py:243-245; torch post-norm encoder layer)
+  lin_fwd(*this, fmode, 6 * B, 3 * hs, hs, WS(m->x6), PP(m->in_w), PP(m->in_b), WS(m->qkv));
+  if (!rc) rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, s);
+  lin_fwd(*this, fmode, 6 * B, hs, hs, WS(m->ctx), PP(m->out_w), PP(m->out_b), WS(m->attn_out));
+  const mmda_ln_args l1 = norm1_fwd(), l2 = norm2_fwd();
+  if (!rc) rc = mmda_layernorm_fwd(&l1, s);
+  if (m->fusion_fp8) {
+    if (!rc) rc = ffn_fp8(m, p_tf, seed, s);
+  } else {
+    mmda_gemm_args e = {};
+    e.drop_p = p_tf; e.drop_seed = seed; e.drop_site = SITE_FFN;
+    gemm(*this, fmode, 0, 1, 6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), hs, WS(m->f1), FFN, PP(m->l1_b), nullptr, 0, MMDA_ACT_RELU, 1, 0,
+         0, 0, 0, &e);
+    lin_fwd(*this, fmode, 6 * B, hs, FFN, WS(m->f1), PP(m->l2_w), PP(m->l2_b), WS(m->f2));
+  }
+  if (!rc) rc = mmda_layernorm_fwd(&l2, s);
+  // heads (models.py:247-249)
+  lin_fwd(*this, fmode, B, NC, 6 * hs, WS(m->hfused), PP(m->head_w), PP(m->head_b), WS(m->logits));
+  if (!rc)
+    rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
+                          s);
+}
+}  // namespace
+
+extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                                 int training, uint64_t seed, void* stream) {
+  if (check_ready(m) || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
+  // The fusion block (projections, private/shared/recon, transformer layer, heads) is 2 % of the FLOPs and feeds the
+  // batch-statistic losses: it always runs on the exact f32 MFMA path.  `mode` (bf16) covers the LSTM GEMMs + recurrences.
+  m->training = training; m->seed = seed;
+  m->plan = plan_step(m);
+  Pass x(m, stream);
+  if (is_gru(m)) {          // GRU parameters -> four-slot layout (everything below reads the padded copies)
+    mmda_gru_pad_job gj[MMDA_GRU_PAD_MAX];
+    int n = gru_jobs(m, m->P, false, gj);
+    x.rc = mmda_gru_pad_params(gj, n, stream);
+    if (x.rc) return x.rc;
+  }
+  const float* xin[3] = {WS(m->mod[0].x), v, a};
+  x.fwd_operands(t_ids, xin);
+  for (int l = 0; l < 2 && !x.rc; ++l) x.fwd_encoder_layer(l, xin, lengths);
+  if (x.rc) return x.rc;
+  if (m->plan.skinny) x.fwd_fusion_skinny();
+  else x.fwd_fusion_tiled();
   if (!m->ev.empty()) { if (m->ev_seen_f % m->ev_stride == 0) m->ev_fwd++; m->ev_seen_f++; }
+  // the side stream's chain is joined -- on the device by the backward pass's stretch A (flag join) or by an event here
   if (!x.rc && m->wT_pending) {                // no fork came by (the eager losses are off and nothing else was pending)
     void* ss = nullptr;
     x.rc = side_fork(m, stream, &ss);
     if (!x.rc) x.rc = weight_transposes(m, ss);
   }
-  if (!x.rc && m->flag_join_ok && m->seed_recon && m->seed_cls && m->side_pending && m->use_side && m->jflags) {
+  if (!x.rc && m->plan.fj_fwd && m->side_pending && m->jflags) {
     x.rc = side_flag_signal(m, 0, m->fj1_armed != 0);      // (see mmda_misa::jflags: fused_bwd_a_kernel waits for the loss chain)
     m->fj1 = x.rc ? 0 : 1; m->fj1_armed = 0;
     return x.rc;
@@ -1247,9 +1338,9 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
   float* L = WS(m->losses);
   const bool ext = m->ext_batch_losses && with_grads && c.use_cmd_sim;      // the caller did (see mmda_misa::ext_batch_losses)
   const bool eager = (m->eager_done || ext) && with_grads;        // forward() already cleared the region and ran diff (+ CMD) on the side stream
+  // seeds the forward stretches stored already: the plan's, while this call takes up that forward pass's chain (eager_done)
+  const bool s_recon = m->eager_done && with_grads && m->plan.seed_recon, s_cls = m->eager_done && with_grads && m->plan.seed_cls;
   m->eager_done = 0;
-  const bool s_recon = eager && m->seed_recon, s_cls = eager && m->seed_cls;      // seeds the forward stretches stored already
-  m->seed_recon = m->seed_cls = 0;
   if (eager) {
     rc = side_join(m, stream);                           // (forward() joined already; kept for callers that split the calls)
     if (rc) return rc;
@@ -1286,547 +1377,455 @@ extern "C" int mmda_misa_zero_grad(mmda_misa* m, void* stream) {
   return MMDA_OK;
 }
 
-extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
-                                  void* stream) {
-  if (check_ready(m) || !m->G || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
-  if (m->last_fwd_inference) return MMDA_EINVAL;        // the last forward was an evaluation pass: nothing was stashed
-  m->early_valid = 0;
-  const mmda_misa_config& c = m->cfg;
-  const int B = m->B, T = m->T, hs = c.hidden, mode = c.mode, NC = 6 + c.ncls;
-  const int fmode = MMDA_F32;       // fusion block: exact path (see mmda_misa_forward)
-  const int R = T * B;
-  const int64_t BH = (int64_t)B * hs;
-  Ctx x{m, stream};
-  const int training = m->training; const uint64_t seed = m->seed;
-  const float p_tf = training ? c.fusion_dropout : 0.f, p_cls = training ? c.dropout : 0.f;
+namespace {
+// d f1 = (d f2 W2) * [f1 > 0] / (1-p), then d x1 += d f1 W1: two row-skinny launches (f1 is stored post-relu, post-dropout, so
+// f1 > 0 <=> kept and pre-activation > 0)
+void Pass::skinny_ffn_dx(bool wt) {
+  mmda_skinny_args g = sk_dxw(wt, 6 * B, hs, FFN, WS(m->d_f2), hs, WS(m->l2_wT), PP(m->l2_w), WS(m->d_f1), FFN, 0);
+  g.gate = WS(m->f1); g.ldgate = FFN; g.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
+  sk_launch(*this, &g, 1);
+  g = sk_dxw(wt, 6 * B, FFN, hs, WS(m->d_f1), FFN, WS(m->l1_wT), PP(m->l1_w), WS(m->d_x1), hs, 1);
+  sk_launch(*this, &g, 1);
+}
+// d utt = d z W_proj of the three projections: one row-skinny launch
+void Pass::skinny_proj_dx(bool wt) {
+  mmda_skinny_args g[3];
+  for (int i = 0; i < 3; ++i) {
+    Mod& md = m->mod[i];
+    g[i] = sk_dxw(wt, B, hs, 4 * md.H, WS(m->d_z + i * BH), hs, WS(m->pwT[i]), PP(md.pw), WS(md.d_utt), 4 * md.H, 0);
+  }
+  sk_launch(*this, g, 3);
+}
 
-  // Weight-gradient GEMMs of the fusion block are collected and issued as one grouped launch on the side stream once
-  // the dX chain (the critical path into the encoders) is through; their inputs are not modified afterwards.
-  x.deferring = true;
-  bool pg_pending = false;               // the fused stretches left LayerNorm parameter-gradient partials (mmda_fused_pg_finish)
-  bool rec_hoisted = false;              // stretch C's launch made d_recon W_rec for stretch A
-  if (B <= SKINNY_MAX_B) {
-    // ---- few rows: the dX chain on row-skinny GEMMs (13 launches); weight gradients deferred exactly as below
-    mmda_skinny_args g[8];
-    const bool wt = m->wT_valid != 0;                   // K-major weight copies from this step's forward (side stream, joined there)
-    // The row-local stretches as one launch each (fused_rows.hip): heads' sigmoid' -> d_hfused -> LayerNorm 2, and LayerNorm 1 ->
-    // ... -> the projection LayerNorms.  MMDA_ROW_FUSE=0: the launches they replace (3 and 6).
-    static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
-    const bool row_fuse = row_fuse_on && wt && c.use_cmd_sim && hs == 128 && NHEAD == 2;
-    if (m->fj1 && !row_fuse) { x.rc = flag_join_fallback(m, stream); m->fj1 = 0; if (x.rc) return x.rc; }     // (no kernel here waits on the device)
-    mmda_ln_bwd_args l2a = {};
-    l2a.rows = 6 * B; l2a.n = hs; l2a.dy = WS(m->d_hfused); l2a.x = WS(m->x1); l2a.res = WS(m->f2); l2a.gamma = PP(m->n2_w);
-    l2a.mean = WS(m->ln2_mean); l2a.rstd = WS(m->ln2_rstd); l2a.d_x = WS(m->d_x1); l2a.d_res = WS(m->d_f2);
-    l2a.dgamma = GG(m->n2_w); l2a.dbeta = GG(m->n2_b); l2a.drop_p = p_tf; l2a.drop_seed = seed; l2a.drop_site = SITE_DROP2;
-    l2a.permute_S = S6; l2a.permute_B = B;
-    if (row_fuse) {
-      FusedBwdC f = {};
-      f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1;
-      f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.d_tcp = WS(m->d_tcp); f.d_scores = WS(m->d_scores); f.d_logits = WS(m->d_logits);
-      // flag join pending: d_tcp is all zeros (no ConfidNet gradients in that mode), but cleared by the side stream's chain, which
-      // this launch does not wait for -- NULL reads as zero
-      if (m->fj1) f.d_tcp = nullptr;
-      // the reconstruction term of stretch A's d_x6 chain, in workgroups of this launch (small batches: both sets fit the chip twice
-      // over; MMDA_FUSED_SPLIT=0: inside stretch A as before)
-      static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
-      rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
-      if (rec_hoisted) { f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.rec_part = WS(m->rec_part); }
-      f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(m->head_w); f.d_hfused = WS(m->d_hfused); f.ln2 = l2a;
-      f.pg_parts = WS(m->pg_parts);
-      x.rc = mmda_fused_bwd_c(&f, stream);
-    } else {
-      x.rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
-                            stream);
-      g[0] = wt ? sk_dx(B, NC, 6 * hs, WS(m->d_logits), NC, WS(m->head_wT), WS(m->d_hfused), 6 * hs, 0)
-                : sk_nn(B, NC, 6 * hs, WS(m->d_logits), NC, PP(m->head_w), WS(m->d_hfused), 6 * hs, 0);
-      sk_launch(x, g, 1);
-      if (!x.rc) x.rc = mmda_layernorm_bwd(&l2a, stream);       // norm2
-    }
-    lin_dw(x, fmode, B, NC, 6 * hs, WS(m->d_logits), WS(m->hfused), GG(m->head_w), GG(m->head_b));
-    // FFN
-    // d f1 = (d f2 W2) * [f1 > 0] / (1-p): f1 is stored post-relu, post-dropout, so f1 > 0 <=> kept and pre-activation > 0
-    static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
-    const bool ffn_fuse = row_fuse && ffn_fuse_on && (FFN % 32) == 0;
-    if (ffn_fuse) {
-      if (!x.rc) {
-        FusedFfnBwd f = {};
-        f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.d_f2 = WS(m->d_f2); f.f1 = WS(m->f1);
-        f.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f; f.l2_wT = WS(m->l2_wT); f.d_f1 = WS(m->d_f1); f.l1_wT = WS(m->l1_wT);
-        f.parts = WS(m->ffn_parts);
-        x.rc = mmda_fused_ffn_bwd(&f, stream);
-      }
-    } else {
-      g[0] = wt ? sk_dx(6 * B, hs, FFN, WS(m->d_f2), hs, WS(m->l2_wT), WS(m->d_f1), FFN, 0)
-                : sk_nn(6 * B, hs, FFN, WS(m->d_f2), hs, PP(m->l2_w), WS(m->d_f1), FFN, 0);
-      g[0].gate = WS(m->f1); g[0].ldgate = FFN; g[0].gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
-      sk_launch(x, g, 1);
-      g[0] = wt ? sk_dx(6 * B, FFN, hs, WS(m->d_f1), FFN, WS(m->l1_wT), WS(m->d_x1), hs, 1)
-                : sk_nn(6 * B, FFN, hs, WS(m->d_f1), FFN, PP(m->l1_w), WS(m->d_x1), hs, 1);
-      sk_launch(x, g, 1);
-    }
-    lin_dw(x, fmode, 6 * B, hs, FFN, WS(m->d_f2), WS(m->f1), GG(m->l2_w), GG(m->l2_b));
-    lin_dw(x, fmode, 6 * B, FFN, hs, WS(m->d_f1), WS(m->x1), GG(m->l1_w), GG(m->l1_b));
-    // norm1 + self-attention ... projection LayerNorms
-    if (row_fuse && !x.rc) {
-      FusedBwdA f = {};
-      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1;
-      if (ffn_fuse) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.d_x1 = WS(m->d_x1); }
-      mmda_ln_bwd_args& l = f.ln1;
-      l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
-      l.mean = WS(m->ln1_mean); l.rstd = WS(m->ln1_rstd); l.d_x = WS(m->d_x6); l.accumulate_dx = 1; l.d_res = WS(m->d_attn_out);
-      l.dgamma = GG(m->n1_w); l.dbeta = GG(m->n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
-      f.d_attn_out = WS(m->d_attn_out); f.out_wT = WS(m->out_wT); f.d_ctx = WS(m->d_ctx);
-      f.qkv = WS(m->qkv); f.probs = WS(m->probs); f.d_qkv = WS(m->d_qkv); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
-      f.in_wT = WS(m->in_wT); f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.x6 = WS(m->x6); f.d_x6 = WS(m->d_x6);
-      if (rec_hoisted) f.rec_part = WS(m->rec_part);
-      f.priv_wT = WS(m->priv_wT); f.sh_wT = WS(m->sh_wT); f.d_orig = WS(m->d_orig);
-      for (int i = 0; i < 3; ++i) {
-        Mod& md = m->mod[i];
-        mmda_ln_bwd_args& lp = f.lnp[i];
-        lp.rows = B; lp.n = hs; lp.dy = WS(m->d_orig + i * BH); lp.x = WS(m->z + i * BH); lp.gamma = PP(md.plw);
-        lp.mean = WS(m->pmean + i * B); lp.rstd = WS(m->prstd + i * B); lp.d_x = WS(m->d_z + i * BH);
-        lp.dgamma = GG(md.plw); lp.dbeta = GG(md.plb); lp.act = c.act;
-        lp.actp = act_params(m, training, seed, SITE_RRELU + i, true);
-      }
-      f.pg_parts = WS(m->pg_parts);
-      if (m->fj1) {
-        // Waiting workgroups hold their CU's LDS (104 KB each): with one on every CU the side stream's kernels could not start, and
-        // the wait would never end -- on the device only while the stretch leaves most of the chip free; otherwise the event, here
-        // (two launches later than the end of the forward pass, where it used to be: the loss chain is the longer one at large B)
-        if (B <= 64) { f.wait_flag = m->jflags; f.wait_value = m->jval[0]; f.wait_err = m->jflags + 2; }
-        else x.rc = flag_join_fallback(m, stream);
-        m->fj1 = 0;
-      }
-      if (!x.rc) x.rc = mmda_fused_bwd_a(&f, stream);
-      pg_pending = true;
-      // the weight gradients of the stretch (deferred: one grouped launch on the side stream, as below)
-      lin_dw(x, fmode, 6 * B, hs, hs, WS(m->d_attn_out), WS(m->ctx), GG(m->out_w), GG(m->out_b));
-      lin_dw(x, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), WS(m->x6), GG(m->in_w), GG(m->in_b));
-      {
-        mmda_gemm_args e = {};
-        e.bias_grad = GG(m->rec_b);      // strideBias = hs: one bias gradient per batched problem
-        gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_recon), hs, WS(m->rsum), hs, GG(m->rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-             hs, &e);
-      }
-      {
-        mmda_gemm_args e = {};
-        e.bias_grad = GG(m->priv_b);
-        gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_x6), hs, WS(m->orig), hs, GG(m->priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-             hs, &e);
-      }
-      lin_dw(x, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), WS(m->orig), GG(m->sh_w), GG(m->sh_b));
-    } else {
-      // norm1 + self-attention
-      if (!x.rc) {
-        mmda_ln_bwd_args l = {};
-        l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
-        l.mean = WS(m->ln1_mean); l.rstd = WS(m->ln1_rstd); l.d_x = WS(m->d_x6); l.accumulate_dx = 1; l.d_res = WS(m->d_attn_out);
-        l.dgamma = GG(m->n1_w); l.dbeta = GG(m->n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
-        x.rc = mmda_layernorm_bwd(&l, stream);
-      }
-      int n = 0;
-      g[n++] = wt ? sk_dx(6 * B, hs, hs, WS(m->d_attn_out), hs, WS(m->out_wT), WS(m->d_ctx), hs, 0)
-                  : sk_nn(6 * B, hs, hs, WS(m->d_attn_out), hs, PP(m->out_w), WS(m->d_ctx), hs, 0);
-      if (!c.use_cmd_sim) g[n++] = wt ? sk_dx(3 * B, 3, hs, WS(m->d_dom), 3, WS(m->d2_wT), WS(m->d_dom_h), hs, 0)
-                                      : sk_nn(3 * B, 3, hs, WS(m->d_dom), 3, PP(m->d2_w), WS(m->d_dom_h), hs, 0);
-      sk_launch(x, g, n);
-      lin_dw(x, fmode, 6 * B, hs, hs, WS(m->d_attn_out), WS(m->ctx), GG(m->out_w), GG(m->out_b));
-      if (!x.rc) x.rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, stream);
-      lin_dw(x, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), WS(m->x6), GG(m->in_w), GG(m->in_b));
-      // adversarial branch: discriminator grads, then the REVERSED gradient into the shared codes (functions.py:17-21)
-      if (!c.use_cmd_sim) {
-        lin_dw(x, fmode, 3 * B, 3, hs, WS(m->d_dom), WS(m->dom_h), GG(m->d2_w), GG(m->d2_b));
-        if (!x.rc) {
-          const mmda_act_params ap = act_params(m, training, seed, SITE_RRELU_DISC, true);
-          x.rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, stream);
-        }
-        lin_dw(x, fmode, 3 * B, hs, hs, WS(m->d_dom_z), WS(m->x6 + 3 * BH), GG(m->d1_w), GG(m->d1_b));
-        g[0] = wt ? sk_dx(3 * B, hs, hs, WS(m->d_dom_z), hs, WS(m->d1_wT), WS(m->d_x6 + 3 * BH), hs, 1)
-                  : sk_nn(3 * B, hs, hs, WS(m->d_dom_z), hs, PP(m->d1_w), WS(m->d_x6 + 3 * BH), hs, 1);
-        g[0].alpha = -c.reverse_grad_weight;
-        sk_launch(x, g, 1);
-      }
-      // d_x6[token j] = (d_x6 + d_qkv[j] W_in + d_recon[j % 3] W_rec[j % 3]) * s (1 - s): the q/k/v projection's and the
-      // reconstruction's input gradients (the latter flows into BOTH private and shared) and the sigmoid backward, six problems
-      for (int j = 0; j < 6; ++j) {
-        const int i = j % 3;
-        g[j] = wt ? sk_dx(B, 3 * hs, hs, WS(m->d_qkv + (int64_t)j * B * 3 * hs), 3 * hs, WS(m->in_wT), WS(m->d_x6 + j * BH), hs, 1)
-                  : sk_nn(B, 3 * hs, hs, WS(m->d_qkv + (int64_t)j * B * 3 * hs), 3 * hs, PP(m->in_w), WS(m->d_x6 + j * BH), hs, 1);
-        g[j].K2 = hs; g[j].A_2nd = WS(m->d_recon + i * BH); g[j].lda_2nd = hs; g[j].ldb_2nd = hs;
-        g[j].B_2nd = wt ? WS(m->rec_wT + (int64_t)i * hs * hs) : PP(m->rec_w + (int64_t)i * hs * hs);
-        g[j].dsig = WS(m->x6 + j * BH); g[j].lddsig = hs;
-      }
-      sk_launch(x, g, 6);
-      {
-        mmda_gemm_args e = {};
-        e.bias_grad = GG(m->rec_b);      // strideBias = hs: one bias gradient per batched problem
-        gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_recon), hs, WS(m->rsum), hs, GG(m->rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-             hs, &e);
-      }
-      // d_orig[i] += d_private[i] W_priv[i] + d_shared[i] W_shared
-      for (int i = 0; i < 3; ++i) {
-        g[i] = wt ? sk_dx(B, hs, hs, WS(m->d_x6 + i * BH), hs, WS(m->priv_wT + (int64_t)i * hs * hs), WS(m->d_orig + i * BH), hs, 1)
-                  : sk_nn(B, hs, hs, WS(m->d_x6 + i * BH), hs, PP(m->priv_w + (int64_t)i * hs * hs), WS(m->d_orig + i * BH), hs, 1);
-        g[i].K2 = hs; g[i].A_2nd = WS(m->d_x6 + (3 + i) * BH); g[i].lda_2nd = hs; g[i].B_2nd = wt ? WS(m->sh_wT) : PP(m->sh_w); g[i].ldb_2nd = hs;
-      }
-      sk_launch(x, g, 3);
-      {
-        mmda_gemm_args e = {};
-        e.bias_grad = GG(m->priv_b);
-        gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_x6), hs, WS(m->orig), hs, GG(m->priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-             hs, &e);
-      }
-      lin_dw(x, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), WS(m->orig), GG(m->sh_w), GG(m->sh_b));
-      // projections
-      if (!x.rc) {
-        mmda_ln_bwd_args l[3];
-        for (int i = 0; i < 3; ++i) {
-          Mod& md = m->mod[i];
-          l[i] = mmda_ln_bwd_args{};
-          l[i].rows = B; l[i].n = hs; l[i].dy = WS(m->d_orig + i * BH); l[i].x = WS(m->z + i * BH); l[i].gamma = PP(md.plw);
-          l[i].mean = WS(m->pmean + i * B); l[i].rstd = WS(m->prstd + i * B); l[i].d_x = WS(m->d_z + i * BH);
-          l[i].dgamma = GG(md.plw); l[i].dbeta = GG(md.plb); l[i].act = c.act;
-          l[i].actp = act_params(m, training, seed, SITE_RRELU + i, true);
-        }
-        x.rc = mmda_layernorm_bwd_multi(l, 3, stream);
-      }
-    }
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i];
-      g[i] = wt ? sk_dx(B, hs, 4 * md.H, WS(m->d_z + i * BH), hs, WS(m->pwT[i]), WS(md.d_utt), 4 * md.H, 0)
-                : sk_nn(B, hs, 4 * md.H, WS(m->d_z + i * BH), hs, PP(md.pw), WS(md.d_utt), 4 * md.H, 0);
-      lin_dw(x, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), WS(md.utt), GG(md.pw), GG(md.pb));
-    }
-    sk_launch(x, g, 3);
-  } else {
-    if (m->fj1) { x.rc = flag_join_fallback(m, stream); m->fj1 = 0; if (x.rc) return x.rc; }      // (cannot happen: the seeds need the fused stretches)
-    // heads
-    x.rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
-                          stream);
-    lin_dx(x, fmode, B, NC, 6 * hs, WS(m->d_logits), PP(m->head_w), WS(m->d_hfused), 0);
-    lin_dw(x, fmode, B, NC, 6 * hs, WS(m->d_logits), WS(m->hfused), GG(m->head_w), GG(m->head_b));
-    // norm2 + FFN
-    if (!x.rc) {
-      mmda_ln_bwd_args l = {};
-      l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_hfused); l.x = WS(m->x1); l.res = WS(m->f2); l.gamma = PP(m->n2_w);
-      l.mean = WS(m->ln2_mean); l.rstd = WS(m->ln2_rstd); l.d_x = WS(m->d_x1); l.d_res = WS(m->d_f2);
-      l.dgamma = GG(m->n2_w); l.dbeta = GG(m->n2_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP2;
-      l.permute_S = S6; l.permute_B = B;
-      x.rc = mmda_layernorm_bwd(&l, stream);
-    }
-    {
-      // d f1 = (d f2 W2) * [f1 > 0] / (1-p): f1 is stored post-relu, post-dropout, so f1 > 0 <=> kept and pre-activation > 0
-      mmda_gemm_args e = {};
-      e.gate = WS(m->f1); e.ldgate = FFN; e.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
-      gemm(x, fmode, 0, 0, 6 * B, FFN, hs, WS(m->d_f2), hs, PP(m->l2_w), FFN, WS(m->d_f1), FFN, nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, &e);
-    }
-    lin_dw(x, fmode, 6 * B, hs, FFN, WS(m->d_f2), WS(m->f1), GG(m->l2_w), GG(m->l2_b));
-    lin_dx(x, fmode, 6 * B, FFN, hs, WS(m->d_f1), PP(m->l1_w), WS(m->d_x1), 1);
-    lin_dw(x, fmode, 6 * B, FFN, hs, WS(m->d_f1), WS(m->x1), GG(m->l1_w), GG(m->l1_b));
-    // norm1 + self-attention
-    if (!x.rc) {
-      mmda_ln_bwd_args l = {};
-      l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
-      l.mean = WS(m->ln1_mean); l.rstd = WS(m->ln1_rstd); l.d_x = WS(m->d_x6); l.accumulate_dx = 1; l.d_res = WS(m->d_attn_out);
-      l.dgamma = GG(m->n1_w); l.dbeta = GG(m->n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
-      x.rc = mmda_layernorm_bwd(&l, stream);
-    }
-    lin_dx(x, fmode, 6 * B, hs, hs, WS(m->d_attn_out), PP(m->out_w), WS(m->d_ctx), 0);
-    lin_dw(x, fmode, 6 * B, hs, hs, WS(m->d_attn_out), WS(m->ctx), GG(m->out_w), GG(m->out_b));
-    if (!x.rc) x.rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, stream);
-    lin_dx(x, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), PP(m->in_w), WS(m->d_x6), 1);
-    lin_dw(x, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), WS(m->x6), GG(m->in_w), GG(m->in_b));
-    // adversarial branch: discriminator grads, then the REVERSED gradient into the shared codes (functions.py:17-21)
-    if (!c.use_cmd_sim) {
-      lin_dx(x, fmode, 3 * B, 3, hs, WS(m->d_dom), PP(m->d2_w), WS(m->d_dom_h), 0);
-      lin_dw(x, fmode, 3 * B, 3, hs, WS(m->d_dom), WS(m->dom_h), GG(m->d2_w), GG(m->d2_b));
-      if (!x.rc) {
-        const mmda_act_params ap = act_params(m, training, seed, SITE_RRELU_DISC, true);
-        x.rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, stream);
-      }
-      lin_dw(x, fmode, 3 * B, hs, hs, WS(m->d_dom_z), WS(m->x6 + 3 * BH), GG(m->d1_w), GG(m->d1_b));
-      mmda_gemm_args e = {};
-      e.alpha = -c.reverse_grad_weight;
-      gemm(x, fmode, 0, 0, 3 * B, hs, hs, WS(m->d_dom_z), hs, PP(m->d1_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
-    }
-    // reconstruct: d(private+shared) goes to both halves of d_x6
-    gemm(x, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
-    gemm(x, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 3, BH,
-         (int64_t)hs * hs, BH);
-    {
-      mmda_gemm_args e = {};
-      e.bias_grad = GG(m->rec_b);      // strideBias = hs: one bias gradient per batched problem
-      gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_recon), hs, WS(m->rsum), hs, GG(m->rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-           hs, &e);
-    }
-    // sigmoid of private/shared
-    if (!x.rc) x.rc = mmda_sigmoid_bwd_inplace(WS(m->d_x6), WS(m->x6), 6 * BH, stream);
-    gemm(x, fmode, 0, 0, B, hs, hs, WS(m->d_x6), hs, PP(m->priv_w), hs, WS(m->d_orig), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
-    {
-      mmda_gemm_args e = {};
-      e.bias_grad = GG(m->priv_b);
-      gemm(x, fmode, 1, 0, hs, hs, B, WS(m->d_x6), hs, WS(m->orig), hs, GG(m->priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
-           hs, &e);
-    }
-    lin_dx(x, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), PP(m->sh_w), WS(m->d_orig), 1);
-    lin_dw(x, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), WS(m->orig), GG(m->sh_w), GG(m->sh_b));
-    // projections
-    for (int i = 0; i < 3 && !x.rc; ++i) {
-      Mod& md = m->mod[i];
-      mmda_ln_bwd_args l = {};
-      l.rows = B; l.n = hs; l.dy = WS(m->d_orig + i * BH); l.x = WS(m->z + i * BH); l.gamma = PP(md.plw);
-      l.mean = WS(m->pmean + i * B); l.rstd = WS(m->prstd + i * B); l.d_x = WS(m->d_z + i * BH);
-      l.dgamma = GG(md.plw); l.dbeta = GG(md.plb); l.act = c.act;
-      l.actp = act_params(m, training, seed, SITE_RRELU + i, true);
-      x.rc = mmda_layernorm_bwd(&l, stream);
-      lin_dx(x, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), PP(md.pw), WS(md.d_utt), 0);
-      lin_dw(x, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), WS(md.utt), GG(md.pw), GG(md.pb));
-    }
-  }
-  if (x.rc) return x.rc;
-  x.deferring = false;
+// the fusion block's dX chain as the fused row-local stretches (fused_rows.hip): heads' sigmoid' -> d_hfused -> LayerNorm 2, the
+// feed-forward pair, and LayerNorm 1 -> ... -> the projection LayerNorms
+void Pass::bwd_fusion_fused() {
   {
-    // side stream: private + shared (the reconstruction's input, needed only by its weight gradient) and every deferred
-    // weight-gradient GEMM of the block
-    void* ss = nullptr;
-    x.rc = side_fork(m, stream, &ss);
-    if (!x.rc && m->misc_deferred) {
-      // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
-      x.rc = mmda_loss_misc(WS(m->scores), WS(m->tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
-                            WS(m->recon), WS(m->orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(m->losses), c.diff_weight,
-                            c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, ss);
-      m->misc_deferred = nullptr;
-    }
-    if (!x.rc && B <= SKINNY_MAX_B) x.rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, ss);
-    // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
-    static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
-    m->esort_valid = 0;
-    if (!x.rc && sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(R)) {
-      x.rc = mmda_embed_sort_ids(t_ids, R, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
-      if (!x.rc && ss != stream) {
-        hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
-        if (hipGetLastError() != hipSuccess) x.rc = MMDA_ELAUNCH;
-      }
-      m->esort_valid = x.rc ? 0 : (ss != stream ? 2 : 1);
-    }
-    if (!x.rc && pg_pending) {
-      // gamma / beta gradients of the five LayerNorms the fused stretches walked: per-sample partials added in sample order
-      float* dg[FUSED_PG_SLOTS] = {GG(m->n2_w), GG(m->n1_w), GG(m->mod[0].plw), GG(m->mod[1].plw), GG(m->mod[2].plw)};
-      float* db[FUSED_PG_SLOTS] = {GG(m->n2_b), GG(m->n1_b), GG(m->mod[0].plb), GG(m->mod[1].plb), GG(m->mod[2].plb)};
-      x.rc = mmda_fused_pg_finish(WS(m->pg_parts), B, hs, dg, db, ss);
-    }
-    if (!x.rc && !x.deferred.empty()) x.rc = mmda_gemm_grouped(x.deferred.data(), (int)x.deferred.size(), ss);
-    x.deferred.clear();
-    // the bf16 operand copies that only the weight-gradient GEMMs read (hseq of both layers, nt form: transposed layer-2 inputs): here,
-    // where the side stream is idle beside the layer-2 recurrence, instead of in front of the loss kernels of the forward pass
-    if (!x.rc && mode == MMDA_BF16 && m->use_bf16_gemm && T > 0) {
-      mmda_convert_job cj[16];
-      const int nj = backward_only_jobs(m, cj);
-      x.rc = mmda_convert_bf16(cj, nj, ss);
-    }
-    // (Clip + Adam of the embedding rows this batch does not touch, here beside the layer-2 recurrence, measured slower: at B=32 its
-    // 170 MB stream slows the recurrence's hand-offs and the step by 14 us; behind the early optimizer pass, by 68 us.)
+    FusedBwdC f = {};
+    f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1;
+    f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.d_tcp = WS(m->d_tcp); f.d_scores = WS(m->d_scores); f.d_logits = WS(m->d_logits);
+    // flag join pending: d_tcp is all zeros (no ConfidNet gradients in that mode), but cleared by the side stream's chain, which
+    // this launch does not wait for -- NULL reads as zero
+    if (m->fj1) f.d_tcp = nullptr;
+    // the reconstruction term of stretch A's d_x6 chain, in workgroups of this launch (small batches: both sets fit the chip twice
+    // over; MMDA_FUSED_SPLIT=0: inside stretch A as before)
+    if (P.rec_hoisted) { f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.rec_part = WS(m->rec_part); }
+    f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(m->head_w); f.d_hfused = WS(m->d_hfused); f.ln2 = norm2_bwd();
+    f.pg_parts = WS(m->pg_parts);
+    rc = mmda_fused_bwd_c(&f, s);
   }
-  if (x.rc) return x.rc;
-  // encoders, top layer first
-  const float* xin[3] = {WS(m->mod[0].x), v, a};
-  // Layer 2's weight-gradient GEMMs run beside the layer-1 recurrent kernel on the side stream (faster than holding them back for
-  // one grouped launch with layer 1's after it).  The wave-autonomous recurrence runs one wave on each of ~110 CUs,
-  // raises its priority and reserves those CUs' whole LDS, so the GEMM's workgroups land on the other ~145 CUs; what the two still
-  // share is L2 and fabric bandwidth (the recurrence slows by ~30 us, the GEMMs' ~65 us leave the critical path).
-  std::vector<mmda_gemm_bf16_args> bside;
-  for (int l = 1; l >= 0; --l) {
-    mmda_lstm_desc desc[3];
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-      desc[i] = mmda_lstm_desc{};
-      desc[i].H = r.H; desc[i].gates = WS(md.gates[l]); desc[i].cstash = WS(md.c[l]); desc[i].hseq = WS(md.hseq[l]);
-      desc[i].wpack[0] = WS(r.pack_b[0]); desc[i].wpack[1] = WS(r.pack_b[1]);
-      desc[i].wpack_c[0] = m->packed_c_valid ? WS(r.pack_c[0]) : nullptr; desc[i].wpack_c[1] = m->packed_c_valid ? WS(r.pack_c[1]) : nullptr;
-      desc[i].utt = WS(md.d_utt); desc[i].layer = l; desc[i].d_hseq = l == 0 ? WS(md.d_hseq1) : nullptr;
-      desc[i].xchg = (m->use_cluster && md.xchg >= 0) ? (void*)WS(md.xchg) : nullptr; desc[i].epoch_base = m->epoch;
-      desc[i].gate_minor = m->gate_minor; desc[i].cell = c.rnncell;
+  if (P.ffn_fuse_bwd) {
+    if (!rc) {
+      FusedFfnBwd f = {};
+      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.d_f2 = WS(m->d_f2); f.f1 = WS(m->f1);
+      f.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f; f.l2_wT = WS(m->l2_wT); f.d_f1 = WS(m->d_f1); f.l1_wT = WS(m->l1_wT);
+      f.parts = WS(m->ffn_parts);
+      rc = mmda_fused_ffn_bwd(&f, s);
     }
-    // The wave-autonomous gate-minor kernel emits the gate gradients as bf16 (the operand of the input-gradient GEMM) -- and only
-    // as bf16: every consumer of dG in this mode is a bf16 GEMM (the transposed operand is re-laid-out from it).  The other
-    // kernels (barrier form: H > 320, ablation switches) write fp32 `gates` as before.
-    const bool kdg = mode == MMDA_BF16 && m->use_bf16_gemm && mmda_lstm_bwd_emits_dg_bf16(mode, 3, desc, B, T) != 0;
-    if (kdg)
-      for (int i = 0; i < 3; ++i) { desc[i].dg_bf16 = WS(m->mod[i].rnn[l].dgb); desc[i].dg_bf16_only = 1; }
-    m->epoch += (unsigned)T + 2u;
-    // the forward pass skipped the streaming backward packing because the resident-weights kernels were going to run: they must
-    if (!m->pack_b_valid && !mmda_lstm_resident_applicable(mode, 3, desc, B, T, 1)) return MMDA_EINVAL;
-    ev_rec(m, m->ev_bwd, l == 1 ? 2 : 3, 0, stream);
-    x.rc = mmda_lstm_bwd(mode, 3, desc, B, T, lengths, stream);
-    ev_rec(m, m->ev_bwd, l == 1 ? 2 : 3, 1, stream);
-    if (x.rc) return x.rc;
-    // All weight / input gradient GEMMs of this layer (three modalities) are independent.  Layer 2: d(normed) feeds the
-    // next recurrent kernel (main stream); its weight gradients run on the side stream underneath that kernel.
-    const bool bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
-    const bool bf_hh = bfg && (B % 8) == 0;        // the time-shifted views of dG^T / hseq^T start B elements into a row
-    std::vector<mmda_gemm_bf16_args> bmain;
-    // gate gradients -> bf16: transposed (A of every dW) and, where an input gradient is needed and the recurrent kernel did not
-    // write it itself, plain (A of dX).  Layer 2 with the kernel-written plain copy: only the weight-gradient GEMMs (side stream)
-    // read the transposed one, so the conversion goes to the side stream with them.
-    mmda_convert_job dgj[3];
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-      const bool plain = (l == 1 || i == 0) && !kdg;
-      dgj[i] = mmda_convert_job{WS(md.gates[l]), 8 * r.H, R, 8 * r.H, nullptr, plain ? WS(r.dgb) : nullptr, plain ? r.ldG : 0, WS(r.dgbT),
-                                m->ldR};
-      if (kdg) { dgj[i].src = WS(r.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
+  } else {
+    skinny_ffn_dx(true);
+  }
+  if (rc) return;
+  FusedBwdA f = {};
+  f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1;
+  if (P.ffn_fuse_bwd) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.d_x1 = WS(m->d_x1); }
+  f.ln1 = norm1_bwd();
+  f.d_attn_out = WS(m->d_attn_out); f.out_wT = WS(m->out_wT); f.d_ctx = WS(m->d_ctx);
+  f.qkv = WS(m->qkv); f.probs = WS(m->probs); f.d_qkv = WS(m->d_qkv); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
+  f.in_wT = WS(m->in_wT); f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.x6 = WS(m->x6); f.d_x6 = WS(m->d_x6);
+  if (P.rec_hoisted) f.rec_part = WS(m->rec_part);
+  f.priv_wT = WS(m->priv_wT); f.sh_wT = WS(m->sh_wT); f.d_orig = WS(m->d_orig);
+  for (int i = 0; i < 3; ++i) f.lnp[i] = proj_ln_bwd(i);
+  f.pg_parts = WS(m->pg_parts);
+  if (m->fj1) {
+    // Waiting workgroups hold their CU's LDS (104 KB each): with one on every CU the side stream's kernels could not start, and
+    // the wait would never end -- on the device only while the stretch leaves most of the chip free (P.fj_device); otherwise the
+    // event, here (two launches later than the end of the forward pass, where it used to be: the loss chain is the longer one at
+    // large B)
+    if (P.fj_device) { f.wait_flag = m->jflags; f.wait_value = m->jval[0]; f.wait_err = m->jflags + 2; }
+    else rc = flag_join_fallback(m, s);
+    m->fj1 = 0;
+  }
+  if (!rc) rc = mmda_fused_bwd_a(&f, s);
+  skinny_proj_dx(true);
+}
+
+// ... as stand-alone row-skinny launches (MMDA_ROW_FUSE=0, the adversarial discriminator, hidden != 128, or no K-major copies)
+void Pass::bwd_fusion_skinny() {
+  const bool wt = m->wT_valid != 0;                   // K-major weight copies from this step's forward (side stream, joined there)
+  mmda_skinny_args g[8];
+  rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
+                        s);
+  g[0] = sk_dxw(wt, B, NC, 6 * hs, WS(m->d_logits), NC, WS(m->head_wT), PP(m->head_w), WS(m->d_hfused), 6 * hs, 0);
+  sk_launch(*this, g, 1);
+  const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
+  if (!rc) rc = mmda_layernorm_bwd(&l2, s);
+  skinny_ffn_dx(wt);
+  // norm1 + self-attention
+  if (!rc) rc = mmda_layernorm_bwd(&l1, s);
+  int n = 0;
+  g[n++] = sk_dxw(wt, 6 * B, hs, hs, WS(m->d_attn_out), hs, WS(m->out_wT), PP(m->out_w), WS(m->d_ctx), hs, 0);
+  if (!c.use_cmd_sim) g[n++] = sk_dxw(wt, 3 * B, 3, hs, WS(m->d_dom), 3, WS(m->d2_wT), PP(m->d2_w), WS(m->d_dom_h), hs, 0);
+  sk_launch(*this, g, n);
+  if (!rc) rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, s);
+  // adversarial branch: the REVERSED gradient into the shared codes (functions.py:17-21)
+  if (!c.use_cmd_sim) {
+    if (!rc) {
+      const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, true);
+      rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-    const bool tn = bfg && m->tn_wgrad;   // weight gradients straight from dG / inputs / hseq as they lie (no dG^T)
-    if (tn && !kdg) return MMDA_EINVAL;                // (forward() set tn_wgrad only where the recurrent kernel writes bf16 dG)
-    const bool dg_on_side = bfg && kdg && l == 1 && m->use_side && !tn;
-    if (bfg && !dg_on_side && !tn) {
-      x.rc = mmda_convert_bf16(dgj, 3, stream);
-      if (x.rc) return x.rc;
+    g[0] = sk_dxw(wt, 3 * B, hs, hs, WS(m->d_dom_z), hs, WS(m->d1_wT), PP(m->d1_w), WS(m->d_x6 + 3 * BH), hs, 1);
+    g[0].alpha = -c.reverse_grad_weight;
+    sk_launch(*this, g, 1);
+  }
+  // d_x6[token j] = (d_x6 + d_qkv[j] W_in + d_recon[j % 3] W_rec[j % 3]) * s (1 - s): the q/k/v projection's and the
+  // reconstruction's input gradients (the latter flows into BOTH private and shared) and the sigmoid backward, six problems
+  for (int j = 0; j < 6; ++j) {
+    const int i = j % 3;
+    g[j] = sk_dxw(wt, B, 3 * hs, hs, WS(m->d_qkv + (int64_t)j * B * 3 * hs), 3 * hs, WS(m->in_wT), PP(m->in_w), WS(m->d_x6 + j * BH), hs, 1);
+    g[j].K2 = hs; g[j].A_2nd = WS(m->d_recon + i * BH); g[j].lda_2nd = hs; g[j].ldb_2nd = hs;
+    g[j].B_2nd = wt ? WS(m->rec_wT + (int64_t)i * hs * hs) : PP(m->rec_w + (int64_t)i * hs * hs);
+    g[j].dsig = WS(m->x6 + j * BH); g[j].lddsig = hs;
+  }
+  sk_launch(*this, g, 6);
+  // d_orig[i] += d_private[i] W_priv[i] + d_shared[i] W_shared
+  for (int i = 0; i < 3; ++i) {
+    g[i] = sk_dxw(wt, B, hs, hs, WS(m->d_x6 + i * BH), hs, WS(m->priv_wT + (int64_t)i * hs * hs), PP(m->priv_w + (int64_t)i * hs * hs),
+                  WS(m->d_orig + i * BH), hs, 1);
+    g[i].K2 = hs; g[i].A_2nd = WS(m->d_x6 + (3 + i) * BH); g[i].lda_2nd = hs; g[i].B_2nd = wt ? WS(m->sh_wT) : PP(m->sh_w); g[i].ldb_2nd = hs;
+  }
+  sk_launch(*this, g, 3);
+  // projections
+  if (!rc) {
+    mmda_ln_bwd_args l[3];
+    for (int i = 0; i < 3; ++i) l[i] = proj_ln_bwd(i);
+    rc = mmda_layernorm_bwd_multi(l, 3, s);
+  }
+  skinny_proj_dx(wt);
+}
+
+// ... many rows: the tiled generic kernel
+void Pass::bwd_fusion_tiled() {
+  // heads
+  rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
+                        s);
+  lin_dx(*this, fmode, B, NC, 6 * hs, WS(m->d_logits), PP(m->head_w), WS(m->d_hfused), 0);
+  // norm2 + FFN
+  const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
+  if (!rc) rc = mmda_layernorm_bwd(&l2, s);
+  {
+    // d f1 = (d f2 W2) * [f1 > 0] / (1-p): f1 is stored post-relu, post-dropout, so f1 > 0 <=> kept and pre-activation > 0
+    mmda_gemm_args e = {};
+    e.gate = WS(m->f1); e.ldgate = FFN; e.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
+    gemm(*this, fmode, 0, 0, 6 * B, FFN, hs, WS(m->d_f2), hs, PP(m->l2_w), FFN, WS(m->d_f1), FFN, nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, &e);
+  }
+  lin_dx(*this, fmode, 6 * B, FFN, hs, WS(m->d_f1), PP(m->l1_w), WS(m->d_x1), 1);
+  // norm1 + self-attention
+  if (!rc) rc = mmda_layernorm_bwd(&l1, s);
+  lin_dx(*this, fmode, 6 * B, hs, hs, WS(m->d_attn_out), PP(m->out_w), WS(m->d_ctx), 0);
+  if (!rc) rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, s);
+  lin_dx(*this, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), PP(m->in_w), WS(m->d_x6), 1);
+  // adversarial branch: the REVERSED gradient into the shared codes (functions.py:17-21)
+  if (!c.use_cmd_sim) {
+    lin_dx(*this, fmode, 3 * B, 3, hs, WS(m->d_dom), PP(m->d2_w), WS(m->d_dom_h), 0);
+    if (!rc) {
+      const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, true);
+      rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-    x.deferring = (l == 1);
-    group_begin(x);
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-      const int H = r.H, G8 = 8 * H;
-      const float* dG = WS(md.gates[l]);
-      const float* in = l == 0 ? xin[i] : WS(md.normed);
-      std::vector<mmda_gemm_bf16_args>& wq = (l == 1) ? bside : bmain;      // weight gradients: side stream for layer 2
-      const unsigned short* dgT = reinterpret_cast<const unsigned short*>(WS(r.dgbT));
-      const unsigned short* hT = reinterpret_cast<const unsigned short*>(WS(r.hbT));
-      // dW_ih (both directions stacked); db_ih = db_hh = column sums of dG ride along as a virtual ones-column
-      if (bfg) {
+    mmda_gemm_args e = {};
+    e.alpha = -c.reverse_grad_weight;
+    gemm(*this, fmode, 0, 0, 3 * B, hs, hs, WS(m->d_dom_z), hs, PP(m->d1_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
+  }
+  // reconstruct: d(private+shared) goes to both halves of d_x6
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 3, BH,
+       (int64_t)hs * hs, BH);
+  // sigmoid of private/shared
+  if (!rc) rc = mmda_sigmoid_bwd_inplace(WS(m->d_x6), WS(m->x6), 6 * BH, s);
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_x6), hs, PP(m->priv_w), hs, WS(m->d_orig), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
+  lin_dx(*this, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), PP(m->sh_w), WS(m->d_orig), 1);
+  // projections
+  for (int i = 0; i < 3 && !rc; ++i) {
+    Mod& md = m->mod[i];
+    const mmda_ln_bwd_args l = proj_ln_bwd(i);
+    rc = mmda_layernorm_bwd(&l, s);
+    lin_dx(*this, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), PP(md.pw), WS(md.d_utt), 0);
+  }
+}
+
+// The fusion block's weight gradients, the same list for every form of its dX chain: head, l2, l1, out, in, [d2, d1], rec, priv, sh,
+// projections 0-2.  One grouped launch on the side stream (bwd_side_chain) once the dX chain, the critical path, is through.
+void Pass::fusion_wgrads() {
+  deferring = true;
+  lin_dw(*this, fmode, B, NC, 6 * hs, WS(m->d_logits), WS(m->hfused), GG(m->head_w), GG(m->head_b));
+  lin_dw(*this, fmode, 6 * B, hs, FFN, WS(m->d_f2), WS(m->f1), GG(m->l2_w), GG(m->l2_b));
+  lin_dw(*this, fmode, 6 * B, FFN, hs, WS(m->d_f1), WS(m->x1), GG(m->l1_w), GG(m->l1_b));
+  lin_dw(*this, fmode, 6 * B, hs, hs, WS(m->d_attn_out), WS(m->ctx), GG(m->out_w), GG(m->out_b));
+  lin_dw(*this, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), WS(m->x6), GG(m->in_w), GG(m->in_b));
+  if (!c.use_cmd_sim) {
+    lin_dw(*this, fmode, 3 * B, 3, hs, WS(m->d_dom), WS(m->dom_h), GG(m->d2_w), GG(m->d2_b));
+    lin_dw(*this, fmode, 3 * B, hs, hs, WS(m->d_dom_z), WS(m->x6 + 3 * BH), GG(m->d1_w), GG(m->d1_b));
+  }
+  mmda_gemm_args e = {};
+  e.bias_grad = GG(m->rec_b);      // strideBias = hs: one bias gradient per batched problem
+  gemm(*this, fmode, 1, 0, hs, hs, B, WS(m->d_recon), hs, WS(m->rsum), hs, GG(m->rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
+       hs, &e);
+  e.bias_grad = GG(m->priv_b);
+  gemm(*this, fmode, 1, 0, hs, hs, B, WS(m->d_x6), hs, WS(m->orig), hs, GG(m->priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
+       hs, &e);
+  lin_dw(*this, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), WS(m->orig), GG(m->sh_w), GG(m->sh_b));
+  for (int i = 0; i < 3; ++i)
+    lin_dw(*this, fmode, B, hs, 4 * m->mod[i].H, WS(m->d_z + i * BH), WS(m->mod[i].utt), GG(m->mod[i].pw), GG(m->mod[i].pb));
+  deferring = false;
+}
+
+// side stream: private + shared (the reconstruction's input, needed only by its weight gradient) and every deferred
+// weight-gradient GEMM of the fusion block
+void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* lengths) {
+  void* ss = nullptr;
+  rc = side_fork(m, s, &ss);
+  if (!rc && m->misc_deferred) {
+    // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
+    rc = mmda_loss_misc(WS(m->scores), WS(m->tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
+                          WS(m->recon), WS(m->orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(m->losses), c.diff_weight,
+                          c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, ss);
+    m->misc_deferred = nullptr;
+  }
+  if (!rc && P.skinny) rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, ss);
+  // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
+  m->esort_valid = 0;
+  if (!rc && P.sort_early) {
+    rc = mmda_embed_sort_ids(t_ids, B * m->T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
+    if (!rc && ss != s) {
+      hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
+      if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
+    }
+    m->esort_valid = rc ? 0 : (ss != s ? 2 : 1);
+  }
+  if (!rc && pg_pending) {
+    // gamma / beta gradients of the five LayerNorms the fused stretches walked: per-sample partials added in sample order
+    float* dg[FUSED_PG_SLOTS] = {GG(m->n2_w), GG(m->n1_w), GG(m->mod[0].plw), GG(m->mod[1].plw), GG(m->mod[2].plw)};
+    float* db[FUSED_PG_SLOTS] = {GG(m->n2_b), GG(m->n1_b), GG(m->mod[0].plb), GG(m->mod[1].plb), GG(m->mod[2].plb)};
+    rc = mmda_fused_pg_finish(WS(m->pg_parts), B, hs, dg, db, ss);
+  }
+  if (!rc && !deferred.empty()) rc = mmda_gemm_grouped(deferred.data(), (int)deferred.size(), ss);
+  deferred.clear();
+  // the bf16 operand copies that only the weight-gradient GEMMs read (hseq of both layers, nt form: transposed layer-2 inputs): here,
+  // where the side stream is idle beside the layer-2 recurrence, instead of in front of the loss kernels of the forward pass
+  if (!rc && P.bfg && m->T > 0) {
+    mmda_convert_job cj[16];
+    const int nj = backward_only_jobs(m, cj);
+    rc = mmda_convert_bf16(cj, nj, ss);
+  }
+  // (Clip + Adam of the embedding rows this batch does not touch, here beside the layer-2 recurrence, measured slower: at B=32 its
+  // 170 MB stream slows the recurrence's hand-offs and the step by 14 us; behind the early optimizer pass, by 68 us.)
+}
+
+// encoder layer l, top layer first: the backward recurrence, then the weight and input gradient GEMMs of the three modalities.
+// Layer 2's weight-gradient GEMMs run beside the layer-1 recurrent kernel on the side stream (faster than holding them back for
+// one grouped launch with layer 1's after it).  The wave-autonomous recurrence runs one wave on each of ~110 CUs,
+// raises its priority and reserves those CUs' whole LDS, so the GEMM's workgroups land on the other ~145 CUs; what the two still
+// share is L2 and fabric bandwidth (the recurrence slows by ~30 us, the GEMMs' ~65 us leave the critical path).
+void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_ids, const int32_t* lengths) {
+  mmda_lstm_desc desc[3];
+  for (int i = 0; i < 3; ++i) desc[i] = lstm_desc(m, i, l, true, P.gm, P.want_c);
+  // The wave-autonomous gate-minor kernel emits the gate gradients as bf16 (the operand of the input-gradient GEMM) -- and only
+  // as bf16: every consumer of dG in this mode is a bf16 GEMM (the transposed operand is re-laid-out from it).  The other
+  // kernels (barrier form: H > 320, ablation switches) write fp32 `gates` as before.
+  if (P.kdg)
+    for (int i = 0; i < 3; ++i) { desc[i].dg_bf16 = WS(m->mod[i].rnn[l].dgb); desc[i].dg_bf16_only = 1; }
+  m->epoch += (unsigned)T + 2u;
+  // the forward pass skipped the streaming backward packing because the resident-weights kernels were going to run: they must
+  if (!P.want_b && !mmda_lstm_resident_applicable(mode, 3, desc, B, T, 1)) { rc = MMDA_EINVAL; return; }
+  ev_rec(m, m->ev_bwd, l == 1 ? 2 : 3, 0, s);
+  rc = mmda_lstm_bwd(mode, 3, desc, B, T, lengths, s);
+  ev_rec(m, m->ev_bwd, l == 1 ? 2 : 3, 1, s);
+  if (rc) return;
+  // All weight / input gradient GEMMs of this layer (three modalities) are independent.  Layer 2: d(normed) feeds the
+  // next recurrent kernel (main stream); its weight gradients run on the side stream underneath that kernel.
+  const bool bfg = P.bfg, bf_hh = bfg && (B % 8) == 0;        // the time-shifted views of dG^T / hseq^T start B elements into a row
+  std::vector<mmda_gemm_bf16_args> bmain, bside;
+  // gate gradients -> bf16: transposed (A of every dW) and, where an input gradient is needed and the recurrent kernel did not
+  // write it itself, plain (A of dX).  Layer 2 with the kernel-written plain copy: only the weight-gradient GEMMs (side stream)
+  // read the transposed one, so the conversion goes to the side stream with them.
+  mmda_convert_job dgj[3];
+  for (int i = 0; i < 3; ++i) {
+    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+    const bool plain = (l == 1 || i == 0) && !P.kdg;
+    dgj[i] = mmda_convert_job{WS(md.gates[l]), 8 * r.H, R, 8 * r.H, nullptr, plain ? WS(r.dgb) : nullptr, plain ? r.ldG : 0, WS(r.dgbT),
+                              m->ldR};
+    if (P.kdg) { dgj[i].src = WS(r.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
+  }
+  const bool tn = P.tn_wgrad;            // weight gradients straight from dG / inputs / hseq as they lie (no dG^T); implies kdg
+  const bool dg_on_side = P.kdg && l == 1 && m->use_side && !tn;
+  if (bfg && !dg_on_side && !tn) {
+    rc = mmda_convert_bf16(dgj, 3, s);
+    if (rc) return;
+  }
+  deferring = (l == 1);
+  group_begin(*this);
+  for (int i = 0; i < 3; ++i) {
+    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+    const int H = r.H, G8 = 8 * H;
+    const float* dG = WS(md.gates[l]);
+    const float* in = l == 0 ? xin[i] : WS(md.normed);
+    std::vector<mmda_gemm_bf16_args>& wq = (l == 1) ? bside : bmain;      // weight gradients: side stream for layer 2
+    const unsigned short* dgT = reinterpret_cast<const unsigned short*>(WS(r.dgbT));
+    const unsigned short* hT = reinterpret_cast<const unsigned short*>(WS(r.hbT));
+    // dW_ih (both directions stacked); db_ih = db_hh = column sums of dG ride along as a virtual ones-column
+    if (bfg) {
+      mmda_gemm_bf16_args g = {};
+      g.M = G8; g.N = r.D; g.K = R; g.A = dgT; g.lda = m->ldR; g.B = WS(r.xbT); g.ldb = m->ldR; g.C = gW_ih(m, r); g.ldc = r.D;
+      g.accumulate = 1; g.bias_grad = gB_ih(m, r); g.bias_grad2 = gB_hh(m, r); g.perm_m_H = P.gm ? H : 0;
+      if (tn) { g.tn = 1; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.xb); g.ldb = r.ldD; }
+      wq.push_back(g);
+    } else {
+      mmda_gemm_args e = {};
+      e.bias_grad = gB_ih(m, r); e.bias_grad2 = gB_hh(m, r);
+      gemm(*this, mode, 1, 0, G8, r.D, R, dG, G8, in, r.D, gW_ih(m, r), r.D, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
+    }
+    // dW_hh: forward direction pairs dG[t] with h[t-1]; reverse direction pairs dG[t] with h[t+1] (zero past len)
+    if (T > 1) {
+      if (bf_hh) {
         mmda_gemm_bf16_args g = {};
-        g.M = G8; g.N = r.D; g.K = R; g.A = dgT; g.lda = m->ldR; g.B = WS(r.xbT); g.ldb = m->ldR; g.C = gW_ih(m, r); g.ldc = r.D;
-        g.accumulate = 1; g.bias_grad = gB_ih(m, r); g.bias_grad2 = gB_hh(m, r); g.perm_m_H = m->gate_minor ? H : 0;
-        if (tn) { g.tn = 1; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.xb); g.ldb = r.ldD; }
-        wq.push_back(g);
-      } else {
-        mmda_gemm_args e = {};
-        e.bias_grad = gB_ih(m, r); e.bias_grad2 = gB_hh(m, r);
-        gemm(x, mode, 1, 0, G8, r.D, R, dG, G8, in, r.D, gW_ih(m, r), r.D, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
-      }
-      // dW_hh: forward direction pairs dG[t] with h[t-1]; reverse direction pairs dG[t] with h[t+1] (zero past len)
-      if (T > 1) {
-        if (bf_hh) {
-          mmda_gemm_bf16_args g = {};
-          g.M = 4 * H; g.N = H; g.K = (T - 1) * B; g.lda = m->ldR; g.ldb = m->ldR; g.ldc = H; g.accumulate = 1;
-          g.perm_m_H = m->gate_minor ? H : 0;
-          if (tn) {
-            // rows of dG / hseq are (t, b): the forward direction pairs rows t B + b of dG with rows (t - 1) B + b of h, the reverse
-            // direction rows t B + b with rows (t + 1) B + b
-            const unsigned short* dg = reinterpret_cast<const unsigned short*>(WS(r.dgb));
-            const unsigned short* h0 = reinterpret_cast<const unsigned short*>(WS(r.hbp[0]));
-            const unsigned short* h1 = reinterpret_cast<const unsigned short*>(WS(r.hbp[1]));
-            g.tn = 1; g.lda = r.ldG; g.ldb = r.ldH;
-            g.A = dg + (int64_t)B * r.ldG; g.B = h0; g.C = gW_hh(m, r, 0);
-            wq.push_back(g);
-            g.A = dg + 4 * H; g.B = h1 + (int64_t)B * r.ldH; g.C = gW_hh(m, r, 1);
-            wq.push_back(g);
-          } else {
+        g.M = 4 * H; g.N = H; g.K = (T - 1) * B; g.lda = m->ldR; g.ldb = m->ldR; g.ldc = H; g.accumulate = 1;
+        g.perm_m_H = P.gm ? H : 0;
+        if (tn) {
+          // rows of dG / hseq are (t, b): the forward direction pairs rows t B + b of dG with rows (t - 1) B + b of h, the reverse
+          // direction rows t B + b with rows (t + 1) B + b
+          const unsigned short* dg = reinterpret_cast<const unsigned short*>(WS(r.dgb));
+          const unsigned short* h0 = reinterpret_cast<const unsigned short*>(WS(r.hbp[0]));
+          const unsigned short* h1 = reinterpret_cast<const unsigned short*>(WS(r.hbp[1]));
+          g.tn = 1; g.lda = r.ldG; g.ldb = r.ldH;
+          g.A = dg + (int64_t)B * r.ldG; g.B = h0; g.C = gW_hh(m, r, 0);
+          wq.push_back(g);
+          g.A = dg + 4 * H; g.B = h1 + (int64_t)B * r.ldH; g.C = gW_hh(m, r, 1);
+          wq.push_back(g);
+        } else {
           g.A = dgT + B; g.B = hT; g.C = gW_hh(m, r, 0);
           wq.push_back(g);
           g.A = dgT + (int64_t)4 * H * m->ldR; g.B = hT + (int64_t)H * m->ldR + B; g.C = gW_hh(m, r, 1);
           wq.push_back(g);
-          }
-        } else {
-          const float* hs_ = WS(md.hseq[l]);
-          gemm(x, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + (int64_t)B * G8, G8, hs_, 2 * H, gW_hh(m, r, 0), H, nullptr, nullptr, 1);
-          gemm(x, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + 4 * H, G8, hs_ + (int64_t)B * 2 * H + H, 2 * H, gW_hh(m, r, 1), H, nullptr,
-               nullptr, 1);
         }
-      }
-      // d(normed) = dG W_ih (layer 2) / d(embedding rows) (text layer 1)
-      if (l == 1 || i == 0) {
-        float* dst = l == 1 ? WS(md.d_normed) : WS(md.d_x);
-        if (bfg) {
-          mmda_gemm_bf16_args g = {};
-          g.M = R; g.N = r.D; g.K = G8; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.wbT); g.ldb = r.ldG; g.C = dst; g.ldc = r.D;
-          bmain.push_back(g);
-        } else {
-          gemm(x, mode, 0, 0, R, r.D, G8, dG, G8, rW_ih(m, r), r.D, dst, r.D);
-        }
+      } else {
+        const float* hs_ = WS(md.hseq[l]);
+        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + (int64_t)B * G8, G8, hs_, 2 * H, gW_hh(m, r, 0), H, nullptr, nullptr, 1);
+        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + 4 * H, G8, hs_ + (int64_t)B * 2 * H + H, 2 * H, gW_hh(m, r, 1), H, nullptr,
+             nullptr, 1);
       }
     }
-    group_end(x);
-    x.deferring = false;
-    if (!x.rc && !bmain.empty()) x.rc = mmda_gemm_bf16_grouped(bmain.data(), (int)bmain.size(), stream);
-    if (l == 1 && !x.rc) {
-      // the inter-layer LayerNorm backward gives d(hseq of layer 1): input gradients on the main stream (they feed the next
-      // recurrent kernel); gamma/beta gradients and this layer's weight-gradient GEMMs on the side stream underneath it
-      mmda_ln_bwd_args lb[3];
-      for (int i = 0; i < 3; ++i) {
-        Mod& md = m->mod[i];
-        lb[i] = mmda_ln_bwd_args{};
-        lb[i].rows = R; lb[i].n = 2 * md.H; lb[i].dy = WS(md.d_normed); lb[i].x = WS(md.hseq[0]); lb[i].gamma = PP(md.ln_w);
-        lb[i].mean = WS(md.ln_mean); lb[i].rstd = WS(md.ln_rstd); lb[i].d_x = WS(md.d_hseq1);
-      }
-      // (the input-gradient launch goes out BEFORE the fork: it reads the LayerNorm weights, which the early optimizer step below may
-      // update on the side stream -- the fork orders the side stream behind it)
-      // 16-byte form (norm.hip): the d_x launch leaves the gamma / beta gradients as per-block partials on its way (it reads dy and x
-      // anyway) and the side stream only adds them up -- instead of a second pass over dy and x there (100 us at B = 256)
-      const bool ln_split = mmda_ln_bwd_parts_applies(lb, 3) &&
-                            mmda_ln_parts_floats(lb, 3) <= (int64_t)512 * 2 * 2 * (m->mod[0].H + m->mod[1].H + m->mod[2].H);
-      if (ln_split) {
-        for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); }
-        x.rc = mmda_ln_bwd_parts(lb, 3, WS(m->ln_parts), stream);
+    // d(normed) = dG W_ih (layer 2) / d(embedding rows) (text layer 1)
+    if (l == 1 || i == 0) {
+      float* dst = l == 1 ? WS(md.d_normed) : WS(md.d_x);
+      if (bfg) {
+        mmda_gemm_bf16_args g = {};
+        g.M = R; g.N = r.D; g.K = G8; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.wbT); g.ldb = r.ldG; g.C = dst; g.ldc = r.D;
+        bmain.push_back(g);
       } else {
-        x.rc = mmda_layernorm_bwd_multi(lb, 3, stream);
-      }
-      void* ss = nullptr;
-      if (!x.rc) x.rc = side_fork(m, stream, &ss);
-      for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); if (!ln_split) lb[i].d_x = nullptr; }
-      if (!x.rc && dg_on_side) x.rc = mmda_convert_bf16(dgj, 3, ss);
-      if (!x.rc) x.rc = ln_split ? mmda_ln_parts_finish(lb, 3, WS(m->ln_parts), ss) : mmda_layernorm_param_grads(lb, 3, ss);
-      if (!x.rc && !x.deferred.empty()) x.rc = mmda_gemm_grouped(x.deferred.data(), (int)x.deferred.size(), ss);
-      const bool l2_early = !bside.empty();
-      if (!x.rc && l2_early) { x.rc = mmda_gemm_bf16_grouped(bside.data(), (int)bside.size(), ss); bside.clear(); }
-      x.deferred.clear();
-      // Everything issued so far on either stream is final for the fusion block, the LayerNorms and -- when its weight-gradient
-      // GEMMs just went out and no GRU re-layout follows -- layer 2: data-parallel ranks may start reducing that prefix now,
-      // beside the layer-1 recurrence (mmda_misa_wait_early_grads).
-      if (!x.rc) {
-        if (!m->ev_early && hipEventCreateWithFlags(&m->ev_early, hipEventDisableTiming) != hipSuccess) x.rc = MMDA_ELAUNCH;
-        if (!x.rc && hipEventRecord(m->ev_early, (hipStream_t)ss) != hipSuccess) x.rc = MMDA_ELAUNCH;
-        m->early_floats = (l2_early && !is_gru(m) && mode == MMDA_BF16 && m->use_bf16_gemm) ? m->rnn1_begin : m->rnn2_begin;
-        m->early_valid = 1;
-        // Single-GPU fused step: clip + Adam of that prefix right here, beside the layer-1 recurrence (nothing issued after this
-        // point reads those fp32 parameters: the remaining GEMMs of a bf16 step read bf16 copies made in the forward pass, and in
-        // the other modes the prefix ends in front of the recurrent layers).  The side stream is a real second stream only when
-        // use_side is on; otherwise this is simply the same work in front of the recurrence.
-        if (!x.rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
-          x.rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
-          if (!x.rc) m->adam_early_done = m->early_floats;
-        }
-      }
-    } else if (!x.rc) {
-      // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
-      if (m->esort_valid) {
-        if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
-          hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, m->jflags + 3, m->esort_val, m->jflags + 2);
-          if (hipGetLastError() != hipSuccess) x.rc = MMDA_ELAUNCH;
-        }
-        if (!x.rc)
-          x.rc = mmda_embed_scatter_presorted(GG(m->embed), reinterpret_cast<const unsigned*>(WS(m->esort)), R, c.d_t, c.vocab,
-                                              WS(m->mod[0].d_x), stream);
-        m->esort_valid = 0;
-      } else {
-        x.rc = mmda_embed_scatter_add_masked(GG(m->embed), t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, stream);
+        gemm(*this, mode, 0, 0, R, r.D, G8, dG, G8, rW_ih(m, r), r.D, dst, r.D);
       }
     }
-    if (x.rc) return x.rc;
   }
+  group_end(*this);
+  deferring = false;
+  if (!rc && !bmain.empty()) rc = mmda_gemm_bf16_grouped(bmain.data(), (int)bmain.size(), s);
+  if (rc) return;
+  if (l == 1) {
+    // the inter-layer LayerNorm backward gives d(hseq of layer 1): input gradients on the main stream (they feed the next
+    // recurrent kernel); gamma/beta gradients and this layer's weight-gradient GEMMs on the side stream underneath it
+    mmda_ln_bwd_args lb[3];
+    for (int i = 0; i < 3; ++i) {
+      Mod& md = m->mod[i];
+      lb[i] = mmda_ln_bwd_args{};
+      lb[i].rows = R; lb[i].n = 2 * md.H; lb[i].dy = WS(md.d_normed); lb[i].x = WS(md.hseq[0]); lb[i].gamma = PP(md.ln_w);
+      lb[i].mean = WS(md.ln_mean); lb[i].rstd = WS(md.ln_rstd); lb[i].d_x = WS(md.d_hseq1);
+    }
+    // (the input-gradient launch goes out BEFORE the fork: it reads the LayerNorm weights, which the early optimizer step below may
+    // update on the side stream -- the fork orders the side stream behind it)
+    // 16-byte form (norm.hip): the d_x launch leaves the gamma / beta gradients as per-block partials on its way (it reads dy and x
+    // anyway) and the side stream only adds them up -- instead of a second pass over dy and x there (100 us at B = 256)
+    const bool ln_split = mmda_ln_bwd_parts_applies(lb, 3) &&
+                          mmda_ln_parts_floats(lb, 3) <= (int64_t)512 * 2 * 2 * (m->mod[0].H + m->mod[1].H + m->mod[2].H);
+    if (ln_split) {
+      for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); }
+      rc = mmda_ln_bwd_parts(lb, 3, WS(m->ln_parts), s);
+    } else {
+      rc = mmda_layernorm_bwd_multi(lb, 3, s);
+    }
+    void* ss = nullptr;
+    if (!rc) rc = side_fork(m, s, &ss);
+    for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); if (!ln_split) lb[i].d_x = nullptr; }
+    if (!rc && dg_on_side) rc = mmda_convert_bf16(dgj, 3, ss);
+    if (!rc) rc = ln_split ? mmda_ln_parts_finish(lb, 3, WS(m->ln_parts), ss) : mmda_layernorm_param_grads(lb, 3, ss);
+    if (!rc && !deferred.empty()) rc = mmda_gemm_grouped(deferred.data(), (int)deferred.size(), ss);
+    const bool l2_early = !bside.empty();
+    if (!rc && l2_early) { rc = mmda_gemm_bf16_grouped(bside.data(), (int)bside.size(), ss); bside.clear(); }
+    deferred.clear();
+    // Everything issued so far on either stream is final for the fusion block, the LayerNorms and -- when its weight-gradient
+    // GEMMs just went out and no GRU re-layout follows -- layer 2: data-parallel ranks may start reducing that prefix now,
+    // beside the layer-1 recurrence (mmda_misa_wait_early_grads).
+    if (rc) return;
+    if (!m->ev_early && hipEventCreateWithFlags(&m->ev_early, hipEventDisableTiming) != hipSuccess) rc = MMDA_ELAUNCH;
+    if (!rc && hipEventRecord(m->ev_early, (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
+    m->early_floats = (l2_early && !is_gru(m) && P.bfg) ? m->rnn1_begin : m->rnn2_begin;
+    m->early_valid = 1;
+    // Single-GPU fused step: clip + Adam of that prefix right here, beside the layer-1 recurrence (nothing issued after this
+    // point reads those fp32 parameters: the remaining GEMMs of a bf16 step read bf16 copies made in the forward pass, and in
+    // the other modes the prefix ends in front of the recurrent layers).  The side stream is a real second stream only when
+    // use_side is on; otherwise this is simply the same work in front of the recurrence.
+    if (!rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
+      rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
+      if (!rc) m->adam_early_done = m->early_floats;
+    }
+  } else {
+    // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
+    if (m->esort_valid) {
+      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
+        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
+        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
+      }
+      if (!rc)
+        rc = mmda_embed_scatter_presorted(GG(m->embed), reinterpret_cast<const unsigned*>(WS(m->esort)), R, c.d_t, c.vocab,
+                                          WS(m->mod[0].d_x), s);
+      m->esort_valid = 0;
+    } else {
+      rc = mmda_embed_scatter_add_masked(GG(m->embed), t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                                  void* stream) {
+  if (check_ready(m) || !m->G || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
+  if (m->plan.inf) return MMDA_EINVAL;                  // the last forward was an evaluation pass: nothing was stashed
+  m->early_valid = 0;
+  Pass x(m, stream);
+  const StepPlan& P = m->plan;
+  // the fused stretches read the K-major weight copies this step's forward made (side stream, joined there)
+  const bool row_fuse = P.row_fuse && m->wT_valid;
+  if (m->fj1 && !row_fuse) { x.rc = flag_join_fallback(m, stream); m->fj1 = 0; if (x.rc) return x.rc; }     // (no kernel here waits on the device)
+  if (row_fuse) x.bwd_fusion_fused();
+  else if (P.skinny) x.bwd_fusion_skinny();
+  else x.bwd_fusion_tiled();
+  x.fusion_wgrads();
+  if (x.rc) return x.rc;
+  x.bwd_side_chain(row_fuse, t_ids, lengths);
+  const float* xin[3] = {WS(m->mod[0].x), v, a};
+  for (int l = 1; l >= 0 && !x.rc; --l) x.bwd_encoder_layer(l, xin, t_ids, lengths);
+  if (x.rc) return x.rc;
   if (!m->ev.empty()) { if (m->ev_seen_b % m->ev_stride == 0) m->ev_bwd++; m->ev_seen_b++; }
-  // every gradient is complete on `stream` when backward returns -- or, in a fused training step whose last optimizer launch can wait
-  // on the device (see mmda_misa::jflags), when that launch completes
+  // every gradient is complete on `stream` when backward returns -- or, in a fused training step whose last optimizer launch can
+  // wait on the device (see mmda_misa::jflags), when that launch completes
   // (only where every gradient the side stream computes lies in the prefix it also stepped -- the bf16 step, whose layer-2 weight
   //  gradients ran there in front of the early optimizer pass: the launch that waits READS the rest of the bucket before it waits)
-  if (!x.rc && m->flag_join_ok && m->adam_early_on && !is_gru(m) && m->use_side && m->side_pending && m->jflags &&
-      m->adam_early_done > 0 && m->adam_early_done == m->rnn1_begin) {
+  if (P.fj_on && m->adam_early_on && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
+      m->adam_early_done == m->rnn1_begin) {
     x.rc = side_flag_signal(m, 1);
     m->fj2 = x.rc ? 0 : 1;
     return x.rc;
   }
-  if (!x.rc) x.rc = side_join(m, stream);
+  x.rc = side_join(m, stream);
   if (!x.rc && is_gru(m)) {                    // fold the four-slot weight gradients into the torch-layout gradient buffer
     mmda_gru_pad_job gj[MMDA_GRU_PAD_MAX];
     int n = gru_jobs(m, m->G, true, gj);
@@ -1899,8 +1898,7 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   m->zero_grad_pending = m->T > 0 ? 1 : 0;
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
-  static const int flag_join_on = mmda_env_int("MMDA_FLAG_JOIN", 1);
-  m->flag_join_ok = (flag_join_on && m->use_side) ? 1 : 0; m->fj1 = m->fj2 = 0;
+  m->fj1 = m->fj2 = 0;
   int rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
   if (rc) return rc;
   rc = mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
@@ -1912,7 +1910,7 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   // (the early optimizer pass beside the layer-1 recurrence: faster than one launch for the whole bucket at the end)
   m->adam_early_on = do_adam ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
   rc = mmda_misa_backward(m, t_ids, v, a, lengths, stream);
-  m->adam_early_on = 0; m->flag_join_ok = 0;
+  m->adam_early_on = 0;
   if (rc) return rc;
   if (m->fj1) { rc = flag_join_fallback(m, stream); m->fj1 = 0; if (rc) return rc; }      // (no stretch took it over: cannot happen)
   if (m->fj2 && !do_adam) { rc = flag_join_fallback(m, stream); m->fj2 = 0; if (rc) return rc; }
