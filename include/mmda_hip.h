@@ -427,6 +427,17 @@ int mmda_clamp(float* g, int64_t n, float clip, void* stream);
 int mmda_clamp_adam_rows(float* p, const float* g, float* m, float* v, int rows, int dim, const unsigned char* mask, int want, float lr,
                          float beta1, float beta2, float eps, float clip, float grad_scale, int step, void* stream);
 int mmda_mark_rows(unsigned char* mask, int rows, const int64_t* ids, int n, void* stream);
+/* torch.optim.SparseAdam on the rows of a (table_rows, D) table that an id list touches (embed_update = sparse), fused with the
+ * coalescing of the gradient rows: for every distinct id at a non-padding position of `ids` (n = T*B positions; position p = t*B + b
+ * is padding when lengths != NULL and t >= lengths[b]; ids outside [0, table_rows) are skipped)
+ *   g = clamp(grad_scale * sum of rows[p] over the id's positions in position order, +-clip)
+ *   m = b1 m + (1-b1) g,  v = b2 v + (1-b2) g^2,  p -= lr sqrt(1-b2^step)/(1-b1^step) * m / (sqrt(v) + eps)
+ * on row id of P, M, V in place.  Untouched rows keep parameter and both moments bit for bit; no dense gradient is written or read.
+ * No float atomics: identical bits on every run.  Lists of fewer than 3072 positions run in one launch (the owner workgroup of the
+ * short-list scatter), longer ones through the stable sort and the two-level list-order sum of mmda_embed_segment_sum. */
+int mmda_embed_rows_sparse_adam(float* P, float* M, float* V, const int64_t* ids, int n, int D, const float* rows, const int32_t* lengths,
+                                int B, int table_rows, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
+                                void* stream);
 /* clip_grad_value_(clip) + torch.optim.RMSprop with torch's defaults besides lr (alpha 0.99, eps 1e-8, no momentum, not centered):
  * the other entry of the reference's optimizer_dict (config.py:24).  grad_scale as in mmda_clamp_adam. */
 int mmda_clamp_rmsprop(float* p, const float* g, float* square_avg, int64_t n, float lr, float alpha, float eps, float clip,
@@ -487,6 +498,14 @@ int mmda_misa_set_inference(mmda_misa* m, int forward_only);
 /* 1 = the forward feed-forward products of the fusion transformer layer (linear1 / linear2) run on block-scaled fp8 operands
  * (mmda_gemm_mx8); their backward stays on the exact f32 path with the stored activations (straight-through).  Default 0. */
 int mmda_misa_set_fusion_fp8(mmda_misa* m, int on);
+/* How a training step treats embed.weight (config.embed_update): 0 = dense (default: the gradient is scattered into the bucket and
+ * dense Adam walks all rows), 1 = sparse (only the rows a batch touches are updated, with torch.optim.SparseAdam's rule: see
+ * mmda_embed_rows_sparse_adam; untouched rows keep parameter and moments), 2 = frozen (the table never changes and no gradient for it
+ * is computed).  In modes 1 and 2 the gradient bucket that mmda_misa_zero_grad clears and mmda_misa_adam_step / mmda_misa_train_step walk
+ * ends at mmda_misa_dense_floats(); no launch of a step reads or writes the whole table.  Mode 1 after mmda_misa_backward or a
+ * train step with do_adam = 0: mmda_misa_adam_step applies the rows update from the (ids, lengths) of that backward, which must
+ * still be alive.  Other values: MMDA_EINVAL. */
+int mmda_misa_set_embed_update(mmda_misa* m, int mode);
 /* Data parallel: the gradient bucket is laid out in the order the backward pass completes it (fusion block, LayerNorms,
  * layer-2 recurrent layers, layer-1 recurrent layers, embedding).  After mmda_misa_backward / mmda_misa_train_step has been
  * ISSUED, the first mmda_misa_early_grad_floats() floats of the bucket are final as soon as an event recorded inside that call
@@ -523,7 +542,8 @@ int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const
                        void* stream);
 int mmda_misa_zero_grad(mmda_misa* m, void* stream);
 int mmda_misa_zero_act_grads(mmda_misa* m, void* stream);
-/* solver.py:185-186: clip_grad_value_(clip) + Adam over the whole bucket; grad_scale = 1/world after an all-reduce */
+/* solver.py:185-186: clip_grad_value_(clip) + Adam over the whole bucket; grad_scale = 1/world after an all-reduce
+ * (mmda_misa_set_embed_update 1 / 2: over the non-embedding prefix, plus the pending rows update in mode 1) */
 int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream);
 /* zero_grad + forward + losses + backward (+ adam if do_adam) = one reference loop iteration */
 int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,

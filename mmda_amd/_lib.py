@@ -182,6 +182,7 @@ SIGNATURES = {
     "mmda_loss_domain": (_I, [_P, _I, _F, _P, _P, _P]),
     "mmda_clamp_adam": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_clamp_adam_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mmda_embed_rows_sparse_adam": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_mark_rows": (_I, [_P, _I, _P, _I, _P]),
     "mmda_clamp": (_I, [_P, _I64, _F, _P]),
     "mmda_clamp_rmsprop": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
@@ -204,6 +205,7 @@ SIGNATURES = {
     "mmda_misa_wait_early_grads": (_I, [_P, _P]),
     "mmda_misa_set_inference": (_I, [_P, _I]),
     "mmda_misa_set_fusion_fp8": (_I, [_P, _I]),
+    "mmda_misa_set_embed_update": (_I, [_P, _I]),
     "mmda_misa_cluster_status": (_I, [_P, C.POINTER(_I)]),
     "mmda_misa_forward": (_I, [_P, _P, _P, _P, _P, _I, _U64, _P]),
     "mmda_misa_losses": (_I, [_P, _P, _I, _P]),

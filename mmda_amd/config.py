@@ -64,6 +64,9 @@ DEFAULTS = dict(
     # added for the MI355X build (not reference flags)
     visual_size=35, acoustic_size=74, vocab_size=20000, precision="bf16", seq_len=50, pretrained_emb=None,
     fusion_fp8=False, dp_global_stats=False,
+    # how embed.weight trains: "dense" (Adam over the whole table: what the reference does), "sparse" (torch.optim.SparseAdam on the
+    # rows a batch touches) or "frozen" (fixed pretrained vectors: what the reference's `embed.requires_grad = False` meant to do)
+    embed_update="dense",
 )
 
 

@@ -159,6 +159,52 @@ void mmda_loss_cmd_arm_flag(unsigned* flag, unsigned value);
 int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
                          float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream);
 
+// internal (gemm.hip): mmda_gemm_grouped with split-K sized as if `absent` were launched too
+int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_args* absent, int n_absent, void* stream);
+
+// ---- sparse update of the embedding table (embed_update = sparse): torch.optim.SparseAdam's rule on the rows a step touches, applied
+// where a row's gradient sum becomes final (norm.hip: the owning workgroup of the short-list scatter; dist.hip: the two levels of the
+// sorted sum).  P / M / V: the table and its two moments; step_size = lr sqrt(1 - b2^t) / (1 - b1^t), made on the host in double
+// (optim.hip: mmda_sparse_adam_args); table_rows bounds the ids that are updated.
+struct SparseAdamArgs { float* P; float* M; float* V; int table_rows; float b1, b2, eps, clip, gscale, step_size; };
+// one element: g = clamp(gscale * sum, +-clip), then the update.  eps is added to sqrt(v) itself (SparseAdam), not to
+// sqrt(v / (1 - b2^t)) as in the dense adam1() of optim.hip.  Every rounding spelled out: both list paths give the same bits from
+// the same sum.
+__device__ __forceinline__ void sparse_adam1(float& p, float g, float& m, float& v, const SparseAdamArgs& a) {
+  g = __fmul_rn(g, a.gscale);
+  g = fminf(fmaxf(g, -a.clip), a.clip);
+  m = __fmaf_rn(a.b1, m, __fmul_rn(1.f - a.b1, g));
+  v = __fmaf_rn(a.b2, v, __fmul_rn(__fmul_rn(1.f - a.b2, g), g));
+  p = __fmaf_rn(-a.step_size, __fdiv_rn(m, __fadd_rn(sqrtf(v), a.eps)), p);
+}
+// what the sums do with a finished row element: add it into the dense gradient, or update the table in place
+struct RowAdd {
+  float* dW; int accumulate;
+  __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
+    float* dst = dW + id * D + c;                          // one writer per table row
+    *dst = accumulate ? *dst + sum : sum;
+  }
+};
+struct RowSparseAdam {
+  SparseAdamArgs a;
+  __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
+    const int64_t o = id * D + c;                          // one writer per table row
+    float p = a.P[o], m = a.M[o], v = a.V[o];
+    sparse_adam1(p, sum, m, v, a);
+    a.P[o] = p; a.M[o] = m; a.V[o] = v;
+  }
+};
+// internal (optim.hip): the arguments above from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
+int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
+                          float clip, float grad_scale, int step);
+// internal: the update over a short id list (norm.hip), over a long one (dist.hip: sorts it first), and over a list already sorted by
+// mmda_embed_sort_ids (dist.hip).  rows (n, D): the gradient rows of the list's positions; lengths / B as in the scatter.
+int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                 void* stream);
+int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                  void* stream);
+int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
+
 // ---- flag joins (misa.hip: side_flag_signal): a kernel of one stream waits, on the device, for a word that a one-thread launch behind
 // the last kernel of ANOTHER stream's chain sets to `value` -- instead of a stream-level event wait, which costs the waiting stream
 // 9 - 12 us of packet processing however early the other chain finished (tools/micro/fork_cost.hip).  Called by every thread of the

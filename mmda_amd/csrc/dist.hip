@@ -32,9 +32,10 @@ __device__ __forceinline__ bool run_start(const unsigned* sid, int p) { return (
 // level 1: one wave per run start; part[p] = rows[pos[p]] + rows[pos[p+1]] + ... over the run, in list order.  A run that is its
 // id's WHOLE segment (nearly all of them: a segment spans runs only across a chunk boundary) goes straight into the table row --
 // the same bits level 2 would have produced from the one partial (0 + part, then the row's update) without the trip through `part`.
-__global__ __launch_bounds__(256) void seg_level1_kernel(const unsigned* __restrict__ sid, const int* __restrict__ pos, int n, int D,
-                                                         const float* __restrict__ rows, float* part, unsigned pad_key, float* dW,
-                                                         int accumulate) {
+// `fin`: what a finished sum does (common.h: RowAdd -> the dense gradient row, RowSparseAdam -> the row's in-place update).
+template <class Fin>
+__device__ __forceinline__ void seg_level1_body(const Fin& fin, const unsigned* __restrict__ sid, const int* __restrict__ pos, int n, int D,
+                                                const float* __restrict__ rows, float* part, unsigned pad_key) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= n) return;
   const unsigned id = sid[p];
@@ -52,32 +53,45 @@ __global__ __launch_bounds__(256) void seg_level1_kernel(const unsigned* __restr
       acc += a; acc += b; acc += e; acc += f;
     }
     for (; q < end; ++q) acc += rows[(int64_t)pos[q] * D + c];
-    if (whole) {
-      float* dst = dW + (int64_t)id * D + c;                          // one writer per table row
-      *dst = accumulate ? *dst + acc : acc;
-    } else {
-      part[(int64_t)p * D + c] = acc;
-    }
+    if (whole) fin((int64_t)id, D, c, acc);
+    else part[(int64_t)p * D + c] = acc;
   }
 }
+__global__ __launch_bounds__(256) void seg_level1_kernel(const unsigned* __restrict__ sid, const int* __restrict__ pos, int n, int D,
+                                                         const float* __restrict__ rows, float* part, unsigned pad_key, float* dW,
+                                                         int accumulate) {
+  seg_level1_body(RowAdd{dW, accumulate}, sid, pos, n, D, rows, part, pad_key);
+}
+__global__ __launch_bounds__(256) void seg_level1_adam_kernel(SparseAdamArgs ad, const unsigned* __restrict__ sid, const int* __restrict__ pos,
+                                                              int n, int D, const float* __restrict__ rows, float* part, unsigned pad_key) {
+  seg_level1_body(RowSparseAdam{ad}, sid, pos, n, D, rows, part, pad_key);
+}
 
-// level 2: one wave per segment head; dW[id] = sum of the segment's run partials, in list order (overwrites the row)
-__global__ __launch_bounds__(256) void seg_level2_kernel(const unsigned* __restrict__ sid, int n, int D, const float* __restrict__ part,
-                                                         float* dW, int accumulate, unsigned pad_key) {
+// level 2: one wave per segment head; the sum of the segment's run partials, in list order, is the row's finished sum
+template <class Fin>
+__device__ __forceinline__ void seg_level2_body(const Fin& fin, const unsigned* __restrict__ sid, int n, int D, const float* __restrict__ part,
+                                                unsigned pad_key) {
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= n) return;
   const unsigned id = sid[p];
   if (id == pad_key || (p > 0 && sid[p - 1] == id)) return;         // wave-uniform: not a segment head
   {
-    const int q2 = (p / CHUNK + 1) * CHUNK;                          // a single run: level 1 wrote the row itself
+    const int q2 = (p / CHUNK + 1) * CHUNK;                          // a single run: level 1 finished the row itself
     if (q2 >= n || sid[q2] != id) return;
   }
   for (int c = lane; c < D; c += 64) {
     float acc = 0.f;
     for (int q = p; q < n && sid[q] == id; q = (q / CHUNK + 1) * CHUNK) acc += part[(int64_t)q * D + c];
-    float* dst = dW + (int64_t)id * D + c;                            // one writer per table row
-    *dst = accumulate ? *dst + acc : acc;
+    fin((int64_t)id, D, c, acc);
   }
+}
+__global__ __launch_bounds__(256) void seg_level2_kernel(const unsigned* __restrict__ sid, int n, int D, const float* __restrict__ part,
+                                                         float* dW, int accumulate, unsigned pad_key) {
+  seg_level2_body(RowAdd{dW, accumulate}, sid, n, D, part, pad_key);
+}
+__global__ __launch_bounds__(256) void seg_level2_adam_kernel(SparseAdamArgs ad, const unsigned* __restrict__ sid, int n, int D,
+                                                              const float* __restrict__ part, unsigned pad_key) {
+  seg_level2_body(RowSparseAdam{ad}, sid, n, D, part, pad_key);
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -187,6 +201,42 @@ int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D
   float* part = mmda_scratch_get((hipStream_t)stream, sizeof(float) * (size_t)n * D);
   if (!part) return MMDA_ELAUNCH;
   return seg_reduce(sorted, reinterpret_cast<const int*>(sorted + n), n, D, rows, part, dW, 1, (unsigned)table_rows, (hipStream_t)stream);
+}
+
+// ---- embed_update = sparse: the same two levels with the row update where a segment's sum becomes final (a whole-segment run in
+// level 1, the cross-chunk segments in level 2).  The pad key is the table's row count: ids from there on are never updated.
+static int seg_reduce_adam(const SparseAdamArgs& ad, const unsigned* kout, const int* vout, int n, int D, const float* rows, float* part,
+                           hipStream_t s) {
+  const unsigned pad_key = (unsigned)ad.table_rows;
+  hipLaunchKernelGGL(seg_level1_adam_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, ad, kout, vout, n, D, rows, part, pad_key);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_sparse_adam/level1");
+  hipLaunchKernelGGL(seg_level2_adam_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, ad, kout, n, D, part, pad_key);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_sparse_adam/level2");
+  return MMDA_OK;
+}
+int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream) {
+  if (!sorted || !rows || n < 0 || D <= 0 || ad.table_rows <= 0) return MMDA_EINVAL;
+  if (n == 0) return MMDA_OK;
+  float* part = mmda_scratch_get((hipStream_t)stream, sizeof(float) * (size_t)n * D);
+  if (!part) return MMDA_ELAUNCH;
+  return seg_reduce_adam(ad, sorted, reinterpret_cast<const int*>(sorted + n), n, D, rows, part, (hipStream_t)stream);
+}
+// sort, then the sums: one piece of the stream's scratch holds the sort's buffers and the run partials
+int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                  void* stream) {
+  if (!ids || !rows || n < 0 || D <= 0 || ad.table_rows <= 0 || (lengths && B <= 0)) return MMDA_EINVAL;
+  if (n == 0) return MMDA_OK;
+  const SegLayout L = seg_layout(n, D);
+  float* work = mmda_scratch_get((hipStream_t)stream, L.total + 256);
+  if (!work) return MMDA_ELAUNCH;
+  unsigned char* w = (unsigned char*)(((uintptr_t)work + 255) & ~(uintptr_t)255);
+  unsigned* kout = (unsigned*)(w + L.keys_out); int* vout = (int*)(w + L.vals_out);
+  int bits = 1;
+  while (bits < 32 && ((unsigned)ad.table_rows >> bits) != 0u) ++bits;
+  const int rc = seg_sort(ids, n, lengths, B, (unsigned)ad.table_rows, bits, (unsigned*)(w + L.keys_in), (int*)(w + L.vals_in), kout, vout,
+                          (void*)(w + L.cub), L.cub_bytes, (hipStream_t)stream);
+  if (rc) return rc;
+  return seg_reduce_adam(ad, kout, vout, n, D, rows, (float*)(w + L.part), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- RCCL all-reduce

@@ -477,7 +477,14 @@ extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
 }
 
 extern "C" int mmda_gemm_grouped(const mmda_gemm_args* args, int n, void* stream) {
-  if (!args || n < 0) return MMDA_EINVAL;
+  return mmda_gemm_grouped_sized(args, n, nullptr, 0, stream);
+}
+
+// internal (misa.hip): the same launch with its split-K sized as if the `absent` problems were part of it too (they are not run).
+// A step that leaves a product out (frozen embedding table: no text layer-1 dX) keeps the slices, and so the bits, of the products
+// that stay.  Counted into the first GROUP_MAX problems' launch.
+int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_args* absent, int n_absent, void* stream) {
+  if (!args || n < 0 || n_absent < 0 || (n_absent && !absent)) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   for (int base = 0; base < n; base += GROUP_MAX) {
     GroupLaunch G;
@@ -486,6 +493,8 @@ extern "C" int mmda_gemm_grouped(const mmda_gemm_args* args, int n, void* stream
     const int cnt = (n - base) < GROUP_MAX ? (n - base) : GROUP_MAX;
     // size split-K so that the whole group offers ~4 workgroups per CU
     int tiles_total = 0;
+    for (int i = 0; base == 0 && i < n_absent; ++i)
+      tiles_total += ceil_div(absent[i].N + (absent[i].bias_grad ? 1 : 0), BN) * ceil_div(absent[i].M, BM) * absent[i].batch;
     for (int i = 0; i < cnt; ++i) {
       const mmda_gemm_args& a = args[base + i];
       if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K < 0 || a.batch < 0 || (a.gather && a.transA)) return MMDA_EINVAL;

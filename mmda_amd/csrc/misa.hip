@@ -65,7 +65,13 @@ struct StepPlan {
   bool zg_here = false;             // the gradient bucket is cleared at the head of the loss chain (eager_side_losses)
   bool rec_hoisted = false;         // stretch C's launch makes d_recon W_rec for stretch A
   bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
+  int embed_update = 0;             // EU_*: how the step treats the embedding table (mmda_misa_set_embed_update)
 };
+
+// embed_update: dense = the table's gradient is scattered into the bucket and dense Adam walks all V rows; sparse = the rows the batch
+// touches take a SparseAdam update where their sums become final, nothing V-sized is read, written or cleared; frozen = the table
+// takes no gradient at all (no text layer-1 dX product, no sort, no scatter).  In both new modes the gradient bucket ends at m->embed.
+enum { EU_DENSE = 0, EU_SPARSE = 1, EU_FROZEN = 2 };
 
 enum { SITE_ATTN = 1, SITE_DROP1 = 2, SITE_FFN = 3, SITE_DROP2 = 4, SITE_CLS = 5, SITE_DISC = 6,
        SITE_RRELU = 7 /* .. 9: the three projections' random slopes */, SITE_RRELU_DISC = 10 };
@@ -108,6 +114,11 @@ struct mmda_misa {
   int adam_early_on = 0; float ae_lr = 0.f, ae_clip = 0.f; int ae_step = 0; int64_t adam_early_done = 0;
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
+  int embed_update = EU_DENSE;
+  // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
+  // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
+  // for backward itself)
+  const int64_t* eu_ids = nullptr; const int32_t* eu_lengths = nullptr; int eu_pending = 0;
   int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
   // state of the last forward (dropout replay in backward)
   int training = 0; uint64_t seed = 0;
@@ -391,15 +402,17 @@ int64_t layout(mmda_misa* m, int B, int T, bool commit) {
 struct Ctx {
   mmda_misa* m; void* s; int rc = 0;
   bool grouping = false; std::vector<mmda_gemm_args> pending;
+  bool absent_next = false; std::vector<mmda_gemm_args> absent;   // a product the step leaves out, still counted when the group is sized
   bool deferring = false; std::vector<mmda_gemm_args> deferred;   // weight-gradient GEMMs: off the critical path, run on the side stream
 };
 
 // independent GEMMs issued between group_begin/group_end go out as ONE grouped launch
-void group_begin(Ctx& c) { c.grouping = true; c.pending.clear(); }
+void group_begin(Ctx& c) { c.grouping = true; c.pending.clear(); c.absent.clear(); }
 void group_end(Ctx& c) {
   c.grouping = false;
-  if (!c.rc && !c.pending.empty()) c.rc = mmda_gemm_grouped(c.pending.data(), (int)c.pending.size(), c.s);
-  c.pending.clear();
+  if (!c.rc && !c.pending.empty())
+    c.rc = mmda_gemm_grouped_sized(c.pending.data(), (int)c.pending.size(), c.absent.data(), (int)c.absent.size(), c.s);
+  c.pending.clear(); c.absent.clear();
 }
 
 void gemm(Ctx& c, int mode, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* Bp, int ldb, float* C,
@@ -411,6 +424,7 @@ void gemm(Ctx& c, int mode, int tA, int tB, int M, int N, int K, const float* A,
   g.mode = mode; g.transA = tA; g.transB = tB; g.M = M; g.N = N; g.K = K; g.batch = batch;
   g.A = A; g.lda = lda; g.strideA = sA; g.B = Bp; g.ldb = ldb; g.strideB = sB; g.C = C; g.ldc = ldc; g.strideC = sC;
   g.bias = bias; g.bias2 = bias2; g.strideBias = sBias; g.accumulate = acc; g.act = act;
+  if (c.absent_next) { c.absent_next = false; if (c.grouping) c.absent.push_back(g); return; }
   if (c.deferring && tA && acc) c.deferred.push_back(g);       // TN + accumulate == a weight gradient
   else if (c.grouping) c.pending.push_back(g);
   else c.rc = mmda_gemm(&g, c.s);
@@ -601,6 +615,9 @@ mmda_lstm_desc lstm_desc(mmda_misa* m, int i, int l, bool bwd, int gate_minor, b
   return d;
 }
 
+// floats of the gradient bucket that a step writes, clears and walks with dense Adam: all of it, or the prefix in front of the table
+int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE ? m->flat : m->embed; }
+
 constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
 
 // the decisions of one step (see StepPlan); the switches that select a form of the step are read here only
@@ -668,7 +685,8 @@ StepPlan plan_step(mmda_misa* m) {
   P.fj_device = P.fj_fwd && B <= FJ_DEVICE_MAX_B;
   P.zg_here = zg_side >= 0 ? zg_side != 0 : P.fj_device;
   P.rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
-  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B);
+  P.embed_update = m->embed_update;
+  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN;
   return P;
 }
 
@@ -887,7 +905,7 @@ int eager_side_losses(mmda_misa* m, void* stream) {
   // device, small batches: see mmda_misa::jflags) -- the chain then has two launches of slack and the clear comes back here, in ONE
   // launch with the activation-gradient region, at the head of the chain.
   if (!rc && P.zg_here && m->zero_grad_pending) {
-    rc = mmda_zero2(WS(m->zero_begin), zend - m->zero_begin, m->G, m->flat, ss);
+    rc = mmda_zero2(WS(m->zero_begin), zend - m->zero_begin, m->G, grad_floats(m), ss);
     m->zero_grad_pending = 0;
   } else if (!rc) {
     if (hipMemsetAsync(WS(m->zero_begin), 0, sizeof(float) * (zend - m->zero_begin), (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
@@ -936,6 +954,14 @@ int ffn_fp8(mmda_misa* m, float p_tf, uint64_t seed, void* stream) {
   return mmda_gemm_mx8(&h, stream);
 }
 }  // namespace
+
+extern "C" int mmda_misa_set_embed_update(mmda_misa* m, int mode) {
+  if (!m) return MMDA_EINVAL;
+  if (mode != EU_DENSE && mode != EU_SPARSE && mode != EU_FROZEN) return MMDA_EINVAL;
+  m->embed_update = mode;
+  m->eu_pending = 0;
+  return MMDA_OK;
+}
 
 extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
   if (!m) return MMDA_EINVAL;
@@ -1373,7 +1399,7 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
 // =============================================================================================== backward
 extern "C" int mmda_misa_zero_grad(mmda_misa* m, void* stream) {
   if (!m || !m->G) return MMDA_EINVAL;
-  if (hipMemsetAsync(m->G, 0, sizeof(float) * m->flat, (hipStream_t)stream) != hipSuccess) return MMDA_ELAUNCH;
+  if (hipMemsetAsync(m->G, 0, sizeof(float) * grad_floats(m), (hipStream_t)stream) != hipSuccess) return MMDA_ELAUNCH;
   return MMDA_OK;
 }
 
@@ -1594,7 +1620,8 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   if (!rc && P.skinny) rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, ss);
   // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
   m->esort_valid = 0;
-  if (!rc && P.sort_early) {
+  // (sparse mode without an optimizer step behind this backward: the rows update runs later, in mmda_misa_adam_step, and sorts there)
+  if (!rc && P.sort_early && !(P.embed_update == EU_SPARSE && !m->adam_early_on)) {
     rc = mmda_embed_sort_ids(t_ids, B * m->T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
     if (!rc && ss != s) {
       hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
@@ -1648,10 +1675,11 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
   // gate gradients -> bf16: transposed (A of every dW) and, where an input gradient is needed and the recurrent kernel did not
   // write it itself, plain (A of dX).  Layer 2 with the kernel-written plain copy: only the weight-gradient GEMMs (side stream)
   // read the transposed one, so the conversion goes to the side stream with them.
+  const bool frozen = P.embed_update == EU_FROZEN;            // no gradient w.r.t. the embedding rows: text layer 1 has no dX product
   mmda_convert_job dgj[3];
   for (int i = 0; i < 3; ++i) {
     Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-    const bool plain = (l == 1 || i == 0) && !P.kdg;
+    const bool plain = (l == 1 || (i == 0 && !frozen)) && !P.kdg;
     dgj[i] = mmda_convert_job{WS(md.gates[l]), 8 * r.H, R, 8 * r.H, nullptr, plain ? WS(r.dgb) : nullptr, plain ? r.ldG : 0, WS(r.dgbT),
                               m->ldR};
     if (P.kdg) { dgj[i].src = WS(r.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
@@ -1717,11 +1745,14 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // d(normed) = dG W_ih (layer 2) / d(embedding rows) (text layer 1)
     if (l == 1 || i == 0) {
       float* dst = l == 1 ? WS(md.d_normed) : WS(md.d_x);
+      const bool skip = l == 0 && frozen;                    // frozen table: the text layer-1 dX product is not run
       if (bfg) {
         mmda_gemm_bf16_args g = {};
         g.M = R; g.N = r.D; g.K = G8; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.wbT); g.ldb = r.ldG; g.C = dst; g.ldc = r.D;
-        bmain.push_back(g);
+        if (!skip) bmain.push_back(g);
       } else {
+        // (left out of a frozen step's group, but counted when its split-K is sized: the weight gradients beside it keep their slices)
+        absent_next = skip;
         gemm(*this, mode, 0, 0, R, r.D, G8, dG, G8, rW_ih(m, r), r.D, dst, r.D);
       }
     }
@@ -1777,7 +1808,31 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
       rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
       if (!rc) m->adam_early_done = m->early_floats;
     }
-  } else {
+  } else if (P.embed_update == EU_SPARSE) {
+    // text: the rows the batch touches are updated where the scatter would have left their sums (SparseAdam, common.h) -- behind an
+    // optimizer step only; otherwise the pass stops at d_x_t and mmda_misa_adam_step applies the update
+    m->eu_pending = 0;
+    if (!m->adam_early_on) {
+      m->eu_ids = t_ids; m->eu_lengths = lengths; m->eu_pending = 1;
+      return;
+    }
+    SparseAdamArgs ad;
+    rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, m->ae_lr,
+                               0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step);
+    if (rc) return;
+    if (m->esort_valid) {
+      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
+        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
+        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
+      }
+      if (!rc) rc = mmda_embed_sparse_adam_presorted(ad, reinterpret_cast<const unsigned*>(WS(m->esort)), R, c.d_t, WS(m->mod[0].d_x), s);
+      m->esort_valid = 0;
+    } else if (mmda_embed_scatter_sorts(R)) {
+      rc = mmda_embed_sparse_adam_sorted(ad, t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
+    } else {
+      rc = mmda_embed_sparse_adam_short(ad, t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
+    }
+  } else if (P.embed_update == EU_DENSE) {
     // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     if (m->esort_valid) {
       if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
@@ -1885,7 +1940,16 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 // =============================================================================================== optimizer / step
 extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
   if (!m || !m->P || !m->G || !m->M1 || !m->V1) return MMDA_EINVAL;
-  return mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->flat, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  int rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  if (!rc && m->embed_update == EU_SPARSE && m->eu_pending) {
+    // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
+    m->eu_pending = 0;
+    if (!m->ws || m->T <= 0) return MMDA_EINVAL;
+    rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->eu_ids, m->B * m->T, m->cfg.d_t,
+                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step,
+                                     stream);
+  }
+  return rc;
 }
 
 extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
@@ -1920,7 +1984,8 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
     // (flag join: this launch does not complete before the side stream's weight-gradient GEMMs and early optimizer pass have)
     const bool fj = m->fj2 != 0;
     m->fj2 = 0;
-    rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, m->flat - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
+    // (sparse / frozen table: the launch ends in front of it -- and stays the waiter)
+    rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, grad_floats(m) - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
                               fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr, stream);
   }
   return rc;

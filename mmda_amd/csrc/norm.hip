@@ -316,8 +316,11 @@ __global__ void embed_gather_kernel(const float* __restrict__ W, const int64_t* 
 // when t >= lengths[b] -- its row is exactly zero (no gradient flows through padding) and it is skipped, as owner and as contributor:
 // a ragged batch holds the pad id hundreds of times.
 constexpr int ES_MAX = 4096;
-__global__ __launch_bounds__(256) void embed_scatter_kernel(float* dW, const int64_t* __restrict__ ids, int rows, int dim, const float* __restrict__ dX,
-                                                            const int* __restrict__ lengths, int B) {
+// `fin(id, dim, d, sum)`: what the owner does with element d of the row's finished sum (common.h: RowAdd adds it into the dense gradient,
+// RowSparseAdam updates the table and its moments in place -- embed_update = sparse); max_id: ids from there on are skipped.
+template <class Fin>
+__device__ __forceinline__ void embed_scatter_body(const Fin& fin, int64_t max_id, const int64_t* __restrict__ ids, int rows, int dim,
+                                                   const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
   __shared__ unsigned mask[ES_MAX / 32];
   __shared__ unsigned short list[ES_MAX];
   __shared__ int base[ES_MAX / 32 + 1];
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(float* dW, const int
   const int p = blockIdx.x;
   const int64_t id = ids[p];
   auto padded = [&](int q) { return lengths != nullptr && (q / B) >= lengths[q % B]; };
-  if (id < 0 || padded(p)) return;                       // block-uniform
+  if (id < 0 || id >= max_id || padded(p)) return;       // block-uniform
   const int nwords = (rows + 31) / 32;
   if (threadIdx.x == 0) earlier = 0;
   for (int i = threadIdx.x; i < nwords; i += 256) mask[i] = 0u;
@@ -395,11 +398,20 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(float* dW, const int
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int d = d0 + lane + 64 * j;
-        if (d < dim) dW[id * (int64_t)dim + d] += ((acc[j] + part[0][lane + 64 * j]) + part[1][lane + 64 * j]) + part[2][lane + 64 * j];
+        if (d < dim) fin(id, dim, d, ((acc[j] + part[0][lane + 64 * j]) + part[1][lane + 64 * j]) + part[2][lane + 64 * j]);
       }
     }
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void embed_scatter_kernel(float* dW, const int64_t* __restrict__ ids, int rows, int dim, const float* __restrict__ dX,
+                                                            const int* __restrict__ lengths, int B) {
+  embed_scatter_body(RowAdd{dW, 1}, INT64_MAX, ids, rows, dim, dX, lengths, B);
+}
+// the same owner, second epilogue: scale, clamp and SparseAdam on row `id` of the table (no dense gradient row is written or read)
+__global__ __launch_bounds__(256) void embed_sparse_adam_kernel(SparseAdamArgs ad, const int64_t* __restrict__ ids, int rows, int dim,
+                                                                const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
+  embed_scatter_body(RowSparseAdam{ad}, (int64_t)ad.table_rows, ids, rows, dim, dX, lengths, B);
 }
 
 __global__ void add_kernel(const float* a, const float* b, float* y, int64_t n) {
@@ -673,6 +685,16 @@ int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int d
   if (mmda_embed_scatter_sorts(rows)) return mmda_embed_scatter_sorted(dW, ids, rows, dim, dX, lengths, B, stream);
   hipLaunchKernelGGL(embed_scatter_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dW, ids, rows, dim, dX, lengths, B);
   MMDA_CHECK_LAUNCH("mmda_embed_scatter_add");
+  return MMDA_OK;
+}
+
+// embed_update = sparse, lists below ES_SORT_MIN positions (the caller chose: mmda_embed_scatter_sorts)
+int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                 void* stream) {
+  if (!ids || !rows || n < 0 || n > ES_MAX || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
+  if (n == 0) return MMDA_OK;
+  hipLaunchKernelGGL(embed_sparse_adam_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ad, ids, n, D, rows, lengths, B);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_sparse_adam");
   return MMDA_OK;
 }
 

@@ -4,6 +4,8 @@
 #include "common.h"
 #include <math.h>
 
+bool mmda_embed_scatter_sorts(int rows);      // norm.hip
+
 namespace {
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
@@ -176,6 +178,30 @@ extern "C" int mmda_clamp_adam_rows(float* p, const float* g, float* m, float* v
                      beta2, eps, clip, grad_scale, step_size, inv_bc2_sqrt);
   MMDA_CHECK_LAUNCH("mmda_clamp_adam_rows");
   return MMDA_OK;
+}
+
+// internal: the scalars of one SparseAdam step.  torch.optim.SparseAdam: step_size = lr sqrt(1 - b2^t) / (1 - b1^t), in double here,
+// once per step (the dense launch keeps its two scalars lr / bc1 and 1 / sqrt(bc2): its eps sits elsewhere)
+int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
+                          float clip, float grad_scale, int step) {
+  if (!out || !P || !M || !V || table_rows <= 0 || step < 1) return MMDA_EINVAL;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  *out = SparseAdamArgs{P, M, V, table_rows, beta1, beta2, eps, clip, grad_scale, (float)((double)lr * sqrt(bc2) / bc1)};
+  return MMDA_OK;
+}
+
+extern "C" int mmda_embed_rows_sparse_adam(float* P, float* M, float* V, const int64_t* ids, int n, int D, const float* rows,
+                                           const int32_t* lengths, int B, int table_rows, float lr, float beta1, float beta2, float eps,
+                                           float clip, float grad_scale, int step, void* stream) {
+  if (!ids || !rows || n < 0 || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
+  SparseAdamArgs ad;
+  const int rc = mmda_sparse_adam_args(&ad, P, M, V, table_rows, lr, beta1, beta2, eps, clip, grad_scale, step);
+  if (rc) return rc;
+  if (n == 0) return MMDA_OK;
+  // the list length picks the form exactly as the dense scatter does (mmda_embed_scatter_add_masked)
+  if (mmda_embed_scatter_sorts(n)) return mmda_embed_sparse_adam_sorted(ad, ids, n, D, rows, lengths, B, stream);
+  return mmda_embed_sparse_adam_short(ad, ids, n, D, rows, lengths, B, stream);
 }
 
 extern "C" int mmda_clamp(float* g, int64_t n, float clip, void* stream) {

@@ -198,7 +198,11 @@ class DataParallelSync:
         if self.world == 1 and not self.force_collectives:
             return 1.0
         n = flat_grads.numel()
-        sparse = self._use_sparse(flat_grads, dense_floats, model)
+        # a frozen embedding table (config.embed_update) has no gradient: the bucket ends at dense_floats and nothing is exchanged for it
+        frozen = getattr(model, "embed_update", "dense") == "frozen"
+        if frozen:
+            n = dense_floats
+        sparse = not frozen and self._use_sparse(flat_grads, dense_floats, model)
         end = dense_floats if sparse else n           # floats that travel by all-reduce
         if not flat_grads.is_cuda:
             self._all_reduce_chunked(flat_grads[:end])

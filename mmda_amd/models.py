@@ -66,6 +66,9 @@ def _reference_sort_key(name: str):
     return (_TOP_ORDER.index(top), sub)
 
 
+EMBED_UPDATE = {"dense": 0, "sparse": 1, "frozen": 2}       # mmda_misa_set_embed_update
+
+
 class MISA(nn.Module):
     """MISA for CMU-MOSEI emotion multi-label classification (reference models.py:15-17), HIP-backed."""
 
@@ -91,6 +94,10 @@ class MISA(nn.Module):
         if self.precision not in ("bf16", "fp32"):
             raise ValueError("config.precision must be 'bf16' or 'fp32'")
 
+        self.embed_update = getattr(config, "embed_update", "dense")
+        if self.embed_update not in EMBED_UPDATE:
+            raise ValueError("config.embed_update must be 'dense', 'sparse' or 'frozen'")
+
         lib = _lib.load()
         cc = _lib.MisaConfig(
             vocab=len(config.word2id), d_t=self.text_size, d_v=self.visual_size, d_a=self.acoustic_size,
@@ -109,6 +116,7 @@ class MISA(nn.Module):
         self.fusion_fp8 = bool(getattr(config, "fusion_fp8", False))
         if self.fusion_fp8:
             _lib.check(lib.mmda_misa_set_fusion_fp8(h, 1), "set_fusion_fp8")
+        _lib.check(lib.mmda_misa_set_embed_update(h, EMBED_UPDATE[self.embed_update]), "set_embed_update")
         self._layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         for i in range(lib.mmda_misa_num_params(h)):
             name, off, rows, cols = C.c_char_p(), C.c_int64(), C.c_int(), C.c_int()
@@ -140,6 +148,14 @@ class MISA(nn.Module):
                 self._register(name, self._layout[name][1])
         self._plist = [(n, self._get(n)) for n in self._names]
         self.reset_parameters()
+        if self.embed_update == "frozen":
+            # what the reference's `self.model.embed.requires_grad = False` (solver.py:86) meant: the optimizer's
+            # filter(lambda p: p.requires_grad, ...) then leaves the table out
+            self.embed.weight.requires_grad_(False)
+        # sparse mode: a backward whose rows update is still to be applied (the next optimizer step consumes it), and the clip value
+        # optim.clip_grad_value_ recorded for it (the clamp applies to the coalesced rows, which exist only inside that update)
+        self._rows_pending = False
+        self._rows_clip = None
 
         # device state (created lazily on the first forward / .to())
         self._P = self._G = self._M = self._V = None
@@ -237,6 +253,8 @@ class MISA(nn.Module):
 
     def _assign_grad_views(self):
         for name, p in self._plist:
+            if name == "embed.weight" and self.embed_update != "dense":
+                continue                                    # no dense gradient exists: see embedding_grad_rows()
             if p.grad is None:
                 off, shape = self._layout[name]
                 p.grad = self._G[off:off + p.numel()].view(shape)
@@ -455,6 +473,8 @@ class MISA(nn.Module):
                        "mmda_misa_train_step")
             self._fwd_id += 1
         self._last = dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo)
+        self._rows_pending = self.embed_update == "sparse" and not fused_adam
+        self._rows_clip = None
         if custom:
             scale = 1.0
             if grad_sync is not None:
@@ -484,8 +504,10 @@ class MISA(nn.Module):
                 if hook:
                     owner.early_step = None
             done = int(owner.early_stepped) if hook else 0
+            if self.embed_update == "sparse":
+                raise _lib.MMDAError("embed_update='sparse' with a gradient exchange is not built yet")
             if done > 0:
-                n = self._P.numel() - done
+                n = self.grad_floats - done
                 o = done * 4
                 _lib.check(self._lib.mmda_clamp_adam(self._P.data_ptr() + o, self._G.data_ptr() + o, self._M.data_ptr() + o,
                                                      self._V.data_ptr() + o, n, lr, 0.9, 0.999, 1e-8, clip, float(scale), max(self._step, 1), s),
@@ -558,6 +580,8 @@ class MISA(nn.Module):
         """(ids (R,) int64, rows (R, d_t) fp32) of the last backward: embed.weight.grad == sum over the list of rows[p] into row
         ids[p].  The dense gradient is non-zero in at most R = T*B of its V rows, so data-parallel ranks exchange these instead of
         V x d_t.  Positions past a sample's length carry id -1 (their rows are exactly zero: no gradient flows through padding)."""
+        if self.embed_update == "frozen":
+            raise _lib.MMDAError("embed_update='frozen': no gradient with respect to the embedding rows is computed")
         t = self._last["t"]
         T, B = t.shape
         R = T * B
@@ -610,6 +634,27 @@ class MISA(nn.Module):
     @property
     def dense_floats(self) -> int:
         return self._dense_floats
+
+    @property
+    def grad_floats(self) -> int:
+        """Floats of the flat buckets that carry a dense gradient and take the dense optimizer launch: everything, or (embed_update
+        'sparse' / 'frozen') the prefix in front of embed.weight."""
+        return self._flat_floats if self.embed_update == "dense" else self._dense_floats
+
+    def apply_sparse_rows(self, lr: float, step: int, clip: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8) -> bool:
+        """embed_update='sparse': the SparseAdam update of the rows the last backward touched (coalesce, scale, clamp, update: one fused
+        native pass over d_x_t), once per backward.  Returns False when no backward is pending."""
+        if self.embed_update != "sparse" or not self._rows_pending:
+            return False
+        from . import ops
+        off, (V, D) = self._layout["embed.weight"]
+        t = self._last["t"]
+        ops.embed_rows_sparse_adam(self._P[off:off + V * D].view(V, D), self._M[off:off + V * D].view(V, D),
+                                   self._V[off:off + V * D].view(V, D), t, self._ws_view("d_x_t", (t.numel(), D)), lr, step,
+                                   lengths=self._last["len_dev"], clip=clip, grad_scale=grad_scale, betas=betas, eps=eps)
+        self._rows_pending = False
+        self._rows_clip = None
+        return True
 
     def cluster_aborted(self) -> bool:
         """True if a resident-weights recurrence ever timed out waiting for its cluster (results are invalid after that).
@@ -705,6 +750,8 @@ class _MISAFn(torch.autograd.Function):
         t, v, a, len_dev = ctx.io
         _lib.check(lib.mmda_misa_backward(model._h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(), s),
                    "mmda_misa_backward")
+        model._rows_pending = model.embed_update == "sparse"
+        model._rows_clip = None
         model._assign_grad_views()
         return (torch.zeros_like(model._anchor),) + (None,) * 7
 

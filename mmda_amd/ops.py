@@ -448,6 +448,23 @@ def clamp_adam_rows(p, g, m, v, mask, want, lr, step, clip=float("inf"), grad_sc
                                    grad_scale, step, stream_ptr()), "clamp_adam_rows")
 
 
+def embed_rows_sparse_adam(p, m, v, ids, rows, lr, step, lengths=None, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+    """torch.optim.SparseAdam on the rows of the (V, D) table p (moments m, v; in place) that the id list touches: per distinct id at a
+    non-padding position, g = clamp(grad_scale * position-order sum of rows[pos], +-clip), then the update.  ids: (n,) or (T, B) int64;
+    rows: (n, D) fp32; lengths: (B,) int32 on the device or None (position t * B + b is padding when t >= lengths[b])."""
+    lib = load()
+    V, D = p.shape
+    n = ids.numel()
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous() and rows.shape == (n, D)
+    assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    B = 0
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and n % lengths.numel() == 0
+        B = lengths.numel()
+    check(lib.mmda_embed_rows_sparse_adam(ptr(_f(p)), ptr(_f(m)), ptr(_f(v)), ptr(ids), n, D, ptr(_f(rows)), ptr(lengths), B, V, lr,
+                                          betas[0], betas[1], eps, clip, grad_scale, step, stream_ptr()), "embed_rows_sparse_adam")
+
+
 def heads_fwd(logits, ncls, threshold=0.35, drop_p=0.0, seed=0, site=0):
     lib = load()
     B = logits.shape[0]

@@ -153,8 +153,14 @@ class Adam(_FlatOptimizer):
         m = self._flat()
         if m is not None:
             P, G, M, V = m.flat_buckets()
-            _lib.check(lib.mmda_clamp_adam(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), P.numel(), g0["lr"], b1, b2,
+            # embed_update 'sparse' / 'frozen': the dense launch ends in front of embed.weight; 'sparse' then updates the rows the last
+            # backward touched, clamped by what clip_grad_value_ recorded for them (the unfused order clips before it steps)
+            n = getattr(m, "grad_floats", P.numel())
+            _lib.check(lib.mmda_clamp_adam(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, g0["lr"], b1, b2,
                                            g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam")
+            if getattr(m, "embed_update", "dense") == "sparse":
+                rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
+                m.apply_sparse_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
             return None
         for group in self.param_groups:
             for p in group["params"]:
@@ -207,9 +213,11 @@ class RMSprop(_FlatOptimizer):
         clip = float("inf") if clip is None else float(clip)
         m = self._flat()
         if m is not None:
+            if getattr(m, "embed_update", "dense") == "sparse":
+                raise _lib.MMDAError("embed_update='sparse' is defined for Adam only (torch has no sparse RMSprop)")
             P, G, _, _ = m.flat_buckets()
             sq = self._square_avg(P)
-            _lib.check(lib.mmda_clamp_rmsprop(P.data_ptr(), G.data_ptr(), sq.data_ptr(), P.numel(), g0["lr"], g0["alpha"], g0["eps"],
+            _lib.check(lib.mmda_clamp_rmsprop(P.data_ptr(), G.data_ptr(), sq.data_ptr(), getattr(m, "grad_floats", P.numel()), g0["lr"], g0["alpha"], g0["eps"],
                                               clip, grad_scale, s), "mmda_clamp_rmsprop")
             return None
         for group in self.param_groups:
@@ -232,7 +240,12 @@ def clip_grad_value_(model_or_params, clip_value):
     lib = _lib.load()
     m = model_or_params
     if hasattr(m, "flat_buckets") and m._G is not None:
-        _lib.check(lib.mmda_clamp(m._G.data_ptr(), m._G.numel(), float(clip_value), _lib.stream_ptr()), "mmda_clamp")
+        # embed_update 'sparse' / 'frozen': the bucket ends in front of embed.weight.  'sparse': the table's gradient rows are not yet
+        # coalesced (clip_grad_value_ clamps the coalesced gradient), so the value is recorded for the pending rows update
+        _lib.check(lib.mmda_clamp(m._G.data_ptr(), getattr(m, "grad_floats", m._G.numel()), float(clip_value), _lib.stream_ptr()),
+                   "mmda_clamp")
+        if getattr(m, "embed_update", "dense") == "sparse" and m._rows_pending:
+            m._rows_clip = float(clip_value) if m._rows_clip is None else min(float(m._rows_clip), float(clip_value))
         return
     for p in m:
         if p.grad is not None:

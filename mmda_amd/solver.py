@@ -56,13 +56,22 @@ class Solver(object):
         if not getattr(cfg, "use_bert", False):
             if getattr(cfg, "pretrained_emb", None) is not None:
                 self.model.embed.weight.data = cfg.pretrained_emb
-            self.model.embed.requires_grad = False     # a no-op in the reference too: the Parameter keeps training
+            # (the reference writes `self.model.embed.requires_grad = False` here, solver.py:86: an attribute on the module that
+            # freezes nothing.  Whether the table trains is config.embed_update: 'dense' (what the reference does), 'sparse', 'frozen')
+        eu = getattr(self.model, "embed_update", "dense")
+        dp_on = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        if eu == "sparse" and self.is_train:
+            from . import _lib
+            if cfg.optimizer is not _optim.Adam:
+                raise _lib.MMDAError("embed_update='sparse' is defined for optimizer='Adam' only (torch has no sparse RMSprop to match)")
+            if dp_on:
+                raise _lib.MMDAError("embed_update='sparse' under data parallelism is not built yet (use 'dense' or 'frozen')")
         self.model.to(self.device)
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate)
             if hasattr(self.optimizer, "attach"):
                 self.optimizer.attach(self.model)
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if dp_on:
             # config.dp_global_stats (not a reference option: the reference is single-device): the batch-statistic losses on the
             # batch of all ranks instead of DDP semantics (mmda_amd/dist.py)
             self.dp = DataParallelSync(global_stats=bool(getattr(cfg, "dp_global_stats", False)))
