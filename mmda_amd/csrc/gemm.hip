@@ -415,9 +415,7 @@ extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
     if (splitk > 64) splitk = 64;
     if (splitk < 1) splitk = 1;
   }
-  // no empty slices (an empty slice would leave its slab unwritten)
-  auto norm_split = [](int nk_, int sk_) { const int per = ceil_div(nk_, sk_ < 1 ? 1 : sk_); return ceil_div(nk_, per); };
-  splitk = norm_split(nk, splitk);
+  splitk = splitk_slices(nk, splitk);
   auto reduce_job = [&](const float* slab, int ldn, int sk) {
     SplitKJob J = {};
     J.slab = slab; J.C = a->C; J.M = a->M; J.N = a->N; J.ldn = ldn; J.ldc = a->ldc; J.sk = sk; J.batch = a->batch;
@@ -437,7 +435,7 @@ extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
       if (sk > 64) sk = 64;
       if (sk < 1) sk = 1;
     }
-    sk = norm_split(nk, sk);
+    sk = splitk_slices(nk, sk);
     float* slab = nullptr;
     const int ldn = a->N;
     if (sk > 1) {
@@ -521,7 +519,7 @@ int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_a
         if (sk > 32) sk = 32;
         if (sk < 1) sk = 1;
       }
-      { const int per = ceil_div(nk, sk); sk = ceil_div(nk, per); }     // no empty slices
+      sk = splitk_slices(nk, sk);
       G.splitk[k] = sk;
       G.slab[k] = nullptr; G.ldn[k] = Ne;
       if (sk > 1) {

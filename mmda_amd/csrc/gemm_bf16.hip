@@ -737,223 +737,258 @@ __global__ __launch_bounds__(256) void convert_kernel(ConvLaunch L) {
   convert_block(L, (int)blockIdx.x, tile);
 }
 
+// ---------------------------------------------------------------------------------------------- host: the launch plan of a call
+// mmda_gemm_bf16_grouped() validates, plans (plan_bf16_call: class -> order -> split -> launches -> reduce jobs; no HIP call), asks
+// for the slabs once, launches what the plan lists and reduces.  DESIGN.md §4 has the decisions as a table.
+
+// Four kernel classes.  Reg64: 64 x 64 register-staged (small / unaligned problems); Reg128: 128 x 128 register-staged; Dma128:
+// 128 x 128 LDS-DMA pipelined (gemm_bf16_dma_kernel); Dma256: its 256 x 128 form.
+enum Class { Reg64, Reg128, Dma128, Dma256, NCLASS };
+inline bool is_dma(Class c) { return c >= Dma128; }
+// the DMA classes first: they hold the largest problems
+constexpr Class LAUNCH_ORDER[NCLASS] = {Dma256, Dma128, Reg64, Reg128};
+
+// MMDA_GEMM_DMA=0 switches the DMA classes off, MMDA_GEMM_DMA_STAGES=2|3 sets the depth of Dma128's LDS ring, MMDA_GEMM_DMA_MIN_ROWS
+// moves the limit of is_dma_call(), MMDA_GEMM_DMA_TALL=1 switches Dma256 on
+struct Switches { int dma_on, dma_stages, dma_min_rows, dma_tall; };
+
+// rows x columns of a class's output tile, threads of a workgroup, workgroups of this class the chip holds at once
+struct ClassShape { int rows, cols, threads, resident; };
+ClassShape shape_of(Class c, const Switches& sw) {
+  // (Reg64: four workgroups per CU.  Dma128: an LDS ring of 2 stages is 64 KB, two workgroups per CU; of 3, 96 KB, one.  Dma256: 147 KB)
+  const ClassShape table[NCLASS] = {{64, 64, 256, 1024}, {128, 128, 256, 512}, {128, 128, 256, sw.dma_stages == 2 ? 512 : 256}, {256, 128, 512, 256}};
+  return table[c];
+}
+
+// One problem of a launch.  ldn / slab_off (floats from the call's slab base): of a split problem (sk > 1), else 0 / -1.
+struct PlanEntry { int problem, tx, ty, sk, first_block, ldn; int64_t slab_off; };
+// One launch: entries [first, first + count) of Bf16Plan::entries; `mixed`: the tn-capable instance (register-staged classes)
+struct PlanLaunch { Class cls; bool mixed; int blocks, first, count; };
+// What a call launches: the launches in issue order, the slab floats of the whole call, the reduce jobs behind the launches
+// (SplitKJob::slab holds the slab's OFFSET in floats; the caller adds the base it gets from its one scratch request)
+struct Bf16Plan { std::vector<PlanEntry> entries; std::vector<PlanLaunch> launches; std::vector<SplitKJob> jobs; int64_t slab_floats; };
+
+inline int cols_of(const mmda_gemm_bf16_args& a) { return a.N + (a.bias_grad ? 1 : 0); }      // + the bias gradient's ones-column
+
+// The DMA classes run only in a call of large-batch problems -- some problem with >= 8192 rows (nt) or k-rows (tn): T * B of the step.
+// Measured (step, ms; DMA class on / off): B=32 0.694 / 0.657, B=64 0.834 / 0.822, B=128 1.167 / 1.174, B=256 1.85 / 2.02 -- below that
+// the problems are a few k-tiles on a few hundred workgroups, where the register-staged 64 x 64 kernel at four workgroups per CU is
+// ahead.
+bool is_dma_call(const mmda_gemm_bf16_args* args, int n, const Switches& sw) {
+  int call_rows = 0;
+  for (int i = 0; i < n; ++i) call_rows = max(call_rows, args[i].tn ? args[i].K : args[i].M);
+  return sw.dma_on && call_rows >= sw.dma_min_rows;
+}
+
+// The class of a problem.  Dma128 takes every problem of a DMA call whose operands can be moved by 16-byte LDS-DMA (nt: always --
+// rows are 16-byte aligned by contract; tn: leading dimensions multiples of 8 and 16-byte aligned bases) and whose output is at least
+// DMA_MIN rows and columns.  Reg128 takes a problem of at least T128_MIN_TILES 128 x 128 tiles (smaller thresholds measured slower at
+// these sizes).
+Class class_of(const mmda_gemm_bf16_args& a, bool dma_call, const Switches& sw) {
+  constexpr int T128_MIN_TILES = 512, DMA_MIN = 96;
+  if (dma_call && a.M >= DMA_MIN && cols_of(a) >= DMA_MIN) {
+    bool ok = true;
+    if (a.tn) ok = !(a.lda & 7) && !(a.ldb & 7) && !(((uintptr_t)a.A | (uintptr_t)a.B) & 15) && ((double)a.K + 64.0) * (double)max(a.lda, a.ldb) < 2.0e9;
+    // Dma256 for the long k-walks of a tall output: K >= 1024, M >= 512 (input gradients: K = 8H; weight gradients: K = T * B).  The
+    // short-K forward products stay on the 128-row form: they are a prologue and an epilogue around five to ten k-tiles, and two
+    // workgroups per CU overlap those where one cannot.
+    // (OFF by default since the end of round 3: with the rest of the step as it is now the B=256 step measures 1.690 ms without the
+    //  class against 1.705 with it -- its 147 KB workgroups do not fit a CU beside a recurrent kernel's, and on the main stream they
+    //  are no faster than two 128-row workgroups per CU; MMDA_GEMM_DMA_TALL=1 switches it on.  Its LDS ring has three stages: two
+    //  measured slower)
+    if (ok && sw.dma_tall && a.K >= 1024 && a.M >= 512) return Dma256;
+    if (ok) return Dma128;
+  }
+  return ceil_div(cols_of(a), 128) * ceil_div(a.M, 128) >= T128_MIN_TILES ? Reg128 : Reg64;
+}
+
+// The order inside a class.  Workgroups are dealt in block order: the problems with the longest K loops go first, so that their
+// workgroups do not form the tail of the launch.
+void longest_k_first(PlanEntry* first, PlanEntry* last, const mmda_gemm_bf16_args* args) {
+  std::stable_sort(first, last, [&](const PlanEntry& x, const PlanEntry& y) { return args[x.problem].K > args[y.problem].K; });
+}
+
+// The DMA classes' split: a workgroup's time is its k-tiles (~1 us each: the latency of the tile in flight), so the launch is cut
+// into pieces of equal length -- target = the k-tiles per workgroup at which the whole launch (`work` k-tiles) fills the resident
+// slots once -- and a problem is split where its k-walk is longer than that (the weight gradients of a large batch, K = T * B, beside
+// the input gradients, K = 8H, of the same launch).  Every slice keeps >= 6 k-tiles (prologue, the C tile's trip through the slab),
+// slabs stay <= 32 MB per problem.
+int split_dma(int nk, double out_mb, int64_t work, int resident) {
+  const int target = (int)std::max<int64_t>(8, ceil_div64(work, resident));
+  int sk = (nk + target / 2) / target;
+  if (sk > nk / 6) sk = nk / 6;
+  while (sk > 1 && sk * out_mb > 32.0) --sk;
+  if (sk > 32) sk = 32;
+  return sk < 1 ? 1 : sk;
+}
+
+// The register-staged classes' split: only a very long k-walk (K >= 8192: the small-modality weight gradients of a large batch, a
+// handful of tiles walking T * B rows) on fewer workgroups than the chip holds; every k-tile is one memory latency, so the walk is cut
+// until the slots are full.  Below that nothing is split any more: with the slices combined through slabs and a reduce launch
+// (round 3) instead of float atomics, a split costs the MOSEI-sized problems more than its parallelism returns -- measured,
+// alternating runs (step, ms; split / no split): B=16 0.621 / 0.612, B=32 0.665 / 0.652, B=64 0.846 / 0.842, B=128 1.206 / 1.196
+// (round 2 split from 8 k-tiles).
+int split_reg(int tiles, int nk, double out_mb) {
+  if (tiles >= 1024 || nk < 128) return 1;
+  int sk = ceil_div(1024, tiles);
+  while (sk > 1 && (nk / sk < 16 || sk * out_mb > 24.0)) --sk;
+  return sk;
+}
+
+// A fresh (non-accumulated) output gains from a split only with a long K loop in a launch that would otherwise leave the chip
+// underfilled; `crowded`: the class's tiles fill the chip without any split-K
+bool fresh_output_stays_whole(const mmda_gemm_bf16_args& a, int nk, bool crowded) { return !a.accumulate && (crowded || nk < 16); }
+
+// The give-back pass over a register-staged class as a whole.  The chip holds `resident` workgroups of this kernel at once; a launch of
+// 1.x times that runs a second, mostly empty round.  While the class sits between one and two rounds, the most finely split problems
+// (the larger one of two equals) give slices back.
+void give_back(PlanEntry* first, PlanEntry* last, int resident) {
+  for (;;) {
+    int64_t tot = 0;
+    PlanEntry* best = nullptr;
+    for (PlanEntry* e = first; e != last; ++e) {
+      tot += (int64_t)e->tx * e->ty * e->sk;
+      if (e->sk > 1 && (!best || e->sk > best->sk || (e->sk == best->sk && e->tx * e->ty > best->tx * best->ty))) best = e;
+    }
+    if (!best || tot <= resident || tot >= 2 * (int64_t)resident) return;
+    --best->sk;
+  }
+}
+
+// The split-K of every problem of one class (entries in launch order): each problem on its own, the class as a whole, no empty slices
+void split_class(PlanEntry* first, PlanEntry* last, const mmda_gemm_bf16_args* args, Class c, int resident) {
+  int64_t all_tiles = 0, work = 0;                        // output tiles, k-tiles of the whole class
+  for (PlanEntry* e = first; e != last; ++e) { all_tiles += e->tx * e->ty; work += (int64_t)e->tx * e->ty * ceil_div(args[e->problem].K, TK); }
+  const bool crowded = all_tiles >= (is_dma(c) ? resident : 512);
+  for (PlanEntry* e = first; e != last; ++e) {
+    const mmda_gemm_bf16_args& a = args[e->problem];
+    const int nk = ceil_div(a.K, TK);
+    const double out_mb = (double)a.M * a.N * 4.0 / 1048576.0;
+    e->sk = is_dma(c) ? split_dma(nk, out_mb, work, resident) : split_reg(e->tx * e->ty, nk, out_mb);
+    if (e->sk > 1 && fresh_output_stays_whole(a, nk, crowded)) e->sk = 1;
+  }
+  if (!is_dma(c)) give_back(first, last, resident);
+  for (PlanEntry* e = first; e != last; ++e) e->sk = splitk_slices(ceil_div(args[e->problem].K, TK), e->sk);
+}
+
+SplitKJob reduce_job(const mmda_gemm_bf16_args& a, const PlanEntry& e) {
+  SplitKJob J = {};
+  J.slab = reinterpret_cast<const float*>((uintptr_t)e.slab_off);      // offset for now; the caller adds the base
+  J.C = a.C; J.M = a.M; J.N = a.N; J.ldn = e.ldn; J.ldc = a.ldc; J.sk = e.sk; J.batch = 1;
+  J.alpha = a.alpha; J.bias = a.bias; J.bias2 = a.bias2; J.bias_grad = a.bias_grad; J.bias_grad2 = a.bias_grad2;
+  J.accumulate = a.accumulate; J.perm_m_H = a.perm_m_H; J.perm_n_H = a.perm_n_H;
+  return J;
+}
+
+// What mmda_gemm_bf16_grouped(args, n) launches.  Pure: no HIP runtime call, no environment, no statics.
+Bf16Plan plan_bf16_call(const mmda_gemm_bf16_args* args, int n, const Switches& sw) {
+  Bf16Plan P = {};
+  P.entries.reserve(n); P.launches.reserve(NCLASS + n / GROUP_MAX);
+  const bool dma_call = is_dma_call(args, n, sw);
+  // ---- per class: its problems in launch order, their split-K, the slabs of the split ones
+  int class_first[NCLASS + 1];
+  for (Class c : {Reg64, Reg128, Dma128, Dma256}) {
+    const ClassShape shape = shape_of(c, sw);
+    class_first[c] = (int)P.entries.size();
+    for (int i = 0; i < n; ++i) {
+      const mmda_gemm_bf16_args& a = args[i];
+      if (a.M == 0 || a.N == 0 || class_of(a, dma_call, sw) != c) continue;
+      P.entries.push_back({i, ceil_div(cols_of(a), shape.cols), ceil_div(a.M, shape.rows), 1, 0, 0, -1});
+    }
+    PlanEntry *first = P.entries.data() + class_first[c], *last = P.entries.data() + P.entries.size();
+    longest_k_first(first, last, args);
+    split_class(first, last, args, c, shape.resident);
+    for (PlanEntry* e = first; e != last; ++e)
+      if (e->sk > 1) {
+        e->ldn = round_up(cols_of(args[e->problem]), 4);
+        e->slab_off = P.slab_floats;
+        P.slab_floats += (int64_t)e->sk * args[e->problem].M * e->ldn;
+      }
+  }
+  class_first[NCLASS] = (int)P.entries.size();
+  // ---- launches in issue order: a class's problems are cut into launches of at most GROUP_MAX; a class that holds a tn problem runs
+  // all its launches on the mixed instance
+  if (P.slab_floats > 0) P.jobs.reserve(P.entries.size());
+  for (Class c : LAUNCH_ORDER) {
+    const int lo = class_first[c], hi = class_first[c + 1];
+    bool mixed = false;
+    for (int k = lo; k < hi; ++k) mixed = mixed || args[P.entries[k].problem].tn;
+    for (int f = lo; f < hi; f += GROUP_MAX) {
+      PlanLaunch L = {c, mixed, 0, f, std::min(GROUP_MAX, hi - f)};
+      for (int k = f; k < f + L.count; ++k) {
+        PlanEntry& e = P.entries[k];
+        e.first_block = L.blocks;
+        L.blocks += round_up(e.tx * e.ty * e.sk, 8);       // every problem starts at a multiple of eight blocks (XCD-aware order)
+        if (e.sk > 1) P.jobs.push_back(reduce_job(args[e.problem], e));
+      }
+      P.launches.push_back(L);
+    }
+  }
+  return P;
+}
+
+// The kernel argument of one launch of the plan; unused slots are padded with the first problem at no blocks
+void fill_group(Bf16Group& G, const mmda_gemm_bf16_args* args, const Bf16Plan& P, const PlanLaunch& L, int tile, float* slab_base) {
+  G.n = L.count;
+  for (int k = 0; k < L.count; ++k) {
+    const PlanEntry& e = P.entries[L.first + k];
+    G.p[k] = args[e.problem]; G.start[k] = e.first_block;
+    G.tile[k] = tile; G.tx[k] = e.tx; G.ty[k] = e.ty; G.splitk[k] = e.sk;
+    G.slab[k] = e.sk > 1 ? slab_base + e.slab_off : nullptr; G.ldn[k] = e.ldn;
+  }
+  for (int k = G.n; k <= GROUP_MAX; ++k) G.start[k] = L.blocks;
+  for (int k = G.n; k < GROUP_MAX; ++k) { G.p[k] = G.p[0]; G.tx[k] = G.ty[k] = G.splitk[k] = 1; G.tile[k] = tile; G.slab[k] = nullptr; G.ldn[k] = 0; }
+}
+
+// The kernel instance of a launch.  (The chain names the instances in the order the launch sites have always named them: the compiler
+// emits instances in order of first use, and keeping that order keeps the code object byte-identical across host-side changes.)
+typedef void (*Kernel)(Bf16Group);
+Kernel pick_kernel(Class c, bool mixed, int dma_stages) {
+  if (c == Dma256) return gemm_bf16_dma_kernel<3, 256>;
+  if (c == Dma128 && dma_stages == 3) return gemm_bf16_dma_kernel<3, 128>;
+  if (c == Dma128) return gemm_bf16_dma_kernel<2, 128>;
+  if (c == Reg128 && !mixed) return gemm_bf16_kernel<128, false>;
+  if (!mixed) return gemm_bf16_kernel<64, false>;
+  if (c == Reg128) return gemm_bf16_kernel<128, true>;
+  return gemm_bf16_kernel<64, true>;
+}
+
+// What the kernels can address
+bool valid_problem(const mmda_gemm_bf16_args& a) {
+  if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K <= 0) return false;
+  if (a.perm_n_H < 0 || a.perm_m_H < 0 || (a.perm_n_H && a.N % (4 * a.perm_n_H)) || (a.perm_m_H && a.M % (4 * a.perm_m_H))) return false;
+  if (a.tn) {
+    if ((a.lda & 3) || (a.ldb & 3) || (((uintptr_t)a.A | (uintptr_t)a.B) & 3) || a.lda < a.M || a.ldb < a.N) return false;
+    return ((double)a.K + 64.0) * a.lda * 2.0 < 4.0e9 && ((double)a.K + 64.0) * a.ldb * 2.0 < 4.0e9;
+  }
+  if ((a.lda & 7) || (a.ldb & 7) || (((uintptr_t)a.A | (uintptr_t)a.B) & 15) || a.lda < ((a.K + 7) & ~7) || a.ldb < ((a.K + 7) & ~7)) return false;
+  // operands are addressed with 32-bit byte offsets through buffer descriptors (row clamping is done by the descriptor's size)
+  return ((double)a.M + 128.0) * a.lda * 2.0 < 4.0e9 && ((double)a.N + 129.0) * a.ldb * 2.0 < 4.0e9;
+}
+
 }  // namespace
 
 extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, void* stream) {
   if (!args || n < 0) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  for (int i = 0; i < n; ++i) {
-    const mmda_gemm_bf16_args& a = args[i];
-    if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K <= 0) return MMDA_EINVAL;
-    if (a.tn) {
-      if ((a.lda & 3) || (a.ldb & 3) || (((uintptr_t)a.A | (uintptr_t)a.B) & 3) || a.lda < a.M || a.ldb < a.N) return MMDA_EINVAL;
-      if (((double)a.K + 64.0) * a.lda * 2.0 >= 4.0e9 || ((double)a.K + 64.0) * a.ldb * 2.0 >= 4.0e9) return MMDA_EINVAL;
-      if (a.perm_n_H < 0 || a.perm_m_H < 0 || (a.perm_n_H && a.N % (4 * a.perm_n_H)) || (a.perm_m_H && a.M % (4 * a.perm_m_H))) return MMDA_EINVAL;
-      continue;
-    }
-    if ((a.lda & 7) || (a.ldb & 7) || (((uintptr_t)a.A | (uintptr_t)a.B) & 15)) return MMDA_EINVAL;
-    if (a.lda < ((a.K + 7) & ~7) || a.ldb < ((a.K + 7) & ~7)) return MMDA_EINVAL;
-    // operands are addressed with 32-bit byte offsets through buffer descriptors (row clamping is done by the descriptor's size)
-    if (((double)a.M + 128.0) * a.lda * 2.0 >= 4.0e9 || ((double)a.N + 129.0) * a.ldb * 2.0 >= 4.0e9) return MMDA_EINVAL;
-    if (a.perm_n_H < 0 || a.perm_m_H < 0 || (a.perm_n_H && a.N % (4 * a.perm_n_H)) || (a.perm_m_H && a.M % (4 * a.perm_m_H))) return MMDA_EINVAL;
-  }
-  // Three kernel classes.  0: 64 x 64 register-staged (small / unaligned problems), 1: 128 x 128 register-staged, 2: 128 x 128
-  // LDS-DMA pipelined (gemm_bf16_dma_kernel).  Class 2 takes every problem whose operands can be moved by 16-byte LDS-DMA (nt: always
-  // -- rows are 16-byte aligned by contract; tn: leading dimensions multiples of 8 and 16-byte aligned bases) and whose output is at
-  // least DMA_MIN rows and columns; MMDA_GEMM_DMA=0 switches it off, MMDA_GEMM_DMA_STAGES=2|3 sets the depth of its LDS ring (2: 64 KB,
-  // two workgroups per CU; 3: 96 KB, one).  Class 1 takes a problem of at least T128_MIN_TILES 128 x 128 tiles (smaller thresholds
-  // measured slower at these sizes).
-  constexpr int T128_MIN_TILES = 512, DMA_MIN = 96;
-  static const int dma_on = mmda_env_int("MMDA_GEMM_DMA", 1);
-  static const int dma_stages = mmda_env_int("MMDA_GEMM_DMA_STAGES", 2);
-  // ... and only in a call of large-batch problems -- some problem with >= 8192 rows (nt) or k-rows (tn): T * B of the step.  Measured
-  // (step, ms; DMA class on / off): B=32 0.694 / 0.657, B=64 0.834 / 0.822, B=128 1.167 / 1.174, B=256 1.85 / 2.02 -- below that the
-  // problems are a few k-tiles on a few hundred workgroups, where the register-staged 64 x 64 kernel at four workgroups per CU is
-  // ahead.  MMDA_GEMM_DMA_MIN_ROWS moves the limit.
-  static const int dma_min_rows = mmda_env_int("MMDA_GEMM_DMA_MIN_ROWS", 8192);
-  int call_rows = 0;
-  for (int i = 0; i < n; ++i) call_rows = max(call_rows, args[i].tn ? args[i].K : args[i].M);
-  const bool dma_call = dma_on && call_rows >= dma_min_rows;
-  // (OFF by default since the end of round 3: with the rest of the step as it is now the B=256 step measures 1.690 ms without the
-  //  class against 1.705 with it -- its 147 KB workgroups do not fit a CU beside a recurrent kernel's, and on the main stream they
-  //  are no faster than two 128-row workgroups per CU; MMDA_GEMM_DMA_TALL=1 switches it on.  Its LDS ring has three stages: two
-  //  measured slower)
-  static const int dma_tall = mmda_env_int("MMDA_GEMM_DMA_TALL", 0);
-  auto class_of = [&](const mmda_gemm_bf16_args& a) {
-    const int Ne = a.N + (a.bias_grad ? 1 : 0);
-    if (dma_call && a.M >= DMA_MIN && Ne >= DMA_MIN) {
-      bool ok = true;
-      if (a.tn) ok = !(a.lda & 7) && !(a.ldb & 7) && !(((uintptr_t)a.A | (uintptr_t)a.B) & 15) && ((double)a.K + 64.0) * (double)max(a.lda, a.ldb) < 2.0e9;
-      // 256-row tiles (class 3) for the long k-walks of a tall output: K >= 1024, M >= 512 (input gradients: K = 8H; weight gradients:
-      // K = T * B).  The short-K forward products stay on the 128-row form: they are a prologue and an epilogue around five to ten
-      // k-tiles, and two workgroups per CU overlap those where one cannot.  MMDA_GEMM_DMA_TALL=0 switches the class off.
-      if (ok && dma_tall && a.K >= 1024 && a.M >= 512) return 3;
-      if (ok) return 2;
-    }
-    return ceil_div(Ne, 128) * ceil_div(a.M, 128) >= T128_MIN_TILES ? 1 : 0;
-  };
-  // ---- plan: per class, the problems in launch order and their split-K
-  struct Plan { std::vector<int> order; std::vector<int> sks; };
-  constexpr int NCLASS = 4;
-  Plan plan[NCLASS];
-  // (T: the class id stands for its tile -- 64 x 64, 128 x 128, 128 x 128, 256 x 128 rows x columns)
-  auto tiles_of = [&](const mmda_gemm_bf16_args& a, int ci) {
-    const int tm = ci == 0 ? 64 : (ci == 3 ? 256 : 128), tn = ci == 0 ? 64 : 128;
-    return ceil_div(a.N + (a.bias_grad ? 1 : 0), tn) * ceil_div(a.M, tm);
-  };
-  for (int ci = 0; ci < NCLASS; ++ci) {
-    const int T = ci;
-    std::vector<int>& order = plan[ci].order;
-    std::vector<int>& sks = plan[ci].sks;
-    sks.assign(n, 1);
-    // Workgroups are dealt in block order: the problems with the longest K loops go first, so that their workgroups do not
-    // form the tail of the launch.  `crowded`: the launch fills the chip twice over without any split-K.
-    int64_t all_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-      const mmda_gemm_bf16_args& a = args[i];
-      if (a.M == 0 || a.N == 0 || class_of(a) != ci) continue;
-      order.push_back(i);
-      all_tiles += tiles_of(a, T);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return args[x].K > args[y].K; });
-    // workgroups of this class the chip holds at once
-    const int resident = ci == 0 ? 1024 : (ci == 1 ? 512 : (ci == 3 ? 256 : (dma_stages == 2 ? 512 : 256)));
-    const bool crowded = all_tiles >= (ci >= 2 ? resident : 512);
-    int64_t work2 = 0;                                    // class 2: k-tiles of the whole launch
-    for (int i : order) work2 += (int64_t)tiles_of(args[i], T) * ceil_div(args[i].K, TK);
-    // pass 1: the split of every problem on its own
-    for (int i : order) {
-      const mmda_gemm_bf16_args& a = args[i];
-      const int tiles = tiles_of(a, T);
-      const int nk = ceil_div(a.K, TK);
-      const double out_mb = (double)a.M * a.N * 4.0 / 1048576.0;
-      int sk = 1;
-      if (ci >= 2) {
-        // the DMA kernel: a workgroup's time is its k-tiles (~1 us each: the latency of the tile in flight), so the launch is cut
-        // into pieces of equal length -- target = the k-tiles per workgroup at which the whole launch fills the resident slots once --
-        // and a problem is split where its k-walk is longer than that (the weight gradients of a large batch, K = T * B, beside
-        // the input gradients, K = 8H, of the same launch).  Every slice keeps >= 6 k-tiles (prologue, the C tile's trip through
-        // the slab), slabs stay <= 32 MB per problem.
-        const int target = (int)std::max<int64_t>(8, ceil_div64(work2, resident));
-        sk = (nk + target / 2) / target;
-        if (sk > nk / 6) sk = nk / 6;
-        while (sk > 1 && sk * out_mb > 32.0) --sk;
-        if (sk > 32) sk = 32;
-        if (sk < 1) sk = 1;
-      } else if (tiles < 1024 && nk >= 128) {
-        // Register-staged classes: split only a very long k-walk (K >= 8192: the small-modality weight gradients of a large batch, a
-        // handful of tiles walking T * B rows) on fewer workgroups than the chip holds; every k-tile is one memory latency, so the walk
-        // is cut until the slots are full.  Below that nothing is split any more: with the slices combined through slabs and a reduce
-        // launch (round 3) instead of float atomics, a split costs the MOSEI-sized problems more than its parallelism returns --
-        // measured, alternating runs (step, ms; split / no split): B=16 0.621 / 0.612, B=32 0.665 / 0.652, B=64 0.846 / 0.842,
-        // B=128 1.206 / 1.196 (round 2 split from 8 k-tiles).
-        sk = ceil_div(1024, tiles);
-        while (sk > 1 && (nk / sk < 16 || sk * out_mb > 24.0)) --sk;
-      }
-      // a fresh (non-accumulated) output gains from a split only with a long K loop in a launch that would otherwise leave the chip
-      // underfilled
-      if (sk > 1 && !a.accumulate && (crowded || nk < 16)) sk = 1;
-      sks[i] = sk;
-    }
-    // pass 2: the launch as a whole.  The chip holds `resident` workgroups of this kernel at once; a launch of 1.x times that runs a
-    // second, mostly empty round.  While the launch sits between one and two rounds, the most finely split problems give slices back.
-    {
-      auto total = [&]() { int64_t t = 0; for (int i : order) t += (int64_t)tiles_of(args[i], T) * sks[i]; return t; };
-      int64_t tot = total();
-      while (ci < 2 && tot > resident && tot < 2 * (int64_t)resident) {
-        int best = -1;
-        for (int i : order) if (sks[i] > 1 && (best < 0 || sks[i] > sks[best] || (sks[i] == sks[best] && tiles_of(args[i], T) > tiles_of(args[best], T)))) best = i;
-        if (best < 0) break;
-        --sks[best];
-        tot = total();
-      }
-    }
-    // no empty slices (an empty slice would leave its slab unwritten): sk = the number of slices that hold k-tiles
-    for (int i : order) {
-      const int nk = ceil_div(args[i].K, TK);
-      const int per = ceil_div(nk, sks[i]);
-      sks[i] = ceil_div(nk, per);
-    }
-  }
+  for (int i = 0; i < n; ++i) if (!valid_problem(args[i])) return MMDA_EINVAL;
+  static const Switches sw = {mmda_env_int("MMDA_GEMM_DMA", 1), mmda_env_int("MMDA_GEMM_DMA_STAGES", 2),
+                              mmda_env_int("MMDA_GEMM_DMA_MIN_ROWS", 8192), mmda_env_int("MMDA_GEMM_DMA_TALL", 0)};
+  Bf16Plan P = plan_bf16_call(args, n, sw);
   // ---- slabs of the split problems: one scratch request for the whole call
-  std::vector<int64_t> slab_off(n, -1);
-  int64_t slab_floats = 0;
-  for (int ci = 0; ci < NCLASS; ++ci)
-    for (int i : plan[ci].order)
-      if (plan[ci].sks[i] > 1) {
-        const mmda_gemm_bf16_args& a = args[i];
-        const int ldn = round_up(a.N + (a.bias_grad ? 1 : 0), 4);
-        slab_off[i] = slab_floats;
-        slab_floats += (int64_t)plan[ci].sks[i] * a.M * ldn;
-      }
-  float* slab_base = nullptr;
-  if (slab_floats > 0) {
-    slab_base = mmda_scratch_get(s, (size_t)slab_floats * sizeof(float));
-    if (!slab_base) return MMDA_ELAUNCH;
-  }
-  // ---- launches (the DMA class first: it holds the largest problems), one reduce launch behind them all
-  std::vector<SplitKJob> jobs;
-  for (int cc = 0; cc < NCLASS; ++cc) {
-    const int ci = cc == 0 ? 3 : (cc == 1 ? 2 : cc - 2);
-    const int T = ci == 0 ? 64 : 128;                      // tile columns; rows: 256 for class 3
-    const int TMr = ci == 3 ? 256 : T;
-    const std::vector<int>& order = plan[ci].order;
-    const std::vector<int>& sks = plan[ci].sks;
-    bool any_tn = false;
-    for (int i : order) any_tn = any_tn || args[i].tn;
-    const int form = any_tn ? 1 : 0;
+  float* slab_base = P.slab_floats > 0 ? mmda_scratch_get(s, (size_t)P.slab_floats * sizeof(float)) : nullptr;
+  if (P.slab_floats > 0 && !slab_base) return MMDA_ELAUNCH;
+  for (const PlanLaunch& L : P.launches) {
+    const ClassShape shape = shape_of(L.cls, sw);
     Bf16Group G;
-    G.n = 0;
-    int blocks = 0;
-    auto flush = [&]() -> int {
-      if (blocks == 0) { G.n = 0; return MMDA_OK; }
-      for (int k = G.n; k <= GROUP_MAX; ++k) G.start[k] = blocks;
-      for (int k = G.n; k < GROUP_MAX; ++k) { G.p[k] = G.p[0]; G.tx[k] = G.ty[k] = G.splitk[k] = 1; G.tile[k] = T; G.slab[k] = nullptr; G.ldn[k] = 0; }
-      if (ci == 3) {
-        hipLaunchKernelGGL((gemm_bf16_dma_kernel<3, 256>), dim3(blocks), dim3(512), 0, s, G);
-      } else if (ci == 2) {
-        if (dma_stages == 3) hipLaunchKernelGGL((gemm_bf16_dma_kernel<3, 128>), dim3(blocks), dim3(256), 0, s, G);
-        else hipLaunchKernelGGL((gemm_bf16_dma_kernel<2, 128>), dim3(blocks), dim3(256), 0, s, G);
-      } else if (form == 0) {
-        if (T == 128) hipLaunchKernelGGL((gemm_bf16_kernel<128, false>), dim3(blocks), dim3(256), 0, s, G);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<64, false>), dim3(blocks), dim3(256), 0, s, G);
-      } else {
-        if (T == 128) hipLaunchKernelGGL((gemm_bf16_kernel<128, true>), dim3(blocks), dim3(256), 0, s, G);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<64, true>), dim3(blocks), dim3(256), 0, s, G);
-      }
-      MMDA_CHECK_LAUNCH("mmda_gemm_bf16_grouped");
-      G.n = 0; blocks = 0;
-      return MMDA_OK;
-    };
-    for (int i : order) {
-      const mmda_gemm_bf16_args& a = args[i];
-      if (G.n == GROUP_MAX) { int rc = flush(); if (rc) return rc; }
-      const int k = G.n++;
-      G.p[k] = a;
-      const int Ne = a.N + (a.bias_grad ? 1 : 0);
-      G.tile[k] = T;
-      G.tx[k] = ceil_div(Ne, T); G.ty[k] = ceil_div(a.M, TMr);
-      const int tiles = G.tx[k] * G.ty[k];
-      const int sk = sks[i];
-      G.splitk[k] = sk;
-      G.slab[k] = nullptr; G.ldn[k] = 0;
-      if (sk > 1) {
-        G.ldn[k] = round_up(Ne, 4);
-        G.slab[k] = slab_base + slab_off[i];
-        SplitKJob J = {};
-        J.slab = G.slab[k]; J.C = a.C; J.M = a.M; J.N = a.N; J.ldn = G.ldn[k]; J.ldc = a.ldc; J.sk = sk; J.batch = 1;
-        J.alpha = a.alpha; J.bias = a.bias; J.bias2 = a.bias2; J.bias_grad = a.bias_grad; J.bias_grad2 = a.bias_grad2;
-        J.accumulate = a.accumulate; J.perm_m_H = a.perm_m_H; J.perm_n_H = a.perm_n_H;
-        jobs.push_back(J);
-      }
-      G.start[k] = blocks;
-      blocks += round_up(tiles * sk, 8);                 // every problem starts at a multiple of eight blocks (XCD-aware order)
-    }
-    int rc = flush();
-    if (rc) return rc;
+    fill_group(G, args, P, L, shape.cols, slab_base);
+    hipLaunchKernelGGL(pick_kernel(L.cls, L.mixed, sw.dma_stages), dim3(L.blocks), dim3(shape.threads), 0, s, G);
+    MMDA_CHECK_LAUNCH("mmda_gemm_bf16_grouped");
   }
-  if (!jobs.empty()) { const int rc = mmda_splitk_reduce(jobs.data(), (int)jobs.size(), s); if (rc) return rc; }
-  return MMDA_OK;
+  // ---- one reduce launch behind them all
+  if (P.jobs.empty()) return MMDA_OK;
+  for (SplitKJob& J : P.jobs) J.slab = slab_base + (int64_t)(uintptr_t)J.slab;
+  return mmda_splitk_reduce(P.jobs.data(), (int)P.jobs.size(), s);
 }
 
 extern "C" int mmda_debug_gemm_dma_mode(int mode) {       // tools/ only: ablate the DMA kernel's k-loop (results are then wrong)

@@ -26,4 +26,11 @@ __host__ __device__ __forceinline__ int splitk_orig(int j, int H) {
   return d * G + (r & 3) * H + (r >> 2);
 }
 
+// No empty slices (an empty slice would leave its slab unwritten): `sk` slices of ceil(nk / sk) k-tiles each -> the number of
+// slices that hold k-tiles.  sk >= 1.
+static inline int splitk_slices(int nk, int sk) {
+  const int per = ceil_div(nk, sk);
+  return ceil_div(nk, per);
+}
+
 int mmda_splitk_reduce(const SplitKJob* jobs, int n, hipStream_t s);   // splitk.hip

@@ -187,6 +187,86 @@ def test_gemm_bf16_split_k_is_bitwise_reproducible():
         assert relerr(outs[0][2], A.float().sum(0)) < TOL["fp32"]
 
 
+def _tn_bar(want, K):
+    """test_gemm_bf16_tn_form_weight_gradient's bar: absolute, against the largest expected magnitude"""
+    return 3e-5 * float(want.abs().max()) * max(1.0, (K / 1600) ** 0.5)
+
+
+def test_gemm_bf16_grouped_more_problems_than_a_launch_holds():
+    """18 problems in one call, nt and tn mixed: one kernel class whose problems are cut into a launch of 16 and a launch of 2 (the cut
+    falls in the middle of the class's K-ordered list), and nt problems that run on the mixed (tn-capable) instance.  Shapes of the
+    tests above, every output at the bar its shape has there."""
+    from mmda_amd import ops
+    torch.manual_seed(18)
+    problems, checks = [], []
+    for i in range(18):
+        kind = i % 5
+        if kind < 3:
+            M, N, K = ((33, 70, 35), (7, 12, 768), (128, 128, 64))[kind]
+            A = torch.randn(M, K); W = torch.randn(N, K) / math.sqrt(K)
+            (Ap, _), (Wp, _) = ops.convert_bf16([(A.to(dev()), None, True, False), (W.to(dev()), None, True, False)])
+            p = dict(A=Ap, B=Wp, K=K)
+            want = A.bfloat16().float() @ W.bfloat16().float().t()
+            if kind == 2:
+                b = torch.randn(N)
+                p["bias"] = b.to(dev()); want = want + b
+            checks.append(("nt", K, want, None, None))
+        elif kind == 3:
+            M = N = K = 64
+            A = (torch.randn(K, M) * 0.5).to(torch.bfloat16).to(dev()); Bm = (torch.randn(K, N) * 0.5).to(torch.bfloat16).to(dev())
+            p = dict(A=A, B=Bm, M=M, N=N, K=K, tn=True)
+            checks.append(("tn", K, A.float().cpu().t() @ Bm.float().cpu(), None, None))
+        else:
+            M, N, K, lda, ldb, a0, b0 = 140, 35, 96, 280, 80, 140, 40
+            A = (torch.randn(K, lda) * 0.5).to(torch.bfloat16).to(dev()); Bm = (torch.randn(K, ldb) * 0.5).to(torch.bfloat16).to(dev())
+            C0 = torch.randn(M, N); bg = torch.zeros(M, device=dev())
+            p = dict(A=A[:, a0:], B=Bm[:, b0:], M=M, N=N, K=K, tn=True, out=C0.clone().to(dev()), accumulate=True, bias_grad=bg)
+            Af, Bf = A.float().cpu()[:, a0:a0 + M], Bm.float().cpu()[:, b0:b0 + N]
+            checks.append(("tn", K, C0 + Af.t() @ Bf, bg, Af.sum(0)))
+        problems.append(p)
+    outs = ops.gemm_bf16_grouped(problems)
+    for i, (out, (form, K, want, bg, want_bg)) in enumerate(zip(outs, checks)):
+        if form == "nt":
+            assert relerr(out, want) < TOL["fp32"], i
+        else:
+            assert float((out.cpu() - want).abs().max()) < _tn_bar(want, K), i
+        if bg is not None:
+            assert float((bg.cpu() - want_bg).abs().max()) < _tn_bar(want_bg, K), i
+
+
+def test_gemm_bf16_grouped_classes_and_both_split_policies_in_one_call():
+    """One call whose problems land in two kernel classes and are split by both policies: a tn weight gradient in the LDS-DMA class
+    (the call holds >= 8192 k-rows; split into equal-length pieces), a tn weight gradient of one 64 x 64 tile walking 129 k-tiles
+    (register-staged class, split because nk >= 128) and a small unsplit nt product -- the slabs of two classes behind one reduce
+    launch.  Against the fp32 matmul of the same bf16 values; twice on fresh outputs, same bits."""
+    from mmda_amd import ops
+    torch.manual_seed(8256)
+    K = 8256
+    A1 = (torch.randn(K, 256) * 0.5).to(torch.bfloat16).to(dev()); B1 = (torch.randn(K, 96) * 0.5).to(torch.bfloat16).to(dev())
+    A2 = (torch.randn(K, 64) * 0.5).to(torch.bfloat16).to(dev()); B2 = (torch.randn(K, 64) * 0.5).to(torch.bfloat16).to(dev())
+    A3 = torch.randn(33, 35); W3 = torch.randn(70, 35) / math.sqrt(35); b3 = torch.randn(70)
+    (A3p, _), (W3p, _) = ops.convert_bf16([(A3.to(dev()), None, True, False), (W3.to(dev()), None, True, False)])
+    C1 = torch.randn(256, 96); C2 = torch.randn(64, 64)
+    runs = []
+    for _ in range(2):
+        bg = torch.zeros(256, device=dev())
+        outs = ops.gemm_bf16_grouped([
+            dict(A=A1, B=B1, M=256, N=96, K=K, tn=True, out=C1.clone().to(dev()), accumulate=True, bias_grad=bg),
+            dict(A=A2, B=B2, M=64, N=64, K=K, tn=True, out=C2.clone().to(dev()), accumulate=True),
+            dict(A=A3p, B=W3p, K=35, bias=b3.to(dev()))])
+        runs.append([o.cpu() for o in outs] + [bg.cpu()])
+    for x, y in zip(*runs):
+        assert torch.equal(x, y)
+    o1, o2, o3, bg = runs[0]
+    want1 = C1 + A1.float().cpu().t() @ B1.float().cpu()
+    want2 = C2 + A2.float().cpu().t() @ B2.float().cpu()
+    want_bg = A1.float().cpu().sum(0)
+    assert float((o1 - want1).abs().max()) < _tn_bar(want1, K)
+    assert float((bg - want_bg).abs().max()) < _tn_bar(want_bg, K)
+    assert float((o2 - want2).abs().max()) < _tn_bar(want2, K)
+    assert relerr(o3, A3.bfloat16().float() @ W3.bfloat16().float().t() + b3) < TOL["fp32"]
+
+
 def test_gemm_bf16_gate_interleave():
     """The gate-minor layout end to end at GEMM level: W_ih rows interleaved by the conversion, bias read through the
     interleave (forward); dW rows and bias gradients written back through it (backward)."""
