@@ -1,5 +1,6 @@
 // Error reporting + ABI version for libmmda_hip.so.
 #include "common.h"
+#include "internal.h"
 #include <string.h>
 
 static thread_local char g_err[256] = "";

@@ -3,6 +3,7 @@
 // problem - q,k,v of 6 x hd, a 6x6 score matrix - lives in one 64-lane wavefront's LDS/registers; this is latency
 // work, not a GEMM.  One workgroup (one wave) per (sample, head).
 #include "common.h"
+#include "internal.h"
 #include "rowlocal.h"
 
 namespace {

@@ -11,19 +11,12 @@
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 bf16 = one 16x16x32 A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) float f32x4;     // 16x16 accumulator fragment
 
-void mmda_set_error(const char* what, hipError_t e);
-
 // Host: the environment switches of DESIGN §7a.  Callers keep the value in a function-local static, so each is read once per process.
 static inline int mmda_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
 static inline bool mmda_env_set(const char* name) { return getenv(name) != nullptr; }
-#define MMDA_CHECK_LAUNCH(name)                                   \
-  do {                                                            \
-    hipError_t _e = hipGetLastError();                            \
-    if (_e != hipSuccess) { mmda_set_error(name, _e); return MMDA_ELAUNCH; } \
-  } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -151,21 +144,10 @@ __device__ __forceinline__ float act_bwd_p(int act, float x, const mmda_act_para
   return x > 0.f ? 1.f : act_slope_p(act, p, idx);
 }
 
-// internal: two buffers cleared by one launch (optim.hip); the tail flag of the single-workgroup CMD launch (losses.hip)
-int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);
-bool mmda_loss_cmd_sets_flag(int B, int D);
-void mmda_loss_cmd_arm_flag(unsigned* flag, unsigned value);
-// internal: mmda_clamp_adam whose launch does not complete before *wait_flag reaches wait_value (optim.hip)
-int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
-                         float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream);
-
-// internal (gemm.hip): mmda_gemm_grouped with split-K sized as if `absent` were launched too
-int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_args* absent, int n_absent, void* stream);
-
 // ---- sparse update of the embedding table (embed_update = sparse): torch.optim.SparseAdam's rule on the rows a step touches, applied
 // where a row's gradient sum becomes final (norm.hip: the owning workgroup of the short-list scatter; dist.hip: the two levels of the
 // sorted sum).  P / M / V: the table and its two moments; step_size = lr sqrt(1 - b2^t) / (1 - b1^t), made on the host in double
-// (optim.hip: mmda_sparse_adam_args); table_rows bounds the ids that are updated.
+// (optim.hip: mmda_sparse_adam_args, internal.h); table_rows bounds the ids that are updated.
 struct SparseAdamArgs { float* P; float* M; float* V; int table_rows; float b1, b2, eps, clip, gscale, step_size; };
 // one element: g = clamp(gscale * sum, +-clip), then the update.  eps is added to sqrt(v) itself (SparseAdam), not to
 // sqrt(v / (1 - b2^t)) as in the dense adam1() of optim.hip.  Every rounding spelled out: both list paths give the same bits from
@@ -194,17 +176,6 @@ struct RowSparseAdam {
     a.P[o] = p; a.M[o] = m; a.V[o] = v;
   }
 };
-// internal (optim.hip): the arguments above from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
-int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
-                          float clip, float grad_scale, int step);
-// internal: the update over a short id list (norm.hip), over a long one (dist.hip: sorts it first), and over a list already sorted by
-// mmda_embed_sort_ids (dist.hip).  rows (n, D): the gradient rows of the list's positions; lengths / B as in the scatter.
-int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                 void* stream);
-int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                  void* stream);
-int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
-
 // ---- flag joins (misa.hip: side_flag_signal): a kernel of one stream waits, on the device, for a word that a one-thread launch behind
 // the last kernel of ANOTHER stream's chain sets to `value` -- instead of a stream-level event wait, which costs the waiting stream
 // 9 - 12 us of packet processing however early the other chain finished (tools/micro/fork_cost.hip).  Called by every thread of the

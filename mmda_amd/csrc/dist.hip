@@ -7,7 +7,7 @@
 //   * mmda_allreduce           in-place sum all-reduce of a float buffer on an RCCL communicator, for hosts that own one (a native
 //                              trainer; the Python host goes through torch.distributed, whose communicator is not exposed).
 #include "common.h"
-#include "splitk.h"
+#include "internal.h"
 #include <dlfcn.h>
 #include <hipcub/hipcub.hpp>
 

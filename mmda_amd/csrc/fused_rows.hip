@@ -6,6 +6,7 @@
 // The six problems of d_x6 and the three of d_orig each become ONE accumulator chain per wave: the products that differ per modality
 // run over the same 16-row tile with the rows of the other modalities zeroed.
 #include "common.h"
+#include "internal.h"
 #include "rowlocal.h"
 #include "fused_rows.h"
 

@@ -4,8 +4,8 @@
 //
 // Tile 64x64x32, 256 threads = 4 waves (2x2), each wave a 32x32 sub-tile = 2x2 MFMA 16x16 accumulators.
 #include "common.h"
+#include "internal.h"
 #include "splitk.h"
-#include <vector>
 
 namespace {
 
@@ -394,83 +394,132 @@ __global__ void colsum_finish_kernel(const float* __restrict__ part, int nparts,
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ host
+// Each entry point validates, plans (a pure function: no HIP call), makes one scratch request and launches; a small named function
+// returns the kernel instance.  The same pattern as gemm_bf16.hip, lstm_cluster.hip and misa.hip.
+namespace {
+
+bool valid_operands(const mmda_gemm_args& a) {
+  return a.A && a.B && a.C && a.M >= 0 && a.N >= 0 && a.K >= 0 && a.batch >= 0 && !(a.gather && a.transA);
+}
+bool valid_problem(const mmda_gemm_args& a) {
+  return valid_operands(a) && (a.mode == MMDA_F32 || a.mode == MMDA_BF16) && !(a.bias_grad && !a.transA);
+}
+bool empty_problem(const mmda_gemm_args& a) { return a.M == 0 || a.N == 0 || a.batch == 0; }
+bool plain_epilogue(const mmda_gemm_args& a) { return a.act == MMDA_ACT_NONE && a.drop_p <= 0.f && !a.gate; }
+int n_eff(const mmda_gemm_args& a) { return a.N + (a.bias_grad ? 1 : 0); }          // + the virtual ones column
+int tiles64(const mmda_gemm_args& a) { return ceil_div(n_eff(a), BN) * ceil_div(a.M, BM) * a.batch; }
+
+// Split-K: these GEMMs are small (B=32: a few dozen output tiles) with long reductions (K = T*B for weight gradients, 2048 for the
+// FFN, 4H for the projections); one block per tile would leave 250 CUs idle behind a serial k-loop.  `tiles` output tiles of `nk`
+// k-tiles each get enough slices to offer `target` workgroups: at least two k-tiles (64 deep) per slice, at most `cap` slices (cap 1:
+// the caller may not split -- an epilogue the reduce launch does not know, or tiles enough already), no empty slice.
+constexpr int SPLIT_TARGET_64 = 768, SPLIT_TARGET_128 = 512, SPLIT_TARGET_GROUP = 1024;
+constexpr int SPLIT_CAP = 64, SPLIT_CAP_GROUP = 32;
+constexpr int SPLIT_MAX_TILES = 256;              // mmda_gemm: a problem with more tiles than this fills the chip unsplit
+int splitk_size(int tiles, int nk, int target, int cap) {
+  const int sk = nk >= 8 ? max(1, min(ceil_div(target, tiles), min(nk / 2, cap))) : 1;
+  return splitk_slices(nk, sk);
+}
+
+SplitKJob splitk_job(const mmda_gemm_args& a, const float* slab, int ldn, int sk) {
+  SplitKJob J = {};
+  J.slab = slab; J.C = a.C; J.M = a.M; J.N = a.N; J.ldn = ldn; J.ldc = a.ldc; J.sk = sk; J.batch = a.batch;
+  J.strideC = a.strideC; J.strideBias = a.strideBias; J.alpha = a.alpha; J.bias = a.bias; J.bias2 = a.bias2;
+  J.bias_grad = a.bias_grad; J.bias_grad2 = a.bias_grad2; J.accumulate = a.accumulate;
+  return J;
+}
+
+// large aligned bf16 GEMMs -> 128x128 tile kernel with 16-byte staging loads
+bool takes_tile128(const mmda_gemm_args& a) {
+  const bool aligned = ((a.lda | a.ldb | a.K) & 3) == 0 && (((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0 &&
+                       ((a.strideA | a.strideB) & 3) == 0 && (!a.transA || (a.M & 3) == 0) && (a.transB || (a.N & 3) == 0);
+  return a.mode == MMDA_BF16 && plain_epilogue(a) && aligned && !a.A2 && !a.gather && !a.bias_grad && a.M >= 128 && a.N >= 128;
+}
+
+enum class GemmClass { Tile64, Tile64Tiny, Tile128 };      // Tile64Tiny: PF = 4 (see gemm_body)
+struct GemmPlan { int rc; GemmClass cls; int sk, ldn; dim3 grid; int64_t slab_floats; };
+
+// everything about the launch of one valid, non-empty problem
+GemmPlan plan_gemm(const mmda_gemm_args& a) {
+  GemmPlan P = {};
+  const bool t128 = takes_tile128(a);
+  const int nk = ceil_div(a.K, BK);
+  P.ldn = t128 ? a.N : n_eff(a);
+  const int tx = ceil_div(P.ldn, t128 ? TN : BN), ty = ceil_div(a.M, t128 ? TM : BM), tiles = tx * ty * a.batch;
+  const bool may_split = tiles <= SPLIT_MAX_TILES && (t128 || plain_epilogue(a));
+  P.sk = splitk_size(tiles, nk, t128 ? SPLIT_TARGET_128 : SPLIT_TARGET_64, may_split ? SPLIT_CAP : 1);
+  P.grid = dim3(tx, ty, a.batch * P.sk);
+  if (P.grid.y > 65535 || P.grid.z > 65535) { P.rc = MMDA_EINVAL; return P; }
+  const bool tiny = ceil_div(nk, P.sk) <= 4 && (int)(P.grid.x * P.grid.y * P.grid.z) <= 1024;
+  P.cls = t128 ? GemmClass::Tile128 : (tiny ? GemmClass::Tile64Tiny : GemmClass::Tile64);
+  if (P.sk > 1) P.slab_floats = (int64_t)((size_t)a.batch * P.sk * a.M * P.ldn);
+  return P;
+}
+
+// (the instances are named in the order the object file has always had them, the 128-tile ones first: DESIGN.md §7)
+typedef void (*GemmKernel)(mmda_gemm_args, int, float*, int);
+GemmKernel pick_tile128(bool ta, bool tb) {
+  if (!ta) return tb ? gemm128_bf16_kernel<false, true> : gemm128_bf16_kernel<false, false>;
+  return !tb ? gemm128_bf16_kernel<true, false> : gemm128_bf16_kernel<true, true>;
+}
+GemmKernel pick_tile64(int mode, bool tiny) {
+  if (mode == MMDA_BF16) return tiny ? gemm_kernel<MMDA_BF16, 4> : gemm_kernel<MMDA_BF16, 1>;
+  return tiny ? gemm_kernel<MMDA_F32, 4> : gemm_kernel<MMDA_F32, 1>;
+}
+GemmKernel pick_kernel(GemmClass c, const mmda_gemm_args& a) {
+  return c == GemmClass::Tile128 ? pick_tile128(a.transA, a.transB) : pick_tile64(a.mode, c == GemmClass::Tile64Tiny);
+}
+
+// One grouped launch.  Slot k runs problem `problem` of the launch's list (the empty ones get no slot) on blocks [start, start + tx *
+// ty * batch * sk); slab_off: where its split-K slab starts in the launch's scratch request, in floats (sk > 1 only).
+struct GroupSlot { int problem, tx, ty, sk, ldn, start; int64_t slab_off; };
+struct GroupPlan { int rc, n, blocks; int64_t slab_floats; GroupSlot slot[GROUP_MAX]; };
+
+// Split-K is sized so that the whole group offers ~4 workgroups per CU; the `absent` problems count into the group without being run.
+GroupPlan plan_group(const mmda_gemm_args* args, int cnt, const mmda_gemm_args* absent, int n_absent) {
+  GroupPlan P = {};
+  int tiles_total = 0;
+  for (int i = 0; i < n_absent; ++i) tiles_total += tiles64(absent[i]);
+  for (int i = 0; i < cnt; ++i) {
+    if (!valid_problem(args[i])) { P.rc = MMDA_EINVAL; return P; }
+    tiles_total += tiles64(args[i]);
+  }
+  for (int i = 0; i < cnt; ++i) {
+    const mmda_gemm_args& a = args[i];
+    if (empty_problem(a)) continue;
+    GroupSlot& S = P.slot[P.n++];
+    S.problem = i;
+    S.ldn = n_eff(a);
+    S.tx = ceil_div(S.ldn, BN); S.ty = ceil_div(a.M, BM);
+    S.sk = splitk_size(tiles_total, ceil_div(a.K, BK), SPLIT_TARGET_GROUP,
+                       plain_epilogue(a) && tiles_total < SPLIT_TARGET_GROUP ? SPLIT_CAP_GROUP : 1);
+    if (S.sk > 1) { S.slab_off = P.slab_floats; P.slab_floats += (int64_t)a.batch * S.sk * a.M * S.ldn; }
+    S.start = P.blocks;
+    P.blocks += S.tx * S.ty * a.batch * S.sk;
+  }
+  return P;
+}
+
+}  // namespace
+
 extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
-  if (!a || !a->A || !a->B || !a->C) return MMDA_EINVAL;
-  if (a->M < 0 || a->N < 0 || a->batch < 0 || a->K < 0 || (a->gather && a->transA)) return MMDA_EINVAL;
-  if (a->M == 0 || a->N == 0 || a->batch == 0) return MMDA_OK;
-  if (a->mode != MMDA_F32 && a->mode != MMDA_BF16) return MMDA_EINVAL;
+  if (!a || !valid_operands(*a)) return MMDA_EINVAL;
+  // An empty problem is MMDA_OK here before its mode and bias_grad are looked at; mmda_gemm_grouped rejects a bad one first.  The two
+  // orders cannot be made one without changing a return code, so each entry point keeps its own.
+  if (empty_problem(*a)) return MMDA_OK;
+  if (!valid_problem(*a)) return MMDA_EINVAL;
+  const GemmPlan P = plan_gemm(*a);
+  if (P.rc) return P.rc;
   hipStream_t s = (hipStream_t)stream;
-  // Split-K: these GEMMs are small (B=32: a few dozen output tiles) with long reductions (K = T*B for weight gradients,
-  // 2048 for the FFN, 4H for the projections); one block per tile would leave 250 CUs idle behind a serial k-loop.
-  const int Neff = a->N + (a->bias_grad ? 1 : 0);          // + the virtual ones column
-  if (a->bias_grad && !a->transA) return MMDA_EINVAL;
-  const int tiles = ceil_div(Neff, BN) * ceil_div(a->M, BM) * a->batch;
-  const int nk = ceil_div(a->K, BK);
-  int splitk = 1;
-  const bool plain_epilogue = a->act == MMDA_ACT_NONE && a->drop_p <= 0.f && !a->gate;
-  if (plain_epilogue && nk >= 8 && tiles <= 256) {
-    splitk = (768 + tiles - 1) / tiles;
-    int max_split = nk / 2;                       // >= 2 k-tiles (64 deep) per block
-    if (splitk > max_split) splitk = max_split;
-    if (splitk > 64) splitk = 64;
-    if (splitk < 1) splitk = 1;
-  }
-  splitk = splitk_slices(nk, splitk);
-  auto reduce_job = [&](const float* slab, int ldn, int sk) {
-    SplitKJob J = {};
-    J.slab = slab; J.C = a->C; J.M = a->M; J.N = a->N; J.ldn = ldn; J.ldc = a->ldc; J.sk = sk; J.batch = a->batch;
-    J.strideC = a->strideC; J.strideBias = a->strideBias; J.alpha = a->alpha; J.bias = a->bias; J.bias2 = a->bias2;
-    J.bias_grad = a->bias_grad; J.bias_grad2 = a->bias_grad2; J.accumulate = a->accumulate;
-    return J;
-  };
-  // large aligned bf16 GEMMs -> 128x128 tile kernel with 16-byte staging loads
-  const bool aligned = ((a->lda | a->ldb | a->K) & 3) == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0 &&
-                       ((a->strideA | a->strideB) & 3) == 0 && (!a->transA || (a->M & 3) == 0) && (a->transB || (a->N & 3) == 0);
-  if (a->mode == MMDA_BF16 && plain_epilogue && aligned && !a->A2 && !a->gather && !a->bias_grad && a->M >= 128 && a->N >= 128) {
-    const int tiles128 = ceil_div(a->N, TN) * ceil_div(a->M, TM) * a->batch;
-    int sk = 1;
-    if (nk >= 8 && tiles128 <= 256) {
-      sk = (512 + tiles128 - 1) / tiles128;
-      if (sk > nk / 2) sk = nk / 2;
-      if (sk > 64) sk = 64;
-      if (sk < 1) sk = 1;
-    }
-    sk = splitk_slices(nk, sk);
-    float* slab = nullptr;
-    const int ldn = a->N;
-    if (sk > 1) {
-      slab = mmda_scratch_get(s, sizeof(float) * (size_t)a->batch * sk * a->M * ldn);
-      if (!slab) return MMDA_ELAUNCH;
-    }
-    dim3 grid128(ceil_div(a->N, TN), ceil_div(a->M, TM), a->batch * sk);
-    if (grid128.y > 65535 || grid128.z > 65535) return MMDA_EINVAL;
-    if (!a->transA && a->transB) hipLaunchKernelGGL((gemm128_bf16_kernel<false, true>), grid128, dim3(256), 0, s, *a, sk, slab, ldn);
-    else if (!a->transA && !a->transB) hipLaunchKernelGGL((gemm128_bf16_kernel<false, false>), grid128, dim3(256), 0, s, *a, sk, slab, ldn);
-    else if (a->transA && !a->transB) hipLaunchKernelGGL((gemm128_bf16_kernel<true, false>), grid128, dim3(256), 0, s, *a, sk, slab, ldn);
-    else hipLaunchKernelGGL((gemm128_bf16_kernel<true, true>), grid128, dim3(256), 0, s, *a, sk, slab, ldn);
-    MMDA_CHECK_LAUNCH("mmda_gemm(128)");
-    if (sk > 1) { SplitKJob J = reduce_job(slab, ldn, sk); return mmda_splitk_reduce(&J, 1, s); }
-    return MMDA_OK;
-  }
   float* slab = nullptr;
-  const int ldn = Neff;
-  if (splitk > 1) {
-    slab = mmda_scratch_get(s, sizeof(float) * (size_t)a->batch * splitk * a->M * ldn);
+  if (P.sk > 1) {
+    slab = mmda_scratch_get(s, sizeof(float) * (size_t)P.slab_floats);
     if (!slab) return MMDA_ELAUNCH;
   }
-  dim3 grid(ceil_div(Neff, BN), ceil_div(a->M, BM), a->batch * splitk);
-  if (grid.y > 65535 || grid.z > 65535) return MMDA_EINVAL;
-  const int per_split = ceil_div(nk, splitk);
-  const bool tiny = per_split <= 4 && (int)(grid.x * grid.y * grid.z) <= 1024;
-  if (a->mode == MMDA_BF16) {
-    if (tiny) hipLaunchKernelGGL((gemm_kernel<MMDA_BF16, 4>), grid, dim3(256), 0, s, *a, splitk, slab, ldn);
-    else hipLaunchKernelGGL((gemm_kernel<MMDA_BF16, 1>), grid, dim3(256), 0, s, *a, splitk, slab, ldn);
-  } else {
-    if (tiny) hipLaunchKernelGGL((gemm_kernel<MMDA_F32, 4>), grid, dim3(256), 0, s, *a, splitk, slab, ldn);
-    else hipLaunchKernelGGL((gemm_kernel<MMDA_F32, 1>), grid, dim3(256), 0, s, *a, splitk, slab, ldn);
-  }
-  MMDA_CHECK_LAUNCH("mmda_gemm");
-  if (splitk > 1) { SplitKJob J = reduce_job(slab, ldn, splitk); return mmda_splitk_reduce(&J, 1, s); }
+  hipLaunchKernelGGL(pick_kernel(P.cls, *a), P.grid, dim3(256), 0, s, *a, P.sk, slab, P.ldn);
+  MMDA_CHECK_LAUNCH(P.cls == GemmClass::Tile128 ? "mmda_gemm(128)" : "mmda_gemm");
+  if (P.sk > 1) { const SplitKJob J = splitk_job(*a, slab, P.ldn, P.sk); return mmda_splitk_reduce(&J, 1, s); }
   return MMDA_OK;
 }
 
@@ -485,69 +534,30 @@ int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_a
   if (!args || n < 0 || n_absent < 0 || (n_absent && !absent)) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   for (int base = 0; base < n; base += GROUP_MAX) {
+    const GroupPlan P = plan_group(args + base, (n - base) < GROUP_MAX ? (n - base) : GROUP_MAX, absent, base == 0 ? n_absent : 0);
+    if (P.rc) return P.rc;
+    if (P.blocks == 0) continue;
+    float* slab = nullptr;
+    if (P.slab_floats) {
+      slab = mmda_scratch_get(s, sizeof(float) * (size_t)P.slab_floats);
+      if (!slab) return MMDA_ELAUNCH;
+    }
     GroupLaunch G;
-    G.n = 0;
-    int blocks = 0;
-    const int cnt = (n - base) < GROUP_MAX ? (n - base) : GROUP_MAX;
-    // size split-K so that the whole group offers ~4 workgroups per CU
-    int tiles_total = 0;
-    for (int i = 0; base == 0 && i < n_absent; ++i)
-      tiles_total += ceil_div(absent[i].N + (absent[i].bias_grad ? 1 : 0), BN) * ceil_div(absent[i].M, BM) * absent[i].batch;
-    for (int i = 0; i < cnt; ++i) {
-      const mmda_gemm_args& a = args[base + i];
-      if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K < 0 || a.batch < 0 || (a.gather && a.transA)) return MMDA_EINVAL;
-      if (a.mode != MMDA_F32 && a.mode != MMDA_BF16) return MMDA_EINVAL;
-      if (a.bias_grad && !a.transA) return MMDA_EINVAL;
-      tiles_total += ceil_div(a.N + (a.bias_grad ? 1 : 0), BN) * ceil_div(a.M, BM) * a.batch;
+    SplitKJob jobs[GROUP_MAX];
+    int njobs = 0;
+    G.n = P.n;
+    for (int k = 0; k < P.n; ++k) {
+      const GroupSlot& S = P.slot[k];
+      G.p[k] = args[base + S.problem];
+      G.start[k] = S.start; G.tx[k] = S.tx; G.ty[k] = S.ty; G.splitk[k] = S.sk; G.ldn[k] = S.ldn;
+      G.slab[k] = S.sk > 1 ? slab + S.slab_off : nullptr;
+      if (S.sk > 1) jobs[njobs++] = splitk_job(G.p[k], G.slab[k], S.ldn, S.sk);
     }
-    std::vector<SplitKJob> jobs;
-    std::vector<int> jk;                   // group slot of each job
-    int64_t slab_floats = 0;
-    for (int i = 0; i < cnt; ++i) {
-      const mmda_gemm_args& a = args[base + i];
-      if (a.M == 0 || a.N == 0 || a.batch == 0) continue;
-      const int k = G.n++;
-      G.p[k] = a;
-      const int Ne = a.N + (a.bias_grad ? 1 : 0);
-      G.tx[k] = ceil_div(Ne, BN); G.ty[k] = ceil_div(a.M, BM);
-      const int nk = ceil_div(a.K, BK);
-      int sk = 1;
-      const bool plain = a.act == MMDA_ACT_NONE && a.drop_p <= 0.f && !a.gate;
-      if (plain && nk >= 8 && tiles_total < 1024) {
-        sk = (1024 + tiles_total - 1) / tiles_total;
-        if (sk > nk / 2) sk = nk / 2;
-        if (sk > 32) sk = 32;
-        if (sk < 1) sk = 1;
-      }
-      sk = splitk_slices(nk, sk);
-      G.splitk[k] = sk;
-      G.slab[k] = nullptr; G.ldn[k] = Ne;
-      if (sk > 1) {
-        SplitKJob J = {};
-        J.C = a.C; J.M = a.M; J.N = a.N; J.ldn = Ne; J.ldc = a.ldc; J.sk = sk; J.batch = a.batch;
-        J.strideC = a.strideC; J.strideBias = a.strideBias; J.alpha = a.alpha; J.bias = a.bias; J.bias2 = a.bias2;
-        J.bias_grad = a.bias_grad; J.bias_grad2 = a.bias_grad2; J.accumulate = a.accumulate;
-        J.slab = reinterpret_cast<const float*>((uintptr_t)slab_floats);      // offset for now; the base is added below
-        slab_floats += (int64_t)a.batch * sk * a.M * Ne;
-        jobs.push_back(J); jk.push_back(k);
-      }
-      G.start[k] = blocks;
-      blocks += G.tx[k] * G.ty[k] * a.batch * sk;
-    }
-    for (int k = G.n; k <= GROUP_MAX; ++k) G.start[k] = blocks;
-    for (int k = G.n; k < GROUP_MAX; ++k) { G.p[k] = G.p[0]; G.tx[k] = G.ty[k] = G.splitk[k] = 1; G.slab[k] = nullptr; G.ldn[k] = 0; }
-    if (blocks == 0) continue;
-    if (!jobs.empty()) {
-      float* slab_base = mmda_scratch_get(s, sizeof(float) * (size_t)slab_floats);
-      if (!slab_base) return MMDA_ELAUNCH;
-      for (size_t j = 0; j < jobs.size(); ++j) {
-        float* p = slab_base + (int64_t)(uintptr_t)jobs[j].slab;
-        jobs[j].slab = p; G.slab[jk[j]] = p;
-      }
-    }
-    hipLaunchKernelGGL(gemm_grouped_kernel, dim3(blocks), dim3(256), 0, s, G);
+    for (int k = P.n; k <= GROUP_MAX; ++k) G.start[k] = P.blocks;
+    for (int k = P.n; k < GROUP_MAX; ++k) { G.p[k] = G.p[0]; G.tx[k] = G.ty[k] = G.splitk[k] = 1; G.slab[k] = nullptr; G.ldn[k] = 0; }
+    hipLaunchKernelGGL(gemm_grouped_kernel, dim3(P.blocks), dim3(256), 0, s, G);
     MMDA_CHECK_LAUNCH("mmda_gemm_grouped");
-    if (!jobs.empty()) { const int rc = mmda_splitk_reduce(jobs.data(), (int)jobs.size(), s); if (rc) return rc; }
+    if (njobs) { const int rc = mmda_splitk_reduce(jobs, njobs, s); if (rc) return rc; }
   }
   return MMDA_OK;
 }

@@ -9,6 +9,7 @@
 // 32 MFMAs per wave and k-tile against 16 ds_read_b128 and 4+4 16-byte global loads per thread.  Two register stages
 // of prefetch (k+1 and k+2) because these problems only offer ~1 workgroup per CU and cannot hide HBM latency by occupancy.
 #include "common.h"
+#include "internal.h"
 #include "convert_tile.h"
 #include "splitk.h"
 #include <algorithm>

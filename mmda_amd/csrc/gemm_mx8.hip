@@ -12,6 +12,7 @@
 // The quantiser writes operands in exactly that order, so a GEMM lane fetches its 32 bytes with two 16-byte loads:
 //   Q[row][kstep][g][32 bytes],  S[row][kstep] = one dword of four scale bytes (byte g = block g)
 #include "common.h"
+#include "internal.h"
 
 namespace {
 

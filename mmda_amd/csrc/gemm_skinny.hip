@@ -13,6 +13,7 @@
 //     alpha, bias, accumulate, activation, dropout, relu-gate, sigmoid-backward factor, second destination.
 // Up to 8 independent problems per launch.  Deterministic: no atomics, fixed reduction order.
 #include "common.h"
+#include "internal.h"
 #include "transpose_tile.h"
 
 namespace {

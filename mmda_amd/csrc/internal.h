@@ -1,0 +1,60 @@
+// Host-side functions that cross the .hip files without being part of the C ABI (include/mmda_hip.h), each declared once, grouped by
+// the file that defines it.  The fused row launches have a header of their own (fused_rows.h), the split-K reduce sits beside its job
+// struct (splitk.h).
+#pragma once
+#include "common.h"
+
+// ---- api.hip
+void mmda_set_error(const char* what, hipError_t e);
+#define MMDA_CHECK_LAUNCH(name)                                   \
+  do {                                                            \
+    hipError_t _e = hipGetLastError();                            \
+    if (_e != hipSuccess) { mmda_set_error(name, _e); return MMDA_ELAUNCH; } \
+  } while (0)
+float* mmda_scratch_get(hipStream_t s, size_t bytes);       // per-stream scratch: valid until the stream's next request
+
+// ---- gemm.hip: mmda_gemm_grouped with split-K sized as if `absent` were launched too
+int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_args* absent, int n_absent, void* stream);
+
+// ---- norm.hip
+// the backward of up to four plain LayerNorms in the 16-byte form, gamma / beta gradients left as per-block partials in `parts`
+bool mmda_ln_bwd_parts_applies(const mmda_ln_bwd_args* a, int n);
+int64_t mmda_ln_parts_floats(const mmda_ln_bwd_args* a, int n);
+int mmda_ln_bwd_parts(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
+int mmda_ln_parts_finish(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
+// mmda_embed_scatter_add with the batch's lengths (padding positions are skipped); lists of `rows` positions take the sort-based form
+int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream);
+bool mmda_embed_scatter_sorts(int rows);
+// embed_update = sparse over a short id list.  rows (n, D): the gradient rows of the list's positions; lengths / B as in the scatter
+int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                 void* stream);
+
+// ---- dist.hip: the sort-based scatter, whole and in two halves (the sorted id list early, the sums behind the gradient rows), and
+// the sparse update over a long list (sorts it first) or one already sorted by mmda_embed_sort_ids
+int mmda_embed_scatter_sorted(float* dW, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B, void* stream);
+int mmda_embed_sort_ids(const int64_t* ids, int n, const int* lengths, int B, int table_rows, unsigned* sorted, void* stream);
+int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D, int table_rows, const float* rows, void* stream);
+int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                  void* stream);
+int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
+
+// ---- optim.hip
+int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      // two buffers cleared by one launch
+// mmda_clamp_adam whose launch does not complete before *wait_flag reaches wait_value
+int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
+                         float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream);
+// SparseAdamArgs from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
+int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
+                          float clip, float grad_scale, int step);
+
+// ---- losses.hip
+// mmda_loss_cmd_pairs whose launch, as the last thing it does, sets *flag = value (flag joins, common.h: flag_wait).  Only the
+// single-workgroup form can: mmda_loss_cmd_sets_flag says whether a call of that shape will, and a flag given to any other shape is
+// MMDA_EINVAL.  flag == nullptr: the plain call.
+bool mmda_loss_cmd_sets_flag(int B, int D);
+int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
+                             float value_scale, float* loss, float* dx, void* stream, unsigned* flag, unsigned value);
+
+// ---- lstm_cluster.hip: the resident recurrences of lstm.hip's entry points
+int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, const int32_t* lengths, void* stream, bool bwd,
+                             int* used);

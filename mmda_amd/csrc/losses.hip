@@ -3,7 +3,7 @@
 // the total loss is a fixed weighted sum (solver.py:175-181), so the backward seed of each term is its weight.
 // These are batch-statistic reductions over (B, 128)-sized tensors: latency work on a handful of workgroups.
 #include "common.h"
-#include "splitk.h"
+#include "internal.h"
 
 namespace {
 
@@ -919,10 +919,6 @@ extern "C" int mmda_loss_conf(const float* scores, const float* tcp, const float
   return MMDA_OK;
 }
 
-extern "C" int64_t mmda_loss_diff_work_floats(int B, int D) {
-  return (int64_t)12 * B * D + 6 * B + 6 * D + (int64_t)12 * B * B;
-}
-
 namespace {
 bool fill_pairs(PairList& pl, int nt, int np, const int* pairs, int max_t) {
   if (nt < 2 || nt > max_t || np < 1 || np > 6 || !pairs) return false;
@@ -934,88 +930,99 @@ bool fill_pairs(PairList& pl, int nt, int np, const int* pairs, int max_t) {
   }
   return true;
 }
+
+// the work buffer of mmda_loss_diff_pairs, laid out for six tensors whatever nt is
+struct DiffWork {
+  float *Ahat, *dA, *invn, *mean, *K, *Ksum;
+  int64_t floats = 0;                             // of the whole buffer (work == nullptr: only this is wanted)
+  DiffWork(float* work, int64_t B, int64_t D) {
+    float** const field[6] = {&Ahat, &dA, &invn, &mean, &K, &Ksum};
+    const int64_t size[6] = {6 * B * D, 6 * B * D, 6 * B, 6 * D, 6 * B * B, 6 * B * B};
+    for (int i = 0; i < 6; ++i) { *field[i] = work ? work + floats : nullptr; floats += size[i]; }
+  }
+};
+
+// Up to this many rows a tensor's rows stay in registers (the fast kernels below: at most 32 per thread), the products go out as
+// row-skinny launches, and the finish launch -- with nothing but such a launch, which takes no scratch, between it and the combine
+// launch -- adds the loss partials itself.
+constexpr int DIFF_FEW_ROWS = 256;
+constexpr int FAST_COLS = 128;                    // columns of the fast forms, DiffLoss and CMD
+
+// the fast DiffLoss kernels at rows per thread 4 / 8 / 16 / 32 (B <= 32 / 64 / 128 / 256)
+typedef void (*DiffPrepKernel)(const float*, int64_t, int, int, float*, float*, float*);
+typedef void (*DiffFinishKernel)(const float*, const float*, int, int, int64_t, float*, const float*, int, float*);
+struct DiffFastKernels { DiffPrepKernel prep; DiffFinishKernel finish; };
+DiffFastKernels pick_diff_fast(int B) {
+  static const DiffPrepKernel prep[4] = {diff_prep_fast_kernel<4>, diff_prep_fast_kernel<8>, diff_prep_fast_kernel<16>,
+                                         diff_prep_fast_kernel<32>};
+  static const DiffFinishKernel finish[4] = {diff_finish_fast_kernel<4>, diff_finish_fast_kernel<8>, diff_finish_fast_kernel<16>,
+                                             diff_finish_fast_kernel<32>};
+  const int i = B <= 32 ? 0 : (B <= 64 ? 1 : (B <= 128 ? 2 : 3));
+  return DiffFastKernels{prep[i], finish[i]};
+}
+
+// the g.batch plain f32 products that `g` describes: one row-skinny launch (up to six), or one batched mmda_gemm
+int diff_products(const mmda_gemm_args& g, bool skinny, void* stream) {
+  if (!skinny) return mmda_gemm(&g, stream);
+  mmda_skinny_args sk[6];
+  for (int k = 0; k < g.batch; ++k) {
+    sk[k] = mmda_skinny_args{};
+    sk[k].M = g.M; sk[k].N = g.N; sk[k].K = g.K; sk[k].transB = g.transB;
+    sk[k].A = g.A + k * g.strideA; sk[k].lda = g.lda;
+    sk[k].B = g.B + k * g.strideB; sk[k].ldb = g.ldb;
+    sk[k].C = g.C + k * g.strideC; sk[k].ldc = g.ldc;
+  }
+  return mmda_gemm_skinny(sk, g.batch, stream);
+}
 }  // namespace
+
+extern "C" int64_t mmda_loss_diff_work_floats(int B, int D) { return DiffWork(nullptr, B, D).floats; }
 
 extern "C" int mmda_loss_diff_pairs(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int B, int D, float scale,
                                     float* loss, float* dx, float* work, void* stream) {
   PairList pl;
   if (!x || !work || B <= 0 || D <= 0 || !fill_pairs(pl, nt, np, pairs_host, 6)) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  float* Ahat = work;                               // 6*B*D
-  float* dA = Ahat + (int64_t)6 * B * D;            // 6*B*D
-  float* invn = dA + (int64_t)6 * B * D;            // 6*B
-  float* mean = invn + 6 * B;                       // 6*D
-  float* K = mean + 6 * D;                          // 6*B*B
-  float* Ksum = K + (int64_t)6 * B * B;             // 6*B*B
-  const bool fast = D <= 128 && B <= 256;            // rows per thread 4 / 8 / 16 / 32 (B <= 32 / 64 / 128 / 256)
-  if (fast) {
-    if (B <= 32) hipLaunchKernelGGL(diff_prep_fast_kernel<4>, dim3(nt), dim3(1024), 0, s, x, stride, B, D, Ahat, invn, mean);
-    else if (B <= 64) hipLaunchKernelGGL(diff_prep_fast_kernel<8>, dim3(nt), dim3(1024), 0, s, x, stride, B, D, Ahat, invn, mean);
-    else if (B <= 128) hipLaunchKernelGGL(diff_prep_fast_kernel<16>, dim3(nt), dim3(1024), 0, s, x, stride, B, D, Ahat, invn, mean);
-    else hipLaunchKernelGGL(diff_prep_fast_kernel<32>, dim3(nt), dim3(1024), 0, s, x, stride, B, D, Ahat, invn, mean);
-  } else {
-    hipLaunchKernelGGL(diff_prep_kernel, dim3(nt), dim3(256), 0, s, x, stride, B, D, Ahat, invn, mean);
-  }
+  const DiffWork w(work, B, D);
+  const bool few_rows = B <= DIFF_FEW_ROWS;
+  const bool fast = D <= FAST_COLS && few_rows;
+  const DiffFastKernels fk = pick_diff_fast(B);
+  if (fast) hipLaunchKernelGGL(fk.prep, dim3(nt), dim3(1024), 0, s, x, stride, B, D, w.Ahat, w.invn, w.mean);
+  else hipLaunchKernelGGL(diff_prep_kernel, dim3(nt), dim3(256), 0, s, x, stride, B, D, w.Ahat, w.invn, w.mean);
   MMDA_CHECK_LAUNCH("mmda_loss_diff/prep");
-  const int64_t BB = (int64_t)B * B;
-  int rc;
-  if (B <= 256) {
-    // few rows: the nt Gram matrices K_k = Ahat_k Ahat_k^T as one row-skinny launch
-    mmda_skinny_args sk[6];
-    for (int k = 0; k < nt; ++k) {
-      sk[k] = mmda_skinny_args{};
-      sk[k].M = B; sk[k].N = B; sk[k].K = D; sk[k].transB = 1; sk[k].A = Ahat + (int64_t)k * B * D; sk[k].lda = D;
-      sk[k].B = Ahat + (int64_t)k * B * D; sk[k].ldb = D; sk[k].C = K + k * BB; sk[k].ldc = B;
-    }
-    rc = mmda_gemm_skinny(sk, nt, stream);
-  } else {
-    mmda_gemm_args g = {};
-    g.mode = MMDA_F32; g.transA = 0; g.transB = 1; g.M = B; g.N = B; g.K = D; g.batch = nt;
-    g.A = Ahat; g.lda = D; g.strideA = (int64_t)B * D;
-    g.B = Ahat; g.ldb = D; g.strideB = (int64_t)B * D;
-    g.C = K; g.ldc = B; g.strideC = (int64_t)B * B;
-    rc = mmda_gemm(&g, stream);
-  }
+  const int64_t BB = (int64_t)B * B, BD = (int64_t)B * D;
+  // the nt Gram matrices K_k = Ahat_k Ahat_k^T
+  mmda_gemm_args g = {};
+  g.mode = MMDA_F32; g.transA = 0; g.transB = 1; g.M = B; g.N = B; g.K = D; g.batch = nt;
+  g.A = w.Ahat; g.lda = D; g.strideA = BD;
+  g.B = w.Ahat; g.ldb = D; g.strideB = BD;
+  g.C = w.K; g.ldc = B; g.strideC = BB;
+  int rc = diff_products(g, few_rows, stream);
   if (rc) return rc;
   int blocks = (int)((BB + 255) / 256); if (blocks > 256) blocks = 256;
   // the loss value: one partial per block (per-stream scratch), added in block order -- by the finish launch below when it follows with
   // nothing but a row-skinny GEMM in between (which takes no scratch), else by a launch of its own right here
   float* lparts = loss ? mmda_scratch_get(s, sizeof(float) * 256) : nullptr;
   if (loss && !lparts) return MMDA_ELAUNCH;
-  hipLaunchKernelGGL(diff_combine_kernel, dim3(blocks), dim3(256), 0, s, K, B, D, scale, lparts, Ksum, pl);
+  hipLaunchKernelGGL(diff_combine_kernel, dim3(blocks), dim3(256), 0, s, w.K, B, D, scale, lparts, w.Ksum, pl);
   MMDA_CHECK_LAUNCH("mmda_loss_diff/combine");
-  const bool sum_later = loss && dx && B <= 256;
+  const bool sum_later = loss && dx && few_rows;
   if (loss && !sum_later) {
     hipLaunchKernelGGL(loss_parts_finish_kernel, dim3(1), dim3(64), 0, s, lparts, blocks, loss);
     MMDA_CHECK_LAUNCH("mmda_loss_diff/loss");
   }
   float* const loss_later = sum_later ? loss : nullptr;
   if (!dx) return MMDA_OK;
-  if (B <= 256) {
-    mmda_skinny_args sk[6];
-    for (int k = 0; k < nt; ++k) {
-      sk[k] = mmda_skinny_args{};
-      sk[k].M = B; sk[k].N = D; sk[k].K = B; sk[k].transB = 0; sk[k].A = Ksum + k * BB; sk[k].lda = B;
-      sk[k].B = Ahat + (int64_t)k * B * D; sk[k].ldb = D; sk[k].C = dA + (int64_t)k * B * D; sk[k].ldc = D;
-    }
-    rc = mmda_gemm_skinny(sk, nt, stream);
-  } else {
-    mmda_gemm_args h = {};
-    h.mode = MMDA_F32; h.transA = 0; h.transB = 0; h.M = B; h.N = D; h.K = B; h.batch = nt;
-    h.A = Ksum; h.lda = B; h.strideA = BB;
-    h.B = Ahat; h.ldb = D; h.strideB = (int64_t)B * D;
-    h.C = dA; h.ldc = D; h.strideC = (int64_t)B * D;
-    rc = mmda_gemm(&h, stream);
-  }
+  // dAhat_k = Ksum_k Ahat_k
+  mmda_gemm_args h = {};
+  h.mode = MMDA_F32; h.transA = 0; h.transB = 0; h.M = B; h.N = D; h.K = B; h.batch = nt;
+  h.A = w.Ksum; h.lda = B; h.strideA = BB;
+  h.B = w.Ahat; h.ldb = D; h.strideB = BD;
+  h.C = w.dA; h.ldc = D; h.strideC = BD;
+  rc = diff_products(h, few_rows, stream);
   if (rc) return rc;
-  if (fast) {
-    if (B <= 32) hipLaunchKernelGGL(diff_finish_fast_kernel<4>, dim3(nt), dim3(1024), 0, s, dA, invn, B, D, stride, dx, lparts, blocks, loss_later);
-    else if (B <= 64) hipLaunchKernelGGL(diff_finish_fast_kernel<8>, dim3(nt), dim3(1024), 0, s, dA, invn, B, D, stride, dx, lparts, blocks, loss_later);
-    else if (B <= 128) hipLaunchKernelGGL(diff_finish_fast_kernel<16>, dim3(nt), dim3(1024), 0, s, dA, invn, B, D, stride, dx, lparts, blocks, loss_later);
-    else hipLaunchKernelGGL(diff_finish_fast_kernel<32>, dim3(nt), dim3(1024), 0, s, dA, invn, B, D, stride, dx, lparts, blocks, loss_later);
-  } else {
-    hipLaunchKernelGGL(diff_finish_kernel, dim3(nt), dim3(256), 0, s, dA, invn, B, D, stride, dx, lparts, blocks, loss_later);
-  }
+  if (fast) hipLaunchKernelGGL(fk.finish, dim3(nt), dim3(1024), 0, s, w.dA, w.invn, B, D, stride, dx, lparts, blocks, loss_later);
+  else hipLaunchKernelGGL(diff_finish_kernel, dim3(nt), dim3(256), 0, s, w.dA, w.invn, B, D, stride, dx, lparts, blocks, loss_later);
   MMDA_CHECK_LAUNCH("mmda_loss_diff/finish");
   return MMDA_OK;
 }
@@ -1027,44 +1034,44 @@ extern "C" int mmda_loss_diff(const float* x, int64_t stride, int B, int D, floa
   return mmda_loss_diff_pairs(x, stride, 6, 6, pairs, B, D, scale, loss, dx, work, stream);
 }
 
-// internal (misa.hip): arm the NEXT mmda_loss_cmd* call of this thread to set *flag = value at the end of its launch -- honoured by the
-// single-workgroup form only (mmda_loss_cmd_sets_flag says whether a call of that shape will)
-static thread_local unsigned* g_cmd_tail_flag = nullptr;
-static thread_local unsigned g_cmd_tail_value = 0u;
-bool mmda_loss_cmd_sets_flag(int B, int D) { return D <= 128 && B <= 64; }
-void mmda_loss_cmd_arm_flag(unsigned* flag, unsigned value) { g_cmd_tail_flag = flag; g_cmd_tail_value = value; }
+namespace {
+typedef void (*CmdFastKernel)(const float*, int64_t, int, int, float, float, float*, float*, PairList, int, unsigned*, unsigned);
+CmdFastKernel pick_cmd_fast(int B) { return B <= 32 ? cmd_fast_kernel<4> : cmd_fast_kernel<8>; }      // rows per thread
+constexpr size_t CMD_FAST_LDS = sizeof(float) * (8 * 3 * 128 + 8 * 3 * 4 * 128 + 32);                // P1, P2, N2 of the fast forms
+}  // namespace
 
-extern "C" int mmda_loss_cmd_pairs(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D,
-                                   float scale, float value_scale, float* loss, float* dx, void* stream) {
-  unsigned* tflag = g_cmd_tail_flag;
-  const unsigned tvalue = g_cmd_tail_value;
-  g_cmd_tail_flag = nullptr;
-  PairList pl;
+// internal: whether a CMD call of this shape takes the single-workgroup form, the one that can set a flag-join word behind its stores
+bool mmda_loss_cmd_sets_flag(int B, int D) { return D <= FAST_COLS && B <= 64; }
+
+// internal (misa.hip): mmda_loss_cmd_pairs that sets *flag = value at the end of its launch (flag == nullptr: the plain call)
+int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
+                             float value_scale, float* loss, float* dx, void* stream, unsigned* flag, unsigned value) {
+  PairList pl;                                            // (at most three tensors: what the fast forms hold)
   if (!x || B <= 0 || D <= 0 || n_moments < 1 || n_moments > 5 || !fill_pairs(pl, nt, np, pairs_host, 3)) return MMDA_EINVAL;
-  if (nt <= 3 && D <= 128 && B <= 64) {
-    const size_t lds_fast = sizeof(float) * (8 * 3 * 128 + 8 * 3 * 4 * 128 + 32);
-    if (B <= 32)
-      hipLaunchKernelGGL(cmd_fast_kernel<4>, dim3(1), dim3(1024), lds_fast, (hipStream_t)stream, x, stride, B, D, scale, value_scale,
-                         loss, dx, pl, n_moments, tflag, tvalue);
-    else
-      hipLaunchKernelGGL(cmd_fast_kernel<8>, dim3(1), dim3(1024), lds_fast, (hipStream_t)stream, x, stride, B, D, scale, value_scale,
-                         loss, dx, pl, n_moments, tflag, tvalue);
+  hipStream_t s = (hipStream_t)stream;
+  if (mmda_loss_cmd_sets_flag(B, D)) {
+    hipLaunchKernelGGL(pick_cmd_fast(B), dim3(1), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments,
+                       flag, value);
     MMDA_CHECK_LAUNCH("mmda_loss_cmd");
     return MMDA_OK;
   }
-  if (nt <= 3 && D <= 128) {
-    const size_t lds_fast = sizeof(float) * (8 * 3 * 128 + 8 * 3 * 4 * 128 + 32);
-    hipLaunchKernelGGL(cmd_stream_kernel, dim3(dx ? nt : 1), dim3(1024), lds_fast, (hipStream_t)stream, x, stride, B, D, scale, value_scale, loss,
-                       dx, pl, n_moments);
+  if (flag) return MMDA_EINVAL;                           // no other form sets it: the waiting kernel would run into its poll limit
+  if (D <= FAST_COLS) {
+    hipLaunchKernelGGL(cmd_stream_kernel, dim3(dx ? nt : 1), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl,
+                       n_moments);
     MMDA_CHECK_LAUNCH("mmda_loss_cmd");
     return MMDA_OK;
   }
   size_t lds = sizeof(float) * 30 * D;
   if (lds > 60 * 1024) return MMDA_EINVAL;
-  hipLaunchKernelGGL(cmd_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, x, stride, B, D, scale, value_scale, loss, dx, pl,
-                     n_moments);
+  hipLaunchKernelGGL(cmd_kernel, dim3(1), dim3(256), lds, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments);
   MMDA_CHECK_LAUNCH("mmda_loss_cmd");
   return MMDA_OK;
+}
+
+extern "C" int mmda_loss_cmd_pairs(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D,
+                                   float scale, float value_scale, float* loss, float* dx, void* stream) {
+  return mmda_loss_cmd_pairs_tail(x, stride, nt, np, pairs_host, n_moments, B, D, scale, value_scale, loss, dx, stream, nullptr, 0u);
 }
 
 extern "C" int mmda_loss_cmd(const float* x, int64_t stride, int B, int D, float scale, float* loss, float* dx, void* stream) {

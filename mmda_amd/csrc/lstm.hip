@@ -12,6 +12,7 @@
 // the backward kernel needs).  Variable lengths: sample b is updated only while t < len_b; the reverse direction
 // walks t = T-1..0 from a zero state, so it effectively starts at len_b-1 (packed-sequence semantics).
 #include "common.h"
+#include "internal.h"
 #include "convert_tile.h"
 #include "transpose_tile.h"
 
@@ -447,11 +448,6 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_kernel(LstmLaunch L) {
     __syncthreads();
   }
 }
-
-}  // namespace
-int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, const int32_t* lengths, void* stream, bool bwd,
-                             int* used);   // lstm_cluster.hip
-namespace {
 
 int pick_maxt(int n, const mmda_lstm_desc* d) {
   int mx = 0;

@@ -20,6 +20,7 @@
 //   barrier, the grid always drains.  All workgroups of a launch are co-resident: the host caps a launch at 240
 //   single-workgroup-per-CU blocks (LDS > 80 KB each) and chunks larger batches over several launches.
 #include "common.h"
+#include "internal.h"
 #include <algorithm>
 #include <type_traits>
 #include <utility>

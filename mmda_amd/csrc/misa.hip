@@ -4,16 +4,7 @@
 // memory is owned here; no torch types; no host<->device synchronisation anywhere in a step.
 #include "common.h"
 #include "fused_rows.h"
-// internal entry points of norm.hip (not part of the C ABI)
-bool mmda_ln_bwd_parts_applies(const mmda_ln_bwd_args* a, int n);
-int64_t mmda_ln_parts_floats(const mmda_ln_bwd_args* a, int n);
-int mmda_ln_bwd_parts(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
-int mmda_ln_parts_finish(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
-int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream);
-bool mmda_embed_scatter_sorts(int rows);
-// ... and of dist.hip: the sort-based scatter in two halves (the sorted id list early, the sums behind the gradient rows)
-int mmda_embed_sort_ids(const int64_t* ids, int n, const int* lengths, int B, int table_rows, unsigned* sorted, void* stream);
-int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D, int table_rows, const float* rows, void* stream);
+#include "internal.h"
 
 #include <map>
 #include <string>
@@ -913,12 +904,12 @@ int eager_side_losses(mmda_misa* m, void* stream) {
   float* L = WS(m->losses);
   if (!rc) rc = mmda_loss_diff(WS(m->x6), BH, B, hs, c.diff_weight, L + 1, WS(m->d_x6), WS(m->diff_work), ss);
   // the chain's last launch sets the flag-join word itself where it can (single-workgroup CMD: no one-thread launch behind it)
-  m->fj1_armed = 0;
-  if (!rc && c.use_cmd_sim && P.fj_fwd && m->jflags && mmda_loss_cmd_sets_flag(B, hs)) {
-    mmda_loss_cmd_arm_flag(m->jflags + 0, m->jval[0] + 1);
-    m->fj1_armed = 1;
+  m->fj1_armed = (!rc && c.use_cmd_sim && P.fj_fwd && m->jflags && mmda_loss_cmd_sets_flag(B, hs)) ? 1 : 0;
+  if (!rc && c.use_cmd_sim) {
+    static const int sim_pairs[6] = {0, 1, 0, 2, 2, 1};      // what mmda_loss_cmd runs: (t,v), (t,a), (a,v), five moments, / 3
+    rc = mmda_loss_cmd_pairs_tail(WS(m->x6 + 3 * BH), BH, 3, 3, sim_pairs, 5, B, hs, c.sim_weight, 1.0f / 3.0f, L + 2, WS(m->d_x6 + 3 * BH), ss,
+                                  m->fj1_armed ? m->jflags + 0 : nullptr, m->jval[0] + 1);
   }
-  if (!rc && c.use_cmd_sim) rc = mmda_loss_cmd(WS(m->x6 + 3 * BH), BH, B, hs, c.sim_weight, L + 2, WS(m->d_x6 + 3 * BH), ss);
   if (!rc && m->zero_grad_pending) { rc = mmda_misa_zero_grad(m, stream); m->zero_grad_pending = 0; }
   m->eager_done = 1;
   return rc;

@@ -1,12 +1,8 @@
 // Row-wise kernels: LayerNorm forward/backward (wave-per-row shuffle reductions), embedding gather / scatter-add,
 // small elementwise helpers.  All HBM-bound; loads are lane-consecutive (coalesced 256 B per wave instruction).
 #include "common.h"
+#include "internal.h"
 #include "rowlocal.h"
-#include "splitk.h"
-
-int mmda_embed_scatter_sorted(float* dW, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B, void* stream);   // dist.hip
-int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream);
-bool mmda_embed_scatter_sorts(int rows);
 
 namespace {
 
@@ -465,6 +461,77 @@ int ln_bwd_check(const mmda_ln_bwd_args* a) {
 }  // namespace
 
 namespace {
+// Slot tables (LnMulti / LnBwdMulti).  The kernels find their problem by searching start[] over all LN_MAXP slots, so a table starts
+// zeroed, takes one ln_add() per problem that has work (start[n] is the running block count) and is closed by ln_close(): the tail of
+// start[] holds the total, which it returns, and the unused slots repeat slot 0.
+template <class Table, class Args>
+int ln_add(Table& L, const Args& a, int blocks) {
+  const int k = L.n++;
+  L.a[k] = a; L.start[k + 1] = L.start[k] + blocks;
+  return k;
+}
+int ln_add(LnBwdMulti& L, const mmda_ln_bwd_args& a, int blocks, int nblk, float* part) {
+  const int k = ln_add(L, a, blocks);
+  L.nblk[k] = nblk; L.part[k] = part;
+  return k;
+}
+void ln_pad_slot(LnMulti& L, int k) { L.a[k] = L.a[0]; }
+void ln_pad_slot(LnBwdMulti& L, int k) { L.a[k] = L.a[0]; L.nblk[k] = 1; L.part[k] = L.part[0]; }
+template <class Table>
+int ln_close(Table& L) {
+  for (int k = L.n + 1; k <= LN_MAXP; ++k) L.start[k] = L.start[L.n];
+  for (int k = L.n; k < LN_MAXP; ++k) ln_pad_slot(L, k);
+  return L.start[L.n];
+}
+// values per lane (64 nq >= n) of the table's widest problem
+template <class Table>
+int ln_max_nq(const Table& L) {
+  int nq = 1;
+  for (int k = 0; k < L.n; ++k) nq = max(nq, ceil_div(L.a[k].n, 64));
+  return nq;
+}
+
+// The 16-byte forms.  Floats per group: rows whose width is no multiple of four take 8-byte groups.
+int ln_vw(int n) { return (n & 3) ? 2 : 4; }
+// What forward and backward ask alike: a plain LayerNorm (no residual, activation or permutation) of even width within LNV_MAX groups
+// per lane ...
+template <class Args>
+bool ln_vec_plain(const Args& q) {
+  return (q.n & 1) == 0 && ceil_div(q.n, ln_vw(q.n) * 64) <= LNV_MAX && !q.res && q.act == MMDA_ACT_NONE && q.permute_S <= 0;
+}
+// ... whose operands (or-ed addresses; a NULL one is aligned) start every row on a group boundary.
+bool ln_vec_aligned(int n, uintptr_t operands) { return (operands & (4 * ln_vw(n) - 1)) == 0; }
+// Forward only: the bf16 copy, when wanted, in whole groups that fit LNV_MAX too.
+bool ln_fwd_vec_applies(const mmda_ln_args& q) {
+  return ln_vec_plain(q) && ln_vec_aligned(q.n, (uintptr_t)q.x | (uintptr_t)q.y | (uintptr_t)q.gamma | (uintptr_t)q.beta) &&
+         (!q.y_bf16 || ((q.ld_bf16 & 7) == 0 && ((uintptr_t)q.y_bf16 & 7) == 0 && ceil_div(q.ld_bf16, ln_vw(q.n) * 64) <= LNV_MAX));
+}
+// Backward only: d_x is wanted and no residual gradient is.
+bool ln_bwd_vec_applies(const mmda_ln_bwd_args& q) {
+  return ln_vec_plain(q) && !q.d_res && q.d_x &&
+         ln_vec_aligned(q.n, (uintptr_t)q.x | (uintptr_t)q.dy | (uintptr_t)q.gamma | (uintptr_t)q.d_x);
+}
+
+// The kernel instance for nq values / nv groups per lane (named in the order the object file has always had them: DESIGN.md §7).
+typedef void (*LnFwdKernel)(LnMulti);
+typedef void (*LnBwdKernel)(LnBwdMulti);
+LnFwdKernel pick_ln_fwd_vec(int nv) {
+  if (nv <= 2) return nv <= 1 ? ln_fwd_vec_kernel<1> : ln_fwd_vec_kernel<2>;
+  return nv <= 3 ? ln_fwd_vec_kernel<3> : ln_fwd_vec_kernel<4>;
+}
+LnFwdKernel pick_ln_fwd(int nq) {
+  if (nq <= 4) return nq <= 2 ? ln_fwd_kernel<2> : ln_fwd_kernel<4>;
+  return nq <= 10 ? ln_fwd_kernel<10> : ln_fwd_kernel<LN_MAXQ>;
+}
+LnBwdKernel pick_ln_bwd(int nq) {
+  if (nq <= 4) return nq <= 2 ? ln_bwd_kernel<2> : ln_bwd_kernel<4>;
+  return nq <= 10 ? ln_bwd_kernel<10> : ln_bwd_kernel<LN_MAXQ>;
+}
+LnBwdKernel pick_ln_bwd_vec(int nv) {
+  if (nv <= 2) return nv <= 1 ? ln_bwd_vec_kernel<1> : ln_bwd_vec_kernel<2>;
+  return nv <= 3 ? ln_bwd_vec_kernel<3> : ln_bwd_vec_kernel<4>;
+}
+
 // partial buffers of the problems that want parameter gradients (per-stream scratch, api.hip) ...
 int ln_pg_alloc(LnBwdMulti& L, hipStream_t s) {
   int64_t floats = 0;
@@ -480,16 +547,11 @@ int ln_pg_alloc(LnBwdMulti& L, hipStream_t s) {
 }
 // ... and the launch that adds them up, behind the launch that wrote them (same stream)
 int ln_pg_finish(const LnBwdMulti& Lw, hipStream_t s) {
-  LnBwdMulti F = Lw;
-  int blocks = 0, n = 0;
-  for (int k = 0; k < Lw.n; ++k) {
-    if (!Lw.part[k]) continue;
-    F.a[n] = Lw.a[k]; F.nblk[n] = Lw.nblk[k]; F.part[n] = Lw.part[k]; F.start[n] = blocks; blocks += ceil_div(2 * Lw.a[k].n, 16); n++;
-  }
-  if (n == 0) return MMDA_OK;
-  F.n = n;
-  for (int k = n; k <= LN_MAXP; ++k) F.start[k] = blocks;
-  for (int k = n; k < LN_MAXP; ++k) { F.a[k] = F.a[0]; F.nblk[k] = 1; F.part[k] = F.part[0]; }
+  LnBwdMulti F = {};
+  for (int k = 0; k < Lw.n; ++k)
+    if (Lw.part[k]) ln_add(F, Lw.a[k], ceil_div(2 * Lw.a[k].n, 16), Lw.nblk[k], Lw.part[k]);
+  if (F.n == 0) return MMDA_OK;
+  const int blocks = ln_close(F);
   hipLaunchKernelGGL(ln_pg_finish_kernel, dim3(blocks), dim3(256), 0, s, F);
   MMDA_CHECK_LAUNCH("mmda_layernorm_param_grads(finish)");
   return MMDA_OK;
@@ -501,44 +563,21 @@ extern "C" int mmda_layernorm_fwd_multi(const mmda_ln_args* a, int n, void* stre
   for (int i = 0; i < n; ++i)
     if (ln_check(a + i)) return MMDA_EINVAL;
   for (int base = 0; base < n; base += LN_MAXP) {
-    LnMulti L;
-    L.n = 0;
-    int blocks = 0;
-    for (int i = base; i < n && i < base + LN_MAXP; ++i) {
-      if (a[i].rows == 0) continue;
-      L.a[L.n] = a[i]; L.start[L.n] = blocks; blocks += ceil_div(a[i].rows, 4); L.n++;
-    }
-    for (int k = L.n; k <= LN_MAXP; ++k) L.start[k] = blocks;
-    for (int k = L.n; k < LN_MAXP; ++k) L.a[k] = L.a[0];
+    LnMulti L = {};
+    for (int i = base; i < n && i < base + LN_MAXP; ++i)
+      if (a[i].rows) ln_add(L, a[i], ceil_div(a[i].rows, 4));
+    const int blocks = ln_close(L);
     if (blocks == 0) continue;
-    int nq = 1;
-    for (int k = 0; k < L.n; ++k) nq = max(nq, ceil_div(L.a[k].n, 64));
+    const int nq = ln_max_nq(L);
     bool vec = nq > 2;                                   // (the 128-wide LayerNorms of the fusion block stay on the scalar form)
+    int nv = 1;                                          // groups per lane: the widest problem in ITS group size (bf16 copy included)
     for (int k = 0; k < L.n; ++k) {
       const mmda_ln_args& q = L.a[k];
-      const int vw = (q.n & 3) ? 2 : 4;                 // bytes per group 8 / 16: every row start must be that aligned
-      vec = vec && (q.n & 1) == 0 && ceil_div(q.n, vw * 64) <= LNV_MAX && !q.res && q.act == MMDA_ACT_NONE && q.permute_S <= 0 &&
-            ((((uintptr_t)q.x | (uintptr_t)q.y | (uintptr_t)q.gamma | (uintptr_t)q.beta) & (4 * vw - 1)) == 0) &&      // (a NULL y is aligned)
-            (!q.y_bf16 || ((q.ld_bf16 & 7) == 0 && ((uintptr_t)q.y_bf16 & 7) == 0 && ceil_div(q.ld_bf16, vw * 64) <= LNV_MAX));
+      vec = vec && ln_fwd_vec_applies(q);
+      nv = max(nv, ceil_div(max(q.n, q.y_bf16 ? q.ld_bf16 : 0), ln_vw(q.n) * 64));
     }
-    if (vec) {
-      int nv = 1;                                        // groups per lane: the widest problem in ITS group size (bf16 copy included)
-      for (int k = 0; k < L.n; ++k) {
-        const int vw = (L.a[k].n & 3) ? 2 : 4;
-        nv = max(nv, ceil_div(max(L.a[k].n, L.a[k].y_bf16 ? L.a[k].ld_bf16 : 0), vw * 64));
-      }
-      if (nv <= 1) hipLaunchKernelGGL(ln_fwd_vec_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-      else if (nv <= 2) hipLaunchKernelGGL(ln_fwd_vec_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-      else if (nv <= 3) hipLaunchKernelGGL(ln_fwd_vec_kernel<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-      else hipLaunchKernelGGL(ln_fwd_vec_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-      MMDA_CHECK_LAUNCH("mmda_layernorm_fwd(vec)");
-      continue;
-    }
-    if (nq <= 2) hipLaunchKernelGGL(ln_fwd_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else if (nq <= 4) hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else if (nq <= 10) hipLaunchKernelGGL(ln_fwd_kernel<10>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else hipLaunchKernelGGL(ln_fwd_kernel<LN_MAXQ>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    MMDA_CHECK_LAUNCH("mmda_layernorm_fwd");
+    hipLaunchKernelGGL(vec ? pick_ln_fwd_vec(nv) : pick_ln_fwd(nq), dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
+    MMDA_CHECK_LAUNCH(vec ? "mmda_layernorm_fwd(vec)" : "mmda_layernorm_fwd");
   }
   return MMDA_OK;
 }
@@ -549,27 +588,19 @@ extern "C" int mmda_layernorm_bwd_multi(const mmda_ln_bwd_args* a, int n, void* 
   for (int i = 0; i < n; ++i)
     if (ln_bwd_check(a + i)) return MMDA_EINVAL;
   for (int base = 0; base < n; base += LN_MAXP) {
-    LnBwdMulti L;
-    L.n = 0;
-    int blocks = 0;
+    LnBwdMulti L = {};
     for (int i = base; i < n && i < base + LN_MAXP; ++i) {
       if (a[i].rows == 0) continue;
       const bool pg = a[i].dgamma || a[i].dbeta;
       // with parameter gradients: 2 rows per wave keeps the per-column atomics at rows/8 adders; without: one row per wave
       int nb = ceil_div(a[i].rows, pg ? 8 : 4);
       if (nb > 1024) nb = 1024;
-      L.a[L.n] = a[i]; L.start[L.n] = blocks; L.nblk[L.n] = nb; blocks += nb; L.n++;
+      ln_add(L, a[i], nb, nb, nullptr);
     }
-    for (int k = L.n; k <= LN_MAXP; ++k) L.start[k] = blocks;
-    for (int k = L.n; k < LN_MAXP; ++k) { L.a[k] = L.a[0]; L.nblk[k] = 1; }
+    const int blocks = ln_close(L);
     if (blocks == 0) continue;
     if (ln_pg_alloc(L, (hipStream_t)stream)) return MMDA_ELAUNCH;
-    int nq = 1;
-    for (int k = 0; k < L.n; ++k) nq = max(nq, ceil_div(L.a[k].n, 64));
-    if (nq <= 2) hipLaunchKernelGGL(ln_bwd_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else if (nq <= 4) hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else if (nq <= 10) hipLaunchKernelGGL(ln_bwd_kernel<10>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-    else hipLaunchKernelGGL(ln_bwd_kernel<LN_MAXQ>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
+    hipLaunchKernelGGL(pick_ln_bwd(ln_max_nq(L)), dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
     MMDA_CHECK_LAUNCH("mmda_layernorm_bwd");
     if (ln_pg_finish(L, (hipStream_t)stream)) return MMDA_ELAUNCH;
   }
@@ -582,12 +613,16 @@ extern "C" int mmda_layernorm_bwd(const mmda_ln_bwd_args* a, void* stream) { ret
 // reads dy and x anyway), and mmda_ln_parts_finish adds them up on whatever stream the caller likes (behind an event).  Replaces
 // the separate column-strip pass over dy and x (mmda_layernorm_param_grads: 100 us at B = 256) when the 16-byte form applies.
 namespace {
-bool ln_bwd_vec_applies(const mmda_ln_bwd_args& q) {
-  const int vw = (q.n & 3) ? 2 : 4;
-  return (q.n & 1) == 0 && ceil_div(q.n, vw * 64) <= LNV_MAX && !q.res && !q.d_res && q.act == MMDA_ACT_NONE && q.permute_S <= 0 && q.d_x &&
-         ((((uintptr_t)q.x | (uintptr_t)q.dy | (uintptr_t)q.gamma | (uintptr_t)q.d_x) & (4 * vw - 1)) == 0);
-}
 int ln_parts_blocks(const mmda_ln_bwd_args& q) { int nb = ceil_div(q.rows, 16); return nb > 512 ? 512 : (nb < 1 ? 1 : nb); }
+// the table of both launches over `parts`; returns the blocks of the d_x launch
+int ln_parts_layout(const mmda_ln_bwd_args* a, int n, float* parts, LnBwdMulti& L) {
+  for (int i = 0; i < n; ++i) {
+    const int nb = ln_parts_blocks(a[i]);
+    ln_add(L, a[i], nb, nb, parts);
+    parts += (int64_t)nb * 2 * a[i].n;
+  }
+  return ln_close(L);
+}
 }  // namespace
 bool mmda_ln_bwd_parts_applies(const mmda_ln_bwd_args* a, int n) {
   if (!a || n <= 0 || n > LN_MAXP) return false;
@@ -600,35 +635,20 @@ int64_t mmda_ln_parts_floats(const mmda_ln_bwd_args* a, int n) {
   for (int i = 0; i < n; ++i) f += (int64_t)ln_parts_blocks(a[i]) * 2 * a[i].n;
   return f;
 }
-static void ln_parts_layout(const mmda_ln_bwd_args* a, int n, float* parts, LnBwdMulti& L, int& blocks) {
-  L.n = 0; blocks = 0;
-  for (int i = 0; i < n; ++i) {
-    const int nb = ln_parts_blocks(a[i]);
-    L.a[L.n] = a[i]; L.start[L.n] = blocks; L.nblk[L.n] = nb; L.part[L.n] = parts; parts += (int64_t)nb * 2 * a[i].n;
-    blocks += nb; L.n++;
-  }
-  for (int k = L.n; k <= LN_MAXP; ++k) L.start[k] = blocks;
-  for (int k = L.n; k < LN_MAXP; ++k) { L.a[k] = L.a[0]; L.nblk[k] = 1; L.part[k] = L.part[0]; }
-}
 int mmda_ln_bwd_parts(const mmda_ln_bwd_args* a, int n, float* parts, void* stream) {
   if (!mmda_ln_bwd_parts_applies(a, n) || !parts) return MMDA_EINVAL;
-  LnBwdMulti L;
-  int blocks = 0;
-  ln_parts_layout(a, n, parts, L, blocks);
-  int ng = 1;
-  for (int k = 0; k < L.n; ++k) ng = max(ng, ceil_div(L.a[k].n, ((L.a[k].n & 3) ? 2 : 4) * 64));
-  if (ng <= 1) hipLaunchKernelGGL(ln_bwd_vec_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-  else if (ng <= 2) hipLaunchKernelGGL(ln_bwd_vec_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-  else if (ng <= 3) hipLaunchKernelGGL(ln_bwd_vec_kernel<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
-  else hipLaunchKernelGGL(ln_bwd_vec_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
+  LnBwdMulti L = {};
+  const int blocks = ln_parts_layout(a, n, parts, L);
+  int nv = 1;
+  for (int k = 0; k < L.n; ++k) nv = max(nv, ceil_div(L.a[k].n, ln_vw(L.a[k].n) * 64));
+  hipLaunchKernelGGL(pick_ln_bwd_vec(nv), dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);
   MMDA_CHECK_LAUNCH("mmda_ln_bwd_parts");
   return MMDA_OK;
 }
 int mmda_ln_parts_finish(const mmda_ln_bwd_args* a, int n, float* parts, void* stream) {
   if (!a || n <= 0 || n > LN_MAXP || !parts) return MMDA_EINVAL;
-  LnBwdMulti L;
-  int blocks = 0;
-  ln_parts_layout(a, n, parts, L, blocks);
+  LnBwdMulti L = {};
+  ln_parts_layout(a, n, parts, L);
   return ln_pg_finish(L, (hipStream_t)stream);
 }
 
@@ -637,18 +657,15 @@ extern "C" int mmda_layernorm_param_grads(const mmda_ln_bwd_args* a, int n, void
   for (int i = 0; i < n; ++i)
     if (ln_bwd_check(a + i) || (!a[i].dgamma && !a[i].dbeta)) return MMDA_EINVAL;
   for (int base = 0; base < n; base += LN_MAXP) {
-    LnBwdMulti L;
-    L.n = 0;
-    int blocks = 0;
+    LnBwdMulti L = {};
     for (int i = base; i < n && i < base + LN_MAXP; ++i) {
       if (a[i].rows == 0) continue;
       const int strips = ceil_div(a[i].n, 64);
       int chunks = ceil_div(a[i].rows, 32);          // 8 rows per wave
       if (chunks * strips > 1024) chunks = (1024 + strips - 1) / strips;
-      L.a[L.n] = a[i]; L.start[L.n] = blocks; L.nblk[L.n] = chunks; blocks += chunks * strips; L.n++;
+      ln_add(L, a[i], chunks * strips, chunks, nullptr);
     }
-    for (int k = L.n; k <= LN_MAXP; ++k) L.start[k] = blocks;
-    for (int k = L.n; k < LN_MAXP; ++k) { L.a[k] = L.a[0]; L.nblk[k] = 1; }
+    const int blocks = ln_close(L);
     if (blocks == 0) continue;
     if (ln_pg_alloc(L, (hipStream_t)stream)) return MMDA_ELAUNCH;
     hipLaunchKernelGGL(ln_param_grads_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, L);

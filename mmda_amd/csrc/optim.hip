@@ -2,9 +2,8 @@
 // lr only -> betas (0.9, 0.999), eps 1e-8, no weight decay; --weight_decay is parsed but never used).  Pure HBM stream:
 // reads p,g,m,v and writes p,m,v = 28 B per parameter, float4 per lane.
 #include "common.h"
+#include "internal.h"
 #include <math.h>
-
-bool mmda_embed_scatter_sorts(int rows);      // norm.hip
 
 namespace {
 

@@ -6,8 +6,6 @@
 #pragma once
 #include "common.h"
 
-float* mmda_scratch_get(hipStream_t s, size_t bytes);       // api.hip
-
 struct SplitKJob {
   const float* slab;        // [batch][sk][M][ldn] raw partial products
   float* C;                 // (M, ldc) per batch entry

@@ -1,6 +1,7 @@
 // The reduce launch of the deterministic split-K (splitk.h): one thread per output element (n fastest: the slab reads and the C
 // accesses of a wave are contiguous), slabs summed in slice order 0, 1, ..., sk - 1.
 #include "splitk.h"
+#include "internal.h"
 
 namespace {
 

@@ -21,10 +21,14 @@ def _f(t):
     return t
 
 
-def gemm(A, B, *, mode="fp32", transA=False, transB=True, bias=None, bias2=None, out=None, accumulate=False, act="none",
-         A2=None, gather=None, alpha=1.0, drop_p=0.0, seed=0, site=0, gate=None, gate_scale=1.0, bias_grad=None, bias_grad2=None):
-    """C = act(alpha * opA(A (+A2)) @ opB(B) + bias + bias2 (+C)).  A,B 2-D or 3-D (batched, uniform strides)."""
-    lib = load()
+def _buf(t):
+    """Device pointer of an fp32 operand; an empty view (a problem with no rows) still names the buffer it was sliced from."""
+    return ptr(_f(t)) or t.untyped_storage().data_ptr() + 4 * t.storage_offset()
+
+
+def _gemm_args(A, B, *, mode="fp32", transA=False, transB=True, bias=None, bias2=None, out=None, accumulate=False, act="none",
+               A2=None, gather=None, alpha=1.0, drop_p=0.0, seed=0, site=0, gate=None, gate_scale=1.0, bias_grad=None, bias_grad2=None):
+    """The mmda_gemm_args of one problem and its output tensor (allocated here unless given)."""
     batched = A.dim() == 3
     Ab = A if batched else A.unsqueeze(0)
     Bb = B if B.dim() == 3 else B.unsqueeze(0)
@@ -37,16 +41,16 @@ def gemm(A, B, *, mode="fp32", transA=False, transB=True, bias=None, bias2=None,
         M, K = Ab.shape[1], Ab.shape[2]
     N = Bb.shape[1] if transB else Bb.shape[2]
     if out is None:
-        out = torch.zeros((nb, M, N), device=A.device, dtype=torch.float32)
+        out = torch.zeros((nb, max(M, 1), N), device=A.device, dtype=torch.float32)[:, :M]
         if not batched and B.dim() == 2:
             out = out[0]
     Cb = out if out.dim() == 3 else out.unsqueeze(0)
     g = _lib.GemmArgs()
     g.mode = MODE[mode]; g.transA = int(transA); g.transB = int(transB); g.M = M; g.N = N; g.K = K; g.batch = nb
-    g.A = ptr(_f(Ab)); g.lda = Ab.shape[2]; g.strideA = Ab.stride(0) if Ab.shape[0] > 1 else 0
+    g.A = _buf(Ab); g.lda = Ab.shape[2]; g.strideA = Ab.stride(0) if Ab.shape[0] > 1 else 0
     g.A2 = ptr(A2); g.gather = ptr(gather)
-    g.B = ptr(_f(Bb)); g.ldb = Bb.shape[2]; g.strideB = Bb.stride(0) if Bb.shape[0] > 1 else 0
-    g.C = ptr(_f(Cb)); g.ldc = N; g.strideC = Cb.stride(0) if Cb.shape[0] > 1 else 0
+    g.B = _buf(Bb); g.ldb = Bb.shape[2]; g.strideB = Bb.stride(0) if Bb.shape[0] > 1 else 0
+    g.C = _buf(Cb); g.ldc = N; g.strideC = Cb.stride(0) if Cb.shape[0] > 1 else 0
     g.bias = ptr(bias); g.bias2 = ptr(bias2)
     g.strideBias = (bias.stride(0) if (bias is not None and bias.dim() == 2) else 0)
     g.accumulate = int(accumulate); g.act = ACT[act]
@@ -55,9 +59,24 @@ def gemm(A, B, *, mode="fp32", transA=False, transB=True, bias=None, bias2=None,
     g.bias_grad = ptr(bias_grad); g.bias_grad2 = ptr(bias_grad2)
     if bias_grad is not None and bias_grad.dim() == 2:
         g.strideBias = bias_grad.stride(0)
-    check(lib.mmda_gemm(C.byref(g), stream_ptr()), "mmda_gemm")
+    return g, out
+
+
+def gemm(A, B, **kw):
+    """C = act(alpha * opA(A (+A2)) @ opB(B) + bias + bias2 (+C)).  A,B 2-D or 3-D (batched, uniform strides).
+    Keywords: see _gemm_args."""
+    g, out = _gemm_args(A, B, **kw)
+    check(load().mmda_gemm(C.byref(g), stream_ptr()), "mmda_gemm")
     return out
 
+
+def gemm_grouped(problems):
+    """mmda_gemm_grouped: independent GEMMs (any shapes, layouts, modes) in one launch per 16.  problems: list of dicts with A, B
+    and the keywords of gemm().  Returns the outputs."""
+    built = [_gemm_args(p["A"], p["B"], **{k: v for k, v in p.items() if k not in ("A", "B")}) for p in problems]
+    arr = (_lib.GemmArgs * len(built))(*[g for g, _ in built])
+    check(load().mmda_gemm_grouped(arr, len(built), stream_ptr()), "mmda_gemm_grouped")
+    return [out for _, out in built]
 
 
 def convert_bf16(jobs):

@@ -450,6 +450,63 @@ def test_gemm_weight_grad_with_fused_bias_grad(mode, M, N, K):
     assert relerr(db, db0 + dY.sum(0)) < TOL[mode] and relerr(db2, dY.sum(0)) < TOL[mode]
 
 
+def _grouped_problems(d):
+    """18 small problems for one mmda_gemm_grouped call: (layout, mode, M, N, K, extras).  K = 768 is 24 k-tiles (splits unless the
+    epilogue forbids it), K = 35 is two (never splits).  Returns a maker of fresh problem lists and the float64 references."""
+    spec = [("nt", "fp32", 33, 70, 768, {}), ("nt", "bf16", 70, 35, 768, {}), ("nn", "fp32", 35, 33, 768, {}),
+            ("nn", "bf16", 140, 70, 35, {}), ("tn", "fp32", 70, 33, 768, {"bias_grad": True, "accumulate": True}),
+            ("tn", "bf16", 35, 140, 768, {}), ("nt", "fp32", 7, 12, 35, {}), ("nt", "fp32", 0, 33, 768, {}),
+            ("nt", "bf16", 64, 64, 768, {"act": "relu"}), ("nn", "fp32", 65, 129, 35, {}), ("tn", "fp32", 33, 35, 35, {}),
+            ("nt", "bf16", 128, 33, 35, {}), ("nn", "bf16", 33, 65, 768, {}), ("tn", "bf16", 70, 70, 35, {}),
+            ("nt", "fp32", 140, 140, 768, {"alpha": -0.5}), ("nn", "fp32", 1, 70, 768, {}),
+            ("tn", "bf16", 33, 70, 768, {}), ("nt", "fp32", 35, 7, 35, {})]
+    g = torch.Generator().manual_seed(21)
+    data, refs = [], []
+    for lay, mode, M, N, K, ex in spec:
+        A = torch.randn((K, M) if lay == "tn" else (M, K), generator=g)
+        B = torch.randn((N, K) if lay == "nt" else (K, N), generator=g) / math.sqrt(K)
+        C0 = torch.randn(M, N, generator=g); bg0 = torch.randn(M, generator=g)
+        opA = A.double().t() if lay == "tn" else A.double(); opB = B.double().t() if lay == "nt" else B.double()
+        ref = ex.get("alpha", 1.0) * (opA @ opB)
+        if ex.get("accumulate"):
+            ref = ref + C0.double()
+        if ex.get("act") == "relu":
+            ref = ref.clamp_min(0)
+        data.append((A.to(d), B.to(d), C0, bg0))
+        refs.append((ref, bg0.double() + opA.sum(1)))
+
+    def make():
+        probs = []
+        for (lay, mode, M, N, K, ex), (A, B, C0, bg0) in zip(spec, data):
+            # (a problem without rows still names real buffers: empty views of one-row tensors)
+            p = dict(A=A if M else torch.zeros(1, K, device=d)[:0], B=B, mode=mode, transA=lay == "tn", transB=lay == "nt")
+            if ex.get("accumulate"):
+                p.update(out=C0.clone().to(d), accumulate=True)
+            if ex.get("bias_grad"):
+                p.update(bias_grad=bg0.clone().to(d))
+            p.update({k: v for k, v in ex.items() if k in ("act", "alpha")})
+            probs.append(p)
+        return probs
+    return spec, make, refs
+
+
+def test_gemm_grouped_two_launches_layouts_modes_split_and_not():
+    """fp32-operand mmda_gemm_grouped: more problems than one launch holds (GROUP_MAX = 16), nt / nn / tn, both modes, odd sizes,
+    split-K and unsplit slots side by side, bias gradient with accumulate, an activation (no split), an empty problem (no slot).
+    Every result against a float64 product; the same call twice gives the same bits (the split-K sums have a fixed order)."""
+    from mmda_amd import ops
+    spec, make, refs = _grouped_problems(dev())
+    first = make(); outs = ops.gemm_grouped(first)
+    again = make(); outs2 = ops.gemm_grouped(again)
+    for (lay, mode, M, N, K, ex), p, p2, out, out2, (ref, bg_ref) in zip(spec, first, again, outs, outs2, refs):
+        assert out.shape == (M, N) and torch.equal(out, out2), (lay, mode, M, N, K)
+        if M == 0:
+            continue
+        assert relerr(out, ref) < TOL[mode], (lay, mode, M, N, K)
+        if ex.get("bias_grad"):
+            assert relerr(p["bias_grad"], bg_ref) < TOL[mode] and torch.equal(p["bias_grad"], p2["bias_grad"])
+
+
 def test_gemm_batched_strided_and_act_gather():
     from mmda_amd import ops
     torch.manual_seed(2)
@@ -508,7 +565,7 @@ def test_colsum_and_embedding():
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
-@pytest.mark.parametrize("n,rows", [(600, 130), (70, 33), (148, 64), (128, 192), (16, 5)])
+@pytest.mark.parametrize("n,rows", [(600, 130), (70, 33), (148, 64), (128, 192), (16, 5), (150, 33), (300, 64)])
 def test_layernorm_fwd_bwd(n, rows):
     from mmda_amd import ops
     torch.manual_seed(5)
@@ -825,7 +882,7 @@ def _side(B, D, seed):
     return [torch.sigmoid(torch.randn(B, D)).requires_grad_(True) for _ in range(6)]
 
 
-@pytest.mark.parametrize("B,D", [(32, 128), (5, 16), (70, 128), (41, 100), (64, 128), (130, 128), (256, 128), (300, 128)])
+@pytest.mark.parametrize("B,D", [(32, 128), (5, 16), (70, 128), (41, 100), (64, 128), (130, 128), (256, 128), (300, 128), (5, 160)])
 def test_diff_cmd_recon_losses_and_grads(B, D):
     from types import SimpleNamespace
     from mmda_amd.utils import functions as F
