@@ -33,7 +33,9 @@ extern "C" {
 #define MMDA_EINVAL (-1)   /* bad argument / unsupported shape */
 #define MMDA_ELAUNCH (-2)  /* hipLaunch / runtime error (hipGetLastError text via mmda_last_error) */
 
-/* activation ids (reference config.py:25-27 activation_dict; prelu/rrelu unsupported) */
+/* activation ids (reference config.py:25-27 activation_dict).  Ids 0..7 need no parameters and are accepted wherever an `act` is
+ * taken; PReLU and RReLU need mmda_act_params, so only the entry points that carry one accept them (LayerNorm, mmda_act_dropout_*_p,
+ * the whole-model API).  Any other id is MMDA_EINVAL everywhere: no entry point reads an unknown id as the identity. */
 #define MMDA_ACT_NONE 0
 #define MMDA_ACT_RELU 1
 #define MMDA_ACT_SIGMOID 2
@@ -46,7 +48,9 @@ extern "C" {
 #define MMDA_ACT_RRELU 9          /* nn.RReLU(): x >= 0 ? x : s x; training: s ~ U(lo, hi) per element, else s = (lo + hi) / 2 */
 /* Parameters of the two parametrised activations of the reference's activation_dict (config.py:25-27); ignored by the others.
  * slope / dslope: device pointers to the PReLU slope and (backward) its gradient, accumulated with one atomic per row.
- * rand != 0 (training): the RReLU slope of element idx is lo + (hi - lo) * u(seed, site, idx), regenerated in the backward pass. */
+ * rand != 0 (training): the RReLU slope of element idx is lo + (hi - lo) * u(seed, site, idx), regenerated in the backward pass.
+ * Checked on the host before any launch: MMDA_ACT_PRELU with slope == NULL is MMDA_EINVAL, and so is MMDA_ACT_RRELU unless
+ * 0 <= lo <= hi and hi > 0 (a zeroed struct is not a request for ReLU). */
 typedef struct mmda_act_params {
   const float* slope; float* dslope;
   float lo, hi; int rand; uint64_t seed; int site;
@@ -86,6 +90,8 @@ typedef struct mmda_gemm_args {
                                                    column sums of dY come out of the same MFMA pass as a virtual all-ones column
                                                    of B; bias_grad2 receives the same sums (b_ih and b_hh share a gradient) */
 } mmda_gemm_args;
+/* act: MMDA_ACT_NONE .. MMDA_ACT_HARDSHRINK (no mmda_act_params here: PReLU / RReLU and unknown ids are MMDA_EINVAL).  K must be
+ * positive unless the problem is empty (M, N or batch zero); an empty problem launches nothing. */
 int mmda_gemm(const mmda_gemm_args* args, void* stream);
 /* n independent GEMMs (any mix of shapes / layouts / modes) in one launch; results as n mmda_gemm calls in any order */
 int mmda_gemm_grouped(const mmda_gemm_args* args, int n, void* stream);
@@ -151,7 +157,7 @@ typedef struct mmda_mx8_args {
   float* C; int ldc;
   const float* bias; int act;
   float drop_p; uint64_t drop_seed; int drop_site;     /* element index m * N + n, as in the f32 path */
-} mmda_mx8_args;
+} mmda_mx8_args;      /* act: MMDA_ACT_NONE .. MMDA_ACT_HARDSHRINK, anything else is MMDA_EINVAL; M, N, K positive */
 int64_t mmda_mx8_quant_bytes(int rows, int K);
 int mmda_mx8_quant(const mmda_mx8_quant_job* jobs, int n, void* stream);
 int mmda_gemm_mx8(const mmda_mx8_args* args, void* stream);
@@ -179,6 +185,7 @@ typedef struct mmda_skinny_args {
   const float* gate; int ldgate; float gate_scale;
   const float* dsig; const float* dsig2; int lddsig;
 } mmda_skinny_args;
+/* act: MMDA_ACT_NONE .. MMDA_ACT_HARDSHRINK, anything else is MMDA_EINVAL; K must be positive. */
 int mmda_gemm_skinny(const mmda_skinny_args* args, int n, void* stream);
 
 /* fp32 transposes, up to 20 per launch: dst[c * ldd + r] = src[r * ld + c] for r < rows, c < cols. */
@@ -224,6 +231,8 @@ typedef struct mmda_ln_args {
   void* y_bf16; int ld_bf16;                    /* optional second output (then y may be NULL): y as bf16 (rows, ld_bf16), columns n..ld_bf16-1 zero -- the
                                                  * K-major operand copy the next layer's input GEMM reads (no conversion launch between) */
 } mmda_ln_args;
+/* act: MMDA_ACT_NONE .. MMDA_ACT_RRELU, with actp as mmda_act_params asks; anything else is MMDA_EINVAL from all five LayerNorm
+ * entry points, before any launch. */
 int mmda_layernorm_fwd(const mmda_ln_args* a, void* stream);
 /* backward: dx_pre = LN'(dy); outputs: d_x = dx_pre * act'(x) (written or accumulated), d_res = dx_pre*dropmask,
  * dgamma += , dbeta += .  dy may be given in permuted (B,S,n) layout (same permute args as forward). */
@@ -236,7 +245,7 @@ typedef struct mmda_ln_bwd_args {
   int act; float drop_p; uint64_t drop_seed; int drop_site;
   int permute_S, permute_B;
   mmda_act_params actp;                         /* act = MMDA_ACT_PRELU / MMDA_ACT_RRELU only (dslope accumulated when d_x is written) */
-} mmda_ln_bwd_args;
+} mmda_ln_bwd_args;      /* act / actp: as mmda_ln_args */
 int mmda_layernorm_bwd(const mmda_ln_bwd_args* a, void* stream);
 /* Several independent LayerNorms in one launch (the three modalities'): results as n single calls. */
 int mmda_layernorm_fwd_multi(const mmda_ln_args* args, int n, void* stream);
@@ -356,7 +365,9 @@ int mmda_sigmoid_bwd_inplace(float* d, const float* y, int64_t n, void* stream);
 int mmda_act_dropout_fwd(const float* z, float* h, int64_t n, int act, float drop_p, uint64_t seed, int site, void* stream);
 int mmda_act_dropout_bwd(const float* dh, const float* z, float* dz, int64_t n, int act, float drop_p, uint64_t seed, int site,
                          void* stream);
-/* the same for the parametrised activations (MMDA_ACT_PRELU / MMDA_ACT_RRELU): parameters in *ap (host struct, copied) */
+/* the same for the parametrised activations (MMDA_ACT_PRELU / MMDA_ACT_RRELU): parameters in *ap (host struct, copied; may be NULL for
+ * ids 0..7).  act outside MMDA_ACT_NONE .. MMDA_ACT_RRELU, or parameters that mmda_act_params rules out: MMDA_EINVAL.  The two entry
+ * points above pass ap = NULL, so they accept ids 0..7. */
 int mmda_act_dropout_fwd_p(const float* z, float* h, int64_t n, int act, const mmda_act_params* ap, float drop_p, uint64_t seed, int site,
                            void* stream);
 int mmda_act_dropout_bwd_p(const float* dh, const float* z, float* dz, int64_t n, int act, const mmda_act_params* ap, float drop_p,

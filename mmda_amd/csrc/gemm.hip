@@ -402,10 +402,13 @@ namespace {
 bool valid_operands(const mmda_gemm_args& a) {
   return a.A && a.B && a.C && a.M >= 0 && a.N >= 0 && a.K >= 0 && a.batch >= 0 && !(a.gather && a.transA);
 }
-bool valid_problem(const mmda_gemm_args& a) {
-  return valid_operands(a) && (a.mode == MMDA_F32 || a.mode == MMDA_BF16) && !(a.bias_grad && !a.transA);
-}
 bool empty_problem(const mmda_gemm_args& a) { return a.M == 0 || a.N == 0 || a.batch == 0; }
+// the epilogue knows the unparametrised activations only (mmda_gemm_args has no mmda_act_params; the kernels take any other id for the
+// identity), and a problem that has outputs needs a k-tile to make them from (plan_gemm divides by the k-tile count)
+bool valid_problem(const mmda_gemm_args& a) {
+  return valid_operands(a) && (a.mode == MMDA_F32 || a.mode == MMDA_BF16) && !(a.bias_grad && !a.transA) &&
+         a.act >= MMDA_ACT_NONE && a.act <= MMDA_ACT_HARDSHRINK && (a.K > 0 || empty_problem(a));
+}
 bool plain_epilogue(const mmda_gemm_args& a) { return a.act == MMDA_ACT_NONE && a.drop_p <= 0.f && !a.gate; }
 int n_eff(const mmda_gemm_args& a) { return a.N + (a.bias_grad ? 1 : 0); }          // + the virtual ones column
 int tiles64(const mmda_gemm_args& a) { return ceil_div(n_eff(a), BN) * ceil_div(a.M, BM) * a.batch; }
@@ -505,8 +508,9 @@ GroupPlan plan_group(const mmda_gemm_args* args, int cnt, const mmda_gemm_args* 
 
 extern "C" int mmda_gemm(const mmda_gemm_args* a, void* stream) {
   if (!a || !valid_operands(*a)) return MMDA_EINVAL;
-  // An empty problem is MMDA_OK here before its mode and bias_grad are looked at; mmda_gemm_grouped rejects a bad one first.  The two
-  // orders cannot be made one without changing a return code, so each entry point keeps its own.
+  // An empty problem is MMDA_OK here before its mode, bias_grad and act are looked at; mmda_gemm_grouped rejects a bad one first.  The
+  // two orders cannot be made one without changing a return code, so each entry point keeps its own.  (K <= 0 is an error of a
+  // problem that has outputs only, in both.)
   if (empty_problem(*a)) return MMDA_OK;
   if (!valid_problem(*a)) return MMDA_EINVAL;
   const GemmPlan P = plan_gemm(*a);

@@ -158,6 +158,7 @@ extern "C" int mmda_gemm_mx8(const mmda_mx8_args* args, void* stream) {
   const mmda_mx8_args& a = *args;
   if (!a.Aq || !a.As || !a.Bq || !a.Bs || !a.C || a.M <= 0 || a.N <= 0 || a.K <= 0) return MMDA_EINVAL;
   if ((a.K % 128) || (a.N % 16) || a.ldc < a.N) return MMDA_EINVAL;
+  if (a.act < MMDA_ACT_NONE || a.act > MMDA_ACT_HARDSHRINK) return MMDA_EINVAL;        // no mmda_act_params here: unparametrised ids only
   if ((((uintptr_t)a.Aq | (uintptr_t)a.Bq) & 15) || (((uintptr_t)a.As | (uintptr_t)a.Bs) & 3)) return MMDA_EINVAL;
   Mx8Launch L;
   L.g = a;

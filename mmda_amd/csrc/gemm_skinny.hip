@@ -194,6 +194,7 @@ extern "C" int mmda_gemm_skinny(const mmda_skinny_args* args, int n, void* strea
     const mmda_skinny_args& a = args[i];
     if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K <= 0 || a.lda < a.K || a.ldc < a.N) return MMDA_EINVAL;
     if (a.transB ? a.ldb < a.K : a.ldb < a.N) return MMDA_EINVAL;
+    if (a.act < MMDA_ACT_NONE || a.act > MMDA_ACT_HARDSHRINK) return MMDA_EINVAL;      // no mmda_act_params here: unparametrised ids only
     if (a.K2 > 0 && (!a.A_2nd || !a.B_2nd || a.lda_2nd < a.K2 || (a.transB ? a.ldb_2nd < a.K2 : a.ldb_2nd < a.N))) return MMDA_EINVAL;
     if (a.C2 && (a.ldc2 < a.N || a.bias || a.act || a.drop_p > 0.f || a.gate)) return MMDA_EINVAL;   // C2 carries alpha/accumulate/dsig2 only
   }

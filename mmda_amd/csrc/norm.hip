@@ -448,15 +448,24 @@ int ew_blocks(int64_t n) {
 }  // namespace
 
 namespace {
+// An activation id with the parameters it needs, checked on the host before any launch: the kernels read p.slope[0] for PReLU
+// (common.h: act_slope_p) and take every id they do not know for the identity.  `ap` may be NULL for the unparametrised ids.  RReLU
+// wants 0 <= lo <= hi with hi > 0 (written so that a NaN fails): a zeroed struct is a caller's mistake, not a request for ReLU.
+int act_check(int act, const mmda_act_params* ap) {
+  if (act < MMDA_ACT_NONE || act > MMDA_ACT_RRELU) return MMDA_EINVAL;
+  if (act == MMDA_ACT_PRELU && (!ap || !ap->slope)) return MMDA_EINVAL;
+  if (act == MMDA_ACT_RRELU && (!ap || !(ap->lo >= 0.f && ap->lo <= ap->hi && ap->hi > 0.f))) return MMDA_EINVAL;
+  return MMDA_OK;
+}
 int ln_check(const mmda_ln_args* a) {
   if (!a->x || (!a->y && !a->y_bf16) || !a->gamma || !a->beta || a->rows < 0 || a->n <= 0 || a->n > LN_MAXQ * 64) return MMDA_EINVAL;      // (y may be NULL when only the bf16 copy is wanted)
   if (a->permute_S > 0 && (a->permute_B <= 0 || a->permute_S * a->permute_B != a->rows)) return MMDA_EINVAL;
-  return MMDA_OK;
+  return act_check(a->act, &a->actp);
 }
 int ln_bwd_check(const mmda_ln_bwd_args* a) {
   if (!a->dy || !a->x || !a->gamma || !a->mean || !a->rstd || a->rows < 0 || a->n <= 0 || a->n > LN_MAXQ * 64) return MMDA_EINVAL;
   if (a->permute_S > 0 && (a->permute_B <= 0 || a->permute_S * a->permute_B != a->rows)) return MMDA_EINVAL;
-  return MMDA_OK;
+  return act_check(a->act, &a->actp);
 }
 }  // namespace
 
@@ -734,7 +743,7 @@ extern "C" int mmda_sigmoid_bwd_inplace(float* d, const float* y, int64_t n, voi
 extern "C" int mmda_act_dropout_fwd_p(const float* z, float* h, int64_t n, int act, const mmda_act_params* ap, float drop_p, uint64_t seed,
                                       int site, void* stream) {
   if (!z || !h || n < 0) return MMDA_EINVAL;
-  if ((act == MMDA_ACT_PRELU && (!ap || !ap->slope)) || (act == MMDA_ACT_RRELU && !ap)) return MMDA_EINVAL;
+  if (act_check(act, ap)) return MMDA_EINVAL;
   if (n == 0) return MMDA_OK;
   const mmda_act_params p = ap ? *ap : mmda_act_params{};
   hipLaunchKernelGGL(act_drop_fwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, z, h, n, act, p, drop_p, seed, site);
@@ -748,7 +757,7 @@ extern "C" int mmda_act_dropout_fwd(const float* z, float* h, int64_t n, int act
 extern "C" int mmda_act_dropout_bwd_p(const float* dh, const float* z, float* dz, int64_t n, int act, const mmda_act_params* ap, float drop_p,
                                       uint64_t seed, int site, void* stream) {
   if (!dh || !z || !dz || n < 0) return MMDA_EINVAL;
-  if ((act == MMDA_ACT_PRELU && (!ap || !ap->slope)) || (act == MMDA_ACT_RRELU && !ap)) return MMDA_EINVAL;
+  if (act_check(act, ap)) return MMDA_EINVAL;
   if (n == 0) return MMDA_OK;
   const mmda_act_params p = ap ? *ap : mmda_act_params{};
   hipLaunchKernelGGL(act_drop_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dh, z, dz, n, act, p, drop_p, seed, site);

@@ -241,7 +241,15 @@ def embed_segment_sum(dW, ids, rows):
     return dW
 
 
-def layernorm_fwd(x, gamma, beta, *, res=None, act="none", drop_p=0.0, seed=0, site=0, permute=None, eps=1e-5):
+def _fill_actp(ap, slope=None, dslope=None, rrelu=None):
+    """mmda_act_params: slope / dslope are one-element device tensors (PReLU), rrelu = (lo, hi, rand, seed, site) (RReLU)."""
+    ap.slope = ptr(slope); ap.dslope = ptr(dslope)
+    if rrelu is not None:
+        ap.lo, ap.hi, ap.rand, ap.seed, ap.site = rrelu[0], rrelu[1], int(rrelu[2]), rrelu[3], rrelu[4]
+    return ap
+
+
+def layernorm_fwd(x, gamma, beta, *, res=None, act="none", drop_p=0.0, seed=0, site=0, permute=None, eps=1e-5, slope=None, rrelu=None):
     lib = load()
     n = x.shape[-1]
     rows = x.numel() // n
@@ -253,6 +261,7 @@ def layernorm_fwd(x, gamma, beta, *, res=None, act="none", drop_p=0.0, seed=0, s
     a.drop_p = drop_p; a.drop_seed = seed; a.drop_site = site
     a.permute_S, a.permute_B = permute if permute else (0, 0)
     a.eps = eps
+    _fill_actp(a.actp, slope, None, rrelu)
     check(lib.mmda_layernorm_fwd(C.byref(a), stream_ptr()), "layernorm_fwd")
     if permute:
         y = y.view(permute[1], permute[0], n)
@@ -260,7 +269,8 @@ def layernorm_fwd(x, gamma, beta, *, res=None, act="none", drop_p=0.0, seed=0, s
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, *, res=None, act="none", drop_p=0.0, seed=0, site=0, permute=None,
-                  want_dres=False):
+                  want_dres=False, slope=None, dslope=None, rrelu=None):
+    """dslope (PReLU, one element) is accumulated into."""
     lib = load()
     n = x.shape[-1]
     rows = x.numel() // n
@@ -273,25 +283,29 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, *, res=None, act="none", drop_p=0.0,
     a.dgamma = ptr(dg); a.dbeta = ptr(db); a.act = ACT[act]
     a.drop_p = drop_p; a.drop_seed = seed; a.drop_site = site
     a.permute_S, a.permute_B = permute if permute else (0, 0)
+    _fill_actp(a.actp, slope, dslope, rrelu)
     check(lib.mmda_layernorm_bwd(C.byref(a), stream_ptr()), "layernorm_bwd")
     return dx, dres, dg, db
 
 
-
-def layernorm_multi(xs, gammas, betas, dys):
+def layernorm_multi(xs, gammas, betas, dys, acts=None, slope=None, dslope=None, rrelu=None):
     """Several LayerNorms through the multi-problem launches: forward, input gradients (no parameter gradients) and the
-    separate parameter-gradient pass.  Returns per problem (y, dx, dgamma, dbeta)."""
+    separate parameter-gradient pass.  Returns per problem (y, dx, dgamma, dbeta).  acts: one activation name per problem (default
+    none); slope / dslope / rrelu are shared by all problems, as in the model (dslope is accumulated into by the input-gradient pass)."""
     lib = load()
     k = len(xs)
     fa = (_lib.LnArgs * k)(); ba = (_lib.LnBwdArgs * k)()
     keep = []
-    for a, b, x, g, be, dy in zip(fa, ba, xs, gammas, betas, dys):
+    for a, b, x, g, be, dy, act in zip(fa, ba, xs, gammas, betas, dys, acts or ["none"] * k):
         rows, n = x.shape
         y = torch.empty_like(x); mean = torch.empty(rows, device=x.device); rstd = torch.empty(rows, device=x.device)
         dx = torch.empty_like(x); dg = torch.zeros(n, device=x.device); db = torch.zeros(n, device=x.device)
         a.rows = rows; a.n = n; a.x = ptr(_f(x)); a.gamma = ptr(g); a.beta = ptr(be); a.y = ptr(y); a.mean = ptr(mean); a.rstd = ptr(rstd)
-        a.eps = 1e-5
+        a.eps = 1e-5; a.act = ACT[act]
+        _fill_actp(a.actp, slope, None, rrelu)
         b.rows = rows; b.n = n; b.dy = ptr(_f(dy)); b.x = ptr(x); b.gamma = ptr(g); b.mean = ptr(mean); b.rstd = ptr(rstd); b.d_x = ptr(dx)
+        b.act = ACT[act]
+        _fill_actp(b.actp, slope, dslope, rrelu)
         keep.append((y, dx, dg, db, mean, rstd))
     check(lib.mmda_layernorm_fwd_multi(fa, k, stream_ptr()), "layernorm_fwd_multi")
     check(lib.mmda_layernorm_bwd_multi(ba, k, stream_ptr()), "layernorm_bwd_multi")      # dgamma/dbeta NULL: dx only
@@ -299,6 +313,26 @@ def layernorm_multi(xs, gammas, betas, dys):
         b.dgamma = ptr(dg); b.dbeta = ptr(db); b.d_x = None
     check(lib.mmda_layernorm_param_grads(ba, k, stream_ptr()), "layernorm_param_grads")
     return [(y, dx, dg, db) for (y, dx, dg, db, _, _) in keep]
+
+
+def act_dropout_fwd(z, act, p=0.0, seed=0, site=0, slope=None, rrelu=None):
+    """h = dropout(act(z)) element-wise, any of the ten activations: mmda_act_dropout_fwd_p."""
+    lib = load()
+    h = torch.empty_like(z)
+    ap = _fill_actp(_lib.ActParams(), slope, None, rrelu)
+    check(lib.mmda_act_dropout_fwd_p(ptr(_f(z)), ptr(h), z.numel(), ACT[act], C.byref(ap), p, seed, site, stream_ptr()), "act_dropout_fwd")
+    return h
+
+
+def act_dropout_bwd(dh, z, act, p=0.0, seed=0, site=0, slope=None, rrelu=None, dslope=None):
+    """dz = dh * dropmask * act'(z); dslope (PReLU, one element) is accumulated into: mmda_act_dropout_bwd_p."""
+    lib = load()
+    dz = torch.empty_like(z)
+    ap = _fill_actp(_lib.ActParams(), slope, dslope, rrelu)
+    check(lib.mmda_act_dropout_bwd_p(ptr(_f(dh)), ptr(_f(z)), ptr(dz), z.numel(), ACT[act], C.byref(ap), p, seed, site, stream_ptr()),
+          "act_dropout_bwd")
+    return dz
+
 
 def lstm_pack(whh, mode):
     """Returns (packed_fwd, packed_bwd) byte tensors for one direction's W_hh (4H,H)."""

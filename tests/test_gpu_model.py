@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import misa_oracle as orc
 from golden_util import SIDE, batch_of, case_names, load_case, sample_idx
+from model_compare import assert_grads_match_oracle, assert_outputs_and_losses_match_oracle, rel, statement_order_losses
 
 DEV = "cuda:0"
 
@@ -25,13 +26,6 @@ def make_model(cfg, seed, precision):
     for mod in ():   # dropout is switched off by running the native path with training=False / model.eval()
         pass
     return m, c, P
-
-
-def rel(got, ref):
-    got = torch.as_tensor(got).detach().float().cpu(); ref = torch.as_tensor(ref).detach().float().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert torch.isfinite(got).all()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-6))
 
 
 def to_dev(batch):
@@ -64,14 +58,9 @@ def test_fp32_unfused_path_matches_golden_and_oracle(name):
     else:
         assert model.domain_label_t is None
     emo = b["emo"]
-    L = dict(cls=solver.get_cls_loss(scores, emo), diff=solver.get_diff_loss(), recon=solver.get_recon_loss(),
-             conf=solver.get_conf_loss(scores, emo))
-    L["sim"] = solver.get_cmd_loss() if cfg.use_cmd_sim else solver.get_domain_loss()
+    L, total = statement_order_losses(solver, cfg, scores, emo)
     for k, v in L.items():
         assert abs(v.item() - float(z["loss::" + k])) < 1e-4 * abs(float(z["loss::" + k])) + 1e-7, k
-    total = L["cls"] + cfg.diff_weight * L["diff"] + cfg.sim_weight * L["sim"] + cfg.recon_weight * L["recon"]
-    if cfg.use_confidNet:
-        total = total + cfg.conf_weight * L["conf"]
     assert abs(total.item() - float(z["loss::total"])) < 1e-4 * abs(float(z["loss::total"]))
     model.zero_grad()
     total.backward()
@@ -524,28 +513,16 @@ def test_degenerate_shapes_against_the_oracle(B, T, precision):
     o, L, G = orc.loss_and_grads(P, cfg, batch)
     tol = 1e-4 if precision == "fp32" else 1e-2
     pub = model._public()
-    assert rel(pub["scores"], o.scores.detach()) < tol and rel(pub["tcp"], o.tcp.detach()) < tol
-    Lg = model.read_losses()
-    for k in ("cls", "diff", "sim", "recon", "conf", "total"):
-        ref = float(getattr(L, k).detach())
-        assert abs(Lg[k] - ref) <= tol * abs(ref) + 1e-6, (k, Lg[k], ref)
+    assert_outputs_and_losses_match_oracle(pub["scores"], pub["tcp"], model.read_losses(), o, L, tol)
     if B == 1:
         # one sample: CMD's matchnorm is sqrt(0) for every moment and the reference's own gradients are NaN (69 of 99 tensors in the
         # oracle = torch autograd): there is no gradient to agree with; the forward pass and the losses are what is defined
         assert any(g is not None and not torch.isfinite(g).all() for g in G.values())
         return
     model._assign_grad_views()
-    for k, p in model.named_parameters():
-        if G[k] is None or k.endswith("self_attn.in_proj_bias"):
-            continue
-        g = p.grad.cpu().double(); ref = G[k].double()
-        if float(ref.norm()) < 1e-12:
-            assert float(g.norm()) < 1e-6, k
-            continue
-        l2 = float((g - ref).norm() / ref.norm())
-        # bf16: the quantisation floor of these tiny cases is higher than at full size (rounding only the LSTM weights and the
-        # inputs to bf16 inside the exact oracle moves vrnn1.weight_ih_l0 by 1.34e-1 at B=8,T=1: eight samples, nothing averages out)
-        assert l2 <= (2e-4 if precision == "fp32" else 2e-1), f"{k}: relative L2 error {l2:.3e}"
+    # bf16: the quantisation floor of these tiny cases is higher than at full size (rounding only the LSTM weights and the
+    # inputs to bf16 inside the exact oracle moves vrnn1.weight_ih_l0 by 1.34e-1 at B=8,T=1: eight samples, nothing averages out)
+    assert_grads_match_oracle(model, G, 2e-4 if precision == "fp32" else 2e-1)
 
 
 @pytest.mark.parametrize("name,precision", [("real_b8_t12_ragged", "fp32"), ("real_b16_t20_adv_confid", "fp32"), ("real_b32_t50_full", "bf16")])
