@@ -449,6 +449,35 @@ int mmda_mark_rows(unsigned char* mask, int rows, const int64_t* ids, int n, voi
 int mmda_embed_rows_sparse_adam(float* P, float* M, float* V, const int64_t* ids, int n, int D, const float* rows, const int32_t* lengths,
                                 int B, int table_rows, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
                                 void* stream);
+/* Dense Adam on a (table_rows, D) table without a pass over it (embed_update = deferred).  A row whose gradient is zero takes an update
+ * that needs nothing but the row and the update's two scalars, so it is applied when the row is next needed.  The caller counts the
+ * updates it applies, seq = 1, 2, 3 ... since the reset; the Adam step NUMBER `step` that makes an update's bias corrections is free
+ * (it may skip or repeat, as it may for mmda_clamp_adam).  State, owned by the caller on the device:
+ *   row_step[table_rows]   seq of the last update each row has taken
+ *   step_scalars           mmda_embed_deferred_scalar_floats(window) = 2 * window floats: for each of the last `window` updates s, at
+ *                          2 (s % window), the floats mmda_clamp_adam passes its kernel for that update -- lr / (1 - b1^step) and
+ *                          1 / sqrt(1 - b2^step), made in double
+ * mmda_embed_deferred_reset: every row current, no update counted yet (a new or a loaded table); the next update is seq 1.
+ * mmda_embed_rows_dense_adam, seq = the last update's + 1: the rows of the distinct ids at non-padding positions of `ids` (as in
+ *   mmda_embed_rows_sparse_adam) first take the updates they missed, then update `seq` with g = the position-order sum of their rows[p] --
+ *   through the same arithmetic as mmda_clamp_adam, so that after mmda_embed_rows_flush P, M and V hold the bits mmda_clamp_adam over
+ *   the whole table would have left, given the scattered gradient, the same lr, step, clip and grad_scale (> 0) at every update.  beta1,
+ *   beta2 and eps must not change while rows are stale.  An update whose seq is a multiple of `window` flushes the table first, so the
+ *   ring never loses scalars a row still needs; no other call reads or writes more than the listed rows.  A seq that is not the last
+ *   one + 1 gives wrong rows without an error: mmda_misa_* and the Python wrapper count for their callers.
+ * mmda_embed_rows_catch_up: the listed rows take the updates they missed up to `upto` (the last seq); one launch, one writer per row
+ *   (an integer claim on row_step), no float atomics.  Run it before reading rows of the table.
+ * mmda_embed_rows_flush: every stale row takes the updates it missed up to `upto`; with nothing stale nothing is written. */
+int64_t mmda_embed_deferred_scalar_floats(int window);
+int mmda_embed_deferred_reset(int32_t* row_step, int table_rows, void* stream);
+int mmda_embed_rows_dense_adam(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids, int n,
+                               int D, const float* rows, const int32_t* lengths, int B, int table_rows, float lr, float beta1, float beta2,
+                               float eps, float clip, float grad_scale, int seq, int step, void* stream);
+int mmda_embed_rows_catch_up(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window, const int64_t* ids,
+                             int n, int D, const int32_t* lengths, int B, int table_rows, float beta1, float beta2, float eps, int upto,
+                             void* stream);
+int mmda_embed_rows_flush(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window, int D, int table_rows,
+                          float beta1, float beta2, float eps, int upto, void* stream);
 /* clip_grad_value_(clip) + torch.optim.RMSprop with torch's defaults besides lr (alpha 0.99, eps 1e-8, no momentum, not centered):
  * the other entry of the reference's optimizer_dict (config.py:24).  grad_scale as in mmda_clamp_adam. */
 int mmda_clamp_rmsprop(float* p, const float* g, float* square_avg, int64_t n, float lr, float alpha, float eps, float clip,
@@ -517,6 +546,23 @@ int mmda_misa_set_fusion_fp8(mmda_misa* m, int on);
  * train step with do_adam = 0: mmda_misa_adam_step applies the rows update from the (ids, lengths) of that backward, which must
  * still be alive.  Other values: MMDA_EINVAL. */
 int mmda_misa_set_embed_update(mmda_misa* m, int mode);
+/* Dense mode (mmda_misa_set_embed_update 0) with the table's update deferred (config.embed_update = deferred): the weights dense Adam
+ * gives, while no launch of a step reads or writes the whole table -- see mmda_embed_rows_dense_adam.  Binds the caller's device memory
+ * (row_step: vocab int32; step_scalars: mmda_embed_deferred_scalar_floats(window) floats; the runtime owns none), marks every row
+ * current (one memset on `stream`) and starts counting updates at zero.  From then on every mmda_misa_forward first catches up the rows
+ * of its batch, a step's bucket ends at mmda_misa_dense_floats() as in modes 1 and 2, and the optimizer step updates the batch's rows
+ * where their sums become final.  The model counts the updates itself, so the `step` numbers of mmda_misa_train_step /
+ * mmda_misa_adam_step are as free as in plain dense mode.  Both pointers NULL: deferral off (flush first).
+ * MMDA_EINVAL: one pointer NULL, window < 1, or embed_update != 0.  mmda_misa_set_embed_update(1 or 2) unbinds.
+ * mmda_misa_embed_deferred_step: after mmda_misa_backward or a train step with do_adam = 0, the rows update of that backward (whose ids
+ *   and lengths must still be alive) with the optimizer's own scalars; mmda_misa_adam_step calls it with Adam's defaults.  MMDA_EINVAL
+ *   when nothing is bound or no backward is pending.
+ * mmda_misa_embed_flush: every stale row of the table takes the updates it missed (required before embed.weight or its moments are read
+ * from outside, saved, or handed to another mode); nothing deferred, or no update since the last flush: no launch. */
+int mmda_misa_set_embed_deferred(mmda_misa* m, int32_t* row_step, float* step_scalars, int window, void* stream);
+int mmda_misa_embed_deferred_step(mmda_misa* m, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
+                                  void* stream);
+int mmda_misa_embed_flush(mmda_misa* m, void* stream);
 /* Data parallel: the gradient bucket is laid out in the order the backward pass completes it (fusion block, LayerNorms,
  * layer-2 recurrent layers, layer-1 recurrent layers, embedding).  After mmda_misa_backward / mmda_misa_train_step has been
  * ISSUED, the first mmda_misa_early_grad_floats() floats of the bucket are final as soon as an event recorded inside that call

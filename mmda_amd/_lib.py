@@ -184,6 +184,11 @@ SIGNATURES = {
     "mmda_clamp_adam_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_embed_rows_sparse_adam": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_mark_rows": (_I, [_P, _I, _P, _I, _P]),
+    "mmda_embed_deferred_scalar_floats": (_I64, [_I]),
+    "mmda_embed_deferred_reset": (_I, [_P, _I, _P]),
+    "mmda_embed_rows_dense_adam": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _I, _P]),
+    "mmda_embed_rows_catch_up": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I, _I, _F, _F, _F, _I, _P]),
+    "mmda_embed_rows_flush": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P]),
     "mmda_clamp": (_I, [_P, _I64, _F, _P]),
     "mmda_clamp_rmsprop": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     "mmda_misa_create": (_I, [C.POINTER(MisaConfig), C.POINTER(C.c_void_p)]),
@@ -206,6 +211,9 @@ SIGNATURES = {
     "mmda_misa_set_inference": (_I, [_P, _I]),
     "mmda_misa_set_fusion_fp8": (_I, [_P, _I]),
     "mmda_misa_set_embed_update": (_I, [_P, _I]),
+    "mmda_misa_set_embed_deferred": (_I, [_P, _P, _P, _I, _P]),
+    "mmda_misa_embed_deferred_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mmda_misa_embed_flush": (_I, [_P, _P]),
     "mmda_misa_cluster_status": (_I, [_P, C.POINTER(_I)]),
     "mmda_misa_forward": (_I, [_P, _P, _P, _P, _P, _I, _U64, _P]),
     "mmda_misa_losses": (_I, [_P, _P, _I, _P]),

@@ -66,7 +66,10 @@ DEFAULTS = dict(
     fusion_fp8=False, dp_global_stats=False,
     # how embed.weight trains: "dense" (Adam over the whole table: what the reference does), "sparse" (torch.optim.SparseAdam on the
     # rows a batch touches) or "frozen" (fixed pretrained vectors: what the reference's `embed.requires_grad = False` meant to do)
-    embed_update="dense",
+    # ... or "deferred": dense Adam's weights bit for bit, with the update of a row the batch does not touch applied when the row is next
+    # needed (or by MISA.flush_embedding()) instead of by a pass over the table every step; embed_deferred_window: steps between the
+    # full flushes that bound how far a row can fall behind
+    embed_update="dense", embed_deferred_window=256,
 )
 
 

@@ -150,7 +150,7 @@ __device__ __forceinline__ float act_bwd_p(int act, float x, const mmda_act_para
 // (optim.hip: mmda_sparse_adam_args, internal.h); table_rows bounds the ids that are updated.
 struct SparseAdamArgs { float* P; float* M; float* V; int table_rows; float b1, b2, eps, clip, gscale, step_size; };
 // one element: g = clamp(gscale * sum, +-clip), then the update.  eps is added to sqrt(v) itself (SparseAdam), not to
-// sqrt(v / (1 - b2^t)) as in the dense adam1() of optim.hip.  Every rounding spelled out: both list paths give the same bits from
+// sqrt(v / (1 - b2^t)) as in the dense adam1() below.  Every rounding spelled out: both list paths give the same bits from
 // the same sum.
 __device__ __forceinline__ void sparse_adam1(float& p, float g, float& m, float& v, const SparseAdamArgs& a) {
   g = __fmul_rn(g, a.gscale);
@@ -176,6 +176,50 @@ struct RowSparseAdam {
     a.P[o] = p; a.M[o] = m; a.V[o] = v;
   }
 };
+// ---- dense Adam, one element (optim.hip: clamp_adam_kernel, clamp_adam_rows_kernel; the deferred table update below)
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
+                                      float gscale, float step_size, float inv_bc2_sqrt) {
+  // every rounding spelled out: the dense kernel and the per-row kernel below must give the same bits (the fused step runs part of the
+  // bucket through each), whatever the compiler would contract in either loop
+  g = __fmul_rn(g, gscale);
+  g = fminf(fmaxf(g, -clip), clip);
+  m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));
+  v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));
+  const float denom = __fmaf_rn(sqrtf(v), inv_bc2_sqrt, eps);
+  p = __fmaf_rn(-step_size, __fdiv_rn(m, denom), p);
+}
+
+// ---- deferred dense update of the embedding table (embed_update = deferred): dense Adam's result, without a pass over the table.  A row
+// whose gradient is zero takes a step that needs nothing but the row and the step's two scalars, so it can be applied later.  Updates are
+// counted as they are applied, 1, 2, 3 ... since the state was reset (`seq`; the Adam step NUMBER t that makes the bias corrections is
+// the caller's and may skip): row_step[id] is the count of the last update row id has taken, and ring[2 (s % window)],
+// ring[2 (s % window) + 1] keep update s's step_size = lr / (1 - b1^t) and 1 / sqrt(1 - b2^t) -- the floats the dense launch of that
+// update is given -- for the last `window` updates.  A stale row is replayed with adam1(g = 0) update by update (optim.hip), a row of
+// the batch takes update `seq` here, where its sum becomes final, with the sum the dense scatter would have added into a cleared
+// gradient row.
+struct DenseRowArgs {
+  float* P; float* M; float* V; int* row_step; float* ring; int window; int table_rows;
+  float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt; int seq;
+};
+// the launch that applies update `seq` also records its scalars (its first thread; the launches that replay it come later on the stream)
+__device__ __forceinline__ void dense_row_record(const DenseRowArgs& a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.ring[2 * (a.seq % a.window)] = a.step_size;
+    a.ring[2 * (a.seq % a.window) + 1] = a.inv_bc2_sqrt;
+  }
+}
+// requires row id current at seq - 1 (every forward catches the batch's rows up); 0 + sum: what `+=` into the cleared row leaves
+struct RowDenseAdam {
+  DenseRowArgs a;
+  __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
+    const int64_t o = id * D + c;                          // one writer per table row
+    float p = a.P[o], m = a.M[o], v = a.V[o];
+    adam1(p, __fadd_rn(0.f, sum), m, v, a.b1, a.b2, a.eps, a.clip, a.gscale, a.step_size, a.inv_bc2_sqrt);
+    a.P[o] = p; a.M[o] = m; a.V[o] = v;
+    if (c == 0) a.row_step[id] = a.seq;
+  }
+};
+
 // ---- flag joins (misa.hip: side_flag_signal): a kernel of one stream waits, on the device, for a word that a one-thread launch behind
 // the last kernel of ANOTHER stream's chain sets to `value` -- instead of a stream-level event wait, which costs the waiting stream
 // 9 - 12 us of packet processing however early the other chain finished (tools/micro/fork_cost.hip).  Called by every thread of the

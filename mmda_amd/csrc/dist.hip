@@ -66,6 +66,11 @@ __global__ __launch_bounds__(256) void seg_level1_adam_kernel(SparseAdamArgs ad,
                                                               int n, int D, const float* __restrict__ rows, float* part, unsigned pad_key) {
   seg_level1_body(RowSparseAdam{ad}, sid, pos, n, D, rows, part, pad_key);
 }
+__global__ __launch_bounds__(256) void seg_level1_dense_kernel(DenseRowArgs ad, const unsigned* __restrict__ sid, const int* __restrict__ pos,
+                                                               int n, int D, const float* __restrict__ rows, float* part, unsigned pad_key) {
+  dense_row_record(ad);
+  seg_level1_body(RowDenseAdam{ad}, sid, pos, n, D, rows, part, pad_key);
+}
 
 // level 2: one wave per segment head; the sum of the segment's run partials, in list order, is the row's finished sum
 template <class Fin>
@@ -92,6 +97,10 @@ __global__ __launch_bounds__(256) void seg_level2_kernel(const unsigned* __restr
 __global__ __launch_bounds__(256) void seg_level2_adam_kernel(SparseAdamArgs ad, const unsigned* __restrict__ sid, int n, int D,
                                                               const float* __restrict__ part, unsigned pad_key) {
   seg_level2_body(RowSparseAdam{ad}, sid, n, D, part, pad_key);
+}
+__global__ __launch_bounds__(256) void seg_level2_dense_kernel(DenseRowArgs ad, const unsigned* __restrict__ sid, int n, int D,
+                                                               const float* __restrict__ part, unsigned pad_key) {
+  seg_level2_body(RowDenseAdam{ad}, sid, n, D, part, pad_key);
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -237,6 +246,38 @@ int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, 
                           (void*)(w + L.cub), L.cub_bytes, (hipStream_t)stream);
   if (rc) return rc;
   return seg_reduce_adam(ad, kout, vout, n, D, rows, (float*)(w + L.part), (hipStream_t)stream);
+}
+
+// ---- embed_update = deferred: the same two levels once more, with dense Adam's step where a segment's sum becomes final
+static int seg_reduce_dense(const DenseRowArgs& ad, const unsigned* kout, const int* vout, int n, int D, const float* rows, float* part,
+                            hipStream_t s) {
+  const unsigned pad_key = (unsigned)ad.table_rows;
+  hipLaunchKernelGGL(seg_level1_dense_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, ad, kout, vout, n, D, rows, part, pad_key);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam/level1");
+  hipLaunchKernelGGL(seg_level2_dense_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, ad, kout, n, D, part, pad_key);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam/level2");
+  return MMDA_OK;
+}
+int mmda_embed_dense_adam_presorted(const DenseRowArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream) {
+  if (!sorted || !rows || n <= 0 || D <= 0 || ad.table_rows <= 0) return MMDA_EINVAL;
+  float* part = mmda_scratch_get((hipStream_t)stream, sizeof(float) * (size_t)n * D);
+  if (!part) return MMDA_ELAUNCH;
+  return seg_reduce_dense(ad, sorted, reinterpret_cast<const int*>(sorted + n), n, D, rows, part, (hipStream_t)stream);
+}
+int mmda_embed_dense_adam_sorted(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                 void* stream) {
+  if (!ids || !rows || n <= 0 || D <= 0 || ad.table_rows <= 0 || (lengths && B <= 0)) return MMDA_EINVAL;
+  const SegLayout L = seg_layout(n, D);
+  float* work = mmda_scratch_get((hipStream_t)stream, L.total + 256);
+  if (!work) return MMDA_ELAUNCH;
+  unsigned char* w = (unsigned char*)(((uintptr_t)work + 255) & ~(uintptr_t)255);
+  unsigned* kout = (unsigned*)(w + L.keys_out); int* vout = (int*)(w + L.vals_out);
+  int bits = 1;
+  while (bits < 32 && ((unsigned)ad.table_rows >> bits) != 0u) ++bits;
+  const int rc = seg_sort(ids, n, lengths, B, (unsigned)ad.table_rows, bits, (unsigned*)(w + L.keys_in), (int*)(w + L.vals_in), kout, vout,
+                          (void*)(w + L.cub), L.cub_bytes, (hipStream_t)stream);
+  if (rc) return rc;
+  return seg_reduce_dense(ad, kout, vout, n, D, rows, (float*)(w + L.part), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- RCCL all-reduce

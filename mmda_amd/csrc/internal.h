@@ -28,6 +28,9 @@ bool mmda_embed_scatter_sorts(int rows);
 // embed_update = sparse over a short id list.  rows (n, D): the gradient rows of the list's positions; lengths / B as in the scatter
 int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
                                  void* stream);
+// embed_update = deferred over a short id list (n >= 1)
+int mmda_embed_dense_adam_short(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                void* stream);
 
 // ---- dist.hip: the sort-based scatter, whole and in two halves (the sorted id list early, the sums behind the gradient rows), and
 // the sparse update over a long list (sorts it first) or one already sorted by mmda_embed_sort_ids
@@ -37,6 +40,10 @@ int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D
 int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
                                   void* stream);
 int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
+// the deferred update over a long list (sorts it first) or one already sorted (n >= 1)
+int mmda_embed_dense_adam_sorted(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                 void* stream);
+int mmda_embed_dense_adam_presorted(const DenseRowArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
 
 // ---- optim.hip
 int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      // two buffers cleared by one launch
@@ -46,6 +53,12 @@ int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n
 // SparseAdamArgs from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
 int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
                           float clip, float grad_scale, int step);
+// update `seq` (Adam step number `step`) of the deferred table update for the rows of an id list (optim.hip; the C ABI's mmda_embed_rows_dense_adam with the two
+// things a training step already has: caught-up rows, a sorted list)
+int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids,
+                                const unsigned* sorted, int n, int D, const float* rows, const int32_t* lengths, int B, int table_rows,
+                                float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int seq, int step,
+                                bool catch_up, void* stream);
 
 // ---- losses.hip
 // mmda_loss_cmd_pairs whose launch, as the last thing it does, sets *flag = value (flag joins, common.h: flag_wait).  Only the

@@ -57,6 +57,7 @@ struct StepPlan {
   bool rec_hoisted = false;         // stretch C's launch makes d_recon W_rec for stretch A
   bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
   int embed_update = 0;             // EU_*: how the step treats the embedding table (mmda_misa_set_embed_update)
+  bool embed_deferred = false;      // dense, with the table's update applied row by row when a row is next needed (mmda_misa_set_embed_deferred)
 };
 
 // embed_update: dense = the table's gradient is scattered into the bucket and dense Adam walks all V rows; sparse = the rows the batch
@@ -110,6 +111,10 @@ struct mmda_misa {
   // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
   // for backward itself)
   const int64_t* eu_ids = nullptr; const int32_t* eu_lengths = nullptr; int eu_pending = 0;
+  // dense mode with deferral (mmda_misa_set_embed_deferred): the caller's per-row step counts and ring of step scalars (common.h:
+  // DenseRowArgs).  Dense Adam's result; the bucket ends at the table as in the sparse mode, which also lends its eu_* fields.
+  // df_seq: updates applied since the binding (what a current row's row_step equals); df_flushed: df_seq at the last full flush.
+  int32_t* df_row_step = nullptr; float* df_ring = nullptr; int df_window = 0; int df_seq = 0, df_flushed = 0;
   int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
   // state of the last forward (dropout replay in backward)
   int training = 0; uint64_t seed = 0;
@@ -607,7 +612,7 @@ mmda_lstm_desc lstm_desc(mmda_misa* m, int i, int l, bool bwd, int gate_minor, b
 }
 
 // floats of the gradient bucket that a step writes, clears and walks with dense Adam: all of it, or the prefix in front of the table
-int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE ? m->flat : m->embed; }
+int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE && !m->df_row_step ? m->flat : m->embed; }
 
 constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
 
@@ -677,6 +682,7 @@ StepPlan plan_step(mmda_misa* m) {
   P.zg_here = zg_side >= 0 ? zg_side != 0 : P.fj_device;
   P.rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
   P.embed_update = m->embed_update;
+  P.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
   P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN;
   return P;
 }
@@ -949,9 +955,60 @@ int ffn_fp8(mmda_misa* m, float p_tf, uint64_t seed, void* stream) {
 extern "C" int mmda_misa_set_embed_update(mmda_misa* m, int mode) {
   if (!m) return MMDA_EINVAL;
   if (mode != EU_DENSE && mode != EU_SPARSE && mode != EU_FROZEN) return MMDA_EINVAL;
+  if (mode != EU_DENSE) { m->df_row_step = nullptr; m->df_ring = nullptr; m->df_window = 0; }     // (the caller flushed first)
   m->embed_update = mode;
   m->eu_pending = 0;
   return MMDA_OK;
+}
+
+extern "C" int mmda_misa_set_embed_deferred(mmda_misa* m, int32_t* row_step, float* step_scalars, int window, void* stream) {
+  if (!m) return MMDA_EINVAL;
+  if (!row_step && !step_scalars) {                        // off: plain dense from the next step on (the caller flushed first)
+    m->df_row_step = nullptr; m->df_ring = nullptr; m->df_window = 0; m->eu_pending = 0;
+    return MMDA_OK;
+  }
+  if (!row_step || !step_scalars || window < 1 || m->embed_update != EU_DENSE) return MMDA_EINVAL;
+  const int rc = mmda_embed_deferred_reset(row_step, m->cfg.vocab, stream);
+  if (rc) return rc;
+  m->df_row_step = row_step; m->df_ring = step_scalars; m->df_window = window; m->eu_pending = 0;
+  m->df_seq = m->df_flushed = 0;
+  return MMDA_OK;
+}
+
+extern "C" int mmda_misa_embed_flush(mmda_misa* m, void* stream) {
+  if (!m) return MMDA_EINVAL;
+  if (!m->df_row_step) return MMDA_OK;                     // nothing is deferred
+  if (!m->P || !m->M1 || !m->V1) return MMDA_EINVAL;
+  if (m->df_flushed == m->df_seq) return MMDA_OK;          // no update since the last flush: nothing is stale, nothing is launched
+  const int rc = mmda_embed_rows_flush(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window,
+                                       m->cfg.d_t, m->cfg.vocab, 0.9f, 0.999f, 1e-8f, m->df_seq, stream);
+  if (!rc) m->df_flushed = m->df_seq;
+  return rc;
+}
+
+namespace {
+// update df_seq + 1 of the deferred table for the rows of one backward's id list, counted here and nowhere else
+int deferred_apply(mmda_misa* m, const int64_t* ids, const unsigned* sorted, const int32_t* lengths, float lr, float beta1, float beta2,
+                   float eps, float clip, float grad_scale, int step, bool catch_up, void* stream) {
+  if (!m->df_row_step || !m->P || !m->M1 || !m->V1 || !m->ws || m->T <= 0 || !ids) return MMDA_EINVAL;
+  if (m->df_seq == INT32_MAX) return MMDA_EINVAL;
+  const int seq = m->df_seq + 1;
+  const int rc = mmda_embed_dense_adam_apply(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, ids,
+                                             sorted, m->B * m->T, m->cfg.d_t, WS(m->mod[0].d_x), lengths, m->B, m->cfg.vocab, lr, beta1,
+                                             beta2, eps, clip, grad_scale, seq, step, catch_up, stream);
+  if (rc) return rc;
+  if (seq % m->df_window == 0) m->df_flushed = seq - 1;    // (that update flushed first)
+  m->df_seq = seq;
+  return MMDA_OK;
+}
+}  // namespace
+
+extern "C" int mmda_misa_embed_deferred_step(mmda_misa* m, float lr, float beta1, float beta2, float eps, float clip, float grad_scale,
+                                             int step, void* stream) {
+  if (!m || !m->df_row_step || m->embed_update != EU_DENSE || !m->eu_pending || step < 1) return MMDA_EINVAL;
+  m->eu_pending = 0;
+  // (another forward may have run since that backward: its rows are brought to the last update again, which costs one launch)
+  return deferred_apply(m, m->eu_ids, nullptr, m->eu_lengths, lr, beta1, beta2, eps, clip, grad_scale, step, true, stream);
 }
 
 extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
@@ -1314,6 +1371,13 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
     x.rc = mmda_gru_pad_params(gj, n, stream);
     if (x.rc) return x.rc;
   }
+  // deferred table update: the rows this batch gathers take the steps they missed first, so the gather reads what dense Adam left
+  if (m->plan.embed_deferred) {
+    if (!m->M1 || !m->V1) return MMDA_EINVAL;
+    x.rc = mmda_embed_rows_catch_up(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, t_ids,
+                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, 0.9f, 0.999f, 1e-8f, m->df_seq, stream);
+    if (x.rc) return x.rc;
+  }
   const float* xin[3] = {WS(m->mod[0].x), v, a};
   x.fwd_operands(t_ids, xin);
   for (int l = 0; l < 2 && !x.rc; ++l) x.fwd_encoder_layer(l, xin, lengths);
@@ -1612,7 +1676,7 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
   m->esort_valid = 0;
   // (sparse mode without an optimizer step behind this backward: the rows update runs later, in mmda_misa_adam_step, and sorts there)
-  if (!rc && P.sort_early && !(P.embed_update == EU_SPARSE && !m->adam_early_on)) {
+  if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !m->adam_early_on)) {
     rc = mmda_embed_sort_ids(t_ids, B * m->T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
     if (!rc && ss != s) {
       hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
@@ -1823,6 +1887,25 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     } else {
       rc = mmda_embed_sparse_adam_short(ad, t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
     }
+  } else if (P.embed_deferred) {
+    // text: the rows the batch touches take this step where the scatter would have left their sums, with those sums (common.h:
+    // RowDenseAdam) -- behind an optimizer step only, as in the sparse mode; every other row takes it when it is next needed
+    m->eu_pending = 0;
+    if (!m->adam_early_on) {
+      m->eu_ids = t_ids; m->eu_lengths = lengths; m->eu_pending = 1;
+      return;
+    }
+    if (!m->M1 || !m->V1) { rc = MMDA_EINVAL; return; }
+    const unsigned* sorted = nullptr;
+    if (m->esort_valid) {
+      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
+        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
+        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
+      }
+      sorted = reinterpret_cast<const unsigned*>(WS(m->esort));
+      m->esort_valid = 0;
+    }
+    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, false, s);
   } else if (P.embed_update == EU_DENSE) {
     // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     if (m->esort_valid) {
@@ -1940,6 +2023,8 @@ extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float gra
                                      WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step,
                                      stream);
   }
+  if (!rc && m->embed_update == EU_DENSE && m->df_row_step && m->eu_pending)
+    rc = mmda_misa_embed_deferred_step(m, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
   return rc;
 }
 

@@ -409,6 +409,12 @@ __global__ __launch_bounds__(256) void embed_sparse_adam_kernel(SparseAdamArgs a
                                                                 const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
   embed_scatter_body(RowSparseAdam{ad}, (int64_t)ad.table_rows, ids, rows, dim, dX, lengths, B);
 }
+// the same owner, third epilogue: step `ad.step` of dense Adam on row `id` (embed_update = deferred; common.h: RowDenseAdam)
+__global__ __launch_bounds__(256) void embed_dense_adam_kernel(DenseRowArgs ad, const int64_t* __restrict__ ids, int rows, int dim,
+                                                               const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
+  dense_row_record(ad);
+  embed_scatter_body(RowDenseAdam{ad}, (int64_t)ad.table_rows, ids, rows, dim, dX, lengths, B);
+}
 
 __global__ void add_kernel(const float* a, const float* b, float* y, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = a[i] + b[i];
@@ -721,6 +727,15 @@ int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, i
   if (n == 0) return MMDA_OK;
   hipLaunchKernelGGL(embed_sparse_adam_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ad, ids, n, D, rows, lengths, B);
   MMDA_CHECK_LAUNCH("mmda_embed_rows_sparse_adam");
+  return MMDA_OK;
+}
+
+// embed_update = deferred, lists below ES_SORT_MIN positions
+int mmda_embed_dense_adam_short(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
+                                void* stream) {
+  if (!ids || !rows || n <= 0 || n > ES_MAX || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
+  hipLaunchKernelGGL(embed_dense_adam_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ad, ids, n, D, rows, lengths, B);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam");
   return MMDA_OK;
 }
 

@@ -7,18 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
-                                      float gscale, float step_size, float inv_bc2_sqrt) {
-  // every rounding spelled out: the dense kernel and the per-row kernel below must give the same bits (the fused step runs part of the
-  // bucket through each), whatever the compiler would contract in either loop
-  g = __fmul_rn(g, gscale);
-  g = fminf(fmaxf(g, -clip), clip);
-  m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));
-  v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));
-  const float denom = __fmaf_rn(sqrtf(v), inv_bc2_sqrt, eps);
-  p = __fmaf_rn(-step_size, __fdiv_rn(m, denom), p);
-}
-
 // wait_flag != nullptr (flag join, common.h): workgroup 0 does not finish before that word reaches wait_value -- so the completion of this
 // launch on its stream implies the completion of the other stream's chain (the update itself does not depend on it).
 __global__ __launch_bounds__(256) void clamp_adam_kernel(float* p, const float* __restrict__ g, float* m, float* v, int64_t n,
@@ -81,6 +69,67 @@ __global__ void mark_rows_kernel(unsigned char* mask, int rows, const int64_t* _
   const int64_t id = ids[i];
   if (id >= 0 && id < rows) mask[id] = 1;
 }
+
+// ---- embed_update = deferred (common.h: DenseRowArgs)
+// updates a + 1 .. t of one row whose gradient was zero in all of them: adam1() with g = 0 and each update's own scalars, in order -- the
+// calls the dense launches of those updates would have made.  One wave; a lane keeps up to RE elements of the row in registers, so the
+// t - a dependent sqrt / div chains of a row run RE at a time.
+constexpr int RE = 5;
+__device__ __forceinline__ void replay_row(float* p, float* m, float* v, int D, int lane, int a, int t, const float* __restrict__ ring,
+                                           int window, float b1, float b2, float eps) {
+  a = max(a, max(t - window, 0));      // memory safety only: the hosts that count the updates (misa.hip, ops.py) flush before a row gets here
+  for (int c0 = 0; c0 < D; c0 += 64 * RE) {
+    float pe[RE], me[RE], ve[RE];
+#pragma unroll
+    for (int k = 0; k < RE; ++k) {
+      const int c = c0 + 64 * k + lane;
+      pe[k] = c < D ? p[c] : 0.f; me[k] = c < D ? m[c] : 0.f; ve[k] = c < D ? v[c] : 0.f;
+    }
+    for (int s = a + 1; s <= t; ++s) {
+      const float step_size = ring[2 * (s % window)], inv_bc2_sqrt = ring[2 * (s % window) + 1];
+#pragma unroll
+      for (int k = 0; k < RE; ++k)
+        if (c0 + 64 * k < D) adam1(pe[k], 0.f, me[k], ve[k], b1, b2, eps, INFINITY, 1.f, step_size, inv_bc2_sqrt);   // wave-uniform
+    }
+#pragma unroll
+    for (int k = 0; k < RE; ++k) {
+      const int c = c0 + 64 * k + lane;
+      if (c < D) { p[c] = pe[k]; m[c] = me[k]; v[c] = ve[k]; }
+    }
+  }
+}
+// the rows of an id list, up to update `t`: one wave per position; the wave whose atomicMax raises row_step[id] owns the
+// row for this launch (an integer claim: one writer per row, no float atomics), every other position of that id sees it current
+__global__ __launch_bounds__(256) void embed_catch_up_kernel(float* P, float* M, float* V, int* row_step, const float* __restrict__ ring,
+                                                             int window, const int64_t* __restrict__ ids, int n, int D,
+                                                             const int* __restrict__ lengths, int B, int table_rows, float b1, float b2,
+                                                             float eps, int t) {
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= n) return;
+  const int64_t id = ids[p];
+  if (id < 0 || id >= table_rows) return;                               // wave-uniform, as everything below
+  if (lengths != nullptr && (p / B) >= lengths[p % B]) return;
+  int a = 0;
+  if (lane == 0) a = atomicMax(row_step + id, t);
+  a = __shfl(a, 0);
+  if (a >= t) return;
+  const int64_t o = id * D;
+  replay_row(P + o, M + o, V + o, D, lane, a, t, ring, window, b1, b2, eps);
+}
+// every stale row of the table, up to update `t`: one wave per row; a table with nothing stale is read (row_step) and not written
+__global__ __launch_bounds__(256) void embed_flush_kernel(float* P, float* M, float* V, int* row_step, const float* __restrict__ ring,
+                                                          int window, int D, int table_rows, float b1, float b2, float eps, int t) {
+  const int lane = threadIdx.x & 63;
+  for (int row = (int)blockIdx.x * 4 + (threadIdx.x >> 6); row < table_rows; row += (int)gridDim.x * 4) {
+    const int a = row_step[row];
+    if (a >= t) continue;                                               // wave-uniform
+    const int64_t o = (int64_t)row * D;
+    replay_row(P + o, M + o, V + o, D, lane, a, t, ring, window, b1, b2, eps);
+    if (lane == 0) row_step[row] = t;
+  }
+}
+// a step that touches no row still leaves its scalars behind
+__global__ void embed_step_record_kernel(DenseRowArgs ad) { dense_row_record(ad); }
 
 // clip_grad_value_ + torch.optim.RMSprop (alpha, eps; no momentum, not centered, no weight decay: the reference constructs its
 // optimizer as config.optimizer(params, lr=...), solver.py:97-99, so every other argument is torch's default)
@@ -201,6 +250,84 @@ extern "C" int mmda_embed_rows_sparse_adam(float* P, float* M, float* V, const i
   // the list length picks the form exactly as the dense scatter does (mmda_embed_scatter_add_masked)
   if (mmda_embed_scatter_sorts(n)) return mmda_embed_sparse_adam_sorted(ad, ids, n, D, rows, lengths, B, stream);
   return mmda_embed_sparse_adam_short(ad, ids, n, D, rows, lengths, B, stream);
+}
+
+// ---- embed_update = deferred: host side
+extern "C" int64_t mmda_embed_deferred_scalar_floats(int window) { return window < 1 ? MMDA_EINVAL : 2 * (int64_t)window; }
+
+extern "C" int mmda_embed_deferred_reset(int32_t* row_step, int table_rows, void* stream) {
+  if (!row_step || table_rows <= 0) return MMDA_EINVAL;
+  if (hipMemsetAsync(row_step, 0, sizeof(int32_t) * (size_t)table_rows, (hipStream_t)stream) != hipSuccess) return MMDA_ELAUNCH;
+  return MMDA_OK;
+}
+
+static bool deferred_state_ok(const float* P, const float* M, const float* V, const int32_t* row_step, const float* step_scalars, int window,
+                              int D, int table_rows) {
+  return P && M && V && row_step && step_scalars && window >= 1 && D > 0 && D <= 1024 && table_rows > 0;
+}
+
+extern "C" int mmda_embed_rows_catch_up(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window,
+                                        const int64_t* ids, int n, int D, const int32_t* lengths, int B, int table_rows, float beta1,
+                                        float beta2, float eps, int upto, void* stream) {
+  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || !ids || n < 0 || (lengths && B <= 0) || upto < 0)
+    return MMDA_EINVAL;
+  if (n == 0 || upto == 0) return MMDA_OK;
+  hipLaunchKernelGGL(embed_catch_up_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, (hipStream_t)stream, P, M, V, row_step, step_scalars, window,
+                     ids, n, D, lengths, B, table_rows, beta1, beta2, eps, upto);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_catch_up");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_embed_rows_flush(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window, int D,
+                                     int table_rows, float beta1, float beta2, float eps, int upto, void* stream) {
+  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || upto < 0) return MMDA_EINVAL;
+  if (upto == 0) return MMDA_OK;
+  int blocks = ceil_div(table_rows, 4);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(embed_flush_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P, M, V, row_step, step_scalars, window, D,
+                     table_rows, beta1, beta2, eps, upto);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_flush");
+  return MMDA_OK;
+}
+
+// internal (misa.hip): update number `seq` (the count of updates since the reset, last + 1), made with Adam step number `step`, for
+// the rows of an id list.  Counts that are multiples of the window flush the table first: the slot this update's scalars take is then
+// needed by no row.  catch_up: bring the list's rows to seq - 1 first (a forward of the same
+// batch has done so already inside a training step).  sorted != nullptr: the list as mmda_embed_sort_ids left it.
+int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids,
+                                const unsigned* sorted, int n, int D, const float* rows, const int32_t* lengths, int B, int table_rows,
+                                float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int seq, int step,
+                                bool catch_up, void* stream) {
+  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || !ids || !rows || n < 0 || (lengths && B <= 0) ||
+      step < 1 || seq < 1)
+    return MMDA_EINVAL;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const DenseRowArgs ad{P, M, V, row_step, step_scalars, window, table_rows, beta1, beta2, eps, clip, grad_scale,
+                        (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), seq};         // the dense launch's two scalars
+  int rc = MMDA_OK;
+  if (seq % window == 0)
+    rc = mmda_embed_rows_flush(P, M, V, row_step, step_scalars, window, D, table_rows, beta1, beta2, eps, seq - 1, stream);
+  else if (catch_up)
+    rc = mmda_embed_rows_catch_up(P, M, V, row_step, step_scalars, window, ids, n, D, lengths, B, table_rows, beta1, beta2, eps, seq - 1,
+                                  stream);
+  if (rc) return rc;
+  if (n == 0) {
+    hipLaunchKernelGGL(embed_step_record_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ad);
+    MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam/record");
+    return MMDA_OK;
+  }
+  if (sorted) return mmda_embed_dense_adam_presorted(ad, sorted, n, D, rows, stream);
+  if (mmda_embed_scatter_sorts(n)) return mmda_embed_dense_adam_sorted(ad, ids, n, D, rows, lengths, B, stream);
+  return mmda_embed_dense_adam_short(ad, ids, n, D, rows, lengths, B, stream);
+}
+
+extern "C" int mmda_embed_rows_dense_adam(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window,
+                                          const int64_t* ids, int n, int D, const float* rows, const int32_t* lengths, int B,
+                                          int table_rows, float lr, float beta1, float beta2, float eps, float clip, float grad_scale,
+                                          int seq, int step, void* stream) {
+  return mmda_embed_dense_adam_apply(P, M, V, row_step, step_scalars, window, ids, nullptr, n, D, rows, lengths, B, table_rows, lr, beta1,
+                                     beta2, eps, clip, grad_scale, seq, step, true, stream);
 }
 
 extern "C" int mmda_clamp(float* g, int64_t n, float clip, void* stream) {

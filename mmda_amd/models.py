@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import Dict, List, Tuple
 
 import torch
@@ -66,7 +67,8 @@ def _reference_sort_key(name: str):
     return (_TOP_ORDER.index(top), sub)
 
 
-EMBED_UPDATE = {"dense": 0, "sparse": 1, "frozen": 2}       # mmda_misa_set_embed_update
+# mmda_misa_set_embed_update ('deferred' is dense plus mmda_misa_set_embed_deferred: the same weights, no pass over the table per step)
+EMBED_UPDATE = {"dense": 0, "sparse": 1, "frozen": 2, "deferred": 0}
 
 
 class MISA(nn.Module):
@@ -95,8 +97,14 @@ class MISA(nn.Module):
             raise ValueError("config.precision must be 'bf16' or 'fp32'")
 
         self.embed_update = getattr(config, "embed_update", "dense")
-        if self.embed_update not in EMBED_UPDATE:
-            raise ValueError("config.embed_update must be 'dense', 'sparse' or 'frozen'")
+        if not isinstance(self.embed_update, str) or self.embed_update not in EMBED_UPDATE:
+            raise ValueError("config.embed_update must be 'dense', 'sparse', 'frozen' or 'deferred'")
+        # deferred: updates between full flushes (MMDA_EMBED_WINDOW overrides the configuration); read by that mode only
+        self.embed_window = 0
+        if self.embed_update == "deferred":
+            self.embed_window = int(os.environ.get("MMDA_EMBED_WINDOW", 0) or getattr(config, "embed_deferred_window", 256))
+            if self.embed_window < 1:
+                raise ValueError("config.embed_deferred_window must be at least 1")
 
         lib = _lib.load()
         cc = _lib.MisaConfig(
@@ -152,10 +160,15 @@ class MISA(nn.Module):
             # what the reference's `self.model.embed.requires_grad = False` (solver.py:86) meant: the optimizer's
             # filter(lambda p: p.requires_grad, ...) then leaves the table out
             self.embed.weight.requires_grad_(False)
-        # sparse mode: a backward whose rows update is still to be applied (the next optimizer step consumes it), and the clip value
+        # deferred mode: per-row step counts and the ring of step scalars (device, made with the flat buckets), and whether a step has
+        # been taken since the last flush
+        self._df_row_step = self._df_ring = None
+        self._df_dirty = False
+        # sparse / deferred mode: a backward whose rows update is still to be applied (the next optimizer step consumes it), and the clip value
         # optim.clip_grad_value_ recorded for it (the clamp applies to the coalesced rows, which exist only inside that update)
         self._rows_pending = False
         self._rows_clip = None
+        self._rows_keep = None
 
         # device state (created lazily on the first forward / .to())
         self._P = self._G = self._M = self._V = None
@@ -215,6 +228,7 @@ class MISA(nn.Module):
                 p.uniform_(-k, k)
 
     def _apply(self, fn, *args, **kwargs):
+        self.flush_embedding()   # (deferred: the copies made below must hold current rows)
         out = super()._apply(fn, *args, **kwargs)
         self._P = None           # parameter storages were replaced: re-flatten lazily
         return out
@@ -250,6 +264,61 @@ class MISA(nn.Module):
         _lib.check(self._lib.mmda_misa_bind(self._h, P.data_ptr(), self._G.data_ptr(), self._M.data_ptr(), self._V.data_ptr()),
                    "mmda_misa_bind")
         self._ws_shape = None
+        if self.embed_update == "deferred":
+            self._bind_deferred()
+
+    def _bind_deferred(self):
+        """(Re)bind the deferred state with every row current (the table holds flushed rows: new, loaded, or flushed by the caller);
+        the native side counts the updates from here."""
+        V = self._layout["embed.weight"][1][0]
+        dev = self._P.device
+        if self._df_row_step is None or self._df_row_step.device != dev:
+            self._df_row_step = torch.zeros(V, dtype=torch.int32, device=dev)
+            self._df_ring = torch.zeros(int(self._lib.mmda_embed_deferred_scalar_floats(self.embed_window)), dtype=torch.float32, device=dev)
+        _lib.check(self._lib.mmda_misa_set_embed_deferred(self._h, self._df_row_step.data_ptr(), self._df_ring.data_ptr(), self.embed_window,
+                                                          _lib.stream_ptr()), "set_embed_deferred")
+        self._df_dirty = False
+
+    def flush_embedding(self):
+        """embed_update='deferred': every row of embed.weight (and of its Adam moments) takes the optimizer steps it has not taken yet.
+        Required before embed.weight is read directly (p.data, flat_buckets()); state_dict(), checkpointing, .to() and load_state_dict()
+        call it themselves.  With no step since the last flush, and in every other mode, nothing is launched."""
+        if self.embed_update != "deferred" or not self._df_dirty or self._P is None or not self._views_valid():
+            return
+        _lib.check(self._lib.mmda_misa_embed_flush(self._h, _lib.stream_ptr()), "embed_flush")
+        self._df_dirty = False
+
+    def state_dict(self, *args, **kwargs):
+        self.flush_embedding()
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        # deferred: the moments of stale rows catch up before the table under them changes; the loaded rows are current at this step
+        self.flush_embedding()
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        if self.embed_update == "deferred" and self._P is not None and self._views_valid():
+            self._bind_deferred()
+        return out
+
+    def set_embed_update(self, mode: str):
+        """Switch how embed.weight trains (config.embed_update) between steps; a deferred table is flushed first."""
+        if not isinstance(mode, str) or mode not in EMBED_UPDATE:
+            raise ValueError("embed_update must be 'dense', 'sparse', 'frozen' or 'deferred'")
+        self.flush_embedding()
+        bound = self._P is not None and self._views_valid()
+        if self.embed_update == "deferred":
+            _lib.check(self._lib.mmda_misa_set_embed_deferred(self._h, None, None, 0, _lib.stream_ptr()), "set_embed_deferred")
+        _lib.check(self._lib.mmda_misa_set_embed_update(self._h, EMBED_UPDATE[mode]), "set_embed_update")
+        self.embed_update = mode
+        if mode == "deferred" and self.embed_window < 1:
+            self.embed_window = int(os.environ.get("MMDA_EMBED_WINDOW", 0) or getattr(self.config, "embed_deferred_window", 256))
+        self._rows_pending = False
+        self._rows_clip = None
+        self.embed.weight.requires_grad_(mode != "frozen")
+        if mode != "dense":
+            self.embed.weight.grad = None
+        if mode == "deferred" and bound:
+            self._bind_deferred()
 
     def _assign_grad_views(self):
         for name, p in self._plist:
@@ -473,8 +542,10 @@ class MISA(nn.Module):
                        "mmda_misa_train_step")
             self._fwd_id += 1
         self._last = dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo)
-        self._rows_pending = self.embed_update == "sparse" and not fused_adam
+        self._rows_pending = self.embed_update in ("sparse", "deferred") and not fused_adam
         self._rows_clip = None
+        self._rows_keep = (t, len_dev) if self._rows_pending else None     # (the native side holds these pointers until the rows update)
+        self._df_dirty = self._df_dirty or (self.embed_update == "deferred" and fused_adam)
         if custom:
             scale = 1.0
             if grad_sync is not None:
@@ -504,8 +575,8 @@ class MISA(nn.Module):
                 if hook:
                     owner.early_step = None
             done = int(owner.early_stepped) if hook else 0
-            if self.embed_update == "sparse":
-                raise _lib.MMDAError("embed_update='sparse' with a gradient exchange is not built yet")
+            if self.embed_update in ("sparse", "deferred"):
+                raise _lib.MMDAError(f"embed_update='{self.embed_update}' with a gradient exchange is not built yet")
             if done > 0:
                 n = self.grad_floats - done
                 o = done * 4
@@ -638,7 +709,7 @@ class MISA(nn.Module):
     @property
     def grad_floats(self) -> int:
         """Floats of the flat buckets that carry a dense gradient and take the dense optimizer launch: everything, or (embed_update
-        'sparse' / 'frozen') the prefix in front of embed.weight."""
+        'sparse' / 'frozen' / 'deferred') the prefix in front of embed.weight."""
         return self._flat_floats if self.embed_update == "dense" else self._dense_floats
 
     def apply_sparse_rows(self, lr: float, step: int, clip: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8) -> bool:
@@ -654,6 +725,22 @@ class MISA(nn.Module):
                                    lengths=self._last["len_dev"], clip=clip, grad_scale=grad_scale, betas=betas, eps=eps)
         self._rows_pending = False
         self._rows_clip = None
+        return True
+
+    def apply_deferred_rows(self, lr: float, step: int, clip: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8) -> bool:
+        """embed_update='deferred': dense Adam's step `step` for the rows the last backward touched, with the sums the dense scatter
+        would have left in embed.weight.grad (one fused native pass over d_x_t), once per backward; every other row takes the step when it
+        is next needed.  Returns False when no backward is pending."""
+        if self.embed_update != "deferred" or not self._rows_pending:
+            return False
+        # (the model-level entry: the native model counts the updates of this path and of the fused step in one place; it runs
+        # mmda_embed_rows_dense_adam on the ids, lengths and d_x_t of that backward, which self._rows_keep keeps alive)
+        _lib.check(self._lib.mmda_misa_embed_deferred_step(self._h, lr, betas[0], betas[1], eps, clip, grad_scale, int(step),
+                                                           _lib.stream_ptr()), "embed_deferred_step")
+        self._rows_pending = False
+        self._rows_clip = None
+        self._rows_keep = None
+        self._df_dirty = True
         return True
 
     def cluster_aborted(self) -> bool:
@@ -750,8 +837,9 @@ class _MISAFn(torch.autograd.Function):
         t, v, a, len_dev = ctx.io
         _lib.check(lib.mmda_misa_backward(model._h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(), s),
                    "mmda_misa_backward")
-        model._rows_pending = model.embed_update == "sparse"
+        model._rows_pending = model.embed_update in ("sparse", "deferred")
         model._rows_clip = None
+        model._rows_keep = (t, len_dev) if model._rows_pending else None   # (the native side holds these pointers until the rows update)
         model._assign_grad_views()
         return (torch.zeros_like(model._anchor),) + (None,) * 7
 

@@ -518,6 +518,84 @@ def embed_rows_sparse_adam(p, m, v, ids, rows, lr, step, lengths=None, clip=floa
                                           betas[0], betas[1], eps, clip, grad_scale, step, stream_ptr()), "embed_rows_sparse_adam")
 
 
+class DeferredState:
+    """Device state of the deferred dense update of one (table_rows, D) table -- row_step (int32 per row) and the ring of step scalars
+    -- and, on the host, the count of updates applied (`seq`) and the count at the last full flush.  The counting is done here, so a
+    caller cannot hand the kernels an update number that is not the last one + 1."""
+
+    def __init__(self, table_rows, window, device="cuda"):
+        lib = load()
+        if window < 1:
+            raise ValueError("window must be at least 1")
+        self.window = int(window)
+        self.row_step = torch.empty(table_rows, dtype=torch.int32, device=device)
+        self.ring = torch.zeros(int(lib.mmda_embed_deferred_scalar_floats(self.window)), dtype=torch.float32, device=device)
+        self.reset()
+
+    def reset(self):
+        """Every row current, no update counted (a new or a loaded table)."""
+        check(load().mmda_embed_deferred_reset(ptr(self.row_step), self.row_step.numel(), stream_ptr()), "embed_deferred_reset")
+        self.seq = 0
+        self.flushed = 0
+
+
+def embed_deferred_state(table_rows, window, device="cuda"):
+    return DeferredState(table_rows, window, device)
+
+
+def embed_rows_dense_adam(p, m, v, state, ids, rows, lr, step, lengths=None, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999),
+                          eps=1e-8):
+    """The next update of dense Adam (clamp_adam's arithmetic, bias corrections of step number `step`) on the rows of the (V, D) table p
+    (moments m, v; in place) that the id list touches, with g = the position-order sum of rows[pos]; every other row takes the update
+    when it is next caught up or flushed (`state`: a DeferredState, which counts the updates).  Arguments as embed_rows_sparse_adam."""
+    lib = load()
+    V, D = p.shape
+    n = ids.numel()
+    assert state.row_step.numel() == V
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous() and rows.shape == (n, D)
+    assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    B = 0
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and n % lengths.numel() == 0
+        B = lengths.numel()
+    seq = state.seq + 1
+    check(lib.mmda_embed_rows_dense_adam(ptr(_f(p)), ptr(_f(m)), ptr(_f(v)), ptr(state.row_step), ptr(state.ring), state.window, ptr(ids), n,
+                                         D, ptr(_f(rows)), ptr(lengths), B, V, lr, betas[0], betas[1], eps, clip, grad_scale, seq, step,
+                                         stream_ptr()), "embed_rows_dense_adam")
+    if seq % state.window == 0:
+        state.flushed = seq - 1                              # (that update flushed first)
+    state.seq = seq
+
+
+def embed_rows_catch_up(p, m, v, state, ids, lengths=None, betas=(0.9, 0.999), eps=1e-8):
+    """The rows of p (and m, v) at the non-padding positions of the id list take the updates they missed: run it before reading those
+    rows."""
+    lib = load()
+    V, D = p.shape
+    assert state.row_step.numel() == V
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+    B = 0
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and ids.numel() % lengths.numel() == 0
+        B = lengths.numel()
+    check(lib.mmda_embed_rows_catch_up(ptr(_f(p)), ptr(_f(m)), ptr(_f(v)), ptr(state.row_step), ptr(state.ring), state.window, ptr(ids),
+                                       ids.numel(), D, ptr(lengths), B, V, betas[0], betas[1], eps, state.seq, stream_ptr()),
+          "embed_rows_catch_up")
+
+
+def embed_rows_flush(p, m, v, state, betas=(0.9, 0.999), eps=1e-8):
+    """Every stale row of p (and m, v) takes the updates it missed: afterwards the three hold what dense Adam over the table gives.
+    With no update since the last flush nothing is launched."""
+    lib = load()
+    V, D = p.shape
+    assert state.row_step.numel() == V
+    if state.flushed == state.seq:
+        return
+    check(lib.mmda_embed_rows_flush(ptr(_f(p)), ptr(_f(m)), ptr(_f(v)), ptr(state.row_step), ptr(state.ring), state.window, D, V, betas[0],
+                                    betas[1], eps, state.seq, stream_ptr()), "embed_rows_flush")
+    state.flushed = state.seq
+
+
 def heads_fwd(logits, ncls, threshold=0.35, drop_p=0.0, seed=0, site=0):
     lib = load()
     B = logits.shape[0]

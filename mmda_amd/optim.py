@@ -54,6 +54,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         m = self._flat()
         if m is None:
             return super().state_dict()
+        if hasattr(m, "flush_embedding"):
+            m.flush_embedding()                             # embed_update 'deferred': the moment buckets hold current rows
         groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
         # the moment buckets are raw images of the flat bucket: its (name, offset, shape) layout travels with them, so that a checkpoint
         # written under another bucket order (another configuration or build) is re-ordered by name on load instead of loading wrongly
@@ -64,6 +66,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         m = self._flat()
+        if m is None or getattr(m, "embed_update", "dense") != "deferred":
+            return self._load_state_dict(sd, m)
+        # embed_update 'deferred': the table takes the steps it is behind under the moments it has; the loaded moments, and the loaded
+        # step count, then find every row current
+        m.flush_embedding()
+        out = self._load_state_dict(sd, m)
+        m._bind_deferred()
+        return out
+
+    def _load_state_dict(self, sd, m):
         if not (isinstance(sd, dict) and sd.get("mmda_flat")):
             if m is not None:
                 # a torch-format state (the reference writes one, solver.py:220): the attached fused step never reads self.state, so
@@ -161,6 +173,10 @@ class Adam(_FlatOptimizer):
             if getattr(m, "embed_update", "dense") == "sparse":
                 rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
                 m.apply_sparse_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
+            elif getattr(m, "embed_update", "dense") == "deferred":
+                # dense Adam's step for the rows of the last backward (two clamps in a row are one clamp at the smaller value)
+                rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
+                m.apply_deferred_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
             return None
         for group in self.param_groups:
             for p in group["params"]:
@@ -215,6 +231,8 @@ class RMSprop(_FlatOptimizer):
         if m is not None:
             if getattr(m, "embed_update", "dense") == "sparse":
                 raise _lib.MMDAError("embed_update='sparse' is defined for Adam only (torch has no sparse RMSprop)")
+            if getattr(m, "embed_update", "dense") == "deferred":
+                raise _lib.MMDAError("embed_update='deferred' is built for Adam only")
             P, G, _, _ = m.flat_buckets()
             sq = self._square_avg(P)
             _lib.check(lib.mmda_clamp_rmsprop(P.data_ptr(), G.data_ptr(), sq.data_ptr(), getattr(m, "grad_floats", P.numel()), g0["lr"], g0["alpha"], g0["eps"],
@@ -244,7 +262,7 @@ def clip_grad_value_(model_or_params, clip_value):
         # coalesced (clip_grad_value_ clamps the coalesced gradient), so the value is recorded for the pending rows update
         _lib.check(lib.mmda_clamp(m._G.data_ptr(), getattr(m, "grad_floats", m._G.numel()), float(clip_value), _lib.stream_ptr()),
                    "mmda_clamp")
-        if getattr(m, "embed_update", "dense") == "sparse" and m._rows_pending:
+        if getattr(m, "embed_update", "dense") in ("sparse", "deferred") and m._rows_pending:
             m._rows_clip = float(clip_value) if m._rows_clip is None else min(float(m._rows_clip), float(clip_value))
         return
     for p in m:

@@ -66,6 +66,12 @@ class Solver(object):
                 raise _lib.MMDAError("embed_update='sparse' is defined for optimizer='Adam' only (torch has no sparse RMSprop to match)")
             if dp_on:
                 raise _lib.MMDAError("embed_update='sparse' under data parallelism is not built yet (use 'dense' or 'frozen')")
+        if eu == "deferred" and self.is_train:
+            from . import _lib
+            if cfg.optimizer is not _optim.Adam:
+                raise _lib.MMDAError("embed_update='deferred' is built for optimizer='Adam' only")
+            if dp_on:
+                raise _lib.MMDAError("embed_update='deferred' under data parallelism is not built yet (use 'dense' or 'frozen')")
         self.model.to(self.device)
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate)

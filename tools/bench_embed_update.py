@@ -1,8 +1,15 @@
-"""Step time of the three config.embed_update modes against each other (dense = the reference point, in the same call).
+"""Step time of the four config.embed_update modes against each other (dense = the reference point, in the same call).
 
     python tools/bench_embed_update.py [--out FILE.json]          B in {32, 256} x {full, ragged} lengths, T = 50, bf16, dropout on,
                                                                   V = 20 000; every shape warmed, the modes alternated --rounds times
     python tools/bench_embed_update.py --only MODE --batch 32     one mode, one shape, few steps: the program of a kernel-trace run
+    python tools/bench_embed_update.py --modes dense,deferred --batches 32,256 --ragged 0
+                                                                  a subset of the modes / shapes, still alternated in one call
+    python tools/bench_embed_update.py --deferred-costs 64,256,1024
+                                                                  what the window of the deferred mode costs (op level): after
+                                                                  window - 1 updates on one id list, the catch-up launch of ANOTHER
+                                                                  list (every row at the largest gap) and the full flush, timed with
+                                                                  events, --rounds times each
 
 Needs the MI355X: there is no fall-back (the model raises on a CPU tensor, and this script checks first).  Prints one JSON line."""
 import argparse
@@ -15,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-MODES = ("dense", "sparse", "frozen")
+MODES = ("dense", "sparse", "frozen", "deferred")
 
 
 def main():
@@ -29,6 +36,10 @@ def main():
     ap.add_argument("--only", choices=MODES, help="time this mode alone (with --batch / --ragged)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ragged", type=int, default=0)
+    ap.add_argument("--modes", help="comma-separated subset of the modes (default: all)")
+    ap.add_argument("--batches", help="comma-separated batch sizes (default: 32,256, each with full and ragged lengths)")
+    ap.add_argument("--window", type=int, default=0, help="deferred: steps between full flushes (default: the configuration's)")
+    ap.add_argument("--deferred-costs", help="comma-separated windows: time the catch-up launch at the largest gap and the flush")
     ap.add_argument("--out", help="also write the result to this file")
     args = ap.parse_args()
 
@@ -41,17 +52,64 @@ def main():
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    modes = (args.only,) if args.only else MODES
-    shapes = [(args.batch, bool(args.ragged))] if args.only else [(32, False), (32, True), (256, False), (256, True)]
+    modes = (args.only,) if args.only else tuple(args.modes.split(",")) if args.modes else MODES
+    if any(mo not in MODES for mo in modes):
+        raise SystemExit(f"--modes: choose from {MODES}")
+    if args.only:
+        shapes = [(args.batch, bool(args.ragged))]
+    elif args.batches:
+        shapes = [(int(b), bool(args.ragged)) for b in args.batches.split(",")]
+    else:
+        shapes = [(32, False), (32, True), (256, False), (256, True)]
     emb = torch.randn(args.vocab, 300, generator=torch.Generator().manual_seed(0))
 
-    def build(mode, B):
+    def build(mode, B, window=0):
         torch.manual_seed(0)
+        kw = {"embed_deferred_window": window or args.window} if (window or args.window) else {}
         cfg = make_config(vocab_size=args.vocab, precision=args.precision, device=str(dev), batch_size=B, seq_len=args.seq_len,
-                          pretrained_emb=emb.clone(), embed_update=mode)
+                          pretrained_emb=emb.clone(), embed_update=mode, **kw)
         s = Solver(cfg, cfg, cfg, None, None, None, is_train=True).build()
         s.model.train()
         return cfg, s.model
+
+    if args.deferred_costs:
+        # the two costs of a window, at the op level on a (vocab, 300) table: window - 1 updates on list A leave every other row
+        # window - 1 updates behind; the catch-up launch of list B (other ids: every row at that gap) and the full flush are then timed
+        # with events.  The gap is rebuilt and both are timed --rounds times after one untimed pass (first launches); the range is
+        # reported, never one sample.
+        from mmda_amd import ops
+        n, D, V = args.batch * args.seq_len, 300, args.vocab
+        g = torch.Generator().manual_seed(0)
+        ids_a = torch.randint(2, V, (n,), generator=g).to(dev)
+        ids_b = torch.randint(2, V, (n,), generator=g).to(dev)
+        rows = (torch.randn(n, D, generator=g) * 1e-2).to(dev)
+        out = []
+        for w in [int(x) for x in args.deferred_costs.split(",")]:
+            P = emb.clone().to(dev); M = torch.zeros_like(P); Vv = torch.zeros_like(P)
+            cu, fl, stale = [], [], 0
+            for rep in range(args.rounds + 1):
+                st = ops.embed_deferred_state(V, w)
+                for k in range(1, w):
+                    ops.embed_rows_dense_adam(P, M, Vv, st, ids_a, rows, 1e-4, k, clip=1.0)
+                stale = int((st.row_step[torch.unique(ids_b)] < w - 1).sum())
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                torch.cuda.synchronize()
+                ev[0].record(); ops.embed_rows_catch_up(P, M, Vv, st, ids_b); ev[1].record()
+                ev[2].record(); ops.embed_rows_flush(P, M, Vv, st); ev[3].record()
+                torch.cuda.synchronize()
+                if rep:
+                    cu.append(ev[0].elapsed_time(ev[1]) * 1e3); fl.append(ev[2].elapsed_time(ev[3]) * 1e3)
+            cu.sort(); fl.sort()
+            out.append({"window": w, "positions": n, "vocab": V, "gap_updates": w - 1, "catch_up_rows": stale, "samples": len(cu),
+                        "catch_up_us": {"min": cu[0], "median": cu[len(cu) // 2], "max": cu[-1]},
+                        "flush_us": {"min": fl[0], "median": fl[len(fl) // 2], "max": fl[-1]},
+                        "flush_us_per_update_median": fl[len(fl) // 2] / w})
+        line = json.dumps({"bench": "embed_deferred_costs", "device": torch.cuda.get_device_name(0), "results": out})
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     results = []
     for B, ragged in shapes:
