@@ -482,6 +482,24 @@ int mmda_embed_rows_flush(float* P, float* M, float* V, int32_t* row_step, const
  * the other entry of the reference's optimizer_dict (config.py:24).  grad_scale as in mmda_clamp_adam. */
 int mmda_clamp_rmsprop(float* p, const float* g, float* square_avg, int64_t n, float lr, float alpha, float eps, float clip,
                        float grad_scale, void* stream);
+/* Gradient accumulation (config.accum_steps): one optimizer step from the gradients of N micro-batches, with the arithmetic of N
+ * data-parallel ranks -- A = ((G_0 + G_1) + G_2) + ..., one fp32 add per element and micro-batch, then mmda_clamp_adam's update with
+ * grad_scale = 1/N.  The accumulator is the caller's, outside any workspace.
+ * mmda_grad_accumulate: acc[i] = g[i] (first != 0: a plain copy, so the accumulator never needs clearing) or acc[i] = acc[i] + g[i],
+ *   i < n.  Any n >= 0; both pointers 16-byte aligned, else MMDA_EINVAL.
+ * mmda_clamp_adam_sum: mmda_clamp_adam with the gradient acc[i] + g[i] -- the closing step reads the last micro-batch's gradients where
+ *   the backward pass left them instead of adding them into the accumulator first; P, M and V get the bits mmda_grad_accumulate followed
+ *   by mmda_clamp_adam over acc would leave, and neither acc nor g is written.  acc == NULL (one micro-batch): mmda_clamp_adam itself.
+ * mmda_embed_rows_append (embed_update = sparse): the n = T*B gradient rows (n, D) and ids of a micro-batch copied to position `offset`
+ *   of a list of `capacity` positions (ids_out int64[capacity], rows_out (capacity, D)); the id of a padding position (lengths != NULL
+ *   and t >= lengths[b], position p = t*B + b) is written as -1, which mmda_embed_rows_sparse_adam skips.  One launch.  MMDA_EINVAL when
+ *   offset + n > capacity.  mmda_embed_rows_sparse_adam with lengths = NULL on the concatenated list then updates the rows any micro-batch
+ *   touched, with sums in list order. */
+int mmda_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
+int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float clip, float grad_scale, int step, void* stream);
+int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids, const float* rows,
+                           int n, int D, const int32_t* lengths, int B, void* stream);
 
 /* ============================================================================================== whole-model API
  * The reference's per-batch loop body (solver.py:139-186) as five calls.  `mmda_misa` is the native runtime object
@@ -602,6 +620,24 @@ int mmda_misa_zero_act_grads(mmda_misa* m, void* stream);
 /* solver.py:185-186: clip_grad_value_(clip) + Adam over the whole bucket; grad_scale = 1/world after an all-reduce
  * (mmda_misa_set_embed_update 1 / 2: over the non-embedding prefix, plus the pending rows update in mode 1) */
 int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream);
+/* One optimizer step from N micro-batches (config.accum_steps; the arithmetic of mmda_grad_accumulate above).  Every micro-batch is
+ * mmda_misa_train_step with do_adam = 0; behind each but the last call mmda_misa_grad_accumulate, behind the last
+ * mmda_misa_adam_step_accumulated with grad_scale = 1/N.  The runtime owns none of the memory:
+ *   acc        the bucket's length in floats (mmda_misa_flat_floats() in dense mode, mmda_misa_dense_floats() in modes 1 and 2), 16-byte
+ *              aligned, never cleared by anyone (first != 0 copies)
+ *   list_ids / list_rows   mode 1 (sparse) only, else ignored: int64[list_capacity] and (list_capacity, d_t) floats.  The micro-batch's
+ *              T*B rows of d_x_t (workspace: the next micro-batch overwrites them) and its ids, padding as -1, are appended at position
+ *              list_used, and the pending rows update of that backward is dropped: a later mmda_misa_adam_step applies nothing stale.
+ *              The caller adds T*B to list_used per micro-batch and starts every optimizer step at 0; micro-batches may differ in T and B.
+ * mmda_misa_adam_step_accumulated: clip + Adam over the bucket with the gradient acc + current bucket (acc == NULL: one micro-batch, the
+ *   current bucket alone); in mode 1 it appends the last micro-batch's rows as above and runs mmda_embed_rows_sparse_adam once on the
+ *   list_used + T*B positions of the list.
+ * MMDA_EINVAL, with nothing launched: deferral bound (mmda_misa_set_embed_deferred: its contract is dense Adam's bits, which a rows
+ * update on a concatenated list does not give), mode 1 without a pending backward or with a list too short, step < 1. */
+int mmda_misa_grad_accumulate(mmda_misa* m, float* acc, int first, int64_t* list_ids, float* list_rows, int64_t list_used,
+                              int64_t list_capacity, void* stream);
+int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, int64_t* list_ids, float* list_rows, int64_t list_used,
+                                    int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream);
 /* zero_grad + forward + losses + backward (+ adam if do_adam) = one reference loop iteration */
 int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
                          const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,

@@ -191,6 +191,9 @@ SIGNATURES = {
     "mmda_embed_rows_flush": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P]),
     "mmda_clamp": (_I, [_P, _I64, _F, _P]),
     "mmda_clamp_rmsprop": (_I, [_P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
+    "mmda_grad_accumulate": (_I, [_P, _P, _I64, _I, _P]),
+    "mmda_clamp_adam_sum": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mmda_embed_rows_append": (_I, [_P, _P, _I64, _I64, _P, _P, _I, _I, _P, _I, _P]),
     "mmda_misa_create": (_I, [C.POINTER(MisaConfig), C.POINTER(C.c_void_p)]),
     "mmda_misa_destroy": (None, [_P]),
     "mmda_misa_num_params": (_I, [_P]),
@@ -222,6 +225,8 @@ SIGNATURES = {
     "mmda_misa_zero_grad": (_I, [_P, _P]),
     "mmda_misa_zero_act_grads": (_I, [_P, _P]),
     "mmda_misa_adam_step": (_I, [_P, _F, _F, _F, _I, _P]),
+    "mmda_misa_grad_accumulate": (_I, [_P, _P, _I, _P, _P, _I64, _I64, _P]),
+    "mmda_misa_adam_step_accumulated": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _I, _P]),
     "mmda_misa_timing_stride": (_I, [_P, _I]),
     "mmda_misa_timing_rotate": (_I, [_P, _I]),
     "mmda_misa_timing_begin": (_I, [_P, _I]),

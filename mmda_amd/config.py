@@ -70,6 +70,9 @@ DEFAULTS = dict(
     # needed (or by MISA.flush_embedding()) instead of by a pass over the table every step; embed_deferred_window: steps between the
     # full flushes that bound how far a row can fall behind
     embed_update="dense", embed_deferred_window=256,
+    # optimizer steps made from this many consecutive batches each (gradient accumulation with data-parallel semantics: the mean over
+    # micro-batches of their gradients, then clip + Adam -- what that many ranks would compute); 1 = the reference's loop
+    accum_steps=1,
 )
 
 

@@ -2028,6 +2028,50 @@ extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float gra
   return rc;
 }
 
+// ---- accumulated steps (accum_steps > 1): the micro-batch is mmda_misa_train_step(do_adam = 0); what happens to its gradients is here
+namespace {
+// sparse table: the rows of the backward that just ran (d_x_t is workspace: the next micro-batch overwrites it) go to the caller's list
+int accum_append_rows(mmda_misa* m, int64_t* list_ids, float* list_rows, int64_t used, int64_t capacity, void* stream) {
+  if (!m->eu_pending || !m->ws || m->T <= 0 || !list_ids || !list_rows) return MMDA_EINVAL;
+  m->eu_pending = 0;                                    // (a later mmda_misa_adam_step must not apply these rows again)
+  const int64_t* ids = m->eu_ids; const int32_t* lengths = m->eu_lengths;
+  m->eu_ids = nullptr; m->eu_lengths = nullptr;
+  return mmda_embed_rows_append(list_ids, list_rows, used, capacity, ids, WS(m->mod[0].d_x), m->B * m->T, m->cfg.d_t, lengths, m->B, stream);
+}
+bool accum_ready(const mmda_misa* m) { return m && m->P && m->G && !m->df_row_step; }
+// sparse table: a backward is pending and the list holds its T B rows behind the `used` it already has (dense / frozen: no list)
+bool accum_list_ok(const mmda_misa* m, const int64_t* list_ids, const float* list_rows, int64_t used, int64_t capacity) {
+  if (m->embed_update != EU_SPARSE) return true;
+  const int64_t R = (int64_t)m->B * m->T;
+  return m->eu_pending && m->ws && m->T > 0 && list_ids && list_rows && used >= 0 && used <= capacity && R <= capacity - used &&
+         used + R <= INT32_MAX;
+}
+}  // namespace
+
+extern "C" int mmda_misa_grad_accumulate(mmda_misa* m, float* acc, int first, int64_t* list_ids, float* list_rows, int64_t list_used,
+                                         int64_t list_capacity, void* stream) {
+  if (!accum_ready(m) || !acc || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
+  int rc = mmda_grad_accumulate(acc, m->G, grad_floats(m), first, stream);
+  if (!rc && m->embed_update == EU_SPARSE) rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
+  return rc;
+}
+
+extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, int64_t* list_ids, float* list_rows, int64_t list_used,
+                                               int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream) {
+  // (everything is checked in front of the dense launch: a refused call changes nothing)
+  if (!accum_ready(m) || !m->M1 || !m->V1 || step < 1 || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
+  int rc = mmda_clamp_adam_sum(m->P, acc, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  if (!rc && m->embed_update == EU_SPARSE) {
+    const int n = (int)(list_used + (int64_t)m->B * m->T);
+    rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
+    // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
+    if (!rc)
+      rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, list_ids, n, m->cfg.d_t, list_rows, nullptr, 0,
+                                       m->cfg.vocab, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  }
+  return rc;
+}
+
 extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
                                     const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
                                     void* stream) {

@@ -32,6 +32,77 @@ __global__ __launch_bounds__(256) void clamp_adam_kernel(float* p, const float* 
   if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
 }
 
+// ---- gradient accumulation (accum_steps > 1): one optimizer step from the gradients of several micro-batches
+// acc = g (first: a plain copy, so the accumulator never needs clearing) or acc = acc + g, one IEEE add per element.  Pure HBM stream:
+// float4 per lane, scalar tail, the shape of clamp_adam_kernel.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* acc, const float* __restrict__ g, int64_t n, int first) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  if (first) {                                             // launch-uniform
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) a4[i] = g4[i];
+    for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) acc[i] = g[i];
+    return;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 aa = a4[i];
+    const float4 gg = g4[i];
+    aa.x = __fadd_rn(aa.x, gg.x); aa.y = __fadd_rn(aa.y, gg.y); aa.z = __fadd_rn(aa.z, gg.z); aa.w = __fadd_rn(aa.w, gg.w);
+    a4[i] = aa;
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) acc[i] = __fadd_rn(acc[i], g[i]);
+}
+
+// clamp_adam_kernel on the sum acc + g: the closing step of an accumulated update reads the last micro-batch's gradients where the
+// backward pass left them, instead of adding them into the accumulator first and reading that back.  The same add, then the same
+// adam1(): the bits of "accumulate, then clamp_adam_kernel over the accumulator".  Neither acc nor g is written.
+__global__ __launch_bounds__(256) void clamp_adam_sum_kernel(float* p, const float* __restrict__ acc, const float* __restrict__ g, float* m,
+                                                             float* v, int64_t n, float b1, float b2, float eps, float clip, float gscale,
+                                                             float step_size, float inv_bc2_sqrt) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  const float4* a4 = reinterpret_cast<const float4*>(acc);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 pp = p4[i], mm = m4[i], vv = v4[i];
+    const float4 aa = a4[i], gg = g4[i];
+    adam1(pp.x, __fadd_rn(aa.x, gg.x), mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.y, __fadd_rn(aa.y, gg.y), mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.z, __fadd_rn(aa.z, gg.z), mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.w, __fadd_rn(aa.w, gg.w), mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    p4[i] = pp; m4[i] = mm; v4[i] = vv;
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride)
+    adam1(p[i], __fadd_rn(acc[i], g[i]), m[i], v[i], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+}
+
+// embed_update = sparse under accumulation: a micro-batch's n = T B gradient rows (width D) and ids, appended at position `offset` of a
+// list that outlives the workspace; the id of a padding position (t >= lengths[b], p = t B + b) becomes -1, which the rows update skips.
+// vec: D % 4 == 0 and 16-byte aligned bases, so every row starts on a 16-byte boundary in both buffers (launch-uniform).
+__global__ __launch_bounds__(256) void embed_rows_append_kernel(int64_t* ids_out, float* rows_out, int64_t offset,
+                                                                const int64_t* __restrict__ ids, const float* __restrict__ rows, int n, int D,
+                                                                const int* __restrict__ lengths, int B, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)n * D;
+  float* dst = rows_out + offset * D;
+  if (vec) {
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    const float4* s4 = reinterpret_cast<const float4*>(rows);
+    for (int64_t i = i0; i < (total >> 2); i += stride) d4[i] = s4[i];
+  } else {
+    for (int64_t i = i0; i < total; i += stride) dst[i] = rows[i];
+  }
+  for (int64_t p = i0; p < n; p += stride) {
+    const bool pad = lengths != nullptr && (int)(p / B) >= lengths[p % B];
+    ids_out[offset + p] = pad ? (int64_t)-1 : ids[p];
+  }
+}
+
 // The same update over the ROWS of a (rows, dim) table whose mask byte equals `want` (dim % 4 == 0 or not: scalar tail per row).
 // The embedding matrix is 6 of the model's 10.8 M parameters and a step touches at most T*B of its V rows: the rows a batch does not
 // touch have a zero gradient that is known before the backward pass ends, so their update runs early, beside the last recurrence
@@ -182,6 +253,54 @@ int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n
   hipLaunchKernelGGL(clamp_adam_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, beta1, beta2, eps, clip,
                      grad_scale, step_size, inv_bc2_sqrt, wait_flag, wait_value, wait_err);
   MMDA_CHECK_LAUNCH("mmda_clamp_adam");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
+  if (!acc || !g || n < 0) return MMDA_EINVAL;
+  if (((uintptr_t)acc | (uintptr_t)g) & 15) return MMDA_EINVAL;                                // float4 path
+  if (n == 0) return MMDA_OK;
+  int64_t blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, acc, g, n, first ? 1 : 0);
+  MMDA_CHECK_LAUNCH("mmda_grad_accumulate");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
+  if (!acc) return mmda_clamp_adam(p, g, m, v, n, lr, beta1, beta2, eps, clip, grad_scale, step, stream);   // one micro-batch: no sum
+  if (!p || !g || !m || !v || n < 0 || step < 1) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // float4 path
+  if (n == 0) return MMDA_OK;
+  double bc1 = 1.0 - pow((double)beta1, (double)step);
+  double bc2 = 1.0 - pow((double)beta2, (double)step);
+  float step_size = (float)((double)lr / bc1);
+  float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  int64_t blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(clamp_adam_sum_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, acc, g, m, v, n, beta1, beta2, eps,
+                     clip, grad_scale, step_size, inv_bc2_sqrt);
+  MMDA_CHECK_LAUNCH("mmda_clamp_adam_sum");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids,
+                                      const float* rows, int n, int D, const int32_t* lengths, int B, void* stream) {
+  if (!ids_out || !rows_out || !ids || !rows || n < 0 || D <= 0 || offset < 0 || capacity < 0 || (lengths && B <= 0)) return MMDA_EINVAL;
+  if (offset > capacity || (int64_t)n > capacity - offset) return MMDA_EINVAL;                 // the list must hold the rows
+  if (((uintptr_t)ids_out | (uintptr_t)ids) & 7 || ((uintptr_t)rows_out | (uintptr_t)rows) & 3) return MMDA_EINVAL;
+  if (n == 0) return MMDA_OK;
+  const int vec = (D & 3) == 0 && (((uintptr_t)rows_out | (uintptr_t)rows) & 15) == 0;
+  const int64_t work = vec ? ((int64_t)n * D) >> 2 : (int64_t)n * D;
+  int64_t blocks = (work + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(embed_rows_append_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ids_out, rows_out, offset, ids, rows, n,
+                     D, lengths, B, vec);
+  MMDA_CHECK_LAUNCH("mmda_embed_rows_append");
   return MMDA_OK;
 }
 

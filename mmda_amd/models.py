@@ -106,6 +106,11 @@ class MISA(nn.Module):
             if self.embed_window < 1:
                 raise ValueError("config.embed_deferred_window must be at least 1")
 
+        # optimizer steps from this many micro-batches each (Solver.train_epoch groups the loader's batches; train_step takes the position)
+        self.accum_steps = getattr(config, "accum_steps", 1)
+        if isinstance(self.accum_steps, bool) or not isinstance(self.accum_steps, int) or self.accum_steps < 1:
+            raise ValueError("config.accum_steps must be an int >= 1")
+
         lib = _lib.load()
         cc = _lib.MisaConfig(
             vocab=len(config.word2id), d_t=self.text_size, d_v=self.visual_size, d_a=self.acoustic_size,
@@ -169,6 +174,15 @@ class MISA(nn.Module):
         self._rows_pending = False
         self._rows_clip = None
         self._rows_keep = None
+
+        # accumulated steps (train_step(accum_count > 1)): the second gradient bucket and, in sparse mode, the (ids, rows) list of the
+        # step's micro-batches -- host-owned, outside the workspace (which is re-carved when a micro-batch changes T or B), made on
+        # first use, grown when a micro-batch needs more, kept across steps; the position the next call must have, and the step's count
+        self._acc = None
+        self._acc_list = None
+        self._acc_used = 0
+        self._acc_next = 0
+        self._acc_count = 1
 
         # device state (created lazily on the first forward / .to())
         self._P = self._G = self._M = self._V = None
@@ -516,14 +530,20 @@ class MISA(nn.Module):
 
     # ------------------------------------------------------------------ fused fast path (Solver.train_epoch)
     def train_step(self, sentences, video, acoustic, lengths, emo_label, lr: float, clip: float, do_adam: bool = True,
-                   training: bool = True, seed=None, grad_sync=None, optimizer=None):
+                   training: bool = True, seed=None, grad_sync=None, optimizer=None, accum_index: int = 0, accum_count: int = 1):
         """One reference loop iteration (solver.py:139-186) in native code: zero_grad, forward, six losses, backward,
         clip + Adam.  ``grad_sync(flat_grad_bucket, dense_floats, model)`` is called between backward and Adam for the
         data-parallel all-reduce (mmda_amd/dist.py) and must return the gradient scale (1/world).
         ``optimizer``: an mmda_amd.optim optimizer attached to this model.  Adam (or None) is stepped by the native fused
         clamp+Adam with ``lr``; any other (RMSprop, config.py:24) by its own fused kernel after the gradient exchange.
-        Losses stay on the device (read them with ``read_losses()``; one sync, not six)."""
+        Losses stay on the device (read them with ``read_losses()``; one sync, not six).
+        ``accum_index`` / ``accum_count``: this batch is micro-batch ``accum_index`` of an optimizer step made from ``accum_count``
+        consecutive calls (0, 1, ... count - 1, the same count in each): the gradients of the micro-batches are summed in that order and
+        the last call takes one clip + Adam step with their mean -- what ``accum_count`` data-parallel ranks would compute."""
         from . import optim as _optim
+        if accum_count != 1 or accum_index != 0 or self._acc_next:
+            return self._accum_micro_step(sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync,
+                                          optimizer, accum_index, accum_count)
         t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
         emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
         if seed is None:
@@ -585,6 +605,76 @@ class MISA(nn.Module):
                            "adam(rest)")
             else:
                 _lib.check(self._lib.mmda_misa_adam_step(self._h, lr, clip, float(scale), self._step, s), "adam_step")
+
+    def _accum_micro_step(self, sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync, optimizer,
+                          index, count) -> None:
+        """Micro-batch ``index`` of an optimizer step made from ``count``: the native step without its optimizer part, then either the
+        add into the second bucket or -- behind the last one -- clip + Adam on (accumulated + this micro-batch's gradients) / count."""
+        from . import optim as _optim
+        expected, self._acc_next = self._acc_next, 0           # (any refusal below leaves the sequence reset)
+        self._acc_used = 0 if expected == 0 else self._acc_used
+        for x in (index, count):
+            if isinstance(x, bool) or not isinstance(x, int):
+                raise _lib.MMDAError("accum_index / accum_count must be ints")
+        if count < 1 or not 0 <= index < count:
+            raise _lib.MMDAError(f"accum_index {index} is outside [0, accum_count = {count})")
+        if index != expected or (index > 0 and count != self._acc_count):
+            raise _lib.MMDAError(f"accumulated step: micro-batch {index} of {count} arrived where {expected} of "
+                                 f"{self._acc_count if expected else count} was due (indices run 0 .. count - 1 with one count); "
+                                 "the sequence starts over")
+        if grad_sync is not None:
+            raise _lib.MMDAError("accum_steps > 1 together with a gradient exchange (grad_sync / data parallel) is not built yet")
+        if optimizer is not None and not isinstance(optimizer, _optim.Adam):
+            raise _lib.MMDAError(f"accum_steps > 1 with optimizer {type(optimizer).__name__} is not built: Adam only")
+        if self.embed_update == "deferred":
+            raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built: the mode's contract is dense Adam's bits, "
+                                 "which one rows update over the micro-batches' concatenated list does not give")
+        if not do_adam:
+            raise _lib.MMDAError("accum_steps > 1 with do_adam=False: the accumulated step ends in its optimizer step")
+        t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
+        emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
+        if seed is None:
+            seed = self._next_seed()
+        s = _lib.stream_ptr()
+        lib, h = self._lib, self._h
+        _lib.check(lib.mmda_misa_train_step(h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(), emo.data_ptr(), int(training),
+                                            seed, 0, lr, clip, max(self._step, 1), s), "mmda_misa_train_step")
+        self._fwd_id += 1
+        self._last = dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo)
+        self._rows_pending = False                             # (sparse: the rows go to the list below, the native side forgets them)
+        self._rows_clip = None
+        self._rows_keep = None
+        closing = index == count - 1
+        n = self.grad_floats
+        if count > 1 and (self._acc is None or self._acc.numel() < n or self._acc.device != t.device):
+            if index > 0:
+                raise _lib.MMDAError("accumulated step: the gradient bucket changed size or device between micro-batches")
+            self._acc = torch.empty(n, dtype=torch.float32, device=t.device)
+        ids_p = rows_p = None
+        cap = 0
+        if self.embed_update == "sparse":
+            D = self._layout["embed.weight"][1][1]
+            need = self._acc_used + t.numel()
+            old = self._acc_list
+            if old is None or old[0].numel() < need or old[0].device != t.device:
+                room = max(need, count * t.numel())            # (equal micro-batches: the step's whole list at once)
+                ids = torch.empty(room, dtype=torch.int64, device=t.device)
+                rows = torch.empty((room, D), dtype=torch.float32, device=t.device)
+                if old is not None and self._acc_used > 0:
+                    ids[:self._acc_used].copy_(old[0][:self._acc_used])
+                    rows[:self._acc_used].copy_(old[1][:self._acc_used])
+                self._acc_list = (ids, rows)
+            ids_p, rows_p, cap = self._acc_list[0].data_ptr(), self._acc_list[1].data_ptr(), self._acc_list[0].numel()
+        if not closing:
+            _lib.check(lib.mmda_misa_grad_accumulate(h, self._acc.data_ptr(), int(index == 0), ids_p, rows_p, self._acc_used, cap, s),
+                       "mmda_misa_grad_accumulate")
+            self._acc_used += t.numel()
+            self._acc_next, self._acc_count = index + 1, count
+            return
+        self._step += 1
+        _lib.check(lib.mmda_misa_adam_step_accumulated(h, self._acc.data_ptr() if count > 1 else None, ids_p, rows_p, self._acc_used, cap,
+                                                       lr, clip, 1.0 / count, self._step, s), "mmda_misa_adam_step_accumulated")
+        self._acc_used = 0
 
     def _global_stats_step(self, t, v, a, len_dev, emo, training: bool, seed: int, dp) -> None:
         """forward + losses + backward of one step with the batch-statistic losses on the batch of ALL ranks (DataParallelSync

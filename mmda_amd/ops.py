@@ -485,6 +485,38 @@ def clamp_adam(p, g, m, v, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0
                               stream_ptr()), "clamp_adam")
 
 
+def grad_accumulate(acc, g, first=False):
+    """acc = g (first) or acc += g, elementwise fp32, in place: one micro-batch's gradients into the accumulator of an accumulated step."""
+    lib = load()
+    assert acc.numel() == g.numel() and acc.dtype == g.dtype == torch.float32 and acc.is_contiguous() and g.is_contiguous()
+    check(lib.mmda_grad_accumulate(ptr(acc), ptr(g), acc.numel(), int(bool(first)), stream_ptr()), "grad_accumulate")
+
+
+def clamp_adam_sum(p, acc, g, m, v, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+    """clamp_adam with the gradient acc + g (neither is written); acc = None: clamp_adam itself."""
+    lib = load()
+    assert acc is None or (acc.numel() == p.numel() and acc.is_contiguous())
+    check(lib.mmda_clamp_adam_sum(ptr(p), ptr(acc), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, clip, grad_scale, step,
+                                  stream_ptr()), "clamp_adam_sum")
+
+
+def embed_rows_append(ids_out, rows_out, offset, ids, rows, lengths=None):
+    """A micro-batch's (T, B) ids and (T * B, D) gradient rows appended at position `offset` of the list (ids_out (cap,) int64, rows_out
+    (cap, D) fp32); positions past a sample's length (lengths: (B,) int32 on the device) get id -1.  Returns the list's new length."""
+    lib = load()
+    n = ids.numel()
+    cap, D = rows_out.shape
+    assert ids.dtype == ids_out.dtype == torch.int64 and ids.is_contiguous() and ids_out.is_contiguous() and ids_out.numel() == cap
+    assert rows.shape == (n, D) and rows.is_contiguous() and rows_out.is_contiguous()
+    B = 0
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and n % lengths.numel() == 0
+        B = lengths.numel()
+    check(lib.mmda_embed_rows_append(ptr(ids_out), ptr(rows_out), int(offset), cap, ptr(ids), ptr(rows), n, D, ptr(lengths), B,
+                                     stream_ptr()), "embed_rows_append")
+    return int(offset) + n
+
+
 def mark_rows(ids, rows):
     """uint8 mask of `rows` bytes: 1 where the row id occurs in `ids` (int64, device)."""
     lib = load()

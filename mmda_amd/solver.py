@@ -72,6 +72,14 @@ class Solver(object):
                 raise _lib.MMDAError("embed_update='deferred' is built for optimizer='Adam' only")
             if dp_on:
                 raise _lib.MMDAError("embed_update='deferred' under data parallelism is not built yet (use 'dense' or 'frozen')")
+        if int(getattr(cfg, "accum_steps", 1)) > 1 and self.is_train:
+            from . import _lib
+            if cfg.optimizer is not _optim.Adam:
+                raise _lib.MMDAError("accum_steps > 1 is built for optimizer='Adam' only (not with RMSprop)")
+            if dp_on:
+                raise _lib.MMDAError("accum_steps > 1 under data parallelism (world x accumulation) is not built yet")
+            if eu == "deferred":
+                raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built (use 'dense': the same weights)")
         self.model.to(self.device)
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate)
@@ -85,19 +93,39 @@ class Solver(object):
         return self
 
     # ------------------------------------------------------------------ train (solver.py:103-307)
+    def _micro_batches(self):
+        """The loader's batches as (batch, accum_index, accum_count): optimizer steps of cfg.accum_steps consecutive batches each, the
+        last one of an epoch of whatever is left (steps never straddle epochs).  A step's count must be known when its first
+        micro-batch is issued, so the loader is read one step ahead; accum_steps = 1 reads it batch by batch as ever."""
+        N = int(getattr(self.train_config, "accum_steps", 1))
+        if N <= 1:
+            for batch in self.train_data_loader:
+                yield batch, 0, 1
+            return
+        group = []
+        for batch in self.train_data_loader:
+            group.append(batch)
+            if len(group) == N:
+                for k, b in enumerate(group):
+                    yield b, k, N
+                group = []
+        for k, b in enumerate(group):
+            yield b, k, len(group)
+
     def train_epoch(self):
         """Fused path.  Returns the epoch's mean losses (dict)."""
         cfg = self.train_config
         self.model.train()
         sums = None
         n = 0
-        for batch in self.train_data_loader:
+        for batch, k, count in self._micro_batches():
             t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
             t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
             l = to_cpu(l)
+            accum = dict(accum_index=k, accum_count=count) if count > 1 else {}
             self.model.train_step(t, v, a, l, emo_label, lr=cfg.learning_rate, clip=cfg.clip,
                                   grad_sync=self.dp.sync if self.dp is not None else None,
-                                  optimizer=getattr(self, "optimizer", None))
+                                  optimizer=getattr(self, "optimizer", None), **accum)
             L = self.model._ws_view("losses", (8,))
             sums = L.clone() if sums is None else sums + L       # stays on the device; one sync per epoch
             n += 1
@@ -109,6 +137,10 @@ class Solver(object):
     def train_epoch_unfused(self):
         """The reference's loop body, statement for statement (solver.py:138-193), through autograd."""
         cfg = self.train_config
+        if int(getattr(cfg, "accum_steps", 1)) > 1:
+            from . import _lib
+            raise _lib.MMDAError("train_epoch_unfused() is the reference's loop, one optimizer step per batch: accum_steps > 1 runs "
+                                 "through train_epoch()")
         self.model.train()
         train_loss = []
         for batch in self.train_data_loader:
