@@ -657,6 +657,21 @@ int mmda_misa_timing_begin(mmda_misa* m, int max_steps);
 int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* steps);
 int mmda_misa_timing_end(mmda_misa* m);
 
+/* ---------------------------------------------------------------------------------------------- device-resident dataset
+ * One batch of the reference's collate_fn (data_loader.py:59-122, use_bert = False) gathered from a dataset that lives on the device, in
+ * ONE launch (mmda_amd/data.py: DeviceLoader).  The dataset: the n samples' time positions back to back, P in all -- words int32 [P],
+ * visual fp32 [P, dv], acoustic fp32 [P, da] -- with offsets int64 [n + 1] (sample i owns positions offsets[i] .. offsets[i + 1] - 1),
+ * emo fp32 [n, 6] (NULL: the dataset has no emotion table) and sentiment fp32 [n].  The batch: order int32 [B], sample indices in batch
+ * order (the host sorts by length, descending), T time steps.  Outputs, time-major: out_ids int64 [T, B], out_v fp32 [T, B, dv],
+ * out_a fp32 [T, B, da], out_emo fp32 [B, 6] (may be NULL), out_y fp32 [B].  With len_b = offsets[order[b] + 1] - offsets[order[b]],
+ * position (t, b) is a copy of row offsets[order[b]] + t when t < len_b, and pad_id / zeros otherwise: every output element is written,
+ * so the outputs need no clearing.  A T below a sample's length cuts the sample off at T.  Copies only: the outputs hold the dataset's
+ * bits.  MMDA_EINVAL, with nothing launched: a NULL pointer other than emo / out_emo, out_emo without emo, B, T, dv or da <= 0.
+ * Nothing checks the indices: an `order` entry outside [0, n) reads out of bounds (the caller validates them on the host). */
+int mmda_collate_gather(const int32_t* words, const float* visual, const float* acoustic, const int64_t* offsets, const float* emo,
+                        const float* sentiment, const int32_t* order, int B, int T, int dv, int da, int pad_id, int64_t* out_ids,
+                        float* out_v, float* out_a, float* out_emo, float* out_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,7 @@ SIGNATURES = {
     "mmda_misa_timing_collect": (_I, [_P, C.POINTER(C.c_float * 4), C.POINTER(_I)]),
     "mmda_misa_timing_end": (_I, [_P]),
     "mmda_misa_train_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _U64, _I, _F, _F, _I, _P]),
+    "mmda_collate_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

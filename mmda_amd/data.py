@@ -5,6 +5,9 @@ here generate tensors of the same shapes, dtypes and ordering rules: batch sorte
 ``pad_sequence`` layout, PAD id 1 past each sample's length (create_dataset.py:25-27: <unk>=0, <pad>=1), emotion labels
 binarised to {0,1} float32, CPU int64 ``lengths``.  The three BERT tensors are returned as zeros of shape (B, T+2):
 they are ignored when use_bert=False.
+
+For real samples (the reference's dataset items): ``collate_fn`` builds the same tuple on the host, ``DevicePrefetcher`` copies it one
+batch ahead, and ``DeviceDataset`` / ``DeviceLoader`` keep the whole dataset on the device and gather each batch there in one launch.
 """
 from __future__ import annotations
 
@@ -154,3 +157,175 @@ class DevicePrefetcher:
                 if torch.is_tensor(x) and x.is_cuda:
                     x.record_stream(cs)
         return cur
+
+
+# ---------------------------------------------------------------------------------------------- device-resident dataset
+class DeviceDataset:
+    """A whole dataset of reference-style samples on the device, uploaded once: the samples' time positions back to back (``words`` int32
+    (P,), ``visual`` (P, dv), ``acoustic`` (P, da)), ``offsets`` int64 (n + 1,), and per sample ``sentiment`` (n,) and ``emo`` (n, 6) or
+    None.  A batch is then a pure function of B sample indices: ``DeviceLoader`` gathers it with one launch.  ``lengths`` (int64) and
+    ``segments`` (object) stay on the host: the batch plan is made from the one, the batch's id list from the other."""
+
+    def __init__(self, words, visual, acoustic, offsets, emo, sentiment, lengths, segments):
+        self.words, self.visual, self.acoustic, self.offsets, self.emo, self.sentiment = words, visual, acoustic, offsets, emo, sentiment
+        self.lengths, self.segments = lengths, segments
+        self.device = words.device
+        self.dv, self.da = int(visual.shape[1]), int(acoustic.shape[1])
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    @classmethod
+    def from_samples(cls, samples, device):
+        """``samples[i]`` is what the reference's ``MSADataset[i]`` returns: ``((word_ids, visual (L, dv), acoustic (L, da), words),
+        label (1, 7) | (1, 1), segment)``.  The label columns are made with collate_fn's own numpy operations, so a gathered batch
+        equals a collated one bit for bit; (1, 1) labels mean no emotion table."""
+        import numpy as np
+        from ._lib import MMDAError
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise MMDAError(f"DeviceDataset lives on the GPU (device={device}): there is no CPU path, use DataLoader + collate_fn")
+        n = len(samples)
+        if n == 0:
+            raise ValueError("DeviceDataset: the dataset is empty")
+        words = [np.asarray(s[0][0], dtype=np.int64).reshape(-1) for s in samples]
+        visual = [np.asarray(s[0][1], dtype=np.float32) for s in samples]
+        acoustic = [np.asarray(s[0][2], dtype=np.float32) for s in samples]
+        lengths = np.array([w.shape[0] for w in words], dtype=np.int64)
+        if int(lengths.min()) <= 0:
+            raise ValueError(f"DeviceDataset: sample {int(lengths.argmin())} has length zero")
+        for i, (v, a) in enumerate(zip(visual, acoustic)):
+            if v.ndim != 2 or a.ndim != 2 or v.shape[0] != lengths[i] or a.shape[0] != lengths[i]:
+                raise ValueError(f"DeviceDataset: sample {i}: visual / acoustic must be (L, d) with the L of its word ids")
+            if v.shape[1] != visual[0].shape[1] or a.shape[1] != acoustic[0].shape[1]:
+                raise ValueError(f"DeviceDataset: sample {i} has feature widths ({v.shape[1]}, {a.shape[1]}), sample 0 has "
+                                 f"({visual[0].shape[1]}, {acoustic[0].shape[1]})")
+        if visual[0].shape[1] == 0 or acoustic[0].shape[1] == 0:
+            raise ValueError("DeviceDataset: zero feature width")
+        flat_w = np.concatenate(words)
+        if flat_w.min() < -2 ** 31 or flat_w.max() >= 2 ** 31:
+            raise ValueError("DeviceDataset: word ids must fit int32")
+        lab = np.stack([np.nan_to_num(np.asarray(s[1], dtype=np.float64))[0] for s in samples])            # as collate_fn does
+        emo = (lab[:, 1:] > 0.0).astype(np.float32) if lab.shape[1] == 7 else None
+        sentiment = lab[:, 0].astype(np.float32)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        segments = np.empty(n, dtype=object)
+        for i, s in enumerate(samples):
+            segments[i] = s[2]
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
+        return cls(up(flat_w.astype(np.int32)), up(np.concatenate(visual)), up(np.concatenate(acoustic)), up(offsets),
+                   None if emo is None else up(emo), up(sentiment), lengths, segments)
+
+
+def _kept(m, batch_size, drop_last=False, shard=None):
+    """How much of an index sequence of ``m`` entries one rank batches, as ``(prefix, per_rank, batches)``: the sequence is cut to its
+    first ``prefix`` entries (a multiple of ``world * batch_size`` under ``drop_last``, else of ``world``; all of it without a shard),
+    the rank keeps ``per_rank`` of them -- less the short tail under ``drop_last`` -- in ``batches`` batches.  The one place that knows
+    the rule: ``batch_plan`` cuts by it and ``DeviceLoader.__len__`` counts by it; it validates ``batch_size`` and ``shard`` too."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    world = 1
+    if shard is not None:
+        rank, world = int(shard[0]), int(shard[1])
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"shard=(rank, world)={tuple(shard)} needs 0 <= rank < world")
+    unit = world * batch_size if (drop_last and shard is not None) else world
+    prefix = m // unit * unit
+    per_rank = prefix // world
+    if drop_last:
+        per_rank = per_rank // batch_size * batch_size
+    return prefix, per_rank, (per_rank + batch_size - 1) // batch_size
+
+
+def batch_plan(lengths, indices, batch_size, drop_last=False, shard=None):
+    """The batches ``DataLoader(batch_size=..., collate_fn=collate_fn)`` makes of the index sequence ``indices``, as two int64 arrays:
+    ``order``, the sample indices of all batches back to back, each batch sorted by length descending (stable, as collate_fn's
+    ``sorted(..., reverse=True)``), and ``bounds`` (batches + 1,): batch k is ``order[bounds[k]:bounds[k + 1]]``, its T is the length of its
+    first sample.  ``shard=(rank, world)``: the sequence is first cut to a multiple of ``world * batch_size`` (``drop_last``) or of
+    ``world``, then rank r keeps ``indices[r::world]`` -- every rank gets the same number of batches of the same sizes, so the collectives
+    of data-parallel training line up."""
+    import numpy as np
+    lengths = np.asarray(lengths, dtype=np.int64)
+    idx = np.asarray(indices)
+    if idx.size and idx.dtype.kind not in "iu":
+        raise TypeError("batch_plan: indices must be integers")
+    idx = idx.astype(np.int64).reshape(-1)
+    batch_size = int(batch_size)
+    prefix, per_rank, _ = _kept(idx.size, batch_size, drop_last, shard)
+    n = lengths.shape[0]
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise IndexError(f"batch_plan: sample index outside [0, {n})")
+    if shard is not None:
+        idx = idx[:prefix][int(shard[0])::int(shard[1])]
+    idx = idx[:per_rank]
+    starts = np.arange(0, idx.size, batch_size, dtype=np.int64)
+    bounds = np.append(starts, idx.size).astype(np.int64)
+    order = np.empty_like(idx)
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        chunk = idx[lo:hi]
+        order[lo:hi] = chunk[np.argsort(-lengths[chunk], kind="stable")]
+    return order, bounds
+
+
+class DeviceLoader:
+    """Drop-in for ``DataLoader(dataset, batch_size, collate_fn=collate_fn)`` over a ``DeviceDataset``: the same 10-tuples, bit for bit,
+    for the same index sequence, with the batch tensors made on the device.  An epoch draws its index sequence (``sampler``, else
+    ``torch.randperm(n, generator=generator)`` when ``shuffle``, else 0 .. n-1), plans its batches on the host (``batch_plan``) and uploads
+    the order once; a batch is then five ``torch.empty`` and one ``mmda_collate_gather`` launch on the current stream -- no copy in either
+    direction, no synchronisation.  The outputs belong to the stream they were made on (the caching allocator's stream ordering keeps them
+    valid while the host runs ahead): consume a batch on the stream that was current when it was yielded.  Every tensor of a yielded
+    tuple is the batch's own, as with ``collate_fn`` -- except the three BERT slots, which are one cached all-zero CPU tensor per shape
+    (``use_bert=False``: nothing reads them), shared by the three slots, by every batch of that shape and across epochs: do not write
+    into it."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, sampler=None, generator=None, drop_last=False, shard=None):
+        if sampler is not None and shuffle:
+            raise ValueError("sampler option is mutually exclusive with shuffle")
+        self.dataset, self.batch_size, self.shuffle, self.sampler, self.generator = dataset, int(batch_size), bool(shuffle), sampler, generator
+        self.drop_last, self.shard = bool(drop_last), shard
+        _kept(0, self.batch_size, self.drop_last, shard)            # refuses a bad batch_size / shard here, not at the first epoch
+        self._bert = {}                      # (B, T + 2) -> the zero tensor the three BERT slots share (use_bert=False)
+
+    def __len__(self):
+        m = len(self.sampler) if self.sampler is not None else len(self.dataset)
+        return _kept(m, self.batch_size, self.drop_last, self.shard)[2]
+
+    def _indices(self):
+        import numpy as np
+        if self.sampler is not None:
+            return np.fromiter(iter(self.sampler), dtype=np.int64)
+        if self.shuffle:
+            return torch.randperm(len(self.dataset), generator=self.generator).numpy()
+        return np.arange(len(self.dataset), dtype=np.int64)
+
+    def __iter__(self):
+        import numpy as np
+        from . import _lib
+        ds = self.dataset
+        order, bounds = batch_plan(ds.lengths, self._indices(), self.batch_size, self.drop_last, self.shard)
+        if order.size == 0:
+            return
+        lib = _lib.load()
+        # the epoch's one host-to-device copy, from page-locked memory so that it does not wait for the device either
+        order_dev = torch.from_numpy(order.astype(np.int32)).pin_memory().to(ds.device, non_blocking=True)
+        lens_np = ds.lengths[order]
+        lens_all = torch.from_numpy(lens_np)
+        segs_all = ds.segments[order]
+        src = tuple(_lib.ptr(x) for x in (ds.words, ds.visual, ds.acoustic, ds.offsets, ds.emo, ds.sentiment))
+        order_ptr, dev, dv, da = order_dev.data_ptr(), ds.device, ds.dv, ds.da
+        for lo, hi in zip(bounds[:-1].tolist(), bounds[1:].tolist()):
+            B, T = hi - lo, int(lens_np[lo])
+            ids = torch.empty(T, B, dtype=torch.int64, device=dev)
+            v = torch.empty(T, B, dv, device=dev)
+            a = torch.empty(T, B, da, device=dev)
+            emo = torch.empty(B, 6, device=dev) if ds.emo is not None else None
+            y = torch.empty(B, device=dev)
+            _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, dv, da, PAD, ids.data_ptr(), v.data_ptr(), a.data_ptr(),
+                                               _lib.ptr(emo), y.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                       "mmda_collate_gather")
+            bert = self._bert.get((B, T + 2))
+            if bert is None:
+                bert = self._bert[(B, T + 2)] = torch.zeros(B, T + 2, dtype=torch.int64)
+            yield ids, v, a, y, emo, lens_all[lo:hi].clone(), bert, bert, bert, segs_all[lo:hi].tolist()

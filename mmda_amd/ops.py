@@ -644,3 +644,29 @@ def dropout_mask_via_act(n, p, seed, site, device):
     z = torch.ones(n, device=device); h = torch.empty(n, device=device)
     check(lib.mmda_act_dropout_fwd(ptr(z), ptr(h), n, ACT["none"], p, seed, site, stream_ptr()), "act_dropout_fwd")
     return h
+
+
+def collate_gather(words, visual, acoustic, offsets, emo, sentiment, order, T, pad_id=1, out=None):
+    """One batch of ``data.collate_fn`` gathered from a device-resident dataset in one launch: words int32 (P,), visual (P, dv), acoustic
+    (P, da), offsets int64 (n + 1,), emo (n, 6) or None, sentiment (n,), all on the device; order int32 (B,) on the device, sample
+    indices in batch order, every one in [0, n) (nothing on the device checks them).  Returns (ids int64 (T, B), visual (T, B, dv),
+    acoustic (T, B, da), emo (B, 6) or None, sentiment (B,)), padding written by the launch itself.  ``out``: the same five tensors to
+    write into (None in the emo slot when emo is None) instead of fresh ``torch.empty`` ones."""
+    lib = load()
+    B, dv, da = order.numel(), visual.shape[1], acoustic.shape[1]
+    assert words.dtype == order.dtype == torch.int32 and offsets.dtype == torch.int64
+    assert all(x.is_cuda and x.is_contiguous() for x in (words, visual, acoustic, offsets, sentiment, order) + (() if emo is None else (emo,)))
+    assert words.numel() == visual.shape[0] == acoustic.shape[0] and offsets.numel() == sentiment.numel() + 1
+    assert emo is None or (emo.dtype == torch.float32 and tuple(emo.shape) == (sentiment.numel(), 6))
+    _f(visual); _f(acoustic); _f(sentiment)
+    dev = words.device
+    if out is None:
+        out = (torch.empty(T, B, dtype=torch.int64, device=dev), torch.empty(T, B, dv, device=dev), torch.empty(T, B, da, device=dev),
+               None if emo is None else torch.empty(B, 6, device=dev), torch.empty(B, device=dev))
+    ids, v, a, e, y = out
+    assert ids.dtype == torch.int64 and tuple(ids.shape) == (T, B) and tuple(v.shape) == (T, B, dv) and tuple(a.shape) == (T, B, da)
+    assert tuple(y.shape) == (B,) and (e is None or tuple(e.shape) == (B, 6))
+    assert all(x.is_cuda and x.is_contiguous() for x in (ids, v, a, y) + (() if e is None else (e,)))
+    check(lib.mmda_collate_gather(ptr(words), ptr(visual), ptr(acoustic), ptr(offsets), ptr(emo), ptr(sentiment), ptr(order), B, int(T), dv,
+                                  da, int(pad_id), ptr(ids), ptr(v), ptr(a), ptr(e), ptr(y), stream_ptr()), "collate_gather")
+    return ids, v, a, e, y
