@@ -500,6 +500,26 @@ int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, float* m, fl
                         float eps, float clip, float grad_scale, int step, void* stream);
 int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids, const float* rows,
                            int n, int D, const int32_t* lengths, int B, void* stream);
+/* Frozen parameters (requires_grad = False): the updates above over the TRAINABLE RUNS of a bucket only.  A run is a range of bucket
+ * floats [begin, begin + len) that trains; what lies between runs is neither loaded nor stored -- P, M, V (square_avg) keep their bits
+ * there, and the gradient there may hold anything, NaN included.  Inside the runs P, M and V get the bits of the dense entry
+ * (mmda_clamp_adam, mmda_clamp_adam_sum, mmda_clamp_rmsprop) with the same scalars.  Runs begin and end anywhere; a launch works in
+ * items, one per 16-byte aligned quad of the bucket that a run touches (16-byte accesses where the quad lies inside the run, single
+ * floats at a run's ends), and `first` is the count of the items of the runs in front.
+ * mmda_runs_build (host only, no device needed): n ranges, ascending and disjoint inside [0, bucket_floats), as a table of at most n
+ *   runs -- empty ranges dropped, touching ranges merged, `first` filled in; returns the table's items (>= 0), *n_out its runs, or
+ *   MMDA_EINVAL.  The caller copies the table to the device once per change of the set, not per step.
+ * The launches take a DEVICE table -- or a slice of one that starts at a run: `items` is then the slice's own count -- of runs that lie
+ * inside the buffers (pointers to bucket offset 0, 16-byte aligned for the Adam forms).  n_runs == 0 or items == 0: nothing is launched. */
+typedef struct mmda_run { int64_t begin, len, first; } mmda_run;
+int64_t mmda_runs_build(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, mmda_run* out, int* n_out);
+int mmda_clamp_adam_runs(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
+                         float beta1, float beta2, float eps, float clip, float grad_scale, int step, void* stream);
+int mmda_clamp_adam_sum_runs(float* p, const float* acc, const float* g, float* m, float* v, const mmda_run* runs, int n_runs,
+                             int64_t items, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
+                             void* stream);
+int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_avg, const mmda_run* runs, int n_runs, int64_t items, float lr,
+                            float alpha, float eps, float clip, float grad_scale, void* stream);
 
 /* ============================================================================================== whole-model API
  * The reference's per-batch loop body (solver.py:139-186) as five calls.  `mmda_misa` is the native runtime object
@@ -564,6 +584,25 @@ int mmda_misa_set_fusion_fp8(mmda_misa* m, int on);
  * train step with do_adam = 0: mmda_misa_adam_step applies the rows update from the (ids, lengths) of that backward, which must
  * still be alive.  Other values: MMDA_EINVAL. */
 int mmda_misa_set_embed_update(mmda_misa* m, int mode);
+/* Frozen parameters (requires_grad = False on the host side).  flags: one byte per parameter in mmda_misa_param_info order, non-zero =
+ * trains; n_params must be mmda_misa_num_params().  Host only (no device call): the caller sends the set when it differs from the
+ * last one it sent, between steps.  From then on
+ *   - every optimizer launch of mmda_misa_train_step, mmda_misa_adam_step and mmda_misa_adam_step_accumulated walks the trainable runs
+ *     of its range only (mmda_clamp_adam_runs and kin: the bits of the dense launch inside the runs, not one byte of P, M or V
+ *     touched outside them); a range in which nothing trains gets no launch.  The table of runs is copied to the device by the first
+ *     such launch after a change, behind a wait for the stream -- the only synchronisation, once per change of the set.
+ *   - the frozen ranges of the gradient bucket are unspecified (gradients the pass computes anyway may land there; nothing reads them).
+ *   - encoder cut: when every recurrent parameter and the three inter-layer LayerNorms ({t,v,a}layer_norm) are frozen and the table
+ *     is -- by its own flag in dense mode, or by mmda_misa_set_embed_update(2) -- mmda_misa_backward stops behind the fusion block: no
+ *     backward recurrence, no encoder weight-gradient product, no scatter, no early optimizer pass (mmda_misa_early_grad_floats() is
+ *     0), and the forward pass of such a step keeps no encoder stash (mmda_misa_set_cut_forward(m, 1): it stashes all the same).
+ *     mmda_misa_backward returns MMDA_EINVAL when the forward pass in front of it was planned under a cut that the set no longer allows.
+ * With every flag set (the state after mmda_misa_create) a step is launch for launch what it is without this call.
+ * mmda_misa_trainable_info (host only): the trainable runs -- sorted, disjoint, touching ones merged; a tensor's range includes the
+ * alignment padding behind it -- up to `capacity` of them in runs[], their number, the floats they cover and whether the cut is on. */
+int mmda_misa_set_trainable(mmda_misa* m, const unsigned char* flags, int n_params);
+int mmda_misa_trainable_info(const mmda_misa* m, mmda_run* runs, int capacity, int* n_runs, int64_t* trainable_floats, int* encoder_cut_on);
+int mmda_misa_set_cut_forward(mmda_misa* m, int keep_stash);
 /* Dense mode (mmda_misa_set_embed_update 0) with the table's update deferred (config.embed_update = deferred): the weights dense Adam
  * gives, while no launch of a step reads or writes the whole table -- see mmda_embed_rows_dense_adam.  Binds the caller's device memory
  * (row_step: vocab int32; step_scalars: mmda_embed_deferred_scalar_floats(window) floats; the runtime owns none), marks every row

@@ -113,6 +113,11 @@ class Mx8Args(C.Structure):
                 ("drop_p", C.c_float), ("drop_seed", C.c_uint64), ("drop_site", C.c_int)]
 
 
+class Run(C.Structure):
+    """mmda_run: a trainable range of a flat bucket (frozen parameters)"""
+    _fields_ = [("begin", C.c_int64), ("len", C.c_int64), ("first", C.c_int64)]
+
+
 CELL = {"lstm": 0, "gru": 1}
 
 # name -> (restype, argtypes).  Every symbol include/mmda_hip.h declares appears here (tests/test_abi.py checks it).
@@ -194,6 +199,10 @@ SIGNATURES = {
     "mmda_grad_accumulate": (_I, [_P, _P, _I64, _I, _P]),
     "mmda_clamp_adam_sum": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_embed_rows_append": (_I, [_P, _P, _I64, _I64, _P, _P, _I, _I, _P, _I, _P]),
+    "mmda_runs_build": (_I64, [C.POINTER(_I64), C.POINTER(_I64), _I, _I64, C.POINTER(Run), C.POINTER(_I)]),
+    "mmda_clamp_adam_runs": (_I, [_P, _P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mmda_clamp_adam_sum_runs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mmda_clamp_rmsprop_runs": (_I, [_P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _P]),
     "mmda_misa_create": (_I, [C.POINTER(MisaConfig), C.POINTER(C.c_void_p)]),
     "mmda_misa_destroy": (None, [_P]),
     "mmda_misa_num_params": (_I, [_P]),
@@ -214,6 +223,9 @@ SIGNATURES = {
     "mmda_misa_set_inference": (_I, [_P, _I]),
     "mmda_misa_set_fusion_fp8": (_I, [_P, _I]),
     "mmda_misa_set_embed_update": (_I, [_P, _I]),
+    "mmda_misa_set_trainable": (_I, [_P, C.c_char_p, _I]),
+    "mmda_misa_trainable_info": (_I, [_P, C.POINTER(Run), _I, C.POINTER(_I), C.POINTER(_I64), C.POINTER(_I)]),
+    "mmda_misa_set_cut_forward": (_I, [_P, _I]),
     "mmda_misa_set_embed_deferred": (_I, [_P, _P, _P, _I, _P]),
     "mmda_misa_embed_deferred_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_misa_embed_flush": (_I, [_P, _P]),

@@ -50,6 +50,12 @@ int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      /
 // mmda_clamp_adam whose launch does not complete before *wait_flag reaches wait_value
 int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
                          float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream);
+// frozen parameters: mmda_runs_build that merges no two ranges across one of `cuts`, and mmda_clamp_adam_runs with that waiter
+int64_t mmda_runs_build_cut(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, const int64_t* cuts, int n_cuts,
+                            mmda_run* out, int* n_out);
+int mmda_clamp_adam_runs_wait(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
+                              float beta1, float beta2, float eps, float clip, float grad_scale, int step, const unsigned* wait_flag,
+                              unsigned wait_value, unsigned* wait_err, void* stream);
 // SparseAdamArgs from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
 int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
                           float clip, float grad_scale, int step);

@@ -42,6 +42,8 @@ struct Mod {           // one modality: two stacked biLSTMs with a LayerNorm bet
 // part of the step.  What a launch's outcome sets or what is consumed later (wT_valid, side_pending, fj1, ...) stays in mmda_misa.
 struct StepPlan {
   bool inf = false;                 // evaluation pass: no backward follows -- no stash, no copies that only the backward pass reads
+  bool enc_cut = false;             // every encoder parameter is frozen (mmda_misa_set_trainable): the backward pass stops in front of the encoders
+  bool enc_nostash = false;         // the encoders keep nothing for a backward pass: an evaluation pass, or a cut step (unless told to stash)
   bool bfg = false;                 // bf16 mode with bf16 operand copies: the LSTM-sized GEMMs read them (gemm_bf16.hip)
   int gm = 0;                       // gate-minor layout of `gates` (see mmda_lstm_desc.gate_minor)
   bool kdg = false;                 // the backward recurrence writes the gate gradients as bf16, and only so
@@ -107,6 +109,16 @@ struct mmda_misa {
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
   int embed_update = EU_DENSE;
+  // Frozen parameters (mmda_misa_set_trainable).  `runs`: the trainable ranges of the bucket, never merged across rnn2_begin, rnn1_begin
+  // or embed -- so the runs of any range a launch of the step covers are a slice of the table -- and closed by an entry that carries the
+  // table's item count.  A tensor's range runs up to the next tensor, alignment padding included.  runs_dev: the table on the device
+  // (the one allocation besides jflags), copied when the set has changed since the last launch that read it.
+  std::vector<mmda_run> runs;
+  int prefix_frozen = 0;           // a tensor in front of the table is frozen
+  int embed_flag = 1;              // the table's own flag (what embed_update makes of the table is a separate matter)
+  int enc_frozen = 0;              // both recurrent layers and the three inter-layer LayerNorms are frozen
+  int cut_keep_stash = 0;          // a cut step runs the stashing forward all the same (mmda_misa_set_cut_forward)
+  mmda_run* runs_dev = nullptr; int runs_dev_cap = 0; int runs_dirty = 1;
   // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
   // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
   // for backward itself)
@@ -614,6 +626,81 @@ mmda_lstm_desc lstm_desc(mmda_misa* m, int i, int l, bool bwd, int gate_minor, b
 // floats of the gradient bucket that a step writes, clears and walks with dense Adam: all of it, or the prefix in front of the table
 int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE && !m->df_row_step ? m->flat : m->embed; }
 
+// ---- frozen parameters
+// a launch over [0, grad_floats) has a frozen float to leave out (else the step is today's: the dense kernels, the early pass)
+bool masked(const mmda_misa* m) { return m->prefix_frozen || (!m->embed_flag && grad_floats(m) == m->flat); }
+// the encoder cut: nothing behind the fusion block trains -- the recurrent layers and the inter-layer LayerNorms are frozen and the
+// table is, by its flag (dense) or by embed_update (the sparse and deferred modes train the table through d_x: no cut)
+bool encoder_cut(const mmda_misa* m) {
+  return m->enc_frozen && (m->embed_update == EU_FROZEN || (m->embed_update == EU_DENSE && !m->df_row_step && !m->embed_flag));
+}
+// the table's slice for the bucket range [lo, hi), both of them 0, rnn2_begin, rnn1_begin, embed or flat
+void runs_slice(const mmda_misa* m, int64_t lo, int64_t hi, int* r0, int* n, int64_t* items) {
+  const int nr = (int)m->runs.size() - 1;
+  int a = 0;
+  while (a < nr && m->runs[a].begin < lo) ++a;
+  int b = a;
+  while (b < nr && m->runs[b].begin < hi) ++b;
+  *r0 = a; *n = b - a; *items = m->runs[b].first - m->runs[a].first;
+}
+// the table on the device, current.  A changed set waits for the streams that may still read the old table: once per change.
+int runs_ready(mmda_misa* m, void* stream) {
+  if (!m->runs_dirty && m->runs_dev) return MMDA_OK;
+  const int need = (int)m->runs.size();
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return MMDA_ELAUNCH;
+  if (m->side && hipStreamSynchronize(m->side) != hipSuccess) return MMDA_ELAUNCH;
+  if (need > m->runs_dev_cap) {
+    if (m->runs_dev) (void)hipFree(m->runs_dev);
+    m->runs_dev = nullptr; m->runs_dev_cap = 0;
+    const int cap = (int)m->params.size() + 1;            // every tensor a run of its own, and the closing entry
+    if (hipMalloc(reinterpret_cast<void**>(&m->runs_dev), sizeof(mmda_run) * cap) != hipSuccess) { m->runs_dev = nullptr; return MMDA_ELAUNCH; }
+    m->runs_dev_cap = cap;
+  }
+  if (hipMemcpy(m->runs_dev, m->runs.data(), sizeof(mmda_run) * need, hipMemcpyHostToDevice) != hipSuccess) return MMDA_ELAUNCH;
+  m->runs_dirty = 0;
+  return MMDA_OK;
+}
+// clamp + Adam over the trainable runs of [lo, hi): the launch a masked step makes where today's makes mmda_clamp_adam[_wait] /
+// mmda_clamp_adam_sum (acc != nullptr) over that range.  A range with nothing to train launches nothing -- but for a waiter.
+int masked_adam(mmda_misa* m, int64_t lo, int64_t hi, const float* acc, float lr, float clip, float grad_scale, int step,
+                const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream) {
+  int r0 = 0, n = 0; int64_t items = 0;
+  runs_slice(m, lo, hi, &r0, &n, &items);
+  if (n > 0 && (m->runs_dirty || !m->runs_dev)) return MMDA_EINVAL;      // (every entry that gets here called runs_ready first)
+  const mmda_run* d = n > 0 ? m->runs_dev + r0 : nullptr;
+  if (acc) return mmda_clamp_adam_sum_runs(m->P, acc, m->G, m->M1, m->V1, d, n, items, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  return mmda_clamp_adam_runs_wait(m->P, m->G, m->M1, m->V1, d, n, items, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, wait_flag,
+                                   wait_value, wait_err, stream);
+}
+// the table from one flag per parameter (nullptr: everything trains)
+int apply_trainable(mmda_misa* m, const unsigned char* flags) {
+  const int np = (int)m->params.size();
+  std::vector<int64_t> begin, len;
+  int prefix_frozen = 0, embed_flag = 1, enc_frozen = 1;
+  for (int i = 0; i < np; ++i) {
+    const ParamInfo& p = m->params[i];
+    const bool on = !flags || flags[i] != 0;
+    const std::string top = p.name.substr(0, p.name.find('.'));
+    if (p.off == m->embed) embed_flag = on ? 1 : 0;
+    else if (!on) prefix_frozen = 1;
+    if (on && ((p.off >= m->rnn2_begin && p.off < m->embed) || top == "tlayer_norm" || top == "vlayer_norm" || top == "alayer_norm")) enc_frozen = 0;
+    if (!on) continue;
+    begin.push_back(p.off);
+    len.push_back((i + 1 < np ? m->params[i + 1].off : m->flat) - p.off);
+  }
+  const int64_t cuts[3] = {m->rnn2_begin, m->rnn1_begin, m->embed};
+  std::vector<mmda_run> runs(begin.size() + 1);
+  int n = 0;
+  const int64_t items = mmda_runs_build_cut(begin.data(), len.data(), (int)begin.size(), m->flat, cuts, 3, runs.data(), &n);
+  if (items < 0) return MMDA_EINVAL;
+  runs.resize(n + 1);
+  runs[n] = mmda_run{m->flat, 0, items};
+  m->runs.swap(runs);
+  m->prefix_frozen = prefix_frozen; m->embed_flag = embed_flag; m->enc_frozen = enc_frozen;
+  m->runs_dirty = 1;
+  return MMDA_OK;
+}
+
 constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
 
 // the decisions of one step (see StepPlan); the switches that select a form of the step are read here only
@@ -639,6 +726,8 @@ StepPlan plan_step(mmda_misa* m) {
     return mmda_lstm_resident_applicable(mode, 3, probe, B, T, backward) != 0;
   };
   P.inf = m->inference != 0;
+  P.enc_cut = !P.inf && encoder_cut(m);
+  P.enc_nostash = P.inf || (P.enc_cut && !m->cut_keep_stash);
   P.bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
   // Gate-minor layout of the pre-activations / stash / gate gradients ([dir][unit][gate], 16-byte accesses in the recurrent
   // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
@@ -647,7 +736,7 @@ StepPlan plan_step(mmda_misa* m) {
   // The backward probe with the backward pass's own descriptors gives the same answer: they differ from these only in pointers
   // (pack_b, d_utt, d_hseq) and in wpack_c, which the backward pass sets because want_c holds -- bf16, resident, training -- and
   // without which probe_resident(1, 2) fails anyway (no exchange buffers without use_cluster).
-  P.kdg = !P.inf && P.bfg && P.gm && probe_resident(1, 2);
+  P.kdg = !P.enc_nostash && P.bfg && P.gm && probe_resident(1, 2);
   // Weight gradients in the tn form of the bf16 GEMM (dW = dG^T X on row-major dG, X, hseq): the transposed copies of the inputs, of
   // hseq and of the gate gradients are not made at all (B=256: 0.33 ms of conversions per step).  Needs the gate gradients as bf16
   // from the recurrent kernel (gate-minor resident path).  Up to T*B = 4096 rows: measured (step, ms) B=32 0.759 -> 0.745, B=64 0.928 ->
@@ -658,9 +747,9 @@ StepPlan plan_step(mmda_misa* m) {
   // without layer 1 alone in the tn form beyond it, measured slower).  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere.
   P.tn_wgrad = P.kdg && tn_on;
   // The forward packing always; the resident-weights backward packing when those kernels will run the backward pass and the
-  // streaming backward packing only when they will not; neither for an evaluation pass.
-  P.want_c = !P.inf && m->use_cluster && mode == MMDA_BF16;
-  P.want_b = !P.inf && !(P.want_c && probe_resident(0, 1));
+  // streaming backward packing only when they will not; neither for a pass whose encoders keep no stash.
+  P.want_c = !P.enc_nostash && m->use_cluster && mode == MMDA_BF16;
+  P.want_b = !P.enc_nostash && !(P.want_c && probe_resident(0, 1));
   P.skinny = B <= SKINNY_MAX_B;
   P.want_wT = P.skinny && !P.inf;
   P.wT_merge = P.bfg && P.want_wT && wt_merge;
@@ -683,7 +772,7 @@ StepPlan plan_step(mmda_misa* m) {
   P.rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
   P.embed_update = m->embed_update;
   P.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
-  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN;
+  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN && !P.enc_cut;
   return P;
 }
 
@@ -699,6 +788,7 @@ extern "C" int mmda_misa_create(const mmda_misa_config* cfg, mmda_misa** out) {
   mmda_misa* m = new mmda_misa();
   m->cfg = *cfg;
   build_params(m);
+  if (apply_trainable(m, nullptr)) { delete m; return MMDA_EINVAL; }
   *out = m;
   return MMDA_OK;
 }
@@ -710,6 +800,7 @@ extern "C" void mmda_misa_destroy(mmda_misa* m) {
   if (m->ev_early) (void)hipEventDestroy(m->ev_early);
   if (m->side) (void)hipStreamDestroy(m->side);
   if (m->jflags) (void)hipFree(m->jflags);
+  if (m->runs_dev) (void)hipFree(m->runs_dev);
   for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
   delete m;
 }
@@ -1018,6 +1109,41 @@ extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
   return MMDA_OK;
 }
 
+// ---- frozen parameters
+extern "C" int mmda_misa_set_trainable(mmda_misa* m, const unsigned char* flags, int n_params) {
+  if (!m || !flags || n_params != (int)m->params.size()) return MMDA_EINVAL;
+  return apply_trainable(m, flags);
+}
+extern "C" int mmda_misa_trainable_info(const mmda_misa* m, mmda_run* runs, int capacity, int* n_runs, int64_t* trainable_floats,
+                                        int* encoder_cut_on) {
+  if (!m || capacity < 0 || (capacity > 0 && !runs)) return MMDA_EINVAL;
+  // the table as its user sees it: runs that touch are one run, whichever section cut lies between them
+  int n = 0; int64_t floats = 0, end = -1, items = 0;
+  mmda_run last = {0, 0, 0};
+  for (size_t i = 0; i + 1 < m->runs.size(); ++i) {
+    const mmda_run& r = m->runs[i];
+    floats += r.len;
+    if (n > 0 && r.begin == end) {
+      last.len += r.len;
+    } else {
+      if (n > 0) items += ((last.begin + last.len - 1) >> 2) - (last.begin >> 2) + 1;
+      last = mmda_run{r.begin, r.len, items};
+      ++n;
+    }
+    if (n <= capacity) runs[n - 1] = last;
+    end = r.begin + r.len;
+  }
+  if (n_runs) *n_runs = n;
+  if (trainable_floats) *trainable_floats = floats;
+  if (encoder_cut_on) *encoder_cut_on = encoder_cut(m) ? 1 : 0;
+  return MMDA_OK;
+}
+extern "C" int mmda_misa_set_cut_forward(mmda_misa* m, int keep_stash) {
+  if (!m) return MMDA_EINVAL;
+  m->cut_keep_stash = keep_stash ? 1 : 0;
+  return MMDA_OK;
+}
+
 namespace {
 // One pass of the step in flight, as a sequence of stages: the GEMM context and what every stage reads -- the plan, the
 // configuration, the batch shape and the dropout of the step.  Each stage sets rc and issues nothing once it is set.
@@ -1129,7 +1255,7 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
   m->wT_valid = 0;
   if (P.bfg) {
     mmda_convert_job cj[9];
-    const int nj = first_jobs(!P.inf, cj);
+    const int nj = first_jobs(!P.enc_nostash, cj);
     // ... and the K-major copies of the fusion block's weights (backward pass) in the same launch: 6 MB of traffic that cost a
     // launch of its own 7 - 9 us at the head of the loss chain (side stream, the longer of the two chains beside the fusion block)
     // or, at B >= 128, 15 us with its gap on the main stream.  MMDA_WT_MERGE=0: on the first fork as before.
@@ -1169,7 +1295,7 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
       gemm(*this, mode, 0, 1, R, 8 * r.H, r.D, in, r.D, rW_ih(m, r), r.D, WS(md.gates[l]), 8 * r.H, rB_ih(m, r), rB_hh(m, r));
     }
     desc[i] = lstm_desc(m, i, l, false, P.gm, false);
-    desc[i].forward_only = P.inf;
+    desc[i].forward_only = P.enc_nostash;
   }
   if (P.bfg && !rc) rc = mmda_gemm_bf16_grouped(bg, 3, s);
   m->epoch += (unsigned)T + 2u;
@@ -1194,12 +1320,12 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
     //  the backward pass needs -- hseq, transposed inputs -- are made later on the side stream: backward_only_jobs)
     if (P.bfg)
       for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(m->mod[i].rnn[1].xb); ln[i].ld_bf16 = m->mod[i].rnn[1].ldD; }
-    // ... and ONLY as that copy where nothing reads the fp32 output: an evaluation pass, or a training step whose layer-2 weight
-    // gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
-    if (P.bfg && (P.inf || P.tn_wgrad))
+    // ... and ONLY as that copy where nothing reads the fp32 output: a pass whose encoders keep no stash, or a training step whose
+    // layer-2 weight gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
+    if (P.bfg && (P.enc_nostash || P.tn_wgrad))
       for (int i = 0; i < 3; ++i) ln[i].y = nullptr;
     rc = mmda_layernorm_fwd_multi(ln, 3, s);
-  } else if (!m->eager_losses && ((P.bfg && !P.inf) || m->zero_grad_pending || m->wT_pending)) {
+  } else if (!m->eager_losses && ((P.bfg && !P.enc_nostash) || m->zero_grad_pending || m->wT_pending)) {
     // side stream, beside the fusion block: the gradient bucket is cleared (train_step) and hseq^T of layer 2 is made for its
     // dW_hh.  Joined at the end of forward(), so everything the backward pass issues on either stream is ordered behind both.
     void* ss = nullptr;
@@ -1528,7 +1654,7 @@ void Pass::bwd_fusion_fused() {
     m->fj1 = 0;
   }
   if (!rc) rc = mmda_fused_bwd_a(&f, s);
-  skinny_proj_dx(true);
+  if (!P.enc_cut) skinny_proj_dx(true);                  // (d_utt feeds the encoders only)
 }
 
 // ... as stand-alone row-skinny launches (MMDA_ROW_FUSE=0, the adversarial discriminator, hidden != 128, or no K-major copies)
@@ -1582,7 +1708,7 @@ void Pass::bwd_fusion_skinny() {
     for (int i = 0; i < 3; ++i) l[i] = proj_ln_bwd(i);
     rc = mmda_layernorm_bwd_multi(l, 3, s);
   }
-  skinny_proj_dx(wt);
+  if (!P.enc_cut) skinny_proj_dx(wt);
 }
 
 // ... many rows: the tiled generic kernel
@@ -1630,7 +1756,7 @@ void Pass::bwd_fusion_tiled() {
     Mod& md = m->mod[i];
     const mmda_ln_bwd_args l = proj_ln_bwd(i);
     rc = mmda_layernorm_bwd(&l, s);
-    lin_dx(*this, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), PP(md.pw), WS(md.d_utt), 0);
+    if (!P.enc_cut) lin_dx(*this, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), PP(md.pw), WS(md.d_utt), 0);
   }
 }
 
@@ -1694,7 +1820,7 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   deferred.clear();
   // the bf16 operand copies that only the weight-gradient GEMMs read (hseq of both layers, nt form: transposed layer-2 inputs): here,
   // where the side stream is idle beside the layer-2 recurrence, instead of in front of the loss kernels of the forward pass
-  if (!rc && P.bfg && m->T > 0) {
+  if (!rc && P.bfg && m->T > 0 && !P.enc_cut) {           // (a cut step runs no encoder weight-gradient GEMM)
     mmda_convert_job cj[16];
     const int nj = backward_only_jobs(m, cj);
     rc = mmda_convert_bf16(cj, nj, ss);
@@ -1860,7 +1986,9 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // the other modes the prefix ends in front of the recurrent layers).  The side stream is a real second stream only when
     // use_side is on; otherwise this is simply the same work in front of the recurrence.
     if (!rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
-      rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
+      // (frozen parameters: over the prefix's trainable runs -- the prefix counts as stepped even where none of it trains)
+      rc = masked(m) ? masked_adam(m, 0, m->early_floats, nullptr, m->ae_lr, m->ae_clip, 1.0f, m->ae_step, nullptr, 0u, nullptr, ss)
+                     : mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
       if (!rc) m->adam_early_done = m->early_floats;
     }
   } else if (P.embed_update == EU_SPARSE) {
@@ -1928,6 +2056,9 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
                                   void* stream) {
   if (check_ready(m) || !m->G || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
   if (m->plan.inf) return MMDA_EINVAL;                  // the last forward was an evaluation pass: nothing was stashed
+  // the trainable set changed behind that forward: a cut pass computes no encoder gradient (and may have stashed nothing)
+  if (m->plan.enc_cut && !encoder_cut(m)) return MMDA_EINVAL;
+  if (masked(m) && m->adam_early_on) { const int rr = runs_ready(m, stream); if (rr) return rr; }
   m->early_valid = 0;
   Pass x(m, stream);
   const StepPlan& P = m->plan;
@@ -1941,7 +2072,10 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
   if (x.rc) return x.rc;
   x.bwd_side_chain(row_fuse, t_ids, lengths);
   const float* xin[3] = {WS(m->mod[0].x), v, a};
-  for (int l = 1; l >= 0 && !x.rc; --l) x.bwd_encoder_layer(l, xin, t_ids, lengths);
+  // Encoder cut: the pass ends here.  No early optimizer pass, no ev_early, no sorted id list and no flag word of this pass exist,
+  // so the join below is the event's (adam_early_done stays 0) and no kernel waits for a word that nobody sets; the recurrent
+  // layers' ranges of the gradient bucket hold what the clear left.
+  for (int l = 1; l >= 0 && !x.rc && !P.enc_cut; --l) x.bwd_encoder_layer(l, xin, t_ids, lengths);
   if (x.rc) return x.rc;
   if (!m->ev.empty()) { if (m->ev_seen_b % m->ev_stride == 0) m->ev_bwd++; m->ev_seen_b++; }
   // every gradient is complete on `stream` when backward returns -- or, in a fused training step whose last optimizer launch can
@@ -1955,7 +2089,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     return x.rc;
   }
   x.rc = side_join(m, stream);
-  if (!x.rc && is_gru(m)) {                    // fold the four-slot weight gradients into the torch-layout gradient buffer
+  if (!x.rc && is_gru(m) && !P.enc_cut) {      // fold the four-slot weight gradients into the torch-layout gradient buffer
     mmda_gru_pad_job gj[MMDA_GRU_PAD_MAX];
     int n = gru_jobs(m, m->G, true, gj);
     x.rc = mmda_gru_unpad_grads(gj, n, stream);
@@ -2014,7 +2148,13 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 // =============================================================================================== optimizer / step
 extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
   if (!m || !m->P || !m->G || !m->M1 || !m->V1) return MMDA_EINVAL;
-  int rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  int rc = MMDA_OK;
+  if (masked(m)) {                                       // frozen parameters: the trainable runs only
+    rc = runs_ready(m, stream);
+    if (!rc) rc = masked_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, nullptr, 0u, nullptr, stream);
+  } else {
+    rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  }
   if (!rc && m->embed_update == EU_SPARSE && m->eu_pending) {
     // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
     m->eu_pending = 0;
@@ -2060,7 +2200,13 @@ extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, i
                                                int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream) {
   // (everything is checked in front of the dense launch: a refused call changes nothing)
   if (!accum_ready(m) || !m->M1 || !m->V1 || step < 1 || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
-  int rc = mmda_clamp_adam_sum(m->P, acc, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  int rc = MMDA_OK;
+  if (masked(m)) {
+    rc = runs_ready(m, stream);
+    if (!rc) rc = masked_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, nullptr, 0u, nullptr, stream);
+  } else {
+    rc = mmda_clamp_adam_sum(m->P, acc, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+  }
   if (!rc && m->embed_update == EU_SPARSE) {
     const int n = (int)(list_used + (int64_t)m->B * m->T);
     rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
@@ -2078,7 +2224,12 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   // the gradient bucket is cleared on the side stream beside the forward pass's fusion block (not at the start of the step: the
   // side stream's first job there, packing W_hh, is what the first recurrent kernel waits for)
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
-  m->inference = 0;                                     // a training step always stashes
+  if (masked(m) && do_adam) {                           // frozen parameters: the run table is on the device before the first launch
+    if (!m->M1 || !m->V1) return MMDA_EINVAL;
+    const int rr = runs_ready(m, stream);
+    if (rr) return rr;
+  }
+  m->inference = 0;                                     // a training step always stashes (but for the encoders of a cut step)
   m->zero_grad_pending = m->T > 0 ? 1 : 0;
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
@@ -2105,8 +2256,12 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
     const bool fj = m->fj2 != 0;
     m->fj2 = 0;
     // (sparse / frozen table: the launch ends in front of it -- and stays the waiter)
-    rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, grad_floats(m) - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
-                              fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr, stream);
+    if (masked(m))
+      rc = masked_adam(m, o, grad_floats(m), nullptr, lr, clip, 1.0f, step, fj ? m->jflags + 1 : nullptr, m->jval[1],
+                       fj ? m->jflags + 2 : nullptr, stream);
+    else
+      rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, grad_floats(m) - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
+                                fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr, stream);
   }
   return rc;
 }

@@ -215,6 +215,96 @@ __global__ __launch_bounds__(256) void clamp_rmsprop_kernel(float* p, const floa
   }
 }
 
+// ---- frozen parameters (requires_grad = False): clamp + update over the TRAINABLE RUNS of a bucket (mmda_hip.h: mmda_run)
+// A work item is one 16-byte aligned quad of the bucket that a run touches; the grid is sized by the items, and item j of the launch
+// finds its run by bisection over the runs' running counts (a few hundred entries at the most, read by every lane: they stay in
+// cache).  A quad that lies inside its run goes through 16-byte accesses like the dense kernels'; a quad at a run's end takes the
+// floats of the run one by one, so no float outside a run is loaded or stored -- two runs that share a quad touch disjoint floats of
+// it.  F: one element / one quad of an update, with the arithmetic of the dense kernel it stands in for.  wait_flag: as in
+// clamp_adam_kernel (the same flag_wait).
+template <class F>
+__global__ __launch_bounds__(256) void runs_kernel(const mmda_run* __restrict__ runs, int n_runs, int64_t items, F f,
+                                                   const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t item0 = n_runs > 0 ? runs[0].first : 0;          // (a slice of a longer table: counts run on from its start)
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
+    const int64_t j = item0 + i;
+    int lo = 0, hi = n_runs - 1;                                   // the last run whose count is <= j
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (runs[mid].first <= j) lo = mid; else hi = mid - 1;
+    }
+    const mmda_run r = runs[lo];
+    const int64_t q = (r.begin >> 2) + (j - r.first);              // the bucket's quad
+    const int64_t e0 = max(q << 2, r.begin), e1 = min((q << 2) + 4, r.begin + r.len);
+    if (e1 - e0 == 4) f.quad(q);
+    else for (int64_t e = e0; e < e1; ++e) f.one(e);
+  }
+  if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
+}
+
+struct RunAdam {            // clamp_adam_kernel's update
+  float* p; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt;
+  __device__ __forceinline__ void quad(int64_t q) const {
+    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
+    const float4 gg = reinterpret_cast<const float4*>(g)[q];
+    adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
+  }
+  __device__ __forceinline__ void one(int64_t e) const { adam1(p[e], g[e], m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt); }
+};
+struct RunAdamSum {         // clamp_adam_sum_kernel's: the gradient is acc + g, neither is written
+  float* p; const float* acc; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt;
+  __device__ __forceinline__ void quad(int64_t q) const {
+    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
+    const float4 aa = reinterpret_cast<const float4*>(acc)[q], gg = reinterpret_cast<const float4*>(g)[q];
+    adam1(pp.x, __fadd_rn(aa.x, gg.x), mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.y, __fadd_rn(aa.y, gg.y), mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.z, __fadd_rn(aa.z, gg.z), mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.w, __fadd_rn(aa.w, gg.w), mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
+  }
+  __device__ __forceinline__ void one(int64_t e) const {
+    adam1(p[e], __fadd_rn(acc[e], g[e]), m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+  }
+};
+struct RunRmsprop {         // clamp_rmsprop_kernel's
+  float* p; const float* g; float* sq; float lr, alpha, eps, clip, gscale;
+  // That kernel leaves contraction to the compiler, which forms no fma in its loop; the same statements unrolled over a quad here did
+  // get one (alpha * sq + ...) and lost the dense launch's bits.  So: the operations its code performs, in its order, with contraction
+  // off for this block -- on plain operators: __fadd_rn / __fmul_rn are functions of a header compiled with contraction on, and what
+  // they return is fused all the same.  tests/test_gpu_frozen.py holds the two launches together.
+  __device__ __forceinline__ void one(int64_t i) const {
+#pragma clang fp contract(off)
+    const float gg = fminf(fmaxf(g[i] * gscale, -clip), clip);
+    const float old = alpha * sq[i];
+    const float add = ((1.0f - alpha) * gg) * gg;
+    const float s = old + add;
+    sq[i] = s;
+    const float num = lr * gg;
+    const float den = sqrtf(s) + eps;
+    p[i] = p[i] - num / den;
+  }
+  __device__ __forceinline__ void quad(int64_t q) const {
+    for (int k = 0; k < 4; ++k) one((q << 2) + k);
+  }
+};
+
+template <class F>
+int launch_runs(const char* what, const mmda_run* runs, int n_runs, int64_t items, const F& f, const unsigned* wait_flag,
+                unsigned wait_value, unsigned* wait_err, void* stream) {
+  int64_t blocks = (items + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(runs_kernel<F>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, runs, n_runs, items, f, wait_flag, wait_value,
+                     wait_err);
+  MMDA_CHECK_LAUNCH(what);
+  return MMDA_OK;
+}
+
 // two buffers cleared by one launch (16-byte stores; counts in floats, multiples of 4, 16-byte aligned bases)
 __global__ __launch_bounds__(256) void zero2_kernel(float4* a, int64_t na4, float4* b, int64_t nb4) {
   const float4 z = {0.f, 0.f, 0.f, 0.f};
@@ -285,6 +375,84 @@ extern "C" int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, f
                      clip, grad_scale, step_size, inv_bc2_sqrt);
   MMDA_CHECK_LAUNCH("mmda_clamp_adam_sum");
   return MMDA_OK;
+}
+
+// ---- trainable runs (frozen parameters): host side
+// internal (misa.hip): mmda_runs_build that never merges two ranges across one of `cuts` (bucket offsets, multiples of 4, inside no
+// range), so that the runs of the bucket between two cuts are a slice of the table
+int64_t mmda_runs_build_cut(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, const int64_t* cuts, int n_cuts,
+                            mmda_run* out, int* n_out) {
+  if (n < 0 || bucket_floats < 0 || !n_out || (n > 0 && (!begin || !len || !out)) || (n_cuts > 0 && !cuts)) return MMDA_EINVAL;
+  int k = 0;
+  int64_t end = 0, items = 0;                            // where the last range ended; work items so far
+  for (int i = 0; i < n; ++i) {
+    if (len[i] < 0 || begin[i] < end || begin[i] > bucket_floats || len[i] > bucket_floats - begin[i]) return MMDA_EINVAL;
+    if (len[i] == 0) continue;
+    bool at_cut = false;
+    for (int c = 0; c < n_cuts; ++c) at_cut = at_cut || cuts[c] == begin[i];
+    if (k > 0 && begin[i] == end && !at_cut) {
+      mmda_run& r = out[k - 1];
+      items -= ((r.begin + r.len - 1) >> 2) - (r.begin >> 2) + 1;
+      r.len += len[i];
+      items += ((r.begin + r.len - 1) >> 2) - (r.begin >> 2) + 1;
+    } else {
+      out[k++] = mmda_run{begin[i], len[i], items};
+      items += ((begin[i] + len[i] - 1) >> 2) - (begin[i] >> 2) + 1;
+    }
+    end = begin[i] + len[i];
+  }
+  *n_out = k;
+  return items;
+}
+
+extern "C" int64_t mmda_runs_build(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, mmda_run* out, int* n_out) {
+  return mmda_runs_build_cut(begin, len, n, bucket_floats, nullptr, 0, out, n_out);
+}
+
+// internal (misa.hip): mmda_clamp_adam_runs whose launch does not complete before *wait_flag reaches wait_value -- clamp_adam_kernel's
+// waiter; with nothing to update, that kernel itself over no floats
+int mmda_clamp_adam_runs_wait(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
+                              float beta1, float beta2, float eps, float clip, float grad_scale, int step, const unsigned* wait_flag,
+                              unsigned wait_value, unsigned* wait_err, void* stream) {
+  if (!p || !g || !m || !v || n_runs < 0 || items < 0 || step < 1) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // 16-byte quads
+  if (n_runs == 0 || items == 0)
+    return wait_flag ? mmda_clamp_adam_wait(p, g, m, v, 0, lr, beta1, beta2, eps, clip, grad_scale, step, wait_flag, wait_value, wait_err, stream)
+                     : MMDA_OK;
+  if (!runs) return MMDA_EINVAL;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const RunAdam f{p, g, m, v, beta1, beta2, eps, clip, grad_scale, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+  return launch_runs("mmda_clamp_adam_runs", runs, n_runs, items, f, wait_flag, wait_value, wait_err, stream);
+}
+
+extern "C" int mmda_clamp_adam_runs(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
+                                    float beta1, float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
+  return mmda_clamp_adam_runs_wait(p, g, m, v, runs, n_runs, items, lr, beta1, beta2, eps, clip, grad_scale, step, nullptr, 0u, nullptr,
+                                   stream);
+}
+
+extern "C" int mmda_clamp_adam_sum_runs(float* p, const float* acc, const float* g, float* m, float* v, const mmda_run* runs, int n_runs,
+                                        int64_t items, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
+                                        void* stream) {
+  if (!acc) return mmda_clamp_adam_runs(p, g, m, v, runs, n_runs, items, lr, beta1, beta2, eps, clip, grad_scale, step, stream);
+  if (!p || !g || !m || !v || n_runs < 0 || items < 0 || step < 1) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;
+  if (n_runs == 0 || items == 0) return MMDA_OK;
+  if (!runs) return MMDA_EINVAL;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const RunAdamSum f{p, acc, g, m, v, beta1, beta2, eps, clip, grad_scale, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+  return launch_runs("mmda_clamp_adam_sum_runs", runs, n_runs, items, f, nullptr, 0u, nullptr, stream);
+}
+
+extern "C" int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_avg, const mmda_run* runs, int n_runs, int64_t items,
+                                       float lr, float alpha, float eps, float clip, float grad_scale, void* stream) {
+  if (!p || !g || !square_avg || n_runs < 0 || items < 0) return MMDA_EINVAL;
+  if (n_runs == 0 || items == 0) return MMDA_OK;
+  if (!runs) return MMDA_EINVAL;
+  const RunRmsprop f{p, g, square_avg, lr, alpha, eps, clip, grad_scale};
+  return launch_runs("mmda_clamp_rmsprop_runs", runs, n_runs, items, f, nullptr, 0u, nullptr, stream);
 }
 
 extern "C" int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids,

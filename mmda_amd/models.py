@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import os
 from typing import Dict, List, Tuple
 
@@ -40,6 +41,7 @@ _PUB = ["scores", "tcp", "utt_t_orig", "utt_v_orig", "utt_a_orig", "utt_private_
 
 
 _SIG_CACHE: Dict[int, bool] = {}
+_REQUIRES_GRAD = operator.attrgetter("requires_grad")
 
 
 def _takes_model(fn) -> bool:
@@ -131,11 +133,13 @@ class MISA(nn.Module):
             _lib.check(lib.mmda_misa_set_fusion_fp8(h, 1), "set_fusion_fp8")
         _lib.check(lib.mmda_misa_set_embed_update(h, EMBED_UPDATE[self.embed_update]), "set_embed_update")
         self._layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        self._native_names: List[str] = []                  # mmda_misa_param_info order = ascending bucket offset
         for i in range(lib.mmda_misa_num_params(h)):
             name, off, rows, cols = C.c_char_p(), C.c_int64(), C.c_int(), C.c_int()
             _lib.check(lib.mmda_misa_param_info(h, i, C.byref(name), C.byref(off), C.byref(rows), C.byref(cols)))
             shape = (rows.value, cols.value) if cols.value > 0 else (rows.value,)
             self._layout[name.value.decode()] = (off.value, shape)
+            self._native_names.append(name.value.decode())
         self._flat_floats = lib.mmda_misa_flat_floats(h)
         self._dense_floats = lib.mmda_misa_dense_floats(h)
         self._names: List[str] = sorted(self._layout, key=_reference_sort_key)
@@ -165,6 +169,13 @@ class MISA(nn.Module):
             # what the reference's `self.model.embed.requires_grad = False` (solver.py:86) meant: the optimizer's
             # filter(lambda p: p.requires_grad, ...) then leaves the table out
             self.embed.weight.requires_grad_(False)
+        # frozen parameters: the requires_grad flags (native order) the native side was last told -- it starts with every flag set --, how
+        # often it was told, and the device table of trainable runs the unfused optimizers step through (made when first needed)
+        self._native_params = [self._get(n) for n in self._native_names]
+        self._embed_index = self._native_names.index("embed.weight")
+        self._trainable_sent = (True,) * len(self._native_names)
+        self._trainable_sends = 0
+        self._runs_cache = None
         # deferred mode: per-row step counts and the ring of step scalars (device, made with the flat buckets), and whether a step has
         # been taken since the last flush
         self._df_row_step = self._df_ring = None
@@ -334,10 +345,106 @@ class MISA(nn.Module):
         if mode == "deferred" and bound:
             self._bind_deferred()
 
+    # ------------------------------------------------------------------ frozen parameters
+    def _match(self, prefixes) -> List[str]:
+        names = []
+        for pre in prefixes:
+            hit = [n for n in self._names if n.startswith(pre)]
+            if not isinstance(pre, str) or not pre or not hit:
+                raise ValueError(f"no parameter of the state dict begins with {pre!r}")
+            names += [n for n in hit if n not in names]
+        return [n for n in self._names if n in names]
+
+    def freeze(self, *prefixes: str) -> List[str]:
+        """requires_grad_(False) on every parameter whose state-dict name begins with one of ``prefixes`` (``"trnn1"``, ``"embed"``,
+        ``"project_t.project_t.weight"``); returns those names.  Nothing else happens here: the flags are read when the next step begins,
+        as PyTorch's are -- a frozen tensor and its optimizer state then keep their bits, its ``.grad`` is None, and when nothing behind
+        the fusion block trains (all six recurrent layers, the three ``*layer_norm`` between them and the table) the backward pass
+        stops in front of the encoders."""
+        names = self._match(prefixes)
+        for n in names:
+            self._get(n).requires_grad_(False)
+        return names
+
+    def unfreeze(self, *prefixes: str) -> List[str]:
+        """The opposite of freeze().  A table frozen by embed_update='frozen' is thawed by set_embed_update(), not here."""
+        names = self._match(prefixes)
+        if "embed.weight" in names and self.embed_update == "frozen":
+            raise _lib.MMDAError("embed.weight is frozen by embed_update='frozen': switch the mode with set_embed_update('dense')")
+        for n in names:
+            self._get(n).requires_grad_(True)
+        return names
+
+    def _trainable_flags(self) -> Tuple[bool, ...]:
+        # (read at every step: the Parameter objects are looked up once, they stay the same objects through .to() and _materialize)
+        flags = tuple(map(_REQUIRES_GRAD, self._native_params))
+        if self.embed_update == "frozen" and flags[self._embed_index]:
+            flags = flags[:self._embed_index] + (False,) + flags[self._embed_index + 1:]
+        return flags
+
+    def frozen_names(self, beyond_embed_update: bool = False) -> List[str]:
+        """State-dict names of the parameters with requires_grad = False (``beyond_embed_update``: the table that embed_update='frozen'
+        froze is not listed)."""
+        out = [n for n in self._names if not self._get(n).requires_grad]
+        if beyond_embed_update and self.embed_update == "frozen":
+            out = [n for n in out if n != "embed.weight"]
+        return out
+
+    def _sync_trainable(self, exchange: bool = False) -> Tuple[bool, ...]:
+        """Read the requires_grad flags (a step begins) and tell the native side when they differ from what it was last told.
+        ``exchange``: a gradient exchange is part of the step."""
+        flags = self._trainable_flags()
+        if flags == self._trainable_sent and not exchange and (flags[self._embed_index] or self.embed_update not in ("sparse", "deferred")):
+            return flags                                    # (the steady state: one tuple compare)
+        frozen = [n for n, f in zip(self._native_names, flags) if not f]
+        if "embed.weight" in frozen and self.embed_update in ("sparse", "deferred"):
+            raise _lib.MMDAError(f"embed.weight.requires_grad=False under embed_update='{self.embed_update}': freeze the table with "
+                                 "set_embed_update(\"frozen\")")
+        if exchange and [n for n in frozen if not (n == "embed.weight" and self.embed_update == "frozen")]:
+            raise _lib.MMDAError("frozen parameters (requires_grad=False) together with a gradient exchange (grad_sync / data parallel) "
+                                 "are not built yet")
+        if flags != self._trainable_sent:
+            _lib.check(self._lib.mmda_misa_set_trainable(self._h, bytes(bytearray(int(f) for f in flags)), len(flags)), "set_trainable")
+            self._trainable_sent = flags
+            self._trainable_sends += 1
+        return flags
+
+    def trainable_info(self):
+        """(runs, trainable_floats, encoder_cut) as the native side holds them: runs = [(begin, length), ...] of the flat buckets, sorted,
+        disjoint, a tensor's range taken up to the next tensor (alignment padding included)."""
+        cap = len(self._native_names) + 1
+        runs = (_lib.Run * cap)()
+        n, floats, cut = C.c_int(), C.c_int64(), C.c_int()
+        _lib.check(self._lib.mmda_misa_trainable_info(self._h, runs, cap, C.byref(n), C.byref(floats), C.byref(cut)), "trainable_info")
+        return [(int(runs[i].begin), int(runs[i].len)) for i in range(n.value)], int(floats.value), bool(cut.value)
+
+    def _trainable_runs(self):
+        """None when every float of [0, grad_floats) trains; else (device table of mmda_run, runs, items) for the unfused optimizers'
+        run-table launches over that range.  Reads the flags (optimizer.step() begins a step of its own)."""
+        flags = self._sync_trainable()
+        n_floats = self.grad_floats
+        offs = [self._layout[n][0] for n in self._native_names] + [self._flat_floats]
+        live = [(offs[i], offs[i + 1] - offs[i], f) for i, f in enumerate(flags) if offs[i] < n_floats]
+        if all(f for _, _, f in live):
+            return None
+        key = (flags, n_floats, self._P.device)
+        if self._runs_cache is None or self._runs_cache[0] != key:
+            from . import ops
+            self._runs_cache = (key,) + ops.runs_table([(b, l) for b, l, f in live if f], n_floats, self._P.device)      # (once per change)
+        return self._runs_cache[1:]
+
+    def set_frozen_forward(self, stash: bool):
+        """A step under the encoder cut keeps no encoder stash in its forward pass (default); ``stash=True`` runs the stashing forward
+        all the same (tools/bench_frozen.py measures both)."""
+        _lib.check(self._lib.mmda_misa_set_cut_forward(self._h, int(bool(stash))), "set_cut_forward")
+
     def _assign_grad_views(self):
         for name, p in self._plist:
             if name == "embed.weight" and self.embed_update != "dense":
                 continue                                    # no dense gradient exists: see embedding_grad_rows()
+            if not p.requires_grad:
+                p.grad = None                               # frozen: what its range of the bucket holds is unspecified
+                continue
             if p.grad is None:
                 off, shape = self._layout[name]
                 p.grad = self._G[off:off + p.numel()].view(shape)
@@ -456,6 +563,8 @@ class MISA(nn.Module):
 
     def _forward_raw(self, t, v, a, len_dev, training: bool, seed: int, inference: bool = False):
         # inference: a forward that no backward will follow (torch.no_grad()): no stash, no backward-only operand copies
+        if not inference:
+            self._sync_trainable()                          # (a step begins: the pass is planned with the set the backward will find)
         _lib.check(self._lib.mmda_misa_set_inference(self._h, int(inference)), "set_inference")
         _lib.check(self._lib.mmda_misa_forward(self._h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(),
                                                int(training), seed, _lib.stream_ptr()), "mmda_misa_forward")
@@ -544,6 +653,7 @@ class MISA(nn.Module):
         if accum_count != 1 or accum_index != 0 or self._acc_next:
             return self._accum_micro_step(sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync,
                                           optimizer, accum_index, accum_count)
+        self._sync_trainable(exchange=grad_sync is not None)
         t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
         emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
         if seed is None:
@@ -631,6 +741,7 @@ class MISA(nn.Module):
                                  "which one rows update over the micro-batches' concatenated list does not give")
         if not do_adam:
             raise _lib.MMDAError("accum_steps > 1 with do_adam=False: the accumulated step ends in its optimizer step")
+        self._sync_trainable()
         t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
         emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
         if seed is None:
@@ -925,6 +1036,7 @@ class _MISAFn(torch.autograd.Function):
             if g is not None and k in slots and g.numel() > 0:
                 slots[k].copy_(g)
         t, v, a, len_dev = ctx.io
+        model._sync_trainable()
         _lib.check(lib.mmda_misa_backward(model._h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(), s),
                    "mmda_misa_backward")
         model._rows_pending = model.embed_update in ("sparse", "deferred")

@@ -500,6 +500,53 @@ def clamp_adam_sum(p, acc, g, m, v, lr, step, clip=float("inf"), grad_scale=1.0,
                                   stream_ptr()), "clamp_adam_sum")
 
 
+def runs_table(ranges, bucket_floats, device="cuda"):
+    """Frozen parameters: the device table of trainable runs for the run-table launches below, from (begin, length) ranges of a flat
+    bucket -- ascending and disjoint; empty ones are dropped, touching ones merged.  Returns (table, runs, items); build it once per
+    change of the set."""
+    lib = load()
+    k = len(ranges)
+    begin = (C.c_int64 * max(k, 1))(*[int(b) for b, _ in ranges])
+    length = (C.c_int64 * max(k, 1))(*[int(l) for _, l in ranges])
+    out = (_lib.Run * max(k, 1))()
+    n = C.c_int()
+    items = int(lib.mmda_runs_build(begin, length, k, int(bucket_floats), out, C.byref(n)))
+    if items < 0:
+        raise _lib.MMDAError("mmda_runs_build: the ranges must be ascending, disjoint and inside the bucket")
+    rows = [[out[i].begin, out[i].len, out[i].first] for i in range(n.value)] or [[0, 0, 0]]
+    return torch.tensor(rows, dtype=torch.int64).to(device), int(n.value), items
+
+
+def clamp_adam_runs(p, g, m, v, runs, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+    """clamp_adam over the trainable runs (runs_table) of the flat buffers only: nothing between the runs is read or written."""
+    lib = load()
+    table, n, items = runs
+    check(lib.mmda_clamp_adam_runs(ptr(p), ptr(g), ptr(m), ptr(v), ptr(table), n, items, lr, betas[0], betas[1], eps, clip, grad_scale, step,
+                                   stream_ptr()), "clamp_adam_runs")
+
+
+def clamp_adam_sum_runs(p, acc, g, m, v, runs, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+    """clamp_adam_sum over the trainable runs only."""
+    lib = load()
+    table, n, items = runs
+    assert acc is None or (acc.numel() == p.numel() and acc.is_contiguous())
+    check(lib.mmda_clamp_adam_sum_runs(ptr(p), ptr(acc), ptr(g), ptr(m), ptr(v), ptr(table), n, items, lr, betas[0], betas[1], eps, clip,
+                                       grad_scale, step, stream_ptr()), "clamp_adam_sum_runs")
+
+
+def clamp_rmsprop(p, g, sq, lr, alpha=0.99, eps=1e-8, clip=float("inf"), grad_scale=1.0):
+    lib = load()
+    check(lib.mmda_clamp_rmsprop(ptr(p), ptr(g), ptr(sq), p.numel(), lr, alpha, eps, clip, grad_scale, stream_ptr()), "clamp_rmsprop")
+
+
+def clamp_rmsprop_runs(p, g, sq, runs, lr, alpha=0.99, eps=1e-8, clip=float("inf"), grad_scale=1.0):
+    """clamp_rmsprop over the trainable runs only."""
+    lib = load()
+    table, n, items = runs
+    check(lib.mmda_clamp_rmsprop_runs(ptr(p), ptr(g), ptr(sq), ptr(table), n, items, lr, alpha, eps, clip, grad_scale, stream_ptr()),
+          "clamp_rmsprop_runs")
+
+
 def embed_rows_append(ids_out, rows_out, offset, ids, rows, lengths=None):
     """A micro-batch's (T, B) ids and (T * B, D) gradient rows appended at position `offset` of the list (ids_out (cap,) int64, rows_out
     (cap, D) fp32); positions past a sample's length (lengths: (B,) int32 on the device) get id -1.  Returns the list's new length."""

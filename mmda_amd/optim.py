@@ -168,8 +168,15 @@ class Adam(_FlatOptimizer):
             # embed_update 'sparse' / 'frozen': the dense launch ends in front of embed.weight; 'sparse' then updates the rows the last
             # backward touched, clamped by what clip_grad_value_ recorded for them (the unfused order clips before it steps)
             n = getattr(m, "grad_floats", P.numel())
-            _lib.check(lib.mmda_clamp_adam(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, g0["lr"], b1, b2,
-                                           g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam")
+            # frozen parameters (requires_grad=False): the same update over the trainable runs of the bucket only
+            runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
+            if runs is not None:
+                table, n_runs, items = runs
+                _lib.check(lib.mmda_clamp_adam_runs(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), table.data_ptr(), n_runs, items,
+                                                    g0["lr"], b1, b2, g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam_runs")
+            else:
+                _lib.check(lib.mmda_clamp_adam(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, g0["lr"], b1, b2,
+                                               g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam")
             if getattr(m, "embed_update", "dense") == "sparse":
                 rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
                 m.apply_sparse_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
@@ -235,6 +242,12 @@ class RMSprop(_FlatOptimizer):
                 raise _lib.MMDAError("embed_update='deferred' is built for Adam only")
             P, G, _, _ = m.flat_buckets()
             sq = self._square_avg(P)
+            runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
+            if runs is not None:                            # frozen parameters: the trainable runs only
+                table, n_runs, items = runs
+                _lib.check(lib.mmda_clamp_rmsprop_runs(P.data_ptr(), G.data_ptr(), sq.data_ptr(), table.data_ptr(), n_runs, items, g0["lr"],
+                                                       g0["alpha"], g0["eps"], clip, grad_scale, s), "mmda_clamp_rmsprop_runs")
+                return None
             _lib.check(lib.mmda_clamp_rmsprop(P.data_ptr(), G.data_ptr(), sq.data_ptr(), getattr(m, "grad_floats", P.numel()), g0["lr"], g0["alpha"], g0["eps"],
                                               clip, grad_scale, s), "mmda_clamp_rmsprop")
             return None

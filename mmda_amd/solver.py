@@ -80,6 +80,11 @@ class Solver(object):
                 raise _lib.MMDAError("accum_steps > 1 under data parallelism (world x accumulation) is not built yet")
             if eu == "deferred":
                 raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built (use 'dense': the same weights)")
+        if self.is_train and hasattr(self.model, "frozen_names") and self.model.frozen_names(beyond_embed_update=True):
+            from . import _lib
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                raise _lib.MMDAError("frozen parameters (requires_grad=False) under data parallelism are not built yet "
+                                     "(embed_update='frozen' alone is)")
         self.model.to(self.device)
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate)
