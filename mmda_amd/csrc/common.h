@@ -176,7 +176,7 @@ struct RowSparseAdam {
     a.P[o] = p; a.M[o] = m; a.V[o] = v;
   }
 };
-// ---- dense Adam, one element (optim.hip: clamp_adam_kernel, clamp_adam_rows_kernel; the deferred table update below)
+// ---- dense Adam, one element (optim.hip: the Adam functor under every walker; the deferred table update below)
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
                                       float gscale, float step_size, float inv_bc2_sqrt) {
   // every rounding spelled out: the dense kernel and the per-row kernel below must give the same bits (the fused step runs part of the

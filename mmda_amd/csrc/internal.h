@@ -47,15 +47,18 @@ int mmda_embed_dense_adam_presorted(const DenseRowArgs& ad, const unsigned* sort
 
 // ---- optim.hip
 int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      // two buffers cleared by one launch
-// mmda_clamp_adam whose launch does not complete before *wait_flag reaches wait_value
-int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
-                         float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream);
-// frozen parameters: mmda_runs_build that merges no two ranges across one of `cuts`, and mmda_clamp_adam_runs with that waiter
+// The launch behind mmda_clamp_adam, _sum, _runs and _sum_runs: clamp + Adam step h.step over n floats (table == nullptr) or over the
+// trainable runs of a table (n unused), with the gradient g or, acc != nullptr, acc + g.  w.flag != nullptr: the launch does not
+// complete before *w.flag reaches w.value (flag joins, common.h) and goes out even where there is nothing to update.
+struct AdamHyper { float lr, beta1, beta2, eps, clip, grad_scale; int step; };
+struct RunTable { const mmda_run* runs; int n_runs; int64_t items; };
+struct FlagWait { const unsigned* flag; unsigned value; unsigned* err; };
+constexpr FlagWait kNoWait{nullptr, 0u, nullptr};
+int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const RunTable* table, const AdamHyper& h,
+                     const FlagWait& w, void* stream);
+// frozen parameters: mmda_runs_build that merges no two ranges across one of `cuts`
 int64_t mmda_runs_build_cut(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, const int64_t* cuts, int n_cuts,
                             mmda_run* out, int* n_out);
-int mmda_clamp_adam_runs_wait(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
-                              float beta1, float beta2, float eps, float clip, float grad_scale, int step, const unsigned* wait_flag,
-                              unsigned wait_value, unsigned* wait_err, void* stream);
 // SparseAdamArgs from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
 int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
                           float clip, float grad_scale, int step);

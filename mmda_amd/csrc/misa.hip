@@ -660,17 +660,20 @@ int runs_ready(mmda_misa* m, void* stream) {
   m->runs_dirty = 0;
   return MMDA_OK;
 }
-// clamp + Adam over the trainable runs of [lo, hi): the launch a masked step makes where today's makes mmda_clamp_adam[_wait] /
-// mmda_clamp_adam_sum (acc != nullptr) over that range.  A range with nothing to train launches nothing -- but for a waiter.
-int masked_adam(mmda_misa* m, int64_t lo, int64_t hi, const float* acc, float lr, float clip, float grad_scale, int step,
-                const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream) {
+// The model's Adam (the reference gives torch.optim.Adam nothing but lr)
+constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kAdamEps = 1e-8f;
+// clamp + Adam over the bucket range [lo, hi) with the gradient G, or acc + G (acc != nullptr: the accumulator, laid out like the
+// bucket): the dense stream, or -- frozen parameters -- the trainable runs of that range, where a range with nothing to train launches
+// nothing but for a waiter (w.flag != nullptr).
+int bucket_adam(mmda_misa* m, int64_t lo, int64_t hi, const float* acc, float lr, float clip, float grad_scale, int step, const FlagWait& w,
+                void* stream) {
+  const AdamHyper h{lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step};
+  if (!masked(m)) return mmda_adam_launch(m->P + lo, acc ? acc + lo : nullptr, m->G + lo, m->M1 + lo, m->V1 + lo, hi - lo, nullptr, h, w, stream);
   int r0 = 0, n = 0; int64_t items = 0;
   runs_slice(m, lo, hi, &r0, &n, &items);
   if (n > 0 && (m->runs_dirty || !m->runs_dev)) return MMDA_EINVAL;      // (every entry that gets here called runs_ready first)
-  const mmda_run* d = n > 0 ? m->runs_dev + r0 : nullptr;
-  if (acc) return mmda_clamp_adam_sum_runs(m->P, acc, m->G, m->M1, m->V1, d, n, items, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
-  return mmda_clamp_adam_runs_wait(m->P, m->G, m->M1, m->V1, d, n, items, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, wait_flag,
-                                   wait_value, wait_err, stream);
+  const RunTable t{n > 0 ? m->runs_dev + r0 : nullptr, n, items};
+  return mmda_adam_launch(m->P, acc, m->G, m->M1, m->V1, 0, &t, h, w, stream);
 }
 // the table from one flag per parameter (nullptr: everything trains)
 int apply_trainable(mmda_misa* m, const unsigned char* flags) {
@@ -1072,7 +1075,7 @@ extern "C" int mmda_misa_embed_flush(mmda_misa* m, void* stream) {
   if (!m->P || !m->M1 || !m->V1) return MMDA_EINVAL;
   if (m->df_flushed == m->df_seq) return MMDA_OK;          // no update since the last flush: nothing is stale, nothing is launched
   const int rc = mmda_embed_rows_flush(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window,
-                                       m->cfg.d_t, m->cfg.vocab, 0.9f, 0.999f, 1e-8f, m->df_seq, stream);
+                                       m->cfg.d_t, m->cfg.vocab, kBeta1, kBeta2, kAdamEps, m->df_seq, stream);
   if (!rc) m->df_flushed = m->df_seq;
   return rc;
 }
@@ -1501,7 +1504,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   if (m->plan.embed_deferred) {
     if (!m->M1 || !m->V1) return MMDA_EINVAL;
     x.rc = mmda_embed_rows_catch_up(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, t_ids,
-                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, 0.9f, 0.999f, 1e-8f, m->df_seq, stream);
+                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, kBeta1, kBeta2, kAdamEps, m->df_seq, stream);
     if (x.rc) return x.rc;
   }
   const float* xin[3] = {WS(m->mod[0].x), v, a};
@@ -1987,8 +1990,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // use_side is on; otherwise this is simply the same work in front of the recurrence.
     if (!rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
       // (frozen parameters: over the prefix's trainable runs -- the prefix counts as stepped even where none of it trains)
-      rc = masked(m) ? masked_adam(m, 0, m->early_floats, nullptr, m->ae_lr, m->ae_clip, 1.0f, m->ae_step, nullptr, 0u, nullptr, ss)
-                     : mmda_clamp_adam(m->P, m->G, m->M1, m->V1, m->early_floats, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, ss);
+      rc = bucket_adam(m, 0, m->early_floats, nullptr, m->ae_lr, m->ae_clip, 1.0f, m->ae_step, kNoWait, ss);
       if (!rc) m->adam_early_done = m->early_floats;
     }
   } else if (P.embed_update == EU_SPARSE) {
@@ -2001,7 +2003,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     }
     SparseAdamArgs ad;
     rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, m->ae_lr,
-                               0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step);
+                               kBeta1, kBeta2, kAdamEps, m->ae_clip, 1.0f, m->ae_step);
     if (rc) return;
     if (m->esort_valid) {
       if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
@@ -2033,7 +2035,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
       sorted = reinterpret_cast<const unsigned*>(WS(m->esort));
       m->esort_valid = 0;
     }
-    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, 0.9f, 0.999f, 1e-8f, m->ae_clip, 1.0f, m->ae_step, false, s);
+    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, kBeta1, kBeta2, kAdamEps, m->ae_clip, 1.0f, m->ae_step, false, s);
   } else if (P.embed_update == EU_DENSE) {
     // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     if (m->esort_valid) {
@@ -2148,23 +2150,18 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 // =============================================================================================== optimizer / step
 extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
   if (!m || !m->P || !m->G || !m->M1 || !m->V1) return MMDA_EINVAL;
-  int rc = MMDA_OK;
-  if (masked(m)) {                                       // frozen parameters: the trainable runs only
-    rc = runs_ready(m, stream);
-    if (!rc) rc = masked_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, nullptr, 0u, nullptr, stream);
-  } else {
-    rc = mmda_clamp_adam(m->P, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
-  }
+  int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;  // frozen parameters: the trainable runs only
+  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, kNoWait, stream);
   if (!rc && m->embed_update == EU_SPARSE && m->eu_pending) {
     // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
     m->eu_pending = 0;
     if (!m->ws || m->T <= 0) return MMDA_EINVAL;
     rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->eu_ids, m->B * m->T, m->cfg.d_t,
-                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step,
+                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step,
                                      stream);
   }
   if (!rc && m->embed_update == EU_DENSE && m->df_row_step && m->eu_pending)
-    rc = mmda_misa_embed_deferred_step(m, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+    rc = mmda_misa_embed_deferred_step(m, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step, stream);
   return rc;
 }
 
@@ -2200,20 +2197,15 @@ extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, i
                                                int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream) {
   // (everything is checked in front of the dense launch: a refused call changes nothing)
   if (!accum_ready(m) || !m->M1 || !m->V1 || step < 1 || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
-  int rc = MMDA_OK;
-  if (masked(m)) {
-    rc = runs_ready(m, stream);
-    if (!rc) rc = masked_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, nullptr, 0u, nullptr, stream);
-  } else {
-    rc = mmda_clamp_adam_sum(m->P, acc, m->G, m->M1, m->V1, grad_floats(m), lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
-  }
+  int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;
+  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, kNoWait, stream);
   if (!rc && m->embed_update == EU_SPARSE) {
     const int n = (int)(list_used + (int64_t)m->B * m->T);
     rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
     // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
     if (!rc)
       rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, list_ids, n, m->cfg.d_t, list_rows, nullptr, 0,
-                                       m->cfg.vocab, lr, 0.9f, 0.999f, 1e-8f, clip, grad_scale, step, stream);
+                                       m->cfg.vocab, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step, stream);
   }
   return rc;
 }
@@ -2256,12 +2248,8 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
     const bool fj = m->fj2 != 0;
     m->fj2 = 0;
     // (sparse / frozen table: the launch ends in front of it -- and stays the waiter)
-    if (masked(m))
-      rc = masked_adam(m, o, grad_floats(m), nullptr, lr, clip, 1.0f, step, fj ? m->jflags + 1 : nullptr, m->jval[1],
-                       fj ? m->jflags + 2 : nullptr, stream);
-    else
-      rc = mmda_clamp_adam_wait(m->P + o, m->G + o, m->M1 + o, m->V1 + o, grad_floats(m) - o, lr, 0.9f, 0.999f, 1e-8f, clip, 1.0f, step,
-                                fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr, stream);
+    rc = bucket_adam(m, o, grad_floats(m), nullptr, lr, clip, 1.0f, step,
+                     FlagWait{fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr}, stream);
   }
   return rc;
 }

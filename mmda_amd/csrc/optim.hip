@@ -1,40 +1,122 @@
-// clip_grad_value_ + Adam fused over one flat fp32 bucket (reference solver.py:185-186 and :97-99: torch.optim.Adam with
-// lr only -> betas (0.9, 0.999), eps 1e-8, no weight decay; --weight_decay is parsed but never used).  Pure HBM stream:
-// reads p,g,m,v and writes p,m,v = 28 B per parameter, float4 per lane.
+// clip_grad_value_ + the optimizer's update fused over flat fp32 buckets (reference solver.py:185-186 and :97-99: torch.optim.Adam
+// with lr only -> betas (0.9, 0.999), eps 1e-8, no weight decay; --weight_decay is parsed but never used).  An update rule is an
+// element functor, a memory layout is a walker kernel that takes one; a launch is a walker instantiated with a rule.
 #include "common.h"
 #include "internal.h"
 #include <math.h>
 
 namespace {
 
-// wait_flag != nullptr (flag join, common.h): workgroup 0 does not finish before that word reaches wait_value -- so the completion of this
-// launch on its stream implies the completion of the other stream's chain (the update itself does not depend on it).
-__global__ __launch_bounds__(256) void clamp_adam_kernel(float* p, const float* __restrict__ g, float* m, float* v, int64_t n,
-                                                         float b1, float b2, float eps, float clip, float gscale,
-                                                         float step_size, float inv_bc2_sqrt, const unsigned* wait_flag,
-                                                         unsigned wait_value, unsigned* wait_err) {
-  const int64_t n4 = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float4* p4 = reinterpret_cast<float4*>(p);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+// ---- the update rules: one element functor per rule
+// quad(q): the rule over floats 4 q .. 4 q + 3 of the flat buffers, with 16-byte accesses (every base is 16-byte aligned); one(e): over
+// float e.  Which quads and floats a launch takes is the walker's business (below), so every launch of a rule gives an element the same
+// bits, whatever layout it is reached through.
+// clip_grad_value_ + Adam (adam1(), common.h).  kSum: the gradient is acc + g, one IEEE add -- the closing step of an accumulated update
+// reads the last micro-batch's gradients where the backward pass left them, instead of adding them into the accumulator first and
+// reading that back: the bits of "accumulate, then Adam over the accumulator".  Neither acc nor g is written.
+struct AdamArgs { float* p; const float* acc; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt; };
+template <bool kSum>
+struct Adam : AdamArgs {
+  __device__ __forceinline__ void quad(int64_t q) const {
+    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
+    float4 gg = reinterpret_cast<const float4*>(g)[q];
+    if constexpr (kSum) {
+      const float4 aa = reinterpret_cast<const float4*>(acc)[q];
+      gg.x = __fadd_rn(aa.x, gg.x); gg.y = __fadd_rn(aa.y, gg.y); gg.z = __fadd_rn(aa.z, gg.z); gg.w = __fadd_rn(aa.w, gg.w);
+    }
     adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
     adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
     adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
     adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
   }
-  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride)
-    adam1(p[i], g[i], m[i], v[i], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+  __device__ __forceinline__ void one(int64_t e) const {
+    float ge = g[e];
+    if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
+    adam1(p[e], ge, m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+  }
+};
+struct RunRmsprop {         // clamp_rmsprop_kernel's (below: the dense launch keeps its one-float-per-lane loop)
+  float* p; const float* g; float* sq; float lr, alpha, eps, clip, gscale;
+  // That kernel leaves contraction to the compiler, which forms no fma in its loop; the same statements unrolled over a quad here did
+  // get one (alpha * sq + ...) and lost the dense launch's bits.  So: the operations its code performs, in its order, with contraction
+  // off for this block -- on plain operators: __fadd_rn / __fmul_rn are functions of a header compiled with contraction on, and what
+  // they return is fused all the same.  tests/test_gpu_frozen.py holds the two launches together.
+  __device__ __forceinline__ void one(int64_t i) const {
+#pragma clang fp contract(off)
+    const float gg = fminf(fmaxf(g[i] * gscale, -clip), clip);
+    const float old = alpha * sq[i];
+    const float add = ((1.0f - alpha) * gg) * gg;
+    const float s = old + add;
+    sq[i] = s;
+    const float num = lr * gg;
+    const float den = sqrtf(s) + eps;
+    p[i] = p[i] - num / den;
+  }
+  __device__ __forceinline__ void quad(int64_t q) const {
+    for (int k = 0; k < 4; ++k) one((q << 2) + k);
+  }
+};
+
+// ---- the walkers: one per memory layout
+// Dense stream over n floats: 16 bytes per lane, a scalar tail.  Pure HBM traffic (Adam: reads p, g, m, v and writes p, m, v = 28 B per
+// parameter).  wait_flag != nullptr (flag join, common.h): workgroup 0 does not finish before that word reaches wait_value -- so the
+// completion of this launch on its stream implies the completion of the other stream's chain (the update itself does not depend on it).
+template <class F>
+__global__ __launch_bounds__(256) void stream_kernel(int64_t n, F f, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) f.quad(i);
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) f.one(i);
+  if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
+}
+
+// The ROWS of a (rows, dim) table whose mask byte equals `want`; vec: dim % 4 == 0 and 16-byte aligned bases, so every row is whole quads
+// (launch-uniform).  The embedding matrix is 6 of the model's 10.8 M parameters and a step touches at most T*B of its V rows: the rows a
+// batch does not touch have a zero gradient that is known before the backward pass ends, so their update runs early, beside the last
+// recurrence (mask 0), and only the touched rows wait for the scattered gradient (mask 1).  One wave per row, lanes along the row.
+template <class F>
+__global__ __launch_bounds__(256) void rows_kernel(int rows, int dim, const unsigned char* __restrict__ mask, int want, int vec, F f) {
+  const int lane = threadIdx.x & 63;
+  const int wpg = (int)gridDim.x * 4;
+  for (int row = (int)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += wpg) {
+    if ((int)mask[row] != want) continue;                // wave-uniform
+    const int64_t o = (int64_t)row * dim;
+    if (vec) for (int i = lane; i < (dim >> 2); i += 64) f.quad((o >> 2) + i);
+    else for (int i = lane; i < dim; i += 64) f.one(o + i);
+  }
+}
+
+// The TRAINABLE RUNS of a bucket (frozen parameters, requires_grad = False; mmda_hip.h: mmda_run).
+// A work item is one 16-byte aligned quad of the bucket that a run touches; the grid is sized by the items, and item j of the launch
+// finds its run by bisection over the runs' running counts (a few hundred entries at the most, read by every lane: they stay in
+// cache).  A quad that lies inside its run goes through quad() like the dense stream's; a quad at a run's end takes the floats of the
+// run one by one, so no float outside a run is loaded or stored -- two runs that share a quad touch disjoint floats of it.  wait_flag:
+// as in stream_kernel (the same flag_wait).
+template <class F>
+__global__ __launch_bounds__(256) void runs_kernel(const mmda_run* __restrict__ runs, int n_runs, int64_t items, F f,
+                                                   const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t item0 = n_runs > 0 ? runs[0].first : 0;          // (a slice of a longer table: counts run on from its start)
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
+    const int64_t j = item0 + i;
+    int lo = 0, hi = n_runs - 1;                                   // the last run whose count is <= j
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (runs[mid].first <= j) lo = mid; else hi = mid - 1;
+    }
+    const mmda_run r = runs[lo];
+    const int64_t q = (r.begin >> 2) + (j - r.first);              // the bucket's quad
+    const int64_t e0 = max(q << 2, r.begin), e1 = min((q << 2) + 4, r.begin + r.len);
+    if (e1 - e0 == 4) f.quad(q);
+    else for (int64_t e = e0; e < e1; ++e) f.one(e);
+  }
   if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
 }
 
 // ---- gradient accumulation (accum_steps > 1): one optimizer step from the gradients of several micro-batches
 // acc = g (first: a plain copy, so the accumulator never needs clearing) or acc = acc + g, one IEEE add per element.  Pure HBM stream:
-// float4 per lane, scalar tail, the shape of clamp_adam_kernel.
+// float4 per lane, scalar tail, the shape of stream_kernel.
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* acc, const float* __restrict__ g, int64_t n, int first) {
   const int64_t n4 = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -52,32 +134,6 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* acc, const 
     a4[i] = aa;
   }
   for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) acc[i] = __fadd_rn(acc[i], g[i]);
-}
-
-// clamp_adam_kernel on the sum acc + g: the closing step of an accumulated update reads the last micro-batch's gradients where the
-// backward pass left them, instead of adding them into the accumulator first and reading that back.  The same add, then the same
-// adam1(): the bits of "accumulate, then clamp_adam_kernel over the accumulator".  Neither acc nor g is written.
-__global__ __launch_bounds__(256) void clamp_adam_sum_kernel(float* p, const float* __restrict__ acc, const float* __restrict__ g, float* m,
-                                                             float* v, int64_t n, float b1, float b2, float eps, float clip, float gscale,
-                                                             float step_size, float inv_bc2_sqrt) {
-  const int64_t n4 = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float4* p4 = reinterpret_cast<float4*>(p);
-  const float4* a4 = reinterpret_cast<const float4*>(acc);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pp = p4[i], mm = m4[i], vv = v4[i];
-    const float4 aa = a4[i], gg = g4[i];
-    adam1(pp.x, __fadd_rn(aa.x, gg.x), mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.y, __fadd_rn(aa.y, gg.y), mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.z, __fadd_rn(aa.z, gg.z), mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.w, __fadd_rn(aa.w, gg.w), mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    p4[i] = pp; m4[i] = mm; v4[i] = vv;
-  }
-  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride)
-    adam1(p[i], __fadd_rn(acc[i], g[i]), m[i], v[i], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
 }
 
 // embed_update = sparse under accumulation: a micro-batch's n = T B gradient rows (width D) and ids, appended at position `offset` of a
@@ -100,37 +156,6 @@ __global__ __launch_bounds__(256) void embed_rows_append_kernel(int64_t* ids_out
   for (int64_t p = i0; p < n; p += stride) {
     const bool pad = lengths != nullptr && (int)(p / B) >= lengths[p % B];
     ids_out[offset + p] = pad ? (int64_t)-1 : ids[p];
-  }
-}
-
-// The same update over the ROWS of a (rows, dim) table whose mask byte equals `want` (dim % 4 == 0 or not: scalar tail per row).
-// The embedding matrix is 6 of the model's 10.8 M parameters and a step touches at most T*B of its V rows: the rows a batch does not
-// touch have a zero gradient that is known before the backward pass ends, so their update runs early, beside the last recurrence
-// (mask 0), and only the touched rows wait for the scattered gradient (mask 1).  One wave per row, lanes along the row.
-__global__ __launch_bounds__(256) void clamp_adam_rows_kernel(float* p, const float* __restrict__ g, float* m, float* v, int rows, int dim,
-                                                              const unsigned char* __restrict__ mask, int want, float b1, float b2,
-                                                              float eps, float clip, float gscale, float step_size, float inv_bc2_sqrt) {
-  const int lane = threadIdx.x & 63;
-  const int wpg = (int)gridDim.x * 4;
-  for (int row = (int)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += wpg) {
-    if ((int)mask[row] != want) continue;                // wave-uniform
-    const int64_t o = (int64_t)row * dim;
-    if ((dim & 3) == 0 && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) {      // launch-uniform
-      float4* p4 = reinterpret_cast<float4*>(p + o);
-      const float4* g4 = reinterpret_cast<const float4*>(g + o);
-      float4* m4 = reinterpret_cast<float4*>(m + o);
-      float4* v4 = reinterpret_cast<float4*>(v + o);
-      for (int i = lane; i < (dim >> 2); i += 64) {
-        float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-        adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-        adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-        adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-        adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-      }
-    } else {
-      for (int i = lane; i < dim; i += 64) adam1(p[o + i], g[o + i], m[o + i], v[o + i], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    }
   }
 }
 
@@ -215,96 +240,6 @@ __global__ __launch_bounds__(256) void clamp_rmsprop_kernel(float* p, const floa
   }
 }
 
-// ---- frozen parameters (requires_grad = False): clamp + update over the TRAINABLE RUNS of a bucket (mmda_hip.h: mmda_run)
-// A work item is one 16-byte aligned quad of the bucket that a run touches; the grid is sized by the items, and item j of the launch
-// finds its run by bisection over the runs' running counts (a few hundred entries at the most, read by every lane: they stay in
-// cache).  A quad that lies inside its run goes through 16-byte accesses like the dense kernels'; a quad at a run's end takes the
-// floats of the run one by one, so no float outside a run is loaded or stored -- two runs that share a quad touch disjoint floats of
-// it.  F: one element / one quad of an update, with the arithmetic of the dense kernel it stands in for.  wait_flag: as in
-// clamp_adam_kernel (the same flag_wait).
-template <class F>
-__global__ __launch_bounds__(256) void runs_kernel(const mmda_run* __restrict__ runs, int n_runs, int64_t items, F f,
-                                                   const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t item0 = n_runs > 0 ? runs[0].first : 0;          // (a slice of a longer table: counts run on from its start)
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
-    const int64_t j = item0 + i;
-    int lo = 0, hi = n_runs - 1;                                   // the last run whose count is <= j
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (runs[mid].first <= j) lo = mid; else hi = mid - 1;
-    }
-    const mmda_run r = runs[lo];
-    const int64_t q = (r.begin >> 2) + (j - r.first);              // the bucket's quad
-    const int64_t e0 = max(q << 2, r.begin), e1 = min((q << 2) + 4, r.begin + r.len);
-    if (e1 - e0 == 4) f.quad(q);
-    else for (int64_t e = e0; e < e1; ++e) f.one(e);
-  }
-  if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
-}
-
-struct RunAdam {            // clamp_adam_kernel's update
-  float* p; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt;
-  __device__ __forceinline__ void quad(int64_t q) const {
-    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
-    const float4 gg = reinterpret_cast<const float4*>(g)[q];
-    adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
-  }
-  __device__ __forceinline__ void one(int64_t e) const { adam1(p[e], g[e], m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt); }
-};
-struct RunAdamSum {         // clamp_adam_sum_kernel's: the gradient is acc + g, neither is written
-  float* p; const float* acc; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt;
-  __device__ __forceinline__ void quad(int64_t q) const {
-    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
-    const float4 aa = reinterpret_cast<const float4*>(acc)[q], gg = reinterpret_cast<const float4*>(g)[q];
-    adam1(pp.x, __fadd_rn(aa.x, gg.x), mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.y, __fadd_rn(aa.y, gg.y), mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.z, __fadd_rn(aa.z, gg.z), mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.w, __fadd_rn(aa.w, gg.w), mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
-  }
-  __device__ __forceinline__ void one(int64_t e) const {
-    adam1(p[e], __fadd_rn(acc[e], g[e]), m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-  }
-};
-struct RunRmsprop {         // clamp_rmsprop_kernel's
-  float* p; const float* g; float* sq; float lr, alpha, eps, clip, gscale;
-  // That kernel leaves contraction to the compiler, which forms no fma in its loop; the same statements unrolled over a quad here did
-  // get one (alpha * sq + ...) and lost the dense launch's bits.  So: the operations its code performs, in its order, with contraction
-  // off for this block -- on plain operators: __fadd_rn / __fmul_rn are functions of a header compiled with contraction on, and what
-  // they return is fused all the same.  tests/test_gpu_frozen.py holds the two launches together.
-  __device__ __forceinline__ void one(int64_t i) const {
-#pragma clang fp contract(off)
-    const float gg = fminf(fmaxf(g[i] * gscale, -clip), clip);
-    const float old = alpha * sq[i];
-    const float add = ((1.0f - alpha) * gg) * gg;
-    const float s = old + add;
-    sq[i] = s;
-    const float num = lr * gg;
-    const float den = sqrtf(s) + eps;
-    p[i] = p[i] - num / den;
-  }
-  __device__ __forceinline__ void quad(int64_t q) const {
-    for (int k = 0; k < 4; ++k) one((q << 2) + k);
-  }
-};
-
-template <class F>
-int launch_runs(const char* what, const mmda_run* runs, int n_runs, int64_t items, const F& f, const unsigned* wait_flag,
-                unsigned wait_value, unsigned* wait_err, void* stream) {
-  int64_t blocks = (items + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(runs_kernel<F>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, runs, n_runs, items, f, wait_flag, wait_value,
-                     wait_err);
-  MMDA_CHECK_LAUNCH(what);
-  return MMDA_OK;
-}
-
 // two buffers cleared by one launch (16-byte stores; counts in floats, multiples of 4, 16-byte aligned bases)
 __global__ __launch_bounds__(256) void zero2_kernel(float4* a, int64_t na4, float4* b, int64_t nb4) {
   const float4 z = {0.f, 0.f, 0.f, 0.f};
@@ -320,60 +255,80 @@ __global__ void clamp_kernel(float* g, int64_t n, float clip) {
     g[i] = fminf(fmaxf(g[i], -clip), clip);
 }
 
+// ---- host side: what every launcher below shares
+// blocks of 256 lanes for a grid-stride loop over `work` items
+int stream_blocks(int64_t work) {
+  const int64_t blocks = (work + 255) / 256;
+  return (int)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks);
+}
+
+// Adam's bias corrections 1 - beta^t, and from them the two scalars every dense launch of step t is given: lr / (1 - b1^t) and
+// 1 / sqrt(1 - b2^t), in double, rounded once
+struct BiasCorrections { double bc1, bc2; };
+BiasCorrections bias_corrections(float beta1, float beta2, int step) {
+  return {1.0 - pow((double)beta1, (double)step), 1.0 - pow((double)beta2, (double)step)};
+}
+struct AdamStepScalars { float step_size, inv_bc2_sqrt; };
+AdamStepScalars adam_step_scalars(float lr, float beta1, float beta2, int step) {
+  const BiasCorrections c = bias_corrections(beta1, beta2, step);
+  return {(float)((double)lr / c.bc1), (float)(1.0 / sqrt(c.bc2))};
+}
+AdamArgs adam_args(float* p, const float* acc, const float* g, float* m, float* v, const AdamHyper& h) {
+  const AdamStepScalars s = adam_step_scalars(h.lr, h.beta1, h.beta2, h.step);
+  return {p, acc, g, m, v, h.beta1, h.beta2, h.eps, h.clip, h.grad_scale, s.step_size, s.inv_bc2_sqrt};
+}
+
+template <class F>
+int launch_stream(const char* what, int64_t n, const F& f, const FlagWait& w, void* stream) {
+  hipLaunchKernelGGL(stream_kernel<F>, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, n, f, w.flag, w.value, w.err);
+  MMDA_CHECK_LAUNCH(what);
+  return MMDA_OK;
+}
+template <class F>
+int launch_runs(const char* what, const RunTable& t, const F& f, const FlagWait& w, void* stream) {
+  hipLaunchKernelGGL(runs_kernel<F>, dim3(stream_blocks(t.items)), dim3(256), 0, (hipStream_t)stream, t.runs, t.n_runs, t.items, f, w.flag,
+                     w.value, w.err);
+  MMDA_CHECK_LAUNCH(what);
+  return MMDA_OK;
+}
+
 }  // namespace
+
+// internal.h: the launch behind every mmda_clamp_adam* entry (and misa.hip's).  A waiter with nothing to update gets the dense stream
+// over no floats.
+int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const RunTable* table, const AdamHyper& h,
+                     const FlagWait& w, void* stream) {
+  if (!p || !g || !m || !v || h.step < 1) return MMDA_EINVAL;
+  if (table ? (table->n_runs < 0 || table->items < 0) : n < 0) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // 16-byte quads
+  const bool empty = table ? (table->n_runs == 0 || table->items == 0) : n == 0;
+  if (empty && !w.flag) return MMDA_OK;
+  if (table && !empty && !table->runs) return MMDA_EINVAL;
+  const char* what = table ? (acc ? "mmda_clamp_adam_sum_runs" : "mmda_clamp_adam_runs") : (acc ? "mmda_clamp_adam_sum" : "mmda_clamp_adam");
+  const AdamArgs a = adam_args(p, acc, g, m, v, h);
+  auto launch = [&](const auto& f) {
+    return table && !empty ? launch_runs(what, *table, f, w, stream) : launch_stream(what, empty ? 0 : n, f, w, stream);
+  };
+  return acc ? launch(Adam<true>{a}) : launch(Adam<false>{a});
+}
 
 extern "C" int mmda_clamp_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                                float eps, float clip, float grad_scale, int step, void* stream) {
-  return mmda_clamp_adam_wait(p, g, m, v, n, lr, beta1, beta2, eps, clip, grad_scale, step, nullptr, 0u, nullptr, stream);
+  return mmda_adam_launch(p, nullptr, g, m, v, n, nullptr, AdamHyper{lr, beta1, beta2, eps, clip, grad_scale, step}, kNoWait, stream);
 }
 
-// internal (misa.hip): the same launch, not complete before *wait_flag reaches wait_value (see clamp_adam_kernel)
-int mmda_clamp_adam_wait(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
-                         float grad_scale, int step, const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err, void* stream) {
-  if (!p || !g || !m || !v || n < 0 || step < 1) return MMDA_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // float4 path
-  if (n == 0 && !wait_flag) return MMDA_OK;
-  double bc1 = 1.0 - pow((double)beta1, (double)step);
-  double bc2 = 1.0 - pow((double)beta2, (double)step);
-  float step_size = (float)((double)lr / bc1);
-  float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  int64_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(clamp_adam_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, beta1, beta2, eps, clip,
-                     grad_scale, step_size, inv_bc2_sqrt, wait_flag, wait_value, wait_err);
-  MMDA_CHECK_LAUNCH("mmda_clamp_adam");
-  return MMDA_OK;
+// acc == nullptr (one micro-batch: no sum): mmda_clamp_adam
+extern "C" int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
+  return mmda_adam_launch(p, acc, g, m, v, n, nullptr, AdamHyper{lr, beta1, beta2, eps, clip, grad_scale, step}, kNoWait, stream);
 }
 
 extern "C" int mmda_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
   if (!acc || !g || n < 0) return MMDA_EINVAL;
   if (((uintptr_t)acc | (uintptr_t)g) & 15) return MMDA_EINVAL;                                // float4 path
   if (n == 0) return MMDA_OK;
-  int64_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(grad_accumulate_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, acc, g, n, first ? 1 : 0);
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, acc, g, n, first ? 1 : 0);
   MMDA_CHECK_LAUNCH("mmda_grad_accumulate");
-  return MMDA_OK;
-}
-
-extern "C" int mmda_clamp_adam_sum(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
-                                   float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
-  if (!acc) return mmda_clamp_adam(p, g, m, v, n, lr, beta1, beta2, eps, clip, grad_scale, step, stream);   // one micro-batch: no sum
-  if (!p || !g || !m || !v || n < 0 || step < 1) return MMDA_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // float4 path
-  if (n == 0) return MMDA_OK;
-  double bc1 = 1.0 - pow((double)beta1, (double)step);
-  double bc2 = 1.0 - pow((double)beta2, (double)step);
-  float step_size = (float)((double)lr / bc1);
-  float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  int64_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(clamp_adam_sum_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, acc, g, m, v, n, beta1, beta2, eps,
-                     clip, grad_scale, step_size, inv_bc2_sqrt);
-  MMDA_CHECK_LAUNCH("mmda_clamp_adam_sum");
   return MMDA_OK;
 }
 
@@ -409,41 +364,18 @@ extern "C" int64_t mmda_runs_build(const int64_t* begin, const int64_t* len, int
   return mmda_runs_build_cut(begin, len, n, bucket_floats, nullptr, 0, out, n_out);
 }
 
-// internal (misa.hip): mmda_clamp_adam_runs whose launch does not complete before *wait_flag reaches wait_value -- clamp_adam_kernel's
-// waiter; with nothing to update, that kernel itself over no floats
-int mmda_clamp_adam_runs_wait(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
-                              float beta1, float beta2, float eps, float clip, float grad_scale, int step, const unsigned* wait_flag,
-                              unsigned wait_value, unsigned* wait_err, void* stream) {
-  if (!p || !g || !m || !v || n_runs < 0 || items < 0 || step < 1) return MMDA_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;   // 16-byte quads
-  if (n_runs == 0 || items == 0)
-    return wait_flag ? mmda_clamp_adam_wait(p, g, m, v, 0, lr, beta1, beta2, eps, clip, grad_scale, step, wait_flag, wait_value, wait_err, stream)
-                     : MMDA_OK;
-  if (!runs) return MMDA_EINVAL;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const RunAdam f{p, g, m, v, beta1, beta2, eps, clip, grad_scale, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
-  return launch_runs("mmda_clamp_adam_runs", runs, n_runs, items, f, wait_flag, wait_value, wait_err, stream);
-}
-
 extern "C" int mmda_clamp_adam_runs(float* p, const float* g, float* m, float* v, const mmda_run* runs, int n_runs, int64_t items, float lr,
                                     float beta1, float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
-  return mmda_clamp_adam_runs_wait(p, g, m, v, runs, n_runs, items, lr, beta1, beta2, eps, clip, grad_scale, step, nullptr, 0u, nullptr,
-                                   stream);
+  const RunTable t{runs, n_runs, items};
+  return mmda_adam_launch(p, nullptr, g, m, v, 0, &t, AdamHyper{lr, beta1, beta2, eps, clip, grad_scale, step}, kNoWait, stream);
 }
 
+// acc == nullptr: mmda_clamp_adam_runs
 extern "C" int mmda_clamp_adam_sum_runs(float* p, const float* acc, const float* g, float* m, float* v, const mmda_run* runs, int n_runs,
                                         int64_t items, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
                                         void* stream) {
-  if (!acc) return mmda_clamp_adam_runs(p, g, m, v, runs, n_runs, items, lr, beta1, beta2, eps, clip, grad_scale, step, stream);
-  if (!p || !g || !m || !v || n_runs < 0 || items < 0 || step < 1) return MMDA_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)acc | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;
-  if (n_runs == 0 || items == 0) return MMDA_OK;
-  if (!runs) return MMDA_EINVAL;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const RunAdamSum f{p, acc, g, m, v, beta1, beta2, eps, clip, grad_scale, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
-  return launch_runs("mmda_clamp_adam_sum_runs", runs, n_runs, items, f, nullptr, 0u, nullptr, stream);
+  const RunTable t{runs, n_runs, items};
+  return mmda_adam_launch(p, acc, g, m, v, 0, &t, AdamHyper{lr, beta1, beta2, eps, clip, grad_scale, step}, kNoWait, stream);
 }
 
 extern "C" int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_avg, const mmda_run* runs, int n_runs, int64_t items,
@@ -452,7 +384,7 @@ extern "C" int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_a
   if (n_runs == 0 || items == 0) return MMDA_OK;
   if (!runs) return MMDA_EINVAL;
   const RunRmsprop f{p, g, square_avg, lr, alpha, eps, clip, grad_scale};
-  return launch_runs("mmda_clamp_rmsprop_runs", runs, n_runs, items, f, nullptr, 0u, nullptr, stream);
+  return launch_runs("mmda_clamp_rmsprop_runs", RunTable{runs, n_runs, items}, f, kNoWait, stream);
 }
 
 extern "C" int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids,
@@ -463,10 +395,7 @@ extern "C" int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t
   if (n == 0) return MMDA_OK;
   const int vec = (D & 3) == 0 && (((uintptr_t)rows_out | (uintptr_t)rows) & 15) == 0;
   const int64_t work = vec ? ((int64_t)n * D) >> 2 : (int64_t)n * D;
-  int64_t blocks = (work + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(embed_rows_append_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ids_out, rows_out, offset, ids, rows, n,
+  hipLaunchKernelGGL(embed_rows_append_kernel, dim3(stream_blocks(work)), dim3(256), 0, (hipStream_t)stream, ids_out, rows_out, offset, ids, rows, n,
                      D, lengths, B, vec);
   MMDA_CHECK_LAUNCH("mmda_embed_rows_append");
   return MMDA_OK;
@@ -482,9 +411,7 @@ int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream) {
   }
   const int64_t n4 = (na + nb) >> 2;
   if (n4 == 0) return MMDA_OK;
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(zero2_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(a), na >> 2,
+  hipLaunchKernelGGL(zero2_kernel, dim3(stream_blocks(n4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(a), na >> 2,
                      reinterpret_cast<float4*>(b), nb >> 2);
   MMDA_CHECK_LAUNCH("mmda_zero2");
   return MMDA_OK;
@@ -503,14 +430,11 @@ extern "C" int mmda_clamp_adam_rows(float* p, const float* g, float* m, float* v
                                     float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step, void* stream) {
   if (!p || !g || !m || !v || !mask || rows < 0 || dim <= 0 || step < 1) return MMDA_EINVAL;
   if (rows == 0) return MMDA_OK;
-  double bc1 = 1.0 - pow((double)beta1, (double)step);
-  double bc2 = 1.0 - pow((double)beta2, (double)step);
-  float step_size = (float)((double)lr / bc1);
-  float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  const Adam<false> f{adam_args(p, nullptr, g, m, v, AdamHyper{lr, beta1, beta2, eps, clip, grad_scale, step})};
+  const int vec = (dim & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
   int blocks = (rows + 3) / 4;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(clamp_adam_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rows, dim, mask, want, beta1,
-                     beta2, eps, clip, grad_scale, step_size, inv_bc2_sqrt);
+  hipLaunchKernelGGL(rows_kernel<Adam<false>>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, dim, mask, want, vec, f);
   MMDA_CHECK_LAUNCH("mmda_clamp_adam_rows");
   return MMDA_OK;
 }
@@ -520,9 +444,8 @@ extern "C" int mmda_clamp_adam_rows(float* p, const float* g, float* m, float* v
 int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
                           float clip, float grad_scale, int step) {
   if (!out || !P || !M || !V || table_rows <= 0 || step < 1) return MMDA_EINVAL;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  *out = SparseAdamArgs{P, M, V, table_rows, beta1, beta2, eps, clip, grad_scale, (float)((double)lr * sqrt(bc2) / bc1)};
+  const BiasCorrections c = bias_corrections(beta1, beta2, step);
+  *out = SparseAdamArgs{P, M, V, table_rows, beta1, beta2, eps, clip, grad_scale, (float)((double)lr * sqrt(c.bc2) / c.bc1)};
   return MMDA_OK;
 }
 
@@ -588,10 +511,9 @@ int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step,
   if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || !ids || !rows || n < 0 || (lengths && B <= 0) ||
       step < 1 || seq < 1)
     return MMDA_EINVAL;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const DenseRowArgs ad{P, M, V, row_step, step_scalars, window, table_rows, beta1, beta2, eps, clip, grad_scale,
-                        (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), seq};         // the dense launch's two scalars
+  const AdamStepScalars sc = adam_step_scalars(lr, beta1, beta2, step);                      // the dense launch's two scalars
+  const DenseRowArgs ad{P, M, V, row_step, step_scalars, window, table_rows, beta1, beta2, eps, clip, grad_scale, sc.step_size,
+                        sc.inv_bc2_sqrt, seq};
   int rc = MMDA_OK;
   if (seq % window == 0)
     rc = mmda_embed_rows_flush(P, M, V, row_step, step_scalars, window, D, table_rows, beta1, beta2, eps, seq - 1, stream);
@@ -620,9 +542,7 @@ extern "C" int mmda_embed_rows_dense_adam(float* P, float* M, float* V, int32_t*
 extern "C" int mmda_clamp(float* g, int64_t n, float clip, void* stream) {
   if (!g || n < 0) return MMDA_EINVAL;
   if (n == 0) return MMDA_OK;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(clamp_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, g, n, clip);
+  hipLaunchKernelGGL(clamp_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, n, clip);
   MMDA_CHECK_LAUNCH("mmda_clamp");
   return MMDA_OK;
 }
@@ -631,10 +551,8 @@ extern "C" int mmda_clamp_rmsprop(float* p, const float* g, float* square_avg, i
                                   float grad_scale, void* stream) {
   if (!p || !g || !square_avg || n < 0) return MMDA_EINVAL;
   if (n == 0) return MMDA_OK;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(clamp_rmsprop_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, n, lr, alpha, eps, clip,
-                     grad_scale);
+  hipLaunchKernelGGL(clamp_rmsprop_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, n, lr, alpha, eps,
+                     clip, grad_scale);
   MMDA_CHECK_LAUNCH("mmda_clamp_rmsprop");
   return MMDA_OK;
 }
