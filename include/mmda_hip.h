@@ -711,6 +711,33 @@ int mmda_collate_gather(const int32_t* words, const float* visual, const float* 
                         const float* sentiment, const int32_t* order, int B, int T, int dv, int da, int pad_id, int64_t* out_ids,
                         float* out_v, float* out_a, float* out_emo, float* out_y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- inference pass
+ * What one evaluation forward left in the workspace, copied into per-SAMPLE result tables in ONE launch per batch (mmda_amd/inference.py:
+ * InferencePass).  The reference only names the pass: src/inference.py is a TODO, utils/tools.py save_hidden / load_hidden want the
+ * per-sample h, models.py:159 asks how to extract the attention scores.
+ * src: the batch, B columns.  scores, labels (B, ncls); tcp (B, 6); hfused (B, 6 hs), row b = h = cat(h[0..5], dim=1) of column b
+ *   (LayerNorm 2 writes it permuted, the head GEMM reads it so); x6 (6, B, hs) = [private t, v, a, shared t, v, a]; probs
+ *   (B, nhead, 6, 6), the softmax rows before attention dropout (mmda_attn_fwd writes them in every mode).
+ * out: tables of n rows, each may be NULL (skipped).  scores, labels (n, ncls); tcp (n, 6); hidden (n, 6 hs) = the hfused row;
+ *   utterance (n, 6, hs): [r][k] = x6[k][b]; attention (n, 6, 6): the heads of probs summed in head order in fp32 and divided by
+ *   nhead -- what nn.MultiheadAttention(need_weights=True) returns.
+ * Column b goes to row dst[b] (int32, device), or to row base + b when dst is NULL.  NOTHING checks the rows: the caller guarantees
+ * that they lie inside the tables and are distinct within a launch (as for mmda_collate_gather's order).  Offsets are 64-bit.  Rows
+ * whose width is a multiple of four floats move as 16-byte accesses when both bases are 16-byte aligned, everything else as 4-byte ones.
+ * MMDA_EINVAL, with nothing launched: src or out NULL, every table NULL, B <= 0, ncls / hs / nhead <= 0, or a table whose source
+ * pointer is NULL.
+ * mmda_misa_infer_collect: the same with src taken from the model's current workspace carve, B columns of its last forward; MMDA_EINVAL
+ * also when the model has no workspace. */
+typedef struct mmda_infer_src {
+  const float* scores; const float* labels; const float* tcp; const float* hfused; const float* x6; const float* probs;
+  int ncls, hs, nhead;
+} mmda_infer_src;
+typedef struct mmda_infer_out {
+  float* scores; float* labels; float* tcp; float* hidden; float* utterance; float* attention;
+} mmda_infer_out;
+int mmda_infer_collect(const mmda_infer_src* src, const mmda_infer_out* out, const int32_t* dst, int64_t base, int B, void* stream);
+int mmda_misa_infer_collect(mmda_misa* m, const mmda_infer_out* out, const int32_t* dst, int64_t base, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

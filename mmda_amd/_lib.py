@@ -118,6 +118,18 @@ class Run(C.Structure):
     _fields_ = [("begin", C.c_int64), ("len", C.c_int64), ("first", C.c_int64)]
 
 
+class InferSrc(C.Structure):
+    """mmda_infer_src: what a forward left in the workspace, B columns"""
+    _fields_ = [("scores", C.c_void_p), ("labels", C.c_void_p), ("tcp", C.c_void_p), ("hfused", C.c_void_p), ("x6", C.c_void_p),
+                ("probs", C.c_void_p), ("ncls", C.c_int), ("hs", C.c_int), ("nhead", C.c_int)]
+
+
+class InferOut(C.Structure):
+    """mmda_infer_out: the result tables of an inference pass, one row per sample (None = not collected)"""
+    _fields_ = [("scores", C.c_void_p), ("labels", C.c_void_p), ("tcp", C.c_void_p), ("hidden", C.c_void_p), ("utterance", C.c_void_p),
+                ("attention", C.c_void_p)]
+
+
 CELL = {"lstm": 0, "gru": 1}
 
 # name -> (restype, argtypes).  Every symbol include/mmda_hip.h declares appears here (tests/test_abi.py checks it).
@@ -246,6 +258,8 @@ SIGNATURES = {
     "mmda_misa_timing_end": (_I, [_P]),
     "mmda_misa_train_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _U64, _I, _F, _F, _I, _P]),
     "mmda_collate_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mmda_infer_collect": (_I, [C.POINTER(InferSrc), C.POINTER(InferOut), _P, _I64, _I, _P]),
+    "mmda_misa_infer_collect": (_I, [_P, C.POINTER(InferOut), _P, _I64, _P]),
 }
 
 _lib = None

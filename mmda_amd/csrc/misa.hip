@@ -2253,3 +2253,14 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   }
   return rc;
 }
+
+// The inference pass's collect launch (infer.hip) on the model's own workspace: the sources are where the last forward of the current
+// (B, T) carve left them, in the layouts that launch's comment states.
+extern "C" int mmda_misa_infer_collect(mmda_misa* m, const mmda_infer_out* out, const int32_t* dst, int64_t base, void* stream) {
+  if (!m || !out || !m->ws || m->B <= 0) return MMDA_EINVAL;
+  mmda_infer_src src = {};
+  src.scores = WS(m->scores); src.labels = WS(m->labels); src.tcp = WS(m->tcp); src.hfused = WS(m->hfused); src.x6 = WS(m->x6);
+  src.probs = WS(m->probs);
+  src.ncls = m->cfg.ncls; src.hs = m->cfg.hidden; src.nhead = NHEAD;
+  return mmda_infer_collect(&src, out, dst, base, m->B, stream);
+}

@@ -717,3 +717,41 @@ def collate_gather(words, visual, acoustic, offsets, emo, sentiment, order, T, p
     check(lib.mmda_collate_gather(ptr(words), ptr(visual), ptr(acoustic), ptr(offsets), ptr(emo), ptr(sentiment), ptr(order), B, int(T), dv,
                                   da, int(pad_id), ptr(ids), ptr(v), ptr(a), ptr(e), ptr(y), stream_ptr()), "collate_gather")
     return ids, v, a, e, y
+
+
+def infer_collect(scores=None, labels=None, tcp=None, hfused=None, x6=None, probs=None, *, out, dst=None, base=0):
+    """One batch of forward results copied into per-sample tables in one launch (``mmda_infer_collect``).  Sources, B columns: scores /
+    labels (B, C), tcp (B, 6), hfused (B, 6 hs), x6 (6, B, hs), probs (B, nhead, 6, 6).  ``out``: dict of tables (n rows) by field name --
+    scores, labels, tcp, hidden (n, 6 hs), utterance (n, 6, hs), attention (n, 6, 6); a missing field is skipped.  Column b goes to row
+    ``dst[b]`` (int32 device tensor of B distinct rows in [0, n)), or to ``base + b``; nothing on the device checks the rows."""
+    lib = load()
+    srcs = dict(scores=scores, labels=labels, tcp=tcp, hfused=hfused, x6=x6, probs=probs)
+    given = [t for t in srcs.values() if t is not None]
+    assert given and all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 for t in given)
+    cols = [t.shape[1] if k == "x6" else t.shape[0] for k, t in srcs.items() if t is not None]
+    B = cols[0]
+    assert all(c == B for c in cols)
+    ncls = next((t.shape[1] for t in (scores, labels) if t is not None), 1)
+    hs = x6.shape[2] if x6 is not None else (hfused.shape[1] // 6 if hfused is not None else 1)
+    nhead = probs.shape[1] if probs is not None else 1
+    unknown = set(out) - {"scores", "labels", "tcp", "hidden", "utterance", "attention"}
+    assert not unknown, unknown
+    n = None
+    for t in out.values():
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
+        n = t.shape[0] if n is None else n
+        assert t.shape[0] == n
+    if dst is not None:
+        assert dst.dtype == torch.int32 and dst.is_cuda and dst.is_contiguous() and dst.numel() == B
+    else:
+        assert n is None or 0 <= base and base + B <= n
+    s = _lib.InferSrc(ptr(scores), ptr(labels), ptr(tcp), ptr(hfused), ptr(x6), ptr(probs), int(ncls), int(hs), int(nhead))
+    o = _lib.InferOut(*(ptr(out.get(k)) for k in ("scores", "labels", "tcp", "hidden", "utterance", "attention")))
+    check(lib.mmda_infer_collect(C.byref(s), C.byref(o), ptr(dst), int(base), int(B), stream_ptr()), "infer_collect")
+    return out
+
+
+def misa_infer_collect(model, out, dst_ptr=None, base=0):
+    """``mmda_misa_infer_collect``: the same with the sources taken from ``model``'s workspace as its last forward left them.  ``out``: an
+    ``_lib.InferOut``; ``dst_ptr``: device address of the batch's int32 rows, or None for rows ``base .. base + B - 1``."""
+    check(model._lib.mmda_misa_infer_collect(model._h, C.byref(out), dst_ptr, int(base), stream_ptr()), "misa_infer_collect")

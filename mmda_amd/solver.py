@@ -260,6 +260,28 @@ class Solver(object):
         self.last_eval_metrics = get_metrics(y_true, y_pred)
         return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
 
+    # ------------------------------------------------------------------ inference (the reference's src/inference.py is a TODO)
+    def infer(self, mode, fields=None, order="loader"):
+        """One inference pass over the ``mode`` split ("train", "dev" or "test") -> ``InferenceResult`` (mmda_amd/inference.py): the
+        per-sample tables stay on the device.  ``order="loader"``: the loader's own batches, rows in the order it yields samples.
+        ``order="length"`` / ``"dataset"``: the loader must be a ``DeviceLoader``; its dataset is batched by ``inference_plan`` at the
+        loader's batch size and row i is sample i of the dataset."""
+        from .data import DeviceLoader
+        from .inference import ORDERS, InferencePass
+        loaders = dict(train=self.train_data_loader, dev=self.dev_data_loader, test=self.test_data_loader)
+        if mode not in loaders:
+            raise ValueError(f"mode must be 'train', 'dev' or 'test', not {mode!r}")
+        if order != "loader" and order not in ORDERS:
+            raise ValueError(f"order must be 'loader', 'length' or 'dataset', not {order!r}")
+        loader = loaders[mode]
+        if order != "loader" and not isinstance(loader, DeviceLoader):
+            raise ValueError(f"order={order!r} re-batches a device-resident dataset: the {mode} loader must be a DeviceLoader "
+                             f"(it is a {type(loader).__name__}); use order='loader'")
+        p = InferencePass(self.model, fields) if fields is not None else InferencePass(self.model)
+        if order == "loader":
+            return p.run_loader(loader)
+        return p.run(loader.dataset, loader.batch_size, order)
+
     # ------------------------------------------------------------------ getters (solver.py:373-462)
     def get_cls_loss(self, predicted_scores, emo_label):
         return F.bce_sum_over_classes(predicted_scores, emo_label.type(torch.float))
