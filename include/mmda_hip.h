@@ -738,6 +738,44 @@ typedef struct mmda_infer_out {
 int mmda_infer_collect(const mmda_infer_src* src, const mmda_infer_out* out, const int32_t* dst, int64_t base, int B, void* stream);
 int mmda_misa_infer_collect(mmda_misa* m, const mmda_infer_out* out, const int32_t* dst, int64_t base, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- encoder cache
+ * With every encoder parameter frozen (the encoder cut of mmda_misa_set_trainable) and no dropout in the encoders (nn.LSTM / nn.GRU, one
+ * layer each, models.py:48-55) a sample's utterance vectors utt_t (4 H_t), utt_v (4 H_v), utt_a (4 H_a) are constants, and nothing behind
+ * the encoders reads anything else of them.  They are kept in tables of one row per SAMPLE (mmda_amd/encoded.py: EncoderCache) and a
+ * step starts at the projections (models.py:63-80) from a gather of B rows.  Row movers, one launch each; offsets are 64-bit; a row moves
+ * as 16-byte accesses when its width is a multiple of four floats and both bases are 16-byte aligned, as 4-byte ones otherwise.  A
+ * segment (t, v, a, emo) is requested by giving BOTH its pointers and skipped by giving neither.
+ * mmda_encoded_collect: utt_* are (B, w*) row-major; row b goes to table row dst[b] (int32, device), or base + b when dst is NULL.
+ *   NOTHING checks the rows: the caller guarantees that they lie inside the tables and are distinct within a launch.
+ * mmda_encoded_gather: output row b is table row rows[b] (int32, device; repeats allowed); tab_emo (n, ncls) -> emo (B, ncls) rides along
+ *   when both are given.  Nothing checks the rows either.
+ * MMDA_EINVAL, with nothing launched: a segment with one pointer NULL, every segment NULL, B <= 0, a requested width <= 0, rows NULL.
+ * mmda_misa_encoded_collect: collect with the sources and widths 4 H_i of the model's current workspace carve (B columns of its last
+ *   forward); MMDA_EINVAL also without a workspace. */
+int mmda_encoded_collect(const float* utt_t, const float* utt_v, const float* utt_a, int wt, int wv, int wa, float* tab_t, float* tab_v,
+                         float* tab_a, const int32_t* dst, int64_t base, int B, void* stream);
+int mmda_encoded_gather(const float* tab_t, const float* tab_v, const float* tab_a, int wt, int wv, int wa, const float* tab_emo, int ncls,
+                        const int32_t* rows, int B, float* utt_t, float* utt_v, float* utt_a, float* emo, void* stream);
+int mmda_misa_encoded_collect(mmda_misa* m, float* tab_t, float* tab_v, float* tab_a, const int32_t* dst, int64_t base, void* stream);
+/* A batch of cached rows: the three tables (n, 4 H_i), the label table (n, ncls; NULL where no labels are gathered) and the B row
+ * indices (int32, device).  B must equal the B of the workspace carve; the carve's T is free (nothing such a step runs depends on it:
+ * the host carves (B, 1)).
+ * mmda_misa_forward_encoded: mmda_misa_forward from the projections on -- one mmda_encoded_gather into the workspace's utt_t / utt_v /
+ *   utt_a, then the fusion block and the heads exactly as mmda_misa_forward runs them.  No W_hh packing, no operand conversion, no
+ *   input GEMM, no recurrence.  Follows mmda_misa_set_inference like mmda_misa_forward.
+ * mmda_misa_train_step_encoded: mmda_misa_train_step with that forward; emo_out (B, ncls) receives the gathered labels the losses read
+ *   and must stay alive until the step has run.  From the projections on it issues the launches of a step under the encoder cut at the
+ *   same B, with the same arguments: parameters, moments and losses get the same bits.
+ * MMDA_EINVAL, with nothing launched: the encoder cut is not in force (a training forward: utt would need a gradient nobody computes),
+ *   eb->B differs from the carve's, a NULL table / rows / emo_out, eb->tab_emo NULL in a train step. */
+typedef struct mmda_encoded_batch {
+  const float* tab_t; const float* tab_v; const float* tab_a; const float* tab_emo;
+  const int32_t* rows; int B;
+} mmda_encoded_batch;
+int mmda_misa_forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, int training, uint64_t seed, void* stream);
+int mmda_misa_train_step_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed, int do_adam,
+                                 float lr, float clip, int step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

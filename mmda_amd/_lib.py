@@ -130,6 +130,12 @@ class InferOut(C.Structure):
                 ("attention", C.c_void_p)]
 
 
+class EncodedBatch(C.Structure):
+    """mmda_encoded_batch: B rows of the encoder cache's tables (tab_emo may be None where no labels are gathered)"""
+    _fields_ = [("tab_t", C.c_void_p), ("tab_v", C.c_void_p), ("tab_a", C.c_void_p), ("tab_emo", C.c_void_p), ("rows", C.c_void_p),
+                ("B", C.c_int)]
+
+
 CELL = {"lstm": 0, "gru": 1}
 
 # name -> (restype, argtypes).  Every symbol include/mmda_hip.h declares appears here (tests/test_abi.py checks it).
@@ -260,6 +266,11 @@ SIGNATURES = {
     "mmda_collate_gather": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mmda_infer_collect": (_I, [C.POINTER(InferSrc), C.POINTER(InferOut), _P, _I64, _I, _P]),
     "mmda_misa_infer_collect": (_I, [_P, C.POINTER(InferOut), _P, _I64, _P]),
+    "mmda_encoded_collect": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _I, _P]),
+    "mmda_encoded_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "mmda_misa_encoded_collect": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
+    "mmda_misa_forward_encoded": (_I, [_P, C.POINTER(EncodedBatch), _I, _U64, _P]),
+    "mmda_misa_train_step_encoded": (_I, [_P, C.POINTER(EncodedBatch), _P, _I, _U64, _I, _F, _F, _I, _P]),
 }
 
 _lib = None

@@ -44,6 +44,7 @@ struct StepPlan {
   bool inf = false;                 // evaluation pass: no backward follows -- no stash, no copies that only the backward pass reads
   bool enc_cut = false;             // every encoder parameter is frozen (mmda_misa_set_trainable): the backward pass stops in front of the encoders
   bool enc_nostash = false;         // the encoders keep nothing for a backward pass: an evaluation pass, or a cut step (unless told to stash)
+  bool enc_cached = false;          // the encoders did not run at all: utt came from the encoder cache (mmda_misa_forward_encoded)
   bool bfg = false;                 // bf16 mode with bf16 operand copies: the LSTM-sized GEMMs read them (gemm_bf16.hip)
   int gm = 0;                       // gate-minor layout of `gates` (see mmda_lstm_desc.gate_minor)
   bool kdg = false;                 // the backward recurrence writes the gate gradients as bf16, and only so
@@ -118,6 +119,7 @@ struct mmda_misa {
   int embed_flag = 1;              // the table's own flag (what embed_update makes of the table is a separate matter)
   int enc_frozen = 0;              // both recurrent layers and the three inter-layer LayerNorms are frozen
   int cut_keep_stash = 0;          // a cut step runs the stashing forward all the same (mmda_misa_set_cut_forward)
+  int enc_cached = 0;              // the forward being planned starts behind the encoders (set by the *_encoded entry points, cleared by mmda_misa_forward)
   mmda_run* runs_dev = nullptr; int runs_dev_cap = 0; int runs_dirty = 1;
   // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
   // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
@@ -731,6 +733,7 @@ StepPlan plan_step(mmda_misa* m) {
   P.inf = m->inference != 0;
   P.enc_cut = !P.inf && encoder_cut(m);
   P.enc_nostash = P.inf || (P.enc_cut && !m->cut_keep_stash);
+  P.enc_cached = m->enc_cached != 0;
   P.bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
   // Gate-minor layout of the pre-activations / stash / gate gradients ([dir][unit][gate], 16-byte accesses in the recurrent
   // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
@@ -1486,9 +1489,64 @@ void Pass::fwd_fusion_tiled() {
 }
 }  // namespace
 
+namespace {
+// A forward pass from the projections on -- utt_t / utt_v / utt_a are in the workspace, from the encoders or from the encoder cache --
+// and its tail: the K-major weight copies nobody has made yet, then the side stream's chain joined, on the device by the backward
+// pass's stretch A (flag join) or by an event here.
+int forward_from_projections(Pass& x, void* stream) {
+  mmda_misa* m = x.m;
+  if (m->plan.skinny) x.fwd_fusion_skinny();
+  else x.fwd_fusion_tiled();
+  if (!x.rc && m->wT_pending) {                // no fork came by (the eager losses are off and nothing else was pending)
+    void* ss = nullptr;
+    x.rc = side_fork(m, stream, &ss);
+    if (!x.rc) x.rc = weight_transposes(m, ss);
+  }
+  if (!x.rc && m->plan.fj_fwd && m->side_pending && m->jflags) {
+    x.rc = side_flag_signal(m, 0, m->fj1_armed != 0);      // (see mmda_misa::jflags: fused_bwd_a_kernel waits for the loss chain)
+    m->fj1 = x.rc ? 0 : 1; m->fj1_armed = 0;
+    return x.rc;
+  }
+  if (m->fj1_armed) return MMDA_ELAUNCH;       // (the CMD launch was armed on the same condition: cannot happen)
+  if (!x.rc) x.rc = side_join(m, stream);      // (the side stream finished long ago: this only orders later work behind it)
+  return x.rc;
+}
+
+bool encoded_batch_ok(const mmda_misa* m, const mmda_encoded_batch* eb) {
+  return eb && eb->tab_t && eb->tab_v && eb->tab_a && eb->rows && eb->B > 0 && eb->B == m->B;
+}
+
+// The forward pass of a step that starts behind the encoders: the plan, ONE gather of the batch's cached rows into utt_t / utt_v /
+// utt_a (and of its labels into emo_out), then the fusion block as ever.  Skipped with the encoders: the GRU parameter padding, the
+// deferred table's catch-up, fwd_operands, both encoder layers and the cluster epochs they advance (no recurrence is launched).  What
+// fwd_operands does for the REST of the step is kept: the K-major fusion-weight copies take the wT_pending route -- the first fork, or
+// the tail above -- in both precisions, since the conversion launch they ride in the bf16 mode does not exist here.
+int forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed, void* stream) {
+  m->training = training; m->seed = seed;
+  m->enc_cached = 1;
+  m->plan = plan_step(m);
+  Pass x(m, stream);
+  m->wT_valid = 0;
+  m->wT_pending = m->plan.want_wT ? 1 : 0;
+  x.rc = mmda_encoded_gather(eb->tab_t, eb->tab_v, eb->tab_a, 4 * m->mod[0].H, 4 * m->mod[1].H, 4 * m->mod[2].H,
+                             emo_out ? eb->tab_emo : nullptr, m->cfg.ncls, eb->rows, m->B, WS(m->mod[0].utt), WS(m->mod[1].utt),
+                             WS(m->mod[2].utt), emo_out, stream);
+  if (x.rc) return x.rc;
+  return forward_from_projections(x, stream);
+}
+}  // namespace
+
+extern "C" int mmda_misa_forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, int training, uint64_t seed, void* stream) {
+  if (check_ready(m) || !encoded_batch_ok(m, eb)) return MMDA_EINVAL;
+  // a training forward: utt would need a gradient path that nobody computes
+  if (!m->inference && !encoder_cut(m)) return MMDA_EINVAL;
+  return forward_encoded(m, eb, nullptr, training, seed, stream);
+}
+
 extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
                                  int training, uint64_t seed, void* stream) {
   if (check_ready(m) || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
+  m->enc_cached = 0;
   // The fusion block (projections, private/shared/recon, transformer layer, heads) is 2 % of the FLOPs and feeds the
   // batch-statistic losses: it always runs on the exact f32 MFMA path.  `mode` (bf16) covers the LSTM GEMMs + recurrences.
   m->training = training; m->seed = seed;
@@ -1511,23 +1569,8 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   x.fwd_operands(t_ids, xin);
   for (int l = 0; l < 2 && !x.rc; ++l) x.fwd_encoder_layer(l, xin, lengths);
   if (x.rc) return x.rc;
-  if (m->plan.skinny) x.fwd_fusion_skinny();
-  else x.fwd_fusion_tiled();
-  if (!m->ev.empty()) { if (m->ev_seen_f % m->ev_stride == 0) m->ev_fwd++; m->ev_seen_f++; }
-  // the side stream's chain is joined -- on the device by the backward pass's stretch A (flag join) or by an event here
-  if (!x.rc && m->wT_pending) {                // no fork came by (the eager losses are off and nothing else was pending)
-    void* ss = nullptr;
-    x.rc = side_fork(m, stream, &ss);
-    if (!x.rc) x.rc = weight_transposes(m, ss);
-  }
-  if (!x.rc && m->plan.fj_fwd && m->side_pending && m->jflags) {
-    x.rc = side_flag_signal(m, 0, m->fj1_armed != 0);      // (see mmda_misa::jflags: fused_bwd_a_kernel waits for the loss chain)
-    m->fj1 = x.rc ? 0 : 1; m->fj1_armed = 0;
-    return x.rc;
-  }
-  if (m->fj1_armed) return MMDA_ELAUNCH;       // (the CMD launch was armed on the same condition: cannot happen)
-  if (!x.rc) x.rc = side_join(m, stream);      // (the side stream finished long ago: this only orders later work behind it)
-  return x.rc;
+  if (!m->ev.empty()) { if (m->ev_seen_f % m->ev_stride == 0) m->ev_fwd++; m->ev_seen_f++; }      // (the recurrent launches' timing)
+  return forward_from_projections(x, stream);
 }
 
 // =============================================================================================== losses
@@ -2054,10 +2097,15 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
 }
 }  // namespace
 
-extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
-                                  void* stream) {
-  if (check_ready(m) || !m->G || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
+namespace {
+// The backward pass.  The batch (ids / v / a / lengths) is read only by what an encoder cut skips -- the encoder layers, the sorted id
+// list, the scatter -- so a step from the encoder cache, which has no batch, passes NULLs: it must be a cut pass planned by a cached
+// forward.
+int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, void* stream) {
+  if (check_ready(m) || !m->G) return MMDA_EINVAL;
   if (m->plan.inf) return MMDA_EINVAL;                  // the last forward was an evaluation pass: nothing was stashed
+  if ((!t_ids || !v || !a || !lengths) && !(m->plan.enc_cached && m->plan.enc_cut)) return MMDA_EINVAL;
+  if (m->plan.enc_cached && !m->plan.enc_cut) return MMDA_EINVAL;      // (a cached forward that trains is a cut one: cannot happen)
   // the trainable set changed behind that forward: a cut pass computes no encoder gradient (and may have stashed nothing)
   if (m->plan.enc_cut && !encoder_cut(m)) return MMDA_EINVAL;
   if (masked(m) && m->adam_early_on) { const int rr = runs_ready(m, stream); if (rr) return rr; }
@@ -2079,7 +2127,7 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
   // layers' ranges of the gradient bucket hold what the clear left.
   for (int l = 1; l >= 0 && !x.rc && !P.enc_cut; --l) x.bwd_encoder_layer(l, xin, t_ids, lengths);
   if (x.rc) return x.rc;
-  if (!m->ev.empty()) { if (m->ev_seen_b % m->ev_stride == 0) m->ev_bwd++; m->ev_seen_b++; }
+  if (!m->ev.empty() && !P.enc_cached) { if (m->ev_seen_b % m->ev_stride == 0) m->ev_bwd++; m->ev_seen_b++; }
   // every gradient is complete on `stream` when backward returns -- or, in a fused training step whose last optimizer launch can
   // wait on the device (see mmda_misa::jflags), when that launch completes
   // (only where every gradient the side stream computes lies in the prefix it also stepped -- the bf16 step, whose layer-2 weight
@@ -2097,6 +2145,13 @@ extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const floa
     x.rc = mmda_gru_unpad_grads(gj, n, stream);
   }
   return x.rc;
+}
+}  // namespace
+
+extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                                  void* stream) {
+  if (!t_ids || !v || !a || !lengths) return MMDA_EINVAL;
+  return backward_pass(m, t_ids, v, a, lengths, stream);
 }
 
 extern "C" int mmda_misa_timing_end(mmda_misa* m) {
@@ -2210,9 +2265,12 @@ extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, i
   return rc;
 }
 
-extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
-                                    const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
-                                    void* stream) {
+namespace {
+// One training step: from a batch (t_ids, v, a, lengths; labels `emo`), or -- eb != nullptr -- from the encoder cache, whose forward
+// gathers the labels into `emo` itself.  The two differ in their forward pass and in the batch the backward pass is handed, nowhere else.
+int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const mmda_encoded_batch* eb,
+               float* emo_gathered, const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
+               void* stream) {
   // the gradient bucket is cleared on the side stream beside the forward pass's fusion block (not at the start of the step: the
   // side stream's first job there, packing W_hh, is what the first recurrent kernel waits for)
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
@@ -2228,7 +2286,7 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   m->fj1 = m->fj2 = 0;
   int rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
   if (rc) return rc;
-  rc = mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
+  rc = eb ? forward_encoded(m, eb, emo_gathered, training, seed, stream) : mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
   m->eager_losses = 0; m->emo_eager = nullptr;
   if (rc) return rc;
   if (m->zero_grad_pending) return MMDA_ELAUNCH;        // forward() always reaches its fusion block
@@ -2236,7 +2294,7 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
   if (rc) return rc;
   // (the early optimizer pass beside the layer-1 recurrence: faster than one launch for the whole bucket at the end)
   m->adam_early_on = do_adam ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
-  rc = mmda_misa_backward(m, t_ids, v, a, lengths, stream);
+  rc = backward_pass(m, t_ids, v, a, lengths, stream);
   m->adam_early_on = 0;
   if (rc) return rc;
   if (m->fj1) { rc = flag_join_fallback(m, stream); m->fj1 = 0; if (rc) return rc; }      // (no stretch took it over: cannot happen)
@@ -2252,6 +2310,30 @@ extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const fl
                      FlagWait{fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr}, stream);
   }
   return rc;
+}
+}  // namespace
+
+extern "C" int mmda_misa_train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                                    const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
+                                    void* stream) {
+  return train_step(m, t_ids, v, a, lengths, nullptr, nullptr, emo, training, seed, do_adam, lr, clip, step, stream);
+}
+
+// mmda_misa_train_step from the encoder cache.  Everything is checked before the first launch: a refused call changes nothing.
+extern "C" int mmda_misa_train_step_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed,
+                                            int do_adam, float lr, float clip, int step, void* stream) {
+  if (check_ready(m) || !m->G || !encoded_batch_ok(m, eb) || !eb->tab_emo || !emo_out) return MMDA_EINVAL;
+  if (!encoder_cut(m)) return MMDA_EINVAL;               // utt would need a gradient path that nobody computes
+  return train_step(m, nullptr, nullptr, nullptr, nullptr, eb, emo_out, emo_out, training, seed, do_adam, lr, clip, step, stream);
+}
+
+// The encoder cache's collect launch (encoded.hip) on the model's own workspace: B columns of the last forward of the current carve.
+extern "C" int mmda_misa_encoded_collect(mmda_misa* m, float* tab_t, float* tab_v, float* tab_a, const int32_t* dst, int64_t base,
+                                         void* stream) {
+  if (!m || !m->ws || m->B <= 0) return MMDA_EINVAL;
+  // (a table that is not given is a segment that is skipped: its source is left out with it)
+  return mmda_encoded_collect(tab_t ? WS(m->mod[0].utt) : nullptr, tab_v ? WS(m->mod[1].utt) : nullptr, tab_a ? WS(m->mod[2].utt) : nullptr,
+                              4 * m->mod[0].H, 4 * m->mod[1].H, 4 * m->mod[2].H, tab_t, tab_v, tab_a, dst, base, m->B, stream);
 }
 
 // The inference pass's collect launch (infer.hip) on the model's own workspace: the sources are where the last forward of the current

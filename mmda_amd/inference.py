@@ -33,6 +33,57 @@ def inference_plan(lengths, batch_size, order="length"):
     return batch_plan(lengths, seq, batch_size)
 
 
+def _model_device(model, who):
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.MMDAError(f"{who}: the model is on {dev}; the pass runs on the GPU only (model.to('cuda'))")
+    return dev
+
+
+def _pass_device(model, dataset, who):
+    """The device a pass of ``model`` over ``dataset`` (a ``DeviceDataset``) runs on; refuses, by ``who``'s name, anything off the GPU."""
+    if torch.device(dataset.device).type != "cuda":
+        raise _lib.MMDAError(f"{who}: the dataset is on {dataset.device}; the pass runs on the GPU only")
+    dev = _model_device(model, who)
+    if torch.device(dataset.device) != dev:
+        raise _lib.MMDAError(f"{who}: the dataset is on {dataset.device}, the model on {dev}")
+    return dev
+
+
+def _eval_batch(m, t, v, a, lengths):
+    """One batch of a pass: ``_prepare``, one seed drawn, the evaluation forward (dropout off, no stash)."""
+    t, v, a, len_dev = m._prepare(t, v, a, lengths)
+    m._forward_raw(t, v, a, len_dev, False, m._next_seed(), inference=True)
+
+
+def dataset_pass(m, ds, plan, bounds, batch_size, dev, collect):
+    """The loop of a pass over a device-resident dataset, shared by ``InferencePass.run`` and ``EncoderCache.build``
+    (mmda_amd/encoded.py): the plan's int32 order is uploaded once; every batch is one ``mmda_collate_gather`` into buffers sized once
+    for the longest batch, ``_eval_batch``, and ``collect(dst_ptr)`` -- the caller's one launch, which copies what the forward left in
+    the workspace to the rows the B int32 indices at ``dst_ptr`` name (the batch's samples).  No read-back, no synchronisation."""
+    n = len(ds)
+    if not n:
+        return
+    lib = m._lib
+    order_dev = torch.from_numpy(plan.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+    lens_np = np.asarray(ds.lengths, dtype=np.int64)[plan]
+    lens_all = torch.from_numpy(lens_np)
+    Bmax, Tmax = int(min(int(batch_size), n)), int(lens_np.max())
+    ids_buf = torch.empty(Tmax * Bmax, dtype=torch.int64, device=dev)
+    v_buf = torch.empty(Tmax * Bmax * ds.dv, device=dev)
+    a_buf = torch.empty(Tmax * Bmax * ds.da, device=dev)
+    y_buf = torch.empty(Bmax, device=dev)
+    src = tuple(_lib.ptr(x) for x in (ds.words, ds.visual, ds.acoustic, ds.offsets, ds.emo, ds.sentiment))
+    order_ptr = order_dev.data_ptr()
+    for lo, hi in zip(bounds[:-1].tolist(), bounds[1:].tolist()):
+        B, T = hi - lo, int(lens_np[lo])
+        ids, v, a = ids_buf[:T * B].view(T, B), v_buf[:T * B * ds.dv].view(T, B, ds.dv), a_buf[:T * B * ds.da].view(T, B, ds.da)
+        _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, ds.dv, ds.da, PAD, ids.data_ptr(), v.data_ptr(),
+                                           a.data_ptr(), None, y_buf.data_ptr(), _lib.stream_ptr()), "mmda_collate_gather")
+        _eval_batch(m, ids, v, a, lens_all[lo:hi])
+        collect(order_ptr + 4 * lo)
+
+
 def _check_fields(fields):
     if isinstance(fields, str):
         fields = (fields,)
@@ -88,10 +139,7 @@ class InferencePass:
 
     # ------------------------------------------------------------------ tables
     def _device(self):
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise _lib.MMDAError(f"InferencePass: the model is on {dev}; the pass runs on the GPU only (model.to('cuda'))")
-        return dev
+        return _model_device(self.model, "InferencePass")
 
     def _tables(self, rows, dev):
         cfg = self.model.config
@@ -109,42 +157,19 @@ class InferencePass:
         return flat, layout, out
 
     def _batch(self, t, v, a, lengths, out, dst_ptr, base):
-        m = self.model
-        t, v, a, len_dev = m._prepare(t, v, a, lengths)
-        m._forward_raw(t, v, a, len_dev, False, m._next_seed(), inference=True)
-        ops.misa_infer_collect(m, out, dst_ptr, base)
+        _eval_batch(self.model, t, v, a, lengths)
+        ops.misa_infer_collect(self.model, out, dst_ptr, base)
 
     # ------------------------------------------------------------------ over a device-resident dataset
     def run(self, dataset, batch_size, order="length"):
         """Row i of every table is sample i of ``dataset`` (a ``DeviceDataset``), whatever ``order`` the batches are visited in
         (``inference_plan``).  Batches are gathered by ``mmda_collate_gather`` into buffers sized once for the longest batch."""
         plan, bounds = inference_plan(dataset.lengths, batch_size, order)
-        if torch.device(dataset.device).type != "cuda":
-            raise _lib.MMDAError(f"InferencePass: the dataset is on {dataset.device}; the pass runs on the GPU only")
-        dev = self._device()
-        if torch.device(dataset.device) != dev:
-            raise _lib.MMDAError(f"InferencePass: the dataset is on {dataset.device}, the model on {dev}")
+        dev = _pass_device(self.model, dataset, "InferencePass")
         m, ds, n = self.model, dataset, len(dataset)
         flat, layout, out = self._tables(n, dev)
         lengths = torch.from_numpy(np.array(ds.lengths, dtype=np.int64))
-        if n:
-            lib = m._lib
-            order_dev = torch.from_numpy(plan.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-            lens_np = np.asarray(ds.lengths, dtype=np.int64)[plan]
-            lens_all = torch.from_numpy(lens_np)
-            Bmax, Tmax = int(min(int(batch_size), n)), int(lens_np.max())
-            ids_buf = torch.empty(Tmax * Bmax, dtype=torch.int64, device=dev)
-            v_buf = torch.empty(Tmax * Bmax * ds.dv, device=dev)
-            a_buf = torch.empty(Tmax * Bmax * ds.da, device=dev)
-            y_buf = torch.empty(Bmax, device=dev)
-            src = tuple(_lib.ptr(x) for x in (ds.words, ds.visual, ds.acoustic, ds.offsets, ds.emo, ds.sentiment))
-            order_ptr = order_dev.data_ptr()
-            for lo, hi in zip(bounds[:-1].tolist(), bounds[1:].tolist()):
-                B, T = hi - lo, int(lens_np[lo])
-                ids, v, a = ids_buf[:T * B].view(T, B), v_buf[:T * B * ds.dv].view(T, B, ds.dv), a_buf[:T * B * ds.da].view(T, B, ds.da)
-                _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, ds.dv, ds.da, PAD, ids.data_ptr(), v.data_ptr(),
-                                                   a.data_ptr(), None, y_buf.data_ptr(), _lib.stream_ptr()), "mmda_collate_gather")
-                self._batch(ids, v, a, lens_all[lo:hi], out, order_ptr + 4 * lo, 0)
+        dataset_pass(m, ds, plan, bounds, batch_size, dev, lambda dst_ptr: ops.misa_infer_collect(m, out, dst_ptr, 0))
         m.check_cluster("inference")
         return InferenceResult(flat, layout, n, lengths, np.array(ds.segments, dtype=object))
 

@@ -176,6 +176,7 @@ class MISA(nn.Module):
         self._trainable_sent = (True,) * len(self._native_names)
         self._trainable_sends = 0
         self._runs_cache = None
+        self._cut_flags = None                              # the flags under which the native side last reported the encoder cut on
         # deferred mode: per-row step counts and the ring of step scalars (device, made with the flat buckets), and whether a step has
         # been taken since the last flush
         self._df_row_step = self._df_ring = None
@@ -339,6 +340,7 @@ class MISA(nn.Module):
             self.embed_window = int(os.environ.get("MMDA_EMBED_WINDOW", 0) or getattr(self.config, "embed_deferred_window", 256))
         self._rows_pending = False
         self._rows_clip = None
+        self._cut_flags = None
         self.embed.weight.requires_grad_(mode != "frozen")
         if mode != "dense":
             self.embed.weight.grad = None
@@ -477,17 +479,7 @@ class MISA(nn.Module):
             raise RuntimeError("Length of all samples has to be greater than 0")     # pack_padded_sequence's rule
         if lmax > T:
             raise RuntimeError("a length exceeds the padded sequence length")
-        if self._ws_shape != (B, T):
-            need = self._lib.mmda_misa_workspace_floats(self._h, B, T)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-                if self._ws is not None and self._ws_shape is not None:
-                    # the old buffer's sticky abort words would be lost with it (the native side never touches a buffer it was
-                    # not handed): look at them first.  Buffers only grow, so this synchronous read happens a few times per run.
-                    self._abort_seen = self._abort_seen or self.cluster_aborted()
-                self._ws = torch.zeros(need, dtype=torch.float32, device=dev)
-            _lib.check(self._lib.mmda_misa_set_workspace_async(self._h, self._ws.data_ptr(), self._ws.numel(), B, T, _lib.stream_ptr()),
-                       "set_workspace")
-            self._ws_shape = (B, T)
+        self._carve(B, T, dev)
         # lengths arrive on the CPU (reference: l = to_cpu(l), solver.py:149).  Convert on the host, stage through a pinned
         # buffer and copy asynchronously; an unchanged batch (benchmark loops) reuses the device copy.
         lens32 = lens.to(device="cpu", dtype=torch.int32)
@@ -505,6 +497,20 @@ class MISA(nn.Module):
         v = video.contiguous().float()
         a = acoustic.contiguous().float()
         return t, v, a, len_dev
+
+    def _carve(self, B: int, T: int, dev):
+        """The workspace laid out for (B, T) batches, grown when it has to be."""
+        if self._ws_shape != (B, T):
+            need = self._lib.mmda_misa_workspace_floats(self._h, B, T)
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                if self._ws is not None and self._ws_shape is not None:
+                    # the old buffer's sticky abort words would be lost with it (the native side never touches a buffer it was
+                    # not handed): look at them first.  Buffers only grow, so this synchronous read happens a few times per run.
+                    self._abort_seen = self._abort_seen or self.cluster_aborted()
+                self._ws = torch.zeros(need, dtype=torch.float32, device=dev)
+            _lib.check(self._lib.mmda_misa_set_workspace_async(self._h, self._ws.data_ptr(), self._ws.numel(), B, T, _lib.stream_ptr()),
+                       "set_workspace")
+            self._ws_shape = (B, T)
 
     def _off(self, name: str) -> int:
         o = self._lib.mmda_misa_tensor_offset(self._h, name.encode())
@@ -715,6 +721,85 @@ class MISA(nn.Module):
                            "adam(rest)")
             else:
                 _lib.check(self._lib.mmda_misa_adam_step(self._h, lr, clip, float(scale), self._step, s), "adam_step")
+
+    # ------------------------------------------------------------------ steps that start behind the encoders (mmda_amd/encoded.py)
+    def _encoded_begin(self, batch, what: str, exchange=None, accum_index: int = 0, accum_count: int = 1):
+        """Everything a step from the encoder cache refuses, by name and before any launch; then the workspace carved at (B, 1) --
+        nothing such a step runs depends on T -- and the native batch."""
+        from .encoded import EncodedBatch
+        if not isinstance(batch, EncodedBatch):
+            raise TypeError(f"{what} takes an EncodedBatch (EncodedLoader yields them), not {type(batch).__name__}")
+        if exchange is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
+                                    and torch.distributed.get_world_size() > 1):
+            raise _lib.MMDAError(f"{what} with a gradient exchange (grad_sync / a process group) is not built")
+        if self.accum_steps > 1 or accum_index != 0 or accum_count != 1 or self._acc_next:
+            raise _lib.MMDAError(f"{what} with gradient accumulation (accum_steps > 1, accum_index, accum_count) is not built")
+        cache = batch.cache
+        cache._refuse(self)                                  # another device, other widths
+        flags = self._sync_trainable()
+        if flags != self._cut_flags:                        # (the steady state: one tuple compare)
+            if not self.trainable_info()[2]:
+                from .encoded import ENCODER_PREFIXES
+                live = [n for n, f in zip(self._native_names, flags) if f and n.split(".")[0] in ENCODER_PREFIXES]
+                if self.embed_update in ("sparse", "deferred"):
+                    live.append(f"embed.weight (embed_update='{self.embed_update}' trains the table through its rows)")
+                raise _lib.MMDAError(f"{what} needs the encoder cut -- every recurrent layer, the three inter-layer LayerNorms and the "
+                                     f"table frozen (MISA.freeze): the cached rows are constants only then.  Still trainable: {live}")
+            self._cut_flags = flags
+        if cache.device.type != "cuda":
+            raise _lib.MMDAError(f"{what}: the cache is on {cache.device}: mmda_amd.MISA has no CPU path (HIP kernels only)")
+        if not self._views_valid():
+            self._materialize(cache.device)
+        self._carve(batch.B, 1, cache.device)
+        return _lib.EncodedBatch(tab_t=cache.utt_t.data_ptr(), tab_v=cache.utt_v.data_ptr(), tab_a=cache.utt_a.data_ptr(),
+                                 tab_emo=_lib.ptr(cache.emo), rows=batch.rows_ptr, B=batch.B)
+
+    def train_step_encoded(self, batch, lr: float, clip: float, do_adam: bool = True, training: bool = True, seed=None, optimizer=None,
+                           grad_sync=None, accum_index: int = 0, accum_count: int = 1):
+        """``train_step`` from the encoder cache: ``batch`` is an ``EncodedBatch``; the step gathers its rows (and labels) in one launch
+        and starts at the projections.  Needs the encoder cut; seeds, the step counter and ``optimizer`` are ``train_step``'s (a
+        custom optimizer, RMSprop, is stepped by its own kernel behind the native step without its Adam).  ``grad_sync`` and the
+        accumulation arguments exist to be refused by name."""
+        from . import optim as _optim
+        eb = self._encoded_begin(batch, "train_step_encoded", grad_sync, accum_index, accum_count)
+        if batch.cache.emo is None:
+            raise _lib.MMDAError("train_step_encoded: the cache has no emotion labels (its dataset had none)")
+        if seed is None:
+            seed = self._next_seed()
+        custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
+        if not custom:
+            self._step += 1
+        emo = torch.empty(batch.B, self.config.num_classes, dtype=torch.float32, device=batch.cache.device)
+        _lib.check(self._lib.mmda_misa_train_step_encoded(self._h, C.byref(eb), emo.data_ptr(), int(training), seed, int(do_adam and not custom),
+                                                          lr, clip, max(self._step, 1), _lib.stream_ptr()), "mmda_misa_train_step_encoded")
+        self._fwd_id += 1
+        self._last = dict(encoded=batch, emo=emo)
+        self._rows_pending, self._rows_clip, self._rows_keep = False, None, None
+        if custom:
+            optimizer.step(clip_value=clip, grad_scale=1.0)
+
+    def forward_encoded(self, batch):
+        """``model(...)`` under ``torch.no_grad()`` from the encoder cache: (scores, labels) of the batch, the side-channel attributes
+        set as ``alignment`` sets them.  Draws one seed, as ``model(...)`` does."""
+        if torch.is_grad_enabled():
+            raise _lib.MMDAError("autograd through forward_encoded is not built: call it under torch.no_grad() (train with train_step_encoded)")
+        eb = self._encoded_begin(batch, "forward_encoded")
+        eb.tab_emo = None
+        seed = self._next_seed()
+        _lib.check(self._lib.mmda_misa_set_inference(self._h, 1), "set_inference")
+        _lib.check(self._lib.mmda_misa_forward_encoded(self._h, C.byref(eb), int(self.training), seed, _lib.stream_ptr()),
+                   "mmda_misa_forward_encoded")
+        self._fwd_id += 1
+        self._last = dict(encoded=batch)
+        pub = self._public()
+        for k in _PUB:
+            if k == "scores":
+                continue
+            val = pub[k].clone() if k in pub else None
+            if k.startswith("domain_label") and self.config.use_cmd_sim:
+                val = None
+            setattr(self, k, val)
+        return pub["scores"].clone(), pub["labels"].clone()
 
     def _accum_micro_step(self, sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync, optimizer,
                           index, count) -> None:

@@ -7,6 +7,8 @@ Two ways through a batch, same kernels underneath:
                                   [RCCL gradient all-reduce], clip + Adam; losses are read back once per epoch.
   * ``train_epoch_unfused()``   - the reference's statement order verbatim (forward, six getters on the module's
                                   side-channel attributes, ``loss.backward()``, clip, ``optimizer.step()``) through autograd.
+``train_epoch()`` and ``eval()`` also take loaders that yield ``EncodedBatch`` (``mmda_amd/encoded.py``: ``EncodedLoader`` over an
+``EncoderCache``, which ``encode(mode)`` builds): steps that start behind the frozen encoders.
 wandb / hypertune / tqdm / sklearn reports of the reference are logging only and are not reproduced.
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ import torch
 from . import models
 from . import optim as _optim
 from .dist import DataParallelSync
+from .encoded import EncodedBatch, EncodedLoader, EncoderCache
 from .utils import to_gpu, to_cpu, set_device
 from .utils import functions as F
 
@@ -124,13 +127,16 @@ class Solver(object):
         sums = None
         n = 0
         for batch, k, count in self._micro_batches():
-            t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
-            t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
-            l = to_cpu(l)
             accum = dict(accum_index=k, accum_count=count) if count > 1 else {}
-            self.model.train_step(t, v, a, l, emo_label, lr=cfg.learning_rate, clip=cfg.clip,
-                                  grad_sync=self.dp.sync if self.dp is not None else None,
-                                  optimizer=getattr(self, "optimizer", None), **accum)
+            step = dict(lr=cfg.learning_rate, clip=cfg.clip, grad_sync=self.dp.sync if self.dp is not None else None,
+                        optimizer=getattr(self, "optimizer", None), **accum)
+            if isinstance(batch, EncodedBatch):                  # an index list into the encoder cache: the step gathers it
+                self.model.train_step_encoded(batch, **step)
+            else:
+                t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
+                t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                l = to_cpu(l)
+                self.model.train_step(t, v, a, l, emo_label, **step)
             L = self.model._ws_view("losses", (8,))
             sums = L.clone() if sums is None else sums + L       # stays on the device; one sync per epoch
             n += 1
@@ -146,6 +152,10 @@ class Solver(object):
             from . import _lib
             raise _lib.MMDAError("train_epoch_unfused() is the reference's loop, one optimizer step per batch: accum_steps > 1 runs "
                                  "through train_epoch()")
+        if isinstance(self.train_data_loader, EncodedLoader):
+            from . import _lib
+            raise _lib.MMDAError("train_epoch_unfused() is the reference's loop through autograd, which a step from the encoder cache "
+                                 "does not go through: an EncodedLoader runs through train_epoch()")
         self.model.train()
         train_loss = []
         for batch in self.train_data_loader:
@@ -236,10 +246,14 @@ class Solver(object):
         acc_dev = None
         with torch.no_grad():
             for batch in dataloader:
-                t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
-                t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
-                l = to_cpu(l)
-                predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
+                if isinstance(batch, EncodedBatch):
+                    predicted_scores, predicted_labels = self.model.forward_encoded(batch)
+                    emo_label = batch.emo()
+                else:
+                    t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
+                    t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                    l = to_cpu(l)
+                    predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
                 emo_label = emo_label.type(torch.float)
                 if predicted_labels.is_cuda:
                     if acc_dev is None:
@@ -281,6 +295,21 @@ class Solver(object):
         if order == "loader":
             return p.run_loader(loader)
         return p.run(loader.dataset, loader.batch_size, order)
+
+    # ------------------------------------------------------------------ encoder cache (mmda_amd/encoded.py)
+    def encode(self, mode, batch_size=None, order="length"):
+        """The ``EncoderCache`` of the ``mode`` split ("train", "dev" or "test"), whose loader must be a ``DeviceLoader``: one evaluation
+        pass over its dataset at ``batch_size`` (default: the loader's).  Wrap it in an ``EncodedLoader`` and hand that to the solver
+        in the split's place to train, or evaluate, from the stored encoder outputs."""
+        from .data import DeviceLoader
+        loaders = dict(train=self.train_data_loader, dev=self.dev_data_loader, test=self.test_data_loader)
+        if mode not in loaders:
+            raise ValueError(f"mode must be 'train', 'dev' or 'test', not {mode!r}")
+        loader = loaders[mode]
+        if not isinstance(loader, DeviceLoader):
+            raise ValueError(f"encode({mode!r}) reads a device-resident dataset: the {mode} loader must be a DeviceLoader "
+                             f"(it is a {type(loader).__name__})")
+        return EncoderCache.build(self.model, loader.dataset, loader.batch_size if batch_size is None else batch_size, order)
 
     # ------------------------------------------------------------------ getters (solver.py:373-462)
     def get_cls_loss(self, predicted_scores, emo_label):
