@@ -124,6 +124,21 @@ typedef struct mmda_gemm_bf16_args {
   int tn;
 } mmda_gemm_bf16_args;
 int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, void* stream);
+/* A read-only view of what mmda_gemm_bf16_grouped(args, n) would launch: rows[i] describes problem i.  Host code only -- no launch,
+ * no device call, no environment: `switches` = {dma_on, dma_stages, dma_min_rows, dma_tall} stands for MMDA_GEMM_DMA,
+ * MMDA_GEMM_DMA_STAGES, MMDA_GEMM_DMA_MIN_ROWS and MMDA_GEMM_DMA_TALL (NULL: their defaults 1, 2, 8192, 0).  Pointers are validated
+ * and inspected for alignment as by the real call but never followed.  Returns the number of GEMM launches of the call (the one
+ * reduce launch behind them, which exists when some sk > 1, not counted), or a negative error; capacity < n is MMDA_EINVAL. */
+enum { MMDA_BF16_REG64 = 0, MMDA_BF16_REG128 = 1, MMDA_BF16_DMA128 = 2, MMDA_BF16_DMA256 = 3 };
+typedef struct mmda_gemm_bf16_plan_row {
+  int cls;                           /* MMDA_BF16_*; -1: an empty problem (M or N zero), nothing is launched for it */
+  int mixed;                         /* 1: its launch runs the tn-capable instance of a register-staged class */
+  int tx, ty, sk;                    /* output tiles along n (the bias gradient's column included) and m; K slices */
+  int per, last;                     /* k-tiles (of 64) per slice, and of the last slice */
+  int launch;                        /* index of its launch within the call, in issue order */
+} mmda_gemm_bf16_plan_row;
+int mmda_gemm_bf16_plan_describe(const mmda_gemm_bf16_args* args, int n, const int switches[4], mmda_gemm_bf16_plan_row* rows,
+                                 int capacity);
 /* fp32 (rows, cols) matrix with leading dim ld -> bf16 copies: `plain` (rows, ldp) and/or `transposed` (cols, ldt); either may be
  * NULL.  ldp >= round_up(cols,8), ldt >= round_up(rows,8); the padding columns are written as zero.  `gather` (optional int64
  * row ids) reads row ids[r] of `src` instead of row r (embedding lookup).  Up to 16 jobs per launch. */

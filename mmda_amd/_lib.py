@@ -39,6 +39,12 @@ class GemmBf16Args(C.Structure):
                 ("tn", C.c_int)]
 
 
+class GemmBf16PlanRow(C.Structure):
+    """mmda_gemm_bf16_plan_row: what the launch plan of a call does with one problem"""
+    _fields_ = [("cls", C.c_int), ("mixed", C.c_int), ("tx", C.c_int), ("ty", C.c_int), ("sk", C.c_int), ("per", C.c_int),
+                ("last", C.c_int), ("launch", C.c_int)]
+
+
 class ConvertJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ld", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("gather", C.c_void_p),
                 ("plain", C.c_void_p), ("ldp", C.c_int), ("transposed", C.c_void_p), ("ldt", C.c_int), ("row_perm_H", C.c_int),
@@ -148,6 +154,7 @@ SIGNATURES = {
     "mmda_gemm": (_I, [C.POINTER(GemmArgs), _P]),
     "mmda_gemm_grouped": (_I, [C.POINTER(GemmArgs), _I, _P]),
     "mmda_gemm_bf16_grouped": (_I, [C.POINTER(GemmBf16Args), _I, _P]),
+    "mmda_gemm_bf16_plan_describe": (_I, [C.POINTER(GemmBf16Args), _I, C.POINTER(C.c_int), C.POINTER(GemmBf16PlanRow), _I]),
     "mmda_convert_bf16": (_I, [C.POINTER(ConvertJob), _I, _P]),
     "mmda_gemm_skinny": (_I, [C.POINTER(SkinnyArgs), _I, _P]),
     "mmda_mx8_quant_bytes": (_I64, [_I, _I]),

@@ -992,6 +992,26 @@ extern "C" int mmda_gemm_bf16_grouped(const mmda_gemm_bf16_args* args, int n, vo
   return mmda_splitk_reduce(P.jobs.data(), (int)P.jobs.size(), s);
 }
 
+// The plan of a call as a table, one row per input problem: for tests and tools that need to know which instance a shape runs on
+extern "C" int mmda_gemm_bf16_plan_describe(const mmda_gemm_bf16_args* args, int n, const int switches[4], mmda_gemm_bf16_plan_row* rows,
+                                            int capacity) {
+  if (!args || !rows || n < 0 || capacity < n) return MMDA_EINVAL;
+  for (int i = 0; i < n; ++i) if (!valid_problem(args[i])) return MMDA_EINVAL;
+  const Switches sw = switches ? Switches{switches[0], switches[1], switches[2], switches[3]} : Switches{1, 2, 8192, 0};
+  const Bf16Plan P = plan_bf16_call(args, n, sw);
+  static_assert(Reg64 == MMDA_BF16_REG64 && Reg128 == MMDA_BF16_REG128 && Dma128 == MMDA_BF16_DMA128 && Dma256 == MMDA_BF16_DMA256, "");
+  for (int i = 0; i < n; ++i) rows[i] = {-1, 0, 0, 0, 0, 0, 0, -1};
+  for (size_t l = 0; l < P.launches.size(); ++l) {
+    const PlanLaunch& L = P.launches[l];
+    for (int k = L.first; k < L.first + L.count; ++k) {
+      const PlanEntry& e = P.entries[k];
+      const int nk = ceil_div(args[e.problem].K, TK), per = ceil_div(nk, e.sk);
+      rows[e.problem] = {(int)L.cls, L.mixed && !is_dma(L.cls) ? 1 : 0, e.tx, e.ty, e.sk, per, nk - (e.sk - 1) * per, (int)l};
+    }
+  }
+  return (int)P.launches.size();
+}
+
 extern "C" int mmda_debug_gemm_dma_mode(int mode) {       // tools/ only: ablate the DMA kernel's k-loop (results are then wrong)
   return hipMemcpyToSymbol(HIP_SYMBOL(g_dma_dbg), &mode, sizeof(int)) == hipSuccess ? MMDA_OK : MMDA_ELAUNCH;
 }

@@ -105,30 +105,73 @@ def convert_bf16(jobs):
     return outs
 
 
-def gemm_bf16_grouped(problems):
-    """problems: list of dicts A[M, lda] bf16, B[N, ldb] bf16 (both K-major), K, optional out/bias/bias2/bias_grad/bias_grad2/accumulate/alpha.
-    C = alpha * A[:, :K] @ B[:, :K]^T + bias + bias2 (+C); bias_grad[m] += sum_k A[m, k].  One launch per 16 problems."""
-    lib = load()
+def _gemm_bf16_args(problems, plan_only=False):
+    """The mmda_gemm_bf16_args array of a call and its output tensors (allocated here unless given).  plan_only: nothing is allocated,
+    and a problem may stand in for its operands by shape alone -- lda / ldb instead of A / B, optional A_addr / B_addr / C_addr / ldc
+    (integers; only their alignment matters), True for a bias / bias_grad that would be given."""
+    FAKE = 1 << 20
+
+    def addr(t):
+        if plan_only and (t is None or isinstance(t, (bool, int))):
+            return (FAKE if t is True else int(t)) if t else None
+        return ptr(t)
+
     arr = (_lib.GemmBf16Args * len(problems))()
     outs = []
     for g, p in zip(arr, problems):
-        A, B = p["A"], p["B"]
+        A, B = p.get("A"), p.get("B")
         tn = bool(p.get("tn", False))
-        assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and (tn or (A.is_contiguous() and B.is_contiguous()))
-        # tn: A is (K, lda) with M <= lda columns in use, B is (K, ldb): C = A[:K, :M]^T @ B[:K, :N]
-        M, N, K = (p["M"], p["N"], p["K"]) if tn else (A.shape[0], B.shape[0], p["K"])
-        g.tn = int(tn); g.perm_m_H = int(p.get("perm_m_H", 0))
+        if plan_only and A is None:
+            M, N, K, lda, ldb = p["M"], p["N"], p["K"], p["lda"], p["ldb"]
+            g.A = p.get("A_addr", FAKE); g.B = p.get("B_addr", FAKE)
+        else:
+            assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and (tn or (A.is_contiguous() and B.is_contiguous()))
+            # tn: A is (K, lda) with M <= lda columns in use, B is (K, ldb): C = A[:K, :M]^T @ B[:K, :N]
+            M, N, K = (p["M"], p["N"], p["K"]) if tn else (A.shape[0], B.shape[0], p["K"])
+            lda, ldb = (A.stride(0), B.stride(0)) if tn else (A.shape[1], B.shape[1])
+            g.A = ptr(A); g.B = ptr(B)
+        g.tn = int(tn); g.perm_m_H = int(p.get("perm_m_H", 0)); g.perm_n_H = int(p.get("perm_n_H", 0))
         out = p.get("out")
-        if out is None:
+        if out is None and not plan_only:
             out = torch.zeros((M, N), device=A.device, dtype=torch.float32)
-        g.M = M; g.N = N; g.K = K; g.A = ptr(A); g.lda = A.stride(0) if tn else A.shape[1]; g.B = ptr(B); g.ldb = B.stride(0) if tn else B.shape[1]
-        g.C = ptr(_f(out)); g.ldc = N
-        g.bias = ptr(p.get("bias")); g.bias2 = ptr(p.get("bias2"))
-        g.bias_grad = ptr(p.get("bias_grad")); g.bias_grad2 = ptr(p.get("bias_grad2"))
+        g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb
+        if out is None:
+            g.C = p.get("C_addr", FAKE); g.ldc = p.get("ldc", N)
+        else:
+            # `out` may be an (M, N) window of a wider buffer: its row stride is the leading dimension
+            g.C = ptr(out if plan_only else _f(out)); g.ldc = out.stride(0) if M > 1 else max(N, out.stride(0))
+        g.bias = addr(p.get("bias")); g.bias2 = addr(p.get("bias2"))
+        g.bias_grad = addr(p.get("bias_grad")); g.bias_grad2 = addr(p.get("bias_grad2"))
         g.accumulate = int(p.get("accumulate", False)); g.alpha = p.get("alpha", 1.0)
         outs.append(out)
-    check(lib.mmda_gemm_bf16_grouped(arr, len(problems), stream_ptr()), "mmda_gemm_bf16_grouped")
+    return arr, outs
+
+
+def gemm_bf16_grouped(problems):
+    """problems: list of dicts A[M, lda] bf16, B[N, ldb] bf16 (both K-major), K, optional out/bias/bias2/bias_grad/bias_grad2/accumulate/
+    alpha/perm_n_H/perm_m_H.  C = alpha * A[:, :K] @ B[:, :K]^T + bias + bias2 (+C); bias_grad[m] += sum_k A[m, k].  `out` may be a
+    row-strided (M, N) window of a larger buffer.  One launch per 16 problems."""
+    arr, outs = _gemm_bf16_args(problems)
+    check(load().mmda_gemm_bf16_grouped(arr, len(problems), stream_ptr()), "mmda_gemm_bf16_grouped")
     return outs
+
+
+BF16_CLASSES = ("Reg64", "Reg128", "Dma128", "Dma256")
+
+
+def gemm_bf16_plan(problems, switches=None):
+    """What gemm_bf16_grouped(problems) would launch (mmda_gemm_bf16_plan_describe: host code only, works without a GPU).  switches:
+    (dma_on, dma_stages, dma_min_rows, dma_tall) in place of the MMDA_GEMM_DMA* environment, None = the defaults (1, 2, 8192, 0).
+    Returns (rows, launches): one dict per problem -- cls (a name of BF16_CLASSES, None for an empty problem), mixed, tx, ty, sk, per,
+    last, launch -- and the number of GEMM launches.  Problems may be given by shape alone (see _gemm_bf16_args)."""
+    arr, _ = _gemm_bf16_args(problems, plan_only=True)
+    rows = (_lib.GemmBf16PlanRow * max(1, len(problems)))()
+    sw = None if switches is None else (C.c_int * 4)(*[int(x) for x in switches])
+    n = load().mmda_gemm_bf16_plan_describe(arr, len(problems), sw, rows, len(problems))
+    if n < 0:
+        check(n, "mmda_gemm_bf16_plan_describe")
+    return [dict(cls=BF16_CLASSES[r.cls] if r.cls >= 0 else None, mixed=bool(r.mixed), tx=r.tx, ty=r.ty, sk=r.sk, per=r.per,
+                 last=r.last, launch=r.launch) for r in rows[:len(problems)]], n
 
 
 def gemm_skinny(problems):

@@ -167,8 +167,10 @@ def test_gemm_bf16_tn_form_weight_gradient(M, N, K, lda, ldb, a0, b0):
 
 def test_gemm_bf16_split_k_is_bitwise_reproducible():
     """Split-K combines through per-slice slabs summed in slice order by a reduce launch (splitk.hip), not through float atomics: the
-    weight-gradient launch of an LSTM layer (tn form, bias-gradient column, accumulate; long K, few tiles -> split) twice on the same
-    inputs gives the same bits -- in the register-staged kernel (K = 1600) and in the LDS-DMA kernel (K = 12800)."""
+    weight-gradient launch of an LSTM layer (tn form, bias-gradient column, accumulate) twice on the same inputs gives the same bits.
+    What runs, by ops.gemm_bf16_plan (test_gemm_bf16_plan_cpu.py pins it): at K = 1600 both problems stay whole on the register-staged
+    64 x 64 mixed instance (25 k-tiles: no split below 128); at K = 12800 the first is split in 9 on the LDS-DMA kernel and the second,
+    whose hseq window starts off the 16-byte grid, in 10 on the register-staged one -- both split policies behind one reduce launch."""
     from mmda_amd import ops
     torch.manual_seed(77)
     for K in (1600, 12800):
