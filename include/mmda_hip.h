@@ -535,6 +535,42 @@ int mmda_clamp_adam_sum_runs(float* p, const float* acc, const float* g, float* 
                              void* stream);
 int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_avg, const mmda_run* runs, int n_runs, int64_t items, float lr,
                             float alpha, float eps, float clip, float grad_scale, void* stream);
+/* Optimizer settings beyond lr: Adam's betas and eps, weight decay, and a gradient scale that lives on the device.
+ *   weight_decay > 0, decoupled == 0 (torch.optim.Adam(weight_decay)): g' = clamp(g grad_scale, +-clip), g'' = fma(wd, p, g'); moments
+ *     and update from g''.
+ *   weight_decay > 0, decoupled != 0 (torch.optim.AdamW): p <- fma(-(lr wd), p, p) first (lr wd made in double, rounded once), then the
+ *     plain update from g' on the decayed p.
+ *   scale_dev != NULL: one float on the device; grad_scale * *scale_dev, rounded once, takes grad_scale's place.  The host never reads
+ *     it: it is the coefficient mmda_grad_norm wrote in front of this launch on the same stream (clip_grad_norm_).
+ * Every rounding is spelled out and the rule is the same element function under every layout below, so an element gets the same bits
+ * through the dense launch, a run table and the rows form.  weight_decay == 0 and scale_dev == NULL: the launch, and the bits, of the
+ * entries above.  0 <= beta < 1, eps >= 0, weight_decay >= 0, else MMDA_EINVAL.
+ * mmda_clamp_adam_opts: what mmda_clamp_adam, _sum, _runs and _sum_runs cover.  acc == NULL: the gradient is g, else acc + g;
+ *   runs == NULL with n_runs == items == 0: the dense range of n floats, else the run table (n unused).
+ * mmda_clamp_adam_rows_opts: mmda_clamp_adam_rows with the settings. */
+typedef struct mmda_adam_opts {
+  float beta1, beta2, eps, weight_decay;
+  int decoupled;
+  const float* scale_dev;
+} mmda_adam_opts;
+int mmda_clamp_adam_opts(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const mmda_run* runs, int n_runs,
+                         int64_t items, float lr, float clip, float grad_scale, int step, const mmda_adam_opts* opts, void* stream);
+int mmda_clamp_adam_rows_opts(float* p, const float* g, float* m, float* v, int rows, int dim, const unsigned char* mask, int want, float lr,
+                              float clip, float grad_scale, int step, const mmda_adam_opts* opts, void* stream);
+/* torch.nn.utils.clip_grad_norm_ in two halves, nothing of it read by the host.
+ * mmda_grad_norm: the global L2 norm of the gradient g (acc != NULL: acc + g, the one fp32 add of mmda_clamp_adam_sum) over n floats,
+ *   or -- runs != NULL -- over the runs of a table, where no float outside a run is loaded.  Squares are summed in double (exact
+ *   products), per lane, then in a fixed order per wave, per block and over the blocks' partials: no atomics, equal bits on every run.
+ *   out2[0] = norm = (float)(grad_scale sqrt(sum)), out2[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32.  Nothing to sum: 0 and 1.
+ *   partials: device doubles, 8-byte aligned, at least mmda_grad_norm_partials(n) (dense) or mmda_grad_norm_partials(items) (runs) of
+ *   them (at most 2048); a smaller partials_capacity, max_norm < 0 or g / acc not 16-byte aligned: MMDA_EINVAL.  Two launches.
+ * mmda_grad_scale: g[i] *= *scale_dev over n floats or over the runs of a table, in place (one launch): with out2 + 1 of the call
+ *   above, clip_grad_norm_'s g.mul_(clip_coef).  mmda_clamp_adam_opts with scale_dev = out2 + 1 and grad_scale = 1 gives the same
+ *   update without writing the gradient. */
+int64_t mmda_grad_norm_partials(int64_t n_or_items);
+int mmda_grad_norm(const float* g, const float* acc, int64_t n, const mmda_run* runs, int n_runs, int64_t items, float max_norm,
+                   float grad_scale, double* partials, int64_t partials_capacity, float* out2, void* stream);
+int mmda_grad_scale(float* g, int64_t n, const mmda_run* runs, int n_runs, int64_t items, const float* scale_dev, void* stream);
 
 /* ============================================================================================== whole-model API
  * The reference's per-batch loop body (solver.py:139-186) as five calls.  `mmda_misa` is the native runtime object
@@ -674,6 +710,22 @@ int mmda_misa_zero_act_grads(mmda_misa* m, void* stream);
 /* solver.py:185-186: clip_grad_value_(clip) + Adam over the whole bucket; grad_scale = 1/world after an all-reduce
  * (mmda_misa_set_embed_update 1 / 2: over the non-embedding prefix, plus the pending rows update in mode 1) */
 int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream);
+/* The optimizer's settings, kept by the handle: every Adam launch of mmda_misa_train_step(_encoded), mmda_misa_adam_step,
+ * mmda_misa_adam_step_accumulated, the sparse rows update and the deferred table's replay reads opts' betas, eps, weight decay and
+ * decay kind (opts->scale_dev is not kept).  opts == NULL: the defaults -- betas 0.9 / 0.999, eps 1e-8, no decay -- under which
+ * every launch and every bit is what it was without this call.  Decay covers what the dense launch covers: with the sparse table the
+ * table's rows follow SparseAdam, which has none.
+ * clip_norm > 0 (0 = off): torch.nn.utils.clip_grad_norm_(clip_norm) in front of clip_grad_value_ and the update.  No update may
+ *   precede the norm, so a training step then runs its backward pass as it does for do_adam = 0 (no early optimizer pass, event join),
+ *   followed by mmda_grad_norm over the gradient bucket (the trainable runs of it when parameters are frozen; acc + G with
+ *   grad_scale = 1/N in the accumulated step) and ONE Adam launch over the bucket with scale_dev = the coefficient.  Norm and coefficient
+ *   stay in the workspace, two floats at mmda_misa_tensor_offset("grad_norm").
+ * MMDA_EINVAL with nothing changed: a beta outside [0, 1), eps < 0, weight_decay < 0, clip_norm < 0, or betas / eps that change while
+ *   rows of a deferred table are stale (flush first).
+ * The stepping entries return MMDA_EINVAL in front of their first launch for: weight_decay > 0 with the deferred table bound (its
+ *   replay ring holds two scalars per update, a decayed zero-gradient step needs a third); clip_norm > 0 with embed_update sparse or
+ *   the deferred table (their rows are updated where the row sums become final, before a norm exists). */
+int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, float clip_norm);
 /* One optimizer step from N micro-batches (config.accum_steps; the arithmetic of mmda_grad_accumulate above).  Every micro-batch is
  * mmda_misa_train_step with do_adam = 0; behind each but the last call mmda_misa_grad_accumulate, behind the last
  * mmda_misa_adam_step_accumulated with grad_scale = 1/N.  The runtime owns none of the memory:

@@ -124,6 +124,12 @@ class Run(C.Structure):
     _fields_ = [("begin", C.c_int64), ("len", C.c_int64), ("first", C.c_int64)]
 
 
+class AdamOpts(C.Structure):
+    """mmda_adam_opts: Adam's settings beyond lr (scale_dev: one device float that multiplies grad_scale, or None)"""
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("decoupled", C.c_int),
+                ("scale_dev", C.c_void_p)]
+
+
 class InferSrc(C.Structure):
     """mmda_infer_src: what a forward left in the workspace, B columns"""
     _fields_ = [("scores", C.c_void_p), ("labels", C.c_void_p), ("tcp", C.c_void_p), ("hfused", C.c_void_p), ("x6", C.c_void_p),
@@ -228,6 +234,12 @@ SIGNATURES = {
     "mmda_clamp_adam_runs": (_I, [_P, _P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_clamp_adam_sum_runs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_clamp_rmsprop_runs": (_I, [_P, _P, _P, _P, _I, _I64, _F, _F, _F, _F, _F, _P]),
+    "mmda_clamp_adam_opts": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I, _I64, _F, _F, _F, _I, C.POINTER(AdamOpts), _P]),
+    "mmda_clamp_adam_rows_opts": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _F, _I, C.POINTER(AdamOpts), _P]),
+    "mmda_grad_norm_partials": (_I64, [_I64]),
+    "mmda_grad_norm": (_I, [_P, _P, _I64, _P, _I, _I64, _F, _F, _P, _I64, _P, _P]),
+    "mmda_grad_scale": (_I, [_P, _I64, _P, _I, _I64, _P, _P]),
+    "mmda_misa_set_adam": (_I, [_P, C.POINTER(AdamOpts), _F]),
     "mmda_misa_create": (_I, [C.POINTER(MisaConfig), C.POINTER(C.c_void_p)]),
     "mmda_misa_destroy": (None, [_P]),
     "mmda_misa_num_params": (_I, [_P]),

@@ -23,6 +23,16 @@ def str2bool(v):
     raise argparse.ArgumentTypeError("Boolean value expected.")
 
 
+def _json_object(text):
+    import json
+    value = json.loads(text)
+    if not isinstance(value, dict):
+        raise argparse.ArgumentTypeError("a JSON object is expected")
+    if "betas" in value:
+        value["betas"] = tuple(value["betas"])
+    return value
+
+
 class Config(object):
     """Attribute bag (reference config.py:71-96).  'optimizer' names resolve to mmda_amd.optim classes."""
 
@@ -73,6 +83,10 @@ DEFAULTS = dict(
     # optimizer steps made from this many consecutive batches each (gradient accumulation with data-parallel semantics: the mean over
     # micro-batches of their gradients, then clip + Adam -- what that many ranks would compute); 1 = the reference's loop
     accum_steps=1,
+    # the optimizer beyond its name and lr: optimizer_kwargs go to its constructor (betas, eps, weight_decay ...); clip_norm is
+    # torch.nn.utils.clip_grad_norm_'s max_norm, applied in front of `clip` (None = off).  optimizer="AdamW" without a weight_decay among
+    # its kwargs takes the weight_decay above -- the reference's flag, which optimizer="Adam" keeps ignoring as the reference does.
+    optimizer_kwargs={}, clip_norm=None,
 )
 
 
@@ -83,6 +97,10 @@ def get_config(parse=True, **optional_kwargs):
     for k, v in DEFAULTS.items():
         if isinstance(v, bool):
             parser.add_argument(f"--{k}", type=str2bool, default=v)
+        elif k == "optimizer_kwargs":                          # a JSON object: --optimizer_kwargs '{"betas": [0.9, 0.98]}'
+            parser.add_argument(f"--{k}", type=_json_object, default=dict(v))
+        elif k == "clip_norm":
+            parser.add_argument(f"--{k}", type=float, default=None)
         elif v is None:
             parser.add_argument(f"--{k}", default=None)
         else:
@@ -103,7 +121,7 @@ def get_config(parse=True, **optional_kwargs):
 
 def make_config(**kw):
     """Programmatic construction with the reference's defaults."""
-    d = dict(DEFAULTS)
+    d = dict(DEFAULTS, optimizer_kwargs={})
     d.update(kw)
     if "word2id" not in d:
         d["word2id"] = range(d["vocab_size"])

@@ -176,17 +176,43 @@ struct RowSparseAdam {
     a.P[o] = p; a.M[o] = m; a.V[o] = v;
   }
 };
-// ---- dense Adam, one element (optim.hip: the Adam functor under every walker; the deferred table update below)
+// ---- dense Adam, one element (optim.hip: the Adam functors under every walker; the deferred table update below)
+// moments and update from a gradient that is already scaled, clamped (and, under L2 decay, decayed)
+__device__ __forceinline__ void adam1_update(float& p, float g, float& m, float& v, float b1, float b2, float eps, float step_size,
+                                             float inv_bc2_sqrt) {
+  m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));
+  v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));
+  const float denom = __fmaf_rn(sqrtf(v), inv_bc2_sqrt, eps);
+  p = __fmaf_rn(-step_size, __fdiv_rn(m, denom), p);
+}
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
                                       float gscale, float step_size, float inv_bc2_sqrt) {
   // every rounding spelled out: the dense kernel and the per-row kernel below must give the same bits (the fused step runs part of the
   // bucket through each), whatever the compiler would contract in either loop
   g = __fmul_rn(g, gscale);
   g = fminf(fmaxf(g, -clip), clip);
-  m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));
-  v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));
-  const float denom = __fmaf_rn(sqrtf(v), inv_bc2_sqrt, eps);
-  p = __fmaf_rn(-step_size, __fdiv_rn(m, denom), p);
+  adam1_update(p, g, m, v, b1, b2, eps, step_size, inv_bc2_sqrt);
+}
+// Adam with weight decay.  decay: MMDA_DECAY_L2 (torch.optim.Adam(weight_decay = wd)): the scaled, clamped gradient takes wd p in one
+// fma and everything follows from that; MMDA_DECAY_DECOUPLED (torch.optim.AdamW): p <- p - (lr wd) p in one fma first, then adam1's
+// moments and update on the decayed p (lr_wd = lr wd, made on the host in double and rounded once, like step_size); anything else:
+// adam1.  Launch-uniform.
+enum { MMDA_DECAY_NONE = 0, MMDA_DECAY_L2 = 1, MMDA_DECAY_DECOUPLED = 2 };
+__device__ __forceinline__ void adam1_decayed(float& p, float g, float& m, float& v, float b1, float b2, float eps, float clip,
+                                              float gscale, float step_size, float inv_bc2_sqrt, int decay, float wd, float lr_wd) {
+  g = __fmul_rn(g, gscale);
+  g = fminf(fmaxf(g, -clip), clip);
+  if (decay == MMDA_DECAY_L2) g = __fmaf_rn(wd, p, g);
+  else if (decay == MMDA_DECAY_DECOUPLED) p = __fmaf_rn(-lr_wd, p, p);
+  adam1_update(p, g, m, v, b1, b2, eps, step_size, inv_bc2_sqrt);
+}
+
+// Wave-wide sum of doubles in a fixed order, the same value in every lane: an xor butterfly (a double has no DPP add; the six round
+// trips are paid once per workgroup of a streaming reduction, where they do not show).
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) v += __shfl_xor(v, o);
+  return v;
 }
 
 // ---- deferred dense update of the embedding table (embed_update = deferred): dense Adam's result, without a pass over the table.  A row

@@ -50,12 +50,19 @@ int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      /
 // The launch behind mmda_clamp_adam, _sum, _runs and _sum_runs: clamp + Adam step h.step over n floats (table == nullptr) or over the
 // trainable runs of a table (n unused), with the gradient g or, acc != nullptr, acc + g.  w.flag != nullptr: the launch does not
 // complete before *w.flag reaches w.value (flag joins, common.h) and goes out even where there is nothing to update.
-struct AdamHyper { float lr, beta1, beta2, eps, clip, grad_scale; int step; };
+// weight_decay > 0: L2 (decoupled == 0) or decoupled decay; scale_dev != nullptr: grad_scale is multiplied by that device float.  The
+// three default to "none", where the launch is the one it has always been.
+struct AdamHyper { float lr, beta1, beta2, eps, clip, grad_scale; int step; float weight_decay = 0.f; int decoupled = 0; const float* scale_dev = nullptr; };
 struct RunTable { const mmda_run* runs; int n_runs; int64_t items; };
 struct FlagWait { const unsigned* flag; unsigned value; unsigned* err; };
 constexpr FlagWait kNoWait{nullptr, 0u, nullptr};
 int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const RunTable* table, const AdamHyper& h,
                      const FlagWait& w, void* stream);
+bool mmda_adam_opts_valid(const mmda_adam_opts* o);           // the ranges mmda_misa_set_adam and the *_opts entries accept
+// The launches behind mmda_grad_norm: the norm of g (acc + g) over n floats or over a table's runs, block partials in `partials`
+// (doubles; mmda_grad_norm_partials sizes it), then norm and clip coefficient in out2[0], out2[1].  An empty range writes 0 and 1.
+int mmda_grad_norm_launch(const float* g, const float* acc, int64_t n, const RunTable* table, float max_norm, float grad_scale,
+                          double* partials, int64_t partials_capacity, float* out2, void* stream);
 // frozen parameters: mmda_runs_build that merges no two ranges across one of `cuts`
 int64_t mmda_runs_build_cut(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, const int64_t* cuts, int n_cuts,
                             mmda_run* out, int* n_out);

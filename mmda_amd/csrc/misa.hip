@@ -107,6 +107,13 @@ struct mmda_misa {
   // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
   // recurrence runs there, on the side stream (set by mmda_misa_train_step around its backward pass)
   int adam_early_on = 0; float ae_lr = 0.f, ae_clip = 0.f; int ae_step = 0; int64_t adam_early_done = 0;
+  // The optimizer's settings (mmda_misa_set_adam): every Adam launch of the handle reads them; scale_dev is not kept (a step with
+  // clip_norm > 0 points its launches at gnorm[1]).  clip_norm > 0: clip_grad_norm_ in front of the update -- no update may precede the
+  // norm, so such a step takes no early optimizer pass.  gnorm: norm and coefficient of the last such step; gnorm_parts: the norm
+  // launch's block partials (doubles).
+  mmda_adam_opts adam = {0.9f, 0.999f, 1e-8f, 0.f, 0, nullptr};
+  float clip_norm = 0.f;
+  int64_t gnorm = -1, gnorm_parts = -1;
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
   int embed_update = EU_DENSE;
@@ -392,11 +399,13 @@ int64_t layout(mmda_misa* m, int B, int T, bool commit) {
   o->d_logits = k.take((int64_t)B * NC); o->d_hfused = k.take(6 * BH); o->d_x1 = k.take(6 * BH); o->d_f2 = k.take(6 * BH);
   o->d_f1 = k.take((int64_t)6 * B * FFN); o->d_attn_out = k.take(6 * BH); o->d_ctx = k.take(6 * BH);
   o->d_qkv = k.take(6 * BH * 3); o->d_z = k.take(3 * BH); o->d_dom_h = k.take(3 * BH); o->d_dom_z = k.take(3 * BH);
+  // ---- clip_norm: the gradient norm and its clip coefficient, and the norm launch's block partials (doubles, two floats each)
+  o->gnorm = k.take(4); o->gnorm_parts = k.take(2 * mmda_grad_norm_partials(INT64_MAX));
   if (commit) {
     std::map<std::string, int64_t>& t = m->tens;
     t.clear();
     t["scores"] = m->scores; t["labels"] = m->labels; t["tcp"] = m->tcp; t["logits"] = m->logits; t["hfused"] = m->hfused;
-    t["x6"] = m->x6; t["orig"] = m->orig; t["recon"] = m->recon; t["dom"] = m->dom; t["losses"] = m->losses;
+    t["x6"] = m->x6; t["orig"] = m->orig; t["recon"] = m->recon; t["dom"] = m->dom; t["losses"] = m->losses; t["grad_norm"] = m->gnorm;
     t["utt_t"] = m->mod[0].utt; t["utt_v"] = m->mod[1].utt; t["utt_a"] = m->mod[2].utt;
     t["d_scores"] = m->d_scores; t["d_tcp"] = m->d_tcp; t["d_x6"] = m->d_x6; t["d_orig"] = m->d_orig;
     t["d_recon"] = m->d_recon; t["d_dom"] = m->d_dom;
@@ -662,20 +671,43 @@ int runs_ready(mmda_misa* m, void* stream) {
   m->runs_dirty = 0;
   return MMDA_OK;
 }
-// The model's Adam (the reference gives torch.optim.Adam nothing but lr)
-constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kAdamEps = 1e-8f;
+// The model's Adam unless mmda_misa_set_adam says otherwise (the reference gives torch.optim.Adam nothing but lr)
+constexpr mmda_adam_opts kAdamDefaults = {0.9f, 0.999f, 1e-8f, 0.f, 0, nullptr};
 // clamp + Adam over the bucket range [lo, hi) with the gradient G, or acc + G (acc != nullptr: the accumulator, laid out like the
 // bucket): the dense stream, or -- frozen parameters -- the trainable runs of that range, where a range with nothing to train launches
 // nothing but for a waiter (w.flag != nullptr).
+// scale_dev: the clip coefficient of a step with clip_norm > 0 (bucket_norm below), else nullptr.
 int bucket_adam(mmda_misa* m, int64_t lo, int64_t hi, const float* acc, float lr, float clip, float grad_scale, int step, const FlagWait& w,
-                void* stream) {
-  const AdamHyper h{lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step};
+                void* stream, const float* scale_dev = nullptr) {
+  const AdamHyper h{lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step, m->adam.weight_decay, m->adam.decoupled, scale_dev};
   if (!masked(m)) return mmda_adam_launch(m->P + lo, acc ? acc + lo : nullptr, m->G + lo, m->M1 + lo, m->V1 + lo, hi - lo, nullptr, h, w, stream);
   int r0 = 0, n = 0; int64_t items = 0;
   runs_slice(m, lo, hi, &r0, &n, &items);
   if (n > 0 && (m->runs_dirty || !m->runs_dev)) return MMDA_EINVAL;      // (every entry that gets here called runs_ready first)
   const RunTable t{n > 0 ? m->runs_dev + r0 : nullptr, n, items};
   return mmda_adam_launch(m->P, acc, m->G, m->M1, m->V1, 0, &t, h, w, stream);
+}
+// clip_norm > 0: the norm of the gradient the step is about to apply -- G or acc + G over [0, grad_floats), the trainable runs of it
+// when parameters are frozen -- and the clip coefficient, into gnorm[0], gnorm[1]
+int bucket_norm(mmda_misa* m, const float* acc, float grad_scale, void* stream) {
+  if (!m->ws || m->gnorm < 0) return MMDA_EINVAL;
+  double* parts = reinterpret_cast<double*>(m->ws + m->gnorm_parts);
+  const int64_t cap = mmda_grad_norm_partials(INT64_MAX);
+  const int64_t hi = grad_floats(m);
+  if (!masked(m)) return mmda_grad_norm_launch(m->G, acc, hi, nullptr, m->clip_norm, grad_scale, parts, cap, m->ws + m->gnorm, stream);
+  int r0 = 0, n = 0; int64_t items = 0;
+  runs_slice(m, 0, hi, &r0, &n, &items);
+  if (n > 0 && (m->runs_dirty || !m->runs_dev)) return MMDA_EINVAL;
+  const RunTable t{n > 0 ? m->runs_dev + r0 : nullptr, n, items};
+  return mmda_grad_norm_launch(m->G, acc, 0, &t, m->clip_norm, grad_scale, parts, cap, m->ws + m->gnorm, stream);
+}
+// what no step does (checked in front of its first launch, so a refused call changes nothing): decay under the deferred table -- the
+// replay ring holds two scalars per update, a decayed zero-gradient step needs a third; a norm clip with a table whose rows are updated
+// where their sums become final, before a norm exists
+bool adam_settings_refused(const mmda_misa* m) {
+  if (m->adam.weight_decay > 0.f && m->df_row_step) return true;
+  if (m->clip_norm > 0.f && (m->embed_update == EU_SPARSE || m->df_row_step)) return true;
+  return false;
 }
 // the table from one flag per parameter (nullptr: everything trains)
 int apply_trainable(mmda_misa* m, const unsigned char* flags) {
@@ -1049,6 +1081,18 @@ int ffn_fp8(mmda_misa* m, float p_tf, uint64_t seed, void* stream) {
 }
 }  // namespace
 
+extern "C" int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, float clip_norm) {
+  if (!m || !(clip_norm >= 0.f)) return MMDA_EINVAL;
+  const mmda_adam_opts o = opts ? *opts : kAdamDefaults;
+  if (!mmda_adam_opts_valid(&o)) return MMDA_EINVAL;
+  // deferred table: the updates that stale rows are still to replay were made with the old betas and eps
+  const bool moved = o.beta1 != m->adam.beta1 || o.beta2 != m->adam.beta2 || o.eps != m->adam.eps;
+  if (moved && m->df_row_step && m->df_flushed != m->df_seq) return MMDA_EINVAL;
+  m->adam = o; m->adam.scale_dev = nullptr;
+  m->clip_norm = clip_norm;
+  return MMDA_OK;
+}
+
 extern "C" int mmda_misa_set_embed_update(mmda_misa* m, int mode) {
   if (!m) return MMDA_EINVAL;
   if (mode != EU_DENSE && mode != EU_SPARSE && mode != EU_FROZEN) return MMDA_EINVAL;
@@ -1078,7 +1122,7 @@ extern "C" int mmda_misa_embed_flush(mmda_misa* m, void* stream) {
   if (!m->P || !m->M1 || !m->V1) return MMDA_EINVAL;
   if (m->df_flushed == m->df_seq) return MMDA_OK;          // no update since the last flush: nothing is stale, nothing is launched
   const int rc = mmda_embed_rows_flush(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window,
-                                       m->cfg.d_t, m->cfg.vocab, kBeta1, kBeta2, kAdamEps, m->df_seq, stream);
+                                       m->cfg.d_t, m->cfg.vocab, m->adam.beta1, m->adam.beta2, m->adam.eps, m->df_seq, stream);
   if (!rc) m->df_flushed = m->df_seq;
   return rc;
 }
@@ -1562,7 +1606,7 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   if (m->plan.embed_deferred) {
     if (!m->M1 || !m->V1) return MMDA_EINVAL;
     x.rc = mmda_embed_rows_catch_up(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, t_ids,
-                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, kBeta1, kBeta2, kAdamEps, m->df_seq, stream);
+                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, m->adam.beta1, m->adam.beta2, m->adam.eps, m->df_seq, stream);
     if (x.rc) return x.rc;
   }
   const float* xin[3] = {WS(m->mod[0].x), v, a};
@@ -2046,7 +2090,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     }
     SparseAdamArgs ad;
     rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, m->ae_lr,
-                               kBeta1, kBeta2, kAdamEps, m->ae_clip, 1.0f, m->ae_step);
+                               m->adam.beta1, m->adam.beta2, m->adam.eps, m->ae_clip, 1.0f, m->ae_step);
     if (rc) return;
     if (m->esort_valid) {
       if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
@@ -2078,7 +2122,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
       sorted = reinterpret_cast<const unsigned*>(WS(m->esort));
       m->esort_valid = 0;
     }
-    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, kBeta1, kBeta2, kAdamEps, m->ae_clip, 1.0f, m->ae_step, false, s);
+    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, m->adam.beta1, m->adam.beta2, m->adam.eps, m->ae_clip, 1.0f, m->ae_step, false, s);
   } else if (P.embed_update == EU_DENSE) {
     // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     if (m->esort_valid) {
@@ -2204,19 +2248,22 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 
 // =============================================================================================== optimizer / step
 extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
-  if (!m || !m->P || !m->G || !m->M1 || !m->V1) return MMDA_EINVAL;
+  if (!m || !m->P || !m->G || !m->M1 || !m->V1 || adam_settings_refused(m)) return MMDA_EINVAL;
+  const bool norm = m->clip_norm > 0.f;
+  if (norm && !m->ws) return MMDA_EINVAL;
   int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;  // frozen parameters: the trainable runs only
-  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, kNoWait, stream);
+  if (!rc && norm) rc = bucket_norm(m, nullptr, grad_scale, stream);
+  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, kNoWait, stream, norm ? m->ws + m->gnorm + 1 : nullptr);
   if (!rc && m->embed_update == EU_SPARSE && m->eu_pending) {
     // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
     m->eu_pending = 0;
     if (!m->ws || m->T <= 0) return MMDA_EINVAL;
     rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->eu_ids, m->B * m->T, m->cfg.d_t,
-                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step,
+                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step,
                                      stream);
   }
   if (!rc && m->embed_update == EU_DENSE && m->df_row_step && m->eu_pending)
-    rc = mmda_misa_embed_deferred_step(m, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step, stream);
+    rc = mmda_misa_embed_deferred_step(m, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step, stream);
   return rc;
 }
 
@@ -2252,15 +2299,19 @@ extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, i
                                                int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream) {
   // (everything is checked in front of the dense launch: a refused call changes nothing)
   if (!accum_ready(m) || !m->M1 || !m->V1 || step < 1 || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
+  if (adam_settings_refused(m)) return MMDA_EINVAL;
+  const bool norm = m->clip_norm > 0.f;
+  if (norm && !m->ws) return MMDA_EINVAL;
   int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;
-  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, kNoWait, stream);
+  if (!rc && norm) rc = bucket_norm(m, acc, grad_scale, stream);
+  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, kNoWait, stream, norm ? m->ws + m->gnorm + 1 : nullptr);
   if (!rc && m->embed_update == EU_SPARSE) {
     const int n = (int)(list_used + (int64_t)m->B * m->T);
     rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
     // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
     if (!rc)
       rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, list_ids, n, m->cfg.d_t, list_rows, nullptr, 0,
-                                       m->cfg.vocab, lr, kBeta1, kBeta2, kAdamEps, clip, grad_scale, step, stream);
+                                       m->cfg.vocab, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step, stream);
   }
   return rc;
 }
@@ -2274,6 +2325,11 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   // the gradient bucket is cleared on the side stream beside the forward pass's fusion block (not at the start of the step: the
   // side stream's first job there, packing W_hh, is what the first recurrent kernel waits for)
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
+  if (do_adam && adam_settings_refused(m)) return MMDA_EINVAL;
+  // clip_norm: no update may precede the norm, so the backward pass runs as it does without an optimizer step (no early pass, event
+  // join); the norm and one launch over the whole bucket follow it
+  const bool norm = do_adam && m->clip_norm > 0.f;
+  const bool early = do_adam && !norm;
   if (masked(m) && do_adam) {                           // frozen parameters: the run table is on the device before the first launch
     if (!m->M1 || !m->V1) return MMDA_EINVAL;
     const int rr = runs_ready(m, stream);
@@ -2293,13 +2349,17 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   rc = mmda_misa_losses(m, emo, 1, stream);
   if (rc) return rc;
   // (the early optimizer pass beside the layer-1 recurrence: faster than one launch for the whole bucket at the end)
-  m->adam_early_on = do_adam ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
+  m->adam_early_on = early ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
   rc = backward_pass(m, t_ids, v, a, lengths, stream);
   m->adam_early_on = 0;
   if (rc) return rc;
   if (m->fj1) { rc = flag_join_fallback(m, stream); m->fj1 = 0; if (rc) return rc; }      // (no stretch took it over: cannot happen)
-  if (m->fj2 && !do_adam) { rc = flag_join_fallback(m, stream); m->fj2 = 0; if (rc) return rc; }
-  if (do_adam) {
+  if (m->fj2 && !early) { rc = flag_join_fallback(m, stream); m->fj2 = 0; if (rc) return rc; }
+  if (norm) {
+    if (!m->M1 || !m->V1) return MMDA_EINVAL;
+    rc = bucket_norm(m, nullptr, 1.0f, stream);
+    if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, 1.0f, step, kNoWait, stream, m->ws + m->gnorm + 1);
+  } else if (do_adam) {
     // the rest of the bucket (layer-1 recurrent layers, embedding -- or everything, if the backward pass stepped nothing early)
     const int64_t o = m->adam_early_done;
     // (flag join: this launch does not complete before the side stream's weight-gradient GEMMs and early optimizer pass have)

@@ -1,6 +1,9 @@
-// clip_grad_value_ + the optimizer's update fused over flat fp32 buckets (reference solver.py:185-186 and :97-99: torch.optim.Adam
-// with lr only -> betas (0.9, 0.999), eps 1e-8, no weight decay; --weight_decay is parsed but never used).  An update rule is an
-// element functor, a memory layout is a walker kernel that takes one; a launch is a walker instantiated with a rule.
+// clip_grad_value_ + the optimizer's update fused over flat fp32 buckets.  The reference builds torch.optim.Adam with lr only
+// (solver.py:97-99: betas (0.9, 0.999), eps 1e-8, no weight decay), and that is what launches by default; betas and eps are arguments
+// of every launch, weight decay (L2 as torch.optim.Adam's, decoupled as torch.optim.AdamW's) and a gradient scale read from device
+// memory (clip_grad_norm_'s coefficient) come with mmda_adam_opts.  An update rule is an element functor, a memory layout is a walker
+// kernel that takes one; a launch is a walker instantiated with a rule.  Also here: the gradient's global L2 norm (grad_norm_kernel)
+// and its in-place scaling (the Scale functor).
 #include "common.h"
 #include "internal.h"
 #include <math.h>
@@ -35,6 +38,46 @@ struct Adam : AdamArgs {
     if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
     adam1(p[e], ge, m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
   }
+};
+// Adam with what mmda_adam_opts adds: weight decay (adam1_decayed(), common.h) and a gradient scale that lives on the device -- the
+// coefficient grad_norm_finish_kernel wrote, never read by the host: gscale * *scale_dev, rounded once, takes gscale's place (with
+// gscale = 1 that is torch's g.mul_(clip_coef)).  The decay kind is a launch-uniform branch, not a template parameter: one scalar
+// compare per element beside 28 B of HBM traffic, against three times the instances under three walkers.  Launches with no decay and
+// no device scale keep the Adam<> instances above.
+struct AdamOptArgs : AdamArgs { int decay; float wd, lr_wd; const float* scale_dev; };
+template <bool kSum>
+struct AdamOpt : AdamOptArgs {
+  __device__ __forceinline__ float scale() const { return scale_dev ? __fmul_rn(gscale, *scale_dev) : gscale; }
+  __device__ __forceinline__ void quad(int64_t q) const {
+    const float gs = scale();
+    float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
+    float4 gg = reinterpret_cast<const float4*>(g)[q];
+    if constexpr (kSum) {
+      const float4 aa = reinterpret_cast<const float4*>(acc)[q];
+      gg.x = __fadd_rn(aa.x, gg.x); gg.y = __fadd_rn(aa.y, gg.y); gg.z = __fadd_rn(aa.z, gg.z); gg.w = __fadd_rn(aa.w, gg.w);
+    }
+    adam1_decayed(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
+  }
+  __device__ __forceinline__ void one(int64_t e) const {
+    float ge = g[e];
+    if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
+    adam1_decayed(p[e], ge, m[e], v[e], b1, b2, eps, clip, scale(), step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+  }
+};
+// g *= *scale_dev in place: clip_grad_norm_'s second half for the unfused loop
+struct Scale {
+  float* g; const float* scale_dev;
+  __device__ __forceinline__ void quad(int64_t q) const {
+    const float s = *scale_dev;
+    float4 gg = reinterpret_cast<float4*>(g)[q];
+    gg.x = __fmul_rn(gg.x, s); gg.y = __fmul_rn(gg.y, s); gg.z = __fmul_rn(gg.z, s); gg.w = __fmul_rn(gg.w, s);
+    reinterpret_cast<float4*>(g)[q] = gg;
+  }
+  __device__ __forceinline__ void one(int64_t e) const { g[e] = __fmul_rn(g[e], *scale_dev); }
 };
 struct RunRmsprop {         // clamp_rmsprop_kernel's (below: the dense launch keeps its one-float-per-lane loop)
   float* p; const float* g; float* sq; float lr, alpha, eps, clip, gscale;
@@ -93,25 +136,88 @@ __global__ __launch_bounds__(256) void rows_kernel(int rows, int dim, const unsi
 // cache).  A quad that lies inside its run goes through quad() like the dense stream's; a quad at a run's end takes the floats of the
 // run one by one, so no float outside a run is loaded or stored -- two runs that share a quad touch disjoint floats of it.  wait_flag:
 // as in stream_kernel (the same flag_wait).
+struct RunItem { int64_t q, e0, e1; };                          // the bucket's quad, and the floats [e0, e1) of it that the run holds
+__device__ __forceinline__ RunItem run_item(const mmda_run* __restrict__ runs, int n_runs, int64_t j) {
+  int lo = 0, hi = n_runs - 1;                                     // the last run whose count is <= j
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (runs[mid].first <= j) lo = mid; else hi = mid - 1;
+  }
+  const mmda_run r = runs[lo];
+  const int64_t q = (r.begin >> 2) + (j - r.first);
+  return {q, max(q << 2, r.begin), min((q << 2) + 4, r.begin + r.len)};
+}
 template <class F>
 __global__ __launch_bounds__(256) void runs_kernel(const mmda_run* __restrict__ runs, int n_runs, int64_t items, F f,
                                                    const unsigned* wait_flag, unsigned wait_value, unsigned* wait_err) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t item0 = n_runs > 0 ? runs[0].first : 0;          // (a slice of a longer table: counts run on from its start)
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
-    const int64_t j = item0 + i;
-    int lo = 0, hi = n_runs - 1;                                   // the last run whose count is <= j
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (runs[mid].first <= j) lo = mid; else hi = mid - 1;
-    }
-    const mmda_run r = runs[lo];
-    const int64_t q = (r.begin >> 2) + (j - r.first);              // the bucket's quad
-    const int64_t e0 = max(q << 2, r.begin), e1 = min((q << 2) + 4, r.begin + r.len);
-    if (e1 - e0 == 4) f.quad(q);
-    else for (int64_t e = e0; e < e1; ++e) f.one(e);
+    const RunItem it = run_item(runs, n_runs, item0 + i);
+    if (it.e1 - it.e0 == 4) f.quad(it.q);
+    else for (int64_t e = it.e0; e < it.e1; ++e) f.one(e);
   }
   if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
+}
+
+// ---- the global L2 norm of the gradient a step is about to apply (torch.nn.utils.clip_grad_norm_)
+// The gradient is g, or acc + g with the one IEEE add the Adam functors make (kSum).  runs == nullptr: the dense range [0, n) in
+// stream_kernel's order, 16 bytes per lane and a scalar tail; otherwise the items of a run table with runs_kernel's mapping, so no float
+// outside a run is loaded (a frozen tensor's gradient slot may hold anything).  The squares are summed in double -- the product of two
+// floats is exact there -- by each lane over its grid-stride items, then in a fixed order inside the wave and across the block's four
+// waves; block b leaves its sum in partials[b].  No atomics: two launches give equal bits.
+template <bool kSum>
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ acc, const float* __restrict__ g, int64_t n,
+                                                        const mmda_run* __restrict__ runs, int n_runs, int64_t items,
+                                                        double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double s = 0.0;
+  auto one = [&](int64_t e) {
+    float ge = g[e];
+    if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
+    s += (double)ge * (double)ge;
+  };
+  auto quad = [&](int64_t q) {
+    float4 gg = reinterpret_cast<const float4*>(g)[q];
+    if constexpr (kSum) {
+      const float4 aa = reinterpret_cast<const float4*>(acc)[q];
+      gg.x = __fadd_rn(aa.x, gg.x); gg.y = __fadd_rn(aa.y, gg.y); gg.z = __fadd_rn(aa.z, gg.z); gg.w = __fadd_rn(aa.w, gg.w);
+    }
+    s += (double)gg.x * (double)gg.x; s += (double)gg.y * (double)gg.y; s += (double)gg.z * (double)gg.z; s += (double)gg.w * (double)gg.w;
+  };
+  if (!runs) {                                                     // launch-uniform
+    const int64_t n4 = n >> 2;
+    for (int64_t i = i0; i < n4; i += stride) quad(i);
+    for (int64_t i = (n4 << 2) + i0; i < n; i += stride) one(i);
+  } else {
+    const int64_t item0 = n_runs > 0 ? runs[0].first : 0;
+    for (int64_t i = i0; i < items; i += stride) {
+      const RunItem it = run_item(runs, n_runs, item0 + i);
+      if (it.e1 - it.e0 == 4) quad(it.q);
+      else for (int64_t e = it.e0; e < it.e1; ++e) one(e);
+    }
+  }
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+// One wave behind it on the stream: lane l adds the partials [l c, (l + 1) c) in block-index order, the 64 lane sums meet in the fixed
+// order of the butterfly.  out[0] = norm = (float)(gscale sqrt(sum)), out[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32:
+// clip_grad_norm_'s two expressions.  nb == 0 (nothing trains): norm 0, coef 1.
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* __restrict__ partials, int nb, float gscale, float max_norm,
+                                                              float* __restrict__ out) {
+  const int c = (nb + 63) >> 6;
+  double s = 0.0;
+  for (int i = threadIdx.x * c; i < min((int)(threadIdx.x + 1) * c, nb); ++i) s += partials[i];
+  s = wave_sum_f64(s);
+  if (threadIdx.x == 0) {
+    const float norm = (float)((double)gscale * sqrt(s));
+    out[0] = norm;
+    out[1] = fminf(1.f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+  }
 }
 
 // ---- gradient accumulation (accum_steps > 1): one optimizer step from the gradients of several micro-batches
@@ -278,6 +384,19 @@ AdamArgs adam_args(float* p, const float* acc, const float* g, float* m, float* 
   return {p, acc, g, m, v, h.beta1, h.beta2, h.eps, h.clip, h.grad_scale, s.step_size, s.inv_bc2_sqrt};
 }
 
+// the decay kind a launch runs with, and lr wd in double, rounded once
+AdamOptArgs adam_opt_args(const AdamArgs& a, const AdamHyper& h) {
+  const int decay = h.weight_decay > 0.f ? (h.decoupled ? MMDA_DECAY_DECOUPLED : MMDA_DECAY_L2) : MMDA_DECAY_NONE;
+  return {a, decay, h.weight_decay, (float)((double)h.lr * (double)h.weight_decay), h.scale_dev};
+}
+bool adam_plain(const AdamHyper& h) { return !(h.weight_decay > 0.f) && !h.scale_dev; }
+bool adam_opts_ok(const mmda_adam_opts* o) {
+  return o && o->beta1 >= 0.f && o->beta1 < 1.f && o->beta2 >= 0.f && o->beta2 < 1.f && o->eps >= 0.f && o->weight_decay >= 0.f;
+}
+AdamHyper adam_hyper(float lr, float clip, float grad_scale, int step, const mmda_adam_opts& o) {
+  return {lr, o.beta1, o.beta2, o.eps, clip, grad_scale, step, o.weight_decay, o.decoupled, o.scale_dev};
+}
+
 template <class F>
 int launch_stream(const char* what, int64_t n, const F& f, const FlagWait& w, void* stream) {
   hipLaunchKernelGGL(stream_kernel<F>, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, n, f, w.flag, w.value, w.err);
@@ -309,7 +428,74 @@ int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float
   auto launch = [&](const auto& f) {
     return table && !empty ? launch_runs(what, *table, f, w, stream) : launch_stream(what, empty ? 0 : n, f, w, stream);
   };
-  return acc ? launch(Adam<true>{a}) : launch(Adam<false>{a});
+  if (adam_plain(h)) return acc ? launch(Adam<true>{a}) : launch(Adam<false>{a});
+  const AdamOptArgs o = adam_opt_args(a, h);
+  return acc ? launch(AdamOpt<true>{o}) : launch(AdamOpt<false>{o});
+}
+
+bool mmda_adam_opts_valid(const mmda_adam_opts* o) { return adam_opts_ok(o); }
+
+// what mmda_clamp_adam, _sum, _runs and _sum_runs cover, with mmda_adam_opts
+extern "C" int mmda_clamp_adam_opts(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const mmda_run* runs,
+                                    int n_runs, int64_t items, float lr, float clip, float grad_scale, int step,
+                                    const mmda_adam_opts* opts, void* stream) {
+  if (!adam_opts_ok(opts) || ((uintptr_t)opts->scale_dev & 3)) return MMDA_EINVAL;
+  const AdamHyper h = adam_hyper(lr, clip, grad_scale, step, *opts);
+  if (!runs && n_runs == 0 && items == 0) return mmda_adam_launch(p, acc, g, m, v, n, nullptr, h, kNoWait, stream);
+  const RunTable t{runs, n_runs, items};
+  return mmda_adam_launch(p, acc, g, m, v, 0, &t, h, kNoWait, stream);
+}
+
+// ---- gradient norm and scale: host side
+namespace {
+int norm_blocks(int64_t n, const RunTable* table) { return stream_blocks(table ? table->items : n / 4); }
+}  // namespace
+
+extern "C" int64_t mmda_grad_norm_partials(int64_t n_or_items) {
+  if (n_or_items < 0) return MMDA_EINVAL;
+  if (n_or_items >= (int64_t)2048 * 256) return 2048;      // (the grid's cap)
+  return stream_blocks(n_or_items);                        // >= the blocks of a dense launch over n floats and of a run launch over n items
+}
+
+// internal.h: the two launches behind mmda_grad_norm (and misa.hip's)
+int mmda_grad_norm_launch(const float* g, const float* acc, int64_t n, const RunTable* table, float max_norm, float grad_scale,
+                          double* partials, int64_t partials_capacity, float* out2, void* stream) {
+  if (!g || !partials || !out2 || !(max_norm >= 0.f)) return MMDA_EINVAL;
+  if (table ? (table->n_runs < 0 || table->items < 0) : n < 0) return MMDA_EINVAL;
+  if (((uintptr_t)g | (uintptr_t)acc) & 15 || ((uintptr_t)partials & 7) || ((uintptr_t)out2 & 3)) return MMDA_EINVAL;
+  const bool empty = table ? (table->n_runs == 0 || table->items == 0) : n == 0;
+  if (table && !empty && !table->runs) return MMDA_EINVAL;
+  const int nb = empty ? 0 : norm_blocks(n, table);
+  if (nb > partials_capacity) return MMDA_EINVAL;
+  if (nb > 0) {
+    const mmda_run* runs = table ? table->runs : nullptr;
+    const int n_runs = table ? table->n_runs : 0;
+    const int64_t items = table ? table->items : 0;
+    if (acc) hipLaunchKernelGGL(grad_norm_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, acc, g, n, runs, n_runs, items, partials);
+    else hipLaunchKernelGGL(grad_norm_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, acc, g, n, runs, n_runs, items, partials);
+    MMDA_CHECK_LAUNCH("mmda_grad_norm");
+  }
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, nb, grad_scale, max_norm, out2);
+  MMDA_CHECK_LAUNCH("mmda_grad_norm/finish");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_grad_norm(const float* g, const float* acc, int64_t n, const mmda_run* runs, int n_runs, int64_t items, float max_norm,
+                              float grad_scale, double* partials, int64_t partials_capacity, float* out2, void* stream) {
+  if (!runs && n_runs == 0 && items == 0)
+    return mmda_grad_norm_launch(g, acc, n, nullptr, max_norm, grad_scale, partials, partials_capacity, out2, stream);
+  const RunTable t{runs, n_runs, items};
+  return mmda_grad_norm_launch(g, acc, 0, &t, max_norm, grad_scale, partials, partials_capacity, out2, stream);
+}
+
+extern "C" int mmda_grad_scale(float* g, int64_t n, const mmda_run* runs, int n_runs, int64_t items, const float* scale_dev, void* stream) {
+  if (!g || !scale_dev || n < 0 || n_runs < 0 || items < 0 || ((uintptr_t)g & 15) || ((uintptr_t)scale_dev & 3)) return MMDA_EINVAL;
+  const bool table = runs || n_runs != 0 || items != 0;
+  if (table ? (n_runs == 0 || items == 0) : n == 0) return MMDA_OK;
+  if (table && !runs) return MMDA_EINVAL;
+  const Scale f{g, scale_dev};
+  return table ? launch_runs("mmda_grad_scale", RunTable{runs, n_runs, items}, f, kNoWait, stream)
+               : launch_stream("mmda_grad_scale", n, f, kNoWait, stream);
 }
 
 extern "C" int mmda_clamp_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -436,6 +622,26 @@ extern "C" int mmda_clamp_adam_rows(float* p, const float* g, float* m, float* v
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(rows_kernel<Adam<false>>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, dim, mask, want, vec, f);
   MMDA_CHECK_LAUNCH("mmda_clamp_adam_rows");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_clamp_adam_rows_opts(float* p, const float* g, float* m, float* v, int rows, int dim, const unsigned char* mask, int want,
+                                         float lr, float clip, float grad_scale, int step, const mmda_adam_opts* opts, void* stream) {
+  if (!adam_opts_ok(opts) || ((uintptr_t)opts->scale_dev & 3)) return MMDA_EINVAL;
+  if (!p || !g || !m || !v || !mask || rows < 0 || dim <= 0 || step < 1) return MMDA_EINVAL;
+  if (rows == 0) return MMDA_OK;
+  const AdamHyper h = adam_hyper(lr, clip, grad_scale, step, *opts);
+  const int vec = (dim & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+  int blocks = (rows + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  const AdamArgs a = adam_args(p, nullptr, g, m, v, h);
+  if (adam_plain(h)) {
+    hipLaunchKernelGGL(rows_kernel<Adam<false>>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, dim, mask, want, vec, Adam<false>{a});
+  } else {
+    const AdamOpt<false> f{adam_opt_args(a, h)};
+    hipLaunchKernelGGL(rows_kernel<AdamOpt<false>>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, dim, mask, want, vec, f);
+  }
+  MMDA_CHECK_LAUNCH("mmda_clamp_adam_rows_opts");
   return MMDA_OK;
 }
 

@@ -44,6 +44,10 @@ _SIG_CACHE: Dict[int, bool] = {}
 _REQUIRES_GRAD = operator.attrgetter("requires_grad")
 
 
+# Adam as the native step runs it until told otherwise: (beta1, beta2, eps, weight_decay, decoupled, clip_norm)
+_ADAM_DEFAULTS = (0.9, 0.999, 1e-8, 0.0, False, 0.0)
+
+
 def _takes_model(fn) -> bool:
     """True if ``fn`` accepts a third positional argument (the model)."""
     import inspect
@@ -177,6 +181,7 @@ class MISA(nn.Module):
         self._trainable_sends = 0
         self._runs_cache = None
         self._cut_flags = None                              # the flags under which the native side last reported the encoder cut on
+        self._adam_pushed = _ADAM_DEFAULTS                  # (beta1, beta2, eps, weight_decay, decoupled, clip_norm) the native side holds
         # deferred mode: per-row step counts and the ring of step scalars (device, made with the flat buckets), and whether a step has
         # been taken since the last flush
         self._df_row_step = self._df_ring = None
@@ -645,12 +650,16 @@ class MISA(nn.Module):
 
     # ------------------------------------------------------------------ fused fast path (Solver.train_epoch)
     def train_step(self, sentences, video, acoustic, lengths, emo_label, lr: float, clip: float, do_adam: bool = True,
-                   training: bool = True, seed=None, grad_sync=None, optimizer=None, accum_index: int = 0, accum_count: int = 1):
+                   training: bool = True, seed=None, grad_sync=None, optimizer=None, accum_index: int = 0, accum_count: int = 1,
+                   clip_norm=None):
         """One reference loop iteration (solver.py:139-186) in native code: zero_grad, forward, six losses, backward,
         clip + Adam.  ``grad_sync(flat_grad_bucket, dense_floats, model)`` is called between backward and Adam for the
         data-parallel all-reduce (mmda_amd/dist.py) and must return the gradient scale (1/world).
         ``optimizer``: an mmda_amd.optim optimizer attached to this model.  Adam (or None) is stepped by the native fused
-        clamp+Adam with ``lr``; any other (RMSprop, config.py:24) by its own fused kernel after the gradient exchange.
+        clamp+Adam with ``lr`` and the optimizer's own ``betas``, ``eps`` and weight decay (``optimizer=None``: Adam's defaults, no
+        decay); any other (RMSprop, config.py:24) by its own fused kernel after the gradient exchange.
+        ``clip_norm``: ``torch.nn.utils.clip_grad_norm_(clip_norm)`` in front of the value clip, on the device; ``grad_norm()`` then
+        holds the step's norm.
         Losses stay on the device (read them with ``read_losses()``; one sync, not six).
         ``accum_index`` / ``accum_count``: this batch is micro-batch ``accum_index`` of an optimizer step made from ``accum_count``
         consecutive calls (0, 1, ... count - 1, the same count in each): the gradients of the micro-batches are summed in that order and
@@ -658,7 +667,8 @@ class MISA(nn.Module):
         from . import optim as _optim
         if accum_count != 1 or accum_index != 0 or self._acc_next:
             return self._accum_micro_step(sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync,
-                                          optimizer, accum_index, accum_count)
+                                          optimizer, accum_index, accum_count, clip_norm)
+        adam = self._push_adam(optimizer, clip_norm, exchange=grad_sync is not None)
         self._sync_trainable(exchange=grad_sync is not None)
         t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
         emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
@@ -699,8 +709,7 @@ class MISA(nn.Module):
                 step_no = max(self._step, 1)
 
                 def _early(n_floats, stream, _gs=gs, _k=step_no):
-                    _lib.check(self._lib.mmda_clamp_adam(self._P.data_ptr(), self._G.data_ptr(), self._M.data_ptr(), self._V.data_ptr(),
-                                                         int(n_floats), lr, 0.9, 0.999, 1e-8, clip, _gs, _k, stream.cuda_stream), "adam(early)")
+                    self._adam_range(0, int(n_floats), lr, clip, _gs, _k, stream.cuda_stream, adam, "adam(early)")
                 owner.early_step = _early
             try:
                 if _takes_model(grad_sync):
@@ -714,13 +723,61 @@ class MISA(nn.Module):
             if self.embed_update in ("sparse", "deferred"):
                 raise _lib.MMDAError(f"embed_update='{self.embed_update}' with a gradient exchange is not built yet")
             if done > 0:
-                n = self.grad_floats - done
-                o = done * 4
-                _lib.check(self._lib.mmda_clamp_adam(self._P.data_ptr() + o, self._G.data_ptr() + o, self._M.data_ptr() + o,
-                                                     self._V.data_ptr() + o, n, lr, 0.9, 0.999, 1e-8, clip, float(scale), max(self._step, 1), s),
-                           "adam(rest)")
+                self._adam_range(done, self.grad_floats - done, lr, clip, float(scale), max(self._step, 1), s, adam, "adam(rest)")
             else:
                 _lib.check(self._lib.mmda_misa_adam_step(self._h, lr, clip, float(scale), self._step, s), "adam_step")
+
+    # ------------------------------------------------------------------ the optimizer's settings
+    def _push_adam(self, optimizer, clip_norm, exchange: bool = False):
+        """What the native Adam of the step about to run must use: the attached optimizer's betas, eps, weight decay and decay kind
+        (``None`` or another optimizer class: Adam's defaults) and ``clip_norm``, sent with ``mmda_misa_set_adam`` when they differ
+        from what was sent last (the steady state: one tuple compare).  Raises, by name and before anything changes, for what no step
+        does.  Returns the tuple."""
+        from . import optim as _optim
+        key = _ADAM_DEFAULTS[:5]
+        if isinstance(optimizer, _optim.Adam):
+            key = optimizer.settings()
+        cn = 0.0 if clip_norm is None else float(clip_norm)
+        if not cn >= 0.0:
+            raise _lib.MMDAError(f"clip_norm must be >= 0 (None or 0: off), not {clip_norm}")
+        if key[3] > 0 and self.embed_update == "deferred":
+            raise _lib.MMDAError("weight_decay > 0 with embed_update='deferred' is not built: the replay ring keeps two scalars per "
+                                 "update and a decayed zero-gradient step needs a third (use 'dense' or 'sparse')")
+        if cn > 0 and self.embed_update in ("sparse", "deferred"):
+            raise _lib.MMDAError(f"clip_norm with embed_update='{self.embed_update}' is not built: the table's rows are updated where "
+                                 "their gradient sums become final, before a norm exists (use 'dense' or 'frozen')")
+        if cn > 0 and exchange:
+            raise _lib.MMDAError("clip_norm with a gradient exchange (grad_sync / data parallel) is not built: the early step updates a "
+                                 "prefix of the bucket before the whole gradient exists")
+        if cn > 0 and optimizer is not None and not isinstance(optimizer, _optim.Adam):
+            raise _lib.MMDAError(f"clip_norm with optimizer {type(optimizer).__name__} is not built: Adam / AdamW only")
+        key = key + (cn,)
+        if key != self._adam_pushed:
+            if self.embed_update == "deferred" and key[:3] != self._adam_pushed[:3]:
+                self.flush_embedding()                      # stale rows replay the steps they missed under the betas those were made with
+            opts = _lib.AdamOpts(beta1=key[0], beta2=key[1], eps=key[2], weight_decay=key[3], decoupled=int(key[4]), scale_dev=None)
+            _lib.check(self._lib.mmda_misa_set_adam(self._h, C.byref(opts), cn), "mmda_misa_set_adam")
+            self._adam_pushed = key
+        return key
+
+    def _adam_range(self, first: int, n: int, lr, clip, grad_scale, step, stream, adam, what: str):
+        """clamp + Adam over floats [first, first + n) of the flat buckets with the settings ``adam`` (the data-parallel step's launches)."""
+        o = first * 4
+        ptrs = [x.data_ptr() + o for x in (self._P, self._G, self._M, self._V)]
+        if adam[3] > 0:
+            opts = _lib.AdamOpts(beta1=adam[0], beta2=adam[1], eps=adam[2], weight_decay=adam[3], decoupled=int(adam[4]), scale_dev=None)
+            rc = self._lib.mmda_clamp_adam_opts(ptrs[0], None, ptrs[1], ptrs[2], ptrs[3], n, None, 0, 0, lr, clip, grad_scale, step,
+                                                C.byref(opts), stream)
+        else:
+            rc = self._lib.mmda_clamp_adam(*ptrs, n, lr, adam[0], adam[1], adam[2], clip, grad_scale, step, stream)
+        _lib.check(rc, what)
+
+    def grad_norm(self) -> torch.Tensor:
+        """The gradient norm of the last step taken with ``clip_norm`` (what ``clip_grad_norm_`` returns), as a 0-d view of device
+        memory: reading it costs no sync until the caller asks for its value."""
+        if self._ws is None:
+            raise _lib.MMDAError("grad_norm(): no step has run yet")
+        return self._ws_view("grad_norm", (2,))[0]
 
     # ------------------------------------------------------------------ steps that start behind the encoders (mmda_amd/encoded.py)
     def _encoded_begin(self, batch, what: str, exchange=None, accum_index: int = 0, accum_count: int = 1):
@@ -755,7 +812,7 @@ class MISA(nn.Module):
                                  tab_emo=_lib.ptr(cache.emo), rows=batch.rows_ptr, B=batch.B)
 
     def train_step_encoded(self, batch, lr: float, clip: float, do_adam: bool = True, training: bool = True, seed=None, optimizer=None,
-                           grad_sync=None, accum_index: int = 0, accum_count: int = 1):
+                           grad_sync=None, accum_index: int = 0, accum_count: int = 1, clip_norm=None):
         """``train_step`` from the encoder cache: ``batch`` is an ``EncodedBatch``; the step gathers its rows (and labels) in one launch
         and starts at the projections.  Needs the encoder cut; seeds, the step counter and ``optimizer`` are ``train_step``'s (a
         custom optimizer, RMSprop, is stepped by its own kernel behind the native step without its Adam).  ``grad_sync`` and the
@@ -764,6 +821,7 @@ class MISA(nn.Module):
         eb = self._encoded_begin(batch, "train_step_encoded", grad_sync, accum_index, accum_count)
         if batch.cache.emo is None:
             raise _lib.MMDAError("train_step_encoded: the cache has no emotion labels (its dataset had none)")
+        self._push_adam(optimizer, clip_norm)
         if seed is None:
             seed = self._next_seed()
         custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
@@ -802,7 +860,7 @@ class MISA(nn.Module):
         return pub["scores"].clone(), pub["labels"].clone()
 
     def _accum_micro_step(self, sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync, optimizer,
-                          index, count) -> None:
+                          index, count, clip_norm=None) -> None:
         """Micro-batch ``index`` of an optimizer step made from ``count``: the native step without its optimizer part, then either the
         add into the second bucket or -- behind the last one -- clip + Adam on (accumulated + this micro-batch's gradients) / count."""
         from . import optim as _optim
@@ -826,6 +884,7 @@ class MISA(nn.Module):
                                  "which one rows update over the micro-batches' concatenated list does not give")
         if not do_adam:
             raise _lib.MMDAError("accum_steps > 1 with do_adam=False: the accumulated step ends in its optimizer step")
+        self._push_adam(optimizer, clip_norm)
         self._sync_trainable()
         t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
         emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()

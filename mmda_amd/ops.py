@@ -590,6 +590,57 @@ def clamp_rmsprop_runs(p, g, sq, runs, lr, alpha=0.99, eps=1e-8, clip=float("inf
           "clamp_rmsprop_runs")
 
 
+def _adam_opts(betas, eps, weight_decay, decoupled, scale_dev):
+    assert scale_dev is None or (scale_dev.dtype == torch.float32 and scale_dev.is_cuda and scale_dev.numel() >= 1)
+    return _lib.AdamOpts(beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, decoupled=int(bool(decoupled)),
+                         scale_dev=ptr(scale_dev))
+
+
+def clamp_adam_opts(p, g, m, v, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                    decoupled=False, scale_dev=None, acc=None, runs=None):
+    """clamp_adam / _sum / _runs / _sum_runs with the settings of mmda_adam_opts: L2 (torch.optim.Adam) or decoupled (torch.optim.AdamW)
+    weight decay, and ``scale_dev``, a device float that multiplies ``grad_scale`` inside the launch.  acc: the gradient is acc + g;
+    runs (runs_table): the trainable runs only."""
+    lib = load()
+    table, n, items = runs if runs is not None else (None, 0, 0)
+    assert acc is None or (acc.numel() == p.numel() and acc.is_contiguous())
+    opts = _adam_opts(betas, eps, weight_decay, decoupled, scale_dev)
+    check(lib.mmda_clamp_adam_opts(ptr(p), ptr(acc), ptr(g), ptr(m), ptr(v), p.numel(), ptr(table), n, items, lr, clip, grad_scale, step,
+                                   C.byref(opts), stream_ptr()), "clamp_adam_opts")
+
+
+def clamp_adam_rows_opts(p, g, m, v, mask, want, lr, step, clip=float("inf"), grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8,
+                         weight_decay=0.0, decoupled=False, scale_dev=None):
+    """clamp_adam_rows with the settings of mmda_adam_opts."""
+    lib = load()
+    rows, dim = p.shape
+    opts = _adam_opts(betas, eps, weight_decay, decoupled, scale_dev)
+    check(lib.mmda_clamp_adam_rows_opts(ptr(p), ptr(g), ptr(m), ptr(v), rows, dim, ptr(mask), int(want), lr, clip, grad_scale, step,
+                                        C.byref(opts), stream_ptr()), "clamp_adam_rows_opts")
+
+
+def grad_norm(g, max_norm, grad_scale=1.0, acc=None, runs=None):
+    """The global L2 norm of the flat gradient g (acc + g; over the runs of a runs_table only) and clip_grad_norm_'s coefficient:
+    a (2,) device tensor [grad_scale * norm, min(1, max_norm / (that + 1e-6))].  Deterministic; nothing is read back."""
+    lib = load()
+    table, n, items = runs if runs is not None else (None, 0, 0)
+    assert g.dtype == torch.float32 and g.is_contiguous() and (acc is None or (acc.numel() == g.numel() and acc.is_contiguous()))
+    cap = int(lib.mmda_grad_norm_partials(items if runs is not None else g.numel()))
+    parts = torch.empty(max(cap, 1), dtype=torch.float64, device=g.device)
+    out = torch.empty(2, dtype=torch.float32, device=g.device)
+    check(lib.mmda_grad_norm(ptr(g), ptr(acc), g.numel(), ptr(table), n, items, max_norm, grad_scale, ptr(parts), cap, ptr(out),
+                             stream_ptr()), "grad_norm")
+    return out
+
+
+def grad_scale_(g, scale_dev, runs=None):
+    """g *= scale_dev[0] in place (over the runs of a runs_table only); scale_dev: a device float, e.g. grad_norm(...)[1:]."""
+    lib = load()
+    table, n, items = runs if runs is not None else (None, 0, 0)
+    assert g.dtype == torch.float32 and g.is_contiguous() and scale_dev.dtype == torch.float32 and scale_dev.is_cuda
+    check(lib.mmda_grad_scale(ptr(g), g.numel(), ptr(table), n, items, ptr(scale_dev), stream_ptr()), "grad_scale")
+
+
 def embed_rows_append(ids_out, rows_out, offset, ids, rows, lengths=None):
     """A micro-batch's (T, B) ids and (T * B, D) gradient rows appended at position `offset` of the list (ids_out (cap,) int64, rows_out
     (cap, D) fp32); positions past a sample's length (lengths: (B,) int32 on the device) get id -1.  Returns the list's new length."""

@@ -1,6 +1,9 @@
 """Optimizers.  ``Adam`` / ``RMSprop`` keep the torch.optim constructors (the reference builds its optimizer as
 ``config.optimizer(params, lr=...)`` out of ``optimizer_dict = {'RMSprop', 'Adam'}``, config.py:24, solver.py:97-99) but step
-with the fused HIP clamp+update kernels.
+with the fused HIP clamp+update kernels.  ``Adam`` takes torch's ``betas``, ``eps`` and ``weight_decay`` (L2, or decoupled with
+``decoupled_weight_decay=True``); ``AdamW`` is that with torch.optim.AdamW's defaults.  What the optimizer was constructed with is what
+steps, on the fused path (``MISA.train_step(optimizer=...)``) as through ``step()``.  ``clip_grad_norm_`` is
+torch.nn.utils.clip_grad_norm_ on the flat gradient bucket, without a read-back.
 
 When every parameter is a view into one flat bucket whose gradient/moment buckets are laid out identically (that is
 how mmda_amd.models.MISA allocates them) the whole model is ONE kernel launch; otherwise one launch per tensor.
@@ -140,10 +143,51 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
 
 class Adam(_FlatOptimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_value=None):
-        if weight_decay != 0:
-            raise NotImplementedError("the reference never passes weight_decay (config.py:143 is a dead flag)")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, clip_value=clip_value))
+    """torch.optim.Adam's constructor (no amsgrad).  ``weight_decay``: L2, added to the clipped gradient as torch.optim.Adam does, or
+    -- ``decoupled_weight_decay=True`` -- torch.optim.AdamW's ``p -= lr * weight_decay * p``.  Attached to a model the bucket is one
+    param group: per-tensor decay exclusions are not built.  With ``embed_update='sparse'`` the decay covers the dense prefix; the
+    table's rows follow SparseAdam, which has none."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, clip_value=None, decoupled_weight_decay=False):
+        b1, b2 = betas
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1): {betas}")
+        if not eps >= 0.0:
+            raise ValueError(f"eps must be >= 0: {eps}")
+        if not weight_decay >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay), clip_value=clip_value))
+
+    def settings(self):
+        """(beta1, beta2, eps, weight_decay, decoupled) of the one param group an attached optimizer may have"""
+        if self._model is not None and len(self.param_groups) != 1:
+            raise _lib.MMDAError(f"{type(self).__name__} attached to a MISA model has {len(self.param_groups)} param groups: the flat bucket "
+                                 "is one group (per-tensor settings such as decay exclusions are not built)")
+        g0 = self.param_groups[0]
+        b1, b2 = g0["betas"]
+        return (float(b1), float(b2), float(g0["eps"]), float(g0.get("weight_decay", 0.0)), bool(g0.get("decoupled_weight_decay", False)))
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_model", None) is not None and len(self.param_groups) >= 1:
+            raise _lib.MMDAError(f"{type(self).__name__} is attached to a MISA model: a second param group is not built (the flat bucket "
+                                 "is one group)")
+        return super().add_param_group(param_group)
+
+    def _launch(self, lib, p, g, m, v, n, runs, lr, clip, grad_scale, t, st, scale_dev, s, what):
+        """one clamp + Adam launch over n floats, or over (table, n_runs, items): the plain entries while they can express the
+        settings (the launch they have always been), else the one that takes mmda_adam_opts"""
+        b1, b2, eps, wd, dec = st
+        table, n_runs, items = runs if runs is not None else (None, 0, 0)
+        if wd > 0 or scale_dev is not None:
+            opts = _lib.AdamOpts(beta1=b1, beta2=b2, eps=eps, weight_decay=wd, decoupled=int(dec), scale_dev=_lib.ptr(scale_dev))
+            rc = lib.mmda_clamp_adam_opts(p, None, g, m, v, n, _lib.ptr(table), n_runs, items, lr, clip, grad_scale, t,
+                                          _lib.C.byref(opts), s)
+        elif runs is not None:
+            rc = lib.mmda_clamp_adam_runs(p, g, m, v, table.data_ptr(), n_runs, items, lr, b1, b2, eps, clip, grad_scale, t, s)
+        else:
+            rc = lib.mmda_clamp_adam(p, g, m, v, n, lr, b1, b2, eps, clip, grad_scale, t, s)
+        _lib.check(rc, what)
 
     def _flat_state(self):
         _, _, M, V = self._model.flat_buckets()
@@ -154,15 +198,22 @@ class Adam(_FlatOptimizer):
         M.copy_(sd["exp_avg"].to(M.device)); V.copy_(sd["exp_avg_sq"].to(V.device))
 
     @torch.no_grad()
-    def step(self, closure=None, clip_value=None, grad_scale=1.0):
+    def step(self, closure=None, clip_value=None, grad_scale=1.0, scale_dev=None):
+        """``scale_dev``: a one-element device tensor that multiplies ``grad_scale`` inside the launch (a clip coefficient that the
+        host never reads), or None."""
         lib = _lib.load()
+        cfg = self.settings()
+        g0 = self.param_groups[0]
+        m = self._flat()
+        if m is not None and hasattr(m, "_push_adam"):
+            # the native side replays a deferred table's rows with the handle's betas and eps: they are this optimizer's (and what no
+            # step does is refused here, by name, before the step is counted)
+            m._push_adam(self, m._adam_pushed[5])
         t = self._next_step()
         s = _lib.stream_ptr()
-        g0 = self.param_groups[0]
         clip = clip_value if clip_value is not None else g0["clip_value"]
         clip = float("inf") if clip is None else float(clip)
         b1, b2 = g0["betas"]
-        m = self._flat()
         if m is not None:
             P, G, M, V = m.flat_buckets()
             # embed_update 'sparse' / 'frozen': the dense launch ends in front of embed.weight; 'sparse' then updates the rows the last
@@ -170,13 +221,8 @@ class Adam(_FlatOptimizer):
             n = getattr(m, "grad_floats", P.numel())
             # frozen parameters (requires_grad=False): the same update over the trainable runs of the bucket only
             runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
-            if runs is not None:
-                table, n_runs, items = runs
-                _lib.check(lib.mmda_clamp_adam_runs(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), table.data_ptr(), n_runs, items,
-                                                    g0["lr"], b1, b2, g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam_runs")
-            else:
-                _lib.check(lib.mmda_clamp_adam(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, g0["lr"], b1, b2,
-                                               g0["eps"], clip, grad_scale, t, s), "mmda_clamp_adam")
+            self._launch(lib, P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, runs, g0["lr"], clip, grad_scale, t, cfg, scale_dev,
+                         s, "mmda_clamp_adam_runs" if runs is not None else "mmda_clamp_adam")
             if getattr(m, "embed_update", "dense") == "sparse":
                 rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
                 m.apply_sparse_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
@@ -199,9 +245,20 @@ class Adam(_FlatOptimizer):
                 ok = all(x.data_ptr() % 16 == 0 for x in (p, g, st["m"], st["v"])) and p.is_contiguous()
                 if not ok:
                     raise _lib.MMDAError("parameter storage is not 16-byte aligned/contiguous")
-                _lib.check(lib.mmda_clamp_adam(p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(),
-                                               group["lr"], b1, b2, group["eps"], clip, grad_scale, t, s), "mmda_clamp_adam")
+                gb1, gb2 = group["betas"]
+                gst = (float(gb1), float(gb2), float(group["eps"]), float(group.get("weight_decay", 0.0)),
+                       bool(group.get("decoupled_weight_decay", False)))
+                self._launch(lib, p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(), None, group["lr"], clip,
+                             grad_scale, t, gst, scale_dev, s, "mmda_clamp_adam")
         return None
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW's constructor and defaults: decoupled weight decay, 1e-2"""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip_value=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_value=clip_value,
+                         decoupled_weight_decay=True)
 
 
 class RMSprop(_FlatOptimizer):
@@ -283,4 +340,50 @@ def clip_grad_value_(model_or_params, clip_value):
             _lib.check(lib.mmda_clamp(p.grad.data_ptr(), p.grad.numel(), float(clip_value), _lib.stream_ptr()), "mmda_clamp")
 
 
-optimizer_dict = {"RMSprop": RMSprop, "Adam": Adam}       # reference config.py:24
+def clip_grad_norm_(model_or_params, max_norm):
+    """torch.nn.utils.clip_grad_norm_(..., max_norm) (L2) on the device: the norm of the flat gradient bucket -- of its trainable runs
+    when parameters are frozen -- then the bucket scaled in place by min(1, max_norm / (norm + 1e-6)).  Returns the norm as a 0-d device
+    tensor; nothing is read back.  A list of parameters takes one norm launch per tensor and a sum on the device."""
+    lib = _lib.load()
+    s = _lib.stream_ptr()
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"max_norm must be >= 0: {max_norm}")
+    m = model_or_params
+    if hasattr(m, "flat_buckets") and m._G is not None:
+        if getattr(m, "embed_update", "dense") in ("sparse", "deferred"):
+            raise _lib.MMDAError(f"clip_grad_norm_ with embed_update='{m.embed_update}' is not built: the table's gradient rows are not "
+                                 "coalesced before the rows update, so no norm of the whole gradient exists")
+        G = m._G
+        n = getattr(m, "grad_floats", G.numel())
+        runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
+        table, n_runs, items = runs if runs is not None else (None, 0, 0)
+        cap = int(lib.mmda_grad_norm_partials(items if runs is not None else n))
+        parts = torch.empty(max(cap, 1), dtype=torch.float64, device=G.device)
+        out = torch.empty(2, dtype=torch.float32, device=G.device)
+        _lib.check(lib.mmda_grad_norm(G.data_ptr(), None, n, _lib.ptr(table), n_runs, items, max_norm, 1.0, parts.data_ptr(), cap,
+                                      out.data_ptr(), s), "mmda_grad_norm")
+        _lib.check(lib.mmda_grad_scale(G.data_ptr(), n, _lib.ptr(table), n_runs, items, out.data_ptr() + 4, s), "mmda_grad_scale")
+        return out[0]
+    grads = [p.grad for p in m if p.grad is not None]
+    if not grads:
+        return torch.zeros(())
+    dev = grads[0].device
+    sq = torch.zeros((), dtype=torch.float64, device=dev)
+    for g in grads:
+        if not (g.is_contiguous() and g.data_ptr() % 16 == 0):
+            raise _lib.MMDAError("gradient storage is not 16-byte aligned/contiguous")
+        cap = int(lib.mmda_grad_norm_partials(g.numel()))
+        parts = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.mmda_grad_norm(g.data_ptr(), None, g.numel(), None, 0, 0, max_norm, 1.0, parts.data_ptr(), cap, out.data_ptr(), s),
+                   "mmda_grad_norm")
+        sq = sq + out[0].double() ** 2
+    norm = sq.sqrt().float()
+    coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0).reshape(1).contiguous()
+    for g in grads:
+        _lib.check(lib.mmda_grad_scale(g.data_ptr(), g.numel(), None, 0, 0, coef.data_ptr(), s), "mmda_grad_scale")
+    return norm
+
+
+optimizer_dict = {"RMSprop": RMSprop, "Adam": Adam, "AdamW": AdamW}       # reference config.py:24, and AdamW

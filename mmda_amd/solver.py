@@ -62,27 +62,46 @@ class Solver(object):
             # (the reference writes `self.model.embed.requires_grad = False` here, solver.py:86: an attribute on the module that
             # freezes nothing.  Whether the table trains is config.embed_update: 'dense' (what the reference does), 'sparse', 'frozen')
         eu = getattr(self.model, "embed_update", "dense")
+        is_adam = isinstance(cfg.optimizer, type) and issubclass(cfg.optimizer, _optim.Adam)          # Adam or AdamW
+        opt_kwargs = dict(getattr(cfg, "optimizer_kwargs", None) or {})
+        if cfg.optimizer is _optim.AdamW and "weight_decay" not in opt_kwargs:
+            opt_kwargs["weight_decay"] = cfg.weight_decay
+        clip_norm = getattr(cfg, "clip_norm", None)
         dp_on = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         if eu == "sparse" and self.is_train:
             from . import _lib
-            if cfg.optimizer is not _optim.Adam:
+            if not is_adam:
                 raise _lib.MMDAError("embed_update='sparse' is defined for optimizer='Adam' only (torch has no sparse RMSprop to match)")
             if dp_on:
                 raise _lib.MMDAError("embed_update='sparse' under data parallelism is not built yet (use 'dense' or 'frozen')")
         if eu == "deferred" and self.is_train:
             from . import _lib
-            if cfg.optimizer is not _optim.Adam:
+            if not is_adam:
                 raise _lib.MMDAError("embed_update='deferred' is built for optimizer='Adam' only")
             if dp_on:
                 raise _lib.MMDAError("embed_update='deferred' under data parallelism is not built yet (use 'dense' or 'frozen')")
         if int(getattr(cfg, "accum_steps", 1)) > 1 and self.is_train:
             from . import _lib
-            if cfg.optimizer is not _optim.Adam:
+            if not is_adam:
                 raise _lib.MMDAError("accum_steps > 1 is built for optimizer='Adam' only (not with RMSprop)")
             if dp_on:
                 raise _lib.MMDAError("accum_steps > 1 under data parallelism (world x accumulation) is not built yet")
             if eu == "deferred":
                 raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built (use 'dense': the same weights)")
+        if self.is_train:
+            from . import _lib
+            if eu == "deferred" and float(opt_kwargs.get("weight_decay", 0) or 0) > 0:
+                raise _lib.MMDAError("weight_decay > 0 with embed_update='deferred' is not built: the replay ring keeps two scalars "
+                                     "per update and a decayed zero-gradient step needs a third (use 'dense' or 'sparse')")
+            if clip_norm is not None and float(clip_norm) > 0:
+                if not is_adam:
+                    raise _lib.MMDAError("clip_norm is built for optimizer='Adam' / 'AdamW' only")
+                if eu in ("sparse", "deferred"):
+                    raise _lib.MMDAError(f"clip_norm with embed_update='{eu}' is not built: the table's rows are updated where their "
+                                         "gradient sums become final, before a norm exists (use 'dense' or 'frozen')")
+                if dp_on:
+                    raise _lib.MMDAError("clip_norm under data parallelism (a gradient exchange) is not built: the early step updates a "
+                                         "prefix of the bucket before the whole gradient exists")
         if self.is_train and hasattr(self.model, "frozen_names") and self.model.frozen_names(beyond_embed_update=True):
             from . import _lib
             if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -90,7 +109,7 @@ class Solver(object):
                                      "(embed_update='frozen' alone is)")
         self.model.to(self.device)
         if self.is_train:
-            self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate)
+            self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate, **opt_kwargs)
             if hasattr(self.optimizer, "attach"):
                 self.optimizer.attach(self.model)
         if dp_on:
@@ -126,9 +145,16 @@ class Solver(object):
         self.model.train()
         sums = None
         n = 0
+        optimizer = getattr(self, "optimizer", None)
+        clip_norm = getattr(cfg, "clip_norm", None)
         for batch, k, count in self._micro_batches():
             accum = dict(accum_index=k, accum_count=count) if count > 1 else {}
-            step = dict(lr=cfg.learning_rate, clip=cfg.clip, grad_sync=self.dp.sync if self.dp is not None else None,
+            if clip_norm is not None:
+                accum["clip_norm"] = clip_norm
+            # the optimizer's own lr: cfg.learning_rate as build() set it, until a torch.optim.lr_scheduler on self.optimizer or a
+            # loaded checkpoint changes it
+            lr = optimizer.param_groups[0]["lr"] if optimizer is not None else cfg.learning_rate
+            step = dict(lr=lr, clip=cfg.clip, grad_sync=self.dp.sync if self.dp is not None else None,
                         optimizer=getattr(self, "optimizer", None), **accum)
             if isinstance(batch, EncodedBatch):                  # an index list into the encoder cache: the step gathers it
                 self.model.train_step_encoded(batch, **step)
@@ -176,6 +202,8 @@ class Solver(object):
             if cfg.use_confidNet:
                 loss = loss + cfg.conf_weight * conf_loss
             loss.backward()
+            if getattr(cfg, "clip_norm", None) is not None:
+                _optim.clip_grad_norm_(self.model, cfg.clip_norm)
             _optim.clip_grad_value_(self.model, cfg.clip)
             self.optimizer.step()
             train_loss.append(loss.item())
