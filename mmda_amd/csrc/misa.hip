@@ -72,6 +72,16 @@ enum { SITE_ATTN = 1, SITE_DROP1 = 2, SITE_FFN = 3, SITE_DROP2 = 4, SITE_CLS = 5
        SITE_RRELU = 7 /* .. 9: the three projections' random slopes */, SITE_RRELU_DISC = 10 };
 constexpr int FFN = 2048, NHEAD = 2, S6 = 6;
 
+// The scalars of one optimizer step.  acc: an accumulator added to the gradient, or nullptr; norm: clip_grad_norm_ in front of it.
+struct OptStep { float lr, clip, grad_scale; int step; const float* acc; bool norm; };
+// The id list and lengths of a backward whose rows update is still to run (the caller keeps them alive, as it does for backward itself)
+struct PendingRows {
+  const int64_t* ids = nullptr; const int32_t* lengths = nullptr; bool on = false;
+  void set(const int64_t* i, const int32_t* l) { ids = i; lengths = l; on = true; }
+  PendingRows take() { const PendingRows r = *this; *this = PendingRows{}; return r; }
+};
+struct RowList { int64_t* ids; float* rows; int64_t used, capacity; };   // an accumulated step's (ids, rows) list: sparse table
+
 }  // namespace
 
 struct mmda_misa {
@@ -105,8 +115,8 @@ struct mmda_misa {
       d_dom_h, d_dom_z;
   // block-scaled fp8 operands of the feed-forward products (fusion_fp8): element bytes and scale bytes, as float offsets
   // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
-  // recurrence runs there, on the side stream (set by mmda_misa_train_step around its backward pass)
-  int adam_early_on = 0; float ae_lr = 0.f, ae_clip = 0.f; int ae_step = 0; int64_t adam_early_done = 0;
+  // recurrence runs there, on the side stream (Pass::early); how far that pass of the last backward got
+  int64_t adam_early_done = 0;
   // The optimizer's settings (mmda_misa_set_adam): every Adam launch of the handle reads them; scale_dev is not kept (a step with
   // clip_norm > 0 points its launches at gnorm[1]).  clip_norm > 0: clip_grad_norm_ in front of the update -- no update may precede the
   // norm, so such a step takes no early optimizer pass.  gnorm: norm and coefficient of the last such step; gnorm_parts: the norm
@@ -131,9 +141,9 @@ struct mmda_misa {
   // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
   // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
   // for backward itself)
-  const int64_t* eu_ids = nullptr; const int32_t* eu_lengths = nullptr; int eu_pending = 0;
+  PendingRows eu;
   // dense mode with deferral (mmda_misa_set_embed_deferred): the caller's per-row step counts and ring of step scalars (common.h:
-  // DenseRowArgs).  Dense Adam's result; the bucket ends at the table as in the sparse mode, which also lends its eu_* fields.
+  // DenseRowArgs).  Dense Adam's result; the bucket ends at the table as in the sparse mode, which also lends its pending rows.
   // df_seq: updates applied since the binding (what a current row's row_step equals); df_flushed: df_seq at the last full flush.
   int32_t* df_row_step = nullptr; float* df_ring = nullptr; int df_window = 0; int df_seq = 0, df_flushed = 0;
   int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
@@ -1098,20 +1108,20 @@ extern "C" int mmda_misa_set_embed_update(mmda_misa* m, int mode) {
   if (mode != EU_DENSE && mode != EU_SPARSE && mode != EU_FROZEN) return MMDA_EINVAL;
   if (mode != EU_DENSE) { m->df_row_step = nullptr; m->df_ring = nullptr; m->df_window = 0; }     // (the caller flushed first)
   m->embed_update = mode;
-  m->eu_pending = 0;
+  m->eu.take();
   return MMDA_OK;
 }
 
 extern "C" int mmda_misa_set_embed_deferred(mmda_misa* m, int32_t* row_step, float* step_scalars, int window, void* stream) {
   if (!m) return MMDA_EINVAL;
   if (!row_step && !step_scalars) {                        // off: plain dense from the next step on (the caller flushed first)
-    m->df_row_step = nullptr; m->df_ring = nullptr; m->df_window = 0; m->eu_pending = 0;
+    m->df_row_step = nullptr; m->df_ring = nullptr; m->df_window = 0; m->eu.take();
     return MMDA_OK;
   }
   if (!row_step || !step_scalars || window < 1 || m->embed_update != EU_DENSE) return MMDA_EINVAL;
   const int rc = mmda_embed_deferred_reset(row_step, m->cfg.vocab, stream);
   if (rc) return rc;
-  m->df_row_step = row_step; m->df_ring = step_scalars; m->df_window = window; m->eu_pending = 0;
+  m->df_row_step = row_step; m->df_ring = step_scalars; m->df_window = window; m->eu.take();
   m->df_seq = m->df_flushed = 0;
   return MMDA_OK;
 }
@@ -1146,10 +1156,10 @@ int deferred_apply(mmda_misa* m, const int64_t* ids, const unsigned* sorted, con
 
 extern "C" int mmda_misa_embed_deferred_step(mmda_misa* m, float lr, float beta1, float beta2, float eps, float clip, float grad_scale,
                                              int step, void* stream) {
-  if (!m || !m->df_row_step || m->embed_update != EU_DENSE || !m->eu_pending || step < 1) return MMDA_EINVAL;
-  m->eu_pending = 0;
+  if (!m || !m->df_row_step || m->embed_update != EU_DENSE || !m->eu.on || step < 1) return MMDA_EINVAL;
+  const PendingRows r = m->eu.take();
   // (another forward may have run since that backward: its rows are brought to the last update again, which costs one launch)
-  return deferred_apply(m, m->eu_ids, nullptr, m->eu_lengths, lr, beta1, beta2, eps, clip, grad_scale, step, true, stream);
+  return deferred_apply(m, r.ids, nullptr, r.lengths, lr, beta1, beta2, eps, clip, grad_scale, step, true, stream);
 }
 
 extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
@@ -1203,6 +1213,7 @@ struct Pass : Ctx {
   const int B, T, R, hs, NC, mode;
   static constexpr int fmode = MMDA_F32;     // the fusion block's GEMMs: exact path (see mmda_misa_forward)
   const int64_t BH; const float p_tf, p_cls; const uint64_t seed;
+  const OptStep* early = nullptr;            // backward of a fused step: the optimizer step this pass may start (see bwd_encoder_layer)
   Pass(mmda_misa* m_, void* s_)
       : Ctx{m_, s_}, P(m_->plan), c(m_->cfg), B(m_->B), T(m_->T), R(m_->T * m_->B), hs(c.hidden), NC(6 + c.ncls), mode(c.mode),
         BH((int64_t)B * hs), p_tf(m_->training ? c.fusion_dropout : 0.f), p_cls(m_->training ? c.dropout : 0.f), seed(m_->seed) {}
@@ -1216,6 +1227,8 @@ struct Pass : Ctx {
   void bwd_fusion_fused(), bwd_fusion_skinny(), bwd_fusion_tiled(), skinny_ffn_dx(bool wt), skinny_proj_dx(bool wt);
   void fusion_wgrads(), bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* lengths);
   void bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_ids, const int32_t* lengths);
+  void bwd_text_rows(const int64_t* t_ids, const int32_t* lengths);
+  const unsigned* take_sorted();
 };
 
 // LayerNorm arguments of the fusion block: the projections' (+ activation), norm1 and norm2 (residual and dropout ride along)
@@ -1892,7 +1905,7 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
   m->esort_valid = 0;
   // (sparse mode without an optimizer step behind this backward: the rows update runs later, in mmda_misa_adam_step, and sorts there)
-  if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !m->adam_early_on)) {
+  if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !early)) {
     rc = mmda_embed_sort_ids(t_ids, B * m->T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
     if (!rc && ss != s) {
       hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
@@ -2075,68 +2088,59 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // point reads those fp32 parameters: the remaining GEMMs of a bf16 step read bf16 copies made in the forward pass, and in
     // the other modes the prefix ends in front of the recurrent layers).  The side stream is a real second stream only when
     // use_side is on; otherwise this is simply the same work in front of the recurrence.
-    if (!rc && m->adam_early_on && m->early_floats > 0 && m->M1 && m->V1) {
+    if (!rc && early && m->early_floats > 0 && m->M1 && m->V1) {
       // (frozen parameters: over the prefix's trainable runs -- the prefix counts as stepped even where none of it trains)
-      rc = bucket_adam(m, 0, m->early_floats, nullptr, m->ae_lr, m->ae_clip, 1.0f, m->ae_step, kNoWait, ss);
+      rc = bucket_adam(m, 0, m->early_floats, nullptr, early->lr, early->clip, early->grad_scale, early->step, kNoWait, ss);
       if (!rc) m->adam_early_done = m->early_floats;
     }
-  } else if (P.embed_update == EU_SPARSE) {
-    // text: the rows the batch touches are updated where the scatter would have left their sums (SparseAdam, common.h) -- behind an
-    // optimizer step only; otherwise the pass stops at d_x_t and mmda_misa_adam_step applies the update
-    m->eu_pending = 0;
-    if (!m->adam_early_on) {
-      m->eu_ids = t_ids; m->eu_lengths = lengths; m->eu_pending = 1;
-      return;
-    }
+  } else {
+    bwd_text_rows(t_ids, lengths);
+  }
+}
+
+// The sorted id list that bwd_side_chain made for this pass, or nullptr (taken once).  Made on the side stream: its word, waited for
+// by one wave in front of the launch that reads the list.
+const unsigned* Pass::take_sorted() {
+  if (!m->esort_valid) return nullptr;
+  if (m->esort_valid == 2) {
+    hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
+    if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
+  }
+  m->esort_valid = 0;
+  return reinterpret_cast<const unsigned*>(WS(m->esort));
+}
+
+// The text rows' end of the pass, behind layer 1: d_x_t goes where embed_update sends it.  Sparse and deferred tables take their rows update
+// here, behind an optimizer step only (`early`); otherwise the pass stops at d_x_t, the rows stay pending for mmda_misa_adam_step.
+void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
+  const float* dx = WS(m->mod[0].d_x);
+  if (P.embed_update == EU_SPARSE || P.embed_deferred) {
+    m->eu.take();
+    if (!early) { m->eu.set(t_ids, lengths); return; }
+  }
+  if (P.embed_update == EU_SPARSE) {
+    // SparseAdam on the rows the batch touches (common.h)
     SparseAdamArgs ad;
-    rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, m->ae_lr,
-                               m->adam.beta1, m->adam.beta2, m->adam.eps, m->ae_clip, 1.0f, m->ae_step);
+    rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, early->lr,
+                               m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale, early->step);
     if (rc) return;
-    if (m->esort_valid) {
-      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
-        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
-        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
-      }
-      if (!rc) rc = mmda_embed_sparse_adam_presorted(ad, reinterpret_cast<const unsigned*>(WS(m->esort)), R, c.d_t, WS(m->mod[0].d_x), s);
-      m->esort_valid = 0;
-    } else if (mmda_embed_scatter_sorts(R)) {
-      rc = mmda_embed_sparse_adam_sorted(ad, t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
-    } else {
-      rc = mmda_embed_sparse_adam_short(ad, t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
-    }
+    const unsigned* sorted = take_sorted();
+    if (rc) return;
+    if (sorted) rc = mmda_embed_sparse_adam_presorted(ad, sorted, R, c.d_t, dx, s);
+    else if (mmda_embed_scatter_sorts(R)) rc = mmda_embed_sparse_adam_sorted(ad, t_ids, R, c.d_t, dx, lengths, B, s);
+    else rc = mmda_embed_sparse_adam_short(ad, t_ids, R, c.d_t, dx, lengths, B, s);
   } else if (P.embed_deferred) {
-    // text: the rows the batch touches take this step where the scatter would have left their sums, with those sums (common.h:
-    // RowDenseAdam) -- behind an optimizer step only, as in the sparse mode; every other row takes it when it is next needed
-    m->eu_pending = 0;
-    if (!m->adam_early_on) {
-      m->eu_ids = t_ids; m->eu_lengths = lengths; m->eu_pending = 1;
-      return;
-    }
+    // dense Adam's step for the rows the batch touches (common.h: RowDenseAdam); every other row takes it when it is next needed
     if (!m->M1 || !m->V1) { rc = MMDA_EINVAL; return; }
-    const unsigned* sorted = nullptr;
-    if (m->esort_valid) {
-      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
-        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
-        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
-      }
-      sorted = reinterpret_cast<const unsigned*>(WS(m->esort));
-      m->esort_valid = 0;
-    }
-    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, m->ae_lr, m->adam.beta1, m->adam.beta2, m->adam.eps, m->ae_clip, 1.0f, m->ae_step, false, s);
+    const unsigned* sorted = take_sorted();
+    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, early->lr, m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale,
+                                 early->step, false, s);
   } else if (P.embed_update == EU_DENSE) {
-    // text: gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
-    if (m->esort_valid) {
-      if (m->esort_valid == 2) {                         // made on the side stream: its word, waited for by one wave
-        hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, m->jflags + 3, m->esort_val, m->jflags + 2);
-        if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
-      }
-      if (!rc)
-        rc = mmda_embed_scatter_presorted(GG(m->embed), reinterpret_cast<const unsigned*>(WS(m->esort)), R, c.d_t, c.vocab,
-                                          WS(m->mod[0].d_x), s);
-      m->esort_valid = 0;
-    } else {
-      rc = mmda_embed_scatter_add_masked(GG(m->embed), t_ids, R, c.d_t, WS(m->mod[0].d_x), lengths, B, s);
-    }
+    // the gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
+    const unsigned* sorted = take_sorted();
+    if (rc) return;
+    if (sorted) rc = mmda_embed_scatter_presorted(GG(m->embed), sorted, R, c.d_t, c.vocab, dx, s);
+    else rc = mmda_embed_scatter_add_masked(GG(m->embed), t_ids, R, c.d_t, dx, lengths, B, s);
   }
 }
 }  // namespace
@@ -2145,16 +2149,19 @@ namespace {
 // The backward pass.  The batch (ids / v / a / lengths) is read only by what an encoder cut skips -- the encoder layers, the sorted id
 // list, the scatter -- so a step from the encoder cache, which has no batch, passes NULLs: it must be a cut pass planned by a cached
 // forward.
-int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, void* stream) {
+// early: the optimizer step behind this pass, which it may start (nullptr: none, the pass stops at the gradients).
+int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const OptStep* early,
+                  void* stream) {
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
   if (m->plan.inf) return MMDA_EINVAL;                  // the last forward was an evaluation pass: nothing was stashed
   if ((!t_ids || !v || !a || !lengths) && !(m->plan.enc_cached && m->plan.enc_cut)) return MMDA_EINVAL;
   if (m->plan.enc_cached && !m->plan.enc_cut) return MMDA_EINVAL;      // (a cached forward that trains is a cut one: cannot happen)
   // the trainable set changed behind that forward: a cut pass computes no encoder gradient (and may have stashed nothing)
   if (m->plan.enc_cut && !encoder_cut(m)) return MMDA_EINVAL;
-  if (masked(m) && m->adam_early_on) { const int rr = runs_ready(m, stream); if (rr) return rr; }
-  m->early_valid = 0;
+  if (masked(m) && early) { const int rr = runs_ready(m, stream); if (rr) return rr; }
+  m->early_valid = 0; m->adam_early_done = 0;
   Pass x(m, stream);
+  x.early = early;
   const StepPlan& P = m->plan;
   // the fused stretches read the K-major weight copies this step's forward made (side stream, joined there)
   const bool row_fuse = P.row_fuse && m->wT_valid;
@@ -2176,7 +2183,7 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   // wait on the device (see mmda_misa::jflags), when that launch completes
   // (only where every gradient the side stream computes lies in the prefix it also stepped -- the bf16 step, whose layer-2 weight
   //  gradients ran there in front of the early optimizer pass: the launch that waits READS the rest of the bucket before it waits)
-  if (P.fj_on && m->adam_early_on && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
+  if (P.fj_on && early && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
       m->adam_early_done == m->rnn1_begin) {
     x.rc = side_flag_signal(m, 1);
     m->fj2 = x.rc ? 0 : 1;
@@ -2195,7 +2202,7 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
 extern "C" int mmda_misa_backward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
                                   void* stream) {
   if (!t_ids || !v || !a || !lengths) return MMDA_EINVAL;
-  return backward_pass(m, t_ids, v, a, lengths, stream);
+  return backward_pass(m, t_ids, v, a, lengths, nullptr, stream);
 }
 
 extern "C" int mmda_misa_timing_end(mmda_misa* m) {
@@ -2247,73 +2254,82 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 }
 
 // =============================================================================================== optimizer / step
-extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
-  if (!m || !m->P || !m->G || !m->M1 || !m->V1 || adam_settings_refused(m)) return MMDA_EINVAL;
-  const bool norm = m->clip_norm > 0.f;
-  if (norm && !m->ws) return MMDA_EINVAL;
-  int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;  // frozen parameters: the trainable runs only
-  if (!rc && norm) rc = bucket_norm(m, nullptr, grad_scale, stream);
-  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, grad_scale, step, kNoWait, stream, norm ? m->ws + m->gnorm + 1 : nullptr);
-  if (!rc && m->embed_update == EU_SPARSE && m->eu_pending) {
-    // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
-    m->eu_pending = 0;
-    if (!m->ws || m->T <= 0) return MMDA_EINVAL;
-    rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->eu_ids, m->B * m->T, m->cfg.d_t,
-                                     WS(m->mod[0].d_x), m->eu_lengths, m->B, m->cfg.vocab, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step,
-                                     stream);
-  }
-  if (!rc && m->embed_update == EU_DENSE && m->df_row_step && m->eu_pending)
-    rc = mmda_misa_embed_deferred_step(m, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step, stream);
-  return rc;
-}
-
-// ---- accumulated steps (accum_steps > 1): the micro-batch is mmda_misa_train_step(do_adam = 0); what happens to its gradients is here
 namespace {
 // sparse table: the rows of the backward that just ran (d_x_t is workspace: the next micro-batch overwrites it) go to the caller's list
-int accum_append_rows(mmda_misa* m, int64_t* list_ids, float* list_rows, int64_t used, int64_t capacity, void* stream) {
-  if (!m->eu_pending || !m->ws || m->T <= 0 || !list_ids || !list_rows) return MMDA_EINVAL;
-  m->eu_pending = 0;                                    // (a later mmda_misa_adam_step must not apply these rows again)
-  const int64_t* ids = m->eu_ids; const int32_t* lengths = m->eu_lengths;
-  m->eu_ids = nullptr; m->eu_lengths = nullptr;
-  return mmda_embed_rows_append(list_ids, list_rows, used, capacity, ids, WS(m->mod[0].d_x), m->B * m->T, m->cfg.d_t, lengths, m->B, stream);
+int accum_append_rows(mmda_misa* m, const RowList& l, void* stream) {
+  if (!m->eu.on || !m->ws || m->T <= 0 || !l.ids || !l.rows) return MMDA_EINVAL;
+  const PendingRows r = m->eu.take();                   // (a later mmda_misa_adam_step must not apply these rows again)
+  return mmda_embed_rows_append(l.ids, l.rows, l.used, l.capacity, r.ids, WS(m->mod[0].d_x), m->B * m->T, m->cfg.d_t, r.lengths, m->B, stream);
 }
 bool accum_ready(const mmda_misa* m) { return m && m->P && m->G && !m->df_row_step; }
 // sparse table: a backward is pending and the list holds its T B rows behind the `used` it already has (dense / frozen: no list)
-bool accum_list_ok(const mmda_misa* m, const int64_t* list_ids, const float* list_rows, int64_t used, int64_t capacity) {
+bool accum_list_ok(const mmda_misa* m, const RowList& l) {
   if (m->embed_update != EU_SPARSE) return true;
   const int64_t R = (int64_t)m->B * m->T;
-  return m->eu_pending && m->ws && m->T > 0 && list_ids && list_rows && used >= 0 && used <= capacity && R <= capacity - used &&
-         used + R <= INT32_MAX;
+  return m->eu.on && m->ws && m->T > 0 && l.ids && l.rows && l.used >= 0 && l.used <= l.capacity && R <= l.capacity - l.used &&
+         l.used + R <= INT32_MAX;
+}
+
+// What every optimizer step is checked for in front of its first launch, so that a refused call changes nothing
+int opt_step_refused(const mmda_misa* m, const OptStep& o) {
+  if (!m->P || !m->G || !m->M1 || !m->V1 || o.step < 1 || (o.norm && !m->ws)) return MMDA_EINVAL;
+  return adam_settings_refused(m) ? MMDA_EINVAL : MMDA_OK;
+}
+
+// The optimizer part of a step, from bucket offset lo (an early pass stepped what lies in front of it): the run table where parameters
+// are frozen, the norm, clamp + Adam over [lo, grad_floats) -- w: that launch waits for the side stream's word -- and the table's rows
+// that are still to be updated: the accumulated step's list (sparse table), or the rows a backward left pending (sparse, deferred).
+// (Behind a fused step nothing is pending: bwd_text_rows takes m->eu whenever it is handed a step, and a cut pass, which does not get
+// that far, needs a frozen or plain dense table (encoder_cut), where the rows part does not apply.)
+int opt_step(mmda_misa* m, const OptStep& o, int64_t lo, const FlagWait& w, const RowList* list, void* stream) {
+  int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;
+  if (!rc && o.norm) rc = bucket_norm(m, o.acc, o.grad_scale, stream);
+  if (!rc) rc = bucket_adam(m, lo, grad_floats(m), o.acc, o.lr, o.clip, o.grad_scale, o.step, w, stream, o.norm ? m->ws + m->gnorm + 1 : nullptr);
+  if (rc) return rc;
+  float* const p = PP(m->embed); float* const m1 = m->M1 + m->embed; float* const v1 = m->V1 + m->embed; const mmda_adam_opts& h = m->adam;
+  if (m->embed_update == EU_SPARSE && list) {
+    const int n = (int)(list->used + (int64_t)m->B * m->T);
+    rc = accum_append_rows(m, *list, stream);
+    // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
+    if (!rc) rc = mmda_embed_rows_sparse_adam(p, m1, v1, list->ids, n, m->cfg.d_t, list->rows, nullptr, 0, m->cfg.vocab, o.lr, h.beta1, h.beta2,
+                                              h.eps, o.clip, o.grad_scale, o.step, stream);
+  } else if (m->embed_update == EU_SPARSE && m->eu.on) {
+    // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
+    const PendingRows r = m->eu.take();
+    if (!m->ws || m->T <= 0) return MMDA_EINVAL;
+    rc = mmda_embed_rows_sparse_adam(p, m1, v1, r.ids, m->B * m->T, m->cfg.d_t, WS(m->mod[0].d_x), r.lengths, m->B, m->cfg.vocab, o.lr, h.beta1,
+                                     h.beta2, h.eps, o.clip, o.grad_scale, o.step, stream);
+  } else if (m->embed_update == EU_DENSE && m->df_row_step && m->eu.on) {
+    rc = mmda_misa_embed_deferred_step(m, o.lr, h.beta1, h.beta2, h.eps, o.clip, o.grad_scale, o.step, stream);
+  }
+  return rc;
 }
 }  // namespace
 
+extern "C" int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, int step, void* stream) {
+  if (!m) return MMDA_EINVAL;
+  const OptStep o{lr, clip, grad_scale, step, nullptr, m->clip_norm > 0.f};
+  const int rc = opt_step_refused(m, o);
+  return rc ? rc : opt_step(m, o, 0, kNoWait, nullptr, stream);
+}
+
+// ---- accumulated steps (accum_steps > 1): the micro-batch is mmda_misa_train_step(do_adam = 0); what happens to its gradients is here
 extern "C" int mmda_misa_grad_accumulate(mmda_misa* m, float* acc, int first, int64_t* list_ids, float* list_rows, int64_t list_used,
                                          int64_t list_capacity, void* stream) {
-  if (!accum_ready(m) || !acc || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
+  const RowList l{list_ids, list_rows, list_used, list_capacity};
+  if (!accum_ready(m) || !acc || !accum_list_ok(m, l)) return MMDA_EINVAL;
   int rc = mmda_grad_accumulate(acc, m->G, grad_floats(m), first, stream);
-  if (!rc && m->embed_update == EU_SPARSE) rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
+  if (!rc && m->embed_update == EU_SPARSE) rc = accum_append_rows(m, l, stream);
   return rc;
 }
 
 extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, int64_t* list_ids, float* list_rows, int64_t list_used,
                                                int64_t list_capacity, float lr, float clip, float grad_scale, int step, void* stream) {
-  // (everything is checked in front of the dense launch: a refused call changes nothing)
-  if (!accum_ready(m) || !m->M1 || !m->V1 || step < 1 || !accum_list_ok(m, list_ids, list_rows, list_used, list_capacity)) return MMDA_EINVAL;
-  if (adam_settings_refused(m)) return MMDA_EINVAL;
-  const bool norm = m->clip_norm > 0.f;
-  if (norm && !m->ws) return MMDA_EINVAL;
-  int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;
-  if (!rc && norm) rc = bucket_norm(m, acc, grad_scale, stream);
-  if (!rc) rc = bucket_adam(m, 0, grad_floats(m), acc, lr, clip, grad_scale, step, kNoWait, stream, norm ? m->ws + m->gnorm + 1 : nullptr);
-  if (!rc && m->embed_update == EU_SPARSE) {
-    const int n = (int)(list_used + (int64_t)m->B * m->T);
-    rc = accum_append_rows(m, list_ids, list_rows, list_used, list_capacity, stream);
-    // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
-    if (!rc)
-      rc = mmda_embed_rows_sparse_adam(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, list_ids, n, m->cfg.d_t, list_rows, nullptr, 0,
-                                       m->cfg.vocab, lr, m->adam.beta1, m->adam.beta2, m->adam.eps, clip, grad_scale, step, stream);
-  }
-  return rc;
+  const RowList l{list_ids, list_rows, list_used, list_capacity};
+  if (!accum_ready(m) || !accum_list_ok(m, l)) return MMDA_EINVAL;
+  const OptStep o{lr, clip, grad_scale, step, acc, m->clip_norm > 0.f};
+  const int rc = opt_step_refused(m, o);
+  return rc ? rc : opt_step(m, o, 0, kNoWait, &l, stream);
 }
 
 namespace {
@@ -2325,22 +2341,19 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   // the gradient bucket is cleared on the side stream beside the forward pass's fusion block (not at the start of the step: the
   // side stream's first job there, packing W_hh, is what the first recurrent kernel waits for)
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
-  if (do_adam && adam_settings_refused(m)) return MMDA_EINVAL;
   // clip_norm: no update may precede the norm, so the backward pass runs as it does without an optimizer step (no early pass, event
   // join); the norm and one launch over the whole bucket follow it
-  const bool norm = do_adam && m->clip_norm > 0.f;
-  const bool early = do_adam && !norm;
-  if (masked(m) && do_adam) {                           // frozen parameters: the run table is on the device before the first launch
-    if (!m->M1 || !m->V1) return MMDA_EINVAL;
-    const int rr = runs_ready(m, stream);
-    if (rr) return rr;
-  }
+  const OptStep o{lr, clip, 1.0f, step, nullptr, do_adam && m->clip_norm > 0.f};
+  const bool early = do_adam && !o.norm;
+  int rc = do_adam ? opt_step_refused(m, o) : MMDA_OK;
+  if (!rc && do_adam && masked(m)) rc = runs_ready(m, stream);     // frozen parameters: the run table is there before the first launch
+  if (rc) return rc;
   m->inference = 0;                                     // a training step always stashes (but for the encoders of a cut step)
   m->zero_grad_pending = m->T > 0 ? 1 : 0;
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
   m->fj1 = m->fj2 = 0;
-  int rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
+  rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
   if (rc) return rc;
   rc = eb ? forward_encoded(m, eb, emo_gathered, training, seed, stream) : mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
   m->eager_losses = 0; m->emo_eager = nullptr;
@@ -2349,27 +2362,16 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   rc = mmda_misa_losses(m, emo, 1, stream);
   if (rc) return rc;
   // (the early optimizer pass beside the layer-1 recurrence: faster than one launch for the whole bucket at the end)
-  m->adam_early_on = early ? 1 : 0; m->ae_lr = lr; m->ae_clip = clip; m->ae_step = step; m->adam_early_done = 0;
-  rc = backward_pass(m, t_ids, v, a, lengths, stream);
-  m->adam_early_on = 0;
+  rc = backward_pass(m, t_ids, v, a, lengths, early ? &o : nullptr, stream);
   if (rc) return rc;
   if (m->fj1) { rc = flag_join_fallback(m, stream); m->fj1 = 0; if (rc) return rc; }      // (no stretch took it over: cannot happen)
   if (m->fj2 && !early) { rc = flag_join_fallback(m, stream); m->fj2 = 0; if (rc) return rc; }
-  if (norm) {
-    if (!m->M1 || !m->V1) return MMDA_EINVAL;
-    rc = bucket_norm(m, nullptr, 1.0f, stream);
-    if (!rc) rc = bucket_adam(m, 0, grad_floats(m), nullptr, lr, clip, 1.0f, step, kNoWait, stream, m->ws + m->gnorm + 1);
-  } else if (do_adam) {
-    // the rest of the bucket (layer-1 recurrent layers, embedding -- or everything, if the backward pass stepped nothing early)
-    const int64_t o = m->adam_early_done;
-    // (flag join: this launch does not complete before the side stream's weight-gradient GEMMs and early optimizer pass have)
-    const bool fj = m->fj2 != 0;
-    m->fj2 = 0;
-    // (sparse / frozen table: the launch ends in front of it -- and stays the waiter)
-    rc = bucket_adam(m, o, grad_floats(m), nullptr, lr, clip, 1.0f, step,
-                     FlagWait{fj ? m->jflags + 1 : nullptr, m->jval[1], fj ? m->jflags + 2 : nullptr}, stream);
-  }
-  return rc;
+  if (!do_adam) return MMDA_OK;
+  // the rest of the bucket (layer-1 recurrent layers, embedding -- or everything, if the backward pass stepped nothing early; a sparse
+  // or frozen table: the launch ends in front of it); flag join: it does not complete before the side stream's chain has
+  const bool fj = m->fj2 != 0;
+  m->fj2 = 0;
+  return opt_step(m, o, m->adam_early_done, fj ? FlagWait{m->jflags + 1, m->jval[1], m->jflags + 2} : kNoWait, nullptr, stream);
 }
 }  // namespace
 

@@ -21,7 +21,8 @@ from typing import Dict, List, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, step_rules
+from . import optim as _optim
 from .config import activation_name
 
 FFN_DIM = 2048          # torch default dim_feedforward of nn.TransformerEncoderLayer (reference models.py:160)
@@ -181,6 +182,7 @@ class MISA(nn.Module):
         self._trainable_sends = 0
         self._runs_cache = None
         self._cut_flags = None                              # the flags under which the native side last reported the encoder cut on
+        self._rules_passed = None                           # the last case step_rules let pass (MISA._rules)
         self._adam_pushed = _ADAM_DEFAULTS                  # (beta1, beta2, eps, weight_decay, decoupled, clip_norm) the native side holds
         # deferred mode: per-row step counts and the ring of step scalars (device, made with the flat buckets), and whether a step has
         # been taken since the last flush
@@ -407,9 +409,7 @@ class MISA(nn.Module):
         if "embed.weight" in frozen and self.embed_update in ("sparse", "deferred"):
             raise _lib.MMDAError(f"embed.weight.requires_grad=False under embed_update='{self.embed_update}': freeze the table with "
                                  "set_embed_update(\"frozen\")")
-        if exchange and [n for n in frozen if not (n == "embed.weight" and self.embed_update == "frozen")]:
-            raise _lib.MMDAError("frozen parameters (requires_grad=False) together with a gradient exchange (grad_sync / data parallel) "
-                                 "are not built yet")
+        step_rules.check(frozen=any(not (n == "embed.weight" and self.embed_update == "frozen") for n in frozen), exchange=exchange)
         if flags != self._trainable_sent:
             _lib.check(self._lib.mmda_misa_set_trainable(self._h, bytes(bytearray(int(f) for f in flags)), len(flags)), "set_trainable")
             self._trainable_sent = flags
@@ -664,113 +664,117 @@ class MISA(nn.Module):
         ``accum_index`` / ``accum_count``: this batch is micro-batch ``accum_index`` of an optimizer step made from ``accum_count``
         consecutive calls (0, 1, ... count - 1, the same count in each): the gradients of the micro-batches are summed in that order and
         the last call takes one clip + Adam step with their mean -- what ``accum_count`` data-parallel ranks would compute."""
-        from . import optim as _optim
         if accum_count != 1 or accum_index != 0 or self._acc_next:
             return self._accum_micro_step(sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync,
                                           optimizer, accum_index, accum_count, clip_norm)
-        adam = self._push_adam(optimizer, clip_norm, exchange=grad_sync is not None)
-        self._sync_trainable(exchange=grad_sync is not None)
-        t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
-        emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
-        if seed is None:
-            seed = self._next_seed()
-        custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
-        if not custom:
-            self._step += 1                        # (a custom optimizer counts its own steps on the same counter)
+        (t, v, a, len_dev), emo, seed, custom, adam = self._step_begin((sentences, video, acoustic, lengths), emo_label, optimizer, clip_norm,
+                                                                       do_adam, seed, exchange=grad_sync is not None)
         s = _lib.stream_ptr()
         fused_adam = do_adam and grad_sync is None and not custom
         gs_owner = getattr(grad_sync, "__self__", None)
-        if gs_owner is not None and getattr(gs_owner, "global_stats", False) and (gs_owner.world > 1 or gs_owner.force_collectives):
+        global_stats = getattr(gs_owner, "global_stats", False) and (gs_owner.world > 1 or gs_owner.force_collectives)
+        if global_stats:
             self._global_stats_step(t, v, a, len_dev, emo, training, seed, gs_owner)
         else:
             _lib.check(self._lib.mmda_misa_train_step(self._h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(),
                                                       emo.data_ptr(), int(training), seed, int(fused_adam), lr, clip, max(self._step, 1), s),
                        "mmda_misa_train_step")
-            self._fwd_id += 1
-        self._last = dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo)
-        self._rows_pending = self.embed_update in ("sparse", "deferred") and not fused_adam
-        self._rows_clip = None
-        self._rows_keep = (t, len_dev) if self._rows_pending else None     # (the native side holds these pointers until the rows update)
+        rows = self.embed_update in ("sparse", "deferred") and not fused_adam     # (pending: the native side holds t, len_dev until then)
+        self._step_end(dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo), rows, (t, len_dev) if rows else None, forwarded=not global_stats)
         self._df_dirty = self._df_dirty or (self.embed_update == "deferred" and fused_adam)
+        if not do_adam or fused_adam:
+            return
+        step_no = max(self._step, 1)
+        early = None
+        if not custom:
+            # A DataParallelSync (dist.py) steps the early-reduced prefix on its communication stream; the rest here, behind the exchange
+            def early(n_floats, stream, _gs=1.0 / float(getattr(gs_owner, "world", 1))):
+                self._adam_range(0, int(n_floats), lr, clip, _gs, step_no, stream.cuda_stream, adam, "adam(early)")
+        scale, done = self._exchange(grad_sync, early) if grad_sync is not None else (1.0, 0)
         if custom:
-            scale = 1.0
-            if grad_sync is not None:
-                scale = grad_sync(self._G, self._dense_floats, self) if _takes_model(grad_sync) else grad_sync(self._G, self._dense_floats)
-            optimizer.step(clip_value=clip, grad_scale=float(scale))
-        elif do_adam and grad_sync is not None:
-            # (bucket, dense_floats, model) or a plain (bucket, dense_floats) callable: decided from its signature, once -- never by
-            # retrying after a TypeError, which could come from inside the exchange after a collective was already issued
-            # A DataParallelSync (mmda_amd/dist.py) steps the early-reduced prefix of the bucket on its communication stream, beside the
-            # rest of the backward pass; the remainder is stepped here, behind the exchange.
-            owner = getattr(grad_sync, "__self__", None)
-            hook = owner is not None and hasattr(owner, "early_step") and hasattr(owner, "early_stepped") and hasattr(owner, "world")
-            if hook:
-                gs = 1.0 / float(owner.world)
-                step_no = max(self._step, 1)
+            optimizer.step(clip_value=clip, grad_scale=scale)
+        elif done > 0:
+            self._adam_range(done, self.grad_floats - done, lr, clip, scale, step_no, s, adam, "adam(rest)")
+        else:
+            _lib.check(self._lib.mmda_misa_adam_step(self._h, lr, clip, scale, self._step, s), "adam_step")
 
-                def _early(n_floats, stream, _gs=gs, _k=step_no):
-                    self._adam_range(0, int(n_floats), lr, clip, _gs, _k, stream.cuda_stream, adam, "adam(early)")
-                owner.early_step = _early
-            try:
-                if _takes_model(grad_sync):
-                    scale = grad_sync(self._G, self._dense_floats, self)
-                else:
-                    scale = grad_sync(self._G, self._dense_floats)
-            finally:
-                if hook:
-                    owner.early_step = None
-            done = int(owner.early_stepped) if hook else 0
-            if self.embed_update in ("sparse", "deferred"):
-                raise _lib.MMDAError(f"embed_update='{self.embed_update}' with a gradient exchange is not built yet")
-            if done > 0:
-                self._adam_range(done, self.grad_floats - done, lr, clip, float(scale), max(self._step, 1), s, adam, "adam(rest)")
-            else:
-                _lib.check(self._lib.mmda_misa_adam_step(self._h, lr, clip, float(scale), self._step, s), "adam_step")
+    # ------------------------------------------------------------------ what the step methods share
+    def _step_begin(self, batch, emo_label, optimizer, clip_norm, do_adam, seed, exchange=False, accumulate=False, encoded=False):
+        """The beginning of a step: what no step does is refused (step_rules), by name and before anything changes; the optimizer's
+        settings and the trainable set reach the native side; the batch -- (sentences, video, acoustic, lengths) or an EncodedBatch -- is
+        prepared; then a seed is drawn and the step counted (a custom optimizer counts its own steps on the same counter, an accumulated
+        step is counted by its closing micro-batch).  Returns (io, labels, seed, custom, Adam settings)."""
+        if encoded:
+            io, adam = self._encoded_begin(batch, "train_step_encoded", optimizer, clip_norm, exchange, accumulate, do_adam)
+            if batch.cache.emo is None:
+                raise _lib.MMDAError("train_step_encoded: the cache has no emotion labels (its dataset had none)")
+            self._send_adam(adam)
+            emo = torch.empty(batch.B, self.config.num_classes, dtype=torch.float32, device=batch.cache.device)
+        else:
+            adam = self._send_adam(self._rules(optimizer, clip_norm, exchange, accumulate, False, do_adam))
+            self._sync_trainable(exchange=exchange)
+            io = self._prepare(*batch)
+            emo = emo_label.to(device=io[0].device, dtype=torch.float32).contiguous()
+        if seed is None:
+            seed = self._next_seed()
+        custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
+        if not custom and not accumulate:
+            self._step += 1
+        return io, emo, seed, custom, adam
+
+    def _step_end(self, last, rows_pending=False, rows_keep=None, forwarded=True):
+        """The end of a native step: what the autograd path, the rows updates and the next step read of it."""
+        if forwarded:
+            self._fwd_id += 1
+        self._last = last
+        self._rows_pending, self._rows_clip, self._rows_keep = rows_pending, None, rows_keep
+
+    def _exchange(self, grad_sync, early=None):
+        """The step's one gradient exchange: ``grad_sync(bucket, dense_floats, model)`` or a plain ``(bucket, dense_floats)`` callable --
+        decided from its signature, never by retrying after a TypeError, which could come from behind an issued collective.  ``early``:
+        a DataParallelSync's early-step hook for the call.  Returns (gradient scale, floats of the bucket prefix the hook stepped)."""
+        owner = getattr(grad_sync, "__self__", None)
+        hook = early is not None and all(hasattr(owner, x) for x in ("early_step", "early_stepped", "world"))
+        if hook:
+            owner.early_step = early
+        try:
+            scale = grad_sync(self._G, self._dense_floats, self) if _takes_model(grad_sync) else grad_sync(self._G, self._dense_floats)
+        finally:
+            if hook:
+                owner.early_step = None
+        return float(scale), (int(owner.early_stepped) if hook else 0)
 
     # ------------------------------------------------------------------ the optimizer's settings
-    def _push_adam(self, optimizer, clip_norm, exchange: bool = False):
-        """What the native Adam of the step about to run must use: the attached optimizer's betas, eps, weight decay and decay kind
-        (``None`` or another optimizer class: Adam's defaults) and ``clip_norm``, sent with ``mmda_misa_set_adam`` when they differ
-        from what was sent last (the steady state: one tuple compare).  Raises, by name and before anything changes, for what no step
-        does.  Returns the tuple."""
-        from . import optim as _optim
-        key = _ADAM_DEFAULTS[:5]
-        if isinstance(optimizer, _optim.Adam):
-            key = optimizer.settings()
-        cn = 0.0 if clip_norm is None else float(clip_norm)
-        if not cn >= 0.0:
-            raise _lib.MMDAError(f"clip_norm must be >= 0 (None or 0: off), not {clip_norm}")
-        if key[3] > 0 and self.embed_update == "deferred":
-            raise _lib.MMDAError("weight_decay > 0 with embed_update='deferred' is not built: the replay ring keeps two scalars per "
-                                 "update and a decayed zero-gradient step needs a third (use 'dense' or 'sparse')")
-        if cn > 0 and self.embed_update in ("sparse", "deferred"):
-            raise _lib.MMDAError(f"clip_norm with embed_update='{self.embed_update}' is not built: the table's rows are updated where "
-                                 "their gradient sums become final, before a norm exists (use 'dense' or 'frozen')")
-        if cn > 0 and exchange:
-            raise _lib.MMDAError("clip_norm with a gradient exchange (grad_sync / data parallel) is not built: the early step updates a "
-                                 "prefix of the bucket before the whole gradient exists")
-        if cn > 0 and optimizer is not None and not isinstance(optimizer, _optim.Adam):
-            raise _lib.MMDAError(f"clip_norm with optimizer {type(optimizer).__name__} is not built: Adam / AdamW only")
-        key = key + (cn,)
+    def _rules(self, optimizer=None, clip_norm=None, exchange=False, accumulate=False, encoded=False, do_adam=True):
+        """The Adam settings of a step -- the attached optimizer's betas, eps, weight decay and decay kind (``None`` or another optimizer
+        class: Adam's defaults) and ``clip_norm`` -- once step_rules lets the step pass (the steady state: one tuple compare)."""
+        key = optimizer.settings() if isinstance(optimizer, _optim.Adam) else _ADAM_DEFAULTS[:5]
+        case = (self.embed_update, type(optimizer), key[3], clip_norm, exchange, accumulate, encoded, do_adam)
+        if case != self._rules_passed:
+            kind, name = _optim.rule_kind(optimizer)
+            step_rules.check(embed_update=self.embed_update, optimizer=kind, optimizer_name=name, weight_decay=key[3], clip_norm=clip_norm,
+                             exchange=exchange, accumulate=accumulate, encoded=encoded, do_adam=do_adam)
+            self._rules_passed = case
+        return key + (0.0 if clip_norm is None else float(clip_norm),)
+
+    def _send_adam(self, key):
+        """``mmda_misa_set_adam`` when the settings differ from what was sent last (the steady state: one tuple compare)."""
         if key != self._adam_pushed:
             if self.embed_update == "deferred" and key[:3] != self._adam_pushed[:3]:
                 self.flush_embedding()                      # stale rows replay the steps they missed under the betas those were made with
             opts = _lib.AdamOpts(beta1=key[0], beta2=key[1], eps=key[2], weight_decay=key[3], decoupled=int(key[4]), scale_dev=None)
-            _lib.check(self._lib.mmda_misa_set_adam(self._h, C.byref(opts), cn), "mmda_misa_set_adam")
+            _lib.check(self._lib.mmda_misa_set_adam(self._h, C.byref(opts), key[5]), "mmda_misa_set_adam")
             self._adam_pushed = key
         return key
 
+    def _push_adam(self, optimizer, clip_norm, exchange: bool = False):
+        """The Adam settings of the step about to run, on the handle; raises, by name and before anything changes, for what no step does"""
+        return self._send_adam(self._rules(optimizer, clip_norm, exchange))
+
     def _adam_range(self, first: int, n: int, lr, clip, grad_scale, step, stream, adam, what: str):
         """clamp + Adam over floats [first, first + n) of the flat buckets with the settings ``adam`` (the data-parallel step's launches)."""
-        o = first * 4
-        ptrs = [x.data_ptr() + o for x in (self._P, self._G, self._M, self._V)]
-        if adam[3] > 0:
-            opts = _lib.AdamOpts(beta1=adam[0], beta2=adam[1], eps=adam[2], weight_decay=adam[3], decoupled=int(adam[4]), scale_dev=None)
-            rc = self._lib.mmda_clamp_adam_opts(ptrs[0], None, ptrs[1], ptrs[2], ptrs[3], n, None, 0, 0, lr, clip, grad_scale, step,
-                                                C.byref(opts), stream)
-        else:
-            rc = self._lib.mmda_clamp_adam(*ptrs, n, lr, adam[0], adam[1], adam[2], clip, grad_scale, step, stream)
-        _lib.check(rc, what)
+        ptrs = [x.data_ptr() + first * 4 for x in (self._P, self._G, self._M, self._V)]
+        _optim.clamp_adam(self._lib, *ptrs, n, None, lr, clip, grad_scale, step, adam, None, stream, what)
 
     def grad_norm(self) -> torch.Tensor:
         """The gradient norm of the last step taken with ``clip_norm`` (what ``clip_grad_norm_`` returns), as a 0-d view of device
@@ -780,17 +784,15 @@ class MISA(nn.Module):
         return self._ws_view("grad_norm", (2,))[0]
 
     # ------------------------------------------------------------------ steps that start behind the encoders (mmda_amd/encoded.py)
-    def _encoded_begin(self, batch, what: str, exchange=None, accum_index: int = 0, accum_count: int = 1):
+    def _encoded_begin(self, batch, what: str, optimizer=None, clip_norm=None, exchange=False, accumulate=False, do_adam=True):
         """Everything a step from the encoder cache refuses, by name and before any launch; then the workspace carved at (B, 1) --
-        nothing such a step runs depends on T -- and the native batch."""
+        nothing such a step runs depends on T -- and the native batch, with the step's Adam settings."""
         from .encoded import EncodedBatch
         if not isinstance(batch, EncodedBatch):
             raise TypeError(f"{what} takes an EncodedBatch (EncodedLoader yields them), not {type(batch).__name__}")
-        if exchange is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
-                                    and torch.distributed.get_world_size() > 1):
-            raise _lib.MMDAError(f"{what} with a gradient exchange (grad_sync / a process group) is not built")
-        if self.accum_steps > 1 or accum_index != 0 or accum_count != 1 or self._acc_next:
-            raise _lib.MMDAError(f"{what} with gradient accumulation (accum_steps > 1, accum_index, accum_count) is not built")
+        dist = torch.distributed
+        adam = self._rules(optimizer, clip_norm, exchange or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1),
+                           accumulate or self.accum_steps > 1 or bool(self._acc_next), True, do_adam)
         cache = batch.cache
         cache._refuse(self)                                  # another device, other widths
         flags = self._sync_trainable()
@@ -809,7 +811,7 @@ class MISA(nn.Module):
             self._materialize(cache.device)
         self._carve(batch.B, 1, cache.device)
         return _lib.EncodedBatch(tab_t=cache.utt_t.data_ptr(), tab_v=cache.utt_v.data_ptr(), tab_a=cache.utt_a.data_ptr(),
-                                 tab_emo=_lib.ptr(cache.emo), rows=batch.rows_ptr, B=batch.B)
+                                 tab_emo=_lib.ptr(cache.emo), rows=batch.rows_ptr, B=batch.B), adam
 
     def train_step_encoded(self, batch, lr: float, clip: float, do_adam: bool = True, training: bool = True, seed=None, optimizer=None,
                            grad_sync=None, accum_index: int = 0, accum_count: int = 1, clip_norm=None):
@@ -817,22 +819,11 @@ class MISA(nn.Module):
         and starts at the projections.  Needs the encoder cut; seeds, the step counter and ``optimizer`` are ``train_step``'s (a
         custom optimizer, RMSprop, is stepped by its own kernel behind the native step without its Adam).  ``grad_sync`` and the
         accumulation arguments exist to be refused by name."""
-        from . import optim as _optim
-        eb = self._encoded_begin(batch, "train_step_encoded", grad_sync, accum_index, accum_count)
-        if batch.cache.emo is None:
-            raise _lib.MMDAError("train_step_encoded: the cache has no emotion labels (its dataset had none)")
-        self._push_adam(optimizer, clip_norm)
-        if seed is None:
-            seed = self._next_seed()
-        custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
-        if not custom:
-            self._step += 1
-        emo = torch.empty(batch.B, self.config.num_classes, dtype=torch.float32, device=batch.cache.device)
+        eb, emo, seed, custom, _ = self._step_begin(batch, None, optimizer, clip_norm, do_adam, seed, exchange=grad_sync is not None,
+                                                    accumulate=accum_index != 0 or accum_count != 1, encoded=True)
         _lib.check(self._lib.mmda_misa_train_step_encoded(self._h, C.byref(eb), emo.data_ptr(), int(training), seed, int(do_adam and not custom),
                                                           lr, clip, max(self._step, 1), _lib.stream_ptr()), "mmda_misa_train_step_encoded")
-        self._fwd_id += 1
-        self._last = dict(encoded=batch, emo=emo)
-        self._rows_pending, self._rows_clip, self._rows_keep = False, None, None
+        self._step_end(dict(encoded=batch, emo=emo))
         if custom:
             optimizer.step(clip_value=clip, grad_scale=1.0)
 
@@ -841,7 +832,7 @@ class MISA(nn.Module):
         set as ``alignment`` sets them.  Draws one seed, as ``model(...)`` does."""
         if torch.is_grad_enabled():
             raise _lib.MMDAError("autograd through forward_encoded is not built: call it under torch.no_grad() (train with train_step_encoded)")
-        eb = self._encoded_begin(batch, "forward_encoded")
+        eb, _ = self._encoded_begin(batch, "forward_encoded")
         eb.tab_emo = None
         seed = self._next_seed()
         _lib.check(self._lib.mmda_misa_set_inference(self._h, 1), "set_inference")
@@ -863,7 +854,6 @@ class MISA(nn.Module):
                           index, count, clip_norm=None) -> None:
         """Micro-batch ``index`` of an optimizer step made from ``count``: the native step without its optimizer part, then either the
         add into the second bucket or -- behind the last one -- clip + Adam on (accumulated + this micro-batch's gradients) / count."""
-        from . import optim as _optim
         expected, self._acc_next = self._acc_next, 0           # (any refusal below leaves the sequence reset)
         self._acc_used = 0 if expected == 0 else self._acc_used
         for x in (index, count):
@@ -875,30 +865,13 @@ class MISA(nn.Module):
             raise _lib.MMDAError(f"accumulated step: micro-batch {index} of {count} arrived where {expected} of "
                                  f"{self._acc_count if expected else count} was due (indices run 0 .. count - 1 with one count); "
                                  "the sequence starts over")
-        if grad_sync is not None:
-            raise _lib.MMDAError("accum_steps > 1 together with a gradient exchange (grad_sync / data parallel) is not built yet")
-        if optimizer is not None and not isinstance(optimizer, _optim.Adam):
-            raise _lib.MMDAError(f"accum_steps > 1 with optimizer {type(optimizer).__name__} is not built: Adam only")
-        if self.embed_update == "deferred":
-            raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built: the mode's contract is dense Adam's bits, "
-                                 "which one rows update over the micro-batches' concatenated list does not give")
-        if not do_adam:
-            raise _lib.MMDAError("accum_steps > 1 with do_adam=False: the accumulated step ends in its optimizer step")
-        self._push_adam(optimizer, clip_norm)
-        self._sync_trainable()
-        t, v, a, len_dev = self._prepare(sentences, video, acoustic, lengths)
-        emo = emo_label.to(device=t.device, dtype=torch.float32).contiguous()
-        if seed is None:
-            seed = self._next_seed()
+        (t, v, a, len_dev), emo, seed, _, _ = self._step_begin((sentences, video, acoustic, lengths), emo_label, optimizer, clip_norm, do_adam,
+                                                               seed, exchange=grad_sync is not None, accumulate=True)
         s = _lib.stream_ptr()
         lib, h = self._lib, self._h
         _lib.check(lib.mmda_misa_train_step(h, t.data_ptr(), v.data_ptr(), a.data_ptr(), len_dev.data_ptr(), emo.data_ptr(), int(training),
                                             seed, 0, lr, clip, max(self._step, 1), s), "mmda_misa_train_step")
-        self._fwd_id += 1
-        self._last = dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo)
-        self._rows_pending = False                             # (sparse: the rows go to the list below, the native side forgets them)
-        self._rows_clip = None
-        self._rows_keep = None
+        self._step_end(dict(t=t, v=v, a=a, len_dev=len_dev, emo=emo))       # (sparse: the rows go to the list below, nothing stays pending)
         closing = index == count - 1
         n = self.grad_floats
         if count > 1 and (self._acc is None or self._acc.numel() < n or self._acc.device != t.device):

@@ -14,7 +14,25 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, step_rules
+
+
+def rule_kind(optimizer):
+    """(kind, class name) of an optimizer, an optimizer class or None, as step_rules takes them"""
+    if optimizer is None:
+        return None, ""
+    cls = optimizer if isinstance(optimizer, type) else type(optimizer)
+    return ("adam" if issubclass(cls, Adam) else "other"), cls.__name__
+
+
+def clamp_adam(lib, p, g, m, v, n, runs, lr, clip, grad_scale, step, settings, scale_dev, stream, what):
+    """One clamp + Adam launch over n floats, or over ``runs`` = (table, n_runs, items), with ``settings`` = (beta1, beta2, eps, weight_decay,
+    decoupled).  Always mmda_clamp_adam_opts: without decay and device scale it launches what the plain entries launch (mmda_hip.h)."""
+    b1, b2, eps, wd, dec = settings[:5]
+    table, n_runs, items = runs if runs is not None else (None, 0, 0)
+    opts = _lib.AdamOpts(beta1=b1, beta2=b2, eps=eps, weight_decay=wd, decoupled=int(dec), scale_dev=_lib.ptr(scale_dev))
+    _lib.check(lib.mmda_clamp_adam_opts(p, None, g, m, v, n, _lib.ptr(table), n_runs, items, lr, clip, grad_scale, step,
+                                        _lib.C.byref(opts), stream), what)
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -174,21 +192,6 @@ class Adam(_FlatOptimizer):
                                  "is one group)")
         return super().add_param_group(param_group)
 
-    def _launch(self, lib, p, g, m, v, n, runs, lr, clip, grad_scale, t, st, scale_dev, s, what):
-        """one clamp + Adam launch over n floats, or over (table, n_runs, items): the plain entries while they can express the
-        settings (the launch they have always been), else the one that takes mmda_adam_opts"""
-        b1, b2, eps, wd, dec = st
-        table, n_runs, items = runs if runs is not None else (None, 0, 0)
-        if wd > 0 or scale_dev is not None:
-            opts = _lib.AdamOpts(beta1=b1, beta2=b2, eps=eps, weight_decay=wd, decoupled=int(dec), scale_dev=_lib.ptr(scale_dev))
-            rc = lib.mmda_clamp_adam_opts(p, None, g, m, v, n, _lib.ptr(table), n_runs, items, lr, clip, grad_scale, t,
-                                          _lib.C.byref(opts), s)
-        elif runs is not None:
-            rc = lib.mmda_clamp_adam_runs(p, g, m, v, table.data_ptr(), n_runs, items, lr, b1, b2, eps, clip, grad_scale, t, s)
-        else:
-            rc = lib.mmda_clamp_adam(p, g, m, v, n, lr, b1, b2, eps, clip, grad_scale, t, s)
-        _lib.check(rc, what)
-
     def _flat_state(self):
         _, _, M, V = self._model.flat_buckets()
         return {"exp_avg": M, "exp_avg_sq": V}
@@ -221,8 +224,8 @@ class Adam(_FlatOptimizer):
             n = getattr(m, "grad_floats", P.numel())
             # frozen parameters (requires_grad=False): the same update over the trainable runs of the bucket only
             runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
-            self._launch(lib, P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, runs, g0["lr"], clip, grad_scale, t, cfg, scale_dev,
-                         s, "mmda_clamp_adam_runs" if runs is not None else "mmda_clamp_adam")
+            clamp_adam(lib, P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, runs, g0["lr"], clip, grad_scale, t, cfg, scale_dev,
+                       s, "mmda_clamp_adam_runs" if runs is not None else "mmda_clamp_adam")
             if getattr(m, "embed_update", "dense") == "sparse":
                 rows_clip = clip if m._rows_clip is None else min(clip, float(m._rows_clip))
                 m.apply_sparse_rows(g0["lr"], t, rows_clip, grad_scale, betas=(b1, b2), eps=g0["eps"])
@@ -248,8 +251,8 @@ class Adam(_FlatOptimizer):
                 gb1, gb2 = group["betas"]
                 gst = (float(gb1), float(gb2), float(group["eps"]), float(group.get("weight_decay", 0.0)),
                        bool(group.get("decoupled_weight_decay", False)))
-                self._launch(lib, p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(), None, group["lr"], clip,
-                             grad_scale, t, gst, scale_dev, s, "mmda_clamp_adam")
+                clamp_adam(lib, p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(), None, group["lr"], clip,
+                           grad_scale, t, gst, scale_dev, s, "mmda_clamp_adam")
         return None
 
 
@@ -293,10 +296,7 @@ class RMSprop(_FlatOptimizer):
         clip = float("inf") if clip is None else float(clip)
         m = self._flat()
         if m is not None:
-            if getattr(m, "embed_update", "dense") == "sparse":
-                raise _lib.MMDAError("embed_update='sparse' is defined for Adam only (torch has no sparse RMSprop)")
-            if getattr(m, "embed_update", "dense") == "deferred":
-                raise _lib.MMDAError("embed_update='deferred' is built for Adam only")
+            step_rules.check(embed_update=getattr(m, "embed_update", "dense"), optimizer="other", optimizer_name=type(self).__name__)
             P, G, _, _ = m.flat_buckets()
             sq = self._square_avg(P)
             runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None
@@ -351,9 +351,7 @@ def clip_grad_norm_(model_or_params, max_norm):
         raise ValueError(f"max_norm must be >= 0: {max_norm}")
     m = model_or_params
     if hasattr(m, "flat_buckets") and m._G is not None:
-        if getattr(m, "embed_update", "dense") in ("sparse", "deferred"):
-            raise _lib.MMDAError(f"clip_grad_norm_ with embed_update='{m.embed_update}' is not built: the table's gradient rows are not "
-                                 "coalesced before the rows update, so no norm of the whole gradient exists")
+        step_rules.check(embed_update=getattr(m, "embed_update", "dense"), clip_norm=1.0)      # (any norm of the whole gradient)
         G = m._G
         n = getattr(m, "grad_floats", G.numel())
         runs = m._trainable_runs() if hasattr(m, "_trainable_runs") else None

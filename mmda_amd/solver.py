@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import models
+from . import models, step_rules
 from . import optim as _optim
 from .dist import DataParallelSync
 from .encoded import EncodedBatch, EncodedLoader, EncoderCache
@@ -62,51 +62,19 @@ class Solver(object):
             # (the reference writes `self.model.embed.requires_grad = False` here, solver.py:86: an attribute on the module that
             # freezes nothing.  Whether the table trains is config.embed_update: 'dense' (what the reference does), 'sparse', 'frozen')
         eu = getattr(self.model, "embed_update", "dense")
-        is_adam = isinstance(cfg.optimizer, type) and issubclass(cfg.optimizer, _optim.Adam)          # Adam or AdamW
         opt_kwargs = dict(getattr(cfg, "optimizer_kwargs", None) or {})
         if cfg.optimizer is _optim.AdamW and "weight_decay" not in opt_kwargs:
             opt_kwargs["weight_decay"] = cfg.weight_decay
         clip_norm = getattr(cfg, "clip_norm", None)
         dp_on = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-        if eu == "sparse" and self.is_train:
-            from . import _lib
-            if not is_adam:
-                raise _lib.MMDAError("embed_update='sparse' is defined for optimizer='Adam' only (torch has no sparse RMSprop to match)")
-            if dp_on:
-                raise _lib.MMDAError("embed_update='sparse' under data parallelism is not built yet (use 'dense' or 'frozen')")
-        if eu == "deferred" and self.is_train:
-            from . import _lib
-            if not is_adam:
-                raise _lib.MMDAError("embed_update='deferred' is built for optimizer='Adam' only")
-            if dp_on:
-                raise _lib.MMDAError("embed_update='deferred' under data parallelism is not built yet (use 'dense' or 'frozen')")
-        if int(getattr(cfg, "accum_steps", 1)) > 1 and self.is_train:
-            from . import _lib
-            if not is_adam:
-                raise _lib.MMDAError("accum_steps > 1 is built for optimizer='Adam' only (not with RMSprop)")
-            if dp_on:
-                raise _lib.MMDAError("accum_steps > 1 under data parallelism (world x accumulation) is not built yet")
-            if eu == "deferred":
-                raise _lib.MMDAError("accum_steps > 1 with embed_update='deferred' is not built (use 'dense': the same weights)")
         if self.is_train:
-            from . import _lib
-            if eu == "deferred" and float(opt_kwargs.get("weight_decay", 0) or 0) > 0:
-                raise _lib.MMDAError("weight_decay > 0 with embed_update='deferred' is not built: the replay ring keeps two scalars "
-                                     "per update and a decayed zero-gradient step needs a third (use 'dense' or 'sparse')")
-            if clip_norm is not None and float(clip_norm) > 0:
-                if not is_adam:
-                    raise _lib.MMDAError("clip_norm is built for optimizer='Adam' / 'AdamW' only")
-                if eu in ("sparse", "deferred"):
-                    raise _lib.MMDAError(f"clip_norm with embed_update='{eu}' is not built: the table's rows are updated where their "
-                                         "gradient sums become final, before a norm exists (use 'dense' or 'frozen')")
-                if dp_on:
-                    raise _lib.MMDAError("clip_norm under data parallelism (a gradient exchange) is not built: the early step updates a "
-                                         "prefix of the bucket before the whole gradient exists")
-        if self.is_train and hasattr(self.model, "frozen_names") and self.model.frozen_names(beyond_embed_update=True):
-            from . import _lib
-            if torch.distributed.is_available() and torch.distributed.is_initialized():
-                raise _lib.MMDAError("frozen parameters (requires_grad=False) under data parallelism are not built yet "
-                                     "(embed_update='frozen' alone is)")
+            # what no step does (step_rules.py), refused here rather than at the first batch.  An exchange: a process group of more than
+            # one rank; for frozen parameters, any initialised process group
+            kind, name = _optim.rule_kind(cfg.optimizer)
+            step_rules.check(embed_update=eu, optimizer=kind, optimizer_name=name, weight_decay=float(opt_kwargs.get("weight_decay", 0) or 0),
+                             clip_norm=clip_norm, exchange=dp_on, accumulate=int(getattr(cfg, "accum_steps", 1)) > 1)
+            step_rules.check(frozen=bool(hasattr(self.model, "frozen_names") and self.model.frozen_names(beyond_embed_update=True)),
+                             exchange=torch.distributed.is_available() and torch.distributed.is_initialized())
         self.model.to(self.device)
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate, **opt_kwargs)

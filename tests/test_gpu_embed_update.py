@@ -416,6 +416,36 @@ def test_sparse_with_rmsprop_raises_at_build(monkeypatch):
     assert s.model.embed.weight.grad is None
 
 
+@pytest.mark.parametrize("mode", ["sparse", "deferred"])
+def test_a_grad_sync_is_refused_in_front_of_the_step(mode):
+    """train_step(grad_sync=...) under a rows mode: refused before anything changes -- the exchange is never called, no seed is drawn,
+    no step is counted and the parameters keep their bits -- and the model then steps as one that was never asked."""
+    from mmda_amd import _lib, make_config, models
+    cfg = orc.default_config(vocab_size=120)
+    c = make_config(precision="fp32", device=DEV, embed_update=mode, **vars(cfg))
+    b = orc.synth_batch(cfg, 8, 12, 61, ragged=True)
+    m, never = models.MISA(c), models.MISA(c)
+    for x in (m, never):
+        x.load_state_dict(orc.synth_params(cfg, 9))
+        x.to(DEV)
+    _step(m, b, seed=1); _step(never, b, seed=1)             # (buckets, workspace and moments exist)
+    calls = []
+
+    def sync(G, n):
+        calls.append(n)
+        return 1.0
+
+    step_no, seed, params = m._step, m._seed, m.flat_buckets()[0].clone()
+    with pytest.raises(_lib.MMDAError, match="not built yet"):
+        _step(m, b, grad_sync=sync)
+    assert not calls
+    assert m._step == step_no and m._seed == seed
+    assert torch.equal(m.flat_buckets()[0], params)
+    _step(m, b); _step(never, b)
+    for x, y in zip(m.flat_buckets(), never.flat_buckets()):
+        assert torch.equal(x, y)
+
+
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 

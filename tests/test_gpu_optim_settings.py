@@ -410,6 +410,53 @@ def test_fused_step_equals_unfused_step(precision, case):
         assert not torch.equal(_state(plain)[0], _state(m)[0])
 
 
+# (name, model kwargs, parameters frozen by requires_grad, whether the norm is clipped)
+TAIL_CASES = [("dense", {}, (), False), ("dense_norm", {}, (), True), ("sparse", dict(embed_update="sparse"), (), False),
+              ("frozen", dict(embed_update="frozen"), (), False), ("frozen_norm", dict(embed_update="frozen"), (), True),
+              ("masked", {}, ("trnn1", "project_v"), False), ("masked_norm", {}, ("trnn1", "project_v"), True)]
+
+
+@pytest.mark.parametrize("case", TAIL_CASES, ids=[c[0] for c in TAIL_CASES])
+def test_the_three_native_tails_give_the_same_bits(case):
+    """One batch at B = 8, T = 12 through each native entry that issues the optimizer part of a step: the fused train_step; train_step
+    without its optimizer, then mmda_misa_adam_step; the same, then mmda_misa_adam_step_accumulated with no accumulator.  The update is
+    an element function of the same gradient bucket (where the bucket is split between the early pass and the rest does not enter it),
+    and the sparse table's rows sum in list order on every path: parameters and both moments are equal bit for bit."""
+    from mmda_amd import _lib
+    _, mkw, frozen, clipped = case
+    models = [_model("fp32", **mkw) for _ in range(3)]
+    cfg = models[0][1]
+    fused, stepped, closed = (m for m, _ in models)
+    b = orc.synth_batch(cfg, 8, 12, 64, ragged=True)
+    for m in (fused, stepped, closed):
+        if frozen:
+            m.freeze(*frozen)
+    clip_norm = None
+    if clipped:
+        probe, _ = _model("fp32", **mkw)
+        clip_norm = 0.5 * _bucket_norm(probe, b)
+        del probe
+    start = _state(fused)
+    _step(fused, b, clip_norm=clip_norm, seed=9)
+    lib, s = fused._lib, _lib.stream_ptr()
+    _step(stepped, b, clip_norm=clip_norm, do_adam=False, seed=9)
+    _lib.check(lib.mmda_misa_adam_step(stepped._h, LR, CLIP, 1.0, 1, s), "adam_step")
+    _step(closed, b, clip_norm=clip_norm, do_adam=False, seed=9)
+    ids = rows = None
+    R = b["t"].numel()
+    if closed.embed_update == "sparse":
+        ids = torch.empty(R, dtype=torch.int64, device=DEV)
+        rows = torch.empty(R, closed.embed.weight.shape[1], dtype=torch.float32, device=DEV)
+    _lib.check(lib.mmda_misa_adam_step_accumulated(closed._h, None, _lib.ptr(ids), _lib.ptr(rows), 0, R if ids is not None else 0,
+                                                   LR, CLIP, 1.0, 1, s), "adam_step_accumulated")
+    assert fused._step == stepped._step == closed._step == 1
+    for other, what in ((stepped, "adam_step"), (closed, "adam_step_accumulated")):
+        _assert_state_equal(_state(fused), _state(other), (case[0], what))
+        if clipped:
+            assert torch.equal(fused.grad_norm().cpu(), other.grad_norm().cpu()) and float(fused.grad_norm()) > clip_norm
+    assert not torch.equal(_state(fused)[0], start[0]) and not fused.cluster_aborted()
+
+
 # ------------------------------------------------------------------------------------------------ 6: the other paths
 def test_accumulated_steps_through_solver():
     """accum_steps = 2 over three batches (steps of 2 and 1) with AdamW and a norm clip, dropout on, against the manual path: the
