@@ -439,6 +439,31 @@ int mmda_loss_misc(const float* scores, const float* tcp, const float* emo, int 
 int mmda_eval_accumulate(const float* pred, const float* truth, int N, int C, double* state, void* stream);
 int mmda_loss_domain(const float* dom, int B, float scale, float* loss, float* ddom, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- threshold calibration
+ * The decision is labels = scores > threshold (reference models.py:249).  A sweep counts, for EVERY cut-off of a grid at once, what
+ * get_metrics / get_accuracy (utils/eval.py:14-65) are functions of -- in integers, so the result is the same bits on every run.
+ *   pos(i,c) = truth[i,c] > 0;  bin(s) = #{k : s > thr[k]} in 0..K for a strictly increasing fp32 grid thr[0..K) (NaN: bin 0);
+ *   "predicted at cut-off k" = bin > k = s > thr[k].
+ * mmda_calib_accumulate ADDS into hist[C][K+1][2] (hist[c][j][p]: rows with bin(scores[i,c]) == j and pos(i,c) == p) and, where pairs
+ * is given, into pairs[K][C+1][C+1] (pairs[k][a][b]: rows with |y & p| == a and |y | p| == b at cut-off k); both are zeroed by the
+ * caller before the first batch.  scores / truth (N, C) fp32 and thr are device pointers.  1 <= C <= 16, 1 <= K <= 256, N >= 0
+ * (N == 0: MMDA_OK, no launch); a NULL among scores / truth / thr / hist or a bound violation is MMDA_EINVAL before any launch. */
+int mmda_calib_accumulate(const float* scores, const float* truth, int64_t N, int C, const float* thr, int K,
+                          unsigned long long* hist, unsigned long long* pairs, void* stream);
+/* One workgroup, no read-back: tp / fp per cut-off as suffix sums of hist, fn from the class's positives, fp64 in a fixed order.
+ * table (optional, K x 10 doubles): the reference's ten figures {acc, f1, precision, recall, micro_*, weighted_*} with ONE cut-off k
+ * for all classes, zero where a denominator is zero; acc = sum pairs[k][a][b] a (720720 / max(b, 1)) / (720720 N), unrounded, NaN
+ * where pairs is NULL.  out_thr[C], out_k[C] (device): the cut-off that maximises `objective`, ties to the lowest k; per_class = 1
+ * (objectives F1 and WEIGHTED_F1 only): every class takes the k of its own best F1, which maximises both over all per-class
+ * assignments on the grid.  MMDA_EINVAL: per_class with MICRO_F1 or ACC; ACC without pairs. */
+enum { MMDA_CALIB_F1 = 0, MMDA_CALIB_MICRO_F1 = 1, MMDA_CALIB_WEIGHTED_F1 = 2, MMDA_CALIB_ACC = 3 };
+int mmda_calib_select(const unsigned long long* hist, const unsigned long long* pairs, int C, int K, const float* thr, int objective,
+                      int per_class, float* out_thr, int32_t* out_k, double* table, void* stream);
+/* mmda_eval_accumulate with the labels made inside: scores[i,c] > thr_c[c], thr_c = C device floats.  The same `state`;
+ * labels_out (optional) receives the (N, C) 0/1 labels. */
+int mmda_eval_accumulate_thr(const float* scores, const float* truth, int N, int C, const float* thr_c, float* labels_out,
+                             double* state, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- optimizer
  * clip_grad_value_(clip) then Adam (solver.py:185-186, :97-99; betas 0.9/0.999, eps 1e-8, no weight decay), fused over
  * a flat bucket.  step = 1-based step count.  grad_scale multiplies g first (1/world for DP averaging). */

@@ -5,7 +5,8 @@ Public surface mirrors the reference's modules: ``models.MISA`` (alias ``Model``
 (``collate_fn``, ``DevicePrefetcher``; the device-resident ``DeviceDataset`` / ``DeviceLoader`` and their host core ``batch_plan`` are
 exported here too), the output side in ``inference`` (``InferencePass``: per-sample scores, confidence and hidden vectors kept on the
 device) and ``utils.tools`` (their files); ``encoded`` holds the encoder cache (``EncoderCache``, ``EncodedLoader``: training the
-fusion block and the heads of a model with frozen encoders from stored encoder outputs).
+fusion block and the heads of a model with frozen encoders from stored encoder outputs); ``calibrate`` sweeps the decision cut-off
+(``ThresholdSweep``, ``Thresholds``: every candidate threshold counted on the device in one launch per batch).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -13,3 +14,4 @@ from .config import Config, get_config, make_config  # noqa: F401
 from .data import DeviceDataset, DeviceLoader, batch_plan  # noqa: F401
 from .inference import FIELDS, InferencePass, InferenceResult, inference_plan  # noqa: F401
 from .encoded import EncodedBatch, EncodedLoader, EncoderCache  # noqa: F401
+from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_grid  # noqa: F401

@@ -215,6 +215,9 @@ SIGNATURES = {
     "mmda_loss_recon": (_I, [_P, _P, _I64, _I, _I, _F, _P, _P, _P, _P]),
     "mmda_loss_misc": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I64, _F, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
     "mmda_eval_accumulate": (_I, [_P, _P, _I, _I, _P, _P]),
+    "mmda_calib_accumulate": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P]),
+    "mmda_calib_select": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "mmda_eval_accumulate_thr": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mmda_loss_domain": (_I, [_P, _I, _F, _P, _P, _P]),
     "mmda_clamp_adam": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_clamp_adam_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _F, _F, _F, _F, _I, _P]),

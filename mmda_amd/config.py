@@ -87,6 +87,10 @@ DEFAULTS = dict(
     # torch.nn.utils.clip_grad_norm_'s max_norm, applied in front of `clip` (None = off).  optimizer="AdamW" without a weight_decay among
     # its kwargs takes the weight_decay above -- the reference's flag, which optimizer="Adam" keeps ignoring as the reference does.
     optimizer_kwargs={}, clip_norm=None,
+    # after the last epoch of Solver.train(): "global" / "per_class" sweep the decision cut-off(s) over the dev split with the best
+    # checkpoint (mmda_amd/calibrate.py; objective: what eval_mode names) and the final test evaluation decides with them; "none": the
+    # reference's loop, which decides with `threshold` throughout
+    calibrate="none",
 )
 
 
@@ -101,6 +105,8 @@ def get_config(parse=True, **optional_kwargs):
             parser.add_argument(f"--{k}", type=_json_object, default=dict(v))
         elif k == "clip_norm":
             parser.add_argument(f"--{k}", type=float, default=None)
+        elif k == "calibrate":
+            parser.add_argument(f"--{k}", choices=("none", "global", "per_class"), default=v)
         elif v is None:
             parser.add_argument(f"--{k}", default=None)
         else:

@@ -221,15 +221,25 @@ class Solver(object):
             if self.dp is not None:
                 torch.distributed.barrier()               # every epoch, on every rank: nobody reads the checkpoint before rank 0 has written it
             history.append(dict(epoch=e, train=tr, valid_loss=valid_loss, valid_acc=valid_acc))
-        test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0)
+        thresholds = self._calibrate_after_training(best_epoch >= 0)
+        test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds)
         print("=" * 50)
         print(f"Best epoch: {best_epoch}")
         print(f"Accuracy: {acc}")
         return history
 
     # ------------------------------------------------------------------ eval (solver.py:311-370)
-    def eval(self, mode=None, to_print=False):
+    def _load_best_checkpoint(self):
+        path = f"checkpoints/model_{self.train_config.name}.std"
+        if os.path.exists(path):
+            self.model.load_state_dict(torch.load(path, weights_only=True))
+
+    def eval(self, mode=None, to_print=False, thresholds=None):
+        """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
+        labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels."""
         assert mode is not None
+        if thresholds is not None:
+            return self._eval_thresholds(mode, to_print, thresholds)
         self.model.eval()
         y_true, y_pred, eval_loss = [], [], []
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
@@ -269,6 +279,91 @@ class Solver(object):
         eval_loss = float(np.mean(eval_loss)) if eval_loss else 0.0
         self.last_eval_metrics = get_metrics(y_true, y_pred)
         return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
+
+    # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py)
+    def _eval_batches(self, dataloader):
+        """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``."""
+        self.model.eval()
+        with torch.no_grad():
+            for batch in dataloader:
+                if isinstance(batch, EncodedBatch):
+                    predicted_scores, _ = self.model.forward_encoded(batch)
+                    emo_label = batch.emo()
+                else:
+                    t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
+                    t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                    l = to_cpu(l)
+                    predicted_scores, _ = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
+                yield predicted_scores, emo_label.type(torch.float)
+
+    def _eval_thresholds(self, mode, to_print, thresholds):
+        from . import _lib
+        if mode == "test" and to_print:
+            self._load_best_checkpoint()
+        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        thr = thresholds.values.to(device=self.device, dtype=torch.float32).contiguous()
+        acc_dev, lib = None, _lib.load()
+        y_true, y_pred = [], []
+        for scores, emo_label in self._eval_batches(dataloader):
+            if not scores.is_cuda:
+                raise _lib.MMDAError("eval(thresholds=...) counts on the GPU only (the HIP path has no CPU fallback)")
+            if thr.numel() != scores.shape[1]:
+                raise ValueError(f"thresholds has {thr.numel()} entries, the model {scores.shape[1]} classes")
+            if acc_dev is None:
+                acc_dev = DeviceEval(scores.shape[1], scores.device)
+            s, t = scores.detach().to(torch.float32).contiguous(), emo_label.contiguous()
+            labels = torch.empty_like(s)
+            _lib.check(lib.mmda_eval_accumulate_thr(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], thr.data_ptr(), labels.data_ptr(),
+                                                    acc_dev.state.data_ptr(), _lib.stream_ptr()), "mmda_eval_accumulate_thr")
+            acc_dev.add_cls_loss(scores, emo_label)
+            y_pred.append(labels)
+            y_true.append(emo_label.detach())
+        y_true = torch.cat(y_true, 0).cpu().numpy().squeeze() if y_true else np.zeros((0,))
+        y_pred = torch.cat(y_pred, 0).cpu().numpy().squeeze() if y_pred else np.zeros((0,))
+        self._check_cluster(f"eval({mode})")
+        if acc_dev is None:
+            self.last_eval_metrics = get_metrics(y_true, y_pred)
+            return 0.0, get_accuracy(y_true, y_pred), y_pred, y_true
+        loss, acc, self.last_eval_metrics = acc_dev.result()
+        return loss, acc, y_pred, y_true
+
+    def calibrate(self, mode="dev", grid=None, objective=None, per_class=True):
+        """Sweeps every cut-off of ``grid`` (default 0.01 .. 0.99) over the ``mode`` split in one pass -- the loop of ``eval`` with
+        ``ThresholdSweep.update`` in ``DeviceEval.update``'s place -- and selects, on the device, the cut-off (``per_class=False``) or the
+        cut-off per class that maximises ``objective`` ("f1", "micro_f1", "weighted_f1", "acc"; None: what ``config.eval_mode`` names).
+        Sets and returns ``self.thresholds``; the sweep's table of the ten figures per cut-off is kept in ``self.last_calibration``."""
+        from .calibrate import ThresholdSweep, check_objective, objective_for
+        if objective is None:
+            objective = objective_for(getattr(self.train_config, "eval_mode", "macro"), per_class)
+        check_objective(objective, per_class)
+        if mode not in ("dev", "test"):
+            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        sweep = ThresholdSweep(int(self.train_config.num_classes), grid, self.device)
+        for scores, emo_label in self._eval_batches(dataloader):
+            sweep.update(scores, emo_label)
+        self._check_cluster(f"calibrate({mode})")
+        self.thresholds = sweep.select(objective, per_class)
+        self.last_calibration = dict(table=sweep.table(), grid=sweep.grid, objective=objective, per_class=bool(per_class))
+        return self.thresholds
+
+    def _calibrate_after_training(self, have_checkpoint):
+        """config.calibrate != "none": the best checkpoint's cut-offs from the dev split, saved by rank 0, for the final test pass."""
+        how = getattr(self.train_config, "calibrate", "none")
+        if how == "none":
+            return None
+        if how not in ("global", "per_class"):
+            raise ValueError(f"config.calibrate must be 'none', 'global' or 'per_class', not {how!r}")
+        if self.dp is not None and getattr(self.dev_data_loader, "shard", None) is not None:
+            raise ValueError(f"calibrate={how!r} sweeps each rank's own dev loader and exchanges nothing: the dev loader must not be "
+                             f"sharded (shard={self.dev_data_loader.shard}); give every rank the whole dev split or set calibrate='none'")
+        if have_checkpoint:
+            self._load_best_checkpoint()
+        thresholds = self.calibrate("dev", per_class=how == "per_class")
+        if self.dp is None or self.dp.rank == 0:
+            os.makedirs("checkpoints", exist_ok=True)
+            thresholds.save(f"checkpoints/thresholds_{self.train_config.name}.pt")
+        return thresholds
 
     # ------------------------------------------------------------------ inference (the reference's src/inference.py is a TODO)
     def infer(self, mode, fields=None, order="loader"):
