@@ -779,6 +779,17 @@ def heads_fwd(logits, ncls, threshold=0.35, drop_p=0.0, seed=0, site=0):
     return tcp, sc, lab
 
 
+def heads_bwd(tcp, scores, dtcp, dscores, ncls, drop_p=0.0, seed=0, site=0):
+    """d_logits (B, 6 + ncls) of the two sigmoid heads; ``dtcp`` / ``dscores`` may be None (that head's columns come out zero)."""
+    lib = load()
+    B = tcp.shape[0]
+    dlogits = torch.empty(B, 6 + ncls, device=tcp.device)
+    check(lib.mmda_heads_bwd(ptr(_f(tcp)), ptr(_f(scores)), ptr(None if dtcp is None else _f(dtcp)),
+                             ptr(None if dscores is None else _f(dscores)), B, ncls, ptr(dlogits), drop_p, seed, site, stream_ptr()),
+          "heads_bwd")
+    return dlogits
+
+
 def dropout_mask_via_act(n, p, seed, site, device):
     """Exposes the counter-based dropout multipliers (for the statistical tests): h = dropout(identity(1))."""
     lib = load()

@@ -220,25 +220,25 @@ def encode_modality(x, lengths, P, m: str, d: int, cell: str, rounding: bool, ti
     return torch.cat((h1, h2), dim=2).permute(1, 0, 2).reshape(B, 4 * d)
 
 
-def forward(P, cfg, t, v, a, lengths, rounding: bool = True, tile_partials: bool = True) -> SimpleNamespace:
+def forward(P, cfg, t, v, a, lengths, rounding: bool = True, tile_partials: bool = True, masks=None) -> SimpleNamespace:
     """misa_oracle.forward with the three encoders on the bf16-emulating loops; the fusion block, heads and losses are the exact
-    fp32 ones (the product keeps them on the exact f32 path in bf16 mode as well)."""
+    fp32 ones (the product keeps them on the exact f32 path in bf16 mode as well).  ``masks``: misa_oracle.forward's."""
     cell = "lstm" if getattr(cfg, "rnncell", "lstm") == "lstm" else "gru"
     lengths = lengths.cpu()
     emb = P["embed.weight"][t]
     utt = {"t": encode_modality(emb, lengths, P, "t", cfg.embedding_size, cell, rounding, tile_partials),
            "v": encode_modality(v, lengths, P, "v", cfg.visual_size, cell, rounding, tile_partials),
            "a": encode_modality(a, lengths, P, "a", cfg.acoustic_size, cell, rounding, tile_partials)}
-    return orc.fusion_from_utterances(P, cfg, utt)
+    return orc.fusion_from_utterances(P, cfg, utt, None, masks)
 
 
-def loss_and_grads(P, cfg, batch, rounding: bool = True, tile_partials: bool = True):
+def loss_and_grads(P, cfg, batch, rounding: bool = True, tile_partials: bool = True, masks=None):
     """misa_oracle.loss_and_grads through the emulating encoders."""
     leaves = {k: p.detach().clone().requires_grad_(True) for k, p in P.items()}
     for k in leaves:                                      # the shared PReLU slope is ONE leaf under all its names
         if k.endswith("activation.weight"):
             leaves[k] = leaves[orc.PRELU_KEY]
-    o = forward(leaves, cfg, batch["t"], batch["v"], batch["a"], batch["l"], rounding, tile_partials)
+    o = forward(leaves, cfg, batch["t"], batch["v"], batch["a"], batch["l"], rounding, tile_partials, masks)
     L = orc.all_losses(o, batch["emo"], cfg)
     L.total.backward()
     grads = {k: (None if p.grad is None else p.grad.detach()) for k, p in leaves.items()}

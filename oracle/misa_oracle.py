@@ -227,16 +227,26 @@ def _linear(x, P, name):
     return x @ P[name + ".weight"].t() + P[name + ".bias"]
 
 
-def ffn_exact(x, P: Params):
-    """linear2(relu(linear1(x))) of the encoder layer (torch/nn/modules/transformer.py _ff_block, dropout off)."""
+def ffn_exact(x, P: Params, mask=None):
+    """linear2(relu(linear1(x))) of the encoder layer (torch/nn/modules/transformer.py _ff_block, dropout off).
+    ``mask``: the feed-forward dropout's multipliers on relu(linear1(x)) (S, B, FFN_DIM)."""
     te = "transformer_encoder.layers.0."
-    return _linear(torch.relu(_linear(x, P, te + "linear1")), P, te + "linear2")
+    f1 = torch.relu(_linear(x, P, te + "linear1"))
+    if mask is not None:
+        f1 = f1 * mask.to(f1.dtype)
+    return _linear(f1, P, te + "linear2")
 
 
-def fusion_layer(x, P: Params, ffn=None):
+def fusion_layer(x, P: Params, ffn=None, masks=None):
     """Post-norm transformer encoder layer on (S=6, B, E) (models.py:160-161,243-245);
     restated from torch/nn/modules/transformer.py slow path: x=LN(x+SA(x)); x=LN(x+FF(x)).
-    ``ffn``: replacement for the feed-forward block (oracle/fp8_emul.py emulates the block-scaled fp8 products with it)."""
+    ``ffn``: replacement for the feed-forward block (oracle/fp8_emul.py emulates the block-scaled fp8 products with it).
+    ``masks``: the training-mode dropout multipliers of oracle/dropout_rng.py ("attn" on the softmax output before att @ v, as
+    torch's multi_head_attention_forward; "drop1" on sa and "drop2" on ff before the residual sums, "ffn" on relu(linear1(x)), as
+    _sa_block / _ff_block); None: dropout off.  Not combined with ``ffn``."""
+    if masks is not None:
+        assert ffn is None, "the feed-forward replacements take no dropout mask"
+        mk = lambda k: masks[k].to(x.dtype)
     te = "transformer_encoder.layers.0."
     S, B, E = x.shape
     hd = E // NHEAD
@@ -248,10 +258,17 @@ def fusion_layer(x, P: Params, ffn=None):
 
     q, k, v = heads(q), heads(k), heads(v)
     att = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(hd), dim=-1)
+    if masks is not None:
+        att = att * mk("attn")
     ctx = (att @ v).permute(2, 0, 1, 3).reshape(S, B, E)
     sa = _linear(ctx, P, te + "self_attn.out_proj")
+    if masks is not None:
+        sa = sa * mk("drop1")
     x = F.layer_norm(x + sa, (E,), P[te + "norm1.weight"], P[te + "norm1.bias"], LN_EPS)
-    ff = (ffn or ffn_exact)(x, P)
+    if masks is not None:
+        ff = ffn_exact(x, P, mk("ffn")) * mk("drop2")
+    else:
+        ff = (ffn or ffn_exact)(x, P)
     return F.layer_norm(x + ff, (E,), P[te + "norm2.weight"], P[te + "norm2.bias"], LN_EPS)
 
 
@@ -267,9 +284,9 @@ class _GradReverse(torch.autograd.Function):
         return -g * ctx.p, None
 
 
-def forward(P: Params, cfg, t, v, a, lengths, ffn=None) -> SimpleNamespace:
-    """Full model forward with all dropout disabled.  Returns every tensor the reference's
-    solver reads off the module (SURVEY.md 8b side channel)."""
+def forward(P: Params, cfg, t, v, a, lengths, ffn=None, masks=None) -> SimpleNamespace:
+    """Full model forward; dropout off unless ``masks`` (oracle/dropout_rng.site_masks) hands in the six sites' multipliers.
+    Returns every tensor the reference's solver reads off the module (SURVEY.md 8b side channel)."""
     dt, dv, da, hs = cfg.embedding_size, cfg.visual_size, cfg.acoustic_size, cfg.hidden_size
     lengths = lengths.cpu()
     emb = P["embed.weight"][t]                                          # models.py:201
@@ -277,12 +294,14 @@ def forward(P: Params, cfg, t, v, a, lengths, ffn=None) -> SimpleNamespace:
     utt = {"t": encode_modality(emb, lengths, P, "t", dt, cell),
            "v": encode_modality(v, lengths, P, "v", dv, cell),
            "a": encode_modality(a, lengths, P, "a", da, cell)}
-    return fusion_from_utterances(P, cfg, utt, ffn)
+    return fusion_from_utterances(P, cfg, utt, ffn, masks)
 
 
-def fusion_from_utterances(P: Params, cfg, utt, ffn=None) -> SimpleNamespace:
+def fusion_from_utterances(P: Params, cfg, utt, ffn=None, masks=None) -> SimpleNamespace:
     """Everything of ``forward`` behind the encoders (models.py:216-249): projections, private/shared, discriminator,
-    reconstruction, the transformer fusion layer and the heads, from the three utterance vectors {"t","v","a"}."""
+    reconstruction, the transformer fusion layer and the heads, from the three utterance vectors {"t","v","a"}.
+    ``masks``: see ``fusion_layer``; besides, "disc" multiplies the discriminator's activation output before layer 2
+    (models.py:124-127) and "cls" the classifier logits before the sigmoid (models.py:150-153; the confidence head has no dropout)."""
     hs = cfg.hidden_size
     if cfg.activation == "prelu":        # learned slope, one parameter shared by the three projections and the discriminator
         slope = P[PRELU_KEY]
@@ -301,22 +320,27 @@ def fusion_from_utterances(P: Params, cfg, utt, ffn=None) -> SimpleNamespace:
         setattr(o, f"utt_{m}_orig", orig)
         setattr(o, f"utt_private_{m}", torch.sigmoid(_linear(orig, P, priv_names[m])))
         setattr(o, f"utt_shared_{m}", torch.sigmoid(_linear(orig, P, "shared.shared_1")))
-    for m in "tva":                                                     # models.py:219-231
+    for i, m in enumerate("tva"):                                       # models.py:219-231
         if cfg.use_cmd_sim:
             setattr(o, f"domain_label_{m}", None)
         else:
             r = _GradReverse.apply(getattr(o, f"utt_shared_{m}"), cfg.reverse_grad_weight)
             hdn = act(_linear(r, P, "discriminator.discriminator_layer_1"))
+            if masks is not None:
+                hdn = hdn * masks["disc"][i].to(hdn.dtype)
             setattr(o, f"domain_label_{m}", _linear(hdn, P, "discriminator.discriminator_layer_2"))
     for m in "tva":                                                     # models.py:254-262
         s = getattr(o, f"utt_private_{m}") + getattr(o, f"utt_shared_{m}")
         setattr(o, f"utt_{m}_recon", _linear(s, P, f"recon_{m}.recon_{m}_1"))
     x = torch.stack((o.utt_private_t, o.utt_private_v, o.utt_private_a,
                      o.utt_shared_t, o.utt_shared_v, o.utt_shared_a), dim=0)
-    hfused = fusion_layer(x, P, ffn)
+    hfused = fusion_layer(x, P, ffn, masks)
     o.h = hfused.permute(1, 0, 2).reshape(x.shape[1], 6 * hs)          # == cat(h[0..5], dim=1)
     o.tcp = torch.sigmoid(_linear(o.h, P, "confidence.confidence_layer_1"))
-    o.scores = torch.sigmoid(_linear(o.h, P, "classifier.classifier_layer"))
+    logits = _linear(o.h, P, "classifier.classifier_layer")
+    if masks is not None:
+        logits = logits * masks["cls"].to(logits.dtype)
+    o.scores = torch.sigmoid(logits)
     o.labels = (o.scores > cfg.threshold).to(o.scores.dtype)           # getBinaryTensor
     return o
 
@@ -438,15 +462,16 @@ class AdamState:
                 p.addcdiv_(self.m[k], denom, value=-self.lr / bc1)
 
 
-def loss_and_grads(P: Params, cfg, batch, ffn=None):
+def loss_and_grads(P: Params, cfg, batch, ffn=None, masks=None):
     """One forward+backward (solver.py:139-183).  Returns (outputs, losses, grads) where grads
     has None for parameters outside the graph (sp_discriminator.*; confidence.* unless
-    use_confidNet) exactly as autograd leaves them in the reference."""
+    use_confidNet) exactly as autograd leaves them in the reference.  ``masks``: the dropout multipliers of a training-mode
+    step (oracle/dropout_rng.site_masks); None: dropout off."""
     leaves = {k: p.detach().clone().requires_grad_(True) for k, p in P.items()}
     for k in leaves:                                      # the shared PReLU slope is ONE leaf under all its names
         if k.endswith("activation.weight"):
             leaves[k] = leaves[PRELU_KEY]
-    o = forward(leaves, cfg, batch["t"], batch["v"], batch["a"], batch["l"], ffn)
+    o = forward(leaves, cfg, batch["t"], batch["v"], batch["a"], batch["l"], ffn, masks)
     L = all_losses(o, batch["emo"], cfg)
     L.total.backward()
     grads = {k: (None if p.grad is None else p.grad.detach()) for k, p in leaves.items()}
