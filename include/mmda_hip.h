@@ -632,11 +632,15 @@ int mmda_misa_set_workspace(mmda_misa* m, float* ws, int64_t floats, int B, int 
  * to the batch maximum, data_loader.py:70-72) costs no device work; abort words found before a clear stay visible through
  * mmda_misa_cluster_status.  Before handing over a NEW buffer read mmda_misa_cluster_status yourself: the old one is not touched. */
 int mmda_misa_set_workspace_async(mmda_misa* m, float* ws, int64_t floats, int B, int T, void* stream);
-/* offset (in floats, inside the workspace) of a named activation / activation-gradient, -1 if unknown. Names:
- *   scores labels tcp logits hfused x6 orig recon dom utt_t utt_v utt_a losses
- *   d_scores d_tcp d_x6 d_orig d_recon d_dom   xchg_t xchg_v xchg_a (exchange buffers; word 0 of each = its sticky abort word)
+/* offset (in floats, inside the workspace) of a named activation / activation-gradient; -1 if unknown, and for every name while no
+ * workspace is bound. Names (all of them: the table kTensorNames in misa.hip):
+ *   scores labels tcp logits hfused x6 orig recon dom losses grad_norm utt_t utt_v utt_a
+ *   d_scores d_tcp d_x6 d_orig d_recon d_dom
+ *   pub_begin pub_end (the solver-visible outputs orig .. labels, contiguous)   zero_begin zero_end (the region cleared per step)
+ *   hseq1_t hseq1_v hseq1_a (layer-1 hseq, (T,B,2H))   d_x_t (gradient w.r.t. the gathered embedding rows, (T*B, d_t))
+ *   xchg_t xchg_v xchg_a (exchange buffers; word 0 of each = its sticky abort word; -1 where a modality has none)
  * x6 = [private_t, private_v, private_a, shared_t, shared_v, shared_a] each (B,hidden); orig/recon = (3,B,hidden);
- * losses = float[8]: cls, diff, sim, recon, conf, total */
+ * losses = float[8]: cls, diff, sim, recon, conf, total; grad_norm = float[2]: norm, clip coefficient (mmda_misa_set_adam) */
 int64_t mmda_misa_tensor_offset(const mmda_misa* m, const char* name);
 /* set the mode / loss switches after creation (bench toggles) */
 int mmda_misa_set_mode(mmda_misa* m, int mode);

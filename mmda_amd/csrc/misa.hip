@@ -6,6 +6,7 @@
 #include "fused_rows.h"
 #include "internal.h"
 
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -14,28 +15,66 @@ namespace {
 
 struct ParamInfo { std::string name; int64_t off; int rows, cols; };
 
-struct Rnn {           // one bidirectional LSTM layer
+// ---- ParamTable: what is fixed at create.  Offsets are floats into the flat parameter bucket (and its gradient / Adam twins).
+struct RnnP {          // one bidirectional LSTM layer
   int D, H;
   int64_t w_ih, w_hh[2], b_ih, b_hh;     // w_ih: (8H,D) = [fwd;rev]; b_*: (8H) = [fwd;rev]
-  int64_t pack_f[2], pack_b[2], pack_c[2];   // workspace float offsets of the packed W_hh (per direction)
-  // bf16 operand copies for the bf16-mode GEMMs (workspace float offsets; leading dimensions in bf16 elements):
+  int ldD, ldG, ldH;                     // leading dimensions of the bf16 operand copies, in bf16 elements: round_up(D | 8H | H, 8)
+};
+struct ModP {          // one modality: two stacked biLSTMs with a LayerNorm between, then a projection
+  int D, H;
+  RnnP rnn[2];
+  int64_t ln_w, ln_b;                    // {t,v,a}layer_norm
+  int64_t pw, pb, plw, plb;              // project_*: Linear + LayerNorm
+};
+struct ParamTable {    // built once by build_params(cfg); the handle holds it const
+  std::vector<ParamInfo> params;
+  std::map<std::string, int> index;
+  int64_t dense = 0, flat = 0;
+  int64_t rnn2_begin = 0, rnn1_begin = 0;    // bucket offsets where the layer-2 / layer-1 recurrent parameters start
+  ModP mod[3];
+  // fusion parameter offsets
+  int64_t priv_w, priv_b, sh_w, sh_b, rec_w, rec_b, d1_w = -1, d1_b = -1, d2_w = -1, d2_b = -1, sp_w, sp_b;
+  int64_t head_w, head_b, embed;
+  int64_t in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b;
+  int64_t prelu_a = -1;                      // config.activation = prelu: the ONE learned slope (nn.PReLU() shared by every use, models.py:30)
+};
+
+// ---- Workspace: what carve(cfg, params, B, T) returns.  Offsets are floats into the bound workspace buffer.
+struct RnnW {
+  int64_t pack_f[2], pack_b[2], pack_c[2];   // the packed W_hh (per direction)
+  // bf16 operand copies for the bf16-mode GEMMs (leading dimensions: RnnP, and Workspace::ldR):
   int64_t wb, wbT;                           // W_ih (8H, ldD) and W_ih^T (D, ldG)
   int64_t xb, xbT;                           // layer input (R, ldD) and its transpose (D, ldR)
   int64_t dgb, dgbT;                         // gate gradients (R, ldG) and transpose (8H, ldR)
   int64_t hbT;                               // hseq^T (2H, ldR)
-  int64_t hbp[2]; int ldH;                   // tn weight-gradient GEMMs: hseq of one direction as bf16 (R, ldH), ldH = round_up(H, 8)
-  int ldD, ldG;
-  // GRU (cfg.rnncell): workspace offsets of the parameters / gradients in the four-slot layout (mmda_gru_pad_job); -1 for LSTM
+  int64_t hbp[2];                            // tn weight-gradient GEMMs: hseq of one direction as bf16 (R, ldH)
+  // GRU (cfg.rnncell): the parameters / gradients in the four-slot layout (mmda_gru_pad_job); -1 for LSTM
   int64_t pw_ih = -1, pw_hh[2] = {-1, -1}, pb_ih = -1, pb_hh = -1, gw_ih = -1, gw_hh[2] = {-1, -1}, gb = -1;
 };
-
-struct Mod {           // one modality: two stacked biLSTMs with a LayerNorm between, then a projection
-  int D, H;
-  Rnn rnn[2];
-  int64_t ln_w, ln_b;                    // {t,v,a}layer_norm
-  int64_t pw, pb, plw, plb;              // project_*: Linear + LayerNorm
-  // workspace
+struct ModW {
+  RnnW rnn[2];
   int64_t x, gates[2], c[2], hseq[2], normed, ln_mean, ln_rstd, utt, d_utt, d_hseq1, d_normed, d_x, xchg, xchg_floats;
+};
+struct Workspace {
+  int B = 0, T = 0, ldR = 0;                 // ldR = round_up(B * T, 8): rows of the transposed bf16 copies
+  int64_t floats = 0;                        // the whole carve
+  ModW mod[3];
+  int64_t pub_begin = 0, pub_end = 0;        // the public outputs, contiguous
+  int64_t zero_begin = 0, zero_end = 0;      // activation-gradient region that is zeroed per step
+  int64_t zero_cls = 0, zero_recon = 0;      // ... its tail: d_scores from zero_cls, d_orig + d_recon from zero_recon (see loss seeds)
+  int64_t gpad_begin = 0, gpad_end = 0;      // GRU: four-slot weight gradients (zeroed at set_workspace, re-zeroed by the unpad kernel)
+  int64_t z, pmean, prstd, orig, x6, rsum, recon, dom_z, dom_h, dom, qkv, probs, ctx, attn_out, ln1_mean, ln1_rstd, x1, f1, f2,
+      ln2_mean, ln2_rstd, hfused, logits, tcp, scores, labels, losses, diff_work, ffn_parts, pg_parts, ln_parts;
+  // block-scaled fp8 operands of the feed-forward products (fusion_fp8): element bytes and scale bytes, as float offsets
+  int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
+  // K-major (transposed) fp32 copies of the fusion block's weights for its input-gradient GEMMs (made once per step)
+  int64_t head_wT, l2_wT, l1_wT, out_wT, in_wT, rec_wT, priv_wT, sh_wT, d1_wT = -1, d2_wT = -1, pwT[3];
+  int64_t d_scores, d_tcp, d_x6, d_orig, d_recon, d_dom, d_logits, d_hfused, d_x1, d_f2, d_f1, d_attn_out, d_ctx, d_qkv, d_z,
+      d_dom_h, d_dom_z;
+  int64_t gnorm = -1, gnorm_parts = -1;      // clip_norm: norm and coefficient of the last such step; the norm launch's block partials (doubles)
+  int64_t esort = -1;                        // sorted (id, position) list of the step's text ids (see mmda_misa::esort_valid)
+  int64_t rec_part = -1;
 };
 
 // Every choice of a form of the training step, made once per step by plan_step() at the start of mmda_misa_forward() and read by every
@@ -82,97 +121,277 @@ struct PendingRows {
 };
 struct RowList { int64_t* ids; float* rows; int64_t used, capacity; };   // an accumulated step's (ids, rows) list: sparse table
 
+int64_t add_param(ParamTable& t, const std::string& name, int rows, int cols) {
+  ParamInfo p{name, t.flat, rows, cols};
+  t.index[name] = (int)t.params.size();
+  t.params.push_back(p);
+  t.flat += (int64_t)rows * (cols > 0 ? cols : 1);
+  return p.off;
+}
+
+ParamTable build_params(const mmda_misa_config& c) {
+  ParamTable t{};
+  const int dims[3] = {c.d_t, c.d_v, c.d_a};
+  const char* mn[3] = {"t", "v", "a"};
+  const int hs = c.hidden;
+  // Order of the dense bucket = the order in which the backward pass completes the gradients (data-parallel ranks start
+  // reducing a prefix while the rest is still being computed, mmda_misa_early_grad_floats): fusion block and LayerNorms first,
+  // then the layer-2 recurrent layers, then layer 1; the embedding matrix closes the bucket.
+  for (int i = 0; i < 3; ++i) { ModP& md = t.mod[i]; md.D = md.H = dims[i]; }
+  for (int i = 0; i < 3; ++i) {
+    ModP& md = t.mod[i];
+    std::string p = std::string("project_") + mn[i] + ".project_" + mn[i];
+    md.pw = add_param(t, p + ".weight", hs, 4 * md.H);
+    md.pb = add_param(t, p + ".bias", hs, 0);
+    md.plw = add_param(t, p + "_layer_norm.weight", hs, 0);
+    md.plb = add_param(t, p + "_layer_norm.bias", hs, 0);
+  }
+  // batched groups: three (hs,hs) weights back to back, then their three biases (uniform strides for batched GEMMs)
+  t.priv_w = add_param(t, "private_t.private_t_1.weight", hs, hs);
+  add_param(t, "private_v.private_v_1.weight", hs, hs);
+  add_param(t, "private_a.private_a_3.weight", hs, hs);          // sic: reference models.py:95
+  t.priv_b = add_param(t, "private_t.private_t_1.bias", hs, 0);
+  add_param(t, "private_v.private_v_1.bias", hs, 0);
+  add_param(t, "private_a.private_a_3.bias", hs, 0);
+  t.sh_w = add_param(t, "shared.shared_1.weight", hs, hs);
+  t.sh_b = add_param(t, "shared.shared_1.bias", hs, 0);
+  t.rec_w = add_param(t, "recon_t.recon_t_1.weight", hs, hs);
+  add_param(t, "recon_v.recon_v_1.weight", hs, hs);
+  add_param(t, "recon_a.recon_a_1.weight", hs, hs);
+  t.rec_b = add_param(t, "recon_t.recon_t_1.bias", hs, 0);
+  add_param(t, "recon_v.recon_v_1.bias", hs, 0);
+  add_param(t, "recon_a.recon_a_1.bias", hs, 0);
+  if (!c.use_cmd_sim) {
+    t.d1_w = add_param(t, "discriminator.discriminator_layer_1.weight", hs, hs);
+    t.d1_b = add_param(t, "discriminator.discriminator_layer_1.bias", hs, 0);
+    t.d2_w = add_param(t, "discriminator.discriminator_layer_2.weight", 3, hs);
+    t.d2_b = add_param(t, "discriminator.discriminator_layer_2.bias", 3, 0);
+  }
+  t.sp_w = add_param(t, "sp_discriminator.sp_discriminator_layer_1.weight", 4, hs);
+  t.sp_b = add_param(t, "sp_discriminator.sp_discriminator_layer_1.bias", 4, 0);
+  // [confidence; classifier] adjacent -> one (6+ncls, 6hs) head GEMM
+  t.head_w = add_param(t, "confidence.confidence_layer_1.weight", 6, 6 * hs);
+  add_param(t, "classifier.classifier_layer.weight", c.ncls, 6 * hs);
+  t.head_b = add_param(t, "confidence.confidence_layer_1.bias", 6, 0);
+  add_param(t, "classifier.classifier_layer.bias", c.ncls, 0);
+  for (int i = 0; i < 3; ++i) {
+    t.mod[i].ln_w = add_param(t, std::string(mn[i]) + "layer_norm.weight", 2 * t.mod[i].H, 0);
+    t.mod[i].ln_b = add_param(t, std::string(mn[i]) + "layer_norm.bias", 2 * t.mod[i].H, 0);
+  }
+  const std::string te = "transformer_encoder.layers.0.";
+  t.in_w = add_param(t, te + "self_attn.in_proj_weight", 3 * hs, hs);
+  t.in_b = add_param(t, te + "self_attn.in_proj_bias", 3 * hs, 0);
+  t.out_w = add_param(t, te + "self_attn.out_proj.weight", hs, hs);
+  t.out_b = add_param(t, te + "self_attn.out_proj.bias", hs, 0);
+  t.l1_w = add_param(t, te + "linear1.weight", FFN, hs);
+  t.l1_b = add_param(t, te + "linear1.bias", FFN, 0);
+  t.l2_w = add_param(t, te + "linear2.weight", hs, FFN);
+  t.l2_b = add_param(t, te + "linear2.bias", hs, 0);
+  t.n1_w = add_param(t, te + "norm1.weight", hs, 0);
+  t.n1_b = add_param(t, te + "norm1.bias", hs, 0);
+  t.n2_w = add_param(t, te + "norm2.weight", hs, 0);
+  t.n2_b = add_param(t, te + "norm2.bias", hs, 0);
+  if (c.act == MMDA_ACT_PRELU) t.prelu_a = add_param(t, "activation.weight", 1, 0);      // last of the block: what follows is re-aligned
+  for (int l = 1; l >= 0; --l) {
+    t.flat = (t.flat + 3) & ~(int64_t)3;
+    (l == 1 ? t.rnn2_begin : t.rnn1_begin) = t.flat;
+    for (int i = 0; i < 3; ++i) {
+      ModP& md = t.mod[i];
+      RnnP& r = md.rnn[l];
+      r.H = md.H; r.D = l == 0 ? md.D : 2 * md.H;
+      r.ldD = round_up(r.D, 8); r.ldG = round_up(8 * r.H, 8); r.ldH = round_up(r.H, 8);
+      const int ng = c.rnncell == MMDA_CELL_GRU ? 3 : 4;      // gate blocks per direction in the torch-layout parameters
+      std::string pre = std::string(mn[i]) + "rnn" + (l == 0 ? "1" : "2") + ".";
+      r.w_ih = add_param(t, pre + "weight_ih_l0", ng * r.H, r.D);
+      add_param(t, pre + "weight_ih_l0_reverse", ng * r.H, r.D);
+      r.w_hh[0] = add_param(t, pre + "weight_hh_l0", ng * r.H, r.H);
+      r.w_hh[1] = add_param(t, pre + "weight_hh_l0_reverse", ng * r.H, r.H);
+      r.b_ih = add_param(t, pre + "bias_ih_l0", ng * r.H, 0);
+      add_param(t, pre + "bias_ih_l0_reverse", ng * r.H, 0);
+      r.b_hh = add_param(t, pre + "bias_hh_l0", ng * r.H, 0);
+      add_param(t, pre + "bias_hh_l0_reverse", ng * r.H, 0);
+    }
+  }
+  t.flat = (t.flat + 3) & ~(int64_t)3;
+  t.dense = t.flat;
+  t.embed = add_param(t, "embed.weight", c.vocab, c.d_t);
+  t.flat = (t.flat + 3) & ~(int64_t)3;
+  return t;
+}
+
+// The workspace for (B, T) batches, as a value: sizes one (Workspace::floats) and is what a bound buffer is read through.  Pure: no HIP
+// call, no handle.
+Workspace carve(const mmda_misa_config& c, const ParamTable& par, int B, int T) {
+  const int hs = c.hidden, NC = 6 + c.ncls;
+  const int64_t R = (int64_t)T * B;
+  int64_t cur = 0;
+  auto take = [&cur](int64_t n) { int64_t o = cur; cur += (n + 3) & ~(int64_t)3; return o; };   // 16-B aligned
+  Workspace w{};
+  w.B = B; w.T = T; w.ldR = round_up(B * T, 8);
+  for (int i = 0; i < 3; ++i) {       // exchange buffers of the recurrences first: their offsets depend on B only
+    const ModP& md = par.mod[i]; ModW& mw = w.mod[i];
+    mw.xchg_floats = (mmda_lstm_xchg_bytes(md.H, B) + 3) / 4;
+    mw.xchg = mw.xchg_floats > 0 ? take(mw.xchg_floats) : -1;
+  }
+  for (int i = 0; i < 3; ++i) {
+    const ModP& md = par.mod[i]; ModW& mw = w.mod[i];
+    for (int l = 0; l < 2; ++l) {
+      const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
+      for (int d = 0; d < 2; ++d) {     // sized for the larger (fp32) packing so the mode can be switched in place
+        rw.pack_f[d] = take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 0) / 4);
+        rw.pack_b[d] = take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 1) / 4);
+        rw.pack_c[d] = take(mmda_lstm_packed_bytes(MMDA_BF16, r.H, 2) / 4);
+      }
+    }
+    for (int l = 0; l < 2; ++l) {
+      const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
+      rw.wb = take((int64_t)8 * r.H * r.ldD / 2); rw.wbT = take((int64_t)r.D * r.ldG / 2);
+      rw.xb = take(R * r.ldD / 2); rw.xbT = take((int64_t)r.D * w.ldR / 2);
+      rw.dgb = take(R * r.ldG / 2); rw.dgbT = take((int64_t)8 * r.H * w.ldR / 2);
+      rw.hbT = take((int64_t)2 * r.H * w.ldR / 2);
+      for (int d = 0; d < 2; ++d) rw.hbp[d] = take(R * r.ldH / 2);
+    }
+    if (c.rnncell == MMDA_CELL_GRU) {
+      for (int l = 0; l < 2; ++l) {
+        const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
+        rw.pw_ih = take((int64_t)8 * r.H * r.D); rw.pw_hh[0] = take((int64_t)4 * r.H * r.H); rw.pw_hh[1] = take((int64_t)4 * r.H * r.H);
+        rw.pb_ih = take(8 * r.H); rw.pb_hh = take(8 * r.H);
+      }
+    }
+    mw.x = (i == 0) ? take(R * md.D) : -1;
+    for (int l = 0; l < 2; ++l) {
+      mw.gates[l] = take(R * 8 * md.H);
+      mw.c[l] = take((int64_t)T * round_up(B, 4) * 2 * md.H);     // batch-minor-by-4 under the gate-minor layout: rows rounded up
+      mw.hseq[l] = take(R * 2 * md.H);
+    }
+    mw.normed = take(R * 2 * md.H);
+    mw.ln_mean = take(R);
+    mw.ln_rstd = take(R);
+    mw.utt = take((int64_t)B * 4 * md.H);
+    mw.d_utt = take((int64_t)B * 4 * md.H);
+    mw.d_hseq1 = take(R * 2 * md.H);
+    mw.d_normed = take(R * 2 * md.H);
+    mw.d_x = (i == 0) ? take(R * md.D) : -1;
+  }
+  const int64_t BH = (int64_t)B * hs;
+  w.z = take(3 * BH); w.pmean = take(3 * B); w.prstd = take(3 * B);
+  // public outputs (what the reference's solver reads off the module) are contiguous so the host can snapshot them at once
+  w.pub_begin = cur;
+  w.orig = take(3 * BH); w.x6 = take(6 * BH); w.recon = take(3 * BH); w.dom = take((int64_t)3 * B * 3);
+  w.tcp = take((int64_t)B * 6); w.scores = take((int64_t)B * c.ncls); w.labels = take((int64_t)B * c.ncls);
+  w.pub_end = cur;
+  w.rsum = take(3 * BH); w.dom_z = take(3 * BH); w.dom_h = take(3 * BH);
+  w.qkv = take(6 * BH * 3); w.probs = take((int64_t)B * NHEAD * S6 * S6); w.ctx = take(6 * BH);
+  w.attn_out = take(6 * BH); w.ln1_mean = take(6 * B); w.ln1_rstd = take(6 * B); w.x1 = take(6 * BH);
+  w.f1 = take((int64_t)6 * B * FFN); w.f2 = take(6 * BH); w.ln2_mean = take(6 * B); w.ln2_rstd = take(6 * B);
+  w.hfused = take(6 * BH); w.logits = take((int64_t)B * NC);
+  w.x1q = take(6 * BH / 4); w.x1s = take(6 * BH / 128 + 4); w.w1q = take((int64_t)FFN * hs / 4); w.w1s = take((int64_t)FFN * hs / 128 + 4);
+  w.f1q = take((int64_t)6 * B * FFN / 4); w.f1s = take((int64_t)6 * B * FFN / 128 + 4);
+  w.w2q = take((int64_t)hs * FFN / 4); w.w2s = take((int64_t)hs * FFN / 128 + 4);
+  w.diff_work = take(mmda_loss_diff_work_floats(B, hs));
+  w.ffn_parts = take((int64_t)(FFN / 32) * 6 * BH);      // partial products of the hidden-sliced feed-forward kernels (fused_rows.hip)
+  w.ln_parts = take((int64_t)512 * 2 * 2 * (par.mod[0].H + par.mod[1].H + par.mod[2].H));   // <= 512 block partials of the three inter-layer LayerNorms' gamma / beta gradients (norm.hip)
+  w.rec_part = take(3 * BH);                             // d_recon W_rec, made beside the backward pass's first stretch for its third (fused_rows.h)
+  w.esort = take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (dist.hip)
+  w.pg_parts = take((int64_t)B * FUSED_PG_SLOTS * 2 * 128);      // per-sample LayerNorm gamma / beta gradient partials of the fused backward stretches
+  w.head_wT = take((int64_t)6 * hs * NC); w.l2_wT = take((int64_t)FFN * hs); w.l1_wT = take((int64_t)hs * FFN);
+  w.out_wT = take((int64_t)hs * hs); w.in_wT = take((int64_t)hs * 3 * hs); w.rec_wT = take((int64_t)3 * hs * hs);
+  w.priv_wT = take((int64_t)3 * hs * hs); w.sh_wT = take((int64_t)hs * hs);
+  if (!c.use_cmd_sim) { w.d1_wT = take((int64_t)hs * hs); w.d2_wT = take((int64_t)hs * 3); }
+  for (int i = 0; i < 3; ++i) w.pwT[i] = take((int64_t)4 * par.mod[i].H * hs);
+  w.gpad_begin = cur;
+  if (c.rnncell == MMDA_CELL_GRU) {
+    for (int i = 0; i < 3; ++i)
+      for (int l = 0; l < 2; ++l) {
+        const RnnP& r = par.mod[i].rnn[l]; RnnW& rw = w.mod[i].rnn[l];
+        rw.gw_ih = take((int64_t)8 * r.H * r.D); rw.gw_hh[0] = take((int64_t)4 * r.H * r.H); rw.gw_hh[1] = take((int64_t)4 * r.H * r.H);
+        rw.gb = take(8 * r.H);
+      }
+  }
+  w.gpad_end = cur;
+  // ---- the loss sums and the activation gradients seeded by the losses (zeroed every step by ONE memset, contiguous)
+  w.zero_begin = cur;
+  w.losses = take(8);
+  w.d_tcp = take((int64_t)B * 6); w.d_x6 = take(6 * BH); w.d_dom = take((int64_t)3 * B * 3);
+  w.zero_cls = cur;                       // (a step whose forward stores these seeds itself clears up to here only)
+  w.d_scores = take((int64_t)B * c.ncls);
+  w.zero_recon = cur;
+  w.d_orig = take(3 * BH); w.d_recon = take(3 * BH);
+  w.zero_end = cur;
+  // ---- fully overwritten gradients
+  w.d_logits = take((int64_t)B * NC); w.d_hfused = take(6 * BH); w.d_x1 = take(6 * BH); w.d_f2 = take(6 * BH);
+  w.d_f1 = take((int64_t)6 * B * FFN); w.d_attn_out = take(6 * BH); w.d_ctx = take(6 * BH);
+  w.d_qkv = take(6 * BH * 3); w.d_z = take(3 * BH); w.d_dom_h = take(3 * BH); w.d_dom_z = take(3 * BH);
+  // ---- clip_norm: the gradient norm and its clip coefficient, and the norm launch's block partials (doubles, two floats each)
+  w.gnorm = take(4); w.gnorm_parts = take(2 * mmda_grad_norm_partials(INT64_MAX));
+  w.floats = cur;
+  return w;
+}
+
+// The names mmda_misa_tensor_offset answers to (include/mmda_hip.h lists them)
+struct TensorName { const char* name; int64_t (*off)(const Workspace&); };
+#define TENSOR(name, expr) {name, [](const Workspace& w) -> int64_t { return w.expr; }}
+const TensorName kTensorNames[] = {
+    TENSOR("scores", scores), TENSOR("labels", labels), TENSOR("tcp", tcp), TENSOR("logits", logits), TENSOR("hfused", hfused),
+    TENSOR("x6", x6), TENSOR("orig", orig), TENSOR("recon", recon), TENSOR("dom", dom), TENSOR("losses", losses),
+    TENSOR("grad_norm", gnorm), TENSOR("utt_t", mod[0].utt), TENSOR("utt_v", mod[1].utt), TENSOR("utt_a", mod[2].utt),
+    TENSOR("d_scores", d_scores), TENSOR("d_tcp", d_tcp), TENSOR("d_x6", d_x6), TENSOR("d_orig", d_orig), TENSOR("d_recon", d_recon),
+    TENSOR("d_dom", d_dom), TENSOR("pub_begin", pub_begin), TENSOR("pub_end", pub_end), TENSOR("zero_begin", zero_begin),
+    TENSOR("zero_end", zero_end), TENSOR("hseq1_t", mod[0].hseq[0]), TENSOR("hseq1_v", mod[1].hseq[0]), TENSOR("hseq1_a", mod[2].hseq[0]),
+    TENSOR("d_x_t", mod[0].d_x),      // gradient w.r.t. the gathered embedding rows (T*B, d_t): the sparse form of embed.weight.grad
+    TENSOR("xchg_t", mod[0].xchg), TENSOR("xchg_v", mod[1].xchg), TENSOR("xchg_a", mod[2].xchg)};   // word 0 of each = its abort word
+#undef TENSOR
+
 }  // namespace
 
 struct mmda_misa {
-  mmda_misa_config cfg;
-  std::vector<ParamInfo> params;
-  std::map<std::string, int> index;
-  int64_t dense = 0, flat = 0;
-  int64_t rnn2_begin = 0, rnn1_begin = 0;    // bucket offsets where the layer-2 / layer-1 recurrent parameters start
-  hipEvent_t ev_early = nullptr;             // recorded by backward() when the gradients of the bucket prefix are final
-  int64_t early_floats = 0; int early_valid = 0;
-  Mod mod[3];
-  StepPlan plan;                             // the decisions of the step in flight (plan_step); its state is below
-  // fusion parameter offsets
-  int64_t priv_w, priv_b, sh_w, sh_b, rec_w, rec_b, d1_w = -1, d1_b = -1, d2_w = -1, d2_b = -1, sp_w, sp_b;
-  int64_t head_w, head_b, embed;
-  int64_t in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b;
-  int64_t prelu_a = -1;                      // config.activation = prelu: the ONE learned slope (nn.PReLU() shared by every use, models.py:30)
+  explicit mmda_misa(const mmda_misa_config& c) : cfg(c), par(build_params(c)) {}
+  mmda_misa(const mmda_misa&) = delete;      // (`lay` refers to this handle's own value)
+  mmda_misa_config cfg;                      // fixed at create, but for cfg.mode (mmda_misa_set_mode)
+  const ParamTable par;                      // fixed at create
+  const Workspace& lay = lay_;               // the carve of the bound (B, T): read-only but for ...
+  void rebind(const Workspace& v) { lay_ = v; }   // ... mmda_misa_set_workspace_async, which replaces it as a whole
+  // ---- bound buffers (mmda_misa_bind, mmda_misa_set_workspace_async)
   float *P = nullptr, *G = nullptr, *M1 = nullptr, *V1 = nullptr;
-  // workspace
-  float* ws = nullptr; int64_t ws_floats = 0; int B = 0, T = 0;
-  std::map<std::string, int64_t> tens;
-  int64_t zero_begin = 0, zero_end = 0;      // activation-gradient region that is zeroed per step
-  int64_t zero_cls = 0, zero_recon = 0;      // ... its tail: d_scores from zero_cls, d_orig + d_recon from zero_recon (see loss seeds)
-  int64_t gpad_begin = 0, gpad_end = 0;      // GRU: four-slot weight gradients (zeroed at set_workspace, re-zeroed by the unpad kernel)
-  int64_t z, pmean, prstd, orig, x6, rsum, recon, dom_z, dom_h, dom, qkv, probs, ctx, attn_out, ln1_mean, ln1_rstd, x1, f1, f2,
-      ln2_mean, ln2_rstd, hfused, logits, tcp, scores, labels, losses, diff_work, ffn_parts, pg_parts, ln_parts;
-  // K-major (transposed) fp32 copies of the fusion block's weights for its input-gradient GEMMs (made once per step)
-  int64_t head_wT, l2_wT, l1_wT, out_wT, in_wT, rec_wT, priv_wT, sh_wT, d1_wT = -1, d2_wT = -1, pwT[3];
-  int wT_valid = 0;
-  int64_t d_scores, d_tcp, d_x6, d_orig, d_recon, d_dom, d_logits, d_hfused, d_x1, d_f2, d_f1, d_attn_out, d_ctx, d_qkv, d_z,
-      d_dom_h, d_dom_z;
-  // block-scaled fp8 operands of the feed-forward products (fusion_fp8): element bytes and scale bytes, as float offsets
-  // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
-  // recurrence runs there, on the side stream (Pass::early); how far that pass of the last backward got
-  int64_t adam_early_done = 0;
+  float* ws = nullptr;
+  // cluster-exchange regions: at the front of the workspace, sized by B alone, so a change of T (every batch under the reference's
+  // collate) neither moves nor clears them -- flags are monotonic epochs.  Cleared (on the caller's stream) only when the buffer
+  // or B changes; the abort words found there before a clear are kept in `abort_sticky`.
+  float* xchg_ws = nullptr; int xchg_B = 0; int abort_sticky = 0;
+  // ---- settings, written only by mmda_misa_set_* (and mmda_misa_timing_stride / _rotate)
   // The optimizer's settings (mmda_misa_set_adam): every Adam launch of the handle reads them; scale_dev is not kept (a step with
   // clip_norm > 0 points its launches at gnorm[1]).  clip_norm > 0: clip_grad_norm_ in front of the update -- no update may precede the
-  // norm, so such a step takes no early optimizer pass.  gnorm: norm and coefficient of the last such step; gnorm_parts: the norm
-  // launch's block partials (doubles).
+  // norm, so such a step takes no early optimizer pass.
   mmda_adam_opts adam = {0.9f, 0.999f, 1e-8f, 0.f, 0, nullptr};
   float clip_norm = 0.f;
-  int64_t gnorm = -1, gnorm_parts = -1;
-  int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
   int fusion_fp8 = 0;
   int embed_update = EU_DENSE;
   // Frozen parameters (mmda_misa_set_trainable).  `runs`: the trainable ranges of the bucket, never merged across rnn2_begin, rnn1_begin
   // or embed -- so the runs of any range a launch of the step covers are a slice of the table -- and closed by an entry that carries the
-  // table's item count.  A tensor's range runs up to the next tensor, alignment padding included.  runs_dev: the table on the device
-  // (the one allocation besides jflags), copied when the set has changed since the last launch that read it.
+  // table's item count.  A tensor's range runs up to the next tensor, alignment padding included.
   std::vector<mmda_run> runs;
   int prefix_frozen = 0;           // a tensor in front of the table is frozen
   int embed_flag = 1;              // the table's own flag (what embed_update makes of the table is a separate matter)
   int enc_frozen = 0;              // both recurrent layers and the three inter-layer LayerNorms are frozen
   int cut_keep_stash = 0;          // a cut step runs the stashing forward all the same (mmda_misa_set_cut_forward)
-  int enc_cached = 0;              // the forward being planned starts behind the encoders (set by the *_encoded entry points, cleared by mmda_misa_forward)
-  mmda_run* runs_dev = nullptr; int runs_dev_cap = 0; int runs_dirty = 1;
-  // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
-  // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
-  // for backward itself)
-  PendingRows eu;
   // dense mode with deferral (mmda_misa_set_embed_deferred): the caller's per-row step counts and ring of step scalars (common.h:
   // DenseRowArgs).  Dense Adam's result; the bucket ends at the table as in the sparse mode, which also lends its pending rows.
-  // df_seq: updates applied since the binding (what a current row's row_step equals); df_flushed: df_seq at the last full flush.
-  int32_t* df_row_step = nullptr; float* df_ring = nullptr; int df_window = 0; int df_seq = 0, df_flushed = 0;
-  int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
-  // state of the last forward (dropout replay in backward)
-  int training = 0; uint64_t seed = 0;
-  // optional per-launch timing of the four recurrent kernels (bench.py roofline leg)
-  unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_cluster.hip)
-  hipStream_t side = nullptr;      // second stream for weight-gradient GEMMs (created lazily; no device memory)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pack = nullptr;
-  int side_pending = 0, use_side = 1;
+  int32_t* df_row_step = nullptr; float* df_ring = nullptr; int df_window = 0;
+  int use_side = 1;
   int use_cluster = 1;
   int use_bf16_gemm = 1;           // bf16 mode: LSTM-sized GEMMs read bf16 operand copies (gemm_bf16.hip)
-  int inference = 0;               // evaluation passes: no stash, no copies that only the backward pass reads
-  int zero_grad_pending = 0;       // train_step: the gradient bucket is cleared inside forward(), beside the fusion block
-  // train_step: the losses that read only the private/shared representations (diff, CMD) are issued by forward() on the side
-  // stream as soon as those exist, beside the transformer layer and the heads; mmda_misa_losses() then adds the rest
-  int eager_losses = 0, eager_done = 0;      // eager_done: that chain, and any loss seeds, not yet taken up by mmda_misa_losses
+  int inference = 0;               // evaluation passes: no stash, no copies that only the backward pass reads (a training step clears it)
   // Data-parallel "global statistics" mode (mmda_misa_set_external_batch_losses): the batch-statistic losses -- DiffLoss, CMD and the
   // confidence loss -- were computed by the caller on the batch of ALL ranks (all-gathered inputs, the same loss entry points), their
   // sums written into losses[1], [2], [4] and their gradient rows of THIS rank added into d_x6 / d_scores / d_tcp behind
   // mmda_misa_zero_act_grads: mmda_misa_losses then only adds what is a mean over samples (cls, recon) and the weighted total.
   int ext_batch_losses = 0;
-  // Loss seeds (training step, fused row-local stretches): the forward stretches store the gradient seeds of the reconstruction loss
-  // (d_recon, d_orig) and -- without ConfidNet, whose loss adds into the same buffer -- of the classification loss (d_scores) where
-  // they produce recon / scores, so the launch that computes cls / conf / recon and the weighted total has no gradient to seed and
-  // leaves the critical path between the forward and the backward pass (14 us at B=32): it runs on the side stream beside the
-  // layer-2 backward recurrence.  Values are bit-identical to the loss launch's (same expressions on the same operands).
-  const float* emo_eager = nullptr;          // labels of the step in flight (train_step)
-  const float* misc_deferred = nullptr;      // labels: the loss-value launch is still to be issued (backward's first side fork)
+  int ev_stride = 1;               // record every ev_stride-th step (the event pairs cost ~35 us per step)
+  int ev_rotate = 0;               // 1: a sampled step brackets ONE of the four recurrent launches (sample index % 4): ~9 us
+  // ---- device resources (created lazily, released by mmda_misa_destroy; no device memory but jflags and runs_dev)
+  hipStream_t side = nullptr;      // second stream for weight-gradient GEMMs
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pack = nullptr;
+  hipEvent_t ev_early = nullptr;             // recorded by backward() when the gradients of the bucket prefix are final
   // Flag joins (training step; common.h: flag_wait): where the main stream needs a side-stream chain's results, the consuming KERNEL
   // waits on the device for a word that a one-thread launch behind the chain sets, instead of the stream waiting for an event -- an
   // event wait costs the main stream 9 - 12 us of packet processing even when the chain finished long ago (tools/micro/fork_cost.hip),
@@ -180,252 +399,57 @@ struct mmda_misa {
   // (fused_bwd_a_kernel).  Backward: nothing on the main stream reads what the side stream's weight-gradient GEMMs and early
   // optimizer pass write; the step's last optimizer launch simply does not complete before they have.  ev_join is still recorded
   // behind each chain for the paths that cannot wait on the device.  MMDA_FLAG_JOIN=0: event joins as before.
-  unsigned* jflags = nullptr;                // device: [0] forward chain done, [1] backward chain done, [2] a wait timed out
-  unsigned jval[2] = {0u, 0u};
+  unsigned* jflags = nullptr;                // device: [0] forward chain done, [1] backward chain done, [2] a wait timed out, [3] id list sorted
+  // runs_dev: the table of trainable runs on the device (the one allocation besides jflags), copied when the set has changed since
+  // the last launch that read it.
+  mmda_run* runs_dev = nullptr; int runs_dev_cap = 0; int runs_dirty = 1;
+  // optional per-launch timing of the four recurrent kernels (bench.py roofline leg)
+  std::vector<hipEvent_t> ev;      // [step][slot][start/stop]
+  // ---- the state of the step in flight
+  StepPlan plan;                             // its decisions (plan_step)
+  int64_t early_floats = 0; int early_valid = 0;
+  // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
+  // recurrence runs there, on the side stream (Pass::early); how far that pass of the last backward got
+  int64_t adam_early_done = 0;
+  int wT_valid = 0;                // the K-major fusion-weight copies in the workspace are this step's
+  int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
+  int enc_cached = 0;              // the forward being planned starts behind the encoders (set by the *_encoded entry points, cleared by mmda_misa_forward)
+  // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
+  // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
+  // for backward itself)
+  PendingRows eu;
+  // deferred table: df_seq: updates applied since the binding (what a current row's row_step equals); df_flushed: df_seq at the last full flush.
+  int df_seq = 0, df_flushed = 0;
+  // state of the last forward (dropout replay in backward)
+  int training = 0; uint64_t seed = 0;
+  unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_cluster.hip)
+  int side_pending = 0;
+  int zero_grad_pending = 0;       // train_step: the gradient bucket is cleared inside forward(), beside the fusion block
+  // train_step: the losses that read only the private/shared representations (diff, CMD) are issued by forward() on the side
+  // stream as soon as those exist, beside the transformer layer and the heads; mmda_misa_losses() then adds the rest
+  int eager_losses = 0, eager_done = 0;      // eager_done: that chain, and any loss seeds, not yet taken up by mmda_misa_losses
+  // Loss seeds (training step, fused row-local stretches): the forward stretches store the gradient seeds of the reconstruction loss
+  // (d_recon, d_orig) and -- without ConfidNet, whose loss adds into the same buffer -- of the classification loss (d_scores) where
+  // they produce recon / scores, so the launch that computes cls / conf / recon and the weighted total has no gradient to seed and
+  // leaves the critical path between the forward and the backward pass (14 us at B=32): it runs on the side stream beside the
+  // layer-2 backward recurrence.  Values are bit-identical to the loss launch's (same expressions on the same operands).
+  const float* emo_eager = nullptr;          // labels of the step in flight (train_step)
+  const float* misc_deferred = nullptr;      // labels: the loss-value launch is still to be issued (backward's first side fork)
+  unsigned jval[2] = {0u, 0u};               // the values the flag-join words [0], [1] were last set to
   // The sort-based embedding scatter of a large batch in two halves: the sorted (id, position) list depends on the ids only and is
   // made on the side stream beside the layer-2 backward recurrence (33 us of launches at B=256 that used to sit between the last
   // GEMM and the optimizer); word [3] tells the main stream it is there (a one-wave wait launch in front of the sums).
-  int64_t esort = -1; int esort_valid = 0; unsigned esort_val = 0u;
-  int64_t rec_part = -1;
+  int esort_valid = 0; unsigned esort_val = 0u;
   int fj1 = 0, fj2 = 0, fj1_armed = 0;
-  int ldR = 0;
-  // cluster-exchange regions: at the front of the workspace, sized by B alone, so a change of T (every batch under the reference's
-  // collate) neither moves nor clears them -- flags are monotonic epochs.  Cleared (on the caller's stream) only when the buffer
-  // or B changes; the abort words found there before a clear are kept in `abort_sticky`.
-  float* xchg_ws = nullptr; int xchg_B = 0; int abort_sticky = 0;
-  std::vector<hipEvent_t> ev;      // [step][slot][start/stop]
   int ev_steps = 0, ev_fwd = 0, ev_bwd = 0;
-  int ev_stride = 1, ev_seen_f = 0, ev_seen_b = 0;   // record every ev_stride-th step (the event pairs cost ~35 us per step)
-  int ev_rotate = 0;                                 // 1: a sampled step brackets ONE of the four recurrent launches (sample index % 4): ~9 us
+  int ev_seen_f = 0, ev_seen_b = 0;
   std::vector<char> ev_done;                         // (step, slot) was recorded
+
+ private:
+  Workspace lay_{};
 };
 
 namespace {
-
-int64_t add_param(mmda_misa* m, const std::string& name, int rows, int cols) {
-  ParamInfo p{name, m->flat, rows, cols};
-  m->index[name] = (int)m->params.size();
-  m->params.push_back(p);
-  m->flat += (int64_t)rows * (cols > 0 ? cols : 1);
-  return p.off;
-}
-
-void build_params(mmda_misa* m) {
-  const mmda_misa_config& c = m->cfg;
-  const int dims[3] = {c.d_t, c.d_v, c.d_a};
-  const char* mn[3] = {"t", "v", "a"};
-  const int hs = c.hidden;
-  // Order of the dense bucket = the order in which the backward pass completes the gradients (data-parallel ranks start
-  // reducing a prefix while the rest is still being computed, mmda_misa_early_grad_floats): fusion block and LayerNorms first,
-  // then the layer-2 recurrent layers, then layer 1; the embedding matrix closes the bucket.
-  for (int i = 0; i < 3; ++i) { Mod& md = m->mod[i]; md.D = md.H = dims[i]; }
-  for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i];
-    std::string p = std::string("project_") + mn[i] + ".project_" + mn[i];
-    md.pw = add_param(m, p + ".weight", hs, 4 * md.H);
-    md.pb = add_param(m, p + ".bias", hs, 0);
-    md.plw = add_param(m, p + "_layer_norm.weight", hs, 0);
-    md.plb = add_param(m, p + "_layer_norm.bias", hs, 0);
-  }
-  // batched groups: three (hs,hs) weights back to back, then their three biases (uniform strides for batched GEMMs)
-  m->priv_w = add_param(m, "private_t.private_t_1.weight", hs, hs);
-  add_param(m, "private_v.private_v_1.weight", hs, hs);
-  add_param(m, "private_a.private_a_3.weight", hs, hs);          // sic: reference models.py:95
-  m->priv_b = add_param(m, "private_t.private_t_1.bias", hs, 0);
-  add_param(m, "private_v.private_v_1.bias", hs, 0);
-  add_param(m, "private_a.private_a_3.bias", hs, 0);
-  m->sh_w = add_param(m, "shared.shared_1.weight", hs, hs);
-  m->sh_b = add_param(m, "shared.shared_1.bias", hs, 0);
-  m->rec_w = add_param(m, "recon_t.recon_t_1.weight", hs, hs);
-  add_param(m, "recon_v.recon_v_1.weight", hs, hs);
-  add_param(m, "recon_a.recon_a_1.weight", hs, hs);
-  m->rec_b = add_param(m, "recon_t.recon_t_1.bias", hs, 0);
-  add_param(m, "recon_v.recon_v_1.bias", hs, 0);
-  add_param(m, "recon_a.recon_a_1.bias", hs, 0);
-  if (!c.use_cmd_sim) {
-    m->d1_w = add_param(m, "discriminator.discriminator_layer_1.weight", hs, hs);
-    m->d1_b = add_param(m, "discriminator.discriminator_layer_1.bias", hs, 0);
-    m->d2_w = add_param(m, "discriminator.discriminator_layer_2.weight", 3, hs);
-    m->d2_b = add_param(m, "discriminator.discriminator_layer_2.bias", 3, 0);
-  }
-  m->sp_w = add_param(m, "sp_discriminator.sp_discriminator_layer_1.weight", 4, hs);
-  m->sp_b = add_param(m, "sp_discriminator.sp_discriminator_layer_1.bias", 4, 0);
-  // [confidence; classifier] adjacent -> one (6+ncls, 6hs) head GEMM
-  m->head_w = add_param(m, "confidence.confidence_layer_1.weight", 6, 6 * hs);
-  add_param(m, "classifier.classifier_layer.weight", c.ncls, 6 * hs);
-  m->head_b = add_param(m, "confidence.confidence_layer_1.bias", 6, 0);
-  add_param(m, "classifier.classifier_layer.bias", c.ncls, 0);
-  for (int i = 0; i < 3; ++i) {
-    m->mod[i].ln_w = add_param(m, std::string(mn[i]) + "layer_norm.weight", 2 * m->mod[i].H, 0);
-    m->mod[i].ln_b = add_param(m, std::string(mn[i]) + "layer_norm.bias", 2 * m->mod[i].H, 0);
-  }
-  const std::string te = "transformer_encoder.layers.0.";
-  m->in_w = add_param(m, te + "self_attn.in_proj_weight", 3 * hs, hs);
-  m->in_b = add_param(m, te + "self_attn.in_proj_bias", 3 * hs, 0);
-  m->out_w = add_param(m, te + "self_attn.out_proj.weight", hs, hs);
-  m->out_b = add_param(m, te + "self_attn.out_proj.bias", hs, 0);
-  m->l1_w = add_param(m, te + "linear1.weight", FFN, hs);
-  m->l1_b = add_param(m, te + "linear1.bias", FFN, 0);
-  m->l2_w = add_param(m, te + "linear2.weight", hs, FFN);
-  m->l2_b = add_param(m, te + "linear2.bias", hs, 0);
-  m->n1_w = add_param(m, te + "norm1.weight", hs, 0);
-  m->n1_b = add_param(m, te + "norm1.bias", hs, 0);
-  m->n2_w = add_param(m, te + "norm2.weight", hs, 0);
-  m->n2_b = add_param(m, te + "norm2.bias", hs, 0);
-  if (c.act == MMDA_ACT_PRELU) m->prelu_a = add_param(m, "activation.weight", 1, 0);      // last of the block: what follows is re-aligned
-  for (int l = 1; l >= 0; --l) {
-    m->flat = (m->flat + 3) & ~(int64_t)3;
-    (l == 1 ? m->rnn2_begin : m->rnn1_begin) = m->flat;
-    for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i];
-      Rnn& r = md.rnn[l];
-      r.H = md.H; r.D = l == 0 ? md.D : 2 * md.H;
-      const int ng = c.rnncell == MMDA_CELL_GRU ? 3 : 4;      // gate blocks per direction in the torch-layout parameters
-      std::string pre = std::string(mn[i]) + "rnn" + (l == 0 ? "1" : "2") + ".";
-      r.w_ih = add_param(m, pre + "weight_ih_l0", ng * r.H, r.D);
-      add_param(m, pre + "weight_ih_l0_reverse", ng * r.H, r.D);
-      r.w_hh[0] = add_param(m, pre + "weight_hh_l0", ng * r.H, r.H);
-      r.w_hh[1] = add_param(m, pre + "weight_hh_l0_reverse", ng * r.H, r.H);
-      r.b_ih = add_param(m, pre + "bias_ih_l0", ng * r.H, 0);
-      add_param(m, pre + "bias_ih_l0_reverse", ng * r.H, 0);
-      r.b_hh = add_param(m, pre + "bias_hh_l0", ng * r.H, 0);
-      add_param(m, pre + "bias_hh_l0_reverse", ng * r.H, 0);
-    }
-  }
-  m->flat = (m->flat + 3) & ~(int64_t)3;
-  m->dense = m->flat;
-  m->embed = add_param(m, "embed.weight", c.vocab, c.d_t);
-  m->flat = (m->flat + 3) & ~(int64_t)3;
-}
-
-struct Carver {
-  int64_t cur = 0;
-  int64_t take(int64_t n) { int64_t o = cur; cur += (n + 3) & ~(int64_t)3; return o; }   // 16-B aligned
-};
-
-// lays out the workspace for (B,T); returns total floats.  With m == nullptr-like dry run when commit == false.
-int64_t layout(mmda_misa* m, int B, int T, bool commit) {
-  const mmda_misa_config& c = m->cfg;
-  const int hs = c.hidden, NC = 6 + c.ncls;
-  const int64_t R = (int64_t)T * B;
-  Carver k;
-  mmda_misa tmp_store;               // only used to keep the code path identical in dry runs
-  mmda_misa* o = commit ? m : &tmp_store;
-  if (!commit) { o->cfg = m->cfg; for (int i = 0; i < 3; ++i) o->mod[i] = m->mod[i]; }
-  for (int i = 0; i < 3; ++i) {       // exchange buffers of the recurrences first: their offsets depend on B only
-    Mod& md = o->mod[i];
-    md.xchg_floats = (mmda_lstm_xchg_bytes(md.H, B) + 3) / 4;
-    md.xchg = md.xchg_floats > 0 ? k.take(md.xchg_floats) : -1;
-  }
-  for (int i = 0; i < 3; ++i) {
-    Mod& md = o->mod[i];
-    for (int l = 0; l < 2; ++l) {
-      Rnn& r = md.rnn[l];
-      for (int d = 0; d < 2; ++d) {     // sized for the larger (fp32) packing so the mode can be switched in place
-        r.pack_f[d] = k.take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 0) / 4);
-        r.pack_b[d] = k.take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 1) / 4);
-        r.pack_c[d] = k.take(mmda_lstm_packed_bytes(MMDA_BF16, r.H, 2) / 4);
-      }
-    }
-    for (int l = 0; l < 2; ++l) {
-      Rnn& r = md.rnn[l];
-      const int ldR = round_up((int)R, 8);
-      r.ldD = round_up(r.D, 8); r.ldG = round_up(8 * r.H, 8);
-      r.wb = k.take((int64_t)8 * r.H * r.ldD / 2); r.wbT = k.take((int64_t)r.D * r.ldG / 2);
-      r.xb = k.take(R * r.ldD / 2); r.xbT = k.take((int64_t)r.D * ldR / 2);
-      r.dgb = k.take(R * r.ldG / 2); r.dgbT = k.take((int64_t)8 * r.H * ldR / 2);
-      r.hbT = k.take((int64_t)2 * r.H * ldR / 2);
-      r.ldH = round_up(r.H, 8);
-      for (int d = 0; d < 2; ++d) r.hbp[d] = k.take(R * r.ldH / 2);
-    }
-    if (c.rnncell == MMDA_CELL_GRU) {
-      for (int l = 0; l < 2; ++l) {
-        Rnn& r = md.rnn[l];
-        r.pw_ih = k.take((int64_t)8 * r.H * r.D); r.pw_hh[0] = k.take((int64_t)4 * r.H * r.H); r.pw_hh[1] = k.take((int64_t)4 * r.H * r.H);
-        r.pb_ih = k.take(8 * r.H); r.pb_hh = k.take(8 * r.H);
-      }
-    }
-    md.x = (i == 0) ? k.take(R * md.D) : -1;
-    for (int l = 0; l < 2; ++l) {
-      md.gates[l] = k.take(R * 8 * md.H);
-      md.c[l] = k.take((int64_t)T * round_up(B, 4) * 2 * md.H);     // batch-minor-by-4 under the gate-minor layout: rows rounded up
-      md.hseq[l] = k.take(R * 2 * md.H);
-    }
-    md.normed = k.take(R * 2 * md.H);
-    md.ln_mean = k.take(R);
-    md.ln_rstd = k.take(R);
-    md.utt = k.take((int64_t)B * 4 * md.H);
-    md.d_utt = k.take((int64_t)B * 4 * md.H);
-    md.d_hseq1 = k.take(R * 2 * md.H);
-    md.d_normed = k.take(R * 2 * md.H);
-    md.d_x = (i == 0) ? k.take(R * md.D) : -1;
-  }
-  const int64_t BH = (int64_t)B * hs;
-  o->z = k.take(3 * BH); o->pmean = k.take(3 * B); o->prstd = k.take(3 * B);
-  // public outputs (what the reference's solver reads off the module) are contiguous so the host can snapshot them at once
-  const int64_t pub_begin = k.cur;
-  o->orig = k.take(3 * BH); o->x6 = k.take(6 * BH); o->recon = k.take(3 * BH); o->dom = k.take((int64_t)3 * B * 3);
-  o->tcp = k.take((int64_t)B * 6); o->scores = k.take((int64_t)B * c.ncls); o->labels = k.take((int64_t)B * c.ncls);
-  const int64_t pub_end = k.cur;
-  o->rsum = k.take(3 * BH); o->dom_z = k.take(3 * BH); o->dom_h = k.take(3 * BH);
-  o->qkv = k.take(6 * BH * 3); o->probs = k.take((int64_t)B * NHEAD * S6 * S6); o->ctx = k.take(6 * BH);
-  o->attn_out = k.take(6 * BH); o->ln1_mean = k.take(6 * B); o->ln1_rstd = k.take(6 * B); o->x1 = k.take(6 * BH);
-  o->f1 = k.take((int64_t)6 * B * FFN); o->f2 = k.take(6 * BH); o->ln2_mean = k.take(6 * B); o->ln2_rstd = k.take(6 * B);
-  o->hfused = k.take(6 * BH); o->logits = k.take((int64_t)B * NC);
-  o->x1q = k.take(6 * BH / 4); o->x1s = k.take(6 * BH / 128 + 4); o->w1q = k.take((int64_t)FFN * hs / 4); o->w1s = k.take((int64_t)FFN * hs / 128 + 4);
-  o->f1q = k.take((int64_t)6 * B * FFN / 4); o->f1s = k.take((int64_t)6 * B * FFN / 128 + 4);
-  o->w2q = k.take((int64_t)hs * FFN / 4); o->w2s = k.take((int64_t)hs * FFN / 128 + 4);
-  o->diff_work = k.take(mmda_loss_diff_work_floats(B, hs));
-  o->ffn_parts = k.take((int64_t)(FFN / 32) * 6 * BH);      // partial products of the hidden-sliced feed-forward kernels (fused_rows.hip)
-  o->ln_parts = k.take((int64_t)512 * 2 * 2 * (o->mod[0].H + o->mod[1].H + o->mod[2].H));   // <= 512 block partials of the three inter-layer LayerNorms' gamma / beta gradients (norm.hip)
-  o->rec_part = k.take(3 * BH);                             // d_recon W_rec, made beside the backward pass's first stretch for its third (fused_rows.h)
-  o->esort = k.take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (dist.hip)
-  o->pg_parts = k.take((int64_t)B * FUSED_PG_SLOTS * 2 * 128);      // per-sample LayerNorm gamma / beta gradient partials of the fused backward stretches
-  o->head_wT = k.take((int64_t)6 * hs * NC); o->l2_wT = k.take((int64_t)FFN * hs); o->l1_wT = k.take((int64_t)hs * FFN);
-  o->out_wT = k.take((int64_t)hs * hs); o->in_wT = k.take((int64_t)hs * 3 * hs); o->rec_wT = k.take((int64_t)3 * hs * hs);
-  o->priv_wT = k.take((int64_t)3 * hs * hs); o->sh_wT = k.take((int64_t)hs * hs);
-  if (!c.use_cmd_sim) { o->d1_wT = k.take((int64_t)hs * hs); o->d2_wT = k.take((int64_t)hs * 3); }
-  for (int i = 0; i < 3; ++i) o->pwT[i] = k.take((int64_t)4 * o->mod[i].H * hs);
-  o->gpad_begin = k.cur;
-  if (c.rnncell == MMDA_CELL_GRU) {
-    for (int i = 0; i < 3; ++i)
-      for (int l = 0; l < 2; ++l) {
-        Rnn& r = o->mod[i].rnn[l];
-        r.gw_ih = k.take((int64_t)8 * r.H * r.D); r.gw_hh[0] = k.take((int64_t)4 * r.H * r.H); r.gw_hh[1] = k.take((int64_t)4 * r.H * r.H);
-        r.gb = k.take(8 * r.H);
-      }
-  }
-  o->gpad_end = k.cur;
-  // ---- the loss sums and the activation gradients seeded by the losses (zeroed every step by ONE memset, contiguous)
-  o->zero_begin = k.cur;
-  o->losses = k.take(8);
-  o->d_tcp = k.take((int64_t)B * 6); o->d_x6 = k.take(6 * BH); o->d_dom = k.take((int64_t)3 * B * 3);
-  o->zero_cls = k.cur;                       // (a step whose forward stores these seeds itself clears up to here only)
-  o->d_scores = k.take((int64_t)B * c.ncls);
-  o->zero_recon = k.cur;
-  o->d_orig = k.take(3 * BH); o->d_recon = k.take(3 * BH);
-  o->zero_end = k.cur;
-  // ---- fully overwritten gradients
-  o->d_logits = k.take((int64_t)B * NC); o->d_hfused = k.take(6 * BH); o->d_x1 = k.take(6 * BH); o->d_f2 = k.take(6 * BH);
-  o->d_f1 = k.take((int64_t)6 * B * FFN); o->d_attn_out = k.take(6 * BH); o->d_ctx = k.take(6 * BH);
-  o->d_qkv = k.take(6 * BH * 3); o->d_z = k.take(3 * BH); o->d_dom_h = k.take(3 * BH); o->d_dom_z = k.take(3 * BH);
-  // ---- clip_norm: the gradient norm and its clip coefficient, and the norm launch's block partials (doubles, two floats each)
-  o->gnorm = k.take(4); o->gnorm_parts = k.take(2 * mmda_grad_norm_partials(INT64_MAX));
-  if (commit) {
-    std::map<std::string, int64_t>& t = m->tens;
-    t.clear();
-    t["scores"] = m->scores; t["labels"] = m->labels; t["tcp"] = m->tcp; t["logits"] = m->logits; t["hfused"] = m->hfused;
-    t["x6"] = m->x6; t["orig"] = m->orig; t["recon"] = m->recon; t["dom"] = m->dom; t["losses"] = m->losses; t["grad_norm"] = m->gnorm;
-    t["utt_t"] = m->mod[0].utt; t["utt_v"] = m->mod[1].utt; t["utt_a"] = m->mod[2].utt;
-    t["d_scores"] = m->d_scores; t["d_tcp"] = m->d_tcp; t["d_x6"] = m->d_x6; t["d_orig"] = m->d_orig;
-    t["d_recon"] = m->d_recon; t["d_dom"] = m->d_dom;
-    t["pub_begin"] = pub_begin; t["pub_end"] = pub_end; t["zero_begin"] = m->zero_begin; t["zero_end"] = m->zero_end;
-    t["hseq1_t"] = m->mod[0].hseq[0]; t["hseq1_v"] = m->mod[1].hseq[0]; t["hseq1_a"] = m->mod[2].hseq[0];
-    t["d_x_t"] = m->mod[0].d_x;      // gradient w.r.t. the gathered embedding rows (T*B, d_t): the sparse form of embed.weight.grad
-    t["xchg_t"] = m->mod[0].xchg; t["xchg_v"] = m->mod[1].xchg; t["xchg_a"] = m->mod[2].xchg;   // word 0 of each = its abort word
-  }
-  return k.cur;
-}
 
 // ---------------------------------------------------------------------------------------------- GEMM shorthands
 struct Ctx {
@@ -587,31 +611,31 @@ int side_join(mmda_misa* m, void* main_stream) {
 // Recurrent-layer parameters / gradients as the kernels see them: the bound flat buffers (LSTM) or the four-slot workspace
 // copies (GRU; filled by mmda_gru_pad_params at the top of forward, folded back by mmda_gru_unpad_grads at the end of backward).
 inline bool is_gru(const mmda_misa* m) { return m->cfg.rnncell == MMDA_CELL_GRU; }
-inline float* rW_ih(mmda_misa* m, const Rnn& r) { return is_gru(m) ? WS(r.pw_ih) : PP(r.w_ih); }
-inline float* rW_hh(mmda_misa* m, const Rnn& r, int d) { return is_gru(m) ? WS(r.pw_hh[d]) : PP(r.w_hh[d]); }
-inline float* rB_ih(mmda_misa* m, const Rnn& r) { return is_gru(m) ? WS(r.pb_ih) : PP(r.b_ih); }
-inline float* rB_hh(mmda_misa* m, const Rnn& r) { return is_gru(m) ? WS(r.pb_hh) : PP(r.b_hh); }
-inline float* gW_ih(mmda_misa* m, const Rnn& r) { return is_gru(m) ? WS(r.gw_ih) : GG(r.w_ih); }
-inline float* gW_hh(mmda_misa* m, const Rnn& r, int d) { return is_gru(m) ? WS(r.gw_hh[d]) : GG(r.w_hh[d]); }
-inline float* gB_ih(mmda_misa* m, const Rnn& r) { return is_gru(m) ? WS(r.gb) : GG(r.b_ih); }
-inline float* gB_hh(mmda_misa* m, const Rnn& r) { return is_gru(m) ? nullptr : GG(r.b_hh); }
+inline float* rW_ih(mmda_misa* m, int i, int l) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].pw_ih) : PP(m->par.mod[i].rnn[l].w_ih); }
+inline float* rW_hh(mmda_misa* m, int i, int l, int d) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].pw_hh[d]) : PP(m->par.mod[i].rnn[l].w_hh[d]); }
+inline float* rB_ih(mmda_misa* m, int i, int l) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].pb_ih) : PP(m->par.mod[i].rnn[l].b_ih); }
+inline float* rB_hh(mmda_misa* m, int i, int l) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].pb_hh) : PP(m->par.mod[i].rnn[l].b_hh); }
+inline float* gW_ih(mmda_misa* m, int i, int l) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].gw_ih) : GG(m->par.mod[i].rnn[l].w_ih); }
+inline float* gW_hh(mmda_misa* m, int i, int l, int d) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].gw_hh[d]) : GG(m->par.mod[i].rnn[l].w_hh[d]); }
+inline float* gB_ih(mmda_misa* m, int i, int l) { return is_gru(m) ? WS(m->lay.mod[i].rnn[l].gb) : GG(m->par.mod[i].rnn[l].b_ih); }
+inline float* gB_hh(mmda_misa* m, int i, int l) { return is_gru(m) ? nullptr : GG(m->par.mod[i].rnn[l].b_hh); }
 
 // GRU: jobs for the pad / unpad kernels; `base` is the flat parameter (pad) or gradient (unpad) buffer
 int gru_jobs(mmda_misa* m, float* base, bool grads, mmda_gru_pad_job* j) {
   int n = 0;
   for (int i = 0; i < 3; ++i)
     for (int l = 0; l < 2; ++l, ++n) {
-      const Rnn& r = m->mod[i].rnn[l];
+      const RnnP& r = m->par.mod[i].rnn[l]; const RnnW& rw = m->lay.mod[i].rnn[l];
       j[n] = mmda_gru_pad_job{};
       j[n].H = r.H; j[n].D = r.D;
       for (int d = 0; d < 2; ++d) {
         j[n].w_ih[d] = base + r.w_ih + (int64_t)d * 3 * r.H * r.D; j[n].w_hh[d] = base + r.w_hh[d];
         j[n].b_ih[d] = base + r.b_ih + (int64_t)d * 3 * r.H; j[n].b_hh[d] = base + r.b_hh + (int64_t)d * 3 * r.H;
-        j[n].pw_hh[d] = grads ? WS(r.gw_hh[d]) : WS(r.pw_hh[d]);
+        j[n].pw_hh[d] = grads ? WS(rw.gw_hh[d]) : WS(rw.pw_hh[d]);
       }
-      j[n].pw_ih = grads ? WS(r.gw_ih) : WS(r.pw_ih);
-      j[n].pb_ih = grads ? WS(r.gb) : WS(r.pb_ih);
-      j[n].pb_hh = grads ? nullptr : WS(r.pb_hh);
+      j[n].pw_ih = grads ? WS(rw.gw_ih) : WS(rw.pw_ih);
+      j[n].pb_ih = grads ? WS(rw.gb) : WS(rw.pb_ih);
+      j[n].pb_hh = grads ? nullptr : WS(rw.pb_hh);
     }
   return n;
 }
@@ -619,7 +643,7 @@ int gru_jobs(mmda_misa* m, float* base, bool grads, mmda_gru_pad_job* j) {
 // parameters of a parametrised activation (prelu / rrelu) at one of its uses; zeros for every other activation
 mmda_act_params act_params(mmda_misa* m, int training, uint64_t seed, int site, bool grads) {
   mmda_act_params p = {};
-  if (m->cfg.act == MMDA_ACT_PRELU) { p.slope = m->P + m->prelu_a; p.dslope = grads ? m->G + m->prelu_a : nullptr; }
+  if (m->cfg.act == MMDA_ACT_PRELU) { p.slope = m->P + m->par.prelu_a; p.dslope = grads ? m->G + m->par.prelu_a : nullptr; }
   if (m->cfg.act == MMDA_ACT_RRELU) { p.lo = 1.0f / 8.0f; p.hi = 1.0f / 3.0f; p.rand = training ? 1 : 0; p.seed = seed; p.site = site; }   // torch defaults
   return p;
 }
@@ -632,24 +656,24 @@ int check_ready(const mmda_misa* m) {
 // recurrent descriptor of modality i, layer l: forward (W_hh packed for the forward kernels, utt) or backward (streaming backward
 // packing, the resident-weights one where `with_c`, d_utt, d(hseq of layer 1))
 mmda_lstm_desc lstm_desc(mmda_misa* m, int i, int l, bool bwd, int gate_minor, bool with_c) {
-  Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-  const int64_t* wp = bwd ? r.pack_b : r.pack_f;
+  const ModW& mw = m->lay.mod[i]; const RnnW& rw = mw.rnn[l];
+  const int64_t* wp = bwd ? rw.pack_b : rw.pack_f;
   mmda_lstm_desc d = {};
-  d.H = r.H; d.gates = WS(md.gates[l]); d.cstash = WS(md.c[l]); d.hseq = WS(md.hseq[l]);
+  d.H = m->par.mod[i].rnn[l].H; d.gates = WS(mw.gates[l]); d.cstash = WS(mw.c[l]); d.hseq = WS(mw.hseq[l]);
   d.wpack[0] = WS(wp[0]); d.wpack[1] = WS(wp[1]);
-  if (with_c) { d.wpack_c[0] = WS(r.pack_c[0]); d.wpack_c[1] = WS(r.pack_c[1]); }
-  d.utt = WS(bwd ? md.d_utt : md.utt); d.layer = l; d.d_hseq = bwd && l == 0 ? WS(md.d_hseq1) : nullptr;
-  d.xchg = (m->use_cluster && md.xchg >= 0) ? (void*)WS(md.xchg) : nullptr; d.epoch_base = m->epoch;
+  if (with_c) { d.wpack_c[0] = WS(rw.pack_c[0]); d.wpack_c[1] = WS(rw.pack_c[1]); }
+  d.utt = WS(bwd ? mw.d_utt : mw.utt); d.layer = l; d.d_hseq = bwd && l == 0 ? WS(mw.d_hseq1) : nullptr;
+  d.xchg = (m->use_cluster && mw.xchg >= 0) ? (void*)WS(mw.xchg) : nullptr; d.epoch_base = m->epoch;
   d.gate_minor = gate_minor; d.cell = m->cfg.rnncell;
   return d;
 }
 
 // floats of the gradient bucket that a step writes, clears and walks with dense Adam: all of it, or the prefix in front of the table
-int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE && !m->df_row_step ? m->flat : m->embed; }
+int64_t grad_floats(const mmda_misa* m) { return m->embed_update == EU_DENSE && !m->df_row_step ? m->par.flat : m->par.embed; }
 
 // ---- frozen parameters
 // a launch over [0, grad_floats) has a frozen float to leave out (else the step is today's: the dense kernels, the early pass)
-bool masked(const mmda_misa* m) { return m->prefix_frozen || (!m->embed_flag && grad_floats(m) == m->flat); }
+bool masked(const mmda_misa* m) { return m->prefix_frozen || (!m->embed_flag && grad_floats(m) == m->par.flat); }
 // the encoder cut: nothing behind the fusion block trains -- the recurrent layers and the inter-layer LayerNorms are frozen and the
 // table is, by its flag (dense) or by embed_update (the sparse and deferred modes train the table through d_x: no cut)
 bool encoder_cut(const mmda_misa* m) {
@@ -673,7 +697,7 @@ int runs_ready(mmda_misa* m, void* stream) {
   if (need > m->runs_dev_cap) {
     if (m->runs_dev) (void)hipFree(m->runs_dev);
     m->runs_dev = nullptr; m->runs_dev_cap = 0;
-    const int cap = (int)m->params.size() + 1;            // every tensor a run of its own, and the closing entry
+    const int cap = (int)m->par.params.size() + 1;            // every tensor a run of its own, and the closing entry
     if (hipMalloc(reinterpret_cast<void**>(&m->runs_dev), sizeof(mmda_run) * cap) != hipSuccess) { m->runs_dev = nullptr; return MMDA_ELAUNCH; }
     m->runs_dev_cap = cap;
   }
@@ -700,16 +724,16 @@ int bucket_adam(mmda_misa* m, int64_t lo, int64_t hi, const float* acc, float lr
 // clip_norm > 0: the norm of the gradient the step is about to apply -- G or acc + G over [0, grad_floats), the trainable runs of it
 // when parameters are frozen -- and the clip coefficient, into gnorm[0], gnorm[1]
 int bucket_norm(mmda_misa* m, const float* acc, float grad_scale, void* stream) {
-  if (!m->ws || m->gnorm < 0) return MMDA_EINVAL;
-  double* parts = reinterpret_cast<double*>(m->ws + m->gnorm_parts);
+  if (!m->ws || m->lay.gnorm < 0) return MMDA_EINVAL;
+  double* parts = reinterpret_cast<double*>(m->ws + m->lay.gnorm_parts);
   const int64_t cap = mmda_grad_norm_partials(INT64_MAX);
   const int64_t hi = grad_floats(m);
-  if (!masked(m)) return mmda_grad_norm_launch(m->G, acc, hi, nullptr, m->clip_norm, grad_scale, parts, cap, m->ws + m->gnorm, stream);
+  if (!masked(m)) return mmda_grad_norm_launch(m->G, acc, hi, nullptr, m->clip_norm, grad_scale, parts, cap, m->ws + m->lay.gnorm, stream);
   int r0 = 0, n = 0; int64_t items = 0;
   runs_slice(m, 0, hi, &r0, &n, &items);
   if (n > 0 && (m->runs_dirty || !m->runs_dev)) return MMDA_EINVAL;
   const RunTable t{n > 0 ? m->runs_dev + r0 : nullptr, n, items};
-  return mmda_grad_norm_launch(m->G, acc, 0, &t, m->clip_norm, grad_scale, parts, cap, m->ws + m->gnorm, stream);
+  return mmda_grad_norm_launch(m->G, acc, 0, &t, m->clip_norm, grad_scale, parts, cap, m->ws + m->lay.gnorm, stream);
 }
 // what no step does (checked in front of its first launch, so a refused call changes nothing): decay under the deferred table -- the
 // replay ring holds two scalars per update, a decayed zero-gradient step needs a third; a norm clip with a table whose rows are updated
@@ -721,27 +745,27 @@ bool adam_settings_refused(const mmda_misa* m) {
 }
 // the table from one flag per parameter (nullptr: everything trains)
 int apply_trainable(mmda_misa* m, const unsigned char* flags) {
-  const int np = (int)m->params.size();
+  const int np = (int)m->par.params.size();
   std::vector<int64_t> begin, len;
   int prefix_frozen = 0, embed_flag = 1, enc_frozen = 1;
   for (int i = 0; i < np; ++i) {
-    const ParamInfo& p = m->params[i];
+    const ParamInfo& p = m->par.params[i];
     const bool on = !flags || flags[i] != 0;
     const std::string top = p.name.substr(0, p.name.find('.'));
-    if (p.off == m->embed) embed_flag = on ? 1 : 0;
+    if (p.off == m->par.embed) embed_flag = on ? 1 : 0;
     else if (!on) prefix_frozen = 1;
-    if (on && ((p.off >= m->rnn2_begin && p.off < m->embed) || top == "tlayer_norm" || top == "vlayer_norm" || top == "alayer_norm")) enc_frozen = 0;
+    if (on && ((p.off >= m->par.rnn2_begin && p.off < m->par.embed) || top == "tlayer_norm" || top == "vlayer_norm" || top == "alayer_norm")) enc_frozen = 0;
     if (!on) continue;
     begin.push_back(p.off);
-    len.push_back((i + 1 < np ? m->params[i + 1].off : m->flat) - p.off);
+    len.push_back((i + 1 < np ? m->par.params[i + 1].off : m->par.flat) - p.off);
   }
-  const int64_t cuts[3] = {m->rnn2_begin, m->rnn1_begin, m->embed};
+  const int64_t cuts[3] = {m->par.rnn2_begin, m->par.rnn1_begin, m->par.embed};
   std::vector<mmda_run> runs(begin.size() + 1);
   int n = 0;
-  const int64_t items = mmda_runs_build_cut(begin.data(), len.data(), (int)begin.size(), m->flat, cuts, 3, runs.data(), &n);
+  const int64_t items = mmda_runs_build_cut(begin.data(), len.data(), (int)begin.size(), m->par.flat, cuts, 3, runs.data(), &n);
   if (items < 0) return MMDA_EINVAL;
   runs.resize(n + 1);
-  runs[n] = mmda_run{m->flat, 0, items};
+  runs[n] = mmda_run{m->par.flat, 0, items};
   m->runs.swap(runs);
   m->prefix_frozen = prefix_frozen; m->embed_flag = embed_flag; m->enc_frozen = enc_frozen;
   m->runs_dirty = 1;
@@ -762,7 +786,7 @@ StepPlan plan_step(mmda_misa* m) {
   static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
   static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
   const mmda_misa_config& c = m->cfg;
-  const int B = m->B, T = m->T, mode = c.mode;
+  const int B = m->lay.B, T = m->lay.T, mode = c.mode;
   StepPlan P;
   // which recurrent kernels will run: decides the packings of W_hh that are made and the layout of `gates`
   auto probe_resident = [&](int gate_minor, int backward) -> bool {
@@ -817,10 +841,10 @@ StepPlan plan_step(mmda_misa* m) {
   P.fj_fwd = P.fj_on && P.seed_recon && P.seed_cls;
   P.fj_device = P.fj_fwd && B <= FJ_DEVICE_MAX_B;
   P.zg_here = zg_side >= 0 ? zg_side != 0 : P.fj_device;
-  P.rec_hoisted = fsplit && m->rec_part >= 0 && B <= 64;
+  P.rec_hoisted = fsplit && m->lay.rec_part >= 0 && B <= 64;
   P.embed_update = m->embed_update;
   P.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
-  P.sort_early = sort_early && T > 0 && m->esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN && !P.enc_cut;
+  P.sort_early = sort_early && T > 0 && m->lay.esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN && !P.enc_cut;
   return P;
 }
 
@@ -833,9 +857,7 @@ extern "C" int mmda_misa_create(const mmda_misa_config* cfg, mmda_misa** out) {
   if (cfg->d_t > 512 || cfg->d_v > 512 || cfg->d_a > 512 || cfg->hidden % NHEAD || cfg->hidden > 1024) return MMDA_EINVAL;
   if (cfg->mode != MMDA_F32 && cfg->mode != MMDA_BF16) return MMDA_EINVAL;
   if (cfg->rnncell != MMDA_CELL_LSTM && cfg->rnncell != MMDA_CELL_GRU) return MMDA_EINVAL;
-  mmda_misa* m = new mmda_misa();
-  m->cfg = *cfg;
-  build_params(m);
+  mmda_misa* m = new mmda_misa(*cfg);
   if (apply_trainable(m, nullptr)) { delete m; return MMDA_EINVAL; }
   *out = m;
   return MMDA_OK;
@@ -852,18 +874,18 @@ extern "C" void mmda_misa_destroy(mmda_misa* m) {
   for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
   delete m;
 }
-extern "C" int mmda_misa_num_params(const mmda_misa* m) { return m ? (int)m->params.size() : MMDA_EINVAL; }
+extern "C" int mmda_misa_num_params(const mmda_misa* m) { return m ? (int)m->par.params.size() : MMDA_EINVAL; }
 extern "C" int mmda_misa_param_info(const mmda_misa* m, int i, const char** name, int64_t* offset, int* rows, int* cols) {
-  if (!m || i < 0 || i >= (int)m->params.size()) return MMDA_EINVAL;
-  const ParamInfo& p = m->params[i];
+  if (!m || i < 0 || i >= (int)m->par.params.size()) return MMDA_EINVAL;
+  const ParamInfo& p = m->par.params[i];
   if (name) *name = p.name.c_str();
   if (offset) *offset = p.off;
   if (rows) *rows = p.rows;
   if (cols) *cols = p.cols;
   return MMDA_OK;
 }
-extern "C" int64_t mmda_misa_flat_floats(const mmda_misa* m) { return m ? m->flat : MMDA_EINVAL; }
-extern "C" int64_t mmda_misa_dense_floats(const mmda_misa* m) { return m ? m->dense : MMDA_EINVAL; }
+extern "C" int64_t mmda_misa_flat_floats(const mmda_misa* m) { return m ? m->par.flat : MMDA_EINVAL; }
+extern "C" int64_t mmda_misa_dense_floats(const mmda_misa* m) { return m ? m->par.dense : MMDA_EINVAL; }
 extern "C" int mmda_misa_bind(mmda_misa* m, float* params, float* grads, float* adam_m, float* adam_v) {
   if (!m || !params) return MMDA_EINVAL;
   if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)adam_m | (uintptr_t)adam_v) & 15) return MMDA_EINVAL;
@@ -872,16 +894,16 @@ extern "C" int mmda_misa_bind(mmda_misa* m, float* params, float* grads, float* 
 }
 extern "C" int64_t mmda_misa_workspace_floats(const mmda_misa* m, int B, int T) {
   if (!m || B <= 0 || T <= 0) return MMDA_EINVAL;
-  return layout(const_cast<mmda_misa*>(m), B, T, false);
+  return carve(m->cfg, m->par, B, T).floats;
 }
 namespace {
 // abort words of the CURRENT exchange regions -> abort_sticky (synchronous device->host copies)
 int harvest_abort(mmda_misa* m) {
   if (!m->ws || !m->xchg_ws || m->xchg_ws != m->ws) return MMDA_OK;
   for (int i = 0; i < 3; ++i) {
-    if (m->mod[i].xchg < 0) continue;
+    if (m->lay.mod[i].xchg < 0) continue;
     unsigned w = 0;
-    if (hipMemcpy(&w, m->ws + m->mod[i].xchg, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return MMDA_ELAUNCH;
+    if (hipMemcpy(&w, m->ws + m->lay.mod[i].xchg, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return MMDA_ELAUNCH;
     if (w) m->abort_sticky = 1;
   }
   return MMDA_OK;
@@ -890,22 +912,22 @@ int harvest_abort(mmda_misa* m) {
 
 extern "C" int mmda_misa_set_workspace_async(mmda_misa* m, float* ws, int64_t floats, int B, int T, void* stream) {
   if (!m || !ws || B <= 0 || T <= 0 || ((uintptr_t)ws & 15)) return MMDA_EINVAL;
-  int64_t need = layout(m, B, T, false);
-  if (floats < need) return MMDA_EINVAL;
+  const Workspace w = carve(m->cfg, m->par, B, T);
+  if (floats < w.floats) return MMDA_EINVAL;
   // The exchange regions keep their place and their contents while the buffer and B stay the same (a new T only): nothing to clear,
   // the flags there are monotonic epochs.  Otherwise they start from zero -- after the abort words of the old ones were looked at
   // (same buffer, new B: one synchronous read per region, rare; a NEW buffer: the caller reads mmda_misa_cluster_status first).
   const bool keep = m->xchg_ws == ws && m->xchg_B == B;
   if (!keep && m->xchg_ws == ws) { int rc = harvest_abort(m); if (rc) return rc; }
-  layout(m, B, T, true);
-  m->ws = ws; m->ws_floats = floats; m->B = B; m->T = T; m->ldR = round_up(B * T, 8);
+  m->rebind(w);
+  m->ws = ws;
   hipStream_t s = (hipStream_t)stream;
   if (!keep) {
     for (int i = 0; i < 3; ++i)
-      if (m->mod[i].xchg >= 0 && hipMemsetAsync(ws + m->mod[i].xchg, 0, sizeof(float) * m->mod[i].xchg_floats, s) != hipSuccess) return MMDA_ELAUNCH;
+      if (w.mod[i].xchg >= 0 && hipMemsetAsync(ws + w.mod[i].xchg, 0, sizeof(float) * w.mod[i].xchg_floats, s) != hipSuccess) return MMDA_ELAUNCH;
     m->xchg_ws = ws; m->xchg_B = B;
   }
-  if (m->gpad_end > m->gpad_begin && hipMemsetAsync(ws + m->gpad_begin, 0, sizeof(float) * (m->gpad_end - m->gpad_begin), s) != hipSuccess)
+  if (w.gpad_end > w.gpad_begin && hipMemsetAsync(ws + w.gpad_begin, 0, sizeof(float) * (w.gpad_end - w.gpad_begin), s) != hipSuccess)
     return MMDA_ELAUNCH;
   return MMDA_OK;
 }
@@ -913,9 +935,10 @@ extern "C" int mmda_misa_set_workspace(mmda_misa* m, float* ws, int64_t floats, 
   return mmda_misa_set_workspace_async(m, ws, floats, B, T, nullptr);       // the null stream: ordered against every blocking stream
 }
 extern "C" int64_t mmda_misa_tensor_offset(const mmda_misa* m, const char* name) {
-  if (!m || !name) return -1;
-  auto it = m->tens.find(name);
-  return it == m->tens.end() ? -1 : it->second;
+  if (!m || !name || !m->ws) return -1;             // (no workspace bound yet: no name has an offset)
+  for (const TensorName& t : kTensorNames)
+    if (!strcmp(t.name, name)) return t.off(m->lay);
+  return -1;
 }
 extern "C" int mmda_misa_set_mode(mmda_misa* m, int mode) {
   if (!m || (mode != MMDA_F32 && mode != MMDA_BF16)) return MMDA_EINVAL;
@@ -965,9 +988,9 @@ extern "C" int mmda_misa_cluster_status(const mmda_misa* m, int* aborted_host) {
     if (w) *aborted_host |= 2;                 // (bit 1: a stream-to-stream flag wait, not a recurrence)
   }
   for (int i = 0; i < 3; ++i) {
-    if (m->mod[i].xchg < 0) continue;
+    if (m->lay.mod[i].xchg < 0) continue;
     unsigned w = 0;
-    if (hipMemcpy(&w, m->ws + m->mod[i].xchg, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return MMDA_ELAUNCH;
+    if (hipMemcpy(&w, m->ws + m->lay.mod[i].xchg, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return MMDA_ELAUNCH;
     if (w) *aborted_host = 1;
   }
   return MMDA_OK;
@@ -979,16 +1002,17 @@ namespace {
 // stream that the end of forward() joins
 void weight_transpose_jobs(mmda_misa* m, std::vector<mmda_transpose_job>& tj) {
   const mmda_misa_config& c = m->cfg;
+  const ParamTable& p = m->par; const Workspace& w = m->lay;
   const int hs_ = c.hidden, NC_ = 6 + c.ncls;
   auto T_ = [&](int64_t src, int rows, int cols, int64_t dst) { tj.push_back(mmda_transpose_job{PP(src), rows, cols, cols, WS(dst), rows}); };
-  T_(m->head_w, NC_, 6 * hs_, m->head_wT); T_(m->l2_w, hs_, FFN, m->l2_wT); T_(m->l1_w, FFN, hs_, m->l1_wT);
-  T_(m->out_w, hs_, hs_, m->out_wT); T_(m->in_w, 3 * hs_, hs_, m->in_wT); T_(m->sh_w, hs_, hs_, m->sh_wT);
+  T_(p.head_w, NC_, 6 * hs_, w.head_wT); T_(p.l2_w, hs_, FFN, w.l2_wT); T_(p.l1_w, FFN, hs_, w.l1_wT);
+  T_(p.out_w, hs_, hs_, w.out_wT); T_(p.in_w, 3 * hs_, hs_, w.in_wT); T_(p.sh_w, hs_, hs_, w.sh_wT);
   for (int i = 0; i < 3; ++i) {
-    T_(m->rec_w + (int64_t)i * hs_ * hs_, hs_, hs_, m->rec_wT + (int64_t)i * hs_ * hs_);
-    T_(m->priv_w + (int64_t)i * hs_ * hs_, hs_, hs_, m->priv_wT + (int64_t)i * hs_ * hs_);
-    T_(m->mod[i].pw, hs_, 4 * m->mod[i].H, m->pwT[i]);
+    T_(p.rec_w + (int64_t)i * hs_ * hs_, hs_, hs_, w.rec_wT + (int64_t)i * hs_ * hs_);
+    T_(p.priv_w + (int64_t)i * hs_ * hs_, hs_, hs_, w.priv_wT + (int64_t)i * hs_ * hs_);
+    T_(p.mod[i].pw, hs_, 4 * p.mod[i].H, w.pwT[i]);
   }
-  if (!c.use_cmd_sim) { T_(m->d1_w, hs_, hs_, m->d1_wT); T_(m->d2_w, 3, hs_, m->d2_wT); }
+  if (!c.use_cmd_sim) { T_(p.d1_w, hs_, hs_, w.d1_wT); T_(p.d2_w, 3, hs_, w.d2_wT); }
 }
 int weight_transposes(mmda_misa* m, void* ss) {
   std::vector<mmda_transpose_job> tj;
@@ -1002,20 +1026,21 @@ int weight_transposes(mmda_misa* m, void* ss) {
 // bf16 operand copies that only the backward pass reads -- hseq of both layers (per direction for the tn weight-gradient GEMMs,
 // transposed for the nt ones) and, nt only, the transposed layer-2 inputs: made on the side stream beside the fusion block.  <= 15 jobs.
 int backward_only_jobs(mmda_misa* m, mmda_convert_job* cj) {
-  const int R = m->B * m->T;
+  const ParamTable& p = m->par; const Workspace& w = m->lay;
+  const int R = w.B * w.T;
   int n = 0;
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i];
+    const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
     for (int l = 0; l < 2; ++l) {
-      Rnn& r = md.rnn[l];
+      const RnnP& r = md.rnn[l]; const RnnW& rw = mw.rnn[l];
       if (m->plan.tn_wgrad) {
         for (int d = 0; d < 2; ++d)
-          cj[n++] = mmda_convert_job{WS(md.hseq[l]) + d * md.H, 2 * md.H, R, md.H, nullptr, WS(r.hbp[d]), r.ldH, nullptr, 0};
+          cj[n++] = mmda_convert_job{WS(mw.hseq[l]) + d * md.H, 2 * md.H, R, md.H, nullptr, WS(rw.hbp[d]), r.ldH, nullptr, 0};
       } else {
-        cj[n++] = mmda_convert_job{WS(md.hseq[l]), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(r.hbT), m->ldR};
+        cj[n++] = mmda_convert_job{WS(mw.hseq[l]), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(rw.hbT), w.ldR};
       }
     }
-    if (!m->plan.tn_wgrad) cj[n++] = mmda_convert_job{WS(md.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(md.rnn[1].xbT), m->ldR};
+    if (!m->plan.tn_wgrad) cj[n++] = mmda_convert_job{WS(mw.normed), 2 * md.H, R, 2 * md.H, nullptr, nullptr, 0, WS(mw.rnn[1].xbT), w.ldR};
   }
   return n;
 }
@@ -1024,8 +1049,8 @@ int backward_only_jobs(mmda_misa* m, mmda_convert_job* cj) {
 // then DiffLoss and CMD with their gradients (they read x6 only), then the gradient bucket if train_step left that to forward()
 int eager_side_losses(mmda_misa* m, void* stream) {
   if (!m->eager_losses) return MMDA_OK;
-  const mmda_misa_config& c = m->cfg;
-  const int B = m->B, hs = c.hidden;
+  const mmda_misa_config& c = m->cfg; const Workspace& w = m->lay;
+  const int B = w.B, hs = c.hidden;
   const int64_t BH = (int64_t)B * hs;
   void* ss = nullptr;
   int rc = side_fork(m, stream, &ss);
@@ -1033,7 +1058,7 @@ int eager_side_losses(mmda_misa* m, void* stream) {
   if (!rc && m->wT_pending) rc = weight_transposes(m, B >= 128 ? stream : ss);
   // (the forward stretches on the main stream STORE the seeds they own: clearing those here would race with them)
   const StepPlan& P = m->plan;
-  const int64_t zend = P.seed_cls ? m->zero_cls : P.seed_recon ? m->zero_recon : m->zero_end;
+  const int64_t zend = P.seed_cls ? w.zero_cls : P.seed_recon ? w.zero_recon : w.zero_end;
   // The gradient bucket (43 MB, 11 us) is cleared on the MAIN stream behind the fork: since the row-local stretches were fused the
   // side stream's loss chain (72 us at B=32), not the main stream's fusion block (55 us), is what the join at the end of forward() waits
   // for.  (Nothing on either stream touches the bucket before the backward pass; MMDA_ZERO_GRAD_SIDE=1: the old place.)
@@ -1041,18 +1066,18 @@ int eager_side_losses(mmda_misa* m, void* stream) {
   // device, small batches: see mmda_misa::jflags) -- the chain then has two launches of slack and the clear comes back here, in ONE
   // launch with the activation-gradient region, at the head of the chain.
   if (!rc && P.zg_here && m->zero_grad_pending) {
-    rc = mmda_zero2(WS(m->zero_begin), zend - m->zero_begin, m->G, grad_floats(m), ss);
+    rc = mmda_zero2(WS(w.zero_begin), zend - w.zero_begin, m->G, grad_floats(m), ss);
     m->zero_grad_pending = 0;
   } else if (!rc) {
-    if (hipMemsetAsync(WS(m->zero_begin), 0, sizeof(float) * (zend - m->zero_begin), (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
+    if (hipMemsetAsync(WS(w.zero_begin), 0, sizeof(float) * (zend - w.zero_begin), (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
   }
-  float* L = WS(m->losses);
-  if (!rc) rc = mmda_loss_diff(WS(m->x6), BH, B, hs, c.diff_weight, L + 1, WS(m->d_x6), WS(m->diff_work), ss);
+  float* L = WS(w.losses);
+  if (!rc) rc = mmda_loss_diff(WS(w.x6), BH, B, hs, c.diff_weight, L + 1, WS(w.d_x6), WS(w.diff_work), ss);
   // the chain's last launch sets the flag-join word itself where it can (single-workgroup CMD: no one-thread launch behind it)
   m->fj1_armed = (!rc && c.use_cmd_sim && P.fj_fwd && m->jflags && mmda_loss_cmd_sets_flag(B, hs)) ? 1 : 0;
   if (!rc && c.use_cmd_sim) {
     static const int sim_pairs[6] = {0, 1, 0, 2, 2, 1};      // what mmda_loss_cmd runs: (t,v), (t,a), (a,v), five moments, / 3
-    rc = mmda_loss_cmd_pairs_tail(WS(m->x6 + 3 * BH), BH, 3, 3, sim_pairs, 5, B, hs, c.sim_weight, 1.0f / 3.0f, L + 2, WS(m->d_x6 + 3 * BH), ss,
+    rc = mmda_loss_cmd_pairs_tail(WS(w.x6 + 3 * BH), BH, 3, 3, sim_pairs, 5, B, hs, c.sim_weight, 1.0f / 3.0f, L + 2, WS(w.d_x6 + 3 * BH), ss,
                                   m->fj1_armed ? m->jflags + 0 : nullptr, m->jval[0] + 1);
   }
   if (!rc && m->zero_grad_pending) { rc = mmda_misa_zero_grad(m, stream); m->zero_grad_pending = 0; }
@@ -1066,27 +1091,27 @@ namespace {
 // linear2): x1 (6B, hs) -> f1 (6B, FFN) -> f2 (6B, hs).  Four launches: quantise {x1, W1, W2}, product 1 (+bias, relu, dropout),
 // quantise f1, product 2 (+bias).  The f32 tensors f1 / f2 the backward pass reads are written as on the exact path.
 int ffn_fp8(mmda_misa* m, float p_tf, uint64_t seed, void* stream) {
-  const mmda_misa_config& c = m->cfg;
-  const int hs = c.hidden, R6 = 6 * m->B;
+  const mmda_misa_config& c = m->cfg; const ParamTable& p = m->par; const Workspace& w = m->lay;
+  const int hs = c.hidden, R6 = 6 * w.B;
   if ((hs % 128) != 0) return MMDA_EINVAL;               // K of product 1 must be whole 128-deep MFMA steps
   auto U8 = [&](int64_t off) { return reinterpret_cast<unsigned char*>(m->ws + off); };
   mmda_mx8_quant_job q[3] = {
-      {m->ws + m->x1, hs, R6, hs, U8(m->x1q), U8(m->x1s)},
-      {m->P + m->l1_w, hs, FFN, hs, U8(m->w1q), U8(m->w1s)},
-      {m->P + m->l2_w, FFN, hs, FFN, U8(m->w2q), U8(m->w2s)}};
+      {m->ws + w.x1, hs, R6, hs, U8(w.x1q), U8(w.x1s)},
+      {m->P + p.l1_w, hs, FFN, hs, U8(w.w1q), U8(w.w1s)},
+      {m->P + p.l2_w, FFN, hs, FFN, U8(w.w2q), U8(w.w2s)}};
   int rc = mmda_mx8_quant(q, 3, stream);
   if (rc) return rc;
   mmda_mx8_args g = {};
-  g.M = R6; g.N = FFN; g.K = hs; g.Aq = U8(m->x1q); g.As = U8(m->x1s); g.Bq = U8(m->w1q); g.Bs = U8(m->w1s);
-  g.C = m->ws + m->f1; g.ldc = FFN; g.bias = m->P + m->l1_b; g.act = MMDA_ACT_RELU; g.drop_p = p_tf; g.drop_seed = seed; g.drop_site = SITE_FFN;
+  g.M = R6; g.N = FFN; g.K = hs; g.Aq = U8(w.x1q); g.As = U8(w.x1s); g.Bq = U8(w.w1q); g.Bs = U8(w.w1s);
+  g.C = m->ws + w.f1; g.ldc = FFN; g.bias = m->P + p.l1_b; g.act = MMDA_ACT_RELU; g.drop_p = p_tf; g.drop_seed = seed; g.drop_site = SITE_FFN;
   rc = mmda_gemm_mx8(&g, stream);
   if (rc) return rc;
-  mmda_mx8_quant_job qf = {m->ws + m->f1, FFN, R6, FFN, U8(m->f1q), U8(m->f1s)};
+  mmda_mx8_quant_job qf = {m->ws + w.f1, FFN, R6, FFN, U8(w.f1q), U8(w.f1s)};
   rc = mmda_mx8_quant(&qf, 1, stream);
   if (rc) return rc;
   mmda_mx8_args h = {};
-  h.M = R6; h.N = hs; h.K = FFN; h.Aq = U8(m->f1q); h.As = U8(m->f1s); h.Bq = U8(m->w2q); h.Bs = U8(m->w2s);
-  h.C = m->ws + m->f2; h.ldc = hs; h.bias = m->P + m->l2_b;
+  h.M = R6; h.N = hs; h.K = FFN; h.Aq = U8(w.f1q); h.As = U8(w.f1s); h.Bq = U8(w.w2q); h.Bs = U8(w.w2s);
+  h.C = m->ws + w.f2; h.ldc = hs; h.bias = m->P + p.l2_b;
   return mmda_gemm_mx8(&h, stream);
 }
 }  // namespace
@@ -1131,7 +1156,7 @@ extern "C" int mmda_misa_embed_flush(mmda_misa* m, void* stream) {
   if (!m->df_row_step) return MMDA_OK;                     // nothing is deferred
   if (!m->P || !m->M1 || !m->V1) return MMDA_EINVAL;
   if (m->df_flushed == m->df_seq) return MMDA_OK;          // no update since the last flush: nothing is stale, nothing is launched
-  const int rc = mmda_embed_rows_flush(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window,
+  const int rc = mmda_embed_rows_flush(PP(m->par.embed), m->M1 + m->par.embed, m->V1 + m->par.embed, m->df_row_step, m->df_ring, m->df_window,
                                        m->cfg.d_t, m->cfg.vocab, m->adam.beta1, m->adam.beta2, m->adam.eps, m->df_seq, stream);
   if (!rc) m->df_flushed = m->df_seq;
   return rc;
@@ -1141,11 +1166,11 @@ namespace {
 // update df_seq + 1 of the deferred table for the rows of one backward's id list, counted here and nowhere else
 int deferred_apply(mmda_misa* m, const int64_t* ids, const unsigned* sorted, const int32_t* lengths, float lr, float beta1, float beta2,
                    float eps, float clip, float grad_scale, int step, bool catch_up, void* stream) {
-  if (!m->df_row_step || !m->P || !m->M1 || !m->V1 || !m->ws || m->T <= 0 || !ids) return MMDA_EINVAL;
+  if (!m->df_row_step || !m->P || !m->M1 || !m->V1 || !m->ws || m->lay.T <= 0 || !ids) return MMDA_EINVAL;
   if (m->df_seq == INT32_MAX) return MMDA_EINVAL;
   const int seq = m->df_seq + 1;
-  const int rc = mmda_embed_dense_adam_apply(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, ids,
-                                             sorted, m->B * m->T, m->cfg.d_t, WS(m->mod[0].d_x), lengths, m->B, m->cfg.vocab, lr, beta1,
+  const int rc = mmda_embed_dense_adam_apply(PP(m->par.embed), m->M1 + m->par.embed, m->V1 + m->par.embed, m->df_row_step, m->df_ring, m->df_window, ids,
+                                             sorted, m->lay.B * m->lay.T, m->cfg.d_t, WS(m->lay.mod[0].d_x), lengths, m->lay.B, m->cfg.vocab, lr, beta1,
                                              beta2, eps, clip, grad_scale, seq, step, catch_up, stream);
   if (rc) return rc;
   if (seq % m->df_window == 0) m->df_flushed = seq - 1;    // (that update flushed first)
@@ -1171,7 +1196,7 @@ extern "C" int mmda_misa_set_fusion_fp8(mmda_misa* m, int on) {
 
 // ---- frozen parameters
 extern "C" int mmda_misa_set_trainable(mmda_misa* m, const unsigned char* flags, int n_params) {
-  if (!m || !flags || n_params != (int)m->params.size()) return MMDA_EINVAL;
+  if (!m || !flags || n_params != (int)m->par.params.size()) return MMDA_EINVAL;
   return apply_trainable(m, flags);
 }
 extern "C" int mmda_misa_trainable_info(const mmda_misa* m, mmda_run* runs, int capacity, int* n_runs, int64_t* trainable_floats,
@@ -1210,12 +1235,13 @@ namespace {
 struct Pass : Ctx {
   const StepPlan& P;
   const mmda_misa_config& c;
+  const ParamTable& p; const Workspace& w;   // read-only views of the handle's two values: no stage moves an offset
   const int B, T, R, hs, NC, mode;
   static constexpr int fmode = MMDA_F32;     // the fusion block's GEMMs: exact path (see mmda_misa_forward)
   const int64_t BH; const float p_tf, p_cls; const uint64_t seed;
   const OptStep* early = nullptr;            // backward of a fused step: the optimizer step this pass may start (see bwd_encoder_layer)
   Pass(mmda_misa* m_, void* s_)
-      : Ctx{m_, s_}, P(m_->plan), c(m_->cfg), B(m_->B), T(m_->T), R(m_->T * m_->B), hs(c.hidden), NC(6 + c.ncls), mode(c.mode),
+      : Ctx{m_, s_}, P(m_->plan), c(m_->cfg), p(m_->par), w(m_->lay), B(w.B), T(w.T), R(w.T * w.B), hs(c.hidden), NC(6 + c.ncls), mode(c.mode),
         BH((int64_t)B * hs), p_tf(m_->training ? c.fusion_dropout : 0.f), p_cls(m_->training ? c.dropout : 0.f), seed(m_->seed) {}
   mmda_ln_args proj_ln_fwd(int i), norm1_fwd(), norm2_fwd();             // LayerNorm arguments (builders below)
   mmda_ln_bwd_args proj_ln_bwd(int i), norm1_bwd(), norm2_bwd();
@@ -1234,45 +1260,45 @@ struct Pass : Ctx {
 // LayerNorm arguments of the fusion block: the projections' (+ activation), norm1 and norm2 (residual and dropout ride along)
 mmda_ln_args Pass::proj_ln_fwd(int i) {
   mmda_ln_args ln = {};
-  ln.rows = B; ln.n = hs; ln.x = WS(m->z + i * BH); ln.gamma = PP(m->mod[i].plw); ln.beta = PP(m->mod[i].plb);
-  ln.y = WS(m->orig + i * BH); ln.mean = WS(m->pmean + i * B); ln.rstd = WS(m->prstd + i * B); ln.act = c.act;
+  ln.rows = B; ln.n = hs; ln.x = WS(w.z + i * BH); ln.gamma = PP(p.mod[i].plw); ln.beta = PP(p.mod[i].plb);
+  ln.y = WS(w.orig + i * BH); ln.mean = WS(w.pmean + i * B); ln.rstd = WS(w.prstd + i * B); ln.act = c.act;
   ln.eps = 1e-5f; ln.actp = act_params(m, m->training, seed, SITE_RRELU + i, false);
   return ln;
 }
 mmda_ln_args Pass::norm1_fwd() {
   mmda_ln_args ln = {};
-  ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x6); ln.res = WS(m->attn_out); ln.gamma = PP(m->n1_w); ln.beta = PP(m->n1_b);
-  ln.y = WS(m->x1); ln.mean = WS(m->ln1_mean); ln.rstd = WS(m->ln1_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
+  ln.rows = 6 * B; ln.n = hs; ln.x = WS(w.x6); ln.res = WS(w.attn_out); ln.gamma = PP(p.n1_w); ln.beta = PP(p.n1_b);
+  ln.y = WS(w.x1); ln.mean = WS(w.ln1_mean); ln.rstd = WS(w.ln1_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
   ln.drop_site = SITE_DROP1; ln.eps = 1e-5f;
   return ln;
 }
 mmda_ln_args Pass::norm2_fwd() {
   mmda_ln_args ln = {};
-  ln.rows = 6 * B; ln.n = hs; ln.x = WS(m->x1); ln.res = WS(m->f2); ln.gamma = PP(m->n2_w); ln.beta = PP(m->n2_b);
-  ln.y = WS(m->hfused); ln.mean = WS(m->ln2_mean); ln.rstd = WS(m->ln2_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
+  ln.rows = 6 * B; ln.n = hs; ln.x = WS(w.x1); ln.res = WS(w.f2); ln.gamma = PP(p.n2_w); ln.beta = PP(p.n2_b);
+  ln.y = WS(w.hfused); ln.mean = WS(w.ln2_mean); ln.rstd = WS(w.ln2_rstd); ln.drop_p = p_tf; ln.drop_seed = seed;
   ln.drop_site = SITE_DROP2; ln.permute_S = S6; ln.permute_B = B; ln.eps = 1e-5f;   // emits h = cat(h[0..5], dim=1)
   return ln;
 }
 mmda_ln_bwd_args Pass::proj_ln_bwd(int i) {
   mmda_ln_bwd_args l = {};
-  l.rows = B; l.n = hs; l.dy = WS(m->d_orig + i * BH); l.x = WS(m->z + i * BH); l.gamma = PP(m->mod[i].plw);
-  l.mean = WS(m->pmean + i * B); l.rstd = WS(m->prstd + i * B); l.d_x = WS(m->d_z + i * BH);
-  l.dgamma = GG(m->mod[i].plw); l.dbeta = GG(m->mod[i].plb); l.act = c.act;
+  l.rows = B; l.n = hs; l.dy = WS(w.d_orig + i * BH); l.x = WS(w.z + i * BH); l.gamma = PP(p.mod[i].plw);
+  l.mean = WS(w.pmean + i * B); l.rstd = WS(w.prstd + i * B); l.d_x = WS(w.d_z + i * BH);
+  l.dgamma = GG(p.mod[i].plw); l.dbeta = GG(p.mod[i].plb); l.act = c.act;
   l.actp = act_params(m, m->training, seed, SITE_RRELU + i, true);
   return l;
 }
 mmda_ln_bwd_args Pass::norm1_bwd() {
   mmda_ln_bwd_args l = {};
-  l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_x1); l.x = WS(m->x6); l.res = WS(m->attn_out); l.gamma = PP(m->n1_w);
-  l.mean = WS(m->ln1_mean); l.rstd = WS(m->ln1_rstd); l.d_x = WS(m->d_x6); l.accumulate_dx = 1; l.d_res = WS(m->d_attn_out);
-  l.dgamma = GG(m->n1_w); l.dbeta = GG(m->n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
+  l.rows = 6 * B; l.n = hs; l.dy = WS(w.d_x1); l.x = WS(w.x6); l.res = WS(w.attn_out); l.gamma = PP(p.n1_w);
+  l.mean = WS(w.ln1_mean); l.rstd = WS(w.ln1_rstd); l.d_x = WS(w.d_x6); l.accumulate_dx = 1; l.d_res = WS(w.d_attn_out);
+  l.dgamma = GG(p.n1_w); l.dbeta = GG(p.n1_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP1;
   return l;
 }
 mmda_ln_bwd_args Pass::norm2_bwd() {
   mmda_ln_bwd_args l = {};
-  l.rows = 6 * B; l.n = hs; l.dy = WS(m->d_hfused); l.x = WS(m->x1); l.res = WS(m->f2); l.gamma = PP(m->n2_w);
-  l.mean = WS(m->ln2_mean); l.rstd = WS(m->ln2_rstd); l.d_x = WS(m->d_x1); l.d_res = WS(m->d_f2);
-  l.dgamma = GG(m->n2_w); l.dbeta = GG(m->n2_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP2;
+  l.rows = 6 * B; l.n = hs; l.dy = WS(w.d_hfused); l.x = WS(w.x1); l.res = WS(w.f2); l.gamma = PP(p.n2_w);
+  l.mean = WS(w.ln2_mean); l.rstd = WS(w.ln2_rstd); l.d_x = WS(w.d_x1); l.d_res = WS(w.d_f2);
+  l.dgamma = GG(p.n2_w); l.dbeta = GG(p.n2_b); l.drop_p = p_tf; l.drop_seed = seed; l.drop_site = SITE_DROP2;
   l.permute_S = S6; l.permute_B = B;
   return l;
 }
@@ -1290,14 +1316,14 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
     int n = 0;
     for (int i = 0; i < 3; ++i) {
       for (int l = 0; l < 2; ++l) {
-        Rnn& r = m->mod[i].rnn[l];
-        cj[n++] = mmda_convert_job{rW_ih(m, r), r.D, 8 * r.H, r.D, nullptr, WS(r.wb), r.ldD,
-                                   transposed ? WS(r.wbT) : nullptr, transposed ? r.ldG : 0, P.gm ? r.H : 0};
+        const RnnP& r = p.mod[i].rnn[l]; const RnnW& rw = w.mod[i].rnn[l];
+        cj[n++] = mmda_convert_job{rW_ih(m, i, l), r.D, 8 * r.H, r.D, nullptr, WS(rw.wb), r.ldD,
+                                   transposed ? WS(rw.wbT) : nullptr, transposed ? r.ldG : 0, P.gm ? r.H : 0};
       }
-      Rnn& r0 = m->mod[i].rnn[0];
-      const float* src = i == 0 ? PP(m->embed) : xin[i];
+      const RnnP& r0 = p.mod[i].rnn[0]; const RnnW& rw0 = w.mod[i].rnn[0];
+      const float* src = i == 0 ? PP(p.embed) : xin[i];
       const bool xt = transposed && !P.tn_wgrad;         // layer-1 inputs transposed: only the nt form of layer 1's dW_ih reads them
-      cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, WS(r0.xb), r0.ldD, xt ? WS(r0.xbT) : nullptr, xt ? m->ldR : 0};
+      cj[n++] = mmda_convert_job{src, r0.D, R, r0.D, i == 0 ? t_ids : nullptr, WS(rw0.xb), r0.ldD, xt ? WS(rw0.xbT) : nullptr, xt ? w.ldR : 0};
     }
     return n;
   };
@@ -1312,8 +1338,8 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
   for (int i = 0; i < 3; ++i)
     for (int l = 0; l < 2; ++l)
       for (int d = 0; d < 2; ++d, ++k) {
-        Rnn& r = m->mod[i].rnn[l];
-        Hs[k] = r.H; Wp[k] = rW_hh(m, r, d); Fp[k] = WS(r.pack_f[d]); Bp[k] = P.want_b ? WS(r.pack_b[d]) : nullptr; Cp[k] = WS(r.pack_c[d]);
+        const RnnP& r = p.mod[i].rnn[l]; const RnnW& rw = w.mod[i].rnn[l];
+        Hs[k] = r.H; Wp[k] = rW_hh(m, i, l, d); Fp[k] = WS(rw.pack_f[d]); Bp[k] = P.want_b ? WS(rw.pack_b[d]) : nullptr; Cp[k] = WS(rw.pack_c[d]);
       }
   m->wT_valid = 0;
   if (P.bfg) {
@@ -1336,7 +1362,7 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
     if (!rc && ss != s && hipEventRecord(m->ev_pack, (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
     if (!rc && P.want_wT) rc = weight_transposes(m, ss);
     // embedding rows (models.py:201)
-    if (!rc) rc = mmda_embed_gather(PP(m->embed), t_ids, R, m->cfg.d_t, WS(m->mod[0].x), s);
+    if (!rc) rc = mmda_embed_gather(PP(p.embed), t_ids, R, m->cfg.d_t, WS(w.mod[0].x), s);
   }
 }
 
@@ -1346,16 +1372,16 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
   mmda_gemm_bf16_args bg[3];
   group_begin(*this);
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
-    const float* in = l == 0 ? xin[i] : WS(md.normed);
+    const RnnP& r = p.mod[i].rnn[l]; const ModW& mw = w.mod[i]; const RnnW& rw = mw.rnn[l];
+    const float* in = l == 0 ? xin[i] : WS(mw.normed);
     // time-batched input-to-hidden GEMM for both directions: (R, D) x (8H, D)^T + b_ih + b_hh
     if (P.bfg) {
       bg[i] = mmda_gemm_bf16_args{};
-      bg[i].M = R; bg[i].N = 8 * r.H; bg[i].K = r.D; bg[i].A = WS(r.xb); bg[i].lda = r.ldD; bg[i].B = WS(r.wb); bg[i].ldb = r.ldD;
-      bg[i].C = WS(md.gates[l]); bg[i].ldc = 8 * r.H; bg[i].bias = rB_ih(m, r); bg[i].bias2 = rB_hh(m, r);
+      bg[i].M = R; bg[i].N = 8 * r.H; bg[i].K = r.D; bg[i].A = WS(rw.xb); bg[i].lda = r.ldD; bg[i].B = WS(rw.wb); bg[i].ldb = r.ldD;
+      bg[i].C = WS(mw.gates[l]); bg[i].ldc = 8 * r.H; bg[i].bias = rB_ih(m, i, l); bg[i].bias2 = rB_hh(m, i, l);
       bg[i].perm_n_H = P.gm ? r.H : 0;
     } else {
-      gemm(*this, mode, 0, 1, R, 8 * r.H, r.D, in, r.D, rW_ih(m, r), r.D, WS(md.gates[l]), 8 * r.H, rB_ih(m, r), rB_hh(m, r));
+      gemm(*this, mode, 0, 1, R, 8 * r.H, r.D, in, r.D, rW_ih(m, i, l), r.D, WS(mw.gates[l]), 8 * r.H, rB_ih(m, i, l), rB_hh(m, i, l));
     }
     desc[i] = lstm_desc(m, i, l, false, P.gm, false);
     desc[i].forward_only = P.enc_nostash;
@@ -1374,15 +1400,15 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
   if (l == 0) {
     mmda_ln_args ln[3];
     for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i];
+      const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
       ln[i] = mmda_ln_args{};
-      ln[i].rows = R; ln[i].n = 2 * md.H; ln[i].x = WS(md.hseq[0]); ln[i].gamma = PP(md.ln_w); ln[i].beta = PP(md.ln_b);
-      ln[i].y = WS(md.normed); ln[i].mean = WS(md.ln_mean); ln[i].rstd = WS(md.ln_rstd); ln[i].eps = 1e-5f;
+      ln[i].rows = R; ln[i].n = 2 * md.H; ln[i].x = WS(mw.hseq[0]); ln[i].gamma = PP(md.ln_w); ln[i].beta = PP(md.ln_b);
+      ln[i].y = WS(mw.normed); ln[i].mean = WS(mw.ln_mean); ln[i].rstd = WS(mw.ln_rstd); ln[i].eps = 1e-5f;
     }
     // (bf16 GEMMs: the LayerNorm also writes its output as the bf16 operand copy layer 2's input GEMM reads; the copies that only
     //  the backward pass needs -- hseq, transposed inputs -- are made later on the side stream: backward_only_jobs)
     if (P.bfg)
-      for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(m->mod[i].rnn[1].xb); ln[i].ld_bf16 = m->mod[i].rnn[1].ldD; }
+      for (int i = 0; i < 3; ++i) { ln[i].y_bf16 = WS(w.mod[i].rnn[1].xb); ln[i].ld_bf16 = p.mod[i].rnn[1].ldD; }
     // ... and ONLY as that copy where nothing reads the fp32 output: a pass whose encoders keep no stash, or a training step whose
     // layer-2 weight gradients take the tn form (they read the bf16 copy; the nt form converts the fp32 output into a transposed copy)
     if (P.bfg && (P.enc_nostash || P.tn_wgrad))
@@ -1404,17 +1430,17 @@ void Pass::fwd_fusion_skinny() {
   mmda_skinny_args g[8];
   mmda_ln_args ln[3];
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i];
-    g[i] = sk_nt(B, hs, 4 * md.H, WS(md.utt), 4 * md.H, PP(md.pw), PP(md.pb), WS(m->z + i * BH), hs);
+    const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
+    g[i] = sk_nt(B, hs, 4 * md.H, WS(mw.utt), 4 * md.H, PP(md.pw), PP(md.pb), WS(w.z + i * BH), hs);
     ln[i] = proj_ln_fwd(i);
   }
   sk_launch(*this, g, 3);
   if (!rc) rc = mmda_layernorm_fwd_multi(ln, 3, s);
   // private x3 and shared (one weight over the stacked 3B rows), sigmoid epilogue
   for (int i = 0; i < 3; ++i)
-    g[i] = sk_nt(B, hs, hs, WS(m->orig + i * BH), hs, PP(m->priv_w + (int64_t)i * hs * hs), PP(m->priv_b + i * hs), WS(m->x6 + i * BH), hs,
+    g[i] = sk_nt(B, hs, hs, WS(w.orig + i * BH), hs, PP(p.priv_w + (int64_t)i * hs * hs), PP(p.priv_b + i * hs), WS(w.x6 + i * BH), hs,
                  MMDA_ACT_SIGMOID);
-  g[3] = sk_nt(3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), PP(m->sh_b), WS(m->x6 + 3 * BH), hs, MMDA_ACT_SIGMOID);
+  g[3] = sk_nt(3 * B, hs, hs, WS(w.orig), hs, PP(p.sh_w), PP(p.sh_b), WS(w.x6 + 3 * BH), hs, MMDA_ACT_SIGMOID);
   sk_launch(*this, g, 4);
   if (!rc) rc = eager_side_losses(m, s);
   const mmda_ln_args l1 = norm1_fwd();
@@ -1422,13 +1448,13 @@ void Pass::fwd_fusion_skinny() {
     if (!rc) {
       FusedFwdA f = {};
       // one sample per workgroup in every stretch (two measured B=32 0.722 ms against 0.712; B=256 equal)
-      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1; f.x6 = WS(m->x6);
-      f.rec_w = PP(m->rec_w); f.rec_b = PP(m->rec_b); f.recon = WS(m->recon);
-      f.in_w = PP(m->in_w); f.in_b = PP(m->in_b); f.qkv = WS(m->qkv);
-      f.ctx = WS(m->ctx); f.probs = WS(m->probs); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
-      f.out_w = PP(m->out_w); f.out_b = PP(m->out_b); f.attn_out = WS(m->attn_out); f.ln1 = l1;
+      f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1; f.x6 = WS(w.x6);
+      f.rec_w = PP(p.rec_w); f.rec_b = PP(p.rec_b); f.recon = WS(w.recon);
+      f.in_w = PP(p.in_w); f.in_b = PP(p.in_b); f.qkv = WS(w.qkv);
+      f.ctx = WS(w.ctx); f.probs = WS(w.probs); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
+      f.out_w = PP(p.out_w); f.out_b = PP(p.out_b); f.attn_out = WS(w.attn_out); f.ln1 = l1;
       if (P.seed_recon) {
-        f.orig = WS(m->orig); f.d_recon = WS(m->d_recon); f.d_orig = WS(m->d_orig);
+        f.orig = WS(w.orig); f.d_recon = WS(w.d_recon); f.d_orig = WS(w.d_orig);
         f.recon_inv_n = 1.0f / (float)(3 * BH); f.recon_scale = c.recon_weight;
       }
       rc = mmda_fused_fwd_a(&f, s);
@@ -1438,20 +1464,20 @@ void Pass::fwd_fusion_skinny() {
     // discriminator's first layer all read x6 only
     int n = 0;
     for (int i = 0; i < 3; ++i) {
-      g[n] = sk_nt(B, hs, hs, WS(m->x6 + i * BH), hs, PP(m->rec_w + (int64_t)i * hs * hs), PP(m->rec_b + i * hs), WS(m->recon + i * BH), hs);
-      g[n++].A2 = WS(m->x6 + (3 + i) * BH);
+      g[n] = sk_nt(B, hs, hs, WS(w.x6 + i * BH), hs, PP(p.rec_w + (int64_t)i * hs * hs), PP(p.rec_b + i * hs), WS(w.recon + i * BH), hs);
+      g[n++].A2 = WS(w.x6 + (3 + i) * BH);
     }
-    g[n++] = sk_nt(6 * B, 3 * hs, hs, WS(m->x6), hs, PP(m->in_w), PP(m->in_b), WS(m->qkv), 3 * hs);
-    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, hs, hs, WS(m->x6 + 3 * BH), hs, PP(m->d1_w), PP(m->d1_b), WS(m->dom_z), hs);
+    g[n++] = sk_nt(6 * B, 3 * hs, hs, WS(w.x6), hs, PP(p.in_w), PP(p.in_b), WS(w.qkv), 3 * hs);
+    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, hs, hs, WS(w.x6 + 3 * BH), hs, PP(p.d1_w), PP(p.d1_b), WS(w.dom_z), hs);
     sk_launch(*this, g, n);
     if (!c.use_cmd_sim && !rc) {
       const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, false);
-      rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
+      rc = mmda_act_dropout_fwd_p(WS(w.dom_z), WS(w.dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-    if (!rc) rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, s);
+    if (!rc) rc = mmda_attn_fwd(WS(w.qkv), S6, B, hs, NHEAD, WS(w.ctx), WS(w.probs), p_tf, seed, SITE_ATTN, s);
     n = 0;
-    g[n++] = sk_nt(6 * B, hs, hs, WS(m->ctx), hs, PP(m->out_w), PP(m->out_b), WS(m->attn_out), hs);
-    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, 3, hs, WS(m->dom_h), hs, PP(m->d2_w), PP(m->d2_b), WS(m->dom), 3);
+    g[n++] = sk_nt(6 * B, hs, hs, WS(w.ctx), hs, PP(p.out_w), PP(p.out_b), WS(w.attn_out), hs);
+    if (!c.use_cmd_sim) g[n++] = sk_nt(3 * B, 3, hs, WS(w.dom_h), hs, PP(p.d2_w), PP(p.d2_b), WS(w.dom), 3);
     sk_launch(*this, g, n);
     if (!rc) rc = mmda_layernorm_fwd(&l1, s);
   }
@@ -1461,15 +1487,15 @@ void Pass::fwd_fusion_skinny() {
   } else if (P.ffn_fuse_fwd) {
     if (!rc) {
       FusedFfnFwd f = {};
-      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.x1 = WS(m->x1); f.w1 = PP(m->l1_w); f.b1 = PP(m->l1_b); f.f1 = WS(m->f1);
-      f.p = p_tf; f.seed = seed; f.site = SITE_FFN; f.w2 = PP(m->l2_w); f.parts = WS(m->ffn_parts);
+      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.x1 = WS(w.x1); f.w1 = PP(p.l1_w); f.b1 = PP(p.l1_b); f.f1 = WS(w.f1);
+      f.p = p_tf; f.seed = seed; f.site = SITE_FFN; f.w2 = PP(p.l2_w); f.parts = WS(w.ffn_parts);
       rc = mmda_fused_ffn_fwd(&f, s);
     }
   } else {
-    g[0] = sk_nt(6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), PP(m->l1_b), WS(m->f1), FFN, MMDA_ACT_RELU);
+    g[0] = sk_nt(6 * B, FFN, hs, WS(w.x1), hs, PP(p.l1_w), PP(p.l1_b), WS(w.f1), FFN, MMDA_ACT_RELU);
     g[0].drop_p = p_tf; g[0].drop_seed = seed; g[0].drop_site = SITE_FFN;
     sk_launch(*this, g, 1);
-    g[0] = sk_nt(6 * B, hs, FFN, WS(m->f1), FFN, PP(m->l2_w), PP(m->l2_b), WS(m->f2), hs);
+    g[0] = sk_nt(6 * B, hs, FFN, WS(w.f1), FFN, PP(p.l2_w), PP(p.l2_b), WS(w.f2), hs);
     sk_launch(*this, g, 1);
   }
   const mmda_ln_args l2 = norm2_fwd();
@@ -1477,19 +1503,19 @@ void Pass::fwd_fusion_skinny() {
     if (!rc) {
       FusedFwdC f = {};
       f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1; f.ln2 = l2;
-      if (P.ffn_fuse_fwd) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(m->l2_b); f.f2 = WS(m->f2); }
-      f.hfused = WS(m->hfused); f.head_w = PP(m->head_w); f.head_b = PP(m->head_b); f.logits = WS(m->logits);
-      f.threshold = c.threshold; f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.labels = WS(m->labels);
+      if (P.ffn_fuse_fwd) { f.ffn_parts = WS(w.ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(p.l2_b); f.f2 = WS(w.f2); }
+      f.hfused = WS(w.hfused); f.head_w = PP(p.head_w); f.head_b = PP(p.head_b); f.logits = WS(w.logits);
+      f.threshold = c.threshold; f.tcp = WS(w.tcp); f.scores = WS(w.scores); f.labels = WS(w.labels);
       f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS;
-      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(m->d_scores); }
+      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(w.d_scores); }
       rc = mmda_fused_fwd_c(&f, s);
     }
   } else {
     if (!rc) rc = mmda_layernorm_fwd(&l2, s);
-    g[0] = sk_nt(B, NC, 6 * hs, WS(m->hfused), 6 * hs, PP(m->head_w), PP(m->head_b), WS(m->logits), NC);
+    g[0] = sk_nt(B, NC, 6 * hs, WS(w.hfused), 6 * hs, PP(p.head_w), PP(p.head_b), WS(w.logits), NC);
     sk_launch(*this, g, 1);
     if (!rc)
-      rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
+      rc = mmda_heads_fwd(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
                             s);
   }
 }
@@ -1497,35 +1523,35 @@ void Pass::fwd_fusion_skinny() {
 // the same, many rows: the tiled generic kernel
 void Pass::fwd_fusion_tiled() {
   for (int i = 0; i < 3 && !rc; ++i) {
-    Mod& md = m->mod[i];
-    lin_fwd(*this, fmode, B, hs, 4 * md.H, WS(md.utt), PP(md.pw), PP(md.pb), WS(m->z + i * BH));
+    const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
+    lin_fwd(*this, fmode, B, hs, 4 * md.H, WS(mw.utt), PP(md.pw), PP(md.pb), WS(w.z + i * BH));
     if (rc) break;
     const mmda_ln_args ln = proj_ln_fwd(i);
     rc = mmda_layernorm_fwd(&ln, s);
   }
   // private (three weights, batched) and shared (one weight over the stacked 3B rows), sigmoid epilogue
-  gemm(*this, fmode, 0, 1, B, hs, hs, WS(m->orig), hs, PP(m->priv_w), hs, WS(m->x6), hs, PP(m->priv_b), nullptr, 0, MMDA_ACT_SIGMOID, 3,
+  gemm(*this, fmode, 0, 1, B, hs, hs, WS(w.orig), hs, PP(p.priv_w), hs, WS(w.x6), hs, PP(p.priv_b), nullptr, 0, MMDA_ACT_SIGMOID, 3,
        BH, (int64_t)hs * hs, BH, hs);
-  gemm(*this, fmode, 0, 1, 3 * B, hs, hs, WS(m->orig), hs, PP(m->sh_w), hs, WS(m->x6 + 3 * BH), hs, PP(m->sh_b), nullptr, 0,
+  gemm(*this, fmode, 0, 1, 3 * B, hs, hs, WS(w.orig), hs, PP(p.sh_w), hs, WS(w.x6 + 3 * BH), hs, PP(p.sh_b), nullptr, 0,
        MMDA_ACT_SIGMOID);
   if (!rc) rc = eager_side_losses(m, s);
   // reconstruct (models.py:254-262)
-  if (!rc) rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, s);
-  gemm(*this, fmode, 0, 1, B, hs, hs, WS(m->rsum), hs, PP(m->rec_w), hs, WS(m->recon), hs, PP(m->rec_b), nullptr, 0, 0, 3, BH,
+  if (!rc) rc = mmda_add(WS(w.x6), WS(w.x6 + 3 * BH), WS(w.rsum), 3 * BH, s);
+  gemm(*this, fmode, 0, 1, B, hs, hs, WS(w.rsum), hs, PP(p.rec_w), hs, WS(w.recon), hs, PP(p.rec_b), nullptr, 0, 0, 3, BH,
        (int64_t)hs * hs, BH, hs);
   // adversarial discriminator behind the gradient-reversal layer (models.py:219-227); identity in forward
   if (!c.use_cmd_sim) {
-    lin_fwd(*this, fmode, 3 * B, hs, hs, WS(m->x6 + 3 * BH), PP(m->d1_w), PP(m->d1_b), WS(m->dom_z));
+    lin_fwd(*this, fmode, 3 * B, hs, hs, WS(w.x6 + 3 * BH), PP(p.d1_w), PP(p.d1_b), WS(w.dom_z));
     if (!rc) {
       const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, false);
-      rc = mmda_act_dropout_fwd_p(WS(m->dom_z), WS(m->dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
+      rc = mmda_act_dropout_fwd_p(WS(w.dom_z), WS(w.dom_h), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-    lin_fwd(*this, fmode, 3 * B, 3, hs, WS(m->dom_h), PP(m->d2_w), PP(m->d2_b), WS(m->dom));
+    lin_fwd(*this, fmode, 3 * B, 3, hs, WS(w.dom_h), PP(p.d2_w), PP(p.d2_b), WS(w.dom));
   }
   // 1-layer transformer fusion over the six tokens (models.py:243-245; torch post-norm encoder layer)
-  lin_fwd(*this, fmode, 6 * B, 3 * hs, hs, WS(m->x6), PP(m->in_w), PP(m->in_b), WS(m->qkv));
-  if (!rc) rc = mmda_attn_fwd(WS(m->qkv), S6, B, hs, NHEAD, WS(m->ctx), WS(m->probs), p_tf, seed, SITE_ATTN, s);
-  lin_fwd(*this, fmode, 6 * B, hs, hs, WS(m->ctx), PP(m->out_w), PP(m->out_b), WS(m->attn_out));
+  lin_fwd(*this, fmode, 6 * B, 3 * hs, hs, WS(w.x6), PP(p.in_w), PP(p.in_b), WS(w.qkv));
+  if (!rc) rc = mmda_attn_fwd(WS(w.qkv), S6, B, hs, NHEAD, WS(w.ctx), WS(w.probs), p_tf, seed, SITE_ATTN, s);
+  lin_fwd(*this, fmode, 6 * B, hs, hs, WS(w.ctx), PP(p.out_w), PP(p.out_b), WS(w.attn_out));
   const mmda_ln_args l1 = norm1_fwd(), l2 = norm2_fwd();
   if (!rc) rc = mmda_layernorm_fwd(&l1, s);
   if (m->fusion_fp8) {
@@ -1533,15 +1559,15 @@ void Pass::fwd_fusion_tiled() {
   } else {
     mmda_gemm_args e = {};
     e.drop_p = p_tf; e.drop_seed = seed; e.drop_site = SITE_FFN;
-    gemm(*this, fmode, 0, 1, 6 * B, FFN, hs, WS(m->x1), hs, PP(m->l1_w), hs, WS(m->f1), FFN, PP(m->l1_b), nullptr, 0, MMDA_ACT_RELU, 1, 0,
+    gemm(*this, fmode, 0, 1, 6 * B, FFN, hs, WS(w.x1), hs, PP(p.l1_w), hs, WS(w.f1), FFN, PP(p.l1_b), nullptr, 0, MMDA_ACT_RELU, 1, 0,
          0, 0, 0, &e);
-    lin_fwd(*this, fmode, 6 * B, hs, FFN, WS(m->f1), PP(m->l2_w), PP(m->l2_b), WS(m->f2));
+    lin_fwd(*this, fmode, 6 * B, hs, FFN, WS(w.f1), PP(p.l2_w), PP(p.l2_b), WS(w.f2));
   }
   if (!rc) rc = mmda_layernorm_fwd(&l2, s);
   // heads (models.py:247-249)
-  lin_fwd(*this, fmode, B, NC, 6 * hs, WS(m->hfused), PP(m->head_w), PP(m->head_b), WS(m->logits));
+  lin_fwd(*this, fmode, B, NC, 6 * hs, WS(w.hfused), PP(p.head_w), PP(p.head_b), WS(w.logits));
   if (!rc)
-    rc = mmda_heads_fwd(WS(m->logits), B, c.ncls, c.threshold, WS(m->tcp), WS(m->scores), WS(m->labels), p_cls, seed, SITE_CLS,
+    rc = mmda_heads_fwd(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
                           s);
 }
 }  // namespace
@@ -1570,7 +1596,7 @@ int forward_from_projections(Pass& x, void* stream) {
 }
 
 bool encoded_batch_ok(const mmda_misa* m, const mmda_encoded_batch* eb) {
-  return eb && eb->tab_t && eb->tab_v && eb->tab_a && eb->rows && eb->B > 0 && eb->B == m->B;
+  return eb && eb->tab_t && eb->tab_v && eb->tab_a && eb->rows && eb->B > 0 && eb->B == m->lay.B;
 }
 
 // The forward pass of a step that starts behind the encoders: the plan, ONE gather of the batch's cached rows into utt_t / utt_v /
@@ -1585,9 +1611,9 @@ int forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, 
   Pass x(m, stream);
   m->wT_valid = 0;
   m->wT_pending = m->plan.want_wT ? 1 : 0;
-  x.rc = mmda_encoded_gather(eb->tab_t, eb->tab_v, eb->tab_a, 4 * m->mod[0].H, 4 * m->mod[1].H, 4 * m->mod[2].H,
-                             emo_out ? eb->tab_emo : nullptr, m->cfg.ncls, eb->rows, m->B, WS(m->mod[0].utt), WS(m->mod[1].utt),
-                             WS(m->mod[2].utt), emo_out, stream);
+  x.rc = mmda_encoded_gather(eb->tab_t, eb->tab_v, eb->tab_a, 4 * m->par.mod[0].H, 4 * m->par.mod[1].H, 4 * m->par.mod[2].H,
+                             emo_out ? eb->tab_emo : nullptr, m->cfg.ncls, eb->rows, m->lay.B, WS(m->lay.mod[0].utt), WS(m->lay.mod[1].utt),
+                             WS(m->lay.mod[2].utt), emo_out, stream);
   if (x.rc) return x.rc;
   return forward_from_projections(x, stream);
 }
@@ -1618,11 +1644,11 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   // deferred table update: the rows this batch gathers take the steps they missed first, so the gather reads what dense Adam left
   if (m->plan.embed_deferred) {
     if (!m->M1 || !m->V1) return MMDA_EINVAL;
-    x.rc = mmda_embed_rows_catch_up(PP(m->embed), m->M1 + m->embed, m->V1 + m->embed, m->df_row_step, m->df_ring, m->df_window, t_ids,
-                                    m->B * m->T, m->cfg.d_t, lengths, m->B, m->cfg.vocab, m->adam.beta1, m->adam.beta2, m->adam.eps, m->df_seq, stream);
+    x.rc = mmda_embed_rows_catch_up(PP(m->par.embed), m->M1 + m->par.embed, m->V1 + m->par.embed, m->df_row_step, m->df_ring, m->df_window, t_ids,
+                                    m->lay.B * m->lay.T, m->cfg.d_t, lengths, m->lay.B, m->cfg.vocab, m->adam.beta1, m->adam.beta2, m->adam.eps, m->df_seq, stream);
     if (x.rc) return x.rc;
   }
-  const float* xin[3] = {WS(m->mod[0].x), v, a};
+  const float* xin[3] = {WS(m->lay.mod[0].x), v, a};
   x.fwd_operands(t_ids, xin);
   for (int l = 0; l < 2 && !x.rc; ++l) x.fwd_encoder_layer(l, xin, lengths);
   if (x.rc) return x.rc;
@@ -1633,19 +1659,19 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
 // =============================================================================================== losses
 extern "C" int mmda_misa_zero_act_grads(mmda_misa* m, void* stream) {
   if (check_ready(m)) return MMDA_EINVAL;
-  if (hipMemsetAsync(WS(m->zero_begin), 0, sizeof(float) * (m->zero_end - m->zero_begin), (hipStream_t)stream) != hipSuccess)
+  if (hipMemsetAsync(WS(m->lay.zero_begin), 0, sizeof(float) * (m->lay.zero_end - m->lay.zero_begin), (hipStream_t)stream) != hipSuccess)
     return MMDA_ELAUNCH;
   return MMDA_OK;
 }
 
 extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, void* stream) {
   if (check_ready(m) || !emo) return MMDA_EINVAL;
-  const mmda_misa_config& c = m->cfg;
-  const int B = m->B, hs = c.hidden;
+  const mmda_misa_config& c = m->cfg; const Workspace& w = m->lay;
+  const int B = w.B, hs = c.hidden;
   const int64_t BH = (int64_t)B * hs;
   hipStream_t s = (hipStream_t)stream;
   int rc = MMDA_OK;
-  float* L = WS(m->losses);
+  float* L = WS(w.losses);
   const bool ext = m->ext_batch_losses && with_grads && c.use_cmd_sim;      // the caller did (see mmda_misa::ext_batch_losses)
   const bool eager = (m->eager_done || ext) && with_grads;        // forward() already cleared the region and ran diff (+ CMD) on the side stream
   // seeds the forward stretches stored already: the plan's, while this call takes up that forward pass's chain (eager_done)
@@ -1656,14 +1682,14 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
     if (rc) return rc;
   } else {
     if (with_grads) { rc = mmda_misa_zero_act_grads(m, stream); if (rc) return rc; }      // covers the loss sums too
-    else if (hipMemsetAsync(WS(m->losses), 0, sizeof(float) * 8, s) != hipSuccess) return MMDA_ELAUNCH;
-    rc = mmda_loss_diff(WS(m->x6), BH, B, hs, c.diff_weight, L + 1, with_grads ? WS(m->d_x6) : nullptr, WS(m->diff_work), stream);
+    else if (hipMemsetAsync(WS(w.losses), 0, sizeof(float) * 8, s) != hipSuccess) return MMDA_ELAUNCH;
+    rc = mmda_loss_diff(WS(w.x6), BH, B, hs, c.diff_weight, L + 1, with_grads ? WS(w.d_x6) : nullptr, WS(w.diff_work), stream);
     if (rc) return rc;
   }
   if (c.use_cmd_sim) {
-    if (!eager) rc = mmda_loss_cmd(WS(m->x6 + 3 * BH), BH, B, hs, c.sim_weight, L + 2, with_grads ? WS(m->d_x6 + 3 * BH) : nullptr, stream);
+    if (!eager) rc = mmda_loss_cmd(WS(w.x6 + 3 * BH), BH, B, hs, c.sim_weight, L + 2, with_grads ? WS(w.d_x6 + 3 * BH) : nullptr, stream);
   } else {
-    rc = mmda_loss_domain(WS(m->dom), B, c.sim_weight, L + 2, with_grads ? WS(m->d_dom) : nullptr, stream);
+    rc = mmda_loss_domain(WS(w.dom), B, c.sim_weight, L + 2, with_grads ? WS(w.d_dom) : nullptr, stream);
   }
   if (rc) return rc;
   // cls, conf (computed every step like solver.py:168; it only seeds gradients with use_confidNet, solver.py:180-181), recon and
@@ -1673,10 +1699,10 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
     m->misc_deferred = emo;
     return MMDA_OK;
   }
-  return mmda_loss_misc(WS(m->scores), WS(m->tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(m->d_scores) : nullptr,
-                        (with_grads && !s_cls) ? WS(m->d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext, c.conf_weight,
-                        WS(m->recon), WS(m->orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(m->d_recon) : nullptr,
-                        (with_grads && !s_recon) ? WS(m->d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
+  return mmda_loss_misc(WS(w.scores), WS(w.tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(w.d_scores) : nullptr,
+                        (with_grads && !s_cls) ? WS(w.d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext, c.conf_weight,
+                        WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(w.d_recon) : nullptr,
+                        (with_grads && !s_recon) ? WS(w.d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
                         c.use_confidNet, stream);
 }
 
@@ -1691,18 +1717,18 @@ namespace {
 // d f1 = (d f2 W2) * [f1 > 0] / (1-p), then d x1 += d f1 W1: two row-skinny launches (f1 is stored post-relu, post-dropout, so
 // f1 > 0 <=> kept and pre-activation > 0)
 void Pass::skinny_ffn_dx(bool wt) {
-  mmda_skinny_args g = sk_dxw(wt, 6 * B, hs, FFN, WS(m->d_f2), hs, WS(m->l2_wT), PP(m->l2_w), WS(m->d_f1), FFN, 0);
-  g.gate = WS(m->f1); g.ldgate = FFN; g.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
+  mmda_skinny_args g = sk_dxw(wt, 6 * B, hs, FFN, WS(w.d_f2), hs, WS(w.l2_wT), PP(p.l2_w), WS(w.d_f1), FFN, 0);
+  g.gate = WS(w.f1); g.ldgate = FFN; g.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
   sk_launch(*this, &g, 1);
-  g = sk_dxw(wt, 6 * B, FFN, hs, WS(m->d_f1), FFN, WS(m->l1_wT), PP(m->l1_w), WS(m->d_x1), hs, 1);
+  g = sk_dxw(wt, 6 * B, FFN, hs, WS(w.d_f1), FFN, WS(w.l1_wT), PP(p.l1_w), WS(w.d_x1), hs, 1);
   sk_launch(*this, &g, 1);
 }
 // d utt = d z W_proj of the three projections: one row-skinny launch
 void Pass::skinny_proj_dx(bool wt) {
   mmda_skinny_args g[3];
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i];
-    g[i] = sk_dxw(wt, B, hs, 4 * md.H, WS(m->d_z + i * BH), hs, WS(m->pwT[i]), PP(md.pw), WS(md.d_utt), 4 * md.H, 0);
+    const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
+    g[i] = sk_dxw(wt, B, hs, 4 * md.H, WS(w.d_z + i * BH), hs, WS(w.pwT[i]), PP(md.pw), WS(mw.d_utt), 4 * md.H, 0);
   }
   sk_launch(*this, g, 3);
 }
@@ -1713,23 +1739,23 @@ void Pass::bwd_fusion_fused() {
   {
     FusedBwdC f = {};
     f.B = B; f.hs = hs; f.ncls = c.ncls; f.nb = 1;
-    f.tcp = WS(m->tcp); f.scores = WS(m->scores); f.d_tcp = WS(m->d_tcp); f.d_scores = WS(m->d_scores); f.d_logits = WS(m->d_logits);
+    f.tcp = WS(w.tcp); f.scores = WS(w.scores); f.d_tcp = WS(w.d_tcp); f.d_scores = WS(w.d_scores); f.d_logits = WS(w.d_logits);
     // flag join pending: d_tcp is all zeros (no ConfidNet gradients in that mode), but cleared by the side stream's chain, which
     // this launch does not wait for -- NULL reads as zero
     if (m->fj1) f.d_tcp = nullptr;
     // the reconstruction term of stretch A's d_x6 chain, in workgroups of this launch (small batches: both sets fit the chip twice
     // over; MMDA_FUSED_SPLIT=0: inside stretch A as before)
-    if (P.rec_hoisted) { f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.rec_part = WS(m->rec_part); }
-    f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(m->head_w); f.d_hfused = WS(m->d_hfused); f.ln2 = norm2_bwd();
-    f.pg_parts = WS(m->pg_parts);
+    if (P.rec_hoisted) { f.d_recon = WS(w.d_recon); f.rec_wT = WS(w.rec_wT); f.rec_part = WS(w.rec_part); }
+    f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(p.head_w); f.d_hfused = WS(w.d_hfused); f.ln2 = norm2_bwd();
+    f.pg_parts = WS(w.pg_parts);
     rc = mmda_fused_bwd_c(&f, s);
   }
   if (P.ffn_fuse_bwd) {
     if (!rc) {
       FusedFfnBwd f = {};
-      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.d_f2 = WS(m->d_f2); f.f1 = WS(m->f1);
-      f.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f; f.l2_wT = WS(m->l2_wT); f.d_f1 = WS(m->d_f1); f.l1_wT = WS(m->l1_wT);
-      f.parts = WS(m->ffn_parts);
+      f.M = 6 * B; f.hs = hs; f.F = FFN; f.S = 32; f.d_f2 = WS(w.d_f2); f.f1 = WS(w.f1);
+      f.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f; f.l2_wT = WS(w.l2_wT); f.d_f1 = WS(w.d_f1); f.l1_wT = WS(w.l1_wT);
+      f.parts = WS(w.ffn_parts);
       rc = mmda_fused_ffn_bwd(&f, s);
     }
   } else {
@@ -1738,15 +1764,15 @@ void Pass::bwd_fusion_fused() {
   if (rc) return;
   FusedBwdA f = {};
   f.B = B; f.hs = hs; f.nhead = NHEAD; f.nb = 1;
-  if (P.ffn_fuse_bwd) { f.ffn_parts = WS(m->ffn_parts); f.n_parts = FFN / 32; f.d_x1 = WS(m->d_x1); }
+  if (P.ffn_fuse_bwd) { f.ffn_parts = WS(w.ffn_parts); f.n_parts = FFN / 32; f.d_x1 = WS(w.d_x1); }
   f.ln1 = norm1_bwd();
-  f.d_attn_out = WS(m->d_attn_out); f.out_wT = WS(m->out_wT); f.d_ctx = WS(m->d_ctx);
-  f.qkv = WS(m->qkv); f.probs = WS(m->probs); f.d_qkv = WS(m->d_qkv); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
-  f.in_wT = WS(m->in_wT); f.d_recon = WS(m->d_recon); f.rec_wT = WS(m->rec_wT); f.x6 = WS(m->x6); f.d_x6 = WS(m->d_x6);
-  if (P.rec_hoisted) f.rec_part = WS(m->rec_part);
-  f.priv_wT = WS(m->priv_wT); f.sh_wT = WS(m->sh_wT); f.d_orig = WS(m->d_orig);
+  f.d_attn_out = WS(w.d_attn_out); f.out_wT = WS(w.out_wT); f.d_ctx = WS(w.d_ctx);
+  f.qkv = WS(w.qkv); f.probs = WS(w.probs); f.d_qkv = WS(w.d_qkv); f.p_tf = p_tf; f.seed = seed; f.site_attn = SITE_ATTN;
+  f.in_wT = WS(w.in_wT); f.d_recon = WS(w.d_recon); f.rec_wT = WS(w.rec_wT); f.x6 = WS(w.x6); f.d_x6 = WS(w.d_x6);
+  if (P.rec_hoisted) f.rec_part = WS(w.rec_part);
+  f.priv_wT = WS(w.priv_wT); f.sh_wT = WS(w.sh_wT); f.d_orig = WS(w.d_orig);
   for (int i = 0; i < 3; ++i) f.lnp[i] = proj_ln_bwd(i);
-  f.pg_parts = WS(m->pg_parts);
+  f.pg_parts = WS(w.pg_parts);
   if (m->fj1) {
     // Waiting workgroups hold their CU's LDS (104 KB each): with one on every CU the side stream's kernels could not start, and
     // the wait would never end -- on the device only while the stretch leaves most of the chip free (P.fj_device); otherwise the
@@ -1764,9 +1790,9 @@ void Pass::bwd_fusion_fused() {
 void Pass::bwd_fusion_skinny() {
   const bool wt = m->wT_valid != 0;                   // K-major weight copies from this step's forward (side stream, joined there)
   mmda_skinny_args g[8];
-  rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
+  rc = mmda_heads_bwd(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
                         s);
-  g[0] = sk_dxw(wt, B, NC, 6 * hs, WS(m->d_logits), NC, WS(m->head_wT), PP(m->head_w), WS(m->d_hfused), 6 * hs, 0);
+  g[0] = sk_dxw(wt, B, NC, 6 * hs, WS(w.d_logits), NC, WS(w.head_wT), PP(p.head_w), WS(w.d_hfused), 6 * hs, 0);
   sk_launch(*this, g, 1);
   const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
   if (!rc) rc = mmda_layernorm_bwd(&l2, s);
@@ -1774,17 +1800,17 @@ void Pass::bwd_fusion_skinny() {
   // norm1 + self-attention
   if (!rc) rc = mmda_layernorm_bwd(&l1, s);
   int n = 0;
-  g[n++] = sk_dxw(wt, 6 * B, hs, hs, WS(m->d_attn_out), hs, WS(m->out_wT), PP(m->out_w), WS(m->d_ctx), hs, 0);
-  if (!c.use_cmd_sim) g[n++] = sk_dxw(wt, 3 * B, 3, hs, WS(m->d_dom), 3, WS(m->d2_wT), PP(m->d2_w), WS(m->d_dom_h), hs, 0);
+  g[n++] = sk_dxw(wt, 6 * B, hs, hs, WS(w.d_attn_out), hs, WS(w.out_wT), PP(p.out_w), WS(w.d_ctx), hs, 0);
+  if (!c.use_cmd_sim) g[n++] = sk_dxw(wt, 3 * B, 3, hs, WS(w.d_dom), 3, WS(w.d2_wT), PP(p.d2_w), WS(w.d_dom_h), hs, 0);
   sk_launch(*this, g, n);
-  if (!rc) rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, s);
+  if (!rc) rc = mmda_attn_bwd(WS(w.qkv), WS(w.probs), WS(w.d_ctx), S6, B, hs, NHEAD, WS(w.d_qkv), p_tf, seed, SITE_ATTN, s);
   // adversarial branch: the REVERSED gradient into the shared codes (functions.py:17-21)
   if (!c.use_cmd_sim) {
     if (!rc) {
       const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, true);
-      rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
+      rc = mmda_act_dropout_bwd_p(WS(w.d_dom_h), WS(w.dom_z), WS(w.d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
-    g[0] = sk_dxw(wt, 3 * B, hs, hs, WS(m->d_dom_z), hs, WS(m->d1_wT), PP(m->d1_w), WS(m->d_x6 + 3 * BH), hs, 1);
+    g[0] = sk_dxw(wt, 3 * B, hs, hs, WS(w.d_dom_z), hs, WS(w.d1_wT), PP(p.d1_w), WS(w.d_x6 + 3 * BH), hs, 1);
     g[0].alpha = -c.reverse_grad_weight;
     sk_launch(*this, g, 1);
   }
@@ -1792,17 +1818,17 @@ void Pass::bwd_fusion_skinny() {
   // reconstruction's input gradients (the latter flows into BOTH private and shared) and the sigmoid backward, six problems
   for (int j = 0; j < 6; ++j) {
     const int i = j % 3;
-    g[j] = sk_dxw(wt, B, 3 * hs, hs, WS(m->d_qkv + (int64_t)j * B * 3 * hs), 3 * hs, WS(m->in_wT), PP(m->in_w), WS(m->d_x6 + j * BH), hs, 1);
-    g[j].K2 = hs; g[j].A_2nd = WS(m->d_recon + i * BH); g[j].lda_2nd = hs; g[j].ldb_2nd = hs;
-    g[j].B_2nd = wt ? WS(m->rec_wT + (int64_t)i * hs * hs) : PP(m->rec_w + (int64_t)i * hs * hs);
-    g[j].dsig = WS(m->x6 + j * BH); g[j].lddsig = hs;
+    g[j] = sk_dxw(wt, B, 3 * hs, hs, WS(w.d_qkv + (int64_t)j * B * 3 * hs), 3 * hs, WS(w.in_wT), PP(p.in_w), WS(w.d_x6 + j * BH), hs, 1);
+    g[j].K2 = hs; g[j].A_2nd = WS(w.d_recon + i * BH); g[j].lda_2nd = hs; g[j].ldb_2nd = hs;
+    g[j].B_2nd = wt ? WS(w.rec_wT + (int64_t)i * hs * hs) : PP(p.rec_w + (int64_t)i * hs * hs);
+    g[j].dsig = WS(w.x6 + j * BH); g[j].lddsig = hs;
   }
   sk_launch(*this, g, 6);
   // d_orig[i] += d_private[i] W_priv[i] + d_shared[i] W_shared
   for (int i = 0; i < 3; ++i) {
-    g[i] = sk_dxw(wt, B, hs, hs, WS(m->d_x6 + i * BH), hs, WS(m->priv_wT + (int64_t)i * hs * hs), PP(m->priv_w + (int64_t)i * hs * hs),
-                  WS(m->d_orig + i * BH), hs, 1);
-    g[i].K2 = hs; g[i].A_2nd = WS(m->d_x6 + (3 + i) * BH); g[i].lda_2nd = hs; g[i].B_2nd = wt ? WS(m->sh_wT) : PP(m->sh_w); g[i].ldb_2nd = hs;
+    g[i] = sk_dxw(wt, B, hs, hs, WS(w.d_x6 + i * BH), hs, WS(w.priv_wT + (int64_t)i * hs * hs), PP(p.priv_w + (int64_t)i * hs * hs),
+                  WS(w.d_orig + i * BH), hs, 1);
+    g[i].K2 = hs; g[i].A_2nd = WS(w.d_x6 + (3 + i) * BH); g[i].lda_2nd = hs; g[i].B_2nd = wt ? WS(w.sh_wT) : PP(p.sh_w); g[i].ldb_2nd = hs;
   }
   sk_launch(*this, g, 3);
   // projections
@@ -1817,49 +1843,49 @@ void Pass::bwd_fusion_skinny() {
 // ... many rows: the tiled generic kernel
 void Pass::bwd_fusion_tiled() {
   // heads
-  rc = mmda_heads_bwd(WS(m->tcp), WS(m->scores), WS(m->d_tcp), WS(m->d_scores), B, c.ncls, WS(m->d_logits), p_cls, seed, SITE_CLS,
+  rc = mmda_heads_bwd(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
                         s);
-  lin_dx(*this, fmode, B, NC, 6 * hs, WS(m->d_logits), PP(m->head_w), WS(m->d_hfused), 0);
+  lin_dx(*this, fmode, B, NC, 6 * hs, WS(w.d_logits), PP(p.head_w), WS(w.d_hfused), 0);
   // norm2 + FFN
   const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
   if (!rc) rc = mmda_layernorm_bwd(&l2, s);
   {
     // d f1 = (d f2 W2) * [f1 > 0] / (1-p): f1 is stored post-relu, post-dropout, so f1 > 0 <=> kept and pre-activation > 0
     mmda_gemm_args e = {};
-    e.gate = WS(m->f1); e.ldgate = FFN; e.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
-    gemm(*this, fmode, 0, 0, 6 * B, FFN, hs, WS(m->d_f2), hs, PP(m->l2_w), FFN, WS(m->d_f1), FFN, nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, &e);
+    e.gate = WS(w.f1); e.ldgate = FFN; e.gate_scale = p_tf > 0.f ? 1.f / (1.f - p_tf) : 1.f;
+    gemm(*this, fmode, 0, 0, 6 * B, FFN, hs, WS(w.d_f2), hs, PP(p.l2_w), FFN, WS(w.d_f1), FFN, nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, &e);
   }
-  lin_dx(*this, fmode, 6 * B, FFN, hs, WS(m->d_f1), PP(m->l1_w), WS(m->d_x1), 1);
+  lin_dx(*this, fmode, 6 * B, FFN, hs, WS(w.d_f1), PP(p.l1_w), WS(w.d_x1), 1);
   // norm1 + self-attention
   if (!rc) rc = mmda_layernorm_bwd(&l1, s);
-  lin_dx(*this, fmode, 6 * B, hs, hs, WS(m->d_attn_out), PP(m->out_w), WS(m->d_ctx), 0);
-  if (!rc) rc = mmda_attn_bwd(WS(m->qkv), WS(m->probs), WS(m->d_ctx), S6, B, hs, NHEAD, WS(m->d_qkv), p_tf, seed, SITE_ATTN, s);
-  lin_dx(*this, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), PP(m->in_w), WS(m->d_x6), 1);
+  lin_dx(*this, fmode, 6 * B, hs, hs, WS(w.d_attn_out), PP(p.out_w), WS(w.d_ctx), 0);
+  if (!rc) rc = mmda_attn_bwd(WS(w.qkv), WS(w.probs), WS(w.d_ctx), S6, B, hs, NHEAD, WS(w.d_qkv), p_tf, seed, SITE_ATTN, s);
+  lin_dx(*this, fmode, 6 * B, 3 * hs, hs, WS(w.d_qkv), PP(p.in_w), WS(w.d_x6), 1);
   // adversarial branch: the REVERSED gradient into the shared codes (functions.py:17-21)
   if (!c.use_cmd_sim) {
-    lin_dx(*this, fmode, 3 * B, 3, hs, WS(m->d_dom), PP(m->d2_w), WS(m->d_dom_h), 0);
+    lin_dx(*this, fmode, 3 * B, 3, hs, WS(w.d_dom), PP(p.d2_w), WS(w.d_dom_h), 0);
     if (!rc) {
       const mmda_act_params ap = act_params(m, m->training, seed, SITE_RRELU_DISC, true);
-      rc = mmda_act_dropout_bwd_p(WS(m->d_dom_h), WS(m->dom_z), WS(m->d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
+      rc = mmda_act_dropout_bwd_p(WS(w.d_dom_h), WS(w.dom_z), WS(w.d_dom_z), 3 * BH, c.act, &ap, p_cls, seed, SITE_DISC, s);
     }
     mmda_gemm_args e = {};
     e.alpha = -c.reverse_grad_weight;
-    gemm(*this, fmode, 0, 0, 3 * B, hs, hs, WS(m->d_dom_z), hs, PP(m->d1_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
+    gemm(*this, fmode, 0, 0, 3 * B, hs, hs, WS(w.d_dom_z), hs, PP(p.d1_w), hs, WS(w.d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
   }
   // reconstruct: d(private+shared) goes to both halves of d_x6
-  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
-  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_recon), hs, PP(m->rec_w), hs, WS(m->d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 3, BH,
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(w.d_recon), hs, PP(p.rec_w), hs, WS(w.d_x6), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(w.d_recon), hs, PP(p.rec_w), hs, WS(w.d_x6 + 3 * BH), hs, nullptr, nullptr, 1, 0, 3, BH,
        (int64_t)hs * hs, BH);
   // sigmoid of private/shared
-  if (!rc) rc = mmda_sigmoid_bwd_inplace(WS(m->d_x6), WS(m->x6), 6 * BH, s);
-  gemm(*this, fmode, 0, 0, B, hs, hs, WS(m->d_x6), hs, PP(m->priv_w), hs, WS(m->d_orig), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
-  lin_dx(*this, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), PP(m->sh_w), WS(m->d_orig), 1);
+  if (!rc) rc = mmda_sigmoid_bwd_inplace(WS(w.d_x6), WS(w.x6), 6 * BH, s);
+  gemm(*this, fmode, 0, 0, B, hs, hs, WS(w.d_x6), hs, PP(p.priv_w), hs, WS(w.d_orig), hs, nullptr, nullptr, 1, 0, 3, BH, (int64_t)hs * hs, BH);
+  lin_dx(*this, fmode, 3 * B, hs, hs, WS(w.d_x6 + 3 * BH), PP(p.sh_w), WS(w.d_orig), 1);
   // projections
   for (int i = 0; i < 3 && !rc; ++i) {
-    Mod& md = m->mod[i];
+    const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
     const mmda_ln_bwd_args l = proj_ln_bwd(i);
     rc = mmda_layernorm_bwd(&l, s);
-    if (!P.enc_cut) lin_dx(*this, fmode, B, hs, 4 * md.H, WS(m->d_z + i * BH), PP(md.pw), WS(md.d_utt), 0);
+    if (!P.enc_cut) lin_dx(*this, fmode, B, hs, 4 * md.H, WS(w.d_z + i * BH), PP(md.pw), WS(mw.d_utt), 0);
   }
 }
 
@@ -1867,25 +1893,25 @@ void Pass::bwd_fusion_tiled() {
 // projections 0-2.  One grouped launch on the side stream (bwd_side_chain) once the dX chain, the critical path, is through.
 void Pass::fusion_wgrads() {
   deferring = true;
-  lin_dw(*this, fmode, B, NC, 6 * hs, WS(m->d_logits), WS(m->hfused), GG(m->head_w), GG(m->head_b));
-  lin_dw(*this, fmode, 6 * B, hs, FFN, WS(m->d_f2), WS(m->f1), GG(m->l2_w), GG(m->l2_b));
-  lin_dw(*this, fmode, 6 * B, FFN, hs, WS(m->d_f1), WS(m->x1), GG(m->l1_w), GG(m->l1_b));
-  lin_dw(*this, fmode, 6 * B, hs, hs, WS(m->d_attn_out), WS(m->ctx), GG(m->out_w), GG(m->out_b));
-  lin_dw(*this, fmode, 6 * B, 3 * hs, hs, WS(m->d_qkv), WS(m->x6), GG(m->in_w), GG(m->in_b));
+  lin_dw(*this, fmode, B, NC, 6 * hs, WS(w.d_logits), WS(w.hfused), GG(p.head_w), GG(p.head_b));
+  lin_dw(*this, fmode, 6 * B, hs, FFN, WS(w.d_f2), WS(w.f1), GG(p.l2_w), GG(p.l2_b));
+  lin_dw(*this, fmode, 6 * B, FFN, hs, WS(w.d_f1), WS(w.x1), GG(p.l1_w), GG(p.l1_b));
+  lin_dw(*this, fmode, 6 * B, hs, hs, WS(w.d_attn_out), WS(w.ctx), GG(p.out_w), GG(p.out_b));
+  lin_dw(*this, fmode, 6 * B, 3 * hs, hs, WS(w.d_qkv), WS(w.x6), GG(p.in_w), GG(p.in_b));
   if (!c.use_cmd_sim) {
-    lin_dw(*this, fmode, 3 * B, 3, hs, WS(m->d_dom), WS(m->dom_h), GG(m->d2_w), GG(m->d2_b));
-    lin_dw(*this, fmode, 3 * B, hs, hs, WS(m->d_dom_z), WS(m->x6 + 3 * BH), GG(m->d1_w), GG(m->d1_b));
+    lin_dw(*this, fmode, 3 * B, 3, hs, WS(w.d_dom), WS(w.dom_h), GG(p.d2_w), GG(p.d2_b));
+    lin_dw(*this, fmode, 3 * B, hs, hs, WS(w.d_dom_z), WS(w.x6 + 3 * BH), GG(p.d1_w), GG(p.d1_b));
   }
   mmda_gemm_args e = {};
-  e.bias_grad = GG(m->rec_b);      // strideBias = hs: one bias gradient per batched problem
-  gemm(*this, fmode, 1, 0, hs, hs, B, WS(m->d_recon), hs, WS(m->rsum), hs, GG(m->rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
+  e.bias_grad = GG(p.rec_b);      // strideBias = hs: one bias gradient per batched problem
+  gemm(*this, fmode, 1, 0, hs, hs, B, WS(w.d_recon), hs, WS(w.rsum), hs, GG(p.rec_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
        hs, &e);
-  e.bias_grad = GG(m->priv_b);
-  gemm(*this, fmode, 1, 0, hs, hs, B, WS(m->d_x6), hs, WS(m->orig), hs, GG(m->priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
+  e.bias_grad = GG(p.priv_b);
+  gemm(*this, fmode, 1, 0, hs, hs, B, WS(w.d_x6), hs, WS(w.orig), hs, GG(p.priv_w), hs, nullptr, nullptr, 1, 0, 3, BH, BH, (int64_t)hs * hs,
        hs, &e);
-  lin_dw(*this, fmode, 3 * B, hs, hs, WS(m->d_x6 + 3 * BH), WS(m->orig), GG(m->sh_w), GG(m->sh_b));
+  lin_dw(*this, fmode, 3 * B, hs, hs, WS(w.d_x6 + 3 * BH), WS(w.orig), GG(p.sh_w), GG(p.sh_b));
   for (int i = 0; i < 3; ++i)
-    lin_dw(*this, fmode, B, hs, 4 * m->mod[i].H, WS(m->d_z + i * BH), WS(m->mod[i].utt), GG(m->mod[i].pw), GG(m->mod[i].pb));
+    lin_dw(*this, fmode, B, hs, 4 * p.mod[i].H, WS(w.d_z + i * BH), WS(w.mod[i].utt), GG(p.mod[i].pw), GG(p.mod[i].pb));
   deferring = false;
 }
 
@@ -1896,17 +1922,17 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   rc = side_fork(m, s, &ss);
   if (!rc && m->misc_deferred) {
     // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
-    rc = mmda_loss_misc(WS(m->scores), WS(m->tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
-                          WS(m->recon), WS(m->orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(m->losses), c.diff_weight,
+    rc = mmda_loss_misc(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
+                          WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
                           c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, ss);
     m->misc_deferred = nullptr;
   }
-  if (!rc && P.skinny) rc = mmda_add(WS(m->x6), WS(m->x6 + 3 * BH), WS(m->rsum), 3 * BH, ss);
-  // the sorted id list of the embedding scatter (see mmda_misa::esort); MMDA_SORT_EARLY=0: made where the scatter runs
+  if (!rc && P.skinny) rc = mmda_add(WS(w.x6), WS(w.x6 + 3 * BH), WS(w.rsum), 3 * BH, ss);
+  // the sorted id list of the embedding scatter (see mmda_misa::esort_valid); MMDA_SORT_EARLY=0: made where the scatter runs
   m->esort_valid = 0;
   // (sparse mode without an optimizer step behind this backward: the rows update runs later, in mmda_misa_adam_step, and sorts there)
   if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !early)) {
-    rc = mmda_embed_sort_ids(t_ids, B * m->T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(m->esort)), ss);
+    rc = mmda_embed_sort_ids(t_ids, B * w.T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(w.esort)), ss);
     if (!rc && ss != s) {
       hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
       if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
@@ -1915,15 +1941,15 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   }
   if (!rc && pg_pending) {
     // gamma / beta gradients of the five LayerNorms the fused stretches walked: per-sample partials added in sample order
-    float* dg[FUSED_PG_SLOTS] = {GG(m->n2_w), GG(m->n1_w), GG(m->mod[0].plw), GG(m->mod[1].plw), GG(m->mod[2].plw)};
-    float* db[FUSED_PG_SLOTS] = {GG(m->n2_b), GG(m->n1_b), GG(m->mod[0].plb), GG(m->mod[1].plb), GG(m->mod[2].plb)};
-    rc = mmda_fused_pg_finish(WS(m->pg_parts), B, hs, dg, db, ss);
+    float* dg[FUSED_PG_SLOTS] = {GG(p.n2_w), GG(p.n1_w), GG(p.mod[0].plw), GG(p.mod[1].plw), GG(p.mod[2].plw)};
+    float* db[FUSED_PG_SLOTS] = {GG(p.n2_b), GG(p.n1_b), GG(p.mod[0].plb), GG(p.mod[1].plb), GG(p.mod[2].plb)};
+    rc = mmda_fused_pg_finish(WS(w.pg_parts), B, hs, dg, db, ss);
   }
   if (!rc && !deferred.empty()) rc = mmda_gemm_grouped(deferred.data(), (int)deferred.size(), ss);
   deferred.clear();
   // the bf16 operand copies that only the weight-gradient GEMMs read (hseq of both layers, nt form: transposed layer-2 inputs): here,
   // where the side stream is idle beside the layer-2 recurrence, instead of in front of the loss kernels of the forward pass
-  if (!rc && P.bfg && m->T > 0 && !P.enc_cut) {           // (a cut step runs no encoder weight-gradient GEMM)
+  if (!rc && P.bfg && w.T > 0 && !P.enc_cut) {           // (a cut step runs no encoder weight-gradient GEMM)
     mmda_convert_job cj[16];
     const int nj = backward_only_jobs(m, cj);
     rc = mmda_convert_bf16(cj, nj, ss);
@@ -1944,7 +1970,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
   // as bf16: every consumer of dG in this mode is a bf16 GEMM (the transposed operand is re-laid-out from it).  The other
   // kernels (barrier form: H > 320, ablation switches) write fp32 `gates` as before.
   if (P.kdg)
-    for (int i = 0; i < 3; ++i) { desc[i].dg_bf16 = WS(m->mod[i].rnn[l].dgb); desc[i].dg_bf16_only = 1; }
+    for (int i = 0; i < 3; ++i) { desc[i].dg_bf16 = WS(w.mod[i].rnn[l].dgb); desc[i].dg_bf16_only = 1; }
   m->epoch += (unsigned)T + 2u;
   // the forward pass skipped the streaming backward packing because the resident-weights kernels were going to run: they must
   if (!P.want_b && !mmda_lstm_resident_applicable(mode, 3, desc, B, T, 1)) { rc = MMDA_EINVAL; return; }
@@ -1962,11 +1988,11 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
   const bool frozen = P.embed_update == EU_FROZEN;            // no gradient w.r.t. the embedding rows: text layer 1 has no dX product
   mmda_convert_job dgj[3];
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+    const RnnP& r = p.mod[i].rnn[l]; const ModW& mw = w.mod[i]; const RnnW& rw = mw.rnn[l];
     const bool plain = (l == 1 || (i == 0 && !frozen)) && !P.kdg;
-    dgj[i] = mmda_convert_job{WS(md.gates[l]), 8 * r.H, R, 8 * r.H, nullptr, plain ? WS(r.dgb) : nullptr, plain ? r.ldG : 0, WS(r.dgbT),
-                              m->ldR};
-    if (P.kdg) { dgj[i].src = WS(r.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
+    dgj[i] = mmda_convert_job{WS(mw.gates[l]), 8 * r.H, R, 8 * r.H, nullptr, plain ? WS(rw.dgb) : nullptr, plain ? r.ldG : 0, WS(rw.dgbT),
+                              w.ldR};
+    if (P.kdg) { dgj[i].src = WS(rw.dgb); dgj[i].ld = r.ldG; dgj[i].src_bf16 = 1; }
   }
   const bool tn = P.tn_wgrad;            // weight gradients straight from dG / inputs / hseq as they lie (no dG^T); implies kdg
   const bool dg_on_side = P.kdg && l == 1 && m->use_side && !tn;
@@ -1977,67 +2003,67 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
   deferring = (l == 1);
   group_begin(*this);
   for (int i = 0; i < 3; ++i) {
-    Mod& md = m->mod[i]; Rnn& r = md.rnn[l];
+    const RnnP& r = p.mod[i].rnn[l]; const ModW& mw = w.mod[i]; const RnnW& rw = mw.rnn[l];
     const int H = r.H, G8 = 8 * H;
-    const float* dG = WS(md.gates[l]);
-    const float* in = l == 0 ? xin[i] : WS(md.normed);
+    const float* dG = WS(mw.gates[l]);
+    const float* in = l == 0 ? xin[i] : WS(mw.normed);
     std::vector<mmda_gemm_bf16_args>& wq = (l == 1) ? bside : bmain;      // weight gradients: side stream for layer 2
-    const unsigned short* dgT = reinterpret_cast<const unsigned short*>(WS(r.dgbT));
-    const unsigned short* hT = reinterpret_cast<const unsigned short*>(WS(r.hbT));
+    const unsigned short* dgT = reinterpret_cast<const unsigned short*>(WS(rw.dgbT));
+    const unsigned short* hT = reinterpret_cast<const unsigned short*>(WS(rw.hbT));
     // dW_ih (both directions stacked); db_ih = db_hh = column sums of dG ride along as a virtual ones-column
     if (bfg) {
       mmda_gemm_bf16_args g = {};
-      g.M = G8; g.N = r.D; g.K = R; g.A = dgT; g.lda = m->ldR; g.B = WS(r.xbT); g.ldb = m->ldR; g.C = gW_ih(m, r); g.ldc = r.D;
-      g.accumulate = 1; g.bias_grad = gB_ih(m, r); g.bias_grad2 = gB_hh(m, r); g.perm_m_H = P.gm ? H : 0;
-      if (tn) { g.tn = 1; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.xb); g.ldb = r.ldD; }
+      g.M = G8; g.N = r.D; g.K = R; g.A = dgT; g.lda = w.ldR; g.B = WS(rw.xbT); g.ldb = w.ldR; g.C = gW_ih(m, i, l); g.ldc = r.D;
+      g.accumulate = 1; g.bias_grad = gB_ih(m, i, l); g.bias_grad2 = gB_hh(m, i, l); g.perm_m_H = P.gm ? H : 0;
+      if (tn) { g.tn = 1; g.A = WS(rw.dgb); g.lda = r.ldG; g.B = WS(rw.xb); g.ldb = r.ldD; }
       wq.push_back(g);
     } else {
       mmda_gemm_args e = {};
-      e.bias_grad = gB_ih(m, r); e.bias_grad2 = gB_hh(m, r);
-      gemm(*this, mode, 1, 0, G8, r.D, R, dG, G8, in, r.D, gW_ih(m, r), r.D, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
+      e.bias_grad = gB_ih(m, i, l); e.bias_grad2 = gB_hh(m, i, l);
+      gemm(*this, mode, 1, 0, G8, r.D, R, dG, G8, in, r.D, gW_ih(m, i, l), r.D, nullptr, nullptr, 1, 0, 1, 0, 0, 0, 0, &e);
     }
     // dW_hh: forward direction pairs dG[t] with h[t-1]; reverse direction pairs dG[t] with h[t+1] (zero past len)
     if (T > 1) {
       if (bf_hh) {
         mmda_gemm_bf16_args g = {};
-        g.M = 4 * H; g.N = H; g.K = (T - 1) * B; g.lda = m->ldR; g.ldb = m->ldR; g.ldc = H; g.accumulate = 1;
+        g.M = 4 * H; g.N = H; g.K = (T - 1) * B; g.lda = w.ldR; g.ldb = w.ldR; g.ldc = H; g.accumulate = 1;
         g.perm_m_H = P.gm ? H : 0;
         if (tn) {
           // rows of dG / hseq are (t, b): the forward direction pairs rows t B + b of dG with rows (t - 1) B + b of h, the reverse
           // direction rows t B + b with rows (t + 1) B + b
-          const unsigned short* dg = reinterpret_cast<const unsigned short*>(WS(r.dgb));
-          const unsigned short* h0 = reinterpret_cast<const unsigned short*>(WS(r.hbp[0]));
-          const unsigned short* h1 = reinterpret_cast<const unsigned short*>(WS(r.hbp[1]));
+          const unsigned short* dg = reinterpret_cast<const unsigned short*>(WS(rw.dgb));
+          const unsigned short* h0 = reinterpret_cast<const unsigned short*>(WS(rw.hbp[0]));
+          const unsigned short* h1 = reinterpret_cast<const unsigned short*>(WS(rw.hbp[1]));
           g.tn = 1; g.lda = r.ldG; g.ldb = r.ldH;
-          g.A = dg + (int64_t)B * r.ldG; g.B = h0; g.C = gW_hh(m, r, 0);
+          g.A = dg + (int64_t)B * r.ldG; g.B = h0; g.C = gW_hh(m, i, l, 0);
           wq.push_back(g);
-          g.A = dg + 4 * H; g.B = h1 + (int64_t)B * r.ldH; g.C = gW_hh(m, r, 1);
+          g.A = dg + 4 * H; g.B = h1 + (int64_t)B * r.ldH; g.C = gW_hh(m, i, l, 1);
           wq.push_back(g);
         } else {
-          g.A = dgT + B; g.B = hT; g.C = gW_hh(m, r, 0);
+          g.A = dgT + B; g.B = hT; g.C = gW_hh(m, i, l, 0);
           wq.push_back(g);
-          g.A = dgT + (int64_t)4 * H * m->ldR; g.B = hT + (int64_t)H * m->ldR + B; g.C = gW_hh(m, r, 1);
+          g.A = dgT + (int64_t)4 * H * w.ldR; g.B = hT + (int64_t)H * w.ldR + B; g.C = gW_hh(m, i, l, 1);
           wq.push_back(g);
         }
       } else {
-        const float* hs_ = WS(md.hseq[l]);
-        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + (int64_t)B * G8, G8, hs_, 2 * H, gW_hh(m, r, 0), H, nullptr, nullptr, 1);
-        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + 4 * H, G8, hs_ + (int64_t)B * 2 * H + H, 2 * H, gW_hh(m, r, 1), H, nullptr,
+        const float* hs_ = WS(mw.hseq[l]);
+        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + (int64_t)B * G8, G8, hs_, 2 * H, gW_hh(m, i, l, 0), H, nullptr, nullptr, 1);
+        gemm(*this, mode, 1, 0, 4 * H, H, (T - 1) * B, dG + 4 * H, G8, hs_ + (int64_t)B * 2 * H + H, 2 * H, gW_hh(m, i, l, 1), H, nullptr,
              nullptr, 1);
       }
     }
     // d(normed) = dG W_ih (layer 2) / d(embedding rows) (text layer 1)
     if (l == 1 || i == 0) {
-      float* dst = l == 1 ? WS(md.d_normed) : WS(md.d_x);
+      float* dst = l == 1 ? WS(mw.d_normed) : WS(mw.d_x);
       const bool skip = l == 0 && frozen;                    // frozen table: the text layer-1 dX product is not run
       if (bfg) {
         mmda_gemm_bf16_args g = {};
-        g.M = R; g.N = r.D; g.K = G8; g.A = WS(r.dgb); g.lda = r.ldG; g.B = WS(r.wbT); g.ldb = r.ldG; g.C = dst; g.ldc = r.D;
+        g.M = R; g.N = r.D; g.K = G8; g.A = WS(rw.dgb); g.lda = r.ldG; g.B = WS(rw.wbT); g.ldb = r.ldG; g.C = dst; g.ldc = r.D;
         if (!skip) bmain.push_back(g);
       } else {
         // (left out of a frozen step's group, but counted when its split-K is sized: the weight gradients beside it keep their slices)
         absent_next = skip;
-        gemm(*this, mode, 0, 0, R, r.D, G8, dG, G8, rW_ih(m, r), r.D, dst, r.D);
+        gemm(*this, mode, 0, 0, R, r.D, G8, dG, G8, rW_ih(m, i, l), r.D, dst, r.D);
       }
     }
   }
@@ -2050,28 +2076,28 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // recurrent kernel); gamma/beta gradients and this layer's weight-gradient GEMMs on the side stream underneath it
     mmda_ln_bwd_args lb[3];
     for (int i = 0; i < 3; ++i) {
-      Mod& md = m->mod[i];
+      const ModP& md = p.mod[i]; const ModW& mw = w.mod[i];
       lb[i] = mmda_ln_bwd_args{};
-      lb[i].rows = R; lb[i].n = 2 * md.H; lb[i].dy = WS(md.d_normed); lb[i].x = WS(md.hseq[0]); lb[i].gamma = PP(md.ln_w);
-      lb[i].mean = WS(md.ln_mean); lb[i].rstd = WS(md.ln_rstd); lb[i].d_x = WS(md.d_hseq1);
+      lb[i].rows = R; lb[i].n = 2 * md.H; lb[i].dy = WS(mw.d_normed); lb[i].x = WS(mw.hseq[0]); lb[i].gamma = PP(md.ln_w);
+      lb[i].mean = WS(mw.ln_mean); lb[i].rstd = WS(mw.ln_rstd); lb[i].d_x = WS(mw.d_hseq1);
     }
     // (the input-gradient launch goes out BEFORE the fork: it reads the LayerNorm weights, which the early optimizer step below may
     // update on the side stream -- the fork orders the side stream behind it)
     // 16-byte form (norm.hip): the d_x launch leaves the gamma / beta gradients as per-block partials on its way (it reads dy and x
     // anyway) and the side stream only adds them up -- instead of a second pass over dy and x there (100 us at B = 256)
     const bool ln_split = mmda_ln_bwd_parts_applies(lb, 3) &&
-                          mmda_ln_parts_floats(lb, 3) <= (int64_t)512 * 2 * 2 * (m->mod[0].H + m->mod[1].H + m->mod[2].H);
+                          mmda_ln_parts_floats(lb, 3) <= (int64_t)512 * 2 * 2 * (p.mod[0].H + p.mod[1].H + p.mod[2].H);
     if (ln_split) {
-      for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); }
-      rc = mmda_ln_bwd_parts(lb, 3, WS(m->ln_parts), s);
+      for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(p.mod[i].ln_w); lb[i].dbeta = GG(p.mod[i].ln_b); }
+      rc = mmda_ln_bwd_parts(lb, 3, WS(w.ln_parts), s);
     } else {
       rc = mmda_layernorm_bwd_multi(lb, 3, s);
     }
     void* ss = nullptr;
     if (!rc) rc = side_fork(m, s, &ss);
-    for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(m->mod[i].ln_w); lb[i].dbeta = GG(m->mod[i].ln_b); if (!ln_split) lb[i].d_x = nullptr; }
+    for (int i = 0; i < 3; ++i) { lb[i].dgamma = GG(p.mod[i].ln_w); lb[i].dbeta = GG(p.mod[i].ln_b); if (!ln_split) lb[i].d_x = nullptr; }
     if (!rc && dg_on_side) rc = mmda_convert_bf16(dgj, 3, ss);
-    if (!rc) rc = ln_split ? mmda_ln_parts_finish(lb, 3, WS(m->ln_parts), ss) : mmda_layernorm_param_grads(lb, 3, ss);
+    if (!rc) rc = ln_split ? mmda_ln_parts_finish(lb, 3, WS(w.ln_parts), ss) : mmda_layernorm_param_grads(lb, 3, ss);
     if (!rc && !deferred.empty()) rc = mmda_gemm_grouped(deferred.data(), (int)deferred.size(), ss);
     const bool l2_early = !bside.empty();
     if (!rc && l2_early) { rc = mmda_gemm_bf16_grouped(bside.data(), (int)bside.size(), ss); bside.clear(); }
@@ -2082,7 +2108,7 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     if (rc) return;
     if (!m->ev_early && hipEventCreateWithFlags(&m->ev_early, hipEventDisableTiming) != hipSuccess) rc = MMDA_ELAUNCH;
     if (!rc && hipEventRecord(m->ev_early, (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
-    m->early_floats = (l2_early && !is_gru(m) && P.bfg) ? m->rnn1_begin : m->rnn2_begin;
+    m->early_floats = (l2_early && !is_gru(m) && P.bfg) ? p.rnn1_begin : p.rnn2_begin;
     m->early_valid = 1;
     // Single-GPU fused step: clip + Adam of that prefix right here, beside the layer-1 recurrence (nothing issued after this
     // point reads those fp32 parameters: the remaining GEMMs of a bf16 step read bf16 copies made in the forward pass, and in
@@ -2107,13 +2133,13 @@ const unsigned* Pass::take_sorted() {
     if (hipGetLastError() != hipSuccess) rc = MMDA_ELAUNCH;
   }
   m->esort_valid = 0;
-  return reinterpret_cast<const unsigned*>(WS(m->esort));
+  return reinterpret_cast<const unsigned*>(WS(w.esort));
 }
 
 // The text rows' end of the pass, behind layer 1: d_x_t goes where embed_update sends it.  Sparse and deferred tables take their rows update
 // here, behind an optimizer step only (`early`); otherwise the pass stops at d_x_t, the rows stay pending for mmda_misa_adam_step.
 void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
-  const float* dx = WS(m->mod[0].d_x);
+  const float* dx = WS(w.mod[0].d_x);
   if (P.embed_update == EU_SPARSE || P.embed_deferred) {
     m->eu.take();
     if (!early) { m->eu.set(t_ids, lengths); return; }
@@ -2121,7 +2147,7 @@ void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
   if (P.embed_update == EU_SPARSE) {
     // SparseAdam on the rows the batch touches (common.h)
     SparseAdamArgs ad;
-    rc = mmda_sparse_adam_args(&ad, PP(m->embed), m->M1 ? m->M1 + m->embed : nullptr, m->V1 ? m->V1 + m->embed : nullptr, c.vocab, early->lr,
+    rc = mmda_sparse_adam_args(&ad, PP(p.embed), m->M1 ? m->M1 + p.embed : nullptr, m->V1 ? m->V1 + p.embed : nullptr, c.vocab, early->lr,
                                m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale, early->step);
     if (rc) return;
     const unsigned* sorted = take_sorted();
@@ -2139,8 +2165,8 @@ void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
     // the gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     const unsigned* sorted = take_sorted();
     if (rc) return;
-    if (sorted) rc = mmda_embed_scatter_presorted(GG(m->embed), sorted, R, c.d_t, c.vocab, dx, s);
-    else rc = mmda_embed_scatter_add_masked(GG(m->embed), t_ids, R, c.d_t, dx, lengths, B, s);
+    if (sorted) rc = mmda_embed_scatter_presorted(GG(p.embed), sorted, R, c.d_t, c.vocab, dx, s);
+    else rc = mmda_embed_scatter_add_masked(GG(p.embed), t_ids, R, c.d_t, dx, lengths, B, s);
   }
 }
 }  // namespace
@@ -2172,7 +2198,7 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   x.fusion_wgrads();
   if (x.rc) return x.rc;
   x.bwd_side_chain(row_fuse, t_ids, lengths);
-  const float* xin[3] = {WS(m->mod[0].x), v, a};
+  const float* xin[3] = {WS(m->lay.mod[0].x), v, a};
   // Encoder cut: the pass ends here.  No early optimizer pass, no ev_early, no sorted id list and no flag word of this pass exist,
   // so the join below is the event's (adam_early_done stays 0) and no kernel waits for a word that nobody sets; the recurrent
   // layers' ranges of the gradient bucket hold what the clear left.
@@ -2184,7 +2210,7 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   // (only where every gradient the side stream computes lies in the prefix it also stepped -- the bf16 step, whose layer-2 weight
   //  gradients ran there in front of the early optimizer pass: the launch that waits READS the rest of the bucket before it waits)
   if (P.fj_on && early && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
-      m->adam_early_done == m->rnn1_begin) {
+      m->adam_early_done == m->par.rnn1_begin) {
     x.rc = side_flag_signal(m, 1);
     m->fj2 = x.rc ? 0 : 1;
     return x.rc;
@@ -2257,16 +2283,16 @@ extern "C" int mmda_misa_timing_collect(mmda_misa* m, float mean_ms[4], int* ste
 namespace {
 // sparse table: the rows of the backward that just ran (d_x_t is workspace: the next micro-batch overwrites it) go to the caller's list
 int accum_append_rows(mmda_misa* m, const RowList& l, void* stream) {
-  if (!m->eu.on || !m->ws || m->T <= 0 || !l.ids || !l.rows) return MMDA_EINVAL;
+  if (!m->eu.on || !m->ws || m->lay.T <= 0 || !l.ids || !l.rows) return MMDA_EINVAL;
   const PendingRows r = m->eu.take();                   // (a later mmda_misa_adam_step must not apply these rows again)
-  return mmda_embed_rows_append(l.ids, l.rows, l.used, l.capacity, r.ids, WS(m->mod[0].d_x), m->B * m->T, m->cfg.d_t, r.lengths, m->B, stream);
+  return mmda_embed_rows_append(l.ids, l.rows, l.used, l.capacity, r.ids, WS(m->lay.mod[0].d_x), m->lay.B * m->lay.T, m->cfg.d_t, r.lengths, m->lay.B, stream);
 }
 bool accum_ready(const mmda_misa* m) { return m && m->P && m->G && !m->df_row_step; }
 // sparse table: a backward is pending and the list holds its T B rows behind the `used` it already has (dense / frozen: no list)
 bool accum_list_ok(const mmda_misa* m, const RowList& l) {
   if (m->embed_update != EU_SPARSE) return true;
-  const int64_t R = (int64_t)m->B * m->T;
-  return m->eu.on && m->ws && m->T > 0 && l.ids && l.rows && l.used >= 0 && l.used <= l.capacity && R <= l.capacity - l.used &&
+  const int64_t R = (int64_t)m->lay.B * m->lay.T;
+  return m->eu.on && m->ws && m->lay.T > 0 && l.ids && l.rows && l.used >= 0 && l.used <= l.capacity && R <= l.capacity - l.used &&
          l.used + R <= INT32_MAX;
 }
 
@@ -2284,11 +2310,11 @@ int opt_step_refused(const mmda_misa* m, const OptStep& o) {
 int opt_step(mmda_misa* m, const OptStep& o, int64_t lo, const FlagWait& w, const RowList* list, void* stream) {
   int rc = masked(m) ? runs_ready(m, stream) : MMDA_OK;
   if (!rc && o.norm) rc = bucket_norm(m, o.acc, o.grad_scale, stream);
-  if (!rc) rc = bucket_adam(m, lo, grad_floats(m), o.acc, o.lr, o.clip, o.grad_scale, o.step, w, stream, o.norm ? m->ws + m->gnorm + 1 : nullptr);
+  if (!rc) rc = bucket_adam(m, lo, grad_floats(m), o.acc, o.lr, o.clip, o.grad_scale, o.step, w, stream, o.norm ? m->ws + m->lay.gnorm + 1 : nullptr);
   if (rc) return rc;
-  float* const p = PP(m->embed); float* const m1 = m->M1 + m->embed; float* const v1 = m->V1 + m->embed; const mmda_adam_opts& h = m->adam;
+  float* const p = PP(m->par.embed); float* const m1 = m->M1 + m->par.embed; float* const v1 = m->V1 + m->par.embed; const mmda_adam_opts& h = m->adam;
   if (m->embed_update == EU_SPARSE && list) {
-    const int n = (int)(list->used + (int64_t)m->B * m->T);
+    const int n = (int)(list->used + (int64_t)m->lay.B * m->lay.T);
     rc = accum_append_rows(m, *list, stream);
     // SparseAdam on the rows any micro-batch touched, sums in list order (micro-batch major); padding went in as id -1
     if (!rc) rc = mmda_embed_rows_sparse_adam(p, m1, v1, list->ids, n, m->cfg.d_t, list->rows, nullptr, 0, m->cfg.vocab, o.lr, h.beta1, h.beta2,
@@ -2296,8 +2322,8 @@ int opt_step(mmda_misa* m, const OptStep& o, int64_t lo, const FlagWait& w, cons
   } else if (m->embed_update == EU_SPARSE && m->eu.on) {
     // the touched rows of the last backward: coalesce, scale, clamp, SparseAdam (the clamp applies to the coalesced sum)
     const PendingRows r = m->eu.take();
-    if (!m->ws || m->T <= 0) return MMDA_EINVAL;
-    rc = mmda_embed_rows_sparse_adam(p, m1, v1, r.ids, m->B * m->T, m->cfg.d_t, WS(m->mod[0].d_x), r.lengths, m->B, m->cfg.vocab, o.lr, h.beta1,
+    if (!m->ws || m->lay.T <= 0) return MMDA_EINVAL;
+    rc = mmda_embed_rows_sparse_adam(p, m1, v1, r.ids, m->lay.B * m->lay.T, m->cfg.d_t, WS(m->lay.mod[0].d_x), r.lengths, m->lay.B, m->cfg.vocab, o.lr, h.beta1,
                                      h.beta2, h.eps, o.clip, o.grad_scale, o.step, stream);
   } else if (m->embed_update == EU_DENSE && m->df_row_step && m->eu.on) {
     rc = mmda_misa_embed_deferred_step(m, o.lr, h.beta1, h.beta2, h.eps, o.clip, o.grad_scale, o.step, stream);
@@ -2349,7 +2375,7 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   if (!rc && do_adam && masked(m)) rc = runs_ready(m, stream);     // frozen parameters: the run table is there before the first launch
   if (rc) return rc;
   m->inference = 0;                                     // a training step always stashes (but for the encoders of a cut step)
-  m->zero_grad_pending = m->T > 0 ? 1 : 0;
+  m->zero_grad_pending = m->lay.T > 0 ? 1 : 0;
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
   m->fj1 = m->fj2 = 0;
@@ -2392,19 +2418,20 @@ extern "C" int mmda_misa_train_step_encoded(mmda_misa* m, const mmda_encoded_bat
 // The encoder cache's collect launch (encoded.hip) on the model's own workspace: B columns of the last forward of the current carve.
 extern "C" int mmda_misa_encoded_collect(mmda_misa* m, float* tab_t, float* tab_v, float* tab_a, const int32_t* dst, int64_t base,
                                          void* stream) {
-  if (!m || !m->ws || m->B <= 0) return MMDA_EINVAL;
+  if (!m || !m->ws || m->lay.B <= 0) return MMDA_EINVAL;
   // (a table that is not given is a segment that is skipped: its source is left out with it)
-  return mmda_encoded_collect(tab_t ? WS(m->mod[0].utt) : nullptr, tab_v ? WS(m->mod[1].utt) : nullptr, tab_a ? WS(m->mod[2].utt) : nullptr,
-                              4 * m->mod[0].H, 4 * m->mod[1].H, 4 * m->mod[2].H, tab_t, tab_v, tab_a, dst, base, m->B, stream);
+  return mmda_encoded_collect(tab_t ? WS(m->lay.mod[0].utt) : nullptr, tab_v ? WS(m->lay.mod[1].utt) : nullptr, tab_a ? WS(m->lay.mod[2].utt) : nullptr,
+                              4 * m->par.mod[0].H, 4 * m->par.mod[1].H, 4 * m->par.mod[2].H, tab_t, tab_v, tab_a, dst, base, m->lay.B, stream);
 }
 
 // The inference pass's collect launch (infer.hip) on the model's own workspace: the sources are where the last forward of the current
 // (B, T) carve left them, in the layouts that launch's comment states.
 extern "C" int mmda_misa_infer_collect(mmda_misa* m, const mmda_infer_out* out, const int32_t* dst, int64_t base, void* stream) {
-  if (!m || !out || !m->ws || m->B <= 0) return MMDA_EINVAL;
+  if (!m || !out || !m->ws || m->lay.B <= 0) return MMDA_EINVAL;
+  const Workspace& w = m->lay;
   mmda_infer_src src = {};
-  src.scores = WS(m->scores); src.labels = WS(m->labels); src.tcp = WS(m->tcp); src.hfused = WS(m->hfused); src.x6 = WS(m->x6);
-  src.probs = WS(m->probs);
+  src.scores = WS(w.scores); src.labels = WS(w.labels); src.tcp = WS(w.tcp); src.hfused = WS(w.hfused); src.x6 = WS(w.x6);
+  src.probs = WS(w.probs);
   src.ncls = m->cfg.ncls; src.hs = m->cfg.hidden; src.nhead = NHEAD;
-  return mmda_infer_collect(&src, out, dst, base, m->B, stream);
+  return mmda_infer_collect(&src, out, dst, base, w.B, stream);
 }

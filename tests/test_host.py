@@ -120,6 +120,19 @@ def test_native_workspace_layout_monotone_and_named():
     assert lib.mmda_misa_tensor_offset(m._h, b"scores") == -1      # no workspace bound yet
 
 
+def test_workspace_totals_match_the_pinned_layout():
+    """Every total of tests/workspace_layout_cases.py (configurations x shapes), asked of one handle per configuration: sizing binds
+    nothing, so no name has an offset afterwards either."""
+    import workspace_layout_cases as wl
+    lib = _lib.load()
+    assert set(wl.TOTALS) == {(c, B, T) for c in wl.CONFIGS for (B, T) in wl.SHAPES}
+    for c, kw in wl.CONFIGS.items():
+        m = MISA(make_config(vocab_size=50, **kw))
+        for (B, T) in wl.SHAPES:
+            assert lib.mmda_misa_workspace_floats(m._h, B, T) == wl.TOTALS[(c, B, T)], (c, B, T)
+        assert lib.mmda_misa_tensor_offset(m._h, b"scores") == -1
+
+
 def test_solver_surface_exists():
     for name in ("build", "train", "train_epoch", "eval", "get_cls_loss", "get_domain_loss", "get_cmd_loss", "get_diff_loss",
                  "get_recon_loss", "get_conf_loss"):
