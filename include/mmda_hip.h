@@ -338,6 +338,42 @@ int64_t mmda_lstm_xchg_bytes(int H, int B);
 int mmda_lstm_resident_applicable(int mode, int n, const mmda_lstm_desc* descs, int B, int T, int backward);
 /* 1 if mmda_lstm_bwd on these descriptors will write mmda_lstm_desc.dg_bf16 (wave-autonomous resident kernel, gate_minor = 1) */
 int mmda_lstm_bwd_emits_dg_bf16(int mode, int n, const mmda_lstm_desc* descs, int B, int T);
+/* A read-only view of what mmda_lstm_fwd (backward = 0) / mmda_lstm_bwd (backward = 1) would run for these descriptors in bf16 mode
+ * on the resident-weights kernels.  Host code only: no launch and no environment; descriptor pointers are checked for NULL as the
+ * real call checks them (xchg, wpack_c, dg_bf16, d_hseq) and never followed.  `switches` = {no_quad, quad_cap}: no_quad stands for
+ * MMDA_LSTM_NO_QUAD; quad_cap > 0 is the most workgroups a four-waves-per-tile launch may hold, quad_cap = 0 asks the runtime for it
+ * as a launch does (an occupancy query: the only device call, and only for a gate-minor wave-sized plan); NULL = {0, 0}.
+ * Returns MMDA_OK with plan->ok = 0 where the streaming kernels would run instead (every other field then 0, kernel -1). */
+enum { MMDA_LSTM_FORM_BARRIER = 0, MMDA_LSTM_FORM_WAVE = 1, MMDA_LSTM_FORM_QUAD = 2 };
+enum { MMDA_LSTM_DHSEQ_RUNTIME = 0, MMDA_LSTM_DHSEQ_ABSENT = 1, MMDA_LSTM_DHSEQ_PRESENT = 2 };
+/* the kernel instances of lstm_cluster.hip, in the order its selection names them (mmda_lstm_kernel_name gives the C++ name) */
+enum {
+  MMDA_LSTM_K_BWD_QUAD_GRU = 0, MMDA_LSTM_K_BWD_QUAD_PRESENT, MMDA_LSTM_K_BWD_QUAD_ABSENT, MMDA_LSTM_K_BWD_QUAD,
+  MMDA_LSTM_K_FWD_QUAD_GRU_NOSTASH, MMDA_LSTM_K_FWD_QUAD_GRU, MMDA_LSTM_K_FWD_QUAD_NOSTASH, MMDA_LSTM_K_FWD_QUAD,
+  MMDA_LSTM_K_STAMPED,               /* mmda_debug_set_lstm_stamps: one entry for the forward and the backward debug kernel */
+  MMDA_LSTM_K_BWD_WAVE_GRU_GM, MMDA_LSTM_K_BWD_WAVE_GRU, MMDA_LSTM_K_FWD_WAVE_GRU_GM, MMDA_LSTM_K_FWD_WAVE_GRU,
+  MMDA_LSTM_K_BWD_WAVE_ABSENT_PAIR, MMDA_LSTM_K_BWD_WAVE_ABSENT, MMDA_LSTM_K_BWD_WAVE_PRESENT_PAIR, MMDA_LSTM_K_BWD_WAVE_PRESENT,
+  MMDA_LSTM_K_BWD_WAVE_GM, MMDA_LSTM_K_BWD_WAVE,
+  MMDA_LSTM_K_BWD_BARRIER_REGS_GM, MMDA_LSTM_K_BWD_BARRIER_REGS, MMDA_LSTM_K_BWD_BARRIER_GM, MMDA_LSTM_K_BWD_BARRIER,
+  MMDA_LSTM_K_FWD_WAVE_GM_NOSTASH, MMDA_LSTM_K_FWD_WAVE_GM, MMDA_LSTM_K_FWD_WAVE,
+  MMDA_LSTM_K_FWD_BARRIER_GM, MMDA_LSTM_K_FWD_BARRIER,
+  MMDA_LSTM_K_COUNT
+};
+typedef struct mmda_lstm_plan {
+  int ok;                            /* 1: the resident-weights kernels run */
+  int form, wpb;                     /* MMDA_LSTM_FORM_*; waves per block (wave form: 1, 2 or 4; quad: 1 tile per block; barrier: 4) */
+  int groups, groups_per_launch, launches;   /* 32-sample batch groups, how many a launch takes (<= groups), launches of the call */
+  int wg_per_group;                  /* workgroups of one batch group, both directions, all descriptors */
+  int wg_per_desc[4];                /* ... and of each descriptor */
+  int gru, gate_minor, no_stash;
+  int dhseq;                         /* MMDA_LSTM_DHSEQ_*: what the backward instance knows about d_hseq at compile time */
+  int bwd_regs;                      /* every descriptor has <= 20 hidden tiles (barrier form: the register-resident backward) */
+  int pair;                          /* 1: the instance that runs pre-reduces the partial dh tiles of a producer pair (PAIR = 1) */
+  int kernel;                        /* MMDA_LSTM_K_* */
+} mmda_lstm_plan;
+int mmda_lstm_plan_describe(int n, const mmda_lstm_desc* descs, int B, int T, int backward, const int switches[2], mmda_lstm_plan* plan);
+/* C++ name of instance `kernel` (MMDA_LSTM_K_*), NULL beyond the last */
+const char* mmda_lstm_kernel_name(int kernel);
 /* diagnostics only: 8 x uint64 per workgroup, phase cycle sums of the resident-weights forward kernel (NULL disables) */
 int mmda_debug_set_lstm_stamps(void* device_buffer);
 /* up to 4 independent biLSTMs (modalities) in ONE launch; all share B, T and lengths (device int32, B entries) */

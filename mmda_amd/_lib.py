@@ -95,6 +95,14 @@ class LstmDesc(C.Structure):
                 ("cell", C.c_int), ("dg_bf16", C.c_void_p), ("dg_bf16_only", C.c_int)]
 
 
+class LstmPlan(C.Structure):
+    """mmda_lstm_plan: what the resident launch plan of an mmda_lstm_fwd / mmda_lstm_bwd call decides"""
+    _fields_ = [("ok", C.c_int), ("form", C.c_int), ("wpb", C.c_int), ("groups", C.c_int), ("groups_per_launch", C.c_int),
+                ("launches", C.c_int), ("wg_per_group", C.c_int), ("wg_per_desc", C.c_int * 4), ("gru", C.c_int),
+                ("gate_minor", C.c_int), ("no_stash", C.c_int), ("dhseq", C.c_int), ("bwd_regs", C.c_int), ("pair", C.c_int),
+                ("kernel", C.c_int)]
+
+
 class GruPadJob(C.Structure):
     _fields_ = [("H", C.c_int), ("D", C.c_int), ("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2),
                 ("b_hh", C.c_void_p * 2), ("pw_ih", C.c_void_p), ("pw_hh", C.c_void_p * 2), ("pb_ih", C.c_void_p), ("pb_hh", C.c_void_p)]
@@ -182,6 +190,8 @@ SIGNATURES = {
     "mmda_lstm_xchg_bytes": (_I64, [_I, _I]),
     "mmda_lstm_resident_applicable": (_I, [_I, _I, C.POINTER(LstmDesc), _I, _I, _I]),
     "mmda_lstm_bwd_emits_dg_bf16": (_I, [_I, _I, C.POINTER(LstmDesc), _I, _I]),
+    "mmda_lstm_plan_describe": (_I, [_I, C.POINTER(LstmDesc), _I, _I, _I, C.POINTER(C.c_int), C.POINTER(LstmPlan)]),
+    "mmda_lstm_kernel_name": (C.c_char_p, [_I]),
     "mmda_debug_set_lstm_stamps": (_I, [_P]),
     "mmda_lstm_pack_whh": (_I, [_I, _I, _P, _P, _P, _P]),
     "mmda_lstm_pack_whh_multi": (_I, [_I, _I, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -2114,9 +2114,14 @@ int quad_block_cap(bool bwd) {
   return std::min(MAX_WG_QUAD, 240 * (bwd ? occ_b : occ_f));
 }
 
-// The single place that decides.  `launching` = false (the two probes): no HIP runtime call is made, so Quad is reported as Wave --
-// neither plan.ok nor "not the barrier form" depends on the difference.
-ResidentPlan plan_resident(int n, const mmda_lstm_desc* descs, int B, int T, bool bwd, bool launching) {
+// What a plan takes from outside the descriptors.  quad_cap: the most blocks a quad launch may hold -- QUAD_CAP_RUNTIME asks the
+// runtime (quad_block_cap: a launch, and the plan view on a device), QUAD_CAP_NEVER (the two probes) makes no HIP runtime call and
+// reports Quad as Wave: neither plan.ok nor "not the barrier form" depends on the difference.  no_quad: MMDA_LSTM_NO_QUAD.
+constexpr int QUAD_CAP_RUNTIME = 0, QUAD_CAP_NEVER = -1;
+struct PlanSwitches { bool no_quad; int quad_cap; };
+
+// The single place that decides.
+ResidentPlan plan_resident(int n, const mmda_lstm_desc* descs, int B, int T, bool bwd, const PlanSwitches& sw) {
   ResidentPlan P{};
   if (n > MAXD || n <= 0) return P;
   P.n = n; P.bwd = bwd; P.ngt = ceil_div(B, GROUP);
@@ -2161,8 +2166,8 @@ ResidentPlan plan_resident(int n, const mmda_lstm_desc* descs, int B, int T, boo
   // Four waves per tile: gate-minor layout, every group's tiles in one launch at one workgroup per tile (the quad kernels' own
   // limits, 12 k-steps and 20 hidden tiles, are wider than the wave form's).  MMDA_LSTM_NO_QUAD: ablation (the one-wave-per-tile
   // kernels).
-  static const bool no_quad = mmda_env_set("MMDA_LSTM_NO_QUAD");
-  const bool quad = launching && wave && P.gate_minor && !no_quad && g_dbg == nullptr && wave_wgs(1) * P.ngt <= quad_block_cap(bwd);
+  const bool quad = sw.quad_cap != QUAD_CAP_NEVER && wave && P.gate_minor && !sw.no_quad && g_dbg == nullptr &&
+                    wave_wgs(1) * P.ngt <= (sw.quad_cap > 0 ? sw.quad_cap : quad_block_cap(bwd));
   if (quad) P.wpb = 1;
   P.form = quad ? Form::Quad : (wave ? Form::Wave : Form::Barrier);
   for (int i = 0; i < n; ++i) {
@@ -2196,46 +2201,87 @@ ResidentPlan plan_resident(int n, const mmda_lstm_desc* descs, int B, int T, boo
   return P;
 }
 
-// The kernel instance of a plan.  Quad first, then the wave and barrier forms by cell and pass.  (The chains name the instances
-// in the order the selection has always named them: the compiler emits instances in order of first use, and keeping that order
-// keeps the code object byte-identical across host-side changes.)
+// The kernel instance of a plan.  Quad first, then the wave and barrier forms by cell and pass.
 typedef void (*Kernel)(CLaunch);
-Kernel pick_kernel(const ResidentPlan& P) {
+// One row per MMDA_LSTM_K_* (include/mmda_hip.h), in the enum's order: the instance's name and its function.  The stamped debug
+// instance is one entry with a kernel per pass.  (The rows name the instances in the order the selection has always named them,
+// backward before forward within a row: the compiler emits instances in order of first use, and keeping that order keeps the code
+// object byte-identical across host-side changes.)
+struct Instance { const char* name; Kernel bwd, fwd; };
+const Instance& instance_of(int id) {
   constexpr int LSTM = MMDA_CELL_LSTM, GRU = MMDA_CELL_GRU;
+  static const Instance table[MMDA_LSTM_K_COUNT] = {
+      {"lstm_bwd_quad_kernel<GRU,2,2>", lstm_bwd_quad_kernel<GRU, 2, 2>, nullptr},
+      {"lstm_bwd_quad_kernel<LSTM,1,1>", lstm_bwd_quad_kernel<LSTM, 1, 1>, nullptr},
+      {"lstm_bwd_quad_kernel<LSTM,0,1>", lstm_bwd_quad_kernel<LSTM, 0, 1>, nullptr},
+      {"lstm_bwd_quad_kernel<LSTM,2,2>", lstm_bwd_quad_kernel<LSTM, 2, 2>, nullptr},
+      {"lstm_fwd_quad_kernel<GRU,1>", nullptr, lstm_fwd_quad_kernel<GRU, 1>},
+      {"lstm_fwd_quad_kernel<GRU,0>", nullptr, lstm_fwd_quad_kernel<GRU, 0>},
+      {"lstm_fwd_quad_kernel<LSTM,1>", nullptr, lstm_fwd_quad_kernel<LSTM, 1>},
+      {"lstm_fwd_quad_kernel<LSTM,0>", nullptr, lstm_fwd_quad_kernel<LSTM, 0>},
+      {"stamped debug instance", lstm_bwd_wave_kernel<20, true, LSTM, true>, lstm_fwd_wave_kernel<10, true, LSTM, true>},
+      {"lstm_bwd_wave_kernel<20,true,GRU,false>", lstm_bwd_wave_kernel<20, true, GRU, false>, nullptr},
+      {"lstm_bwd_wave_kernel<20,false,GRU,false>", lstm_bwd_wave_kernel<20, false, GRU, false>, nullptr},
+      {"lstm_fwd_wave_kernel<10,true,GRU,false>", nullptr, lstm_fwd_wave_kernel<10, true, GRU, false>},
+      {"lstm_fwd_wave_kernel<10,false,GRU,false>", nullptr, lstm_fwd_wave_kernel<10, false, GRU, false>},
+      {"lstm_bwd_wave_kernel<20,true,LSTM,false,0,1,1>", lstm_bwd_wave_kernel<20, true, LSTM, false, 0, 1, 1>, nullptr},
+      {"lstm_bwd_wave_kernel<20,true,LSTM,false,0,1>", lstm_bwd_wave_kernel<20, true, LSTM, false, 0, 1>, nullptr},
+      {"lstm_bwd_wave_kernel<20,true,LSTM,false,1,1,1>", lstm_bwd_wave_kernel<20, true, LSTM, false, 1, 1, 1>, nullptr},
+      {"lstm_bwd_wave_kernel<20,true,LSTM,false,1,1>", lstm_bwd_wave_kernel<20, true, LSTM, false, 1, 1>, nullptr},
+      {"lstm_bwd_wave_kernel<20,true,LSTM,false>", lstm_bwd_wave_kernel<20, true, LSTM, false>, nullptr},
+      {"lstm_bwd_wave_kernel<20,false,LSTM,false>", lstm_bwd_wave_kernel<20, false, LSTM, false>, nullptr},
+      {"lstm_bwd_cluster_kernel<10,true>", lstm_bwd_cluster_kernel<10, true>, nullptr},
+      {"lstm_bwd_cluster_kernel<10,false>", lstm_bwd_cluster_kernel<10, false>, nullptr},
+      {"lstm_bwd_cluster_kernel<0,true>", lstm_bwd_cluster_kernel<0, true>, nullptr},
+      {"lstm_bwd_cluster_kernel<0,false>", lstm_bwd_cluster_kernel<0, false>, nullptr},
+      {"lstm_fwd_wave_kernel<10,true,LSTM,false,1>", nullptr, lstm_fwd_wave_kernel<10, true, LSTM, false, 1>},
+      {"lstm_fwd_wave_kernel<10,true,LSTM,false,0>", nullptr, lstm_fwd_wave_kernel<10, true, LSTM, false, 0>},
+      {"lstm_fwd_wave_kernel<10,false,LSTM,false>", nullptr, lstm_fwd_wave_kernel<10, false, LSTM, false>},
+      {"lstm_fwd_cluster_kernel<10,true>", nullptr, lstm_fwd_cluster_kernel<10, true>},
+      {"lstm_fwd_cluster_kernel<10,false>", nullptr, lstm_fwd_cluster_kernel<10, false>},
+  };
+  return table[id];
+}
+
+// Which instance a plan runs (no function is named here: the view of a plan needs the answer without a launch).
+int pick_instance(const ResidentPlan& P) {
   const bool gm = P.gate_minor, wave = P.form == Form::Wave;
   if (P.form == Form::Quad) {              // gate-minor only
     if (P.bwd) {
-      if (P.gru) return lstm_bwd_quad_kernel<GRU, 2, 2>;
-      if (P.dhseq == DHseq::Present) return lstm_bwd_quad_kernel<LSTM, 1, 1>;
-      if (P.dhseq == DHseq::Absent) return lstm_bwd_quad_kernel<LSTM, 0, 1>;
-      return lstm_bwd_quad_kernel<LSTM, 2, 2>;
+      if (P.gru) return MMDA_LSTM_K_BWD_QUAD_GRU;
+      if (P.dhseq == DHseq::Present) return MMDA_LSTM_K_BWD_QUAD_PRESENT;
+      if (P.dhseq == DHseq::Absent) return MMDA_LSTM_K_BWD_QUAD_ABSENT;
+      return MMDA_LSTM_K_BWD_QUAD;
     }
-    if (P.gru) return P.no_stash ? lstm_fwd_quad_kernel<GRU, 1> : lstm_fwd_quad_kernel<GRU, 0>;
-    return P.no_stash ? lstm_fwd_quad_kernel<LSTM, 1> : lstm_fwd_quad_kernel<LSTM, 0>;
+    if (P.gru) return P.no_stash ? MMDA_LSTM_K_FWD_QUAD_GRU_NOSTASH : MMDA_LSTM_K_FWD_QUAD_GRU;
+    return P.no_stash ? MMDA_LSTM_K_FWD_QUAD_NOSTASH : MMDA_LSTM_K_FWD_QUAD;
   }
   // wave form, stamped: a debug instance of its own (see plan_resident)
-  if (P.stamped) return P.bwd ? lstm_bwd_wave_kernel<20, true, LSTM, true> : lstm_fwd_wave_kernel<10, true, LSTM, true>;
+  if (P.stamped) return MMDA_LSTM_K_STAMPED;
   if (P.gru) {                             // wave form (plan_resident admits the GRU cell to no other)
-    if (P.bwd) return gm ? lstm_bwd_wave_kernel<20, true, GRU, false> : lstm_bwd_wave_kernel<20, false, GRU, false>;
-    return gm ? lstm_fwd_wave_kernel<10, true, GRU, false> : lstm_fwd_wave_kernel<10, false, GRU, false>;
+    if (P.bwd) return gm ? MMDA_LSTM_K_BWD_WAVE_GRU_GM : MMDA_LSTM_K_BWD_WAVE_GRU;
+    return gm ? MMDA_LSTM_K_FWD_WAVE_GRU_GM : MMDA_LSTM_K_FWD_WAVE_GRU;
   }
   if (P.bwd && wave) {
     // gate-minor with dG as bf16 only: d_hseq is known at compile time; pairing only at four waves per block (plan_resident)
-    if (P.dhseq == DHseq::Absent)
-      return P.pair_bwd ? lstm_bwd_wave_kernel<20, true, LSTM, false, 0, 1, 1> : lstm_bwd_wave_kernel<20, true, LSTM, false, 0, 1>;
-    if (P.dhseq == DHseq::Present)
-      return P.pair_bwd ? lstm_bwd_wave_kernel<20, true, LSTM, false, 1, 1, 1> : lstm_bwd_wave_kernel<20, true, LSTM, false, 1, 1>;
-    return gm ? lstm_bwd_wave_kernel<20, true, LSTM, false> : lstm_bwd_wave_kernel<20, false, LSTM, false>;
+    if (P.dhseq == DHseq::Absent) return P.pair_bwd ? MMDA_LSTM_K_BWD_WAVE_ABSENT_PAIR : MMDA_LSTM_K_BWD_WAVE_ABSENT;
+    if (P.dhseq == DHseq::Present) return P.pair_bwd ? MMDA_LSTM_K_BWD_WAVE_PRESENT_PAIR : MMDA_LSTM_K_BWD_WAVE_PRESENT;
+    return gm ? MMDA_LSTM_K_BWD_WAVE_GM : MMDA_LSTM_K_BWD_WAVE;
   }
   if (P.bwd) {                             // barrier form
-    if (P.bwd_regs) return gm ? lstm_bwd_cluster_kernel<10, true> : lstm_bwd_cluster_kernel<10, false>;
-    return gm ? lstm_bwd_cluster_kernel<0, true> : lstm_bwd_cluster_kernel<0, false>;
+    if (P.bwd_regs) return gm ? MMDA_LSTM_K_BWD_BARRIER_REGS_GM : MMDA_LSTM_K_BWD_BARRIER_REGS;
+    return gm ? MMDA_LSTM_K_BWD_BARRIER_GM : MMDA_LSTM_K_BWD_BARRIER;
   }
   if (wave) {
-    if (gm) return P.no_stash ? lstm_fwd_wave_kernel<10, true, LSTM, false, 1> : lstm_fwd_wave_kernel<10, true, LSTM, false, 0>;
-    return lstm_fwd_wave_kernel<10, false, LSTM, false>;
+    if (gm) return P.no_stash ? MMDA_LSTM_K_FWD_WAVE_GM_NOSTASH : MMDA_LSTM_K_FWD_WAVE_GM;
+    return MMDA_LSTM_K_FWD_WAVE;
   }
-  return gm ? lstm_fwd_cluster_kernel<10, true> : lstm_fwd_cluster_kernel<10, false>;   // barrier form
+  return gm ? MMDA_LSTM_K_FWD_BARRIER_GM : MMDA_LSTM_K_FWD_BARRIER;   // barrier form
+}
+
+Kernel pick_kernel(const ResidentPlan& P) {
+  const Instance& k = instance_of(pick_instance(P));
+  return P.bwd ? k.bwd : k.fwd;
 }
 
 // Placement (speed only): blocks b and b + 8 are dealt to the same XCD, so the members of one cluster (first role, members; its
@@ -2274,22 +2320,53 @@ void ensure_dynamic_lds(Kernel kernel, size_t bytes) {
 
 extern "C" int mmda_lstm_resident_applicable(int mode, int n, const mmda_lstm_desc* descs, int B, int T, int backward) {
   if (mode != MMDA_BF16 || !descs || B <= 0 || T <= 0) return 0;
-  return plan_resident(n, descs, B, T, backward != 0, false).ok ? 1 : 0;
+  return plan_resident(n, descs, B, T, backward != 0, {false, QUAD_CAP_NEVER}).ok ? 1 : 0;
 }
 
 extern "C" int mmda_lstm_bwd_emits_dg_bf16(int mode, int n, const mmda_lstm_desc* descs, int B, int T) {
   // the wave-autonomous backward kernels with the gate-minor layout (one layout for all descriptors of a plan) are the ones that
   // write mmda_lstm_desc.dg_bf16
   if (mode != MMDA_BF16 || !descs || B <= 0 || T <= 0) return 0;
-  const ResidentPlan P = plan_resident(n, descs, B, T, true, false);
+  const ResidentPlan P = plan_resident(n, descs, B, T, true, {false, QUAD_CAP_NEVER});
   return (P.ok && P.form != Form::Barrier && P.gate_minor) ? 1 : 0;
+}
+
+extern "C" int mmda_lstm_plan_describe(int n, const mmda_lstm_desc* descs, int B, int T, int backward, const int switches[2],
+                                       mmda_lstm_plan* plan) {
+  if (!descs || !plan || B <= 0 || T <= 0) return MMDA_EINVAL;
+  *plan = mmda_lstm_plan{};
+  plan->kernel = -1;
+  for (int i = 0; i < n && i < MAXD; ++i)
+    if (descs[i].H <= 0 || descs[i].H > 512) return MMDA_OK;           // mmda_lstm_fwd / bwd reject these before any plan is made
+  const PlanSwitches sw = {switches && switches[0] != 0, (switches && switches[1] > 0) ? switches[1] : QUAD_CAP_RUNTIME};
+  const ResidentPlan P = plan_resident(n, descs, B, T, backward != 0, sw);
+  if (!P.ok) return MMDA_OK;
+  plan->ok = 1;
+  plan->form = P.form == Form::Quad ? MMDA_LSTM_FORM_QUAD : (P.form == Form::Wave ? MMDA_LSTM_FORM_WAVE : MMDA_LSTM_FORM_BARRIER);
+  plan->wpb = P.wpb;
+  plan->groups = P.ngt;
+  plan->groups_per_launch = std::min(P.groups_per_launch, P.ngt);
+  plan->launches = ceil_div(P.ngt, P.groups_per_launch);
+  plan->wg_per_group = P.wg_per_group;
+  for (int i = 0; i < n; ++i) plan->wg_per_desc[i] = 2 * P.members[i];
+  plan->gru = P.gru; plan->gate_minor = P.gate_minor; plan->no_stash = P.no_stash; plan->bwd_regs = P.bwd_regs;
+  plan->dhseq = P.dhseq == DHseq::Present ? MMDA_LSTM_DHSEQ_PRESENT : (P.dhseq == DHseq::Absent ? MMDA_LSTM_DHSEQ_ABSENT : MMDA_LSTM_DHSEQ_RUNTIME);
+  plan->kernel = pick_instance(P);
+  // ResidentPlan.pair_bwd sizes the LDS of every gate-minor LSTM backward at four waves per block; only these two instances pair
+  plan->pair = (plan->kernel == MMDA_LSTM_K_BWD_WAVE_ABSENT_PAIR || plan->kernel == MMDA_LSTM_K_BWD_WAVE_PRESENT_PAIR) ? 1 : 0;
+  return MMDA_OK;
+}
+
+extern "C" const char* mmda_lstm_kernel_name(int kernel) {
+  return (kernel >= 0 && kernel < MMDA_LSTM_K_COUNT) ? instance_of(kernel).name : nullptr;
 }
 
 // returns MMDA_OK and sets *used = 1 when the cluster kernels ran; *used = 0 means "not applicable, use the streaming path"
 int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, const int32_t* lengths, void* stream, bool bwd,
                              int* used) {
   *used = 0;
-  const ResidentPlan P = plan_resident(n, descs, B, T, bwd, true);
+  static const bool no_quad = mmda_env_set("MMDA_LSTM_NO_QUAD");
+  const ResidentPlan P = plan_resident(n, descs, B, T, bwd, {no_quad, QUAD_CAP_RUNTIME});
   if (!P.ok) return MMDA_OK;
   const bool wave = P.form != Form::Barrier, quad = P.form == Form::Quad;
   const Kernel kernel = pick_kernel(P);

@@ -413,6 +413,51 @@ def lstm_xchg(H, B, device):
     return torch.zeros(n, dtype=torch.uint8, device=device) if n > 0 else None
 
 
+LSTM_FORMS = ("barrier", "wave", "quad")
+LSTM_DHSEQ = ("run-time", "absent", "present")
+
+
+def lstm_kernel_names():
+    """The C++ names of the resident recurrences' kernel instances, in the order of the MMDA_LSTM_K_* enum"""
+    lib, out = load(), []
+    while (s := lib.mmda_lstm_kernel_name(len(out))) is not None:
+        out.append(s.decode())
+    return out
+
+
+def lstm_plan(descs, B, T, backward=False, no_quad=False, quad_cap=0):
+    """What mmda_lstm_fwd / mmda_lstm_bwd would run for these descriptors on the resident-weights kernels (mmda_lstm_plan_describe:
+    host code only; without a GPU give quad_cap > 0).  descs: an array of _lib.LstmDesc as the real call takes it, or a list of dicts
+    by shape alone -- H and optionally cell ('lstm' / 'gru'), gate_minor, forward_only, d_hseq, dg_bf16, dg_bf16_only, xchg, wpack_c (the
+    last five as booleans: only whether a pointer is NULL matters; xchg and wpack_c default to present).  no_quad stands for
+    MMDA_LSTM_NO_QUAD; quad_cap > 0 replaces the occupancy query behind the quad form's limit, 0 asks the runtime as a launch does.
+    Returns a dict: ok, form (a name of LSTM_FORMS), wpb, groups, groups_per_launch, launches, wg_per_group, wg_per_desc, gru,
+    gate_minor, no_stash, dhseq (a name of LSTM_DHSEQ), bwd_regs, pair, kernel (the instance's C++ name); ok = False: the streaming
+    kernels run and the other entries are None."""
+    if not isinstance(descs, C.Array):
+        arr = (_lib.LstmDesc * max(1, len(descs)))()
+        for d, p in zip(arr, descs):
+            fake = lambda on: 4096 if on else None           # never followed
+            d.H = p["H"]; d.cell = _lib.CELL[p.get("cell", "lstm")]; d.gate_minor = int(p.get("gate_minor", False))
+            d.forward_only = int(p.get("forward_only", False)); d.dg_bf16_only = int(p.get("dg_bf16_only", False))
+            d.xchg = fake(p.get("xchg", True)); d.d_hseq = fake(p.get("d_hseq", False)); d.dg_bf16 = fake(p.get("dg_bf16", False))
+            d.wpack_c[0] = d.wpack_c[1] = fake(p.get("wpack_c", True))
+        n = len(descs)
+    else:
+        arr, n = descs, len(descs)
+    plan = _lib.LstmPlan()
+    sw = (C.c_int * 2)(int(no_quad), int(quad_cap))
+    check(load().mmda_lstm_plan_describe(n, arr, B, T, int(backward), sw, C.byref(plan)), "mmda_lstm_plan_describe")
+    keys = ("form", "wpb", "groups", "groups_per_launch", "launches", "wg_per_group", "wg_per_desc", "gru", "gate_minor", "no_stash",
+            "dhseq", "bwd_regs", "pair", "kernel")
+    if not plan.ok:
+        return dict({k: None for k in keys}, ok=False)
+    return dict(ok=True, form=LSTM_FORMS[plan.form], wpb=plan.wpb, groups=plan.groups, groups_per_launch=plan.groups_per_launch,
+                launches=plan.launches, wg_per_group=plan.wg_per_group, wg_per_desc=list(plan.wg_per_desc)[:n], gru=bool(plan.gru),
+                gate_minor=bool(plan.gate_minor), no_stash=bool(plan.no_stash), dhseq=LSTM_DHSEQ[plan.dhseq],
+                bwd_regs=bool(plan.bwd_regs), pair=bool(plan.pair), kernel=load().mmda_lstm_kernel_name(plan.kernel).decode())
+
+
 def _to_gate_minor(x, H):
     """(..., 4H) [gate][unit] -> [unit][gate] (the resident-weights kernels' 16-byte layout)"""
     return x.reshape(*x.shape[:-1], 4, H).transpose(-1, -2).reshape(*x.shape[:-1], 4 * H).contiguous()

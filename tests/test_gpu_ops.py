@@ -661,7 +661,10 @@ def _lstm_case(T, B, H, D, ragged, seed):
                                           # barrier-synchronised form (H > 320; 21 hidden tiles: the backward's LDS-resident variant)
                                           (4, 8, 336, True),
                                           # a launch chunked over batch groups: barrier form, 11 groups at 10 per launch
-                                          (3, 330, 336, True)])
+                                          (3, 330, 336, True),
+                                          # ... and wave form at four waves per block, 13 groups at 12 per launch; gate-minor: the
+                                          # dg_bf16_only call pairs, the other does not (tests/test_gpu_lstm_forms.py has more)
+                                          (3, 400, 300, True)])
 def test_lstm_fwd_bwd_vs_nn_lstm(mode, T, B, H, ragged):
     """Three implementations of the recurrence behind one entry point: exact f32-MFMA streaming kernel, bf16 streaming kernel,
     and the bf16 kernel with W_hh resident in LDS across a cluster of workgroups (per-step h / dG all-gather)."""
@@ -696,6 +699,7 @@ def test_lstm_fwd_bwd_vs_nn_lstm(mode, T, B, H, ragged):
     assert not ops.lstm_aborted(fw), "cluster exchange timed out in backward"
     mask = (torch.arange(T)[:, None] < lengths[None, :]).reshape(T * B)
     assert float(dG.cpu()[~mask].abs().max() if (~mask).any() else 0.0) == 0.0, "dG must be zero at padded positions"
+    pair, others = False, []                    # further (dG, hseq, oracle form) to hold to the bounds below
     if "dg_bf16" in fw:
         # the kernel's own bf16 copy of dG (kernel column order [dir][unit][gate]) == the fp32 dG rounded, zeros at padding
         want = ops._to_gate_minor(dG.view(T, B, 2, 4 * H), H).reshape(T * B, 8 * H).to(torch.bfloat16)
@@ -705,36 +709,52 @@ def test_lstm_fwd_bwd_vs_nn_lstm(mode, T, B, H, ragged):
                                  layer=1, resident=resident, gate_minor=gate_minor)
         ops.lstm_bidir_bwd(fw2, d_utt.view(B, 4 * H).to(d), d_out.to(d), mode=mode, layer=1, dg_bf16_only=True)
         assert not ops.lstm_aborted(fw2)
-        assert torch.equal(fw2["dg_bf16"].view(torch.int16), fw["dg_bf16"].view(torch.int16))
+        # The two calls may run different instances: at four waves per block the dg_bf16_only call takes a PAIR = 1 instance, which
+        # adds two fp32 partial-dh tiles before the one bf16 rounding, the other call the run-time instance, which rounds each tile.
+        # Both are legitimate roundings (oracle/bf16_emul.py: tile_partials=32 / True).  Same pairing: the same bits.  Otherwise each
+        # call is held to its own oracle below.
+        shape = dict(H=H, gate_minor=True, d_hseq=True, dg_bf16=True)
+        pair, pair2 = (ops.lstm_plan([dict(shape, dg_bf16_only=o)], B, T, backward=True)["pair"] for o in (False, True))
+        if pair2 == pair:
+            assert torch.equal(fw2["dg_bf16"].view(torch.int16), fw["dg_bf16"].view(torch.int16))
+        else:
+            dG2 = ops._from_gate_minor(fw2["dg_bf16"].float().view(T, B, 2, 4 * H), H).view(T * B, 8 * H)
+            assert float(dG2.cpu()[~mask].abs().max() if (~mask).any() else 0.0) == 0.0, "dg_bf16 must be zero at padded positions"
+            assert relerr(fw2["hseq"], pad) < tol
+            others.append((dG2, fw2["hseq"], 32 if pair2 else resident))
     btol = tol * (3 if mode == "bf16" else 1)
-    dx = ops.gemm(dG, wih.to(d), mode=mode, transB=False).view(T, B, D)
-    assert relerr(dx, x.grad) < btol
-    dwih = ops.gemm(dG, x.detach().reshape(T * B, D).to(d), mode=mode, transA=True, transB=False)
-    assert relerr(dwih, torch.cat((rnn.weight_ih_l0.grad, rnn.weight_ih_l0_reverse.grad), 0)) < btol
-    db = ops.colsum(dG)
-    assert relerr(db, torch.cat((rnn.bias_ih_l0.grad, rnn.bias_ih_l0_reverse.grad), 0)) < btol
-    hseq = fw["hseq"].view(T * B, 2 * H)
-    if T > 1:
-        dG3 = dG.view(T, B, 8 * H); hs3 = hseq.view(T, B, 2 * H)
-        dwf = ops.gemm(dG3[1:, :, :4 * H].reshape(-1, 4 * H).contiguous(), hs3[:-1, :, :H].reshape(-1, H).contiguous(), mode=mode,
-                       transA=True, transB=False)
-        dwr = ops.gemm(dG3[:-1, :, 4 * H:].reshape(-1, 4 * H).contiguous(), hs3[1:, :, H:].reshape(-1, H).contiguous(), mode=mode,
-                       transA=True, transB=False)
-        assert relerr(dwf, rnn.weight_hh_l0.grad) < btol
-        assert relerr(dwr, rnn.weight_hh_l0_reverse.grad) < btol
-    if mode == "bf16":
-        # The bounds above are against exact fp32 nn.LSTM, i.e. they include the quantisation of the operands.  Against the
-        # bf16-emulating loops (same rounding points: x, W_ih, W_hh, h, dG and -- resident kernels -- the per-tile partial dh)
-        # what is left is summation order and the v_exp/v_rcp activations: hidden states within 1e-3 of the max magnitude,
-        # every gradient within 1e-2 relative L2 (north_star's bf16 bound; measured 1e-3 .. 3e-3).
-        oe, hne, dxe, ge = _emul_layer(rnn, x, lengths, d_out, d_hn, "lstm", tile_partials=resident)
-        assert relerr(fw["hseq"], oe) < 1e-3
-        assert relerr(utt[:, 1], hne[0]) < 1e-3 and relerr(utt[:, 3], hne[1]) < 1e-3
-        assert _l2(dx, dxe) < 1e-2
-        assert _l2(dwih, torch.cat((ge["weight_ih_l0"], ge["weight_ih_l0_reverse"]), 0)) < 1e-2
-        assert _l2(db, torch.cat((ge["bias_ih_l0"], ge["bias_ih_l0_reverse"]), 0)) < 1e-2
+    emul = {}
+    for dG, hseq, tile_partials in [(dG, fw["hseq"], 32 if pair else resident)] + others:
+        dx = ops.gemm(dG, wih.to(d), mode=mode, transB=False).view(T, B, D)
+        assert relerr(dx, x.grad) < btol
+        dwih = ops.gemm(dG, x.detach().reshape(T * B, D).to(d), mode=mode, transA=True, transB=False)
+        assert relerr(dwih, torch.cat((rnn.weight_ih_l0.grad, rnn.weight_ih_l0_reverse.grad), 0)) < btol
+        db = ops.colsum(dG)
+        assert relerr(db, torch.cat((rnn.bias_ih_l0.grad, rnn.bias_ih_l0_reverse.grad), 0)) < btol
+        hseq = hseq.view(T * B, 2 * H)
         if T > 1:
-            assert _l2(dwf, ge["weight_hh_l0"]) < 1e-2 and _l2(dwr, ge["weight_hh_l0_reverse"]) < 1e-2
+            dG3 = dG.view(T, B, 8 * H); hs3 = hseq.view(T, B, 2 * H)
+            dwf = ops.gemm(dG3[1:, :, :4 * H].reshape(-1, 4 * H).contiguous(), hs3[:-1, :, :H].reshape(-1, H).contiguous(), mode=mode,
+                           transA=True, transB=False)
+            dwr = ops.gemm(dG3[:-1, :, 4 * H:].reshape(-1, 4 * H).contiguous(), hs3[1:, :, H:].reshape(-1, H).contiguous(), mode=mode,
+                           transA=True, transB=False)
+            assert relerr(dwf, rnn.weight_hh_l0.grad) < btol
+            assert relerr(dwr, rnn.weight_hh_l0_reverse.grad) < btol
+        if mode == "bf16":
+            # The bounds above are against exact fp32 nn.LSTM, i.e. they include the quantisation of the operands.  Against the
+            # bf16-emulating loops (same rounding points: x, W_ih, W_hh, h, dG and -- resident kernels -- the per-tile partial dh)
+            # what is left is summation order and the v_exp/v_rcp activations: hidden states within 1e-3 of the max magnitude,
+            # every gradient within 1e-2 relative L2 (north_star's bf16 bound; measured 1e-3 .. 3e-3).
+            if tile_partials not in emul:
+                emul[tile_partials] = _emul_layer(rnn, x, lengths, d_out, d_hn, "lstm", tile_partials=tile_partials)
+            oe, hne, dxe, ge = emul[tile_partials]
+            assert relerr(hseq.view(T, B, 2 * H), oe) < 1e-3
+            assert relerr(utt[:, 1], hne[0]) < 1e-3 and relerr(utt[:, 3], hne[1]) < 1e-3
+            assert _l2(dx, dxe) < 1e-2
+            assert _l2(dwih, torch.cat((ge["weight_ih_l0"], ge["weight_ih_l0_reverse"]), 0)) < 1e-2
+            assert _l2(db, torch.cat((ge["bias_ih_l0"], ge["bias_ih_l0_reverse"]), 0)) < 1e-2
+            if T > 1:
+                assert _l2(dwf, ge["weight_hh_l0"]) < 1e-2 and _l2(dwr, ge["weight_hh_l0_reverse"]) < 1e-2
 
 @pytest.mark.parametrize("mode,T,B,H,ragged", [("fp32", 6, 5, 20, True), ("fp32", 9, 33, 74, True), ("bf16", 9, 33, 74, True),
                                                ("fp32", 5, 16, 300, False), ("bf16", 12, 32, 300, True), ("fp32", 1, 3, 35, False),
