@@ -21,6 +21,11 @@ static inline bool mmda_env_set(const char* name) { return getenv(name) != nullp
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// blocks of 256 lanes for a grid-stride loop over `work` items
+static inline int stream_blocks(int64_t work) {
+  const int64_t blocks = (work + 255) / 256;
+  return (int)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks);
+}
 
 // fp32 -> bf16 round-to-nearest-even via the hardware cast (keeps NaN a NaN, MI355X_MICROARCH correctness table)
 __device__ __forceinline__ unsigned short f2bf(float x) {
@@ -145,9 +150,9 @@ __device__ __forceinline__ float act_bwd_p(int act, float x, const mmda_act_para
 }
 
 // ---- sparse update of the embedding table (embed_update = sparse): torch.optim.SparseAdam's rule on the rows a step touches, applied
-// where a row's gradient sum becomes final (norm.hip: the owning workgroup of the short-list scatter; dist.hip: the two levels of the
-// sorted sum).  P / M / V: the table and its two moments; step_size = lr sqrt(1 - b2^t) / (1 - b1^t), made on the host in double
-// (optim.hip: mmda_sparse_adam_args, internal.h); table_rows bounds the ids that are updated.
+// where a row's gradient sum becomes final (embed_rows.hip: the owning workgroup of the short form, the two levels of the sort form).
+// P / M / V: the table and its two moments; step_size = lr sqrt(1 - b2^t) / (1 - b1^t), made on the host in double
+// (mmda_sparse_adam_args); table_rows bounds the ids that are updated.
 struct SparseAdamArgs { float* P; float* M; float* V; int table_rows; float b1, b2, eps, clip, gscale, step_size; };
 // one element: g = clamp(gscale * sum, +-clip), then the update.  eps is added to sqrt(v) itself (SparseAdam), not to
 // sqrt(v / (1 - b2^t)) as in the dense adam1() below.  Every rounding spelled out: both list paths give the same bits from
@@ -159,9 +164,11 @@ __device__ __forceinline__ void sparse_adam1(float& p, float g, float& m, float&
   v = __fmaf_rn(a.b2, v, __fmul_rn(__fmul_rn(1.f - a.b2, g), g));
   p = __fmaf_rn(-a.step_size, __fdiv_rn(m, __fadd_rn(sqrtf(v), a.eps)), p);
 }
-// what the sums do with a finished row element: add it into the dense gradient, or update the table in place
+// what the sums do with a finished row element: add it into the dense gradient, or update the table in place.  begin(): called by
+// every thread of the launch that makes a row's first sums (the short form's one launch, level 1 of the sort form), before anything else
 struct RowAdd {
   float* dW; int accumulate;
+  __device__ __forceinline__ void begin() const {}
   __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
     float* dst = dW + id * D + c;                          // one writer per table row
     *dst = accumulate ? *dst + sum : sum;
@@ -169,6 +176,7 @@ struct RowAdd {
 };
 struct RowSparseAdam {
   SparseAdamArgs a;
+  __device__ __forceinline__ void begin() const {}
   __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
     const int64_t o = id * D + c;                          // one writer per table row
     float p = a.P[o], m = a.M[o], v = a.V[o];
@@ -176,7 +184,7 @@ struct RowSparseAdam {
     a.P[o] = p; a.M[o] = m; a.V[o] = v;
   }
 };
-// ---- dense Adam, one element (optim.hip: the Adam functors under every walker; the deferred table update below)
+// ---- dense Adam, one element (optim.hip: the Adam functors under every walker; embed_rows.hip: the deferred table update below)
 // moments and update from a gradient that is already scaled, clamped (and, under L2 decay, decayed)
 __device__ __forceinline__ void adam1_update(float& p, float g, float& m, float& v, float b1, float b2, float eps, float step_size,
                                              float inv_bc2_sqrt) {
@@ -220,7 +228,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // counted as they are applied, 1, 2, 3 ... since the state was reset (`seq`; the Adam step NUMBER t that makes the bias corrections is
 // the caller's and may skip): row_step[id] is the count of the last update row id has taken, and ring[2 (s % window)],
 // ring[2 (s % window) + 1] keep update s's step_size = lr / (1 - b1^t) and 1 / sqrt(1 - b2^t) -- the floats the dense launch of that
-// update is given -- for the last `window` updates.  A stale row is replayed with adam1(g = 0) update by update (optim.hip), a row of
+// update is given -- for the last `window` updates.  A stale row is replayed with adam1(g = 0) update by update (embed_rows.hip), a row of
 // the batch takes update `seq` here, where its sum becomes final, with the sum the dense scatter would have added into a cleared
 // gradient row.
 struct DenseRowArgs {
@@ -237,6 +245,7 @@ __device__ __forceinline__ void dense_row_record(const DenseRowArgs& a) {
 // requires row id current at seq - 1 (every forward catches the batch's rows up); 0 + sum: what `+=` into the cleared row leaves
 struct RowDenseAdam {
   DenseRowArgs a;
+  __device__ __forceinline__ void begin() const { dense_row_record(a); }
   __device__ __forceinline__ void operator()(int64_t id, int D, int c, float sum) const {
     const int64_t o = id * D + c;                          // one writer per table row
     float p = a.P[o], m = a.M[o], v = a.V[o];

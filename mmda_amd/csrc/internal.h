@@ -22,28 +22,27 @@ bool mmda_ln_bwd_parts_applies(const mmda_ln_bwd_args* a, int n);
 int64_t mmda_ln_parts_floats(const mmda_ln_bwd_args* a, int n);
 int mmda_ln_bwd_parts(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
 int mmda_ln_parts_finish(const mmda_ln_bwd_args* a, int n, float* parts, void* stream);
-// mmda_embed_scatter_add with the batch's lengths (padding positions are skipped); lists of `rows` positions take the sort-based form
-int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream);
-bool mmda_embed_scatter_sorts(int rows);
-// embed_update = sparse over a short id list.  rows (n, D): the gradient rows of the list's positions; lengths / B as in the scatter
-int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                 void* stream);
-// embed_update = deferred over a short id list (n >= 1)
-int mmda_embed_dense_adam_short(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                void* stream);
 
-// ---- dist.hip: the sort-based scatter, whole and in two halves (the sorted id list early, the sums behind the gradient rows), and
-// the sparse update over a long list (sorts it first) or one already sorted by mmda_embed_sort_ids
-int mmda_embed_scatter_sorted(float* dW, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B, void* stream);
+// ---- embed_rows.hip: lists of (id, row) pairs into rows of the embedding table
+// What describes a list: n positions p = t * B + b with ids[p] and the D floats rows[p]; `sorted` (optional): the list as
+// mmda_embed_sort_ids left it; lengths / B (optional): position p is padding, and skipped, when t >= lengths[b].  The list's length and
+// `sorted` decide the form the sums take, inside embed_rows.hip and nowhere else.
+struct EmbedList { const int64_t* ids; const unsigned* sorted; int n, D; const float* rows; const int* lengths; int B; };
+bool mmda_embed_scatter_sorts(int rows);      // an unsorted list of this length is sorted first: worth sorting early, beside a recurrence
+// `sorted` (2 n words: keys, then positions) from the ids of a table of table_rows rows
 int mmda_embed_sort_ids(const int64_t* ids, int n, const int* lengths, int B, int table_rows, unsigned* sorted, void* stream);
-int mmda_embed_scatter_presorted(float* dW, const unsigned* sorted, int n, int D, int table_rows, const float* rows, void* stream);
-int mmda_embed_sparse_adam_sorted(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                  void* stream);
-int mmda_embed_sparse_adam_presorted(const SparseAdamArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
-// the deferred update over a long list (sorts it first) or one already sorted (n >= 1)
-int mmda_embed_dense_adam_sorted(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                 void* stream);
-int mmda_embed_dense_adam_presorted(const DenseRowArgs& ad, const unsigned* sorted, int n, int D, const float* rows, void* stream);
+// one function per row rule (common.h).  Add: dW[id] += the sum of the id's rows; table_rows is read for a sorted list only
+int mmda_embed_list_add(float* dW, const EmbedList& list, int table_rows, void* stream);
+// embed_update = sparse.  SparseAdamArgs from the optimizer's scalars: MMDA_EINVAL for a bad pointer / step
+int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
+                          float clip, float grad_scale, int step);
+int mmda_embed_list_sparse_adam(const SparseAdamArgs& ad, const EmbedList& list, void* stream);
+// embed_update = deferred.  Update `seq` (Adam step number `step`) of the deferred table update for the rows of an id list: the C ABI's
+// mmda_embed_rows_dense_adam with the two things a training step already has, caught-up rows and a sorted list
+int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids,
+                                const unsigned* sorted, int n, int D, const float* rows, const int32_t* lengths, int B, int table_rows,
+                                float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int seq, int step,
+                                bool catch_up, void* stream);
 
 // ---- optim.hip
 int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream);      // two buffers cleared by one launch
@@ -66,15 +65,12 @@ int mmda_grad_norm_launch(const float* g, const float* acc, int64_t n, const Run
 // frozen parameters: mmda_runs_build that merges no two ranges across one of `cuts`
 int64_t mmda_runs_build_cut(const int64_t* begin, const int64_t* len, int n, int64_t bucket_floats, const int64_t* cuts, int n_cuts,
                             mmda_run* out, int* n_out);
-// SparseAdamArgs from the optimizer's scalars; MMDA_EINVAL for a bad pointer / step
-int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
-                          float clip, float grad_scale, int step);
-// update `seq` (Adam step number `step`) of the deferred table update for the rows of an id list (optim.hip; the C ABI's mmda_embed_rows_dense_adam with the two
-// things a training step already has: caught-up rows, a sorted list)
-int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids,
-                                const unsigned* sorted, int n, int D, const float* rows, const int32_t* lengths, int B, int table_rows,
-                                float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int seq, int step,
-                                bool catch_up, void* stream);
+// Adam's bias corrections 1 - beta^t, and from them the two scalars every dense launch of step t is given: lr / (1 - b1^t) and
+// 1 / sqrt(1 - b2^t), in double, rounded once
+struct BiasCorrections { double bc1, bc2; };
+BiasCorrections bias_corrections(float beta1, float beta2, int step);
+struct AdamStepScalars { float step_size, inv_bc2_sqrt; };
+AdamStepScalars adam_step_scalars(float lr, float beta1, float beta2, int step);
 
 // ---- losses.hip
 // mmda_loss_cmd_pairs whose launch, as the last thing it does, sets *flag = value (flag joins, common.h: flag_wait).  Only the

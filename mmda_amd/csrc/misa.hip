@@ -1,6 +1,6 @@
 // Native runtime for one MISA training iteration (reference loop body solver.py:139-186 over models.py:163-285).
 // Host-side C++ only: lays the parameters out in one flat bucket, carves the workspace, and issues the HIP kernels of
-// gemm.hip / lstm.hip / norm.hip / attn.hip / losses.hip / optim.hip in dependency order on one stream.  No device
+// gemm.hip / lstm.hip / norm.hip / embed_rows.hip / attn.hip / losses.hip / optim.hip in dependency order on one stream.  No device
 // memory is owned here; no torch types; no host<->device synchronisation anywhere in a step.
 #include "common.h"
 #include "fused_rows.h"
@@ -292,7 +292,7 @@ Workspace carve(const mmda_misa_config& c, const ParamTable& par, int B, int T) 
   w.ffn_parts = take((int64_t)(FFN / 32) * 6 * BH);      // partial products of the hidden-sliced feed-forward kernels (fused_rows.hip)
   w.ln_parts = take((int64_t)512 * 2 * 2 * (par.mod[0].H + par.mod[1].H + par.mod[2].H));   // <= 512 block partials of the three inter-layer LayerNorms' gamma / beta gradients (norm.hip)
   w.rec_part = take(3 * BH);                             // d_recon W_rec, made beside the backward pass's first stretch for its third (fused_rows.h)
-  w.esort = take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (dist.hip)
+  w.esort = take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (embed_rows.hip)
   w.pg_parts = take((int64_t)B * FUSED_PG_SLOTS * 2 * 128);      // per-sample LayerNorm gamma / beta gradient partials of the fused backward stretches
   w.head_wT = take((int64_t)6 * hs * NC); w.l2_wT = take((int64_t)FFN * hs); w.l1_wT = take((int64_t)hs * FFN);
   w.out_wT = take((int64_t)hs * hs); w.in_wT = take((int64_t)hs * 3 * hs); w.rec_wT = take((int64_t)3 * hs * hs);
@@ -2144,29 +2144,24 @@ void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
     m->eu.take();
     if (!early) { m->eu.set(t_ids, lengths); return; }
   }
+  if (P.embed_update == EU_FROZEN) return;
+  // the list, with the sorted form of it if this pass made one; embed_rows.hip picks the form the sums take
+  const EmbedList list{t_ids, take_sorted(), R, c.d_t, dx, lengths, B};
+  if (rc) return;
   if (P.embed_update == EU_SPARSE) {
     // SparseAdam on the rows the batch touches (common.h)
     SparseAdamArgs ad;
     rc = mmda_sparse_adam_args(&ad, PP(p.embed), m->M1 ? m->M1 + p.embed : nullptr, m->V1 ? m->V1 + p.embed : nullptr, c.vocab, early->lr,
                                m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale, early->step);
-    if (rc) return;
-    const unsigned* sorted = take_sorted();
-    if (rc) return;
-    if (sorted) rc = mmda_embed_sparse_adam_presorted(ad, sorted, R, c.d_t, dx, s);
-    else if (mmda_embed_scatter_sorts(R)) rc = mmda_embed_sparse_adam_sorted(ad, t_ids, R, c.d_t, dx, lengths, B, s);
-    else rc = mmda_embed_sparse_adam_short(ad, t_ids, R, c.d_t, dx, lengths, B, s);
+    if (!rc) rc = mmda_embed_list_sparse_adam(ad, list, s);
   } else if (P.embed_deferred) {
     // dense Adam's step for the rows the batch touches (common.h: RowDenseAdam); every other row takes it when it is next needed
     if (!m->M1 || !m->V1) { rc = MMDA_EINVAL; return; }
-    const unsigned* sorted = take_sorted();
-    if (!rc) rc = deferred_apply(m, t_ids, sorted, lengths, early->lr, m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale,
-                                 early->step, false, s);
-  } else if (P.embed_update == EU_DENSE) {
+    rc = deferred_apply(m, t_ids, list.sorted, lengths, early->lr, m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale,
+                        early->step, false, s);
+  } else {
     // the gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
-    const unsigned* sorted = take_sorted();
-    if (rc) return;
-    if (sorted) rc = mmda_embed_scatter_presorted(GG(p.embed), sorted, R, c.d_t, c.vocab, dx, s);
-    else rc = mmda_embed_scatter_add_masked(GG(p.embed), t_ids, R, c.d_t, dx, lengths, B, s);
+    rc = mmda_embed_list_add(GG(p.embed), list, c.vocab, s);
   }
 }
 }  // namespace

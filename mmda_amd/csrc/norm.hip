@@ -1,5 +1,4 @@
-// Row-wise kernels: LayerNorm forward/backward (wave-per-row shuffle reductions), embedding gather / scatter-add,
-// small elementwise helpers.  All HBM-bound; loads are lane-consecutive (coalesced 256 B per wave instruction).
+// Row-wise kernels: LayerNorm forward/backward (wave-per-row shuffle reductions) and small elementwise helpers.  All HBM-bound; loads are lane-consecutive (coalesced 256 B per wave instruction).
 #include "common.h"
 #include "internal.h"
 #include "rowlocal.h"
@@ -295,127 +294,6 @@ __global__ __launch_bounds__(256) void ln_param_grads_kernel(LnBwdMulti L) {
   }
 }
 
-__global__ void embed_gather_kernel(const float* __restrict__ W, const int64_t* __restrict__ ids, int rows, int dim, float* out) {
-  int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* src = W + ids[row] * (int64_t)dim;
-  float* dst = out + (int64_t)row * dim;
-  for (int i = threadIdx.x & 63; i < dim; i += 64) dst[i] = src[i];
-}
-
-// dW[ids[p]] += dX[p] for every position p, deterministically: one workgroup per position; the workgroup of the FIRST position that
-// holds an id owns that id -- it marks every position with the same id in an LDS bit mask (one pass over the id list), compacts the
-// marks into an ordered list, and its four waves add the rows of four contiguous quarters of that list in position order (eight row
-// loads in flight per lane and dimension group), the quarters' sums are added in order and the total goes to the table row (single
-// writer: no atomics, identical bits on every run; float atomics gave the rows of repeated ids in arrival order).  Lists of up to
-// ES_MAX positions (longer ones take the sort-based path of dist.hip).  `lengths` (optional, with B): position p = t * B + b is padding
-// when t >= lengths[b] -- its row is exactly zero (no gradient flows through padding) and it is skipped, as owner and as contributor:
-// a ragged batch holds the pad id hundreds of times.
-constexpr int ES_MAX = 4096;
-// `fin(id, dim, d, sum)`: what the owner does with element d of the row's finished sum (common.h: RowAdd adds it into the dense gradient,
-// RowSparseAdam updates the table and its moments in place -- embed_update = sparse); max_id: ids from there on are skipped.
-template <class Fin>
-__device__ __forceinline__ void embed_scatter_body(const Fin& fin, int64_t max_id, const int64_t* __restrict__ ids, int rows, int dim,
-                                                   const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
-  __shared__ unsigned mask[ES_MAX / 32];
-  __shared__ unsigned short list[ES_MAX];
-  __shared__ int base[ES_MAX / 32 + 1];
-  __shared__ int earlier;
-  __shared__ float part[3][1024];
-  const int p = blockIdx.x;
-  const int64_t id = ids[p];
-  auto padded = [&](int q) { return lengths != nullptr && (q / B) >= lengths[q % B]; };
-  if (id < 0 || id >= max_id || padded(p)) return;       // block-uniform
-  const int nwords = (rows + 31) / 32;
-  if (threadIdx.x == 0) earlier = 0;
-  for (int i = threadIdx.x; i < nwords; i += 256) mask[i] = 0u;
-  __syncthreads();
-  // one pass over the ids, eight loads in flight per thread
-#pragma unroll 8
-  for (int q = threadIdx.x; q < rows; q += 256)
-    if (ids[q] == id && !padded(q)) atomicOr(&mask[q >> 5], 1u << (q & 31));
-  __syncthreads();
-  for (int i = threadIdx.x; i < (p + 31) / 32; i += 256) {      // an earlier position with this id owns it
-    unsigned m = mask[i];
-    if (32 * i + 32 > p) m &= (1u << (p - 32 * i)) - 1u;
-    if (m) earlier = 1;                                  // benign race: every writer stores 1
-  }
-  __syncthreads();
-  if (earlier) return;                                   // block-uniform
-  // ordered list of the positions >= p that hold the id
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int i = p >> 5; i < nwords; ++i) {
-      base[i] = c;
-      unsigned m = mask[i];
-      if (i == (p >> 5)) m &= ~((1u << (p & 31)) - 1u);
-      c += __builtin_popcount(m);
-    }
-    base[nwords] = c;
-  }
-  __syncthreads();
-  const int total = base[nwords];
-  for (int i = (p >> 5) + threadIdx.x; i < nwords; i += 256) {
-    unsigned m = mask[i];
-    if (i == (p >> 5)) m &= ~((1u << (p & 31)) - 1u);
-    int o = base[i];
-    while (m) { list[o++] = (unsigned short)(32 * i + __builtin_ctz(m)); m &= m - 1; }
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int per = (total + 3) / 4;
-  const int q0 = min(total, wave * per), q1 = min(total, q0 + per);
-  for (int d0 = 0; d0 < dim; d0 += 256) {                // dimension groups of 256: lane handles d0 + lane + 64 j, j < 4
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int q = q0; q < q1; q += 8) {
-      float v[8][4];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int64_t r = list[min(q + u, q1 - 1)];      // (clamped: no load under a branch; the surplus is masked below)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int d = d0 + lane + 64 * j;
-          v[u][j] = dX[r * dim + min(d, dim - 1)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (q + u < q1) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] += v[u][j];
-        }
-    }
-    if (wave > 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) part[wave - 1][lane + 64 * j] = acc[j];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int d = d0 + lane + 64 * j;
-        if (d < dim) fin(id, dim, d, ((acc[j] + part[0][lane + 64 * j]) + part[1][lane + 64 * j]) + part[2][lane + 64 * j]);
-      }
-    }
-    __syncthreads();
-  }
-}
-__global__ __launch_bounds__(256) void embed_scatter_kernel(float* dW, const int64_t* __restrict__ ids, int rows, int dim, const float* __restrict__ dX,
-                                                            const int* __restrict__ lengths, int B) {
-  embed_scatter_body(RowAdd{dW, 1}, INT64_MAX, ids, rows, dim, dX, lengths, B);
-}
-// the same owner, second epilogue: scale, clamp and SparseAdam on row `id` of the table (no dense gradient row is written or read)
-__global__ __launch_bounds__(256) void embed_sparse_adam_kernel(SparseAdamArgs ad, const int64_t* __restrict__ ids, int rows, int dim,
-                                                                const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
-  embed_scatter_body(RowSparseAdam{ad}, (int64_t)ad.table_rows, ids, rows, dim, dX, lengths, B);
-}
-// the same owner, third epilogue: step `ad.step` of dense Adam on row `id` (embed_update = deferred; common.h: RowDenseAdam)
-__global__ __launch_bounds__(256) void embed_dense_adam_kernel(DenseRowArgs ad, const int64_t* __restrict__ ids, int rows, int dim,
-                                                               const float* __restrict__ dX, const int* __restrict__ lengths, int B) {
-  dense_row_record(ad);
-  embed_scatter_body(RowDenseAdam{ad}, (int64_t)ad.table_rows, ids, rows, dim, dX, lengths, B);
-}
-
 __global__ void add_kernel(const float* a, const float* b, float* y, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = a[i] + b[i];
 }
@@ -687,55 +565,6 @@ extern "C" int mmda_layernorm_param_grads(const mmda_ln_bwd_args* a, int n, void
     MMDA_CHECK_LAUNCH("mmda_layernorm_param_grads");
     if (ln_pg_finish(L, (hipStream_t)stream)) return MMDA_ELAUNCH;
   }
-  return MMDA_OK;
-}
-
-extern "C" int mmda_embed_gather(const float* W, const int64_t* ids, int rows, int dim, float* out, void* stream) {
-  if (!W || !ids || !out || rows < 0 || dim <= 0) return MMDA_EINVAL;
-  if (rows == 0) return MMDA_OK;
-  hipLaunchKernelGGL(embed_gather_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, W, ids, rows, dim, out);
-  MMDA_CHECK_LAUNCH("mmda_embed_gather");
-  return MMDA_OK;
-}
-
-extern "C" int mmda_embed_scatter_add(float* dW, const int64_t* ids, int rows, int dim, const float* dX, void* stream) {
-  if (!dW || !ids || !dX || rows < 0 || dim <= 0 || dim > 1024) return MMDA_EINVAL;
-  if (rows == 0) return MMDA_OK;
-  // long lists: sort-based list-order sums (dist.hip) -- the scan below costs rows^2 / 256 id compares (B=256, T=50: 158 us against
-  // 9 us at B=32).
-  return mmda_embed_scatter_add_masked(dW, ids, rows, dim, dX, nullptr, 0, stream);
-}
-
-// (internal) lists of this length take the sort-based form
-constexpr int ES_SORT_MIN = 3072;
-static_assert(ES_SORT_MIN <= ES_MAX, "the scan form holds at most ES_MAX positions");
-bool mmda_embed_scatter_sorts(int rows) { return rows >= ES_SORT_MIN; }
-// (internal, misa.hip) the same with the batch's lengths: positions p = t * B + b with t >= lengths[b] are padding and are skipped
-int mmda_embed_scatter_add_masked(float* dW, const int64_t* ids, int rows, int dim, const float* dX, const int* lengths, int B, void* stream) {
-  if (!dW || !ids || !dX || rows < 0 || dim <= 0 || dim > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
-  if (rows == 0) return MMDA_OK;
-  if (mmda_embed_scatter_sorts(rows)) return mmda_embed_scatter_sorted(dW, ids, rows, dim, dX, lengths, B, stream);
-  hipLaunchKernelGGL(embed_scatter_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dW, ids, rows, dim, dX, lengths, B);
-  MMDA_CHECK_LAUNCH("mmda_embed_scatter_add");
-  return MMDA_OK;
-}
-
-// embed_update = sparse, lists below ES_SORT_MIN positions (the caller chose: mmda_embed_scatter_sorts)
-int mmda_embed_sparse_adam_short(const SparseAdamArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                 void* stream) {
-  if (!ids || !rows || n < 0 || n > ES_MAX || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
-  if (n == 0) return MMDA_OK;
-  hipLaunchKernelGGL(embed_sparse_adam_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ad, ids, n, D, rows, lengths, B);
-  MMDA_CHECK_LAUNCH("mmda_embed_rows_sparse_adam");
-  return MMDA_OK;
-}
-
-// embed_update = deferred, lists below ES_SORT_MIN positions
-int mmda_embed_dense_adam_short(const DenseRowArgs& ad, const int64_t* ids, int n, int D, const float* rows, const int* lengths, int B,
-                                void* stream) {
-  if (!ids || !rows || n <= 0 || n > ES_MAX || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
-  hipLaunchKernelGGL(embed_dense_adam_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ad, ids, n, D, rows, lengths, B);
-  MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam");
   return MMDA_OK;
 }
 

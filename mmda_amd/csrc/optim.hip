@@ -8,6 +8,15 @@
 #include "internal.h"
 #include <math.h>
 
+// ---- Adam's bias corrections and step scalars (internal.h: the rows code of embed_rows.hip makes its scalars from the same two)
+BiasCorrections bias_corrections(float beta1, float beta2, int step) {
+  return {1.0 - pow((double)beta1, (double)step), 1.0 - pow((double)beta2, (double)step)};
+}
+AdamStepScalars adam_step_scalars(float lr, float beta1, float beta2, int step) {
+  const BiasCorrections c = bias_corrections(beta1, beta2, step);
+  return {(float)((double)lr / c.bc1), (float)(1.0 / sqrt(c.bc2))};
+}
+
 namespace {
 
 // ---- the update rules: one element functor per rule
@@ -242,28 +251,6 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* acc, const 
   for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) acc[i] = __fadd_rn(acc[i], g[i]);
 }
 
-// embed_update = sparse under accumulation: a micro-batch's n = T B gradient rows (width D) and ids, appended at position `offset` of a
-// list that outlives the workspace; the id of a padding position (t >= lengths[b], p = t B + b) becomes -1, which the rows update skips.
-// vec: D % 4 == 0 and 16-byte aligned bases, so every row starts on a 16-byte boundary in both buffers (launch-uniform).
-__global__ __launch_bounds__(256) void embed_rows_append_kernel(int64_t* ids_out, float* rows_out, int64_t offset,
-                                                                const int64_t* __restrict__ ids, const float* __restrict__ rows, int n, int D,
-                                                                const int* __restrict__ lengths, int B, int vec) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)n * D;
-  float* dst = rows_out + offset * D;
-  if (vec) {
-    float4* d4 = reinterpret_cast<float4*>(dst);
-    const float4* s4 = reinterpret_cast<const float4*>(rows);
-    for (int64_t i = i0; i < (total >> 2); i += stride) d4[i] = s4[i];
-  } else {
-    for (int64_t i = i0; i < total; i += stride) dst[i] = rows[i];
-  }
-  for (int64_t p = i0; p < n; p += stride) {
-    const bool pad = lengths != nullptr && (int)(p / B) >= lengths[p % B];
-    ids_out[offset + p] = pad ? (int64_t)-1 : ids[p];
-  }
-}
 
 __global__ void mark_rows_kernel(unsigned char* mask, int rows, const int64_t* __restrict__ ids, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -271,67 +258,6 @@ __global__ void mark_rows_kernel(unsigned char* mask, int rows, const int64_t* _
   const int64_t id = ids[i];
   if (id >= 0 && id < rows) mask[id] = 1;
 }
-
-// ---- embed_update = deferred (common.h: DenseRowArgs)
-// updates a + 1 .. t of one row whose gradient was zero in all of them: adam1() with g = 0 and each update's own scalars, in order -- the
-// calls the dense launches of those updates would have made.  One wave; a lane keeps up to RE elements of the row in registers, so the
-// t - a dependent sqrt / div chains of a row run RE at a time.
-constexpr int RE = 5;
-__device__ __forceinline__ void replay_row(float* p, float* m, float* v, int D, int lane, int a, int t, const float* __restrict__ ring,
-                                           int window, float b1, float b2, float eps) {
-  a = max(a, max(t - window, 0));      // memory safety only: the hosts that count the updates (misa.hip, ops.py) flush before a row gets here
-  for (int c0 = 0; c0 < D; c0 += 64 * RE) {
-    float pe[RE], me[RE], ve[RE];
-#pragma unroll
-    for (int k = 0; k < RE; ++k) {
-      const int c = c0 + 64 * k + lane;
-      pe[k] = c < D ? p[c] : 0.f; me[k] = c < D ? m[c] : 0.f; ve[k] = c < D ? v[c] : 0.f;
-    }
-    for (int s = a + 1; s <= t; ++s) {
-      const float step_size = ring[2 * (s % window)], inv_bc2_sqrt = ring[2 * (s % window) + 1];
-#pragma unroll
-      for (int k = 0; k < RE; ++k)
-        if (c0 + 64 * k < D) adam1(pe[k], 0.f, me[k], ve[k], b1, b2, eps, INFINITY, 1.f, step_size, inv_bc2_sqrt);   // wave-uniform
-    }
-#pragma unroll
-    for (int k = 0; k < RE; ++k) {
-      const int c = c0 + 64 * k + lane;
-      if (c < D) { p[c] = pe[k]; m[c] = me[k]; v[c] = ve[k]; }
-    }
-  }
-}
-// the rows of an id list, up to update `t`: one wave per position; the wave whose atomicMax raises row_step[id] owns the
-// row for this launch (an integer claim: one writer per row, no float atomics), every other position of that id sees it current
-__global__ __launch_bounds__(256) void embed_catch_up_kernel(float* P, float* M, float* V, int* row_step, const float* __restrict__ ring,
-                                                             int window, const int64_t* __restrict__ ids, int n, int D,
-                                                             const int* __restrict__ lengths, int B, int table_rows, float b1, float b2,
-                                                             float eps, int t) {
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (p >= n) return;
-  const int64_t id = ids[p];
-  if (id < 0 || id >= table_rows) return;                               // wave-uniform, as everything below
-  if (lengths != nullptr && (p / B) >= lengths[p % B]) return;
-  int a = 0;
-  if (lane == 0) a = atomicMax(row_step + id, t);
-  a = __shfl(a, 0);
-  if (a >= t) return;
-  const int64_t o = id * D;
-  replay_row(P + o, M + o, V + o, D, lane, a, t, ring, window, b1, b2, eps);
-}
-// every stale row of the table, up to update `t`: one wave per row; a table with nothing stale is read (row_step) and not written
-__global__ __launch_bounds__(256) void embed_flush_kernel(float* P, float* M, float* V, int* row_step, const float* __restrict__ ring,
-                                                          int window, int D, int table_rows, float b1, float b2, float eps, int t) {
-  const int lane = threadIdx.x & 63;
-  for (int row = (int)blockIdx.x * 4 + (threadIdx.x >> 6); row < table_rows; row += (int)gridDim.x * 4) {
-    const int a = row_step[row];
-    if (a >= t) continue;                                               // wave-uniform
-    const int64_t o = (int64_t)row * D;
-    replay_row(P + o, M + o, V + o, D, lane, a, t, ring, window, b1, b2, eps);
-    if (lane == 0) row_step[row] = t;
-  }
-}
-// a step that touches no row still leaves its scalars behind
-__global__ void embed_step_record_kernel(DenseRowArgs ad) { dense_row_record(ad); }
 
 // clip_grad_value_ + torch.optim.RMSprop (alpha, eps; no momentum, not centered, no weight decay: the reference constructs its
 // optimizer as config.optimizer(params, lr=...), solver.py:97-99, so every other argument is torch's default)
@@ -362,23 +288,6 @@ __global__ void clamp_kernel(float* g, int64_t n, float clip) {
 }
 
 // ---- host side: what every launcher below shares
-// blocks of 256 lanes for a grid-stride loop over `work` items
-int stream_blocks(int64_t work) {
-  const int64_t blocks = (work + 255) / 256;
-  return (int)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks);
-}
-
-// Adam's bias corrections 1 - beta^t, and from them the two scalars every dense launch of step t is given: lr / (1 - b1^t) and
-// 1 / sqrt(1 - b2^t), in double, rounded once
-struct BiasCorrections { double bc1, bc2; };
-BiasCorrections bias_corrections(float beta1, float beta2, int step) {
-  return {1.0 - pow((double)beta1, (double)step), 1.0 - pow((double)beta2, (double)step)};
-}
-struct AdamStepScalars { float step_size, inv_bc2_sqrt; };
-AdamStepScalars adam_step_scalars(float lr, float beta1, float beta2, int step) {
-  const BiasCorrections c = bias_corrections(beta1, beta2, step);
-  return {(float)((double)lr / c.bc1), (float)(1.0 / sqrt(c.bc2))};
-}
 AdamArgs adam_args(float* p, const float* acc, const float* g, float* m, float* v, const AdamHyper& h) {
   const AdamStepScalars s = adam_step_scalars(h.lr, h.beta1, h.beta2, h.step);
   return {p, acc, g, m, v, h.beta1, h.beta2, h.eps, h.clip, h.grad_scale, s.step_size, s.inv_bc2_sqrt};
@@ -573,20 +482,6 @@ extern "C" int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_a
   return launch_runs("mmda_clamp_rmsprop_runs", RunTable{runs, n_runs, items}, f, kNoWait, stream);
 }
 
-extern "C" int mmda_embed_rows_append(int64_t* ids_out, float* rows_out, int64_t offset, int64_t capacity, const int64_t* ids,
-                                      const float* rows, int n, int D, const int32_t* lengths, int B, void* stream) {
-  if (!ids_out || !rows_out || !ids || !rows || n < 0 || D <= 0 || offset < 0 || capacity < 0 || (lengths && B <= 0)) return MMDA_EINVAL;
-  if (offset > capacity || (int64_t)n > capacity - offset) return MMDA_EINVAL;                 // the list must hold the rows
-  if (((uintptr_t)ids_out | (uintptr_t)ids) & 7 || ((uintptr_t)rows_out | (uintptr_t)rows) & 3) return MMDA_EINVAL;
-  if (n == 0) return MMDA_OK;
-  const int vec = (D & 3) == 0 && (((uintptr_t)rows_out | (uintptr_t)rows) & 15) == 0;
-  const int64_t work = vec ? ((int64_t)n * D) >> 2 : (int64_t)n * D;
-  hipLaunchKernelGGL(embed_rows_append_kernel, dim3(stream_blocks(work)), dim3(256), 0, (hipStream_t)stream, ids_out, rows_out, offset, ids, rows, n,
-                     D, lengths, B, vec);
-  MMDA_CHECK_LAUNCH("mmda_embed_rows_append");
-  return MMDA_OK;
-}
-
 // internal (misa.hip): a[0 .. na) = b[0 .. nb) = 0 in ONE launch (two memsets are two launches of ~5 us each on a latency-bound chain)
 int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream) {
   if (na < 0 || nb < 0 || (na && !a) || (nb && !b)) return MMDA_EINVAL;
@@ -643,106 +538,6 @@ extern "C" int mmda_clamp_adam_rows_opts(float* p, const float* g, float* m, flo
   }
   MMDA_CHECK_LAUNCH("mmda_clamp_adam_rows_opts");
   return MMDA_OK;
-}
-
-// internal: the scalars of one SparseAdam step.  torch.optim.SparseAdam: step_size = lr sqrt(1 - b2^t) / (1 - b1^t), in double here,
-// once per step (the dense launch keeps its two scalars lr / bc1 and 1 / sqrt(bc2): its eps sits elsewhere)
-int mmda_sparse_adam_args(SparseAdamArgs* out, float* P, float* M, float* V, int table_rows, float lr, float beta1, float beta2, float eps,
-                          float clip, float grad_scale, int step) {
-  if (!out || !P || !M || !V || table_rows <= 0 || step < 1) return MMDA_EINVAL;
-  const BiasCorrections c = bias_corrections(beta1, beta2, step);
-  *out = SparseAdamArgs{P, M, V, table_rows, beta1, beta2, eps, clip, grad_scale, (float)((double)lr * sqrt(c.bc2) / c.bc1)};
-  return MMDA_OK;
-}
-
-extern "C" int mmda_embed_rows_sparse_adam(float* P, float* M, float* V, const int64_t* ids, int n, int D, const float* rows,
-                                           const int32_t* lengths, int B, int table_rows, float lr, float beta1, float beta2, float eps,
-                                           float clip, float grad_scale, int step, void* stream) {
-  if (!ids || !rows || n < 0 || D <= 0 || D > 1024 || (lengths && B <= 0)) return MMDA_EINVAL;
-  SparseAdamArgs ad;
-  const int rc = mmda_sparse_adam_args(&ad, P, M, V, table_rows, lr, beta1, beta2, eps, clip, grad_scale, step);
-  if (rc) return rc;
-  if (n == 0) return MMDA_OK;
-  // the list length picks the form exactly as the dense scatter does (mmda_embed_scatter_add_masked)
-  if (mmda_embed_scatter_sorts(n)) return mmda_embed_sparse_adam_sorted(ad, ids, n, D, rows, lengths, B, stream);
-  return mmda_embed_sparse_adam_short(ad, ids, n, D, rows, lengths, B, stream);
-}
-
-// ---- embed_update = deferred: host side
-extern "C" int64_t mmda_embed_deferred_scalar_floats(int window) { return window < 1 ? MMDA_EINVAL : 2 * (int64_t)window; }
-
-extern "C" int mmda_embed_deferred_reset(int32_t* row_step, int table_rows, void* stream) {
-  if (!row_step || table_rows <= 0) return MMDA_EINVAL;
-  if (hipMemsetAsync(row_step, 0, sizeof(int32_t) * (size_t)table_rows, (hipStream_t)stream) != hipSuccess) return MMDA_ELAUNCH;
-  return MMDA_OK;
-}
-
-static bool deferred_state_ok(const float* P, const float* M, const float* V, const int32_t* row_step, const float* step_scalars, int window,
-                              int D, int table_rows) {
-  return P && M && V && row_step && step_scalars && window >= 1 && D > 0 && D <= 1024 && table_rows > 0;
-}
-
-extern "C" int mmda_embed_rows_catch_up(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window,
-                                        const int64_t* ids, int n, int D, const int32_t* lengths, int B, int table_rows, float beta1,
-                                        float beta2, float eps, int upto, void* stream) {
-  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || !ids || n < 0 || (lengths && B <= 0) || upto < 0)
-    return MMDA_EINVAL;
-  if (n == 0 || upto == 0) return MMDA_OK;
-  hipLaunchKernelGGL(embed_catch_up_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, (hipStream_t)stream, P, M, V, row_step, step_scalars, window,
-                     ids, n, D, lengths, B, table_rows, beta1, beta2, eps, upto);
-  MMDA_CHECK_LAUNCH("mmda_embed_rows_catch_up");
-  return MMDA_OK;
-}
-
-extern "C" int mmda_embed_rows_flush(float* P, float* M, float* V, int32_t* row_step, const float* step_scalars, int window, int D,
-                                     int table_rows, float beta1, float beta2, float eps, int upto, void* stream) {
-  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || upto < 0) return MMDA_EINVAL;
-  if (upto == 0) return MMDA_OK;
-  int blocks = ceil_div(table_rows, 4);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(embed_flush_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P, M, V, row_step, step_scalars, window, D,
-                     table_rows, beta1, beta2, eps, upto);
-  MMDA_CHECK_LAUNCH("mmda_embed_rows_flush");
-  return MMDA_OK;
-}
-
-// internal (misa.hip): update number `seq` (the count of updates since the reset, last + 1), made with Adam step number `step`, for
-// the rows of an id list.  Counts that are multiples of the window flush the table first: the slot this update's scalars take is then
-// needed by no row.  catch_up: bring the list's rows to seq - 1 first (a forward of the same
-// batch has done so already inside a training step).  sorted != nullptr: the list as mmda_embed_sort_ids left it.
-int mmda_embed_dense_adam_apply(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window, const int64_t* ids,
-                                const unsigned* sorted, int n, int D, const float* rows, const int32_t* lengths, int B, int table_rows,
-                                float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int seq, int step,
-                                bool catch_up, void* stream) {
-  if (!deferred_state_ok(P, M, V, row_step, step_scalars, window, D, table_rows) || !ids || !rows || n < 0 || (lengths && B <= 0) ||
-      step < 1 || seq < 1)
-    return MMDA_EINVAL;
-  const AdamStepScalars sc = adam_step_scalars(lr, beta1, beta2, step);                      // the dense launch's two scalars
-  const DenseRowArgs ad{P, M, V, row_step, step_scalars, window, table_rows, beta1, beta2, eps, clip, grad_scale, sc.step_size,
-                        sc.inv_bc2_sqrt, seq};
-  int rc = MMDA_OK;
-  if (seq % window == 0)
-    rc = mmda_embed_rows_flush(P, M, V, row_step, step_scalars, window, D, table_rows, beta1, beta2, eps, seq - 1, stream);
-  else if (catch_up)
-    rc = mmda_embed_rows_catch_up(P, M, V, row_step, step_scalars, window, ids, n, D, lengths, B, table_rows, beta1, beta2, eps, seq - 1,
-                                  stream);
-  if (rc) return rc;
-  if (n == 0) {
-    hipLaunchKernelGGL(embed_step_record_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ad);
-    MMDA_CHECK_LAUNCH("mmda_embed_rows_dense_adam/record");
-    return MMDA_OK;
-  }
-  if (sorted) return mmda_embed_dense_adam_presorted(ad, sorted, n, D, rows, stream);
-  if (mmda_embed_scatter_sorts(n)) return mmda_embed_dense_adam_sorted(ad, ids, n, D, rows, lengths, B, stream);
-  return mmda_embed_dense_adam_short(ad, ids, n, D, rows, lengths, B, stream);
-}
-
-extern "C" int mmda_embed_rows_dense_adam(float* P, float* M, float* V, int32_t* row_step, float* step_scalars, int window,
-                                          const int64_t* ids, int n, int D, const float* rows, const int32_t* lengths, int B,
-                                          int table_rows, float lr, float beta1, float beta2, float eps, float clip, float grad_scale,
-                                          int seq, int step, void* stream) {
-  return mmda_embed_dense_adam_apply(P, M, V, row_step, step_scalars, window, ids, nullptr, n, D, rows, lengths, B, table_rows, lr, beta1,
-                                     beta2, eps, clip, grad_scale, seq, step, true, stream);
 }
 
 extern "C" int mmda_clamp(float* g, int64_t n, float clip, void* stream) {
