@@ -451,7 +451,7 @@ int mmda_loss_diff_pairs(const float* x, int64_t stride, int nt, int np, const i
                          float* loss, float* dx, float* work, void* stream);
 /* cmd: solver.py:409-420 + functions.py:88-109 over shared_t, shared_v, shared_a = x + k*stride (k=0..2), 5 moments */
 int mmda_loss_cmd(const float* x, int64_t stride, int B, int D, float scale, float* loss, float* dx, void* stream);
-/* general form: nt (2..3) tensors, np pairs, n_moments (1..5); *loss += value_scale * sum over pairs; gradients are
+/* general form: nt (2..3) tensors, np (1..6) pairs, n_moments (1..5), D <= 512; *loss += value_scale * sum over pairs; gradients are
  * scaled by scale*value_scale.  utils.CMD()(x1, x2, n) (functions.py:88-109) is nt=2, pairs={0,1}, value_scale=1. */
 int mmda_loss_cmd_pairs(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D,
                         float scale, float value_scale, float* loss, float* dx, void* stream);
@@ -474,6 +474,27 @@ int mmda_loss_misc(const float* scores, const float* tcp, const float* emo, int 
  * (N, C) fp32, an entry counts as set when > 0.  C <= 16.  One read-back per evaluation pass instead of one per batch. */
 int mmda_eval_accumulate(const float* pred, const float* truth, int N, int C, double* state, void* stream);
 int mmda_loss_domain(const float* dom, int B, float scale, float* loss, float* ddom, void* stream);
+/* A read-only view of which kernel form the loss entry points above pick for a shape.  Host code only: no launch, no device call.
+ * The launchers take their decisions from the same functions, so what this reports is what runs.
+ *   B, D               rows and columns of one tensor
+ *   have_loss, have_dx whether the call passes `loss` / `dx` (NULL or not)
+ *   cmd_nt             tensors of the CMD call (2..3; the stream form launches one workgroup per tensor when dx is given)
+ *   n_recon            elements of the recon call; <= 0 stands for 3 * B * D (the model's three contiguous tensors) */
+enum { MMDA_LOSS_DIFF_GENERIC = 0, MMDA_LOSS_DIFF_FAST4, MMDA_LOSS_DIFF_FAST8, MMDA_LOSS_DIFF_FAST16, MMDA_LOSS_DIFF_FAST32 };
+enum { MMDA_LOSS_DIFF_SKINNY = 0, MMDA_LOSS_DIFF_BATCHED = 1 };
+enum { MMDA_LOSS_DIFF_SUM_NONE = 0, MMDA_LOSS_DIFF_SUM_FINISH, MMDA_LOSS_DIFF_SUM_OWN_LAUNCH };
+enum { MMDA_LOSS_CMD_FAST4 = 0, MMDA_LOSS_CMD_FAST8, MMDA_LOSS_CMD_STREAM, MMDA_LOSS_CMD_SERIAL, MMDA_LOSS_CMD_REJECT };
+typedef struct mmda_loss_forms {
+  int diff_form;                     /* MMDA_LOSS_DIFF_GENERIC / FAST*: the prep and the finish kernel */
+  int diff_products;                 /* MMDA_LOSS_DIFF_SKINNY (row-skinny launches) or MMDA_LOSS_DIFF_BATCHED (one mmda_gemm) */
+  int diff_loss_sum;                 /* MMDA_LOSS_DIFF_SUM_*: who adds the combine launch's loss partials (NONE: loss == NULL) */
+  int diff_combine_blocks;           /* workgroups of the combine launch = loss partials */
+  int cmd_form;                      /* MMDA_LOSS_CMD_*; REJECT: the call returns MMDA_EINVAL */
+  int cmd_grid;                      /* workgroups of the CMD launch (0 when rejected) */
+  int recon_blocks;                  /* workgroups of mmda_loss_recon's launch over n_recon contiguous elements */
+  int misc_recon_blocks;             /* recon workgroups of mmda_loss_misc for n_recon elements */
+} mmda_loss_forms;
+int mmda_loss_forms_describe(int B, int D, int have_loss, int have_dx, int cmd_nt, int64_t n_recon, mmda_loss_forms* out);
 
 /* ---------------------------------------------------------------------------------------------- threshold calibration
  * The decision is labels = scores > threshold (reference models.py:249).  A sweep counts, for EVERY cut-off of a grid at once, what

@@ -103,6 +103,12 @@ class LstmPlan(C.Structure):
                 ("kernel", C.c_int)]
 
 
+class LossForms(C.Structure):
+    """mmda_loss_forms: which kernel form the loss entry points pick for a shape"""
+    _fields_ = [("diff_form", C.c_int), ("diff_products", C.c_int), ("diff_loss_sum", C.c_int), ("diff_combine_blocks", C.c_int),
+                ("cmd_form", C.c_int), ("cmd_grid", C.c_int), ("recon_blocks", C.c_int), ("misc_recon_blocks", C.c_int)]
+
+
 class GruPadJob(C.Structure):
     _fields_ = [("H", C.c_int), ("D", C.c_int), ("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2),
                 ("b_hh", C.c_void_p * 2), ("pw_ih", C.c_void_p), ("pw_hh", C.c_void_p * 2), ("pb_ih", C.c_void_p), ("pb_hh", C.c_void_p)]
@@ -229,6 +235,7 @@ SIGNATURES = {
     "mmda_calib_select": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "mmda_eval_accumulate_thr": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mmda_loss_domain": (_I, [_P, _I, _F, _P, _P, _P]),
+    "mmda_loss_forms_describe": (_I, [_I, _I, _I, _I, _I, _I64, C.POINTER(LossForms)]),
     "mmda_clamp_adam": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_clamp_adam_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_embed_rows_sparse_adam": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),

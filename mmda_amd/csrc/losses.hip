@@ -475,6 +475,16 @@ __global__ __launch_bounds__(256) void cmd_kernel(const float* __restrict__ x, i
   }
 }
 
+// The fast and the stream form keep the moment differences and norms of pairs 0..2 in registers (the model's calls have three pairs).
+// A list may hold six: for pairs 3..5 the difference is taken again from the moments where it is needed, under a launch-uniform branch,
+// so the three-pair path keeps its registers and its bits.
+__device__ __forceinline__ float cmd_pair_diff(const PairList& pl, const float (&mom)[3][5], int p, int k) {
+  float a = 0.f, b = 0.f;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) { a = (pl.a[p] == t) ? mom[t][k] : a; b = (pl.b[p] == t) ? mom[t][k] : b; }
+  return a - b;
+}
+
 // Parallel form of cmd_kernel for the training shapes (nt <= 3 tensors, D <= 128 columns, B <= 64 rows): 1024 threads =
 // 128 columns x 8 row groups, every element is loaded once and stays in registers through the three passes (mean, central
 // moments, gradient); cross-row reductions go through LDS.  cmd_kernel walks the rows serially per (tensor, column) with
@@ -485,7 +495,7 @@ __device__ __forceinline__ void cmd_fast_body(const float* __restrict__ x, int64
   extern __shared__ float sm[];
   float* P1 = sm;                                // [8][3][128]
   float* P2 = sm + 8 * 3 * 128;                  // [8][3][4][128]
-  float* N2 = P2 + 8 * 3 * 4 * 128;              // [2][16] per-wave partial squared norms
+  float* N2 = P2 + 8 * 3 * 4 * 128;              // [2][32] per-wave partial squared norms, [pair 0..5][moment]
   const int tid = threadIdx.x, c = tid & 127, rg = tid >> 7;
   const int cc = min(c, D - 1);
   const bool c_ok = c < D;
@@ -555,8 +565,18 @@ __device__ __forceinline__ void cmd_fast_body(const float* __restrict__ x, int64
 #pragma unroll
       for (int k = 0; k < 5; ++k) {
         const float s = wave_sum(dk[p][k] * dk[p][k]);
-        if ((tid & 63) == 0) N2[(tid >> 6) * 16 + p * 5 + k] = s;
+        if ((tid & 63) == 0) N2[(tid >> 6) * 32 + p * 5 + k] = s;
       }
+    if (pl.np > 3) {                                     // uniform
+#pragma unroll
+      for (int p = 3; p < 6; ++p)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+          const float d = (p < pl.np && k < nmom && c_ok) ? cmd_pair_diff(pl, mom, p, k) : 0.f;
+          const float s = wave_sum(d * d);
+          if ((tid & 63) == 0) N2[(tid >> 6) * 32 + p * 5 + k] = s;
+        }
+    }
   }
   __syncthreads();
   float nrm[3][5], total = 0.f;
@@ -564,9 +584,16 @@ __device__ __forceinline__ void cmd_fast_body(const float* __restrict__ x, int64
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      nrm[p][k] = sqrtf(N2[p * 5 + k] + N2[16 + p * 5 + k]);
+      nrm[p][k] = sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
       if (p < pl.np && k < nmom) total += nrm[p][k];
     }
+  if (pl.np > 3) {                                       // uniform
+#pragma unroll
+    for (int p = 3; p < 6; ++p)
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+        if (p < pl.np && k < nmom) total += sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
+  }
   if (tid == 0 && loss) atomicAdd(loss, total * vscale);
   if (!dx) return;
   float U[3][5];
@@ -584,6 +611,18 @@ __device__ __forceinline__ void cmd_fast_body(const float* __restrict__ x, int64
         for (int t = 0; t < 3; ++t) U[t][k] += (pl.a[p] == t ? u : 0.f) - (pl.b[p] == t ? u : 0.f);
       }
     }
+  if (pl.np > 3) {                                       // uniform
+#pragma unroll
+    for (int p = 3; p < 6; ++p)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        if (p < pl.np && k < nmom) {
+          const float u = (c_ok ? cmd_pair_diff(pl, mom, p, k) : 0.f) / sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
+#pragma unroll
+          for (int t = 0; t < 3; ++t) U[t][k] += (pl.a[p] == t ? u : 0.f) - (pl.b[p] == t ? u : 0.f);
+        }
+      }
+  }
   const float gs = scale * vscale / B;
   float old[3][CMD_RPT];
 #pragma unroll
@@ -629,7 +668,7 @@ __global__ __launch_bounds__(1024) void cmd_stream_kernel(const float* __restric
   extern __shared__ float sm[];
   float* P1 = sm;                                // [8][3][128]
   float* P2 = sm + 8 * 3 * 128;                  // [8][3][4][128]
-  float* N2 = P2 + 8 * 3 * 4 * 128;              // [2][16] per-wave partial squared norms
+  float* N2 = P2 + 8 * 3 * 4 * 128;              // [2][32] per-wave partial squared norms, [pair 0..5][moment]
   const int tid = threadIdx.x, c = tid & 127, rg = tid >> 7;
   const int cc = min(c, D - 1);
   const bool c_ok = c < D;
@@ -715,8 +754,18 @@ __global__ __launch_bounds__(1024) void cmd_stream_kernel(const float* __restric
 #pragma unroll
       for (int k = 0; k < 5; ++k) {
         const float s = wave_sum(dk[p][k] * dk[p][k]);
-        if ((tid & 63) == 0) N2[(tid >> 6) * 16 + p * 5 + k] = s;
+        if ((tid & 63) == 0) N2[(tid >> 6) * 32 + p * 5 + k] = s;
       }
+    if (pl.np > 3) {                                     // uniform
+#pragma unroll
+      for (int p = 3; p < 6; ++p)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+          const float d = (p < pl.np && k < nmom && c_ok) ? cmd_pair_diff(pl, mom, p, k) : 0.f;
+          const float s = wave_sum(d * d);
+          if ((tid & 63) == 0) N2[(tid >> 6) * 32 + p * 5 + k] = s;
+        }
+    }
   }
   __syncthreads();
   float nrm[3][5], total = 0.f;
@@ -724,9 +773,16 @@ __global__ __launch_bounds__(1024) void cmd_stream_kernel(const float* __restric
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      nrm[p][k] = sqrtf(N2[p * 5 + k] + N2[16 + p * 5 + k]);
+      nrm[p][k] = sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
       if (p < pl.np && k < nmom) total += nrm[p][k];
     }
+  if (pl.np > 3) {                                       // uniform
+#pragma unroll
+    for (int p = 3; p < 6; ++p)
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+        if (p < pl.np && k < nmom) total += sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
+  }
   if (tid == 0 && loss && blockIdx.x == 0) atomicAdd(loss, total * vscale);      // (single adder: every workgroup holds the same total)
   if (!dx) return;
   float U[3][5];
@@ -744,6 +800,18 @@ __global__ __launch_bounds__(1024) void cmd_stream_kernel(const float* __restric
         for (int t = 0; t < 3; ++t) U[t][k] += (pl.a[p] == t ? u : 0.f) - (pl.b[p] == t ? u : 0.f);
       }
     }
+  if (pl.np > 3) {                                       // uniform
+#pragma unroll
+    for (int p = 3; p < 6; ++p)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        if (p < pl.np && k < nmom) {
+          const float u = (c_ok ? cmd_pair_diff(pl, mom, p, k) : 0.f) / sqrtf(N2[p * 5 + k] + N2[32 + p * 5 + k]);
+#pragma unroll
+          for (int t = 0; t < 3; ++t) U[t][k] += (pl.a[p] == t ? u : 0.f) - (pl.b[p] == t ? u : 0.f);
+        }
+      }
+  }
   const float gs = scale * vscale / B;
   if (gridDim.x > 1) {
     // One workgroup per tensor (large batches): every workgroup walked the moments of all tensors -- a single workgroup pulls its
@@ -947,17 +1015,49 @@ struct DiffWork {
 // launch -- adds the loss partials itself.
 constexpr int DIFF_FEW_ROWS = 256;
 constexpr int FAST_COLS = 128;                    // columns of the fast forms, DiffLoss and CMD
+constexpr int CMD_SERIAL_COLS = 512;              // the serial CMD form keeps 30 * D floats in LDS: 60 KB at this many columns
+
+// Which form a loss call takes for its shape: THE decision, read by the launchers below and by mmda_loss_forms_describe.
+struct DiffForms {
+  int form;                                       // MMDA_LOSS_DIFF_GENERIC / FAST4 / FAST8 / FAST16 / FAST32 (rows per thread 4 .. 32)
+  bool skinny;                                    // the products as row-skinny launches, else one batched mmda_gemm
+  int sum;                                        // MMDA_LOSS_DIFF_SUM_*
+  int blocks;                                     // of the combine launch
+};
+DiffForms diff_forms(int B, int D, bool have_loss, bool have_dx) {
+  DiffForms f;
+  const bool few_rows = B <= DIFF_FEW_ROWS;
+  f.form = !(D <= FAST_COLS && few_rows) ? MMDA_LOSS_DIFF_GENERIC
+           : (B <= 32 ? MMDA_LOSS_DIFF_FAST4 : (B <= 64 ? MMDA_LOSS_DIFF_FAST8 : (B <= 128 ? MMDA_LOSS_DIFF_FAST16 : MMDA_LOSS_DIFF_FAST32)));
+  f.skinny = few_rows;
+  f.sum = !have_loss ? MMDA_LOSS_DIFF_SUM_NONE : (have_dx && few_rows ? MMDA_LOSS_DIFF_SUM_FINISH : MMDA_LOSS_DIFF_SUM_OWN_LAUNCH);
+  const int64_t b = ((int64_t)B * B + 255) / 256;
+  f.blocks = (int)(b > 256 ? 256 : b);
+  return f;
+}
+struct CmdForms { int form, grid; };              // MMDA_LOSS_CMD_*; workgroups
+CmdForms cmd_forms(int B, int D, int nt, bool have_dx) {
+  if (D > CMD_SERIAL_COLS) return CmdForms{MMDA_LOSS_CMD_REJECT, 0};
+  if (D > FAST_COLS) return CmdForms{MMDA_LOSS_CMD_SERIAL, 1};
+  if (B <= 32) return CmdForms{MMDA_LOSS_CMD_FAST4, 1};
+  if (B <= 64) return CmdForms{MMDA_LOSS_CMD_FAST8, 1};
+  return CmdForms{MMDA_LOSS_CMD_STREAM, have_dx ? nt : 1};
+}
+int recon_blocks_of(int64_t n) { const int64_t b = (n + 255) / 256; return (int)(b > 64 ? 64 : b); }
+// (mmda_loss_misc: eight elements per thread at least: the last workgroup adds the partials one after the other, and 3 x 32 x 128
+//  elements do not need 64 of them)
+int misc_recon_blocks_of(int64_t n) { const int64_t b = (n + 2047) / 2048; return (int)(b > 64 ? 64 : (b < 1 ? 1 : b)); }
 
 // the fast DiffLoss kernels at rows per thread 4 / 8 / 16 / 32 (B <= 32 / 64 / 128 / 256)
 typedef void (*DiffPrepKernel)(const float*, int64_t, int, int, float*, float*, float*);
 typedef void (*DiffFinishKernel)(const float*, const float*, int, int, int64_t, float*, const float*, int, float*);
 struct DiffFastKernels { DiffPrepKernel prep; DiffFinishKernel finish; };
-DiffFastKernels pick_diff_fast(int B) {
+DiffFastKernels pick_diff_fast(int form) {        // form: one of the four MMDA_LOSS_DIFF_FAST*
   static const DiffPrepKernel prep[4] = {diff_prep_fast_kernel<4>, diff_prep_fast_kernel<8>, diff_prep_fast_kernel<16>,
                                          diff_prep_fast_kernel<32>};
   static const DiffFinishKernel finish[4] = {diff_finish_fast_kernel<4>, diff_finish_fast_kernel<8>, diff_finish_fast_kernel<16>,
                                              diff_finish_fast_kernel<32>};
-  const int i = B <= 32 ? 0 : (B <= 64 ? 1 : (B <= 128 ? 2 : 3));
+  const int i = form - MMDA_LOSS_DIFF_FAST4;
   return DiffFastKernels{prep[i], finish[i]};
 }
 
@@ -984,9 +1084,9 @@ extern "C" int mmda_loss_diff_pairs(const float* x, int64_t stride, int nt, int 
   if (!x || !work || B <= 0 || D <= 0 || !fill_pairs(pl, nt, np, pairs_host, 6)) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const DiffWork w(work, B, D);
-  const bool few_rows = B <= DIFF_FEW_ROWS;
-  const bool fast = D <= FAST_COLS && few_rows;
-  const DiffFastKernels fk = pick_diff_fast(B);
+  const DiffForms df = diff_forms(B, D, loss != nullptr, dx != nullptr);
+  const bool fast = df.form != MMDA_LOSS_DIFF_GENERIC;
+  const DiffFastKernels fk = fast ? pick_diff_fast(df.form) : DiffFastKernels{nullptr, nullptr};
   if (fast) hipLaunchKernelGGL(fk.prep, dim3(nt), dim3(1024), 0, s, x, stride, B, D, w.Ahat, w.invn, w.mean);
   else hipLaunchKernelGGL(diff_prep_kernel, dim3(nt), dim3(256), 0, s, x, stride, B, D, w.Ahat, w.invn, w.mean);
   MMDA_CHECK_LAUNCH("mmda_loss_diff/prep");
@@ -997,17 +1097,17 @@ extern "C" int mmda_loss_diff_pairs(const float* x, int64_t stride, int nt, int 
   g.A = w.Ahat; g.lda = D; g.strideA = BD;
   g.B = w.Ahat; g.ldb = D; g.strideB = BD;
   g.C = w.K; g.ldc = B; g.strideC = BB;
-  int rc = diff_products(g, few_rows, stream);
+  int rc = diff_products(g, df.skinny, stream);
   if (rc) return rc;
-  int blocks = (int)((BB + 255) / 256); if (blocks > 256) blocks = 256;
+  const int blocks = df.blocks;
   // the loss value: one partial per block (per-stream scratch), added in block order -- by the finish launch below when it follows with
   // nothing but a row-skinny GEMM in between (which takes no scratch), else by a launch of its own right here
   float* lparts = loss ? mmda_scratch_get(s, sizeof(float) * 256) : nullptr;
   if (loss && !lparts) return MMDA_ELAUNCH;
   hipLaunchKernelGGL(diff_combine_kernel, dim3(blocks), dim3(256), 0, s, w.K, B, D, scale, lparts, w.Ksum, pl);
   MMDA_CHECK_LAUNCH("mmda_loss_diff/combine");
-  const bool sum_later = loss && dx && few_rows;
-  if (loss && !sum_later) {
+  const bool sum_later = df.sum == MMDA_LOSS_DIFF_SUM_FINISH;
+  if (df.sum == MMDA_LOSS_DIFF_SUM_OWN_LAUNCH) {
     hipLaunchKernelGGL(loss_parts_finish_kernel, dim3(1), dim3(64), 0, s, lparts, blocks, loss);
     MMDA_CHECK_LAUNCH("mmda_loss_diff/loss");
   }
@@ -1019,7 +1119,7 @@ extern "C" int mmda_loss_diff_pairs(const float* x, int64_t stride, int nt, int 
   h.A = w.Ksum; h.lda = B; h.strideA = BB;
   h.B = w.Ahat; h.ldb = D; h.strideB = BD;
   h.C = w.dA; h.ldc = D; h.strideC = BD;
-  rc = diff_products(h, few_rows, stream);
+  rc = diff_products(h, df.skinny, stream);
   if (rc) return rc;
   if (fast) hipLaunchKernelGGL(fk.finish, dim3(nt), dim3(1024), 0, s, w.dA, w.invn, B, D, stride, dx, lparts, blocks, loss_later);
   else hipLaunchKernelGGL(diff_finish_kernel, dim3(nt), dim3(256), 0, s, w.dA, w.invn, B, D, stride, dx, lparts, blocks, loss_later);
@@ -1036,12 +1136,15 @@ extern "C" int mmda_loss_diff(const float* x, int64_t stride, int B, int D, floa
 
 namespace {
 typedef void (*CmdFastKernel)(const float*, int64_t, int, int, float, float, float*, float*, PairList, int, unsigned*, unsigned);
-CmdFastKernel pick_cmd_fast(int B) { return B <= 32 ? cmd_fast_kernel<4> : cmd_fast_kernel<8>; }      // rows per thread
-constexpr size_t CMD_FAST_LDS = sizeof(float) * (8 * 3 * 128 + 8 * 3 * 4 * 128 + 32);                // P1, P2, N2 of the fast forms
+CmdFastKernel pick_cmd_fast(int form) { return form == MMDA_LOSS_CMD_FAST4 ? cmd_fast_kernel<4> : cmd_fast_kernel<8>; }      // rows per thread
+constexpr size_t CMD_FAST_LDS = sizeof(float) * (8 * 3 * 128 + 8 * 3 * 4 * 128 + 64);               // P1, P2, N2 of the fast forms
 }  // namespace
 
 // internal: whether a CMD call of this shape takes the single-workgroup form, the one that can set a flag-join word behind its stores
-bool mmda_loss_cmd_sets_flag(int B, int D) { return D <= FAST_COLS && B <= 64; }
+bool mmda_loss_cmd_sets_flag(int B, int D) {
+  const int form = cmd_forms(B, D, 3, true).form;
+  return form == MMDA_LOSS_CMD_FAST4 || form == MMDA_LOSS_CMD_FAST8;
+}
 
 // internal (misa.hip): mmda_loss_cmd_pairs that sets *flag = value at the end of its launch (flag == nullptr: the plain call)
 int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
@@ -1049,22 +1152,23 @@ int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, con
   PairList pl;                                            // (at most three tensors: what the fast forms hold)
   if (!x || B <= 0 || D <= 0 || n_moments < 1 || n_moments > 5 || !fill_pairs(pl, nt, np, pairs_host, 3)) return MMDA_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (mmda_loss_cmd_sets_flag(B, D)) {
-    hipLaunchKernelGGL(pick_cmd_fast(B), dim3(1), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments,
+  const CmdForms cf = cmd_forms(B, D, nt, dx != nullptr);
+  if (cf.form == MMDA_LOSS_CMD_REJECT) return MMDA_EINVAL;
+  if (cf.form == MMDA_LOSS_CMD_FAST4 || cf.form == MMDA_LOSS_CMD_FAST8) {
+    hipLaunchKernelGGL(pick_cmd_fast(cf.form), dim3(cf.grid), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments,
                        flag, value);
     MMDA_CHECK_LAUNCH("mmda_loss_cmd");
     return MMDA_OK;
   }
   if (flag) return MMDA_EINVAL;                           // no other form sets it: the waiting kernel would run into its poll limit
-  if (D <= FAST_COLS) {
-    hipLaunchKernelGGL(cmd_stream_kernel, dim3(dx ? nt : 1), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl,
+  if (cf.form == MMDA_LOSS_CMD_STREAM) {
+    hipLaunchKernelGGL(cmd_stream_kernel, dim3(cf.grid), dim3(1024), CMD_FAST_LDS, s, x, stride, B, D, scale, value_scale, loss, dx, pl,
                        n_moments);
     MMDA_CHECK_LAUNCH("mmda_loss_cmd");
     return MMDA_OK;
   }
-  size_t lds = sizeof(float) * 30 * D;
-  if (lds > 60 * 1024) return MMDA_EINVAL;
-  hipLaunchKernelGGL(cmd_kernel, dim3(1), dim3(256), lds, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments);
+  const size_t lds = sizeof(float) * 30 * D;              // (D <= CMD_SERIAL_COLS: 60 KB at the most)
+  hipLaunchKernelGGL(cmd_kernel, dim3(cf.grid), dim3(256), lds, s, x, stride, B, D, scale, value_scale, loss, dx, pl, n_moments);
   MMDA_CHECK_LAUNCH("mmda_loss_cmd");
   return MMDA_OK;
 }
@@ -1088,7 +1192,7 @@ extern "C" int mmda_loss_recon(const float* recon, const float* orig, int64_t st
   const int nl = (stride == n) ? 1 : 3;
   for (int k = 0; k < nl; ++k) {
     int64_t cnt = (nl == 1) ? 3 * n : n;
-    int blocks = (int)((cnt + 255) / 256); if (blocks > 64) blocks = 64;
+    const int blocks = recon_blocks_of(cnt);
     float* parts = loss ? mmda_scratch_get((hipStream_t)stream, sizeof(float) * 64) : nullptr;
     if (loss && !parts) return MMDA_ELAUNCH;
     hipLaunchKernelGGL(recon_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, recon + k * stride, orig + k * stride, cnt,
@@ -1110,15 +1214,25 @@ extern "C" int mmda_loss_misc(const float* scores, const float* tcp, const float
   a.conf_grads = conf_grads && d_scores && d_tcp; a.conf_scale = conf_scale; a.with_conf = with_conf;
   a.recon = recon; a.orig = orig; a.n_recon = n_recon; a.recon_inv_n = 1.0f / (float)n_recon; a.recon_scale = recon_scale;
   a.d_recon = d_recon; a.d_orig = d_orig; a.L = L; a.dw = diff_w; a.sw = sim_w; a.rw = recon_w; a.cw = conf_w; a.use_conf = use_conf;
-  // (eight elements per thread at least: the last workgroup adds the partials one after the other, and 3 x 32 x 128 elements do not
-  //  need 64 of them)
-  int rb = (int)((n_recon + 2047) / 2048); if (rb > 64) rb = 64; if (rb < 1) rb = 1;
+  const int rb = misc_recon_blocks_of(n_recon);
   a.recon_blocks = rb;
   const int blocks = 1 + (with_conf ? ncls : 0) + rb;
   a.parts = mmda_scratch_get((hipStream_t)stream, sizeof(float) * blocks);
   if (!a.parts) return MMDA_ELAUNCH;
   hipLaunchKernelGGL(misc_losses_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   MMDA_CHECK_LAUNCH("mmda_loss_misc");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_loss_forms_describe(int B, int D, int have_loss, int have_dx, int cmd_nt, int64_t n_recon, mmda_loss_forms* out) {
+  if (!out || B <= 0 || D <= 0 || cmd_nt < 2 || cmd_nt > 3) return MMDA_EINVAL;
+  const DiffForms df = diff_forms(B, D, have_loss != 0, have_dx != 0);
+  const CmdForms cf = cmd_forms(B, D, cmd_nt, have_dx != 0);
+  const int64_t n = n_recon > 0 ? n_recon : (int64_t)3 * B * D;
+  out->diff_form = df.form; out->diff_products = df.skinny ? MMDA_LOSS_DIFF_SKINNY : MMDA_LOSS_DIFF_BATCHED;
+  out->diff_loss_sum = df.sum; out->diff_combine_blocks = df.blocks;
+  out->cmd_form = cf.form; out->cmd_grid = cf.grid;
+  out->recon_blocks = recon_blocks_of(n); out->misc_recon_blocks = misc_recon_blocks_of(n);
   return MMDA_OK;
 }
 

@@ -458,6 +458,27 @@ def lstm_plan(descs, B, T, backward=False, no_quad=False, quad_cap=0):
                 bwd_regs=bool(plan.bwd_regs), pair=bool(plan.pair), kernel=load().mmda_lstm_kernel_name(plan.kernel).decode())
 
 
+LOSS_DIFF_FORMS = ("generic", "fast4", "fast8", "fast16", "fast32")
+LOSS_DIFF_PRODUCTS = ("skinny", "batched")
+LOSS_DIFF_SUMS = (None, "finish", "own_launch")
+LOSS_CMD_FORMS = ("fast4", "fast8", "stream", "serial", "reject")
+
+
+def loss_forms(B, D, have_loss=True, have_dx=True, cmd_nt=3, n_recon=0):
+    """Which kernel form the loss entry points pick for (B, D) tensors (mmda_loss_forms_describe: host code only, no GPU; the
+    launchers read the same decision).  have_loss / have_dx: whether the call passes `loss` / `dx`; cmd_nt: tensors of the CMD call;
+    n_recon: elements of the recon call (0: 3 * B * D).  Returns a dict: diff (a name of LOSS_DIFF_FORMS), diff_products
+    ('skinny' / 'batched'), diff_loss_sum ('finish' / 'own_launch', None without `loss`), diff_combine_blocks, cmd (a name of
+    LOSS_CMD_FORMS), cmd_grid, recon_blocks (mmda_loss_recon), misc_recon_blocks (mmda_loss_misc)."""
+    f = _lib.LossForms()
+    check(load().mmda_loss_forms_describe(int(B), int(D), int(bool(have_loss)), int(bool(have_dx)), int(cmd_nt), int(n_recon),
+                                          C.byref(f)), "mmda_loss_forms_describe")
+    return dict(diff=LOSS_DIFF_FORMS[f.diff_form], diff_products=LOSS_DIFF_PRODUCTS[f.diff_products],
+                diff_loss_sum=LOSS_DIFF_SUMS[f.diff_loss_sum], diff_combine_blocks=f.diff_combine_blocks,
+                cmd=LOSS_CMD_FORMS[f.cmd_form], cmd_grid=f.cmd_grid, recon_blocks=f.recon_blocks,
+                misc_recon_blocks=f.misc_recon_blocks)
+
+
 def _to_gate_minor(x, H):
     """(..., 4H) [gate][unit] -> [unit][gate] (the resident-weights kernels' 16-byte layout)"""
     return x.reshape(*x.shape[:-1], 4, H).transpose(-1, -2).reshape(*x.shape[:-1], 4 * H).contiguous()

@@ -70,7 +70,8 @@ def diff_loss_multi(tensors, pairs):
 
 
 def cmd_loss_multi(tensors, pairs, n_moments=5, value_scale=1.0):
-    """value_scale * sum over `pairs` of CMD(tensors[i], tensors[j], n_moments) (functions.py:88-109)."""
+    """value_scale * sum over `pairs` of CMD(tensors[i], tensors[j], n_moments) (functions.py:88-109).  Two or three tensors of at
+    most 512 columns and one to six pairs, every one of which is computed whatever the shape; anything beyond raises MMDAError."""
     _need_cuda(*tensors)
     lib = _lib.load()
 
