@@ -757,6 +757,18 @@ int mmda_misa_set_embed_deferred(mmda_misa* m, int32_t* row_step, float* step_sc
 int mmda_misa_embed_deferred_step(mmda_misa* m, float lr, float beta1, float beta2, float eps, float clip, float grad_scale, int step,
                                   void* stream);
 int mmda_misa_embed_flush(mmda_misa* m, void* stream);
+/* Plain dense mode, fused step (mmda_misa_train_step with do_adam = 1): the rows of embed.weight that the batch does not index have a
+ * zero gradient, so their Adam step runs as a background pass of `workgroups` workgroups on an internal low-priority stream beside the
+ * forward pass, and the step's last optimizer launch walks only the rows the batch does index.  The bits of the dense launch; the step
+ * still completes on `stream` only when the pass has.  on = 0: the one dense launch over the whole table; on = 1: the pass in every
+ * eligible step (a handle left alone runs it where it pays: batches of up to 32 samples); workgroups = 0: the default throttle; on not
+ * 0 / 1, workgroups outside [0, 4096]: MMDA_EINVAL.  Overrides MMDA_EMBED_BG / MMDA_EMBED_BG_WGS for this handle.
+ * The pass runs only where the step is eligible: from a batch (not the encoder cache), no norm clip, nothing frozen, embed_update 0
+ * without deferral, T > 0, a table of whole 16-byte quads; every other step is launch for launch what it was.
+ * One caveat: after a step that returns an error, rows the batch does not index may already have taken the step.
+ * mmda_misa_embed_background_active: 1 if the last mmda_misa_train_step ran the pass, else 0 (host only). */
+int mmda_misa_set_embed_background(mmda_misa* m, int on, int workgroups);
+int mmda_misa_embed_background_active(const mmda_misa* m);
 /* Data parallel: the gradient bucket is laid out in the order the backward pass completes it (fusion block, LayerNorms,
  * layer-2 recurrent layers, layer-1 recurrent layers, embedding).  After mmda_misa_backward / mmda_misa_train_step has been
  * ISSUED, the first mmda_misa_early_grad_floats() floats of the bucket are final as soon as an event recorded inside that call

@@ -286,6 +286,8 @@ SIGNATURES = {
     "mmda_misa_set_embed_deferred": (_I, [_P, _P, _P, _I, _P]),
     "mmda_misa_embed_deferred_step": (_I, [_P, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mmda_misa_embed_flush": (_I, [_P, _P]),
+    "mmda_misa_set_embed_background": (_I, [_P, _I, _I]),
+    "mmda_misa_embed_background_active": (_I, [_P]),
     "mmda_misa_cluster_status": (_I, [_P, C.POINTER(_I)]),
     "mmda_misa_forward": (_I, [_P, _P, _P, _P, _P, _I, _U64, _P]),
     "mmda_misa_losses": (_I, [_P, _P, _I, _P]),

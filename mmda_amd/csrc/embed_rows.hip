@@ -18,9 +18,13 @@
 
 namespace {
 
-__global__ void embed_gather_kernel(const float* __restrict__ W, const int64_t* __restrict__ ids, int rows, int dim, float* out) {
+// stamp != nullptr: the row of the table a position reads is stamped with the step's epoch on the way (internal.h: RowStamp; st.ids and
+// st.n are this launch's own ids and rows)
+__global__ void embed_gather_kernel(const float* __restrict__ W, const int64_t* __restrict__ ids, int rows, int dim, float* out,
+                                    unsigned* stamp, unsigned epoch, int table_rows) {
   int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  if (stamp && (threadIdx.x & 63) == 0 && ids[row] >= 0 && ids[row] < table_rows) stamp[ids[row]] = epoch;
   const float* src = W + ids[row] * (int64_t)dim;
   float* dst = out + (int64_t)row * dim;
   for (int i = threadIdx.x & 63; i < dim; i += 64) dst[i] = src[i];
@@ -414,12 +418,17 @@ int embed_rows_apply(const Fin& fin, const RowKeys& keys, const EmbedList& l, co
 
 }  // namespace
 
-extern "C" int mmda_embed_gather(const float* W, const int64_t* ids, int rows, int dim, float* out, void* stream) {
+int mmda_embed_gather_stamped(const float* W, const int64_t* ids, int rows, int dim, float* out, const RowStamp* st, void* stream) {
   if (!W || !ids || !out || rows < 0 || dim <= 0) return MMDA_EINVAL;
+  if (st && (!st->stamp || st->ids != ids || st->n != rows || st->table_rows <= 0 || rows == 0)) return MMDA_EINVAL;
   if (rows == 0) return MMDA_OK;
-  hipLaunchKernelGGL(embed_gather_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, W, ids, rows, dim, out);
+  hipLaunchKernelGGL(embed_gather_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, W, ids, rows, dim, out,
+                     st ? st->stamp : nullptr, st ? st->epoch : 0u, st ? st->table_rows : 0);
   MMDA_CHECK_LAUNCH("mmda_embed_gather");
   return MMDA_OK;
+}
+extern "C" int mmda_embed_gather(const float* W, const int64_t* ids, int rows, int dim, float* out, void* stream) {
+  return mmda_embed_gather_stamped(W, ids, rows, dim, out, nullptr, stream);
 }
 
 // ---- RowAdd: the dense gradient

@@ -57,6 +57,21 @@ struct FlagWait { const unsigned* flag; unsigned value; unsigned* err; };
 constexpr FlagWait kNoWait{nullptr, 0u, nullptr};
 int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const RunTable* table, const AdamHyper& h,
                      const FlagWait& w, void* stream);
+// The embedding table walked by stamp.  stamp[r] == epoch: row r is one the step's batch indexes -- the launch that
+// reads the step's ids writes the epoch there (RowStamp, below), nothing clears the stamps between steps.  Fewer than 2^31 floats.
+struct TableRows { const unsigned* stamp; unsigned epoch; int rows, dim; };
+bool mmda_table_rows_ok(const TableRows& t);
+// The step's closing launch: mmda_adam_launch's dense stream over the n floats at p / g / m / v, then the rows of the table that FOLLOWS
+// them (at float n) whose stamp equals the epoch, gradient read from g.  w: as above.
+int mmda_adam_tail_launch(float* p, const float* g, float* m, float* v, int64_t n, const TableRows& t, const AdamHyper& h, const FlagWait& w,
+                          void* stream);
+// The background pass: step h.step with a zero gradient for the rows of the table at p / m / v whose stamp differs from the epoch, by
+// `workgroups` (1 .. 4096) workgroups with non-temporal accesses, each holding lds_bytes of LDS it does not use (0 .. 64 KB: keeps
+// them off the CUs of a resident recurrence).  No gradient buffer is read; h.scale_dev must be nullptr.
+int mmda_adam_background_launch(float* p, float* m, float* v, const TableRows& t, const AdamHyper& h, int workgroups, int lds_bytes,
+                                void* stream);
+// What the launch that reads a step's n ids is handed to stamp their rows: stamp[ids[i]] = epoch for every id inside the table
+struct RowStamp { unsigned* stamp; unsigned epoch; int table_rows; const int64_t* ids; int n; };
 bool mmda_adam_opts_valid(const mmda_adam_opts* o);           // the ranges mmda_misa_set_adam and the *_opts entries accept
 // The launches behind mmda_grad_norm: the norm of g (acc + g) over n floats or over a table's runs, block partials in `partials`
 // (doubles; mmda_grad_norm_partials sizes it), then norm and clip coefficient in out2[0], out2[1].  An empty range writes 0 and 1.
@@ -79,6 +94,12 @@ AdamStepScalars adam_step_scalars(float lr, float beta1, float beta2, int step);
 bool mmda_loss_cmd_sets_flag(int B, int D);
 int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
                              float value_scale, float* loss, float* dx, void* stream, unsigned* flag, unsigned value);
+
+// ---- lstm.hip / embed_rows.hip: the launch that reads a step's ids, stamping their rows on its way (st == nullptr: the C ABI's call)
+int mmda_lstm_pack_convert_transpose_stamped(int n, const int* H, const float* const* whh, void* const* packed_fwd, void* const* packed_bwd,
+                                             void* const* packed_c, const mmda_convert_job* jobs, int njobs, const mmda_transpose_job* tjobs,
+                                             int ntjobs, const RowStamp* st, void* stream);
+int mmda_embed_gather_stamped(const float* W, const int64_t* ids, int rows, int dim, float* out, const RowStamp* st, void* stream);
 
 // ---- lstm_cluster.hip: the resident recurrences of lstm.hip's entry points
 int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, const int32_t* lengths, void* stream, bool bwd,

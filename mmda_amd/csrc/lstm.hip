@@ -156,9 +156,16 @@ __global__ void pack_multi_kernel(PackMulti P) { pack_block<MODE>(P, (int)blockI
 // lookup) in ONE launch: blocks [0, pack_blocks) pack, the rest convert.  Both only depend on the step's inputs and weights, and as
 // two launches on two streams they cost the main stream a fork and a cross-stream wait in front of the first recurrent kernel.
 // Blocks past the conversions transpose fp32 matrices (the fusion block's K-major weight copies for the backward pass).
-__global__ __launch_bounds__(256) void pack_convert_kernel(PackMulti P, ConvLaunch L, TrLaunch R, int pack_blocks, int conv_end) {
+// st.stamp != nullptr: the launch also stamps the rows of the embedding table that the step's ids name (internal.h: RowStamp), one id per
+// lane across the grid -- it is the launch that reads the ids anyway, and the step's first.
+__global__ __launch_bounds__(256) void pack_convert_kernel(PackMulti P, ConvLaunch L, TrLaunch R, int pack_blocks, int conv_end, RowStamp st) {
   __shared__ __attribute__((aligned(16))) unsigned short tile[64][66];
   static_assert(sizeof(tile) >= sizeof(float) * 32 * 33, "the transpose tile is laid over the conversion tile");
+  if (st.stamp)                                          // launch-uniform
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < st.n; i += (int)(gridDim.x * blockDim.x)) {
+      const int64_t id = st.ids[i];
+      if (id >= 0 && id < st.table_rows) st.stamp[id] = st.epoch;
+    }
   if ((int)blockIdx.x < pack_blocks) pack_block<MMDA_BF16>(P, (int)blockIdx.x);
   else if ((int)blockIdx.x < conv_end) convert_block(L, (int)blockIdx.x - pack_blocks, tile);
   else transpose_block(R, (int)blockIdx.x - conv_end, reinterpret_cast<float (*)[33]>(&tile[0][0]));
@@ -572,10 +579,11 @@ int pack_build(int mode, int n, const int* H, const float* const* whh, void* con
 }
 }  // namespace
 
-extern "C" int mmda_lstm_pack_convert_transpose(int n, const int* H, const float* const* whh, void* const* packed_fwd,
-                                                void* const* packed_bwd, void* const* packed_c, const mmda_convert_job* jobs, int njobs,
-                                                const mmda_transpose_job* tjobs, int ntjobs, void* stream) {
+int mmda_lstm_pack_convert_transpose_stamped(int n, const int* H, const float* const* whh, void* const* packed_fwd, void* const* packed_bwd,
+                                             void* const* packed_c, const mmda_convert_job* jobs, int njobs, const mmda_transpose_job* tjobs,
+                                             int ntjobs, const RowStamp* st, void* stream) {
   if (!jobs || njobs < 0 || njobs > CONV_MAX) return MMDA_EINVAL;
+  if (st && (!st->stamp || !st->ids || st->n < 0 || st->table_rows <= 0)) return MMDA_EINVAL;
   PackMulti P;
   int pblocks = 0, cblocks = 0, tblocks = 0;
   int rc = pack_build(MMDA_BF16, n, H, whh, packed_fwd, packed_bwd, packed_c, P, pblocks);
@@ -586,11 +594,17 @@ extern "C" int mmda_lstm_pack_convert_transpose(int n, const int* H, const float
   TrLaunch R;
   rc = tr_build(tjobs, ntjobs, R, tblocks);
   if (rc) return rc;
-  if (pblocks + cblocks + tblocks == 0) return MMDA_OK;
+  if (pblocks + cblocks + tblocks == 0) return st ? MMDA_EINVAL : MMDA_OK;      // (no launch to carry the stamps: pack_build refuses n = 0 first)
   hipLaunchKernelGGL(pack_convert_kernel, dim3(pblocks + cblocks + tblocks), dim3(256), 0, (hipStream_t)stream, P, L, R, pblocks,
-                     pblocks + cblocks);
+                     pblocks + cblocks, st ? *st : RowStamp{nullptr, 0u, 0, nullptr, 0});
   MMDA_CHECK_LAUNCH("mmda_lstm_pack_convert_transpose");
   return MMDA_OK;
+}
+
+extern "C" int mmda_lstm_pack_convert_transpose(int n, const int* H, const float* const* whh, void* const* packed_fwd,
+                                                void* const* packed_bwd, void* const* packed_c, const mmda_convert_job* jobs, int njobs,
+                                                const mmda_transpose_job* tjobs, int ntjobs, void* stream) {
+  return mmda_lstm_pack_convert_transpose_stamped(n, H, whh, packed_fwd, packed_bwd, packed_c, jobs, njobs, tjobs, ntjobs, nullptr, stream);
 }
 
 extern "C" int mmda_lstm_pack_whh_and_convert(int n, const int* H, const float* const* whh, void* const* packed_fwd, void* const* packed_bwd,

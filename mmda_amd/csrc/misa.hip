@@ -5,6 +5,7 @@
 #include "common.h"
 #include "fused_rows.h"
 #include "internal.h"
+#include <algorithm>
 
 #include <cstring>
 #include <map>
@@ -100,6 +101,9 @@ struct StepPlan {
   bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
   int embed_update = 0;             // EU_*: how the step treats the embedding table (mmda_misa_set_embed_update)
   bool embed_deferred = false;      // dense, with the table's update applied row by row when a row is next needed (mmda_misa_set_embed_deferred)
+  // The table rows the batch does not index take the step on a low-priority stream beside the forward pass (mmda_misa::bg; DESIGN section
+  // 4a), by embed_bg_wgs workgroups, forked behind the step's first launch or (embed_bg_late) behind the layer-1 forward recurrence.
+  bool embed_bg = false, embed_bg_late = false; int embed_bg_wgs = 0, embed_bg_lds = 0;
 };
 
 // embed_update: dense = the table's gradient is scattered into the bucket and dense Adam walks all V rows; sparse = the rows the batch
@@ -392,6 +396,21 @@ struct mmda_misa {
   hipStream_t side = nullptr;      // second stream for weight-gradient GEMMs
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pack = nullptr;
   hipEvent_t ev_early = nullptr;             // recorded by backward() when the gradients of the bucket prefix are final
+  // The background pass over the embedding table (StepPlan::embed_bg).  A row the batch does not index has gradient zero, and its Adam
+  // step needs nothing the step computes: a few workgroups on `bg`, a stream of the lowest priority, trickle that update under the
+  // forward pass, where HBM is nearly idle, and the step's closing launch walks only the rows the batch does index.  Which rows those
+  // are: row_stamp[V] on the device, where the launch that reads the step's ids writes bg_epoch (internal.h: RowStamp) -- padding
+  // positions too, so the gather never reads a row the pass writes; no clear per step, the epoch moves on (all stamps are cleared
+  // when it wraps to 0).  Fork: ev_bg_fork behind that launch, so the pass is ordered behind the stamps, the previous step and whatever
+  // the caller queued.  Join: ev_bg_done, waited for by the side stream in front of the word it sets for the closing launch (flag
+  // join), else by the main stream behind that launch.  All created at the first eligible step.
+  hipStream_t bg = nullptr; hipEvent_t ev_bg_fork = nullptr, ev_bg_done = nullptr;
+  unsigned* row_stamp = nullptr; unsigned bg_epoch = 0u;
+  int bg_on = -1, bg_wgs = 0;                // mmda_misa_set_embed_background; -1 / 0: MMDA_EMBED_BG's / MMDA_EMBED_BG_WGS's (else the default)
+  // (the pass's workgroups hold LDS they never touch, MMDA_EMBED_BG_LDS bytes: a resident recurrence reserves the whole LDS of its CUs,
+  //  so the two never share a CU -- sharing one cost each forward recurrence 24 us of its hand-offs at any throttle)
+  const OptStep* bg_step = nullptr;          // train_step: the optimizer step of the step in flight, where its kind may run the pass
+  int bg_pending = 0, bg_active = 0;         // the pass went out and is not joined yet; the last train_step ran it
   // Flag joins (training step; common.h: flag_wait): where the main stream needs a side-stream chain's results, the consuming KERNEL
   // waits on the device for a word that a one-thread launch behind the chain sets, instead of the stream waiting for an event -- an
   // event wait costs the main stream 9 - 12 us of packet processing even when the chain finished long ago (tools/micro/fork_cost.hip),
@@ -543,6 +562,10 @@ void ev_rec(mmda_misa* m, int step, int slot, int which, void* stream) {
 
 // Fork: work issued on the returned stream starts after everything already on `main_stream` and runs beside what follows
 // there; side_join() makes `main_stream` wait for it.  Without overlap the main stream itself is returned.
+unsigned fork_event_flags() {
+  static const int sysfence = mmda_env_int("MMDA_EVENT_SYSFENCE", 0);
+  return hipEventDisableTiming | (sysfence ? 0u : hipEventDisableSystemFence);
+}
 int side_fork(mmda_misa* m, void* main_stream, void** out) {
   *out = main_stream;
   if (!m->use_side) return MMDA_OK;
@@ -552,8 +575,7 @@ int side_fork(mmda_misa* m, void* main_stream, void** out) {
     // memory may not be visible to the host and other devices", neither of which waits on these events; every kernel still ends with
     // its own device-scope release).  With the fence a recorded event costs the recording stream 6 us between two launches, without
     // it 3 (tools/micro/fork_cost.hip).  MMDA_EVENT_SYSFENCE=1: with the fence.
-    static const int sysfence = mmda_env_int("MMDA_EVENT_SYSFENCE", 0);
-    const unsigned evf = hipEventDisableTiming | (sysfence ? 0u : hipEventDisableSystemFence);
+    const unsigned evf = fork_event_flags();
     if (hipEventCreateWithFlags(&m->ev_fork, evf) != hipSuccess) return MMDA_ELAUNCH;
     if (hipEventCreateWithFlags(&m->ev_join, evf) != hipSuccess) return MMDA_ELAUNCH;
     if (hipEventCreateWithFlags(&m->ev_pack, evf) != hipSuccess) return MMDA_ELAUNCH;
@@ -601,6 +623,55 @@ int side_join(mmda_misa* m, void* main_stream) {
   if (hipEventRecord(m->ev_join, m->side) != hipSuccess) return MMDA_ELAUNCH;
   if (hipStreamWaitEvent((hipStream_t)main_stream, m->ev_join, 0) != hipSuccess) return MMDA_ELAUNCH;
   m->side_pending = 0;
+  return MMDA_OK;
+}
+
+// ---- the background pass over the embedding table (see mmda_misa::bg)
+// Its stream, events and stamps, made once; then the step's epoch.  What the launch that reads the n ids stamps with: *st.
+int bg_begin(mmda_misa* m, const int64_t* ids, int n, void* main_stream, RowStamp* st) {
+  const size_t bytes = sizeof(unsigned) * (size_t)m->cfg.vocab;
+  if (!m->bg) {
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return MMDA_ELAUNCH;
+    if (hipStreamCreateWithPriority(&m->bg, hipStreamNonBlocking, least) != hipSuccess) { m->bg = nullptr; return MMDA_ELAUNCH; }
+    if (hipEventCreateWithFlags(&m->ev_bg_fork, fork_event_flags()) != hipSuccess) return MMDA_ELAUNCH;
+    if (hipEventCreateWithFlags(&m->ev_bg_done, fork_event_flags()) != hipSuccess) return MMDA_ELAUNCH;
+  }
+  if (!m->row_stamp) {
+    if (hipMalloc(reinterpret_cast<void**>(&m->row_stamp), bytes) != hipSuccess) { m->row_stamp = nullptr; return MMDA_ELAUNCH; }
+    if (hipMemset(m->row_stamp, 0, bytes) != hipSuccess) return MMDA_ELAUNCH;
+    m->bg_epoch = 0u;
+  }
+  if (!m->ev_bg_fork || !m->ev_bg_done) return MMDA_ELAUNCH;
+  if (++m->bg_epoch == 0u) {                             // wrapped: a stamp of 2^32 steps ago would read as this step's
+    if (hipMemsetAsync(m->row_stamp, 0, bytes, (hipStream_t)main_stream) != hipSuccess) return MMDA_ELAUNCH;
+    m->bg_epoch = 1u;
+  }
+  *st = RowStamp{m->row_stamp, m->bg_epoch, m->cfg.vocab, ids, n};
+  return MMDA_OK;
+}
+TableRows bg_table(const mmda_misa* m) { return TableRows{m->row_stamp, m->bg_epoch, m->cfg.vocab, m->cfg.d_t}; }
+AdamHyper bg_hyper(const mmda_misa* m, const OptStep& o) {
+  return AdamHyper{o.lr, m->adam.beta1, m->adam.beta2, m->adam.eps, o.clip, o.grad_scale, o.step, m->adam.weight_decay, m->adam.decoupled, nullptr};
+}
+// the fork and the pass: behind everything `main_stream` holds
+int bg_launch(mmda_misa* m, void* main_stream) {
+  if (!m->bg_step || !m->bg || !m->row_stamp) return MMDA_EINVAL;
+  if (hipEventRecord(m->ev_bg_fork, (hipStream_t)main_stream) != hipSuccess) return MMDA_ELAUNCH;
+  if (hipStreamWaitEvent(m->bg, m->ev_bg_fork, 0) != hipSuccess) return MMDA_ELAUNCH;
+  const int64_t e = m->par.embed;
+  const int rc = mmda_adam_background_launch(m->P + e, m->M1 + e, m->V1 + e, bg_table(m), bg_hyper(m, *m->bg_step), m->plan.embed_bg_wgs,
+                                             m->plan.embed_bg_lds, m->bg);
+  if (rc) return rc;
+  m->bg_pending = 1; m->bg_active = 1;                   // (from here on rows may have taken the step, whatever the step returns)
+  if (hipEventRecord(m->ev_bg_done, m->bg) != hipSuccess) return MMDA_ELAUNCH;
+  return MMDA_OK;
+}
+// join: `stream` (the side stream in front of its flag word, or the main stream) goes on only when the pass is through
+int bg_join(mmda_misa* m, void* stream) {
+  if (!m->bg_pending) return MMDA_OK;
+  if (hipStreamWaitEvent((hipStream_t)stream, m->ev_bg_done, 0) != hipSuccess) return MMDA_ELAUNCH;
+  m->bg_pending = 0;
   return MMDA_OK;
 }
 
@@ -773,6 +844,8 @@ int apply_trainable(mmda_misa* m, const unsigned char* flags) {
 }
 
 constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
+// the background pass over the embedding table: on or off, and its workgroups, where nothing else says (measured: DESIGN section 4a)
+constexpr int kEmbedBgDefault = 1, kEmbedBgWorkgroups = 32, kEmbedBgLds = 1024, kEmbedBgMaxB = 32;
 
 // the decisions of one step (see StepPlan); the switches that select a form of the step are read here only
 StepPlan plan_step(mmda_misa* m) {
@@ -785,6 +858,10 @@ StepPlan plan_step(mmda_misa* m) {
   static const int zg_side = mmda_env_int("MMDA_ZERO_GRAD_SIDE", -1);
   static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
   static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
+  static const int bg_on = mmda_env_int("MMDA_EMBED_BG", kEmbedBgDefault);
+  static const int bg_wgs = mmda_env_int("MMDA_EMBED_BG_WGS", 0);
+  static const int bg_late = mmda_env_int("MMDA_EMBED_BG_LATE", 0);
+  static const int bg_lds = mmda_env_int("MMDA_EMBED_BG_LDS", kEmbedBgLds);
   const mmda_misa_config& c = m->cfg;
   const int B = m->lay.B, T = m->lay.T, mode = c.mode;
   StepPlan P;
@@ -845,6 +922,19 @@ StepPlan plan_step(mmda_misa* m) {
   P.embed_update = m->embed_update;
   P.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
   P.sort_early = sort_early && T > 0 && m->lay.esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN && !P.enc_cut;
+  // The background pass: a fused step from a batch with the native Adam behind it and no norm clip (bg_step: train_step), a plain
+  // dense table, nothing frozen (no run table).  Not under clip_norm: a non-finite norm poisons the zero gradients of the dense launch
+  // too, and that must stay so.  The table is whole quads and fewer than 2^31 floats (the walkers' index arithmetic).
+  // Where it pays (measured): up to one 32-sample batch group of the resident recurrences, which then hold 152 of the
+  // CUs; from the second group on they want every CU, and the pass's workgroups -- which keep off a recurrence's CUs by holding LDS --
+  // delay their placement (B=64: 0.763 -> 0.816 ms).  MMDA_EMBED_BG=2, or the handle's own switch: wherever the step is eligible.
+  const int bg_switch = m->bg_on >= 0 ? (m->bg_on ? 2 : 0) : bg_on;
+  const int64_t tab = (int64_t)c.vocab * c.d_t;
+  P.embed_bg = bg_switch != 0 && (bg_switch >= 2 || B <= kEmbedBgMaxB) && m->bg_step && !P.enc_cached && !P.enc_cut && P.embed_update == EU_DENSE &&
+               !P.embed_deferred && !masked(m) && T > 0 && m->M1 && m->V1 && tab > 0 && (tab & 3) == 0 && tab < ((int64_t)1 << 31);
+  P.embed_bg_late = bg_late != 0;
+  P.embed_bg_lds = std::max(0, std::min(65536, bg_lds));
+  P.embed_bg_wgs = std::min(4096, m->bg_wgs > 0 ? m->bg_wgs : bg_wgs > 0 ? bg_wgs : kEmbedBgWorkgroups);
   return P;
 }
 
@@ -868,6 +958,10 @@ extern "C" void mmda_misa_destroy(mmda_misa* m) {
   if (m->ev_join) (void)hipEventDestroy(m->ev_join);
   if (m->ev_pack) (void)hipEventDestroy(m->ev_pack);
   if (m->ev_early) (void)hipEventDestroy(m->ev_early);
+  if (m->bg) { (void)hipStreamSynchronize(m->bg); (void)hipStreamDestroy(m->bg); }
+  if (m->ev_bg_fork) (void)hipEventDestroy(m->ev_bg_fork);
+  if (m->ev_bg_done) (void)hipEventDestroy(m->ev_bg_done);
+  if (m->row_stamp) (void)hipFree(m->row_stamp);
   if (m->side) (void)hipStreamDestroy(m->side);
   if (m->jflags) (void)hipFree(m->jflags);
   if (m->runs_dev) (void)hipFree(m->runs_dev);
@@ -1151,6 +1245,13 @@ extern "C" int mmda_misa_set_embed_deferred(mmda_misa* m, int32_t* row_step, flo
   return MMDA_OK;
 }
 
+extern "C" int mmda_misa_set_embed_background(mmda_misa* m, int on, int workgroups) {
+  if (!m || (on != 0 && on != 1) || workgroups < 0 || workgroups > 4096) return MMDA_EINVAL;
+  m->bg_on = on; m->bg_wgs = workgroups;
+  return MMDA_OK;
+}
+extern "C" int mmda_misa_embed_background_active(const mmda_misa* m) { return m ? m->bg_active : MMDA_EINVAL; }
+
 extern "C" int mmda_misa_embed_flush(mmda_misa* m, void* stream) {
   if (!m) return MMDA_EINVAL;
   if (!m->df_row_step) return MMDA_OK;                     // nothing is deferred
@@ -1351,7 +1452,10 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
     std::vector<mmda_transpose_job> tj;
     if (P.wT_merge) weight_transpose_jobs(m, tj);
     if (tj.size() > 20) tj.clear();
-    rc = mmda_lstm_pack_convert_transpose(12, Hs, Wp, Fp, Bp, P.want_c ? Cp : nullptr, cj, nj, tj.data(), (int)tj.size(), s);
+    RowStamp st;
+    if (P.embed_bg) rc = bg_begin(m, t_ids, R, s, &st);
+    if (!rc) rc = mmda_lstm_pack_convert_transpose_stamped(12, Hs, Wp, Fp, Bp, P.want_c ? Cp : nullptr, cj, nj, tj.data(), (int)tj.size(),
+                                                           P.embed_bg ? &st : nullptr, s);
     m->wT_pending = (P.want_wT && tj.empty()) ? 1 : 0;
     if (!tj.empty()) m->wT_valid = rc ? 0 : 1;
   } else {
@@ -1362,8 +1466,12 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
     if (!rc && ss != s && hipEventRecord(m->ev_pack, (hipStream_t)ss) != hipSuccess) rc = MMDA_ELAUNCH;
     if (!rc && P.want_wT) rc = weight_transposes(m, ss);
     // embedding rows (models.py:201)
-    if (!rc) rc = mmda_embed_gather(PP(p.embed), t_ids, R, m->cfg.d_t, WS(w.mod[0].x), s);
+    RowStamp st;
+    if (!rc && P.embed_bg) rc = bg_begin(m, t_ids, R, s, &st);
+    if (!rc) rc = mmda_embed_gather_stamped(PP(p.embed), t_ids, R, m->cfg.d_t, WS(w.mod[0].x), P.embed_bg ? &st : nullptr, s);
   }
+  // the background pass over the table rows this batch does not index: forked here, behind the launch that stamped the others
+  if (!rc && P.embed_bg && !P.embed_bg_late) rc = bg_launch(m, s);
 }
 
 // encoder layer l: input GEMM and recurrence of the three modalities; then layer 1's LayerNorm, or layer 2's fork beside the fusion block
@@ -1397,6 +1505,7 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
   rc = mmda_lstm_fwd(mode, 3, desc, B, T, lengths, s);
   ev_rec(m, m->ev_fwd, l, 1, s);
   if (rc) return;
+  if (l == 0 && P.embed_bg && P.embed_bg_late) { rc = bg_launch(m, s); if (rc) return; }     // (MMDA_EMBED_BG_LATE=1: the later fork)
   if (l == 0) {
     mmda_ln_args ln[3];
     for (int i = 0; i < 3; ++i) {
@@ -1954,8 +2063,9 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
     const int nj = backward_only_jobs(m, cj);
     rc = mmda_convert_bf16(cj, nj, ss);
   }
-  // (Clip + Adam of the embedding rows this batch does not touch, here beside the layer-2 recurrence, measured slower: at B=32 its
-  // 170 MB stream slows the recurrence's hand-offs and the step by 14 us; behind the early optimizer pass, by 68 us.)
+  // (Clip + Adam of the embedding rows this batch does not touch does not belong here: as a burst of the full grid beside the layer-2
+  // recurrence its 170 MB stream slows the recurrence's hand-offs and the step by 14 us at B=32; behind the early optimizer pass, by
+  // 68 us.  It runs as a trickle of a few workgroups under the forward pass instead: mmda_misa::bg)
 }
 
 // encoder layer l, top layer first: the backward recurrence, then the weight and input gradient GEMMs of the three modalities.
@@ -2206,7 +2316,9 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   //  gradients ran there in front of the early optimizer pass: the launch that waits READS the rest of the bucket before it waits)
   if (P.fj_on && early && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
       m->adam_early_done == m->par.rnn1_begin) {
-    x.rc = side_flag_signal(m, 1);
+    // (the background pass over the table joins here too: the word is set behind it, and the main stream pays nothing)
+    x.rc = bg_join(m, m->side);
+    if (!x.rc) x.rc = side_flag_signal(m, 1);
     m->fj2 = x.rc ? 0 : 1;
     return x.rc;
   }
@@ -2356,9 +2468,10 @@ extern "C" int mmda_misa_adam_step_accumulated(mmda_misa* m, const float* acc, i
 namespace {
 // One training step: from a batch (t_ids, v, a, lengths; labels `emo`), or -- eb != nullptr -- from the encoder cache, whose forward
 // gathers the labels into `emo` itself.  The two differ in their forward pass and in the batch the backward pass is handed, nowhere else.
-int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const mmda_encoded_batch* eb,
-               float* emo_gathered, const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
-               void* stream) {
+// (the body of train_step below, which closes it: whatever this returns, the background pass over the table is joined)
+int train_step_body(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const mmda_encoded_batch* eb,
+                    float* emo_gathered, const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
+                    void* stream) {
   // the gradient bucket is cleared on the side stream beside the forward pass's fusion block (not at the start of the step: the
   // side stream's first job there, packing W_hh, is what the first recurrent kernel waits for)
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
@@ -2374,10 +2487,11 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   m->eager_losses = 1; m->eager_done = 0;
   m->emo_eager = emo; m->misc_deferred = nullptr;
   m->fj1 = m->fj2 = 0;
+  // the kind of step that may run the background pass over the table (plan_step decides): from a batch, the native Adam behind it, no norm
+  m->bg_step = (early && !eb) ? &o : nullptr;
   rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
-  if (rc) return rc;
-  rc = eb ? forward_encoded(m, eb, emo_gathered, training, seed, stream) : mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
-  m->eager_losses = 0; m->emo_eager = nullptr;
+  if (!rc) rc = eb ? forward_encoded(m, eb, emo_gathered, training, seed, stream) : mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
+  m->eager_losses = 0; m->emo_eager = nullptr; m->bg_step = nullptr;
   if (rc) return rc;
   if (m->zero_grad_pending) return MMDA_ELAUNCH;        // forward() always reaches its fusion block
   rc = mmda_misa_losses(m, emo, 1, stream);
@@ -2392,7 +2506,24 @@ int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* 
   // or frozen table: the launch ends in front of it); flag join: it does not complete before the side stream's chain has
   const bool fj = m->fj2 != 0;
   m->fj2 = 0;
-  return opt_step(m, o, m->adam_early_done, fj ? FlagWait{m->jflags + 1, m->jval[1], m->jflags + 2} : kNoWait, nullptr, stream);
+  const FlagWait w = fj ? FlagWait{m->jflags + 1, m->jval[1], m->jflags + 2} : kNoWait;
+  if (!m->bg_active) return opt_step(m, o, m->adam_early_done, w, nullptr, stream);
+  // The background pass stepped the table rows this batch does not index: the launch covers the rest of the bucket in front of the
+  // table and the rows whose stamp is this step's, which read the scattered gradient -- one launch, as ever.  (Such a step has no run
+  // table, no norm, no accumulator and no pending rows: plan_step.)
+  const int64_t lo = m->adam_early_done;
+  return mmda_adam_tail_launch(m->P + lo, m->G + lo, m->M1 + lo, m->V1 + lo, m->par.embed - lo, bg_table(m), bg_hyper(m, o), w, stream);
+}
+
+int train_step(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const mmda_encoded_batch* eb,
+               float* emo_gathered, const float* emo, int training, uint64_t seed, int do_adam, float lr, float clip, int step,
+               void* stream) {
+  if (m) m->bg_active = 0;
+  const int rc = train_step_body(m, t_ids, v, a, lengths, eb, emo_gathered, emo, training, seed, do_adam, lr, clip, step, stream);
+  // Where the side stream did not take the pass's join into its flag word (fp32 step, MMDA_FLAG_JOIN=0, GRU, no early optimizer pass,
+  // a step that failed half-way), the caller's stream waits for it here, behind the closing launch.
+  const int rj = (m && m->bg_pending) ? bg_join(m, stream) : MMDA_OK;
+  return rc ? rc : rj;
 }
 }  // namespace
 

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "internal.h"
 #include <math.h>
+#include <type_traits>
 
 // ---- Adam's bias corrections and step scalars (internal.h: the rows code of embed_rows.hip makes its scalars from the same two)
 BiasCorrections bias_corrections(float beta1, float beta2, int step) {
@@ -29,6 +30,12 @@ namespace {
 struct AdamArgs { float* p; const float* acc; const float* g; float* m; float* v; float b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt; };
 template <bool kSum>
 struct Adam : AdamArgs {
+  __device__ __forceinline__ void step4(float4& pp, const float4& gg, float4& mm, float4& vv) const {
+    adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+  }
   __device__ __forceinline__ void quad(int64_t q) const {
     float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
     float4 gg = reinterpret_cast<const float4*>(g)[q];
@@ -36,16 +43,17 @@ struct Adam : AdamArgs {
       const float4 aa = reinterpret_cast<const float4*>(acc)[q];
       gg.x = __fadd_rn(aa.x, gg.x); gg.y = __fadd_rn(aa.y, gg.y); gg.z = __fadd_rn(aa.z, gg.z); gg.w = __fadd_rn(aa.w, gg.w);
     }
-    adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
-    adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+    step4(pp, gg, mm, vv);
     reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
   }
   __device__ __forceinline__ void one(int64_t e) const {
     float ge = g[e];
     if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
     adam1(p[e], ge, m[e], v[e], b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
+  }
+  // the step of an element whose gradient is gz, a zero the launch is handed at run time (background_kernel below): g is not read
+  __device__ __forceinline__ void one_zero(float& pe, float& me, float& ve, float gz) const {
+    adam1(pe, gz, me, ve, b1, b2, eps, clip, gscale, step_size, inv_bc2_sqrt);
   }
 };
 // Adam with what mmda_adam_opts adds: weight decay (adam1_decayed(), common.h) and a gradient scale that lives on the device -- the
@@ -57,6 +65,12 @@ struct AdamOptArgs : AdamArgs { int decay; float wd, lr_wd; const float* scale_d
 template <bool kSum>
 struct AdamOpt : AdamOptArgs {
   __device__ __forceinline__ float scale() const { return scale_dev ? __fmul_rn(gscale, *scale_dev) : gscale; }
+  __device__ __forceinline__ void step4(float4& pp, const float4& gg, float4& mm, float4& vv, float gs) const {
+    adam1_decayed(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    adam1_decayed(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+  }
   __device__ __forceinline__ void quad(int64_t q) const {
     const float gs = scale();
     float4 pp = reinterpret_cast<float4*>(p)[q], mm = reinterpret_cast<float4*>(m)[q], vv = reinterpret_cast<float4*>(v)[q];
@@ -65,16 +79,16 @@ struct AdamOpt : AdamOptArgs {
       const float4 aa = reinterpret_cast<const float4*>(acc)[q];
       gg.x = __fadd_rn(aa.x, gg.x); gg.y = __fadd_rn(aa.y, gg.y); gg.z = __fadd_rn(aa.z, gg.z); gg.w = __fadd_rn(aa.w, gg.w);
     }
-    adam1_decayed(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
-    adam1_decayed(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
-    adam1_decayed(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
-    adam1_decayed(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, clip, gs, step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+    step4(pp, gg, mm, vv, gs);
     reinterpret_cast<float4*>(p)[q] = pp; reinterpret_cast<float4*>(m)[q] = mm; reinterpret_cast<float4*>(v)[q] = vv;
   }
   __device__ __forceinline__ void one(int64_t e) const {
     float ge = g[e];
     if constexpr (kSum) ge = __fadd_rn(acc[e], ge);
     adam1_decayed(p[e], ge, m[e], v[e], b1, b2, eps, clip, scale(), step_size, inv_bc2_sqrt, decay, wd, lr_wd);
+  }
+  __device__ __forceinline__ void one_zero(float& pe, float& me, float& ve, float gz) const {
+    adam1_decayed(pe, gz, me, ve, b1, b2, eps, clip, scale(), step_size, inv_bc2_sqrt, decay, wd, lr_wd);
   }
 };
 // g *= *scale_dev in place: clip_grad_norm_'s second half for the unfused loop
@@ -167,6 +181,77 @@ __global__ __launch_bounds__(256) void runs_kernel(const mmda_run* __restrict__ 
     else for (int64_t e = it.e0; e < it.e1; ++e) f.one(e);
   }
   if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
+}
+
+// The embedding table BY STAMP (internal.h: TableRows): row r is one the step's batch indexes when stamp[r] == epoch.  Both kernels walk
+// the table flat -- item i is quad i of the table (vec: dim % 4 == 0 and 16-byte aligned bases, launch-uniform) or float i, its row
+// i / (dim / 4) or i / dim; fewer than 2^31 items, so the index arithmetic is 32-bit -- and consecutive lanes take consecutive items, so
+// a wave's accesses are whole lines whichever rows it skips.
+//
+// The step's closing launch: the dense stream over [0, n) as stream_kernel walks it, then the rows of the table at float `off` that the
+// batch indexes, through the same quad() / one() -- they read the scattered gradient.  The other rows took the step already
+// (background_kernel).  wait_flag: as in stream_kernel.
+template <class F>
+__global__ __launch_bounds__(256) void stream_table_kernel(int64_t n, int64_t off, TableRows t, int vec, F f, const unsigned* wait_flag,
+                                                           unsigned wait_value, unsigned* wait_err) {
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = i0; i < n4; i += stride) f.quad(i);
+  for (int64_t i = (n4 << 2) + i0; i < n; i += stride) f.one(i);
+  const unsigned per_row = vec ? (unsigned)t.dim >> 2 : (unsigned)t.dim;
+  const int64_t items = (int64_t)t.rows * per_row;
+  for (int64_t i = i0; i < items; i += stride) {
+    if (t.stamp[(unsigned)i / per_row] != t.epoch) continue;
+    if (vec) f.quad((off >> 2) + i);
+    else f.one(off + i);
+  }
+  if (blockIdx.x == 0) flag_wait(wait_flag, wait_value, wait_err);
+}
+
+// The background pass: the rows the batch does NOT index take the step with the gradient gz -- a zero handed over at run time, so the
+// functor's arithmetic is compiled as it is for a gradient read from memory, signed zeros included; g is not read.  f's p, m, v are the
+// table's own.  A few workgroups (the launch's grid is its throttle) stream the table with non-temporal accesses beside the step's
+// latency-bound kernels: four items per lane in flight, loads first.  No atomics, no waiting.  The launch may ask for LDS it never
+// touches: a resident recurrence reserves the whole LDS of the CUs it runs on, so a workgroup that holds any is placed on another CU
+// and does not queue its 16-byte accesses in front of a recurrence wave's hand-off loads in that CU's vector memory path.
+template <class F>
+__global__ __launch_bounds__(256) void background_kernel(TableRows t, int vec, F f, float gz) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  const unsigned per_row = vec ? (unsigned)t.dim >> 2 : (unsigned)t.dim;
+  const unsigned items = (unsigned)t.rows * per_row;
+  if (vec) {
+    f32x4* const P4 = reinterpret_cast<f32x4*>(f.p); f32x4* const M4 = reinterpret_cast<f32x4*>(f.m); f32x4* const V4 = reinterpret_cast<f32x4*>(f.v);
+    for (unsigned base = blockIdx.x * blockDim.x + threadIdx.x; base < items; base += 4u * stride) {
+      // (base + k stride < 2^31 + 4 * 2^20: no wrap -- the launcher caps the grid at 4096 workgroups)
+      bool on[4]; f32x4 pp[4], mm[4], vv[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned i = base + (unsigned)k * stride;
+        on[k] = i < items && t.stamp[min(i, items - 1u) / per_row] != t.epoch;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned i = base + (unsigned)k * stride;
+        if (on[k]) { pp[k] = __builtin_nontemporal_load(P4 + i); mm[k] = __builtin_nontemporal_load(M4 + i); vv[k] = __builtin_nontemporal_load(V4 + i); }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned i = base + (unsigned)k * stride;
+        if (!on[k]) continue;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { float pe = pp[k][c], me = mm[k][c], ve = vv[k][c]; f.one_zero(pe, me, ve, gz); pp[k][c] = pe; mm[k][c] = me; vv[k][c] = ve; }
+        __builtin_nontemporal_store(pp[k], P4 + i); __builtin_nontemporal_store(mm[k], M4 + i); __builtin_nontemporal_store(vv[k], V4 + i);
+      }
+    }
+    return;
+  }
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < items; i += stride) {
+    if (t.stamp[i / per_row] == t.epoch) continue;
+    float pe = __builtin_nontemporal_load(f.p + i), me = __builtin_nontemporal_load(f.m + i), ve = __builtin_nontemporal_load(f.v + i);
+    f.one_zero(pe, me, ve, gz);
+    __builtin_nontemporal_store(pe, f.p + i); __builtin_nontemporal_store(me, f.m + i); __builtin_nontemporal_store(ve, f.v + i);
+  }
 }
 
 // ---- the global L2 norm of the gradient a step is about to apply (torch.nn.utils.clip_grad_norm_)
@@ -340,6 +425,45 @@ int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float
   if (adam_plain(h)) return acc ? launch(Adam<true>{a}) : launch(Adam<false>{a});
   const AdamOptArgs o = adam_opt_args(a, h);
   return acc ? launch(AdamOpt<true>{o}) : launch(AdamOpt<false>{o});
+}
+
+// internal.h: the two launches of a step whose table is walked by stamp
+bool mmda_table_rows_ok(const TableRows& t) {
+  return t.stamp && t.rows > 0 && t.dim > 0 && (int64_t)t.rows * t.dim < ((int64_t)1 << 31);
+}
+int mmda_adam_tail_launch(float* p, const float* g, float* m, float* v, int64_t n, const TableRows& t, const AdamHyper& h, const FlagWait& w,
+                          void* stream) {
+  if (!p || !g || !m || !v || h.step < 1 || n < 0 || !mmda_table_rows_ok(t)) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMDA_EINVAL;
+  const int vec = (n & 3) == 0 && (t.dim & 3) == 0;
+  const int64_t items = (int64_t)t.rows * (vec ? t.dim >> 2 : t.dim);
+  const int blocks = stream_blocks(items > n / 4 ? items : n / 4);
+  const AdamArgs a = adam_args(p, nullptr, g, m, v, h);
+  auto launch = [&](const auto& f) {
+    using F = std::decay_t<decltype(f)>;
+    hipLaunchKernelGGL(stream_table_kernel<F>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, n, t, vec, f, w.flag, w.value, w.err);
+    MMDA_CHECK_LAUNCH("mmda_clamp_adam/table_tail");
+    return (int)MMDA_OK;
+  };
+  if (adam_plain(h)) return launch(Adam<false>{a});
+  return launch(AdamOpt<false>{adam_opt_args(a, h)});
+}
+int mmda_adam_background_launch(float* p, float* m, float* v, const TableRows& t, const AdamHyper& h, int workgroups, int lds_bytes,
+                                void* stream) {
+  if (!p || !m || !v || h.step < 1 || h.scale_dev || workgroups < 1 || workgroups > 4096 || !mmda_table_rows_ok(t)) return MMDA_EINVAL;
+  if (lds_bytes < 0 || lds_bytes > 65536) return MMDA_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 3) return MMDA_EINVAL;
+  const int vec = (t.dim & 3) == 0 && (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+  const AdamArgs a = adam_args(p, nullptr, nullptr, m, v, h);
+  const float gz = 0.0f;
+  auto launch = [&](const auto& f) {
+    using F = std::decay_t<decltype(f)>;
+    hipLaunchKernelGGL(background_kernel<F>, dim3(workgroups), dim3(256), (size_t)lds_bytes, (hipStream_t)stream, t, vec, f, gz);
+    MMDA_CHECK_LAUNCH("mmda_clamp_adam/table_background");
+    return (int)MMDA_OK;
+  };
+  if (adam_plain(h)) return launch(Adam<false>{a});
+  return launch(AdamOpt<false>{adam_opt_args(a, h)});
 }
 
 bool mmda_adam_opts_valid(const mmda_adam_opts* o) { return adam_opts_ok(o); }

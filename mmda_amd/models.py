@@ -1107,6 +1107,17 @@ class MISA(nn.Module):
         self.fusion_fp8 = bool(on)
         _lib.check(self._lib.mmda_misa_set_fusion_fp8(self._h, int(on)), "set_fusion_fp8")
 
+    def set_embed_background(self, on: bool, workgroups: int = 0):
+        """Plain dense mode: the Adam step of the table rows a batch does not index runs as a throttled background pass beside the
+        forward pass of the fused step (the bits of the one dense launch).  ``on=True``: in every eligible step (a model left alone runs
+        it where it pays, at batches of up to 32 samples); ``workgroups``: the throttle, 0 = the default.  Overrides MMDA_EMBED_BG /
+        MMDA_EMBED_BG_WGS for this model."""
+        _lib.check(self._lib.mmda_misa_set_embed_background(self._h, int(bool(on)), int(workgroups)), "set_embed_background")
+
+    def embed_background_active(self) -> bool:
+        """Whether the last fused training step ran the background pass over the embedding table."""
+        return self._lib.mmda_misa_embed_background_active(self._h) == 1
+
     def set_precision(self, precision: str):
         self.precision = precision
         _lib.check(self._lib.mmda_misa_set_mode(self._h, _lib.BF16 if precision == "bf16" else _lib.F32), "set_mode")
