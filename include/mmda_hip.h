@@ -438,6 +438,16 @@ int mmda_heads_bwd(const float* tcp, const float* scores, const float* dtcp, con
  * Gradients are ACCUMULATED into the d_* buffers.
  * cls: solver.py:373-385   sum_c mean_b BCE (log clamp -100) */
 int mmda_loss_cls(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores, void* stream);
+/* The classification criterion beyond the reference's plain BCE: a positive-class weight w_c >= 0 and a focusing exponent g,
+ *   l(s, y) = -( w_c y (1-s)^g lp + (1-y) s^g lq ),  lp = max(log s, -100), lq = max(log1p(-s), -100);  cls = sum_c mean_b l
+ *   dl/ds   = - w_c y ( (1-s)^g / max(s, 1e-12) - g (1-s)^(g-1) lp ) + (1-y) ( s^g / max(1-s, 1e-12) - g s^(g-1) lq )
+ * g = 0: F.binary_cross_entropy(s, y, weight = y w + (1 - y)); w = 1: the focal loss on probabilities; both: the plain criterion.
+ * focal_gamma: 0, or 1 .. 8 (between 0 and 1 the gradient diverges where the loss vanishes: refused).  n_weights: 0 (every weight 1)
+ * or ncls, which is then at most 16; pos_weight[c] finite and >= 0.  A NULL mmda_cls_opts* stands for the plain criterion everywhere;
+ * so does {0, 0}, and both run the expressions the entry points without _opts have always run.  Anything else: MMDA_EINVAL, no launch. */
+typedef struct mmda_cls_opts { float focal_gamma; int n_weights; float pos_weight[16]; } mmda_cls_opts;
+int mmda_loss_cls_opts(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores,
+                       const mmda_cls_opts* opts, void* stream);
 /* conf: solver.py:451-462 */
 int mmda_loss_conf(const float* scores, const float* tcp, const float* emo, int B, int ncls, float scale,
                    float* loss, float* dscores, float* dtcp, void* stream);
@@ -468,6 +478,15 @@ int mmda_loss_misc(const float* scores, const float* tcp, const float* emo, int 
                    int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
                    float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
                    float conf_w, int use_conf, void* stream);
+/* the same launch with the classification term under `opts` (NULL: mmda_loss_misc) */
+int mmda_loss_misc_opts(const float* scores, const float* tcp, const float* emo, int B, int ncls, float* d_scores, float* d_tcp,
+                        int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
+                        float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
+                        float conf_w, int use_conf, const mmda_cls_opts* opts, void* stream);
+/* Positives per class of an (N, C) fp32 label table, an entry counting as set when > 0 (the convention of mmda_eval_accumulate),
+ * ADDED into counts[C] (device, 64-bit, zeroed by the caller): one launch, integer sums throughout, so the result is exact and the
+ * same on every run.  1 <= C <= 16, N >= 0 (N == 0: MMDA_OK, no launch).  What mmda_amd.class_pos_weight turns into (N - n_c) / n_c. */
+int mmda_label_counts(const float* emo, int64_t N, int C, int64_t* counts, void* stream);
 /* Evaluation counts on the device (reference utils/eval.py:14-31 get_accuracy and the tp/fp/fn that sklearn's
  * f1/precision/recall in get_metrics :33-65 are functions of), ACCUMULATED into `state` = 3*C + 2 doubles (zeroed by the caller
  * before the first batch): tp[C], fp[C], fn[C], sum_i |y_i & p_i| / max(|y_i | p_i|, 1), number of samples.  pred / truth are
@@ -824,6 +843,12 @@ int mmda_misa_adam_step(mmda_misa* m, float lr, float clip, float grad_scale, in
  *   replay ring holds two scalars per update, a decayed zero-gradient step needs a third); clip_norm > 0 with embed_update sparse or
  *   the deferred table (their rows are updated where the row sums become final, before a norm exists). */
 int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, float clip_norm);
+/* The classification criterion of the handle (mmda_cls_opts above; NULL: the plain one, which is the default).  The handle keeps a
+ * copy, and every classification loss it computes follows it: mmda_misa_losses, mmda_misa_train_step, mmda_misa_train_step_encoded,
+ * accumulated steps, the loss-value launch a step defers to its backward pass, and the seed the forward stretch stores.  The step's
+ * plan does not depend on it: no launch is added or moved.  MMDA_EINVAL with nothing changed and nothing launched: a focal_gamma other
+ * than 0 or 1 .. 8, n_weights other than 0 or the model's ncls, weights for more than 16 classes, a negative or non-finite weight. */
+int mmda_misa_set_cls_loss(mmda_misa* m, const mmda_cls_opts* opts);
 /* One optimizer step from N micro-batches (config.accum_steps; the arithmetic of mmda_grad_accumulate above).  Every micro-batch is
  * mmda_misa_train_step with do_adam = 0; behind each but the last call mmda_misa_grad_accumulate, behind the last
  * mmda_misa_adam_step_accumulated with grad_scale = 1/N.  The runtime owns none of the memory:

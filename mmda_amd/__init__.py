@@ -11,7 +11,7 @@ fusion block and the heads of a model with frozen encoders from stored encoder o
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
 from .config import Config, get_config, make_config  # noqa: F401
-from .data import DeviceDataset, DeviceLoader, batch_plan  # noqa: F401
+from .data import DeviceDataset, DeviceLoader, batch_plan, class_pos_weight  # noqa: F401
 from .inference import FIELDS, InferencePass, InferenceResult, inference_plan  # noqa: F401
 from .encoded import EncodedBatch, EncodedLoader, EncoderCache  # noqa: F401
 from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_grid  # noqa: F401

@@ -144,6 +144,19 @@ class AdamOpts(C.Structure):
                 ("scale_dev", C.c_void_p)]
 
 
+class ClsOpts(C.Structure):
+    """mmda_cls_opts: the classification criterion beyond plain BCE (n_weights: 0, or the number of classes)"""
+    _fields_ = [("focal_gamma", C.c_float), ("n_weights", C.c_int), ("pos_weight", C.c_float * 16)]
+
+
+def cls_opts(pos_weight, focal_gamma):
+    """``byref(ClsOpts)`` of a setting ``step_rules.cls_setting`` returned, or None (a NULL pointer) for the plain criterion."""
+    if pos_weight is None and focal_gamma == 0.0:
+        return None
+    w = tuple(pos_weight or ())
+    return C.byref(ClsOpts(focal_gamma=focal_gamma, n_weights=len(w), pos_weight=(C.c_float * 16)(*w)))
+
+
 class InferSrc(C.Structure):
     """mmda_infer_src: what a forward left in the workspace, B columns"""
     _fields_ = [("scores", C.c_void_p), ("labels", C.c_void_p), ("tcp", C.c_void_p), ("hfused", C.c_void_p), ("x6", C.c_void_p),
@@ -222,6 +235,11 @@ SIGNATURES = {
     "mmda_heads_fwd": (_I, [_P, _I, _I, _F, _P, _P, _P, _F, _U64, _I, _P]),
     "mmda_heads_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _U64, _I, _P]),
     "mmda_loss_cls": (_I, [_P, _P, _I, _I, _F, _P, _P, _P]),
+    "mmda_loss_cls_opts": (_I, [_P, _P, _I, _I, _F, _P, _P, C.POINTER(ClsOpts), _P]),
+    "mmda_loss_misc_opts": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I64, _F, _P, _P, _P, _F, _F, _F, _F, _I,
+                                 C.POINTER(ClsOpts), _P]),
+    "mmda_label_counts": (_I, [_P, _I64, _I, _P, _P]),
+    "mmda_misa_set_cls_loss": (_I, [_P, C.POINTER(ClsOpts)]),
     "mmda_loss_conf": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "mmda_loss_diff": (_I, [_P, _I64, _I, _I, _F, _P, _P, _P, _P]),
     "mmda_loss_diff_work_floats": (_I64, [_I, _I]),

@@ -33,6 +33,22 @@ def _json_object(text):
     return value
 
 
+def _pos_weight(text):
+    """--pos_weight balanced, or a JSON list: --pos_weight '[1, 4, 4, 11, 5, 9]'"""
+    import json
+    if text.strip().lower() == "balanced":
+        return "balanced"
+    if text.strip().lower() in ("none", ""):
+        return None
+    try:
+        value = json.loads(text)
+    except ValueError:
+        value = None
+    if not isinstance(value, list) or not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in value):
+        raise argparse.ArgumentTypeError("'balanced' or a JSON list of numbers is expected")
+    return [float(x) for x in value]
+
+
 class Config(object):
     """Attribute bag (reference config.py:71-96).  'optimizer' names resolve to mmda_amd.optim classes."""
 
@@ -91,6 +107,10 @@ DEFAULTS = dict(
     # checkpoint (mmda_amd/calibrate.py; objective: what eval_mode names) and the final test evaluation decides with them; "none": the
     # reference's loop, which decides with `threshold` throughout
     calibrate="none",
+    # the classification criterion beyond the reference's plain BCE: pos_weight -- None, one weight per class on the
+    # positive term (BCEWithLogitsLoss's convention), or "balanced", which Solver.build() resolves to (N - n_c) / n_c from the training
+    # set's labels -- and the focal exponent focal_gamma (0, or 1 .. 8).  The defaults are the reference's criterion, bit for bit.
+    pos_weight=None, focal_gamma=0.0,
 )
 
 
@@ -105,6 +125,8 @@ def get_config(parse=True, **optional_kwargs):
             parser.add_argument(f"--{k}", type=_json_object, default=dict(v))
         elif k == "clip_norm":
             parser.add_argument(f"--{k}", type=float, default=None)
+        elif k == "pos_weight":
+            parser.add_argument(f"--{k}", type=_pos_weight, default=None)
         elif k == "calibrate":
             parser.add_argument(f"--{k}", choices=("none", "global", "per_class"), default=v)
         elif v is None:

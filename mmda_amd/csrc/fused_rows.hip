@@ -470,6 +470,9 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_a_kernel(FusedFwdA P) {
   for (int i = wave; i < ntok; i += FR_THREADS / 64) ln_fwd_row<2>(P.ln1, (i / nb) * B + b0 + (i % nb), lane);
 }
 
+// CLS_OPTS: the seed of the class-weighted / focal criterion (P.cls; cls_term.h).  An instance of its own, so that the plain criterion's
+// kernel -- the default step's -- is the code it was, registers and all.
+template <bool CLS_OPTS>
 __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
   __shared__ f4 sp[2 * 12 * 32];                         // sum_parts_rows: two halves x (<= 12 rows x 32 column groups)
   const int b0 = (int)blockIdx.x * P.nb;
@@ -512,7 +515,13 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
         P.labels[b * P.ncls + k] = sc > P.threshold ? 1.f : 0.f;
         if (P.d_scores) {                                               // (the expression of misc_losses_kernel, losses.hip)
           const float yv = P.emo[b * P.ncls + k];
+          if constexpr (CLS_OPTS) {
+            float v, d;
+            cls_term(P.cls, sc, yv, k, v, d);
+            P.d_scores[b * P.ncls + k] = d / B;
+          } else {
           P.d_scores[b * P.ncls + k] = (sc - yv) / fmaxf(sc * (1.f - sc), 1e-12f) / B;
+          }
         }
       }
     }
@@ -678,7 +687,9 @@ int mmda_fused_fwd_a(const FusedFwdA* a, void* stream) {
 
 int mmda_fused_fwd_c(const FusedFwdC* a, void* stream) {
   if (!a || a->B <= 0 || a->nb <= 0 || a->nb > 2 || a->hs != 128 || a->ln2.n != 128 || (a->d_scores && !a->emo)) return MMDA_EINVAL;
-  hipLaunchKernelGGL(fused_fwd_c_kernel, dim3(ceil_div(a->B, a->nb)), dim3(FR_THREADS), 0, (hipStream_t)stream, *a);
+  const bool opts = a->d_scores && !cls_plain(a->cls);
+  hipLaunchKernelGGL(opts ? fused_fwd_c_kernel<true> : fused_fwd_c_kernel<false>, dim3(ceil_div(a->B, a->nb)), dim3(FR_THREADS), 0,
+                     (hipStream_t)stream, *a);
   MMDA_CHECK_LAUNCH("mmda_fused_fwd_c");
   return MMDA_OK;
 }

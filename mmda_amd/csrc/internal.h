@@ -95,6 +95,9 @@ bool mmda_loss_cmd_sets_flag(int B, int D);
 int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
                              float value_scale, float* loss, float* dx, void* stream, unsigned* flag, unsigned value);
 
+// what mmda_loss_cls_opts, mmda_loss_misc_opts and mmda_misa_set_cls_loss accept for a model of ncls classes (o == nullptr: plain, valid)
+bool mmda_cls_opts_valid(const mmda_cls_opts* o, int ncls);
+
 // ---- lstm.hip / embed_rows.hip: the launch that reads a step's ids, stamping their rows on its way (st == nullptr: the C ABI's call)
 int mmda_lstm_pack_convert_transpose_stamped(int n, const int* H, const float* const* whh, void* const* packed_fwd, void* const* packed_bwd,
                                              void* const* packed_c, const mmda_convert_job* jobs, int njobs, const mmda_transpose_job* tjobs,

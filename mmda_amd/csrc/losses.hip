@@ -4,6 +4,7 @@
 // These are batch-statistic reductions over (B, 128)-sized tensors: latency work on a handful of workgroups.
 #include "common.h"
 #include "internal.h"
+#include "cls_term.h"
 
 namespace {
 
@@ -61,15 +62,25 @@ __device__ __forceinline__ void loss_parts_add(const float* __restrict__ parts, 
 // ------------------------------------------------------------------------------------------------ cls (BCE)
 // loss = sum_c (1/B) sum_b -(y log s + (1-y) log(1-s)), logs clamped at -100 (torch BCELoss);
 // grad  = (s - y) / max(s (1-s), 1e-12) / B   (torch binary_cross_entropy_backward)
+// With class weights or a focal exponent (ct; cls_term.h) the element is cls_term's; the plain criterion keeps the expression above.
 __global__ __launch_bounds__(256) void cls_kernel(const float* __restrict__ s, const float* __restrict__ y, int B, int ncls,
-                                                  float scale, float* loss, float* ds) {
+                                                  float scale, float* loss, float* ds, ClsTerm ct) {
   __shared__ float red[16];
   float acc = 0.f;
+  if (cls_plain(ct)) {                                     // launch-uniform
   for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
     float sv = s[e], yv = y[e];
     float lp = fmaxf(logf(sv), -100.f), lq = fmaxf(log1pf(-sv), -100.f);
     acc += -(yv * lp + (1.f - yv) * lq);
     if (ds) ds[e] += scale * (sv - yv) / fmaxf(sv * (1.f - sv), 1e-12f) / B;
+  }
+  } else {
+  for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
+    float v, d;
+    cls_term(ct, s[e], y[e], e % ncls, v, d);
+    acc += v;
+    if (ds) ds[e] += scale * d / B;
+  }
   }
   float t = block_sum(acc, red);
   if (threadIdx.x == 0 && loss) atomicAdd(loss, t / B);
@@ -133,6 +144,7 @@ struct MiscLossArgs {
   float* parts;                             // one partial per workgroup (role order); the last workgroup adds them in that order
   float dw, sw, rw, cw; int use_conf, with_conf;
   int recon_blocks;
+  ClsTerm ct;                               // the classification criterion (cls_term.h); plain: role 0's own expression
 };
 
 __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
@@ -142,11 +154,20 @@ __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
   const int role = blockIdx.x;
   if (role == 0) {
     float acc = 0.f;
+    if (cls_plain(a.ct)) {                                 // launch-uniform
     for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
       float sv = a.scores[e], yv = a.emo[e];
       float lp = fmaxf(logf(sv), -100.f), lq = fmaxf(log1pf(-sv), -100.f);
       acc += -(yv * lp + (1.f - yv) * lq);
       if (a.d_scores) atomicAdd(&a.d_scores[e], (sv - yv) / fmaxf(sv * (1.f - sv), 1e-12f) / B);
+    }
+    } else {
+    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
+      float v, d;
+      cls_term(a.ct, a.scores[e], a.emo[e], e % ncls, v, d);
+      acc += v;
+      if (a.d_scores) atomicAdd(&a.d_scores[e], d / B);
+    }
     }
     float t = block_sum(acc, red);
     if (threadIdx.x == 0) a.parts[role] = t / B;
@@ -946,7 +967,59 @@ __global__ __launch_bounds__(256) void eval_counts_kernel(const float* __restric
   if (lead && cnt != 0.0) { atomicAdd(&state[3 * C], jac); atomicAdd(&state[3 * C + 1], cnt); }
 }
 
+// ------------------------------------------------------------------------------------------------ label counts
+// counts[c] += rows of the (N, C) table with an entry > 0 in column c.  Integers from the lanes up: a wave's sum by shuffles, the
+// workgroup's four through LDS, one 64-bit integer atomic per class and workgroup -- exact, and the same bits whatever the arrival order.
+__global__ __launch_bounds__(256) void label_counts_kernel(const float* __restrict__ emo, int64_t N, int C, unsigned long long* counts) {
+  __shared__ unsigned part[4][EVAL_MAXC];
+  unsigned n[EVAL_MAXC];
+#pragma unroll
+  for (int c = 0; c < EVAL_MAXC; ++c) n[c] = 0u;
+  // (a thread's count stays below 2^32: at most N / 256 rows each, N checked by the launcher)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int c = 0; c < EVAL_MAXC; ++c)
+      if (c < C) n[c] += emo[i * C + c] > 0.f ? 1u : 0u;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < EVAL_MAXC; ++c) {
+    unsigned v = n[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) part[wave][c] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < C) {
+    const int c = threadIdx.x;
+    const unsigned long long t = (unsigned long long)part[0][c] + part[1][c] + part[2][c] + part[3][c];
+    if (t) atomicAdd(&counts[c], t);
+  }
+}
+
 }  // namespace
+
+bool mmda_cls_opts_valid(const mmda_cls_opts* o, int ncls) {
+  if (!o) return true;
+  const float g = o->focal_gamma;
+  if (!(g == 0.f || (g >= 1.f && g <= 8.f))) return false;                    // (NaN fails both)
+  if (o->n_weights == 0) return true;
+  if (o->n_weights != ncls || ncls > CLS_MAXW) return false;
+  for (int c = 0; c < ncls; ++c)
+    if (!(o->pos_weight[c] >= 0.f) || !(o->pos_weight[c] <= 3.402823466e38f)) return false;
+  return true;
+}
+
+extern "C" int mmda_label_counts(const float* emo, int64_t N, int C, int64_t* counts, void* stream) {
+  if (!emo || !counts || N < 0 || C <= 0 || C > EVAL_MAXC || ((uintptr_t)counts & 7) || N > ((int64_t)1 << 40)) return MMDA_EINVAL;
+  if (N == 0) return MMDA_OK;
+  const int64_t b = (N + 255) / 256;
+  const int blocks = (int)(b > 256 ? 256 : b);
+  hipLaunchKernelGGL(label_counts_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, emo, N, C,
+                     reinterpret_cast<unsigned long long*>(counts));
+  MMDA_CHECK_LAUNCH("mmda_label_counts");
+  return MMDA_OK;
+}
 
 extern "C" int mmda_heads_fwd(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
                               float drop_p, uint64_t seed, int site, void* stream) {
@@ -968,12 +1041,18 @@ extern "C" int mmda_heads_bwd(const float* tcp, const float* scores, const float
   return MMDA_OK;
 }
 
-extern "C" int mmda_loss_cls(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores,
-                             void* stream) {
-  if (!scores || !emo || B <= 0 || ncls <= 0) return MMDA_EINVAL;
-  hipLaunchKernelGGL(cls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, emo, B, ncls, scale, loss, dscores);
+extern "C" int mmda_loss_cls_opts(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores,
+                                  const mmda_cls_opts* opts, void* stream) {
+  if (!scores || !emo || B <= 0 || ncls <= 0 || !mmda_cls_opts_valid(opts, ncls)) return MMDA_EINVAL;
+  hipLaunchKernelGGL(cls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, emo, B, ncls, scale, loss, dscores,
+                     cls_term_of(opts));
   MMDA_CHECK_LAUNCH("mmda_loss_cls");
   return MMDA_OK;
+}
+
+extern "C" int mmda_loss_cls(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores,
+                             void* stream) {
+  return mmda_loss_cls_opts(scores, emo, B, ncls, scale, loss, dscores, nullptr, stream);
 }
 
 extern "C" int mmda_loss_conf(const float* scores, const float* tcp, const float* emo, int B, int ncls, float scale, float* loss,
@@ -1207,9 +1286,19 @@ extern "C" int mmda_loss_misc(const float* scores, const float* tcp, const float
                               int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
                               float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
                               float conf_w, int use_conf, void* stream) {
+  return mmda_loss_misc_opts(scores, tcp, emo, B, ncls, d_scores, d_tcp, with_conf, conf_grads, conf_scale, recon, orig, n_recon, recon_scale,
+                             d_recon, d_orig, L, diff_w, sim_w, recon_w, conf_w, use_conf, nullptr, stream);
+}
+
+extern "C" int mmda_loss_misc_opts(const float* scores, const float* tcp, const float* emo, int B, int ncls, float* d_scores, float* d_tcp,
+                                   int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
+                                   float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
+                                   float conf_w, int use_conf, const mmda_cls_opts* opts, void* stream) {
   if (!scores || !emo || !recon || !orig || !L || B <= 0 || ncls <= 0 || n_recon <= 0) return MMDA_EINVAL;
   if (with_conf && (!tcp || ncls != 6)) return MMDA_EINVAL;
+  if (!mmda_cls_opts_valid(opts, ncls)) return MMDA_EINVAL;
   MiscLossArgs a = {};
+  a.ct = cls_term_of(opts);
   a.scores = scores; a.tcp = tcp; a.emo = emo; a.B = B; a.ncls = ncls; a.d_scores = d_scores; a.d_tcp = d_tcp;
   a.conf_grads = conf_grads && d_scores && d_tcp; a.conf_scale = conf_scale; a.with_conf = with_conf;
   a.recon = recon; a.orig = orig; a.n_recon = n_recon; a.recon_inv_n = 1.0f / (float)n_recon; a.recon_scale = recon_scale;

@@ -368,6 +368,10 @@ struct mmda_misa {
   // norm, so such a step takes no early optimizer pass.
   mmda_adam_opts adam = {0.9f, 0.999f, 1e-8f, 0.f, 0, nullptr};
   float clip_norm = 0.f;
+  // The classification criterion (mmda_misa_set_cls_loss): what every loss launch of the handle and the forward stretch's seed are
+  // given (cls()); cls_on == 0: the plain one.  plan_step does not read it.
+  mmda_cls_opts cls_opts = {}; int cls_on = 0;
+  const mmda_cls_opts* cls() const { return cls_on ? &cls_opts : nullptr; }
   int fusion_fp8 = 0;
   int embed_update = EU_DENSE;
   // Frozen parameters (mmda_misa_set_trainable).  `runs`: the trainable ranges of the bucket, never merged across rnn2_begin, rnn1_begin
@@ -1222,6 +1226,13 @@ extern "C" int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, floa
   return MMDA_OK;
 }
 
+extern "C" int mmda_misa_set_cls_loss(mmda_misa* m, const mmda_cls_opts* opts) {
+  if (!m || !mmda_cls_opts_valid(opts, m->cfg.ncls)) return MMDA_EINVAL;
+  m->cls_on = opts && !(opts->n_weights == 0 && opts->focal_gamma == 0.f);
+  m->cls_opts = m->cls_on ? *opts : mmda_cls_opts{};
+  return MMDA_OK;
+}
+
 extern "C" int mmda_misa_set_embed_update(mmda_misa* m, int mode) {
   if (!m) return MMDA_EINVAL;
   if (mode != EU_DENSE && mode != EU_SPARSE && mode != EU_FROZEN) return MMDA_EINVAL;
@@ -1616,7 +1627,7 @@ void Pass::fwd_fusion_skinny() {
       f.hfused = WS(w.hfused); f.head_w = PP(p.head_w); f.head_b = PP(p.head_b); f.logits = WS(w.logits);
       f.threshold = c.threshold; f.tcp = WS(w.tcp); f.scores = WS(w.scores); f.labels = WS(w.labels);
       f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS;
-      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(w.d_scores); }
+      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(w.d_scores); f.cls = cls_term_of(m->cls()); }
       rc = mmda_fused_fwd_c(&f, s);
     }
   } else {
@@ -1808,11 +1819,11 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
     m->misc_deferred = emo;
     return MMDA_OK;
   }
-  return mmda_loss_misc(WS(w.scores), WS(w.tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(w.d_scores) : nullptr,
-                        (with_grads && !s_cls) ? WS(w.d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext, c.conf_weight,
-                        WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(w.d_recon) : nullptr,
-                        (with_grads && !s_recon) ? WS(w.d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
-                        c.use_confidNet, stream);
+  return mmda_loss_misc_opts(WS(w.scores), WS(w.tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(w.d_scores) : nullptr,
+                             (with_grads && !s_cls) ? WS(w.d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext,
+                             c.conf_weight, WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(w.d_recon) : nullptr,
+                             (with_grads && !s_recon) ? WS(w.d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
+                             c.use_confidNet, m->cls(), stream);
 }
 
 // =============================================================================================== backward
@@ -2031,9 +2042,9 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   rc = side_fork(m, s, &ss);
   if (!rc && m->misc_deferred) {
     // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
-    rc = mmda_loss_misc(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
-                          WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
-                          c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, ss);
+    rc = mmda_loss_misc_opts(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
+                             WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
+                             c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, m->cls(), ss);
     m->misc_deferred = nullptr;
   }
   if (!rc && P.skinny) rc = mmda_add(WS(w.x6), WS(w.x6 + 3 * BH), WS(w.rsum), 3 * BH, ss);

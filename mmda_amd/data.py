@@ -218,6 +218,53 @@ class DeviceDataset:
                    None if emo is None else up(emo), up(sentiment), lengths, segments)
 
 
+def class_pos_weight(labels, cap=None):
+    """Per-class positive weights ``(N - n_c) / n_c`` of an (N, C) label table (``BCEWithLogitsLoss``'s ``pos_weight`` convention),
+    n_c the rows with an entry > 0 in class c: what ``config.pos_weight = "balanced"`` resolves to.  ``labels``: a tensor, or a
+    ``DeviceDataset`` (its ``emo`` table).  On the device the counts are one ``mmda_label_counts`` launch, exact 64-bit integers; a CPU
+    tensor is counted with a torch sum.  A class with no positive gets 1.0; ``cap`` clips from above.  Returns C float64 values on the
+    host."""
+    from . import _lib
+    if isinstance(labels, DeviceDataset):
+        if labels.emo is None:
+            raise ValueError("class_pos_weight: the dataset has no emotion labels")
+        labels = labels.emo
+    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[1] < 1:
+        raise ValueError("class_pos_weight: an (N, C) label tensor or a DeviceDataset is expected")
+    if cap is not None and not float(cap) > 0.0:
+        raise ValueError(f"class_pos_weight: cap must be > 0, not {cap}")
+    N, C = int(labels.shape[0]), int(labels.shape[1])
+    if labels.is_cuda:
+        lab = labels.detach().to(torch.float32).contiguous()
+        counts = torch.zeros(C, dtype=torch.int64, device=lab.device)
+        _lib.check(_lib.load().mmda_label_counts(lab.data_ptr(), N, C, counts.data_ptr(), _lib.stream_ptr()), "mmda_label_counts")
+        n = counts.cpu()
+    else:
+        n = (labels.detach() > 0).sum(dim=0).to(torch.int64)
+    n = n.to(torch.float64)
+    w = torch.where(n > 0, (N - n) / n.clamp(min=1.0), torch.ones_like(n))
+    return w if cap is None else w.clamp(max=float(cap))
+
+
+def host_labels(dataset):
+    """One host pass over a dataset's labels -> (N, C) float tensor of 0 / 1, for loaders whose data is not resident on the device.  An
+    item is a reference-style sample ``(features, label (1, 7), segment)`` -- columns 1.. of the label, as collate_fn reads them -- or an
+    already collated batch (its fifth entry is the emotion table)."""
+    import numpy as np
+    rows = []
+    for item in dataset:
+        if len(item) == 3:
+            lab = np.nan_to_num(np.asarray(item[1], dtype=np.float64)).reshape(1, -1)
+            if lab.shape[1] < 2:
+                raise ValueError("pos_weight='balanced': the dataset's samples carry no emotion labels")
+            rows.append(torch.from_numpy((lab[:, 1:] > 0.0).astype(np.float32)))
+        else:
+            rows.append((torch.as_tensor(item[4]).detach().cpu().float() > 0).float())
+    if not rows:
+        raise ValueError("pos_weight='balanced': the training set is empty")
+    return torch.cat(rows, 0)
+
+
 def _kept(m, batch_size, drop_last=False, shard=None):
     """How much of an index sequence of ``m`` entries one rank batches, as ``(prefix, per_rank, batches)``: the sequence is cut to its
     first ``prefix`` entries (a multiple of ``world * batch_size`` under ``drop_last``, else of ``world``; all of it without a shard),

@@ -137,6 +137,12 @@ class MISA(nn.Module):
         if self.fusion_fp8:
             _lib.check(lib.mmda_misa_set_fusion_fp8(h, 1), "set_fusion_fp8")
         _lib.check(lib.mmda_misa_set_embed_update(h, EMBED_UPDATE[self.embed_update]), "set_embed_update")
+        # the classification criterion (config.pos_weight, config.focal_gamma).  "balanced" needs the training set's
+        # labels: Solver.build() resolves it and calls set_cls_loss; until then the weights are off
+        pw = getattr(config, "pos_weight", None)
+        if isinstance(pw, str) and pw != "balanced":
+            raise ValueError("config.pos_weight must be None, a list of num_classes floats or 'balanced'")
+        self.set_cls_loss(None if isinstance(pw, str) else pw, getattr(config, "focal_gamma", 0.0))
         self._layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self._native_names: List[str] = []                  # mmda_misa_param_info order = ascending bucket offset
         for i in range(lib.mmda_misa_num_params(h)):
@@ -353,6 +359,16 @@ class MISA(nn.Module):
             self.embed.weight.grad = None
         if mode == "deferred" and bound:
             self._bind_deferred()
+
+    def set_cls_loss(self, pos_weight=None, focal_gamma: float = 0.0):
+        """The classification criterion of every step and loss of this model from now on: ``pos_weight`` -- None or one
+        weight >= 0 per class on the positive term -- and the focal exponent ``focal_gamma`` (0, or 1 .. 8).  What is refused is raised
+        by name (step_rules.CLS_RULES) with nothing changed.  ``self.cls_loss`` reports the setting in force; weights that are all 1
+        count as none, so with ``focal_gamma = 0`` the step is the default one."""
+        w, g = step_rules.cls_setting(pos_weight, focal_gamma, self.output_size)
+        _lib.check(self._lib.mmda_misa_set_cls_loss(self._h, _lib.cls_opts(w, g)), "mmda_misa_set_cls_loss")
+        self.cls_loss = dict(pos_weight=w, focal_gamma=g)
+        return self.cls_loss
 
     # ------------------------------------------------------------------ frozen parameters
     def _match(self, prefixes) -> List[str]:

@@ -76,6 +76,10 @@ class Solver(object):
             step_rules.check(frozen=bool(hasattr(self.model, "frozen_names") and self.model.frozen_names(beyond_embed_update=True)),
                              exchange=torch.distributed.is_available() and torch.distributed.is_initialized())
         self.model.to(self.device)
+        self.cls_pos_weight = None
+        if isinstance(getattr(cfg, "pos_weight", None), str):
+            self.cls_pos_weight = self._balanced_pos_weight()
+            self.model.set_cls_loss(self.cls_pos_weight, getattr(cfg, "focal_gamma", 0.0))
         if self.is_train:
             self.optimizer = cfg.optimizer([p for p in self.model.parameters() if p.requires_grad], lr=cfg.learning_rate, **opt_kwargs)
             if hasattr(self.optimizer, "attach"):
@@ -86,6 +90,30 @@ class Solver(object):
             self.dp = DataParallelSync(global_stats=bool(getattr(cfg, "dp_global_stats", False)))
             self.dp.broadcast_parameters(self.model)
         return self
+
+    def _balanced_pos_weight(self):
+        """config.pos_weight = "balanced": (N - n_c) / n_c per class from the training set's labels -- one launch over the label table
+        where that is resident on the device (DeviceLoader, EncodedLoader), one host pass over ``loader.dataset`` otherwise."""
+        from .data import DeviceLoader, class_pos_weight, host_labels
+        cfg, loader = self.train_config, self.train_data_loader
+        if cfg.pos_weight != "balanced":
+            raise ValueError("config.pos_weight must be None, a list of num_classes floats or 'balanced'")
+        if loader is None or (not isinstance(loader, EncodedLoader) and not hasattr(loader, "dataset")):
+            raise ValueError("pos_weight='balanced' is resolved from the training set: the solver has no training loader with a dataset "
+                             "(give the weights as a list, or mmda_amd.class_pos_weight(labels))")
+        if isinstance(loader, DeviceLoader):
+            labels = loader.dataset
+        elif isinstance(loader, EncodedLoader):
+            labels = loader.cache.emo
+            if labels is None:
+                raise ValueError("pos_weight='balanced': the encoder cache holds no emotion labels")
+        else:
+            labels = host_labels(loader.dataset)
+        return [float(x) for x in class_pos_weight(labels)]
+
+    def _cls_setting(self):
+        """the model's classification criterion, as keyword arguments of bce_sum_over_classes / DeviceEval.add_cls_loss"""
+        return dict(getattr(self.model, "cls_loss", None) or {})
 
     # ------------------------------------------------------------------ train (solver.py:103-307)
     def _micro_batches(self):
@@ -265,7 +293,7 @@ class Solver(object):
                     if acc_dev is None:
                         acc_dev = DeviceEval(predicted_labels.shape[1], predicted_labels.device)
                     acc_dev.update(predicted_labels, emo_label)
-                    acc_dev.add_cls_loss(predicted_scores, emo_label)
+                    acc_dev.add_cls_loss(predicted_scores, emo_label, **self._cls_setting())
                 else:
                     eval_loss.append(self.get_cls_loss(predicted_scores, emo_label).item())
                 y_pred.append(predicted_labels.detach())
@@ -315,7 +343,7 @@ class Solver(object):
             labels = torch.empty_like(s)
             _lib.check(lib.mmda_eval_accumulate_thr(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], thr.data_ptr(), labels.data_ptr(),
                                                     acc_dev.state.data_ptr(), _lib.stream_ptr()), "mmda_eval_accumulate_thr")
-            acc_dev.add_cls_loss(scores, emo_label)
+            acc_dev.add_cls_loss(scores, emo_label, **self._cls_setting())
             y_pred.append(labels)
             y_true.append(emo_label.detach())
         y_true = torch.cat(y_true, 0).cpu().numpy().squeeze() if y_true else np.zeros((0,))
@@ -404,7 +432,7 @@ class Solver(object):
 
     # ------------------------------------------------------------------ getters (solver.py:373-462)
     def get_cls_loss(self, predicted_scores, emo_label):
-        return F.bce_sum_over_classes(predicted_scores, emo_label.type(torch.float))
+        return F.bce_sum_over_classes(predicted_scores, emo_label.type(torch.float), **self._cls_setting())
 
     def get_domain_loss(self):
         if self.train_config.use_cmd_sim:

@@ -30,6 +30,52 @@ RULES = (
 )
 
 
+# What the classification criterion refuses.  These are refusals of a SETTING, raised where it is made (MISA.set_cls_loss,
+# bce_sum_over_classes, DeviceEval.add_cls_loss), not of a step: the criterion combines with every step form, so RULES has no entry for it.
+CLS_MAX_CLASSES = 16
+CLS_RULES = (
+    ("cls_gamma", "focal_gamma must be 0 or between 1 and 8, not {gamma}: for 0 < gamma < 1 the gradient's (1-s)^(gamma-1) diverges where "
+                  "the loss vanishes"),
+    ("cls_weight_count", "pos_weight has {n} entries, the model {ncls} classes"),
+    ("cls_weight_classes", "pos_weight is built for at most 16 classes, not {ncls}"),
+    ("cls_weight_value", "pos_weight must be finite and >= 0, not {bad} (class {c})"),
+)
+
+
+def cls_verdict(pos_weight, focal_gamma, num_classes: int):
+    """(rule, format values) of the first rule that refuses the setting, or None.  ``pos_weight``: None or a sequence of numbers."""
+    try:
+        g = float(focal_gamma)
+    except (TypeError, ValueError):
+        return "cls_gamma", dict(gamma=repr(focal_gamma))
+    if not (g == 0.0 or 1.0 <= g <= 8.0):
+        return "cls_gamma", dict(gamma=focal_gamma)
+    if pos_weight is None:
+        return None
+    w = list(pos_weight)
+    if len(w) != num_classes:
+        return "cls_weight_count", dict(n=len(w), ncls=num_classes)
+    if num_classes > CLS_MAX_CLASSES:
+        return "cls_weight_classes", dict(ncls=num_classes)
+    for c, x in enumerate(w):
+        x = float(x)
+        if not (0.0 <= x < float("inf")):
+            return "cls_weight_value", dict(bad=x, c=c)
+    return None
+
+
+def cls_setting(pos_weight, focal_gamma, num_classes: int):
+    """The setting as the native side takes it, (weights tuple or None, gamma), or MMDAError with the text of the rule that refuses it.
+    Weights that are all 1 are passed down as None: with gamma = 0 that is the plain criterion, whose bits are the reference's."""
+    hit = cls_verdict(pos_weight, focal_gamma, num_classes)
+    if hit is not None:
+        raise MMDAError(dict(CLS_RULES)[hit[0]].format(**hit[1]))
+    w = None if pos_weight is None else tuple(float(x) for x in pos_weight)
+    if w is not None and all(x == 1.0 for x in w):
+        w = None
+    return w, float(focal_gamma)
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:

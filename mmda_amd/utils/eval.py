@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..step_rules import cls_setting
 
 KEYS = ["acc", "f1", "precision", "recall", "micro_f1", "micro_precision", "micro_recall", "weighted_f1", "weighted_precision",
         "weighted_recall"]
@@ -77,11 +78,13 @@ class DeviceEval:
         _lib.check(self._lib.mmda_eval_accumulate(p.data_ptr(), t.data_ptr(), p.shape[0], self.C, self.state.data_ptr(),
                                                   _lib.stream_ptr()), "mmda_eval_accumulate")
 
-    def add_cls_loss(self, scores: torch.Tensor, truth: torch.Tensor):
-        """adds this batch's classification loss (solver.py:373-385) to the running sum, on the device"""
+    def add_cls_loss(self, scores: torch.Tensor, truth: torch.Tensor, pos_weight=None, focal_gamma=0.0):
+        """adds this batch's classification loss (solver.py:373-385; under ``pos_weight`` / ``focal_gamma`` the criterion of
+        ``bce_sum_over_classes``) to the running sum, on the device"""
         s = scores.detach().to(torch.float32).contiguous(); t = truth.detach().to(torch.float32).contiguous()
-        _lib.check(self._lib.mmda_loss_cls(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], 1.0, self.loss_sum.data_ptr(), None,
-                                           _lib.stream_ptr()), "mmda_loss_cls")
+        opts = _lib.cls_opts(*cls_setting(pos_weight, focal_gamma, s.shape[1]))
+        _lib.check(self._lib.mmda_loss_cls_opts(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], 1.0, self.loss_sum.data_ptr(), None,
+                                                opts, _lib.stream_ptr()), "mmda_loss_cls_opts")
         self.batches += 1
 
     def result(self):

@@ -13,6 +13,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from .. import _lib
+from ..step_rules import cls_setting
 
 
 def _need_cuda(*ts):
@@ -102,18 +103,21 @@ class CMD(nn.Module):
         return cmd_loss_multi([x1, x2], [(0, 1)], n_moments)
 
 
-def bce_sum_over_classes(scores, emo):
-    """sum_c BCELoss_mean(scores[:,c], emo[:,c])   (solver.py:373-385)"""
+def bce_sum_over_classes(scores, emo, pos_weight=None, focal_gamma=0.0):
+    """sum_c BCELoss_mean(scores[:,c], emo[:,c])   (solver.py:373-385); with ``pos_weight`` (one weight per class on the positive term)
+    and / or ``focal_gamma`` the class-weighted / focal criterion of DESIGN.md 4k.  The defaults -- and weights that are all 1 -- are
+    the plain criterion's launch."""
     _need_cuda(scores, emo)
     lib = _lib.load()
+    opts = _lib.cls_opts(*cls_setting(pos_weight, focal_gamma, scores.shape[1]))
 
     def run(s, y):
         s = s.contiguous().float(); y = y.contiguous().float()
         B, nc = s.shape
         loss = torch.zeros((), device=s.device)
         ds = torch.zeros_like(s)
-        _lib.check(lib.mmda_loss_cls(s.data_ptr(), y.data_ptr(), B, nc, 1.0, loss.data_ptr(), ds.data_ptr(), _lib.stream_ptr()),
-                   "mmda_loss_cls")
+        _lib.check(lib.mmda_loss_cls_opts(s.data_ptr(), y.data_ptr(), B, nc, 1.0, loss.data_ptr(), ds.data_ptr(), opts,
+                                          _lib.stream_ptr()), "mmda_loss_cls_opts")
         return loss, (ds, None)
 
     return _GradInForward.apply(run, scores, emo)
