@@ -5,7 +5,7 @@
 // (~1 us each: store drain + L2 round trip) instead of kernel boundaries (5 - 12 us each for these latency-bound sizes).
 #pragma once
 #include "../../include/mmda_hip.h"
-#include "cls_term.h"
+#include "loss_terms.h"
 #include <stdint.h>
 
 // stretch C: heads backward -> d_hfused = d_logits W_head -> LayerNorm 2 backward (d_x1, d_f2 + its gamma/beta gradients)
@@ -70,7 +70,7 @@ struct FusedFwdC {
   float threshold; float* tcp; float* scores; float* labels; float p_cls; uint64_t seed; int site_cls;
   // optional (training step): the classification loss's gradient seed d_scores = (s - y) / max(s (1 - s), 1e-12) / B, stored here
   const float* emo; float* d_scores;
-  // ... or, with class weights / a focal exponent, cls_term's gradient / B (cls_term.h; a kernel instance of its own)
+  // ... or, with class weights / a focal exponent, cls_term's gradient / B (loss_terms.h; a kernel instance of its own)
   ClsTerm cls;
 };
 // The feed-forward pair of the transformer layer (linear1 hs -> F with relu + dropout, linear2 F -> hs) as ONE launch per direction,

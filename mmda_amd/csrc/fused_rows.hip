@@ -205,17 +205,7 @@ __global__ __launch_bounds__(FR_THREADS) void fused_bwd_c_kernel(FusedBwdC P) {
   // heads backward: sigmoid' (and the dropout of the class scores) into d_logits
   for (int e = threadIdx.x; e < nb * NC; e += FR_THREADS) {
     const int b = b0 + e / NC, c = e % NC;
-    float g = 0.f;
-    if (c < 6) {
-      if (P.d_tcp) { const float t = P.tcp[b * 6 + c]; g = P.d_tcp[b * 6 + c] * t * (1.f - t); }
-    } else {
-      const int k = c - 6;
-      if (P.d_scores) {
-        const float s = P.scores[b * P.ncls + k];
-        g = P.d_scores[b * P.ncls + k] * s * (1.f - s) * drop_mul(P.p_cls, P.seed, P.site_cls, (uint64_t)(b * P.ncls + k));
-      }
-    }
-    P.d_logits[b * NC + c] = g;
+    P.d_logits[b * NC + c] = head_bwd_one(b, c, P.ncls, P.tcp, P.scores, P.d_tcp, P.d_scores, P.p_cls, P.seed, P.site_cls);
   }
   stage_sync();
   // d_hfused (nb, 6 hs) = d_logits (nb, NC) W_head (NC, 6 hs): a dozen terms per element
@@ -418,9 +408,8 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_a_kernel(FusedFwdA P) {
         const int64_t o = ((int64_t)(r / nb) * B + b0 + (r % nb)) * hs + col;
         const float rv = acc[i] + P.rec_b[(r / nb) * hs + col];
         P.recon[o] = rv;
-        if (P.d_recon) {                                                // (the expression of misc_losses_kernel, losses.hip)
-          const float d = rv - P.orig[o];
-          const float gr = 2.f * d * P.recon_inv_n * P.recon_scale;
+        if (P.d_recon) {
+          const float gr = recon_seed(rv - P.orig[o], P.recon_inv_n, P.recon_scale);
           P.d_recon[o] = gr;
           P.d_orig[o] = 0.f - gr;
         }
@@ -470,7 +459,7 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_a_kernel(FusedFwdA P) {
   for (int i = wave; i < ntok; i += FR_THREADS / 64) ln_fwd_row<2>(P.ln1, (i / nb) * B + b0 + (i % nb), lane);
 }
 
-// CLS_OPTS: the seed of the class-weighted / focal criterion (P.cls; cls_term.h).  An instance of its own, so that the plain criterion's
+// CLS_OPTS: the seed of the class-weighted / focal criterion (P.cls; loss_terms.h).  An instance of its own, so that the plain criterion's
 // kernel -- the default step's -- is the code it was, registers and all.
 template <bool CLS_OPTS>
 __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
@@ -506,24 +495,15 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
     if (lane == 0) {
       const float z = acc + P.head_b[c];
       P.logits[b * NC + c] = z;
-      if (c < 6) {
-        P.tcp[b * 6 + c] = sigmoidf_(z);
-      } else {
-        const int k = c - 6;
-        const float sc = sigmoidf_(z * drop_mul(P.p_cls, P.seed, P.site_cls, (uint64_t)(b * P.ncls + k)));
-        P.scores[b * P.ncls + k] = sc;
-        P.labels[b * P.ncls + k] = sc > P.threshold ? 1.f : 0.f;
-        if (P.d_scores) {                                               // (the expression of misc_losses_kernel, losses.hip)
+      head_fwd_one(z, b, c, P, [&](int k, float sc) {
+        if (P.d_scores) {                                               // the classification loss's seed of class k
           const float yv = P.emo[b * P.ncls + k];
-          if constexpr (CLS_OPTS) {
-            float v, d;
-            cls_term(P.cls, sc, yv, k, v, d);
-            P.d_scores[b * P.ncls + k] = d / B;
-          } else {
-          P.d_scores[b * P.ncls + k] = (sc - yv) / fmaxf(sc * (1.f - sc), 1e-12f) / B;
-          }
+          float v, d;
+          if constexpr (CLS_OPTS) cls_term(P.cls, sc, yv, k, v, d);
+          else bce_plain(sc, yv, 1.f, v, d);
+          P.d_scores[b * P.ncls + k] = d / B;
         }
-      }
+      });
     }
   }
 }

@@ -4,100 +4,90 @@
 // These are batch-statistic reductions over (B, 128)-sized tensors: latency work on a handful of workgroups.
 #include "common.h"
 #include "internal.h"
-#include "cls_term.h"
+#include "loss_terms.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ heads
+// (the element: head_fwd_one / head_bwd_one, loss_terms.h -- the fused stretches call the same)
 __global__ void heads_fwd_kernel(const float* __restrict__ logits, int B, int ncls, float thr, float* tcp, float* scores,
                                  float* labels, float p, uint64_t seed, int site) {
   const int NC = 6 + ncls;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x) {
-    int b = e / NC, c = e % NC;
-    float z = logits[e];
-    if (c < 6) {
-      tcp[b * 6 + c] = sigmoidf_(z);
-    } else {
-      int k = c - 6;
-      float s = sigmoidf_(z * drop_mul(p, seed, site, (uint64_t)(b * ncls + k)));
-      scores[b * ncls + k] = s;
-      labels[b * ncls + k] = s > thr ? 1.f : 0.f;
-    }
-  }
+  const HeadFwdArgs h = {ncls, thr, tcp, scores, labels, p, seed, site};
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x)
+    head_fwd_one(logits[e], e / NC, e % NC, h, [](int, float) {});
 }
 
 __global__ void heads_bwd_kernel(const float* __restrict__ tcp, const float* __restrict__ scores, const float* dtcp,
                                  const float* dscores, int B, int ncls, float* dlogits, float p, uint64_t seed, int site) {
   const int NC = 6 + ncls;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x) {
-    int b = e / NC, c = e % NC;
-    float g = 0.f;
-    if (c < 6) {
-      if (dtcp) { float t = tcp[b * 6 + c]; g = dtcp[b * 6 + c] * t * (1.f - t); }
-    } else {
-      int k = c - 6;
-      if (dscores) {
-        float s = scores[b * ncls + k];
-        g = dscores[b * ncls + k] * s * (1.f - s) * drop_mul(p, seed, site, (uint64_t)(b * ncls + k));
-      }
-    }
-    dlogits[e] = g;
-  }
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x)
+    dlogits[e] = head_bwd_one(e / NC, e % NC, ncls, tcp, scores, dtcp, dscores, p, seed, site);
 }
 
 // A loss that several workgroups contribute to: every workgroup leaves its partial in parts[block] and ONE thread adds them in block
 // order (float atomics added them in arrival order: the reported value changed in its last bits from run to run).
-__global__ void loss_parts_finish_kernel(const float* __restrict__ parts, int n, float* loss) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void loss_parts_add(const float* __restrict__ parts, int n, float* loss) {
   float t = 0.f;
   for (int i = 0; i < n; ++i) t += parts[i];
   *loss += t;
 }
-__device__ __forceinline__ void loss_parts_add(const float* __restrict__ parts, int n, float* loss) {   // same, from inside a later kernel
-  float t = 0.f;
-  for (int i = 0; i < n; ++i) t += parts[i];
-  *loss += t;
+__global__ void loss_parts_finish_kernel(const float* __restrict__ parts, int n, float* loss) {          // as a launch of its own
+  if (threadIdx.x == 0 && blockIdx.x == 0) loss_parts_add(parts, n, loss);
 }
+
+// How a small loss adds a gradient term where another term may add too: the stand-alone kernels are alone on their buffers and add
+// plainly; the one-launch form (misc_losses_kernel) has cls and conf in different workgroups on d_scores and adds atomically.
+struct AddPlain { __device__ __forceinline__ void operator()(float* p, float v) const { *p += v; } };
+struct AddAtomic { __device__ __forceinline__ void operator()(float* p, float v) const { atomicAdd(p, v); } };
 
 // ------------------------------------------------------------------------------------------------ cls (BCE)
 // loss = sum_c (1/B) sum_b -(y log s + (1-y) log(1-s)), logs clamped at -100 (torch BCELoss);
 // grad  = (s - y) / max(s (1-s), 1e-12) / B   (torch binary_cross_entropy_backward)
-// With class weights or a focal exponent (ct; cls_term.h) the element is cls_term's; the plain criterion keeps the expression above.
+// With class weights or a focal exponent (ct) the element is cls_term's, else bce_plain's (loss_terms.h).
+// One workgroup: returns its loss value; ds (optional) += scale * gradient.
+template <typename Add>
+__device__ __forceinline__ float cls_block(const float* __restrict__ s, const float* __restrict__ y, int B, int ncls, float scale, float* ds,
+                                           const ClsTerm& ct, float* red) {
+  const Add add;
+  float acc = 0.f;
+  if (cls_plain(ct)) {                                     // launch-uniform
+    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
+      float v, d;
+      bce_plain(s[e], y[e], scale, v, d);
+      acc += v;
+      if (ds) add(&ds[e], d / B);
+    }
+  } else {
+    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
+      float v, d;
+      cls_term(ct, s[e], y[e], e % ncls, v, d);
+      acc += v;
+      if (ds) add(&ds[e], scale * d / B);
+    }
+  }
+  return block_sum(acc, red) / B;
+}
+
 __global__ __launch_bounds__(256) void cls_kernel(const float* __restrict__ s, const float* __restrict__ y, int B, int ncls,
                                                   float scale, float* loss, float* ds, ClsTerm ct) {
   __shared__ float red[16];
-  float acc = 0.f;
-  if (cls_plain(ct)) {                                     // launch-uniform
-  for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
-    float sv = s[e], yv = y[e];
-    float lp = fmaxf(logf(sv), -100.f), lq = fmaxf(log1pf(-sv), -100.f);
-    acc += -(yv * lp + (1.f - yv) * lq);
-    if (ds) ds[e] += scale * (sv - yv) / fmaxf(sv * (1.f - sv), 1e-12f) / B;
-  }
-  } else {
-  for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
-    float v, d;
-    cls_term(ct, s[e], y[e], e % ncls, v, d);
-    acc += v;
-    if (ds) ds[e] += scale * d / B;
-  }
-  }
-  float t = block_sum(acc, red);
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, t / B);
+  const float t = cls_block<AddPlain>(s, y, B, ncls, scale, ds, ct, red);
+  if (threadIdx.x == 0 && loss) atomicAdd(loss, t);
 }
 
 // ------------------------------------------------------------------------------------------------ conf (ConfidNet)
 // One workgroup per class c (solver.py:458-460):
 //   tcp  : mean_b (tcp - y*s)^2 / nnz
 //   mcp  : CrossEntropyLoss on a 1-D input with float target = -sum_b y_b * log_softmax_over_batch(s)_b / nnz
-__global__ __launch_bounds__(256) void conf_kernel(const float* __restrict__ s, const float* __restrict__ tcp,
-                                                   const float* __restrict__ y, int B, int ncls, float scale, float* loss,
-                                                   float* ds, float* dtcp) {
-  __shared__ float red[16];
-  __shared__ float smax[4];
-  const int c = blockIdx.x;
+// Returns class c's loss value; ds / dtcp (each optional) += scale * gradient.
+template <typename Add>
+__device__ __forceinline__ float conf_block(const float* __restrict__ s, const float* __restrict__ tcp, const float* __restrict__ y, int c,
+                                            int B, int ncls, float scale, float* ds, float* dtcp, float* red, float* smax) {
+  const Add add;
+  const int nthr = blockDim.x;
   float nz = 0.f, sy = 0.f, mx = -INFINITY;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+  for (int b = threadIdx.x; b < B; b += nthr) {
     float yv = y[b * ncls + c];
     nz += (yv != 0.f) ? 1.f : 0.f;
     sy += yv;
@@ -111,23 +101,55 @@ __global__ __launch_bounds__(256) void conf_kernel(const float* __restrict__ s, 
   __syncthreads();
   mx = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
   float se = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) se += expf(s[b * ncls + c] - mx);
+  for (int b = threadIdx.x; b < B; b += nthr) se += expf(s[b * ncls + c] - mx);
   se = block_sum(se, red);
   const float lse = mx + logf(se);
   float lt = 0.f, lm = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+  for (int b = threadIdx.x; b < B; b += nthr) {
     int e = b * ncls + c;
     float sv = s[e], yv = y[e], tv = tcp[e];
     float diff = tv - yv * sv;
     lt += diff * diff;
     lm += -yv * (sv - lse);
     float gt = 2.f * diff / (B * nz);
-    if (dtcp) dtcp[e] += scale * gt;
-    if (ds) ds[e] += scale * (-yv * gt + (-yv + sy * expf(sv - lse)) / nz);
+    if (dtcp) add(&dtcp[e], scale * gt);
+    if (ds) add(&ds[e], scale * (-yv * gt + (-yv + sy * expf(sv - lse)) / nz));
   }
   lt = block_sum(lt, red);
   lm = block_sum(lm, red);
-  if (threadIdx.x == 0 && loss) loss[blockIdx.x] = lt / (B * nz) + lm / nz;      // `loss` = this launch's partial array (one per class)
+  return lt / (B * nz) + lm / nz;
+}
+
+__global__ __launch_bounds__(256) void conf_kernel(const float* __restrict__ s, const float* __restrict__ tcp,
+                                                   const float* __restrict__ y, int B, int ncls, float scale, float* loss,
+                                                   float* ds, float* dtcp) {
+  __shared__ float red[16];
+  __shared__ float smax[4];
+  const float v = conf_block<AddPlain>(s, tcp, y, blockIdx.x, B, ncls, scale, ds, dtcp, red, smax);
+  if (threadIdx.x == 0 && loss) loss[blockIdx.x] = v;                             // `loss` = this launch's partial array (one per class)
+}
+
+// ------------------------------------------------------------------------------------------------ recon (MSE)
+// Workgroup `block` of `blocks` over n elements: returns its share of mean((rec - orig)^2); drec += seed, dorig -= seed (each optional;
+// one writer per element in every launch form, so plain adds)
+__device__ __forceinline__ float recon_block(const float* __restrict__ rec, const float* __restrict__ orig, int64_t n, int block, int blocks,
+                                             float inv_n, float scale, float* drec, float* dorig, float* red) {
+  float acc = 0.f;
+  for (int64_t e = block * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)blocks * blockDim.x) {
+    float d = rec[e] - orig[e];
+    acc += d * d;
+    float g = recon_seed(d, inv_n, scale);
+    if (drec) drec[e] += g;
+    if (dorig) dorig[e] -= g;
+  }
+  return block_sum(acc, red) * inv_n;
+}
+
+__global__ __launch_bounds__(256) void recon_kernel(const float* __restrict__ rec, const float* __restrict__ orig, int64_t n,
+                                                    float inv_n, float scale, float* loss, float* drec, float* dorig) {
+  __shared__ float red[16];
+  const float t = recon_block(rec, orig, n, blockIdx.x, gridDim.x, inv_n, scale, drec, dorig, red);
+  if (threadIdx.x == 0 && loss) loss[blockIdx.x] = t;                             // `loss` = this launch's partial array (one per block)
 }
 
 // ------------------------------------------------------------------------------------------------ cls + conf + recon + total
@@ -144,7 +166,7 @@ struct MiscLossArgs {
   float* parts;                             // one partial per workgroup (role order); the last workgroup adds them in that order
   float dw, sw, rw, cw; int use_conf, with_conf;
   int recon_blocks;
-  ClsTerm ct;                               // the classification criterion (cls_term.h); plain: role 0's own expression
+  ClsTerm ct;                               // the classification criterion (loss_terms.h)
 };
 
 __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
@@ -152,76 +174,18 @@ __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
   __shared__ float smax[4];
   const int B = a.B, ncls = a.ncls;
   const int role = blockIdx.x;
+  float part;                                              // this workgroup's value, stored below
   if (role == 0) {
-    float acc = 0.f;
-    if (cls_plain(a.ct)) {                                 // launch-uniform
-    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
-      float sv = a.scores[e], yv = a.emo[e];
-      float lp = fmaxf(logf(sv), -100.f), lq = fmaxf(log1pf(-sv), -100.f);
-      acc += -(yv * lp + (1.f - yv) * lq);
-      if (a.d_scores) atomicAdd(&a.d_scores[e], (sv - yv) / fmaxf(sv * (1.f - sv), 1e-12f) / B);
-    }
-    } else {
-    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
-      float v, d;
-      cls_term(a.ct, a.scores[e], a.emo[e], e % ncls, v, d);
-      acc += v;
-      if (a.d_scores) atomicAdd(&a.d_scores[e], d / B);
-    }
-    }
-    float t = block_sum(acc, red);
-    if (threadIdx.x == 0) a.parts[role] = t / B;
+    part = cls_block<AddAtomic>(a.scores, a.emo, B, ncls, 1.f, a.d_scores, a.ct, red);
   } else if (role <= (a.with_conf ? ncls : 0)) {
-    const int c = role - 1;
-    const float* s = a.scores; const float* y = a.emo;
-    float nz = 0.f, sy = 0.f, mx = -INFINITY;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-      float yv = y[b * ncls + c];
-      nz += (yv != 0.f) ? 1.f : 0.f;
-      sy += yv;
-      mx = fmaxf(mx, s[b * ncls + c]);
-    }
-    nz = block_sum(nz, red);
-    sy = block_sum(sy, red);
-    mx = wave_max(mx);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-    float se = 0.f;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) se += expf(s[b * ncls + c] - mx);
-    se = block_sum(se, red);
-    const float lse = mx + logf(se);
-    float lt = 0.f, lm = 0.f;
     const bool cg = a.conf_grads && a.d_scores;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-      int e = b * ncls + c;
-      float sv = s[e], yv = y[e], tv = a.tcp[e];
-      float diff = tv - yv * sv;
-      lt += diff * diff;
-      lm += -yv * (sv - lse);
-      float gt = 2.f * diff / (B * nz);
-      if (cg) {
-        atomicAdd(&a.d_tcp[e], a.conf_scale * gt);
-        atomicAdd(&a.d_scores[e], a.conf_scale * (-yv * gt + (-yv + sy * expf(sv - lse)) / nz));
-      }
-    }
-    lt = block_sum(lt, red);
-    lm = block_sum(lm, red);
-    if (threadIdx.x == 0) a.parts[role] = lt / (B * nz) + lm / nz;
+    part = conf_block<AddAtomic>(a.scores, a.tcp, a.emo, role - 1, B, ncls, a.conf_scale, cg ? a.d_scores : nullptr, cg ? a.d_tcp : nullptr, red,
+                                 smax);
   } else {
-    const int rb = role - 1 - (a.with_conf ? ncls : 0);
-    float acc = 0.f;
-    for (int64_t e = rb * (int64_t)blockDim.x + threadIdx.x; e < a.n_recon; e += (int64_t)a.recon_blocks * blockDim.x) {
-      float d = a.recon[e] - a.orig[e];
-      acc += d * d;
-      float g = 2.f * d * a.recon_inv_n * a.recon_scale;
-      if (a.d_recon) a.d_recon[e] += g;
-      if (a.d_orig) a.d_orig[e] -= g;
-    }
-    float t = block_sum(acc, red);
-    if (threadIdx.x == 0) a.parts[role] = t * a.recon_inv_n;
+    part = recon_block(a.recon, a.orig, a.n_recon, role - 1 - (a.with_conf ? ncls : 0), a.recon_blocks, a.recon_inv_n, a.recon_scale,
+                       a.d_recon, a.d_orig, red);
   }
+  if (threadIdx.x == 0) a.parts[role] = part;
   // the last block to arrive sees every sum (release by the fence before the ticket, agent-scope reads after it)
   if (threadIdx.x == 0) {
     __threadfence();
@@ -259,6 +223,9 @@ __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
 // (3) loss_pair(i,j) = mean((Ahat_i^T Ahat_j)^2) = sum(K_i o K_j)/D^2 ;  Ksum_i = sum_{j in pairs(i)} K_j * 2*scale/D^2
 // (4) dAhat_i = Ksum_i Ahat_i (batched GEMM)
 // (5) dx_i += dAhat_i*invn - colmean(dAhat_i*invn)   (norm detached, centring backward)
+// torch.nan_to_num at its defaults: NaN -> 0, +-inf -> the largest finite float
+__device__ __forceinline__ float nan_to_num(float v) { return (v != v) ? 0.f : fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f); }
+
 __global__ __launch_bounds__(256) void diff_prep_kernel(const float* __restrict__ x, int64_t stride, int B, int D, float* Ahat,
                                                         float* invn, float* mean) {
   const int k = blockIdx.x;
@@ -268,7 +235,7 @@ __global__ __launch_bounds__(256) void diff_prep_kernel(const float* __restrict_
     float s = 0.f;
     for (int r = 0; r < B; ++r) {
       float v = X[(int64_t)r * D + i];
-      v = (v != v) ? 0.f : fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f);   // nan_to_num
+      v = nan_to_num(v);
       s += v;
     }
     M[i] = s / B;
@@ -279,7 +246,7 @@ __global__ __launch_bounds__(256) void diff_prep_kernel(const float* __restrict_
     float ss = 0.f;
     for (int i = lane; i < D; i += 64) {
       float v = X[(int64_t)r * D + i];
-      v = (v != v) ? 0.f : fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f);
+      v = nan_to_num(v);
       float c = v - M[i];
       ss += c * c;
     }
@@ -288,7 +255,7 @@ __global__ __launch_bounds__(256) void diff_prep_kernel(const float* __restrict_
     if (lane == 0) invn[k * B + r] = inv;
     for (int i = lane; i < D; i += 64) {
       float v = X[(int64_t)r * D + i];
-      v = (v != v) ? 0.f : fminf(fmaxf(v, -3.402823466e38f), 3.402823466e38f);
+      v = nan_to_num(v);
       Ahat[((int64_t)k * B + r) * D + i] = (v - M[i]) * inv;
     }
   }
@@ -311,7 +278,7 @@ __global__ __launch_bounds__(1024) void diff_prep_fast_kernel(const float* __res
   for (int j = 0; j < RPT; ++j) {
     const int r = rg + 8 * j;
     float val = X[(int64_t)min(r, B - 1) * D + cc];
-    val = (val != val) ? 0.f : fminf(fmaxf(val, -3.402823466e38f), 3.402823466e38f);   // nan_to_num
+    val = nan_to_num(val);
     v[j] = (c_ok && r < B) ? val : 0.f;
   }
   float s = 0.f;
@@ -883,22 +850,6 @@ __global__ __launch_bounds__(1024) void cmd_stream_kernel(const float* __restric
         dx[(int64_t)t * stride + (int64_t)(r0 + 8 * j) * D + c] = old[t][j] + gs * g;
       }
   }
-}
-
-// ------------------------------------------------------------------------------------------------ recon (MSE)
-__global__ __launch_bounds__(256) void recon_kernel(const float* __restrict__ rec, const float* __restrict__ orig, int64_t n,
-                                                    float inv_n, float scale, float* loss, float* drec, float* dorig) {
-  __shared__ float red[16];
-  float acc = 0.f;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    float d = rec[e] - orig[e];
-    acc += d * d;
-    float g = 2.f * d * inv_n * scale;
-    if (drec) drec[e] += g;
-    if (dorig) dorig[e] -= g;
-  }
-  float t = block_sum(acc, red);
-  if (threadIdx.x == 0 && loss) loss[blockIdx.x] = t * inv_n;                   // `loss` = this launch's partial array (one per block)
 }
 
 // ------------------------------------------------------------------------------------------------ domain (CE)

@@ -1,6 +1,7 @@
 // Row-local pieces of the fusion block's backward pass as device functions: one LayerNorm-backward row (wave per row) and the
 // attention backward of one (sample, head) at head width 64 and six tokens (wave per pair).  Shared by the stand-alone kernels
 // (norm.hip, attn.hip) and the fused per-sample kernels (fused_rows.hip) -- one body, the same arithmetic order and dropout indices.
+// (loss_terms.h is the sibling for the heads and the small losses.)
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-"""The class-weighted / focal classification criterion (mmda_amd/csrc/cls_term.h): its restatement in torch, the case
+"""The class-weighted / focal classification criterion (mmda_amd/csrc/loss_terms.h): its restatement in torch, the case
 table of the device tests and their metrics.  Importable without a GPU.
 
 Restatement, in whatever dtype the scores have (float64: the reference; float32: the yardstick of the bounds):

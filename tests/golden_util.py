@@ -19,9 +19,9 @@ LARGE = ("real_b32_t500_ragged", "real_b256_t6_full")     # BASELINE configs[3] 
 
 def case_names(large=False):
     # the model fixtures of gen_golden.py (eval_metrics.npz belongs to gen_golden_eval.py, optim_bits.npz to gen_optim_bits.py,
-    # embed_rows_bits.npz to gen_embed_rows_bits.py: tests of their own); the large cases (no stored inputs, a CPU oracle backward of a minute at T = 500) only on request
+    # embed_rows_bits.npz to gen_embed_rows_bits.py, losses_bits.npz to gen_losses_bits.py: tests of their own); the large cases (no stored inputs, a CPU oracle backward of a minute at T = 500) only on request
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
-                   if os.path.basename(p) not in ("eval_metrics.npz", "optim_bits.npz", "embed_rows_bits.npz"))
+                   if os.path.basename(p) not in ("eval_metrics.npz", "optim_bits.npz", "embed_rows_bits.npz", "losses_bits.npz"))
     return [n for n in names if large or n not in LARGE]
 
 

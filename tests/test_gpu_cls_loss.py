@@ -1,4 +1,4 @@
-"""MI355X: the class-weighted / focal classification criterion (mmda_amd/csrc/cls_term.h) at its three device sites --
+"""MI355X: the class-weighted / focal classification criterion (mmda_amd/csrc/loss_terms.h) at its three device sites --
 mmda_loss_cls_opts, role 0 of mmda_loss_misc_opts and the seed the forward stretch stores -- against the float64 restatement of
 tests/cls_loss_cases.py, bit identity with the plain criterion and between step forms, mmda_label_counts, and Solver with
 pos_weight="balanced".
