@@ -346,17 +346,16 @@ int mmda_lstm_bwd_emits_dg_bf16(int mode, int n, const mmda_lstm_desc* descs, in
  * Returns MMDA_OK with plan->ok = 0 where the streaming kernels would run instead (every other field then 0, kernel -1). */
 enum { MMDA_LSTM_FORM_BARRIER = 0, MMDA_LSTM_FORM_WAVE = 1, MMDA_LSTM_FORM_QUAD = 2 };
 enum { MMDA_LSTM_DHSEQ_RUNTIME = 0, MMDA_LSTM_DHSEQ_ABSENT = 1, MMDA_LSTM_DHSEQ_PRESENT = 2 };
-/* the kernel instances of lstm_cluster.hip, in the order its selection names them (mmda_lstm_kernel_name gives the C++ name) */
+/* the kernel instances of lstm_barrier.hip, lstm_wave.hip and lstm_quad.hip, ordered by form, then pass, then specialisation
+ * (mmda_lstm_kernel_name gives the C++ name) */
 enum {
-  MMDA_LSTM_K_BWD_QUAD_GRU = 0, MMDA_LSTM_K_BWD_QUAD_PRESENT, MMDA_LSTM_K_BWD_QUAD_ABSENT, MMDA_LSTM_K_BWD_QUAD,
-  MMDA_LSTM_K_FWD_QUAD_GRU_NOSTASH, MMDA_LSTM_K_FWD_QUAD_GRU, MMDA_LSTM_K_FWD_QUAD_NOSTASH, MMDA_LSTM_K_FWD_QUAD,
-  MMDA_LSTM_K_STAMPED,               /* mmda_debug_set_lstm_stamps: one entry for the forward and the backward debug kernel */
-  MMDA_LSTM_K_BWD_WAVE_GRU_GM, MMDA_LSTM_K_BWD_WAVE_GRU, MMDA_LSTM_K_FWD_WAVE_GRU_GM, MMDA_LSTM_K_FWD_WAVE_GRU,
+  MMDA_LSTM_K_FWD_BARRIER_GM = 0, MMDA_LSTM_K_FWD_BARRIER, MMDA_LSTM_K_BWD_BARRIER_GM, MMDA_LSTM_K_BWD_BARRIER,
+  MMDA_LSTM_K_FWD_WAVE_GM_NOSTASH, MMDA_LSTM_K_FWD_WAVE_GM, MMDA_LSTM_K_FWD_WAVE, MMDA_LSTM_K_FWD_WAVE_GRU_GM, MMDA_LSTM_K_FWD_WAVE_GRU,
   MMDA_LSTM_K_BWD_WAVE_ABSENT_PAIR, MMDA_LSTM_K_BWD_WAVE_ABSENT, MMDA_LSTM_K_BWD_WAVE_PRESENT_PAIR, MMDA_LSTM_K_BWD_WAVE_PRESENT,
-  MMDA_LSTM_K_BWD_WAVE_GM, MMDA_LSTM_K_BWD_WAVE,
-  MMDA_LSTM_K_BWD_BARRIER_REGS_GM, MMDA_LSTM_K_BWD_BARRIER_REGS, MMDA_LSTM_K_BWD_BARRIER_GM, MMDA_LSTM_K_BWD_BARRIER,
-  MMDA_LSTM_K_FWD_WAVE_GM_NOSTASH, MMDA_LSTM_K_FWD_WAVE_GM, MMDA_LSTM_K_FWD_WAVE,
-  MMDA_LSTM_K_FWD_BARRIER_GM, MMDA_LSTM_K_FWD_BARRIER,
+  MMDA_LSTM_K_BWD_WAVE_GM, MMDA_LSTM_K_BWD_WAVE, MMDA_LSTM_K_BWD_WAVE_GRU_GM, MMDA_LSTM_K_BWD_WAVE_GRU,
+  MMDA_LSTM_K_STAMPED,               /* mmda_debug_set_lstm_stamps: one entry for the forward and the backward debug kernel (wave form) */
+  MMDA_LSTM_K_FWD_QUAD_NOSTASH, MMDA_LSTM_K_FWD_QUAD, MMDA_LSTM_K_FWD_QUAD_GRU_NOSTASH, MMDA_LSTM_K_FWD_QUAD_GRU,
+  MMDA_LSTM_K_BWD_QUAD_PRESENT, MMDA_LSTM_K_BWD_QUAD_ABSENT, MMDA_LSTM_K_BWD_QUAD, MMDA_LSTM_K_BWD_QUAD_GRU,
   MMDA_LSTM_K_COUNT
 };
 typedef struct mmda_lstm_plan {
@@ -367,7 +366,6 @@ typedef struct mmda_lstm_plan {
   int wg_per_desc[4];                /* ... and of each descriptor */
   int gru, gate_minor, no_stash;
   int dhseq;                         /* MMDA_LSTM_DHSEQ_*: what the backward instance knows about d_hseq at compile time */
-  int bwd_regs;                      /* every descriptor has <= 20 hidden tiles (barrier form: the register-resident backward) */
   int pair;                          /* 1: the instance that runs pre-reduces the partial dh tiles of a producer pair (PAIR = 1) */
   int kernel;                        /* MMDA_LSTM_K_* */
 } mmda_lstm_plan;

@@ -99,7 +99,7 @@ class LstmPlan(C.Structure):
     """mmda_lstm_plan: what the resident launch plan of an mmda_lstm_fwd / mmda_lstm_bwd call decides"""
     _fields_ = [("ok", C.c_int), ("form", C.c_int), ("wpb", C.c_int), ("groups", C.c_int), ("groups_per_launch", C.c_int),
                 ("launches", C.c_int), ("wg_per_group", C.c_int), ("wg_per_desc", C.c_int * 4), ("gru", C.c_int),
-                ("gate_minor", C.c_int), ("no_stash", C.c_int), ("dhseq", C.c_int), ("bwd_regs", C.c_int), ("pair", C.c_int),
+                ("gate_minor", C.c_int), ("no_stash", C.c_int), ("dhseq", C.c_int), ("pair", C.c_int),
                 ("kernel", C.c_int)]
 
 

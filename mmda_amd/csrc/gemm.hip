@@ -396,7 +396,7 @@ __global__ void colsum_finish_kernel(const float* __restrict__ part, int nparts,
 
 // ------------------------------------------------------------------------------------------------ host
 // Each entry point validates, plans (a pure function: no HIP call), makes one scratch request and launches; a small named function
-// returns the kernel instance.  The same pattern as gemm_bf16.hip, lstm_cluster.hip and misa.hip.
+// returns the kernel instance.  The same pattern as gemm_bf16.hip, lstm_resident.hip and misa.hip.
 namespace {
 
 bool valid_operands(const mmda_gemm_args& a) {

@@ -104,6 +104,6 @@ int mmda_lstm_pack_convert_transpose_stamped(int n, const int* H, const float* c
                                              int ntjobs, const RowStamp* st, void* stream);
 int mmda_embed_gather_stamped(const float* W, const int64_t* ids, int rows, int dim, float* out, const RowStamp* st, void* stream);
 
-// ---- lstm_cluster.hip: the resident recurrences of lstm.hip's entry points
+// ---- lstm_resident.hip: the resident recurrences of lstm.hip's entry points
 int mmda_lstm_cluster_launch(int n, const mmda_lstm_desc* descs, int B, int T, const int32_t* lengths, void* stream, bool bwd,
                              int* used);

@@ -445,7 +445,7 @@ struct mmda_misa {
   int df_seq = 0, df_flushed = 0;
   // state of the last forward (dropout replay in backward)
   int training = 0; uint64_t seed = 0;
-  unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_cluster.hip)
+  unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_resident.h)
   int side_pending = 0;
   int zero_grad_pending = 0;       // train_step: the gradient bucket is cleared inside forward(), beside the fusion block
   // train_step: the losses that read only the private/shared representations (diff, CMD) are issued by forward() on the side

@@ -432,7 +432,7 @@ def lstm_plan(descs, B, T, backward=False, no_quad=False, quad_cap=0):
     last five as booleans: only whether a pointer is NULL matters; xchg and wpack_c default to present).  no_quad stands for
     MMDA_LSTM_NO_QUAD; quad_cap > 0 replaces the occupancy query behind the quad form's limit, 0 asks the runtime as a launch does.
     Returns a dict: ok, form (a name of LSTM_FORMS), wpb, groups, groups_per_launch, launches, wg_per_group, wg_per_desc, gru,
-    gate_minor, no_stash, dhseq (a name of LSTM_DHSEQ), bwd_regs, pair, kernel (the instance's C++ name); ok = False: the streaming
+    gate_minor, no_stash, dhseq (a name of LSTM_DHSEQ), pair, kernel (the instance's C++ name); ok = False: the streaming
     kernels run and the other entries are None."""
     if not isinstance(descs, C.Array):
         arr = (_lib.LstmDesc * max(1, len(descs)))()
@@ -449,13 +449,13 @@ def lstm_plan(descs, B, T, backward=False, no_quad=False, quad_cap=0):
     sw = (C.c_int * 2)(int(no_quad), int(quad_cap))
     check(load().mmda_lstm_plan_describe(n, arr, B, T, int(backward), sw, C.byref(plan)), "mmda_lstm_plan_describe")
     keys = ("form", "wpb", "groups", "groups_per_launch", "launches", "wg_per_group", "wg_per_desc", "gru", "gate_minor", "no_stash",
-            "dhseq", "bwd_regs", "pair", "kernel")
+            "dhseq", "pair", "kernel")
     if not plan.ok:
         return dict({k: None for k in keys}, ok=False)
     return dict(ok=True, form=LSTM_FORMS[plan.form], wpb=plan.wpb, groups=plan.groups, groups_per_launch=plan.groups_per_launch,
                 launches=plan.launches, wg_per_group=plan.wg_per_group, wg_per_desc=list(plan.wg_per_desc)[:n], gru=bool(plan.gru),
                 gate_minor=bool(plan.gate_minor), no_stash=bool(plan.no_stash), dhseq=LSTM_DHSEQ[plan.dhseq],
-                bwd_regs=bool(plan.bwd_regs), pair=bool(plan.pair), kernel=load().mmda_lstm_kernel_name(plan.kernel).decode())
+                pair=bool(plan.pair), kernel=load().mmda_lstm_kernel_name(plan.kernel).decode())
 
 
 LOSS_DIFF_FORMS = ("generic", "fast4", "fast8", "fast16", "fast32")

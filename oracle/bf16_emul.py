@@ -6,7 +6,7 @@ cores bf16 operands; this file restates the SAME recurrences as explicit loops (
 to bf16 (round-to-nearest-even, ``Tensor.bfloat16()``) at exactly the points the HIP kernels round at, and nowhere else:
 
   forward   pre   = bf16(x) . bf16(W_ih)^T + b_ih + b_hh                (time-batched input GEMM, gemm_bf16.hip)
-            gates = pre[t] + bf16(h_{t-1}) . bf16(W_hh)^T               (lstm_cluster.hip / lstm.hip; h, c themselves stay fp32)
+            gates = pre[t] + bf16(h_{t-1}) . bf16(W_hh)^T               (lstm_resident.h / lstm.hip; h, c themselves stay fp32)
   backward  dG_t in fp32 from the fp32 stash, then                      (lstm_bwd_wave_kernel)
             dh_{t-1} = sum over 16-unit hidden tiles of bf16( bf16(dG_t)[tile's gate rows] . bf16(W_hh)[those rows] )
                        (``tile_partials=32``: over 32-unit tile PAIRS -- the large-batch form of the kernel adds two tiles'
@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from . import misa_oracle as orc
 
-TILE = 16          # hidden units per producer wave of the backward exchange (lstm_cluster.hip: one wave = one 16-unit tile)
+TILE = 16          # hidden units per producer wave of the backward exchange (lstm_wave.hip, lstm_quad.hip: one wave = one 16-unit tile)
 
 
 def _q(x: torch.Tensor, on: bool) -> torch.Tensor:

@@ -1,4 +1,4 @@
-"""The launch forms of the resident-weights recurrences (mmda_amd/csrc/lstm_cluster.hip), defined once for the CPU test that proves
+"""The launch forms of the resident-weights recurrences (mmda_amd/csrc/lstm_resident.hip and its three kernel files), defined once for the CPU test that proves
 from the launch plan what each case reaches (test_lstm_plan_cpu.py) and the GPU test that checks its numbers
 (test_gpu_lstm_forms.py).
 
@@ -37,9 +37,9 @@ KERNELS = {
                                  bwd="lstm_bwd_quad_kernel<LSTM,2,2>", bwd16="lstm_bwd_quad_kernel<LSTM,1,1>",
                                  bwd16_nodh="lstm_bwd_quad_kernel<LSTM,0,1>"),
     ("barrier", "lstm", False): dict(fwd="lstm_fwd_cluster_kernel<10,false>", fwd_only="lstm_fwd_cluster_kernel<10,false>",
-                                     bwd="lstm_bwd_cluster_kernel<0,false>"),
+                                     bwd="lstm_bwd_cluster_kernel<false>"),
     ("barrier", "lstm", True): dict(fwd="lstm_fwd_cluster_kernel<10,true>", fwd_only="lstm_fwd_cluster_kernel<10,true>",
-                                    bwd="lstm_bwd_cluster_kernel<0,true>"),
+                                    bwd="lstm_bwd_cluster_kernel<true>"),
     ("wave", "gru", False): dict(fwd="lstm_fwd_wave_kernel<10,false,GRU,false>", fwd_only="lstm_fwd_wave_kernel<10,false,GRU,false>",
                                  bwd="lstm_bwd_wave_kernel<20,false,GRU,false>"),
     ("wave", "gru", True): dict(fwd="lstm_fwd_wave_kernel<10,true,GRU,false>", fwd_only="lstm_fwd_wave_kernel<10,true,GRU,false>",

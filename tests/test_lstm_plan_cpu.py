@@ -16,9 +16,6 @@ CAPS = (240, 512)                                    # min(512, 240 * blocks per
 # instances no case runs, and why
 EXCLUDED = {
     "stamped debug instance": "runs only after mmda_debug_set_lstm_stamps() handed the library a stamp buffer (tools/ diagnostics)",
-    "lstm_bwd_cluster_kernel<10,true>": "unreachable: the barrier form needs a descriptor with more than 10 k-steps, i.e. H > 320 and "
-                                        "21 or more hidden tiles, while bwd_regs needs every descriptor to have at most 20",
-    "lstm_bwd_cluster_kernel<10,false>": "unreachable: as lstm_bwd_cluster_kernel<10,true>",
 }
 
 
@@ -107,7 +104,7 @@ def swept():
 
 def test_cases_reach_every_instance_the_plan_can_return(swept):
     names = ops.lstm_kernel_names()
-    assert len(names) == len(set(names)) == 28
+    assert len(names) == len(set(names)) == 26
     reached = {k for c in lc.CASES for k in c["expect"]["kernels"].values()}
     assert reached <= set(names) and set(EXCLUDED) <= set(names)
     assert not reached & set(EXCLUDED)

@@ -12,7 +12,7 @@ pre = torch.randn(T, B, 2, 4 * H, device=d)
 wf = (torch.rand(4 * H, H, device=d) - 0.5) * 0.1; wr = (torch.rand(4 * H, H, device=d) - 0.5) * 0.1
 lengths = torch.full((B,), T)
 dbg = torch.zeros(128 * 8, dtype=torch.int64, device=d)
-# H = 300 takes the wave-autonomous form; with stamps on, the library runs its stamped gate-minor instance (lstm_fwd_wave_kernel, DBG)
+# H = 300 takes the wave-autonomous form; with stamps on, the library runs its stamped gate-minor instance (lstm_wave.hip: lstm_fwd_wave_kernel, DBG)
 wave_names = ["poll", "issue fragment loads + flush previous stash", "fragment wait + MFMA", "cell update + LDS tile", "publish + drain", "-", "-", "-"]
 for it in range(3):
     lib.mmda_debug_set_lstm_stamps(dbg.data_ptr())
