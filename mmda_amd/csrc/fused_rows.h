@@ -105,3 +105,13 @@ int mmda_fused_bwd_a(const FusedBwdA* a, void* stream);
 constexpr int FUSED_PG_SLOTS = 5;
 int mmda_fused_pg_finish(const float* pg_parts, int B, int hs, float* const* dgamma, float* const* dbeta, void* stream);
 extern "C" int mmda_debug_set_fused_stamps(void* device_buffer);     // tools/ only (16 x u64)
+// tests/ and tools/ only: each launch alone (nothing but a call of the launcher above; tests/fused_rows_cases.py mirrors the structs),
+// and sizeof of struct `which`: 0 FusedFwdA, 1 FusedFwdC, 2 FusedBwdC, 3 FusedBwdA, 4 FusedFfnFwd, 5 FusedFfnBwd, 6 ClsTerm; else -1
+extern "C" int mmda_debug_fused_fwd_a(const FusedFwdA* a, void* stream);
+extern "C" int mmda_debug_fused_ffn_fwd(const FusedFfnFwd* a, void* stream);
+extern "C" int mmda_debug_fused_fwd_c(const FusedFwdC* a, void* stream);
+extern "C" int mmda_debug_fused_bwd_c(const FusedBwdC* a, void* stream);
+extern "C" int mmda_debug_fused_ffn_bwd(const FusedFfnBwd* a, void* stream);
+extern "C" int mmda_debug_fused_bwd_a(const FusedBwdA* a, void* stream);
+extern "C" int mmda_debug_fused_pg_finish(const float* pg_parts, int B, int hs, float* const* dgamma, float* const* dbeta, void* stream);
+extern "C" int mmda_debug_fused_sizeof(int which);

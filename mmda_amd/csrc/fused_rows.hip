@@ -731,10 +731,35 @@ extern "C" int mmda_debug_set_fused_stamps(void* device_buffer) { g_fr_dbg = (un
 
 int mmda_fused_bwd_a(const FusedBwdA* a, void* stream) {
   if (!a || a->B <= 0 || a->nb <= 0 || a->nb > 2 || a->hs != 128 || a->nhead != 2) return MMDA_EINVAL;
+  // (every row of this stretch is hs wide: the GEMM stages read and write 128 columns of what the LayerNorms leave)
+  if (a->ln1.n != 128 || a->lnp[0].n != 128 || a->lnp[1].n != 128 || a->lnp[2].n != 128) return MMDA_EINVAL;
   if ((a->ln1.dgamma || a->ln1.dbeta || a->lnp[0].dgamma || a->lnp[0].dbeta) && !a->pg_parts) return MMDA_EINVAL;
   FusedBwdA P = *a;
   P.dbg = g_fr_dbg;
   hipLaunchKernelGGL(fused_bwd_a_kernel, dim3(ceil_div(a->B, a->nb)), dim3(FR_THREADS), 0, (hipStream_t)stream, P);
   MMDA_CHECK_LAUNCH("mmda_fused_bwd_a");
   return MMDA_OK;
+}
+
+// tests/ and tools/ only (fused_rows.h): each launch alone, and the struct sizes the ctypes mirrors of tests/fused_rows_cases.py must have
+extern "C" int mmda_debug_fused_fwd_a(const FusedFwdA* a, void* stream) { return mmda_fused_fwd_a(a, stream); }
+extern "C" int mmda_debug_fused_ffn_fwd(const FusedFfnFwd* a, void* stream) { return mmda_fused_ffn_fwd(a, stream); }
+extern "C" int mmda_debug_fused_fwd_c(const FusedFwdC* a, void* stream) { return mmda_fused_fwd_c(a, stream); }
+extern "C" int mmda_debug_fused_bwd_c(const FusedBwdC* a, void* stream) { return mmda_fused_bwd_c(a, stream); }
+extern "C" int mmda_debug_fused_ffn_bwd(const FusedFfnBwd* a, void* stream) { return mmda_fused_ffn_bwd(a, stream); }
+extern "C" int mmda_debug_fused_bwd_a(const FusedBwdA* a, void* stream) { return mmda_fused_bwd_a(a, stream); }
+extern "C" int mmda_debug_fused_pg_finish(const float* pg_parts, int B, int hs, float* const* dgamma, float* const* dbeta, void* stream) {
+  return mmda_fused_pg_finish(pg_parts, B, hs, dgamma, dbeta, stream);
+}
+extern "C" int mmda_debug_fused_sizeof(int which) {
+  switch (which) {
+    case 0: return (int)sizeof(FusedFwdA);
+    case 1: return (int)sizeof(FusedFwdC);
+    case 2: return (int)sizeof(FusedBwdC);
+    case 3: return (int)sizeof(FusedBwdA);
+    case 4: return (int)sizeof(FusedFfnFwd);
+    case 5: return (int)sizeof(FusedFfnBwd);
+    case 6: return (int)sizeof(ClsTerm);
+    default: return -1;
+  }
 }
