@@ -538,6 +538,46 @@ int mmda_calib_select(const unsigned long long* hist, const unsigned long long* 
 int mmda_eval_accumulate_thr(const float* scores, const float* truth, int N, int C, const float* thr_c, float* labels_out,
                              double* state, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- ranking metrics
+ * How well a score table RANKS, before any cut-off is chosen (mmda_amd/ranking.py): per class AUROC, average precision
+ * (of the positives, and of the negatives under the negated score) and FPR at a TPR level; per row the label-ranking figures.  All
+ * counting is in integers, so the same bits come out on every run.
+ *   order: scores compare as fp32 with -0 == +0; a NaN counts as -inf (it ties with other NaNs and with a real -inf).
+ *   pos(i,c) = truth[i,c] > 0.
+ * mmda_rank_counts OVERWRITES counts[N][C][4] = {gp, gn, ep, en}: among the rows j of class c, the positives / negatives with
+ * s_j > s_i (gp, gn) and with s_j == s_i, row i itself included (ep, en).  N^2 C comparisons: 1 <= C <= 16, 0 <= N <= 2^20 and
+ * N^2 C <= 2^42, else MMDA_EINVAL (the launch is quadratic; a mistaken call must not hold the device for minutes).
+ * mmda_rank_finish: out[(C + 1)][6] doubles {n_pos, n_neg, auroc, ap, ap_neg, fpr_at_tpr} per class, from counts and truth:
+ *   ln = n_neg - gn - en, lp = n_pos - gp - ep
+ *   auroc      = (2 sum_{i pos} ln_i + sum_{i pos} en_i) / (2 n_pos n_neg)            NaN when n_pos == 0 or n_neg == 0
+ *   ap         = (1 / n_pos) sum_{i pos} (gp + ep) / (gp + ep + gn + en)              NaN when n_pos == 0
+ *   ap_neg     = (1 / n_neg) sum_{i neg} (ln + en) / (ln + en + lp + ep)              NaN when n_neg == 0
+ *   fpr_at_tpr = min{gn_i + en_i : i pos, gp_i + ep_i >= need} / n_neg, need = max(1, ceil(tpr_level * (double)n_pos))
+ *                                                                                     NaN when n_pos == 0 or n_neg == 0
+ * The AUROC numerator and the FPR minimum are integer reductions followed by one fp64 division; the two AP sums are fp64 in a fixed
+ * order.  Row C: the means over the classes where a figure is defined, added in class order (NaN where none is); its first two
+ * columns hold the number of classes that entered auroc and ap.  0 < tpr_level <= 1, else MMDA_EINVAL.  Two launches, no read-back.
+ * mmda_rank_rows_accumulate ADDS one batch of rows into state[2 + 3 (C + 1)] (uint64, zeroed by the caller before the first batch):
+ *   state[0] rows, state[1] coverage_sum, then rows_by_P[C + 1], lrap_num[C + 1], bad_sum[C + 1], indexed by P = the row's positives:
+ *   with rank_j = #{k : s_k >= s_j} and L_j = #{k positive : s_k >= s_j} over the row's C scores,
+ *   lrap_num += sum_{j positive} L_j (720720 / rank_j), bad_sum += sum_{j positive} (rank_j - L_j), coverage_sum += max_{j positive} rank_j.
+ * Common to the three: scores / truth (N, C) fp32 device pointers; N == 0: MMDA_OK, no launch and nothing written (the
+ * figures of an empty split are the caller's to state); counts 16-byte, out and state 8-byte aligned; a NULL pointer, C outside 1..16, N < 0 or N over the cap above: MMDA_EINVAL before any launch.
+ * mmda_rank_plan_describe (host only, the launcher of mmda_rank_counts reads the same function): the launch a shape gets. */
+typedef struct mmda_rank_plan {
+  int rows_per_wg;                   /* elements i of one class a workgroup owns: one thread each */
+  int tile;                          /* rows j staged in LDS at a time, split into a positives and a negatives list */
+  int tiles;                         /* ceil(N / tile) */
+  int splits;                        /* ranges the j rows are cut into (grid z); > 1: counts is cleared, then 32-bit integer adds */
+  int tiles_per_split;
+  int grid_x, grid_y, grid_z;        /* row blocks, classes, splits */
+  int64_t counts_bytes;              /* N * C * 4 * sizeof(uint32_t) */
+} mmda_rank_plan;
+int mmda_rank_plan_describe(int64_t N, int C, mmda_rank_plan* out);
+int mmda_rank_counts(const float* scores, const float* truth, int64_t N, int C, uint32_t* counts, void* stream);
+int mmda_rank_finish(const uint32_t* counts, const float* truth, int64_t N, int C, double tpr_level, double* out, void* stream);
+int mmda_rank_rows_accumulate(const float* scores, const float* truth, int64_t N, int C, unsigned long long* state, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- optimizer
  * clip_grad_value_(clip) then Adam (solver.py:185-186, :97-99; betas 0.9/0.999, eps 1e-8, no weight decay), fused over
  * a flat bucket.  step = 1-based step count.  grad_scale multiplies g first (1/world for DP averaging). */

@@ -6,7 +6,9 @@ Public surface mirrors the reference's modules: ``models.MISA`` (alias ``Model``
 exported here too), the output side in ``inference`` (``InferencePass``: per-sample scores, confidence and hidden vectors kept on the
 device) and ``utils.tools`` (their files); ``encoded`` holds the encoder cache (``EncoderCache``, ``EncodedLoader``: training the
 fusion block and the heads of a model with frozen encoders from stored encoder outputs); ``calibrate`` sweeps the decision cut-off
-(``ThresholdSweep``, ``Thresholds``: every candidate threshold counted on the device in one launch per batch).
+(``ThresholdSweep``, ``Thresholds``: every candidate threshold counted on the device in one launch per batch); ``ranking`` measures
+how a score table ranks before any cut-off (``ranking_metrics``: exact per-class AUROC / AP and the label-ranking figures;
+``failure_prediction``: the same over ConfidNet's ``tcp``).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -15,3 +17,4 @@ from .data import DeviceDataset, DeviceLoader, batch_plan, class_pos_weight  # n
 from .inference import FIELDS, InferencePass, InferenceResult, inference_plan  # noqa: F401
 from .encoded import EncodedBatch, EncodedLoader, EncoderCache  # noqa: F401
 from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_grid  # noqa: F401
+from .ranking import RankingResult, failure_prediction, rank_plan, ranking_metrics  # noqa: F401

@@ -109,6 +109,12 @@ class LossForms(C.Structure):
                 ("cmd_form", C.c_int), ("cmd_grid", C.c_int), ("recon_blocks", C.c_int), ("misc_recon_blocks", C.c_int)]
 
 
+class RankPlan(C.Structure):
+    """mmda_rank_plan: the launch mmda_rank_counts gives a shape"""
+    _fields_ = [("rows_per_wg", C.c_int), ("tile", C.c_int), ("tiles", C.c_int), ("splits", C.c_int), ("tiles_per_split", C.c_int),
+                ("grid_x", C.c_int), ("grid_y", C.c_int), ("grid_z", C.c_int), ("counts_bytes", C.c_int64)]
+
+
 class GruPadJob(C.Structure):
     _fields_ = [("H", C.c_int), ("D", C.c_int), ("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2),
                 ("b_hh", C.c_void_p * 2), ("pw_ih", C.c_void_p), ("pw_hh", C.c_void_p * 2), ("pb_ih", C.c_void_p), ("pb_hh", C.c_void_p)]
@@ -252,6 +258,10 @@ SIGNATURES = {
     "mmda_calib_accumulate": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P]),
     "mmda_calib_select": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "mmda_eval_accumulate_thr": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "mmda_rank_plan_describe": (_I, [_I64, _I, C.POINTER(RankPlan)]),
+    "mmda_rank_counts": (_I, [_P, _P, _I64, _I, _P, _P]),
+    "mmda_rank_finish": (_I, [_P, _P, _I64, _I, C.c_double, _P, _P]),
+    "mmda_rank_rows_accumulate": (_I, [_P, _P, _I64, _I, _P, _P]),
     "mmda_loss_domain": (_I, [_P, _I, _F, _P, _P, _P]),
     "mmda_loss_forms_describe": (_I, [_I, _I, _I, _I, _I, _I64, C.POINTER(LossForms)]),
     "mmda_clamp_adam": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _I, _P]),

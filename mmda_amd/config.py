@@ -111,6 +111,10 @@ DEFAULTS = dict(
     # positive term (BCEWithLogitsLoss's convention), or "balanced", which Solver.build() resolves to (N - n_c) / n_c from the training
     # set's labels -- and the focal exponent focal_gamma (0, or 1 .. 8).  The defaults are the reference's criterion, bit for bit.
     pos_weight=None, focal_gamma=0.0,
+    # which dev figure Solver.train() keeps the best checkpoint by: "valid_loss" (the reference's loop: the lowest dev loss), or the
+    # highest "map" / "auroc" -- macro average precision / macro AUROC of the dev scores (mmda_amd/ranking.py), figures
+    # that move neither with `threshold` nor with the criterion's weights
+    select_by="valid_loss",
 )
 
 
@@ -129,6 +133,8 @@ def get_config(parse=True, **optional_kwargs):
             parser.add_argument(f"--{k}", type=_pos_weight, default=None)
         elif k == "calibrate":
             parser.add_argument(f"--{k}", choices=("none", "global", "per_class"), default=v)
+        elif k == "select_by":
+            parser.add_argument(f"--{k}", choices=("valid_loss", "map", "auroc"), default=v)
         elif v is None:
             parser.add_argument(f"--{k}", default=None)
         else:

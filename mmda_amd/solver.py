@@ -51,6 +51,9 @@ class Solver(object):
     # ------------------------------------------------------------------ build (solver.py:60-100)
     def build(self, cuda=True):
         cfg = self.train_config
+        from .ranking import check_select_by
+        check_select_by(getattr(cfg, "select_by", "valid_loss"),
+                        process_group=torch.distributed.is_available() and torch.distributed.is_initialized())
         if self.model is None:
             self.model = getattr(models, cfg.model)(cfg)
         for name, param in self.model.named_parameters():
@@ -224,6 +227,10 @@ class Solver(object):
     def train(self):
         cfg = self.train_config
         best_valid_loss = float("inf")
+        # config.select_by != "valid_loss": the best checkpoint is the one with the HIGHEST dev figure of Solver.rank (build() has
+        # refused that under a process group); "valid_loss" takes none of these branches
+        select_by = getattr(cfg, "select_by", "valid_loss")
+        best_figure = float("-inf")
         best_epoch = -1
         history = []
         for e in range(cfg.n_epoch):
@@ -237,9 +244,22 @@ class Solver(object):
             # Data parallel: whether this epoch is the best one is decided ONCE, from rank 0's dev loss (a sharded dev loader, or one
             # ULP of difference between ranks, must not send one rank into the checkpoint barrier and another into the next epoch's
             # all-reduce), and the cluster check in front of the save is collective, so an error is raised on every rank.
-            decided = self.dp.agree(valid_loss) if self.dp is not None else valid_loss
-            if decided <= best_valid_loss:
-                best_valid_loss, best_epoch = decided, e
+            extra = {}
+            if select_by == "valid_loss":
+                decided = self.dp.agree(valid_loss) if self.dp is not None else valid_loss
+                is_best = decided <= best_valid_loss
+                if is_best:
+                    best_valid_loss = decided
+            else:
+                from .ranking import SELECT_BY
+                figure = self.rank("dev", confidence=False)["scores"].as_dict()[SELECT_BY[select_by]]
+                print(f"Valid {select_by}: {figure}")
+                is_best = figure >= best_figure                 # a NaN (no class with both kinds of rows) is never the best
+                if is_best:
+                    best_figure = figure
+                extra = {f"valid_{select_by}": figure}
+            if is_best:
+                best_epoch = e
                 print("Found new best model on dev set!")
                 self._check_cluster_all_ranks("before saving the checkpoint")  # never save weights a failed exchange produced
                 if self.dp is None or self.dp.rank == 0:
@@ -248,7 +268,7 @@ class Solver(object):
                     torch.save(self.optimizer.state_dict(), f"checkpoints/optim_{cfg.name}.std")     # solver.py:220
             if self.dp is not None:
                 torch.distributed.barrier()               # every epoch, on every rank: nobody reads the checkpoint before rank 0 has written it
-            history.append(dict(epoch=e, train=tr, valid_loss=valid_loss, valid_acc=valid_acc))
+            history.append(dict(epoch=e, train=tr, valid_loss=valid_loss, valid_acc=valid_acc, **extra))
         thresholds = self._calibrate_after_training(best_epoch >= 0)
         test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds)
         print("=" * 50)
@@ -309,20 +329,24 @@ class Solver(object):
         return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
 
     # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py)
-    def _eval_batches(self, dataloader):
-        """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``."""
+    def _eval_batches(self, dataloader, confidence=False):
+        """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``;
+        ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence in them."""
         self.model.eval()
         with torch.no_grad():
             for batch in dataloader:
                 if isinstance(batch, EncodedBatch):
-                    predicted_scores, _ = self.model.forward_encoded(batch)
+                    predicted_scores, predicted_labels = self.model.forward_encoded(batch)
                     emo_label = batch.emo()
                 else:
                     t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
                     t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
                     l = to_cpu(l)
-                    predicted_scores, _ = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
-                yield predicted_scores, emo_label.type(torch.float)
+                    predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
+                if confidence:
+                    yield predicted_scores, emo_label.type(torch.float), predicted_labels, self.model.tcp
+                else:
+                    yield predicted_scores, emo_label.type(torch.float)
 
     def _eval_thresholds(self, mode, to_print, thresholds):
         from . import _lib
@@ -392,6 +416,35 @@ class Solver(object):
             os.makedirs("checkpoints", exist_ok=True)
             thresholds.save(f"checkpoints/thresholds_{self.train_config.name}.pt")
         return thresholds
+
+    # ------------------------------------------------------------------ ranking metrics (mmda_amd/ranking.py)
+    def rank(self, mode="dev", tpr=0.95, confidence=True):
+        """How the model RANKS the ``mode`` split ("dev" or "test"), before any cut-off: the loop of ``eval`` keeping scores, truth, the
+        model's decisions and ``model.tcp`` of every batch on the device, then ``{"scores": ranking_metrics(scores, truth),
+        "confidence": failure_prediction(tcp, labels == truth)}`` -- both ``RankingResult``s on the device; ``confidence`` is None
+        where it is not asked for or the model has no confidence column per class.  Sets and returns ``self.last_ranking``.  Waits for
+        nothing but the cluster check; reading a result back (``.cpu()``, ``.as_dict()``) is the caller's."""
+        from . import _lib
+        from .ranking import failure_prediction, ranking_metrics
+        if mode not in ("dev", "test"):
+            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        S, T, L, Q = [], [], [], []
+        for scores, emo_label, labels, tcp in self._eval_batches(dataloader, confidence=True):
+            if not scores.is_cuda:
+                raise _lib.MMDAError("rank() counts on the GPU only (the HIP path has no CPU fallback)")
+            S.append(scores.detach()); T.append(emo_label.detach()); L.append(labels.detach())
+            Q.append(None if tcp is None else tcp.detach())
+        self._check_cluster(f"rank({mode})")
+        if not S:
+            raise ValueError(f"rank({mode!r}): the {mode} loader yields no batch")
+        scores, truth = torch.cat(S, 0), torch.cat(T, 0)
+        out = {"scores": ranking_metrics(scores, truth, tpr=tpr), "confidence": None}
+        if confidence and all(q is not None and q.shape == l.shape for q, l in zip(Q, L)):
+            correct = (torch.cat(L, 0) > 0) == (truth > 0)
+            out["confidence"] = failure_prediction(torch.cat(Q, 0), correct.to(torch.float32), tpr=tpr)
+        self.last_ranking = out
+        return out
 
     # ------------------------------------------------------------------ inference (the reference's src/inference.py is a TODO)
     def infer(self, mode, fields=None, order="loader"):
