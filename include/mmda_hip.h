@@ -430,6 +430,15 @@ int mmda_heads_fwd(const float* logits, int B, int ncls, float threshold, float*
 /* dlogits from dscores/dtcp (either may be NULL = zero) */
 int mmda_heads_bwd(const float* tcp, const float* scores, const float* dtcp, const float* dscores, int B, int ncls,
                    float* dlogits, float drop_p, uint64_t seed, int site, void* stream);
+/* The same pair under a task.  MMDA_TASK_EMOTION: the two calls above.  MMDA_TASK_SENTIMENT: the score columns are regression outputs,
+ * scores = dropout(logits[:, 6:]) with no sigmoid (the reference's classifier is Linear, Dropout, Sigmoid: the task drops the last stage)
+ * and dlogits = dscores * dropout with no s (1 - s); tcp, labels = scores > threshold and the six confidence columns are as above. */
+#define MMDA_TASK_EMOTION 0
+#define MMDA_TASK_SENTIMENT 1
+int mmda_heads_fwd_task(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
+                        float drop_p, uint64_t seed, int site, int task, void* stream);
+int mmda_heads_bwd_task(const float* tcp, const float* scores, const float* dtcp, const float* dscores, int B, int ncls,
+                        float* dlogits, float drop_p, uint64_t seed, int site, int task, void* stream);
 
 /* Every loss entry point computes the loss value AND d(loss)/d(inputs) in one pass ("gradient in forward").
  * `scale` multiplies the gradients (loss weight); *loss gets the UNscaled value added (zero it first).
@@ -446,6 +455,14 @@ int mmda_loss_cls(const float* scores, const float* emo, int B, int ncls, float 
 typedef struct mmda_cls_opts { float focal_gamma; int n_weights; float pos_weight[16]; } mmda_cls_opts;
 int mmda_loss_cls_opts(const float* scores, const float* emo, int B, int ncls, float scale, float* loss, float* dscores,
                        const mmda_cls_opts* opts, void* stream);
+/* The sentiment task's criterion, a mean over the batch as nn.L1Loss / nn.MSELoss(reduction="mean") over a (B,) column (config.py's
+ * criterion_dict['mosi'] = 'L1Loss'; the commented nn.L1Loss of solver.py):
+ *   MMDA_SENTI_L1   l = |s - y|,    dl/ds = sign(s - y), 0 where s == y (torch's l1_loss backward)
+ *   MMDA_SENTI_MSE  l = (s - y)^2,  dl/ds = 2 (s - y)
+ * *loss += sum_c mean_b l; dscores += scale * dl/ds / B (each optional). */
+#define MMDA_SENTI_L1 0
+#define MMDA_SENTI_MSE 1
+int mmda_loss_reg(const float* scores, const float* y, int B, int ncls, int kind, float scale, float* loss, float* dscores, void* stream);
 /* conf: solver.py:451-462 */
 int mmda_loss_conf(const float* scores, const float* tcp, const float* emo, int B, int ncls, float scale,
                    float* loss, float* dscores, float* dtcp, void* stream);
@@ -577,6 +594,25 @@ int mmda_rank_plan_describe(int64_t N, int C, mmda_rank_plan* out);
 int mmda_rank_counts(const float* scores, const float* truth, int64_t N, int C, uint32_t* counts, void* stream);
 int mmda_rank_finish(const uint32_t* counts, const float* truth, int64_t N, int C, double tpr_level, double* out, void* stream);
 int mmda_rank_rows_accumulate(const float* scores, const float* truth, int64_t N, int C, unsigned long long* state, void* stream);
+
+/* ---------------------------------------------------------------------------------------------- sentiment table
+ * The figures of the reference's eval_mosei_senti (src/utils/eval_metrics.py) from one device state, one launch per batch.
+ * state: MMDA_SENTI_STATE_WORDS 8-byte words, 8-byte aligned, cleared by the caller before the first batch:
+ *   uint64  [0] n  [1] n_nonzero (truth != 0)  [2] Acc-7 hits  [3] Acc-5 hits (rint of the values clipped to +-3 / +-2: half to even, as
+ *           np.round)  [4..7] the 2x2 table of (truth >= 0, pred >= 0) over all rows, index 2 * truth bit + pred bit  [8..11] the table of
+ *           (truth > 0, pred > 0) over the rows with truth != 0  [12] n_extreme (|truth| > 2)  [13] the launch's ticket, 0 between launches
+ *   double  [16] sum |p - t|  [17] the same over the extreme rows  [18] sum p  [19] sum t  [20] sum p^2  [21] sum t^2  [22] sum p t
+ * The counts are integer adds and do not depend on how the rows are split into batches; the float64 sums are added in a fixed order
+ * (per-workgroup partials, then workgroup order, no float atomic), so the same batches give the same bits on every run.  One state
+ * takes launches of one stream at a time.
+ * mmda_senti_finish writes MMDA_SENTI_FIGURES doubles: mae, corr (Pearson, clipped to [-1, 1]), acc7 (the reference's 'mult'), acc5,
+ * acc2 and f1 (>= 0 over all rows), acc2_non0 and f1_non0 (> 0 over the rows with truth != 0), mae_intensity (over |truth| > 2).  The F1s
+ * are sklearn's average='weighted' over the labels present.  NaN where numpy gives NaN: corr of a constant column or a single row,
+ * mae_intensity without an extreme row; the two non0 figures are NaN without a non-zero truth, where the reference itself fails. */
+#define MMDA_SENTI_STATE_WORDS 24
+#define MMDA_SENTI_FIGURES 9
+int mmda_senti_accumulate(const float* pred, const float* truth, int64_t N, void* state, void* stream);
+int mmda_senti_finish(const void* state, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- optimizer
  * clip_grad_value_(clip) then Adam (solver.py:185-186, :97-99; betas 0.9/0.999, eps 1e-8, no weight decay), fused over
@@ -887,6 +923,13 @@ int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, float clip_norm
  * plan does not depend on it: no launch is added or moved.  MMDA_EINVAL with nothing changed and nothing launched: a focal_gamma other
  * than 0 or 1 .. 8, n_weights other than 0 or the model's ncls, weights for more than 16 classes, a negative or non-finite weight. */
 int mmda_misa_set_cls_loss(mmda_misa* m, const mmda_cls_opts* opts);
+/* The task of the handle.  MMDA_TASK_EMOTION (the default): the classifier above; loss_kind is not read.  MMDA_TASK_SENTIMENT: the
+ * model's one score column is a regression output (mmda_heads_fwd_task) and the loss the handle calls cls is mmda_loss_reg's loss_kind
+ * (MMDA_SENTI_L1 / MMDA_SENTI_MSE) against the (B, 1) target given where the labels were.  Read when a step begins, at the sites that
+ * read the criterion; the step's plan does not depend on it.  MMDA_EINVAL with nothing changed: an unknown task or kind; under the
+ * sentiment task a model with ncls != 1 or use_confidNet (the confidence target truth * pred is defined for labels in {0, 1}), or a
+ * weighted / focal criterion set -- and mmda_misa_set_cls_loss refuses such a criterion while the task is set. */
+int mmda_misa_set_task(mmda_misa* m, int task, int loss_kind);
 /* One optimizer step from N micro-batches (config.accum_steps; the arithmetic of mmda_grad_accumulate above).  Every micro-batch is
  * mmda_misa_train_step with do_adam = 0; behind each but the last call mmda_misa_grad_accumulate, behind the last
  * mmda_misa_adam_step_accumulated with grad_scale = 1/N.  The runtime owns none of the memory:

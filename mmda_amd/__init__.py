@@ -8,7 +8,8 @@ device) and ``utils.tools`` (their files); ``encoded`` holds the encoder cache (
 fusion block and the heads of a model with frozen encoders from stored encoder outputs); ``calibrate`` sweeps the decision cut-off
 (``ThresholdSweep``, ``Thresholds``: every candidate threshold counted on the device in one launch per batch); ``ranking`` measures
 how a score table ranks before any cut-off (``ranking_metrics``: exact per-class AUROC / AP and the label-ranking figures;
-``failure_prediction``: the same over ConfidNet's ``tcp``).
+``failure_prediction``: the same over ConfidNet's ``tcp``); ``sentiment`` holds the table of the second task (``config.task =
+"sentiment"``): ``sentiment_metrics`` / ``SentimentEval``, the figures of the reference's ``eval_mosei_senti`` from one device state.
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -18,3 +19,4 @@ from .inference import FIELDS, InferencePass, InferenceResult, inference_plan  #
 from .encoded import EncodedBatch, EncodedLoader, EncoderCache  # noqa: F401
 from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_grid  # noqa: F401
 from .ranking import RankingResult, failure_prediction, rank_plan, ranking_metrics  # noqa: F401
+from .sentiment import SentimentEval, sentiment_metrics  # noqa: F401

@@ -182,6 +182,9 @@ class EncodedBatch(C.Structure):
 
 
 CELL = {"lstm": 0, "gru": 1}
+TASK = {"emotion": 0, "sentiment": 1}            # MMDA_TASK_*
+SENTI_LOSS = {"l1": 0, "mse": 1}                 # MMDA_SENTI_*
+SENTI_STATE_WORDS, SENTI_FIGURES = 24, 9         # MMDA_SENTI_STATE_WORDS, MMDA_SENTI_FIGURES
 
 # name -> (restype, argtypes).  Every symbol include/mmda_hip.h declares appears here (tests/test_abi.py checks it).
 _P, _I, _I64, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
@@ -240,6 +243,12 @@ SIGNATURES = {
     "mmda_act_dropout_bwd_p": (_I, [_P, _P, _P, _I64, _I, C.POINTER(ActParams), _F, _U64, _I, _P]),
     "mmda_heads_fwd": (_I, [_P, _I, _I, _F, _P, _P, _P, _F, _U64, _I, _P]),
     "mmda_heads_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _U64, _I, _P]),
+    "mmda_heads_fwd_task": (_I, [_P, _I, _I, _F, _P, _P, _P, _F, _U64, _I, _I, _P]),
+    "mmda_heads_bwd_task": (_I, [_P, _P, _P, _P, _I, _I, _P, _F, _U64, _I, _I, _P]),
+    "mmda_loss_reg": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "mmda_senti_accumulate": (_I, [_P, _P, _I64, _P, _P]),
+    "mmda_senti_finish": (_I, [_P, _P, _P]),
+    "mmda_misa_set_task": (_I, [_P, _I, _I]),
     "mmda_loss_cls": (_I, [_P, _P, _I, _I, _F, _P, _P, _P]),
     "mmda_loss_cls_opts": (_I, [_P, _P, _I, _I, _F, _P, _P, C.POINTER(ClsOpts), _P]),
     "mmda_loss_misc_opts": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _P, _P, _I64, _F, _P, _P, _P, _F, _F, _F, _F, _I,

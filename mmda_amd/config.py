@@ -115,6 +115,11 @@ DEFAULTS = dict(
     # highest "map" / "auroc" -- macro average precision / macro AUROC of the dev scores (mmda_amd/ranking.py), figures
     # that move neither with `threshold` nor with the criterion's weights
     select_by="valid_loss",
+    # which of a MOSEI sample's two targets the model's head is trained on: "emotion" -- the six-class multi-label
+    # classifier, the reference's published configuration -- or "sentiment": the (-3, 3) regression target, one output column
+    # (num_classes=1) without the sigmoid, under senti_loss "l1" (the reference's commented nn.L1Loss, config.py's criterion_dict['mosi'])
+    # or "mse"; evaluation then reports the reference's eval_mosei_senti table
+    task="emotion", senti_loss="l1",
 )
 
 
@@ -135,6 +140,10 @@ def get_config(parse=True, **optional_kwargs):
             parser.add_argument(f"--{k}", choices=("none", "global", "per_class"), default=v)
         elif k == "select_by":
             parser.add_argument(f"--{k}", choices=("valid_loss", "map", "auroc"), default=v)
+        elif k == "task":
+            parser.add_argument(f"--{k}", choices=("emotion", "sentiment"), default=v)
+        elif k == "senti_loss":
+            parser.add_argument(f"--{k}", choices=("l1", "mse"), default=v)
         elif v is None:
             parser.add_argument(f"--{k}", default=None)
         else:

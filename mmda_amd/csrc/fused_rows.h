@@ -13,6 +13,8 @@ struct FusedBwdC {
   int B, hs, ncls, nb;
   const float* tcp; const float* scores; const float* d_tcp; const float* d_scores; float* d_logits;
   float p_cls; uint64_t seed; int site_cls;
+  int reg;                        // REG_NONE, or the sentiment task (loss_terms.h): no sigmoid' behind the score column.  It takes the four
+                                  // bytes that padded site_cls up to the pointer behind it: the struct's size and offsets are what they were
   const float* head_w;            // (6 + ncls, 6 hs) row-major
   float* d_hfused;                // (B, 6 hs)
   mmda_ln_bwd_args ln2;           // rows = 6 B (token-major), permute_S / permute_B set
@@ -68,6 +70,8 @@ struct FusedFwdC {
   const float* ffn_parts; int n_parts; const float* b2; float* f2;      // optional: f2 = sum of the partials (slice order) + b2, first
   const float* hfused; const float* head_w; const float* head_b; float* logits;      // (B, 6 hs), (6 + ncls, 6 hs), 6 + ncls, (B, 6 + ncls)
   float threshold; float* tcp; float* scores; float* labels; float p_cls; uint64_t seed; int site_cls;
+  int reg;                        // REG_NONE, or the sentiment task's criterion: scores without the sigmoid, reg_term's seed (in site_cls's padding,
+                                  // as in FusedBwdC)
   // optional (training step): the classification loss's gradient seed d_scores = (s - y) / max(s (1 - s), 1e-12) / B, stored here
   const float* emo; float* d_scores;
   // ... or, with class weights / a focal exponent, cls_term's gradient / B (loss_terms.h; a kernel instance of its own)

@@ -189,6 +189,8 @@ __device__ __forceinline__ void rec_part_rows(const FusedBwdC& P, int b0, int nb
   }
 }
 
+// REG: the sentiment task's head (P.reg), an instance of its own like the forward stretch's
+template <bool REG>
 __global__ __launch_bounds__(FR_THREADS) void fused_bwd_c_kernel(FusedBwdC P) {
   __shared__ float red[2 * 8 * 128];
   __shared__ __attribute__((aligned(16))) float lds_a[6 * (128 + 4)];
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(FR_THREADS) void fused_bwd_c_kernel(FusedBwdC P) {
   // heads backward: sigmoid' (and the dropout of the class scores) into d_logits
   for (int e = threadIdx.x; e < nb * NC; e += FR_THREADS) {
     const int b = b0 + e / NC, c = e % NC;
-    P.d_logits[b * NC + c] = head_bwd_one(b, c, P.ncls, P.tcp, P.scores, P.d_tcp, P.d_scores, P.p_cls, P.seed, P.site_cls);
+    P.d_logits[b * NC + c] = head_bwd_one<REG>(b, c, P.ncls, P.tcp, P.scores, P.d_tcp, P.d_scores, P.p_cls, P.seed, P.site_cls);
   }
   stage_sync();
   // d_hfused (nb, 6 hs) = d_logits (nb, NC) W_head (NC, 6 hs): a dozen terms per element
@@ -460,8 +462,8 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_a_kernel(FusedFwdA P) {
 }
 
 // CLS_OPTS: the seed of the class-weighted / focal criterion (P.cls; loss_terms.h).  An instance of its own, so that the plain criterion's
-// kernel -- the default step's -- is the code it was, registers and all.
-template <bool CLS_OPTS>
+// kernel -- the default step's -- is the code it was, registers and all.  REG: the sentiment task (P.reg), likewise.
+template <bool CLS_OPTS, bool REG = false>
 __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
   __shared__ f4 sp[2 * 12 * 32];                         // sum_parts_rows: two halves x (<= 12 rows x 32 column groups)
   const int b0 = (int)blockIdx.x * P.nb;
@@ -495,11 +497,12 @@ __global__ __launch_bounds__(FR_THREADS) void fused_fwd_c_kernel(FusedFwdC P) {
     if (lane == 0) {
       const float z = acc + P.head_b[c];
       P.logits[b * NC + c] = z;
-      head_fwd_one(z, b, c, P, [&](int k, float sc) {
+      head_fwd_one<REG>(z, b, c, P, [&](int k, float sc) {
         if (P.d_scores) {                                               // the classification loss's seed of class k
           const float yv = P.emo[b * P.ncls + k];
           float v, d;
-          if constexpr (CLS_OPTS) cls_term(P.cls, sc, yv, k, v, d);
+          if constexpr (REG) reg_term(P.reg, sc, yv, v, d);
+          else if constexpr (CLS_OPTS) cls_term(P.cls, sc, yv, k, v, d);
           else bce_plain(sc, yv, 1.f, v, d);
           P.d_scores[b * P.ncls + k] = d / B;
         }
@@ -667,8 +670,10 @@ int mmda_fused_fwd_a(const FusedFwdA* a, void* stream) {
 
 int mmda_fused_fwd_c(const FusedFwdC* a, void* stream) {
   if (!a || a->B <= 0 || a->nb <= 0 || a->nb > 2 || a->hs != 128 || a->ln2.n != 128 || (a->d_scores && !a->emo)) return MMDA_EINVAL;
+  if (!reg_valid(a->reg) || (a->reg != REG_NONE && !cls_plain(a->cls))) return MMDA_EINVAL;
   const bool opts = a->d_scores && !cls_plain(a->cls);
-  hipLaunchKernelGGL(opts ? fused_fwd_c_kernel<true> : fused_fwd_c_kernel<false>, dim3(ceil_div(a->B, a->nb)), dim3(FR_THREADS), 0,
+  void (*const reg_kernel)(FusedFwdC) = fused_fwd_c_kernel<false, true>;        // (a name without a comma for the launch macro)
+  hipLaunchKernelGGL(a->reg != REG_NONE ? reg_kernel : opts ? fused_fwd_c_kernel<true> : fused_fwd_c_kernel<false>, dim3(ceil_div(a->B, a->nb)), dim3(FR_THREADS), 0,
                      (hipStream_t)stream, *a);
   MMDA_CHECK_LAUNCH("mmda_fused_fwd_c");
   return MMDA_OK;
@@ -721,7 +726,8 @@ int mmda_fused_bwd_c(const FusedBwdC* a, void* stream) {
   if (!a || a->B <= 0 || a->nb <= 0 || a->hs != 128 || a->ln2.n != 128) return MMDA_EINVAL;
   if ((a->ln2.dgamma || a->ln2.dbeta) && !a->pg_parts) return MMDA_EINVAL;       // parameter gradients go through the partials
   if (a->rec_part && (!a->d_recon || !a->rec_wT || a->nb > 2)) return MMDA_EINVAL;
-  hipLaunchKernelGGL(fused_bwd_c_kernel, dim3(ceil_div(a->B, a->nb) * (a->rec_part ? 2 : 1)), dim3(FR_THREADS), 0, (hipStream_t)stream, *a);
+  if (!reg_valid(a->reg)) return MMDA_EINVAL;
+  hipLaunchKernelGGL(a->reg != REG_NONE ? fused_bwd_c_kernel<true> : fused_bwd_c_kernel<false>, dim3(ceil_div(a->B, a->nb) * (a->rec_part ? 2 : 1)), dim3(FR_THREADS), 0, (hipStream_t)stream, *a);
   MMDA_CHECK_LAUNCH("mmda_fused_bwd_c");
   return MMDA_OK;
 }

@@ -97,6 +97,12 @@ int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, con
 
 // what mmda_loss_cls_opts, mmda_loss_misc_opts and mmda_misa_set_cls_loss accept for a model of ncls classes (o == nullptr: plain, valid)
 bool mmda_cls_opts_valid(const mmda_cls_opts* o, int ncls);
+// mmda_loss_misc_opts with the criterion of the handle's task: reg = REG_NONE (loss_terms.h) is that call; else the cls role is the
+// regression criterion's, and opts and with_conf must be off
+int mmda_loss_misc_reg(const float* scores, const float* tcp, const float* emo, int B, int ncls, float* d_scores, float* d_tcp,
+                       int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
+                       float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
+                       float conf_w, int use_conf, const mmda_cls_opts* opts, int reg, void* stream);
 
 // ---- lstm.hip / embed_rows.hip: the launch that reads a step's ids, stamping their rows on its way (st == nullptr: the C ABI's call)
 int mmda_lstm_pack_convert_transpose_stamped(int n, const int* H, const float* const* whh, void* const* packed_fwd, void* const* packed_bwd,

@@ -10,8 +10,17 @@
 // g = 0 or 1 <= g <= 8 (mmda_cls_opts_valid): between 0 and 1, (1-s)^(g-1) diverges where lp vanishes.  Finite at s = 0 and s = 1.
 // The plain criterion (no weights, g = 0) is computed here too, once: each site takes `cls_plain`, a launch-uniform branch, between
 // bce_plain and cls_term, so the default step's bits are what they were.
+// The sentiment task (mmda_misa_set_task) replaces the class head by a regression output and the criterion by reg_term:
+//   head   s = z * dropout (no sigmoid: the reference's classifier is Linear, Dropout, Sigmoid and the task drops the last stage)
+//   l1     l = |s - y|,    dl/ds = sign(s - y), 0 where s == y                                     (torch l1_loss backward)
+//   mse    l = (s - y)^2,  dl/ds = 2 (s - y)
+// both a mean over the batch.  `reg` below is REG_NONE for the classifier, else the criterion: launch-uniform wherever it is a value, a
+// kernel instance of its own wherever the file has one for the weighted criterion.
 #pragma once
 #include "common.h"
+
+constexpr int REG_NONE = 0, REG_L1 = 1, REG_MSE = 2;      // = 0, 1 + MMDA_SENTI_L1, 1 + MMDA_SENTI_MSE (mmda_hip.h)
+__host__ __device__ __forceinline__ bool reg_valid(int reg) { return reg >= REG_NONE && reg <= REG_MSE; }
 
 constexpr int CLS_MAXW = 16;              // = EVAL_MAXC (losses.hip): classes a weight list can have
 
@@ -55,6 +64,13 @@ __device__ __forceinline__ void bce_plain(float s, float y, float scale, float& 
   dvalue = scale * (s - y) / fmaxf(s * (1.f - s), 1e-12f);
 }
 
+// the regression criterion: value and d(value)/ds of one element (reg: REG_L1 or REG_MSE)
+__device__ __forceinline__ void reg_term(int reg, float s, float y, float& value, float& dvalue) {
+  const float d = s - y;
+  if (reg == REG_L1) { value = fabsf(d); dvalue = d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f; }
+  else { value = d * d; dvalue = 2.f * d; }
+}
+
 // the reconstruction MSE's gradient seed of one element: d = recon - orig, inv_n = 1 / elements
 __device__ __forceinline__ float recon_seed(float d, float inv_n, float scale) { return 2.f * d * inv_n * scale; }
 
@@ -62,21 +78,26 @@ __device__ __forceinline__ float recon_seed(float d, float inv_n, float scale) {
 // the score through the class-score dropout (element index b ncls + k) and the label against the threshold; then(k, score) follows a
 // class score where it was made (the forward stretch stores the classification loss's seed there).
 // H: HeadFwdArgs, or the forward stretch's own argument block, which carries the same members and is read in place.
+// REG: the sentiment task's output -- the same element without the sigmoid.
 struct HeadFwdArgs { int ncls; float threshold; float* tcp; float* scores; float* labels; float p_cls; uint64_t seed; int site_cls; };
-template <typename H, typename Then>
+template <bool REG = false, typename H, typename Then>
 __device__ __forceinline__ void head_fwd_one(float z, int b, int c, const H& h, Then&& then) {
   if (c < 6) {
     h.tcp[b * 6 + c] = sigmoidf_(z);
   } else {
     const int k = c - 6;
-    const float s = sigmoidf_(z * drop_mul(h.p_cls, h.seed, h.site_cls, (uint64_t)(b * h.ncls + k)));
+    const float zd = z * drop_mul(h.p_cls, h.seed, h.site_cls, (uint64_t)(b * h.ncls + k));
+    float s;
+    if constexpr (REG) s = zd; else s = sigmoidf_(zd);
     h.scores[b * h.ncls + k] = s;
     h.labels[b * h.ncls + k] = s > h.threshold ? 1.f : 0.f;
     then(k, s);
   }
 }
 
-// d(loss)/d(logit) of the same element: sigmoid' (and the dropout multiplier of the class scores); a head without a gradient gives 0
+// d(loss)/d(logit) of the same element: sigmoid' (and the dropout multiplier of the class scores); a head without a gradient gives 0.
+// REG: no s (1 - s) factor behind the regression output.
+template <bool REG = false>
 __device__ __forceinline__ float head_bwd_one(int b, int c, int ncls, const float* tcp, const float* scores, const float* dtcp,
                                               const float* dscores, float p, uint64_t seed, int site) {
   float g = 0.f;
@@ -85,8 +106,12 @@ __device__ __forceinline__ float head_bwd_one(int b, int c, int ncls, const floa
   } else {
     const int k = c - 6;
     if (dscores) {
-      const float s = scores[b * ncls + k];
-      g = dscores[b * ncls + k] * s * (1.f - s) * drop_mul(p, seed, site, (uint64_t)(b * ncls + k));
+      if constexpr (REG) {
+        g = dscores[b * ncls + k] * drop_mul(p, seed, site, (uint64_t)(b * ncls + k));
+      } else {
+        const float s = scores[b * ncls + k];
+        g = dscores[b * ncls + k] * s * (1.f - s) * drop_mul(p, seed, site, (uint64_t)(b * ncls + k));
+      }
     }
   }
   return g;

@@ -10,19 +10,22 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------ heads
 // (the element: head_fwd_one / head_bwd_one, loss_terms.h -- the fused stretches call the same)
+// (REG: the sentiment task's regression output, an instance of its own)
+template <bool REG>
 __global__ void heads_fwd_kernel(const float* __restrict__ logits, int B, int ncls, float thr, float* tcp, float* scores,
                                  float* labels, float p, uint64_t seed, int site) {
   const int NC = 6 + ncls;
   const HeadFwdArgs h = {ncls, thr, tcp, scores, labels, p, seed, site};
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x)
-    head_fwd_one(logits[e], e / NC, e % NC, h, [](int, float) {});
+    head_fwd_one<REG>(logits[e], e / NC, e % NC, h, [](int, float) {});
 }
 
+template <bool REG>
 __global__ void heads_bwd_kernel(const float* __restrict__ tcp, const float* __restrict__ scores, const float* dtcp,
                                  const float* dscores, int B, int ncls, float* dlogits, float p, uint64_t seed, int site) {
   const int NC = 6 + ncls;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B * NC; e += gridDim.x * blockDim.x)
-    dlogits[e] = head_bwd_one(e / NC, e % NC, ncls, tcp, scores, dtcp, dscores, p, seed, site);
+    dlogits[e] = head_bwd_one<REG>(e / NC, e % NC, ncls, tcp, scores, dtcp, dscores, p, seed, site);
 }
 
 // A loss that several workgroups contribute to: every workgroup leaves its partial in parts[block] and ONE thread adds them in block
@@ -44,14 +47,22 @@ struct AddAtomic { __device__ __forceinline__ void operator()(float* p, float v)
 // ------------------------------------------------------------------------------------------------ cls (BCE)
 // loss = sum_c (1/B) sum_b -(y log s + (1-y) log(1-s)), logs clamped at -100 (torch BCELoss);
 // grad  = (s - y) / max(s (1-s), 1e-12) / B   (torch binary_cross_entropy_backward)
-// With class weights or a focal exponent (ct) the element is cls_term's, else bce_plain's (loss_terms.h).
+// With class weights or a focal exponent (ct) the element is cls_term's, else bce_plain's (loss_terms.h); under the sentiment task
+// (reg != REG_NONE) it is reg_term's: the mean of |s - y| or (s - y)^2 over the batch.
 // One workgroup: returns its loss value; ds (optional) += scale * gradient.
 template <typename Add>
 __device__ __forceinline__ float cls_block(const float* __restrict__ s, const float* __restrict__ y, int B, int ncls, float scale, float* ds,
-                                           const ClsTerm& ct, float* red) {
+                                           const ClsTerm& ct, int reg, float* red) {
   const Add add;
   float acc = 0.f;
-  if (cls_plain(ct)) {                                     // launch-uniform
+  if (reg != REG_NONE) {                                   // launch-uniform, as the two below
+    for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
+      float v, d;
+      reg_term(reg, s[e], y[e], v, d);
+      acc += v;
+      if (ds) add(&ds[e], scale * d / B);
+    }
+  } else if (cls_plain(ct)) {
     for (int e = threadIdx.x; e < B * ncls; e += blockDim.x) {
       float v, d;
       bce_plain(s[e], y[e], scale, v, d);
@@ -70,9 +81,9 @@ __device__ __forceinline__ float cls_block(const float* __restrict__ s, const fl
 }
 
 __global__ __launch_bounds__(256) void cls_kernel(const float* __restrict__ s, const float* __restrict__ y, int B, int ncls,
-                                                  float scale, float* loss, float* ds, ClsTerm ct) {
+                                                  float scale, float* loss, float* ds, ClsTerm ct, int reg) {
   __shared__ float red[16];
-  const float t = cls_block<AddPlain>(s, y, B, ncls, scale, ds, ct, red);
+  const float t = cls_block<AddPlain>(s, y, B, ncls, scale, ds, ct, reg, red);
   if (threadIdx.x == 0 && loss) atomicAdd(loss, t);
 }
 
@@ -167,6 +178,7 @@ struct MiscLossArgs {
   float dw, sw, rw, cw; int use_conf, with_conf;
   int recon_blocks;
   ClsTerm ct;                               // the classification criterion (loss_terms.h)
+  int reg;                                  // ... or the sentiment task's (REG_L1 / REG_MSE)
 };
 
 __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
@@ -176,7 +188,7 @@ __global__ __launch_bounds__(256) void misc_losses_kernel(MiscLossArgs a) {
   const int role = blockIdx.x;
   float part;                                              // this workgroup's value, stored below
   if (role == 0) {
-    part = cls_block<AddAtomic>(a.scores, a.emo, B, ncls, 1.f, a.d_scores, a.ct, red);
+    part = cls_block<AddAtomic>(a.scores, a.emo, B, ncls, 1.f, a.d_scores, a.ct, a.reg, red);
   } else if (role <= (a.with_conf ? ncls : 0)) {
     const bool cg = a.conf_grads && a.d_scores;
     part = conf_block<AddAtomic>(a.scores, a.tcp, a.emo, role - 1, B, ncls, a.conf_scale, cg ? a.d_scores : nullptr, cg ? a.d_tcp : nullptr, red,
@@ -972,23 +984,45 @@ extern "C" int mmda_label_counts(const float* emo, int64_t N, int C, int64_t* co
   return MMDA_OK;
 }
 
-extern "C" int mmda_heads_fwd(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
-                              float drop_p, uint64_t seed, int site, void* stream) {
+extern "C" int mmda_heads_fwd_task(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
+                                   float drop_p, uint64_t seed, int site, int task, void* stream) {
   if (!logits || !tcp || !scores || !labels || B <= 0 || ncls <= 0) return MMDA_EINVAL;
+  if (task != MMDA_TASK_EMOTION && task != MMDA_TASK_SENTIMENT) return MMDA_EINVAL;
   int n = B * (6 + ncls);
-  hipLaunchKernelGGL(heads_fwd_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, logits, B, ncls, threshold, tcp,
+  hipLaunchKernelGGL(task ? heads_fwd_kernel<true> : heads_fwd_kernel<false>, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, logits, B, ncls, threshold, tcp,
                      scores, labels, drop_p, seed, site);
   MMDA_CHECK_LAUNCH("mmda_heads_fwd");
   return MMDA_OK;
 }
 
-extern "C" int mmda_heads_bwd(const float* tcp, const float* scores, const float* dtcp, const float* dscores, int B, int ncls,
-                              float* dlogits, float drop_p, uint64_t seed, int site, void* stream) {
+extern "C" int mmda_heads_fwd(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
+                              float drop_p, uint64_t seed, int site, void* stream) {
+  return mmda_heads_fwd_task(logits, B, ncls, threshold, tcp, scores, labels, drop_p, seed, site, MMDA_TASK_EMOTION, stream);
+}
+
+extern "C" int mmda_heads_bwd_task(const float* tcp, const float* scores, const float* dtcp, const float* dscores, int B, int ncls,
+                                   float* dlogits, float drop_p, uint64_t seed, int site, int task, void* stream) {
   if (!tcp || !scores || !dlogits || B <= 0 || ncls <= 0) return MMDA_EINVAL;
+  if (task != MMDA_TASK_EMOTION && task != MMDA_TASK_SENTIMENT) return MMDA_EINVAL;
   int n = B * (6 + ncls);
-  hipLaunchKernelGGL(heads_bwd_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, tcp, scores, dtcp, dscores, B,
+  hipLaunchKernelGGL(task ? heads_bwd_kernel<true> : heads_bwd_kernel<false>, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, tcp, scores, dtcp, dscores, B,
                      ncls, dlogits, drop_p, seed, site);
   MMDA_CHECK_LAUNCH("mmda_heads_bwd");
+  return MMDA_OK;
+}
+
+extern "C" int mmda_heads_bwd(const float* tcp, const float* scores, const float* dtcp, const float* dscores, int B, int ncls,
+                              float* dlogits, float drop_p, uint64_t seed, int site, void* stream) {
+  return mmda_heads_bwd_task(tcp, scores, dtcp, dscores, B, ncls, dlogits, drop_p, seed, site, MMDA_TASK_EMOTION, stream);
+}
+
+// the sentiment task's criterion alone: *loss += mean over the batch, dscores += scale * gradient (each optional)
+extern "C" int mmda_loss_reg(const float* scores, const float* y, int B, int ncls, int kind, float scale, float* loss, float* dscores,
+                             void* stream) {
+  if (!scores || !y || B <= 0 || ncls <= 0 || (kind != MMDA_SENTI_L1 && kind != MMDA_SENTI_MSE)) return MMDA_EINVAL;
+  hipLaunchKernelGGL(cls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, y, B, ncls, scale, loss, dscores, ClsTerm{},
+                     1 + kind);
+  MMDA_CHECK_LAUNCH("mmda_loss_reg");
   return MMDA_OK;
 }
 
@@ -996,7 +1030,7 @@ extern "C" int mmda_loss_cls_opts(const float* scores, const float* emo, int B, 
                                   const mmda_cls_opts* opts, void* stream) {
   if (!scores || !emo || B <= 0 || ncls <= 0 || !mmda_cls_opts_valid(opts, ncls)) return MMDA_EINVAL;
   hipLaunchKernelGGL(cls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, emo, B, ncls, scale, loss, dscores,
-                     cls_term_of(opts));
+                     cls_term_of(opts), REG_NONE);
   MMDA_CHECK_LAUNCH("mmda_loss_cls");
   return MMDA_OK;
 }
@@ -1245,11 +1279,20 @@ extern "C" int mmda_loss_misc_opts(const float* scores, const float* tcp, const 
                                    int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
                                    float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
                                    float conf_w, int use_conf, const mmda_cls_opts* opts, void* stream) {
+  return mmda_loss_misc_reg(scores, tcp, emo, B, ncls, d_scores, d_tcp, with_conf, conf_grads, conf_scale, recon, orig, n_recon, recon_scale,
+                            d_recon, d_orig, L, diff_w, sim_w, recon_w, conf_w, use_conf, opts, REG_NONE, stream);
+}
+
+int mmda_loss_misc_reg(const float* scores, const float* tcp, const float* emo, int B, int ncls, float* d_scores, float* d_tcp,
+                       int with_conf, int conf_grads, float conf_scale, const float* recon, const float* orig, int64_t n_recon,
+                       float recon_scale, float* d_recon, float* d_orig, float* L, float diff_w, float sim_w, float recon_w,
+                       float conf_w, int use_conf, const mmda_cls_opts* opts, int reg, void* stream) {
+  if (!reg_valid(reg) || (reg != REG_NONE && (opts || with_conf))) return MMDA_EINVAL;
   if (!scores || !emo || !recon || !orig || !L || B <= 0 || ncls <= 0 || n_recon <= 0) return MMDA_EINVAL;
   if (with_conf && (!tcp || ncls != 6)) return MMDA_EINVAL;
   if (!mmda_cls_opts_valid(opts, ncls)) return MMDA_EINVAL;
   MiscLossArgs a = {};
-  a.ct = cls_term_of(opts);
+  a.ct = cls_term_of(opts); a.reg = reg;
   a.scores = scores; a.tcp = tcp; a.emo = emo; a.B = B; a.ncls = ncls; a.d_scores = d_scores; a.d_tcp = d_tcp;
   a.conf_grads = conf_grads && d_scores && d_tcp; a.conf_scale = conf_scale; a.with_conf = with_conf;
   a.recon = recon; a.orig = orig; a.n_recon = n_recon; a.recon_inv_n = 1.0f / (float)n_recon; a.recon_scale = recon_scale;

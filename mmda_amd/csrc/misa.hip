@@ -372,6 +372,9 @@ struct mmda_misa {
   // given (cls()); cls_on == 0: the plain one.  plan_step does not read it.
   mmda_cls_opts cls_opts = {}; int cls_on = 0;
   const mmda_cls_opts* cls() const { return cls_on ? &cls_opts : nullptr; }
+  // The task (mmda_misa_set_task): REG_NONE (loss_terms.h) is the emotion classifier; REG_L1 / REG_MSE make the one output column a
+  // regression output with that criterion, at the same sites that read cls().  plan_step does not read it either.
+  int reg = REG_NONE;
   int fusion_fp8 = 0;
   int embed_update = EU_DENSE;
   // Frozen parameters (mmda_misa_set_trainable).  `runs`: the trainable ranges of the bucket, never merged across rnn2_begin, rnn1_begin
@@ -1228,8 +1231,21 @@ extern "C" int mmda_misa_set_adam(mmda_misa* m, const mmda_adam_opts* opts, floa
 
 extern "C" int mmda_misa_set_cls_loss(mmda_misa* m, const mmda_cls_opts* opts) {
   if (!m || !mmda_cls_opts_valid(opts, m->cfg.ncls)) return MMDA_EINVAL;
-  m->cls_on = opts && !(opts->n_weights == 0 && opts->focal_gamma == 0.f);
+  const int on = opts && !(opts->n_weights == 0 && opts->focal_gamma == 0.f);
+  if (on && m->reg != REG_NONE) return MMDA_EINVAL;      // class weights and the focal exponent belong to the classifier
+  m->cls_on = on;
   m->cls_opts = m->cls_on ? *opts : mmda_cls_opts{};
+  return MMDA_OK;
+}
+
+extern "C" int mmda_misa_set_task(mmda_misa* m, int task, int loss_kind) {
+  if (!m || (task != MMDA_TASK_EMOTION && task != MMDA_TASK_SENTIMENT)) return MMDA_EINVAL;
+  if (task == MMDA_TASK_SENTIMENT) {
+    if (loss_kind != MMDA_SENTI_L1 && loss_kind != MMDA_SENTI_MSE) return MMDA_EINVAL;
+    // one output column; the confidence loss's target truth * pred is defined for labels in {0, 1}
+    if (m->cfg.ncls != 1 || m->cfg.use_confidNet || m->cls_on) return MMDA_EINVAL;
+  }
+  m->reg = task == MMDA_TASK_SENTIMENT ? 1 + loss_kind : REG_NONE;
   return MMDA_OK;
 }
 
@@ -1626,7 +1642,7 @@ void Pass::fwd_fusion_skinny() {
       if (P.ffn_fuse_fwd) { f.ffn_parts = WS(w.ffn_parts); f.n_parts = FFN / 32; f.b2 = PP(p.l2_b); f.f2 = WS(w.f2); }
       f.hfused = WS(w.hfused); f.head_w = PP(p.head_w); f.head_b = PP(p.head_b); f.logits = WS(w.logits);
       f.threshold = c.threshold; f.tcp = WS(w.tcp); f.scores = WS(w.scores); f.labels = WS(w.labels);
-      f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS;
+      f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.reg = m->reg;
       if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(w.d_scores); f.cls = cls_term_of(m->cls()); }
       rc = mmda_fused_fwd_c(&f, s);
     }
@@ -1635,8 +1651,8 @@ void Pass::fwd_fusion_skinny() {
     g[0] = sk_nt(B, NC, 6 * hs, WS(w.hfused), 6 * hs, PP(p.head_w), PP(p.head_b), WS(w.logits), NC);
     sk_launch(*this, g, 1);
     if (!rc)
-      rc = mmda_heads_fwd(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
-                            s);
+      rc = mmda_heads_fwd_task(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
+                                 m->reg != REG_NONE, s);
   }
 }
 
@@ -1687,8 +1703,8 @@ void Pass::fwd_fusion_tiled() {
   // heads (models.py:247-249)
   lin_fwd(*this, fmode, B, NC, 6 * hs, WS(w.hfused), PP(p.head_w), PP(p.head_b), WS(w.logits));
   if (!rc)
-    rc = mmda_heads_fwd(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
-                          s);
+    rc = mmda_heads_fwd_task(WS(w.logits), B, c.ncls, c.threshold, WS(w.tcp), WS(w.scores), WS(w.labels), p_cls, seed, SITE_CLS,
+                               m->reg != REG_NONE, s);
 }
 }  // namespace
 
@@ -1819,11 +1835,11 @@ extern "C" int mmda_misa_losses(mmda_misa* m, const float* emo, int with_grads, 
     m->misc_deferred = emo;
     return MMDA_OK;
   }
-  return mmda_loss_misc_opts(WS(w.scores), WS(w.tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(w.d_scores) : nullptr,
-                             (with_grads && !s_cls) ? WS(w.d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext,
-                             c.conf_weight, WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(w.d_recon) : nullptr,
-                             (with_grads && !s_recon) ? WS(w.d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
-                             c.use_confidNet, m->cls(), stream);
+  return mmda_loss_misc_reg(WS(w.scores), WS(w.tcp), emo, B, c.ncls, (with_grads && !s_cls) ? WS(w.d_scores) : nullptr,
+                            (with_grads && !s_cls) ? WS(w.d_tcp) : nullptr, c.ncls == 6 && !ext, with_grads && c.use_confidNet && !ext,
+                            c.conf_weight, WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, (with_grads && !s_recon) ? WS(w.d_recon) : nullptr,
+                            (with_grads && !s_recon) ? WS(w.d_orig) : nullptr, L, c.diff_weight, c.sim_weight, c.recon_weight, c.conf_weight,
+                            c.use_confidNet, m->cls(), m->reg, stream);
 }
 
 // =============================================================================================== backward
@@ -1866,7 +1882,7 @@ void Pass::bwd_fusion_fused() {
     // the reconstruction term of stretch A's d_x6 chain, in workgroups of this launch (small batches: both sets fit the chip twice
     // over; MMDA_FUSED_SPLIT=0: inside stretch A as before)
     if (P.rec_hoisted) { f.d_recon = WS(w.d_recon); f.rec_wT = WS(w.rec_wT); f.rec_part = WS(w.rec_part); }
-    f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.head_w = PP(p.head_w); f.d_hfused = WS(w.d_hfused); f.ln2 = norm2_bwd();
+    f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.reg = m->reg; f.head_w = PP(p.head_w); f.d_hfused = WS(w.d_hfused); f.ln2 = norm2_bwd();
     f.pg_parts = WS(w.pg_parts);
     rc = mmda_fused_bwd_c(&f, s);
   }
@@ -1910,8 +1926,8 @@ void Pass::bwd_fusion_fused() {
 void Pass::bwd_fusion_skinny() {
   const bool wt = m->wT_valid != 0;                   // K-major weight copies from this step's forward (side stream, joined there)
   mmda_skinny_args g[8];
-  rc = mmda_heads_bwd(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
-                        s);
+  rc = mmda_heads_bwd_task(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
+                           m->reg != REG_NONE, s);
   g[0] = sk_dxw(wt, B, NC, 6 * hs, WS(w.d_logits), NC, WS(w.head_wT), PP(p.head_w), WS(w.d_hfused), 6 * hs, 0);
   sk_launch(*this, g, 1);
   const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
@@ -1963,8 +1979,8 @@ void Pass::bwd_fusion_skinny() {
 // ... many rows: the tiled generic kernel
 void Pass::bwd_fusion_tiled() {
   // heads
-  rc = mmda_heads_bwd(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
-                        s);
+  rc = mmda_heads_bwd_task(WS(w.tcp), WS(w.scores), WS(w.d_tcp), WS(w.d_scores), B, c.ncls, WS(w.d_logits), p_cls, seed, SITE_CLS,
+                           m->reg != REG_NONE, s);
   lin_dx(*this, fmode, B, NC, 6 * hs, WS(w.d_logits), PP(p.head_w), WS(w.d_hfused), 0);
   // norm2 + FFN
   const mmda_ln_bwd_args l2 = norm2_bwd(), l1 = norm1_bwd();
@@ -2042,9 +2058,9 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   rc = side_fork(m, s, &ss);
   if (!rc && m->misc_deferred) {
     // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
-    rc = mmda_loss_misc_opts(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
-                             WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
-                             c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, m->cls(), ss);
+    rc = mmda_loss_misc_reg(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
+                            WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
+                            c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, m->cls(), m->reg, ss);
     m->misc_deferred = nullptr;
   }
   if (!rc && P.skinny) rc = mmda_add(WS(w.x6), WS(w.x6 + 3 * BH), WS(w.rsum), 3 * BH, ss);

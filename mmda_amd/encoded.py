@@ -61,7 +61,8 @@ class EncoderCache:
     int64 and ``segments`` on the host; ``fingerprint``, the int64 sum over the int32 view of every parameter the encoders read, taken
     when the rows were made.  Row i is sample i of the ``DeviceDataset`` the cache was built from."""
 
-    def __init__(self, flat, widths, n, emo, lengths, segments, fingerprint, model=None):
+    def __init__(self, flat, widths, n, emo, lengths, segments, fingerprint, model=None, task="emotion"):
+        self.task = task                         # what ``emo`` holds: the emotion labels, or (task="sentiment") the (n, 1) sentiment column
         self.flat, self.widths, self.n = flat, tuple(int(w) for w in widths), int(n)
         self.emo, self.lengths, self.segments, self.fingerprint = emo, lengths, segments, int(fingerprint)
         self.model = model                       # the model the fingerprint was last taken of (EncodedLoader checks against it)
@@ -87,8 +88,11 @@ class EncoderCache:
         dev = _pass_device(model, dataset, "EncoderCache")
         n, widths = len(dataset), encoder_widths(model)
         flat = torch.empty(sum((n * w + 3) // 4 * 4 for w in widths), dtype=torch.float32, device=dev)
-        cache = cls(flat, widths, n, None if dataset.emo is None else dataset.emo.clone(),
-                    torch.from_numpy(np.array(dataset.lengths, dtype=np.int64)), np.array(dataset.segments, dtype=object), 0, model)
+        task = getattr(model, "task", "emotion")
+        # the label table the steps gather from: under the sentiment task the dataset's sentiment column, one float per sample
+        labels = dataset.sentiment.reshape(n, 1).clone() if task == "sentiment" else None if dataset.emo is None else dataset.emo.clone()
+        cache = cls(flat, widths, n, labels, torch.from_numpy(np.array(dataset.lengths, dtype=np.int64)),
+                    np.array(dataset.segments, dtype=object), 0, model, task)
         tabs = tuple(getattr(cache, f"utt_{m}").data_ptr() for m in MODALITIES)
         lib, h = model._lib, model._h
         dataset_pass(model, dataset, plan, bounds, batch_size, dev, lambda dst_ptr: _lib.check(
@@ -132,13 +136,14 @@ class EncoderCache:
 
     @classmethod
     def load(cls, path, device):
-        """The cache of ``save`` on ``device``.  It knows no model yet: ``cache.check(model)`` before training from it."""
+        """The cache of ``save`` on ``device``.  It knows no model yet: ``cache.check(model)`` before training from it.  (The file's keys
+        are what they were: a label table one column wide is the sentiment column, the dataset's emotion table has six.)"""
         d = torch.load(path, weights_only=True, map_location="cpu")
         seg = np.empty(len(d["segments"]), dtype=object)
         for i, s in enumerate(d["segments"]):
             seg[i] = s
         return cls(d["flat"].to(device), d["widths"], d["n"], None if d["emo"] is None else d["emo"].to(device), d["lengths"], seg,
-                   d["fingerprint"])
+                   d["fingerprint"], task="sentiment" if d["emo"] is not None and d["emo"].shape[1] == 1 else "emotion")
 
 
 class EncodedBatch:
@@ -149,7 +154,7 @@ class EncodedBatch:
         self.cache, self.rows, self.rows_ptr, self.B, self.lengths, self.segments = cache, rows, rows.data_ptr(), int(B), lengths, segments
 
     def emo(self):
-        """The batch's labels (B, 6): a torch gather, for callers outside the fused step (which gathers them itself)."""
+        """The batch's labels (B, 6) -- under the sentiment task the (B, 1) sentiment column --: a torch gather, for callers outside the fused step (which gathers them itself)."""
         if self.cache.emo is None:
             raise _lib.MMDAError("encoder cache: the dataset it was built from has no emotion labels")
         return self.cache.emo.index_select(0, self.rows)

@@ -118,6 +118,11 @@ class MISA(nn.Module):
         if isinstance(self.accum_steps, bool) or not isinstance(self.accum_steps, int) or self.accum_steps < 1:
             raise ValueError("config.accum_steps must be an int >= 1")
 
+        # what the sentiment task refuses (step_rules.SENTI_RULES), by name and before the native model exists
+        step_rules.task_check(getattr(config, "task", "emotion"), getattr(config, "senti_loss", "l1"), num_classes=self.output_size,
+                              use_confidNet=bool(getattr(config, "use_confidNet", False)), pos_weight=getattr(config, "pos_weight", None),
+                              focal_gamma=getattr(config, "focal_gamma", 0.0))
+
         lib = _lib.load()
         cc = _lib.MisaConfig(
             vocab=len(config.word2id), d_t=self.text_size, d_v=self.visual_size, d_a=self.acoustic_size,
@@ -142,7 +147,10 @@ class MISA(nn.Module):
         pw = getattr(config, "pos_weight", None)
         if isinstance(pw, str) and pw != "balanced":
             raise ValueError("config.pos_weight must be None, a list of num_classes floats or 'balanced'")
+        self.task, self.senti_loss = "emotion", "l1"
         self.set_cls_loss(None if isinstance(pw, str) else pw, getattr(config, "focal_gamma", 0.0))
+        # the task (config.task, config.senti_loss): under "sentiment" the one output column is the regression output
+        self.set_task(getattr(config, "task", "emotion"), getattr(config, "senti_loss", "l1"))
         self._layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self._native_names: List[str] = []                  # mmda_misa_param_info order = ascending bucket offset
         for i in range(lib.mmda_misa_num_params(h)):
@@ -366,9 +374,24 @@ class MISA(nn.Module):
         by name (step_rules.CLS_RULES) with nothing changed.  ``self.cls_loss`` reports the setting in force; weights that are all 1
         count as none, so with ``focal_gamma = 0`` the step is the default one."""
         w, g = step_rules.cls_setting(pos_weight, focal_gamma, self.output_size)
+        step_rules.task_check(self.task, self.senti_loss, num_classes=self.output_size, pos_weight=w, focal_gamma=g)
         _lib.check(self._lib.mmda_misa_set_cls_loss(self._h, _lib.cls_opts(w, g)), "mmda_misa_set_cls_loss")
         self.cls_loss = dict(pos_weight=w, focal_gamma=g)
         return self.cls_loss
+
+    def set_task(self, task: str = "emotion", senti_loss: str = "l1"):
+        """Which target the head is trained on, from the next step on.  ``"emotion"``: the classifier.  ``"sentiment"``:
+        the model's one score column (``num_classes == 1``) is a regression output -- no sigmoid in ``forward``, ``scores`` are the raw
+        outputs, ``labels = scores > threshold`` as ever -- and the loss every step calls ``cls`` is the batch mean of ``|s - y|``
+        (``senti_loss="l1"``) or ``(s - y)^2`` (``"mse"``) against the ``(B,)`` or ``(B, 1)`` sentiment column given where the emotion
+        labels were.  What is refused is raised by name (step_rules.SENTI_RULES) with nothing changed."""
+        step_rules.task_check(task, senti_loss, num_classes=self.output_size,
+                              use_confidNet=bool(getattr(self.config, "use_confidNet", False)),
+                              pos_weight=self.cls_loss["pos_weight"], focal_gamma=self.cls_loss["focal_gamma"])
+        _lib.check(self._lib.mmda_misa_set_task(self._h, _lib.TASK[task], _lib.SENTI_LOSS[senti_loss if task == "sentiment" else "l1"]),
+                   "mmda_misa_set_task")
+        self.task, self.senti_loss = task, (senti_loss if task == "sentiment" else self.senti_loss)
+        return self.task
 
     # ------------------------------------------------------------------ frozen parameters
     def _match(self, prefixes) -> List[str]:
@@ -724,6 +747,9 @@ class MISA(nn.Module):
             io, adam = self._encoded_begin(batch, "train_step_encoded", optimizer, clip_norm, exchange, accumulate, do_adam)
             if batch.cache.emo is None:
                 raise _lib.MMDAError("train_step_encoded: the cache has no emotion labels (its dataset had none)")
+            if batch.cache.task != self.task:
+                raise _lib.MMDAError(f"train_step_encoded: the cache's label table was stored under task='{batch.cache.task}', the model's "
+                                     f"task is '{self.task}': rebuild it (EncoderCache.build)")
             self._send_adam(adam)
             emo = torch.empty(batch.B, self.config.num_classes, dtype=torch.float32, device=batch.cache.device)
         else:
@@ -731,6 +757,9 @@ class MISA(nn.Module):
             self._sync_trainable(exchange=exchange)
             io = self._prepare(*batch)
             emo = emo_label.to(device=io[0].device, dtype=torch.float32).contiguous()
+            if self.task == "sentiment" and emo.numel() != io[0].shape[1]:
+                raise ValueError(f"task='sentiment' takes the (B,) or (B, 1) sentiment column: the target has {emo.numel()} entries, the "
+                                 f"batch {io[0].shape[1]} samples")
         if seed is None:
             seed = self._next_seed()
         custom = do_adam and optimizer is not None and not isinstance(optimizer, _optim.Adam)
@@ -1028,7 +1057,8 @@ class MISA(nn.Module):
                    "embed_segment_sum")
 
     def read_losses(self) -> Dict[str, float]:
-        """cls, diff, sim, recon, conf, total of the last losses pass (one device->host sync)."""
+        """cls, diff, sim, recon, conf, total of the last losses pass (one device->host sync); under task='sentiment' cls is the
+        regression loss."""
         L = self._ws_view("losses", (8,)).tolist()
         return dict(cls=L[0], diff=L[1], sim=L[2], recon=L[3], conf=L[4], total=L[5])
 

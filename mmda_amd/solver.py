@@ -54,6 +54,11 @@ class Solver(object):
         from .ranking import check_select_by
         check_select_by(getattr(cfg, "select_by", "valid_loss"),
                         process_group=torch.distributed.is_available() and torch.distributed.is_initialized())
+        # what the sentiment task refuses (step_rules.SENTI_RULES), here rather than at the first batch or behind the last epoch
+        step_rules.task_check(getattr(cfg, "task", "emotion"), getattr(cfg, "senti_loss", "l1"), num_classes=cfg.num_classes,
+                              use_confidNet=bool(getattr(cfg, "use_confidNet", False)), pos_weight=getattr(cfg, "pos_weight", None),
+                              focal_gamma=getattr(cfg, "focal_gamma", 0.0), calibrate=getattr(cfg, "calibrate", "none"),
+                              select_by=getattr(cfg, "select_by", "valid_loss"))
         if self.model is None:
             self.model = getattr(models, cfg.model)(cfg)
         for name, param in self.model.named_parameters():
@@ -114,6 +119,10 @@ class Solver(object):
             labels = host_labels(loader.dataset)
         return [float(x) for x in class_pos_weight(labels)]
 
+    def _sentiment(self):
+        """the model's task is the sentiment regression (the step's target is the batch's ``y`` column, evaluation the sentiment table)"""
+        return getattr(self.model, "task", "emotion") == "sentiment"
+
     def _cls_setting(self):
         """the model's classification criterion, as keyword arguments of bce_sum_over_classes / DeviceEval.add_cls_loss"""
         return dict(getattr(self.model, "cls_loss", None) or {})
@@ -146,6 +155,7 @@ class Solver(object):
         n = 0
         optimizer = getattr(self, "optimizer", None)
         clip_norm = getattr(cfg, "clip_norm", None)
+        senti = self._sentiment()
         for batch, k, count in self._micro_batches():
             accum = dict(accum_index=k, accum_count=count) if count > 1 else {}
             if clip_norm is not None:
@@ -159,7 +169,7 @@ class Solver(object):
                 self.model.train_step_encoded(batch, **step)
             else:
                 t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
-                t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(y if senti else emo_label)
                 l = to_cpu(l)
                 self.model.train_step(t, v, a, l, emo_label, **step)
             L = self.model._ws_view("losses", (8,))
@@ -189,13 +199,13 @@ class Solver(object):
             t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); y = to_gpu(y); emo_label = to_gpu(emo_label)
             l = to_cpu(l)
             predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
-            emo_label = emo_label.type(torch.float)
+            emo_label = (y if self._sentiment() else emo_label).type(torch.float)
             cls_loss = self.get_cls_loss(predicted_scores, emo_label)
             diff_loss = self.get_diff_loss()
             domain_loss = self.get_domain_loss()
             recon_loss = self.get_recon_loss()
             cmd_loss = self.get_cmd_loss()
-            conf_loss = self.get_conf_loss(predicted_scores, emo_label)
+            conf_loss = self.get_conf_loss(predicted_scores, emo_label) if cfg.use_confidNet or not self._sentiment() else 0.0
             similarity_loss = cmd_loss if cfg.use_cmd_sim else domain_loss
             loss = cls_loss + cfg.diff_weight * diff_loss + cfg.sim_weight * similarity_loss + cfg.recon_weight * recon_loss
             if cfg.use_confidNet:
@@ -241,6 +251,8 @@ class Solver(object):
             print("-" * 100)
             print("Epochs: {}, Valid loss: {}, Valid acc: {}".format(e, valid_loss, valid_acc))
             print("-" * 100)
+            if self._sentiment():
+                self._print_sentiment()
             # Data parallel: whether this epoch is the best one is decided ONCE, from rank 0's dev loss (a sharded dev loader, or one
             # ULP of difference between ranks, must not send one rank into the checkpoint barrier and another into the next epoch's
             # all-reduce), and the cluster check in front of the save is collective, so an error is raised on every rank.
@@ -271,6 +283,8 @@ class Solver(object):
             history.append(dict(epoch=e, train=tr, valid_loss=valid_loss, valid_acc=valid_acc, **extra))
         thresholds = self._calibrate_after_training(best_epoch >= 0)
         test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds)
+        if self._sentiment():
+            self._print_sentiment()
         print("=" * 50)
         print(f"Best epoch: {best_epoch}")
         print(f"Accuracy: {acc}")
@@ -286,6 +300,10 @@ class Solver(object):
         """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
         labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels."""
         assert mode is not None
+        if self._sentiment():
+            if thresholds is not None:
+                step_rules.task_check("sentiment", self.model.senti_loss, calibrate="thresholds")
+            return self._eval_sentiment(mode, to_print)
         if thresholds is not None:
             return self._eval_thresholds(mode, to_print, thresholds)
         self.model.eval()
@@ -328,6 +346,45 @@ class Solver(object):
         self.last_eval_metrics = get_metrics(y_true, y_pred)
         return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
 
+    # ------------------------------------------------------------------ the sentiment task (mmda_amd/sentiment.py)
+    def _eval_sentiment(self, mode, to_print):
+        """``eval`` under task='sentiment': (mean batch loss, acc2_non0, preds (N,), truths (N,)).  The loop of ``eval``; per batch one
+        collector launch (``SentimentEval.update``) and one loss launch adding into a device sum, nothing read back until the pass is
+        over.  ``self.last_sentiment``: the reference's eval_mosei_senti keys (and 'f1_non0'), all from the one collector state."""
+        from . import _lib
+        from .sentiment import SentimentEval
+        if mode == "test" and to_print:
+            self._load_best_checkpoint()
+        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        kind = _lib.SENTI_LOSS[self.model.senti_loss]
+        lib, ev, loss_sum, batches = _lib.load(), None, None, 0
+        preds, truths = [], []
+        for scores, y in self._eval_batches(dataloader):
+            if not scores.is_cuda:
+                raise _lib.MMDAError("eval() under task='sentiment' counts on the GPU only (the HIP path has no CPU fallback)")
+            s, t = scores.detach().to(torch.float32).contiguous().reshape(-1), y.contiguous().reshape(-1)
+            if ev is None:
+                ev, loss_sum = SentimentEval(s.device), torch.zeros(1, dtype=torch.float32, device=s.device)
+            ev.update(s, t)
+            _lib.check(lib.mmda_loss_reg(s.data_ptr(), t.data_ptr(), s.numel(), 1, kind, 1.0, loss_sum.data_ptr(), None, _lib.stream_ptr()),
+                       "mmda_loss_reg")
+            batches += 1
+            preds.append(s); truths.append(t)
+        self._check_cluster(f"eval({mode})")
+        if ev is None:
+            self.last_sentiment = None
+            return 0.0, float("nan"), np.zeros((0,), np.float32), np.zeros((0,), np.float32)
+        self.last_sentiment = ev.as_dict()
+        self.last_sentiment_counts = ev.counts()
+        return (float(loss_sum.item()) / batches, self.last_sentiment["acc2_non0"], torch.cat(preds).cpu().numpy(),
+                torch.cat(truths).cpu().numpy())
+
+    def _print_sentiment(self):
+        from .sentiment import format_table
+        if getattr(self, "last_sentiment", None):
+            c = self.last_sentiment_counts
+            print(format_table(self.last_sentiment, c["n"], c["n_nonzero"]))
+
     # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py, DESIGN.md 4j)
     def _eval_batches(self, dataloader, confidence=False):
         """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``;
@@ -340,7 +397,7 @@ class Solver(object):
                     emo_label = batch.emo()
                 else:
                     t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
-                    t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                    t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(y if self._sentiment() else emo_label)
                     l = to_cpu(l)
                     predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
                 if confidence:
@@ -385,6 +442,8 @@ class Solver(object):
         cut-off per class that maximises ``objective`` ("f1", "micro_f1", "weighted_f1", "acc"; None: what ``config.eval_mode`` names).
         Sets and returns ``self.thresholds``; the sweep's table of the ten figures per cut-off is kept in ``self.last_calibration``."""
         from .calibrate import ThresholdSweep, check_objective, objective_for
+        if self._sentiment():
+            step_rules.task_check("sentiment", self.model.senti_loss, calibrate="Solver.calibrate")
         if objective is None:
             objective = objective_for(getattr(self.train_config, "eval_mode", "macro"), per_class)
         check_objective(objective, per_class)
@@ -426,6 +485,8 @@ class Solver(object):
         nothing but the cluster check; reading a result back (``.cpu()``, ``.as_dict()``) is the caller's."""
         from . import _lib
         from .ranking import failure_prediction, ranking_metrics
+        if self._sentiment():
+            step_rules.task_check("sentiment", self.model.senti_loss, rank=True)
         if mode not in ("dev", "test"):
             raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
@@ -485,6 +546,8 @@ class Solver(object):
 
     # ------------------------------------------------------------------ getters (solver.py:373-462)
     def get_cls_loss(self, predicted_scores, emo_label):
+        if self._sentiment():                             # the task's criterion against the sentiment column
+            return F.senti_loss(predicted_scores, emo_label.type(torch.float), self.model.senti_loss)
         return F.bce_sum_over_classes(predicted_scores, emo_label.type(torch.float), **self._cls_setting())
 
     def get_domain_loss(self):

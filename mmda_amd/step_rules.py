@@ -76,6 +76,67 @@ def cls_setting(pos_weight, focal_gamma, num_classes: int):
     return w, float(focal_gamma)
 
 
+# What the sentiment task refuses.  Like CLS_RULES these are refusals of a SETTING, raised where it is made (MISA.__init__,
+# MISA.set_task, MISA.set_cls_loss, Solver.build, Solver.calibrate, Solver.rank) with nothing changed: the task combines with every step
+# form -- the target reaches the step through the pointer the labels came through -- so RULES has no entry for it either.
+TASKS = ("emotion", "sentiment")
+SENTI_LOSSES = ("l1", "mse")
+SENTI_RULES = (
+    ("task_name", "task must be 'emotion' or 'sentiment', not {task!r}"),
+    ("senti_loss", "senti_loss must be 'l1' or 'mse', not {loss!r}"),
+    ("senti_classes", "task='sentiment' has one regression output: num_classes must be 1, not {ncls}"),
+    ("senti_confid", "task='sentiment' with use_confidNet is not built: the confidence target truth * pred is defined for labels in {{0, 1}}"),
+    ("senti_pos_weight", "task='sentiment' with pos_weight is not built: the weight belongs to the positive term of the classification "
+                         "criterion"),
+    ("senti_focal", "task='sentiment' with focal_gamma = {gamma} is not built: the focal factor belongs to the classification criterion "
+                    "(focal_gamma must be 0)"),
+    ("senti_calibrate", "task='sentiment' with threshold calibration (Solver.calibrate, calibrate={how!r}) is not built: the cut-off "
+                        "figures are classification figures"),
+    ("senti_rank", "task='sentiment' with Solver.rank is not built: AUROC and average precision are classification figures"),
+    ("senti_select_by", "task='sentiment' with select_by={select_by!r} is not built: the ranking figures are classification figures (the "
+                        "best checkpoint is the one with the lowest dev loss: the dev MAE under senti_loss='l1')"),
+)
+
+
+def task_verdict(task="emotion", senti_loss="l1", num_classes=1, use_confidNet=False, pos_weight=None, focal_gamma=0.0,
+                 calibrate="none", select_by="valid_loss", rank=False):
+    """(rule, format values) of the first rule of SENTI_RULES that refuses the setting, or None.  ``calibrate``: config.calibrate, or any
+    other value than "none" for a call of Solver.calibrate; ``rank``: a call of Solver.rank.  Under task='emotion' nothing is looked at
+    but the task's name."""
+    if task not in TASKS:
+        return "task_name", dict(task=task)
+    if task == "emotion":
+        return None
+    if senti_loss not in SENTI_LOSSES:
+        return "senti_loss", dict(loss=senti_loss)
+    if isinstance(num_classes, bool) or num_classes != 1:
+        return "senti_classes", dict(ncls=num_classes)
+    if use_confidNet:
+        return "senti_confid", {}
+    if pos_weight is not None:
+        return "senti_pos_weight", {}
+    try:
+        zero = float(focal_gamma) == 0.0
+    except (TypeError, ValueError):
+        zero = False
+    if not zero:
+        return "senti_focal", dict(gamma=focal_gamma)
+    if calibrate not in (None, "none"):
+        return "senti_calibrate", dict(how=calibrate)
+    if rank:
+        return "senti_rank", {}
+    if select_by not in (None, "valid_loss"):
+        return "senti_select_by", dict(select_by=select_by)
+    return None
+
+
+def task_check(task="emotion", senti_loss="l1", **values) -> None:
+    """Raises MMDAError with the text of the rule that refuses the setting (``task_verdict``'s arguments)."""
+    hit = task_verdict(task, senti_loss, **values)
+    if hit is not None:
+        raise MMDAError(dict(SENTI_RULES)[hit[0]].format(**hit[1]))
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:

@@ -13,7 +13,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from .. import _lib
-from ..step_rules import cls_setting
+from ..step_rules import cls_setting, task_check
 
 
 def _need_cuda(*ts):
@@ -121,6 +121,26 @@ def bce_sum_over_classes(scores, emo, pos_weight=None, focal_gamma=0.0):
         return loss, (ds, None)
 
     return _GradInForward.apply(run, scores, emo)
+
+
+def senti_loss(scores, y, kind="l1"):
+    """The sentiment task's criterion: nn.L1Loss / nn.MSELoss(reduction="mean") of the (B, 1) regression output against
+    the (B,) or (B, 1) sentiment column.  ``kind``: "l1" or "mse"."""
+    _need_cuda(scores, y)
+    lib = _lib.load()
+    task_check("sentiment", kind, num_classes=scores.shape[1] if scores.dim() > 1 else 1)
+
+    def run(s, t):
+        s = s.contiguous().float(); t = t.contiguous().float()
+        if s.numel() != t.numel():
+            raise ValueError(f"senti_loss: {s.numel()} outputs, {t.numel()} targets")
+        loss = torch.zeros((), device=s.device)
+        ds = torch.zeros_like(s)
+        _lib.check(lib.mmda_loss_reg(s.data_ptr(), t.data_ptr(), s.numel(), 1, _lib.SENTI_LOSS[kind], 1.0, loss.data_ptr(), ds.data_ptr(),
+                                     _lib.stream_ptr()), "mmda_loss_reg")
+        return loss, (ds, None)
+
+    return _GradInForward.apply(run, scores, y)
 
 
 def conf_loss(scores, tcp, emo):
