@@ -776,6 +776,26 @@ int64_t mmda_misa_flat_floats(const mmda_misa* m);    /* whole bucket incl. embe
 int64_t mmda_misa_dense_floats(const mmda_misa* m);   /* non-embedding prefix */
 int mmda_misa_bind(mmda_misa* m, float* params, float* grads, float* adam_m, float* adam_v);
 int64_t mmda_misa_workspace_floats(const mmda_misa* m, int B, int T);
+/* A read-only view, in the style of mmda_lstm_plan_describe and mmda_gemm_bf16_plan_describe, of the plan a forward pass over (B, T)
+ * batches gets on this handle as it is set now: every choice of a form of the training step, one int per choice (the fields are
+ * StepPlan's, csrc/step_plan.h, which documents each).  Host code only: no launch, no device call, no environment; works without a
+ * workspace or buffers bound.  req: what the pass is asked to be -- fused: it belongs to mmda_misa_train_step; has_labels: labels are
+ * given; has_opt_step: an optimizer step of the kind that may run the background pass over the table follows (from a batch, do_adam,
+ * no clip_norm); enc_cached: it starts behind the encoders (mmda_misa_forward_encoded).  mmda_misa_forward is {0, 0, 0, 0}.
+ * switches: NULL = the defaults (NOT the process's environment), else MMDA_MISA_STEP_SWITCHES values standing for, in this order,
+ *   MMDA_GEMM_TN MMDA_WT_MERGE MMDA_ROW_FUSE MMDA_FFN_FUSE MMDA_LOSS_SEEDS MMDA_FLAG_JOIN MMDA_ZERO_GRAD_SIDE MMDA_FUSED_SPLIT
+ *   MMDA_SORT_EARLY MMDA_EMBED_BG MMDA_EMBED_BG_WGS MMDA_EMBED_BG_LATE MMDA_EMBED_BG_LDS
+ * (defaults 1 1 1 1 1 1 -1 1 1 1 0 0 1024).  MMDA_EINVAL, with *out untouched: m, req or out NULL, B <= 0, T <= 0, or switches given
+ * with another n_switches. */
+#define MMDA_MISA_STEP_SWITCHES 13
+typedef struct mmda_misa_step_request { int fused, has_labels, has_opt_step, enc_cached; } mmda_misa_step_request;
+typedef struct mmda_misa_step_plan {
+  int fused, inf, enc_cut, enc_nostash, enc_cached, bfg, gm, kdg, tn_wgrad, want_b, want_c, want_wT, wT_merge, skinny, row_fuse,
+      ffn_fuse_fwd, ffn_fuse_bwd, seed_recon, seed_cls, fj_on, fj_fwd, fj_device, zg_here, rec_hoisted, sort_early, embed_update,
+      embed_deferred, embed_bg, embed_bg_late, embed_bg_wgs, embed_bg_lds;
+} mmda_misa_step_plan;
+int mmda_misa_plan_describe(const mmda_misa* m, int B, int T, const mmda_misa_step_request* req, const int* switches, int n_switches,
+                            mmda_misa_step_plan* out);
 int mmda_misa_set_workspace(mmda_misa* m, float* ws, int64_t floats, int B, int T);
 /* The same with the (rare) clears enqueued on `stream`.  The exchange buffers of the recurrences sit at the front of the workspace at
  * offsets that depend on B alone and are cleared only when the buffer or B changes, so a new T per batch (the reference's collate pads
@@ -783,7 +803,7 @@ int mmda_misa_set_workspace(mmda_misa* m, float* ws, int64_t floats, int B, int 
  * mmda_misa_cluster_status.  Before handing over a NEW buffer read mmda_misa_cluster_status yourself: the old one is not touched. */
 int mmda_misa_set_workspace_async(mmda_misa* m, float* ws, int64_t floats, int B, int T, void* stream);
 /* offset (in floats, inside the workspace) of a named activation / activation-gradient; -1 if unknown, and for every name while no
- * workspace is bound. Names (all of them: the table kTensorNames in misa.hip):
+ * workspace is bound. Names (all of them: the table in tensor_offset(), step_plan.hip):
  *   scores labels tcp logits hfused x6 orig recon dom losses grad_norm utt_t utt_v utt_a
  *   d_scores d_tcp d_x6 d_orig d_recon d_dom
  *   pub_begin pub_end (the solver-visible outputs orig .. labels, contiguous)   zero_begin zero_end (the region cleared per step)

@@ -103,6 +103,26 @@ class LstmPlan(C.Structure):
                 ("kernel", C.c_int)]
 
 
+class MisaStepRequest(C.Structure):
+    """mmda_misa_step_request: what one forward pass is asked to be"""
+    _fields_ = [("fused", C.c_int), ("has_labels", C.c_int), ("has_opt_step", C.c_int), ("enc_cached", C.c_int)]
+
+
+STEP_PLAN_FIELDS = ("fused", "inf", "enc_cut", "enc_nostash", "enc_cached", "bfg", "gm", "kdg", "tn_wgrad", "want_b", "want_c", "want_wT",
+                    "wT_merge", "skinny", "row_fuse", "ffn_fuse_fwd", "ffn_fuse_bwd", "seed_recon", "seed_cls", "fj_on", "fj_fwd",
+                    "fj_device", "zg_here", "rec_hoisted", "sort_early", "embed_update", "embed_deferred", "embed_bg", "embed_bg_late",
+                    "embed_bg_wgs", "embed_bg_lds")
+# the step's switches in the order mmda_misa_plan_describe takes them (MMDA_MISA_STEP_SWITCHES of them), with their defaults
+STEP_SWITCHES = {"MMDA_GEMM_TN": 1, "MMDA_WT_MERGE": 1, "MMDA_ROW_FUSE": 1, "MMDA_FFN_FUSE": 1, "MMDA_LOSS_SEEDS": 1, "MMDA_FLAG_JOIN": 1,
+                 "MMDA_ZERO_GRAD_SIDE": -1, "MMDA_FUSED_SPLIT": 1, "MMDA_SORT_EARLY": 1, "MMDA_EMBED_BG": 1, "MMDA_EMBED_BG_WGS": 0,
+                 "MMDA_EMBED_BG_LATE": 0, "MMDA_EMBED_BG_LDS": 1024}
+
+
+class MisaStepPlan(C.Structure):
+    """mmda_misa_step_plan: every choice of a form of the training step, one int per StepPlan field"""
+    _fields_ = [(k, C.c_int) for k in STEP_PLAN_FIELDS]
+
+
 class LossForms(C.Structure):
     """mmda_loss_forms: which kernel form the loss entry points pick for a shape"""
     _fields_ = [("diff_form", C.c_int), ("diff_products", C.c_int), ("diff_loss_sum", C.c_int), ("diff_combine_blocks", C.c_int),
@@ -305,6 +325,7 @@ SIGNATURES = {
     "mmda_misa_dense_floats": (_I64, [_P]),
     "mmda_misa_bind": (_I, [_P, _P, _P, _P, _P]),
     "mmda_misa_workspace_floats": (_I64, [_P, _I, _I]),
+    "mmda_misa_plan_describe": (_I, [_P, _I, _I, C.POINTER(MisaStepRequest), C.POINTER(C.c_int), _I, C.POINTER(MisaStepPlan)]),
     "mmda_misa_set_workspace": (_I, [_P, _P, _I64, _I, _I]),
     "mmda_misa_set_workspace_async": (_I, [_P, _P, _I64, _I, _I, _P]),
     "mmda_misa_tensor_offset": (_I64, [_P, C.c_char_p]),

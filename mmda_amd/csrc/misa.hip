@@ -1,119 +1,17 @@
 // Native runtime for one MISA training iteration (reference loop body solver.py:139-186 over models.py:163-285).
-// Host-side C++ only: lays the parameters out in one flat bucket, carves the workspace, and issues the HIP kernels of
-// gemm.hip / lstm.hip / norm.hip / embed_rows.hip / attn.hip / losses.hip / optim.hip in dependency order on one stream.  No device
-// memory is owned here; no torch types; no host<->device synchronisation anywhere in a step.
-#include "common.h"
-#include "fused_rows.h"
-#include "internal.h"
+// Host-side C++ only: holds the parameter table, the workspace carve and the step's plan (step_plan.h makes all three), and issues the
+// HIP kernels of gemm.hip / lstm.hip / norm.hip / embed_rows.hip / attn.hip / losses.hip / optim.hip in dependency order on one
+// stream.  No device memory is owned here; no torch types; no host<->device synchronisation anywhere in a step.
+#include "step_plan.h"
 #include <algorithm>
-
 #include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+
+using namespace mmda_step;
 
 namespace {
 
-struct ParamInfo { std::string name; int64_t off; int rows, cols; };
-
-// ---- ParamTable: what is fixed at create.  Offsets are floats into the flat parameter bucket (and its gradient / Adam twins).
-struct RnnP {          // one bidirectional LSTM layer
-  int D, H;
-  int64_t w_ih, w_hh[2], b_ih, b_hh;     // w_ih: (8H,D) = [fwd;rev]; b_*: (8H) = [fwd;rev]
-  int ldD, ldG, ldH;                     // leading dimensions of the bf16 operand copies, in bf16 elements: round_up(D | 8H | H, 8)
-};
-struct ModP {          // one modality: two stacked biLSTMs with a LayerNorm between, then a projection
-  int D, H;
-  RnnP rnn[2];
-  int64_t ln_w, ln_b;                    // {t,v,a}layer_norm
-  int64_t pw, pb, plw, plb;              // project_*: Linear + LayerNorm
-};
-struct ParamTable {    // built once by build_params(cfg); the handle holds it const
-  std::vector<ParamInfo> params;
-  std::map<std::string, int> index;
-  int64_t dense = 0, flat = 0;
-  int64_t rnn2_begin = 0, rnn1_begin = 0;    // bucket offsets where the layer-2 / layer-1 recurrent parameters start
-  ModP mod[3];
-  // fusion parameter offsets
-  int64_t priv_w, priv_b, sh_w, sh_b, rec_w, rec_b, d1_w = -1, d1_b = -1, d2_w = -1, d2_b = -1, sp_w, sp_b;
-  int64_t head_w, head_b, embed;
-  int64_t in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b;
-  int64_t prelu_a = -1;                      // config.activation = prelu: the ONE learned slope (nn.PReLU() shared by every use, models.py:30)
-};
-
-// ---- Workspace: what carve(cfg, params, B, T) returns.  Offsets are floats into the bound workspace buffer.
-struct RnnW {
-  int64_t pack_f[2], pack_b[2], pack_c[2];   // the packed W_hh (per direction)
-  // bf16 operand copies for the bf16-mode GEMMs (leading dimensions: RnnP, and Workspace::ldR):
-  int64_t wb, wbT;                           // W_ih (8H, ldD) and W_ih^T (D, ldG)
-  int64_t xb, xbT;                           // layer input (R, ldD) and its transpose (D, ldR)
-  int64_t dgb, dgbT;                         // gate gradients (R, ldG) and transpose (8H, ldR)
-  int64_t hbT;                               // hseq^T (2H, ldR)
-  int64_t hbp[2];                            // tn weight-gradient GEMMs: hseq of one direction as bf16 (R, ldH)
-  // GRU (cfg.rnncell): the parameters / gradients in the four-slot layout (mmda_gru_pad_job); -1 for LSTM
-  int64_t pw_ih = -1, pw_hh[2] = {-1, -1}, pb_ih = -1, pb_hh = -1, gw_ih = -1, gw_hh[2] = {-1, -1}, gb = -1;
-};
-struct ModW {
-  RnnW rnn[2];
-  int64_t x, gates[2], c[2], hseq[2], normed, ln_mean, ln_rstd, utt, d_utt, d_hseq1, d_normed, d_x, xchg, xchg_floats;
-};
-struct Workspace {
-  int B = 0, T = 0, ldR = 0;                 // ldR = round_up(B * T, 8): rows of the transposed bf16 copies
-  int64_t floats = 0;                        // the whole carve
-  ModW mod[3];
-  int64_t pub_begin = 0, pub_end = 0;        // the public outputs, contiguous
-  int64_t zero_begin = 0, zero_end = 0;      // activation-gradient region that is zeroed per step
-  int64_t zero_cls = 0, zero_recon = 0;      // ... its tail: d_scores from zero_cls, d_orig + d_recon from zero_recon (see loss seeds)
-  int64_t gpad_begin = 0, gpad_end = 0;      // GRU: four-slot weight gradients (zeroed at set_workspace, re-zeroed by the unpad kernel)
-  int64_t z, pmean, prstd, orig, x6, rsum, recon, dom_z, dom_h, dom, qkv, probs, ctx, attn_out, ln1_mean, ln1_rstd, x1, f1, f2,
-      ln2_mean, ln2_rstd, hfused, logits, tcp, scores, labels, losses, diff_work, ffn_parts, pg_parts, ln_parts;
-  // block-scaled fp8 operands of the feed-forward products (fusion_fp8): element bytes and scale bytes, as float offsets
-  int64_t x1q, x1s, w1q, w1s, f1q, f1s, w2q, w2s;
-  // K-major (transposed) fp32 copies of the fusion block's weights for its input-gradient GEMMs (made once per step)
-  int64_t head_wT, l2_wT, l1_wT, out_wT, in_wT, rec_wT, priv_wT, sh_wT, d1_wT = -1, d2_wT = -1, pwT[3];
-  int64_t d_scores, d_tcp, d_x6, d_orig, d_recon, d_dom, d_logits, d_hfused, d_x1, d_f2, d_f1, d_attn_out, d_ctx, d_qkv, d_z,
-      d_dom_h, d_dom_z;
-  int64_t gnorm = -1, gnorm_parts = -1;      // clip_norm: norm and coefficient of the last such step; the norm launch's block partials (doubles)
-  int64_t esort = -1;                        // sorted (id, position) list of the step's text ids (see mmda_misa::esort_valid)
-  int64_t rec_part = -1;
-};
-
-// Every choice of a form of the training step, made once per step by plan_step() at the start of mmda_misa_forward() and read by every
-// part of the step.  What a launch's outcome sets or what is consumed later (wT_valid, side_pending, fj1, ...) stays in mmda_misa.
-struct StepPlan {
-  bool inf = false;                 // evaluation pass: no backward follows -- no stash, no copies that only the backward pass reads
-  bool enc_cut = false;             // every encoder parameter is frozen (mmda_misa_set_trainable): the backward pass stops in front of the encoders
-  bool enc_nostash = false;         // the encoders keep nothing for a backward pass: an evaluation pass, or a cut step (unless told to stash)
-  bool enc_cached = false;          // the encoders did not run at all: utt came from the encoder cache (mmda_misa_forward_encoded)
-  bool bfg = false;                 // bf16 mode with bf16 operand copies: the LSTM-sized GEMMs read them (gemm_bf16.hip)
-  int gm = 0;                       // gate-minor layout of `gates` (see mmda_lstm_desc.gate_minor)
-  bool kdg = false;                 // the backward recurrence writes the gate gradients as bf16, and only so
-  bool tn_wgrad = false;            // the weight-gradient GEMMs read dG / inputs / hseq as they lie (tn form): no transposed copies
-  bool want_b = false, want_c = false;     // W_hh packings made: for the streaming / the resident-weights backward kernels
-  bool want_wT = false, wT_merge = false;  // K-major fusion-weight copies (row-skinny backward); made in the step's first launch
-  bool skinny = false;              // fusion block on row-skinny GEMMs (B <= SKINNY_MAX_B), else on the tiled generic kernel
-  bool row_fuse = false;            // ... as fused row-local stretches (the backward pass also needs wT_valid)
-  bool ffn_fuse_fwd = false, ffn_fuse_bwd = false;   // the feed-forward pair fused (forward / backward differ: see plan_step)
-  bool seed_recon = false, seed_cls = false;         // the forward stretches store these loss seeds (see mmda_misa::emo_eager)
-  bool fj_on = false, fj_fwd = false, fj_device = false;   // flag joins; the forward one; ... waited for on the device
-  bool zg_here = false;             // the gradient bucket is cleared at the head of the loss chain (eager_side_losses)
-  bool rec_hoisted = false;         // stretch C's launch makes d_recon W_rec for stretch A
-  bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
-  int embed_update = 0;             // EU_*: how the step treats the embedding table (mmda_misa_set_embed_update)
-  bool embed_deferred = false;      // dense, with the table's update applied row by row when a row is next needed (mmda_misa_set_embed_deferred)
-  // The table rows the batch does not index take the step on a low-priority stream beside the forward pass (mmda_misa::bg; DESIGN section
-  // 4a), by embed_bg_wgs workgroups, forked behind the step's first launch or (embed_bg_late) behind the layer-1 forward recurrence.
-  bool embed_bg = false, embed_bg_late = false; int embed_bg_wgs = 0, embed_bg_lds = 0;
-};
-
-// embed_update: dense = the table's gradient is scattered into the bucket and dense Adam walks all V rows; sparse = the rows the batch
-// touches take a SparseAdam update where their sums become final, nothing V-sized is read, written or cleared; frozen = the table
-// takes no gradient at all (no text layer-1 dX product, no sort, no scatter).  In both new modes the gradient bucket ends at m->embed.
-enum { EU_DENSE = 0, EU_SPARSE = 1, EU_FROZEN = 2 };
-
 enum { SITE_ATTN = 1, SITE_DROP1 = 2, SITE_FFN = 3, SITE_DROP2 = 4, SITE_CLS = 5, SITE_DISC = 6,
        SITE_RRELU = 7 /* .. 9: the three projections' random slopes */, SITE_RRELU_DISC = 10 };
-constexpr int FFN = 2048, NHEAD = 2, S6 = 6;
 
 // The scalars of one optimizer step.  acc: an accumulator added to the gradient, or nullptr; norm: clip_grad_norm_ in front of it.
 struct OptStep { float lr, clip, grad_scale; int step; const float* acc; bool norm; };
@@ -124,227 +22,13 @@ struct PendingRows {
   PendingRows take() { const PendingRows r = *this; *this = PendingRows{}; return r; }
 };
 struct RowList { int64_t* ids; float* rows; int64_t used, capacity; };   // an accumulated step's (ids, rows) list: sparse table
-
-int64_t add_param(ParamTable& t, const std::string& name, int rows, int cols) {
-  ParamInfo p{name, t.flat, rows, cols};
-  t.index[name] = (int)t.params.size();
-  t.params.push_back(p);
-  t.flat += (int64_t)rows * (cols > 0 ? cols : 1);
-  return p.off;
-}
-
-ParamTable build_params(const mmda_misa_config& c) {
-  ParamTable t{};
-  const int dims[3] = {c.d_t, c.d_v, c.d_a};
-  const char* mn[3] = {"t", "v", "a"};
-  const int hs = c.hidden;
-  // Order of the dense bucket = the order in which the backward pass completes the gradients (data-parallel ranks start
-  // reducing a prefix while the rest is still being computed, mmda_misa_early_grad_floats): fusion block and LayerNorms first,
-  // then the layer-2 recurrent layers, then layer 1; the embedding matrix closes the bucket.
-  for (int i = 0; i < 3; ++i) { ModP& md = t.mod[i]; md.D = md.H = dims[i]; }
-  for (int i = 0; i < 3; ++i) {
-    ModP& md = t.mod[i];
-    std::string p = std::string("project_") + mn[i] + ".project_" + mn[i];
-    md.pw = add_param(t, p + ".weight", hs, 4 * md.H);
-    md.pb = add_param(t, p + ".bias", hs, 0);
-    md.plw = add_param(t, p + "_layer_norm.weight", hs, 0);
-    md.plb = add_param(t, p + "_layer_norm.bias", hs, 0);
-  }
-  // batched groups: three (hs,hs) weights back to back, then their three biases (uniform strides for batched GEMMs)
-  t.priv_w = add_param(t, "private_t.private_t_1.weight", hs, hs);
-  add_param(t, "private_v.private_v_1.weight", hs, hs);
-  add_param(t, "private_a.private_a_3.weight", hs, hs);          // sic: reference models.py:95
-  t.priv_b = add_param(t, "private_t.private_t_1.bias", hs, 0);
-  add_param(t, "private_v.private_v_1.bias", hs, 0);
-  add_param(t, "private_a.private_a_3.bias", hs, 0);
-  t.sh_w = add_param(t, "shared.shared_1.weight", hs, hs);
-  t.sh_b = add_param(t, "shared.shared_1.bias", hs, 0);
-  t.rec_w = add_param(t, "recon_t.recon_t_1.weight", hs, hs);
-  add_param(t, "recon_v.recon_v_1.weight", hs, hs);
-  add_param(t, "recon_a.recon_a_1.weight", hs, hs);
-  t.rec_b = add_param(t, "recon_t.recon_t_1.bias", hs, 0);
-  add_param(t, "recon_v.recon_v_1.bias", hs, 0);
-  add_param(t, "recon_a.recon_a_1.bias", hs, 0);
-  if (!c.use_cmd_sim) {
-    t.d1_w = add_param(t, "discriminator.discriminator_layer_1.weight", hs, hs);
-    t.d1_b = add_param(t, "discriminator.discriminator_layer_1.bias", hs, 0);
-    t.d2_w = add_param(t, "discriminator.discriminator_layer_2.weight", 3, hs);
-    t.d2_b = add_param(t, "discriminator.discriminator_layer_2.bias", 3, 0);
-  }
-  t.sp_w = add_param(t, "sp_discriminator.sp_discriminator_layer_1.weight", 4, hs);
-  t.sp_b = add_param(t, "sp_discriminator.sp_discriminator_layer_1.bias", 4, 0);
-  // [confidence; classifier] adjacent -> one (6+ncls, 6hs) head GEMM
-  t.head_w = add_param(t, "confidence.confidence_layer_1.weight", 6, 6 * hs);
-  add_param(t, "classifier.classifier_layer.weight", c.ncls, 6 * hs);
-  t.head_b = add_param(t, "confidence.confidence_layer_1.bias", 6, 0);
-  add_param(t, "classifier.classifier_layer.bias", c.ncls, 0);
-  for (int i = 0; i < 3; ++i) {
-    t.mod[i].ln_w = add_param(t, std::string(mn[i]) + "layer_norm.weight", 2 * t.mod[i].H, 0);
-    t.mod[i].ln_b = add_param(t, std::string(mn[i]) + "layer_norm.bias", 2 * t.mod[i].H, 0);
-  }
-  const std::string te = "transformer_encoder.layers.0.";
-  t.in_w = add_param(t, te + "self_attn.in_proj_weight", 3 * hs, hs);
-  t.in_b = add_param(t, te + "self_attn.in_proj_bias", 3 * hs, 0);
-  t.out_w = add_param(t, te + "self_attn.out_proj.weight", hs, hs);
-  t.out_b = add_param(t, te + "self_attn.out_proj.bias", hs, 0);
-  t.l1_w = add_param(t, te + "linear1.weight", FFN, hs);
-  t.l1_b = add_param(t, te + "linear1.bias", FFN, 0);
-  t.l2_w = add_param(t, te + "linear2.weight", hs, FFN);
-  t.l2_b = add_param(t, te + "linear2.bias", hs, 0);
-  t.n1_w = add_param(t, te + "norm1.weight", hs, 0);
-  t.n1_b = add_param(t, te + "norm1.bias", hs, 0);
-  t.n2_w = add_param(t, te + "norm2.weight", hs, 0);
-  t.n2_b = add_param(t, te + "norm2.bias", hs, 0);
-  if (c.act == MMDA_ACT_PRELU) t.prelu_a = add_param(t, "activation.weight", 1, 0);      // last of the block: what follows is re-aligned
-  for (int l = 1; l >= 0; --l) {
-    t.flat = (t.flat + 3) & ~(int64_t)3;
-    (l == 1 ? t.rnn2_begin : t.rnn1_begin) = t.flat;
-    for (int i = 0; i < 3; ++i) {
-      ModP& md = t.mod[i];
-      RnnP& r = md.rnn[l];
-      r.H = md.H; r.D = l == 0 ? md.D : 2 * md.H;
-      r.ldD = round_up(r.D, 8); r.ldG = round_up(8 * r.H, 8); r.ldH = round_up(r.H, 8);
-      const int ng = c.rnncell == MMDA_CELL_GRU ? 3 : 4;      // gate blocks per direction in the torch-layout parameters
-      std::string pre = std::string(mn[i]) + "rnn" + (l == 0 ? "1" : "2") + ".";
-      r.w_ih = add_param(t, pre + "weight_ih_l0", ng * r.H, r.D);
-      add_param(t, pre + "weight_ih_l0_reverse", ng * r.H, r.D);
-      r.w_hh[0] = add_param(t, pre + "weight_hh_l0", ng * r.H, r.H);
-      r.w_hh[1] = add_param(t, pre + "weight_hh_l0_reverse", ng * r.H, r.H);
-      r.b_ih = add_param(t, pre + "bias_ih_l0", ng * r.H, 0);
-      add_param(t, pre + "bias_ih_l0_reverse", ng * r.H, 0);
-      r.b_hh = add_param(t, pre + "bias_hh_l0", ng * r.H, 0);
-      add_param(t, pre + "bias_hh_l0_reverse", ng * r.H, 0);
-    }
-  }
-  t.flat = (t.flat + 3) & ~(int64_t)3;
-  t.dense = t.flat;
-  t.embed = add_param(t, "embed.weight", c.vocab, c.d_t);
-  t.flat = (t.flat + 3) & ~(int64_t)3;
-  return t;
-}
-
-// The workspace for (B, T) batches, as a value: sizes one (Workspace::floats) and is what a bound buffer is read through.  Pure: no HIP
-// call, no handle.
-Workspace carve(const mmda_misa_config& c, const ParamTable& par, int B, int T) {
-  const int hs = c.hidden, NC = 6 + c.ncls;
-  const int64_t R = (int64_t)T * B;
-  int64_t cur = 0;
-  auto take = [&cur](int64_t n) { int64_t o = cur; cur += (n + 3) & ~(int64_t)3; return o; };   // 16-B aligned
-  Workspace w{};
-  w.B = B; w.T = T; w.ldR = round_up(B * T, 8);
-  for (int i = 0; i < 3; ++i) {       // exchange buffers of the recurrences first: their offsets depend on B only
-    const ModP& md = par.mod[i]; ModW& mw = w.mod[i];
-    mw.xchg_floats = (mmda_lstm_xchg_bytes(md.H, B) + 3) / 4;
-    mw.xchg = mw.xchg_floats > 0 ? take(mw.xchg_floats) : -1;
-  }
-  for (int i = 0; i < 3; ++i) {
-    const ModP& md = par.mod[i]; ModW& mw = w.mod[i];
-    for (int l = 0; l < 2; ++l) {
-      const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
-      for (int d = 0; d < 2; ++d) {     // sized for the larger (fp32) packing so the mode can be switched in place
-        rw.pack_f[d] = take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 0) / 4);
-        rw.pack_b[d] = take(mmda_lstm_packed_bytes(MMDA_F32, r.H, 1) / 4);
-        rw.pack_c[d] = take(mmda_lstm_packed_bytes(MMDA_BF16, r.H, 2) / 4);
-      }
-    }
-    for (int l = 0; l < 2; ++l) {
-      const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
-      rw.wb = take((int64_t)8 * r.H * r.ldD / 2); rw.wbT = take((int64_t)r.D * r.ldG / 2);
-      rw.xb = take(R * r.ldD / 2); rw.xbT = take((int64_t)r.D * w.ldR / 2);
-      rw.dgb = take(R * r.ldG / 2); rw.dgbT = take((int64_t)8 * r.H * w.ldR / 2);
-      rw.hbT = take((int64_t)2 * r.H * w.ldR / 2);
-      for (int d = 0; d < 2; ++d) rw.hbp[d] = take(R * r.ldH / 2);
-    }
-    if (c.rnncell == MMDA_CELL_GRU) {
-      for (int l = 0; l < 2; ++l) {
-        const RnnP& r = md.rnn[l]; RnnW& rw = mw.rnn[l];
-        rw.pw_ih = take((int64_t)8 * r.H * r.D); rw.pw_hh[0] = take((int64_t)4 * r.H * r.H); rw.pw_hh[1] = take((int64_t)4 * r.H * r.H);
-        rw.pb_ih = take(8 * r.H); rw.pb_hh = take(8 * r.H);
-      }
-    }
-    mw.x = (i == 0) ? take(R * md.D) : -1;
-    for (int l = 0; l < 2; ++l) {
-      mw.gates[l] = take(R * 8 * md.H);
-      mw.c[l] = take((int64_t)T * round_up(B, 4) * 2 * md.H);     // batch-minor-by-4 under the gate-minor layout: rows rounded up
-      mw.hseq[l] = take(R * 2 * md.H);
-    }
-    mw.normed = take(R * 2 * md.H);
-    mw.ln_mean = take(R);
-    mw.ln_rstd = take(R);
-    mw.utt = take((int64_t)B * 4 * md.H);
-    mw.d_utt = take((int64_t)B * 4 * md.H);
-    mw.d_hseq1 = take(R * 2 * md.H);
-    mw.d_normed = take(R * 2 * md.H);
-    mw.d_x = (i == 0) ? take(R * md.D) : -1;
-  }
-  const int64_t BH = (int64_t)B * hs;
-  w.z = take(3 * BH); w.pmean = take(3 * B); w.prstd = take(3 * B);
-  // public outputs (what the reference's solver reads off the module) are contiguous so the host can snapshot them at once
-  w.pub_begin = cur;
-  w.orig = take(3 * BH); w.x6 = take(6 * BH); w.recon = take(3 * BH); w.dom = take((int64_t)3 * B * 3);
-  w.tcp = take((int64_t)B * 6); w.scores = take((int64_t)B * c.ncls); w.labels = take((int64_t)B * c.ncls);
-  w.pub_end = cur;
-  w.rsum = take(3 * BH); w.dom_z = take(3 * BH); w.dom_h = take(3 * BH);
-  w.qkv = take(6 * BH * 3); w.probs = take((int64_t)B * NHEAD * S6 * S6); w.ctx = take(6 * BH);
-  w.attn_out = take(6 * BH); w.ln1_mean = take(6 * B); w.ln1_rstd = take(6 * B); w.x1 = take(6 * BH);
-  w.f1 = take((int64_t)6 * B * FFN); w.f2 = take(6 * BH); w.ln2_mean = take(6 * B); w.ln2_rstd = take(6 * B);
-  w.hfused = take(6 * BH); w.logits = take((int64_t)B * NC);
-  w.x1q = take(6 * BH / 4); w.x1s = take(6 * BH / 128 + 4); w.w1q = take((int64_t)FFN * hs / 4); w.w1s = take((int64_t)FFN * hs / 128 + 4);
-  w.f1q = take((int64_t)6 * B * FFN / 4); w.f1s = take((int64_t)6 * B * FFN / 128 + 4);
-  w.w2q = take((int64_t)hs * FFN / 4); w.w2s = take((int64_t)hs * FFN / 128 + 4);
-  w.diff_work = take(mmda_loss_diff_work_floats(B, hs));
-  w.ffn_parts = take((int64_t)(FFN / 32) * 6 * BH);      // partial products of the hidden-sliced feed-forward kernels (fused_rows.hip)
-  w.ln_parts = take((int64_t)512 * 2 * 2 * (par.mod[0].H + par.mod[1].H + par.mod[2].H));   // <= 512 block partials of the three inter-layer LayerNorms' gamma / beta gradients (norm.hip)
-  w.rec_part = take(3 * BH);                             // d_recon W_rec, made beside the backward pass's first stretch for its third (fused_rows.h)
-  w.esort = take(2 * (int64_t)B * T + 64);              // sorted (id, position) list of the step's text ids (embed_rows.hip)
-  w.pg_parts = take((int64_t)B * FUSED_PG_SLOTS * 2 * 128);      // per-sample LayerNorm gamma / beta gradient partials of the fused backward stretches
-  w.head_wT = take((int64_t)6 * hs * NC); w.l2_wT = take((int64_t)FFN * hs); w.l1_wT = take((int64_t)hs * FFN);
-  w.out_wT = take((int64_t)hs * hs); w.in_wT = take((int64_t)hs * 3 * hs); w.rec_wT = take((int64_t)3 * hs * hs);
-  w.priv_wT = take((int64_t)3 * hs * hs); w.sh_wT = take((int64_t)hs * hs);
-  if (!c.use_cmd_sim) { w.d1_wT = take((int64_t)hs * hs); w.d2_wT = take((int64_t)hs * 3); }
-  for (int i = 0; i < 3; ++i) w.pwT[i] = take((int64_t)4 * par.mod[i].H * hs);
-  w.gpad_begin = cur;
-  if (c.rnncell == MMDA_CELL_GRU) {
-    for (int i = 0; i < 3; ++i)
-      for (int l = 0; l < 2; ++l) {
-        const RnnP& r = par.mod[i].rnn[l]; RnnW& rw = w.mod[i].rnn[l];
-        rw.gw_ih = take((int64_t)8 * r.H * r.D); rw.gw_hh[0] = take((int64_t)4 * r.H * r.H); rw.gw_hh[1] = take((int64_t)4 * r.H * r.H);
-        rw.gb = take(8 * r.H);
-      }
-  }
-  w.gpad_end = cur;
-  // ---- the loss sums and the activation gradients seeded by the losses (zeroed every step by ONE memset, contiguous)
-  w.zero_begin = cur;
-  w.losses = take(8);
-  w.d_tcp = take((int64_t)B * 6); w.d_x6 = take(6 * BH); w.d_dom = take((int64_t)3 * B * 3);
-  w.zero_cls = cur;                       // (a step whose forward stores these seeds itself clears up to here only)
-  w.d_scores = take((int64_t)B * c.ncls);
-  w.zero_recon = cur;
-  w.d_orig = take(3 * BH); w.d_recon = take(3 * BH);
-  w.zero_end = cur;
-  // ---- fully overwritten gradients
-  w.d_logits = take((int64_t)B * NC); w.d_hfused = take(6 * BH); w.d_x1 = take(6 * BH); w.d_f2 = take(6 * BH);
-  w.d_f1 = take((int64_t)6 * B * FFN); w.d_attn_out = take(6 * BH); w.d_ctx = take(6 * BH);
-  w.d_qkv = take(6 * BH * 3); w.d_z = take(3 * BH); w.d_dom_h = take(3 * BH); w.d_dom_z = take(3 * BH);
-  // ---- clip_norm: the gradient norm and its clip coefficient, and the norm launch's block partials (doubles, two floats each)
-  w.gnorm = take(4); w.gnorm_parts = take(2 * mmda_grad_norm_partials(INT64_MAX));
-  w.floats = cur;
-  return w;
-}
-
-// The names mmda_misa_tensor_offset answers to (include/mmda_hip.h lists them)
-struct TensorName { const char* name; int64_t (*off)(const Workspace&); };
-#define TENSOR(name, expr) {name, [](const Workspace& w) -> int64_t { return w.expr; }}
-const TensorName kTensorNames[] = {
-    TENSOR("scores", scores), TENSOR("labels", labels), TENSOR("tcp", tcp), TENSOR("logits", logits), TENSOR("hfused", hfused),
-    TENSOR("x6", x6), TENSOR("orig", orig), TENSOR("recon", recon), TENSOR("dom", dom), TENSOR("losses", losses),
-    TENSOR("grad_norm", gnorm), TENSOR("utt_t", mod[0].utt), TENSOR("utt_v", mod[1].utt), TENSOR("utt_a", mod[2].utt),
-    TENSOR("d_scores", d_scores), TENSOR("d_tcp", d_tcp), TENSOR("d_x6", d_x6), TENSOR("d_orig", d_orig), TENSOR("d_recon", d_recon),
-    TENSOR("d_dom", d_dom), TENSOR("pub_begin", pub_begin), TENSOR("pub_end", pub_end), TENSOR("zero_begin", zero_begin),
-    TENSOR("zero_end", zero_end), TENSOR("hseq1_t", mod[0].hseq[0]), TENSOR("hseq1_v", mod[1].hseq[0]), TENSOR("hseq1_a", mod[2].hseq[0]),
-    TENSOR("d_x_t", mod[0].d_x),      // gradient w.r.t. the gathered embedding rows (T*B, d_t): the sparse form of embed.weight.grad
-    TENSOR("xchg_t", mod[0].xchg), TENSOR("xchg_v", mod[1].xchg), TENSOR("xchg_a", mod[2].xchg)};   // word 0 of each = its abort word
-#undef TENSOR
+// What one forward pass is asked to be: the parameters of that call, handed down to it (the handle keeps settings and outcomes)
+struct StepRequest {
+  bool fused = false;            // called from train_step: eager side losses, flag joins, the bucket clear rides inside forward
+  const float* emo = nullptr;    // labels of a fused step (loss seeds stored by the forward stretches)
+  const OptStep* opt = nullptr;  // the optimizer step behind this pass, where its kind may start early work (background table pass)
+  bool enc_cached = false;       // the forward starts behind the encoders
+};
 
 }  // namespace
 
@@ -416,7 +100,6 @@ struct mmda_misa {
   int bg_on = -1, bg_wgs = 0;                // mmda_misa_set_embed_background; -1 / 0: MMDA_EMBED_BG's / MMDA_EMBED_BG_WGS's (else the default)
   // (the pass's workgroups hold LDS they never touch, MMDA_EMBED_BG_LDS bytes: a resident recurrence reserves the whole LDS of its CUs,
   //  so the two never share a CU -- sharing one cost each forward recurrence 24 us of its hand-offs at any throttle)
-  const OptStep* bg_step = nullptr;          // train_step: the optimizer step of the step in flight, where its kind may run the pass
   int bg_pending = 0, bg_active = 0;         // the pass went out and is not joined yet; the last train_step ran it
   // Flag joins (training step; common.h: flag_wait): where the main stream needs a side-stream chain's results, the consuming KERNEL
   // waits on the device for a word that a one-thread launch behind the chain sets, instead of the stream waiting for an event -- an
@@ -435,11 +118,10 @@ struct mmda_misa {
   StepPlan plan;                             // its decisions (plan_step)
   int64_t early_floats = 0; int early_valid = 0;
   // fused train step without a gradient exchange: clamp+Adam of the bucket prefix whose gradients are final beside the layer-1 backward
-  // recurrence runs there, on the side stream (Pass::early); how far that pass of the last backward got
+  // recurrence runs there, on the side stream (Pass::opt); how far that pass of the last backward got
   int64_t adam_early_done = 0;
   int wT_valid = 0;                // the K-major fusion-weight copies in the workspace are this step's
   int wT_pending = 0;              // the K-major fusion-weight copies of this step are still to be made (on the next fork)
-  int enc_cached = 0;              // the forward being planned starts behind the encoders (set by the *_encoded entry points, cleared by mmda_misa_forward)
   // sparse mode, backward without an optimizer step behind it (do_adam = 0, the autograd path): the pass stops at d_x_t and
   // mmda_misa_adam_step applies the rows update from the id list / lengths of that backward (the caller keeps them alive, as it does
   // for backward itself)
@@ -451,15 +133,14 @@ struct mmda_misa {
   unsigned epoch = 1;              // monotonic cluster-exchange epoch (never reset; see lstm_resident.h)
   int side_pending = 0;
   int zero_grad_pending = 0;       // train_step: the gradient bucket is cleared inside forward(), beside the fusion block
-  // train_step: the losses that read only the private/shared representations (diff, CMD) are issued by forward() on the side
-  // stream as soon as those exist, beside the transformer layer and the heads; mmda_misa_losses() then adds the rest
-  int eager_losses = 0, eager_done = 0;      // eager_done: that chain, and any loss seeds, not yet taken up by mmda_misa_losses
+  // train_step (StepPlan::fused): the losses that read only the private/shared representations (diff, CMD) are issued by forward() on
+  // the side stream as soon as those exist, beside the transformer layer and the heads; mmda_misa_losses() then adds the rest
+  int eager_done = 0;                        // that chain, and any loss seeds, not yet taken up by mmda_misa_losses
   // Loss seeds (training step, fused row-local stretches): the forward stretches store the gradient seeds of the reconstruction loss
   // (d_recon, d_orig) and -- without ConfidNet, whose loss adds into the same buffer -- of the classification loss (d_scores) where
   // they produce recon / scores, so the launch that computes cls / conf / recon and the weighted total has no gradient to seed and
   // leaves the critical path between the forward and the backward pass (14 us at B=32): it runs on the side stream beside the
   // layer-2 backward recurrence.  Values are bit-identical to the loss launch's (same expressions on the same operands).
-  const float* emo_eager = nullptr;          // labels of the step in flight (train_step)
   const float* misc_deferred = nullptr;      // labels: the loss-value launch is still to be issued (backward's first side fork)
   unsigned jval[2] = {0u, 0u};               // the values the flag-join words [0], [1] were last set to
   // The sort-based embedding scatter of a large batch in two halves: the sorted (id, position) list depends on the ids only and is
@@ -530,7 +211,6 @@ void lin_dw(Ctx& c, int mode, int M, int N, int K, const float* dy, const float*
 }
 
 // ---- row-skinny forms (fusion block at B <= SKINNY_MAX_B): see gemm_skinny.hip
-constexpr int SKINNY_MAX_B = 256;
 // y(M,N) = act(x(M,K) W(N,K)^T + b)
 mmda_skinny_args sk_nt(int M, int N, int K, const float* x, int ldx, const float* W, const float* b, float* y, int ldy, int act = 0) {
   mmda_skinny_args g = {};
@@ -661,13 +341,13 @@ TableRows bg_table(const mmda_misa* m) { return TableRows{m->row_stamp, m->bg_ep
 AdamHyper bg_hyper(const mmda_misa* m, const OptStep& o) {
   return AdamHyper{o.lr, m->adam.beta1, m->adam.beta2, m->adam.eps, o.clip, o.grad_scale, o.step, m->adam.weight_decay, m->adam.decoupled, nullptr};
 }
-// the fork and the pass: behind everything `main_stream` holds
-int bg_launch(mmda_misa* m, void* main_stream) {
-  if (!m->bg_step || !m->bg || !m->row_stamp) return MMDA_EINVAL;
+// the fork and the pass (the step's optimizer step: `opt`): behind everything `main_stream` holds
+int bg_launch(mmda_misa* m, const OptStep* opt, void* main_stream) {
+  if (!opt || !m->bg || !m->row_stamp) return MMDA_EINVAL;
   if (hipEventRecord(m->ev_bg_fork, (hipStream_t)main_stream) != hipSuccess) return MMDA_ELAUNCH;
   if (hipStreamWaitEvent(m->bg, m->ev_bg_fork, 0) != hipSuccess) return MMDA_ELAUNCH;
   const int64_t e = m->par.embed;
-  const int rc = mmda_adam_background_launch(m->P + e, m->M1 + e, m->V1 + e, bg_table(m), bg_hyper(m, *m->bg_step), m->plan.embed_bg_wgs,
+  const int rc = mmda_adam_background_launch(m->P + e, m->M1 + e, m->V1 + e, bg_table(m), bg_hyper(m, *opt), m->plan.embed_bg_wgs,
                                              m->plan.embed_bg_lds, m->bg);
   if (rc) return rc;
   m->bg_pending = 1; m->bg_active = 1;                   // (from here on rows may have taken the step, whatever the step returns)
@@ -850,99 +530,28 @@ int apply_trainable(mmda_misa* m, const unsigned char* flags) {
   return MMDA_OK;
 }
 
-constexpr int FJ_DEVICE_MAX_B = 64;     // the forward flag join is waited for on the device up to this batch (Pass::bwd_fusion_fused)
-// the background pass over the embedding table: on or off, and its workgroups, where nothing else says (measured: DESIGN section 4a)
-constexpr int kEmbedBgDefault = 1, kEmbedBgWorkgroups = 32, kEmbedBgLds = 1024, kEmbedBgMaxB = 32;
-
-// the decisions of one step (see StepPlan); the switches that select a form of the step are read here only
-StepPlan plan_step(mmda_misa* m) {
-  static const int tn_on = mmda_env_int("MMDA_GEMM_TN", 1);
-  static const int wt_merge = mmda_env_int("MMDA_WT_MERGE", 1);
-  static const int row_fuse_on = mmda_env_int("MMDA_ROW_FUSE", 1);
-  static const int ffn_fuse_on = mmda_env_int("MMDA_FFN_FUSE", 1);
-  static const int loss_seeds_on = mmda_env_int("MMDA_LOSS_SEEDS", 1);
-  static const int flag_join_on = mmda_env_int("MMDA_FLAG_JOIN", 1);
-  static const int zg_side = mmda_env_int("MMDA_ZERO_GRAD_SIDE", -1);
-  static const int fsplit = mmda_env_int("MMDA_FUSED_SPLIT", 1);
-  static const int sort_early = mmda_env_int("MMDA_SORT_EARLY", 1);
-  static const int bg_on = mmda_env_int("MMDA_EMBED_BG", kEmbedBgDefault);
-  static const int bg_wgs = mmda_env_int("MMDA_EMBED_BG_WGS", 0);
-  static const int bg_late = mmda_env_int("MMDA_EMBED_BG_LATE", 0);
-  static const int bg_lds = mmda_env_int("MMDA_EMBED_BG_LDS", kEmbedBgLds);
-  const mmda_misa_config& c = m->cfg;
-  const int B = m->lay.B, T = m->lay.T, mode = c.mode;
-  StepPlan P;
-  // which recurrent kernels will run: decides the packings of W_hh that are made and the layout of `gates`
-  auto probe_resident = [&](int gate_minor, int backward) -> bool {
-    if (T <= 0 || mode != MMDA_BF16) return false;
-    mmda_lstm_desc probe[3];
-    for (int i = 0; i < 3; ++i) probe[i] = lstm_desc(m, i, 0, false, gate_minor, true);
-    if (backward == 2) return mmda_lstm_bwd_emits_dg_bf16(mode, 3, probe, B, T) != 0;      // ... and writes the gate gradients as bf16
-    return mmda_lstm_resident_applicable(mode, 3, probe, B, T, backward) != 0;
-  };
-  P.inf = m->inference != 0;
-  P.enc_cut = !P.inf && encoder_cut(m);
-  P.enc_nostash = P.inf || (P.enc_cut && !m->cut_keep_stash);
-  P.enc_cached = m->enc_cached != 0;
-  P.bfg = mode == MMDA_BF16 && m->use_bf16_gemm;
-  // Gate-minor layout of the pre-activations / stash / gate gradients ([dir][unit][gate], 16-byte accesses in the recurrent
-  // kernels): possible when the bf16 GEMMs produce and consume them (the interleave rides on the W_ih conversion and on the
-  // GEMM epilogues) AND the resident-weights kernels will run, forward and backward.
-  if (P.bfg && (B % 8) == 0 && T > 0) P.gm = probe_resident(1, 0) && probe_resident(1, 1);
-  // The backward probe with the backward pass's own descriptors gives the same answer: they differ from these only in pointers
-  // (pack_b, d_utt, d_hseq) and in wpack_c, which the backward pass sets because want_c holds -- bf16, resident, training -- and
-  // without which probe_resident(1, 2) fails anyway (no exchange buffers without use_cluster).
-  P.kdg = !P.enc_nostash && P.bfg && P.gm && probe_resident(1, 2);
-  // Weight gradients in the tn form of the bf16 GEMM (dW = dG^T X on row-major dG, X, hseq): the transposed copies of the inputs, of
-  // hseq and of the gate gradients are not made at all (B=256: 0.33 ms of conversions per step).  Needs the gate gradients as bf16
-  // from the recurrent kernel (gate-minor resident path).  Up to T*B = 4096 rows: measured (step, ms) B=32 0.759 -> 0.745, B=64 0.928 ->
-  // 0.917, but B=128 1.362 -> 1.391, B=256 2.39 -> 2.55, T=500 4.06 -> 4.08 -- in isolation the tn kernel matches the nt one at K = 1600
-  // and runs 15 - 20 % slower at K = 12800 (twice the LDS read instructions per k-tile), which at large batches outweighs the
-  // conversions it saves.  Round 3: the LDS-DMA pipelined GEMM (gemm_bf16_dma_kernel) runs the tn form at K = 12800 as fast as the nt
-  // form, so both layers take it at every size (B=256: the 0.47 ms of transposing conversions per step with it; a row limit, with or
-  // without layer 1 alone in the tn form beyond it, measured slower).  MMDA_GEMM_TN=0: the transposed-copy (nt) form everywhere.
-  P.tn_wgrad = P.kdg && tn_on;
-  // The forward packing always; the resident-weights backward packing when those kernels will run the backward pass and the
-  // streaming backward packing only when they will not; neither for a pass whose encoders keep no stash.
-  P.want_c = !P.enc_nostash && m->use_cluster && mode == MMDA_BF16;
-  P.want_b = !P.enc_nostash && !(P.want_c && probe_resident(0, 1));
-  P.skinny = B <= SKINNY_MAX_B;
-  P.want_wT = P.skinny && !P.inf;
-  P.wT_merge = P.bfg && P.want_wT && wt_merge;
-  // The row-local stretches as one launch each (fused_rows.hip): recon + qkv -> attention -> out-proj -> LayerNorm 1, and LayerNorm 2
-  // -> heads; backward: heads' sigmoid' -> d_hfused -> LayerNorm 2, and LayerNorm 1 -> ... -> the projection LayerNorms.
-  // MMDA_ROW_FUSE=0: the launches they replace (4 and 3 forward, 3 and 6 backward).
-  P.row_fuse = P.skinny && row_fuse_on && c.use_cmd_sim && c.hidden == 128 && NHEAD == 2;
-  // The feed-forward pair as one launch split over the hidden units.  The fp8 forward (fusion_fp8) has products of its own, but the
-  // backward pass reads the f32 f1 / f2 it writes like the exact path's, so the fused dX kernel serves it as well.
-  P.ffn_fuse_fwd = P.row_fuse && ffn_fuse_on && !m->fusion_fp8 && (FFN % 32) == 0;
-  P.ffn_fuse_bwd = P.row_fuse && ffn_fuse_on && (FFN % 32) == 0;
-  // loss seeds by the stretches (see mmda_misa::emo_eager); MMDA_LOSS_SEEDS=0: by the loss launch behind the forward pass, as before
-  P.seed_recon = loss_seeds_on && P.row_fuse && m->eager_losses && m->emo_eager;
-  P.seed_cls = P.seed_recon && !c.use_confidNet;
-  // flag joins (see mmda_misa::jflags) in a fused training step (train_step sets eager_losses around its forward pass)
-  P.fj_on = flag_join_on && m->use_side && m->eager_losses;
-  P.fj_fwd = P.fj_on && P.seed_recon && P.seed_cls;
-  P.fj_device = P.fj_fwd && B <= FJ_DEVICE_MAX_B;
-  P.zg_here = zg_side >= 0 ? zg_side != 0 : P.fj_device;
-  P.rec_hoisted = fsplit && m->lay.rec_part >= 0 && B <= 64;
-  P.embed_update = m->embed_update;
-  P.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
-  P.sort_early = sort_early && T > 0 && m->lay.esort >= 0 && mmda_embed_scatter_sorts(T * B) && P.embed_update != EU_FROZEN && !P.enc_cut;
-  // The background pass: a fused step from a batch with the native Adam behind it and no norm clip (bg_step: train_step), a plain
-  // dense table, nothing frozen (no run table).  Not under clip_norm: a non-finite norm poisons the zero gradients of the dense launch
-  // too, and that must stay so.  The table is whole quads and fewer than 2^31 floats (the walkers' index arithmetic).
-  // Where it pays (measured): up to one 32-sample batch group of the resident recurrences, which then hold 152 of the
-  // CUs; from the second group on they want every CU, and the pass's workgroups -- which keep off a recurrence's CUs by holding LDS --
-  // delay their placement (B=64: 0.763 -> 0.816 ms).  MMDA_EMBED_BG=2, or the handle's own switch: wherever the step is eligible.
-  const int bg_switch = m->bg_on >= 0 ? (m->bg_on ? 2 : 0) : bg_on;
-  const int64_t tab = (int64_t)c.vocab * c.d_t;
-  P.embed_bg = bg_switch != 0 && (bg_switch >= 2 || B <= kEmbedBgMaxB) && m->bg_step && !P.enc_cached && !P.enc_cut && P.embed_update == EU_DENSE &&
-               !P.embed_deferred && !masked(m) && T > 0 && m->M1 && m->V1 && tab > 0 && (tab & 3) == 0 && tab < ((int64_t)1 << 31);
-  P.embed_bg_late = bg_late != 0;
-  P.embed_bg_lds = std::max(0, std::min(65536, bg_lds));
-  P.embed_bg_wgs = std::min(4096, m->bg_wgs > 0 ? m->bg_wgs : bg_wgs > 0 ? bg_wgs : kEmbedBgWorkgroups);
-  return P;
+// the process's switches that select a form of the step: read here, once, and nowhere else in this file
+const StepSwitches& step_switches() {
+  static const StepSwitches d, sw = {
+      mmda_env_int("MMDA_GEMM_TN", d.gemm_tn), mmda_env_int("MMDA_WT_MERGE", d.wt_merge), mmda_env_int("MMDA_ROW_FUSE", d.row_fuse),
+      mmda_env_int("MMDA_FFN_FUSE", d.ffn_fuse), mmda_env_int("MMDA_LOSS_SEEDS", d.loss_seeds), mmda_env_int("MMDA_FLAG_JOIN", d.flag_join),
+      mmda_env_int("MMDA_ZERO_GRAD_SIDE", d.zero_grad_side), mmda_env_int("MMDA_FUSED_SPLIT", d.fused_split),
+      mmda_env_int("MMDA_SORT_EARLY", d.sort_early), mmda_env_int("MMDA_EMBED_BG", d.embed_bg), mmda_env_int("MMDA_EMBED_BG_WGS", d.embed_bg_wgs),
+      mmda_env_int("MMDA_EMBED_BG_LATE", d.embed_bg_late), mmda_env_int("MMDA_EMBED_BG_LDS", d.embed_bg_lds)};
+  return sw;
+}
+// what plan_step is given for a pass over (B, T) batches: the handle's settings and the request, as values
+PlanInput plan_input(const mmda_misa* m, const StepRequest& r, int B, int T) {
+  PlanInput in = {};
+  in.cfg = m->cfg; in.B = B; in.T = T;
+  for (int i = 0; i < 3; ++i) { in.H[i] = m->par.mod[i].H; in.xchg[i] = mmda_lstm_xchg_bytes(in.H[i], B) > 0; }
+  in.use_side = m->use_side != 0; in.use_cluster = m->use_cluster != 0; in.use_bf16_gemm = m->use_bf16_gemm != 0;
+  in.inference = m->inference != 0; in.fusion_fp8 = m->fusion_fp8 != 0;
+  in.embed_update = m->embed_update; in.embed_deferred = m->embed_update == EU_DENSE && m->df_row_step != nullptr;
+  in.masked = masked(m); in.encoder_cut = encoder_cut(m); in.cut_keep_stash = m->cut_keep_stash != 0;
+  in.bg_on = m->bg_on; in.bg_wgs = m->bg_wgs; in.moments = m->M1 && m->V1;
+  in.fused = r.fused; in.has_labels = r.emo != nullptr; in.has_opt = r.opt != nullptr; in.enc_cached = r.enc_cached;
+  return in;
 }
 
 }  // namespace
@@ -997,6 +606,21 @@ extern "C" int64_t mmda_misa_workspace_floats(const mmda_misa* m, int B, int T) 
   if (!m || B <= 0 || T <= 0) return MMDA_EINVAL;
   return carve(m->cfg, m->par, B, T).floats;
 }
+// The plan a forward pass over (B, T) batches would get: host only, no workspace needed, the switches given instead of read
+extern "C" int mmda_misa_plan_describe(const mmda_misa* m, int B, int T, const mmda_misa_step_request* req, const int* switches,
+                                       int n_switches, mmda_misa_step_plan* out) {
+  if (!m || !req || !out || B <= 0 || T <= 0 || (switches && n_switches != MMDA_MISA_STEP_SWITCHES)) return MMDA_EINVAL;
+  static const float labels = 0.f; static const OptStep opt = {};      // stand for "given": plan_input tests the pointers only
+  const StepRequest r{req->fused != 0, req->has_labels ? &labels : nullptr, req->has_opt_step ? &opt : nullptr, req->enc_cached != 0};
+  StepSwitches sw;
+  if (switches) memcpy(&sw, switches, sizeof(sw));
+  const StepPlan P = plan_step(plan_input(m, r, B, T), sw);
+  *out = mmda_misa_step_plan{P.fused, P.inf, P.enc_cut, P.enc_nostash, P.enc_cached, P.bfg, P.gm, P.kdg, P.tn_wgrad, P.want_b, P.want_c,
+                             P.want_wT, P.wT_merge, P.skinny, P.row_fuse, P.ffn_fuse_fwd, P.ffn_fuse_bwd, P.seed_recon, P.seed_cls, P.fj_on,
+                             P.fj_fwd, P.fj_device, P.zg_here, P.rec_hoisted, P.sort_early, P.embed_update, P.embed_deferred, P.embed_bg,
+                             P.embed_bg_late, P.embed_bg_wgs, P.embed_bg_lds};
+  return MMDA_OK;
+}
 namespace {
 // abort words of the CURRENT exchange regions -> abort_sticky (synchronous device->host copies)
 int harvest_abort(mmda_misa* m) {
@@ -1037,9 +661,7 @@ extern "C" int mmda_misa_set_workspace(mmda_misa* m, float* ws, int64_t floats, 
 }
 extern "C" int64_t mmda_misa_tensor_offset(const mmda_misa* m, const char* name) {
   if (!m || !name || !m->ws) return -1;             // (no workspace bound yet: no name has an offset)
-  for (const TensorName& t : kTensorNames)
-    if (!strcmp(t.name, name)) return t.off(m->lay);
-  return -1;
+  return tensor_offset(m->lay, name);
 }
 extern "C" int mmda_misa_set_mode(mmda_misa* m, int mode) {
   if (!m || (mode != MMDA_F32 && mode != MMDA_BF16)) return MMDA_EINVAL;
@@ -1149,7 +771,8 @@ int backward_only_jobs(mmda_misa* m, mmda_convert_job* cj) {
 // side stream, right after x6 = [private x3, shared x3] exists: clear the loss sums and the loss-seeded activation gradients,
 // then DiffLoss and CMD with their gradients (they read x6 only), then the gradient bucket if train_step left that to forward()
 int eager_side_losses(mmda_misa* m, void* stream) {
-  if (!m->eager_losses) return MMDA_OK;
+  const StepPlan& P = m->plan;
+  if (!P.fused) return MMDA_OK;
   const mmda_misa_config& c = m->cfg; const Workspace& w = m->lay;
   const int B = w.B, hs = c.hidden;
   const int64_t BH = (int64_t)B * hs;
@@ -1158,7 +781,6 @@ int eager_side_losses(mmda_misa* m, void* stream) {
   // (large batches: the loss chain on the side stream is the longer one by far -- the weight transposes go to the main stream)
   if (!rc && m->wT_pending) rc = weight_transposes(m, B >= 128 ? stream : ss);
   // (the forward stretches on the main stream STORE the seeds they own: clearing those here would race with them)
-  const StepPlan& P = m->plan;
   const int64_t zend = P.seed_cls ? w.zero_cls : P.seed_recon ? w.zero_recon : w.zero_end;
   // The gradient bucket (43 MB, 11 us) is cleared on the MAIN stream behind the fork: since the row-local stretches were fused the
   // side stream's loss chain (72 us at B=32), not the main stream's fusion block (55 us), is what the join at the end of forward() waits
@@ -1367,10 +989,12 @@ struct Pass : Ctx {
   const int B, T, R, hs, NC, mode;
   static constexpr int fmode = MMDA_F32;     // the fusion block's GEMMs: exact path (see mmda_misa_forward)
   const int64_t BH; const float p_tf, p_cls; const uint64_t seed;
-  const OptStep* early = nullptr;            // backward of a fused step: the optimizer step this pass may start (see bwd_encoder_layer)
-  Pass(mmda_misa* m_, void* s_)
+  // StepRequest::emo and ::opt of the pass.  opt, forward: its kind may run the background pass over the table (fwd_operands);
+  // backward of a fused step: the optimizer step this pass may start (see bwd_encoder_layer)
+  const float* emo; const OptStep* opt;
+  Pass(mmda_misa* m_, void* s_, const float* emo_ = nullptr, const OptStep* opt_ = nullptr)
       : Ctx{m_, s_}, P(m_->plan), c(m_->cfg), p(m_->par), w(m_->lay), B(w.B), T(w.T), R(w.T * w.B), hs(c.hidden), NC(6 + c.ncls), mode(c.mode),
-        BH((int64_t)B * hs), p_tf(m_->training ? c.fusion_dropout : 0.f), p_cls(m_->training ? c.dropout : 0.f), seed(m_->seed) {}
+        BH((int64_t)B * hs), p_tf(m_->training ? c.fusion_dropout : 0.f), p_cls(m_->training ? c.dropout : 0.f), seed(m_->seed), emo(emo_), opt(opt_) {}
   mmda_ln_args proj_ln_fwd(int i), norm1_fwd(), norm2_fwd();             // LayerNorm arguments (builders below)
   mmda_ln_bwd_args proj_ln_bwd(int i), norm1_bwd(), norm2_bwd();
   // forward, in this order: operands, layers 1 and 2, the fusion block in one of two forms
@@ -1498,7 +1122,7 @@ void Pass::fwd_operands(const int64_t* t_ids, const float* const* xin) {
     if (!rc) rc = mmda_embed_gather_stamped(PP(p.embed), t_ids, R, m->cfg.d_t, WS(w.mod[0].x), P.embed_bg ? &st : nullptr, s);
   }
   // the background pass over the table rows this batch does not index: forked here, behind the launch that stamped the others
-  if (!rc && P.embed_bg && !P.embed_bg_late) rc = bg_launch(m, s);
+  if (!rc && P.embed_bg && !P.embed_bg_late) rc = bg_launch(m, opt, s);
 }
 
 // encoder layer l: input GEMM and recurrence of the three modalities; then layer 1's LayerNorm, or layer 2's fork beside the fusion block
@@ -1532,7 +1156,7 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
   rc = mmda_lstm_fwd(mode, 3, desc, B, T, lengths, s);
   ev_rec(m, m->ev_fwd, l, 1, s);
   if (rc) return;
-  if (l == 0 && P.embed_bg && P.embed_bg_late) { rc = bg_launch(m, s); if (rc) return; }     // (MMDA_EMBED_BG_LATE=1: the later fork)
+  if (l == 0 && P.embed_bg && P.embed_bg_late) { rc = bg_launch(m, opt, s); if (rc) return; }     // (MMDA_EMBED_BG_LATE=1: the later fork)
   if (l == 0) {
     mmda_ln_args ln[3];
     for (int i = 0; i < 3; ++i) {
@@ -1550,13 +1174,13 @@ void Pass::fwd_encoder_layer(int l, const float* const* xin, const int32_t* leng
     if (P.bfg && (P.enc_nostash || P.tn_wgrad))
       for (int i = 0; i < 3; ++i) ln[i].y = nullptr;
     rc = mmda_layernorm_fwd_multi(ln, 3, s);
-  } else if (!m->eager_losses && ((P.bfg && !P.enc_nostash) || m->zero_grad_pending || m->wT_pending)) {
+  } else if (!P.fused && ((P.bfg && !P.enc_nostash) || m->zero_grad_pending || m->wT_pending)) {
     // side stream, beside the fusion block: the gradient bucket is cleared (train_step) and hseq^T of layer 2 is made for its
     // dW_hh.  Joined at the end of forward(), so everything the backward pass issues on either stream is ordered behind both.
     void* ss = nullptr;
     rc = side_fork(m, s, &ss);
     if (!rc && m->wT_pending) rc = weight_transposes(m, ss);
-    if (!rc && m->zero_grad_pending && !m->eager_losses) { rc = mmda_misa_zero_grad(m, ss); m->zero_grad_pending = 0; }
+    if (!rc && m->zero_grad_pending && !P.fused) { rc = mmda_misa_zero_grad(m, ss); m->zero_grad_pending = 0; }
   }
 }
 
@@ -1643,7 +1267,7 @@ void Pass::fwd_fusion_skinny() {
       f.hfused = WS(w.hfused); f.head_w = PP(p.head_w); f.head_b = PP(p.head_b); f.logits = WS(w.logits);
       f.threshold = c.threshold; f.tcp = WS(w.tcp); f.scores = WS(w.scores); f.labels = WS(w.labels);
       f.p_cls = p_cls; f.seed = seed; f.site_cls = SITE_CLS; f.reg = m->reg;
-      if (P.seed_cls) { f.emo = m->emo_eager; f.d_scores = WS(w.d_scores); f.cls = cls_term_of(m->cls()); }
+      if (P.seed_cls) { f.emo = emo; f.d_scores = WS(w.d_scores); f.cls = cls_term_of(m->cls()); }
       rc = mmda_fused_fwd_c(&f, s);
     }
   } else {
@@ -1740,11 +1364,11 @@ bool encoded_batch_ok(const mmda_misa* m, const mmda_encoded_batch* eb) {
 // deferred table's catch-up, fwd_operands, both encoder layers and the cluster epochs they advance (no recurrence is launched).  What
 // fwd_operands does for the REST of the step is kept: the K-major fusion-weight copies take the wT_pending route -- the first fork, or
 // the tail above -- in both precisions, since the conversion launch they ride in the bf16 mode does not exist here.
-int forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed, void* stream) {
+int forward_encoded(mmda_misa* m, const StepRequest& req, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed,
+                    void* stream) {
   m->training = training; m->seed = seed;
-  m->enc_cached = 1;
-  m->plan = plan_step(m);
-  Pass x(m, stream);
+  m->plan = plan_step(plan_input(m, req, m->lay.B, m->lay.T), step_switches());
+  Pass x(m, stream, req.emo, req.opt);
   m->wT_valid = 0;
   m->wT_pending = m->plan.want_wT ? 1 : 0;
   x.rc = mmda_encoded_gather(eb->tab_t, eb->tab_v, eb->tab_a, 4 * m->par.mod[0].H, 4 * m->par.mod[1].H, 4 * m->par.mod[2].H,
@@ -1753,24 +1377,16 @@ int forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, 
   if (x.rc) return x.rc;
   return forward_from_projections(x, stream);
 }
-}  // namespace
 
-extern "C" int mmda_misa_forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, int training, uint64_t seed, void* stream) {
-  if (check_ready(m) || !encoded_batch_ok(m, eb)) return MMDA_EINVAL;
-  // a training forward: utt would need a gradient path that nobody computes
-  if (!m->inference && !encoder_cut(m)) return MMDA_EINVAL;
-  return forward_encoded(m, eb, nullptr, training, seed, stream);
-}
-
-extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
-                                 int training, uint64_t seed, void* stream) {
+// The forward pass from a batch, as `req` asks for it (mmda_misa_forward: StepRequest{}; train_step: its own)
+int forward_pass(mmda_misa* m, const StepRequest& req, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                 int training, uint64_t seed, void* stream) {
   if (check_ready(m) || !t_ids || !v || !a || !lengths) return MMDA_EINVAL;
-  m->enc_cached = 0;
   // The fusion block (projections, private/shared/recon, transformer layer, heads) is 2 % of the FLOPs and feeds the
   // batch-statistic losses: it always runs on the exact f32 MFMA path.  `mode` (bf16) covers the LSTM GEMMs + recurrences.
   m->training = training; m->seed = seed;
-  m->plan = plan_step(m);
-  Pass x(m, stream);
+  m->plan = plan_step(plan_input(m, req, m->lay.B, m->lay.T), step_switches());
+  Pass x(m, stream, req.emo, req.opt);
   if (is_gru(m)) {          // GRU parameters -> four-slot layout (everything below reads the padded copies)
     mmda_gru_pad_job gj[MMDA_GRU_PAD_MAX];
     int n = gru_jobs(m, m->P, false, gj);
@@ -1790,6 +1406,19 @@ extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float
   if (x.rc) return x.rc;
   if (!m->ev.empty()) { if (m->ev_seen_f % m->ev_stride == 0) m->ev_fwd++; m->ev_seen_f++; }      // (the recurrent launches' timing)
   return forward_from_projections(x, stream);
+}
+}  // namespace
+
+extern "C" int mmda_misa_forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, int training, uint64_t seed, void* stream) {
+  if (check_ready(m) || !encoded_batch_ok(m, eb)) return MMDA_EINVAL;
+  // a training forward: utt would need a gradient path that nobody computes
+  if (!m->inference && !encoder_cut(m)) return MMDA_EINVAL;
+  return forward_encoded(m, StepRequest{false, nullptr, nullptr, true}, eb, nullptr, training, seed, stream);
+}
+
+extern "C" int mmda_misa_forward(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths,
+                                 int training, uint64_t seed, void* stream) {
+  return forward_pass(m, StepRequest{}, t_ids, v, a, lengths, training, seed, stream);
 }
 
 // =============================================================================================== losses
@@ -2057,7 +1686,7 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   void* ss = nullptr;
   rc = side_fork(m, s, &ss);
   if (!rc && m->misc_deferred) {
-    // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::emo_eager)
+    // loss values of the step (the forward stretches stored every gradient seed: see mmda_misa::misc_deferred)
     rc = mmda_loss_misc_reg(WS(w.scores), WS(w.tcp), m->misc_deferred, B, c.ncls, nullptr, nullptr, c.ncls == 6, 0, c.conf_weight,
                             WS(w.recon), WS(w.orig), 3 * BH, c.recon_weight, nullptr, nullptr, WS(w.losses), c.diff_weight,
                             c.sim_weight, c.recon_weight, c.conf_weight, c.use_confidNet, m->cls(), m->reg, ss);
@@ -2067,7 +1696,7 @@ void Pass::bwd_side_chain(bool pg_pending, const int64_t* t_ids, const int32_t* 
   // the sorted id list of the embedding scatter (see mmda_misa::esort_valid); MMDA_SORT_EARLY=0: made where the scatter runs
   m->esort_valid = 0;
   // (sparse mode without an optimizer step behind this backward: the rows update runs later, in mmda_misa_adam_step, and sorts there)
-  if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !early)) {
+  if (!rc && P.sort_early && !((P.embed_update == EU_SPARSE || P.embed_deferred) && !opt)) {
     rc = mmda_embed_sort_ids(t_ids, B * w.T, lengths, B, c.vocab, reinterpret_cast<unsigned*>(WS(w.esort)), ss);
     if (!rc && ss != s) {
       hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)ss, m->jflags + 3, ++m->esort_val);
@@ -2251,9 +1880,9 @@ void Pass::bwd_encoder_layer(int l, const float* const* xin, const int64_t* t_id
     // point reads those fp32 parameters: the remaining GEMMs of a bf16 step read bf16 copies made in the forward pass, and in
     // the other modes the prefix ends in front of the recurrent layers).  The side stream is a real second stream only when
     // use_side is on; otherwise this is simply the same work in front of the recurrence.
-    if (!rc && early && m->early_floats > 0 && m->M1 && m->V1) {
+    if (!rc && opt && m->early_floats > 0 && m->M1 && m->V1) {
       // (frozen parameters: over the prefix's trainable runs -- the prefix counts as stepped even where none of it trains)
-      rc = bucket_adam(m, 0, m->early_floats, nullptr, early->lr, early->clip, early->grad_scale, early->step, kNoWait, ss);
+      rc = bucket_adam(m, 0, m->early_floats, nullptr, opt->lr, opt->clip, opt->grad_scale, opt->step, kNoWait, ss);
       if (!rc) m->adam_early_done = m->early_floats;
     }
   } else {
@@ -2274,12 +1903,12 @@ const unsigned* Pass::take_sorted() {
 }
 
 // The text rows' end of the pass, behind layer 1: d_x_t goes where embed_update sends it.  Sparse and deferred tables take their rows update
-// here, behind an optimizer step only (`early`); otherwise the pass stops at d_x_t, the rows stay pending for mmda_misa_adam_step.
+// here, behind an optimizer step only (`opt`); otherwise the pass stops at d_x_t, the rows stay pending for mmda_misa_adam_step.
 void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
   const float* dx = WS(w.mod[0].d_x);
   if (P.embed_update == EU_SPARSE || P.embed_deferred) {
     m->eu.take();
-    if (!early) { m->eu.set(t_ids, lengths); return; }
+    if (!opt) { m->eu.set(t_ids, lengths); return; }
   }
   if (P.embed_update == EU_FROZEN) return;
   // the list, with the sorted form of it if this pass made one; embed_rows.hip picks the form the sums take
@@ -2288,14 +1917,14 @@ void Pass::bwd_text_rows(const int64_t* t_ids, const int32_t* lengths) {
   if (P.embed_update == EU_SPARSE) {
     // SparseAdam on the rows the batch touches (common.h)
     SparseAdamArgs ad;
-    rc = mmda_sparse_adam_args(&ad, PP(p.embed), m->M1 ? m->M1 + p.embed : nullptr, m->V1 ? m->V1 + p.embed : nullptr, c.vocab, early->lr,
-                               m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale, early->step);
+    rc = mmda_sparse_adam_args(&ad, PP(p.embed), m->M1 ? m->M1 + p.embed : nullptr, m->V1 ? m->V1 + p.embed : nullptr, c.vocab, opt->lr,
+                               m->adam.beta1, m->adam.beta2, m->adam.eps, opt->clip, opt->grad_scale, opt->step);
     if (!rc) rc = mmda_embed_list_sparse_adam(ad, list, s);
   } else if (P.embed_deferred) {
     // dense Adam's step for the rows the batch touches (common.h: RowDenseAdam); every other row takes it when it is next needed
     if (!m->M1 || !m->V1) { rc = MMDA_EINVAL; return; }
-    rc = deferred_apply(m, t_ids, list.sorted, lengths, early->lr, m->adam.beta1, m->adam.beta2, m->adam.eps, early->clip, early->grad_scale,
-                        early->step, false, s);
+    rc = deferred_apply(m, t_ids, list.sorted, lengths, opt->lr, m->adam.beta1, m->adam.beta2, m->adam.eps, opt->clip, opt->grad_scale,
+                        opt->step, false, s);
   } else {
     // the gradient w.r.t. the embedding rows, scattered densely into embed.weight.grad (sparse=False)
     rc = mmda_embed_list_add(GG(p.embed), list, c.vocab, s);
@@ -2307,8 +1936,8 @@ namespace {
 // The backward pass.  The batch (ids / v / a / lengths) is read only by what an encoder cut skips -- the encoder layers, the sorted id
 // list, the scatter -- so a step from the encoder cache, which has no batch, passes NULLs: it must be a cut pass planned by a cached
 // forward.
-// early: the optimizer step behind this pass, which it may start (nullptr: none, the pass stops at the gradients).
-int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const OptStep* early,
+// opt: the optimizer step behind this pass, which it may start (nullptr: none, the pass stops at the gradients).
+int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const float* a, const int32_t* lengths, const OptStep* opt,
                   void* stream) {
   if (check_ready(m) || !m->G) return MMDA_EINVAL;
   if (m->plan.inf) return MMDA_EINVAL;                  // the last forward was an evaluation pass: nothing was stashed
@@ -2316,10 +1945,9 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   if (m->plan.enc_cached && !m->plan.enc_cut) return MMDA_EINVAL;      // (a cached forward that trains is a cut one: cannot happen)
   // the trainable set changed behind that forward: a cut pass computes no encoder gradient (and may have stashed nothing)
   if (m->plan.enc_cut && !encoder_cut(m)) return MMDA_EINVAL;
-  if (masked(m) && early) { const int rr = runs_ready(m, stream); if (rr) return rr; }
+  if (masked(m) && opt) { const int rr = runs_ready(m, stream); if (rr) return rr; }
   m->early_valid = 0; m->adam_early_done = 0;
-  Pass x(m, stream);
-  x.early = early;
+  Pass x(m, stream, nullptr, opt);
   const StepPlan& P = m->plan;
   // the fused stretches read the K-major weight copies this step's forward made (side stream, joined there)
   const bool row_fuse = P.row_fuse && m->wT_valid;
@@ -2341,7 +1969,7 @@ int backward_pass(mmda_misa* m, const int64_t* t_ids, const float* v, const floa
   // wait on the device (see mmda_misa::jflags), when that launch completes
   // (only where every gradient the side stream computes lies in the prefix it also stepped -- the bf16 step, whose layer-2 weight
   //  gradients ran there in front of the early optimizer pass: the launch that waits READS the rest of the bucket before it waits)
-  if (P.fj_on && early && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
+  if (P.fj_on && opt && !is_gru(m) && m->side_pending && m->jflags && m->adam_early_done > 0 &&
       m->adam_early_done == m->par.rnn1_begin) {
     // (the background pass over the table joins here too: the word is set behind it, and the main stream pays nothing)
     x.rc = bg_join(m, m->side);
@@ -2511,14 +2139,12 @@ int train_step_body(mmda_misa* m, const int64_t* t_ids, const float* v, const fl
   if (rc) return rc;
   m->inference = 0;                                     // a training step always stashes (but for the encoders of a cut step)
   m->zero_grad_pending = m->lay.T > 0 ? 1 : 0;
-  m->eager_losses = 1; m->eager_done = 0;
-  m->emo_eager = emo; m->misc_deferred = nullptr;
+  m->eager_done = 0; m->misc_deferred = nullptr;
   m->fj1 = m->fj2 = 0;
-  // the kind of step that may run the background pass over the table (plan_step decides): from a batch, the native Adam behind it, no norm
-  m->bg_step = (early && !eb) ? &o : nullptr;
+  // opt: the kind of step that may run the background pass over the table (plan_step decides): from a batch, the native Adam behind it, no norm
+  const StepRequest req{true, emo, (early && !eb) ? &o : nullptr, eb != nullptr};
   rc = m->zero_grad_pending ? MMDA_OK : mmda_misa_zero_grad(m, stream);
-  if (!rc) rc = eb ? forward_encoded(m, eb, emo_gathered, training, seed, stream) : mmda_misa_forward(m, t_ids, v, a, lengths, training, seed, stream);
-  m->eager_losses = 0; m->emo_eager = nullptr; m->bg_step = nullptr;
+  if (!rc) rc = eb ? forward_encoded(m, req, eb, emo_gathered, training, seed, stream) : forward_pass(m, req, t_ids, v, a, lengths, training, seed, stream);
   if (rc) return rc;
   if (m->zero_grad_pending) return MMDA_ELAUNCH;        // forward() always reaches its fusion block
   rc = mmda_misa_losses(m, emo, 1, stream);

@@ -458,6 +458,25 @@ def lstm_plan(descs, B, T, backward=False, no_quad=False, quad_cap=0):
                 pair=bool(plan.pair), kernel=load().mmda_lstm_kernel_name(plan.kernel).decode())
 
 
+def step_plan(handle, B, T, *, fused=False, labels=False, opt_step=False, enc_cached=False, switches=None):
+    """The plan a forward pass over (B, T) batches gets on a model handle as it is set now (mmda_misa_plan_describe: host code only,
+    works without a GPU, a workspace or bound buffers).  fused / labels / opt_step / enc_cached: what the pass is asked to be -- part of
+    train_step, with labels, with an optimizer step that may run the background table pass behind it, starting behind the encoders.
+    switches: None for the defaults (the process's environment is NOT read), or a dict from names of _lib.STEP_SWITCHES to values, the
+    rest at their defaults.  Returns a dict with one entry per field of _lib.STEP_PLAN_FIELDS: bools, but for the ints gm,
+    embed_update, embed_bg_wgs and embed_bg_lds."""
+    req = _lib.MisaStepRequest(int(fused), int(labels), int(opt_step), int(enc_cached))
+    sw = None
+    if switches is not None:
+        assert set(switches) <= set(_lib.STEP_SWITCHES), sorted(set(switches) - set(_lib.STEP_SWITCHES))
+        sw = (C.c_int * len(_lib.STEP_SWITCHES))(*dict(_lib.STEP_SWITCHES, **switches).values())
+    plan = _lib.MisaStepPlan()
+    check(load().mmda_misa_plan_describe(handle, int(B), int(T), C.byref(req), sw, len(_lib.STEP_SWITCHES), C.byref(plan)),
+          "mmda_misa_plan_describe")
+    ints = ("gm", "embed_update", "embed_bg_wgs", "embed_bg_lds")
+    return {k: getattr(plan, k) if k in ints else bool(getattr(plan, k)) for k in _lib.STEP_PLAN_FIELDS}
+
+
 LOSS_DIFF_FORMS = ("generic", "fast4", "fast8", "fast16", "fast32")
 LOSS_DIFF_PRODUCTS = ("skinny", "batched")
 LOSS_DIFF_SUMS = (None, "finish", "own_launch")
