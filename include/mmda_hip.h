@@ -1067,6 +1067,40 @@ int mmda_misa_forward_encoded(mmda_misa* m, const mmda_encoded_batch* eb, int tr
 int mmda_misa_train_step_encoded(mmda_misa* m, const mmda_encoded_batch* eb, float* emo_out, int training, uint64_t seed, int do_adam,
                                  float lr, float clip, int step, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- modality masking
+ * A batch with some of its three inputs blanked, and what each input contributes to a value (mmda_amd/modality.py).
+ * Modalities: 0 = text, 1 = visual, 2 = acoustic.  A keep set is three bits, bit m set = modality m is kept; 7 keeps everything, 0
+ * nothing.  Blanking column b: every word id at t < len becomes unk_id (padding keeps pad_id), the column's visual / acoustic rows
+ * become 0.0f.  Lengths and labels do not change, nothing is rescaled.
+ * The random keep set of SAMPLE s (its dataset index, whatever batch it sits in): with u_m = (float)(rng_u32(seed, 11, 3 s + m) >> 8)
+ *   * 2^-24 (the counter-based generator of the dropout sites, site 11), modality m is dropped iff p_m > 0 && u_m < p_m (fp32); a draw
+ *   that would drop all three drops none.  A column's keep set is random_keep(s) & keep_const.
+ * mmda_collate_gather_masked: mmda_collate_gather's arguments, grid and outputs under that keep set, in the same ONE launch; a dropped
+ *   modality is written without its source being read.  out_keep (optional): uint8 [B], the columns' keep sets.  keep_const = 7 with
+ *   p = {0, 0, 0} writes the bytes of mmda_collate_gather.  MMDA_EINVAL also for keep_const outside 0 .. 7 or a p outside [0, 1).
+ * mmda_modality_mask: the out-of-place form for a batch that exists already.  ids int64 [T, B], v fp32 [T, B, dv], a fp32 [T, B, da]
+ *   are read and never written; out_ids / out_v / out_a of the same shapes receive the masked copies (every element is written).
+ *   Column b's keep set is keep[b] & 7 (uint8 [B], device) or, keep == NULL, keep_const.  An id equal to pad_id stays: pad_id is
+ *   reserved, never a word, so no lengths are read.  One launch.  MMDA_EINVAL, nothing launched: a NULL pointer other than keep,
+ *   T, B, dv or da <= 0, keep_const outside 0 .. 7, an output that is its input.
+ * mmda_modality_attrib: V fp32 [8, n, C], V[k] = a value (a score column, tcp) under keep set k.  One thread per (row, class) writes
+ *   phi [n, 3, C]: the exact Shapley value of three players, phi_m = sum over the S without m of w(|S|) (V[S | m] - V[S]),
+ *     w(0) = w(2) = 1/3, w(1) = 1/6, the four terms added in ascending S in fp32;
+ *   loo [n, 3, C] = V[7] - V[7 without m];
+ *   dominant int32 [n, C]: the m of the largest phi_m, compared by a strict > in ascending m among the phi_m that are not NaN (ties go
+ *     to the lowest m, a NaN never wins); -1 where all three are NaN;
+ *   counts int64 [3, C], OVERWRITTEN (cleared on the stream, then integer adds): the rows each modality dominates, per class.  The
+ *     same bits on every run.
+ *   MMDA_EINVAL, nothing launched: a NULL pointer, n or C <= 0, n C >= 2^39. */
+typedef struct mmda_modality_p { float p[3]; } mmda_modality_p;      /* the drop rates of text, visual, acoustic; passed by value */
+int mmda_collate_gather_masked(const int32_t* words, const float* visual, const float* acoustic, const int64_t* offsets, const float* emo,
+                               const float* sentiment, const int32_t* order, int B, int T, int dv, int da, int pad_id, int keep_const,
+                               mmda_modality_p p, uint64_t seed, int unk_id, int64_t* out_ids, float* out_v, float* out_a,
+                               float* out_emo, float* out_y, uint8_t* out_keep, void* stream);
+int mmda_modality_mask(const int64_t* ids, const float* v, const float* a, int T, int B, int dv, int da, const uint8_t* keep,
+                       int keep_const, int pad_id, int unk_id, int64_t* out_ids, float* out_v, float* out_a, void* stream);
+int mmda_modality_attrib(const float* V, int64_t n, int C, float* phi, float* loo, int32_t* dominant, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,10 @@ fusion block and the heads of a model with frozen encoders from stored encoder o
 (``ThresholdSweep``, ``Thresholds``: every candidate threshold counted on the device in one launch per batch); ``ranking`` measures
 how a score table ranks before any cut-off (``ranking_metrics``: exact per-class AUROC / AP and the label-ranking figures;
 ``failure_prediction``: the same over ConfidNet's ``tcp``); ``sentiment`` holds the table of the second task (``config.task =
-"sentiment"``): ``sentiment_metrics`` / ``SentimentEval``, the figures of the reference's ``eval_mosei_senti`` from one device state.
+"sentiment"``): ``sentiment_metrics`` / ``SentimentEval``, the figures of the reference's ``eval_mosei_senti`` from one device state;
+``modality`` masks inputs (``DeviceLoader(modality_dropout=..., keep=...)``, ``keep_bits``: the random keep sets restated in numpy) and
+attributes a value to the three modalities (``ModalityPass`` / ``ModalityResult``: the split under all eight keep sets, exact Shapley
+values from one launch).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -20,3 +23,4 @@ from .encoded import EncodedBatch, EncodedLoader, EncoderCache  # noqa: F401
 from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_grid  # noqa: F401
 from .ranking import RankingResult, failure_prediction, rank_plan, ranking_metrics  # noqa: F401
 from .sentiment import SentimentEval, sentiment_metrics  # noqa: F401
+from .modality import MODALITIES, ModalityPass, ModalityResult, keep_bits, parse_keep  # noqa: F401

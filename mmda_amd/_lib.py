@@ -201,6 +201,11 @@ class EncodedBatch(C.Structure):
                 ("B", C.c_int)]
 
 
+class ModalityP(C.Structure):
+    """mmda_modality_p: the drop rates of text, visual, acoustic (passed by value)"""
+    _fields_ = [("p", C.c_float * 3)]
+
+
 CELL = {"lstm": 0, "gru": 1}
 TASK = {"emotion": 0, "sentiment": 1}            # MMDA_TASK_*
 SENTI_LOSS = {"l1": 0, "mse": 1}                 # MMDA_SENTI_*
@@ -370,6 +375,9 @@ SIGNATURES = {
     "mmda_misa_encoded_collect": (_I, [_P, _P, _P, _P, _P, _I64, _P]),
     "mmda_misa_forward_encoded": (_I, [_P, C.POINTER(EncodedBatch), _I, _U64, _P]),
     "mmda_misa_train_step_encoded": (_I, [_P, C.POINTER(EncodedBatch), _P, _I, _U64, _I, _F, _F, _I, _P]),
+    "mmda_collate_gather_masked": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, ModalityP, _U64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mmda_modality_mask": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "mmda_modality_attrib": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -325,15 +325,41 @@ class DeviceLoader:
     valid while the host runs ahead): consume a batch on the stream that was current when it was yielded.  Every tensor of a yielded
     tuple is the batch's own, as with ``collate_fn`` -- except the three BERT slots, which are one cached all-zero CPU tensor per shape
     (``use_bert=False``: nothing reads them), shared by the three slots, by every batch of that shape and across epochs: do not write
-    into it."""
+    into it.
 
-    def __init__(self, dataset, batch_size, shuffle=False, sampler=None, generator=None, drop_last=False, shard=None):
+    Modality masking (mmda_amd/modality.py).  ``modality_dropout=(p_t, p_v, p_a)``: every sample's text / visual /
+    acoustic input is blanked with that probability (never all three), a function of (seed, the sample's dataset index) and so
+    independent of batch size and order; ``keep``: a fixed keep set (an int 0 .. 7 or modality names) ANDed with the random one.  With
+    either given, every batch is one ``mmda_collate_gather_masked`` launch in the plain launch's place, under the seed
+    ``(modality_seed + epoch) mod 2^64``; ``epoch`` counts the ``__iter__`` calls from 0 (``set_epoch(e)`` sets the next one), and
+    ``last_keep`` is the device uint8 (B,) of the keep sets of the batch just yielded.  With all three at their defaults the loader
+    calls ``mmda_collate_gather`` exactly as it always has (``last_keep`` stays None)."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, sampler=None, generator=None, drop_last=False, shard=None,
+                 modality_dropout=None, modality_seed=0, keep=None):
+        from .modality import parse_dropout, parse_keep
         if sampler is not None and shuffle:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         self.dataset, self.batch_size, self.shuffle, self.sampler, self.generator = dataset, int(batch_size), bool(shuffle), sampler, generator
         self.drop_last, self.shard = bool(drop_last), shard
         _kept(0, self.batch_size, self.drop_last, shard)            # refuses a bad batch_size / shard here, not at the first epoch
         self._bert = {}                      # (B, T + 2) -> the zero tensor the three BERT slots share (use_bert=False)
+        self.modality_dropout = parse_dropout(modality_dropout)
+        if isinstance(modality_seed, bool) or not isinstance(modality_seed, int):
+            raise ValueError(f"modality_seed must be an int, not {modality_seed!r}")
+        self.modality_seed = modality_seed
+        self.keep = None if keep is None else parse_keep(keep)
+        self.epoch, self.last_keep = 0, None
+
+    def set_epoch(self, epoch):
+        """The epoch number the next ``__iter__`` runs under (the random keep sets' seed is ``modality_seed + epoch``)."""
+        if isinstance(epoch, bool) or not isinstance(epoch, int) or epoch < 0:
+            raise ValueError(f"epoch must be an int >= 0, not {epoch!r}")
+        self.epoch = epoch
+
+    @property
+    def masked(self):
+        return self.modality_dropout is not None or self.keep is not None
 
     def __len__(self):
         m = len(self.sampler) if self.sampler is not None else len(self.dataset)
@@ -351,10 +377,16 @@ class DeviceLoader:
         import numpy as np
         from . import _lib
         ds = self.dataset
+        epoch, self.epoch = self.epoch, self.epoch + 1
         order, bounds = batch_plan(ds.lengths, self._indices(), self.batch_size, self.drop_last, self.shard)
         if order.size == 0:
             return
         lib = _lib.load()
+        masked = self.masked
+        if masked:
+            keep_const = 7 if self.keep is None else self.keep
+            p = _lib.ModalityP((_lib.C.c_float * 3)(*(self.modality_dropout or (0.0, 0.0, 0.0))))
+            seed = (self.modality_seed + epoch) % (1 << 64)
         # the epoch's one host-to-device copy, from page-locked memory so that it does not wait for the device either
         order_dev = torch.from_numpy(order.astype(np.int32)).pin_memory().to(ds.device, non_blocking=True)
         lens_np = ds.lengths[order]
@@ -369,9 +401,16 @@ class DeviceLoader:
             a = torch.empty(T, B, da, device=dev)
             emo = torch.empty(B, 6, device=dev) if ds.emo is not None else None
             y = torch.empty(B, device=dev)
-            _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, dv, da, PAD, ids.data_ptr(), v.data_ptr(), a.data_ptr(),
-                                               _lib.ptr(emo), y.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "mmda_collate_gather")
+            if masked:
+                self.last_keep = kept = torch.empty(B, dtype=torch.uint8, device=dev)
+                _lib.check(lib.mmda_collate_gather_masked(*src, order_ptr + 4 * lo, B, T, dv, da, PAD, keep_const, p, seed, UNK,
+                                                          ids.data_ptr(), v.data_ptr(), a.data_ptr(), _lib.ptr(emo), y.data_ptr(),
+                                                          kept.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                           "mmda_collate_gather_masked")
+            else:
+                _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, dv, da, PAD, ids.data_ptr(), v.data_ptr(),
+                                                   a.data_ptr(), _lib.ptr(emo), y.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream), "mmda_collate_gather")
             bert = self._bert.get((B, T + 2))
             if bert is None:
                 bert = self._bert[(B, T + 2)] = torch.zeros(B, T + 2, dtype=torch.int64)

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .data import PAD, batch_plan
+from .data import PAD, UNK, batch_plan
+from .modality import parse_keep
 
 FIELDS = ("scores", "labels", "tcp", "hidden", "utterance", "attention")
 ORDERS = ("length", "dataset")
@@ -56,11 +57,13 @@ def _eval_batch(m, t, v, a, lengths):
     m._forward_raw(t, v, a, len_dev, False, m._next_seed(), inference=True)
 
 
-def dataset_pass(m, ds, plan, bounds, batch_size, dev, collect):
-    """The loop of a pass over a device-resident dataset, shared by ``InferencePass.run`` and ``EncoderCache.build``
-    (mmda_amd/encoded.py): the plan's int32 order is uploaded once; every batch is one ``mmda_collate_gather`` into buffers sized once
-    for the longest batch, ``_eval_batch``, and ``collect(dst_ptr)`` -- the caller's one launch, which copies what the forward left in
-    the workspace to the rows the B int32 indices at ``dst_ptr`` name (the batch's samples).  No read-back, no synchronisation."""
+def dataset_pass(m, ds, plan, bounds, batch_size, dev, collect, keeps=None):
+    """The loop of a pass over a device-resident dataset, shared by ``InferencePass.run``, ``EncoderCache.build``
+    (mmda_amd/encoded.py) and ``ModalityPass.run`` (mmda_amd/modality.py): the plan's int32 order is uploaded once; every batch is one
+    ``mmda_collate_gather`` into buffers sized once for the longest batch, ``_eval_batch``, and ``collect(dst_ptr)`` -- the caller's one
+    launch, which copies what the forward left in the workspace to the rows the B int32 indices at ``dst_ptr`` name (the batch's
+    samples).  No read-back, no synchronisation.  ``keeps``: keep sets (ints 0 .. 7); every batch is then gathered,
+    evaluated and collected once per keep set k -- ``mmda_collate_gather_masked`` in the plain gather's place, ``collect(dst_ptr, k)``."""
     n = len(ds)
     if not n:
         return
@@ -75,13 +78,22 @@ def dataset_pass(m, ds, plan, bounds, batch_size, dev, collect):
     y_buf = torch.empty(Bmax, device=dev)
     src = tuple(_lib.ptr(x) for x in (ds.words, ds.visual, ds.acoustic, ds.offsets, ds.emo, ds.sentiment))
     order_ptr = order_dev.data_ptr()
+    no_drop = _lib.ModalityP()
     for lo, hi in zip(bounds[:-1].tolist(), bounds[1:].tolist()):
         B, T = hi - lo, int(lens_np[lo])
         ids, v, a = ids_buf[:T * B].view(T, B), v_buf[:T * B * ds.dv].view(T, B, ds.dv), a_buf[:T * B * ds.da].view(T, B, ds.da)
-        _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, ds.dv, ds.da, PAD, ids.data_ptr(), v.data_ptr(),
-                                           a.data_ptr(), None, y_buf.data_ptr(), _lib.stream_ptr()), "mmda_collate_gather")
-        _eval_batch(m, ids, v, a, lens_all[lo:hi])
-        collect(order_ptr + 4 * lo)
+        if keeps is None:
+            _lib.check(lib.mmda_collate_gather(*src, order_ptr + 4 * lo, B, T, ds.dv, ds.da, PAD, ids.data_ptr(), v.data_ptr(),
+                                               a.data_ptr(), None, y_buf.data_ptr(), _lib.stream_ptr()), "mmda_collate_gather")
+            _eval_batch(m, ids, v, a, lens_all[lo:hi])
+            collect(order_ptr + 4 * lo)
+            continue
+        for k in keeps:
+            _lib.check(lib.mmda_collate_gather_masked(*src, order_ptr + 4 * lo, B, T, ds.dv, ds.da, PAD, int(k), no_drop, 0, UNK,
+                                                      ids.data_ptr(), v.data_ptr(), a.data_ptr(), None, y_buf.data_ptr(), None,
+                                                      _lib.stream_ptr()), "mmda_collate_gather_masked")
+            _eval_batch(m, ids, v, a, lens_all[lo:hi])
+            collect(order_ptr + 4 * lo, k)
 
 
 def _check_fields(fields):
@@ -161,20 +173,23 @@ class InferencePass:
         ops.misa_infer_collect(self.model, out, dst_ptr, base)
 
     # ------------------------------------------------------------------ over a device-resident dataset
-    def run(self, dataset, batch_size, order="length"):
+    def run(self, dataset, batch_size, order="length", keep=None):
         """Row i of every table is sample i of ``dataset`` (a ``DeviceDataset``), whatever ``order`` the batches are visited in
-        (``inference_plan``).  Batches are gathered by ``mmda_collate_gather`` into buffers sized once for the longest batch."""
+        (``inference_plan``).  Batches are gathered by ``mmda_collate_gather`` into buffers sized once for the longest batch.
+        ``keep``: a keep set (``modality.parse_keep``) -- the batches are then gathered by
+        ``mmda_collate_gather_masked`` with the other modalities blanked; None is the plain pass."""
+        keeps = None if keep is None else (parse_keep(keep),)
         plan, bounds = inference_plan(dataset.lengths, batch_size, order)
         dev = _pass_device(self.model, dataset, "InferencePass")
         m, ds, n = self.model, dataset, len(dataset)
         flat, layout, out = self._tables(n, dev)
         lengths = torch.from_numpy(np.array(ds.lengths, dtype=np.int64))
-        dataset_pass(m, ds, plan, bounds, batch_size, dev, lambda dst_ptr: ops.misa_infer_collect(m, out, dst_ptr, 0))
+        dataset_pass(m, ds, plan, bounds, batch_size, dev, lambda dst_ptr, k=None: ops.misa_infer_collect(m, out, dst_ptr, 0), keeps)
         m.check_cluster("inference")
         return InferenceResult(flat, layout, n, lengths, np.array(ds.segments, dtype=object))
 
     # ------------------------------------------------------------------ over any loader of the reference's tuples
-    def run_loader(self, loader):
+    def run_loader(self, loader, keep=None):
         """``loader``: any iterable of the reference's 10-tuples (``DataLoader`` + ``collate_fn``, ``DevicePrefetcher``,
         ``DeviceLoader``, a list).  Rows come in the order the loader yields samples; ``segments`` is the tuples' last slot, ``lengths``
         their sixth, concatenated.
@@ -182,7 +197,14 @@ class InferencePass:
         Sizing the tables: ``len(loader.dataset)`` is used, as an upper bound on the samples one pass yields (a sampler, ``drop_last`` or
         a shard may yield fewer; the result is cut to the rows written), when the loader has a ``dataset`` with a length that is not the
         loader itself.  Otherwise -- a plain list, or a stand-in loader whose ``dataset`` is the loader -- a first counting pass over the
-        batches' ``lengths`` sizes them, so such a loader must yield the same number of samples twice."""
+        batches' ``lengths`` sizes them, so such a loader must yield the same number of samples twice.
+
+        ``keep``: a keep set (``modality.parse_keep``) -- every batch is masked, out of place, by one
+        ``mmda_modality_mask`` launch in front of ``_prepare``; None is the plain pass.  A loader over the encoder cache is refused."""
+        from . import step_rules
+        from .encoded import EncodedLoader
+        keep = None if keep is None else parse_keep(keep)
+        step_rules.modality_check(keep, encoded=isinstance(loader, EncodedLoader))
         dev = self._device()
         m = self.model
         ds = getattr(loader, "dataset", None)
@@ -199,6 +221,8 @@ class InferencePass:
             if done + B > rows:
                 raise _lib.MMDAError(f"InferencePass: the loader yields more than the {rows} samples its tables were sized for")
             t, v, a = (x if x.is_cuda else x.to(dev) for x in (t, v, a))
+            if keep is not None:
+                t, v, a = ops.modality_mask(t.contiguous(), v.contiguous().float(), a.contiguous().float(), keep)
             self._batch(t, v, a, l, out, None, done)
             lengths.append(l.to(torch.int64))
             segments.extend(list(ids))

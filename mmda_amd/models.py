@@ -872,9 +872,13 @@ class MISA(nn.Module):
         if custom:
             optimizer.step(clip_value=clip, grad_scale=1.0)
 
-    def forward_encoded(self, batch):
+    def forward_encoded(self, batch, keep=None):
         """``model(...)`` under ``torch.no_grad()`` from the encoder cache: (scores, labels) of the batch, the side-channel attributes
-        set as ``alignment`` sets them.  Draws one seed, as ``model(...)`` does."""
+        set as ``alignment`` sets them.  Draws one seed, as ``model(...)`` does.  ``keep`` exists to be refused by name: a keep set
+        other than 7 (mmda_amd/modality.py) needs the encoders run on the masked input, and the cache holds whole samples."""
+        if keep is not None:
+            from .modality import parse_keep
+            step_rules.modality_check(parse_keep(keep), encoded=True)
         if torch.is_grad_enabled():
             raise _lib.MMDAError("autograd through forward_encoded is not built: call it under torch.no_grad() (train with train_step_encoded)")
         eb, _ = self._encoded_begin(batch, "forward_encoded")

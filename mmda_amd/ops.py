@@ -945,3 +945,80 @@ def misa_infer_collect(model, out, dst_ptr=None, base=0):
     """``mmda_misa_infer_collect``: the same with the sources taken from ``model``'s workspace as its last forward left them.  ``out``: an
     ``_lib.InferOut``; ``dst_ptr``: device address of the batch's int32 rows, or None for rows ``base .. base + B - 1``."""
     check(model._lib.mmda_misa_infer_collect(model._h, C.byref(out), dst_ptr, int(base), stream_ptr()), "misa_infer_collect")
+
+
+# ---------------------------------------------------------------------------------------------- modality masking (DESIGN.md 4n)
+def collate_gather_masked(words, visual, acoustic, offsets, emo, sentiment, order, T, keep=None, p=None, seed=0, pad_id=1, unk_id=0,
+                          out=None, out_keep=None):
+    """``collate_gather`` under a keep set, in the same one launch (``mmda_collate_gather_masked``).  ``keep``: the constant keep set
+    (``modality.parse_keep``: None = everything, an int 0 .. 7 or modality names); ``p``: None or the drop rates (p_t, p_v, p_a) of the
+    random keep set, a function of (``seed``, sample index); column b gets ``random_keep(order[b]) & keep``.  Returns ``collate_gather``'s
+    five tensors and the columns' keep sets, uint8 (B,) (``out_keep``: the tensor to write them into)."""
+    from .modality import parse_dropout, parse_keep
+    lib = load()
+    keep_const, p = parse_keep(keep), parse_dropout(p) or (0.0, 0.0, 0.0)
+    B, dv, da = order.numel(), visual.shape[1], acoustic.shape[1]
+    assert words.dtype == order.dtype == torch.int32 and offsets.dtype == torch.int64
+    assert all(x.is_cuda and x.is_contiguous() for x in (words, visual, acoustic, offsets, sentiment, order) + (() if emo is None else (emo,)))
+    assert words.numel() == visual.shape[0] == acoustic.shape[0] and offsets.numel() == sentiment.numel() + 1
+    assert emo is None or (emo.dtype == torch.float32 and tuple(emo.shape) == (sentiment.numel(), 6))
+    _f(visual); _f(acoustic); _f(sentiment)
+    dev = words.device
+    if out is None:
+        out = (torch.empty(T, B, dtype=torch.int64, device=dev), torch.empty(T, B, dv, device=dev), torch.empty(T, B, da, device=dev),
+               None if emo is None else torch.empty(B, 6, device=dev), torch.empty(B, device=dev))
+    if out_keep is None:
+        out_keep = torch.empty(B, dtype=torch.uint8, device=dev)
+    ids, v, a, e, y = out
+    assert ids.dtype == torch.int64 and tuple(ids.shape) == (T, B) and tuple(v.shape) == (T, B, dv) and tuple(a.shape) == (T, B, da)
+    assert tuple(y.shape) == (B,) and (e is None or tuple(e.shape) == (B, 6))
+    assert out_keep.dtype == torch.uint8 and tuple(out_keep.shape) == (B,)
+    assert all(x.is_cuda and x.is_contiguous() for x in (ids, v, a, y, out_keep) + (() if e is None else (e,)))
+    check(lib.mmda_collate_gather_masked(ptr(words), ptr(visual), ptr(acoustic), ptr(offsets), ptr(emo), ptr(sentiment), ptr(order), B,
+                                         int(T), dv, da, int(pad_id), keep_const, _lib.ModalityP((C.c_float * 3)(*p)),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(unk_id), ptr(ids), ptr(v), ptr(a), ptr(e), ptr(y),
+                                         ptr(out_keep), stream_ptr()), "collate_gather_masked")
+    return ids, v, a, e, y, out_keep
+
+
+def modality_mask(ids, v, a, keep, out=None, pad_id=1, unk_id=0):
+    """Masked copies of a batch that exists already, in one launch (``mmda_modality_mask``): ids int64 (T, B), v (T, B, dv), a (T, B, da)
+    on the device are read and never written.  ``keep``: a keep set for every column (``modality.parse_keep``) or a uint8 (B,) device
+    tensor of one keep set per column.  An id equal to ``pad_id`` stays.  ``out``: the three tensors to write into (not the inputs)."""
+    from .modality import parse_keep
+    lib = load()
+    assert ids.dim() == 2 and v.dim() == 3 and a.dim() == 3
+    T, B = ids.shape
+    dv, da = v.shape[2], a.shape[2]
+    assert ids.dtype == torch.int64 and tuple(v.shape[:2]) == (T, B) and tuple(a.shape[:2]) == (T, B)
+    _f(v); _f(a)
+    assert all(x.is_cuda and x.is_contiguous() for x in (ids, v, a))
+    if torch.is_tensor(keep):
+        assert keep.dtype == torch.uint8 and keep.is_cuda and keep.is_contiguous() and tuple(keep.shape) == (B,)
+        keep_ptr, keep_const = keep.data_ptr(), 7
+    else:
+        keep_ptr, keep_const = None, parse_keep(keep)
+    if out is None:
+        out = (torch.empty_like(ids), torch.empty_like(v), torch.empty_like(a))
+    oi, ov, oa = out
+    for x, y in zip(out, (ids, v, a)):
+        assert x.is_cuda and x.is_contiguous() and x.dtype == y.dtype and x.shape == y.shape and x.data_ptr() != y.data_ptr()
+    check(lib.mmda_modality_mask(ptr(ids), ptr(v), ptr(a), int(T), int(B), int(dv), int(da), keep_ptr, keep_const, int(pad_id), int(unk_id),
+                                 ptr(oi), ptr(ov), ptr(oa), stream_ptr()), "modality_mask")
+    return oi, ov, oa
+
+
+def modality_attrib(V):
+    """``V (8, n, C)`` fp32 on the device, V[k] = a value under keep set k -> ``(phi (n, 3, C), loo (n, 3, C), dominant (n, C) int32,
+    counts (3, C) int64)`` from one ``mmda_modality_attrib`` launch: exact Shapley values of the three modalities, the leave-one-out
+    differences, the modality with the largest Shapley value (-1 where all three are NaN) and the rows each modality dominates."""
+    lib = load()
+    assert V.dim() == 3 and V.shape[0] == 8 and V.is_cuda
+    _f(V)
+    V = V.contiguous()
+    n, nc = int(V.shape[1]), int(V.shape[2])
+    phi, loo = torch.empty(n, 3, nc, device=V.device), torch.empty(n, 3, nc, device=V.device)
+    dominant = torch.empty(n, nc, dtype=torch.int32, device=V.device)
+    counts = torch.empty(3, nc, dtype=torch.int64, device=V.device)
+    check(lib.mmda_modality_attrib(ptr(V), n, nc, ptr(phi), ptr(loo), ptr(dominant), ptr(counts), stream_ptr()), "modality_attrib")
+    return phi, loo, dominant, counts

@@ -296,16 +296,36 @@ class Solver(object):
         if os.path.exists(path):
             self.model.load_state_dict(torch.load(path, weights_only=True))
 
-    def eval(self, mode=None, to_print=False, thresholds=None):
+    def _keep(self, keep, dataloader):
+        """A keep set (mmda_amd/modality.py) as its three bits, or None; refused by name over the encoder cache (step_rules.MODALITY_RULES)"""
+        if keep is None:
+            return None
+        from .modality import parse_keep
+        keep = parse_keep(keep)
+        step_rules.modality_check(keep, encoded=isinstance(dataloader, EncodedLoader))
+        return keep
+
+    @staticmethod
+    def _mask(t, v, a, keep):
+        """the batch's inputs under a keep set: masked copies from one launch, the loader's tensors untouched (None: the inputs)"""
+        if keep is None:
+            return t, v, a
+        from . import ops
+        return ops.modality_mask(t.contiguous(), v.contiguous().float(), a.contiguous().float(), keep)
+
+    def eval(self, mode=None, to_print=False, thresholds=None, keep=None):
         """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
-        labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels."""
+        labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels.
+        ``keep``: None, or a keep set (an int 0 .. 7 or modality names, mmda_amd/modality.py): the split is evaluated with the other
+        modalities blanked -- one ``mmda_modality_mask`` launch per batch in front of the forward; None is the plain pass."""
         assert mode is not None
+        keep = self._keep(keep, self.dev_data_loader if mode == "dev" else self.test_data_loader)
         if self._sentiment():
             if thresholds is not None:
                 step_rules.task_check("sentiment", self.model.senti_loss, calibrate="thresholds")
-            return self._eval_sentiment(mode, to_print)
+            return self._eval_sentiment(mode, to_print, keep)
         if thresholds is not None:
-            return self._eval_thresholds(mode, to_print, thresholds)
+            return self._eval_thresholds(mode, to_print, thresholds, keep)
         self.model.eval()
         y_true, y_pred, eval_loss = [], [], []
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
@@ -319,11 +339,12 @@ class Solver(object):
         with torch.no_grad():
             for batch in dataloader:
                 if isinstance(batch, EncodedBatch):
-                    predicted_scores, predicted_labels = self.model.forward_encoded(batch)
+                    predicted_scores, predicted_labels = self.model.forward_encoded(batch, keep=keep)
                     emo_label = batch.emo()
                 else:
                     t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
                     t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
+                    t, v, a = self._mask(t, v, a, keep)
                     l = to_cpu(l)
                     predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
                 emo_label = emo_label.type(torch.float)
@@ -347,7 +368,7 @@ class Solver(object):
         return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
 
     # ------------------------------------------------------------------ the sentiment task (mmda_amd/sentiment.py)
-    def _eval_sentiment(self, mode, to_print):
+    def _eval_sentiment(self, mode, to_print, keep=None):
         """``eval`` under task='sentiment': (mean batch loss, acc2_non0, preds (N,), truths (N,)).  The loop of ``eval``; per batch one
         collector launch (``SentimentEval.update``) and one loss launch adding into a device sum, nothing read back until the pass is
         over.  ``self.last_sentiment``: the reference's eval_mosei_senti keys (and 'f1_non0'), all from the one collector state."""
@@ -359,7 +380,7 @@ class Solver(object):
         kind = _lib.SENTI_LOSS[self.model.senti_loss]
         lib, ev, loss_sum, batches = _lib.load(), None, None, 0
         preds, truths = [], []
-        for scores, y in self._eval_batches(dataloader):
+        for scores, y in self._eval_batches(dataloader, keep=keep):
             if not scores.is_cuda:
                 raise _lib.MMDAError("eval() under task='sentiment' counts on the GPU only (the HIP path has no CPU fallback)")
             s, t = scores.detach().to(torch.float32).contiguous().reshape(-1), y.contiguous().reshape(-1)
@@ -386,18 +407,20 @@ class Solver(object):
             print(format_table(self.last_sentiment, c["n"], c["n_nonzero"]))
 
     # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py)
-    def _eval_batches(self, dataloader, confidence=False):
+    def _eval_batches(self, dataloader, confidence=False, keep=None):
         """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``;
-        ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence in them."""
+        ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence in them.
+        ``keep``: None or a keep set's three bits (``_keep``)."""
         self.model.eval()
         with torch.no_grad():
             for batch in dataloader:
                 if isinstance(batch, EncodedBatch):
-                    predicted_scores, predicted_labels = self.model.forward_encoded(batch)
+                    predicted_scores, predicted_labels = self.model.forward_encoded(batch, keep=keep)
                     emo_label = batch.emo()
                 else:
                     t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
                     t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(y if self._sentiment() else emo_label)
+                    t, v, a = self._mask(t, v, a, keep)
                     l = to_cpu(l)
                     predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
                 if confidence:
@@ -405,7 +428,7 @@ class Solver(object):
                 else:
                     yield predicted_scores, emo_label.type(torch.float)
 
-    def _eval_thresholds(self, mode, to_print, thresholds):
+    def _eval_thresholds(self, mode, to_print, thresholds, keep=None):
         from . import _lib
         if mode == "test" and to_print:
             self._load_best_checkpoint()
@@ -413,7 +436,7 @@ class Solver(object):
         thr = thresholds.values.to(device=self.device, dtype=torch.float32).contiguous()
         acc_dev, lib = None, _lib.load()
         y_true, y_pred = [], []
-        for scores, emo_label in self._eval_batches(dataloader):
+        for scores, emo_label in self._eval_batches(dataloader, keep=keep):
             if not scores.is_cuda:
                 raise _lib.MMDAError("eval(thresholds=...) counts on the GPU only (the HIP path has no CPU fallback)")
             if thr.numel() != scores.shape[1]:
@@ -508,11 +531,12 @@ class Solver(object):
         return out
 
     # ------------------------------------------------------------------ inference (the reference's src/inference.py is a TODO)
-    def infer(self, mode, fields=None, order="loader"):
+    def infer(self, mode, fields=None, order="loader", keep=None):
         """One inference pass over the ``mode`` split ("train", "dev" or "test") -> ``InferenceResult`` (mmda_amd/inference.py): the
         per-sample tables stay on the device.  ``order="loader"``: the loader's own batches, rows in the order it yields samples.
         ``order="length"`` / ``"dataset"``: the loader must be a ``DeviceLoader``; its dataset is batched by ``inference_plan`` at the
-        loader's batch size and row i is sample i of the dataset."""
+        loader's batch size and row i is sample i of the dataset.  ``keep``: None, or a keep set (mmda_amd/modality.py) -- the pass
+        runs with the other modalities blanked (``InferencePass.run`` / ``run_loader`` with that ``keep``)."""
         from .data import DeviceLoader
         from .inference import ORDERS, InferencePass
         loaders = dict(train=self.train_data_loader, dev=self.dev_data_loader, test=self.test_data_loader)
@@ -525,9 +549,40 @@ class Solver(object):
             raise ValueError(f"order={order!r} re-batches a device-resident dataset: the {mode} loader must be a DeviceLoader "
                              f"(it is a {type(loader).__name__}); use order='loader'")
         p = InferencePass(self.model, fields) if fields is not None else InferencePass(self.model)
+        keep = self._keep(keep, loader)
         if order == "loader":
-            return p.run_loader(loader)
-        return p.run(loader.dataset, loader.batch_size, order)
+            return p.run_loader(loader, keep=keep)
+        return p.run(loader.dataset, loader.batch_size, order, keep=keep)
+
+    # ------------------------------------------------------------------ modality attribution (mmda_amd/modality.py)
+    def modalities(self, mode="dev", values=None, to_print=False):
+        """The ``mode`` split ("dev" or "test") under all eight keep sets -> ``ModalityResult``, kept in ``self.last_modalities``: what
+        the model scores, and how confident ConfidNet is, with every subset of {text, visual, acoustic} blanked; its ``attribution``
+        gives each modality's exact Shapley value per sample and class.  ``values``: None -- ("scores", "tcp"), under task='sentiment'
+        ("scores",) -- or a subset.  Over a ``DeviceLoader`` the pass is ``ModalityPass.run`` on its dataset at its batch size: eight
+        masked gathers per batch, row i = sample i.  Any other loader of the reference's tuples is walked eight times
+        (``ModalityPass.run_loader``: ``InferencePass.run_loader(loader, keep=k)`` for k = 0 .. 7), which is slower -- every batch is
+        copied once more by the mask launch and the loader's own work is done eight times -- but gives the same tables, rows in the
+        loader's order.  A loader over the encoder cache is refused by name.  ``to_print``: one table, per keep set acc / F1 / mean
+        tcp and per class the mean Shapley value of each modality (read back for the print)."""
+        from .data import DeviceLoader
+        from .modality import ModalityPass, format_table
+        if mode not in ("dev", "test"):
+            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        step_rules.modality_check(0, encoded=isinstance(loader, EncodedLoader))
+        if values is None:
+            values = ("scores",) if self._sentiment() else ("scores", "tcp")
+        p = ModalityPass(self.model, values)
+        res = p.run(loader.dataset, loader.batch_size) if isinstance(loader, DeviceLoader) else p.run_loader(loader)
+        self.last_modalities = res
+        if to_print:
+            metrics = None if self._sentiment() or res.truth is None or res.scores is None else res.metrics()
+            which = "scores" if res.scores is not None else "tcp"
+            phi = res.attribution(which)["phi"].mean(dim=0).cpu().numpy()
+            tcp = None if res.tcp is None else res.tcp.mean(dim=(1, 2)).cpu().numpy()
+            print(format_table(metrics, tcp, phi))
+        return res
 
     # ------------------------------------------------------------------ encoder cache (mmda_amd/encoded.py)
     def encode(self, mode, batch_size=None, order="length"):

@@ -137,6 +137,31 @@ def task_check(task="emotion", senti_loss="l1", **values) -> None:
         raise MMDAError(dict(SENTI_RULES)[hit[0]].format(**hit[1]))
 
 
+# What modality masking refuses.  A keep set is an operation on a batch's INPUTS, made where the batch is made; a path
+# that has no inputs left to mask refuses it where the keep set is given (MISA.forward_encoded, InferencePass, Solver.eval / infer /
+# modalities), with nothing run.
+MODALITY_RULES = (
+    ("modality_encoded", "a keep set ({keep}) on the encoder cache (EncodedLoader / forward_encoded) is not built: the cache holds the "
+                         "encoder outputs of whole samples, and a masked input needs the encoders run again (use the DeviceLoader the "
+                         "cache was built from)"),
+)
+
+
+def modality_verdict(keep=None, encoded: bool = False):
+    """(rule, format values) of the first rule of MODALITY_RULES that refuses the setting, or None.  ``keep``: None or the keep set's
+    three bits (7 keeps everything and is refused nowhere); ``encoded``: the batches come from the encoder cache."""
+    if encoded and keep is not None and int(keep) != 7:
+        return "modality_encoded", dict(keep=int(keep))
+    return None
+
+
+def modality_check(keep=None, encoded: bool = False) -> None:
+    """Raises MMDAError with the text of the rule that refuses the setting (``modality_verdict``'s arguments)."""
+    hit = modality_verdict(keep, encoded)
+    if hit is not None:
+        raise MMDAError(dict(MODALITY_RULES)[hit[0]].format(**hit[1]))
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:
