@@ -614,6 +614,58 @@ int mmda_rank_rows_accumulate(const float* scores, const float* truth, int64_t N
 int mmda_senti_accumulate(const float* pred, const float* truth, int64_t N, void* state, void* stream);
 int mmda_senti_finish(const void* state, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- reliability and logit scaling
+ * Are the numbers of a score table probabilities (mmda_amd/reliability.py).  prob / target: (N, C) fp32 device tables,
+ * y = target > 0.  A NaN prob counts in n_nan[c] and nowhere else; any other value is clamped to [0, 1] (-0 becomes 0).  Its bin is
+ * j = min(M - 1, (int)(p * (float)M)): one fp32 multiply, truncated.  1 <= C <= 16, 1 <= M <= 64, at most 2^20 rows per call and per state.
+ * state: MMDA_RELIAB_STATE_WORDS(C, M) 8-byte words, 8-byte aligned, cleared by the caller before the first batch:
+ *   uint64  [0] the launch's ticket, 0 between launches  [1] unused  [2 + c] n_nan
+ *   double  [2 + C + c] sum (p - y)^2   [2 + 2 C + c] sum -[y max(log p, -100) + (1 - y) max(log(1 - p), -100)], logs in float64
+ *   uint64  [2 + 3 C + 3 (c M + j) + {0, 1, 2}] cnt, pos, sum_p = sum rint(p 2^40) of bin j of class c
+ * The integers do not depend on the order of arrival or on how the rows are split into batches.  The float64 sums use no float atomic:
+ * thread (r, c) of a workgroup adds rows 16 (b + k gridDim) + r of class c in row order, the 16 row lanes of a class are added as
+ * ((r0 + r1) + (r2 + r3)) per wave and the four waves in order, the workgroups leave partials and the last one to arrive adds them in
+ * workgroup order on top of the state: the same batches give the same bits.  At most MMDA_RELIAB_GRID_CAP workgroups; beyond
+ * 16 MMDA_RELIAB_GRID_CAP rows a workgroup strides.  One state takes launches of one stream at a time.
+ * mmda_reliab_finish: figures (C + 2, MMDA_RELIAB_FIGURES) doubles {n, n_nan, base_rate, mean_p, ece, mce, brier, nll} -- the class rows,
+ * row C their means (each column over the classes where it is not NaN, added in class order; NaN where none is), row C + 1 all classes'
+ * bins and sums pooled -- and diagram (C, M, 3) doubles {cnt, pos / cnt, sum_p / (2^40 cnt)} (an empty bin: 0, NaN, NaN).
+ *   ece = sum_j |pos_j 2^40 - sum_p_j| / (2^40 n), mce = max_j |pos_j 2^40 - sum_p_j| / (2^40 cnt_j): exact integers, one division each.
+ *   n = 0: every figure of the row but n and n_nan is NaN.  One workgroup, nothing read back.
+ * mmda_scaling_fit: q = sigmoid(a z + b), z = log p' - log1p(-p') in float64 of the fp32 score clamped to [2^-23, 1 - 2^-23], NaN scores
+ * left out.  how: MMDA_SCALING_TEMPERATURE fits a (b = 0), MMDA_SCALING_PLATT a and b; per_class: one group per class, else one group
+ * of all classes; a group's parameters minimise its mean NLL.  A clear of the work header and a prepare launch (z, the groups' n and
+ * positives), then exactly max_iter (1 .. MMDA_SCALING_MAX_ITER) iteration launches: the workgroups leave float64 partials of
+ * (NLL, gradient, Hessian) per group in the order above, the last one to arrive adds them in workgroup order and takes one damped
+ * Newton step per group -- accept the trial point unless its NLL rose (beyond 2^-43 relative, the rounding of the sum), else go back and
+ * raise the damping -- and a group that has converged (max |d mean NLL / d theta| <= 1e-12) or is degenerate is frozen: later launches
+ * leave its bits alone, and return at once when every group is frozen.  No workgroup waits for another; nothing is read back.
+ * Outputs, per class (a group's values repeated for its classes): a, b doubles -- the last accepted point -- status int32
+ * (MMDA_SCALING_OK; MMDA_SCALING_DEGENERATE: no positive or no negative, a = 1, b = 0; MMDA_SCALING_MAXITER), iterations int32 (the
+ * evaluations the group took part in).  work: mmda_scaling_work_bytes(N, C) bytes, 8-byte aligned (-1 for a shape out of range).
+ * mmda_scaling_apply: out = (float) sigmoid(a_c z + b_c), out of place; NaN stays NaN.
+ * Common: N == 0 is MMDA_OK with no launch and nothing written.  MMDA_EINVAL before any launch: a NULL pointer, a misaligned one
+ * (8 bytes for state, figures, diagram, work, a, b; 4 for the rest), C, M or N outside the limits, max_iter outside
+ * 1 .. MMDA_SCALING_MAX_ITER, an unknown how, work_bytes below mmda_scaling_work_bytes(N, C). */
+#define MMDA_RELIAB_MAX_CLASSES 16
+#define MMDA_RELIAB_MAX_BINS 64
+#define MMDA_RELIAB_MAX_ROWS (1 << 20)
+#define MMDA_RELIAB_GRID_CAP 32
+#define MMDA_RELIAB_FIGURES 8
+#define MMDA_RELIAB_STATE_WORDS(C, M) (2 + 3 * (C) + 3 * (C) * (M))
+#define MMDA_SCALING_TEMPERATURE 0
+#define MMDA_SCALING_PLATT 1
+#define MMDA_SCALING_MAX_ITER 256
+#define MMDA_SCALING_OK 0
+#define MMDA_SCALING_DEGENERATE 1
+#define MMDA_SCALING_MAXITER 2
+int mmda_reliab_accumulate(const float* prob, const float* target, int64_t N, int C, int M, void* state, void* stream);
+int mmda_reliab_finish(const void* state, int C, int M, double* figures, double* diagram, void* stream);
+int64_t mmda_scaling_work_bytes(int64_t N, int C);
+int mmda_scaling_fit(const float* prob, const float* target, int64_t N, int C, int how, int per_class, int max_iter, void* work,
+                     int64_t work_bytes, double* a, double* b, int32_t* status, int32_t* iterations, void* stream);
+int mmda_scaling_apply(const float* prob, const double* a, const double* b, int64_t N, int C, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- optimizer
  * clip_grad_value_(clip) then Adam (solver.py:185-186, :97-99; betas 0.9/0.999, eps 1e-8, no weight decay), fused over
  * a flat bucket.  step = 1-based step count.  grad_scale multiplies g first (1/world for DP averaging). */

@@ -12,7 +12,10 @@ how a score table ranks before any cut-off (``ranking_metrics``: exact per-class
 "sentiment"``): ``sentiment_metrics`` / ``SentimentEval``, the figures of the reference's ``eval_mosei_senti`` from one device state;
 ``modality`` masks inputs (``DeviceLoader(modality_dropout=..., keep=...)``, ``keep_bits``: the random keep sets restated in numpy) and
 attributes a value to the three modalities (``ModalityPass`` / ``ModalityResult``: the split under all eight keep sets, exact Shapley
-values from one launch).
+values from one launch); ``reliability`` asks whether the scores are probabilities (``reliability_metrics`` / ``ReliabilityEval``: the
+reliability diagram, ECE, MCE, Brier score and NLL per class from one integer state a launch per batch adds to) and fits the monotone
+rescaling that makes them so (``fit_scaling`` -> ``Scaling``: temperature or Platt scaling of the logits, per class or shared, by a
+damped Newton iteration whose state never leaves the device; ``config.scaling``).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -24,3 +27,4 @@ from .calibrate import ThresholdSweep, Thresholds, confidence_curve, default_gri
 from .ranking import RankingResult, failure_prediction, rank_plan, ranking_metrics  # noqa: F401
 from .sentiment import SentimentEval, sentiment_metrics  # noqa: F401
 from .modality import MODALITIES, ModalityPass, ModalityResult, keep_bits, parse_keep  # noqa: F401
+from .reliability import ReliabilityEval, ReliabilityResult, Scaling, fit_scaling, reliability_metrics  # noqa: F401

@@ -210,6 +210,8 @@ CELL = {"lstm": 0, "gru": 1}
 TASK = {"emotion": 0, "sentiment": 1}            # MMDA_TASK_*
 SENTI_LOSS = {"l1": 0, "mse": 1}                 # MMDA_SENTI_*
 SENTI_STATE_WORDS, SENTI_FIGURES = 24, 9         # MMDA_SENTI_STATE_WORDS, MMDA_SENTI_FIGURES
+SCALING_HOW = {"temperature": 0, "platt": 1}     # MMDA_SCALING_*
+RELIAB_FIGURES, RELIAB_GRID_CAP, SCALING_MAX_ITER = 8, 32, 256   # MMDA_RELIAB_FIGURES, MMDA_RELIAB_GRID_CAP, MMDA_SCALING_MAX_ITER
 
 # name -> (restype, argtypes).  Every symbol include/mmda_hip.h declares appears here (tests/test_abi.py checks it).
 _P, _I, _I64, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
@@ -273,6 +275,11 @@ SIGNATURES = {
     "mmda_loss_reg": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "mmda_senti_accumulate": (_I, [_P, _P, _I64, _P, _P]),
     "mmda_senti_finish": (_I, [_P, _P, _P]),
+    "mmda_reliab_accumulate": (_I, [_P, _P, _I64, _I, _I, _P, _P]),
+    "mmda_reliab_finish": (_I, [_P, _I, _I, _P, _P, _P]),
+    "mmda_scaling_work_bytes": (_I64, [_I64, _I]),
+    "mmda_scaling_fit": (_I, [_P, _P, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _P]),
+    "mmda_scaling_apply": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
     "mmda_misa_set_task": (_I, [_P, _I, _I]),
     "mmda_loss_cls": (_I, [_P, _P, _I, _I, _F, _P, _P, _P]),
     "mmda_loss_cls_opts": (_I, [_P, _P, _I, _I, _F, _P, _P, C.POINTER(ClsOpts), _P]),

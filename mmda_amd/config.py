@@ -120,6 +120,10 @@ DEFAULTS = dict(
     # (num_classes=1) without the sigmoid, under senti_loss "l1" (the reference's commented nn.L1Loss, config.py's criterion_dict['mosi'])
     # or "mse"; evaluation then reports the reference's eval_mosei_senti table
     task="emotion", senti_loss="l1",
+    # after the last epoch of Solver.train(), in front of `calibrate`: "temperature" / "platt" fit one logit scaling q = sigmoid(a z + b)
+    # of the scores (a alone / a and b; mmda_amd/reliability.py) on the dev split with the best checkpoint; the cut-offs
+    # of `calibrate` are then chosen on, and the final test evaluation scores with, the scaled scores; "none": raw scores throughout
+    scaling="none",
 )
 
 
@@ -144,6 +148,8 @@ def get_config(parse=True, **optional_kwargs):
             parser.add_argument(f"--{k}", choices=("emotion", "sentiment"), default=v)
         elif k == "senti_loss":
             parser.add_argument(f"--{k}", choices=("l1", "mse"), default=v)
+        elif k == "scaling":
+            parser.add_argument(f"--{k}", choices=("none", "temperature", "platt"), default=v)
         elif v is None:
             parser.add_argument(f"--{k}", default=None)
         else:

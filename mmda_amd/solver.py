@@ -59,6 +59,9 @@ class Solver(object):
                               use_confidNet=bool(getattr(cfg, "use_confidNet", False)), pos_weight=getattr(cfg, "pos_weight", None),
                               focal_gamma=getattr(cfg, "focal_gamma", 0.0), calibrate=getattr(cfg, "calibrate", "none"),
                               select_by=getattr(cfg, "select_by", "valid_loss"))
+        if getattr(cfg, "scaling", "none") not in ("none", "temperature", "platt"):
+            raise ValueError(f"config.scaling must be 'none', 'temperature' or 'platt', not {cfg.scaling!r}")
+        step_rules.scaling_check(getattr(cfg, "task", "emotion"), getattr(cfg, "scaling", "none"))
         if self.model is None:
             self.model = getattr(models, cfg.model)(cfg)
         for name, param in self.model.named_parameters():
@@ -281,8 +284,9 @@ class Solver(object):
             if self.dp is not None:
                 torch.distributed.barrier()               # every epoch, on every rank: nobody reads the checkpoint before rank 0 has written it
             history.append(dict(epoch=e, train=tr, valid_loss=valid_loss, valid_acc=valid_acc, **extra))
-        thresholds = self._calibrate_after_training(best_epoch >= 0)
-        test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds)
+        scaling = self._scale_after_training(best_epoch >= 0)
+        thresholds = self._calibrate_after_training(best_epoch >= 0, scaling)
+        test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds, scaling=scaling)
         if self._sentiment():
             self._print_sentiment()
         print("=" * 50)
@@ -313,19 +317,24 @@ class Solver(object):
         from . import ops
         return ops.modality_mask(t.contiguous(), v.contiguous().float(), a.contiguous().float(), keep)
 
-    def eval(self, mode=None, to_print=False, thresholds=None, keep=None):
+    def eval(self, mode=None, to_print=False, thresholds=None, keep=None, scaling=None):
         """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
         labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels.
         ``keep``: None, or a keep set (an int 0 .. 7 or modality names, mmda_amd/modality.py): the split is evaluated with the other
-        modalities blanked -- one ``mmda_modality_mask`` launch per batch in front of the forward; None is the plain pass."""
+        modalities blanked -- one ``mmda_modality_mask`` launch per batch in front of the forward; None is the plain pass.
+        ``scaling``: None, or a ``Scaling`` (mmda_amd/reliability.py): the scores of every batch are scaled behind the forward pass (one
+        ``mmda_scaling_apply`` launch), and labels, counts and the loss come from the scaled scores -- under ``thresholds``, or under
+        ``config.threshold`` in every class without them."""
         assert mode is not None
         keep = self._keep(keep, self.dev_data_loader if mode == "dev" else self.test_data_loader)
         if self._sentiment():
             if thresholds is not None:
                 step_rules.task_check("sentiment", self.model.senti_loss, calibrate="thresholds")
+            if scaling is not None:
+                step_rules.scaling_check("sentiment", scaling="Solver.eval")
             return self._eval_sentiment(mode, to_print, keep)
-        if thresholds is not None:
-            return self._eval_thresholds(mode, to_print, thresholds, keep)
+        if thresholds is not None or scaling is not None:
+            return self._eval_thresholds(mode, to_print, thresholds, keep, scaling)
         self.model.eval()
         y_true, y_pred, eval_loss = [], [], []
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
@@ -407,10 +416,11 @@ class Solver(object):
             print(format_table(self.last_sentiment, c["n"], c["n_nonzero"]))
 
     # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py)
-    def _eval_batches(self, dataloader, confidence=False, keep=None):
+    def _eval_batches(self, dataloader, confidence=False, keep=None, scaling=None):
         """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``;
         ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence in them.
-        ``keep``: None or a keep set's three bits (``_keep``)."""
+        ``keep``: None or a keep set's three bits (``_keep``).  ``scaling``: None, or a ``Scaling``: the scores are its ``apply`` of the
+        model's (one launch per batch); the decisions and ``tcp`` stay the model's own."""
         self.model.eval()
         with torch.no_grad():
             for batch in dataloader:
@@ -423,20 +433,27 @@ class Solver(object):
                     t, v, a = self._mask(t, v, a, keep)
                     l = to_cpu(l)
                     predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
+                if scaling is not None:
+                    predicted_scores = scaling.apply(predicted_scores)
                 if confidence:
                     yield predicted_scores, emo_label.type(torch.float), predicted_labels, self.model.tcp
                 else:
                     yield predicted_scores, emo_label.type(torch.float)
 
-    def _eval_thresholds(self, mode, to_print, thresholds, keep=None):
+    def _eval_thresholds(self, mode, to_print, thresholds, keep=None, scaling=None):
+        """``eval`` under cut-offs per class and / or a scaling; ``thresholds=None``: ``config.threshold`` in every class"""
         from . import _lib
         if mode == "test" and to_print:
             self._load_best_checkpoint()
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        thr = thresholds.values.to(device=self.device, dtype=torch.float32).contiguous()
+        if thresholds is None:
+            thr = torch.full((int(self.train_config.num_classes),), float(self.train_config.threshold), dtype=torch.float32,
+                             device=self.device)
+        else:
+            thr = thresholds.values.to(device=self.device, dtype=torch.float32).contiguous()
         acc_dev, lib = None, _lib.load()
         y_true, y_pred = [], []
-        for scores, emo_label in self._eval_batches(dataloader, keep=keep):
+        for scores, emo_label in self._eval_batches(dataloader, keep=keep, scaling=scaling):
             if not scores.is_cuda:
                 raise _lib.MMDAError("eval(thresholds=...) counts on the GPU only (the HIP path has no CPU fallback)")
             if thr.numel() != scores.shape[1]:
@@ -459,14 +476,17 @@ class Solver(object):
         loss, acc, self.last_eval_metrics = acc_dev.result()
         return loss, acc, y_pred, y_true
 
-    def calibrate(self, mode="dev", grid=None, objective=None, per_class=True):
+    def calibrate(self, mode="dev", grid=None, objective=None, per_class=True, scaling=None):
         """Sweeps every cut-off of ``grid`` (default 0.01 .. 0.99) over the ``mode`` split in one pass -- the loop of ``eval`` with
         ``ThresholdSweep.update`` in ``DeviceEval.update``'s place -- and selects, on the device, the cut-off (``per_class=False``) or the
         cut-off per class that maximises ``objective`` ("f1", "micro_f1", "weighted_f1", "acc"; None: what ``config.eval_mode`` names).
-        Sets and returns ``self.thresholds``; the sweep's table of the ten figures per cut-off is kept in ``self.last_calibration``."""
+        Sets and returns ``self.thresholds``; the sweep's table of the ten figures per cut-off is kept in ``self.last_calibration``.
+        ``scaling``: None, or a ``Scaling``: the cut-offs are chosen on the scaled scores (``eval`` must then be given both)."""
         from .calibrate import ThresholdSweep, check_objective, objective_for
         if self._sentiment():
             step_rules.task_check("sentiment", self.model.senti_loss, calibrate="Solver.calibrate")
+            if scaling is not None:
+                step_rules.scaling_check("sentiment", scaling="Solver.calibrate")
         if objective is None:
             objective = objective_for(getattr(self.train_config, "eval_mode", "macro"), per_class)
         check_objective(objective, per_class)
@@ -474,14 +494,14 @@ class Solver(object):
             raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
         dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
         sweep = ThresholdSweep(int(self.train_config.num_classes), grid, self.device)
-        for scores, emo_label in self._eval_batches(dataloader):
+        for scores, emo_label in self._eval_batches(dataloader, scaling=scaling):
             sweep.update(scores, emo_label)
         self._check_cluster(f"calibrate({mode})")
         self.thresholds = sweep.select(objective, per_class)
         self.last_calibration = dict(table=sweep.table(), grid=sweep.grid, objective=objective, per_class=bool(per_class))
         return self.thresholds
 
-    def _calibrate_after_training(self, have_checkpoint):
+    def _calibrate_after_training(self, have_checkpoint, scaling=None):
         """config.calibrate != "none": the best checkpoint's cut-offs from the dev split, saved by rank 0, for the final test pass."""
         how = getattr(self.train_config, "calibrate", "none")
         if how == "none":
@@ -493,11 +513,75 @@ class Solver(object):
                              f"sharded (shard={self.dev_data_loader.shard}); give every rank the whole dev split or set calibrate='none'")
         if have_checkpoint:
             self._load_best_checkpoint()
-        thresholds = self.calibrate("dev", per_class=how == "per_class")
+        thresholds = self.calibrate("dev", per_class=how == "per_class", scaling=scaling)
         if self.dp is None or self.dp.rank == 0:
             os.makedirs("checkpoints", exist_ok=True)
             thresholds.save(f"checkpoints/thresholds_{self.train_config.name}.pt")
         return thresholds
+
+    # ------------------------------------------------------------------ reliability and logit scaling (mmda_amd/reliability.py)
+    def _score_tables(self, mode, who, confidence, scaling=None):
+        """(scores, truth, labels, tcp or None) of the ``mode`` split, concatenated on the device: the loop of ``rank``"""
+        from . import _lib
+        if mode not in ("dev", "test"):
+            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        S, T, L, Q = [], [], [], []
+        for scores, emo_label, labels, tcp in self._eval_batches(dataloader, confidence=True, scaling=scaling):
+            if not scores.is_cuda:
+                raise _lib.MMDAError(f"{who}() counts on the GPU only (the HIP path has no CPU fallback)")
+            S.append(scores.detach()); T.append(emo_label.detach()); L.append(labels.detach())
+            Q.append(None if tcp is None else tcp.detach())
+        self._check_cluster(f"{who}({mode})")
+        if not S:
+            raise ValueError(f"{who}({mode!r}): the {mode} loader yields no batch")
+        tcp = torch.cat(Q, 0) if confidence and all(q is not None and q.shape == l.shape for q, l in zip(Q, L)) else None
+        return torch.cat(S, 0), torch.cat(T, 0), torch.cat(L, 0), tcp
+
+    def reliability(self, mode="dev", bins=15, scaling=None):
+        """Whether the numbers of the ``mode`` split ("dev" or "test") are probabilities: ``{"scores": reliability_metrics(scores,
+        truth), "confidence": reliability_metrics(tcp, labels == truth)}`` -- ``ReliabilityResult``s on the device, in the shape of
+        ``rank``; ``confidence`` is None where the model has no confidence column per class.  ``scaling``: None, or a ``Scaling`` the
+        scores pass through first (the model's decisions and ``tcp`` do not).  Sets and returns ``self.last_reliability``."""
+        from .reliability import reliability_metrics
+        if self._sentiment():
+            step_rules.scaling_check("sentiment", reliability=True)
+        scores, truth, labels, tcp = self._score_tables(mode, "reliability", True, scaling)
+        out = {"scores": reliability_metrics(scores, truth, bins), "confidence": None}
+        if tcp is not None:
+            correct = (labels > 0) == (truth > 0)
+            out["confidence"] = reliability_metrics(tcp, correct.to(torch.float32), bins)
+        self.last_reliability = out
+        return out
+
+    def fit_scaling(self, mode="dev", how="temperature", per_class=False, max_iter=64):
+        """Fits the logit scaling of the ``mode`` split's scores (``reliability.fit_scaling``: the iteration runs on the device, nothing
+        is read back).  Sets and returns ``self.scaling``."""
+        from .reliability import fit_scaling
+        if self._sentiment():
+            step_rules.scaling_check("sentiment", scaling=how)
+        scores, truth, _, _ = self._score_tables(mode, "fit_scaling", False)
+        self.scaling = fit_scaling(scores, truth, how=how, per_class=per_class, max_iter=max_iter)
+        return self.scaling
+
+    def _scale_after_training(self, have_checkpoint):
+        """config.scaling != "none": the best checkpoint's logit scaling from the dev split, saved by rank 0, for the cut-offs of
+        ``_calibrate_after_training`` and the final test pass."""
+        how = getattr(self.train_config, "scaling", "none")
+        if how == "none":
+            return None
+        if how not in ("temperature", "platt"):
+            raise ValueError(f"config.scaling must be 'none', 'temperature' or 'platt', not {how!r}")
+        if self.dp is not None and getattr(self.dev_data_loader, "shard", None) is not None:
+            raise ValueError(f"scaling={how!r} fits on each rank's own dev loader and exchanges nothing: the dev loader must not be "
+                             f"sharded (shard={self.dev_data_loader.shard}); give every rank the whole dev split or set scaling='none'")
+        if have_checkpoint:
+            self._load_best_checkpoint()
+        scaling = self.fit_scaling("dev", how=how)
+        if self.dp is None or self.dp.rank == 0:
+            os.makedirs("checkpoints", exist_ok=True)
+            scaling.save(f"checkpoints/scaling_{self.train_config.name}.pt")
+        return scaling
 
     # ------------------------------------------------------------------ ranking metrics (mmda_amd/ranking.py, DESIGN.md 4l)
     def rank(self, mode="dev", tpr=0.95, confidence=True):

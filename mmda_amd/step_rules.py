@@ -162,6 +162,30 @@ def modality_check(keep=None, encoded: bool = False) -> None:
         raise MMDAError(dict(MODALITY_RULES)[hit[0]].format(**hit[1]))
 
 
+# What reliability and logit scaling refuse: both read a score as the probability of a label, and the sentiment task's
+# one output column is a regression value.  Refused where it is asked for (config.scaling at Solver.build, Solver.reliability /
+# fit_scaling, a scaling handed to Solver.eval / calibrate), with nothing run.
+SCALING_RULES = (
+    ("senti_scaling", "task='sentiment' with {what} is not built: reliability and logit scaling read a score as the probability of a "
+                      "label, and the sentiment output is a regression value"),
+)
+
+
+def scaling_verdict(task="emotion", scaling="none", reliability=False):
+    """(rule, format values) of the first rule of SCALING_RULES that refuses the setting, or None.  ``scaling``: config.scaling, or any
+    other value than "none" / None for a scaling fitted or applied by a call; ``reliability``: a call of Solver.reliability."""
+    if task == "sentiment" and (reliability or scaling not in (None, "none")):
+        return "senti_scaling", dict(what="Solver.reliability" if reliability else f"logit scaling (scaling={scaling!r})")
+    return None
+
+
+def scaling_check(task="emotion", scaling="none", reliability=False) -> None:
+    """Raises MMDAError with the text of the rule that refuses the setting (``scaling_verdict``'s arguments)."""
+    hit = scaling_verdict(task, scaling, reliability)
+    if hit is not None:
+        raise MMDAError(dict(SCALING_RULES)[hit[0]].format(**hit[1]))
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:

@@ -38,3 +38,14 @@ def save_tcp(args, tensor, dataset=''):
 
 def load_tcp(args, dataset=''):
     return _load(args, "tcp_vectors", dataset)
+
+
+def save_scaling(args, scaling, dataset=''):
+    """A ``Scaling`` (mmda_amd/reliability.py) beside the tcp files, under ``scaling/``: what ``Scaling.save`` writes."""
+    os.makedirs("scaling", exist_ok=True)
+    scaling.save(_file(args, "scaling", dataset))
+
+
+def load_scaling(args, dataset='', device="cpu"):
+    from ..reliability import Scaling
+    return Scaling.load(_file(args, "scaling", dataset), device)
