@@ -69,9 +69,13 @@ int mmda_scratch_release(void);
  * C[b] = epilogue( opA(A[b] (+A2[b])) * opB(B[b]) + bias[b] + bias2[b] (+ C[b] if accumulate) )
  *   opA: transA=0 -> A is (M,K) row-major with leading dim lda; transA=1 -> A is (K,M) row-major
  *   opB: transB=1 -> B is (N,K) row-major (an nn.Linear weight: y = x W^T); transB=0 -> B is (K,N)
- *   gather: optional int64 row ids: row m of A is A + gather[m]*lda (embedding lookup fused into the GEMM)
+ *   gather: optional int64 row ids: row m of A is A + gather[m]*lda (embedding lookup fused into the GEMM).  Read at m < M only:
+ *             the array needs no more than M entries, whatever the tile grid covers.
  *   epilogue: act (MMDA_ACT_*), then optional inverted dropout (p, seed, site) on the result,
  *             then optional gate: C *= (gate[m,n] > 0 ? gate_scale : 0)   (relu/dropout backward)
+ *   batch: entry b reads A + b*strideA, B + b*strideB, bias / bias2 / bias_grad + b*strideBias and writes C + b*strideC.  The gate
+ *             has no stride of its own: entry b reads gate + b*strideC + m*ldgate + n, so a batched gate lies as its C does (one
+ *             batch stride for both, ldgate free).
  * Replaces: every nn.Linear / aten::mm / addmm on the path (models.py:48-55 W_ih, :63-153, :160-161) and their
  * autograd transposes. */
 typedef struct mmda_gemm_args {
@@ -95,6 +99,25 @@ typedef struct mmda_gemm_args {
 int mmda_gemm(const mmda_gemm_args* args, void* stream);
 /* n independent GEMMs (any mix of shapes / layouts / modes) in one launch; results as n mmda_gemm calls in any order */
 int mmda_gemm_grouped(const mmda_gemm_args* args, int n, void* stream);
+/* A read-only view of what mmda_gemm (grouped = 0: each of the n problems as a call of its own) or mmda_gemm_grouped (grouped = 1: the
+ * list in launches of 16) would launch: rows[i] describes problem i.  Host code only -- no launch, no device call; pointers are
+ * validated and inspected for alignment as by the real call but never followed.  The split-K scratch is taken to start 16-byte
+ * aligned.  Returns the number of GEMM launches (the reduce launches behind them not counted), or a negative error; capacity < n is
+ * MMDA_EINVAL. */
+enum { MMDA_GEMM_NONE = -1, MMDA_GEMM_TILE64 = 0, MMDA_GEMM_TILE64TINY = 1, MMDA_GEMM_TILE128 = 2, MMDA_GEMM_GROUPSLOT = 3 };
+typedef struct mmda_gemm_plan_row {
+  int cls;                           /* MMDA_GEMM_*: the 64 x 64 tile with one k-tile of prefetch / with up to four k-tiles loaded up
+                                        front / the 128 x 128 bf16 tile / a slot of the grouped kernel; NONE: an empty problem */
+  int mode, ta, tb;                  /* with cls, the kernel instance: MMDA_F32 / MMDA_BF16, transA, transB */
+  int tx, ty, sk;                    /* output tiles along n (the bias gradient's column included) and m; K slices */
+  int per, last;                     /* k-tiles (of 32) per slice, and of the last slice */
+  int ldn;                           /* row length of a split-K slab: N, + 1 with a bias gradient */
+  int blocks;                        /* workgroups of the problem: tx * ty * batch * sk */
+  int launch;                        /* index of its launch within the call, in issue order (-1: none) */
+  int64_t slab_off;                  /* grouped, sk > 1: where its slab starts in the launch's scratch request, in floats */
+  int reduce;                        /* the reduce launch behind a split problem: 0 none, 1 scalar form, 2 16-byte form */
+} mmda_gemm_plan_row;
+int mmda_gemm_plan_describe(const mmda_gemm_args* args, int n, int grouped, mmda_gemm_plan_row* rows, int capacity);
 
 /* ---------------------------------------------------------------------------------------------- bf16-operand GEMM
  * The LSTM-sized GEMMs of the bf16 mode read bf16 operands that are K-MAJOR (rows of A and of B are contiguous along k):

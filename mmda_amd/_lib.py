@@ -45,6 +45,13 @@ class GemmBf16PlanRow(C.Structure):
                 ("last", C.c_int), ("launch", C.c_int)]
 
 
+class GemmPlanRow(C.Structure):
+    """mmda_gemm_plan_row: what mmda_gemm / mmda_gemm_grouped would do with one problem"""
+    _fields_ = [("cls", C.c_int), ("mode", C.c_int), ("ta", C.c_int), ("tb", C.c_int), ("tx", C.c_int), ("ty", C.c_int), ("sk", C.c_int),
+                ("per", C.c_int), ("last", C.c_int), ("ldn", C.c_int), ("blocks", C.c_int), ("launch", C.c_int),
+                ("slab_off", C.c_int64), ("reduce", C.c_int)]
+
+
 class ConvertJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ld", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("gather", C.c_void_p),
                 ("plain", C.c_void_p), ("ldp", C.c_int), ("transposed", C.c_void_p), ("ldt", C.c_int), ("row_perm_H", C.c_int),
@@ -222,6 +229,7 @@ SIGNATURES = {
     "mmda_debug_gemm_dma_mode": (_I, [_I]),
     "mmda_gemm": (_I, [C.POINTER(GemmArgs), _P]),
     "mmda_gemm_grouped": (_I, [C.POINTER(GemmArgs), _I, _P]),
+    "mmda_gemm_plan_describe": (_I, [C.POINTER(GemmArgs), _I, _I, C.POINTER(GemmPlanRow), _I]),
     "mmda_gemm_bf16_grouped": (_I, [C.POINTER(GemmBf16Args), _I, _P]),
     "mmda_gemm_bf16_plan_describe": (_I, [C.POINTER(GemmBf16Args), _I, C.POINTER(C.c_int), C.POINTER(GemmBf16PlanRow), _I]),
     "mmda_convert_bf16": (_I, [C.POINTER(ConvertJob), _I, _P]),

@@ -566,6 +566,53 @@ int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_a
   return MMDA_OK;
 }
 
+// The plans above as a table, one row per input problem: for tests and tools that need to know which instance a shape runs on.  The
+// same plan_gemm / plan_group as the launchers; the slab is taken to start 16-byte aligned (the scratch buffer is a hipMalloc
+// allocation), so a slot's slab is as aligned as its offset.
+extern "C" int mmda_gemm_plan_describe(const mmda_gemm_args* args, int n, int grouped, mmda_gemm_plan_row* rows, int capacity) {
+  if (!args || !rows || n < 0 || capacity < n) return MMDA_EINVAL;
+  const mmda_gemm_plan_row none = {MMDA_GEMM_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0, 0};
+  auto row_of = [&](const mmda_gemm_args& a, int cls, int tx, int ty, int sk, int ldn, int launch, int64_t slab_off) {
+    const int nk = ceil_div(a.K, BK), per = ceil_div(nk, sk);
+    mmda_gemm_plan_row r = {cls, a.mode, a.transA ? 1 : 0, a.transB ? 1 : 0, tx, ty, sk, per, nk - (sk - 1) * per, ldn,
+                            tx * ty * a.batch * sk, launch, slab_off, 0};
+    if (sk > 1) {
+      const SplitKJob J = splitk_job(a, reinterpret_cast<const float*>((uintptr_t)slab_off * sizeof(float)), ldn, sk);
+      r.reduce = splitk_reduce_is_vec(J) ? 2 : 1;
+    }
+    return r;
+  };
+  int launches = 0;
+  if (!grouped) {
+    for (int i = 0; i < n; ++i) {
+      const mmda_gemm_args& a = args[i];
+      if (!valid_operands(a)) return MMDA_EINVAL;
+      rows[i] = none;
+      if (empty_problem(a)) continue;
+      if (!valid_problem(a)) return MMDA_EINVAL;
+      const GemmPlan P = plan_gemm(a);
+      if (P.rc) return P.rc;
+      static_assert((int)GemmClass::Tile64 == MMDA_GEMM_TILE64 && (int)GemmClass::Tile64Tiny == MMDA_GEMM_TILE64TINY &&
+                    (int)GemmClass::Tile128 == MMDA_GEMM_TILE128, "");
+      rows[i] = row_of(a, (int)P.cls, (int)P.grid.x, (int)P.grid.y, P.sk, P.ldn, launches++, 0);
+    }
+    return launches;
+  }
+  for (int base = 0; base < n; base += GROUP_MAX) {
+    const int cnt = (n - base) < GROUP_MAX ? (n - base) : GROUP_MAX;
+    const GroupPlan P = plan_group(args + base, cnt, nullptr, 0);
+    if (P.rc) return P.rc;
+    for (int i = 0; i < cnt; ++i) rows[base + i] = none;
+    if (P.blocks == 0) continue;
+    for (int k = 0; k < P.n; ++k) {
+      const GroupSlot& S = P.slot[k];
+      rows[base + S.problem] = row_of(args[base + S.problem], MMDA_GEMM_GROUPSLOT, S.tx, S.ty, S.sk, S.ldn, launches, S.slab_off);
+    }
+    ++launches;
+  }
+  return launches;
+}
+
 extern "C" int mmda_colsum(const float* X, int ld, int M, int N, float* out, float* out2, void* stream) {
   if (!X || !out || M < 0 || N <= 0) return MMDA_EINVAL;
   if (M == 0) return MMDA_OK;

@@ -31,4 +31,11 @@ static inline int splitk_slices(int nk, int sk) {
   return ceil_div(nk, per);
 }
 
+// The reduce launch has two forms.  The 16-byte one (a thread sums four neighbouring columns) takes a job whose slab rows, output rows
+// and both bases are 16-byte aligned: ldn, N and ldc multiples of four, one batch entry.  Every other job goes to the scalar form.
+// Read by the reduce launcher and by the plan views (mmda_gemm_plan_describe).
+static inline bool splitk_reduce_is_vec(const SplitKJob& J) {
+  return J.batch == 1 && !(J.ldn & 3) && !(J.N & 3) && !(J.ldc & 3) && !((uintptr_t)J.C & 15) && !((uintptr_t)J.slab & 15);
+}
+
 int mmda_splitk_reduce(const SplitKJob* jobs, int n, hipStream_t s);   // splitk.hip

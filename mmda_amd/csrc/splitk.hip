@@ -89,9 +89,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(SplitKLaunch L) {
 
 int mmda_splitk_reduce(const SplitKJob* jobs, int n, hipStream_t s) {
   // jobs that qualify for the 16-byte form go out in launches of their own
-  auto is_vec = [](const SplitKJob& J) {
-    return J.batch == 1 && !(J.ldn & 3) && !(J.N & 3) && !(J.ldc & 3) && !((uintptr_t)J.C & 15) && !((uintptr_t)J.slab & 15);
-  };
   for (int form = 0; form < 2; ++form) {
     SplitKLaunch L;
     int blocks = 0;
@@ -108,7 +105,7 @@ int mmda_splitk_reduce(const SplitKJob* jobs, int n, hipStream_t s) {
     };
     for (int i = 0; i < n; ++i) {
       const SplitKJob& J = jobs[i];
-      if ((is_vec(J) ? 1 : 0) != form) continue;
+      if ((splitk_reduce_is_vec(J) ? 1 : 0) != form) continue;
       if (L.n == SPLITK_JOBS_MAX) { const int rc = flush(); if (rc) return rc; }
       L.j[L.n] = J;
       L.start[L.n] = blocks;

@@ -79,6 +79,34 @@ def gemm_grouped(problems):
     return [out for _, out in built]
 
 
+GEMM_CLASSES = ("Tile64", "Tile64Tiny", "Tile128", "GroupSlot")
+GEMM_REDUCE = (None, "scalar", "vector")
+
+
+def gemm_plan(problems, grouped=False):
+    """What mmda_gemm (each problem a call of its own) or, grouped, mmda_gemm_grouped would launch for these problems
+    (mmda_gemm_plan_describe: host code only, works without a GPU).  problems: _lib.GemmArgs structures, or dicts of their field names
+    (pointer fields as integers: only their alignment matters; batch defaults to 1, A / B / C to an aligned address).  Returns (rows,
+    launches): one dict per problem -- cls (a name of GEMM_CLASSES, None for an empty problem), mode, ta, tb, tx, ty, sk, per, last, ldn,
+    blocks, launch, slab_off, reduce (None, "scalar" or "vector") -- and the number of GEMM launches."""
+    arr = (_lib.GemmArgs * max(1, len(problems)))()
+    for k, p in enumerate(problems):
+        if isinstance(p, _lib.GemmArgs):
+            C.memmove(C.byref(arr[k]), C.byref(p), C.sizeof(_lib.GemmArgs))
+            continue
+        g = arr[k]
+        g.batch = 1; g.A = g.B = g.C = 1 << 20
+        for name, v in p.items():
+            setattr(g, name, v)
+    rows = (_lib.GemmPlanRow * max(1, len(problems)))()
+    n = load().mmda_gemm_plan_describe(arr, len(problems), int(bool(grouped)), rows, len(problems))
+    if n < 0:
+        check(n, "mmda_gemm_plan_describe")
+    return [dict(cls=GEMM_CLASSES[r.cls] if r.cls >= 0 else None, mode=r.mode, ta=bool(r.ta), tb=bool(r.tb), tx=r.tx, ty=r.ty, sk=r.sk,
+                 per=r.per, last=r.last, ldn=r.ldn, blocks=r.blocks, launch=r.launch, slab_off=r.slab_off, reduce=GEMM_REDUCE[r.reduce])
+            for r in rows[:len(problems)]], n
+
+
 def convert_bf16(jobs):
     """jobs: list of (src[rows, cols] fp32 or bf16, gather or None, want_plain, want_transposed) -> list of (plain, transposed) bf16 tensors.
 

@@ -32,11 +32,12 @@ def test_struct_sizes_match_c_layout():
     code = textwrap.dedent("""
         #include <stdio.h>
         #include "mmda_hip.h"
-        int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mmda_gemm_args), sizeof(mmda_ln_args), sizeof(mmda_ln_bwd_args),
+        int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mmda_gemm_args), sizeof(mmda_ln_args), sizeof(mmda_ln_bwd_args),
                           sizeof(mmda_lstm_desc), sizeof(mmda_misa_config), sizeof(mmda_gemm_bf16_args),
                           sizeof(mmda_convert_job), sizeof(mmda_skinny_args), sizeof(mmda_transpose_job), sizeof(mmda_gru_pad_job),
                           sizeof(mmda_mx8_quant_job), sizeof(mmda_mx8_args), sizeof(mmda_act_params), sizeof(mmda_lstm_plan),
-                          sizeof(mmda_loss_forms), sizeof(mmda_misa_step_request), sizeof(mmda_misa_step_plan));
+                          sizeof(mmda_loss_forms), sizeof(mmda_misa_step_request), sizeof(mmda_misa_step_plan),
+                          sizeof(mmda_gemm_plan_row));
                    return 0;}""")
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(code)
@@ -45,7 +46,7 @@ def test_struct_sizes_match_c_layout():
     sizes = [ctypes.sizeof(x) for x in (_lib.GemmArgs, _lib.LnArgs, _lib.LnBwdArgs, _lib.LstmDesc, _lib.MisaConfig,
                                        _lib.GemmBf16Args, _lib.ConvertJob, _lib.SkinnyArgs, _lib.TransposeJob, _lib.GruPadJob,
                                        _lib.Mx8QuantJob, _lib.Mx8Args, _lib.ActParams, _lib.LstmPlan, _lib.LossForms, _lib.MisaStepRequest,
-                                       _lib.MisaStepPlan)]
+                                       _lib.MisaStepPlan, _lib.GemmPlanRow)]
     assert [int(x) for x in out] == sizes
 
 
