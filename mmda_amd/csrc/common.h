@@ -255,7 +255,7 @@ struct RowDenseAdam {
   }
 };
 
-// ---- flag joins (misa.hip: side_flag_signal): a kernel of one stream waits, on the device, for a word that a one-thread launch behind
+// ---- flag joins (misa_streams.hip: side_flag_signal): a kernel of one stream waits, on the device, for a word that a one-thread launch behind
 // the last kernel of ANOTHER stream's chain sets to `value` -- instead of a stream-level event wait, which costs the waiting stream
 // 9 - 12 us of packet processing however early the other chain finished (tools/micro/fork_cost.hip).  Called by every thread of the
 // workgroup; thread 0 polls (bounded: a word that never arrives is reported through *err and the kernel goes on), a workgroup

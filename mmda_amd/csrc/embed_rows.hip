@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void embed_rows_append_kernel(int64_t* ids_out
 constexpr int RE = 5;
 __device__ __forceinline__ void replay_row(float* p, float* m, float* v, int D, int lane, int a, int t, const float* __restrict__ ring,
                                            int window, float b1, float b2, float eps) {
-  a = max(a, max(t - window, 0));      // memory safety only: the hosts that count the updates (misa.hip, ops.py) flush before a row gets here
+  a = max(a, max(t - window, 0));      // memory safety only: the hosts that count the updates (misa_step.hip, ops.py) flush before a row gets here
   for (int c0 = 0; c0 < D; c0 += 64 * RE) {
     float pe[RE], me[RE], ve[RE];
 #pragma unroll
@@ -434,7 +434,7 @@ extern "C" int mmda_embed_gather(const float* W, const int64_t* ids, int rows, i
 // ---- RowAdd: the dense gradient
 bool mmda_embed_scatter_sorts(int rows) { return list_form(nullptr, rows, false) == ListForm::Sort; }
 
-// (internal, misa.hip) dW[id] += the list-order sum of the id's rows.  A sorted list has table_rows as its pad key
+// (internal, misa_backward.hip) dW[id] += the list-order sum of the id's rows.  A sorted list has table_rows as its pad key
 // (mmda_embed_sort_ids); an unsorted one is keyed here with no bound on its ids, all 32 key bits
 int mmda_embed_list_add(float* dW, const EmbedList& l, int table_rows, void* stream) {
   const bool presorted = list_form(l.sorted, l.n, false) == ListForm::Presorted;
@@ -463,7 +463,7 @@ extern "C" int mmda_embed_segment_sum(float* dW, const int64_t* ids, int n, int 
                           (hipStream_t)stream, "mmda_embed_segment_sum");
 }
 
-// ---- the sorted list on its own (internal, misa.hip): it depends on the ids only, so a training step makes it early, beside a
+// ---- the sorted list on its own (internal, misa_backward.hip): it depends on the ids only, so a training step makes it early, beside a
 // recurrence, and only the sums wait for the gradient rows.  `sorted`: 2 n words the caller keeps (keys, then positions);
 // table_rows: ids lie in [0, table_rows).
 int mmda_embed_sort_ids(const int64_t* ids, int n, const int* lengths, int B, int table_rows, unsigned* sorted, void* stream) {
@@ -555,7 +555,7 @@ extern "C" int mmda_embed_rows_flush(float* P, float* M, float* V, int32_t* row_
   return MMDA_OK;
 }
 
-// internal (misa.hip): update number `seq` (the count of updates since the reset, last + 1), made with Adam step number `step`, for
+// internal (misa_step.hip): update number `seq` (the count of updates since the reset, last + 1), made with Adam step number `step`, for
 // the rows of an id list.  Counts that are multiples of the window flush the table first: the slot this update's scalars take is then
 // needed by no row.  catch_up: bring the list's rows to seq - 1 first (a forward of the same
 // batch has done so already inside a training step).  sorted != nullptr: the list as mmda_embed_sort_ids left it.

@@ -531,7 +531,7 @@ extern "C" int mmda_gemm_grouped(const mmda_gemm_args* args, int n, void* stream
   return mmda_gemm_grouped_sized(args, n, nullptr, 0, stream);
 }
 
-// internal (misa.hip): the same launch with its split-K sized as if the `absent` problems were part of it too (they are not run).
+// internal (misa_pass.h): the same launch with its split-K sized as if the `absent` problems were part of it too (they are not run).
 // A step that leaves a product out (frozen embedding table: no text layer-1 dX) keeps the slices, and so the bits, of the products
 // that stay.  Counted into the first GROUP_MAX problems' launch.
 int mmda_gemm_grouped_sized(const mmda_gemm_args* args, int n, const mmda_gemm_args* absent, int n_absent, void* stream) {

@@ -28,7 +28,7 @@ __device__ __forceinline__ void copy_row(const float* __restrict__ src, float* _
 
 // One wave per batch column b, lanes along a row; the four waves of a workgroup take four adjacent columns; blockIdx.y picks the field.
 // A wave reads its row index once (dst[b], or base + b), so every address of its segment is known up front.  Source layouts, as the
-// forward leaves them (misa.hip):
+// forward leaves them (misa_forward.hip):
 //   scores / labels (B, C), tcp (B, 6): row b.
 //   hfused: LayerNorm 2 runs over rows (s, b) of the (6, B, hs) token block and writes them PERMUTED -- norm2_fwd sets permute_S = 6,
 //     permute_B = B, so row (s * B + b) lands at b * 6 hs + s * hs -- and the head GEMM reads the result as (B, 6 hs) with lda = 6 hs.

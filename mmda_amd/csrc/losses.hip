@@ -646,7 +646,7 @@ __device__ __forceinline__ void cmd_fast_body(const float* __restrict__ x, int64
 
 template <int CMD_RPT>
 // tail_flag (optional): set to tail_value when the (single) workgroup's stores are out -- the launch is the last of a stream's chain
-// and another stream's kernel waits for that word on the device (misa.hip: flag joins), instead of a one-thread launch behind it
+// and another stream's kernel waits for that word on the device (misa_streams.hip: flag joins), instead of a one-thread launch behind it
 __global__ __launch_bounds__(1024) void cmd_fast_kernel(const float* __restrict__ x, int64_t stride, int B, int D, float scale,
                                                         float vscale, float* loss, float* dx, PairList pl, int nmom,
                                                         unsigned* tail_flag, unsigned tail_value) {
@@ -1210,7 +1210,7 @@ bool mmda_loss_cmd_sets_flag(int B, int D) {
   return form == MMDA_LOSS_CMD_FAST4 || form == MMDA_LOSS_CMD_FAST8;
 }
 
-// internal (misa.hip): mmda_loss_cmd_pairs that sets *flag = value at the end of its launch (flag == nullptr: the plain call)
+// internal (misa_forward.hip): mmda_loss_cmd_pairs that sets *flag = value at the end of its launch (flag == nullptr: the plain call)
 int mmda_loss_cmd_pairs_tail(const float* x, int64_t stride, int nt, int np, const int* pairs_host, int n_moments, int B, int D, float scale,
                              float value_scale, float* loss, float* dx, void* stream, unsigned* flag, unsigned value) {
   PairList pl;                                            // (at most three tensors: what the fast forms hold)

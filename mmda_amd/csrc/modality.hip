@@ -7,7 +7,7 @@
 
 namespace {
 
-enum { SITE_MODALITY = 11 };                                   // the next id after misa.hip's dropout sites
+enum { SITE_MODALITY = 11 };                                   // the next id after misa_handle.h's dropout sites
 
 using DropP = mmda_modality_p;
 

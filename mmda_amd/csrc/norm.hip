@@ -501,7 +501,7 @@ extern "C" int mmda_layernorm_bwd_multi(const mmda_ln_bwd_args* a, int n, void* 
 }
 extern "C" int mmda_layernorm_bwd(const mmda_ln_bwd_args* a, void* stream) { return mmda_layernorm_bwd_multi(a, a ? 1 : -1, stream); }
 
-// Internal (misa.hip): the backward of up to LN_MAXP plain LayerNorms with the gamma / beta gradients left as per-block partials in a
+// Internal (misa_backward.hip): the backward of up to LN_MAXP plain LayerNorms with the gamma / beta gradients left as per-block partials in a
 // caller-owned buffer (`parts`, mmda_ln_parts_floats floats) -- the d_x launch on the critical stream computes them on the way (it
 // reads dy and x anyway), and mmda_ln_parts_finish adds them up on whatever stream the caller likes (behind an event).  Replaces
 // the separate column-strip pass over dy and x (mmda_layernorm_param_grads: 100 us at B = 256) when the 16-byte form applies.

@@ -407,7 +407,7 @@ int launch_runs(const char* what, const RunTable& t, const F& f, const FlagWait&
 
 }  // namespace
 
-// internal.h: the launch behind every mmda_clamp_adam* entry (and misa.hip's).  A waiter with nothing to update gets the dense stream
+// internal.h: the launch behind every mmda_clamp_adam* entry (and misa_step.hip's).  A waiter with nothing to update gets the dense stream
 // over no floats.
 int mmda_adam_launch(float* p, const float* acc, const float* g, float* m, float* v, int64_t n, const RunTable* table, const AdamHyper& h,
                      const FlagWait& w, void* stream) {
@@ -490,7 +490,7 @@ extern "C" int64_t mmda_grad_norm_partials(int64_t n_or_items) {
   return stream_blocks(n_or_items);                        // >= the blocks of a dense launch over n floats and of a run launch over n items
 }
 
-// internal.h: the two launches behind mmda_grad_norm (and misa.hip's)
+// internal.h: the two launches behind mmda_grad_norm (and misa_step.hip's)
 int mmda_grad_norm_launch(const float* g, const float* acc, int64_t n, const RunTable* table, float max_norm, float grad_scale,
                           double* partials, int64_t partials_capacity, float* out2, void* stream) {
   if (!g || !partials || !out2 || !(max_norm >= 0.f)) return MMDA_EINVAL;
@@ -606,7 +606,7 @@ extern "C" int mmda_clamp_rmsprop_runs(float* p, const float* g, float* square_a
   return launch_runs("mmda_clamp_rmsprop_runs", RunTable{runs, n_runs, items}, f, kNoWait, stream);
 }
 
-// internal (misa.hip): a[0 .. na) = b[0 .. nb) = 0 in ONE launch (two memsets are two launches of ~5 us each on a latency-bound chain)
+// internal (misa_forward.hip): a[0 .. na) = b[0 .. nb) = 0 in ONE launch (two memsets are two launches of ~5 us each on a latency-bound chain)
 int mmda_zero2(float* a, int64_t na, float* b, int64_t nb, void* stream) {
   if (na < 0 || nb < 0 || (na && !a) || (nb && !b)) return MMDA_EINVAL;
   if (((uintptr_t)a | (uintptr_t)b) & 15 || (na & 3) || (nb & 3)) {           // odd shapes: the runtime's fills

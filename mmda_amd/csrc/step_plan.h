@@ -1,6 +1,6 @@
 // The three values one MISA training step is built from, each made by a pure host function (step_plan.hip: no HIP call, no handle, no
-// environment): the parameter table (build_params), the workspace carve (carve) and the step's plan (plan_step).  misa.hip holds them
-// on its handle and issues the launches they describe.
+// environment): the parameter table (build_params), the workspace carve (carve) and the step's plan (plan_step).  The handle (misa_handle.h)
+// holds them and the misa*.hip files issue the launches they describe.
 #pragma once
 #include "common.h"
 #include "fused_rows.h"
@@ -70,7 +70,7 @@ struct Workspace {
   int64_t d_scores, d_tcp, d_x6, d_orig, d_recon, d_dom, d_logits, d_hfused, d_x1, d_f2, d_f1, d_attn_out, d_ctx, d_qkv, d_z,
       d_dom_h, d_dom_z;
   int64_t gnorm = -1, gnorm_parts = -1;      // clip_norm: norm and coefficient of the last such step; the norm launch's block partials (doubles)
-  int64_t esort = -1;                        // sorted (id, position) list of the step's text ids (see mmda_misa::esort_valid)
+  int64_t esort = -1;                        // sorted (id, position) list of the step's text ids (see StepState::esort_valid)
   int64_t rec_part = -1;
 };
 // The workspace for (B, T) batches, as a value: sizes one (Workspace::floats) and is what a bound buffer is read through.
@@ -106,14 +106,14 @@ struct StepPlan {
   bool skinny = false;              // fusion block on row-skinny GEMMs (B <= SKINNY_MAX_B), else on the tiled generic kernel
   bool row_fuse = false;            // ... as fused row-local stretches (the backward pass also needs wT_valid)
   bool ffn_fuse_fwd = false, ffn_fuse_bwd = false;   // the feed-forward pair fused (forward / backward differ: see plan_step)
-  bool seed_recon = false, seed_cls = false;         // the forward stretches store these loss seeds (see mmda_misa::misc_deferred)
+  bool seed_recon = false, seed_cls = false;         // the forward stretches store these loss seeds (see StepState::misc_deferred)
   bool fj_on = false, fj_fwd = false, fj_device = false;   // flag joins; the forward one; ... waited for on the device
   bool zg_here = false;             // the gradient bucket is cleared at the head of the loss chain (eager_side_losses)
   bool rec_hoisted = false;         // stretch C's launch makes d_recon W_rec for stretch A
   bool sort_early = false;          // the embedding scatter's id list is sorted beside the layer-2 backward recurrence
   int embed_update = 0;             // EU_*: how the step treats the embedding table (mmda_misa_set_embed_update)
   bool embed_deferred = false;      // dense, with the table's update applied row by row when a row is next needed (mmda_misa_set_embed_deferred)
-  // The table rows the batch does not index take the step on a low-priority stream beside the forward pass (mmda_misa::bg; DESIGN section
+  // The table rows the batch does not index take the step on a low-priority stream beside the forward pass (BgStream; DESIGN section
   // 4a), by embed_bg_wgs workgroups, forked behind the step's first launch or (embed_bg_late) behind the layer-1 forward recurrence.
   bool embed_bg = false, embed_bg_late = false; int embed_bg_wgs = 0, embed_bg_lds = 0;
 };

@@ -292,11 +292,11 @@ StepPlan plan_step(const PlanInput& in, const StepSwitches& sw) {
   // backward pass reads the f32 f1 / f2 it writes like the exact path's, so the fused dX kernel serves it as well.
   P.ffn_fuse_fwd = P.row_fuse && sw.ffn_fuse && !in.fusion_fp8 && (FFN % 32) == 0;
   P.ffn_fuse_bwd = P.row_fuse && sw.ffn_fuse && (FFN % 32) == 0;
-  // loss seeds by the stretches of a fused step that knows its labels (see mmda_misa::misc_deferred); MMDA_LOSS_SEEDS=0: by the loss
+  // loss seeds by the stretches of a fused step that knows its labels (see StepState::misc_deferred); MMDA_LOSS_SEEDS=0: by the loss
   // launch behind the forward pass, as before
   P.seed_recon = sw.loss_seeds && P.row_fuse && in.fused && in.has_labels;
   P.seed_cls = P.seed_recon && !c.use_confidNet;
-  // flag joins (see mmda_misa::jflags) in a fused training step
+  // flag joins (see SideStream::jflags) in a fused training step
   P.fj_on = sw.flag_join && in.use_side && in.fused;
   P.fj_fwd = P.fj_on && P.seed_recon && P.seed_cls;
   P.fj_device = P.fj_fwd && B <= FJ_DEVICE_MAX_B;
