@@ -1176,6 +1176,32 @@ int mmda_modality_mask(const int64_t* ids, const float* v, const float* a, int T
                        int keep_const, int pad_id, int unk_id, int64_t* out_ids, float* out_v, float* out_a, void* stream);
 int mmda_modality_attrib(const float* V, int64_t n, int C, float* phi, float* loo, int32_t* dominant, int64_t* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- MC-dropout statistics
+ * K stochastic draws per sample reduced to per-SAMPLE float64 tables in ONE launch (mmda_amd/uncertainty.py).
+ * p fp32 (B K, W) row-major: row b K + k is draw k of sample b.  Sample b writes row dst[b] (int32, device) of every table that is not
+ * NULL, or row base + b when dst is NULL; offsets are 64-bit and NOTHING checks the rows (mmda_infer_collect's contract).  The tables
+ * are (n, W) float64; draws is (n, K, W) fp32, the draws themselves, copied.  Per (sample, column), every fp32 draw widened once:
+ *   mean = (1/K) sum p_k;  var = (1/K) sum (p_k - mean)^2, the population form, a second pass over the same values, exactly 0 at K = 1;
+ *   vote = the share of draws with p_k > thr[w] (fp32 compare; a NaN draw is not above); skipped when thr is NULL;
+ *   bernoulli != 0, with h(q) = -q ln q - (1 - q) ln(1 - q) in nats and h(0) = h(1) = 0: entropy = h(mean), expected_entropy =
+ *     (1/K) sum h(p_k), mutual_info = max(0, entropy - expected_entropy).  bernoulli == 0: those three pointers must be NULL.
+ * A NaN draw makes mean, var and the three entropy figures of its (sample, column) NaN -- the vote stays the count it is -- and touches
+ * no other element.  One wave per (sample, column); lane l adds its draws k = l, l + 64, ... in that order and a fixed xor butterfly
+ * adds the lanes: the order of every addition is a function of K alone, so the bits of a sample depend neither on B, dst nor the run.
+ * No atomics.  MMDA_EINVAL, with nothing launched: p or out NULL; every table NULL (a vote table without thr counts as NULL); B < 1, K
+ * outside 1 .. 256, W outside 1 .. 64; an entropy table without bernoulli.
+ * mmda_misa_mc_reduce: the same with p and W taken from the model's current workspace carve -- which = 0: scores (B K, ncls), Bernoulli
+ *   (but not under the sentiment task, whose one column is no probability); which = 1: tcp (B K, 6), not Bernoulli.  The carve's B must
+ *   be a multiple of K; MMDA_EINVAL otherwise, for another `which`, or when the model has no workspace. */
+typedef struct mmda_mc_out {
+  double* mean; double* var; double* entropy; double* expected_entropy; double* mutual_info; double* vote;
+  float* draws;
+} mmda_mc_out;
+int mmda_mc_reduce(const float* p, int B, int K, int W, const float* thr, int bernoulli, const mmda_mc_out* out, const int32_t* dst,
+                   int64_t base, void* stream);
+int mmda_misa_mc_reduce(mmda_misa* m, int K, int which, const float* thr, const mmda_mc_out* out, const int32_t* dst, int64_t base,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,10 @@ attributes a value to the three modalities (``ModalityPass`` / ``ModalityResult`
 values from one launch); ``reliability`` asks whether the scores are probabilities (``reliability_metrics`` / ``ReliabilityEval``: the
 reliability diagram, ECE, MCE, Brier score and NLL per class from one integer state a launch per batch adds to) and fits the monotone
 rescaling that makes them so (``fit_scaling`` -> ``Scaling``: temperature or Platt scaling of the logits, per class or shared, by a
-damped Newton iteration whose state never leaves the device; ``config.scaling``).
+damped Newton iteration whose state never leaves the device; ``config.scaling``); ``uncertainty`` gives ``tcp`` its baselines
+(``MCDropoutPass`` / ``MCDropoutResult``: K dropout draws per sample from ONE forward of the fusion block over rows repeated K times,
+reduced on the device to mean, variance, entropy and mutual information; ``mc_statistics``: that reduction over any table;
+``config.mc_passes``).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -28,3 +31,4 @@ from .ranking import RankingResult, failure_prediction, rank_plan, ranking_metri
 from .sentiment import SentimentEval, sentiment_metrics  # noqa: F401
 from .modality import MODALITIES, ModalityPass, ModalityResult, keep_bits, parse_keep  # noqa: F401
 from .reliability import ReliabilityEval, ReliabilityResult, Scaling, fit_scaling, reliability_metrics  # noqa: F401
+from .uncertainty import MCDropoutPass, MCDropoutResult, mc_statistics  # noqa: F401

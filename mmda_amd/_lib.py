@@ -213,6 +213,15 @@ class ModalityP(C.Structure):
     _fields_ = [("p", C.c_float * 3)]
 
 
+class McOut(C.Structure):
+    """mmda_mc_out: the per-sample tables of an MC-dropout reduction (None = not written); float64 but for ``draws`` (fp32)"""
+    _fields_ = [("mean", C.c_void_p), ("var", C.c_void_p), ("entropy", C.c_void_p), ("expected_entropy", C.c_void_p),
+                ("mutual_info", C.c_void_p), ("vote", C.c_void_p), ("draws", C.c_void_p)]
+
+
+MC_MAX_PASSES, MC_MAX_WIDTH = 256, 64            # the K and W one mmda_mc_reduce launch takes
+
+
 CELL = {"lstm": 0, "gru": 1}
 TASK = {"emotion": 0, "sentiment": 1}            # MMDA_TASK_*
 SENTI_LOSS = {"l1": 0, "mse": 1}                 # MMDA_SENTI_*
@@ -393,6 +402,8 @@ SIGNATURES = {
     "mmda_collate_gather_masked": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, ModalityP, _U64, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mmda_modality_mask": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "mmda_modality_attrib": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P]),
+    "mmda_mc_reduce": (_I, [_P, _I, _I, _I, _P, _I, C.POINTER(McOut), _P, _I64, _P]),
+    "mmda_misa_mc_reduce": (_I, [_P, _I, _I, _P, C.POINTER(McOut), _P, _I64, _P]),
 }
 
 _lib = None

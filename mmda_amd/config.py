@@ -124,6 +124,10 @@ DEFAULTS = dict(
     # of the scores (a alone / a and b; mmda_amd/reliability.py) on the dev split with the best checkpoint; the cut-offs
     # of `calibrate` are then chosen on, and the final test evaluation scores with, the scaled scores; "none": raw scores throughout
     scaling="none",
+    # after the final test pass of Solver.train(): N > 0 runs MC dropout with N draws per sample over the test split with the best
+    # checkpoint (mmda_amd/uncertainty.py) and prints how each confidence -- maximum class probability, the MC-dropout
+    # figures, ConfidNet's tcp -- ranks the right decisions above the wrong ones; 0: nothing happens
+    mc_passes=0,
 )
 
 

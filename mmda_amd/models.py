@@ -899,6 +899,26 @@ class MISA(nn.Module):
             setattr(self, k, val)
         return pub["scores"].clone(), pub["labels"].clone()
 
+    def _forward_encoded_raw(self, cache, rows_ptr: int, B: int, training: bool, seed: int):
+        """A forward from ``B`` cached rows (``rows_ptr``: their int32 indices on the device, repeats allowed) that no backward will
+        follow: ``mmda_misa_set_inference(1)`` and ``mmda_misa_forward_encoded`` at the carve (B, 1), with the seed it is GIVEN -- none
+        is drawn.  Unlike ``_encoded_begin`` it does not ask for the encoder cut: an inference forward trains nothing, so the cached
+        rows only have to be those of the current encoders (the caller's concern: ``EncoderCache`` fingerprints).  Results stay in
+        the workspace (mmda_amd/uncertainty.py reduces them there)."""
+        cache._refuse(self)                                  # another device, other widths
+        if cache.device.type != "cuda":
+            raise _lib.MMDAError(f"the cache is on {cache.device}: mmda_amd.MISA has no CPU path (HIP kernels only)")
+        if not self._views_valid():
+            self._materialize(cache.device)
+        self._carve(int(B), 1, cache.device)
+        eb = _lib.EncodedBatch(tab_t=cache.utt_t.data_ptr(), tab_v=cache.utt_v.data_ptr(), tab_a=cache.utt_a.data_ptr(), tab_emo=None,
+                               rows=rows_ptr, B=int(B))
+        _lib.check(self._lib.mmda_misa_set_inference(self._h, 1), "set_inference")
+        _lib.check(self._lib.mmda_misa_forward_encoded(self._h, C.byref(eb), int(training), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.stream_ptr()),
+                   "mmda_misa_forward_encoded")
+        self._fwd_id += 1
+        self._last = dict(encoded=cache)
+
     def _accum_micro_step(self, sentences, video, acoustic, lengths, emo_label, lr, clip, do_adam, training, seed, grad_sync, optimizer,
                           index, count, clip_norm=None) -> None:
         """Micro-batch ``index`` of an optimizer step made from ``count``: the native step without its optimizer part, then either the

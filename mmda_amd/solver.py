@@ -289,6 +289,10 @@ class Solver(object):
         test_loss, acc, _, _ = self.eval(mode="test", to_print=best_epoch >= 0, thresholds=thresholds, scaling=scaling)
         if self._sentiment():
             self._print_sentiment()
+        if int(getattr(cfg, "mc_passes", 0) or 0) > 0:     # (0, the default: nothing below runs)
+            if best_epoch >= 0:
+                self._load_best_checkpoint()
+            self.uncertainty("test", passes=int(cfg.mc_passes), to_print=True)
         print("=" * 50)
         print(f"Best epoch: {best_epoch}")
         print(f"Accuracy: {acc}")
@@ -666,6 +670,55 @@ class Solver(object):
             phi = res.attribution(which)["phi"].mean(dim=0).cpu().numpy()
             tcp = None if res.tcp is None else res.tcp.mean(dim=(1, 2)).cpu().numpy()
             print(format_table(metrics, tcp, phi))
+        return res
+
+    # ------------------------------------------------------------------ MC-dropout uncertainty (mmda_amd/uncertainty.py)
+    def uncertainty(self, mode="dev", passes=None, to_print=False, seed=0, columns=256):
+        """MC dropout over the ``mode`` split ("dev" or "test") -> ``MCDropoutResult``, on the device: ``passes`` draws per sample
+        (None: ``config.mc_passes``, or 32 where that is 0) from one forward of the fusion block per chunk.  A ``DeviceLoader``'s
+        dataset is used as it is, an ``EncodedLoader``'s cache goes through ``run_cache``, and any other loader's ``dataset`` of the
+        reference's samples is uploaded once (``DeviceDataset.from_samples``).  ``self.last_uncertainty``: per kind of confidence --
+        maximum class probability, the MC-dropout figures and, with ConfidNet, ``tcp`` and its mean over the draws -- the macro
+        AUROC, AUPR-Success, AUPR-Error and FPR@95TPR of "does it rank the right decisions above the wrong ones", every kind against
+        the same deterministic decisions (this read-back and the cluster check are the call's waits; the pass itself has none).
+        ``to_print``: that table."""
+        from .data import DeviceDataset, DeviceLoader
+        from .uncertainty import KINDS, MCDropoutPass, check_settings
+        if mode not in ("dev", "test"):
+            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        cfg = self.train_config
+        if passes is None:
+            passes = int(getattr(cfg, "mc_passes", 0) or 0) or 32
+        check_settings(passes, columns, getattr(cfg, "task", "emotion"))
+        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        p = MCDropoutPass(self.model, passes=passes, seed=seed, columns=columns)
+        if isinstance(loader, EncodedLoader):
+            res, truth = p.run_cache(loader.cache), loader.cache.emo
+        else:
+            ds = loader.dataset if isinstance(loader, DeviceLoader) else None
+            if ds is None:
+                src = getattr(loader, "dataset", None)
+                if src is None or src is loader or not hasattr(src, "__len__"):
+                    raise ValueError(f"uncertainty({mode!r}) re-batches the split's samples: the {mode} loader must be a DeviceLoader, an "
+                                     f"EncodedLoader or have a `dataset` of the reference's samples (it is a {type(loader).__name__})")
+                ds = DeviceDataset.from_samples([src[i] for i in range(len(src))], next(self.model.parameters()).device)
+            res, truth = p.run(ds, getattr(loader, "batch_size", None) or cfg.batch_size), ds.emo
+        self._check_cluster(f"uncertainty({mode})")
+        self.last_uncertainty = None
+        if truth is not None and truth.shape == res.labels.shape:
+            kinds = tuple(k for k in KINDS if not k.startswith("tcp") or
+                          (bool(getattr(cfg, "use_confidNet", False)) and res.tcp.shape == res.labels.shape))
+            table = {}
+            for k, fp in res.failure_table(truth, kinds).items():
+                d = fp.as_dict()
+                table[k] = dict(auroc=d["macro_auroc"], aupr_success=d["macro_aupr_success"], aupr_error=d["macro_aupr_error"],
+                                fpr_at_95tpr=d["macro_fpr_at_95tpr"])
+            self.last_uncertainty = table
+            if to_print:
+                print(f"failure prediction on the {mode} split, {res.passes} MC-dropout draws per sample (macro over classes)")
+                print(f"{'confidence':<12} {'AUROC':>8} {'AUPR-Succ':>10} {'AUPR-Err':>9} {'FPR@95TPR':>10}")
+                for k, r in table.items():
+                    print(f"{k:<12} {r['auroc']:8.4f} {r['aupr_success']:10.4f} {r['aupr_error']:9.4f} {r['fpr_at_95tpr']:10.4f}")
         return res
 
     # ------------------------------------------------------------------ encoder cache (mmda_amd/encoded.py)
