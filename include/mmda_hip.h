@@ -1202,6 +1202,47 @@ int mmda_mc_reduce(const float* p, int B, int K, int W, const float* thr, int be
 int mmda_misa_mc_reduce(mmda_misa* m, int K, int which, const float* thr, const mmda_mc_out* out, const int32_t* dst, int64_t base,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------------- bootstrap intervals
+ * How far a figure of a report would move on another draw of the split (mmda_amd/bootstrap.py): the non-parametric
+ * bootstrap over the n rows.  Replicate r = 0 .. R - 1 draws, for k = 0 .. n - 1,
+ *   u = rng_u32(seed, 12, ((uint64)r << 32) + k)   (csrc/common.h; 12 = SITE_BOOTSTRAP),   j(r, k) = ((uint64)u * n) >> 32,
+ * so a replicate depends on (seed, r, n) alone; replicate R is the identity j(R, k) = k, the point estimate.  Every table below has
+ * R + 1 rows, row R the identity's.  1 <= n <= 2^20, 1 <= C <= 16, 1 <= R <= 8192; anything else is MMDA_EINVAL with nothing launched.
+ * mmda_boot_pack: labels, truth fp32 (n, C) -> codes[n], bit c = labels[i][c] > 0, bit 16 + c = truth[i][c] > 0.
+ * mmda_boot_counts OVERWRITES state[(R + 1)][3 C + 2] (int64): tp[C], fp[C], fn[C] of the drawn rows, acc_num = sum over the draws of
+ *   720720 |y & p| / max(|y | p|, 1) (an integer: 720720 = lcm(1 .. 16)), and n.  form: 0 = what mmda_boot_plan_describe names,
+ *   1 = the code table in LDS (n <= 16384, else MMDA_EINVAL), 2 = codes gathered from memory.  Integer adds only: the state depends
+ *   neither on the form nor on the run.
+ * mmda_boot_figures: out[(R + 1)][10 + 3 C] doubles from the states: acc (= acc_num / (720720 n), not rounded), f1, precision, recall
+ *   (macro), micro_f1, micro_precision, micro_recall, weighted_f1, weighted_precision, weighted_recall -- utils/eval.py's
+ *   metrics_from_counts -- then f1[C], precision[C], recall[C].
+ * mmda_boot_rank: n <= 16384.  The tables describe each class's rows in sorted order (descending score under ranking.py's order, ties
+ *   adjacent), all int32 (C, n): inv[c][row] = the row's sorted position; first[c][p] / last[c][p] = the first / last position of
+ *   the tie group position p is in; pos[c][p] != 0 = the row at position p is a positive.  out[(R + 1)][(C + 1)][6] doubles, the
+ *   columns and NaN rules of mmda_rank_finish with every row counted as often as the replicate draws it, row C the means.
+ * mmda_boot_summary: a (and b, or NULL) doubles [(R + 1)][F]; x_r = a[r][f] (- b[r][f]); out[F][ncols], ncols 6: point (row R), mean,
+ *   std (two-pass, ddof 1), lo, hi (the q_lo / q_hi percentiles, linear interpolation at h = (m - 1) q), defined (m, the replicates
+ *   where x is not NaN); ncols 9: and p_le = (1 + #{x <= 0}) / (m + 1), p_ge = (1 + #{x >= 0}) / (m + 1), p_two = min(1, 2 min(p_le,
+ *   p_ge)).  Sums in sorted order; m < 2: std NaN; m == 0: mean, std, lo, hi NaN.  R <= 8192, F >= 1.
+ * mmda_boot_plan_describe (host only; mmda_boot_counts reads the same function): the form of the count launch of a shape. */
+typedef struct mmda_boot_plan {
+  int form;                 /* 1 = LDS, 2 = global */
+  int threads;              /* of a workgroup of the count kernel */
+  int wgs_per_replicate;
+  int lds_bytes;            /* dynamic LDS of the count kernel */
+  int state_words;          /* 3 C + 2 */
+  int lds_rows;             /* the largest n of the LDS form and of mmda_boot_rank */
+  int rank_lds_bytes;       /* dynamic LDS of mmda_boot_rank's kernel, 0 where n is over its limit */
+  int max_replicates;
+} mmda_boot_plan;
+int mmda_boot_plan_describe(int64_t n, int C, int R, mmda_boot_plan* out);
+int mmda_boot_pack(const float* labels, const float* truth, int64_t n, int C, uint32_t* codes, void* stream);
+int mmda_boot_counts(const uint32_t* codes, int64_t n, int C, int R, uint64_t seed, int form, int64_t* state, void* stream);
+int mmda_boot_figures(const int64_t* state, int C, int R, double* out, void* stream);
+int mmda_boot_rank(const int32_t* inv, const int32_t* first, const int32_t* last, const int32_t* pos, int64_t n, int C, int R,
+                   uint64_t seed, double tpr_level, double* out, void* stream);
+int mmda_boot_summary(const double* a, const double* b, int R, int F, double q_lo, double q_hi, int ncols, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,9 @@ rescaling that makes them so (``fit_scaling`` -> ``Scaling``: temperature or Pla
 damped Newton iteration whose state never leaves the device; ``config.scaling``); ``uncertainty`` gives ``tcp`` its baselines
 (``MCDropoutPass`` / ``MCDropoutResult``: K dropout draws per sample from ONE forward of the fusion block over rows repeated K times,
 reduced on the device to mean, variance, entropy and mutual information; ``mc_statistics``: that reduction over any table;
-``config.mc_passes``).
+``config.mc_passes``); ``bootstrap`` says how far any of those figures would move on another draw of the split (``Bootstrap``: the rows
+resampled R times on the device by a counter-based generator, percentile intervals per figure and paired comparisons over the same
+resamples; ``resample_indices``: the draws restated in numpy; ``config.bootstrap``).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -32,3 +34,4 @@ from .sentiment import SentimentEval, sentiment_metrics  # noqa: F401
 from .modality import MODALITIES, ModalityPass, ModalityResult, keep_bits, parse_keep  # noqa: F401
 from .reliability import ReliabilityEval, ReliabilityResult, Scaling, fit_scaling, reliability_metrics  # noqa: F401
 from .uncertainty import MCDropoutPass, MCDropoutResult, mc_statistics  # noqa: F401
+from .bootstrap import Bootstrap, BootstrapResult, BootstrapSummary, boot_plan, resample_indices  # noqa: F401

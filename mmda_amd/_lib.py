@@ -219,7 +219,13 @@ class McOut(C.Structure):
                 ("mutual_info", C.c_void_p), ("vote", C.c_void_p), ("draws", C.c_void_p)]
 
 
-MC_MAX_PASSES, MC_MAX_WIDTH = 256, 64            # the K and W one mmda_mc_reduce launch takes
+class BootPlan(C.Structure):
+    """mmda_boot_plan: the form mmda_boot_counts gives a shape, and the limits of the bootstrap entry points"""
+    _fields_ = [("form", C.c_int), ("threads", C.c_int), ("wgs_per_replicate", C.c_int), ("lds_bytes", C.c_int),
+                ("state_words", C.c_int), ("lds_rows", C.c_int), ("rank_lds_bytes", C.c_int), ("max_replicates", C.c_int)]
+
+
+MC_MAX_PASSES, MC_MAX_WIDTH = 256, 64           # the K and W one mmda_mc_reduce launch takes
 
 
 CELL = {"lstm": 0, "gru": 1}
@@ -404,6 +410,12 @@ SIGNATURES = {
     "mmda_modality_attrib": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P]),
     "mmda_mc_reduce": (_I, [_P, _I, _I, _I, _P, _I, C.POINTER(McOut), _P, _I64, _P]),
     "mmda_misa_mc_reduce": (_I, [_P, _I, _I, _P, C.POINTER(McOut), _P, _I64, _P]),
+    "mmda_boot_plan_describe": (_I, [_I64, _I, _I, C.POINTER(BootPlan)]),
+    "mmda_boot_pack": (_I, [_P, _P, _I64, _I, _P, _P]),
+    "mmda_boot_counts": (_I, [_P, _I64, _I, _I, _U64, _I, _P, _P]),
+    "mmda_boot_figures": (_I, [_P, _I, _I, _P, _P]),
+    "mmda_boot_rank": (_I, [_P, _P, _P, _P, _I64, _I, _I, _U64, C.c_double, _P, _P]),
+    "mmda_boot_summary": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _I, _P, _P]),
 }
 
 _lib = None

@@ -128,6 +128,10 @@ DEFAULTS = dict(
     # checkpoint (mmda_amd/uncertainty.py) and prints how each confidence -- maximum class probability, the MC-dropout
     # figures, ConfidNet's tcp -- ranks the right decisions above the wrong ones; 0: nothing happens
     mc_passes=0,
+    # after the final test pass of Solver.train(), behind `scaling` / `calibrate`: R > 0 resamples the test split R times (1 .. 8192)
+    # with the best checkpoint (mmda_amd/bootstrap.py) and prints every figure of the cut-off and ranking reports as
+    # `figure  point  [lo, hi]`, with calibrated cut-offs also their paired difference to `threshold`; 0: nothing happens
+    bootstrap=0,
 )
 
 

@@ -187,6 +187,44 @@ class ModalityResult:
             out.append(dict(m, keep=k, kept=keep_names(k)))
         return out
 
+    def bootstrap(self, truth=None, threshold=None, replicates=2000, seed=0, alpha=0.05):
+        """The eight keep sets' decision figures with bootstrap intervals (mmda_amd/bootstrap.py), the same resamples for all eight:
+        ``dict(bootstrap, names, results, summary, vs_full)`` -- ``results`` the eight ``BootstrapResult``s (labels
+        ``scores[k] > threshold``, as ``metrics`` makes them), ``summary`` their (8, F, 6) table of point, mean, std, lo, hi, defined on
+        the device, ``vs_full`` the (8, F, 9) paired differences ``keep set k - keep set 7``; F = 10 + 3 C, named by ``names``.
+        ``truth`` / ``threshold``: as for ``metrics``."""
+        import torch
+        from . import _lib
+        from .bootstrap import Bootstrap
+        if self.task == "sentiment":
+            raise _lib.MMDAError("ModalityResult.bootstrap under task='sentiment' is not built: the figures are classification figures")
+        S = self._value("scores")
+        truth = self.truth if truth is None else truth
+        if truth is None:
+            raise ValueError("bootstrap: the pass has no labels of its own; give truth (n, C)")
+        C = int(S.shape[2])
+        truth = torch.as_tensor(truth).to(device=S.device, dtype=torch.float32).contiguous()
+        if tuple(truth.shape) != (self.n, C):
+            raise ValueError(f"bootstrap: truth is {tuple(truth.shape)}, the scores are {(self.n, C)}")
+        thr = self.threshold if threshold is None else getattr(threshold, "values", threshold)
+        thr = torch.as_tensor(thr, dtype=torch.float32).reshape(-1).to(S.device)
+        if thr.numel() == 1:
+            thr = thr.expand(C)
+        if thr.numel() != C:
+            raise ValueError(f"bootstrap: threshold has {thr.numel()} entries, the scores {C} classes")
+        thr, lib = thr.contiguous(), _lib.load()
+        bs = Bootstrap(self.n, replicates, seed, S.device)
+        results = []
+        for k in range(8):
+            labels = torch.empty(self.n, C, dtype=torch.float32, device=S.device)
+            scratch = torch.zeros(3 * C + 2, dtype=torch.float64, device=S.device)
+            _lib.check(lib.mmda_eval_accumulate_thr(S[k].data_ptr(), truth.data_ptr(), self.n, C, thr.data_ptr(), labels.data_ptr(),
+                                                    scratch.data_ptr(), _lib.stream_ptr()), "mmda_eval_accumulate_thr")
+            results.append(bs.decisions(labels, truth))
+        return dict(bootstrap=bs, names=results[7].names, results=results,
+                    summary=torch.stack([r.summary(alpha).table for r in results]),
+                    vs_full=torch.stack([bs.compare(r, results[7], alpha).table for r in results]))
+
     def cpu(self):
         """The same result on the host."""
         mv = lambda x: None if x is None else x.cpu()

@@ -62,6 +62,8 @@ class Solver(object):
         if getattr(cfg, "scaling", "none") not in ("none", "temperature", "platt"):
             raise ValueError(f"config.scaling must be 'none', 'temperature' or 'platt', not {cfg.scaling!r}")
         step_rules.scaling_check(getattr(cfg, "task", "emotion"), getattr(cfg, "scaling", "none"))
+        if int(getattr(cfg, "bootstrap", 0) or 0) != 0:        # (0, the default: nothing is looked at)
+            step_rules.bootstrap_check(task=getattr(cfg, "task", "emotion"), replicates=int(cfg.bootstrap))
         if self.model is None:
             self.model = getattr(models, cfg.model)(cfg)
         for name, param in self.model.named_parameters():
@@ -293,6 +295,10 @@ class Solver(object):
             if best_epoch >= 0:
                 self._load_best_checkpoint()
             self.uncertainty("test", passes=int(cfg.mc_passes), to_print=True)
+        if int(getattr(cfg, "bootstrap", 0) or 0) > 0:     # (0, the default: nothing below runs)
+            if best_epoch >= 0:
+                self._load_best_checkpoint()
+            self.bootstrap("test", replicates=int(cfg.bootstrap), thresholds=thresholds, scaling=scaling, to_print=True)
         print("=" * 50)
         print(f"Best epoch: {best_epoch}")
         print(f"Accuracy: {acc}")
@@ -720,6 +726,56 @@ class Solver(object):
                 for k, r in table.items():
                     print(f"{k:<12} {r['auroc']:8.4f} {r['aupr_success']:10.4f} {r['aupr_error']:9.4f} {r['fpr_at_95tpr']:10.4f}")
         return res
+
+    # ------------------------------------------------------------------ bootstrap intervals (mmda_amd/bootstrap.py)
+    def bootstrap(self, mode="test", replicates=2000, seed=0, alpha=0.05, thresholds=None, scaling=None, confidence=True, to_print=False):
+        """How far the figures of the ``mode`` split ("dev" or "test") would move on another draw of it: the split is gathered once
+        (the loop of ``rank``) and resampled ``replicates`` times on the device.  Sets and returns ``self.last_bootstrap``:
+        ``metrics`` -- the cut-off figures of ``eval`` under the same ``thresholds`` / ``scaling`` (the model's own decisions where
+        both are None) --, ``ranking`` (``rank``'s score table), ``confidence`` (its failure-prediction table, None where the model has
+        no confidence column per class or it is not asked for) and, with ``thresholds``, ``vs_default``: the paired comparison of those
+        cut-offs against ``config.threshold`` in every class, same resamples on both sides.  The first three are ``BootstrapResult``s
+        (``summary(alpha)`` gives point, mean, std, lo, hi), kept on the device; ``summaries`` holds their ``BootstrapSummary``s at
+        ``alpha``.  ``to_print``: ``figure  point  [lo, hi]`` for the ten cut-off figures and the macro ranking figures."""
+        from .bootstrap import Bootstrap
+        from .utils.eval import KEYS
+        cfg = self.train_config
+        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        sharded = getattr(loader, "shard", None) if self.dp is not None else None
+        step_rules.bootstrap_check(task="sentiment" if self._sentiment() else "emotion", replicates=replicates, sharded=sharded, mode=mode)
+        scores, truth, labels, tcp = self._score_tables(mode, "bootstrap", confidence, scaling)
+        n, C = int(scores.shape[0]), int(scores.shape[1])
+        bs = Bootstrap(n, replicates, seed, scores.device)
+        s32 = scores.to(torch.float32)
+        cut = lambda thr: (s32 > thr.to(device=s32.device, dtype=torch.float32).reshape(1, -1)).to(torch.float32)
+        default_thr = torch.full((C,), float(cfg.threshold), dtype=torch.float32)
+        if thresholds is not None:
+            if thresholds.values.numel() != C:
+                raise ValueError(f"thresholds has {thresholds.values.numel()} entries, the model {C} classes")
+            decided = cut(thresholds.values)
+        else:
+            decided = labels if scaling is None else cut(default_thr)
+        out = dict(bootstrap=bs, alpha=float(alpha), metrics=bs.decisions(decided, truth), ranking=bs.ranking(scores, truth),
+                   confidence=None, vs_default=None)
+        if tcp is not None:
+            correct = ((labels > 0) == (truth > 0)).to(torch.float32)
+            out["confidence"] = bs.ranking(tcp, correct, failure=True)
+        if thresholds is not None:
+            out["vs_default"] = bs.compare(out["metrics"], bs.decisions(cut(default_thr), truth), alpha)
+        out["summaries"] = {k: out[k].summary(alpha) for k in ("metrics", "ranking", "confidence") if out[k] is not None}
+        self.last_bootstrap = out
+        if to_print:
+            print(f"bootstrap of the {mode} split: {n} rows, {replicates} replicates, {100 * (1 - alpha):g} % percentile intervals")
+            print(out["summaries"]["metrics"].format(KEYS))
+            print(out["summaries"]["ranking"].format(("macro_auroc", "map", "macro_ap_neg", "macro_fpr_at_tpr")))
+            if out["confidence"] is not None:
+                names = out["confidence"].names[-4:]
+                print("failure prediction (tcp)")
+                print(out["summaries"]["confidence"].format(names))
+            if out["vs_default"] is not None:
+                print(f"calibrated cut-offs minus threshold = {cfg.threshold}")
+                print(out["vs_default"].format(KEYS))
+        return out
 
     # ------------------------------------------------------------------ encoder cache (mmda_amd/encoded.py)
     def encode(self, mode, batch_size=None, order="length"):

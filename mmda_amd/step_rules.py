@@ -186,6 +186,51 @@ def scaling_check(task="emotion", scaling="none", reliability=False) -> None:
         raise MMDAError(dict(SCALING_RULES)[hit[0]].format(**hit[1]))
 
 
+# What the bootstrap refuses.  Refused where it is asked for (config.bootstrap at Solver.build, Solver.bootstrap, the
+# Bootstrap class and its calls), with nothing run.  The limits are those of csrc/bootstrap.hip.
+BOOT_MAX_REPLICATES, BOOT_MAX_ROWS, BOOT_MAX_CLASSES, BOOT_RANK_MAX_ROWS = 8192, 1 << 20, 16, 16384
+BOOTSTRAP_RULES = (
+    ("boot_sentiment", "task='sentiment' with the bootstrap (Solver.bootstrap, bootstrap={replicates}) is not built: the resampled "
+                       "figures are classification figures"),
+    ("boot_sharded", "the bootstrap resamples each rank's own {mode} loader and exchanges nothing: under a process group the {mode} loader "
+                     "must not be sharded (shard={shard}); give every rank the whole split or set bootstrap=0"),
+    ("boot_replicates", "replicates must be an integer in 1 .. 8192 (one workgroup sorts a figure's replicates in LDS), not {replicates!r}"),
+    ("boot_rows", "a bootstrap over n = {n} rows is outside 1 .. 2^20 = 1048576 rows"),
+    ("boot_classes", "a bootstrap table must have 1 .. 16 classes (a row is packed into 16 + 16 bits), not C = {C}"),
+    ("boot_rank_rows", "a ranking bootstrap over n = {n} rows is over the limit of 16384 rows: a replicate's row weights and their scan "
+                       "stay in 128 KiB of LDS"),
+    ("boot_compare", "compare needs two results of the same Bootstrap over the same figures: {why}"),
+)
+
+
+def bootstrap_verdict(task="emotion", replicates=1, n=1, C=1, rank=False, sharded=None, mode="test", compare=None):
+    """(rule, format values) of the first rule of BOOTSTRAP_RULES that refuses the setting, or None.  ``rank``: the ranking figures
+    are asked for; ``sharded``: the shard of the split's loader under a process group, or None; ``compare``: None, or why two results
+    cannot be compared."""
+    if task == "sentiment":
+        return "boot_sentiment", dict(replicates=replicates)
+    if sharded is not None:
+        return "boot_sharded", dict(mode=mode, shard=sharded)
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or not 1 <= replicates <= BOOT_MAX_REPLICATES:
+        return "boot_replicates", dict(replicates=replicates)
+    if not 1 <= n <= BOOT_MAX_ROWS:
+        return "boot_rows", dict(n=n)
+    if not 1 <= C <= BOOT_MAX_CLASSES:
+        return "boot_classes", dict(C=C)
+    if rank and n > BOOT_RANK_MAX_ROWS:
+        return "boot_rank_rows", dict(n=n)
+    if compare is not None:
+        return "boot_compare", dict(why=compare)
+    return None
+
+
+def bootstrap_check(**values) -> None:
+    """Raises MMDAError with the text of the rule that refuses the setting (``bootstrap_verdict``'s arguments)."""
+    hit = bootstrap_verdict(**values)
+    if hit is not None:
+        raise MMDAError(dict(BOOTSTRAP_RULES)[hit[0]].format(**hit[1]))
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:

@@ -152,14 +152,21 @@ class MCDropoutResult:
             return self.tcp_mean.to(torch.float32)
         raise ValueError(f"unknown kind {kind!r}: the kinds are {KINDS}")
 
-    def failure_table(self, truth, kinds=None, tpr=0.95):
+    def failure_table(self, truth, kinds=None, tpr=0.95, bootstrap=None):
         """``{kind: failure_prediction(confidence(kind), correct)}`` with ``correct = (labels == truth)`` of the DETERMINISTIC decision
         for every kind, so the rows of the table differ in the confidence only.  ``kinds=None``: every kind whose table has the
-        decisions' shape (the ``tcp`` kinds need six classes)."""
+        decisions' shape (the ``tcp`` kinds need six classes).  ``bootstrap``: None, or a ``Bootstrap`` over this result's n rows
+        (mmda_amd/bootstrap.py): the table is then ``{kind: dict(result, summary, vs_tcp)}`` -- the kind's resampled failure-prediction
+        figures (``BootstrapResult``, row R the unresampled table), their intervals (``BootstrapSummary`` (F, 6)) and the paired
+        difference ``kind - tcp`` over the same resamples ((F, 9); None where ``tcp`` is not among the kinds)."""
         if kinds is None:
             kinds = tuple(k for k in KINDS if not k.startswith("tcp") or self.tcp.shape == self.labels.shape)
         truth = torch.as_tensor(truth).to(self.labels.device)
         correct = ((self.labels > 0) == (truth > 0)).to(torch.float32)
+        if bootstrap is not None:
+            res = {k: bootstrap.ranking(self.confidence(k), correct, tpr=tpr, failure=True) for k in kinds}
+            return {k: dict(result=r, summary=r.summary(), vs_tcp=bootstrap.compare(r, res["tcp"]) if "tcp" in res else None)
+                    for k, r in res.items()}
         return {k: failure_prediction(self.confidence(k), correct, tpr=tpr) for k in kinds}
 
     def cpu(self):
