@@ -458,3 +458,15 @@ def ptr(t):
 def stream_ptr():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def device_tables(a, b, who, names=None, dims="(N, C)"):
+    """The two tables an evaluation report of ``who`` is given, detached, fp32 and contiguous: ``MMDAError`` unless both are device
+    tensors; with ``names`` (how the message calls them, such as "scores and truth") ``ValueError`` unless both are 2-D of one
+    shape."""
+    import torch
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda):
+        raise MMDAError(f"{who} needs device tensors (the HIP path has no CPU fallback)")
+    if names is not None and (a.dim() != 2 or b.shape != a.shape):
+        raise ValueError(f"{names} must both be {dims}, not {tuple(a.shape)} and {tuple(b.shape)}")
+    return a.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()

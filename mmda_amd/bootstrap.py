@@ -35,13 +35,13 @@ import numpy as np
 
 from . import _lib, step_rules
 from .modality import _rng_u32
+from .utils.eval import LCM
 
 SITE_BOOTSTRAP = 12                      # the next free id after modality.SITE_MODALITY
 MAX_REPLICATES = step_rules.BOOT_MAX_REPLICATES
 MAX_ROWS = step_rules.BOOT_MAX_ROWS
 MAX_CLASSES = step_rules.BOOT_MAX_CLASSES
 RANK_MAX_ROWS = step_rules.BOOT_RANK_MAX_ROWS
-LCM = 720720                             # lcm(1 .. 16), as calibrate.LCM
 SUMMARY_COLUMNS = ("point", "mean", "std", "lo", "hi", "defined")
 COMPARE_COLUMNS = SUMMARY_COLUMNS + ("p_le", "p_ge", "p_two")
 FORMS = {"auto": 0, "lds": 1, "global": 2}
@@ -291,15 +291,11 @@ class Bootstrap:
             raise _lib.MMDAError(f"Bootstrap resamples on the GPU only (the HIP path has no CPU fallback), not on {self.device}")
 
     def _tables(self, a, b, who, rank=False):
-        import torch
-        if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda):
-            raise _lib.MMDAError(f"{who} needs device tensors (the HIP path has no CPU fallback)")
-        if a.dim() != 2 or a.shape != b.shape:
-            raise ValueError(f"{who}: the two tables must both be (n, C), not {tuple(a.shape)} and {tuple(b.shape)}")
+        a, b = _lib.device_tables(a, b, who, f"{who}: the two tables", "(n, C)")
         if a.shape[0] != self.n:
             raise ValueError(f"{who}: the tables have {a.shape[0]} rows, this Bootstrap resamples n = {self.n}")
         step_rules.bootstrap_check(replicates=self.R, n=self.n, C=int(a.shape[1]), rank=rank)
-        return a.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()
+        return a, b
 
     def decisions(self, labels, truth, form="auto"):
         """The decision figures of labels / truth (n, C) on the device under every replicate: a pack launch, the count launch

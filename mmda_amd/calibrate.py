@@ -18,10 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .utils.eval import KEYS, metrics_from_counts
+from .utils.eval import KEYS, LCM, host_tables, metrics_from_counts
 
 MAX_CLASSES, MAX_GRID = 16, 256
-LCM = 720720                                                     # lcm(1 .. 16): a / max(b, 1) is an integer multiple of 1 / LCM
 OBJECTIVES = {"f1": 0, "micro_f1": 1, "weighted_f1": 2, "acc": 3}
 PER_CLASS_OBJECTIVES = ("f1", "weighted_f1")
 EVAL_MODE_OBJECTIVE = {"macro": "f1", "micro": "micro_f1", "weighted": "weighted_f1"}
@@ -82,10 +81,7 @@ def _bins(scores, grid):
 def sweep_counts(scores, truth, grid):
     """(hist (C, K+1, 2), pairs (K, C+1, C+1)), int64, of host arrays scores / truth (N, C)."""
     grid = check_grid(grid)
-    s = np.asarray(scores, dtype=np.float32)
-    pos = np.asarray(truth) > 0
-    if s.ndim != 2 or pos.shape != s.shape:
-        raise ValueError(f"scores and truth must both be (N, C), not {s.shape} and {pos.shape}")
+    s, pos = host_tables(scores, truth, "scores and truth")
     N, C = s.shape
     K = grid.shape[0]
     bins = _bins(s, grid)
@@ -156,12 +152,6 @@ def select_from_counts(hist, pairs, grid, objective="f1", per_class=True):
 
 
 # ---------------------------------------------------------------------------------------------------- device
-def _device_pair(a, b, who):
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda):
-        raise _lib.MMDAError(f"{who} needs device tensors (the HIP path has no CPU fallback)")
-    return a.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()
-
-
 class Thresholds:
     """One cut-off per class: ``values`` (C,) float32 and ``k`` (C,) int32, their indices into ``grid``; on the device when they come
     from ``ThresholdSweep.select``.  ``Solver.eval(mode, thresholds=...)`` decides with them."""
@@ -231,7 +221,7 @@ class ThresholdSweep:
 
     def update(self, scores, truth):
         """scores, truth: (N, C) on the device; no synchronisation."""
-        self._accumulate(*_device_pair(scores, truth, "ThresholdSweep.update"))
+        self._accumulate(*_lib.device_tables(scores, truth, "ThresholdSweep.update"))      # (_accumulate checks the shapes)
 
     def update_result(self, result, truth):
         """The ``scores`` table of an ``InferenceResult`` against ``truth`` (n, C), rows in the result's order."""
@@ -271,7 +261,7 @@ def confidence_curve(tcp, correct, cutoffs):
     """ConfidNet's ``tcp`` (n, C) against ``correct = (labels == truth)`` (n, C), both on the device, by the sweep's kernel: per class
     and cut-off, (kept, kept_correct) -- how many decisions have ``tcp > cutoffs[k]`` and how many of those are correct -- as two (C, K)
     int64 device tensors (suffix sums of the histogram and nothing more; no read-back)."""
-    t, c = _device_pair(tcp, correct, "confidence_curve")
+    t, c = _lib.device_tables(tcp, correct, "confidence_curve")
     sweep = ThresholdSweep(t.shape[1] if t.dim() == 2 else 0, cutoffs, t.device, pairs=False)
     sweep._accumulate(t, c)
     hist = sweep._counts.view(sweep.C, sweep.K + 1, 2)

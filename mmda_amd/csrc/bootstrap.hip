@@ -13,9 +13,8 @@
 // Everything counted is an integer, combined by integer adds only, so no state depends on the form or on the order of arrival.  The
 // floating-point sums (the two AP sums, the mean and std of a summary) are added in an order that is a function of the shape alone.
 #include "internal.h"
-#include <algorithm>
-#include <utility>
-#include <vector>
+#include "dynamic_lds.h"
+#include "eval_terms.h"
 
 // No product is fused into a sum in this file: the host restatements (numpy) round every product and every sum on its own.  Plain
 // operators under this pragma, not __dmul_rn / __dadd_rn: those inline to operators that carry the headers' contraction mode.
@@ -25,7 +24,6 @@ namespace {
 
 enum { SITE_BOOTSTRAP = 12 };                  // the next id after modality.hip's SITE_MODALITY
 
-constexpr int BOOT_MAXC = 16;                  // 16 predicted and 16 true bits per code
 constexpr int64_t BOOT_MAXN = (int64_t)1 << 20;
 constexpr int BOOT_MAXR = 8192;                // replicates: what one workgroup of mmda_boot_summary sorts in 64 KiB of LDS
 constexpr int BOOT_LDS_ROWS = 16384;           // the code table sits in LDS up to here (64 KiB); the ranking kernel's row limit
@@ -34,24 +32,12 @@ constexpr int BOOT_DRAWS_PER_WG = 4096;        // a replicate is split into work
 constexpr int BOOT_MAX_WGS = 16;               // ... at most this many
 constexpr int BOOT_RANK_THREADS = 1024;
 constexpr int BOOT_SUM_THREADS = 1024;
-constexpr unsigned BOOT_LCM = 720720u;         // lcm(1 .. 16), calibrate.py's LCM
 
 enum { BOOT_FORM_AUTO = 0, BOOT_FORM_LDS = 1, BOOT_FORM_GLOBAL = 2 };
 
 __device__ __forceinline__ uint32_t boot_draw(uint64_t seed, uint32_t r, uint32_t k, uint32_t n) {
   const uint32_t u = rng_u32(seed, SITE_BOOTSTRAP, ((uint64_t)r << 32) + (uint64_t)k);
   return (uint32_t)(((uint64_t)u * (uint64_t)n) >> 32);      // < n
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize, once per kernel and size (lstm_resident.hip's ensure_dynamic_lds)
-template <typename Kernel>
-void boot_dynamic_lds(Kernel kernel, size_t bytes) {
-  static std::vector<std::pair<const void*, size_t>> attr_max;
-  const void* kf = reinterpret_cast<const void*>(kernel);
-  auto it = std::find_if(attr_max.begin(), attr_max.end(), [&](const std::pair<const void*, size_t>& e) { return e.first == kf; });
-  if (it != attr_max.end() && it->second >= bytes) return;
-  if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); }
-  if (it == attr_max.end()) attr_max.push_back({kf, bytes}); else it->second = bytes;
 }
 
 // ------------------------------------------------------------------------------------------------ decision figures
@@ -75,7 +61,7 @@ template <bool LDS>
 __global__ __launch_bounds__(BOOT_THREADS) void boot_counts_kernel(const uint32_t* __restrict__ codes, int n, int C, int R, uint64_t seed,
                                                                    unsigned long long* __restrict__ state) {
   extern __shared__ uint32_t tab_s[];
-  __shared__ unsigned long long acc_s[3 * BOOT_MAXC + 2];
+  __shared__ unsigned long long acc_s[3 * EVAL_MAXC + 2];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int r = blockIdx.y;
   const int words = 3 * C + 2;
@@ -86,9 +72,9 @@ __global__ __launch_bounds__(BOOT_THREADS) void boot_counts_kernel(const uint32_
   const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x;
   const int k0 = (int)blockIdx.x * per;
   const int k1 = k0 + per < n ? k0 + per : n;
-  unsigned tp[BOOT_MAXC], fp[BOOT_MAXC], fn[BOOT_MAXC];
+  unsigned tp[EVAL_MAXC], fp[EVAL_MAXC], fn[EVAL_MAXC];
 #pragma unroll
-  for (int c = 0; c < BOOT_MAXC; ++c) { tp[c] = 0u; fp[c] = 0u; fn[c] = 0u; }
+  for (int c = 0; c < EVAL_MAXC; ++c) { tp[c] = 0u; fp[c] = 0u; fn[c] = 0u; }
   unsigned long long acc = 0ull;
   unsigned cnt = 0u;
   for (int k = k0 + tid; k < k1; k += BOOT_THREADS) {
@@ -97,9 +83,9 @@ __global__ __launch_bounds__(BOOT_THREADS) void boot_counts_kernel(const uint32_
     const uint32_t p = code & 0xffffu, y = code >> 16;
     const uint32_t a = p & y, b = p & ~y, d = y & ~p;
 #pragma unroll
-    for (int c = 0; c < BOOT_MAXC; ++c) { tp[c] += (a >> c) & 1u; fp[c] += (b >> c) & 1u; fn[c] += (d >> c) & 1u; }
+    for (int c = 0; c < EVAL_MAXC; ++c) { tp[c] += (a >> c) & 1u; fp[c] += (b >> c) & 1u; fn[c] += (d >> c) & 1u; }
     const unsigned uni = (unsigned)__popc(p | y);
-    acc += (unsigned long long)((BOOT_LCM / (uni ? uni : 1u)) * (unsigned)__popc(a));
+    acc += (unsigned long long)(((unsigned)EVAL_LCM / (uni ? uni : 1u)) * (unsigned)__popc(a));
     cnt += 1u;
   }
   auto wsum = [](unsigned v) {
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(BOOT_THREADS) void boot_counts_kernel(const uint32_
     return v;
   };
 #pragma unroll
-  for (int c = 0; c < BOOT_MAXC; ++c) {
+  for (int c = 0; c < EVAL_MAXC; ++c) {
     if (c < C) {                                                // uniform
       const unsigned a = wsum(tp[c]), b = wsum(fp[c]), d = wsum(fn[c]);
       if (lane == 0) {
@@ -129,32 +115,19 @@ __global__ __launch_bounds__(BOOT_THREADS) void boot_counts_kernel(const uint32_
   }
 }
 
-__device__ __forceinline__ double boot_div(double a, double b) { return b > 0.0 ? a / b : 0.0; }
-
-// One thread per replicate: utils/eval.py's metrics_from_counts, every product and sum rounded on its own (no contraction), the class
-// sums in class order.
+// One thread per replicate: eval_terms.h's decision figures of the replicate's state, then the per-class triples.
 __global__ __launch_bounds__(64) void boot_figures_kernel(const long long* __restrict__ state, int C, int rows, double* __restrict__ out) {
   const int r = blockIdx.x * 64 + threadIdx.x;
   if (r >= rows) return;
   const long long* st = state + (int64_t)r * (3 * C + 2);
   double* o = out + (int64_t)r * (10 + 3 * C);
-  double TP = 0.0, FP = 0.0, FN = 0.0;
-  for (int c = 0; c < C; ++c) { TP += (double)st[c]; FP += (double)st[C + c]; FN += (double)st[2 * C + c]; }
-  const double sup_sum = TP + FN;
-  double f1s = 0.0, ps = 0.0, rs = 0.0, wf = 0.0, wp = 0.0, wr = 0.0;
-  for (int c = 0; c < C; ++c) {
-    const double tp = (double)st[c], fp = (double)st[C + c], fn = (double)st[2 * C + c];
-    const double prec = boot_div(tp, tp + fp), rec = boot_div(tp, tp + fn), f1 = boot_div(2.0 * tp, 2.0 * tp + fp + fn);
-    const double w = sup_sum > 0.0 ? boot_div(tp + fn, sup_sum) : 0.0;
-    f1s = f1s + f1; ps = ps + prec; rs = rs + rec;
-    wf = wf + w * f1; wp = wp + w * prec; wr = wr + w * rec;
-    o[10 + c] = f1; o[10 + C + c] = prec; o[10 + 2 * C + c] = rec;
-  }
-  const double n = (double)st[3 * C + 1];
-  o[0] = n > 0.0 ? (double)st[3 * C] / ((double)BOOT_LCM * n) : __builtin_nan("");
-  o[1] = f1s / (double)C; o[2] = ps / (double)C; o[3] = rs / (double)C;
-  o[4] = boot_div(2.0 * TP, 2.0 * TP + FP + FN); o[5] = boot_div(TP, TP + FP); o[6] = boot_div(TP, TP + FN);
-  o[7] = wf; o[8] = wp; o[9] = wr;
+  double sup_sum = 0.0;
+  for (int c = 0; c < C; ++c) sup_sum += (double)(st[c] + st[2 * C + c]);
+  DecisionFigures fig;
+  for (int c = 0; c < C; ++c)
+    fig.add((double)st[c], (double)st[C + c], (double)st[2 * C + c], sup_sum, o[10 + c], o[10 + C + c], o[10 + 2 * C + c]);
+  const long long n = st[3 * C + 1];
+  fig.write(C, n > 0, (unsigned long long)st[3 * C], (unsigned long long)n, o);
 }
 
 // ------------------------------------------------------------------------------------------------ ranking figures
@@ -213,10 +186,7 @@ __global__ __launch_bounds__(BOOT_RANK_THREADS) void boot_rank_kernel(const int3
     __syncthreads();                                            // the wave totals are read; W / SN of the tile are written
   }
   const unsigned long long Nn = carry_n, P = (unsigned long long)carry_w - carry_n;
-  const double need_d = ceil(level * (double)P);
-  const unsigned long long need = need_d < 1.0 ? 1ull : (unsigned long long)need_d;
-  unsigned long long num = 0ull, fmin = ~0ull;
-  double ap = 0.0, apn = 0.0;
+  RankFigures<WAVES> fig(level, P);
   for (int p = tid; p < n; p += T) {
     const unsigned long long w = W[p] - (p ? W[p - 1] : 0u);
     if (!w) continue;
@@ -225,61 +195,16 @@ __global__ __launch_bounds__(BOOT_RANK_THREADS) void boot_rank_kernel(const int3
     b = b < p ? p : b >= n ? n - 1 : b;
     const unsigned long long wb = W[b], gnen = SN[b];
     const unsigned long long wa = a ? W[a - 1] : 0u, gn = a ? SN[a - 1] : 0u;
-    const unsigned long long gpep = wb - gnen, gp = wa - gn;
-    if (pos_c[p] != 0) {
-      num += w * (2ull * (Nn - gnen) + (gnen - gn));
-      ap = ap + (double)w * ((double)gpep / (double)wb);
-      if (gpep >= need && gnen < fmin) fmin = gnen;
-    } else {
-      const unsigned long long lnen = Nn - gn, lpep = P - gp;
-      apn = apn + (double)w * ((double)lnen / (double)(lnen + lpep));
-    }
+    if (pos_c[p] != 0) fig.positive(w, wb - gnen, gn, gnen, Nn);
+    else fig.negative(w, wa - gn, gn, P, Nn);
   }
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    num += __shfl_xor(num, o);
-    const unsigned long long other = __shfl_xor(fmin, o);
-    fmin = other < fmin ? other : fmin;
-    ap += __shfl_xor(ap, o);
-    apn += __shfl_xor(apn, o);
-  }
-  if (lane == 0) { num_s[wave] = num; min_s[wave] = fmin; ap_s[wave] = ap; apn_s[wave] = apn; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < WAVES; ++w) {
-      num += num_s[w];
-      fmin = min_s[w] < fmin ? min_s[w] : fmin;
-      ap += ap_s[w];
-      apn += apn_s[w];
-    }
-    const double nan = __builtin_nan("");
-    double* row = out + ((int64_t)r * (C + 1) + c) * 6;
-    const bool both = P > 0 && Nn > 0;
-    row[0] = (double)P;
-    row[1] = (double)Nn;
-    row[2] = both ? (double)num / (double)(2ull * P * Nn) : nan;
-    row[3] = P > 0 ? ap / (double)P : nan;
-    row[4] = Nn > 0 ? apn / (double)Nn : nan;
-    row[5] = both ? (double)fmin / (double)Nn : nan;
-  }
+  if (fig.reduce(num_s, min_s, ap_s, apn_s)) fig.write(P, Nn, out + ((int64_t)r * (C + 1) + c) * 6);
 }
 
-// Row C of every replicate's table, one thread per replicate: rank.hip's rank_macro_kernel.
+// Row C of every replicate's table, one thread per replicate.
 __global__ __launch_bounds__(64) void boot_rank_macro_kernel(int C, int rows, double* __restrict__ out) {
   const int r = blockIdx.x * 64 + threadIdx.x;
-  if (r >= rows) return;
-  double* tab = out + (int64_t)r * (C + 1) * 6;
-  double* macro = tab + (int64_t)C * 6;
-  for (int f = 2; f < 6; ++f) {
-    double sum = 0.0;
-    int cnt = 0;
-    for (int c = 0; c < C; ++c) {
-      const double v = tab[(int64_t)c * 6 + f];
-      if (v == v) { sum += v; ++cnt; }
-    }
-    macro[f] = cnt > 0 ? sum / (double)cnt : __builtin_nan("");
-    if (f < 4) macro[f - 2] = (double)cnt;
-  }
+  if (r < rows) rank_macro_row(C, out + (int64_t)r * (C + 1) * 6);
 }
 
 // ------------------------------------------------------------------------------------------------ summaries
@@ -369,7 +294,7 @@ __global__ __launch_bounds__(BOOT_SUM_THREADS) void boot_summary_kernel(const do
   }
 }
 
-bool boot_shape_ok(int64_t n, int C, int R) { return n >= 1 && n <= BOOT_MAXN && C >= 1 && C <= BOOT_MAXC && R >= 1 && R <= BOOT_MAXR; }
+bool boot_shape_ok(int64_t n, int C, int R) { return n >= 1 && n <= BOOT_MAXN && C >= 1 && C <= EVAL_MAXC && R >= 1 && R <= BOOT_MAXR; }
 
 }  // namespace
 
@@ -409,7 +334,7 @@ extern "C" int mmda_boot_counts(const uint32_t* codes, int64_t n, int C, int R, 
   unsigned long long* st = reinterpret_cast<unsigned long long*>(state);
   if (form == BOOT_FORM_LDS) {
     const size_t lds = (size_t)n * sizeof(uint32_t);
-    boot_dynamic_lds(boot_counts_kernel<true>, lds);
+    ensure_dynamic_lds(boot_counts_kernel<true>, lds);
     hipLaunchKernelGGL(boot_counts_kernel<true>, grid, dim3(BOOT_THREADS), lds, (hipStream_t)stream, codes, (int)n, C, R, seed, st);
   } else {
     hipLaunchKernelGGL(boot_counts_kernel<false>, grid, dim3(BOOT_THREADS), 0, (hipStream_t)stream, codes, (int)n, C, R, seed, st);
@@ -431,7 +356,7 @@ extern "C" int mmda_boot_rank(const int32_t* inv, const int32_t* first, const in
   if (!inv || !first || !last || !pos || !out || ((uintptr_t)out & 7)) return MMDA_EINVAL;
   if (!boot_shape_ok(n, C, R) || n > BOOT_LDS_ROWS || !(tpr_level > 0.0 && tpr_level <= 1.0)) return MMDA_EINVAL;
   const size_t lds = 2 * (size_t)n * sizeof(uint32_t);
-  boot_dynamic_lds(boot_rank_kernel, lds);
+  ensure_dynamic_lds(boot_rank_kernel, lds);
   hipLaunchKernelGGL(boot_rank_kernel, dim3(R + 1, C), dim3(BOOT_RANK_THREADS), lds, (hipStream_t)stream, inv, first, last, pos, (int)n, C, R,
                      seed, tpr_level, out);
   MMDA_CHECK_LAUNCH("mmda_boot_rank");
@@ -448,7 +373,7 @@ extern "C" int mmda_boot_summary(const double* a, const double* b, int R, int F,
   int Rp = 2;
   while (Rp < R) Rp <<= 1;
   const size_t lds = (size_t)Rp * sizeof(unsigned long long);
-  boot_dynamic_lds(boot_summary_kernel, lds);
+  ensure_dynamic_lds(boot_summary_kernel, lds);
   hipLaunchKernelGGL(boot_summary_kernel, dim3(F), dim3(BOOT_SUM_THREADS), lds, (hipStream_t)stream, a, b, R, F, Rp, q_lo, q_hi, ncols, out);
   MMDA_CHECK_LAUNCH("mmda_boot_summary");
   return MMDA_OK;

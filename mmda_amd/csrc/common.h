@@ -222,6 +222,14 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int o = 1; o < WAVE; o <<= 1) v += __shfl_xor(v, o);
   return v;
 }
+// The same butterfly with the widest step first (32 .. 1), doubles or integers.  Two orders exist because results are pinned to each:
+// the Jaccard sum of the evaluation counts and the MC-dropout tables to 32 .. 1, the streaming reductions above to 1 .. 32.
+template <typename T>
+__device__ __forceinline__ T wave_sum_widest_first(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // ---- deferred dense update of the embedding table (embed_update = deferred): dense Adam's result, without a pass over the table.  A row
 // whose gradient is zero takes a step that needs nothing but the row and the step's two scalars, so it can be applied later.  Updates are

@@ -22,7 +22,7 @@
 constexpr int REG_NONE = 0, REG_L1 = 1, REG_MSE = 2;      // = 0, 1 + MMDA_SENTI_L1, 1 + MMDA_SENTI_MSE (mmda_hip.h)
 __host__ __device__ __forceinline__ bool reg_valid(int reg) { return reg >= REG_NONE && reg <= REG_MSE; }
 
-constexpr int CLS_MAXW = 16;              // = EVAL_MAXC (losses.hip): classes a weight list can have
+constexpr int CLS_MAXW = 16;              // = EVAL_MAXC (eval_terms.h): classes a weight list can have
 
 // by value in the kernel arguments: no buffer, no upload
 struct ClsTerm {

@@ -889,77 +889,6 @@ __global__ __launch_bounds__(256) void domain_kernel(const float* __restrict__ d
   if (threadIdx.x == 0 && loss) atomicAdd(loss, t / rows);
 }
 
-// ------------------------------------------------------------------------------------------------ evaluation counts
-// Per-class tp / fp / fn over (pred > 0, truth > 0) and the Jaccard-style accuracy sum of the reference's get_accuracy
-// (utils/eval.py:14-31), accumulated into a device state so that an evaluation pass over many batches needs one read-back:
-//   state[0..C) tp, [C..2C) fp, [2C..3C) fn, [3C] sum_i |y_i & p_i| / max(|y_i | p_i|, 1), [3C+1] samples      (doubles)
-constexpr int EVAL_MAXC = 16;
-__global__ __launch_bounds__(256) void eval_counts_kernel(const float* __restrict__ pred, const float* __restrict__ truth, int N, int C,
-                                                          double* state) {
-  double tp[EVAL_MAXC], fp[EVAL_MAXC], fn[EVAL_MAXC];
-#pragma unroll
-  for (int c = 0; c < EVAL_MAXC; ++c) { tp[c] = 0.0; fp[c] = 0.0; fn[c] = 0.0; }
-  double jac = 0.0, cnt = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
-    int inter = 0, uni = 0;
-#pragma unroll
-    for (int c = 0; c < EVAL_MAXC; ++c) {
-      if (c < C) {
-        const bool y = truth[(int64_t)i * C + c] > 0.f, p = pred[(int64_t)i * C + c] > 0.f;
-        tp[c] += (y && p) ? 1.0 : 0.0; fp[c] += (!y && p) ? 1.0 : 0.0; fn[c] += (y && !p) ? 1.0 : 0.0;
-        inter += (y && p) ? 1 : 0; uni += (y || p) ? 1 : 0;
-      }
-    }
-    jac += (double)inter / (double)(uni > 0 ? uni : 1);
-    cnt += 1.0;
-  }
-  auto wsum = [](double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-  };
-  const bool lead = (threadIdx.x & 63) == 0;
-#pragma unroll
-  for (int c = 0; c < EVAL_MAXC; ++c) {
-    if (c < C) {
-      const double a = wsum(tp[c]), b = wsum(fp[c]), d = wsum(fn[c]);
-      if (lead) { if (a != 0.0) atomicAdd(&state[c], a); if (b != 0.0) atomicAdd(&state[C + c], b); if (d != 0.0) atomicAdd(&state[2 * C + c], d); }
-    }
-  }
-  jac = wsum(jac); cnt = wsum(cnt);
-  if (lead && cnt != 0.0) { atomicAdd(&state[3 * C], jac); atomicAdd(&state[3 * C + 1], cnt); }
-}
-
-// ------------------------------------------------------------------------------------------------ label counts
-// counts[c] += rows of the (N, C) table with an entry > 0 in column c.  Integers from the lanes up: a wave's sum by shuffles, the
-// workgroup's four through LDS, one 64-bit integer atomic per class and workgroup -- exact, and the same bits whatever the arrival order.
-__global__ __launch_bounds__(256) void label_counts_kernel(const float* __restrict__ emo, int64_t N, int C, unsigned long long* counts) {
-  __shared__ unsigned part[4][EVAL_MAXC];
-  unsigned n[EVAL_MAXC];
-#pragma unroll
-  for (int c = 0; c < EVAL_MAXC; ++c) n[c] = 0u;
-  // (a thread's count stays below 2^32: at most N / 256 rows each, N checked by the launcher)
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int c = 0; c < EVAL_MAXC; ++c)
-      if (c < C) n[c] += emo[i * C + c] > 0.f ? 1u : 0u;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < EVAL_MAXC; ++c) {
-    unsigned v = n[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) part[wave][c] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < C) {
-    const int c = threadIdx.x;
-    const unsigned long long t = (unsigned long long)part[0][c] + part[1][c] + part[2][c] + part[3][c];
-    if (t) atomicAdd(&counts[c], t);
-  }
-}
-
 }  // namespace
 
 bool mmda_cls_opts_valid(const mmda_cls_opts* o, int ncls) {
@@ -971,17 +900,6 @@ bool mmda_cls_opts_valid(const mmda_cls_opts* o, int ncls) {
   for (int c = 0; c < ncls; ++c)
     if (!(o->pos_weight[c] >= 0.f) || !(o->pos_weight[c] <= 3.402823466e38f)) return false;
   return true;
-}
-
-extern "C" int mmda_label_counts(const float* emo, int64_t N, int C, int64_t* counts, void* stream) {
-  if (!emo || !counts || N < 0 || C <= 0 || C > EVAL_MAXC || ((uintptr_t)counts & 7) || N > ((int64_t)1 << 40)) return MMDA_EINVAL;
-  if (N == 0) return MMDA_OK;
-  const int64_t b = (N + 255) / 256;
-  const int blocks = (int)(b > 256 ? 256 : b);
-  hipLaunchKernelGGL(label_counts_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, emo, N, C,
-                     reinterpret_cast<unsigned long long*>(counts));
-  MMDA_CHECK_LAUNCH("mmda_label_counts");
-  return MMDA_OK;
 }
 
 extern "C" int mmda_heads_fwd_task(const float* logits, int B, int ncls, float threshold, float* tcp, float* scores, float* labels,
@@ -1316,15 +1234,6 @@ extern "C" int mmda_loss_forms_describe(int B, int D, int have_loss, int have_dx
   out->diff_loss_sum = df.sum; out->diff_combine_blocks = df.blocks;
   out->cmd_form = cf.form; out->cmd_grid = cf.grid;
   out->recon_blocks = recon_blocks_of(n); out->misc_recon_blocks = misc_recon_blocks_of(n);
-  return MMDA_OK;
-}
-
-extern "C" int mmda_eval_accumulate(const float* pred, const float* truth, int N, int C, double* state, void* stream) {
-  if (!pred || !truth || !state || N < 0 || C <= 0 || C > EVAL_MAXC || ((uintptr_t)state & 7)) return MMDA_EINVAL;
-  if (N == 0) return MMDA_OK;
-  int blocks = (N + 255) / 256; if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(eval_counts_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, truth, N, C, state);
-  MMDA_CHECK_LAUNCH("mmda_eval_accumulate");
   return MMDA_OK;
 }
 

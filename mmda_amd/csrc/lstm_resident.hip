@@ -2,9 +2,7 @@
 // block and chunking), the instance table and pick_instance, block placement, the C entry points that view a plan, and the launch
 // itself.  No kernel lives here: lstm_barrier.hip, lstm_wave.hip and lstm_quad.hip hand theirs over by instance id.
 #include "lstm_resident.h"
-#include <algorithm>
-#include <utility>
-#include <vector>
+#include "dynamic_lds.h"
 
 using namespace mmda_resident;
 
@@ -260,16 +258,6 @@ bool place_blocks(std::vector<std::pair<int, int>>& clusters, int stride, int pe
   return fits;
 }
 
-// The attribute holds ONE value per kernel function (the last set wins): keep the LARGEST size ever asked of a function and set it
-// again only when a larger one appears -- B = 32 (160 KB), then B = 64 (32 KB), then B = 32 again must still find 160 KB
-void ensure_dynamic_lds(Kernel kernel, size_t bytes) {
-  static std::vector<std::pair<const void*, size_t>> attr_max;
-  const void* kf = reinterpret_cast<const void*>(kernel);
-  auto it = std::find_if(attr_max.begin(), attr_max.end(), [&](const std::pair<const void*, size_t>& e) { return e.first == kf; });
-  if (it != attr_max.end() && it->second >= bytes) return;
-  if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); }
-  if (it == attr_max.end()) attr_max.push_back({kf, bytes}); else it->second = bytes;
-}
 }  // namespace
 
 extern "C" int mmda_lstm_resident_applicable(int mode, int n, const mmda_lstm_desc* descs, int B, int T, int backward) {

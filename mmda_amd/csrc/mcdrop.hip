@@ -16,19 +16,6 @@ struct McArgs {
   const int32_t* dst; int64_t base; int B, K, W, bernoulli;
 };
 
-// The sum of one double per lane over the wave: a butterfly of six xor steps, widest first.  a + b and b + a are the same bits, so every
-// lane ends with the same total, and the order of the additions is fixed by the lane numbers alone.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // h(q) = -q ln q - (1 - q) ln(1 - q) in nats; h(0) = h(1) = 0 by the limit, a NaN stays a NaN
 __device__ __forceinline__ double bernoulli_entropy(double q) {
   if (q == 0.0 || q == 1.0) return 0.0;
@@ -37,10 +24,10 @@ __device__ __forceinline__ double bernoulli_entropy(double q) {
 
 // One wave per (sample b, column w): blockIdx.x = b, the four waves of a workgroup take w = wave, wave + 4, ...  Lane l holds draws
 // k = l, l + 64, l + 128, l + 192 (those below K) of its column, widened once to float64, in registers; a lane's partial sum adds them in
-// that order and wave_sum adds the 64 partials, so the order of every addition is a function of K alone -- not of B, dst or the
-// workgroup -- and two runs give the same bits.  The variance is a second pass over the same registers against the finished mean
-// (exactly 0 at K = 1: the mean of one draw is the draw).  A NaN draw reaches every sum of its own (b, w) and nothing else; the vote
-// is a count of `p > thr`, which a NaN fails.  No atomics, no LDS, no scratch.
+// that order and wave_sum_widest_first (common.h: six xor steps, 32 .. 1) adds the 64 partials, so the order of every addition is a
+// function of K alone -- not of B, dst or the workgroup -- and two runs give the same bits.  The variance is a second pass over the
+// same registers against the finished mean (exactly 0 at K = 1: the mean of one draw is the draw).  A NaN draw reaches every sum of
+// its own (b, w) and nothing else; the vote is a count of `p > thr`, which a NaN fails.  No atomics, no LDS, no scratch.
 __global__ __launch_bounds__(256) void mc_reduce_kernel(const McArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = (int)blockIdx.x;
@@ -66,7 +53,7 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(const McArgs a) {
     double s = 0.0;
 #pragma unroll
     for (int j = 0; j < MC_PER_LANE; ++j) s += (lane + 64 * j < K) ? d[j] : 0.0;
-    const double mean = wave_sum(s) / (double)K;
+    const double mean = wave_sum_widest_first(s) / (double)K;
     const int64_t at = r * W + w;
     if (a.o.mean && lane == 0) a.o.mean[at] = mean;
     if (a.o.var) {
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(const McArgs a) {
         const double e = d[j] - mean;
         q += (lane + 64 * j < K) ? e * e : 0.0;
       }
-      const double var = wave_sum(q) / (double)K;
+      const double var = wave_sum_widest_first(q) / (double)K;
       if (lane == 0) a.o.var[at] = var;
     }
     if (a.o.vote && a.thr) {
@@ -84,14 +71,14 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(const McArgs a) {
       int c = 0;
 #pragma unroll
       for (int j = 0; j < MC_PER_LANE; ++j) c += (lane + 64 * j < K && f[j] > t) ? 1 : 0;
-      c = wave_sum(c);
+      c = wave_sum_widest_first(c);
       if (lane == 0) a.o.vote[at] = (double)c / (double)K;       // the correctly rounded share (c * (1 / K) is an ulp off at K = 65)
     }
     if (a.bernoulli && (a.o.entropy || a.o.expected_entropy || a.o.mutual_info)) {
       double e = 0.0;
 #pragma unroll
       for (int j = 0; j < MC_PER_LANE; ++j) e += (lane + 64 * j < K) ? bernoulli_entropy(d[j]) : 0.0;
-      const double eh = wave_sum(e) / (double)K;
+      const double eh = wave_sum_widest_first(e) / (double)K;
       const double h = bernoulli_entropy(mean);
       const double diff = h - eh;
       const double mi = diff > 0.0 ? diff : (diff != diff ? diff : 0.0);       // max(0, .) that keeps a NaN

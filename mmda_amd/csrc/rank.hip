@@ -9,17 +9,16 @@
 // state), so no result depends on the order of arrival; the only floating-point sums, the two AP sums of mmda_rank_finish, are
 // thread-strided partials added by a fixed tree.  No floating-point atomic anywhere.
 #include "internal.h"
+#include "eval_terms.h"
 
 namespace {
 
-constexpr int RANK_MAXC = 16;                 // = CALIB_MAXC: rank <= 16 divides RANK_LCM
 constexpr int RANK_ROWS = 128;                // elements i per workgroup, one thread each
 constexpr int RANK_TILE = 512;                // rows j staged at a time: two lists of at most RANK_TILE keys, 4 KB of LDS
 constexpr int RANK_TARGET_WGS = 1024;         // the j rows are split until the grid has about this many workgroups (4 per CU)
 constexpr int RANK_FINISH_THREADS = 1024;     // of the one workgroup a class gets in mmda_rank_finish: sixteen waves hide its loads
 constexpr int64_t RANK_MAXN = (int64_t)1 << 20;
 constexpr int64_t RANK_MAXPAIRS = (int64_t)1 << 42;
-constexpr unsigned RANK_LCM = 720720u;        // lcm(1 .. 16)
 
 // fp32 -> uint32, strictly monotone on the order above: a < b <=> key(a) < key(b), a == b <=> key(a) == key(b).
 // NaN -> the bits of -inf, -0 -> +0, then the usual sign flip (negatives inverted, the others get the top bit).
@@ -130,82 +129,36 @@ __global__ __launch_bounds__(RANK_FINISH_THREADS) void rank_finish_kernel(const 
   P = 0;
   for (int w = 0; w < WAVES; ++w) P += p_s[w];                             // every thread needs it
   const unsigned long long Nn = (unsigned long long)N - P;
-  const double need_d = ceil(level * (double)P);
-  const unsigned long long need = need_d < 1.0 ? 1ull : (unsigned long long)need_d;
-  unsigned long long num = 0, fmin = ~0ull;
-  double ap = 0.0, apn = 0.0;
+  RankFigures<WAVES> fig(level, P);
   for (int i = tid; i < N; i += RANK_FINISH_THREADS) {
     const int64_t el = (int64_t)i * C + c;
     const uint4 k = *reinterpret_cast<const uint4*>(counts + el * 4);      // gp, gn, ep, en
     const unsigned long long gp = k.x, gn = k.y, ep = k.z, en = k.w;
-    const unsigned long long ln = Nn - gn - en, lp = P - gp - ep;
-    if (truth[el] > 0.f) {
-      num += 2ull * ln + en;
-      ap += (double)(gp + ep) / (double)(gp + ep + gn + en);               // ep >= 1: the element itself
-      if (gp + ep >= need && gn + en < fmin) fmin = gn + en;
-    } else {
-      apn += (double)(ln + en) / (double)(ln + en + lp + ep);              // en >= 1
-    }
+    if (truth[el] > 0.f) fig.positive(1ull, gp + ep, gn, gn + en, Nn);     // ep >= 1: the element itself
+    else fig.negative(1ull, gp, gn, P, Nn);                               // en >= 1
   }
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    num += __shfl_xor(num, o);
-    const unsigned long long other = __shfl_xor(fmin, o);
-    fmin = other < fmin ? other : fmin;
-    ap += __shfl_xor(ap, o);
-    apn += __shfl_xor(apn, o);
-  }
-  if (lane == 0) { num_s[wave] = num; min_s[wave] = fmin; ap_s[wave] = ap; apn_s[wave] = apn; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < WAVES; ++w) {
-      num += num_s[w];
-      fmin = min_s[w] < fmin ? min_s[w] : fmin;
-      ap += ap_s[w];
-      apn += apn_s[w];
-    }
-    const double nan = __builtin_nan("");
-    double* row = out + (int64_t)c * 6;
-    const bool both = P > 0 && Nn > 0;
-    row[0] = (double)P;
-    row[1] = (double)Nn;
-    row[2] = both ? (double)num / (double)(2ull * P * Nn) : nan;
-    row[3] = P > 0 ? ap / (double)P : nan;
-    row[4] = Nn > 0 ? apn / (double)Nn : nan;
-    row[5] = both ? (double)fmin / (double)Nn : nan;                       // level <= 1: need <= P, the lowest positive qualifies
-  }
+  if (fig.reduce(num_s, min_s, ap_s, apn_s)) fig.write(P, Nn, out + (int64_t)c * 6);
 }
 
-// Row C of the table, by one thread behind the class rows: per figure the mean over the classes where it is defined, in class order.
+// Row C of the table, by one thread behind the class rows.
 __global__ void rank_macro_kernel(int C, double* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double* macro = out + (int64_t)C * 6;
-  for (int f = 2; f < 6; ++f) {
-    double sum = 0.0;
-    int cnt = 0;
-    for (int c = 0; c < C; ++c) {
-      const double v = out[(int64_t)c * 6 + f];
-      if (v == v) { sum += v; ++cnt; }
-    }
-    macro[f] = cnt > 0 ? sum / (double)cnt : __builtin_nan("");
-    if (f < 4) macro[f - 2] = (double)cnt;                                 // classes that entered auroc, ap
-  }
+  if (threadIdx.x == 0 && blockIdx.x == 0) rank_macro_row(C, out);
 }
 
 // ------------------------------------------------------------------------------------------------ label ranking, per row
 // One thread per row: its C keys in registers, every positive j against every k.  The row's terms are integers (rank_j <= 16 divides
-// RANK_LCM), added per workgroup in LDS (64-bit) and from there, where non-zero, into the state.
+// EVAL_LCM), added per workgroup in LDS (64-bit) and from there, where non-zero, into the state.
 __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict__ scores, const float* __restrict__ truth, int64_t N, int C,
                                                         unsigned long long* __restrict__ state) {
-  __shared__ unsigned long long acc_s[2 + 3 * (RANK_MAXC + 1)];
+  __shared__ unsigned long long acc_s[2 + 3 * (EVAL_MAXC + 1)];
   const int words = 2 + 3 * (C + 1);
   for (int w = threadIdx.x; w < words; w += 256) acc_s[w] = 0ull;
   __syncthreads();
   for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < N; row += (int64_t)gridDim.x * 256) {
-    unsigned key[RANK_MAXC];
+    unsigned key[EVAL_MAXC];
     unsigned posmask = 0u;
 #pragma unroll
-    for (int c = 0; c < RANK_MAXC; ++c) {
+    for (int c = 0; c < EVAL_MAXC; ++c) {
       key[c] = 0u;
       if (c < C) {
         key[c] = rank_key(scores[row * C + c]);
@@ -214,18 +167,18 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
     }
     unsigned lrap = 0u, bad = 0u, cov = 0u;
 #pragma unroll
-    for (int j = 0; j < RANK_MAXC; ++j) {
+    for (int j = 0; j < EVAL_MAXC; ++j) {
       if (j < C && ((posmask >> j) & 1u)) {
         unsigned rank = 0u, L = 0u;
 #pragma unroll
-        for (int k = 0; k < RANK_MAXC; ++k) {
+        for (int k = 0; k < EVAL_MAXC; ++k) {
           if (k < C) {
             const unsigned ge = key[k] >= key[j] ? 1u : 0u;
             rank += ge;
             L += ge & (posmask >> k);
           }
         }
-        lrap += L * (RANK_LCM / rank);                          // rank >= 1: k == j
+        lrap += L * ((unsigned)EVAL_LCM / rank);                          // rank >= 1: k == j
         bad += rank - L;
         cov = rank > cov ? rank : cov;
       }
@@ -246,7 +199,7 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
 
 // what the three entry points accept for (N, C)
 bool rank_shape_ok(int64_t N, int C) {
-  return C >= 1 && C <= RANK_MAXC && N >= 0 && N <= RANK_MAXN && N * N * C <= RANK_MAXPAIRS;
+  return C >= 1 && C <= EVAL_MAXC && N >= 0 && N <= RANK_MAXN && N * N * C <= RANK_MAXPAIRS;
 }
 
 }  // namespace

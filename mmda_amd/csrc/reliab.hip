@@ -10,6 +10,7 @@
 // add per non-zero cell and workgroup.  Float64 sums use no atomic (senti.hip's convention): the workgroups leave partials, the last
 // one to arrive -- a ticket that is 0 between launches -- adds them in workgroup order.  No workgroup waits for another.
 #include "internal.h"
+#include "eval_terms.h"
 
 // every float64 expression below is restated in numpy by the tests: a product and a sum stay two roundings
 #pragma clang fp contract(off)
@@ -34,20 +35,6 @@ __device__ __forceinline__ double rl_rows_of_wave(double v) {
   v += __shfl_xor(v, 16);
   v += __shfl_xor(v, 32);
   return v;
-}
-
-// the last workgroup to arrive sees every partial (release by the fence before the ticket, agent-scope reads after it)
-__device__ __forceinline__ bool rl_last_to_arrive(unsigned long long* ticket, int* flag_s) {
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long prev = atomicAdd(ticket, 1ull);
-    *flag_s = prev == (unsigned long long)gridDim.x - 1ull;
-  }
-  __syncthreads();
-  if (!*flag_s) return false;
-  __threadfence();
-  return true;
 }
 
 __device__ __forceinline__ double rl_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(RL_THREADS) void reliab_accumulate_kernel(const flo
     for (int w = 0; w < RL_WAVES; ++w) v += red_s[w][cc][f];
     parts[((int64_t)blockIdx.x * 2 + f) * RL_MAXC + cc] = v;
   }
-  if (!rl_last_to_arrive(st, &last_s)) return;
+  if (!last_to_arrive(st, &last_s)) return;
   if (tid < 2 * C) {
     const int cc = tid % C, f = tid / C;
     double t = 0.0;
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(RL_THREADS) void scaling_prepare_kernel(const float
     if (n_s[tid]) atomicAdd(work + SC_N + tid, (unsigned long long)n_s[tid]);
     if (p_s[tid]) atomicAdd(work + SC_P + tid, (unsigned long long)p_s[tid]);
   }
-  if (!rl_last_to_arrive(work, &last_s)) return;
+  if (!last_to_arrive(work, &last_s)) return;
   const int G = per_class ? C : 1;
   if (tid < G) {
     const unsigned long long n = __hip_atomic_load(work + SC_N + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -356,7 +343,7 @@ __global__ __launch_bounds__(RL_THREADS) void scaling_iterate_kernel(const float
     }
     wd[SC_PARTS + ((int64_t)blockIdx.x * RL_MAXC + gg) * SC_NQ + k] = v;
   }
-  if (!rl_last_to_arrive(work, &last_s)) return;
+  if (!last_to_arrive(work, &last_s)) return;
   if (tid < G * SC_NQ) {
     const int gg = tid / SC_NQ, k = tid % SC_NQ;
     double t = 0.0;

@@ -11,6 +11,7 @@
 // use no atomic (loss_parts_add's convention, losses.hip): a thread adds its rows in row order, a workgroup its threads in a fixed
 // order, the workgroups leave partials, and the last one to arrive adds them in workgroup order -- the same batches give the same bits.
 #include "internal.h"
+#include "eval_terms.h"
 
 namespace {
 
@@ -67,16 +68,7 @@ __global__ __launch_bounds__(SENTI_THREADS) void senti_accumulate_kernel(const f
     for (int w = 0; w < SENTI_THREADS / WAVE; ++w) v += red_s[w][tid];
     parts[blockIdx.x * SENTI_NF + tid] = v;
   }
-  // the last workgroup to arrive sees every partial (release by the fence before the ticket, agent-scope reads after it)
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned long long prev = atomicAdd(&st[SENTI_TICKET], 1ull);
-    last_s = prev == (unsigned long long)gridDim.x - 1ull;
-  }
-  __syncthreads();
-  if (!last_s) return;
-  __threadfence();
+  if (!last_to_arrive(&st[SENTI_TICKET], &last_s)) return;
   if (tid < SENTI_NF) {
     double t = 0.0;
     for (int b = 0; b < (int)gridDim.x; ++b) t += __hip_atomic_load(parts + b * SENTI_NF + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

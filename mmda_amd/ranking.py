@@ -38,11 +38,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from .utils.eval import LCM, host_tables
 
 MAX_CLASSES = 16
 MAX_ROWS = 1 << 20                                               # rows of one table: the count launch is quadratic
 MAX_PAIRS = 1 << 42                                              # N^2 C comparisons of one table
-LCM = 720720                                                     # lcm(1 .. 16), as calibrate.LCM: L / rank is a multiple of 1 / LCM
 COLUMNS = ("n_pos", "n_neg", "auroc", "ap", "ap_neg", "fpr_at_tpr")
 SELECT_BY = {"valid_loss": None, "map": "map", "auroc": "macro_auroc"}
 
@@ -84,17 +84,9 @@ def score_keys(scores):
     return np.where(neg, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
 
 
-def _tables(scores, truth):
-    s = np.asarray(scores, dtype=np.float32)
-    pos = np.asarray(truth) > 0
-    if s.ndim != 2 or pos.shape != s.shape:
-        raise ValueError(f"scores and truth must both be (N, C), not {s.shape} and {pos.shape}")
-    return s, pos
-
-
 def rank_counts_host(scores, truth):
     """(N, C, 4) uint32 {gp, gn, ep, en} of host arrays scores / truth (N, C), by sorting each class's keys: O(N log N)."""
-    s, pos = _tables(scores, truth)
+    s, pos = host_tables(scores, truth, "scores and truth")
     N, C = s.shape
     keys = score_keys(s)
     out = np.zeros((N, C, 4), dtype=np.uint32)
@@ -150,7 +142,7 @@ def state_words(C):
 def label_ranking_host(scores, truth):
     """The row state of host arrays scores / truth (N, C) as int64 [2 + 3 (C + 1)]: rows, coverage_sum, rows_by_P[C + 1],
     lrap_num[C + 1], bad_sum[C + 1]."""
-    s, pos = _tables(scores, truth)
+    s, pos = host_tables(scores, truth, "scores and truth")
     N, C = s.shape
     if not 1 <= C <= MAX_CLASSES:
         raise ValueError(f"a score table must have 1 .. {MAX_CLASSES} classes, not {C}")
@@ -196,14 +188,6 @@ def rank_plan(N, C):
     return plan
 
 
-def _device_tables(scores, truth, who):
-    if not (isinstance(scores, torch.Tensor) and isinstance(truth, torch.Tensor) and scores.is_cuda and truth.is_cuda):
-        raise _lib.MMDAError(f"{who} needs device tensors (the HIP path has no CPU fallback)")
-    if scores.dim() != 2 or truth.shape != scores.shape:
-        raise ValueError(f"scores and truth must both be (N, C), not {tuple(scores.shape)} and {tuple(truth.shape)}")
-    return scores.detach().to(torch.float32).contiguous(), truth.detach().to(torch.float32).contiguous()
-
-
 def _counts(s, t):
     """the counts of device tables already checked: the one place that launches mmda_rank_counts"""
     N, C = s.shape
@@ -216,7 +200,7 @@ def _counts(s, t):
 
 def rank_counts(scores, truth):
     """(N, C, 4) int32 on the device, the bits of the uint32 counts {gp, gn, ep, en}: one launch (and a clear where the plan splits)."""
-    return _counts(*_device_tables(scores, truth, "rank_counts"))
+    return _counts(*_lib.device_tables(scores, truth, "rank_counts", "scores and truth"))
 
 
 def _table(s, t, tpr):
@@ -250,7 +234,7 @@ class RowRanking:
         self.state = torch.zeros(state_words(self.C), dtype=torch.int64, device=self.device)
 
     def update(self, scores, truth):
-        s, t = _device_tables(scores, truth, "RowRanking.update")
+        s, t = _lib.device_tables(scores, truth, "RowRanking.update", "scores and truth")
         if s.shape[1] != self.C:
             raise ValueError(f"scores and truth must both be (N, {self.C}), not {tuple(s.shape)}")
         step = max_rows(self.C)                                  # what one call takes: the row cap and the comparison cap
@@ -300,7 +284,7 @@ class RankingResult:
 def ranking_metrics(scores, truth, tpr=0.95, micro=False, label_ranking=True):
     """``RankingResult`` of device tables scores / truth (N, C): the per-class table and its means (two launches), the label-ranking
     state (one launch) and, ``micro=True``, the pooled figures by a second pass over the (N C, 1) view.  No read-back."""
-    s, t = _device_tables(scores, truth, "ranking_metrics")
+    s, t = _lib.device_tables(scores, truth, "ranking_metrics", "scores and truth")
     N, C = s.shape
     table, counts = _table(s, t, tpr)
     pooled = None
@@ -332,6 +316,6 @@ class FailurePrediction(RankingResult):
 def failure_prediction(tcp, correct, tpr=0.95):
     """ConfidNet's ``tcp`` (n, C) against ``correct = (labels == truth)`` (n, C), both on the device: does the confidence rank the
     correct decisions above the wrong ones.  ``FailurePrediction``, on the device."""
-    s, t = _device_tables(tcp, correct, "failure_prediction")
+    s, t = _lib.device_tables(tcp, correct, "failure_prediction", "scores and truth")
     table, counts = _table(s, t, tpr)
     return FailurePrediction(table, None, None, tpr, counts)

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .utils.eval import host_tables
 
 MAX_CLASSES, MAX_BINS, MAX_ROWS = 16, 64, 1 << 20
 FIX = 1 << 40
@@ -57,14 +58,6 @@ def check_how(how):
 
 
 # ---------------------------------------------------------------------------------------------------- host (numpy): the report
-def _tables(prob, target):
-    p = np.asarray(prob, dtype=np.float32)
-    y = np.asarray(target) > 0
-    if p.ndim != 2 or y.shape != p.shape:
-        raise ValueError(f"prob and target must both be (N, C), not {p.shape} and {y.shape}")
-    return p, y
-
-
 def clean(prob):
     """(p float32 clamped to [0, 1] with -0 -> 0 and NaN -> 0, nan mask)"""
     p = np.asarray(prob, dtype=np.float32)
@@ -79,7 +72,7 @@ def bin_index(p32, M):
 
 def elementwise_host(prob, target):
     """(sq, nll) float64 (N, C): the terms of the two sums, 0 at a NaN."""
-    p32, y = _tables(prob, target)
+    p32, y = host_tables(prob, target, "prob and target")
     p32, nan = clean(p32)
     p = p32.astype(np.float64)
     with np.errstate(divide="ignore"):
@@ -91,7 +84,7 @@ def elementwise_host(prob, target):
 def state_host(prob, target, bins=15):
     """The state of host arrays as a dict: ``cnt``, ``pos``, ``sum_p`` (C, M) uint64, ``n_nan`` (C,) uint64, ``sum_sq``, ``sum_nll``
     (C,) float64 (numpy's own summation order)."""
-    p32, y = _tables(prob, target)
+    p32, y = host_tables(prob, target, "prob and target")
     N, C = p32.shape
     check_shape(C, bins)
     p32, nan = clean(p32)
@@ -215,7 +208,7 @@ def nll_sums_host(z, y, a, b):
 
 
 def _groups(scores, truth, per_class):
-    s, y = _tables(scores, truth)
+    s, y = host_tables(scores, truth, "prob and target")
     z = logit_host(s)
     cols = [[c] for c in range(s.shape[1])] if per_class else [list(range(s.shape[1]))]
     out = []
@@ -264,7 +257,7 @@ def fit_scaling_host(scores, truth, how="temperature", per_class=False, max_iter
     """``(a, b float64 (C,), status, iterations int32 (C,))`` of host arrays: the iteration of ``mmda_scaling_fit`` in numpy (its sums
     in numpy's order)."""
     check_how(how)
-    s32, _ = _tables(scores, truth)
+    s32, _ = host_tables(scores, truth, "prob and target")
     C = s32.shape[1]
     a, b = np.ones(C), np.zeros(C)
     status, iters = np.ones(C, np.int32), np.zeros(C, np.int32)
@@ -289,14 +282,6 @@ def apply_host(scores, a, b):
 
 
 # ---------------------------------------------------------------------------------------------------- device
-def _device_tables(prob, target, who):
-    if not (isinstance(prob, torch.Tensor) and isinstance(target, torch.Tensor) and prob.is_cuda and target.is_cuda):
-        raise _lib.MMDAError(f"{who} needs device tensors (the HIP path has no CPU fallback)")
-    if prob.dim() != 2 or target.shape != prob.shape:
-        raise ValueError(f"prob and target must both be (N, C), not {tuple(prob.shape)} and {tuple(target.shape)}")
-    return prob.detach().to(torch.float32).contiguous(), target.detach().to(torch.float32).contiguous()
-
-
 class ReliabilityResult:
     """``figures`` (C + 2, 8) float64, columns ``FIGURES``: the class rows, row C their means, row C + 1 all classes pooled;
     ``diagram`` (C, M, 3) float64 ``{cnt, pos / cnt, mean p}`` per bin.  On the device as ``ReliabilityEval.result`` returns it;
@@ -348,7 +333,7 @@ class ReliabilityEval:
         return self
 
     def update(self, prob, target):
-        p, t = _device_tables(prob, target, "ReliabilityEval.update")
+        p, t = _lib.device_tables(prob, target, "ReliabilityEval.update", "prob and target")
         if p.shape[1] != self.C:
             raise ValueError(f"prob and target must both be (N, {self.C}), not {tuple(p.shape)}")
         if self.rows + p.shape[0] > MAX_ROWS:
@@ -375,7 +360,7 @@ class ReliabilityEval:
 
 def reliability_metrics(prob, target, bins=15):
     """``ReliabilityResult`` of device tables prob / target (N, C): two launches, no read-back."""
-    p, t = _device_tables(prob, target, "reliability_metrics")
+    p, t = _lib.device_tables(prob, target, "reliability_metrics", "prob and target")
     return ReliabilityEval(p.shape[1], bins, p.device).update(p, t).result()
 
 
@@ -434,7 +419,7 @@ def fit_scaling(scores, truth, how="temperature", per_class=False, max_iter=64):
     check_how(how)
     if isinstance(max_iter, bool) or not 1 <= int(max_iter) <= _lib.SCALING_MAX_ITER:
         raise ValueError(f"max_iter must be in 1 .. {_lib.SCALING_MAX_ITER}, not {max_iter!r}")
-    s, t = _device_tables(scores, truth, "fit_scaling")
+    s, t = _lib.device_tables(scores, truth, "fit_scaling", "prob and target")
     N, C = s.shape
     check_shape(C)
     if N > MAX_ROWS:

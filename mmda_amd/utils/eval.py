@@ -16,6 +16,16 @@ from ..step_rules import cls_setting
 
 KEYS = ["acc", "f1", "precision", "recall", "micro_f1", "micro_precision", "micro_recall", "weighted_f1", "weighted_precision",
         "weighted_recall"]
+LCM = 720720                             # lcm(1 .. 16): a / max(b, 1) with b <= 16 classes is an integer multiple of 1 / LCM (EVAL_LCM)
+
+
+def host_tables(values, truth, names):
+    """(values float32, truth > 0) of two host arrays that must both be (N, C); ``names``: how the message calls them."""
+    v = np.asarray(values, dtype=np.float32)
+    pos = np.asarray(truth) > 0
+    if v.ndim != 2 or pos.shape != v.shape:
+        raise ValueError(f"{names} must both be (N, C), not {v.shape} and {pos.shape}")
+    return v, pos
 
 
 def _div(a, b):

@@ -50,6 +50,22 @@ def case(n, C):
     return dict(scores=scores, truth=truth, labels=labels, truth_d=truth_d)
 
 
+SWEEP_SHAPES = [(2, 1), (37, 6), (300, 16)]                     # (300, 16): the longest class sums
+SWEEP_GRID = np.array([0.1, 0.25, THRESHOLD, 0.5, 0.8], dtype=np.float32)
+
+
+def sweep_case(n, C):
+    """(scores, truth_d, labels per cut-off of SWEEP_GRID) for the tests that hold a threshold sweep against the bootstrap's identity
+    replicate: ``case``'s decision tables with row n // 5 cleared in the SCORES too, so that it predicts nothing at any cut-off and
+    takes the ``max(union, 1)`` branch on both sides; the NaN and +-inf of ``value_case`` go through ``s > t`` on both."""
+    c = case(n, C)
+    scores = c["scores"].copy()
+    scores[n // 5] = 0.0
+    with np.errstate(invalid="ignore"):
+        labels = [(scores > t).astype(np.float32) for t in SWEEP_GRID]
+    return scores, c["truth_d"], labels
+
+
 def materialised_decisions(labels, truth, j):
     """(state int64 [3 C + 2], get_metrics' dict) of the rows ``j`` of the decision tables"""
     p, y = labels[j] > 0, truth[j] > 0

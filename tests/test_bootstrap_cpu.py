@@ -62,6 +62,23 @@ def test_weighted_decisions_equal_the_materialised_resample(shape):
     assert len(bt.decision_names(C)) == 10 + 3 * C
 
 
+@pytest.mark.parametrize("shape", bc.SWEEP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_a_sweep_row_and_the_identity_replicate_agree_on_the_host(shape):
+    """The inputs of tests/test_gpu_eval_terms.py hold what they are meant to, and the numpy restatements of its two sides
+    (``table_from_counts``, ``figures_from_states``) agree on them to the bound of the decision figures."""
+    from mmda_amd import calibrate as cal
+    n, C = shape
+    scores, truth_d, labels = bc.sweep_case(n, C)
+    assert bc.SWEEP_GRID[2] == np.float32(bc.THRESHOLD) and not truth_d[n // 5].any() and not any(l[n // 5].any() for l in labels)
+    if C >= 6:
+        assert np.isnan(scores).any() and np.isposinf(scores).any() and np.isneginf(scores).any()
+    table = cal.table_from_counts(*cal.sweep_counts(scores, truth_d, bc.SWEEP_GRID), n)
+    for k in range(len(bc.SWEEP_GRID)):
+        _, figures = bt.decisions_host(labels[k], truth_d, bc.SEED, 1)
+        assert bc.same_bits(table[k, 0], figures[1, 0])             # one division of the same two integers
+        assert (np.abs(table[k, 1:] - figures[1, 1:10]) <= (C + 2) * bc.EPS).all(), k
+
+
 @pytest.mark.parametrize("shape", CPU_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_weighted_ranking_equals_the_materialised_resample(shape):
     n, C = shape
