@@ -630,21 +630,28 @@ class MISA(nn.Module):
             if self._anchor is None or self._anchor.device != t.device:
                 self._anchor = torch.zeros(1, device=t.device, requires_grad=True)
             outs = _MISAFn.apply(self._anchor, self, t, v, a, len_dev, self.training, seed)
-            named = dict(zip(_PUB, outs[:-1]))
-            labels = outs[-1]
-        else:
-            self._forward_raw(t, v, a, len_dev, self.training, seed, inference=True)
-            pub = self._public()
-            named = {k: pub[k].clone() if k in pub else None for k in _PUB}
-            labels = pub["labels"].clone()
+            return self._publish(dict(zip(_PUB, outs[:-1])), outs[-1])
+        self._forward_raw(t, v, a, len_dev, self.training, seed, inference=True)
+        return self._publish_workspace()
+
+    def _publish(self, named, labels):
+        """Sets the side-channel attributes the getters read (every name of ``_PUB`` but ``scores``; the domain labels are None under
+        ``use_cmd_sim``) from ``named`` and returns (scores, labels)."""
         for k in _PUB:
-            if k in ("scores",):
+            if k == "scores":
                 continue
             val = named.get(k)
             if k.startswith("domain_label") and self.config.use_cmd_sim:
                 val = None
             setattr(self, k, val)
         return named["scores"], labels
+
+    def _publish_workspace(self):
+        """What a forward under ``no_grad`` left in the workspace, published: one clone per tensor of ``_PUB`` in its order, then the
+        labels -- the workspace is overwritten by the next forward, the attributes must not be."""
+        pub = self._public()
+        named = {k: pub[k].clone() if k in pub else None for k in _PUB}
+        return self._publish(named, pub["labels"].clone())
 
     def forward(self, sentences, video, acoustic, lengths, bert_sent=None, bert_sent_type=None, bert_sent_mask=None):
         """reference models.py:282-285: returns (predicted_scores (B,6), predicted_labels (B,6) in {0,1})."""
@@ -889,15 +896,7 @@ class MISA(nn.Module):
                    "mmda_misa_forward_encoded")
         self._fwd_id += 1
         self._last = dict(encoded=batch)
-        pub = self._public()
-        for k in _PUB:
-            if k == "scores":
-                continue
-            val = pub[k].clone() if k in pub else None
-            if k.startswith("domain_label") and self.config.use_cmd_sim:
-                val = None
-            setattr(self, k, val)
-        return pub["scores"].clone(), pub["labels"].clone()
+        return self._publish_workspace()
 
     def _forward_encoded_raw(self, cache, rows_ptr: int, B: int, training: bool, seed: int):
         """A forward from ``B`` cached rows (``rows_ptr``: their int32 indices on the device, repeats allowed) that no backward will

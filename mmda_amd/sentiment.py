@@ -38,6 +38,8 @@ class SentimentEval:
         if device.type != "cuda":
             raise _lib.MMDAError(f"SentimentEval counts on the GPU (device={device}): the HIP path has no CPU fallback")
         self.state = torch.zeros(_lib.SENTI_STATE_WORDS, dtype=torch.int64, device=device)
+        self.loss_sum = torch.zeros(1, dtype=torch.float32, device=device)
+        self.batches = 0
         self._lib = _lib.load()
 
     def update(self, pred: torch.Tensor, truth: torch.Tensor):
@@ -51,6 +53,21 @@ class SentimentEval:
         _lib.check(self._lib.mmda_senti_accumulate(p.data_ptr(), t.data_ptr(), p.numel(), self.state.data_ptr(), _lib.stream_ptr()),
                    "mmda_senti_accumulate")
         return self
+
+    def add_loss(self, pred: torch.Tensor, truth: torch.Tensor, senti_loss: str):
+        """adds this batch's criterion (``senti_loss``: 'l1' or 'mse', the mean over the batch's rows) to the running sum, on the
+        device: ``DeviceEval.add_cls_loss`` for the sentiment task.  ``pred``, ``truth``: as ``update`` takes them."""
+        p = pred.detach().to(torch.float32).contiguous().reshape(-1)
+        t = truth.detach().to(torch.float32).contiguous().reshape(-1)
+        if not (p.is_cuda and t.is_cuda) or p.numel() != t.numel():
+            raise _lib.MMDAError("SentimentEval.add_loss needs device tensors of equal size (the HIP path has no CPU fallback)")
+        _lib.check(self._lib.mmda_loss_reg(p.data_ptr(), t.data_ptr(), p.numel(), 1, _lib.SENTI_LOSS[senti_loss], 1.0,
+                                           self.loss_sum.data_ptr(), None, _lib.stream_ptr()), "mmda_loss_reg")
+        self.batches += 1
+
+    def mean_loss(self) -> float:
+        """the mean of the batches' losses: one read-back"""
+        return float(self.loss_sum.item()) / max(self.batches, 1)
 
     def figures(self) -> torch.Tensor:
         """(9,) float64 on the device, in the order of ``FIGURES``: one launch, nothing read back."""

@@ -28,6 +28,9 @@ from .utils import functions as F
 
 from .utils.eval import get_accuracy, get_metrics, DeviceEval      # reference utils/eval.py
 
+DEV_TEST = ("dev", "test")                # the splits a report takes, and the splits a loader-wide pass (infer, encode) takes
+SPLITS = ("train", "dev", "test")
+
 
 class Solver(object):
     def __init__(self, train_config, dev_config, test_config, train_data_loader, dev_data_loader, test_data_loader,
@@ -304,11 +307,26 @@ class Solver(object):
         print(f"Accuracy: {acc}")
         return history
 
-    # ------------------------------------------------------------------ eval (solver.py:311-370)
+    # ------------------------------------------------------------------ eval (solver.py:311-370; the passes: DESIGN.md 4s)
     def _load_best_checkpoint(self):
         path = f"checkpoints/model_{self.train_config.name}.std"
         if os.path.exists(path):
             self.model.load_state_dict(torch.load(path, weights_only=True))
+
+    def _split(self, mode, among=None):
+        """The ``mode`` split's loader.  ``among``: None -- ``eval``'s rule, anything but "dev" is the test split -- or the splits the
+        caller takes (``DEV_TEST``, ``SPLITS``): any other mode is refused by name."""
+        if among is None:
+            return self.dev_data_loader if mode == "dev" else self.test_data_loader
+        if mode not in among:
+            raise ValueError(f"mode must be {', '.join(map(repr, among[:-1]))} or {among[-1]!r}, not {mode!r}")
+        return getattr(self, f"{mode}_data_loader")
+
+    def _begin_pass(self, mode, to_print):
+        """An evaluation pass begins: the printed test pass runs on the best checkpoint, where there is one.  -> the split's loader"""
+        if mode == "test" and to_print:
+            self._load_best_checkpoint()
+        return self._split(mode)
 
     def _keep(self, keep, dataloader):
         """A keep set (mmda_amd/modality.py) as its three bits, or None; refused by name over the encoder cache (step_rules.MODALITY_RULES)"""
@@ -327,110 +345,12 @@ class Solver(object):
         from . import ops
         return ops.modality_mask(t.contiguous(), v.contiguous().float(), a.contiguous().float(), keep)
 
-    def eval(self, mode=None, to_print=False, thresholds=None, keep=None, scaling=None):
-        """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
-        labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels.
-        ``keep``: None, or a keep set (an int 0 .. 7 or modality names, mmda_amd/modality.py): the split is evaluated with the other
-        modalities blanked -- one ``mmda_modality_mask`` launch per batch in front of the forward; None is the plain pass.
-        ``scaling``: None, or a ``Scaling`` (mmda_amd/reliability.py): the scores of every batch are scaled behind the forward pass (one
-        ``mmda_scaling_apply`` launch), and labels, counts and the loss come from the scaled scores -- under ``thresholds``, or under
-        ``config.threshold`` in every class without them."""
-        assert mode is not None
-        keep = self._keep(keep, self.dev_data_loader if mode == "dev" else self.test_data_loader)
-        if self._sentiment():
-            if thresholds is not None:
-                step_rules.task_check("sentiment", self.model.senti_loss, calibrate="thresholds")
-            if scaling is not None:
-                step_rules.scaling_check("sentiment", scaling="Solver.eval")
-            return self._eval_sentiment(mode, to_print, keep)
-        if thresholds is not None or scaling is not None:
-            return self._eval_thresholds(mode, to_print, thresholds, keep, scaling)
-        self.model.eval()
-        y_true, y_pred, eval_loss = [], [], []
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        if mode == "test" and to_print:
-            path = f"checkpoints/model_{self.train_config.name}.std"
-            if os.path.exists(path):
-                self.model.load_state_dict(torch.load(path, weights_only=True))
-        # Device-side evaluation: predictions, the per-batch classification loss and the metric counts stay on the GPU; one
-        # read-back at the end of the pass instead of three per batch (solver.py:350-360 calls .item()/.cpu() per batch).
-        acc_dev = None
-        with torch.no_grad():
-            for batch in dataloader:
-                if isinstance(batch, EncodedBatch):
-                    predicted_scores, predicted_labels = self.model.forward_encoded(batch, keep=keep)
-                    emo_label = batch.emo()
-                else:
-                    t, v, a, y, emo_label, l, bert_sent, bert_sent_type, bert_sent_mask, ids = batch
-                    t = to_gpu(t); v = to_gpu(v); a = to_gpu(a); emo_label = to_gpu(emo_label)
-                    t, v, a = self._mask(t, v, a, keep)
-                    l = to_cpu(l)
-                    predicted_scores, predicted_labels = self.model(t, v, a, l, bert_sent, bert_sent_type, bert_sent_mask)
-                emo_label = emo_label.type(torch.float)
-                if predicted_labels.is_cuda:
-                    if acc_dev is None:
-                        acc_dev = DeviceEval(predicted_labels.shape[1], predicted_labels.device)
-                    acc_dev.update(predicted_labels, emo_label)
-                    acc_dev.add_cls_loss(predicted_scores, emo_label, **self._cls_setting())
-                else:
-                    eval_loss.append(self.get_cls_loss(predicted_scores, emo_label).item())
-                y_pred.append(predicted_labels.detach())
-                y_true.append(emo_label.detach())
-        y_true = torch.cat(y_true, 0).cpu().numpy().squeeze() if y_true else np.zeros((0,))
-        y_pred = torch.cat(y_pred, 0).cpu().numpy().squeeze() if y_pred else np.zeros((0,))
-        self._check_cluster(f"eval({mode})")
-        if acc_dev is not None:
-            loss, acc, self.last_eval_metrics = acc_dev.result()
-            return loss, acc, y_pred, y_true
-        eval_loss = float(np.mean(eval_loss)) if eval_loss else 0.0
-        self.last_eval_metrics = get_metrics(y_true, y_pred)
-        return eval_loss, get_accuracy(y_true, y_pred), y_pred, y_true
-
-    # ------------------------------------------------------------------ the sentiment task (mmda_amd/sentiment.py, DESIGN.md 4m)
-    def _eval_sentiment(self, mode, to_print, keep=None):
-        """``eval`` under task='sentiment': (mean batch loss, acc2_non0, preds (N,), truths (N,)).  The loop of ``eval``; per batch one
-        collector launch (``SentimentEval.update``) and one loss launch adding into a device sum, nothing read back until the pass is
-        over.  ``self.last_sentiment``: the reference's eval_mosei_senti keys (and 'f1_non0'), all from the one collector state."""
-        from . import _lib
-        from .sentiment import SentimentEval
-        if mode == "test" and to_print:
-            self._load_best_checkpoint()
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        kind = _lib.SENTI_LOSS[self.model.senti_loss]
-        lib, ev, loss_sum, batches = _lib.load(), None, None, 0
-        preds, truths = [], []
-        for scores, y in self._eval_batches(dataloader, keep=keep):
-            if not scores.is_cuda:
-                raise _lib.MMDAError("eval() under task='sentiment' counts on the GPU only (the HIP path has no CPU fallback)")
-            s, t = scores.detach().to(torch.float32).contiguous().reshape(-1), y.contiguous().reshape(-1)
-            if ev is None:
-                ev, loss_sum = SentimentEval(s.device), torch.zeros(1, dtype=torch.float32, device=s.device)
-            ev.update(s, t)
-            _lib.check(lib.mmda_loss_reg(s.data_ptr(), t.data_ptr(), s.numel(), 1, kind, 1.0, loss_sum.data_ptr(), None, _lib.stream_ptr()),
-                       "mmda_loss_reg")
-            batches += 1
-            preds.append(s); truths.append(t)
-        self._check_cluster(f"eval({mode})")
-        if ev is None:
-            self.last_sentiment = None
-            return 0.0, float("nan"), np.zeros((0,), np.float32), np.zeros((0,), np.float32)
-        self.last_sentiment = ev.as_dict()
-        self.last_sentiment_counts = ev.counts()
-        return (float(loss_sum.item()) / batches, self.last_sentiment["acc2_non0"], torch.cat(preds).cpu().numpy(),
-                torch.cat(truths).cpu().numpy())
-
-    def _print_sentiment(self):
-        from .sentiment import format_table
-        if getattr(self, "last_sentiment", None):
-            c = self.last_sentiment_counts
-            print(format_table(self.last_sentiment, c["n"], c["n_nonzero"]))
-
-    # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py, DESIGN.md 4j)
     def _eval_batches(self, dataloader, confidence=False, keep=None, scaling=None):
-        """The loop of ``eval``: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``;
-        ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence in them.
-        ``keep``: None or a keep set's three bits (``_keep``).  ``scaling``: None, or a ``Scaling``: the scores are its ``apply`` of the
-        model's (one launch per batch); the decisions and ``tcp`` stay the model's own."""
+        """The one walk over an evaluation split: (scores, truth) of every batch, on the device, under ``model.eval()`` and ``no_grad``,
+        one forward per batch; ``confidence=True``: (scores, truth, labels, tcp) -- the model's own decisions and ConfidNet's confidence
+        in them.  ``truth`` is the batch's ``y`` column under the sentiment task and its emotion labels otherwise.  ``keep``: None or a
+        keep set's three bits (``_keep``).  ``scaling``: None, or a ``Scaling``: the scores are its ``apply`` of the model's (one launch
+        per batch); the decisions and ``tcp`` stay the model's own."""
         self.model.eval()
         with torch.no_grad():
             for batch in dataloader:
@@ -450,32 +370,53 @@ class Solver(object):
                 else:
                     yield predicted_scores, emo_label.type(torch.float)
 
-    def _eval_thresholds(self, mode, to_print, thresholds, keep=None, scaling=None):
-        """``eval`` under cut-offs per class and / or a scaling; ``thresholds=None``: ``config.threshold`` in every class"""
+    def eval(self, mode=None, to_print=False, thresholds=None, keep=None, scaling=None):
+        """``thresholds``: None -- the model's own labels (``scores > config.threshold``) -- or a ``Thresholds`` (mmda_amd/calibrate.py):
+        labels and counts then come from ``scores > thresholds.values`` class by class, and the returned ``y_pred`` are those labels.
+        ``keep``: None, or a keep set (an int 0 .. 7 or modality names, mmda_amd/modality.py): the split is evaluated with the other
+        modalities blanked -- one ``mmda_modality_mask`` launch per batch in front of the forward; None is the plain pass.
+        ``scaling``: None, or a ``Scaling`` (mmda_amd/reliability.py): the scores of every batch are scaled behind the forward pass (one
+        ``mmda_scaling_apply`` launch), and labels, counts and the loss come from the scaled scores -- under ``thresholds``, or under
+        ``config.threshold`` in every class without them."""
+        assert mode is not None
+        keep = self._keep(keep, self._split(mode))
+        if self._sentiment():
+            if thresholds is not None:
+                step_rules.task_check("sentiment", self.model.senti_loss, calibrate="thresholds")
+            if scaling is not None:
+                step_rules.scaling_check("sentiment", scaling="Solver.eval")
+            return self._eval_sentiment(mode, to_print, keep)
+        return self._eval_emotion(mode, to_print, thresholds, keep, scaling)
+
+    def _eval_emotion(self, mode, to_print, thresholds=None, keep=None, scaling=None):
+        """``eval`` of the emotion labels.  Predictions, the per-batch classification loss and the metric counts stay on the GPU: one
+        read-back at the end of the pass instead of three per batch (solver.py:350-360 calls .item()/.cpu() per batch).  Without
+        ``thresholds`` and ``scaling`` the model's own labels are counted (``DeviceEval.update``); otherwise the labels are cut from the
+        (scaled) scores in the launch that counts them (``DeviceEval.update_thr``; ``thresholds=None``: ``config.threshold`` in every
+        class).  These are two launches and two label tensors, not one path with a default."""
         from . import _lib
-        if mode == "test" and to_print:
-            self._load_best_checkpoint()
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        if thresholds is None:
+        dataloader = self._begin_pass(mode, to_print)
+        own = thresholds is None and scaling is None
+        if own:
+            thr = None
+        elif thresholds is None:
             thr = torch.full((int(self.train_config.num_classes),), float(self.train_config.threshold), dtype=torch.float32,
                              device=self.device)
         else:
             thr = thresholds.values.to(device=self.device, dtype=torch.float32).contiguous()
-        acc_dev, lib = None, _lib.load()
+        acc_dev = None
         y_true, y_pred = [], []
-        for scores, emo_label in self._eval_batches(dataloader, keep=keep, scaling=scaling):
+        for scores, emo_label, labels, _ in self._eval_batches(dataloader, confidence=True, keep=keep, scaling=scaling):
             if not scores.is_cuda:
-                raise _lib.MMDAError("eval(thresholds=...) counts on the GPU only (the HIP path has no CPU fallback)")
-            if thr.numel() != scores.shape[1]:
-                raise ValueError(f"thresholds has {thr.numel()} entries, the model {scores.shape[1]} classes")
+                raise _lib.MMDAError(f"{'eval()' if own else 'eval(thresholds=...)'} counts on the GPU only (the HIP path has no CPU fallback)")
             if acc_dev is None:
                 acc_dev = DeviceEval(scores.shape[1], scores.device)
-            s, t = scores.detach().to(torch.float32).contiguous(), emo_label.contiguous()
-            labels = torch.empty_like(s)
-            _lib.check(lib.mmda_eval_accumulate_thr(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], thr.data_ptr(), labels.data_ptr(),
-                                                    acc_dev.state.data_ptr(), _lib.stream_ptr()), "mmda_eval_accumulate_thr")
+            if own:
+                acc_dev.update(labels, emo_label)
+            else:
+                labels = acc_dev.update_thr(scores, emo_label, thr)
             acc_dev.add_cls_loss(scores, emo_label, **self._cls_setting())
-            y_pred.append(labels)
+            y_pred.append(labels.detach())
             y_true.append(emo_label.detach())
         y_true = torch.cat(y_true, 0).cpu().numpy().squeeze() if y_true else np.zeros((0,))
         y_pred = torch.cat(y_pred, 0).cpu().numpy().squeeze() if y_pred else np.zeros((0,))
@@ -486,9 +427,43 @@ class Solver(object):
         loss, acc, self.last_eval_metrics = acc_dev.result()
         return loss, acc, y_pred, y_true
 
+    # ------------------------------------------------------------------ the sentiment task (mmda_amd/sentiment.py)
+    def _eval_sentiment(self, mode, to_print, keep=None):
+        """``eval`` under task='sentiment': (mean batch loss, acc2_non0, preds (N,), truths (N,)).  Per batch one collector launch
+        (``SentimentEval.update``) and one loss launch adding into a device sum (``SentimentEval.add_loss``), nothing read back until the
+        pass is over.  ``self.last_sentiment``: the reference's eval_mosei_senti keys (and 'f1_non0'), all from the one collector state."""
+        from . import _lib
+        from .sentiment import SentimentEval
+        dataloader = self._begin_pass(mode, to_print)
+        ev = None
+        preds, truths = [], []
+        for scores, y in self._eval_batches(dataloader, keep=keep):
+            if not scores.is_cuda:
+                raise _lib.MMDAError("eval() under task='sentiment' counts on the GPU only (the HIP path has no CPU fallback)")
+            s, t = scores.detach().to(torch.float32).contiguous().reshape(-1), y.contiguous().reshape(-1)
+            if ev is None:
+                ev = SentimentEval(s.device)
+            ev.update(s, t)
+            ev.add_loss(s, t, self.model.senti_loss)
+            preds.append(s); truths.append(t)
+        self._check_cluster(f"eval({mode})")
+        if ev is None:
+            self.last_sentiment = None
+            return 0.0, float("nan"), np.zeros((0,), np.float32), np.zeros((0,), np.float32)
+        self.last_sentiment = ev.as_dict()
+        self.last_sentiment_counts = ev.counts()
+        return ev.mean_loss(), self.last_sentiment["acc2_non0"], torch.cat(preds).cpu().numpy(), torch.cat(truths).cpu().numpy()
+
+    def _print_sentiment(self):
+        from .sentiment import format_table
+        if getattr(self, "last_sentiment", None):
+            c = self.last_sentiment_counts
+            print(format_table(self.last_sentiment, c["n"], c["n_nonzero"]))
+
+    # ------------------------------------------------------------------ threshold calibration (mmda_amd/calibrate.py, DESIGN.md 4j)
     def calibrate(self, mode="dev", grid=None, objective=None, per_class=True, scaling=None):
-        """Sweeps every cut-off of ``grid`` (default 0.01 .. 0.99) over the ``mode`` split in one pass -- the loop of ``eval`` with
-        ``ThresholdSweep.update`` in ``DeviceEval.update``'s place -- and selects, on the device, the cut-off (``per_class=False``) or the
+        """Sweeps every cut-off of ``grid`` (default 0.01 .. 0.99) over the ``mode`` split in one pass -- ``_eval_batches`` with
+        ``ThresholdSweep.update`` per batch -- and selects, on the device, the cut-off (``per_class=False``) or the
         cut-off per class that maximises ``objective`` ("f1", "micro_f1", "weighted_f1", "acc"; None: what ``config.eval_mode`` names).
         Sets and returns ``self.thresholds``; the sweep's table of the ten figures per cut-off is kept in ``self.last_calibration``.
         ``scaling``: None, or a ``Scaling``: the cut-offs are chosen on the scaled scores (``eval`` must then be given both)."""
@@ -500,9 +475,7 @@ class Solver(object):
         if objective is None:
             objective = objective_for(getattr(self.train_config, "eval_mode", "macro"), per_class)
         check_objective(objective, per_class)
-        if mode not in ("dev", "test"):
-            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        dataloader = self._split(mode, DEV_TEST)
         sweep = ThresholdSweep(int(self.train_config.num_classes), grid, self.device)
         for scores, emo_label in self._eval_batches(dataloader, scaling=scaling):
             sweep.update(scores, emo_label)
@@ -531,11 +504,11 @@ class Solver(object):
 
     # ------------------------------------------------------------------ reliability and logit scaling (mmda_amd/reliability.py)
     def _score_tables(self, mode, who, confidence, scaling=None):
-        """(scores, truth, labels, tcp or None) of the ``mode`` split, concatenated on the device: the loop of ``rank``"""
+        """(scores, truth, labels, tcp or None) of the ``mode`` split, concatenated on the device: the one gather, behind
+        ``rank``, ``reliability``, ``fit_scaling`` and ``bootstrap`` (``who``, for the messages).  ``tcp`` is None where it is not asked
+        for (``confidence``) or the model has no confidence column per class."""
         from . import _lib
-        if mode not in ("dev", "test"):
-            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        dataloader = self._split(mode, DEV_TEST)
         S, T, L, Q = [], [], [], []
         for scores, emo_label, labels, tcp in self._eval_batches(dataloader, confidence=True, scaling=scaling):
             if not scores.is_cuda:
@@ -595,32 +568,19 @@ class Solver(object):
 
     # ------------------------------------------------------------------ ranking metrics (mmda_amd/ranking.py)
     def rank(self, mode="dev", tpr=0.95, confidence=True):
-        """How the model RANKS the ``mode`` split ("dev" or "test"), before any cut-off: the loop of ``eval`` keeping scores, truth, the
+        """How the model RANKS the ``mode`` split ("dev" or "test"), before any cut-off: ``_score_tables`` keeps scores, truth, the
         model's decisions and ``model.tcp`` of every batch on the device, then ``{"scores": ranking_metrics(scores, truth),
         "confidence": failure_prediction(tcp, labels == truth)}`` -- both ``RankingResult``s on the device; ``confidence`` is None
         where it is not asked for or the model has no confidence column per class.  Sets and returns ``self.last_ranking``.  Waits for
         nothing but the cluster check; reading a result back (``.cpu()``, ``.as_dict()``) is the caller's."""
-        from . import _lib
         from .ranking import failure_prediction, ranking_metrics
         if self._sentiment():
             step_rules.task_check("sentiment", self.model.senti_loss, rank=True)
-        if mode not in ("dev", "test"):
-            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
-        dataloader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        S, T, L, Q = [], [], [], []
-        for scores, emo_label, labels, tcp in self._eval_batches(dataloader, confidence=True):
-            if not scores.is_cuda:
-                raise _lib.MMDAError("rank() counts on the GPU only (the HIP path has no CPU fallback)")
-            S.append(scores.detach()); T.append(emo_label.detach()); L.append(labels.detach())
-            Q.append(None if tcp is None else tcp.detach())
-        self._check_cluster(f"rank({mode})")
-        if not S:
-            raise ValueError(f"rank({mode!r}): the {mode} loader yields no batch")
-        scores, truth = torch.cat(S, 0), torch.cat(T, 0)
+        scores, truth, labels, tcp = self._score_tables(mode, "rank", confidence)
         out = {"scores": ranking_metrics(scores, truth, tpr=tpr), "confidence": None}
-        if confidence and all(q is not None and q.shape == l.shape for q, l in zip(Q, L)):
-            correct = (torch.cat(L, 0) > 0) == (truth > 0)
-            out["confidence"] = failure_prediction(torch.cat(Q, 0), correct.to(torch.float32), tpr=tpr)
+        if tcp is not None:
+            correct = (labels > 0) == (truth > 0)
+            out["confidence"] = failure_prediction(tcp, correct.to(torch.float32), tpr=tpr)
         self.last_ranking = out
         return out
 
@@ -633,12 +593,9 @@ class Solver(object):
         runs with the other modalities blanked (``InferencePass.run`` / ``run_loader`` with that ``keep``)."""
         from .data import DeviceLoader
         from .inference import ORDERS, InferencePass
-        loaders = dict(train=self.train_data_loader, dev=self.dev_data_loader, test=self.test_data_loader)
-        if mode not in loaders:
-            raise ValueError(f"mode must be 'train', 'dev' or 'test', not {mode!r}")
+        loader = self._split(mode, SPLITS)
         if order != "loader" and order not in ORDERS:
             raise ValueError(f"order must be 'loader', 'length' or 'dataset', not {order!r}")
-        loader = loaders[mode]
         if order != "loader" and not isinstance(loader, DeviceLoader):
             raise ValueError(f"order={order!r} re-batches a device-resident dataset: the {mode} loader must be a DeviceLoader "
                              f"(it is a {type(loader).__name__}); use order='loader'")
@@ -661,9 +618,7 @@ class Solver(object):
         tcp and per class the mean Shapley value of each modality (read back for the print)."""
         from .data import DeviceLoader
         from .modality import ModalityPass, format_table
-        if mode not in ("dev", "test"):
-            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
-        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
+        loader = self._split(mode, DEV_TEST)
         step_rules.modality_check(0, encoded=isinstance(loader, EncodedLoader))
         if values is None:
             values = ("scores",) if self._sentiment() else ("scores", "tcp")
@@ -690,13 +645,11 @@ class Solver(object):
         ``to_print``: that table."""
         from .data import DeviceDataset, DeviceLoader
         from .uncertainty import KINDS, MCDropoutPass, check_settings
-        if mode not in ("dev", "test"):
-            raise ValueError(f"mode must be 'dev' or 'test', not {mode!r}")
+        loader = self._split(mode, DEV_TEST)
         cfg = self.train_config
         if passes is None:
             passes = int(getattr(cfg, "mc_passes", 0) or 0) or 32
         check_settings(passes, columns, getattr(cfg, "task", "emotion"))
-        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
         p = MCDropoutPass(self.model, passes=passes, seed=seed, columns=columns)
         if isinstance(loader, EncodedLoader):
             res, truth = p.run_cache(loader.cache), loader.cache.emo
@@ -730,7 +683,7 @@ class Solver(object):
     # ------------------------------------------------------------------ bootstrap intervals (mmda_amd/bootstrap.py)
     def bootstrap(self, mode="test", replicates=2000, seed=0, alpha=0.05, thresholds=None, scaling=None, confidence=True, to_print=False):
         """How far the figures of the ``mode`` split ("dev" or "test") would move on another draw of it: the split is gathered once
-        (the loop of ``rank``) and resampled ``replicates`` times on the device.  Sets and returns ``self.last_bootstrap``:
+        (``_score_tables``) and resampled ``replicates`` times on the device.  Sets and returns ``self.last_bootstrap``:
         ``metrics`` -- the cut-off figures of ``eval`` under the same ``thresholds`` / ``scaling`` (the model's own decisions where
         both are None) --, ``ranking`` (``rank``'s score table), ``confidence`` (its failure-prediction table, None where the model has
         no confidence column per class or it is not asked for) and, with ``thresholds``, ``vs_default``: the paired comparison of those
@@ -740,8 +693,7 @@ class Solver(object):
         from .bootstrap import Bootstrap
         from .utils.eval import KEYS
         cfg = self.train_config
-        loader = self.dev_data_loader if mode == "dev" else self.test_data_loader
-        sharded = getattr(loader, "shard", None) if self.dp is not None else None
+        sharded = getattr(self._split(mode), "shard", None) if self.dp is not None else None
         step_rules.bootstrap_check(task="sentiment" if self._sentiment() else "emotion", replicates=replicates, sharded=sharded, mode=mode)
         scores, truth, labels, tcp = self._score_tables(mode, "bootstrap", confidence, scaling)
         n, C = int(scores.shape[0]), int(scores.shape[1])
@@ -783,10 +735,7 @@ class Solver(object):
         pass over its dataset at ``batch_size`` (default: the loader's).  Wrap it in an ``EncodedLoader`` and hand that to the solver
         in the split's place to train, or evaluate, from the stored encoder outputs."""
         from .data import DeviceLoader
-        loaders = dict(train=self.train_data_loader, dev=self.dev_data_loader, test=self.test_data_loader)
-        if mode not in loaders:
-            raise ValueError(f"mode must be 'train', 'dev' or 'test', not {mode!r}")
-        loader = loaders[mode]
+        loader = self._split(mode, SPLITS)
         if not isinstance(loader, DeviceLoader):
             raise ValueError(f"encode({mode!r}) reads a device-resident dataset: the {mode} loader must be a DeviceLoader "
                              f"(it is a {type(loader).__name__})")

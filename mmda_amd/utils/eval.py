@@ -88,6 +88,19 @@ class DeviceEval:
         _lib.check(self._lib.mmda_eval_accumulate(p.data_ptr(), t.data_ptr(), p.shape[0], self.C, self.state.data_ptr(),
                                                   _lib.stream_ptr()), "mmda_eval_accumulate")
 
+    def update_thr(self, scores: torch.Tensor, truth: torch.Tensor, thr: torch.Tensor) -> torch.Tensor:
+        """``update`` for labels that are cut here: counts ``scores > thr`` class by class (scores, truth (N, C); thr (C,) fp32, all on
+        the device) in the same launch that writes those labels, and returns them (N, C) fp32; no synchronisation."""
+        s, t = scores.detach().to(torch.float32).contiguous(), truth.detach().to(torch.float32).contiguous()
+        if not (s.is_cuda and t.is_cuda and thr.is_cuda) or s.shape != t.shape or s.shape[1] != self.C:
+            raise _lib.MMDAError(f"DeviceEval.update_thr needs device tensors (N, {self.C}) (the HIP path has no CPU fallback)")
+        if thr.numel() != self.C:
+            raise ValueError(f"thresholds has {thr.numel()} entries, the model {s.shape[1]} classes")
+        labels = torch.empty_like(s)
+        _lib.check(self._lib.mmda_eval_accumulate_thr(s.data_ptr(), t.data_ptr(), s.shape[0], s.shape[1], thr.data_ptr(), labels.data_ptr(),
+                                                      self.state.data_ptr(), _lib.stream_ptr()), "mmda_eval_accumulate_thr")
+        return labels
+
     def add_cls_loss(self, scores: torch.Tensor, truth: torch.Tensor, pos_weight=None, focal_gamma=0.0):
         """adds this batch's classification loss (solver.py:373-385; under ``pos_weight`` / ``focal_gamma`` the criterion of
         ``bce_sum_over_classes``) to the running sum, on the device"""

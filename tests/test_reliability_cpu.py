@@ -282,7 +282,7 @@ def test_sentiment_refusal_names_the_rule():
 
 def test_defaults_leave_the_eval_and_calibrate_argument_paths_unchanged():
     from mmda_amd.solver import Solver
-    for fn in (Solver.eval, Solver.calibrate, Solver._eval_batches, Solver._eval_thresholds, Solver.reliability,
+    for fn in (Solver.eval, Solver.calibrate, Solver._eval_batches, Solver._eval_emotion, Solver.reliability,
                Solver._calibrate_after_training):
         assert inspect.signature(fn).parameters["scaling"].default is None
     names = list(inspect.signature(Solver.eval).parameters)
@@ -298,22 +298,21 @@ def test_defaults_leave_the_eval_and_calibrate_argument_paths_unchanged():
         def _sentiment(self):
             return False
 
-        def _eval_thresholds(self, *a):
-            calls.append(a)
-            return "thr"
-
         def _eval_batches(self, dataloader, confidence=False, keep=None, scaling=None):
-            calls.append(("batches", scaling))
+            calls.append((keep, scaling))
             return iter(())
 
     s = Probe()
     s.dev_data_loader = s.test_data_loader = []
-    thr, sc = object(), object()
-    assert s.eval("dev", thresholds=thr) == "thr" and calls.pop() == ("dev", False, thr, None, None)
-    assert s.eval("dev", scaling=sc) == "thr" and calls.pop() == ("dev", False, None, None, sc)
-    assert s.eval("test", True, thr, None, sc) == "thr" and calls.pop() == ("test", True, thr, None, sc)
-    # without either, eval() stays in its own loop: neither helper is reached
-    s.model = type("M", (), {"eval": lambda self: None})()
+    s.device = torch.device("cpu")
+    s.train_config = type("C", (), {"num_classes": 2, "threshold": 0.5, "name": "no_such_run"})()
     s._check_cluster = lambda where: None
-    out = s.eval("dev")
-    assert calls == [] and out[0] == 0.0 and out[2].shape == (0,)
+    thr, sc = type("T", (), {"values": torch.tensor([0.25, 0.75])})(), object()
+    # what a caller observes of "the defaults change nothing": every form walks its split exactly once, and exactly the scaling it was
+    # given reaches the walk
+    for args, kw, want in ((("dev",), {}, None), (("dev",), dict(thresholds=thr), None), (("dev",), dict(scaling=sc), sc),
+                           (("test", True, thr, None, sc), {}, sc)):
+        out = s.eval(*args, **kw)
+        assert calls == [(None, want)], (args, kw)
+        calls.clear()
+        assert out[0] == 0.0 and out[2].shape == (0,)
