@@ -1243,6 +1243,50 @@ int mmda_boot_rank(const int32_t* inv, const int32_t* first, const int32_t* last
                    uint64_t seed, double tpr_level, double* out, void* stream);
 int mmda_boot_summary(const double* a, const double* b, int R, int F, double q_lo, double q_hi, int ncols, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- nearest neighbours, Trust Score
+ * Exact set-wise k-nearest-neighbour search between two device tables (mmda_amd/neighbours.py; csrc/knn.hip).
+ * mmda_knn_sets: query (Q, D), base (N, D) fp32, row-major, dense; member[N]: bit s set = base row in set s (any number of sets, or
+ *   none).  dist / index (Q, S, k): per (query row, set) the k nearest member rows -- squared Euclidean distances ascending, equal
+ *   distances by lower row number; where a set has fewer than k eligible rows the tail is +inf / -1.  exclude_self != 0: query row i
+ *   ignores base row i (by row number, whatever its distance).  A pair whose distance is NaN or +inf (a non-finite entry in either
+ *   row) is never selected.  Three launches, no float atomics, no read-back:
+ *     1. row norms |q|^2, |b|^2 (one wave per row, lane l adds elements l, l + 64, .. by fmaf, a fixed xor butterfly adds the lanes);
+ *     2. grid (query tiles, slabs): the products q.b of a tile_q x 128 tile on v_mfma_f32_32x32x2_f32, operands staged through LDS in
+ *        32-wide pieces of D, k ascending from 0 -- one fmaf chain per pair whatever the tile --, d = fmaf(-2, q.b, |q|^2 + |b|^2),
+ *        and the running lists of the workgroup's (query row, set)s updated in LDS from the tile; the Q x N matrix is never written;
+ *     3. one wave per (query row, set): the slabs' lists merged by (distance, row number), the k survivors recomputed as
+ *        sum_i (q_i - b_i)^2 (fmaf, lane l the elements l, l + 64, .., the same butterfly) and sorted by (that distance, row number).
+ *   dist holds the recomputed value: a query equal to a base row reports exactly 0.  Both forms are functions of the two rows and D
+ *   alone, so Q calls over one row each give the bits of one call over Q rows.  1 <= D <= 1024, 1 <= S <= 16, 1 <= k <= 16, N >= 1,
+ *   Q >= 0 (0: MMDA_OK, no launch); work: what mmda_knn_plan_describe sizes, 16-byte aligned; work_bytes below that, a NULL pointer
+ *   or a shape outside the limits: MMDA_EINVAL before any launch.
+ * mmda_knn_plan_describe (host only; the launcher reads the same function): the launches of a shape.
+ * mmda_trust_score: dist (n, 2 C, k) fp32 as mmda_knn_sets wrote it over the sets s = 2 c + v (the base rows with truth[:, c] == v),
+ *   labels (n, C) fp32 the decisions (> 0: positive).  With y = labels[i][c] > 0, p = dist[i][2 c + y][0], o = dist[i][2 c + 1 - y][0]:
+ *   trust[i][c] = sqrt(o) / (sqrt(p) + 1e-12) in float64 (1e-12: the published implementation's min_dist); p = +inf (no row of the
+ *   decided label) gives 0, else o = +inf gives +inf.  Optional (NULL: not written) d_pred / d_other (n, C) fp32 = p / o and, with index
+ *   (n, 2 C, k), nearest_pred / nearest_other (n, C) int32 their row numbers.  One launch.  1 <= C <= 8, 1 <= k <= 16, n >= 0;
+ *   dist, labels or trust NULL, a nearest table without index: MMDA_EINVAL. */
+typedef struct mmda_knn_plan {
+  int tile_q;               /* query rows of a workgroup: 64, or 32 where the lists of 64 rows would not fit (S k > 200) */
+  int tile_b;               /* base rows of one distance tile */
+  int slab_rows;            /* base rows of a slab: a multiple of tile_b */
+  int slabs;
+  int merge;                /* 1: the last launch merges the lists of more than one slab */
+  int launches;
+  int grid_x, grid_y;       /* of the search launch: query tiles, slabs */
+  int threads;              /* of a workgroup of the search launch */
+  int lds_bytes;            /* dynamic LDS of a workgroup of the search launch */
+  int vector_loads;         /* 1: D % 4 == 0, rows are staged by 16-byte loads (where the tables are 16-byte aligned) */
+  int max_slabs;
+  int64_t work_bytes;       /* row norms, then the slabs' lists */
+} mmda_knn_plan;
+int mmda_knn_plan_describe(int64_t Q, int64_t N, int D, int S, int k, mmda_knn_plan* out);
+int mmda_knn_sets(const float* query, const float* base, const uint32_t* member, int64_t Q, int64_t N, int D, int S, int k,
+                  int exclude_self, float* dist, int32_t* index, void* work, int64_t work_bytes, void* stream);
+int mmda_trust_score(const float* dist, const int32_t* index, const float* labels, int64_t n, int C, int k, double* trust,
+                     float* d_pred, float* d_other, int32_t* nearest_pred, int32_t* nearest_other, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,10 @@ damped Newton iteration whose state never leaves the device; ``config.scaling``)
 reduced on the device to mean, variance, entropy and mutual information; ``mc_statistics``: that reduction over any table;
 ``config.mc_passes``); ``bootstrap`` says how far any of those figures would move on another draw of the split (``Bootstrap``: the rows
 resampled R times on the device by a counter-based generator, percentile intervals per figure and paired comparisons over the same
-resamples; ``resample_indices``: the draws restated in numpy; ``config.bootstrap``).
+resamples; ``resample_indices``: the draws restated in numpy; ``config.bootstrap``); ``neighbours`` searches one device table for the
+nearest rows of another, exactly (``knn_search``, ``NeighbourIndex``: a distance GEMM on the f32-input MFMA whose matrix is never
+written) and builds ``tcp``'s third baseline on it (``TrustIndex`` / ``TrustResult``: the Trust Score, the distance to the nearest
+training example of the other label over that to the nearest of the decided one; ``config.trust_k``).
 """
 from . import _lib  # noqa: F401
 from .models import MISA, Model  # noqa: F401
@@ -35,3 +38,4 @@ from .modality import MODALITIES, ModalityPass, ModalityResult, keep_bits, parse
 from .reliability import ReliabilityEval, ReliabilityResult, Scaling, fit_scaling, reliability_metrics  # noqa: F401
 from .uncertainty import MCDropoutPass, MCDropoutResult, mc_statistics  # noqa: F401
 from .bootstrap import Bootstrap, BootstrapResult, BootstrapSummary, boot_plan, resample_indices  # noqa: F401
+from .neighbours import NeighbourIndex, TrustIndex, TrustResult, knn_search  # noqa: F401

@@ -225,7 +225,15 @@ class BootPlan(C.Structure):
                 ("state_words", C.c_int), ("lds_rows", C.c_int), ("rank_lds_bytes", C.c_int), ("max_replicates", C.c_int)]
 
 
-MC_MAX_PASSES, MC_MAX_WIDTH = 256, 64           # the K and W one mmda_mc_reduce launch takes
+class KnnPlan(C.Structure):
+    """mmda_knn_plan: the launches mmda_knn_sets gives a shape, and the work buffer it is to be handed"""
+    _fields_ = [("tile_q", C.c_int), ("tile_b", C.c_int), ("slab_rows", C.c_int), ("slabs", C.c_int), ("merge", C.c_int),
+                ("launches", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("threads", C.c_int), ("lds_bytes", C.c_int),
+                ("vector_loads", C.c_int), ("max_slabs", C.c_int), ("work_bytes", C.c_int64)]
+
+
+KNN_MAX_D, KNN_MAX_SETS, KNN_MAX_K, TRUST_MAX_CLASSES = 1024, 16, 16, 8      # the limits of csrc/knn.hip
+MC_MAX_PASSES, MC_MAX_WIDTH = 256, 64          # the K and W one mmda_mc_reduce launch takes
 
 
 CELL = {"lstm": 0, "gru": 1}
@@ -416,6 +424,9 @@ SIGNATURES = {
     "mmda_boot_figures": (_I, [_P, _I, _I, _P, _P]),
     "mmda_boot_rank": (_I, [_P, _P, _P, _P, _I64, _I, _I, _U64, C.c_double, _P, _P]),
     "mmda_boot_summary": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _I, _P, _P]),
+    "mmda_knn_plan_describe": (_I, [_I64, _I64, _I, _I, _I, C.POINTER(KnnPlan)]),
+    "mmda_knn_sets": (_I, [_P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P, _P, _I64, _P]),
+    "mmda_trust_score": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -132,6 +132,12 @@ DEFAULTS = dict(
     # with the best checkpoint (mmda_amd/bootstrap.py) and prints every figure of the cut-off and ranking reports as
     # `figure  point  [lo, hi]`, with calibrated cut-offs also their paired difference to `threshold`; 0: nothing happens
     bootstrap=0,
+    # after the final test pass of Solver.train(), next to `mc_passes`' table: N > 0 (1 .. 16) fits the Trust Score on the hidden
+    # vectors of the training split with the best checkpoint (mmda_amd/neighbours.py), N the neighbour count of its
+    # density filter and `trust_alpha` in [0, 1) the share of each label's rows the filter drops, and prints how it ranks the right
+    # decisions of the test split above the wrong ones beside maximum class probability and ConfidNet's tcp; 0: nothing happens
+    trust_k=0,
+    trust_alpha=0.0,
 )
 
 

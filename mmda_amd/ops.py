@@ -1050,3 +1050,56 @@ def modality_attrib(V):
     counts = torch.empty(3, nc, dtype=torch.int64, device=V.device)
     check(lib.mmda_modality_attrib(ptr(V), n, nc, ptr(phi), ptr(loo), ptr(dominant), ptr(counts), stream_ptr()), "modality_attrib")
     return phi, loo, dominant, counts
+
+
+KNN_PLAN_FIELDS = ("tile_q", "tile_b", "slab_rows", "slabs", "merge", "launches", "grid_x", "grid_y", "threads", "lds_bytes",
+                   "vector_loads", "max_slabs", "work_bytes")
+
+
+def knn_plan(Q, N, D, S=1, k=1):
+    """The launches ``mmda_knn_sets`` gives a shape (mmda_knn_plan_describe: host code only, no GPU; the launcher reads the same
+    function), as a dict: ``tile_q`` / ``tile_b`` (query / base rows of a distance tile), ``slab_rows`` and ``slabs`` (how the base is
+    cut across workgroups), ``merge`` (whether the last launch merges more than one slab's lists), ``launches``, ``grid_x`` /
+    ``grid_y`` / ``threads`` / ``lds_bytes`` of the search launch, ``vector_loads``, ``max_slabs`` and ``work_bytes`` (the buffer the
+    caller allocates).  A shape outside the limits raises ``MMDAError``."""
+    p = _lib.KnnPlan()
+    check(load().mmda_knn_plan_describe(int(Q), int(N), int(D), int(S), int(k), C.byref(p)), "mmda_knn_plan_describe")
+    return {f: bool(getattr(p, f)) if f in ("merge", "vector_loads") else int(getattr(p, f)) for f in KNN_PLAN_FIELDS}
+
+
+def knn_sets(query, base, member, S, k, exclude_self=False, work=None):
+    """``mmda_knn_sets`` over device tables: query (Q, D), base (N, D) fp32 contiguous, member (N,) int32 (bit s = row in set s) ->
+    (dist (Q, S, k) fp32, index (Q, S, k) int32).  ``work``: None (allocated here, ``knn_plan``'s ``work_bytes``) or a uint8 device
+    buffer of at least that size."""
+    _f(query), _f(base)
+    assert query.is_contiguous() and base.is_contiguous() and query.dim() == 2 and base.dim() == 2 and query.shape[1] == base.shape[1]
+    assert member.is_cuda and member.dtype == torch.int32 and member.is_contiguous() and member.numel() == base.shape[0]
+    Q, D, N = int(query.shape[0]), int(query.shape[1]), int(base.shape[0])
+    plan = knn_plan(Q, N, D, S, k)
+    if work is None:
+        work = torch.empty(plan["work_bytes"], dtype=torch.uint8, device=query.device)
+    dist = torch.empty(Q, int(S), int(k), dtype=torch.float32, device=query.device)
+    index = torch.empty(Q, int(S), int(k), dtype=torch.int32, device=query.device)
+    check(load().mmda_knn_sets(ptr(query) or ptr(base), ptr(base), ptr(member), Q, N, D, int(S), int(k), int(bool(exclude_self)),
+                               ptr(dist) or ptr(base), ptr(index) or ptr(base), ptr(work), int(work.numel()), stream_ptr()),
+          "mmda_knn_sets")
+    return dist, index
+
+
+def trust_score(dist, labels, index=None, tables=False):
+    """``mmda_trust_score``: dist (n, 2 C, k) fp32 and the decisions labels (n, C) fp32 -> trust (n, C) float64; ``tables=True``
+    (needs ``index`` (n, 2 C, k) int32): ``(trust, d_pred, d_other, nearest_pred, nearest_other)``."""
+    _f(dist), _f(labels)
+    n, C = int(labels.shape[0]), int(labels.shape[1])
+    assert dist.is_contiguous() and labels.is_contiguous() and dist.dim() == 3 and dist.shape[0] == n and dist.shape[1] == 2 * C
+    k = int(dist.shape[2])
+    dev = dist.device
+    trust = torch.empty(n, C, dtype=torch.float64, device=dev)
+    extra = [None] * 4
+    if tables:
+        assert index is not None and index.dtype == torch.int32 and index.is_contiguous() and index.shape == dist.shape
+        extra = [torch.empty(n, C, dtype=dt, device=dev) for dt in (torch.float32, torch.float32, torch.int32, torch.int32)]
+    if n:
+        check(load().mmda_trust_score(ptr(dist), ptr(index), ptr(labels), n, C, k, ptr(trust), *[ptr(t) for t in extra], stream_ptr()),
+              "mmda_trust_score")
+    return (trust, *extra) if tables else trust

@@ -67,6 +67,10 @@ class Solver(object):
         step_rules.scaling_check(getattr(cfg, "task", "emotion"), getattr(cfg, "scaling", "none"))
         if int(getattr(cfg, "bootstrap", 0) or 0) != 0:        # (0, the default: nothing is looked at)
             step_rules.bootstrap_check(task=getattr(cfg, "task", "emotion"), replicates=int(cfg.bootstrap))
+        if int(getattr(cfg, "trust_k", 0) or 0) != 0:          # (0, the default: nothing is looked at)
+            from .neighbours import check_trust_settings
+            check_trust_settings(int(cfg.trust_k), float(getattr(cfg, "trust_alpha", 0.0) or 0.0), cfg.num_classes,
+                                 getattr(cfg, "task", "emotion"))
         if self.model is None:
             self.model = getattr(models, cfg.model)(cfg)
         for name, param in self.model.named_parameters():
@@ -298,7 +302,11 @@ class Solver(object):
             if best_epoch >= 0:
                 self._load_best_checkpoint()
             self.uncertainty("test", passes=int(cfg.mc_passes), to_print=True)
-        if int(getattr(cfg, "bootstrap", 0) or 0) > 0:     # (0, the default: nothing below runs)
+        if int(getattr(cfg, "trust_k", 0) or 0) > 0:       # (0, the default: nothing below runs)
+            if best_epoch >= 0:
+                self._load_best_checkpoint()
+            self.trust("test", k=int(cfg.trust_k), alpha=float(getattr(cfg, "trust_alpha", 0.0) or 0.0), to_print=True)
+        if int(getattr(cfg, "bootstrap", 0) or 0) > 0:    # (0, the default: nothing below runs)
             if best_epoch >= 0:
                 self._load_best_checkpoint()
             self.bootstrap("test", replicates=int(cfg.bootstrap), thresholds=thresholds, scaling=scaling, to_print=True)
@@ -679,6 +687,73 @@ class Solver(object):
                 for k, r in table.items():
                     print(f"{k:<12} {r['auroc']:8.4f} {r['aupr_success']:10.4f} {r['aupr_error']:9.4f} {r['fpr_at_95tpr']:10.4f}")
         return res
+
+    # ------------------------------------------------------------------ Trust Score (mmda_amd/neighbours.py)
+    def _sample_tables(self, mode, fields, who):
+        """(``InferenceResult`` with ``fields``, truth (n, C) on the device) of the ``mode`` split ("train", "dev" or "test"), row i of
+        both the same sample.  A ``DeviceLoader``'s dataset is walked as it is (``InferencePass.run``: row i = sample i, whatever the
+        loader shuffles or masks); a loader with a ``dataset`` of the reference's samples has it uploaded once
+        (``DeviceDataset.from_samples``) and walked the same way; a plain list of the reference's tuples, or a stand-in whose
+        ``dataset`` is itself, is walked by ``InferencePass.run_loader`` and once more for the tuples' emotion labels, so it must yield
+        the same batches twice.  A loader over the encoder cache is refused by name."""
+        from .data import DeviceDataset, DeviceLoader
+        from .inference import InferencePass
+        loader = self._split(mode, SPLITS)
+        if isinstance(loader, EncodedLoader):
+            raise ValueError(f"{who}({mode!r}) reads the hidden vectors of the split's samples: the {mode} loader must not be an "
+                             f"EncodedLoader (the encoder cache holds utterance rows, not samples)")
+        p = InferencePass(self.model, fields)
+        ds = loader.dataset if isinstance(loader, DeviceLoader) else None
+        src = getattr(loader, "dataset", None)
+        if ds is None and src is not None and src is not loader and hasattr(src, "__len__") and hasattr(src, "__getitem__"):
+            ds = DeviceDataset.from_samples([src[i] for i in range(len(src))], next(self.model.parameters()).device)
+        if ds is not None:
+            return p.run(ds, getattr(loader, "batch_size", None) or self.train_config.batch_size), ds.emo
+        res = p.run_loader(loader)
+        truth = [torch.as_tensor(batch[4]) for batch in loader]
+        if not truth:
+            raise ValueError(f"{who}({mode!r}): the {mode} loader yields no batch")
+        return res, torch.cat(truth, 0).to(res._flat.device)
+
+    def trust(self, mode="dev", k=10, alpha=0.0, fit="train", to_print=False, bootstrap=None):
+        """The Trust Score of the ``mode`` split's decisions ("dev" or "test") against the ``fit`` split ("train", "dev" or "test") ->
+        ``TrustResult``, on the device: one ``InferencePass`` over ``fit`` for its hidden vectors, one over ``mode`` (scores, decisions,
+        ``tcp``, hidden vectors), ``TrustIndex.fit(hidden, truth, k, alpha)`` and ``.score``.  The splits are taken the way
+        ``uncertainty`` takes them (a ``DeviceLoader``'s dataset as it is, any other loader's ``dataset`` uploaded once), row i = sample
+        i.  ``self.last_trust``: per kind of confidence -- ``mcp``, ``trust`` and, with ConfidNet, ``tcp`` -- the macro AUROC,
+        AUPR-Success, AUPR-Error and FPR@95TPR of "does it rank the right decisions above the wrong ones", every kind against the same
+        deterministic decisions (this read-back and the cluster check are the call's waits).  ``bootstrap``: None, or a ``Bootstrap``
+        over the split's rows -- ``self.last_trust_bootstrap`` is then ``TrustResult.failure_table(..., bootstrap=bootstrap)``: per
+        kind the resampled figures, their intervals and the paired ``vs_tcp`` difference.  ``to_print``: the table."""
+        from .neighbours import TrustIndex, check_trust_settings
+        cfg = self.train_config
+        self._split(mode, DEV_TEST)
+        self._split(fit, SPLITS)
+        check_trust_settings(k, alpha, cfg.num_classes, getattr(cfg, "task", "emotion"))
+        base, fit_truth = self._sample_tables(fit, ("hidden",), "trust")
+        res, truth = self._sample_tables(mode, ("scores", "labels", "tcp", "hidden"), "trust")
+        self._check_cluster(f"trust({mode})")
+        if fit_truth is None or truth is None or truth.shape != res.labels.shape or fit_truth.shape[0] != base.hidden.shape[0]:
+            raise ValueError(f"trust({mode!r}, fit={fit!r}) needs the emotion labels of both splits")
+        index = TrustIndex.fit(base.hidden, fit_truth.to(base.hidden.device), k=k, alpha=alpha)
+        out = index.score(res.hidden, res.labels)
+        others = {"mcp": torch.maximum(res.scores, 1.0 - res.scores)}
+        if bool(getattr(cfg, "use_confidNet", False)) and res.tcp.shape == res.labels.shape:
+            others["tcp"] = res.tcp
+        table = {}
+        for kind, fp in out.failure_table(truth, others).items():
+            d = fp.as_dict()
+            table[kind] = dict(auroc=d["macro_auroc"], aupr_success=d["macro_aupr_success"], aupr_error=d["macro_aupr_error"],
+                               fpr_at_95tpr=d["macro_fpr_at_95tpr"])
+        self.last_trust = {kind: table[kind] for kind in ("mcp", "trust", "tcp") if kind in table}
+        self.last_trust_bootstrap = None if bootstrap is None else out.failure_table(truth, others, bootstrap=bootstrap)
+        if to_print:
+            print(f"failure prediction on the {mode} split, Trust Score against the {fit} split (k = {int(k)}, alpha = {float(alpha):g}; "
+                  f"macro over classes)")
+            print(f"{'confidence':<12} {'AUROC':>8} {'AUPR-Succ':>10} {'AUPR-Err':>9} {'FPR@95TPR':>10}")
+            for kind, r in self.last_trust.items():
+                print(f"{kind:<12} {r['auroc']:8.4f} {r['aupr_success']:10.4f} {r['aupr_error']:9.4f} {r['fpr_at_95tpr']:10.4f}")
+        return out
 
     # ------------------------------------------------------------------ bootstrap intervals (mmda_amd/bootstrap.py, DESIGN.md 4q)
     def bootstrap(self, mode="test", replicates=2000, seed=0, alpha=0.05, thresholds=None, scaling=None, confidence=True, to_print=False):

@@ -231,6 +231,28 @@ def bootstrap_check(**values) -> None:
         raise MMDAError(dict(BOOTSTRAP_RULES)[hit[0]].format(**hit[1]))
 
 
+# What the Trust Score refuses.  Refused where it is asked for (config.trust_k at Solver.build, Solver.trust,
+# TrustIndex.fit), with nothing run.
+TRUST_RULES = (
+    ("trust_sentiment", "task='sentiment' with the Trust Score (Solver.trust, trust_k={k}) is not built: its sets are the training rows "
+                        "of each label, and the sentiment task's one output column is a regression value"),
+)
+
+
+def trust_verdict(task="emotion", k=10):
+    """(rule, format values) of the first rule of TRUST_RULES that refuses the setting, or None."""
+    if task == "sentiment":
+        return "trust_sentiment", dict(k=k)
+    return None
+
+
+def trust_check(**values) -> None:
+    """Raises MMDAError with the text of the rule that refuses the setting (``trust_verdict``'s arguments)."""
+    hit = trust_verdict(**values)
+    if hit is not None:
+        raise MMDAError(dict(TRUST_RULES)[hit[0]].format(**hit[1]))
+
+
 def verdict(embed_update: str = "dense", optimizer: str | None = None, weight_decay: float = 0.0, clip_norm=None,
             exchange: bool = False, accumulate: bool = False, encoded: bool = False, frozen: bool = False,
             do_adam: bool = True) -> str | None:
